@@ -181,3 +181,31 @@ def test_bench_under_torchrun_and_rank_mismatch():
     # WORLD_SIZE says 2 ranks, --gpus says 4
     p, out = _run_bench(["--gpus", "4", "--dry-run"], {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert p.returncode != 0 and "--gpus 4 but WORLD_SIZE=2" in p.stderr and not out
+
+
+def test_bench_dump_outputs_layout(tmp_path):
+    """bench.py --dump-outputs: a frame within 64 MB is written whole as float32; a larger one as a sample of pixels
+    drawn with a fixed seed (the same pixels every run) with their flat indices; an extra config never dumps (only the
+    headline workload's outputs are written)."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    rng = np.random.default_rng(3)
+    small = rng.random((48, 64, 4), dtype=np.float32)
+    info = bench.dump_outputs(str(tmp_path / "small"), small)
+    got = np.load(str(tmp_path / "small" / "radiance.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, small) and info["files"] == {"radiance.npy": [48, 64, 4]}
+    big = rng.random((2160, 3840, 4), dtype=np.float32)  # 133 MB
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    names = ("radiance_sample.npy", "radiance_sample_index.npy")
+    assert sorted(os.listdir(str(tmp_path / "a"))) == sorted(names)
+    assert sum(os.path.getsize(str(tmp_path / "a" / n)) for n in names) <= 64 << 20
+    val, idx = (np.load(str(tmp_path / "a" / n)) for n in names)
+    assert val.dtype == np.float32 and idx.dtype == np.float64 and len(val) == len(idx) > 1000000
+    assert np.array_equal(val, big.reshape(-1, 4)[idx.astype(np.int64)])
+    for n in names:
+        assert np.array_equal(np.load(str(tmp_path / "a" / n)), np.load(str(tmp_path / "b" / n)))
+    a2 = bench.parse_args(bench._extra_argv(["--steps", "7", "--dump-outputs", "out"], {"config": "c3"}, 5, 2))
+    assert a2.dump_outputs is None and a2.config == "c3" and a2.steps == 5
+    assert bench.parse_args(["--dump-outputs", "out"]).dump_outputs == "out"

@@ -39,6 +39,10 @@ class CameraParams(C.Structure):
     ]
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "steps", "leaves", "shades", "env_lookups")]
 
@@ -102,6 +106,10 @@ SIGNATURES = {
     "fspt_read_radiance": (C.c_int, [_VP, _F]),
     "fspt_draw": (C.c_int, [_VP, C.c_float, C.c_float, C.c_int, C.c_float, C.POINTER(C.c_uint8)]),
     "fspt_draw_scaled": (C.c_int, [_VP, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_uint8)]),
+    "fspt_features": (C.c_int, [_VP, C.POINTER(CameraParams), C.c_uint32, C.c_uint64]),
+    "fspt_read_features": (C.c_int, [_VP, _F]),
+    "fspt_denoise": (C.c_int, [_VP, C.POINTER(DenoiseParams), _F]),
+    "fspt_draw_denoised": (C.c_int, [_VP, C.c_float, C.c_float, C.POINTER(C.c_uint8)]),
     "fspt_intersect": (C.c_int, [_VP, _F, C.c_uint32, _F, C.POINTER(C.c_int32), _U32, _U32]),
     "fspt_intersect_form": (C.c_int, [_VP, C.c_int, _F, C.c_uint32, _F, C.POINTER(C.c_int32), _U32, _U32]),
     "fspt_scene_two_level_nodes": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),

@@ -568,6 +568,7 @@ int fspt_target_destroy(fspt_target *t) {
   t->pending.clear();
   if (t->stream) hipStreamSynchronize(t->stream);
   hipFree(t->accum_own); hipFree(t->ray_pos); hipFree(t->ray_dir); hipFree(t->work_counters); hipFree(t->counters);
+  hipFree(t->feat); hipFree(t->dn_tmp[0]); hipFree(t->dn_tmp[1]); hipFree(t->dn_out);
   {
     fspt_target::WfLane &ln = t->wf;
     for (void *m : ln.mem) hipFree(m);
@@ -890,6 +891,106 @@ int fspt_draw_scaled(fspt_target *t, float exposure, float saturation, int denoi
   if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
   hipFree(d);
   if (e != hipSuccess) { fspt_set_error("fspt_draw: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
+  return FSPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// guided denoiser
+// ---------------------------------------------------------------------------
+// NULL arguments first, then the device: every call fails with FSPT_E_NO_DEVICE where no HIP device is visible
+static int dn_enter(fspt_target *t, bool args_ok, const char *fn) {
+  if (!t || !args_ok) { fspt_set_error("%s: NULL argument", fn); return FSPT_E_INVALID; }
+  if (fspt_device_count() <= 0) { fspt_set_error("%s: no HIP device available; libfspt has no CPU fallback", fn); return FSPT_E_NO_DEVICE; }
+  HIP_TRY(hipSetDevice(t->scene->device));
+  FLUSH_OR_RETURN(t);
+  return FSPT_OK;
+}
+static int dn_alloc(float4 **buf, size_t bytes) {
+  if (!*buf) HIP_TRY(hipMalloc((void **)buf, bytes));
+  return FSPT_OK;
+}
+
+int fspt_features(fspt_target *t, const fspt_camera_params *cam, uint32_t samples, uint64_t seed) {
+  int rc = dn_enter(t, cam != nullptr, "fspt_features");
+  if (rc) return rc;
+  if (samples == 0) { fspt_set_error("fspt_features: samples must be >= 1"); return FSPT_E_INVALID; }
+  const size_t px = (size_t)t->W * t->H;
+  if ((rc = dn_alloc(&t->feat, px * 32))) return rc;
+  fspt::FeatureP p{};
+  p.scene = t->scene->d;
+  p.W = t->W; p.H = t->H;
+  std::memcpy(p.cam.P, cam->P, 12); std::memcpy(p.cam.I, cam->I, 12);
+  p.cam.fov_scale = cam->fov_scale; p.cam.lens[0] = cam->lens[0]; p.cam.lens[1] = cam->lens[1];
+  p.samples = samples;
+  p.seed = seed;
+  p.feat = t->feat;
+  t->feat_valid = false;
+  HIP_TRY(fspt::launch_features(p, t->stream));
+  t->feat_valid = true;
+  return FSPT_OK;
+}
+
+int fspt_read_features(fspt_target *t, float *out) {
+  int rc = dn_enter(t, out != nullptr, "fspt_read_features");
+  if (rc) return rc;
+  if (!t->feat_valid) { fspt_set_error("fspt_read_features: no fspt_features call yet"); return FSPT_E_STATE; }
+  HIP_TRY(hipMemcpyAsync(out, t->feat, (size_t)t->W * t->H * 32, hipMemcpyDeviceToHost, t->stream));
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  return FSPT_OK;
+}
+
+int fspt_denoise(fspt_target *t, const fspt_denoise_params *prm, float *out) {
+  int rc = dn_enter(t, true, "fspt_denoise");
+  if (rc) return rc;
+  fspt_denoise_params q = {FSPT_DENOISE_ITERATIONS, FSPT_DENOISE_SIGMA_COLOR, FSPT_DENOISE_SIGMA_NORMAL, FSPT_DENOISE_SIGMA_DEPTH};
+  if (prm) q = *prm;
+  // sigma_color, sigma_depth: +inf switches the weight off; sigma_normal: 0 switches it off (it is an exponent)
+  if (q.iterations > 16u || !(q.sigma_color >= 0.0f) || !(q.sigma_depth > 0.0f) || !(q.sigma_normal >= 0.0f && q.sigma_normal < INFINITY)) {
+    fspt_set_error("fspt_denoise: need iterations <= 16, sigma_color >= 0, sigma_normal in [0, inf), sigma_depth > 0");
+    return FSPT_E_INVALID;
+  }
+  if (!t->feat_valid) { fspt_set_error("fspt_denoise: no fspt_features call yet"); return FSPT_E_STATE; }
+  const size_t px = (size_t)t->W * t->H;
+  if ((rc = dn_alloc(&t->dn_out, px * 16))) return rc;
+  t->dn_valid = false;
+  if (q.iterations == 0) {
+    HIP_TRY(hipMemcpyAsync(t->dn_out, t->accum, px * 16, hipMemcpyDeviceToDevice, t->stream));
+  } else {
+    if (q.iterations > 1u && ((rc = dn_alloc(&t->dn_tmp[0], px * 16)) || (rc = dn_alloc(&t->dn_tmp[1], px * 16)))) return rc;
+    for (uint32_t k = 0; k < q.iterations; ++k) {
+      fspt::AtrousP p{};
+      p.src = k == 0 ? t->accum : t->dn_tmp[(k - 1) & 1u];
+      p.dst = k + 1 == q.iterations ? t->dn_out : t->dn_tmp[k & 1u];
+      p.feat = t->feat;
+      p.W = t->W; p.H = t->H;
+      p.step = 1 << k;
+      p.demod = k == 0; p.remod = k + 1 == q.iterations;
+      p.sc_step = std::ldexp(q.sigma_color, -(int)k);
+      p.sn = q.sigma_normal;
+      p.sz_step = std::ldexp(q.sigma_depth, (int)k);
+      HIP_TRY(fspt::launch_atrous(p, t->stream));
+    }
+  }
+  t->dn_valid = true;
+  if (out) {
+    HIP_TRY(hipMemcpyAsync(out, t->dn_out, px * 16, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+  }
+  return FSPT_OK;
+}
+
+int fspt_draw_denoised(fspt_target *t, float exposure, float saturation, uint8_t *out_rgba8) {
+  int rc = dn_enter(t, out_rgba8 != nullptr, "fspt_draw_denoised");
+  if (rc) return rc;
+  if (!t->dn_valid) { fspt_set_error("fspt_draw_denoised: no fspt_denoise call yet"); return FSPT_E_STATE; }
+  size_t n = (size_t)t->W * t->H;
+  uint32_t *d = nullptr;
+  HIP_TRY(hipMalloc((void **)&d, n * 4));
+  hipError_t e = fspt::launch_draw(t->dn_out, t->W, t->H, exposure, saturation, 0, 0.0f, 1.0f, d, t->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_rgba8, d, n * 4, hipMemcpyDeviceToHost, t->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  hipFree(d);
+  if (e != hipSuccess) { fspt_set_error("fspt_draw_denoised: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
   return FSPT_OK;
 }
 

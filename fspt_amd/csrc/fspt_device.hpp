@@ -294,6 +294,29 @@ struct TilePackP {
 };
 hipError_t launch_tile_pack(const TilePackP &p, bool unpack, hipStream_t stream);
 
+// guided denoiser (fspt_denoise.*)
+struct FeatureP {
+  DScene scene;
+  uint32_t W, H;
+  CameraP cam;
+  uint32_t samples;
+  uint64_t seed;  // the camera rays' randBase values: fspt_rand_base_next's stream from this state
+  float4 *feat;   // 2 x float4 per pixel: (albedo.rgb, depth), (normal.xyz, coverage)
+};
+struct AtrousP {
+  const float4 *src; // u^k, or (demod) the accumulator
+  float4 *dst;
+  const float4 *feat;
+  uint32_t W, H;
+  int step;          // 2^k
+  int demod, remod;  // first iteration: u0 = c / max(a, 1e-3); last: out = a * u^K
+  float sc_step;     // sigma_c * 2^-k (INFINITY: w_c = 1)
+  float sn;          // sigma_n (0: w_n = 1)
+  float sz_step;     // sigma_z * 2^k (INFINITY: w_z = 1)
+};
+hipError_t launch_features(const FeatureP &p, hipStream_t stream);
+hipError_t launch_atrous(const AtrousP &p, hipStream_t stream);
+
 // launchers (fspt_kernels.hip)
 hipError_t launch_trace(const TraceP &p, bool gen_rays, bool count, int num_cus, hipStream_t stream);
 size_t wf_max_stack_entries(); // deepest tree (entries per lane) whose traversal stacks fit the LDS of every kernel

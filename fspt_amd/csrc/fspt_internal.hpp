@@ -187,6 +187,11 @@ struct fspt_target {
   uint32_t ev_used = 0;       // pairs used by the last render
   bool ev_overflow = false;
   bool stage_events = true;   // fspt_target_set_stage_timing: a HIP event pair around every launch (fspt_last_stage_ms)
+  // guided denoiser (fspt_features / fspt_denoise / fspt_draw_denoised): allocated on first use
+  float4 *feat = nullptr;                 // 2 x float4 per pixel (fspt_read_features)
+  float4 *dn_tmp[2] = {nullptr, nullptr}; // a-trous ping-pong
+  float4 *dn_out = nullptr;               // the last denoised frame
+  bool feat_valid = false, dn_valid = false;
 };
 
 static const uint32_t WORK_RING = 4096;

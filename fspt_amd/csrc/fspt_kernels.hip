@@ -2345,6 +2345,178 @@ __global__ void k_math(int op, const float *a, const float *b, uint32_t n, float
 }
 
 // ---------------------------------------------------------------------------
+// Guided denoiser: the guide buffers of the first hit and the edge-avoiding a-trous filter.
+// ---------------------------------------------------------------------------
+// What shade_hit computes at hit (tHit, slot ti) of ray (ro, rd) before the `inside` flip: texDiffuse and macroNormal
+// (tracer.fs:447-470), with the same helpers and the same arithmetic; only the diffuse and normal layers are fetched.
+FM_DEV void first_hit_guides(const DScene &S, V3 ro, V3 rd, float tHit, int ti, V3 &albedo, V3 &normal) {
+  const float4 *hp = S.hitrec + (size_t)ti * HITREC_F4;
+  const float4 h0 = hp[0], h1 = hp[1], h2 = hp[2], h3 = hp[3], h4 = hp[4], h5 = hp[5], h6 = hp[6], h7 = hp[7], h8 = hp[8],
+               h9 = hp[9], h10 = hp[10];
+  V3 v1 = v3(h0.x, h0.y, h0.z), e1 = v3(h0.w, h1.x, h1.y), e2 = v3(h1.z, h1.w, h2.x);
+  V3 n1 = v3(h2.y, h2.z, h2.w), t1 = v3(h3.x, h3.y, h3.z), b1 = v3(h3.w, h4.x, h4.y);
+  V3 n2 = v3(h4.z, h4.w, h5.x), t2 = v3(h5.y, h5.z, h5.w), b2 = v3(h6.x, h6.y, h6.z);
+  V3 n3 = v3(h6.w, h7.x, h7.y), t3 = v3(h7.z, h7.w, h8.x), b3 = v3(h8.y, h8.z, h8.w);
+  V3 origin = vfma(rd, tHit, ro);
+  V3 w;
+  {
+    V3 vv2 = origin - v1;
+    float d00 = dot(e1, e1), d01 = dot(e1, e2), d11 = dot(e2, e2);
+    float d20 = dot(vv2, e1), d21 = dot(vv2, e2);
+    float invDenom = 1.0f / fma_(d00, d11, -(d01 * d01));
+    float bv = fma_(d11, d20, -(d01 * d21)) * invDenom;
+    float bw = fma_(d00, d21, -(d01 * d20)) * invDenom;
+    w = v3((1.0f - bv) - bw, bv, bw);
+  }
+  float tcx = fma_(w.z, h10.x, fma_(w.y, h9.z, w.x * h9.x));
+  float tcy = fma_(w.z, h10.y, fma_(w.y, h9.w, w.x * h9.y));
+  V3 texNormal;
+  const uint4 *tset = S.tex_sets + (size_t)__float_as_uint(h10.z) * 3;
+  const uint4 ts0 = tset[0], ts1 = tset[1];
+  if (ts0.x == TEXSET_CONST) {
+    uint32_t q = ts1.x;
+    albedo = v3(unorm8(q & 255u), unorm8((q >> 8) & 255u), unorm8((q >> 16) & 255u));
+    q = ts1.w;
+    texNormal = v3((unorm8(q & 255u) - 0.5f) * 2.0f, (unorm8((q >> 8) & 255u) - 0.5f) * 2.0f,
+                   (unorm8((q >> 16) & 255u) - 0.0f) * 1.0f);
+  } else {
+    const TexCoord tc = bilinear_coord((int)S.atlas_res, (int)S.atlas_res, tcx, tcy, true);
+    Tap4 qd, qn;
+    if (ts0.x == TEXSET_QUAD) {
+      const uint4 *img = S.atlas4 + (size_t)ts0.y * 8u;
+      const int tiles_x = ((int)S.atlas_res + 3) >> 2;
+      const uint4 t00 = img[tile_offset<2, 1>(tc.i0, tc.j0, tiles_x)], t10 = img[tile_offset<2, 1>(tc.i1, tc.j0, tiles_x)];
+      const uint4 t01 = img[tile_offset<2, 1>(tc.i0, tc.j1, tiles_x)], t11 = img[tile_offset<2, 1>(tc.i1, tc.j1, tiles_x)];
+      qd = Tap4{t00.x, t10.x, t01.x, t11.x, tc.a, tc.b};
+      qn = Tap4{t00.w, t10.w, t01.w, t11.w, tc.a, tc.b};
+    } else {
+      const uint4 ts2 = tset[2];
+      const TapGeom tg = tap_geom(tc, (int)S.atlas_res);
+      qd = layer_taps(S, tg, ts2.x, ts1.x);
+      qn = layer_taps(S, tg, ts2.w, ts1.w);
+    }
+    albedo = v3(tap_channel(qd, 0), tap_channel(qd, 1), tap_channel(qd, 2));
+    texNormal = v3((tap_channel(qn, 0) - 0.5f) * 2.0f, (tap_channel(qn, 1) - 0.5f) * 2.0f,
+                   (tap_channel(qn, 2) - 0.0f) * 1.0f);
+  }
+  V3 baryNormal = bary3(w, n1, n2, n3);
+  V3 baryTangent = bary3(w, t1, t2, t3);
+  V3 baryBitangent = bary3(w, b1, b2, b3);
+  normal = normalize(
+      v3(fma_(texNormal.z, baryNormal.x, fma_(texNormal.y, baryBitangent.x, texNormal.x * baryTangent.x)),
+         fma_(texNormal.z, baryNormal.y, fma_(texNormal.y, baryBitangent.y, texNormal.x * baryTangent.y)),
+         fma_(texNormal.z, baryNormal.z, fma_(texNormal.y, baryBitangent.z, texNormal.x * baryTangent.z))));
+}
+
+// fspt_rand_base_next on the device: the s-th value of the host stream seeded with `seed` (same integer steps, same one
+// rounding in the float multiply: bit-identical)
+FM_DEV float rand_base_step(uint64_t &st) {
+  uint64_t x = st;
+  x ^= x >> 12;
+  x ^= x << 25;
+  x ^= x >> 27;
+  st = x;
+  const uint64_t r = x * 2685821657736338717ULL;
+  return ((float)(r >> 40) * (1.0f / 16777216.0f)) * 10000.0f;
+}
+
+// One thread per pixel of the whole target (16 x 16-pixel blocks: a wave's camera rays start on a 16 x 4 patch), `samples`
+// camera rays each - exactly k_camera's ray for randBase r_s - traced to their closest hit with the wave's LDS stack like
+// k_intersect.  Per pixel: the float32 sums in sample order / samples of (texDiffuse, t) and (macroNormal, hit); a miss
+// counts as albedo (1, 1, 1), normal 0, depth MAX_T, hit 0.
+__global__ __launch_bounds__(BLOCK_THREADS) void k_features(const FeatureP p) {
+  extern __shared__ int lds_stack[];
+  const uint32_t tid = threadIdx.y * blockDim.x + threadIdx.x;
+  const int lane = (int)(tid & (WAVE - 1));
+  const int wave = (int)(tid / WAVE);
+  const DScene &S = p.scene;
+  int *stack = lds_stack + (size_t)wave * S.stack_n * WAVE + lane;
+  const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+  if (x >= p.W || y >= p.H) return;
+  Counters cnt = {0, 0, 0, 0, 0, 0};
+  uint64_t st = p.seed;
+  float ar = 0.0f, ag = 0.0f, ab = 0.0f, z = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f, hits = 0.0f;
+  for (uint32_t s = 0; s < p.samples; ++s) {
+    const float rb = rand_base_step(st);
+    V3 o, d;
+    camera_ray(x, y, p.W, p.H, p.cam, rb, o, d);
+    int hitA, hitB;
+    float tB;
+    trace_rays<false, false>(S, stack, o, false, d, d, hitA, tB, hitB, cnt);
+    V3 a = v3(1.0f, 1.0f, 1.0f), n = v3(0.0f, 0.0f, 0.0f);
+    float h = 0.0f;
+    if (hitB >= 0) {
+      first_hit_guides(S, o, d, tB, hitB, a, n);
+      h = 1.0f;
+    }
+    ar += a.x; ag += a.y; ab += a.z; z += tB;
+    nx += n.x; ny += n.y; nz += n.z; hits += h;
+  }
+  const float fs = (float)p.samples;
+  const size_t i = (size_t)y * p.W + x;
+  p.feat[2 * i] = make_float4(ar / fs, ag / fs, ab / fs, z / fs);
+  p.feat[2 * i + 1] = make_float4(nx / fs, ny / fs, nz / fs, hits / fs);
+}
+
+// One iteration of the edge-avoiding a-trous filter (include/fspt.h): 5 x 5 B3 taps `step` pixels apart,
+// weighted by luminance, normal and depth similarity; 16 x 16-pixel blocks, every tap read through the caches.  The first
+// iteration reads the accumulator and divides the albedo out on the fly (u0 = c / max(a, 1e-3)); the last multiplies
+// it back in.
+FM_DEV float luma(float4 u) { return (0.2126f * u.x + 0.7152f * u.y) + 0.0722f * u.z; }
+FM_DEV float4 atrous_load(const AtrousP &p, size_t q, float4 f0) {
+  float4 u = p.src[q];
+  if (p.demod) u = make_float4(u.x / max_(f0.x, 1e-3f), u.y / max_(f0.y, 1e-3f), u.z / max_(f0.z, 1e-3f), 1.0f);
+  return u;
+}
+__global__ __launch_bounds__(BLOCK_THREADS) void k_atrous(const AtrousP p) {
+  const int x = (int)(blockIdx.x * blockDim.x + threadIdx.x), y = (int)(blockIdx.y * blockDim.y + threadIdx.y);
+  const int W = (int)p.W, H = (int)p.H;
+  if (x >= W || y >= H) return;
+  const float B[5] = {1.0f / 16.0f, 0.25f, 0.375f, 0.25f, 1.0f / 16.0f};
+  const size_t ip = (size_t)y * W + x;
+  const float4 fp0 = p.feat[2 * ip], fp1 = p.feat[2 * ip + 1];
+  const float4 up = atrous_load(p, ip, fp0);
+  const float Lp = luma(up);
+  const float lenp = sqrt_(fma_(fp1.z, fp1.z, fma_(fp1.y, fp1.y, fp1.x * fp1.x)));
+  const bool hp = fp1.w != 0.0f;
+  const float zden = p.sz_step * max_(fp0.w, 1e-3f); // sigma_z * step * max(z_p, 1e-3)
+  float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f;
+  for (int j = -2; j <= 2; ++j) {
+    const int yy = y + j * p.step;
+    if (yy < 0 || yy >= H) continue;
+    for (int i = -2; i <= 2; ++i) {
+      const int xx = x + i * p.step;
+      if (xx < 0 || xx >= W) continue;
+      const size_t iq = (size_t)yy * W + xx;
+      const float4 fq0 = p.feat[2 * iq], fq1 = p.feat[2 * iq + 1];
+      const float4 uq = atrous_load(p, iq, fq0);
+      float w = B[i + 2] * B[j + 2];
+      if (p.sc_step != INFINITY) {
+        const float Lq = luma(uq);
+        w *= exp2f(-(abs_(Lp - Lq) / (p.sc_step * (Lp + Lq) + 1e-4f)) * 1.44269504f);
+      }
+      if (p.sn != 0.0f && (i != 0 || j != 0)) {
+        const bool hq = fq1.w != 0.0f;
+        if (hp || hq) {
+          const float lenq = sqrt_(fma_(fq1.z, fq1.z, fma_(fq1.y, fq1.y, fq1.x * fq1.x)));
+          if (hp != hq || lenp == 0.0f || lenq == 0.0f) w = 0.0f;
+          else {
+            const float c = fma_(fp1.z, fq1.z, fma_(fp1.y, fq1.y, fp1.x * fq1.x)) / (lenp * lenq);
+            w *= c > 0.0f ? exp2f(p.sn * log2f(c)) : 0.0f;
+          }
+        }
+      }
+      if (p.sz_step != INFINITY) w *= exp2f(-(abs_(fp0.w - fq0.w) / zden) * 1.44269504f);
+      sr = fma_(w, uq.x, sr); sg = fma_(w, uq.y, sg); sb = fma_(w, uq.z, sb);
+      sw += w;
+    }
+  }
+  float4 o = make_float4(sr / sw, sg / sw, sb / sw, 1.0f);
+  if (p.remod) o = make_float4(fp0.x * o.x, fp0.y * o.y, fp0.z * o.z, 1.0f);
+  p.dst[ip] = o;
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
 // Stacks deeper than the default 64 KB of dynamic LDS (trees deeper than ~31 levels under a 512-thread block) need the
@@ -2542,6 +2714,19 @@ hipError_t launch_intersect(const IntersectP &p, hipStream_t stream) {
 hipError_t launch_math(int op, const float *a, const float *b, uint32_t n, float *out, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_math, dim3((n + 255) / 256), dim3(256), 0, stream, op, a, b, n, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_features(const FeatureP &p, hipStream_t stream) {
+  const size_t lds = stack_bytes(p.scene);
+  hipError_t e = allow_lds(k_features, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_features, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), lds, stream, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_atrous(const AtrousP &p, hipStream_t stream) {
+  hipLaunchKernelGGL(k_atrous, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), 0, stream, p);
   return hipGetLastError();
 }
 

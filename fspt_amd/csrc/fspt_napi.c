@@ -656,6 +656,49 @@ static napi_value Draw(napi_env env, napi_callback_info info) {
   FSPT_OK_OR_THROW(fspt_draw_scaled((fspt_target *)h, (float)ex, (float)sat, den ? 1 : 0, (float)sig, (float)scale, (uint8_t *)p));
   return a[5];
 }
+/* guided denoiser (include/fspt.h fspt_features / fspt_denoise / fspt_draw_denoised) */
+static napi_value Features(napi_env env, napi_callback_info info) {
+  /* features(target, params (as render), samples, seed) */
+  napi_value a[4]; void *h; uint32_t n; uint64_t seed64 = 0;
+  if (get_args(env, info, 4, a)) return NULL;
+  fspt_camera_params cp;
+  if (parse_camera_params(env, a[1], &cp)) return NULL;
+  if (unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[2], &n));
+  if (parse_seed(env, a[3], &seed64)) return NULL;
+  FSPT_OK_OR_THROW(fspt_features((fspt_target *)h, &cp, n, seed64));
+  return undefined(env);
+}
+static napi_value Denoise(napi_env env, napi_callback_info info) {
+  /* denoise(target, {iterations, sigmaColor, sigmaNormal, sigmaDepth} | null = defaults, Float32Array(W*H*4) | null) */
+  napi_value a[3]; void *h, *p = NULL; size_t n = 0; napi_valuetype vt;
+  if (get_args(env, info, 3, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  fspt_denoise_params dp = {FSPT_DENOISE_ITERATIONS, FSPT_DENOISE_SIGMA_COLOR, FSPT_DENOISE_SIGMA_NORMAL, FSPT_DENOISE_SIGMA_DEPTH};
+  NAPI_OK(napi_typeof(env, a[1], &vt));
+  const int given = vt == napi_object;
+  if (given) {
+    double k, c, nn, z;
+    if (prop_f64(env, a[1], "iterations", dp.iterations, &k) || prop_f64(env, a[1], "sigmaColor", dp.sigma_color, &c) ||
+        prop_f64(env, a[1], "sigmaNormal", dp.sigma_normal, &nn) || prop_f64(env, a[1], "sigmaDepth", dp.sigma_depth, &z)) return NULL;
+    if (!(k >= 0.0 && k <= 16.0 && k == (double)(uint32_t)k)) { napi_throw_range_error(env, NULL, "fspt_napi: iterations must be an integer in [0, 16]"); return NULL; }
+    dp.iterations = (uint32_t)k; dp.sigma_color = (float)c; dp.sigma_normal = (float)nn; dp.sigma_depth = (float)z;
+  }
+  NAPI_OK(napi_typeof(env, a[2], &vt));
+  if (vt != napi_null && vt != napi_undefined) {
+    if (typed(env, a[2], napi_float32_array, 0, &p, &n) || check_target_len(env, h, n)) return NULL;
+  }
+  FSPT_OK_OR_THROW(fspt_denoise((fspt_target *)h, given ? &dp : NULL, (float *)p));
+  return p ? a[2] : undefined(env);
+}
+static napi_value DrawDenoised(napi_env env, napi_callback_info info) {
+  /* drawDenoised(target, exposure, saturation, Uint8Array(W*H*4)) */
+  napi_value a[4]; void *h, *p; size_t n; double ex, sat;
+  if (get_args(env, info, 4, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  if (get_f64(env, a[1], &ex) || get_f64(env, a[2], &sat) || typed(env, a[3], napi_uint8_array, 0, &p, &n)) return NULL;
+  if (check_target_len(env, h, n)) return NULL;
+  FSPT_OK_OR_THROW(fspt_draw_denoised((fspt_target *)h, (float)ex, (float)sat, (uint8_t *)p));
+  return a[3];
+}
 static napi_value SetViewport(napi_env env, napi_callback_info info) {
   napi_value a[3]; void *h; uint32_t w, hh;
   if (get_args(env, info, 3, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
@@ -1015,7 +1058,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
       {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
-      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
+      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},
       {"renderAsync", RenderAsync}, {"multiCreate", MultiCreate}, {"multiDestroy", MultiDestroy}, {"multiTarget", MultiTarget},
       {"multiCamera", MultiCamera}, {"multiTrace", MultiTrace}, {"multiRender", MultiRender}, {"multiRenderAsync", MultiRenderAsync},

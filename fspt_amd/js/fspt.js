@@ -363,6 +363,24 @@ class PathTracer {
     return addon.draw(this._target, exposure === undefined ? 1 : exposure, saturation === undefined ? 1 : saturation,
       !!denoise, maxSigma === undefined ? 3 : maxSigma, out, resScale === undefined ? 1 : resScale);   // draw.fs `scale`
   }
+  /** Guided denoiser (include/fspt.h, DESIGN.md 8).  features(): guide buffers of the current view - `samples` camera rays
+   *  per pixel to their first hit; denoise(): the edge-avoiding a-trous filter of the accumulator, {iterations, sigmaColor,
+   *  sigmaNormal, sigmaDepth} (omitted = the library's defaults) -> Float32Array(W*H*4); drawDenoised(): drawQuad of that
+   *  frame (call it in place of drawQuad). */
+  features(samples, seed) {
+    addon.features(this._target, { P: this.eye, I: this.dir, fovScale: this.fovScale, lens: this.lensFeatures,
+      envTheta: this.envTheta, numBounces: this.numBounces }, samples === undefined ? 8 : samples, seed === undefined ? 1 : seed);
+  }
+  denoise(opts, out) {
+    out = out || new Float32Array(this.resolution[0] * this.resolution[1] * 4);
+    if (out.length !== this.resolution[0] * this.resolution[1] * 4) throw new RangeError('denoise: need W*H*4 floats');
+    return addon.denoise(this._target, opts || null, out);
+  }
+  drawDenoised(exposure, saturation, out) {
+    out = out || new Uint8Array(this.resolution[0] * this.resolution[1] * 4);
+    if (out.length !== this.resolution[0] * this.resolution[1] * 4) throw new RangeError('drawDenoised: need W*H*4 bytes');
+    return addon.drawDenoised(this._target, exposure === undefined ? 1 : exposure, saturation === undefined ? 1 : saturation, out);
+  }
   /** gl.viewport(0, 0, w, h) of drawCamera / drawTracer (main.js:744,761); the reference: resolution * resScale. */
   setViewport(w, h) { addon.setViewport(this._target, w || 0, h || 0); }
   setShard(shard, nShards, tile) { addon.setShard(this._target, shard, nShards, tile || 32); }

@@ -4,8 +4,10 @@ reference's format (scene/<name>.json with props / static_props / animated_props
     python -m fspt_amd.render --out bunny.png --width 960 --height 540 --spp 256 --bounces 8
     python -m fspt_amd.render --scene web/scene/bunny.json --out bunny.png
     python -m fspt_amd.render --scene 'web/scene/anim_{frame}.json' --frames 0:24 --out 'out/{frame}.png'
+    python -m fspt_amd.render --out bunny.png --spp 16 --atrous 5 --feature-samples 8   # guided denoiser
 
-Path tracing runs in the HIP kernels (fspt_render), tone mapping in the draw.fs kernel (fspt_draw).
+Path tracing runs in the HIP kernels (fspt_render), tone mapping in the draw.fs kernel (fspt_draw); --atrous K runs
+the guided a-trous denoiser (fspt_features + fspt_denoise, K iterations) before tone mapping (fspt_draw_denoised).
 """
 import argparse
 import time
@@ -25,13 +27,17 @@ def main():
     ap.add_argument("--mesh-n", type=int, default=76)
     ap.add_argument("--exposure", type=float, default=1.0)
     ap.add_argument("--saturation", type=float, default=1.0)
-    ap.add_argument("--denoise", action="store_true")
+    ap.add_argument("--denoise", action="store_true", help="draw.fs's 5x5 firefly clamp")
+    ap.add_argument("--atrous", type=int, default=0, help="guided a-trous denoiser iterations (0 = off; built-in scene)")
+    ap.add_argument("--feature-samples", type=int, default=8, help="camera rays per pixel of the denoiser's guide buffers")
     ap.add_argument("--hdr", default=None, help="also save the RGBA32F radiance buffer as .npy")
     ap.add_argument("--scene", default=None, help="scene JSON ({frame} is replaced per frame with --frames)")
     ap.add_argument("--assets", default=None, help="web root the JSON's paths are relative to (default: parent of the scene folder)")
     ap.add_argument("--frames", default=None, help="A:B = frames A..B-1 (the reference's ?frame=N loop, main.js:851-866)")
     ap.add_argument("--seed", type=int, default=1)
     args = ap.parse_args()
+    if args.atrous and args.scene:
+        ap.error("--atrous is available for the built-in scene")
     if args.scene:
         from . import scene_file as F
         spp = args.spp if "--spp" in " ".join(__import__("sys").argv) else None  # default: the scene's `samples`
@@ -58,7 +64,12 @@ def main():
     pt.render(args.spp)
     pt.sync()
     dt = time.perf_counter() - t0
-    rgba = pt.draw(args.exposure, args.saturation, args.denoise)
+    if args.atrous > 0:
+        pt.features(args.feature_samples, args.seed)
+        pt.denoise(iterations=args.atrous)
+        rgba = pt.drawDenoised(args.exposure, args.saturation)
+    else:
+        rgba = pt.draw(args.exposure, args.saturation, args.denoise)
     print(f"{args.width}x{args.height} x {args.spp} spp in {dt:.3f} s = {args.width * args.height * args.spp / dt / 1e6:.0f} Msamples/s")
     if args.hdr:
         np.save(args.hdr, pt.readRadiance())

@@ -31,6 +31,8 @@ def device_memory(device=0):
 
 
 PIPELINES = {"megakernel": 0, "wavefront": 1, "stream": 2}  # fspt_target_set_pipeline codes
+# fspt_denoise's defaults (include/fspt.h FSPT_DENOISE_*; tests/test_denoise_cpu.py pins the two)
+DENOISE_DEFAULTS = {"iterations": 4, "sigma_color": 4.0, "sigma_normal": 32.0, "sigma_depth": 0.05}
 
 
 class Scene:
@@ -288,6 +290,42 @@ class PathTracer:
         out = np.zeros((H, W, 4), np.uint8)
         L.check(L.lib().fspt_draw_scaled(self._t, float(exposure), float(saturation), 1 if denoise else 0,
                                          float(max_sigma), float(scale), L.u8ptr(out)))
+        return out
+
+    # ---- guided denoiser (include/fspt.h fspt_features / fspt_denoise) --------------------------------
+    def features(self, samples=8, seed=1):
+        """Guide buffers of the set_camera() view: `samples` camera rays per pixel to their first hit (fspt_features)."""
+        cp = L.CameraParams()
+        cp.P = (C.c_float * 3)(*self.eye); cp.I = (C.c_float * 3)(*self.dir)
+        cp.fov_scale = self.fovScale; cp.lens = (C.c_float * 2)(*self.lensFeatures)
+        cp.env_theta = self.envTheta; cp.num_bounces = self.num_bounces
+        L.check(L.lib().fspt_features(self._t, C.byref(cp), int(samples), int(seed)))
+
+    def readFeatures(self):
+        """float32 [H, W, 8], row 0 = bottom: albedo.rgb, depth, normal.xyz, coverage (sample means)."""
+        W, H = self.resolution
+        out = np.zeros((H, W, 8), np.float32)
+        L.check(L.lib().fspt_read_features(self._t, L.fptr(out)))
+        return out
+
+    def denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None):
+        """Edge-avoiding a-trous filter of the current accumulator guided by the last features() -> float32 [H, W, 4].
+        None = the library's default (DENOISE_DEFAULTS = include/fspt.h FSPT_DENOISE_*)."""
+        W, H = self.resolution
+        out = np.zeros((H, W, 4), np.float32)
+        given = {"iterations": iterations, "sigma_color": sigma_color, "sigma_normal": sigma_normal, "sigma_depth": sigma_depth}
+        prm = None
+        if any(v is not None for v in given.values()):
+            v = {k: DENOISE_DEFAULTS[k] if x is None else x for k, x in given.items()}
+            prm = L.DenoiseParams(int(v["iterations"]), float(v["sigma_color"]), float(v["sigma_normal"]), float(v["sigma_depth"]))
+        L.check(L.lib().fspt_denoise(self._t, C.byref(prm) if prm is not None else None, L.fptr(out)))
+        return out
+
+    def drawDenoised(self, exposure=1.0, saturation=1.0):
+        """draw() of the last denoise() result (fspt_draw_denoised): tonemapped RGBA8 [H, W, 4], row 0 = bottom."""
+        W, H = self.resolution
+        out = np.zeros((H, W, 4), np.uint8)
+        L.check(L.lib().fspt_draw_denoised(self._t, float(exposure), float(saturation), L.u8ptr(out)))
         return out
 
     def counters(self):

@@ -174,6 +174,26 @@ int fspt_draw(fspt_target *target, float exposure, float saturation, int denoise
 int fspt_draw_scaled(fspt_target *target, float exposure, float saturation, int denoise,
                      float max_sigma, float scale, uint8_t *out_rgba8);
 
+/* Guided denoiser (DESIGN.md 8; the reference lists "denoising" under post processing).  fspt_features: `samples` camera
+ * rays per pixel of the whole target (k_camera's ray for randBase r_s, the s-th fspt_rand_base_next value from `seed`) to
+ * their first hit; per pixel the float32 means of (texDiffuse, t) and (macroNormal before the `inside` flip, hit), a miss
+ * counting as (1,1,1), 1e5, (0,0,0), 0.  fspt_denoise: K edge-avoiding a-trous iterations on the current accumulator c
+ * with the features a, n, z, h:  u = c / max(a, 1e-3);  u'(p) = sum_q w u(q) / sum_q w over q = p + 2^k (i, j), i, j in
+ * -2..2 inside the image;  w = B[i] B[j] wc wn wz, B = (1,4,6,4,1)/16;  wc = exp(-|L(u_p) - L(u_q)| / (sc 2^-k (L(u_p) +
+ * L(u_q)) + 1e-4)), L = Rec.709 luma;  wn = 1 if sn = 0, q = p or h_p = h_q = 0, else 0 if one h or one |n| is 0, else
+ * max(0, n_p.n_q / |n_p||n_q|)^sn;  wz = exp(-|z_p - z_q| / (sz 2^k max(z_p, 1e-3)));  out = (a u_K, 1) (K = 0: c).
+ * sc = sz = +inf switch wc, wz off.  fspt_draw_denoised = fspt_draw of the last denoised frame (denoise 0, scale 1). */
+typedef struct fspt_denoise_params { uint32_t iterations; float sigma_color, sigma_normal, sigma_depth; } fspt_denoise_params;
+#define FSPT_DENOISE_ITERATIONS 4    /* defaults (params NULL): the best of a 78-setting scan on the MI355X (DESIGN 8.1) */
+#define FSPT_DENOISE_SIGMA_COLOR 4.0f
+#define FSPT_DENOISE_SIGMA_NORMAL 32.0f
+#define FSPT_DENOISE_SIGMA_DEPTH 0.05f
+int fspt_features(fspt_target *t, const fspt_camera_params *cam, uint32_t samples, uint64_t seed); /* samples >= 1 */
+int fspt_read_features(fspt_target *t, float *out);              /* W*H*8 floats, rows bottom-up; blocking */
+int fspt_denoise(fspt_target *t, const fspt_denoise_params *p,    /* NULL = defaults; iterations <= 16 */
+                 float *out);                                      /* W*H*4 floats, or NULL: keep on the device */
+int fspt_draw_denoised(fspt_target *t, float exposure, float saturation, uint8_t *out_rgba8);
+
 /* intersectScene (tracer.fs:366-404) as a stand-alone entry: n rays (origin xyz, dir xyz) -> closest hit t and
  * triangle index (-1 = miss, t = 1e5), optionally loop-iteration and leaf-visit counts per ray.  Host pointers. */
 int fspt_intersect(fspt_scene *scene, const float *rays, uint32_t n, float *t_out,

@@ -106,6 +106,7 @@ SIGNATURES = {
     "fspt_read_radiance": (C.c_int, [_VP, _F]),
     "fspt_draw": (C.c_int, [_VP, C.c_float, C.c_float, C.c_int, C.c_float, C.POINTER(C.c_uint8)]),
     "fspt_draw_scaled": (C.c_int, [_VP, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_uint8)]),
+    "fspt_present": (C.c_int, [_VP, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]),
     "fspt_features": (C.c_int, [_VP, C.POINTER(CameraParams), C.c_uint32, C.c_uint64]),
     "fspt_read_features": (C.c_int, [_VP, _F]),
     "fspt_denoise": (C.c_int, [_VP, C.POINTER(DenoiseParams), _F]),

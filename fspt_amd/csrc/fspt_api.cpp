@@ -566,7 +566,23 @@ int fspt_target_destroy(fspt_target *t) {
   // (fspt_target_bind_accumulator) may already have been freed by its owner - destroy never writes to it.  A caller
   // that wants the recorded ticks in its buffer calls fspt_sync (or re-binds, which flushes) first.
   t->pending.clear();
+  if (t->pr_lane.stream) hipStreamSynchronize(t->pr_lane.stream); // (fspt_present's second lane; its work comes first)
   if (t->stream) hipStreamSynchronize(t->stream);
+  {
+    fspt_target::WfLane &ln = t->pr_lane;
+    if (ln.stream) wf_release_all(ln);
+    hipFree(ln.counts); hipFree(ln.heads);
+    if (ln.counts_host) hipHostFree(ln.counts_host);
+    if (ln.live_host) hipHostFree(ln.live_host);
+    if (ln.counts_ready) hipEventDestroy(ln.counts_ready);
+    if (ln.stream) hipStreamDestroy(ln.stream);
+    for (int k = 0; k < 2; ++k) {
+      hipFree(t->pr_dev[k]);
+      if (t->pr_host[k]) hipHostFree(t->pr_host[k]);
+      if (t->pr_copied[k]) hipEventDestroy(t->pr_copied[k]);
+    }
+    for (hipEvent_t ev : {t->pr_acc, t->pr_hop}) if (ev) hipEventDestroy(ev);
+  }
   hipFree(t->accum_own); hipFree(t->ray_pos); hipFree(t->ray_dir); hipFree(t->work_counters); hipFree(t->counters);
   hipFree(t->feat); hipFree(t->dn_tmp[0]); hipFree(t->dn_tmp[1]); hipFree(t->dn_out);
   {
@@ -698,6 +714,7 @@ static int render_ticks(fspt_target *t, const fspt_camera_params *cam, uint32_t 
     if (rc) return rc;
     HIP_TRY(hipEventRecord(t->ev1, t->stream));
     t->timed = true; t->last_launches = n_ticks;
+    t->acc_ticks = first_tick + n_ticks;
     return FSPT_OK;
   }
   fspt::TraceP p{};
@@ -722,6 +739,7 @@ static int render_ticks(fspt_target *t, const fspt_camera_params *cam, uint32_t 
   }
   HIP_TRY(hipEventRecord(t->ev1, t->stream));
   t->timed = true; t->last_launches = n_ticks;
+  t->acc_ticks = first_tick + n_ticks;
   return FSPT_OK;
 }
 
@@ -731,6 +749,7 @@ static int render_ticks(fspt_target *t, const fspt_camera_params *cam, uint32_t 
 // changes state the ticks depend on.
 static bool same_view(const fspt_camera_params &a, const fspt_camera_params &b) { return std::memcmp(&a, &b, sizeof(a)) == 0; }
 int flush_pending(fspt_target *t) {
+  { int rc_j = present_join(t); if (rc_j) return rc_j; }
   if (t->pending.empty()) return FSPT_OK;
   std::vector<fspt_target::Deferred> q;
   q.swap(t->pending); // (a failing batch drops the rest: the error is reported once)
@@ -760,23 +779,12 @@ int materialise_rays(fspt_target *t) {
   return FSPT_OK;
 }
 
+static int present_flush(fspt_target *t); // (fspt_present: the recorded ticks without a join)
+
 extern "C" {
 
-int fspt_trace(fspt_target *t, uint32_t tick, float rand_base, float env_theta, uint32_t num_bounces) {
-  if (!t) { fspt_set_error("fspt_trace: NULL target"); return FSPT_E_INVALID; }
-  if (!t->rays_valid) { fspt_set_error("fspt_trace: call fspt_camera or fspt_set_rays first"); return FSPT_E_STATE; }
-  HIP_TRY(hipSetDevice(t->scene->device));
-  num_bounces = clamp_bounces(num_bounces);
-  if (!t->rays_injected) {
-    // rays come from fspt_camera: record the tick; it runs with its neighbours in one batch at the next flush point
-    fspt_target::Deferred d;
-    d.cam = t->last_cam; d.cam.env_theta = env_theta; d.cam.num_bounces = num_bounces;
-    d.rb_cam = t->last_rb_cam; d.tick = tick; d.rb_trace = rand_base;
-    t->pending.push_back(d);
-    if (!t->defer || t->pending.size() >= (size_t)t->batch_ticks) return flush_pending(t);
-    return FSPT_OK;
-  }
-  FLUSH_OR_RETURN(t);
+// a tick traced from the ray buffers (fspt_set_rays), on the target's stream
+static int trace_from_buffers(fspt_target *t, uint32_t tick, float rand_base, float env_theta, uint32_t num_bounces) {
   if (t->pipeline == 1) {
     fspt_camera_params cp{};
     cp.env_theta = env_theta; cp.num_bounces = num_bounces;
@@ -795,6 +803,7 @@ int fspt_trace(fspt_target *t, uint32_t tick, float rand_base, float env_theta, 
     if (rc) return rc;
     HIP_TRY(hipEventRecord(t->ev1, t->stream));
     t->timed = true; t->last_launches = 1;
+    t->acc_ticks = tick + 1;
     return FSPT_OK;
   }
   t->ev_used = 0;
@@ -807,7 +816,37 @@ int fspt_trace(fspt_target *t, uint32_t tick, float rand_base, float env_theta, 
   HIP_TRY(fspt::launch_trace(p, false, t->count != 0, t->scene->num_cus, t->stream));
   HIP_TRY(hipEventRecord(t->ev1, t->stream));
   t->timed = true; t->last_launches = 1;
+  t->acc_ticks = tick + 1;
   return FSPT_OK;
+}
+
+int fspt_trace(fspt_target *t, uint32_t tick, float rand_base, float env_theta, uint32_t num_bounces) {
+  if (!t) { fspt_set_error("fspt_trace: NULL target"); return FSPT_E_INVALID; }
+  if (!t->rays_valid) { fspt_set_error("fspt_trace: call fspt_camera or fspt_set_rays first"); return FSPT_E_STATE; }
+  HIP_TRY(hipSetDevice(t->scene->device));
+  num_bounces = clamp_bounces(num_bounces);
+  if (!t->rays_injected) {
+    // rays come from fspt_camera: record the tick; it runs with its neighbours in one batch at the next flush point
+    fspt_target::Deferred d;
+    d.cam = t->last_cam; d.cam.env_theta = env_theta; d.cam.num_bounces = num_bounces;
+    d.rb_cam = t->last_rb_cam; d.tick = tick; d.rb_trace = rand_base;
+    t->pending.push_back(d);
+    // (running recorded ticks is not a join: under present they go the present way, and the frame in flight stays)
+    if (!t->defer || t->pending.size() >= (size_t)t->batch_ticks) return t->pr_active ? present_flush(t) : flush_pending(t);
+    return FSPT_OK;
+  }
+  if (t->pr_active) {
+    // a tick is not a join: the recorded ticks go the present way, this one behind the last accumulator access
+    int rc = present_flush(t);
+    if (rc) return rc;
+    if (t->pr_acc_stream && t->pr_acc_stream != t->stream) HIP_TRY(hipStreamWaitEvent(t->stream, t->pr_acc, 0));
+    if ((rc = trace_from_buffers(t, tick, rand_base, env_theta, num_bounces))) return rc;
+    HIP_TRY(hipEventRecord(t->pr_acc, t->stream));
+    t->pr_acc_stream = t->stream;
+    return FSPT_OK;
+  }
+  FLUSH_OR_RETURN(t);
+  return trace_from_buffers(t, tick, rand_base, env_theta, num_bounces);
 }
 
 int fspt_trace_test(fspt_target *t, uint32_t tick) {
@@ -825,6 +864,7 @@ int fspt_trace_test(fspt_target *t, uint32_t tick) {
   HIP_TRY(fspt::launch_bvh_test(p, t->stream));
   HIP_TRY(hipEventRecord(t->ev1, t->stream));
   t->timed = true; t->last_launches = 1;
+  t->acc_ticks = tick + 1;
   return FSPT_OK;
 }
 
@@ -853,6 +893,7 @@ int fspt_clear(fspt_target *t) {
   HIP_TRY(hipSetDevice(t->scene->device));
   FLUSH_OR_RETURN(t);
   HIP_TRY(hipMemsetAsync(t->accum, 0, (size_t)t->W * t->H * 16, t->stream));
+  t->acc_ticks = 0;
   return FSPT_OK;
 }
 
@@ -891,6 +932,113 @@ int fspt_draw_scaled(fspt_target *t, float exposure, float saturation, int denoi
   if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
   hipFree(d);
   if (e != hipSuccess) { fspt_set_error("fspt_draw: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
+  return FSPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// pipelined present
+// ---------------------------------------------------------------------------
+} // extern "C"
+
+// Every entry but fspt_camera / fspt_trace (recording) and fspt_present joins the pipeline through flush_pending: it
+// waits for everything a present enqueued, so that its behaviour is what it was without present.
+int present_join(fspt_target *t) {
+  t->pr_dirty = true; // the caller may enqueue work on the target's stream: lane 1 waits for it at the next present
+  if (!t->pr_active) return FSPT_OK;
+  t->pr_active = false; t->pr_slot = -1; t->pr_acc_stream = nullptr;
+  HIP_TRY(hipSetDevice(t->scene->device));
+  if (t->pr_lane.stream) HIP_TRY(hipStreamSynchronize(t->pr_lane.stream));
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  return FSPT_OK;
+}
+
+static int present_alloc(fspt_target *t) {
+  if (t->pr_acc) return FSPT_OK;
+  const size_t bytes = (size_t)t->W * t->H * 4;
+  for (int k = 0; k < 2; ++k) {
+    HIP_TRY(hipMalloc((void **)&t->pr_dev[k], bytes));
+    HIP_TRY(hipHostMalloc((void **)&t->pr_host[k], bytes, hipHostMallocDefault));
+    HIP_TRY(hipEventCreateWithFlags(&t->pr_copied[k], hipEventDisableTiming));
+  }
+  HIP_TRY(hipEventCreateWithFlags(&t->pr_hop, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&t->pr_acc, hipEventDisableTiming)); // (last: it marks the set as complete)
+  return FSPT_OK;
+}
+
+// One run of recorded ticks under present.  The batch scheduler alternates lanes; every other form runs on the target's
+// stream behind the last accumulator access, in order.  Either way pr_acc / pr_acc_stream end behind the run's last write.
+static int present_run(fspt_target *t, const fspt_camera_params *cam, uint32_t first_tick, uint32_t n_ticks,
+                       const float *rbc, const float *rbt) {
+  if (t->pipeline == 1 && t->sched == 0 && !t->stream_fallback) {
+    uint32_t lane = t->pr_next;
+    int rc = render_wavefront_present(t, lane, cam, first_tick, n_ticks, rbc, rbt);
+    if (rc == FSPT_E_NOMEM && lane == 1) { lane = 0; rc = render_wavefront_present(t, 0, cam, first_tick, n_ticks, rbc, rbt); }
+    if (rc != FSPT_E_NOMEM) {
+      if (rc) return rc;
+      t->pr_next = lane ^ 1u;
+      t->acc_ticks = first_tick + n_ticks;
+      return FSPT_OK;
+    }
+    // not even lane 0 fits the batch scheduler's floor: render_ticks moves the target to the stream scheduler
+  }
+  if (t->pr_acc_stream && t->pr_acc_stream != t->stream) HIP_TRY(hipStreamWaitEvent(t->stream, t->pr_acc, 0));
+  int rc = render_ticks(t, cam, first_tick, n_ticks, rbc, rbt);
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(t->pr_acc, t->stream));
+  t->pr_acc_stream = t->stream;
+  return FSPT_OK;
+}
+
+// The recorded ticks, in runs of one view as flush_pending forms them, the present way (no join).
+static int present_flush(fspt_target *t) {
+  std::vector<fspt_target::Deferred> q;
+  q.swap(t->pending); // (a failing run drops the rest: the error is reported once)
+  std::vector<float> rbc, rbt;
+  size_t i = 0;
+  while (i < q.size()) {
+    size_t j = i + 1;
+    while (j < q.size() && same_view(q[j].cam, q[i].cam) && q[j].tick == q[j - 1].tick + 1) ++j;
+    rbc.clear(); rbt.clear();
+    for (size_t k = i; k < j; ++k) { rbc.push_back(q[k].rb_cam); rbt.push_back(q[k].rb_trace); }
+    int rc = present_run(t, &q[i].cam, q[i].tick, (uint32_t)(j - i), rbc.data(), rbt.data());
+    if (rc) return rc;
+    i = j;
+  }
+  return FSPT_OK;
+}
+
+extern "C" {
+
+int fspt_present(fspt_target *t, float exposure, float saturation, int denoise, float max_sigma, float scale,
+                 uint8_t *out_rgba8, uint32_t *ticks_out) {
+  if (!t || !out_rgba8 || !ticks_out) { fspt_set_error("fspt_present: NULL argument"); return FSPT_E_INVALID; }
+  if (fspt_device_count() <= 0) { fspt_set_error("fspt_present: no HIP device available; libfspt has no CPU fallback"); return FSPT_E_NO_DEVICE; }
+  if (!(scale > 0.0f && scale <= 1.0f)) { fspt_set_error("fspt_present: scale must be in (0, 1]"); return FSPT_E_INVALID; }
+  HIP_TRY(hipSetDevice(t->scene->device));
+  int rc = present_alloc(t);
+  if (rc) return rc;
+  t->pr_active = true;
+  t->ev_used = 0; t->ev_overflow = false; // fspt_last_stage_ms: the batches this present enqueues
+  if ((rc = present_flush(t))) return rc;
+  hipStream_t ds = t->pr_acc_stream ? t->pr_acc_stream : t->stream; // (the stream of the last accumulator write)
+  // this frame: k_draw behind the last accumulator write (same stream), into a device buffer of its slot, then a copy to
+  // pinned memory
+  const size_t n = (size_t)t->W * t->H;
+  const int slot = t->pr_slot < 0 ? 0 : t->pr_slot ^ 1;
+  HIP_TRY(fspt::launch_draw(t->accum, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, t->pr_dev[slot], ds));
+  HIP_TRY(hipEventRecord(t->pr_acc, ds)); // the next resolve writes the accumulator only after this draw has read it
+  t->pr_acc_stream = ds;
+  HIP_TRY(hipMemcpyAsync(t->pr_host[slot], t->pr_dev[slot], n * 4, hipMemcpyDeviceToHost, ds));
+  HIP_TRY(hipEventRecord(t->pr_copied[slot], ds));
+  t->pr_ticks[slot] = t->acc_ticks;
+  // the previous present's frame
+  const int prev = t->pr_slot;
+  t->pr_slot = slot;
+  *ticks_out = 0;
+  if (prev >= 0) {
+    HIP_TRY(hipEventSynchronize(t->pr_copied[prev]));
+    if (t->pr_ticks[prev]) { std::memcpy(out_rgba8, t->pr_host[prev], n * 4); *ticks_out = t->pr_ticks[prev]; }
+  }
   return FSPT_OK;
 }
 
@@ -1118,6 +1266,7 @@ int fspt_target_set_memory_limit(fspt_target *t, uint64_t bytes) {
   if (!t) { fspt_set_error("fspt_target_set_memory_limit: NULL target"); return FSPT_E_INVALID; }
   FLUSH_OR_RETURN(t);
   if (t->stream_fallback) { HIP_TRY(hipSetDevice(t->scene->device)); wf_release(t->wf); t->stream_fallback = false; } // what fits is decided afresh
+  if (t->pr_lane.bytes || t->pr_lane.susp_bytes) { HIP_TRY(hipSetDevice(t->scene->device)); wf_release_all(t->pr_lane); } // (fspt_present's second lane: made again if it fits)
   t->mem_limit = bytes;
   return FSPT_OK;
 }
@@ -1125,7 +1274,7 @@ int fspt_target_set_memory_limit(fspt_target *t, uint64_t bytes) {
 int fspt_target_path_state_bytes(fspt_target *t, uint64_t *bytes, uint32_t *batch_ticks) {
   if (!t || !bytes) { fspt_set_error("fspt_target_path_state_bytes: NULL argument"); return FSPT_E_INVALID; }
   uint64_t b = 0;
-  b = t->wf.bytes + t->wf.susp_bytes;
+  b = t->wf.bytes + t->wf.susp_bytes + t->pr_lane.bytes + t->pr_lane.susp_bytes; // (fspt_present's second lane: 0 until present makes it)
   *bytes = b;
   if (batch_ticks) *batch_ticks = t->batch_ticks;
   return FSPT_OK;

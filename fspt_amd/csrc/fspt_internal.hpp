@@ -192,9 +192,27 @@ struct fspt_target {
   float4 *dn_tmp[2] = {nullptr, nullptr}; // a-trous ping-pong
   float4 *dn_out = nullptr;               // the last denoised frame
   bool feat_valid = false, dn_valid = false;
+  // fspt_present: a swap chain with one frame of latency.  Under present the batch scheduler alternates
+  // batches between two lanes: lane 0 = wf on the target's stream, lane 1 = pr_lane on a stream of its own, sized for
+  // the present batches it runs (not for ticks_seen).  Every other entry joins first (present_join).
+  WfLane pr_lane;
+  uint32_t pr_next = 0;              // lane of the next present batch
+  hipEvent_t pr_acc = nullptr;       // recorded behind the last present launch that read or wrote the accumulator ...
+  hipStream_t pr_acc_stream = nullptr; // ... on this stream (nullptr: no such launch since the last join)
+  hipEvent_t pr_hop = nullptr;       // lane 1 waits for the target's stream behind this event ...
+  bool pr_dirty = true;              // ... when something may have been enqueued there since the last present
+  bool pr_active = false;            // present work may be in flight on the lane streams
+  uint32_t *pr_dev[2] = {nullptr, nullptr}; // k_draw's frames (device) and their copies (pinned host), by slot
+  uint8_t *pr_host[2] = {nullptr, nullptr};
+  hipEvent_t pr_copied[2] = {nullptr, nullptr};
+  uint32_t pr_ticks[2] = {0, 0};     // the frame's sample count (1 + its newest tick index; 0: no tick yet)
+  int pr_slot = -1;                  // slot of the frame the last present enqueued (-1: none since the last join)
+  uint32_t acc_ticks = 0;            // 1 + the index of the most recent tick traced into the accumulator (0: none since
+                                     // create / fspt_clear; fspt_target_bind_accumulator does not reset it)
 };
 
 static const uint32_t WORK_RING = 4096;
+static const uint32_t PR_LANE_TICKS = 4; // fspt_present's second lane: runs of at most this many ticks (longer ones: lane 0)
 static const uint32_t WF_ROUNDS_MAX = fspt::MAX_PATH_ITERS + 4;
 static const uint32_t EV_PAIRS = 4096;
 static const size_t WF_HEADS_BYTES = (size_t)(WF_ROUNDS_MAX + 2) * fspt::WF_HEADS * fspt::WF_HEAD_STRIDE * sizeof(uint32_t);
@@ -215,7 +233,9 @@ struct StPlan {
 
 // ---- fspt_api.cpp
 int check_device(int device);
-int flush_pending(fspt_target *t);     // execute the recorded two-call ticks
+int flush_pending(fspt_target *t);     // execute the recorded two-call ticks (and join a pipelined present first; fspt_trace's
+                                       // own flushes do not join: under present they go through present_flush)
+int present_join(fspt_target *t);      // wait for everything fspt_present enqueued on the lane streams
 int materialise_rays(fspt_target *t);  // the ray buffers as the most recent fspt_camera call left them
 uint32_t clamp_bounces(uint32_t nb);
 // ---- fspt_sched_batch.cpp
@@ -224,6 +244,7 @@ uint64_t susp_need(const fspt_target *t, uint64_t max_paths, uint32_t *stride_ou
 int susp_ensure(fspt_target *t, fspt_target::WfLane &ln, uint64_t max_paths, bool *on);
 size_t wf_slot_bytes();
 void wf_release(fspt_target::WfLane &ln);
+void wf_release_all(fspt_target::WfLane &ln); // ... and its suspension records
 int wf_plan_and_ensure(fspt_target *t, uint64_t work_total, uint32_t n_ticks, uint32_t &batch);
 void prim_collect(fspt_target *t, bool wait);
 void prim_reset(fspt_target *t);
@@ -235,6 +256,10 @@ uint32_t wide_bit(const fspt_target *t, int kind, double paths);
 uint32_t wf_tail_slice(const fspt_target *t); // fspt_sched_batch.cpp: the tail kernel's slice length for this target's scene
 int render_wavefront(fspt_target *t, const fspt_camera_params *cam, uint32_t first_tick, uint32_t n_ticks,
                      const float *rb_cam, const float *rb_trace, bool rays_from_buffers);
+// fspt_present's form: the batches of a run on lane `lane` (0: wf on the target's stream, 1: pr_lane); the resolve waits for
+// pr_acc and records it.  FSPT_E_NOMEM: lane 1 does not fit (nothing launched).
+int render_wavefront_present(fspt_target *t, uint32_t lane, const fspt_camera_params *cam, uint32_t first_tick,
+                             uint32_t n_ticks, const float *rb_cam, const float *rb_trace);
 // ---- fspt_sched_stream.cpp
 int st_ensure(fspt_target *t, fspt_target::WfLane &ln, uint32_t cap, uint32_t fin_slots, uint64_t budget_bytes);
 int st_plan(const fspt_target *t, uint32_t units, uint32_t nbt, uint32_t nb, StPlan &pl);

@@ -656,6 +656,19 @@ static napi_value Draw(napi_env env, napi_callback_info info) {
   FSPT_OK_OR_THROW(fspt_draw_scaled((fspt_target *)h, (float)ex, (float)sat, den ? 1 : 0, (float)sig, (float)scale, (uint8_t *)p));
   return a[5];
 }
+static napi_value Present(napi_env env, napi_callback_info info) {
+  /* present(target, exposure, saturation, denoise, maxSigma, Uint8Array(W*H*4), scale) -> ticks: fspt_present (drawQuad
+   * inside tick(), one frame of latency; 0 = nothing presented, the array untouched) */
+  napi_value a[7], r; void *h, *p; size_t n; double ex, sat, sig, scale; bool den; uint32_t ticks = 0;
+  if (get_args(env, info, 7, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  if (get_f64(env, a[1], &ex) || get_f64(env, a[2], &sat)) return NULL;
+  NAPI_OK(napi_get_value_bool(env, a[3], &den));
+  if (get_f64(env, a[4], &sig) || typed(env, a[5], napi_uint8_array, 0, &p, &n) || get_f64(env, a[6], &scale)) return NULL;
+  if (check_target_len(env, h, n)) return NULL;
+  FSPT_OK_OR_THROW(fspt_present((fspt_target *)h, (float)ex, (float)sat, den ? 1 : 0, (float)sig, (float)scale, (uint8_t *)p, &ticks));
+  NAPI_OK(napi_create_uint32(env, ticks, &r));
+  return r;
+}
 /* guided denoiser (include/fspt.h fspt_features / fspt_denoise / fspt_draw_denoised) */
 static napi_value Features(napi_env env, napi_callback_info info) {
   /* features(target, params (as render), samples, seed) */
@@ -1058,7 +1071,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
       {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
-      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
+      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},
       {"renderAsync", RenderAsync}, {"multiCreate", MultiCreate}, {"multiDestroy", MultiDestroy}, {"multiTarget", MultiTarget},
       {"multiCamera", MultiCamera}, {"multiTrace", MultiTrace}, {"multiRender", MultiRender}, {"multiRenderAsync", MultiRenderAsync},

@@ -37,13 +37,16 @@ int susp_ensure(fspt_target *t, fspt_target::WfLane &ln, uint64_t max_paths, boo
   uint32_t stride; size_t recs;
   const uint64_t need = susp_need(t, max_paths, &stride, &recs);
   *on = true;
+  // the limit covers both lanes of fspt_present (the other one holds nothing unless present ran)
+  const fspt_target::WfLane &other = &ln == &t->wf ? t->pr_lane : t->wf;
+  const uint64_t held = other.bytes + other.susp_bytes;
   if (ln.susp[0] && ln.susp_stride == stride && ln.susp_recs >= recs) {
     // the path state may have grown since the records were made: the limit covers both
-    if (!t->mem_limit || ln.bytes + ln.susp_bytes <= t->mem_limit) return FSPT_OK;
+    if (!t->mem_limit || held + ln.bytes + ln.susp_bytes <= t->mem_limit) return FSPT_OK;
   }
   for (int *&b : ln.susp) { if (b) { HIP_TRY(hipFree(b)); b = nullptr; } }
   ln.susp_bytes = 0; ln.susp_recs = 0;
-  if (t->mem_limit && ln.bytes + need > t->mem_limit) { *on = false; return FSPT_OK; }
+  if (t->mem_limit && held + ln.bytes + need > t->mem_limit) { *on = false; return FSPT_OK; }
   for (int *&b : ln.susp) {
     hipError_t e = hipMalloc((void **)&b, recs * stride * sizeof(int));
     if (e == hipErrorOutOfMemory) {
@@ -75,6 +78,14 @@ void wf_release(fspt_target::WfLane &ln) {
   ln.st_cap = ln.st_fin = 0;
   ln.bytes = 0;
   ln.zeroed = false;
+}
+
+// wf_release and the suspension records: everything of the lane's path state.  Safe with the lane's work in flight:
+// wf_release synchronises the lane's own stream (for fspt_present's second lane: the stream all its work is on) first.
+void wf_release_all(fspt_target::WfLane &ln) {
+  wf_release(ln);
+  for (int *&b : ln.susp) { if (b) { hipFree(b); b = nullptr; } }
+  ln.susp_bytes = 0; ln.susp_recs = 0;
 }
 
 // Path state of one lane for `slots` path slots.  `budget_slots` = what fspt_target_set_memory_limit leaves this lane;
@@ -153,6 +164,8 @@ int wf_plan_and_ensure(fspt_target *t, uint64_t work_total, uint32_t n_ticks, ui
       if (rec <= lim / 4) lim -= rec;
       budget = lim / wf_slot_bytes();
     }
+    // fspt_present's second lane gives way when this one has to grow (present makes it again if it still fits)
+    if (t->pr_lane.bytes && t->wf.slots < batch * work_total) wf_release_all(t->pr_lane);
     int rc = wf_ensure(t, t->wf, (uint32_t)(batch * work_total), budget);
     if (rc != FSPT_E_NOMEM) return rc;
     if (batch / 2 < floor_ticks || batch <= 1) { t->batch_ticks = configured; return rc; } // (message set by wf_ensure)
@@ -274,6 +287,29 @@ uint32_t wide_bit(const fspt_target *t, int kind, double paths) {
   return on ? 1u << kind : 0u;
 }
 
+// fspt_present's second lane: path state for the present batches it runs (`slots`), in what the memory limit leaves
+// beside lane 0.  FSPT_E_NOMEM: it does not fit (present then runs its batches on lane 0, in order).
+static int pr_lane_ensure(fspt_target *t, uint64_t slots) {
+  fspt_target::WfLane &ln = t->pr_lane;
+  if (ln.slots >= slots && ln.counts) return FSPT_OK;
+  uint64_t budget = ~0ull;
+  if (t->mem_limit) {
+    const uint64_t used = t->wf.bytes + t->wf.susp_bytes;
+    budget = t->mem_limit > used ? (t->mem_limit - used) / wf_slot_bytes() : 0;
+  }
+  if (slots > budget || slots > 0xFFFFFFFFull) {
+    if (ln.bytes) wf_release_all(ln);
+    fspt_set_error("fspt_present: a second lane of %llu slots does not fit the target's memory limit", (unsigned long long)slots);
+    return FSPT_E_NOMEM;
+  }
+  if (!ln.stream) HIP_TRY(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
+  return wf_ensure(t, ln, (uint32_t)slots, budget);
+}
+
+static int wf_run(fspt_target *t, fspt_target::WfLane &ln, hipStream_t st, bool present, uint32_t batch, uint32_t work_total,
+                  const fspt_camera_params *cam, uint32_t first_tick, uint32_t n_ticks, const float *rb_cam,
+                  const float *rb_trace, bool rays_from_buffers);
+
 // n_ticks ticks through the wavefront pipeline.  rays_from_buffers: two-call form (n_ticks == 1).
 int render_wavefront(fspt_target *t, const fspt_camera_params *cam, uint32_t first_tick, uint32_t n_ticks,
                             const float *rb_cam, const float *rb_trace, bool rays_from_buffers) {
@@ -286,6 +322,61 @@ int render_wavefront(fspt_target *t, const fspt_camera_params *cam, uint32_t fir
   uint32_t batch;
   int rc = wf_plan_and_ensure(t, work_total, n_ticks, batch);
   if (rc) return rc;
+  // The batch scheduler runs on the target's own stream: everything already queued there (clear, ray upload, earlier
+  // renders) comes first by stream order.  (Rounds 1-4 ran it on a stream of its own behind an event of the target's
+  // stream and made the target's stream wait for an event behind the last resolve: two hops between hardware queues per
+  // call - ~0.12 ms of launch latency in front of every 20-tick region, profiles/r05/launch_list_c2.txt.)
+  fspt_target::WfLane &ln = t->wf;
+  hipStream_t st = FSPT_BATCH_ON_TARGET_STREAM ? t->stream : ln.stream;
+  if (!FSPT_BATCH_ON_TARGET_STREAM) {
+    HIP_TRY(hipEventRecord(t->ev_start, t->stream));
+    HIP_TRY(hipStreamWaitEvent(st, t->ev_start, 0));
+  }
+  if ((rc = wf_run(t, ln, st, false, batch, work_total, cam, first_tick, n_ticks, rb_cam, rb_trace, rays_from_buffers))) return rc;
+  if (!FSPT_BATCH_ON_TARGET_STREAM) {
+    HIP_TRY(hipEventRecord(ln.resolved, st));
+    HIP_TRY(hipStreamWaitEvent(t->stream, ln.resolved, 0));
+  }
+  return FSPT_OK;
+}
+
+int render_wavefront_present(fspt_target *t, uint32_t lane, const fspt_camera_params *cam, uint32_t first_tick,
+                             uint32_t n_ticks, const float *rb_cam, const float *rb_trace) {
+  fspt::TraceP tp{};
+  fill_trace_params(t, tp);
+  const uint32_t work_total = tp.n_owned_tiles * tp.tile * tp.tile;
+  if (work_total == 0) return FSPT_OK;
+  uint32_t batch;
+  int rc;
+  if (lane == 0) { // as render_wavefront
+    if ((rc = wf_plan_and_ensure(t, work_total, n_ticks, batch))) return rc;
+    return wf_run(t, t->wf, t->stream, true, batch, work_total, cam, first_tick, n_ticks, rb_cam, rb_trace, false);
+  }
+  // lane 1: runs of up to PR_LANE_TICKS ticks, one batch each (wf_plan's caps, without ticks_seen); a longer run goes
+  // to lane 0, whose path state the batch scheduler sizes anyway - lane 1 never holds more than PR_LANE_TICKS ticks
+  if (n_ticks > PR_LANE_TICKS) return FSPT_E_NOMEM;
+  const uint64_t fit = WF_SLOT_BUDGET / work_total;
+  batch = n_ticks < (uint32_t)fspt::WF_MAX_BATCH ? n_ticks : (uint32_t)fspt::WF_MAX_BATCH;
+  if (batch > fit) batch = fit > 1 ? (uint32_t)fit : 1u;
+  if ((uint64_t)batch * work_total > 0x1FFFFFFFull) return FSPT_E_NOMEM; // (lane 0 reports it)
+  if ((rc = pr_lane_ensure(t, (uint64_t)batch * work_total))) return rc;
+  fspt_target::WfLane &ln = t->pr_lane;
+  if (t->pr_dirty) { // the target's stream got work since the last present (fspt_clear, a fused render, ...): it comes first
+    HIP_TRY(hipEventRecord(t->pr_hop, t->stream));
+    HIP_TRY(hipStreamWaitEvent(ln.stream, t->pr_hop, 0));
+    t->pr_dirty = false;
+  }
+  return wf_run(t, ln, ln.stream, true, batch, work_total, cam, first_tick, n_ticks, rb_cam, rb_trace, false);
+}
+
+// The batches of one run on lane `ln`, enqueued on `st`.  present: fspt_present's form - the resolve waits for the last
+// launch that read or wrote the accumulator on the other lane (pr_acc) and records pr_acc behind itself.
+static int wf_run(fspt_target *t, fspt_target::WfLane &ln, hipStream_t st, bool present, uint32_t batch, uint32_t work_total,
+                  const fspt_camera_params *cam, uint32_t first_tick, uint32_t n_ticks, const float *rb_cam,
+                  const float *rb_trace, bool rays_from_buffers) {
+  fspt::TraceP tp{};
+  fill_trace_params(t, tp);
+  int rc;
 
   fspt::WfP p{};
   p.scene = t->scene->d;
@@ -301,17 +392,6 @@ int render_wavefront(fspt_target *t, const fspt_camera_params *cam, uint32_t fir
   const int cus = t->scene->num_cus;
   const bool gen = !rays_from_buffers;
   const uint32_t nb = cam->num_bounces;
-
-  // The batch scheduler runs on the target's own stream: everything already queued there (clear, ray upload, earlier
-  // renders) comes first by stream order.  (Rounds 1-4 ran it on a stream of its own behind an event of the target's
-  // stream and made the target's stream wait for an event behind the last resolve: two hops between hardware queues per
-  // call - ~0.12 ms of launch latency in front of every 20-tick region, profiles/r05/launch_list_c2.txt.)
-  fspt_target::WfLane &ln = t->wf;
-  hipStream_t st = FSPT_BATCH_ON_TARGET_STREAM ? t->stream : ln.stream;
-  if (!FSPT_BATCH_ON_TARGET_STREAM) {
-    HIP_TRY(hipEventRecord(t->ev_start, t->stream));
-    HIP_TRY(hipStreamWaitEvent(st, t->ev_start, 0));
-  }
 
   uint32_t done = 0;
   while (done < n_ticks) {
@@ -364,7 +444,8 @@ int render_wavefront(fspt_target *t, const fspt_camera_params *cam, uint32_t fir
     p.wide = wide_bit(t, fspt::WF_K_PRIMARY, -1.0) | wide_bit(t, fspt::WF_K_TAIL, -1.0);
     p.tail_adaptive = (t->node_form[2] < 0 ? FSPT_WIDE_TAIL : t->node_form[2]) == 2 ? 1u : 0u;
     p.tail_slice = wf_tail_slice(t);
-    const bool time_primary = t->count == 0 && !t->prim_pending;
+    // (present: not timed - an overlapped launch shares the chip with the other lane's tail; the table's choice is used)
+    const bool time_primary = t->count == 0 && !t->prim_pending && !present;
     bool prev_trace_suspends = false; // (no carry launch behind a trace launch that cannot have suspended anything)
     for (uint32_t r = 1; r <= last && r <= tail; ++r) {
       set_round(r);
@@ -406,8 +487,11 @@ int render_wavefront(fspt_target *t, const fspt_camera_params *cam, uint32_t fir
     p.live_out = resolve_clears ? ln.live_dev : nullptr;
     p.zero_rounds = resolve_clears ? WF_ROUNDS_MAX + 2 : 0u;
     if (!resolve_clears) HIP_TRY(hipMemcpyAsync(ln.counts_host, ln.counts, sizeof(fspt::WfCounts) * (WF_ROUNDS_MAX + 2), hipMemcpyDeviceToHost, st));
-    // the running mean is order-dependent (tracer.fs:517): batches resolve in tick order - they follow each other on `st`
+    // the running mean is order-dependent (tracer.fs:517): batches resolve in tick order - they follow each other on `st`;
+    // under present the previous accumulator access may be on the other lane's stream (its resolve or its frame's k_draw)
+    if (present && t->pr_acc_stream && t->pr_acc_stream != st) HIP_TRY(hipStreamWaitEvent(st, t->pr_acc, 0));
     if ((rc = launch(fspt::WF_K_RESOLVE))) return rc;
+    if (present) { HIP_TRY(hipEventRecord(t->pr_acc, st)); t->pr_acc_stream = st; }
     p.zero_rounds = 0u;
     HIP_TRY(hipEventRecord(ln.counts_ready, st));
     ln.counts_pending = true;
@@ -419,10 +503,6 @@ int render_wavefront(fspt_target *t, const fspt_camera_params *cam, uint32_t fir
     }
     ln.zeroed = true;
     done += nbt;
-  }
-  if (!FSPT_BATCH_ON_TARGET_STREAM) {
-    HIP_TRY(hipEventRecord(ln.resolved, st));
-    HIP_TRY(hipStreamWaitEvent(t->stream, ln.resolved, 0));
   }
   return FSPT_OK;
 }

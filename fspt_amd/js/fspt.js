@@ -363,6 +363,14 @@ class PathTracer {
     return addon.draw(this._target, exposure === undefined ? 1 : exposure, saturation === undefined ? 1 : saturation,
       !!denoise, maxSigma === undefined ? 3 : maxSigma, out, resScale === undefined ? 1 : resScale);   // draw.fs `scale`
   }
+  /** drawQuad inside tick() (main.js:838-857), pipelined with one frame of latency (include/fspt.h fspt_present,
+   *  DESIGN.md 4.3): enqueues the ticks recorded since the last call and their frame, writes the PREVIOUS call's frame
+   *  into `out` and returns its sample count (1 + its newest tick index; 0 = nothing presented yet, `out` untouched). */
+  present(exposure, saturation, denoise, maxSigma, out, resScale) {
+    if (!out || out.length !== this.resolution[0] * this.resolution[1] * 4) throw new RangeError('present: need W*H*4 bytes');
+    return addon.present(this._target, exposure === undefined ? 1 : exposure, saturation === undefined ? 1 : saturation,
+      !!denoise, maxSigma === undefined ? 3 : maxSigma, out, resScale === undefined ? 1 : resScale);
+  }
   /** Guided denoiser (include/fspt.h, DESIGN.md 8).  features(): guide buffers of the current view - `samples` camera rays
    *  per pixel to their first hit; denoise(): the edge-avoiding a-trous filter of the accumulator, {iterations, sigmaColor,
    *  sigmaNormal, sigmaDepth} (omitted = the library's defaults) -> Float32Array(W*H*4); drawDenoised(): drawQuad of that

@@ -292,6 +292,21 @@ class PathTracer:
                                          float(max_sigma), float(scale), L.u8ptr(out)))
         return out
 
+    def present(self, exposure=1.0, saturation=1.0, denoise=False, max_sigma=3.0, scale=1.0, out=None):
+        """drawQuad inside tick() (main.js:838-857), pipelined with one frame of latency (fspt_present): enqueues
+        the ticks recorded since the last call and their frame, and returns (the PREVIOUS call's frame, its sample count =
+        1 + its newest tick index).  (None, 0) when there is nothing to present yet (first call after any other call on
+        this tracer but tick()).  `out`: an optional uint8 [H, W, 4] array the frame is written to."""
+        W, H = self.resolution
+        if out is None:
+            out = np.zeros((H, W, 4), np.uint8)
+        elif out.dtype != np.uint8 or out.size != W * H * 4 or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous uint8 array of W*H*4 elements")
+        ticks = C.c_uint32()
+        L.check(L.lib().fspt_present(self._t, float(exposure), float(saturation), 1 if denoise else 0,
+                                     float(max_sigma), float(scale), L.u8ptr(out), C.byref(ticks)))
+        return (out if ticks.value else None), int(ticks.value)
+
     # ---- guided denoiser (include/fspt.h fspt_features / fspt_denoise, DESIGN 8) --------------------------------
     def features(self, samples=8, seed=1):
         """Guide buffers of the set_camera() view: `samples` camera rays per pixel to their first hit (fspt_features)."""

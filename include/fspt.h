@@ -173,6 +173,13 @@ int fspt_draw(fspt_target *target, float exposure, float saturation, int denoise
  * draws with scale 0.25 while the camera is being dragged (main.js:819,840), 1.0 otherwise. */
 int fspt_draw_scaled(fspt_target *target, float exposure, float saturation, int denoise,
                      float max_sigma, float scale, uint8_t *out_rgba8);
+/* drawQuad inside tick() (main.js:838-857), pipelined with one frame of latency: enqueues the ticks
+ * recorded since the last flush and fspt_draw_scaled's k_draw of the result, then writes the frame the PREVIOUS call
+ * enqueued to out_rgba8 and its sample count (1 + its newest tick index) to *ticks_out, blocking only for that frame.
+ * *ticks_out = 0: nothing to present (first call after a join; out untouched).  Every entry but fspt_camera and
+ * fspt_trace joins. */
+int fspt_present(fspt_target *t, float exposure, float saturation, int denoise, float max_sigma, float scale,
+                 uint8_t *out_rgba8, uint32_t *ticks_out);
 
 /* Guided denoiser (DESIGN.md 8; the reference lists "denoising" under post processing).  fspt_features: `samples` camera
  * rays per pixel of the whole target (k_camera's ray for randBase r_s, the s-th fspt_rand_base_next value from `seed`) to

@@ -90,6 +90,8 @@ SIGNATURES = {
     "fspt_target_create": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(_VP)]),
     "fspt_target_destroy": (C.c_int, [_VP]),
     "fspt_target_set_viewport": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
+    "fspt_target_set_sampler": (C.c_int, [_VP, C.c_int, C.c_uint32]),
+    "fspt_target_get_sampler": (C.c_int, [_VP, C.POINTER(C.c_int), _U32]),
     "fspt_target_set_shard": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
     "fspt_target_bind_accumulator": (C.c_int, [_VP, _VP]),
     "fspt_target_accumulator": (C.c_int, [_VP, C.POINTER(_VP)]),
@@ -120,6 +122,7 @@ SIGNATURES = {
     "fspt_counters_reset": (C.c_int, [_VP]),
     "fspt_get_trace_lds_steps": (C.c_int, [_VP, C.POINTER(C.c_uint64)]),
     "fspt_math_eval": (C.c_int, [C.c_int, C.c_int, _F, _F, C.c_uint32, _F]),
+    "fspt_sampler_eval": (C.c_int, [C.c_int, C.c_uint32, _U32, _U32, _U32, C.c_uint32, _F]),
     "fspt_last_kernel_ms": (C.c_int, [_VP, _F, _U32]),
     "fspt_target_set_pipeline": (C.c_int, [_VP, C.c_int, C.c_uint32]),
     "fspt_target_set_primary_form": (C.c_int, [_VP, C.c_int]),

@@ -774,7 +774,9 @@ int materialise_rays(fspt_target *t) {
   fspt::CameraP c;
   std::memcpy(c.P, t->last_cam.P, 12); std::memcpy(c.I, t->last_cam.I, 12);
   c.fov_scale = t->last_cam.fov_scale; c.lens[0] = t->last_cam.lens[0]; c.lens[1] = t->last_cam.lens[1];
-  HIP_TRY(fspt::launch_camera(t->W, t->H, t->vw, t->vh, c, t->last_rb_cam, t->ray_pos, t->ray_dir, t->stream));
+  // (the Sobol sampler: sample index acc_ticks - the tick that would trace these rays next)
+  HIP_TRY(fspt::launch_camera(t->W, t->H, t->vw, t->vh, c, t->last_rb_cam, t->ray_pos, t->ray_dir, t->stream, (uint32_t)t->sampler,
+                              t->sampler_seed, t->acc_ticks));
   t->cam_recorded = false;
   return FSPT_OK;
 }
@@ -885,6 +887,25 @@ int fspt_target_set_deferred(fspt_target *t, int enable) {
   if (!t) { fspt_set_error("fspt_target_set_deferred: NULL target"); return FSPT_E_INVALID; }
   FLUSH_OR_RETURN(t);
   t->defer = enable != 0;
+  return FSPT_OK;
+}
+
+int fspt_target_set_sampler(fspt_target *t, int sampler, uint32_t seed) {
+  if (!t) { fspt_set_error("fspt_target_set_sampler: NULL target"); return FSPT_E_INVALID; }
+  if (sampler != FSPT_SAMPLER_REFERENCE && sampler != FSPT_SAMPLER_SOBOL) {
+    fspt_set_error("fspt_target_set_sampler: sampler must be FSPT_SAMPLER_REFERENCE (0) or FSPT_SAMPLER_SOBOL (1), got %d", sampler);
+    return FSPT_E_INVALID;
+  }
+  FLUSH_OR_RETURN(t);
+  t->sampler = sampler;
+  t->sampler_seed = seed;
+  return FSPT_OK;
+}
+
+int fspt_target_get_sampler(fspt_target *t, int *sampler, uint32_t *seed) {
+  if (!t) { fspt_set_error("fspt_target_get_sampler: NULL target"); return FSPT_E_INVALID; }
+  if (sampler) *sampler = t->sampler;
+  if (seed) *seed = t->sampler_seed;
   return FSPT_OK;
 }
 
@@ -1405,6 +1426,28 @@ int fspt_intersect_form(fspt_scene *s, int two_level, const float *rays, uint32_
   if (e != hipSuccess) { fspt_set_error("fspt_intersect: %s", hipGetErrorString(e)); rc = FSPT_E_HIP; }
   hipFree(d_rays); hipFree(d_t); hipFree(d_i); hipFree(d_s); hipFree(d_l);
   return rc;
+}
+
+int fspt_sampler_eval(int device, uint32_t seed, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim, uint32_t n,
+                      float *out) {
+  if (!pixel || !sample || !dim || !out) { fspt_set_error("fspt_sampler_eval: NULL argument"); return FSPT_E_INVALID; }
+  int rc = check_device(device);
+  if (rc) return rc;
+  if (n == 0) return FSPT_OK;
+  const size_t bytes = (size_t)n * 4;
+  uint32_t *d_in = nullptr;
+  float *d_out = nullptr;
+  hipError_t e = hipMalloc((void **)&d_in, 3 * bytes);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_out, bytes);
+  if (e == hipSuccess) e = hipMemcpy(d_in, pixel, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_in + n, sample, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_in + 2 * (size_t)n, dim, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = fspt::launch_sampler_eval(seed, d_in, d_in + n, d_in + 2 * (size_t)n, n, d_out, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
+  hipFree(d_in); hipFree(d_out);
+  if (e != hipSuccess) { fspt_set_error("fspt_sampler_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
+  return FSPT_OK;
 }
 
 int fspt_math_eval(int device, int op, const float *a, const float *b, uint32_t n, float *out) {

@@ -122,6 +122,8 @@ struct TraceP {
   // sharding
   uint32_t shard, n_shards, tile;
   uint32_t tiles_x, tiles_y, n_owned_tiles;
+  uint32_t sampler;  // FSPT_SAMPLER_*: which instantiation launch_trace picks
+  uint32_t smp_seed; // FSPT_SAMPLER_SOBOL's seed
 };
 
 struct IntersectP {
@@ -172,6 +174,10 @@ constexpr uint32_t WF_FLAG_SUSP = 1u << 19;
 #define FSPT_WF_LAG_MAX 4
 #endif
 constexpr uint32_t WF_LAG_SHIFT = 20, WF_LAG_MASK = 7u, WF_LAG_MAX = FSPT_WF_LAG_MAX;
+// Sobol sampler only (fspt.h FSPT_SAMPLER_SOBOL): bits 23-31 of the flags hold half the path's sampler dimension count
+// (always even, at most 4 + 8 * MAX_PATH_ITERS = 516: 9 bits)
+constexpr uint32_t WF_DIM_SHIFT = 23;
+static_assert(((4u + 8u * MAX_PATH_ITERS) >> 1) < (1u << (32u - WF_DIM_SHIFT)), "WF_DIM_SHIFT: dimension count does not fit");
 constexpr int WF_SUSP_HEADER = 8; // ints before the stack entries of a record: state index, node, t, hit, sp | ray << 8, shadow result, -, -
 #ifndef FSPT_WF_HEADS
 #define FSPT_WF_HEADS 16
@@ -276,6 +282,8 @@ struct WfP {
   float4 *accum;
   unsigned long long *counters;
   uint32_t shard, n_shards, tile, tiles_x, tiles_y, n_owned_tiles;
+  uint32_t sampler;  // as in TraceP; a slot's sample index is first_tick + slot % n_batch
+  uint32_t smp_seed;
 };
 
 // kernel classes; also the slots of fspt_last_stage_ms
@@ -321,7 +329,10 @@ hipError_t launch_atrous(const AtrousP &p, hipStream_t stream);
 hipError_t launch_trace(const TraceP &p, bool gen_rays, bool count, int num_cus, hipStream_t stream);
 size_t wf_max_stack_entries(); // deepest tree (entries per lane) whose traversal stacks fit the LDS of every kernel
 hipError_t launch_camera(uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const CameraP &cam, float rand_base, float4 *pos, float4 *dir,
-                         hipStream_t stream);
+                         hipStream_t stream, uint32_t sampler = 0, uint32_t smp_seed = 0, uint32_t sample = 0);
+// the Sobol sampler's value for n (pixel, sample, dim) triples (fspt_sampler_eval)
+hipError_t launch_sampler_eval(uint32_t seed, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim, uint32_t n,
+                               float *out, hipStream_t stream);
 hipError_t launch_intersect(const IntersectP &p, hipStream_t stream);
 hipError_t launch_bvh_test(const TraceP &p, hipStream_t stream);
 hipError_t launch_draw(const float4 *acc, uint32_t W, uint32_t H, float exposure, float saturation, int denoise,

@@ -108,6 +108,8 @@ struct fspt_target {
   // wavefront pipeline
   uint32_t vw = 0, vh = 0;    // viewport (gl.viewport of the two draws); default = the whole target
   int pipeline = 1;           // 0 = megakernel, 1 = wavefront
+  int sampler = 0;            // FSPT_SAMPLER_REFERENCE / FSPT_SAMPLER_SOBOL (fspt_target_set_sampler)
+  uint32_t sampler_seed = 0;  // FSPT_SAMPLER_SOBOL's seed
   int sched = 0;              // wavefront pipeline: 0 = batch scheduler (all ticks x all pixels per batch), 1 = stream (fixed pool)
   bool stream_fallback = false; // sched 0, but the path state of FSPT_MIN_BATCH ticks did not fit: calls run on the stream scheduler (cleared by every setter that changes what fits)
   uint32_t pool_paths = 0;    // stream: paths per state set and lane (0 = default)

@@ -471,18 +471,33 @@ FM_DEV V3 env_sample(const DScene &S, V3 dir, float envTheta, Counters &cnt) {
   float sc = exp2_(fma_(e, 255.0f, -128.0f));
   return v3(r * sc, g * sc, b * sc);
 }
+// The random numbers of a path (compile-time choice, fspt.h fspt_target_set_sampler): SMP_REF is the reference's rnd()
+// from its running float seed; SMP_SOBOL the Owen-scrambled Sobol sampler (fspt_math.hpp), whose dimension is the number
+// of values the sample has drawn so far - camera_ray dims 0..3, then shade_hit's calls in order.
+enum { SMP_REF = 0, SMP_SOBOL = 1 };
+template <int SMP>
+struct Rng {
+  float ref;                         // SMP_REF
+  uint32_t seed, pixel, sample, dim; // SMP_SOBOL
+  FM_DEV float next() {
+    if constexpr (SMP == SMP_SOBOL) return sobol_value(seed, pixel, sample, dim++);
+    else return rnd(ref);
+  }
+};
+
 // sampleEnv (tracer.fs:421-434)
-FM_DEV void sample_env(const DScene &S, float envTheta, float &seed, V3 &dir, float &pdf) {
+template <class R>
+FM_DEV void sample_env(const DScene &S, float envTheta, R &rng, V3 &dir, float &pdf) {
   float nb = (float)S.n_bins;
-  int idx = (int)(nb * rnd(seed));
+  int idx = (int)(nb * rng.next());
   if (idx > (int)S.n_bins - 1) idx = (int)S.n_bins - 1;
   if (idx < 0) idx = 0;
   uint4 bn = S.bins[idx];
   float bx = (float)bn.x, by = (float)bn.y, bz = (float)bn.z, bw = (float)bn.w;
   float dx = (float)S.env_w, dy = (float)S.env_h;
   if (!S.env) { dx = 1.0f; dy = 2048.0f; }
-  float r1 = rnd(seed);
-  float r2 = rnd(seed);
+  float r1 = rng.next();
+  float r2 = rng.next();
   float ux = -envTheta + fma_(bz - bx, r1, bx) / dx;
   float uy = 0.0f + fma_(bw - by, r2, by) / dy;
   float theta = ux * M_TAU_F;
@@ -537,8 +552,9 @@ FM_DEV V3 frame_combine(V3 t, V3 b, V3 n, V3 h) {
   return v3(fma_(n.x, h.z, fma_(b.x, h.y, t.x * h.x)), fma_(n.y, h.z, fma_(b.y, h.y, t.y * h.x)),
             fma_(n.z, h.z, fma_(b.z, h.y, t.z * h.x)));
 }
-FM_DEV V3 sample_microfacet(V3 normal, float rough, float &seed) {
-  float r1 = rnd(seed), r2 = rnd(seed);
+template <class R>
+FM_DEV V3 sample_microfacet(V3 normal, float rough, R &rng) {
+  float r1 = rng.next(), r2 = rng.next();
   V3 t, b;
   local_frame(normal, t, b);
   float a = max_(0.001f, rough);
@@ -550,8 +566,9 @@ FM_DEV V3 sample_microfacet(V3 normal, float rough, float &seed) {
   V3 h = v3(sinTheta * cosPhi, sinTheta * sinPhi, cosTheta);
   return frame_combine(t, b, normal, h);
 }
-FM_DEV V3 sample_lambert(V3 normal, float &seed) {
-  float r1 = rnd(seed), r2 = rnd(seed);
+template <class R>
+FM_DEV V3 sample_lambert(V3 normal, R &rng) {
+  float r1 = rng.next(), r2 = rng.next();
   V3 t, b;
   local_frame(normal, t, b);
   float r = sqrt_(r1);
@@ -580,14 +597,15 @@ FM_DEV V3 eval_specular(V3 incident, V3 normal, V3 diffuse, float metallic, floa
 }
 
 // ---------------------------------------------------------------------------
-// camera.fs main (37-46) for pixel (x, y)
+// camera.fs main (37-46) for pixel (x, y); SMP_SOBOL: sample `sample` of the sampler seeded `sseed`, dims 0..3
 // ---------------------------------------------------------------------------
-FM_DEV void camera_ray(uint32_t x, uint32_t y, uint32_t W, uint32_t H, const CameraP &cam, float randBase, V3 &o,
-                       V3 &d) {
+template <int SMP>
+FM_DEV void camera_ray(uint32_t x, uint32_t y, uint32_t W, uint32_t H, const CameraP &cam, float randBase, uint32_t sseed,
+                       uint32_t sample, V3 &o, V3 &d) {
   float fx = (float)x + 0.5f, fy = (float)y + 0.5f;
   float resx = (float)W, resy = (float)H;
   float uvx = fma_(fx / resx, 2.0f, -1.0f), uvy = fma_(fy / resy, 2.0f, -1.0f);
-  float seed = fma_(fx, resy, randBase) + fy;
+  Rng<SMP> rng{fma_(fx, resy, randBase) + fy, sseed, y * W + x, sample, 0u};
   V3 Iv = v3(cam.I[0], cam.I[1], cam.I[2]), Pv = v3(cam.P[0], cam.P[1], cam.P[2]);
   V3 basisX = normalize(cross(Iv, v3(0.0f, 1.0f, 0.0f)));
   V3 basisY = normalize(cross(basisX, Iv));
@@ -597,18 +615,18 @@ FM_DEV void camera_ray(uint32_t x, uint32_t y, uint32_t W, uint32_t H, const Cam
   screen.x = (fma_(icy * basisY.x, fov, (icx * basisX.x) * fov) + Iv.x) + Pv.x;
   screen.y = (fma_(icy * basisY.y, fov, (icx * basisX.y) * fov) + Iv.y) + Pv.y;
   screen.z = (fma_(icy * basisY.z, fov, (icx * basisX.z) * fov) + Iv.z) + Pv.z;
-  float theta = (rnd(seed) * M_PI_F) * 2.0f;
-  float r = sqrt_(rnd(seed)) * 1.414f;
+  float theta = (rng.next() * M_PI_F) * 2.0f;
+  float r = sqrt_(rng.next()) * 1.414f;
   float st, ct;
   sincos_(theta, st, ct);
   V3 aa;
   aa.x = (r * ((basisX.x * ct) / resx + (basisY.x * st) / resy)) * fov;
   aa.y = (r * ((basisX.y * ct) / resx + (basisY.y * st) / resy)) * fov;
   aa.z = (r * ((basisX.z * ct) / resx + (basisY.z * st) / resy)) * fov;
-  float theta2 = (rnd(seed) * M_PI_F) * 2.0f;
+  float theta2 = (rng.next() * M_PI_F) * 2.0f;
   float s2, c2;
   sincos_(theta2, s2, c2);
-  float sq = sqrt_(rnd(seed));
+  float sq = sqrt_(rng.next());
   float lx = cam.lens[0], ly = cam.lens[1];
   V3 dof;
   dof.x = (fma_(s2, basisY.x, c2 * basisX.x) * ly) * sq;
@@ -617,6 +635,9 @@ FM_DEV void camera_ray(uint32_t x, uint32_t y, uint32_t W, uint32_t H, const Cam
   o = Pv + dof;
   V3 tgt = v3(fma_(dof.x, lx, screen.x + aa.x), fma_(dof.y, lx, screen.y + aa.y), fma_(dof.z, lx, screen.z + aa.z));
   d = normalize(tgt - o);
+}
+FM_DEV void camera_ray(uint32_t x, uint32_t y, uint32_t W, uint32_t H, const CameraP &cam, float randBase, V3 &o, V3 &d) {
+  camera_ray<SMP_REF>(x, y, W, H, cam, randBase, 0u, 0u, o, d);
 }
 
 // ---------------------------------------------------------------------------
@@ -634,12 +655,15 @@ struct Path {
   bool hasShadow;
   bool primary;   // pending ray is the camera ray
   uint32_t lag;   // rounds the path has lagged behind its generation because a traversal of it was suspended (<= WF_LAG_MAX)
+  uint32_t dim;   // SMP_SOBOL: sampler dimensions the sample has used (4 after the camera ray; always even, <= 4 + 8 * MAX_PATH_ITERS)
 };
 
 // tracer.fs:447-499: shade the hit (t, tri) of ray (ro, rd); sets up the next
 // shadow + extension rays in `ps`.
-template <bool COUNT>
-FM_DEV void shade_hit(const DScene &S, Path &ps, float tHit, int ti, float randBase, float envTheta, Counters &cnt) {
+// SMP_SOBOL: ps.pix is the full-target pixel, `sample` the tick, `sseed` the sampler seed (randBase is unused)
+template <bool COUNT, int SMP>
+FM_DEV void shade_hit(const DScene &S, Path &ps, float tHit, int ti, float randBase, uint32_t sseed, uint32_t sample,
+                      float envTheta, Counters &cnt) {
   if (COUNT) cnt.shades++;
   const float4 *hp = S.hitrec + (size_t)ti * HITREC_F4; // 192 B = 3 whole cache lines
   const float4 h0 = hp[0], h1 = hp[1], h2 = hp[2], h3 = hp[3], h4 = hp[4], h5 = hp[5], h6 = hp[6], h7 = hp[7], h8 = hp[8],
@@ -718,7 +742,8 @@ FM_DEV void shade_hit(const DScene &S, Path &ps, float tHit, int ti, float randB
                    (tap_channel(qn, 2) - 0.0f) * 1.0f);
   }
   rough = rough * rough;
-  float seed = fma_(origin.z, 4761.52835f, ((origin.x * randBase) * origin.y) * 1.396529836f);
+  Rng<SMP> rng{fma_(origin.z, 4761.52835f, ((origin.x * randBase) * origin.y) * 1.396529836f), sseed, (uint32_t)ps.pix, sample,
+               ps.dim};
   V3 baryNormal = bary3(w, n1, n2, n3);
   V3 baryTangent = bary3(w, t1, t2, t3);
   V3 baryBitangent = bary3(w, b1, b2, b3);
@@ -739,13 +764,13 @@ FM_DEV void shade_hit(const DScene &S, Path &ps, float tHit, int ti, float randB
   V3 incident = -rd;
   V3 envThroughput, bsdfThroughput;
   float bsdfPdf;
-  V3 microNormal = sample_microfacet(macroNormal, rough, seed);
+  V3 microNormal = sample_microfacet(macroNormal, rough, rng);
   V3 envDir;
   float envPdf;
-  sample_env(S, envTheta, seed, envDir, envPdf);
+  sample_env(S, envTheta, rng, envDir, envPdf);
   float cosEnv = dot(macroNormal, envDir);
   float F = schlick(incident, microNormal, nsx, nsy);
-  bool specular = fma_(1.0f, metallic, F * (1.0f - metallic)) > rnd(seed);
+  bool specular = fma_(1.0f, metallic, F * (1.0f - metallic)) > rng.next();
   bool refracted = false;
   // bsdfThroughput = numB * clamp(n . rd) / bsdfPdf and envThroughput = numE * clamp(n . envDir) / envPdf in the reflect
   // and the Lambert branch (tracer.fs:476-480, 490-495): the branches leave the numerators, the six divisions happen once
@@ -773,7 +798,7 @@ FM_DEV void shade_hit(const DScene &S, Path &ps, float tHit, int ti, float randB
     }
     refracted = true; // tracer.fs:488 `i--`
   } else {
-    rd = sample_lambert(macroNormal, seed);
+    rd = sample_lambert(macroNormal, rng);
     bsdfPdf = abs_(dot(rd, macroNormal)) * INV_PI_F;
     numB = numE = v3(texDiffuse.x * INV_PI_F, texDiffuse.y * INV_PI_F, texDiffuse.z * INV_PI_F);
   }
@@ -810,6 +835,7 @@ FM_DEV void shade_hit(const DScene &S, Path &ps, float tHit, int ti, float randB
   if (!refracted) ps.bounce++;
   ps.iters++;
   ps.primary = false;
+  if constexpr (SMP == SMP_SOBOL) ps.dim = rng.dim;
 }
 
 // One S step of a live path (tracer.fs:500-512 + the loop bound of 446): consume the
@@ -839,11 +865,11 @@ FM_DEV bool consume_rays(const DScene &S, Path &ps, int hitA, int hitB, float en
   if (ps.bounce >= (int)numBounces || ps.iters >= MAX_PATH_ITERS) return true; // tracer.fs:446 bound, live hit
   return false;
 }
-template <bool COUNT>
-FM_DEV bool advance_path(const DScene &S, Path &ps, int hitA, float tB, int hitB, float randBase, float envTheta,
-                         uint32_t numBounces, Counters &cnt) {
+template <bool COUNT, int SMP>
+FM_DEV bool advance_path(const DScene &S, Path &ps, int hitA, float tB, int hitB, float randBase, uint32_t sseed,
+                         uint32_t sample, float envTheta, uint32_t numBounces, Counters &cnt) {
   if (consume_rays<COUNT>(S, ps, hitA, hitB, envTheta, numBounces, cnt)) return true;
-  shade_hit<COUNT>(S, ps, tB, hitB, randBase, envTheta, cnt);
+  shade_hit<COUNT, SMP>(S, ps, tB, hitB, randBase, sseed, sample, envTheta, cnt);
   return false;
 }
 
@@ -885,7 +911,7 @@ FM_DEV uint32_t wf_work_index(const WfP &p, uint32_t g) { return g / p.n_batch; 
 // ---------------------------------------------------------------------------
 // The path-trace kernel: tracer.fs main() (436-518) over the whole frame.
 // ---------------------------------------------------------------------------
-template <bool GEN_RAYS, bool COUNT>
+template <bool GEN_RAYS, bool COUNT, int SMP>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_trace(const TraceP p) {
   extern __shared__ int lds_stack[];
   const int lane = threadIdx.x & (WAVE - 1);
@@ -916,7 +942,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_trace(const TraceP p) {
     // ================= S phase =================
     bool need_pixel = (ps.pix < 0);
     if (ps.pix >= 0) {
-      if (advance_path<COUNT>(S, ps, hitA, tB, hitB, p.rand_base, p.env_theta, p.num_bounces, cnt)) {
+      if (advance_path<COUNT, SMP>(S, ps, hitA, tB, hitB, p.rand_base, p.smp_seed, p.tick, p.env_theta, p.num_bounces, cnt)) {
         p.accum[ps.pix] = accumulate_sample(p.accum[ps.pix], ps.color, p.tick);
         ps.pix = -1;
         need_pixel = true;
@@ -946,7 +972,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_trace(const TraceP p) {
           ps.pix = (int)(y * p.W + x);
           if (COUNT) cnt.samples++;
           if (GEN_RAYS) {
-            camera_ray(x, y, p.W, p.H, p.cam, p.rand_base_cam, ps.ro, ps.rd);
+            camera_ray<SMP>(x, y, p.W, p.H, p.cam, p.rand_base_cam, p.smp_seed, p.tick, ps.ro, ps.rd);
           } else {
             float4 po = p.ray_pos[ps.pix], di = p.ray_dir[ps.pix];
             ps.ro = v3(po.x, po.y, po.z);
@@ -956,6 +982,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_trace(const TraceP p) {
           ps.color = v3(0.0f, 0.0f, 0.0f);
           ps.bounce = 0;
           ps.iters = 0;
+          ps.dim = 4u;
           ps.primary = true;
           ps.hasShadow = false;
           need_pixel = false;
@@ -1062,24 +1089,30 @@ FM_DEV uint32_t lane_rank(unsigned long long m) {
 }
 
 // ---- path state <-> registers ---------------------------------------------------------------
+template <int SMP>
 FM_DEV uint32_t pack_flags(const Path &ps, bool col_zero) {
-  return ((uint32_t)ps.bounce & 255u) | (((uint32_t)ps.iters & 255u) << 8) | (ps.primary ? WF_FLAG_PRIMARY : 0u) |
-         (ps.hasShadow ? WF_FLAG_SHADOW : 0u) | (col_zero ? WF_FLAG_COLZERO : 0u) | ((ps.lag & WF_LAG_MASK) << WF_LAG_SHIFT);
+  uint32_t f = ((uint32_t)ps.bounce & 255u) | (((uint32_t)ps.iters & 255u) << 8) | (ps.primary ? WF_FLAG_PRIMARY : 0u) |
+               (ps.hasShadow ? WF_FLAG_SHADOW : 0u) | (col_zero ? WF_FLAG_COLZERO : 0u) | ((ps.lag & WF_LAG_MASK) << WF_LAG_SHIFT);
+  if constexpr (SMP == SMP_SOBOL) f |= (ps.dim >> 1) << WF_DIM_SHIFT;
+  return f;
 }
 // state of a surviving path -> index k of `o`; the colour array is only written while the colour is non-zero
-// (it is +0 until the first light arrives), D / P only when the path has a NEE shadow ray
+// (it is +0 until the first light arrives), D / P only when the path has a NEE shadow ray.  SMP_SOBOL: the colour entry
+// is always written and carries the path's pixel in .w (the stream scheduler's slot ids do not determine it)
+template <int SMP>
 FM_DEV void store_path(const WfSet &o, uint32_t k, const Path &ps, uint32_t slot) {
-  const bool col_zero = ps.color.x == 0.0f && ps.color.y == 0.0f && ps.color.z == 0.0f;
+  const bool col_zero = SMP == SMP_REF && ps.color.x == 0.0f && ps.color.y == 0.0f && ps.color.z == 0.0f;
   st4(o.A + k, make_float4(ps.ro.x, ps.ro.y, ps.ro.z, __uint_as_float(slot)));
-  st4(o.B + k, make_float4(ps.rd.x, ps.rd.y, ps.rd.z, __uint_as_float(pack_flags(ps, col_zero))));
+  st4(o.B + k, make_float4(ps.rd.x, ps.rd.y, ps.rd.z, __uint_as_float(pack_flags<SMP>(ps, col_zero))));
   st4(o.C + k, make_float4(ps.thr.x, ps.thr.y, ps.thr.z, ps.wy));
-  if (!col_zero) st4(o.E + k, make_float4(ps.color.x, ps.color.y, ps.color.z, 0.0f));
+  if (!col_zero) st4(o.E + k, make_float4(ps.color.x, ps.color.y, ps.color.z, SMP == SMP_SOBOL ? __uint_as_float((uint32_t)ps.pix) : 0.0f));
   if (ps.hasShadow) {
     st4(o.D + k, make_float4(ps.envDir.x, ps.envDir.y, ps.envDir.z, ps.wx));
     st4(o.P + k, make_float4(ps.pend.x, ps.pend.y, ps.pend.z, 0.0f));
   }
 }
 // path k of `in` with the traversal results of its rays; returns the slot
+template <int SMP>
 FM_DEV uint32_t load_path(const WfSet &in, uint32_t k, Path &ps, const int *shadow_hit, int &hitA) {
   const float4 ro = ld4(in.A + k), rd = ld4(in.B + k), th = ld4(in.C + k);
   const uint32_t flags = __float_as_uint(rd.w);
@@ -1095,7 +1128,8 @@ FM_DEV uint32_t load_path(const WfSet &in, uint32_t k, Path &ps, const int *shad
   ps.primary = (flags & WF_FLAG_PRIMARY) != 0u;
   ps.hasShadow = (flags & WF_FLAG_SHADOW) != 0u;
   ps.lag = (flags >> WF_LAG_SHIFT) & WF_LAG_MASK;
-  ps.pix = 0;
+  ps.pix = SMP == SMP_SOBOL ? (int)__float_as_uint(co.w) : 0;
+  ps.dim = (flags >> WF_DIM_SHIFT) << 1;
   ps.wx = 0.0f;
   ps.envDir = v3(0.0f, 0.0f, 0.0f);
   ps.pend = v3(0.0f, 0.0f, 0.0f);
@@ -1548,7 +1582,7 @@ FM_DEV void flush_counters(const Counters &cnt, unsigned long long *counters, in
 #ifndef WF_PRIMARY_SLICE
 #define WF_PRIMARY_SLICE 8u // traversal steps between two looks at the wave's sample counter
 #endif
-template <bool COUNT, bool LDSTAB, int R, bool WIDE = false>
+template <bool COUNT, bool LDSTAB, int R, bool WIDE, int SMP>
 __global__ __launch_bounds__(WF_PRIMARY_THREADS, WF_LOGIC_WAVES) void k_wf_primary(const WfP p) {
   extern __shared__ int lds_dyn[]; // the waves' traversal stacks | [tables] | [camera rays and hits of the block iteration]
   constexpr int NW = WF_PRIMARY_THREADS / WAVE;
@@ -1616,7 +1650,7 @@ __global__ __launch_bounds__(WF_PRIMARY_THREADS, WF_LOGIC_WAVES) void k_wf_prima
       valid1 = i < n_in && work_to_pixel(p, wf_work_index(p, g), fx, fy);
       if (valid1) {
         if (p.gen_rays) {
-          camera_ray(fx, fy, p.W, p.H, p.cam, p.rb_cam[g % p.n_batch], o1, d1);
+          camera_ray<SMP>(fx, fy, p.W, p.H, p.cam, p.rb_cam[g % p.n_batch], p.smp_seed, p.first_tick + g % p.n_batch, o1, d1);
         } else {
           float4 po = p.ray_pos[fy * p.W + fx], di = p.ray_dir[fy * p.W + fx];
           o1 = v3(po.x, po.y, po.z);
@@ -1644,7 +1678,7 @@ __global__ __launch_bounds__(WF_PRIMARY_THREADS, WF_LOGIC_WAVES) void k_wf_prima
         int h = -2; // -2: the sample does not exist (outside the viewport / beyond the launch)
         if (i < n_in && work_to_pixel(p, wf_work_index(p, g), fx, fy)) {
           if (p.gen_rays) {
-            camera_ray(fx, fy, p.W, p.H, p.cam, p.rb_cam[g % p.n_batch], o, d);
+            camera_ray<SMP>(fx, fy, p.W, p.H, p.cam, p.rb_cam[g % p.n_batch], p.smp_seed, p.first_tick + g % p.n_batch, o, d);
           } else {
             const float4 po = p.ray_pos[fy * p.W + fx], di = p.ray_dir[fy * p.W + fx];
             o = v3(po.x, po.y, po.z);
@@ -1747,12 +1781,17 @@ __global__ __launch_bounds__(WF_PRIMARY_THREADS, WF_LOGIC_WAVES) void k_wf_prima
         ps.envDir = v3(0.0f, 0.0f, 0.0f);
         ps.pend = v3(0.0f, 0.0f, 0.0f);
         ps.wx = ps.wy = 0.0f;
-        ps.bounce = 0; ps.iters = 0; ps.pix = 0; ps.lag = 0u;
+        ps.bounce = 0; ps.iters = 0; ps.pix = 0; ps.lag = 0u; ps.dim = 4u;
         ps.hasShadow = false; ps.primary = true;
         const uint32_t j = (first + i) % p.n_batch;
-        const bool finished = advance_path<COUNT>(S, ps, -1, tB, hitB, s_rb[j], p.env_theta, p.num_bounces, cnt);
+        if constexpr (SMP == SMP_SOBOL) {
+          uint32_t fx = 0, fy = 0;
+          work_to_pixel(p, wf_work_index(p, first + i), fx, fy);
+          ps.pix = (int)(fy * p.W + fx);
+        }
+        const bool finished = advance_path<COUNT, SMP>(S, ps, -1, tB, hitB, s_rb[j], p.smp_seed, p.first_tick + j, p.env_theta, p.num_bounces, cnt);
         if (finished) st3(p.fin + 3 * (size_t)slot, ps.color);
-        else store_path(out, s_base[par] + my_off + lane_rank(m_surv[u]), ps, slot);
+        else store_path<SMP>(out, s_base[par] + my_off + lane_rank(m_surv[u]), ps, slot);
       }
       my_off += (uint32_t)__popcll(m_surv[u]);
     }
@@ -1769,7 +1808,7 @@ __global__ __launch_bounds__(WF_PRIMARY_THREADS, WF_LOGIC_WAVES) void k_wf_prima
 //   2a every thread finishes its own non-shaded paths (NEE result, environment on a miss -> fin[slot]);
 //   2b the listed paths are shaded by consecutive threads - whole waves of shading work, instead of the 1-in-5 lanes
 //      a round-2 wave has when every thread keeps its own path (VALU lane utilisation 0.34 in round 1's profile).
-template <bool COUNT, bool LDSTAB>
+template <bool COUNT, bool LDSTAB, int SMP>
 __global__ __launch_bounds__(WF_LOGIC_THREADS, WF_LOGIC_WAVES) void k_wf_logic(const WfP p) {
   constexpr int U = WF_LOGIC_U;
   extern __shared__ int lds_dyn[]; // the staged tables
@@ -1861,12 +1900,13 @@ __global__ __launch_bounds__(WF_LOGIC_THREADS, WF_LOGIC_WAVES) void k_wf_logic(c
       if (active) {
         Path ps;
         int hitA;
-        const uint32_t slot = load_path(in, i, ps, p.shadow_hit, hitA);
+        const uint32_t slot = load_path<SMP>(in, i, ps, p.shadow_hit, hitA);
         const float2 h = ld2(p.hit + i);
         const uint32_t j = slot % p.n_batch;
-        const bool finished = advance_path<COUNT>(S, ps, hitA, h.x, __float_as_int(h.y), s_rb[j], p.env_theta, p.num_bounces, cnt);
+        const bool finished = advance_path<COUNT, SMP>(S, ps, hitA, h.x, __float_as_int(h.y), s_rb[j], p.smp_seed, p.first_tick + j,
+                                                       p.env_theta, p.num_bounces, cnt);
         if (finished) st3(p.fin + 3 * (size_t)slot, ps.color);
-        else store_path(out, k_out, ps, slot);
+        else store_path<SMP>(out, k_out, ps, slot);
       }
     }
     __syncthreads(); // s_list / s_total are rewritten by the next iteration
@@ -1915,7 +1955,7 @@ FM_DEV V3 shfl3(V3 v, int src) { return v3(__shfl(v.x, src, WAVE), __shfl(v.y, s
 // dependent chains of the paths still alive, walked by a few lanes on a mostly idle chip - there a step costs a cache-miss
 // latency, and two levels per round trip shorten the chain (profiles/r05/launch_list_*.txt: the tail launch is 0.8 ms of a
 // 9.9 ms batch on the 70 k-triangle scene, 2.4 of 13.3 ms on the 1 M-triangle one, most of it this end phase).
-template <bool COUNT, bool ANYHIT, bool GEN, int WIDE = 0>
+template <bool COUNT, bool ANYHIT, bool GEN, int WIDE, int SMP>
 __global__ __launch_bounds__(BLOCK_THREADS, WF_TAIL_WAVES) void k_wf_tail(const WfP p) {
   extern __shared__ int lds_stack[];
   const int lane = threadIdx.x & (WAVE - 1);
@@ -1984,8 +2024,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, WF_TAIL_WAVES) void k_wf_tail(const 
       uint32_t take = want < avail ? want : avail;
       if (is_main && ps.pix < 0 && g_w < 0 && rank < take) {
         int unused;
-        slot = load_path(in, pool_next + rank, ps, nullptr, unused);
-        ps.pix = 0;
+        slot = load_path<SMP>(in, pool_next + rank, ps, nullptr, unused); // (ps.pix >= 0: SMP_SOBOL's pixel, else 0)
       }
       pool_next += take;
     }
@@ -2023,7 +2062,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, WF_TAIL_WAVES) void k_wf_tail(const 
       if (is_main && ps.pix < 0 && g_w >= 0) {
         const uint32_t fx = g_pix % p.W, fy = g_pix / p.W;
         if (p.gen_rays) {
-          camera_ray(fx, fy, p.W, p.H, p.cam, p.rb_cam[g_j], ps.ro, ps.rd);
+          camera_ray<SMP>(fx, fy, p.W, p.H, p.cam, p.rb_cam[g_j], p.smp_seed, p.first_tick + g_j, ps.ro, ps.rd);
         } else {
           const float4 po = p.ray_pos[g_pix], di = p.ray_dir[g_pix];
           ps.ro = v3(po.x, po.y, po.z);
@@ -2034,9 +2073,9 @@ __global__ __launch_bounds__(BLOCK_THREADS, WF_TAIL_WAVES) void k_wf_tail(const 
         ps.envDir = v3(0.0f, 0.0f, 1.0f);
         ps.pend = v3(0.0f, 0.0f, 0.0f);
         ps.wx = ps.wy = 0.0f;
-        ps.bounce = 0; ps.iters = 0;
+        ps.bounce = 0; ps.iters = 0; ps.dim = 4u;
         ps.hasShadow = false; ps.primary = true;
-        ps.pix = 0;
+        ps.pix = SMP == SMP_SOBOL ? (int)g_pix : 0;
         slot = g_j; // (only its tick is used: slot % n_batch)
         g_path = true;
         if (COUNT) cnt.samples++;
@@ -2075,7 +2114,8 @@ __global__ __launch_bounds__(BLOCK_THREADS, WF_TAIL_WAVES) void k_wf_tail(const 
     const float tR = r_t;
     const int hitR = r_hit;
     if (ready) {
-      if (advance_path<COUNT>(S, ps, hitA, tR, hitR, p.rb_trace[slot % p.n_batch], p.env_theta, p.num_bounces, cnt)) {
+      if (advance_path<COUNT, SMP>(S, ps, hitA, tR, hitR, p.rb_trace[slot % p.n_batch], p.smp_seed, p.first_tick + slot % p.n_batch,
+                                   p.env_theta, p.num_bounces, cnt)) {
         if (GEN && g_path) {
           g_acc = accumulate_sample(g_acc, ps.color, p.first_tick + g_j);
           g_path = false;
@@ -2207,16 +2247,23 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_tile_pack(const TilePackP p) 
 }
 
 // camera.fs as a stand-alone pass (drawCamera, main.js:741-756)
+template <int SMP>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_camera(uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, CameraP cam,
-                                                         float randBase, float4 *pos, float4 *dir) {
+                                                         float randBase, uint32_t sseed, uint32_t sample, float4 *pos, float4 *dir) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= W * H) return;
   uint32_t x = i % W, y = i / W;
   if (x >= vw || y >= vh) return; // outside gl.viewport: the ray textures keep their old texels
   V3 o, d;
-  camera_ray(x, y, W, H, cam, randBase, o, d);
+  camera_ray<SMP>(x, y, W, H, cam, randBase, sseed, sample, o, d);
   pos[i] = make_float4(o.x, o.y, o.z, 1.0f);
   dir[i] = make_float4(d.x, d.y, d.z, 1.0f);
+}
+
+// the Sobol sampler's device function for n (pixel, sample, dim) triples (fspt_sampler_eval, a test hook)
+__global__ void k_sampler_eval(uint32_t seed, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim, uint32_t n, float *out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = sobol_value(seed, pixel[i], sample[i], dim[i]);
 }
 
 // draw.fs (1-93): exposure -> ACES fit -> saturation -> gamma (+ optional 5x5 firefly filter) -> RGBA8
@@ -2539,14 +2586,16 @@ hipError_t launch_trace(const TraceP &p, bool gen_rays, bool count, int num_cus,
   if (grid == 0) return hipSuccess;
   dim3 g(grid), b(BLOCK_THREADS);
   hipError_t e;
-#define FSPT_LAUNCH_MEGA(G, C)                                                              \
+#define FSPT_LAUNCH_MEGA_S(G, C, M)                                                          \
   do {                                                                                        \
-    if ((e = allow_lds(k_trace<G, C>, lds)) != hipSuccess) return e;                          \
-    hipLaunchKernelGGL((k_trace<G, C>), g, b, lds, stream, p);                                \
+    if ((e = allow_lds(k_trace<G, C, M>, lds)) != hipSuccess) return e;                       \
+    hipLaunchKernelGGL((k_trace<G, C, M>), g, b, lds, stream, p);                             \
   } while (0)
+#define FSPT_LAUNCH_MEGA(G, C) do { if (p.sampler) FSPT_LAUNCH_MEGA_S(G, C, SMP_SOBOL); else FSPT_LAUNCH_MEGA_S(G, C, SMP_REF); } while (0)
   if (gen_rays) { if (count) FSPT_LAUNCH_MEGA(true, true); else FSPT_LAUNCH_MEGA(true, false); }
   else { if (count) FSPT_LAUNCH_MEGA(false, true); else FSPT_LAUNCH_MEGA(false, false); }
 #undef FSPT_LAUNCH_MEGA
+#undef FSPT_LAUNCH_MEGA_S
   return hipGetLastError();
 }
 
@@ -2613,22 +2662,24 @@ hipError_t launch_wf(int kernel, const WfP &p, int count, int num_cus, hipStream
     const uint32_t per_block = WAVES_PER_BLOCK * (WF_TAIL_PAIRS_AUTO && !(p.ctl && p.finish) ? 1u : (uint32_t)WF_TAIL_PAIRS);
     uint32_t grid = min((total + per_block - 1) / per_block, (uint32_t)num_cus * (WF_TAIL_WAVES > 4 ? WF_TAIL_WAVES : 4));
     size_t lds = stack_bytes(p.scene);
-#define FSPT_LAUNCH_TAIL(C, A, Wd)                                                                         \
-    do {                                                                                                     \
-      if (p.ctl && p.finish) {                                                                               \
-        if ((e = allow_lds(k_wf_tail<C, A, true, Wd>, lds)) != hipSuccess) return e;                         \
-        hipLaunchKernelGGL((k_wf_tail<C, A, true, Wd>), dim3(grid), dim3(BLOCK_THREADS), lds, stream, p);    \
-      } else {                                                                                               \
-        if ((e = allow_lds(k_wf_tail<C, A, false, Wd>, lds)) != hipSuccess) return e;                        \
-        hipLaunchKernelGGL((k_wf_tail<C, A, false, Wd>), dim3(grid), dim3(BLOCK_THREADS), lds, stream, p);   \
-      }                                                                                                      \
+#define FSPT_LAUNCH_TAIL_S(C, A, Wd, M)                                                                       \
+    do {                                                                                                        \
+      if (p.ctl && p.finish) {                                                                                  \
+        if ((e = allow_lds(k_wf_tail<C, A, true, Wd, M>, lds)) != hipSuccess) return e;                         \
+        hipLaunchKernelGGL((k_wf_tail<C, A, true, Wd, M>), dim3(grid), dim3(BLOCK_THREADS), lds, stream, p);    \
+      } else {                                                                                                  \
+        if ((e = allow_lds(k_wf_tail<C, A, false, Wd, M>, lds)) != hipSuccess) return e;                        \
+        hipLaunchKernelGGL((k_wf_tail<C, A, false, Wd, M>), dim3(grid), dim3(BLOCK_THREADS), lds, stream, p);   \
+      }                                                                                                         \
     } while (0)
+#define FSPT_LAUNCH_TAIL(C, A, Wd) do { if (p.sampler) FSPT_LAUNCH_TAIL_S(C, A, Wd, SMP_SOBOL); else FSPT_LAUNCH_TAIL_S(C, A, Wd, SMP_REF); } while (0)
     if (count == 1) FSPT_LAUNCH_TAIL(true, false, 0);
     else if (count == 2) FSPT_LAUNCH_TAIL(true, true, 0);
     else if (wide && p.tail_adaptive) FSPT_LAUNCH_TAIL(false, true, 2);
     else if (wide) FSPT_LAUNCH_TAIL(false, true, 1);
     else FSPT_LAUNCH_TAIL(false, true, 0);
 #undef FSPT_LAUNCH_TAIL
+#undef FSPT_LAUNCH_TAIL_S
   } else if (kernel == WF_K_LOGIC || kernel == WF_K_PRIMARY) {
     // resident blocks per CU at WF_LOGIC_WAVES waves per SIMD (4 SIMDs): 2 blocks of 512 threads at 4 waves; twice that many in flight
     const uint32_t threads = kernel == WF_K_PRIMARY ? (uint32_t)WF_PRIMARY_THREADS : (uint32_t)WF_LOGIC_THREADS;
@@ -2642,23 +2693,27 @@ hipError_t launch_wf(int kernel, const WfP &p, int count, int num_cus, hipStream
     if (kernel == WF_K_PRIMARY) {
       const size_t dyn = (size_t)(WF_PRIMARY_THREADS / WAVE) * p.scene.stack_n * WAVE * sizeof(int) + (tab ? tab_bytes : 0u) +
                          (prim_r > 1u ? (size_t)prim_r * WF_PRIMARY_THREADS * 32u : 0u); // + ray and hit of every sample of a block iteration
-#define FSPT_LAUNCH_PRIMARY(C, T, RR, Wd)                                                                      \
-      do {                                                                                                       \
-        if ((e = allow_lds(k_wf_primary<C, T, RR, Wd>, dyn)) != hipSuccess) return e;                            \
-        hipLaunchKernelGGL((k_wf_primary<C, T, RR, Wd>), dim3(grid), dim3(WF_PRIMARY_THREADS), dyn, stream, p);  \
+#define FSPT_LAUNCH_PRIMARY_S(C, T, RR, Wd, M)                                                                    \
+      do {                                                                                                          \
+        if ((e = allow_lds(k_wf_primary<C, T, RR, Wd, M>, dyn)) != hipSuccess) return e;                            \
+        hipLaunchKernelGGL((k_wf_primary<C, T, RR, Wd, M>), dim3(grid), dim3(WF_PRIMARY_THREADS), dyn, stream, p);  \
       } while (0)
+#define FSPT_LAUNCH_PRIMARY(C, T, RR, Wd) do { if (p.sampler) FSPT_LAUNCH_PRIMARY_S(C, T, RR, Wd, SMP_SOBOL); else FSPT_LAUNCH_PRIMARY_S(C, T, RR, Wd, SMP_REF); } while (0)
 #define FSPT_LAUNCH_PRIMARY_R(C, T, Wd) do { if (prim_r > 1u) FSPT_LAUNCH_PRIMARY(C, T, 2, Wd); else FSPT_LAUNCH_PRIMARY(C, T, 1, Wd); } while (0)
       if (count) { if (tab) FSPT_LAUNCH_PRIMARY_R(true, true, false); else FSPT_LAUNCH_PRIMARY_R(true, false, false); }
       else if (wide) { if (tab) FSPT_LAUNCH_PRIMARY_R(false, true, true); else FSPT_LAUNCH_PRIMARY_R(false, false, true); }
       else { if (tab) FSPT_LAUNCH_PRIMARY_R(false, true, false); else FSPT_LAUNCH_PRIMARY_R(false, false, false); }
 #undef FSPT_LAUNCH_PRIMARY_R
 #undef FSPT_LAUNCH_PRIMARY
+#undef FSPT_LAUNCH_PRIMARY_S
     } else {
       const size_t dyn = tab ? tab_bytes : 0u;
-#define FSPT_LAUNCH_LOGIC(C, T) hipLaunchKernelGGL((k_wf_logic<C, T>), dim3(grid), dim3(WF_LOGIC_THREADS), dyn, stream, p)
+#define FSPT_LAUNCH_LOGIC_S(C, T, M) hipLaunchKernelGGL((k_wf_logic<C, T, M>), dim3(grid), dim3(WF_LOGIC_THREADS), dyn, stream, p)
+#define FSPT_LAUNCH_LOGIC(C, T) do { if (p.sampler) FSPT_LAUNCH_LOGIC_S(C, T, SMP_SOBOL); else FSPT_LAUNCH_LOGIC_S(C, T, SMP_REF); } while (0)
       if (count) { if (tab) FSPT_LAUNCH_LOGIC(true, true); else FSPT_LAUNCH_LOGIC(true, false); }
       else { if (tab) FSPT_LAUNCH_LOGIC(false, true); else FSPT_LAUNCH_LOGIC(false, false); }
 #undef FSPT_LAUNCH_LOGIC
+#undef FSPT_LAUNCH_LOGIC_S
     }
   } else {
     uint32_t grid = min((p.work_total + BLOCK_THREADS - 1) / BLOCK_THREADS, (uint32_t)num_cus * WF_RESOLVE_BLOCKS_PER_CU);
@@ -2677,10 +2732,18 @@ hipError_t launch_tile_pack(const TilePackP &p, bool unpack, hipStream_t stream)
 }
 
 hipError_t launch_camera(uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const CameraP &cam, float rand_base, float4 *pos, float4 *dir,
-                         hipStream_t stream) {
+                         hipStream_t stream, uint32_t sampler, uint32_t smp_seed, uint32_t sample) {
   uint32_t n = W * H;
-  hipLaunchKernelGGL(k_camera, dim3((n + BLOCK_THREADS - 1) / BLOCK_THREADS), dim3(BLOCK_THREADS), 0, stream, W, H, vw, vh, cam,
-                     rand_base, pos, dir);
+  const dim3 g((n + BLOCK_THREADS - 1) / BLOCK_THREADS), b(BLOCK_THREADS);
+  if (sampler) hipLaunchKernelGGL(k_camera<SMP_SOBOL>, g, b, 0, stream, W, H, vw, vh, cam, rand_base, smp_seed, sample, pos, dir);
+  else hipLaunchKernelGGL(k_camera<SMP_REF>, g, b, 0, stream, W, H, vw, vh, cam, rand_base, 0u, 0u, pos, dir);
+  return hipGetLastError();
+}
+
+hipError_t launch_sampler_eval(uint32_t seed, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim, uint32_t n,
+                               float *out, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_sampler_eval, dim3((n + 255) / 256), dim3(256), 0, stream, seed, pixel, sample, dim, n, out);
   return hipGetLastError();
 }
 

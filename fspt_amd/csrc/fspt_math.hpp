@@ -213,4 +213,45 @@ FM_DEV float rnd(float &seed) {
   return fract_(sin_(seed) * 43758.5453123f);
 }
 
+// ---- Owen-scrambled Sobol sampler (fspt.h FSPT_SAMPLER_SOBOL) ----------------------------------------------
+// A padded 2-D sequence: dimensions (2k, 2k+1) of a sample are the two coordinates of a Sobol (0,2)-sequence of their own,
+// index-shuffled and scrambled per (seed, pixel, pair).  All arithmetic on uint32, wrapping.
+FM_DEV uint32_t brev32(uint32_t x) { return __builtin_bitreverse32(x); }
+// Laine-Karras style permutation (Burley 2020): nested uniform scramble of a bit-reversed value
+FM_DEV uint32_t lk_perm(uint32_t x, uint32_t s) {
+  x += s;
+  x ^= x * 0x6c50b47cu;
+  x ^= x * 0xb82f1e52u;
+  x ^= x * 0xc7afe638u;
+  x ^= x * 0x8d22f6e6u;
+  return x;
+}
+FM_DEV uint32_t nus_scramble(uint32_t x, uint32_t s) { return brev32(lk_perm(brev32(x), s)); }
+FM_DEV uint32_t hash_u32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+// second Sobol dimension: the Pascal matrix mod 2.  Bit (31 - m) of the result is the XOR of the index bits k whose bit
+// set contains m's (Lucas), i.e. the superset-XOR transform of the index's bits - five shift/mask steps, then a reversal.
+FM_DEV uint32_t sobol1(uint32_t i) {
+  i ^= (i >> 1) & 0x55555555u;
+  i ^= (i >> 2) & 0x33333333u;
+  i ^= (i >> 4) & 0x0f0f0f0fu;
+  i ^= (i >> 8) & 0x00ff00ffu;
+  i ^= (i >> 16) & 0x0000ffffu;
+  return brev32(i);
+}
+// value of dimension `dim` of sample `sample` of `pixel`, in [0, 1) (24 bits, exact in float32)
+FM_DEV float sobol_value(uint32_t seed, uint32_t pixel, uint32_t sample, uint32_t dim) {
+  const uint32_t key = hash_u32(seed ^ hash_u32(pixel ^ hash_u32((dim >> 1) + 0x9e3779b9u)));
+  const uint32_t i = nus_scramble(sample, key); // index shuffle, shared by the pair's two coordinates
+  uint32_t x = (dim & 1u) ? sobol1(i) : brev32(i);
+  x = nus_scramble(x, hash_u32(key ^ (0x68bc21ebu + (dim & 1u))));
+  return (float)(x >> 8) * 5.9604644775390625e-8f; // 2^-24
+}
+
 }  // namespace fm

@@ -16,6 +16,8 @@ void fill_trace_params(fspt_target *t, fspt::TraceP &p) {
   p.tiles_y = (t->H + t->tile - 1) / t->tile;
   uint32_t n_tiles = p.tiles_x * p.tiles_y;
   p.n_owned_tiles = (n_tiles > t->shard) ? (n_tiles - t->shard + t->n_shards - 1) / t->n_shards : 0;
+  p.sampler = (uint32_t)t->sampler;
+  p.smp_seed = t->sampler_seed;
 }
 
 // Records of suspended traversals: one per lane of the trace grid a launch over `max_paths` paths gets (a lane parks at
@@ -389,6 +391,7 @@ static int wf_run(fspt_target *t, fspt_target::WfLane &ln, hipStream_t st, bool 
   p.counters = t->count ? t->counters : nullptr;
   p.shard = tp.shard; p.n_shards = tp.n_shards; p.tile = tp.tile; p.tiles_x = tp.tiles_x; p.tiles_y = tp.tiles_y;
   p.n_owned_tiles = tp.n_owned_tiles;
+  p.sampler = tp.sampler; p.smp_seed = tp.smp_seed;
   const int cus = t->scene->num_cus;
   const bool gen = !rays_from_buffers;
   const uint32_t nb = cam->num_bounces;

@@ -392,6 +392,15 @@ class PathTracer {
   /** gl.viewport(0, 0, w, h) of drawCamera / drawTracer (main.js:744,761); the reference: resolution * resScale. */
   setViewport(w, h) { addon.setViewport(this._target, w || 0, h || 0); }
   setShard(shard, nShards, tile) { addon.setShard(this._target, shard, nShards, tile || 32); }
+  /** the paths' random numbers (include/fspt.h fspt_target_set_sampler): 'reference' (default, rnd() bit for bit) or
+   *  'sobol' (Owen-scrambled Sobol seeded by `seed`, an integer in [0, 2^32)) */
+  setSampler(kind, seed) {
+    const code = { reference: 0, sobol: 1 }[kind];
+    if (code === undefined) throw new RangeError("setSampler: kind must be 'reference' or 'sobol'");
+    const s = seed === undefined ? 0 : seed;
+    if (!Number.isInteger(s) || s < 0 || s > 0xFFFFFFFF) throw new RangeError('setSampler: seed must be an integer in [0, 2^32)');
+    addon.setSampler(this._target, code, s);
+  }
   /** 'wavefront' (batches of ticks), 'stream' (fixed pool of live paths), 'megakernel' (include/fspt_tuning.h) */
   setPipeline(name, batch) { addon.setPipeline(this._target, pipelineCode(name), batch || 0); }
   /** traversal steps a starved trace wave walks on before it suspends its rays (0 = never; include/fspt.h) */

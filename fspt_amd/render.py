@@ -5,6 +5,7 @@ reference's format (scene/<name>.json with props / static_props / animated_props
     python -m fspt_amd.render --scene web/scene/bunny.json --out bunny.png
     python -m fspt_amd.render --scene 'web/scene/anim_{frame}.json' --frames 0:24 --out 'out/{frame}.png'
     python -m fspt_amd.render --out bunny.png --spp 16 --atrous 5 --feature-samples 8   # guided denoiser
+    python -m fspt_amd.render --out bunny.png --spp 16 --sampler sobol --sampler-seed 3  # Owen-scrambled Sobol sampler
 
 Path tracing runs in the HIP kernels (fspt_render), tone mapping in the draw.fs kernel (fspt_draw); --atrous K runs
 the guided a-trous denoiser (fspt_features + fspt_denoise, K iterations) before tone mapping (fspt_draw_denoised).
@@ -35,9 +36,16 @@ def main():
     ap.add_argument("--assets", default=None, help="web root the JSON's paths are relative to (default: parent of the scene folder)")
     ap.add_argument("--frames", default=None, help="A:B = frames A..B-1 (the reference's ?frame=N loop, main.js:851-866)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--sampler", choices=("reference", "sobol"), default="reference",
+                    help="the paths' random numbers (fspt_target_set_sampler; built-in scene)")
+    ap.add_argument("--sampler-seed", type=int, default=0, help="seed of --sampler sobol, in [0, 2^32)")
     args = ap.parse_args()
     if args.atrous and args.scene:
         ap.error("--atrous is available for the built-in scene")
+    if args.scene and args.sampler != "reference":
+        ap.error("--sampler is available for the built-in scene")
+    if not 0 <= args.sampler_seed <= 0xFFFFFFFF:
+        ap.error("--sampler-seed must lie in [0, 2^32)")
     if args.scene:
         from . import scene_file as F
         spp = args.spp if "--spp" in " ".join(__import__("sys").argv) else None  # default: the scene's `samples`
@@ -60,6 +68,8 @@ def main():
     arrays = S.bunny_scene(n=args.mesh_n)
     pt = PathTracer(arrays, args.width, args.height, num_bounces=args.bounces)
     pt.set_camera(**S.BUNNY_CAMERA)
+    if args.sampler != "reference":
+        pt.set_sampler(args.sampler, args.sampler_seed)
     t0 = time.perf_counter()
     pt.render(args.spp)
     pt.sync()

@@ -30,7 +30,37 @@ def device_memory(device=0):
     return int(f.value), int(t.value)
 
 
+def sampler_eval(seed, pixel, sample, dim, device=0):
+    """FSPT_SAMPLER_SOBOL's device function for the (pixel, sample, dim) triples (fspt_sampler_eval, a test hook):
+    float32 values in [0, 1), arrays broadcast against each other."""
+    seed = _sampler_seed(seed)
+    pixel, sample, dim = (np.ascontiguousarray(a, dtype=np.uint32) for a in np.broadcast_arrays(
+        *(_u32_array(a, name) for a, name in ((pixel, "pixel"), (sample, "sample"), (dim, "dim")))))
+    out = np.empty(pixel.shape, np.float32)
+    L.check(L.lib().fspt_sampler_eval(int(device), seed, L.u32ptr(pixel), L.u32ptr(sample), L.u32ptr(dim), int(pixel.size),
+                                      L.fptr(out)))
+    return out
+
+
+def _u32_array(a, name):
+    a = np.asarray(a)
+    if a.dtype.kind not in "iu":
+        raise TypeError("%s must be integers, got %s" % (name, a.dtype))
+    if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+        raise ValueError("%s must lie in [0, 2^32)" % name)
+    return a
+
+
+def _sampler_seed(seed):
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise TypeError("sampler seed must be an integer, got %r" % (seed,))
+    if not 0 <= int(seed) <= 0xFFFFFFFF:
+        raise ValueError("sampler seed must lie in [0, 2^32), got %d" % int(seed))
+    return int(seed)
+
+
 PIPELINES = {"megakernel": 0, "wavefront": 1, "stream": 2}  # fspt_target_set_pipeline codes
+SAMPLERS = {"reference": 0, "sobol": 1}  # fspt_target_set_sampler codes
 # fspt_denoise's defaults (include/fspt.h FSPT_DENOISE_*; tests/test_denoise_cpu.py pins the two)
 DENOISE_DEFAULTS = {"iterations": 4, "sigma_color": 4.0, "sigma_normal": 32.0, "sigma_depth": 0.05}
 
@@ -124,6 +154,20 @@ class PathTracer:
         """gl.viewport(0, 0, w, h) of drawCamera / drawTracer (main.js:744,761); 0, 0 = the whole target.  The
         reference uses resolution * 0.25 while the camera moves (resScale, main.js:840)."""
         L.check(L.lib().fspt_target_set_viewport(self._t, int(w), int(h)))
+
+    def set_sampler(self, kind="sobol", seed=0):
+        """The paths' random numbers (fspt_target_set_sampler): "reference" (the default: rnd(), bit for bit)
+        or "sobol" (Owen-scrambled Sobol, seeded by `seed`; rand_base values then no longer affect radiance).  Runs the
+        recorded ticks first; does not clear the accumulator."""
+        if kind not in SAMPLERS:
+            raise ValueError("sampler must be one of %s, got %r" % (sorted(SAMPLERS), kind))
+        L.check(L.lib().fspt_target_set_sampler(self._t, SAMPLERS[kind], _sampler_seed(seed)))
+
+    def get_sampler(self):
+        """(kind, seed) of fspt_target_get_sampler."""
+        k, s = C.c_int(), C.c_uint32()
+        L.check(L.lib().fspt_target_get_sampler(self._t, C.byref(k), C.byref(s)))
+        return {v: n for n, v in SAMPLERS.items()}[k.value], int(s.value)
 
     def bind_accumulator(self, device_ptr, keep=None):
         """Accumulate into caller-owned device memory (e.g. a torch tensor) so a

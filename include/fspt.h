@@ -153,6 +153,8 @@ float fspt_rand_base_next(uint64_t *state);
 /* gl.viewport(0, 0, w, h) of drawCamera / drawTracer (main.js:744,761; resScale 0.25 while dragging, main.js:840):
  * only pixels x < w, y < h are traced, the rest keeps its contents.  0, 0 restores the whole target. */
 int fspt_target_set_viewport(fspt_target *target, uint32_t w, uint32_t h);
+enum { FSPT_SAMPLER_REFERENCE = 0, FSPT_SAMPLER_SOBOL = 1 }; /* the paths' random numbers: rnd() bit for bit (default) | Owen-scrambled Sobol (DESIGN 8.2) */
+int fspt_target_set_sampler(fspt_target *target, int sampler, uint32_t seed); int fspt_target_get_sampler(fspt_target *target, int *sampler, uint32_t *seed);
 
 /* Several GPUs (one frame cut into 32x32 tiles over the devices of a node; the reference has nothing here - README.md:28
  * lists "Tiled rendering" as a TODO): include/fspt_multi.h, included at the end of this file. */

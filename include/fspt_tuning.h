@@ -125,6 +125,15 @@ enum {
 };
 int fspt_math_eval(int device, int op, const float *a, const float *b, uint32_t n,
                    float *out);
+/* fspt_target_set_sampler (fspt.h): FSPT_SAMPLER_SOBOL draws value(seed, pixel, sample, dim) with pixel = y*W + x
+ * of the full target, sample = the tick (the running mean's weight index) and dim = the values the sample has drawn so far
+ * (the camera ray 0..3, then each shaded hit in call order: 6 values, 8 on the Lambert branch).  rand_base arguments and
+ * fspt_render's seed then do not affect radiance; rays materialised before they are traced (fspt_read_rays,
+ * fspt_trace_test) use sample index 1 + the last tick accumulated (0 after create or fspt_clear).  Every pipeline and
+ * scheduler gives the same bits.  Like every setter it runs the recorded ticks first and keeps the accumulator.
+ * Test hook: the FSPT_SAMPLER_SOBOL device function value(seed, pixel[i], sample[i], dim[i]) for n triples (host arrays). */
+int fspt_sampler_eval(int device, uint32_t seed, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim,
+                      uint32_t n, float *out);
 
 #ifdef __cplusplus
 }

@@ -92,6 +92,9 @@ SIGNATURES = {
     "fspt_target_set_viewport": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
     "fspt_target_set_sampler": (C.c_int, [_VP, C.c_int, C.c_uint32]),
     "fspt_target_get_sampler": (C.c_int, [_VP, C.POINTER(C.c_int), _U32]),
+    "fspt_target_set_lights": (C.c_int, [_VP, C.c_int, C.c_float]),
+    "fspt_target_get_lights": (C.c_int, [_VP, C.POINTER(C.c_int), _F]),
+    "fspt_scene_light_count": (C.c_int, [_VP, _U32]),
     "fspt_target_set_shard": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
     "fspt_target_bind_accumulator": (C.c_int, [_VP, _VP]),
     "fspt_target_accumulator": (C.c_int, [_VP, C.POINTER(_VP)]),
@@ -123,6 +126,9 @@ SIGNATURES = {
     "fspt_get_trace_lds_steps": (C.c_int, [_VP, C.POINTER(C.c_uint64)]),
     "fspt_math_eval": (C.c_int, [C.c_int, C.c_int, _F, _F, C.c_uint32, _F]),
     "fspt_sampler_eval": (C.c_int, [C.c_int, C.c_uint32, _U32, _U32, _U32, C.c_uint32, _F]),
+    "fspt_scene_light_table": (C.c_int, [_VP, _U32, _U32, _U32, _F, _F, _U32, _U32, _F, _U32]),
+    "fspt_light_sample_eval": (C.c_int, [_VP, _F, C.c_uint32, C.POINTER(C.c_int32), _F]),
+    "fspt_light_alias_table": (C.c_int, [_F, C.c_uint32, _F, _U32]),
     "fspt_last_kernel_ms": (C.c_int, [_VP, _F, _U32]),
     "fspt_target_set_pipeline": (C.c_int, [_VP, C.c_int, C.c_uint32]),
     "fspt_target_set_primary_form": (C.c_int, [_VP, C.c_int]),

@@ -62,7 +62,120 @@ int check_device(int device) {
   return FSPT_OK;
 }
 
+// Vose alias table in float64 (stored float32): entry i is taken with probability (prob_i + sum_{alias_j = i} (1 - prob_j)) / n
+static bool alias_build(const float *w, uint32_t n, std::vector<float> &prob, std::vector<uint32_t> &alias) {
+  double sum = 0.0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!(w[i] >= 0.0f) || !std::isfinite(w[i])) return false;
+    sum += (double)w[i];
+  }
+  if (!(sum > 0.0) || !std::isfinite(sum)) return false;
+  std::vector<double> sc(n);
+  std::vector<uint32_t> small, large;
+  for (uint32_t i = 0; i < n; ++i) {
+    sc[i] = ((double)w[i] / sum) * (double)n;
+    (sc[i] < 1.0 ? small : large).push_back(i);
+  }
+  prob.assign(n, 1.0f);
+  alias.resize(n);
+  for (uint32_t i = 0; i < n; ++i) alias[i] = i;
+  while (!small.empty() && !large.empty()) {
+    const uint32_t l = small.back(), g = large.back();
+    small.pop_back(); large.pop_back();
+    prob[l] = (float)sc[l];
+    alias[l] = g;
+    sc[g] = (sc[g] + sc[l]) - 1.0;
+    (sc[g] < 1.0 ? small : large).push_back(g);
+  }
+  // what is left holds probability 1 up to rounding: kept whole
+  return true;
+}
+
+// The scene's emitter light table: per-triangle weights on the device (k_light_weights over one leaf slot of
+// each triangle), the alias table of the triangles with weight > 0 on the host, their light records on the device
+int light_table_ensure(fspt_scene *s) {
+  if (s->lights_built) return FSPT_OK;
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  const uint32_t T = s->n_tris;
+  // leaf slots and their triangles (the hit records are stored per slot)
+  const size_t slots_n = s->n_slots;
+  s->l_slot_tri.resize(slots_n);
+  {
+    const hipError_t e = hipMemcpy(s->l_slot_tri.data(), s->slot_tri, slots_n * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { fspt_set_error("light table: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
+  }
+  std::vector<uint32_t> first(T, 0xFFFFFFFFu);
+  for (size_t sl = slots_n; sl-- > 0;) if (s->l_slot_tri[sl] < T) first[s->l_slot_tri[sl]] = (uint32_t)sl;
+  std::vector<uint32_t> tri_slot(T, 0u);
+  for (uint32_t i = 0; i < T; ++i) tri_slot[i] = first[i] == 0xFFFFFFFFu ? 0u : first[i];
+  uint32_t *d_slots = nullptr;
+  float *d_w = nullptr;
+  hipError_t e = hipMalloc((void **)&d_slots, (size_t)T * 4);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_w, (size_t)T * 4);
+  if (e == hipSuccess) e = hipMemcpy(d_slots, tri_slot.data(), (size_t)T * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = fspt::launch_light_weights(s->d, d_slots, T, d_w, nullptr, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  s->l_weight.assign(T, 0.0f);
+  if (e == hipSuccess) e = hipMemcpy(s->l_weight.data(), d_w, (size_t)T * 4, hipMemcpyDeviceToHost);
+  for (uint32_t i = 0; i < T; ++i) if (first[i] == 0xFFFFFFFFu) s->l_weight[i] = 0.0f; // (a triangle in no leaf: never hit)
+  s->l_tri.clear();
+  std::vector<float> wl;
+  std::vector<uint32_t> ent_slot;
+  for (uint32_t i = 0; i < T; ++i)
+    if (s->l_weight[i] > 0.0f) { s->l_tri.push_back(i); wl.push_back(s->l_weight[i]); ent_slot.push_back(tri_slot[i]); }
+  const uint32_t n = (uint32_t)s->l_tri.size();
+  s->l_prob.clear(); s->l_alias_h.clear();
+  std::vector<float> lp(n, 0.0f);
+  s->l_pick_h.assign(slots_n, 0.0f);
+  if (e == hipSuccess && n > 0) {
+    if (!alias_build(wl.data(), n, s->l_prob, s->l_alias_h)) { hipFree(d_slots); hipFree(d_w); fspt_set_error("light table: bad weights"); return FSPT_E_INVALID; }
+    std::vector<double> real(n, 0.0);
+    for (uint32_t i = 0; i < n; ++i) {
+      real[i] += (double)s->l_prob[i];
+      if (s->l_alias_h[i] != i) real[s->l_alias_h[i]] += 1.0 - (double)s->l_prob[i];
+    }
+    std::vector<float> tri_p(T, 0.0f);
+    for (uint32_t i = 0; i < n; ++i) { lp[i] = (float)(real[i] / (double)n); tri_p[s->l_tri[i]] = lp[i]; }
+    for (size_t sl = 0; sl < slots_n; ++sl) if (s->l_slot_tri[sl] < T) s->l_pick_h[sl] = tri_p[s->l_slot_tri[sl]];
+    std::vector<uint32_t> al(2 * (size_t)n);
+    for (uint32_t i = 0; i < n; ++i) { std::memcpy(&al[2 * i], &s->l_prob[i], 4); al[2 * i + 1] = s->l_alias_h[i]; }
+    e = hipMalloc(&s->l_alias, (size_t)n * 8);
+    if (e == hipSuccess) e = hipMemcpy(s->l_alias, al.data(), (size_t)n * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(&s->l_p, (size_t)n * 4);
+    if (e == hipSuccess) e = hipMemcpy(s->l_p, lp.data(), (size_t)n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(&s->l_rec, (size_t)n * 64);
+    if (e == hipSuccess) e = hipMemcpy(d_slots, ent_slot.data(), (size_t)n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = fspt::launch_light_weights(s->d, d_slots, n, d_w, (float4 *)s->l_rec, nullptr);
+    if (e == hipSuccess) e = hipMalloc(&s->l_pick, slots_n * 4);
+    if (e == hipSuccess) e = hipMemcpy(s->l_pick, s->l_pick_h.data(), slots_n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+  }
+  hipFree(d_slots); hipFree(d_w);
+  if (e != hipSuccess) { fspt_set_error("light table: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
+  s->d.light_alias = (const uint2 *)s->l_alias;
+  s->d.light_rec = (const float4 *)s->l_rec;
+  s->d.light_p = (const float *)s->l_p;
+  s->d.light_pick = (const float *)s->l_pick;
+  s->d.n_lights = n;
+  s->lights_built = true;
+  return FSPT_OK;
+}
+
 extern "C" {
+
+int fspt_light_alias_table(const float *weights, uint32_t n, float *prob, uint32_t *alias) {
+  if (!weights || !prob || !alias || n == 0) { fspt_set_error("fspt_light_alias_table: NULL/empty argument"); return FSPT_E_INVALID; }
+  std::vector<float> p;
+  std::vector<uint32_t> a;
+  if (!alias_build(weights, n, p, a)) {
+    fspt_set_error("fspt_light_alias_table: weights must be finite and >= 0 with a positive finite sum");
+    return FSPT_E_INVALID;
+  }
+  std::memcpy(prob, p.data(), (size_t)n * 4);
+  std::memcpy(alias, a.data(), (size_t)n * 4);
+  return FSPT_OK;
+}
 
 const char *fspt_last_error(void) { return g_err; }
 int fspt_abi_version(void) { return FSPT_ABI_VERSION; }
@@ -492,6 +605,7 @@ int fspt_scene_create(const fspt_scene_desc *desc, int device, fspt_scene **out)
   s->n_tris = T;
   s->n_interior = n_interior;
   s->has_dielectric = has_dielectric;
+  s->n_slots = n_slots;
   *out = s;
   return FSPT_OK;
 }
@@ -500,6 +614,7 @@ int fspt_scene_destroy(fspt_scene *s) {
   if (!s) return FSPT_OK;
   hipSetDevice(s->device);
   hipFree(s->nodes); hipFree(s->quads); hipFree(s->tris); hipFree(s->slot_tri); hipFree(s->shade); hipFree(s->atlas); hipFree(s->atlas4); hipFree(s->tex_sets); hipFree(s->env); hipFree(s->bins);
+  hipFree(s->l_alias); hipFree(s->l_rec); hipFree(s->l_p); hipFree(s->l_pick);
   delete s;
   return FSPT_OK;
 }
@@ -906,6 +1021,77 @@ int fspt_target_get_sampler(fspt_target *t, int *sampler, uint32_t *seed) {
   if (!t) { fspt_set_error("fspt_target_get_sampler: NULL target"); return FSPT_E_INVALID; }
   if (sampler) *sampler = t->sampler;
   if (seed) *seed = t->sampler_seed;
+  return FSPT_OK;
+}
+
+int fspt_target_set_lights(fspt_target *t, int mode, float emitter_fraction) {
+  if (!t) { fspt_set_error("fspt_target_set_lights: NULL target"); return FSPT_E_INVALID; }
+  if (mode != FSPT_LIGHTS_OFF && mode != FSPT_LIGHTS_EMITTERS) {
+    fspt_set_error("fspt_target_set_lights: mode must be FSPT_LIGHTS_OFF (0) or FSPT_LIGHTS_EMITTERS (1), got %d", mode);
+    return FSPT_E_INVALID;
+  }
+  if (!(emitter_fraction > 0.0f && emitter_fraction <= 1.0f)) {
+    fspt_set_error("fspt_target_set_lights: emitter_fraction must lie in (0, 1], got %g", (double)emitter_fraction);
+    return FSPT_E_INVALID;
+  }
+  FLUSH_OR_RETURN(t);
+  if (mode == FSPT_LIGHTS_EMITTERS) {
+    const int rc = light_table_ensure(t->scene);
+    if (rc) return rc;
+  }
+  t->lights = mode;
+  t->emitter_fraction = emitter_fraction;
+  return FSPT_OK;
+}
+
+int fspt_target_get_lights(fspt_target *t, int *mode, float *emitter_fraction) {
+  if (!t) { fspt_set_error("fspt_target_get_lights: NULL target"); return FSPT_E_INVALID; }
+  if (mode) *mode = t->lights;
+  if (emitter_fraction) *emitter_fraction = t->emitter_fraction;
+  return FSPT_OK;
+}
+
+int fspt_scene_light_count(fspt_scene *s, uint32_t *n_lights) {
+  if (!s || !n_lights) { fspt_set_error("fspt_scene_light_count: NULL argument"); return FSPT_E_INVALID; }
+  const int rc = light_table_ensure(s);
+  if (rc) return rc;
+  *n_lights = s->d.n_lights;
+  return FSPT_OK;
+}
+
+int fspt_scene_light_table(fspt_scene *s, uint32_t *n_tris, uint32_t *n_lights, uint32_t *n_slots, float *weights, float *prob,
+                           uint32_t *alias, uint32_t *tris, float *pick, uint32_t *slot_tri) {
+  if (!s) { fspt_set_error("fspt_scene_light_table: NULL scene"); return FSPT_E_INVALID; }
+  const int rc = light_table_ensure(s);
+  if (rc) return rc;
+  if (n_tris) *n_tris = (uint32_t)s->l_weight.size();
+  if (n_lights) *n_lights = (uint32_t)s->l_tri.size();
+  if (n_slots) *n_slots = (uint32_t)s->l_pick_h.size();
+  auto put = [](auto *dst, const auto &v) { if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
+  put(weights, s->l_weight); put(prob, s->l_prob); put(alias, s->l_alias_h); put(tris, s->l_tri); put(pick, s->l_pick_h);
+  put(slot_tri, s->l_slot_tri);
+  return FSPT_OK;
+}
+
+int fspt_light_sample_eval(fspt_scene *s, const float *in, uint32_t n, int32_t *tri, float *out) {
+  if (!s || !in || !tri || !out) { fspt_set_error("fspt_light_sample_eval: NULL argument"); return FSPT_E_INVALID; }
+  int rc = light_table_ensure(s);
+  if (rc) return rc;
+  if (s->d.n_lights == 0) { fspt_set_error("fspt_light_sample_eval: the scene has no emitter"); return FSPT_E_STATE; }
+  if (n == 0) return FSPT_OK;
+  float *d_in = nullptr, *d_out = nullptr;
+  int *d_e = nullptr;
+  hipError_t e = hipMalloc((void **)&d_in, (size_t)n * 40);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_out, (size_t)n * 32);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_e, (size_t)n * 4);
+  if (e == hipSuccess) e = hipMemcpy(d_in, in, (size_t)n * 40, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = fspt::launch_light_eval(s->d, d_in, n, d_e, d_out, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, d_out, (size_t)n * 32, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(tri, d_e, (size_t)n * 4, hipMemcpyDeviceToHost);
+  hipFree(d_in); hipFree(d_out); hipFree(d_e);
+  if (e != hipSuccess) { fspt_set_error("fspt_light_sample_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
+  for (uint32_t i = 0; i < n; ++i) tri[i] = (int32_t)s->l_tri[(uint32_t)tri[i]];
   return FSPT_OK;
 }
 

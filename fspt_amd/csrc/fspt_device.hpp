@@ -95,6 +95,15 @@ struct DScene {
   int root_ref;
   uint32_t stack_n; // LDS stack entries per lane (tree depth + 1)
   uint32_t n_top;   // nodes [0, n_top) are the top of the tree in breadth-first order
+  // emitter light table (fspt_target_set_lights; built on the first target that turns the mode on, NULL before):
+  //   light_alias[i] = (prob_i bits, alias_i): Vose alias table over the n_lights entries
+  //   light_rec[4 i .. 4 i + 3] = 64-byte light record: v1.xyz e1.xyz e2.xyz, uv0 uv1 uv2, (uint bits) texture set
+  //   light_p[i] = the probability the float32 table realises for entry i; light_pick[slot] = that of the slot's triangle (0: none)
+  const uint2 *light_alias;
+  const float4 *light_rec;
+  const float *light_p;
+  const float *light_pick;
+  uint32_t n_lights;
 };
 
 struct CameraP {
@@ -124,6 +133,8 @@ struct TraceP {
   uint32_t tiles_x, tiles_y, n_owned_tiles;
   uint32_t sampler;  // FSPT_SAMPLER_*: which instantiation launch_trace picks
   uint32_t smp_seed; // FSPT_SAMPLER_SOBOL's seed
+  uint32_t lights;   // 1: the FSPT_LIGHTS_EMITTERS instantiations (only when scene.n_lights > 0)
+  float light_q;     // q, the probability a vertex's NEE goes to an emitter (emitter_fraction, 1 without an environment map)
 };
 
 struct IntersectP {
@@ -155,6 +166,10 @@ struct IntersectP {
 //   C  accumulatedReflectance.xyz, weights.y
 //   E  color.xyz, -   (only touched while the colour is non-zero)
 //   D  envDir.xyz, weights.x             P  reflectance*envThroughput.xyz, -     (only when the path has a NEE shadow ray)
+//   FSPT_LIGHTS_EMITTERS instantiations: P.w = the shadow ray's t bound (MAX_T: environment; below: an
+//   emitter point).  A path whose last vertex could sample an emitter (q > 0) has flag WF_FLAG_LQ and D / P are written
+//   whatever its shadow ray: D.w then holds q / pb (pb = that vertex's bsdfPdf: the MIS weight of an emitter its
+//   extension ray hits) and weights.x is 1 (folded into P.xyz).
 // Per round (indexed like the state): hit (t, index) of the extension ray, shadow_hit = index of the NEE ray.
 // fin[slot]: the finished sample colour, slot-major (a wave's finishing paths are neighbours).
 // ---------------------------------------------------------------------------
@@ -162,6 +177,10 @@ constexpr int WF_MAX_BATCH = 128;
 constexpr int WF_HIT_TERMINAL = -2; // hit[k].index of an extension ray that hit something but whose path has no bounce left
 constexpr int WF_HIT_PENDING = -3;  // hit[k].index of a path whose traversal was SUSPENDED by the trace launch (hit[k].t = its record)
 constexpr uint32_t WF_FLAG_PRIMARY = 1u << 16, WF_FLAG_SHADOW = 1u << 17, WF_FLAG_COLZERO = 1u << 18;
+// FSPT_LIGHTS_EMITTERS instantiations only: bit 15 (the top bit of the iteration count, which never exceeds
+// MAX_PATH_ITERS = 64 and so is read through a 7-bit mask there): D.w holds q / pb, see above
+constexpr uint32_t WF_FLAG_LQ = 1u << 15;
+static_assert(MAX_PATH_ITERS < 128, "WF_FLAG_LQ: the iteration count must fit 7 bits");
 // Suspended traversals (k_wf_trace): what a trace launch costs beyond its work is its LONGEST ray - a dependent chain of
 // up to a few hundred node fetches that a handful of lanes walk while the rest of the chip idles (~0.2 ms per launch,
 // profiles/r03).  A wave that can get no more work and has been walking for WfP::susp_budget steps writes the state of
@@ -175,9 +194,9 @@ constexpr uint32_t WF_FLAG_SUSP = 1u << 19;
 #endif
 constexpr uint32_t WF_LAG_SHIFT = 20, WF_LAG_MASK = 7u, WF_LAG_MAX = FSPT_WF_LAG_MAX;
 // Sobol sampler only (fspt.h FSPT_SAMPLER_SOBOL): bits 23-31 of the flags hold half the path's sampler dimension count
-// (always even, at most 4 + 8 * MAX_PATH_ITERS = 516: 9 bits)
+// (always even, at most 4 + 12 * MAX_PATH_ITERS = 772 with emitter sampling: 9 bits)
 constexpr uint32_t WF_DIM_SHIFT = 23;
-static_assert(((4u + 8u * MAX_PATH_ITERS) >> 1) < (1u << (32u - WF_DIM_SHIFT)), "WF_DIM_SHIFT: dimension count does not fit");
+static_assert(((4u + 12u * MAX_PATH_ITERS) >> 1) < (1u << (32u - WF_DIM_SHIFT)), "WF_DIM_SHIFT: dimension count does not fit");
 constexpr int WF_SUSP_HEADER = 8; // ints before the stack entries of a record: state index, node, t, hit, sp | ray << 8, shadow result, -, -
 #ifndef FSPT_WF_HEADS
 #define FSPT_WF_HEADS 16
@@ -284,6 +303,8 @@ struct WfP {
   uint32_t shard, n_shards, tile, tiles_x, tiles_y, n_owned_tiles;
   uint32_t sampler;  // as in TraceP; a slot's sample index is first_tick + slot % n_batch
   uint32_t smp_seed;
+  uint32_t lights;   // as in TraceP
+  float light_q;
 };
 
 // kernel classes; also the slots of fspt_last_stage_ms
@@ -334,6 +355,11 @@ hipError_t launch_camera(uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const
 hipError_t launch_sampler_eval(uint32_t seed, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim, uint32_t n,
                                float *out, hipStream_t stream);
 hipError_t launch_intersect(const IntersectP &p, hipStream_t stream);
+// light table build (fspt_target_set_lights): w[i] for the triangle in leaf slot slots[i]; with rec != NULL
+// also its 64-byte light record rec[4 i .. 4 i + 3]
+hipError_t launch_light_weights(const DScene &S, const uint32_t *slots, uint32_t n, float *w, float4 *rec, hipStream_t stream);
+// fspt_light_sample_eval: 10 floats per query (ro.xyz, n.xyz, u0..u3) -> entry index, 8 floats (x.xyz, pdf_L, Le.rgb, n . w)
+hipError_t launch_light_eval(const DScene &S, const float *in, uint32_t n, int *entry, float *out, hipStream_t stream);
 hipError_t launch_bvh_test(const TraceP &p, hipStream_t stream);
 hipError_t launch_draw(const float4 *acc, uint32_t W, uint32_t H, float exposure, float saturation, int denoise,
                        float max_sigma, float scale, uint32_t *out, hipStream_t stream);

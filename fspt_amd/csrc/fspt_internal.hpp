@@ -41,7 +41,22 @@ struct fspt_scene {
   void *nodes = nullptr, *quads = nullptr /* two-level nodes, or NULL */, *tris = nullptr /* leaf records */, *slot_tri = nullptr, *shade = nullptr, *atlas = nullptr, *atlas4 = nullptr, *tex_sets = nullptr, *env = nullptr, *bins = nullptr;
   uint32_t depth = 0, n_nodes = 0, n_tris = 0, n_interior = 0;
   bool has_dielectric = false; // some triangle can refract (tracer.fs:481-488: unbounded path length)
+  // emitter light table, built by light_table_ensure on the first target that turns FSPT_LIGHTS_EMITTERS on;
+  // device arrays behind d.light_*, host copies for fspt_scene_light_table
+  size_t n_slots = 0;   // leaf slots (hit records, slot_tri entries)
+  bool lights_built = false;
+  void *l_alias = nullptr, *l_rec = nullptr, *l_p = nullptr, *l_pick = nullptr;
+  std::vector<float> l_weight;      // per triangle (reference order)
+  std::vector<uint32_t> l_tri;      // per table entry: its triangle
+  std::vector<float> l_prob;        // per entry
+  std::vector<uint32_t> l_alias_h;  // per entry
+  std::vector<float> l_pick_h;      // per leaf slot
+  std::vector<uint32_t> l_slot_tri; // per leaf slot: its triangle
 };
+int light_table_ensure(fspt_scene *s); // (fspt_api.cpp) builds the table once; FSPT_OK when it exists
+#ifndef FSPT_LIGHTS_ENV_Q_MAX
+#define FSPT_LIGHTS_ENV_Q_MAX 0.875f // largest q of a scene with an environment map (fspt_sched_batch.cpp fill_trace_params)
+#endif
 
 static const int WF_ARRAYS = 15;
 #ifndef FSPT_TAIL_SLICE_LARGE
@@ -110,6 +125,8 @@ struct fspt_target {
   int pipeline = 1;           // 0 = megakernel, 1 = wavefront
   int sampler = 0;            // FSPT_SAMPLER_REFERENCE / FSPT_SAMPLER_SOBOL (fspt_target_set_sampler)
   uint32_t sampler_seed = 0;  // FSPT_SAMPLER_SOBOL's seed
+  int lights = 0;             // FSPT_LIGHTS_OFF / FSPT_LIGHTS_EMITTERS (fspt_target_set_lights)
+  float emitter_fraction = 0.5f; // q of a scene with an environment map (1 without one)
   int sched = 0;              // wavefront pipeline: 0 = batch scheduler (all ticks x all pixels per batch), 1 = stream (fixed pool)
   bool stream_fallback = false; // sched 0, but the path state of FSPT_MIN_BATCH ticks did not fit: calls run on the stream scheduler (cleared by every setter that changes what fits)
   uint32_t pool_paths = 0;    // stream: paths per state set and lane (0 = default)

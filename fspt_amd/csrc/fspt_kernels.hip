@@ -201,13 +201,14 @@ struct Counters {
 // ---------------------------------------------------------------------------
 // ANYHIT: ray A stops at its first hit (only `shadow.index == -1` is consumed, tracer.fs:502).
 // WIDE: walk the two-level nodes (S.quads, must be non-NULL): two steps per memory round trip, same walk.
+// tA: ray A's t bound (an emitter shadow ray ends short of its light point; MAX_T otherwise)
 template <bool COUNT, bool ANYHIT, bool WIDE = false>
 FM_DEV void trace_rays(const DScene &S, int *stack, V3 o, bool hasA, V3 dA, V3 dB, int &hitA, float &tB, int &hitB,
-                       Counters &cnt) {
+                       Counters &cnt, float tA = MAX_T) {
   int slot = hasA ? 0 : 1;
   V3 d = hasA ? dA : dB;
   V3 inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-  float t = MAX_T;
+  float t = hasA ? tA : MAX_T;
   int hit = -1;
   int cur = S.root_ref;
   int sp = 0;
@@ -597,6 +598,76 @@ FM_DEV V3 eval_specular(V3 incident, V3 normal, V3 diffuse, float metallic, floa
 }
 
 // ---------------------------------------------------------------------------
+// Emitter sampling (fspt.h FSPT_LIGHTS_EMITTERS)
+// ---------------------------------------------------------------------------
+// The diffuse and emissive layers of material texture set `set` at uv (s, t): shade_hit's taps and decode for those two layers
+FM_DEV void light_tex(const DScene &S, uint32_t set, float s, float t, V3 &td, V3 &te) {
+  const uint4 *tset = S.tex_sets + (size_t)set * 3;
+  const uint4 ts0 = tset[0], ts1 = tset[1];
+  if (ts0.x == TEXSET_CONST) {
+    td = v3(unorm8(ts1.x & 255u), unorm8((ts1.x >> 8) & 255u), unorm8((ts1.x >> 16) & 255u));
+    te = v3(unorm8(ts1.y & 255u), unorm8((ts1.y >> 8) & 255u), unorm8((ts1.y >> 16) & 255u));
+    return;
+  }
+  const TexCoord tc = bilinear_coord((int)S.atlas_res, (int)S.atlas_res, s, t, true);
+  Tap4 qd, qe;
+  if (ts0.x == TEXSET_QUAD) {
+    const uint4 *img = S.atlas4 + (size_t)ts0.y * 8u;
+    const int tiles_x = ((int)S.atlas_res + 3) >> 2;
+    const uint4 t00 = img[tile_offset<2, 1>(tc.i0, tc.j0, tiles_x)], t10 = img[tile_offset<2, 1>(tc.i1, tc.j0, tiles_x)];
+    const uint4 t01 = img[tile_offset<2, 1>(tc.i0, tc.j1, tiles_x)], t11 = img[tile_offset<2, 1>(tc.i1, tc.j1, tiles_x)];
+    qd = Tap4{t00.x, t10.x, t01.x, t11.x, tc.a, tc.b};
+    qe = Tap4{t00.y, t10.y, t01.y, t11.y, tc.a, tc.b};
+  } else {
+    const uint4 ts2 = tset[2];
+    const TapGeom tg = tap_geom(tc, (int)S.atlas_res);
+    qd = layer_taps(S, tg, ts2.x, ts1.x);
+    qe = layer_taps(S, tg, ts2.y, ts1.y);
+  }
+  td = v3(tap_channel(qd, 0), tap_channel(qd, 1), tap_channel(qd, 2));
+  te = v3(tap_channel(qe, 0), tap_channel(qe, 1), tap_channel(qe, 2));
+}
+// emitted radiance 30 * texEmissive * texDiffuse (tracer.fs:467)
+FM_DEV V3 light_le(V3 td, V3 te) { return v3((te.x * td.x) * 30.0f, (te.y * td.y) * 30.0f, (te.z * td.z) * 30.0f); }
+// The point of a triangle at the warped square sample (u2, u3): barycentrics b0 = 1 - sqrt(u2), b1 = u3 sqrt(u2), b2 = the
+// rest (uniform in area); the same map places the 16 stratified points of the table's weights
+FM_DEV void tri_point(float u2, float u3, V3 v1, V3 e1, V3 e2, float uv0x, float uv0y, float uv1x, float uv1y, float uv2x,
+                      float uv2y, V3 &x, float &s, float &t) {
+  const float su = sqrt_(u2), b1 = u3 * su, b2 = su - b1, b0 = 1.0f - su;
+  x = vfma(e2, b2, vfma(e1, b1, v1));
+  s = fma_(b2, uv2x, fma_(b1, uv1x, b0 * uv0x));
+  t = fma_(b2, uv2y, fma_(b1, uv1y, b0 * uv0y));
+}
+// One emitter sample seen from ro: entry e (alias table: slot floor(u1 n), coin = the fraction), the point x on its
+// triangle, the unit direction w from ro, the distance, pdf_L = p_e dist^2 / (A |cos_l|) (solid angle; 0 when the
+// triangle is seen edge-on) and Le
+struct LightSample { uint32_t e; V3 x, w, le; float dist, pdf; };
+FM_DEV void light_sample(const DScene &S, V3 ro, float u1, float u2, float u3, LightSample &ls) {
+  const float fn = u1 * (float)S.n_lights;
+  uint32_t i = (uint32_t)fn;
+  if (i > S.n_lights - 1u) i = S.n_lights - 1u;
+  const uint2 al = S.light_alias[i];
+  ls.e = (fn - (float)i) < __uint_as_float(al.x) ? i : al.y;
+  const float4 *r = S.light_rec + (size_t)ls.e * 4u;
+  const float4 a = r[0], b = r[1], c = r[2], d = r[3];
+  const V3 v1 = v3(a.x, a.y, a.z), e1 = v3(a.w, b.x, b.y), e2 = v3(b.z, b.w, c.x);
+  float s, t;
+  tri_point(u2, u3, v1, e1, e2, c.y, c.z, c.w, d.x, d.y, d.z, ls.x, s, t);
+  V3 td, te;
+  light_tex(S, __float_as_uint(d.w), s, t, td, te);
+  ls.le = light_le(td, te);
+  const V3 dv = ls.x - ro;
+  const float d2 = dot(dv, dv);
+  ls.dist = sqrt_(d2);
+  ls.w = dv * (1.0f / ls.dist);
+  const float gl = abs_(dot(cross(e1, e2), ls.w)); // 2 A |cos_l|
+  ls.pdf = gl > 0.0f ? ((S.light_p[ls.e] * d2) * 2.0f) / gl : 0.0f;
+}
+// The emitter shadow ray ends this much short of the light point (relative: t < dist * LIGHT_T_SCALE), so the emitter
+// itself - and a surface it lies flush against or touches - does not occlude it
+constexpr float LIGHT_T_SCALE = 1.0f - 1.0e-4f;
+
+// ---------------------------------------------------------------------------
 // camera.fs main (37-46) for pixel (x, y); SMP_SOBOL: sample `sample` of the sampler seeded `sseed`, dims 0..3
 // ---------------------------------------------------------------------------
 template <int SMP>
@@ -655,15 +726,20 @@ struct Path {
   bool hasShadow;
   bool primary;   // pending ray is the camera ray
   uint32_t lag;   // rounds the path has lagged behind its generation because a traversal of it was suspended (<= WF_LAG_MAX)
-  uint32_t dim;   // SMP_SOBOL: sampler dimensions the sample has used (4 after the camera ray; always even, <= 4 + 8 * MAX_PATH_ITERS)
+  uint32_t dim;   // SMP_SOBOL: sampler dimensions the sample has used (4 after the camera ray; always even, <= 4 + 12 * MAX_PATH_ITERS)
+  float lq;       // LIGHTS: q / pb of the vertex that cast the pending extension ray (0: its hit gets emission weight 1)
+  float lt;       // LIGHTS: t bound of the pending shadow ray (MAX_T: environment, below: an emitter point)
 };
 
 // tracer.fs:447-499: shade the hit (t, tri) of ray (ro, rd); sets up the next
 // shadow + extension rays in `ps`.
 // SMP_SOBOL: ps.pix is the full-target pixel, `sample` the tick, `sseed` the sampler seed (randBase is unused)
-template <bool COUNT, int SMP>
+// LIGHTS (FSPT_LIGHTS_EMITTERS): the emission of the hit is MIS-weighted against emitter sampling at the
+// previous vertex (ps.lq), and a vertex with q > 0 may spend its shadow ray on an emitter; lightQ = the scene's q,
+// numBounces decides whether the extension ray's hit will be shaded
+template <bool COUNT, int SMP, bool LIGHTS = false>
 FM_DEV void shade_hit(const DScene &S, Path &ps, float tHit, int ti, float randBase, uint32_t sseed, uint32_t sample,
-                      float envTheta, Counters &cnt) {
+                      float envTheta, Counters &cnt, float lightQ = 0.0f, uint32_t numBounces = 0u) {
   if (COUNT) cnt.shades++;
   const float4 *hp = S.hitrec + (size_t)ti * HITREC_F4; // 192 B = 3 whole cache lines
   const float4 h0 = hp[0], h1 = hp[1], h2 = hp[2], h3 = hp[3], h4 = hp[4], h5 = hp[5], h6 = hp[6], h7 = hp[7], h8 = hp[8],
@@ -758,9 +834,26 @@ FM_DEV void shade_hit(const DScene &S, Path &ps, float tHit, int ti, float randB
   V3 ro = origin + off;
 
   V3 thr = ps.thr;
+  if constexpr (LIGHTS) {
+    // balance heuristic against the emitter strategy of the previous vertex: pb^2 / (pb^2 + (q pick t^2 / (A |cos_l|))^2);
+    // exactly 1 (x 1.0f: the reference's bits) after a camera ray or a vertex with q = 0, and on a triangle with pick 0
+    float emw = 1.0f;
+    if (ps.lq > 0.0f) {
+      const float pk = S.light_pick[ti];
+      if (pk > 0.0f) {
+        const float den = 0.5f * abs_(dot(cross(e1, e2), rd)); // A |cos_l|
+        const float x = den > 0.0f ? ((ps.lq * pk) * (tHit * tHit)) / den : __builtin_inff();
+        emw = 1.0f / fma_(x, x, 1.0f);
+      }
+    }
+    ps.color = v3(fma_(((thr.x * texEmissive.x) * texDiffuse.x) * emw, 30.0f, ps.color.x),
+                  fma_(((thr.y * texEmissive.y) * texDiffuse.y) * emw, 30.0f, ps.color.y),
+                  fma_(((thr.z * texEmissive.z) * texDiffuse.z) * emw, 30.0f, ps.color.z));
+  } else {
   ps.color = v3(fma_((thr.x * texEmissive.x) * texDiffuse.x, 30.0f, ps.color.x),
                 fma_((thr.y * texEmissive.y) * texDiffuse.y, 30.0f, ps.color.y),
                 fma_((thr.z * texEmissive.z) * texDiffuse.z, 30.0f, ps.color.z));
+  }
   V3 incident = -rd;
   V3 envThroughput, bsdfThroughput;
   float bsdfPdf;
@@ -827,6 +920,46 @@ FM_DEV void shade_hit(const DScene &S, Path &ps, float tHit, int ti, float randB
   ps.hasShadow = (dielectric < 0.0f && cosEnv > 0.0f); // tracer.fs:500
   ps.envDir = envDir;
   ps.pend = thr * envThroughput;
+  if constexpr (LIGHTS) {
+    // q: emitter NEE only where the extension ray's hit will be shaded (its emission is what the MIS weight splits) and
+    // where the BSDF estimator is f cos / pdf of the chosen lobe with that lobe's own direction density: the Lambert lobe
+    // (its direction does not depend on the microfacet normal the lobe choice used) and the specular lobe when it is
+    // chosen with probability 1 (metallic = 1).  Elsewhere q = 0: no extra random numbers, the reference's arithmetic.
+    const bool lobe_ok = !specular || metallic >= 1.0f;
+    const float q = (lightQ > 0.0f && S.n_lights > 0u && lobe_ok && !inside && dielectric < 0.0f &&
+                     ps.bounce + 1 < (int)numBounces && ps.iters + 1 < MAX_PATH_ITERS) ? lightQ : 0.0f;
+    ps.lq = 0.0f;
+    ps.lt = MAX_T;
+    if (q > 0.0f) {
+      const float u0 = rng.next(), u1 = rng.next(), u2 = rng.next(), u3 = rng.next();
+      ps.lq = bsdfPdf > 0.0f ? q / bsdfPdf : 0.0f;
+      if (u0 < q) { // an emitter: thr f(w) Le cos w_L / (q pdf_L)
+        LightSample ls;
+        light_sample(S, ro, u1, u2, u3, ls);
+        const float cn = dot(macroNormal, ls.w);
+        V3 f;
+        float pB;
+        if (specular) {
+          f = eval_specular(incident, macroNormal, texDiffuse, metallic, rough, ls.w);
+          pB = gtr2_pdf(incident, macroNormal, rough, ls.w);
+        } else {
+          f = v3(texDiffuse.x * INV_PI_F, texDiffuse.y * INV_PI_F, texDiffuse.z * INV_PI_F);
+          pB = abs_(cn) * INV_PI_F;
+        }
+        const float qp = q * ls.pdf, a2 = qp * qp;
+        const float sc = ((cn * a2) / fma_(pB, pB, a2)) / qp; // cos w_L / (q pdf_L)
+        ps.hasShadow = cn > 0.0f && ls.pdf > 0.0f && sc < __builtin_inff();
+        ps.envDir = ls.w;
+        ps.pend = v3(((thr.x * f.x) * ls.le.x) * sc, ((thr.y * f.y) * ls.le.y) * sc, ((thr.z * f.z) * ls.le.z) * sc);
+        ps.wx = 1.0f;
+        ps.lt = ls.dist * LIGHT_T_SCALE;
+      } else { // the environment: the reference's NEE / (1 - q)
+        const float sc = ps.wx / (1.0f - q);
+        ps.pend = v3(ps.pend.x * sc, ps.pend.y * sc, ps.pend.z * sc);
+        ps.wx = 1.0f;
+      }
+    }
+  }
   ps.ro = ro;
   ps.rd = rd;
   // tracer.fs:508: accumulatedReflectance *= bsdfThroughput happens after both traces; the
@@ -844,11 +977,11 @@ FM_DEV void shade_hit(const DScene &S, Path &ps, float tHit, int ti, float randB
 // then holds the un-clamped sample colour.  Shared by the megakernel and the wavefront
 // pipeline so both run the same arithmetic in the same order.
 // ... its first half: everything but the shading of a live hit.  Returns true when the path is finished.
-template <bool COUNT>
+template <bool COUNT, bool LIGHTS = false>
 FM_DEV bool consume_rays(const DScene &S, Path &ps, int hitA, int hitB, float envTheta, uint32_t numBounces, Counters &cnt) {
-  // NEE result (tracer.fs:500-505)
+  // NEE result (tracer.fs:500-505; LIGHTS: an emitter shadow ray - bound below MAX_T - carries its whole contribution in pend)
   if (ps.hasShadow && hitA == -1) {
-    V3 es = env_sample<COUNT>(S, ps.envDir, envTheta, cnt);
+    V3 es = (LIGHTS && ps.lt < MAX_T) ? v3(1.0f, 1.0f, 1.0f) : env_sample<COUNT>(S, ps.envDir, envTheta, cnt);
     ps.color = v3(fma_(ps.pend.x * es.x, ps.wx, ps.color.x), fma_(ps.pend.y * es.y, ps.wx, ps.color.y),
                   fma_(ps.pend.z * es.z, ps.wx, ps.color.z));
   }
@@ -865,11 +998,11 @@ FM_DEV bool consume_rays(const DScene &S, Path &ps, int hitA, int hitB, float en
   if (ps.bounce >= (int)numBounces || ps.iters >= MAX_PATH_ITERS) return true; // tracer.fs:446 bound, live hit
   return false;
 }
-template <bool COUNT, int SMP>
+template <bool COUNT, int SMP, bool LIGHTS = false>
 FM_DEV bool advance_path(const DScene &S, Path &ps, int hitA, float tB, int hitB, float randBase, uint32_t sseed,
-                         uint32_t sample, float envTheta, uint32_t numBounces, Counters &cnt) {
-  if (consume_rays<COUNT>(S, ps, hitA, hitB, envTheta, numBounces, cnt)) return true;
-  shade_hit<COUNT, SMP>(S, ps, tB, hitB, randBase, sseed, sample, envTheta, cnt);
+                         uint32_t sample, float envTheta, uint32_t numBounces, Counters &cnt, float lightQ = 0.0f) {
+  if (consume_rays<COUNT, LIGHTS>(S, ps, hitA, hitB, envTheta, numBounces, cnt)) return true;
+  shade_hit<COUNT, SMP, LIGHTS>(S, ps, tB, hitB, randBase, sseed, sample, envTheta, cnt, lightQ, numBounces);
   return false;
 }
 
@@ -911,7 +1044,7 @@ FM_DEV uint32_t wf_work_index(const WfP &p, uint32_t g) { return g / p.n_batch; 
 // ---------------------------------------------------------------------------
 // The path-trace kernel: tracer.fs main() (436-518) over the whole frame.
 // ---------------------------------------------------------------------------
-template <bool GEN_RAYS, bool COUNT, int SMP>
+template <bool GEN_RAYS, bool COUNT, int SMP, bool LIGHTS = false>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_trace(const TraceP p) {
   extern __shared__ int lds_stack[];
   const int lane = threadIdx.x & (WAVE - 1);
@@ -928,6 +1061,8 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_trace(const TraceP p) {
   ps.iters = 0;
   ps.wx = ps.wy = 0.0f;
   ps.lag = 0u;
+  ps.lq = 0.0f;
+  ps.lt = MAX_T;
   ps.ro = ps.rd = ps.thr = ps.color = ps.envDir = ps.pend = v3(0.0f, 0.0f, 0.0f);
 
   // traversal results of the previous T phase
@@ -942,7 +1077,8 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_trace(const TraceP p) {
     // ================= S phase =================
     bool need_pixel = (ps.pix < 0);
     if (ps.pix >= 0) {
-      if (advance_path<COUNT, SMP>(S, ps, hitA, tB, hitB, p.rand_base, p.smp_seed, p.tick, p.env_theta, p.num_bounces, cnt)) {
+      if (advance_path<COUNT, SMP, LIGHTS>(S, ps, hitA, tB, hitB, p.rand_base, p.smp_seed, p.tick, p.env_theta, p.num_bounces, cnt,
+                                           p.light_q)) {
         p.accum[ps.pix] = accumulate_sample(p.accum[ps.pix], ps.color, p.tick);
         ps.pix = -1;
         need_pixel = true;
@@ -983,6 +1119,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_trace(const TraceP p) {
           ps.bounce = 0;
           ps.iters = 0;
           ps.dim = 4u;
+          ps.lq = 0.0f;
           ps.primary = true;
           ps.hasShadow = false;
           need_pixel = false;
@@ -994,7 +1131,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_trace(const TraceP p) {
 
     // ================= T phase =================
     if (ps.pix >= 0) {
-      trace_rays<COUNT, false>(S, stack, ps.ro, ps.hasShadow, ps.envDir, ps.rd, hitA, tB, hitB, cnt);
+      trace_rays<COUNT, false>(S, stack, ps.ro, ps.hasShadow, ps.envDir, ps.rd, hitA, tB, hitB, cnt, LIGHTS ? ps.lt : MAX_T);
     }
   }
 
@@ -1089,30 +1226,34 @@ FM_DEV uint32_t lane_rank(unsigned long long m) {
 }
 
 // ---- path state <-> registers ---------------------------------------------------------------
-template <int SMP>
+template <int SMP, bool LIGHTS = false>
 FM_DEV uint32_t pack_flags(const Path &ps, bool col_zero) {
   uint32_t f = ((uint32_t)ps.bounce & 255u) | (((uint32_t)ps.iters & 255u) << 8) | (ps.primary ? WF_FLAG_PRIMARY : 0u) |
                (ps.hasShadow ? WF_FLAG_SHADOW : 0u) | (col_zero ? WF_FLAG_COLZERO : 0u) | ((ps.lag & WF_LAG_MASK) << WF_LAG_SHIFT);
   if constexpr (SMP == SMP_SOBOL) f |= (ps.dim >> 1) << WF_DIM_SHIFT;
+  if constexpr (LIGHTS) f |= ps.lq > 0.0f ? WF_FLAG_LQ : 0u;
   return f;
 }
 // state of a surviving path -> index k of `o`; the colour array is only written while the colour is non-zero
 // (it is +0 until the first light arrives), D / P only when the path has a NEE shadow ray.  SMP_SOBOL: the colour entry
 // is always written and carries the path's pixel in .w (the stream scheduler's slot ids do not determine it)
-template <int SMP>
+// LIGHTS: P.w = the shadow ray's bound; a path with q / pb > 0 (flag WF_FLAG_LQ) writes D / P in any case, D.w = q / pb
+// (its weights.x is 1 then: shade_hit folded it into pend)
+template <int SMP, bool LIGHTS = false>
 FM_DEV void store_path(const WfSet &o, uint32_t k, const Path &ps, uint32_t slot) {
   const bool col_zero = SMP == SMP_REF && ps.color.x == 0.0f && ps.color.y == 0.0f && ps.color.z == 0.0f;
+  const bool lq = LIGHTS && ps.lq > 0.0f;
   st4(o.A + k, make_float4(ps.ro.x, ps.ro.y, ps.ro.z, __uint_as_float(slot)));
-  st4(o.B + k, make_float4(ps.rd.x, ps.rd.y, ps.rd.z, __uint_as_float(pack_flags<SMP>(ps, col_zero))));
+  st4(o.B + k, make_float4(ps.rd.x, ps.rd.y, ps.rd.z, __uint_as_float(pack_flags<SMP, LIGHTS>(ps, col_zero))));
   st4(o.C + k, make_float4(ps.thr.x, ps.thr.y, ps.thr.z, ps.wy));
   if (!col_zero) st4(o.E + k, make_float4(ps.color.x, ps.color.y, ps.color.z, SMP == SMP_SOBOL ? __uint_as_float((uint32_t)ps.pix) : 0.0f));
-  if (ps.hasShadow) {
-    st4(o.D + k, make_float4(ps.envDir.x, ps.envDir.y, ps.envDir.z, ps.wx));
-    st4(o.P + k, make_float4(ps.pend.x, ps.pend.y, ps.pend.z, 0.0f));
+  if (ps.hasShadow || lq) {
+    st4(o.D + k, make_float4(ps.envDir.x, ps.envDir.y, ps.envDir.z, lq ? ps.lq : ps.wx));
+    st4(o.P + k, make_float4(ps.pend.x, ps.pend.y, ps.pend.z, LIGHTS ? ps.lt : 0.0f));
   }
 }
 // path k of `in` with the traversal results of its rays; returns the slot
-template <int SMP>
+template <int SMP, bool LIGHTS = false>
 FM_DEV uint32_t load_path(const WfSet &in, uint32_t k, Path &ps, const int *shadow_hit, int &hitA) {
   const float4 ro = ld4(in.A + k), rd = ld4(in.B + k), th = ld4(in.C + k);
   const uint32_t flags = __float_as_uint(rd.w);
@@ -1124,7 +1265,7 @@ FM_DEV uint32_t load_path(const WfSet &in, uint32_t k, Path &ps, const int *shad
   ps.wy = th.w;
   ps.color = v3(co.x, co.y, co.z);
   ps.bounce = (int)(flags & 255u);
-  ps.iters = (int)((flags >> 8) & 255u);
+  ps.iters = (int)((flags >> 8) & (LIGHTS ? 127u : 255u));
   ps.primary = (flags & WF_FLAG_PRIMARY) != 0u;
   ps.hasShadow = (flags & WF_FLAG_SHADOW) != 0u;
   ps.lag = (flags >> WF_LAG_SHIFT) & WF_LAG_MASK;
@@ -1133,13 +1274,17 @@ FM_DEV uint32_t load_path(const WfSet &in, uint32_t k, Path &ps, const int *shad
   ps.wx = 0.0f;
   ps.envDir = v3(0.0f, 0.0f, 0.0f);
   ps.pend = v3(0.0f, 0.0f, 0.0f);
+  ps.lq = 0.0f;
+  ps.lt = MAX_T;
   hitA = -1;
-  if (ps.hasShadow) {
+  const bool lq = LIGHTS && (flags & WF_FLAG_LQ) != 0u;
+  if (ps.hasShadow || lq) {
     const float4 sd = ld4(in.D + k), pe = ld4(in.P + k);
     ps.envDir = v3(sd.x, sd.y, sd.z);
-    ps.wx = sd.w;
+    ps.wx = lq ? 1.0f : sd.w;
     ps.pend = v3(pe.x, pe.y, pe.z);
-    if (shadow_hit) hitA = ldi(shadow_hit + k);
+    if constexpr (LIGHTS) { ps.lq = lq ? sd.w : 0.0f; ps.lt = pe.w; }
+    if (ps.hasShadow && shadow_hit) hitA = ldi(shadow_hit + k);
   }
   return __float_as_uint(ro.w);
 }
@@ -1155,7 +1300,7 @@ FM_DEV void carry_path(const WfSet &in, const WfSet &o, uint32_t i, uint32_t k) 
   st4(o.A + k, a);
   st4(o.C + k, c);
   if (!(fl & WF_FLAG_COLZERO)) st4(o.E + k, ld4(in.E + i));
-  if (fl & WF_FLAG_SHADOW) { st4(o.D + k, ld4(in.D + i)); st4(o.P + k, ld4(in.P + i)); }
+  if (fl & (WF_FLAG_SHADOW | WF_FLAG_LQ)) { st4(o.D + k, ld4(in.D + i)); st4(o.P + k, ld4(in.P + i)); } // (WF_FLAG_LQ: LIGHTS paths only)
   b.w = __uint_as_float(fl);
   st4(o.B + k, b);
 }
@@ -1216,7 +1361,8 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_wf_carry(const WfP p) {
 // WIDE: the interior loop walks the two-level nodes (fspt_device.hpp "quad"): two of the reference's steps per memory
 // round trip at twice the lane-requests per fetch - for the launches that are bound by the LATENCY of their rays' dependent
 // chains (few paths; a scene that does not fit the L2), not by the request rate of the vector-memory pipeline.
-template <bool COUNT, bool ANYHIT, bool WIDE = false>
+// LIGHTS: a shadow ray's t starts at its bound (P.w: short of an emitter point, or MAX_T)
+template <bool COUNT, bool ANYHIT, bool WIDE = false, bool LIGHTS = false>
 __global__ __launch_bounds__(BLOCK_THREADS, WF_TRACE_WAVES) void k_wf_trace(const WfP p) {
   extern __shared__ int lds_stack[];
   const int lane = threadIdx.x & (WAVE - 1);
@@ -1337,6 +1483,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, WF_TRACE_WAVES) void k_wf_trace(cons
         if (!resume && (fl & WF_FLAG_SUSP)) mode = 3u;
         is_shadow = has_shadow && mode != 1u;
         t = MAX_T;
+        if (LIGHTS && is_shadow) t = st.P[k].w;
         hit = -1;
         cur = mode == 3u ? REF_SENTINEL : S.root_ref;
         sp = 0;
@@ -1351,7 +1498,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, WF_TRACE_WAVES) void k_wf_trace(cons
         }
         d = is_shadow ? v3(sd.x, sd.y, sd.z) : v3(rd.x, rd.y, rd.z);
         inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-        const bool live = (fl & 255u) < p.num_bounces && ((fl >> 8) & 255u) < (uint32_t)MAX_PATH_ITERS;
+        const bool live = (fl & 255u) < p.num_bounces && ((fl >> 8) & (LIGHTS ? 127u : 255u)) < (uint32_t)MAX_PATH_ITERS;
         // bit 29 of a path item (mode 0): the traversal may be suspended (the path has not lagged WF_LAG_MAX rounds yet)
         const bool may_susp = susp_on && ((fl >> WF_LAG_SHIFT) & WF_LAG_MASK) < WF_LAG_MAX;
         path = k | (mode << 29) | (may_susp ? (1u << 29) : 0u) | (live ? 0u : 0x80000000u);
@@ -1536,6 +1683,9 @@ FM_DEV LdsTables stage_tables(void *base, const DScene &S, const float *rb_trace
 #ifndef WF_LOGIC_WAVES
 #define WF_LOGIC_WAVES 4 // 4 waves/SIMD (<= 128 VGPRs): measured best of {3, 4, 5(39 spills)} (profiles/r01)
 #endif
+#ifndef WF_LIGHTS_WAVES
+#define WF_LIGHTS_WAVES 3 // the FSPT_LIGHTS_EMITTERS logic and tail kernels: at 128 VGPRs the emitter sample spilled 2-3 registers to scratch
+#endif
 
 template <bool COUNT>
 FM_DEV void flush_counters(const Counters &cnt, unsigned long long *counters, int first, int lane) {
@@ -1582,7 +1732,7 @@ FM_DEV void flush_counters(const Counters &cnt, unsigned long long *counters, in
 #ifndef WF_PRIMARY_SLICE
 #define WF_PRIMARY_SLICE 8u // traversal steps between two looks at the wave's sample counter
 #endif
-template <bool COUNT, bool LDSTAB, int R, bool WIDE, int SMP>
+template <bool COUNT, bool LDSTAB, int R, bool WIDE, int SMP, bool LIGHTS = false>
 __global__ __launch_bounds__(WF_PRIMARY_THREADS, WF_LOGIC_WAVES) void k_wf_primary(const WfP p) {
   extern __shared__ int lds_dyn[]; // the waves' traversal stacks | [tables] | [camera rays and hits of the block iteration]
   constexpr int NW = WF_PRIMARY_THREADS / WAVE;
@@ -1782,6 +1932,7 @@ __global__ __launch_bounds__(WF_PRIMARY_THREADS, WF_LOGIC_WAVES) void k_wf_prima
         ps.pend = v3(0.0f, 0.0f, 0.0f);
         ps.wx = ps.wy = 0.0f;
         ps.bounce = 0; ps.iters = 0; ps.pix = 0; ps.lag = 0u; ps.dim = 4u;
+        ps.lq = 0.0f; ps.lt = MAX_T;
         ps.hasShadow = false; ps.primary = true;
         const uint32_t j = (first + i) % p.n_batch;
         if constexpr (SMP == SMP_SOBOL) {
@@ -1789,9 +1940,10 @@ __global__ __launch_bounds__(WF_PRIMARY_THREADS, WF_LOGIC_WAVES) void k_wf_prima
           work_to_pixel(p, wf_work_index(p, first + i), fx, fy);
           ps.pix = (int)(fy * p.W + fx);
         }
-        const bool finished = advance_path<COUNT, SMP>(S, ps, -1, tB, hitB, s_rb[j], p.smp_seed, p.first_tick + j, p.env_theta, p.num_bounces, cnt);
+        const bool finished = advance_path<COUNT, SMP, LIGHTS>(S, ps, -1, tB, hitB, s_rb[j], p.smp_seed, p.first_tick + j, p.env_theta,
+                                                               p.num_bounces, cnt, p.light_q);
         if (finished) st3(p.fin + 3 * (size_t)slot, ps.color);
-        else store_path<SMP>(out, s_base[par] + my_off + lane_rank(m_surv[u]), ps, slot);
+        else store_path<SMP, LIGHTS>(out, s_base[par] + my_off + lane_rank(m_surv[u]), ps, slot);
       }
       my_off += (uint32_t)__popcll(m_surv[u]);
     }
@@ -1808,8 +1960,8 @@ __global__ __launch_bounds__(WF_PRIMARY_THREADS, WF_LOGIC_WAVES) void k_wf_prima
 //   2a every thread finishes its own non-shaded paths (NEE result, environment on a miss -> fin[slot]);
 //   2b the listed paths are shaded by consecutive threads - whole waves of shading work, instead of the 1-in-5 lanes
 //      a round-2 wave has when every thread keeps its own path (VALU lane utilisation 0.34 in round 1's profile).
-template <bool COUNT, bool LDSTAB, int SMP>
-__global__ __launch_bounds__(WF_LOGIC_THREADS, WF_LOGIC_WAVES) void k_wf_logic(const WfP p) {
+template <bool COUNT, bool LDSTAB, int SMP, bool LIGHTS = false>
+__global__ __launch_bounds__(WF_LOGIC_THREADS, LIGHTS ? WF_LIGHTS_WAVES : WF_LOGIC_WAVES) void k_wf_logic(const WfP p) {
   constexpr int U = WF_LOGIC_U;
   extern __shared__ int lds_dyn[]; // the staged tables
   __shared__ uint16_t s_list[U * WF_LOGIC_THREADS];
@@ -1900,13 +2052,13 @@ __global__ __launch_bounds__(WF_LOGIC_THREADS, WF_LOGIC_WAVES) void k_wf_logic(c
       if (active) {
         Path ps;
         int hitA;
-        const uint32_t slot = load_path<SMP>(in, i, ps, p.shadow_hit, hitA);
+        const uint32_t slot = load_path<SMP, LIGHTS>(in, i, ps, p.shadow_hit, hitA);
         const float2 h = ld2(p.hit + i);
         const uint32_t j = slot % p.n_batch;
-        const bool finished = advance_path<COUNT, SMP>(S, ps, hitA, h.x, __float_as_int(h.y), s_rb[j], p.smp_seed, p.first_tick + j,
-                                                       p.env_theta, p.num_bounces, cnt);
+        const bool finished = advance_path<COUNT, SMP, LIGHTS>(S, ps, hitA, h.x, __float_as_int(h.y), s_rb[j], p.smp_seed, p.first_tick + j,
+                                                               p.env_theta, p.num_bounces, cnt, p.light_q);
         if (finished) st3(p.fin + 3 * (size_t)slot, ps.color);
-        else store_path<SMP>(out, k_out, ps, slot);
+        else store_path<SMP, LIGHTS>(out, k_out, ps, slot);
       }
     }
     __syncthreads(); // s_list / s_total are rewritten by the next iteration
@@ -1955,8 +2107,8 @@ FM_DEV V3 shfl3(V3 v, int src) { return v3(__shfl(v.x, src, WAVE), __shfl(v.y, s
 // dependent chains of the paths still alive, walked by a few lanes on a mostly idle chip - there a step costs a cache-miss
 // latency, and two levels per round trip shorten the chain (profiles/r05/launch_list_*.txt: the tail launch is 0.8 ms of a
 // 9.9 ms batch on the 70 k-triangle scene, 2.4 of 13.3 ms on the 1 M-triangle one, most of it this end phase).
-template <bool COUNT, bool ANYHIT, bool GEN, int WIDE, int SMP>
-__global__ __launch_bounds__(BLOCK_THREADS, WF_TAIL_WAVES) void k_wf_tail(const WfP p) {
+template <bool COUNT, bool ANYHIT, bool GEN, int WIDE, int SMP, bool LIGHTS = false>
+__global__ __launch_bounds__(BLOCK_THREADS, LIGHTS ? WF_LIGHTS_WAVES : WF_TAIL_WAVES) void k_wf_tail(const WfP p) {
   extern __shared__ int lds_stack[];
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = wave_index();
@@ -1981,6 +2133,8 @@ __global__ __launch_bounds__(BLOCK_THREADS, WF_TAIL_WAVES) void k_wf_tail(const 
   ps.pix = -1;
   ps.hasShadow = false;
   ps.lag = 0u;
+  ps.lq = 0.0f;
+  ps.lt = MAX_T;
   ps.ro = ps.rd = ps.envDir = v3(0.0f, 0.0f, 1.0f);
   uint32_t slot = 0;
   // this lane's ray (even lanes: the path's extension ray, odd lanes: its NEE shadow ray): RAY_NONE, RAY_GOING (its
@@ -2024,7 +2178,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, WF_TAIL_WAVES) void k_wf_tail(const 
       uint32_t take = want < avail ? want : avail;
       if (is_main && ps.pix < 0 && g_w < 0 && rank < take) {
         int unused;
-        slot = load_path<SMP>(in, pool_next + rank, ps, nullptr, unused); // (ps.pix >= 0: SMP_SOBOL's pixel, else 0)
+        slot = load_path<SMP, LIGHTS>(in, pool_next + rank, ps, nullptr, unused); // (ps.pix >= 0: SMP_SOBOL's pixel, else 0)
       }
       pool_next += take;
     }
@@ -2074,6 +2228,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, WF_TAIL_WAVES) void k_wf_tail(const 
         ps.pend = v3(0.0f, 0.0f, 0.0f);
         ps.wx = ps.wy = 0.0f;
         ps.bounce = 0; ps.iters = 0; ps.dim = 4u;
+        ps.lq = 0.0f; ps.lt = MAX_T;
         ps.hasShadow = false; ps.primary = true;
         ps.pix = SMP == SMP_SOBOL ? (int)g_pix : 0;
         slot = g_j; // (only its tick is used: slot % n_batch)
@@ -2094,8 +2249,9 @@ __global__ __launch_bounds__(BLOCK_THREADS, WF_TAIL_WAVES) void k_wf_tail(const 
     const V3 o = shfl3(ps.ro, src);
     const V3 d_sh = shfl3(ps.envDir, src);
     const V3 d = is_main ? ps.rd : d_sh;
+    const float t_sh = LIGHTS ? __shfl(ps.lt, src, WAVE) : MAX_T; // (LIGHTS: the shadow ray's bound)
     if (r_state == RAY_NONE && (is_main ? pair_live : pair_shadow)) { // a new ray starts at the root
-      r_state = RAY_GOING; r_cur = S.root_ref; r_sp = 0; r_t = MAX_T; r_hit = -1;
+      r_state = RAY_GOING; r_cur = S.root_ref; r_sp = 0; r_t = is_main ? MAX_T : t_sh; r_hit = -1;
       if (COUNT) cnt.rays++;
     }
     if (r_state != RAY_GOING) r_cur = REF_SENTINEL;
@@ -2114,8 +2270,8 @@ __global__ __launch_bounds__(BLOCK_THREADS, WF_TAIL_WAVES) void k_wf_tail(const 
     const float tR = r_t;
     const int hitR = r_hit;
     if (ready) {
-      if (advance_path<COUNT, SMP>(S, ps, hitA, tR, hitR, p.rb_trace[slot % p.n_batch], p.smp_seed, p.first_tick + slot % p.n_batch,
-                                   p.env_theta, p.num_bounces, cnt)) {
+      if (advance_path<COUNT, SMP, LIGHTS>(S, ps, hitA, tR, hitR, p.rb_trace[slot % p.n_batch], p.smp_seed, p.first_tick + slot % p.n_batch,
+                                           p.env_theta, p.num_bounces, cnt, p.light_q)) {
         if (GEN && g_path) {
           g_acc = accumulate_sample(g_acc, ps.color, p.first_tick + g_j);
           g_path = false;
@@ -2568,6 +2724,47 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_atrous(const AtrousP p) {
 // ---------------------------------------------------------------------------
 // Stacks deeper than the default 64 KB of dynamic LDS (trees deeper than ~31 levels under a 512-thread block) need the
 // per-kernel opt-in; gfx950 has 160 KB per CU.
+// ---- light table (fspt_target_set_lights) ----------------------------------------------------------------
+// w = A * mean over 16 stratified points (the 4 x 4 cell centres of the warped square, tri_point) of luma(Le), Rec. 709
+__global__ __launch_bounds__(BLOCK_THREADS) void k_light_weights(const DScene S, const uint32_t *slots, uint32_t n, float *w, float4 *rec) {
+  const uint32_t i = blockIdx.x * BLOCK_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const float4 *hp = S.hitrec + (size_t)slots[i] * HITREC_F4;
+  const float4 h0 = hp[0], h1 = hp[1], h2 = hp[2], h9 = hp[9], h10 = hp[10];
+  const V3 v1 = v3(h0.x, h0.y, h0.z), e1 = v3(h0.w, h1.x, h1.y), e2 = v3(h1.z, h1.w, h2.x);
+  const uint32_t set = __float_as_uint(h10.z);
+  float sum = 0.0f;
+  for (int k = 0; k < 16; ++k) {
+    V3 x, td, te;
+    float s, t;
+    tri_point(((float)(k & 3) + 0.5f) * 0.25f, ((float)(k >> 2) + 0.5f) * 0.25f, v1, e1, e2, h9.x, h9.y, h9.z, h9.w, h10.x, h10.y, x, s, t);
+    light_tex(S, set, s, t, td, te);
+    const V3 le = light_le(td, te);
+    sum += fma_(0.0722f, le.z, fma_(0.7152f, le.y, 0.2126f * le.x));
+  }
+  const V3 cr = cross(e1, e2);
+  w[i] = (0.5f * sqrt_(dot(cr, cr))) * (sum * 0.0625f);
+  if (rec) {
+    float4 *r = rec + (size_t)i * 4u;
+    r[0] = make_float4(v1.x, v1.y, v1.z, e1.x);
+    r[1] = make_float4(e1.y, e1.z, e2.x, e2.y);
+    r[2] = make_float4(e2.z, h9.x, h9.y, h9.z);
+    r[3] = make_float4(h9.w, h10.x, h10.y, h10.z);
+  }
+}
+// test hook: light_sample for n queries (ro.xyz, n.xyz, u0..u3; u0 is the strategy value, unused here)
+__global__ __launch_bounds__(BLOCK_THREADS) void k_light_eval(const DScene S, const float *in, uint32_t n, int *entry, float *out) {
+  const uint32_t i = blockIdx.x * BLOCK_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const float *q = in + (size_t)i * 10u;
+  LightSample ls;
+  light_sample(S, v3(q[0], q[1], q[2]), q[7], q[8], q[9], ls);
+  entry[i] = (int)ls.e;
+  float *o = out + (size_t)i * 8u;
+  o[0] = ls.x.x; o[1] = ls.x.y; o[2] = ls.x.z; o[3] = ls.pdf;
+  o[4] = ls.le.x; o[5] = ls.le.y; o[6] = ls.le.z; o[7] = dot(v3(q[3], q[4], q[5]), ls.w);
+}
+
 template <class K>
 static hipError_t allow_lds(K kernel, size_t bytes) {
   if (bytes <= 48u * 1024u) return hipSuccess;
@@ -2586,16 +2783,18 @@ hipError_t launch_trace(const TraceP &p, bool gen_rays, bool count, int num_cus,
   if (grid == 0) return hipSuccess;
   dim3 g(grid), b(BLOCK_THREADS);
   hipError_t e;
-#define FSPT_LAUNCH_MEGA_S(G, C, M)                                                          \
+#define FSPT_LAUNCH_MEGA_SL(G, C, M, L)                                                      \
   do {                                                                                        \
-    if ((e = allow_lds(k_trace<G, C, M>, lds)) != hipSuccess) return e;                       \
-    hipLaunchKernelGGL((k_trace<G, C, M>), g, b, lds, stream, p);                             \
+    if ((e = allow_lds(k_trace<G, C, M, L>, lds)) != hipSuccess) return e;                    \
+    hipLaunchKernelGGL((k_trace<G, C, M, L>), g, b, lds, stream, p);                          \
   } while (0)
+#define FSPT_LAUNCH_MEGA_S(G, C, M) do { if (p.lights) FSPT_LAUNCH_MEGA_SL(G, C, M, true); else FSPT_LAUNCH_MEGA_SL(G, C, M, false); } while (0)
 #define FSPT_LAUNCH_MEGA(G, C) do { if (p.sampler) FSPT_LAUNCH_MEGA_S(G, C, SMP_SOBOL); else FSPT_LAUNCH_MEGA_S(G, C, SMP_REF); } while (0)
   if (gen_rays) { if (count) FSPT_LAUNCH_MEGA(true, true); else FSPT_LAUNCH_MEGA(true, false); }
   else { if (count) FSPT_LAUNCH_MEGA(false, true); else FSPT_LAUNCH_MEGA(false, false); }
 #undef FSPT_LAUNCH_MEGA
 #undef FSPT_LAUNCH_MEGA_S
+#undef FSPT_LAUNCH_MEGA_SL
   return hipGetLastError();
 }
 
@@ -2647,31 +2846,34 @@ hipError_t launch_wf(int kernel, const WfP &p, int count, int num_cus, hipStream
       grid = min(grid, (uint32_t)num_cus * min((uint32_t)blocks, (uint32_t)WF_TRACE_GRID_RESIDENT));
 #endif
     }
-#define FSPT_LAUNCH_TRACE(C, A, Wd)                                                                        \
+#define FSPT_LAUNCH_TRACE_L(C, A, Wd, L)                                                                   \
     do {                                                                                                     \
-      if ((e = allow_lds(k_wf_trace<C, A, Wd>, lds)) != hipSuccess) return e;                                \
-      hipLaunchKernelGGL((k_wf_trace<C, A, Wd>), dim3(grid), dim3(BLOCK_THREADS), lds, stream, q);           \
+      if ((e = allow_lds(k_wf_trace<C, A, Wd, L>, lds)) != hipSuccess) return e;                             \
+      hipLaunchKernelGGL((k_wf_trace<C, A, Wd, L>), dim3(grid), dim3(BLOCK_THREADS), lds, stream, q);        \
     } while (0)
+#define FSPT_LAUNCH_TRACE(C, A, Wd) do { if (p.lights) FSPT_LAUNCH_TRACE_L(C, A, Wd, true); else FSPT_LAUNCH_TRACE_L(C, A, Wd, false); } while (0)
     if (count == 1) FSPT_LAUNCH_TRACE(true, false, false);
     else if (count == 2) FSPT_LAUNCH_TRACE(true, true, false);
     else if (wide) FSPT_LAUNCH_TRACE(false, true, true);
     else FSPT_LAUNCH_TRACE(false, true, false);
 #undef FSPT_LAUNCH_TRACE
+#undef FSPT_LAUNCH_TRACE_L
   } else if (kernel == WF_K_TAIL) {
     // paths a block holds at a time (two lanes per path; one pair per wave when the kernel spreads a small launch's paths)
     const uint32_t per_block = WAVES_PER_BLOCK * (WF_TAIL_PAIRS_AUTO && !(p.ctl && p.finish) ? 1u : (uint32_t)WF_TAIL_PAIRS);
     uint32_t grid = min((total + per_block - 1) / per_block, (uint32_t)num_cus * (WF_TAIL_WAVES > 4 ? WF_TAIL_WAVES : 4));
     size_t lds = stack_bytes(p.scene);
-#define FSPT_LAUNCH_TAIL_S(C, A, Wd, M)                                                                       \
-    do {                                                                                                        \
-      if (p.ctl && p.finish) {                                                                                  \
-        if ((e = allow_lds(k_wf_tail<C, A, true, Wd, M>, lds)) != hipSuccess) return e;                         \
-        hipLaunchKernelGGL((k_wf_tail<C, A, true, Wd, M>), dim3(grid), dim3(BLOCK_THREADS), lds, stream, p);    \
-      } else {                                                                                                  \
-        if ((e = allow_lds(k_wf_tail<C, A, false, Wd, M>, lds)) != hipSuccess) return e;                        \
-        hipLaunchKernelGGL((k_wf_tail<C, A, false, Wd, M>), dim3(grid), dim3(BLOCK_THREADS), lds, stream, p);   \
-      }                                                                                                         \
+#define FSPT_LAUNCH_TAIL_SL(C, A, Wd, M, L)                                                                      \
+    do {                                                                                                           \
+      if (p.ctl && p.finish) {                                                                                     \
+        if ((e = allow_lds(k_wf_tail<C, A, true, Wd, M, L>, lds)) != hipSuccess) return e;                         \
+        hipLaunchKernelGGL((k_wf_tail<C, A, true, Wd, M, L>), dim3(grid), dim3(BLOCK_THREADS), lds, stream, p);    \
+      } else {                                                                                                     \
+        if ((e = allow_lds(k_wf_tail<C, A, false, Wd, M, L>, lds)) != hipSuccess) return e;                        \
+        hipLaunchKernelGGL((k_wf_tail<C, A, false, Wd, M, L>), dim3(grid), dim3(BLOCK_THREADS), lds, stream, p);   \
+      }                                                                                                            \
     } while (0)
+#define FSPT_LAUNCH_TAIL_S(C, A, Wd, M) do { if (p.lights) FSPT_LAUNCH_TAIL_SL(C, A, Wd, M, true); else FSPT_LAUNCH_TAIL_SL(C, A, Wd, M, false); } while (0)
 #define FSPT_LAUNCH_TAIL(C, A, Wd) do { if (p.sampler) FSPT_LAUNCH_TAIL_S(C, A, Wd, SMP_SOBOL); else FSPT_LAUNCH_TAIL_S(C, A, Wd, SMP_REF); } while (0)
     if (count == 1) FSPT_LAUNCH_TAIL(true, false, 0);
     else if (count == 2) FSPT_LAUNCH_TAIL(true, true, 0);
@@ -2680,6 +2882,7 @@ hipError_t launch_wf(int kernel, const WfP &p, int count, int num_cus, hipStream
     else FSPT_LAUNCH_TAIL(false, true, 0);
 #undef FSPT_LAUNCH_TAIL
 #undef FSPT_LAUNCH_TAIL_S
+#undef FSPT_LAUNCH_TAIL_SL
   } else if (kernel == WF_K_LOGIC || kernel == WF_K_PRIMARY) {
     // resident blocks per CU at WF_LOGIC_WAVES waves per SIMD (4 SIMDs): 2 blocks of 512 threads at 4 waves; twice that many in flight
     const uint32_t threads = kernel == WF_K_PRIMARY ? (uint32_t)WF_PRIMARY_THREADS : (uint32_t)WF_LOGIC_THREADS;
@@ -2693,11 +2896,12 @@ hipError_t launch_wf(int kernel, const WfP &p, int count, int num_cus, hipStream
     if (kernel == WF_K_PRIMARY) {
       const size_t dyn = (size_t)(WF_PRIMARY_THREADS / WAVE) * p.scene.stack_n * WAVE * sizeof(int) + (tab ? tab_bytes : 0u) +
                          (prim_r > 1u ? (size_t)prim_r * WF_PRIMARY_THREADS * 32u : 0u); // + ray and hit of every sample of a block iteration
-#define FSPT_LAUNCH_PRIMARY_S(C, T, RR, Wd, M)                                                                    \
-      do {                                                                                                          \
-        if ((e = allow_lds(k_wf_primary<C, T, RR, Wd, M>, dyn)) != hipSuccess) return e;                            \
-        hipLaunchKernelGGL((k_wf_primary<C, T, RR, Wd, M>), dim3(grid), dim3(WF_PRIMARY_THREADS), dyn, stream, p);  \
+#define FSPT_LAUNCH_PRIMARY_SL(C, T, RR, Wd, M, L)                                                                   \
+      do {                                                                                                             \
+        if ((e = allow_lds(k_wf_primary<C, T, RR, Wd, M, L>, dyn)) != hipSuccess) return e;                            \
+        hipLaunchKernelGGL((k_wf_primary<C, T, RR, Wd, M, L>), dim3(grid), dim3(WF_PRIMARY_THREADS), dyn, stream, p);  \
       } while (0)
+#define FSPT_LAUNCH_PRIMARY_S(C, T, RR, Wd, M) do { if (p.lights) FSPT_LAUNCH_PRIMARY_SL(C, T, RR, Wd, M, true); else FSPT_LAUNCH_PRIMARY_SL(C, T, RR, Wd, M, false); } while (0)
 #define FSPT_LAUNCH_PRIMARY(C, T, RR, Wd) do { if (p.sampler) FSPT_LAUNCH_PRIMARY_S(C, T, RR, Wd, SMP_SOBOL); else FSPT_LAUNCH_PRIMARY_S(C, T, RR, Wd, SMP_REF); } while (0)
 #define FSPT_LAUNCH_PRIMARY_R(C, T, Wd) do { if (prim_r > 1u) FSPT_LAUNCH_PRIMARY(C, T, 2, Wd); else FSPT_LAUNCH_PRIMARY(C, T, 1, Wd); } while (0)
       if (count) { if (tab) FSPT_LAUNCH_PRIMARY_R(true, true, false); else FSPT_LAUNCH_PRIMARY_R(true, false, false); }
@@ -2706,14 +2910,17 @@ hipError_t launch_wf(int kernel, const WfP &p, int count, int num_cus, hipStream
 #undef FSPT_LAUNCH_PRIMARY_R
 #undef FSPT_LAUNCH_PRIMARY
 #undef FSPT_LAUNCH_PRIMARY_S
+#undef FSPT_LAUNCH_PRIMARY_SL
     } else {
       const size_t dyn = tab ? tab_bytes : 0u;
-#define FSPT_LAUNCH_LOGIC_S(C, T, M) hipLaunchKernelGGL((k_wf_logic<C, T, M>), dim3(grid), dim3(WF_LOGIC_THREADS), dyn, stream, p)
+#define FSPT_LAUNCH_LOGIC_SL(C, T, M, L) hipLaunchKernelGGL((k_wf_logic<C, T, M, L>), dim3(grid), dim3(WF_LOGIC_THREADS), dyn, stream, p)
+#define FSPT_LAUNCH_LOGIC_S(C, T, M) do { if (p.lights) FSPT_LAUNCH_LOGIC_SL(C, T, M, true); else FSPT_LAUNCH_LOGIC_SL(C, T, M, false); } while (0)
 #define FSPT_LAUNCH_LOGIC(C, T) do { if (p.sampler) FSPT_LAUNCH_LOGIC_S(C, T, SMP_SOBOL); else FSPT_LAUNCH_LOGIC_S(C, T, SMP_REF); } while (0)
       if (count) { if (tab) FSPT_LAUNCH_LOGIC(true, true); else FSPT_LAUNCH_LOGIC(true, false); }
       else { if (tab) FSPT_LAUNCH_LOGIC(false, true); else FSPT_LAUNCH_LOGIC(false, false); }
 #undef FSPT_LAUNCH_LOGIC
 #undef FSPT_LAUNCH_LOGIC_S
+#undef FSPT_LAUNCH_LOGIC_SL
     }
   } else {
     uint32_t grid = min((p.work_total + BLOCK_THREADS - 1) / BLOCK_THREADS, (uint32_t)num_cus * WF_RESOLVE_BLOCKS_PER_CU);
@@ -2752,6 +2959,18 @@ hipError_t launch_draw(const float4 *acc, uint32_t W, uint32_t H, float exposure
   uint32_t n = W * H;
   hipLaunchKernelGGL(k_draw, dim3((n + BLOCK_THREADS - 1) / BLOCK_THREADS), dim3(BLOCK_THREADS), 0, stream, acc, W, H,
                      exposure, saturation, denoise, max_sigma, scale, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_light_weights(const DScene &S, const uint32_t *slots, uint32_t n, float *w, float4 *rec, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_light_weights, dim3((n + BLOCK_THREADS - 1) / BLOCK_THREADS), dim3(BLOCK_THREADS), 0, stream, S, slots, n, w, rec);
+  return hipGetLastError();
+}
+
+hipError_t launch_light_eval(const DScene &S, const float *in, uint32_t n, int *entry, float *out, hipStream_t stream) {
+  if (n == 0 || S.n_lights == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_light_eval, dim3((n + BLOCK_THREADS - 1) / BLOCK_THREADS), dim3(BLOCK_THREADS), 0, stream, S, in, n, entry, out);
   return hipGetLastError();
 }
 

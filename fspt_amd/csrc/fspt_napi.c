@@ -729,6 +729,15 @@ static napi_value SetSampler(napi_env env, napi_callback_info info) {
   FSPT_OK_OR_THROW(fspt_target_set_sampler((fspt_target *)h, kind, seed));
   return undefined(env);
 }
+/* setLights(target, mode, emitterFraction): fspt_target_set_lights (mode: FSPT_LIGHTS_OFF / FSPT_LIGHTS_EMITTERS) */
+static napi_value SetLights(napi_env env, napi_callback_info info) {
+  napi_value a[3]; void *h; int32_t mode; double f;
+  if (get_args(env, info, 3, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  NAPI_OK(napi_get_value_int32(env, a[1], &mode));
+  NAPI_OK(napi_get_value_double(env, a[2], &f));
+  FSPT_OK_OR_THROW(fspt_target_set_lights((fspt_target *)h, mode, (float)f));
+  return undefined(env);
+}
 static napi_value SetShard(napi_env env, napi_callback_info info) {
   napi_value a[4]; void *h; uint32_t s, n, tile;
   if (get_args(env, info, 4, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
@@ -1080,7 +1089,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
       {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
-      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
+      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},
       {"renderAsync", RenderAsync}, {"multiCreate", MultiCreate}, {"multiDestroy", MultiDestroy}, {"multiTarget", MultiTarget},
       {"multiCamera", MultiCamera}, {"multiTrace", MultiTrace}, {"multiRender", MultiRender}, {"multiRenderAsync", MultiRenderAsync},

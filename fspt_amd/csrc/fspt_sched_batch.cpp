@@ -18,6 +18,12 @@ void fill_trace_params(fspt_target *t, fspt::TraceP &p) {
   p.n_owned_tiles = (n_tiles > t->shard) ? (n_tiles - t->shard + t->n_shards - 1) / t->n_shards : 0;
   p.sampler = (uint32_t)t->sampler;
   p.smp_seed = t->sampler_seed;
+  // the emitter instantiations only where there is an emitter to sample (a scene without one: the default kernels, same bits)
+  p.lights = (t->lights == FSPT_LIGHTS_EMITTERS && p.scene.n_lights > 0u) ? 1u : 0u;
+  // With an environment map q stays below 1 (FSPT_LIGHTS_ENV_Q_MAX): the reference's MIS weights of a vertex are evaluated at
+  // ITS env sample and ITS BSDF sample, so they are not a partition of unity per direction, and the environment term is
+  // only unbiased while the env NEE contribution is still traced sometimes
+  p.light_q = p.lights ? (p.scene.env ? (t->emitter_fraction < FSPT_LIGHTS_ENV_Q_MAX ? t->emitter_fraction : FSPT_LIGHTS_ENV_Q_MAX) : 1.0f) : 0.0f;
 }
 
 // Records of suspended traversals: one per lane of the trace grid a launch over `max_paths` paths gets (a lane parks at
@@ -392,6 +398,7 @@ static int wf_run(fspt_target *t, fspt_target::WfLane &ln, hipStream_t st, bool 
   p.shard = tp.shard; p.n_shards = tp.n_shards; p.tile = tp.tile; p.tiles_x = tp.tiles_x; p.tiles_y = tp.tiles_y;
   p.n_owned_tiles = tp.n_owned_tiles;
   p.sampler = tp.sampler; p.smp_seed = tp.smp_seed;
+  p.lights = tp.lights; p.light_q = tp.light_q;
   const int cus = t->scene->num_cus;
   const bool gen = !rays_from_buffers;
   const uint32_t nb = cam->num_bounces;

@@ -401,6 +401,15 @@ class PathTracer {
     if (!Number.isInteger(s) || s < 0 || s > 0xFFFFFFFF) throw new RangeError('setSampler: seed must be an integer in [0, 2^32)');
     addon.setSampler(this._target, code, s);
   }
+  /** next-event estimation of emissive triangles (include/fspt.h fspt_target_set_lights, DESIGN 8.3): 'emitters' or 'off'
+   *  (default, the reference bit for bit); emitterFraction in (0, 1], default 0.5 */
+  setLights(mode, emitterFraction) {
+    const code = { off: 0, emitters: 1 }[mode === undefined ? 'emitters' : mode];
+    if (code === undefined) throw new RangeError("setLights: mode must be 'off' or 'emitters'");
+    const f = emitterFraction === undefined ? 0.5 : emitterFraction;
+    if (typeof f !== 'number' || !(f > 0 && f <= 1)) throw new RangeError('setLights: emitterFraction must be a number in (0, 1]');
+    addon.setLights(this._target, code, f);
+  }
   /** 'wavefront' (batches of ticks), 'stream' (fixed pool of live paths), 'megakernel' (include/fspt_tuning.h) */
   setPipeline(name, batch) { addon.setPipeline(this._target, pipelineCode(name), batch || 0); }
   /** traversal steps a starved trace wave walks on before it suspends its rays (0 = never; include/fspt.h) */

@@ -6,6 +6,7 @@ reference's format (scene/<name>.json with props / static_props / animated_props
     python -m fspt_amd.render --scene 'web/scene/anim_{frame}.json' --frames 0:24 --out 'out/{frame}.png'
     python -m fspt_amd.render --out bunny.png --spp 16 --atrous 5 --feature-samples 8   # guided denoiser
     python -m fspt_amd.render --out bunny.png --spp 16 --sampler sobol --sampler-seed 3  # Owen-scrambled Sobol sampler
+    python -m fspt_amd.render --scene web/scene/bunny.json --lights --emitter-fraction 0.5  # sample emissive triangles
 
 Path tracing runs in the HIP kernels (fspt_render), tone mapping in the draw.fs kernel (fspt_draw); --atrous K runs
 the guided a-trous denoiser (fspt_features + fspt_denoise, K iterations) before tone mapping (fspt_draw_denoised).
@@ -39,7 +40,14 @@ def main():
     ap.add_argument("--sampler", choices=("reference", "sobol"), default="reference",
                     help="the paths' random numbers (fspt_target_set_sampler; built-in scene)")
     ap.add_argument("--sampler-seed", type=int, default=0, help="seed of --sampler sobol, in [0, 2^32)")
+    ap.add_argument("--lights", action="store_true", help="next-event estimation of emissive triangles (fspt_target_set_lights)")
+    ap.add_argument("--emitter-fraction", type=float, default=0.5,
+                    help="with --lights: probability a vertex samples an emitter rather than the environment, in (0, 1]")
     args = ap.parse_args()
+    if not 0.0 < args.emitter_fraction <= 1.0:
+        ap.error("--emitter-fraction must lie in (0, 1]")
+    if args.emitter_fraction != 0.5 and not args.lights:
+        ap.error("--emitter-fraction needs --lights")
     if args.atrous and args.scene:
         ap.error("--atrous is available for the built-in scene")
     if args.scene and args.sampler != "reference":
@@ -50,6 +58,8 @@ def main():
         from . import scene_file as F
         spp = args.spp if "--spp" in " ".join(__import__("sys").argv) else None  # default: the scene's `samples`
         kw = dict(samples=spp, bounces=args.bounces, seed=args.seed, saturation=args.saturation, denoise=args.denoise)
+        if args.lights:
+            kw.update(lights="emitters", emitter_fraction=args.emitter_fraction)
         if args.frames:
             a, b = (int(x) for x in args.frames.split(":"))
             t0 = time.perf_counter()
@@ -70,6 +80,8 @@ def main():
     pt.set_camera(**S.BUNNY_CAMERA)
     if args.sampler != "reference":
         pt.set_sampler(args.sampler, args.sampler_seed)
+    if args.lights:
+        pt.set_lights("emitters", args.emitter_fraction)
     t0 = time.perf_counter()
     pt.render(args.spp)
     pt.sync()

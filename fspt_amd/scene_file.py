@@ -89,16 +89,19 @@ def load_scene_file(scene_path, asset_root=None, leaf_size=4):
 
 
 def render_frame(arrays, settings, width, height, samples=None, bounces=4, seed=1, saturation=1.0, denoise=False,
-                 max_sigma=3.0, device=0):
+                 max_sigma=3.0, device=0, lights=None, emitter_fraction=0.5):
     """One frame as the reference produces it in frame mode: `samples` ticks from a cleared accumulator
     (main.js:838-857; its very first, discarded tick is not reproduced), then drawQuad.  Returns
-    (rgba8 [H, W, 4] top row first - what canvas.toBlob encodes -, radiance [H, W, 4] bottom row first)."""
+    (rgba8 [H, W, 4] top row first - what canvas.toBlob encodes -, radiance [H, W, 4] bottom row first).
+    lights="emitters": next-event estimation of emissive triangles (PathTracer.set_lights)."""
     from .tracer import PathTracer
     pt = PathTracer(arrays, width, height, device=device, num_bounces=bounces)
     try:
         pt.eye, pt.dir = list(settings["eye"]), list(settings["dir"])
         pt.fovScale, pt.envTheta = settings["fov_scale"], settings["env_theta"]
         pt.lensFeatures = [settings["focus"], settings["aperture"]]
+        if lights is not None:
+            pt.set_lights(lights, emitter_fraction)
         pt.seed(seed)
         pt.render(int(samples if samples is not None else settings["samples"]))
         rgba = pt.draw(settings["exposure"], saturation, denoise, max_sigma)

@@ -42,6 +42,18 @@ def sampler_eval(seed, pixel, sample, dim, device=0):
     return out
 
 
+def light_alias_table(weights):
+    """The Vose alias table (float32 prob, uint32 alias) the light table stores for these weights (fspt_light_alias_table,
+    a pure host function: no device needed)."""
+    w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+    if w.size == 0:
+        raise ValueError("weights must not be empty")
+    prob = np.empty(w.size, np.float32)
+    alias = np.empty(w.size, np.uint32)
+    L.check(L.lib().fspt_light_alias_table(L.fptr(w), int(w.size), L.fptr(prob), L.u32ptr(alias)))
+    return prob, alias
+
+
 def _u32_array(a, name):
     a = np.asarray(a)
     if a.dtype.kind not in "iu":
@@ -61,6 +73,7 @@ def _sampler_seed(seed):
 
 PIPELINES = {"megakernel": 0, "wavefront": 1, "stream": 2}  # fspt_target_set_pipeline codes
 SAMPLERS = {"reference": 0, "sobol": 1}  # fspt_target_set_sampler codes
+LIGHTS = {"off": 0, "emitters": 1}  # fspt_target_set_lights codes
 # fspt_denoise's defaults (include/fspt.h FSPT_DENOISE_*; tests/test_denoise_cpu.py pins the two)
 DENOISE_DEFAULTS = {"iterations": 4, "sigma_color": 4.0, "sigma_normal": 32.0, "sigma_depth": 0.05}
 
@@ -91,6 +104,35 @@ class Scene:
         L.check(L.lib().fspt_intersect_form(self._h, 1 if two_level else 0, L.fptr(rays), n, L.fptr(t),
                                             idx.ctypes.data_as(C.POINTER(C.c_int32)), L.u32ptr(steps), L.u32ptr(leaves)))
         return t, idx, steps, leaves
+
+    def light_count(self):
+        """Entries of the emitter light table (fspt_scene_light_count; builds the table if no tracer has yet)."""
+        n = C.c_uint32()
+        L.check(L.lib().fspt_scene_light_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    def light_table(self):
+        """The emitter light table (fspt_scene_light_table) as a dict of numpy arrays: weights (per triangle),
+        prob, alias, tris (per entry), pick, slot_tri (per leaf slot)."""
+        nt, nl, ns = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        L.check(L.lib().fspt_scene_light_table(self._h, C.byref(nt), C.byref(nl), C.byref(ns), None, None, None, None, None, None))
+        r = {"weights": np.zeros(nt.value, np.float32), "prob": np.zeros(nl.value, np.float32),
+             "alias": np.zeros(nl.value, np.uint32), "tris": np.zeros(nl.value, np.uint32),
+             "pick": np.zeros(ns.value, np.float32), "slot_tri": np.zeros(ns.value, np.uint32)}
+        L.check(L.lib().fspt_scene_light_table(self._h, None, None, None, L.fptr(r["weights"]), L.fptr(r["prob"]),
+                                               L.u32ptr(r["alias"]), L.u32ptr(r["tris"]), L.fptr(r["pick"]),
+                                               L.u32ptr(r["slot_tri"])))
+        return r
+
+    def light_sample_eval(self, queries):
+        """The device's emitter sample for queries float32 [n, 10] = (ro.xyz, n.xyz, u0, u1, u2, u3) (fspt_light_sample_eval,
+        a test hook) -> tri int32 [n], out float32 [n, 8] = (point.xyz, pdf_L, Le.rgb, n . w)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 10)
+        tri = np.zeros(q.shape[0], np.int32)
+        out = np.zeros((q.shape[0], 8), np.float32)
+        L.check(L.lib().fspt_light_sample_eval(self._h, L.fptr(q), int(q.shape[0]), tri.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               L.fptr(out)))
+        return tri, out
 
     def two_level_nodes(self):
         """(the scene has two-level nodes, their bytes): fspt_scene_create builds them when every box of the tree is the
@@ -162,6 +204,26 @@ class PathTracer:
         if kind not in SAMPLERS:
             raise ValueError("sampler must be one of %s, got %r" % (sorted(SAMPLERS), kind))
         L.check(L.lib().fspt_target_set_sampler(self._t, SAMPLERS[kind], _sampler_seed(seed)))
+
+    def set_lights(self, mode="emitters", emitter_fraction=0.5):
+        """Next-event estimation of emissive triangles (fspt_target_set_lights): "emitters" lets a shading
+        vertex spend its shadow ray on an emitter with probability emitter_fraction (1 when the scene has no environment
+        map), MIS-weighted; "off" (the default) is the reference bit for bit.  emitter_fraction in (0, 1].  Runs the
+        recorded ticks first; does not clear the accumulator."""
+        if mode not in LIGHTS:
+            raise ValueError("lights mode must be one of %s, got %r" % (sorted(LIGHTS), mode))
+        if isinstance(emitter_fraction, bool) or not isinstance(emitter_fraction, (int, float, np.integer, np.floating)):
+            raise TypeError("emitter_fraction must be a number, got %r" % (emitter_fraction,))
+        f = float(emitter_fraction)
+        if not 0.0 < f <= 1.0:
+            raise ValueError("emitter_fraction must lie in (0, 1], got %r" % (emitter_fraction,))
+        L.check(L.lib().fspt_target_set_lights(self._t, LIGHTS[mode], f))
+
+    def get_lights(self):
+        """(mode, emitter_fraction) of fspt_target_get_lights."""
+        m, f = C.c_int(), C.c_float()
+        L.check(L.lib().fspt_target_get_lights(self._t, C.byref(m), C.byref(f)))
+        return {v: n for n, v in LIGHTS.items()}[m.value], float(f.value)
 
     def get_sampler(self):
         """(kind, seed) of fspt_target_get_sampler."""

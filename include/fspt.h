@@ -155,7 +155,7 @@ float fspt_rand_base_next(uint64_t *state);
 int fspt_target_set_viewport(fspt_target *target, uint32_t w, uint32_t h);
 enum { FSPT_SAMPLER_REFERENCE = 0, FSPT_SAMPLER_SOBOL = 1 }; /* the paths' random numbers: rnd() bit for bit (default) | Owen-scrambled Sobol (DESIGN 8.2) */
 int fspt_target_set_sampler(fspt_target *target, int sampler, uint32_t seed); int fspt_target_get_sampler(fspt_target *target, int *sampler, uint32_t *seed);
-
+enum { FSPT_LIGHTS_OFF = 0, FSPT_LIGHTS_EMITTERS = 1 }; /* NEE of emissive triangles: off (default, the reference bit for bit) | emitters (fspt_tuning.h) */ int fspt_target_set_lights(fspt_target *target, int mode, float emitter_fraction); int fspt_target_get_lights(fspt_target *target, int *mode, float *emitter_fraction); int fspt_scene_light_count(fspt_scene *scene, uint32_t *n_lights);
 /* Several GPUs (one frame cut into 32x32 tiles over the devices of a node; the reference has nothing here - README.md:28
  * lists "Tiled rendering" as a TODO): include/fspt_multi.h, included at the end of this file. */
 

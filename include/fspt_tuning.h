@@ -134,6 +134,27 @@ int fspt_math_eval(int device, int op, const float *a, const float *b, uint32_t 
  * Test hook: the FSPT_SAMPLER_SOBOL device function value(seed, pixel[i], sample[i], dim[i]) for n triples (host arrays). */
 int fspt_sampler_eval(int device, uint32_t seed, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim,
                       uint32_t n, float *out);
+/* fspt_target_set_lights (fspt.h): FSPT_LIGHTS_EMITTERS lets each shading vertex spend its shadow ray on a
+ * point of an emissive triangle (probability q = emitter_fraction, in (0, 1]; at most 0.875 with an environment map, 1
+ * when the scene has none)
+ * instead of the environment, MIS-weighted against BSDF hits on emitters: the same expected image as FSPT_LIGHTS_OFF, lower
+ * variance where geometry lights the scene.  The scene's light table is built on the first call that turns the mode on
+ * (fspt_scene_light_count: its entries - emissive triangles of non-zero estimated power - building it if needed).  Like
+ * every setter it runs the recorded ticks first and keeps the accumulator.
+ * Emitter light table, test hooks.
+ * fspt_scene_light_table: builds the table if needed and reads it back.  Sizes first (any may be NULL): triangles,
+ * entries, leaf slots; then the arrays (any may be NULL): weights[n_tris] (A * mean luma of 30 * emissive * diffuse over
+ * 16 stratified points, 0 for a triangle that emits nothing), prob[n_lights] and alias[n_lights] (the float32 Vose table),
+ * tris[n_lights] (an entry's triangle), pick[n_slots] (the probability the stored table realises for the slot's triangle,
+ * 0 outside the table), slot_tri[n_slots] (a leaf slot's triangle). */
+int fspt_scene_light_table(fspt_scene *scene, uint32_t *n_tris, uint32_t *n_lights, uint32_t *n_slots, float *weights,
+                           float *prob, uint32_t *alias, uint32_t *tris, float *pick, uint32_t *slot_tri);
+/* the device's emitter sample for n queries of 10 floats (ro.xyz, n.xyz, u0, u1, u2, u3; u0 - the strategy value - is not
+ * used): tri[i] = the sampled entry's triangle, out[8 i ..] = point.xyz, pdf_L (solid angle, realised selection
+ * probability), Le.rgb, n . w.  FSPT_E_STATE when the scene has no emitter. */
+int fspt_light_sample_eval(fspt_scene *scene, const float *in, uint32_t n, int32_t *tri, float *out);
+/* pure host function: the Vose alias table (float64, stored float32) of n weights (finite, >= 0, some > 0) */
+int fspt_light_alias_table(const float *weights, uint32_t n, float *prob, uint32_t *alias);
 
 #ifdef __cplusplus
 }

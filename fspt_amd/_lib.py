@@ -171,6 +171,9 @@ SIGNATURES = {
     "fspt_builder_commit_obj": (C.c_int, [_VP, C.POINTER(GroupMaterial), C.c_uint32]),
     "fspt_builder_normalize": (C.c_int, [_VP, C.c_double]),
     "fspt_builder_build": (C.c_int, [_VP, C.c_uint32]),
+    "fspt_builder_build_gpu": (C.c_int, [_VP, C.c_uint32, C.c_int]),
+    "fspt_builder_gpu_stats": (C.c_int, [_VP, _F, _U32, _U32]),
+    "fspt_builder_tri_order": (C.c_int, [_VP, _U32]),
     "fspt_builder_counts": (C.c_int, [_VP, _U32, _U32, _U32]),
     "fspt_builder_autofocus": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "fspt_builder_get": (C.c_int, [_VP, _F, _F, _F, _F, _F]),

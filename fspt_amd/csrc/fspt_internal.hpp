@@ -284,3 +284,18 @@ int st_ensure(fspt_target *t, fspt_target::WfLane &ln, uint32_t cap, uint32_t fi
 int st_plan(const fspt_target *t, uint32_t units, uint32_t nbt, uint32_t nb, StPlan &pl);
 int render_stream(fspt_target *t, const fspt_camera_params *cam, uint32_t first_tick, uint32_t n_ticks,
                   const float *rb_cam, const float *rb_trace, bool rays_from_buffers);
+// ---- fspt_bvh_build.hip: the GPU binned-SAH builder behind fspt_builder_build_gpu (scene_build.cpp packs its result)
+namespace fspt {
+struct BvhGpuResult {
+  std::vector<int32_t> left, right; // children per node (-1, -1: leaf); node 0 is the root, the rest in no fixed order
+  std::vector<uint32_t> lo, cnt;    // the node's triangle range [lo, lo + cnt) of `order`
+  std::vector<uint32_t> box_keys;   // 12 per node: box min.xyz max.xyz, centroid min.xyz max.xyz as ordered keys
+  std::vector<uint32_t> order;      // triangle indices in leaf order
+  float kernel_ms = 0.0f;           // first kernel to last, from events (the per-level readbacks included)
+  uint32_t launches = 0, readbacks = 0;
+};
+// n > 0 triangles of 9 finite floats, 1 <= leaf_size <= 64, device >= 0; leaves the calling thread's device as it was.
+int bvh_build_gpu(const float *verts, uint32_t n, uint32_t leaf_size, int device, BvhGpuResult &out);
+float bvh_key_float(uint32_t k);
+uint32_t bvh_max_depth(); // deepest node depth fspt_scene_create accepts: min(64, wf_max_stack_entries()) - 1
+}  // namespace fspt

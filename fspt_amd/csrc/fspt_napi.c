@@ -27,7 +27,7 @@
  * Handles are napi externals with finalizers (a dropped tracer frees its device memory when it is collected), and while
  * a renderAsync job runs every other call on its target / multi throws Error('render in flight') - see "handles" below.
  *   enableCounters(target, on) / counters(target) -> object
- *   builderCreate / builderParseObj / builderCommit / builderNormalize / builderBuild / builderAutofocus /
+ *   builderCreate / builderParseObj / builderCommit / builderNormalize / builderBuild / builderBuildGpu / builderAutofocus /
  *   builderDestroy                                                   (native obj_loader.js + bvh.js, 1:1 fspt_builder_*)
  *   envBins(Uint8Array rgbe, w, h) -> Uint32Array                    (native env_sampler.js)
  *   sceneDestroy / targetDestroy / deviceCount / abiVersion / setTextureInterleaveBudget
@@ -1006,16 +1006,10 @@ static napi_value BuilderNormalize(napi_env env, napi_callback_info info) {
   FSPT_OK_OR_THROW(fspt_builder_normalize((fspt_builder *)h, size));
   return undefined(env);
 }
-/* builderBuild(b, leafSize) -> {bvh,tri,mat,norm,uv: Float32Array, depth} */
-static napi_value BuilderBuild(napi_env env, napi_callback_info info) {
-  napi_value a[2]; void *h; uint32_t leaf = 4;
-  if (get_args(env, info, 2, a)) return NULL;
-  if (unwrap_k(env, a[0], H_BUILDER, &h)) return NULL;
-  NAPI_OK(napi_get_value_uint32(env, a[1], &leaf));
-  fspt_builder *b = (fspt_builder *)h;
-  FSPT_OK_OR_THROW(fspt_builder_build(b, leaf));
+/* the built tree's arrays: {bvh,tri,mat,norm,uv: Float32Array, depth} */
+static napi_value builder_arrays(napi_env env, fspt_builder *b) {
   uint32_t nn, nt, depth;
-  fspt_builder_counts(b, &nn, &nt, &depth);
+  FSPT_OK_OR_THROW(fspt_builder_counts(b, &nn, &nt, &depth));
   float *bvh, *tri, *mat, *norm, *uv;
   napi_value o, v;
   napi_create_object(env, &o);
@@ -1027,6 +1021,25 @@ static napi_value BuilderBuild(napi_env env, napi_callback_info info) {
   napi_set_named_property(env, o, "norm", tn); napi_set_named_property(env, o, "uv", tu);
   napi_create_uint32(env, depth, &v); napi_set_named_property(env, o, "depth", v);
   return o;
+}
+/* builderBuild(b, leafSize) -> {bvh,tri,mat,norm,uv: Float32Array, depth} */
+static napi_value BuilderBuild(napi_env env, napi_callback_info info) {
+  napi_value a[2]; void *h; uint32_t leaf = 4;
+  if (get_args(env, info, 2, a)) return NULL;
+  if (unwrap_k(env, a[0], H_BUILDER, &h)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[1], &leaf));
+  FSPT_OK_OR_THROW(fspt_builder_build((fspt_builder *)h, leaf));
+  return builder_arrays(env, (fspt_builder *)h);
+}
+/* builderBuildGpu(b, leafSize, device) -> the same, from the binned-SAH tree built on `device` */
+static napi_value BuilderBuildGpu(napi_env env, napi_callback_info info) {
+  napi_value a[3]; void *h; uint32_t leaf = 4; int32_t device = 0;
+  if (get_args(env, info, 3, a)) return NULL;
+  if (unwrap_k(env, a[0], H_BUILDER, &h)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[1], &leaf));
+  NAPI_OK(napi_get_value_int32(env, a[2], &device));
+  FSPT_OK_OR_THROW(fspt_builder_build_gpu((fspt_builder *)h, leaf, device));
+  return builder_arrays(env, (fspt_builder *)h);
 }
 /* builderAutofocus(b, eye[3], dir[3]) -> distance (shootAutoFocusRay, main.js:447-546) */
 static napi_value BuilderAutofocus(napi_env env, napi_callback_info info) {
@@ -1096,7 +1109,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"multiClear", MultiClear}, {"multiSync", MultiSync}, {"multiSetExchange", MultiSetExchange}, {"multiGetExchange", MultiGetExchange}, {"multiLastStageMs", MultiLastStageMs}, {"multiReadRadiance", MultiReadRadiance}, {"multiDraw", MultiDraw},
       {"enableCounters", EnableCounters}, {"counters", GetCounters}, {"builderCreate", BuilderCreate}, {"builderDestroy", BuilderDestroy},
       {"builderParseObj", BuilderParseObj}, {"builderCommit", BuilderCommit}, {"builderNormalize", BuilderNormalize},
-      {"builderBuild", BuilderBuild}, {"builderAutofocus", BuilderAutofocus}, {"envBins", EnvBins},
+      {"builderBuild", BuilderBuild}, {"builderBuildGpu", BuilderBuildGpu}, {"builderAutofocus", BuilderAutofocus}, {"envBins", EnvBins},
       {"randBaseNext", RandBaseNext}, {"deviceCount", DeviceCount}, {"deviceMemory", DeviceMemory}, {"abiVersion", AbiVersion}};
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
     napi_value f;

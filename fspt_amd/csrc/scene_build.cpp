@@ -12,6 +12,7 @@
 //   env_sampler.js:1-74   ProcessEnvRadiance (importance bins)
 // Build with -ffp-contract=off: JS never fuses a*b+c.
 #include "../../include/fspt.h"
+#include "fspt_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -21,8 +22,6 @@
 #include <map>
 #include <string>
 #include <vector>
-
-void fspt_set_error(const char *fmt, ...);
 
 namespace {
 
@@ -155,6 +154,10 @@ struct fspt_builder {
   struct HostNode { Box box; int left, right; uint32_t lo, hi; bool leaf; };
   std::vector<HostNode> host_nodes;
   std::vector<uint32_t> tri_order;
+  // the last fspt_builder_build_gpu (fspt_builder_gpu_stats); gpu_built is false after fspt_builder_build
+  bool gpu_built = false;
+  float gpu_kernel_ms = 0.0f;
+  uint32_t gpu_launches = 0, gpu_readbacks = 0;
 };
 
 namespace {
@@ -535,6 +538,58 @@ struct BvhBuilder {
   }
 };
 
+// packing loops, main.js:360-392, shared by both builders.  `nodes` in pre-order (serializeTree, bvh.js:33-50), a leaf's
+// triangles are order[lo..hi); fbox: the float32 boxes to store (6 per node), or NULL for (float) of the float64 boxes.
+void pack_tree(fspt_builder *b, const std::vector<BuildNode> &nodes, const std::vector<uint32_t> &order, const float *fbox,
+               uint32_t depth) {
+  size_t nn = nodes.size(), nt = b->geometry.size();
+  b->bvh.assign(nn * 9, 0.0f);
+  b->tri.clear(); b->mat.clear(); b->norm.clear(); b->uv.clear();
+  b->tri.reserve(nt * 9); b->mat.reserve(nt * 12); b->norm.reserve(nt * 27); b->uv.reserve(nt * 6);
+  for (size_t i = 0; i < nn; ++i) {
+    const BuildNode &nd = nodes[i];
+    int32_t w[3];
+    // leaf children are JS `undefined` -> Int32Array 0 (maskBVHBuffer, main.js:272-282)
+    w[0] = nd.leaf ? 0 : nd.left;
+    w[1] = nd.leaf ? 0 : nd.right;
+    w[2] = nd.leaf ? (int32_t)(b->tri.size() / 9) : -1;
+    std::memcpy(&b->bvh[i * 9], w, 12);
+    if (fbox) {
+      std::memcpy(&b->bvh[i * 9 + 3], fbox + i * 6, 24);
+    } else {
+      b->bvh[i * 9 + 3] = (float)nd.box.mn.x; b->bvh[i * 9 + 4] = (float)nd.box.mn.y; b->bvh[i * 9 + 5] = (float)nd.box.mn.z;
+      b->bvh[i * 9 + 6] = (float)nd.box.mx.x; b->bvh[i * 9 + 7] = (float)nd.box.mx.y; b->bvh[i * 9 + 8] = (float)nd.box.mx.z;
+    }
+    if (nd.leaf) {
+      for (uint32_t k = nd.lo; k < nd.hi; ++k) {  // getTriangles = indices[0] order
+        const Tri &t = b->geometry[order[k]];
+        for (int v = 0; v < 3; ++v) {
+          b->tri.push_back((float)t.v[v].x); b->tri.push_back((float)t.v[v].y); b->tri.push_back((float)t.v[v].z);
+        }
+        for (int q = 0; q < 12; ++q) b->mat.push_back((float)t.mat[q]);
+        for (int v = 0; v < 3; ++v) {
+          D3 tg = t.tangents.size() > (size_t)v ? t.tangents[v] : d3(NAN, NAN, NAN);
+          D3 bt = t.bitangents.size() > (size_t)v ? t.bitangents[v] : d3(NAN, NAN, NAN);
+          b->norm.push_back((float)t.n[v].x); b->norm.push_back((float)t.n[v].y); b->norm.push_back((float)t.n[v].z);
+          b->norm.push_back((float)tg.x); b->norm.push_back((float)tg.y); b->norm.push_back((float)tg.z);
+          b->norm.push_back((float)bt.x); b->norm.push_back((float)bt.y); b->norm.push_back((float)bt.z);
+        }
+        for (int v = 0; v < 3; ++v) { b->uv.push_back((float)t.uv[v][0]); b->uv.push_back((float)t.uv[v][1]); }
+      }
+    }
+  }
+  b->n_nodes = (uint32_t)nn;
+  b->n_tris = (uint32_t)nt;
+  b->depth = depth;
+  b->host_nodes.resize(nn);
+  for (size_t i = 0; i < nn; ++i) {
+    const BuildNode &nd = nodes[i];
+    b->host_nodes[i] = fspt_builder::HostNode{nd.box, nd.left, nd.right, nd.lo, nd.hi, nd.leaf};
+  }
+  b->tri_order = order;
+  b->built = true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -627,49 +682,116 @@ int fspt_builder_build(fspt_builder *b, uint32_t leaf_size) {
     fspt_set_error("fspt_builder_build: SAH found no valid split (degenerate geometry); bvh.js would not terminate");
     return FSPT_E_INVALID;
   }
-  // packing loops, main.js:360-392.  Node order is already pre-order (serializeTree, bvh.js:33-50).
-  size_t nn = bb.nodes.size(), nt = b->geometry.size();
-  b->bvh.assign(nn * 9, 0.0f);
-  b->tri.clear(); b->mat.clear(); b->norm.clear(); b->uv.clear();
-  b->tri.reserve(nt * 9); b->mat.reserve(nt * 12); b->norm.reserve(nt * 27); b->uv.reserve(nt * 6);
-  for (size_t i = 0; i < nn; ++i) {
-    const BuildNode &nd = bb.nodes[i];
-    int32_t w[3];
-    // leaf children are JS `undefined` -> Int32Array 0 (maskBVHBuffer, main.js:272-282)
-    w[0] = nd.leaf ? 0 : nd.left;
-    w[1] = nd.leaf ? 0 : nd.right;
-    w[2] = nd.leaf ? (int32_t)(b->tri.size() / 9) : -1;
-    std::memcpy(&b->bvh[i * 9], w, 12);
-    b->bvh[i * 9 + 3] = (float)nd.box.mn.x; b->bvh[i * 9 + 4] = (float)nd.box.mn.y; b->bvh[i * 9 + 5] = (float)nd.box.mn.z;
-    b->bvh[i * 9 + 6] = (float)nd.box.mx.x; b->bvh[i * 9 + 7] = (float)nd.box.mx.y; b->bvh[i * 9 + 8] = (float)nd.box.mx.z;
-    if (nd.leaf) {
-      for (uint32_t k = nd.lo; k < nd.hi; ++k) {  // getTriangles = indices[0] order
-        const Tri &t = b->geometry[bb.idx[0][k]];
-        for (int v = 0; v < 3; ++v) {
-          b->tri.push_back((float)t.v[v].x); b->tri.push_back((float)t.v[v].y); b->tri.push_back((float)t.v[v].z);
+  pack_tree(b, bb.nodes, bb.idx[0], nullptr, bb.depth);
+  b->gpu_built = false;
+  return FSPT_OK;
+}
+
+// The binned-SAH tree of fspt_bvh_build.hip: the GPU builds it, the host renumbers it in pre-order, recomputes the float64
+// boxes autofocus walks (in the order add_vertex would meet the triangles: bit for bit what a sweep over each node's range
+// gives) and packs it with the same loops.
+int fspt_builder_build_gpu(fspt_builder *b, uint32_t leaf_size, int device) {
+  if (!b) { fspt_set_error("fspt_builder_build_gpu: NULL builder"); return FSPT_E_INVALID; }
+  if (leaf_size == 0 || leaf_size > 64) { fspt_set_error("fspt_builder_build_gpu: leaf_size must be 1..64"); return FSPT_E_INVALID; }
+  if (device < 0) { fspt_set_error("fspt_builder_build_gpu: device %d out of range", device); return FSPT_E_INVALID; }
+  if (!b->pending.empty()) { fspt_set_error("fspt_builder_build_gpu: an OBJ is waiting for fspt_builder_commit_obj"); return FSPT_E_STATE; }
+  if (b->geometry.empty()) { fspt_set_error("fspt_builder_build_gpu: no triangles"); return FSPT_E_INVALID; }
+  if (b->geometry.size() > (size_t)INT32_MAX / 2) { fspt_set_error("fspt_builder_build_gpu: too many triangles"); return FSPT_E_INVALID; }
+  const size_t nt = b->geometry.size();
+  std::vector<float> verts(nt * 9);
+  for (size_t i = 0; i < nt; ++i)
+    for (int v = 0; v < 3; ++v) {
+      const D3 &p = b->geometry[i].v[v];
+      const float f[3] = {(float)p.x, (float)p.y, (float)p.z};
+      for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(f[k])) {
+          fspt_set_error("fspt_builder_build_gpu: triangle %zu has a non-finite vertex", i);
+          return FSPT_E_INVALID;
         }
-        for (int q = 0; q < 12; ++q) b->mat.push_back((float)t.mat[q]);
-        for (int v = 0; v < 3; ++v) {
-          D3 tg = t.tangents.size() > (size_t)v ? t.tangents[v] : d3(NAN, NAN, NAN);
-          D3 bt = t.bitangents.size() > (size_t)v ? t.bitangents[v] : d3(NAN, NAN, NAN);
-          b->norm.push_back((float)t.n[v].x); b->norm.push_back((float)t.n[v].y); b->norm.push_back((float)t.n[v].z);
-          b->norm.push_back((float)tg.x); b->norm.push_back((float)tg.y); b->norm.push_back((float)tg.z);
-          b->norm.push_back((float)bt.x); b->norm.push_back((float)bt.y); b->norm.push_back((float)bt.z);
-        }
-        for (int v = 0; v < 3; ++v) { b->uv.push_back((float)t.uv[v][0]); b->uv.push_back((float)t.uv[v][1]); }
+        verts[i * 9 + v * 3 + k] = f[k];
       }
     }
+  fspt::BvhGpuResult r;
+  int rc = fspt::bvh_build_gpu(verts.data(), (uint32_t)nt, leaf_size, device, r);
+  if (rc) return rc;
+  // pre-order renumbering (left first), checking that the device handed back one tree over every triangle
+  const size_t nn = r.left.size();
+  auto bad = [](const char *what) { fspt_set_error("fspt_builder_build_gpu: inconsistent tree from the device (%s)", what); return FSPT_E_HIP; };
+  std::vector<int32_t> pre(nn, -1);
+  std::vector<uint32_t> gid, node_depth;
+  std::vector<BuildNode> nodes;
+  gid.reserve(nn); node_depth.reserve(nn); nodes.reserve(nn);
+  std::vector<std::pair<uint32_t, uint32_t>> st{{0u, 0u}};
+  uint32_t depth = 0, next_lo = 0;
+  while (!st.empty()) {
+    const uint32_t g = st.back().first, d = st.back().second;
+    st.pop_back();
+    if (g >= nn || pre[g] >= 0) return bad("node visited twice or out of range");
+    pre[g] = (int32_t)nodes.size();
+    gid.push_back(g);
+    node_depth.push_back(d);
+    depth = std::max(depth, d);
+    BuildNode nd;
+    nd.lo = r.lo[g];
+    nd.hi = r.lo[g] + r.cnt[g];
+    nd.leaf = r.left[g] < 0;
+    if (nd.hi < nd.lo || nd.hi > nt) return bad("range");
+    if (nd.leaf) {
+      if (nd.lo != next_lo || r.cnt[g] == 0 || r.cnt[g] > leaf_size) return bad("leaf range");
+      next_lo = nd.hi;
+    } else {
+      if (r.right[g] < 0) return bad("children");
+      st.push_back({(uint32_t)r.right[g], d + 1});
+      st.push_back({(uint32_t)r.left[g], d + 1});
+    }
+    nodes.push_back(nd);
   }
-  b->n_nodes = (uint32_t)nn;
-  b->n_tris = (uint32_t)nt;
-  b->depth = bb.depth;
-  b->host_nodes.resize(nn);
-  for (size_t i = 0; i < nn; ++i) {
-    const BuildNode &nd = bb.nodes[i];
-    b->host_nodes[i] = fspt_builder::HostNode{nd.box, nd.left, nd.right, nd.lo, nd.hi, nd.leaf};
+  if (nodes.size() != nn || next_lo != nt) return bad("coverage");
+  if (depth > fspt::bvh_max_depth()) return bad("depth");
+  std::vector<uint8_t> seen(nt, 0);
+  for (uint32_t t : r.order) {
+    if (t >= nt || seen[t]) return bad("triangle order");
+    seen[t] = 1;
   }
-  b->tri_order = bb.idx[0];
-  b->built = true;
+  std::vector<float> fbox(nn * 6);
+  for (size_t i = nn; i-- > 0;) {
+    BuildNode &nd = nodes[i];
+    const uint32_t g = gid[i];
+    for (int k = 0; k < 6; ++k) fbox[i * 6 + k] = fspt::bvh_key_float(r.box_keys[(size_t)g * 12 + k]);
+    if (nd.leaf) {
+      for (uint32_t k = nd.lo; k < nd.hi; ++k) {
+        const Tri &t = b->geometry[r.order[k]];
+        nd.box.add_vertex(t.v[0]); nd.box.add_vertex(t.v[1]); nd.box.add_vertex(t.v[2]);
+      }
+    } else {
+      nd.left = pre[(size_t)r.left[g]];
+      nd.right = pre[(size_t)r.right[g]];
+      // the left range comes first: its extremes win ties, as in a sweep of add_vertex over the whole range
+      const Box &l = nodes[(size_t)nd.left].box, &rt = nodes[(size_t)nd.right].box;
+      nd.box.mn = d3(rt.mn.x < l.mn.x ? rt.mn.x : l.mn.x, rt.mn.y < l.mn.y ? rt.mn.y : l.mn.y, rt.mn.z < l.mn.z ? rt.mn.z : l.mn.z);
+      nd.box.mx = d3(rt.mx.x > l.mx.x ? rt.mx.x : l.mx.x, rt.mx.y > l.mx.y ? rt.mx.y : l.mx.y, rt.mx.z > l.mx.z ? rt.mx.z : l.mx.z);
+    }
+  }
+  pack_tree(b, nodes, r.order, fbox.data(), depth);
+  b->gpu_built = true;
+  b->gpu_kernel_ms = r.kernel_ms;
+  b->gpu_launches = r.launches;
+  b->gpu_readbacks = r.readbacks;
+  return FSPT_OK;
+}
+
+int fspt_builder_tri_order(const fspt_builder *b, uint32_t *order) {
+  if (!b || !b->built) { fspt_set_error("fspt_builder_tri_order: builder not built"); return FSPT_E_STATE; }
+  if (!order) { fspt_set_error("fspt_builder_tri_order: NULL argument"); return FSPT_E_INVALID; }
+  std::memcpy(order, b->tri_order.data(), b->tri_order.size() * 4);
+  return FSPT_OK;
+}
+
+int fspt_builder_gpu_stats(const fspt_builder *b, float *kernel_ms, uint32_t *launches, uint32_t *readbacks) {
+  if (!b || !b->built || !b->gpu_built) { fspt_set_error("fspt_builder_gpu_stats: the builder's tree was not built on the GPU"); return FSPT_E_STATE; }
+  if (kernel_ms) *kernel_ms = b->gpu_kernel_ms;
+  if (launches) *launches = b->gpu_launches;
+  if (readbacks) *readbacks = b->gpu_readbacks;
   return FSPT_OK;
 }
 

@@ -208,9 +208,12 @@ function packReferenceScene(bvh) {
  *  sceneOrProps: the scene JSON (props / static_props / animated_props, worldTransforms, normalize, atlasRes) or a
  *  bare props array; objTexts: {path: OBJ text}; env: {rgbe, width, height} | null;
  *  opts: {mtlTexts: {url: MTL text}, assets: {url: decoded image}, focusRays: [[eye, dir], ...],
- *         host: {TexturePacker, getMaterial, ParseMaterials} (the reference's modules) + atlasPixels(packer)}. */
+ *         host: {TexturePacker, getMaterial, ParseMaterials} (the reference's modules) + atlasPixels(packer),
+ *         bvh: 'sah' (default: the reference's tree) | 'gpu' (binned SAH built on HIP device opts.device, DESIGN 8.4)}. */
 function buildScene(sceneOrProps, objTexts, env, leafSize, opts) {
   opts = opts || {};
+  const bvh = opts.bvh === undefined ? 'sah' : opts.bvh;
+  if (bvh !== 'sah' && bvh !== 'gpu') throw new RangeError("buildScene: opts.bvh must be 'sah' or 'gpu'");
   const scene = Array.isArray(sceneOrProps) ? { props: sceneOrProps } : sceneOrProps;
   const props = mergeSceneProps(scene);
   // the reference's own host modules when the caller has them (INTEGRATION.md), the resolver above otherwise
@@ -241,7 +244,7 @@ function buildScene(sceneOrProps, objTexts, env, leafSize, opts) {
       addon.builderCommit(b, mats);
     }
     if (scene.normalize) addon.builderNormalize(b, scene.normalize);
-    s = addon.builderBuild(b, leafSize || 4);
+    s = bvh === 'gpu' ? addon.builderBuildGpu(b, leafSize || 4, opts.device || 0) : addon.builderBuild(b, leafSize || 4);
     s.focus = (opts.focusRays || []).map(([eye, dir]) => 1 - 1 / addon.builderAutofocus(b, eye, dir));   // main.js:544
   } finally {
     addon.builderDestroy(b);
@@ -260,6 +263,7 @@ function buildScene(sceneOrProps, objTexts, env, leafSize, opts) {
   if (env) { s.env = env.rgbe; s.envW = env.width; s.envH = env.height; s.bins = addon.envBins(env.rgbe, env.width, env.height); }
   else { s.env = null; s.envW = 0; s.envH = 0; s.bins = new Uint32Array([0, 0, 1, 2048]); }   // main.js:292
   s.leafSize = leafSize || 4;
+  s.bvhBuilder = bvh;
   return s;
 }
 

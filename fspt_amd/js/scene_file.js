@@ -145,8 +145,9 @@ function mtllibUrls(objText, basePath) {
  *  names - OBJ texts, the MTL libraries of their `mtllib` lines, the texture images of prop fields and MTL `map_*`
  *  statements, the RGBE environment image - then initBVH through buildScene and the auto-focus ray.
  *  Returns {scene (buildScene's arrays), settings (initGlobals' values, main.js:50-75)}.  Paths in the JSON are relative
- *  to the web root (`assetRoot`, default: the parent of the scene file's folder). */
-function loadSceneFile(scenePath, assetRoot, leafSize) {
+ *  to the web root (`assetRoot`, default: the parent of the scene file's folder).  buildOpts: {bvh: 'sah' | 'gpu', device}
+ *  (buildScene's builder choice). */
+function loadSceneFile(scenePath, assetRoot, leafSize, buildOpts) {
   const sceneJson = JSON.parse(fs.readFileSync(scenePath, 'utf8'));
   const root = assetRoot || path.dirname(path.dirname(path.resolve(scenePath)));
   const props = F.mergeSceneProps(sceneJson);
@@ -167,7 +168,8 @@ function loadSceneFile(scenePath, assetRoot, leafSize) {
   if (typeof e === 'string') { const img = readImage(root, e); env = { rgbe: img.data, width: img.width, height: img.height }; }
   else if (e && e.length) throw new Error('array-of-stops environments are not supported (broken in the reference itself); use an RGBE image or none');
   const eye = (sceneJson.cameraPos || [0, 0, 2]).map(Number), dir = (sceneJson.cameraDir || [0, 0, -1]).map(Number);
-  const scene = F.buildScene(sceneJson, objTexts, env, leafSize || 4, { mtlTexts, assets, focusRays: [[eye, dir]] });
+  const bo = buildOpts || {};
+  const scene = F.buildScene(sceneJson, objTexts, env, leafSize || 4, { mtlTexts, assets, focusRays: [[eye, dir]], bvh: bo.bvh, device: bo.device });
   const settings = { eye, dir, fovScale: Number(sceneJson.fovScale || 0.5), envTheta: Number(sceneJson.environmentTheta || 0),
     exposure: Number(sceneJson.exposure || 1.0), samples: Math.floor(Number(sceneJson.samples || 2000)), focus: scene.focus[0], aperture: 0.02 };
   return { scene, settings };
@@ -198,7 +200,7 @@ function renderFrame(scene, settings, width, height, opts) {
 
 /** scene file -> PNG file (the reference POSTs canvas.toBlob's PNG to /upload/<scene>/<frame>, main.js:859-866) */
 function renderToPng(scenePath, outPath, width, height, opts) {
-  const { scene, settings } = loadSceneFile(scenePath, opts && opts.assetRoot);
+  const { scene, settings } = loadSceneFile(scenePath, opts && opts.assetRoot, 4, { bvh: opts && opts.bvh, device: opts && opts.device });
   const fr = renderFrame(scene, settings, width, height, opts);
   const rgb = new Uint8Array(width * height * 3);
   for (let i = 0, j = 0; i < fr.rgba.length; i += 4, j += 3) { rgb[j] = fr.rgba[i]; rgb[j + 1] = fr.rgba[i + 1]; rgb[j + 2] = fr.rgba[i + 2]; }
@@ -223,7 +225,7 @@ function renderSequence(scenePattern, frames, outPattern, width, height, opts) {
 module.exports = { decodePng, encodePng, decodeJpeg, mtllibUrls, loadSceneFile, renderFrame, renderToPng, renderSequence };
 
 // node fspt_amd/js/scene_file.js scene/bunny.json out.png [--width W] [--height H] [--samples N] [--bounces B] [--seed S]
-//                                [--asset-root DIR] [--denoise] [--frames A:B]   (mirrors `python -m fspt_amd.render`;
+//                                [--asset-root DIR] [--denoise] [--frames A:B] [--bvh sah|gpu]   (mirrors `python -m fspt_amd.render`;
 //                                with --frames both paths contain {frame}: the reference's ?frame=N loop)
 if (require.main === module) {
   const argv = process.argv.slice(2), pos = [], o = { width: 960, height: 540 };
@@ -233,10 +235,10 @@ if (require.main === module) {
     else if (a.startsWith('--')) o[a.slice(2).replace(/-([a-z])/g, (m, c) => c.toUpperCase())] = argv[++i];
     else pos.push(a);
   }
-  if (pos.length !== 2) { console.error('usage: node scene_file.js <scene.json> <out.png> [--width W] [--height H] [--samples N] [--bounces B] [--seed S] [--asset-root DIR] [--denoise]'); process.exit(2); }
+  if (pos.length !== 2) { console.error('usage: node scene_file.js <scene.json> <out.png> [--width W] [--height H] [--samples N] [--bounces B] [--seed S] [--asset-root DIR] [--denoise] [--frames A:B] [--bvh sah|gpu]'); process.exit(2); }
   const num = (k) => (o[k] === undefined ? undefined : Number(o[k]));
   const t0 = Date.now();
-  const ro = { samples: num('samples'), bounces: num('bounces'), seed: num('seed'), assetRoot: o.assetRoot, denoise: !!o.denoise };
+  const ro = { samples: num('samples'), bounces: num('bounces'), seed: num('seed'), assetRoot: o.assetRoot, denoise: !!o.denoise, bvh: o.bvh };
   if (o.frames) {
     const [a, b] = String(o.frames).split(':').map(Number), frames = [];
     for (let n = a; n < b; n++) frames.push(n);

@@ -7,6 +7,7 @@ reference's format (scene/<name>.json with props / static_props / animated_props
     python -m fspt_amd.render --out bunny.png --spp 16 --atrous 5 --feature-samples 8   # guided denoiser
     python -m fspt_amd.render --out bunny.png --spp 16 --sampler sobol --sampler-seed 3  # Owen-scrambled Sobol sampler
     python -m fspt_amd.render --scene web/scene/bunny.json --lights --emitter-fraction 0.5  # sample emissive triangles
+    python -m fspt_amd.render --mesh-n 289 --bvh gpu --spp 16 --out c3.png  # binned-SAH tree built on the GPU
 
 Path tracing runs in the HIP kernels (fspt_render), tone mapping in the draw.fs kernel (fspt_draw); --atrous K runs
 the guided a-trous denoiser (fspt_features + fspt_denoise, K iterations) before tone mapping (fspt_draw_denoised).
@@ -37,6 +38,8 @@ def main():
     ap.add_argument("--assets", default=None, help="web root the JSON's paths are relative to (default: parent of the scene folder)")
     ap.add_argument("--frames", default=None, help="A:B = frames A..B-1 (the reference's ?frame=N loop, main.js:851-866)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--bvh", choices=("sah", "gpu"), default="sah",
+                    help="BVH builder: the reference's full-sweep SAH on the CPU, or binned SAH on the GPU (DESIGN 8.4)")
     ap.add_argument("--sampler", choices=("reference", "sobol"), default="reference",
                     help="the paths' random numbers (fspt_target_set_sampler; built-in scene)")
     ap.add_argument("--sampler-seed", type=int, default=0, help="seed of --sampler sobol, in [0, 2^32)")
@@ -63,10 +66,10 @@ def main():
         if args.frames:
             a, b = (int(x) for x in args.frames.split(":"))
             t0 = time.perf_counter()
-            out = F.render_sequence(args.scene, range(a, b), args.out, args.width, args.height, args.assets, **kw)
+            out = F.render_sequence(args.scene, range(a, b), args.out, args.width, args.height, args.assets, bvh=args.bvh, **kw)
             print(f"{len(out)} frames in {time.perf_counter() - t0:.2f} s:", *out)
         else:
-            arrays, settings = F.load_scene_file(args.scene, args.assets)
+            arrays, settings = F.load_scene_file(args.scene, args.assets, bvh=args.bvh)
             settings["exposure"] = settings["exposure"] * args.exposure
             rgba, rad = F.render_frame(arrays, settings, args.width, args.height, **kw)
             if args.hdr:
@@ -75,7 +78,10 @@ def main():
             Image.fromarray(rgba[:, :, :3]).save(args.out)
             print("wrote", args.out, f"({arrays.n_tris} triangles, {spp or settings['samples']} spp)")
         return
-    arrays = S.bunny_scene(n=args.mesh_n)
+    t0 = time.perf_counter()
+    arrays = S.bunny_scene(n=args.mesh_n, bvh=args.bvh)
+    print(f"scene: {arrays.n_tris} triangles, {arrays.n_nodes} nodes, depth {arrays.depth} ({args.bvh} tree) in "
+          f"{time.perf_counter() - t0:.2f} s")
     pt = PathTracer(arrays, args.width, args.height, num_bounces=args.bounces)
     pt.set_camera(**S.BUNNY_CAMERA)
     if args.sampler != "reference":

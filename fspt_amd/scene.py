@@ -308,13 +308,22 @@ def _rot_array(rot):
     return arr, len(rot)
 
 
+BVH_BUILDERS = ("sah", "gpu")
+
+
 def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas_res=2048, images=None,
-                world_transforms=None, normalize=None, mtl_texts=None, focus_rays=None):
+                world_transforms=None, normalize=None, mtl_texts=None, focus_rays=None, bvh="sah", device=0,
+                keep_order=False):
     """initBVH (main.js:284-445) for props = list of scene-JSON prop dicts and obj_texts = {path: OBJ text}.
     env = RGBE uint8 [h*w*4] or None; world_transforms = scene.worldTransforms; normalize = scene.normalize;
     mtl_texts = {url: MTL text} for `mtllib` lines (url = <dir of the OBJ>/<name>, obj_loader.js:186);
     images = {url: decoded RGBA8 [h, w, 4], row 0 = top} for texture maps; focus_rays = [(eye, dir), ...] ->
-    meta["focus"] = shootAutoFocusRay's lensFeatures[0] = 1 - 1/dist for each (main.js:447-546)."""
+    meta["focus"] = shootAutoFocusRay's lensFeatures[0] = 1 - 1/dist for each (main.js:447-546).
+    bvh = "sah": the reference's full-sweep SAH tree (bvh.js, on the CPU); "gpu": the binned-SAH tree built on HIP device
+    `device` (fspt_builder_build_gpu; leaf_size 1..64).  meta["bvh"] names the builder; keep_order=True adds
+    meta["tri_order"]: packed triangle k is the k'th triangle of the OBJs in the order they were added."""
+    if bvh not in BVH_BUILDERS:
+        raise ValueError(f"bvh must be one of {BVH_BUILDERS}, not {bvh!r}")
     lib = L.lib()
     packer = TexturePacker(atlas_res)
     focus = []
@@ -371,13 +380,19 @@ def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas
             L.check(lib.fspt_builder_commit_obj(b, mats, ng.value))
         if normalize:
             L.check(lib.fspt_builder_normalize(b, float(normalize)))
-        L.check(lib.fspt_builder_build(b, leaf_size))
+        if bvh == "gpu":
+            L.check(lib.fspt_builder_build_gpu(b, leaf_size, int(device)))
+        else:
+            L.check(lib.fspt_builder_build(b, leaf_size))
         nn, nt, dp = C.c_uint32(), C.c_uint32(), C.c_uint32()
         L.check(lib.fspt_builder_counts(b, C.byref(nn), C.byref(nt), C.byref(dp)))
-        bvh = np.zeros(nn.value * 9, np.float32); tri = np.zeros(nt.value * 9, np.float32)
+        bvh_arr = np.zeros(nn.value * 9, np.float32); tri = np.zeros(nt.value * 9, np.float32)
         mat = np.zeros(nt.value * 12, np.float32); norm = np.zeros(nt.value * 27, np.float32)
         uv = np.zeros(nt.value * 6, np.float32)
-        L.check(lib.fspt_builder_get(b, L.fptr(bvh), L.fptr(tri), L.fptr(mat), L.fptr(norm), L.fptr(uv)))
+        L.check(lib.fspt_builder_get(b, L.fptr(bvh_arr), L.fptr(tri), L.fptr(mat), L.fptr(norm), L.fptr(uv)))
+        if keep_order:
+            order = np.zeros(nt.value, np.uint32)
+            L.check(lib.fspt_builder_tri_order(b, L.u32ptr(order)))
         for eye, d in (focus_rays or []):
             dist = C.c_double()
             L.check(lib.fspt_builder_autofocus(b, (C.c_double * 3)(*[float(x) for x in eye]),
@@ -391,19 +406,22 @@ def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas
         bins = env_bins(env, env_w, env_h)
     else:
         bins = np.array([0, 0, 1, 2048], dtype=np.uint32)  # main.js:292
-    return SceneArrays(bvh=bvh, tri=tri, mat=mat, norm=norm, uv=uv, atlas=atlas, atlas_res=packer.res,
+    meta = {"layers": packer.describe(), "focus": focus, "bvh": bvh}
+    if keep_order:
+        meta["tri_order"] = order
+    return SceneArrays(bvh=bvh_arr, tri=tri, mat=mat, norm=norm, uv=uv, atlas=atlas, atlas_res=packer.res,
                        atlas_layers=len(packer.image_set), env=env, env_w=env_w, env_h=env_h, bins=bins,
-                       leaf_size=leaf_size, depth=dp.value, meta={"layers": packer.describe(), "focus": focus})
+                       leaf_size=leaf_size, depth=dp.value, meta=meta)
 
 
 def build_scene_json(scene, obj_texts, mtl_texts=None, images=None, env=None, env_w=0, env_h=0, leaf_size=4,
-                     focus_rays=None):
+                     focus_rays=None, bvh="sah", device=0):
     """build_scene for a whole scene JSON (props / static_props / animated_props, worldTransforms, normalize,
     atlasRes: main.js:284-445,869-871,944)."""
     return build_scene(merge_scene_props(scene), obj_texts, env=env, env_w=env_w, env_h=env_h, leaf_size=leaf_size,
                        atlas_res=scene.get("atlasRes") or 2048, images=images,
                        world_transforms=scene.get("worldTransforms"), normalize=scene.get("normalize"),
-                       mtl_texts=mtl_texts, focus_rays=focus_rays)
+                       mtl_texts=mtl_texts, focus_rays=focus_rays, bvh=bvh, device=device)
 
 
 def merge_scene_props(scene):
@@ -595,14 +613,15 @@ def bunny_props_textured():
     return p
 
 
-def bunny_scene_textured(n=76, env_size=(2048, 1024), sun_deg=1.5, sun_gain=60.0, res=2048):
+def bunny_scene_textured(n=76, env_size=(2048, 1024), sun_deg=1.5, sun_gain=60.0, res=2048, bvh="sah", device=0):
     """The 'bunny' configs with the reference's real atlas size: 2048^2 image maps on both quads (7 image layers + the
     flat-colour layers, 16 MB each) - the 4 x 4-tap bilinear atlas gather of tracer.fs:453-456 on an atlas that does not
     fit any cache."""
     texts = {"synthetic/cube_sphere.obj": cube_sphere_obj(n), "synthetic/quad.obj": QUAD_OBJ}
     env, w, h = synthetic_env(env_size[0], env_size[1], sun_deg=sun_deg, sun_gain=sun_gain)
-    s = build_scene(bunny_props_textured(), texts, env=env, env_w=w, env_h=h, images=procedural_maps(res), atlas_res=res)
-    s.meta = dict(kind="bunny-synthetic-textured", n=n, res=res)
+    s = build_scene(bunny_props_textured(), texts, env=env, env_w=w, env_h=h, images=procedural_maps(res), atlas_res=res,
+                    bvh=bvh, device=device)
+    s.meta = dict(kind="bunny-synthetic-textured", n=n, res=res, bvh=bvh)
     return s
 
 
@@ -616,11 +635,11 @@ def lens_features(focal_depth, aperture):
     return [1.0 - 1.0 / focal_depth, aperture]
 
 
-def bunny_scene(n=76, env_size=(2048, 1024), sun_deg=1.5, sun_gain=60.0):
+def bunny_scene(n=76, env_size=(2048, 1024), sun_deg=1.5, sun_gain=60.0, bvh="sah", device=0):
     """The BASELINE 'bunny' configs: n=76 -> 69 312 + 4 triangles (C1/C2/C5),
     n=289 -> 1 002 252 + 4 (C3)."""
     texts = {"synthetic/cube_sphere.obj": cube_sphere_obj(n), "synthetic/quad.obj": QUAD_OBJ}
     env, w, h = synthetic_env(env_size[0], env_size[1], sun_deg=sun_deg, sun_gain=sun_gain)
-    s = build_scene(bunny_props(), texts, env=env, env_w=w, env_h=h)
-    s.meta = dict(kind="bunny-synthetic", n=n)
+    s = build_scene(bunny_props(), texts, env=env, env_w=w, env_h=h, bvh=bvh, device=device)
+    s.meta = dict(kind="bunny-synthetic", n=n, bvh=bvh)
     return s

@@ -40,10 +40,10 @@ def mtllib_urls(obj_text, base_path):
     return urls
 
 
-def load_scene_file(scene_path, asset_root=None, leaf_size=4):
+def load_scene_file(scene_path, asset_root=None, leaf_size=4, bvh="sah", device=0):
     """Returns (SceneArrays, settings).  settings = camera and display values with the reference's defaults
     (initGlobals, main.js:50-75): eye, dir, fov_scale, env_theta, exposure, samples, focus (lensFeatures[0]
-    after shootAutoFocusRay), aperture (index.html default 0.02)."""
+    after shootAutoFocusRay), aperture (index.html default 0.02).  bvh / device: scene.build_scene's builder choice."""
     with open(scene_path, "r", encoding="utf-8") as fh:
         scene = json.load(fh)
     root = asset_root or os.path.dirname(os.path.dirname(os.path.abspath(scene_path)))
@@ -81,7 +81,7 @@ def load_scene_file(scene_path, asset_root=None, leaf_size=4):
     eye = [float(x) for x in (scene.get("cameraPos") or [0, 0, 2])]
     d = [float(x) for x in (scene.get("cameraDir") or [0, 0, -1])]
     arrays = S.build_scene_json(scene, obj_texts, mtl_texts, images, env=env, env_w=env_w, env_h=env_h,
-                                leaf_size=leaf_size, focus_rays=[(eye, d)])
+                                leaf_size=leaf_size, focus_rays=[(eye, d)], bvh=bvh, device=device)
     settings = dict(eye=eye, dir=d, fov_scale=float(scene.get("fovScale") or 0.5),
                     env_theta=float(scene.get("environmentTheta") or 0), exposure=float(scene.get("exposure") or 1.0),
                     samples=int(scene.get("samples") or 2000), focus=arrays.meta["focus"][0], aperture=0.02)
@@ -112,14 +112,15 @@ def render_frame(arrays, settings, width, height, samples=None, bounces=4, seed=
     return rgba[::-1].copy(), rad
 
 
-def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, **kw):
+def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", **kw):
     """frame=N sequencing (main.js:851-866, 966-969): for every N in `frames` load `scene_pattern.format(frame=N)`
     (the per-frame scene JSON the reference's server hands out for `?frame=N`), render it, write
-    `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1."""
+    `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1.
+    bvh="gpu" builds every frame's tree on the render device."""
     from PIL import Image
     written = []
     for n in frames:
-        arrays, settings = load_scene_file(scene_pattern.format(frame=n), asset_root)
+        arrays, settings = load_scene_file(scene_pattern.format(frame=n), asset_root, bvh=bvh, device=kw.get("device", 0))
         rgba, _ = render_frame(arrays, settings, width, height, **kw)
         out = out_pattern.format(frame=n)
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)

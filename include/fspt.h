@@ -274,8 +274,8 @@ int fspt_builder_mtllib_name(const fspt_builder *b, uint32_t index, const char *
 int fspt_builder_commit_obj(fspt_builder *b, const fspt_group_material *mats, uint32_t n_groups);
 /* scene.normalize (main.js:337-348): centre on the scene bounds and scale the longest side to 2*size. */
 int fspt_builder_normalize(fspt_builder *b, double size);
-/* new BVH(geometry, leaf_size) + serializeTree + packing loops (bvh.js:5-91, main.js:355-392). */
-int fspt_builder_build(fspt_builder *b, uint32_t leaf_size);
+/* new BVH(geometry, leaf_size) + serializeTree + packing (bvh.js:5-91, main.js:355-392); _gpu: binned SAH on `device` (DESIGN 8.4) */
+int fspt_builder_build(fspt_builder *b, uint32_t leaf_size); int fspt_builder_build_gpu(fspt_builder *b, uint32_t leaf_size, int device);
 int fspt_builder_counts(const fspt_builder *b, uint32_t *n_nodes, uint32_t *n_tris, uint32_t *depth);
 /* shootAutoFocusRay (main.js:447-546) on the built tree, in float64: distance along (eye, dir) to the first
  * triangle, 1e6 when there is none; the reference then sets lensFeatures[0] = 1 - 1/dist. */

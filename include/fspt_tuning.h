@@ -114,6 +114,13 @@ int fspt_get_trace_lds_steps(fspt_target *target, uint64_t *steps);
  * and how the tests check that dropped tracers give their memory back. */
 int fspt_device_memory(int device, uint64_t *free_bytes, uint64_t *total_bytes);
 
+/* Of the builder's last fspt_builder_build_gpu: HIP-event time from its first kernel to its last (the per-level
+ * readbacks included), kernel launches, device-to-host readbacks.  FSPT_E_STATE after fspt_builder_build. */
+int fspt_builder_gpu_stats(const fspt_builder *b, float *kernel_ms, uint32_t *launches, uint32_t *readbacks);
+/* The built tree's triangle order (n_tris): packed triangle k (fspt_builder_get) is the builder's triangle order[k], in the
+ * order the OBJs added them - what a second builder's tree is compared against triangle by triangle. */
+int fspt_builder_tri_order(const fspt_builder *b, uint32_t *order);
+
 /* ---- test hook ------------------------------------------------------------------------------------------------------ */
 /* Device-side evaluation of the deterministic math primitives (DESIGN.md
  * "fspt-math"), for bitwise comparison against the oracle's C versions.

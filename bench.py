@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s of the path-trace hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--scaling weak|strong] [--full]
 
 One "step" = one tick of the reference's render loop (main.js:838-857): one sample for every pixel of the frame
 (camera ray -> full path, tracer.fs:436-518) accumulated into the running-mean radiance buffer.  N=1 workload =
@@ -20,6 +20,13 @@ ranks (no data-path collective); ONE exchange of the RGBA32F radiance buffer to 
 
 The timed region (exactly K steps between barriers) is run --reps times (default 5) and the MEDIAN is reported
 (box-to-box and run-to-run spread is a few per cent).  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: it sets up, warms up, times the regions, writes --dump-outputs and
+prints the line (value, ms_per_step, the per-region times and the run's configuration).  --full adds everything else, after
+the headline's timed regions as before: the oracle check of the timed accumulator (parity_check), the roofline and per-kernel
+figures (counting ticks of their own, priced against the request-rate microbenchmark run before the GPU is touched), the
+CPU oracle baseline and the recorded GLSL one, and the other BASELINE configs as extra_configs.  --no-cpu-baseline,
+--no-extra-configs, --no-parity-check and --no-l1-microbench leave out single parts of --full.
 
 --dump-outputs DIR: rank 0 also writes what the timed path left for its caller after the last timed step of the headline
 workload - the running-mean radiance buffer - as DIR/radiance.npy (float32, H x W x 4), so that two builds can be compared
@@ -183,14 +190,17 @@ def parse_args(argv=None):
     ap.add_argument("--tick-mode", action="store_true",
                     help="a step is ONE tick() call (drawCamera + drawTracer, main.js:838-857) followed by a sync - the interactive "
                          "form, where every sample is observed before the next is issued - instead of one tick of a fused render(steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: parity check against the oracle, roofline and per-kernel figures, CPU "
+                         "baseline and extra_configs (off: a plain run only sets up, warms up, times and prints the headline)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--stage-events", default="last", choices=["first", "last", "all"],
                     help="which timed regions carry the per-launch HIP event pairs behind the per-kernel times (they cost ~1.3 %% of a "
                          "20-step region): only the last one (default: a warm, steady-state region; the reported per-kernel times and the "
                          "roofline are that region's), only the first one, or all")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="only the headline workload (default: after it, BASELINE configs[2] and [4] at N = 1 / configs[3] at N > 1 as extra_configs)")
-    ap.add_argument("--no-parity-check", action="store_true", help="skip the oracle comparison of the timed run's accumulator")
+                    help="--full: only the headline workload (otherwise after it, BASELINE configs[2] and [4] at N = 1 / configs[3] at N > 1 as extra_configs)")
+    ap.add_argument("--no-parity-check", action="store_true", help="--full: skip the oracle comparison of the timed run's accumulator")
     ap.add_argument("--pipeline", default="wavefront", choices=["wavefront", "megakernel", "stream"])
     ap.add_argument("--pool", type=int, default=0, help="stream scheduler: live paths per state set (0 = library default)")
     ap.add_argument("--drain", type=int, default=-1, help="stream scheduler: drain iterations before the tail kernel (-1 = default)")
@@ -517,19 +527,24 @@ def run_workload(args, env):
     # is DEFERRED (main() runs it after the timed regions of every workload, when the other ranks have already been
     # released: VERDICT r4 weak 8 iii - seven ranks used to sit in a barrier with a 600 s timeout meanwhile).  The frame as
     # the timed regions left it is copied to the host now (the counting ticks add to the accumulator later).
-    frame = accum.cpu().numpy() if (not args.no_parity_check or n_gpus > 1 or args.dump_outputs) else None  # N > 1: mandatory - bytes that crossed xGMI are verified
+    # --full, N > 1: the check is mandatory - bytes that crossed xGMI are verified
+    check_parity = args.full and (not args.no_parity_check or n_gpus > 1)
+    frame = accum.cpu().numpy() if (check_parity or args.dump_outputs) else None
 
     def finish():
-        check = None
         dumped = dump_outputs(args.dump_outputs, frame) if args.dump_outputs else None
-        if frame is not None and (not args.no_parity_check or n_gpus > 1):
-            check = parity_check(arrays, W, H, cam, lens, args.bounces, args.warmup + args.reps * args.steps, 1, frame)
-        out = report(args, pt, arrays, cam, lens, W, H, n_gpus, world_seen, value, elapsed, times, kernel_ms, launches,
-                     stages, build_s)
-        out["stage_events"] = {"regions": args.stage_events, "region": ev_rep, "region_ms_per_step": round(times[ev_rep] * 1e3 / args.steps, 4),
-                               "is": "the timed region whose launches carried HIP event pairs (fspt_target_set_stage_timing): roofline.kernels.* "
-                                     "and roofline.avg_launch_ms are that region's; `value` is the median of all regions"}
-        out["parity_check"] = check
+        if not args.full:
+            out = report(args, pt, arrays, cam, W, H, n_gpus, world_seen, value, elapsed, times, build_s)
+        else:
+            check = None
+            if check_parity:
+                check = parity_check(arrays, W, H, cam, lens, args.bounces, args.warmup + args.reps * args.steps, 1, frame)
+            out = full_report(args, pt, arrays, cam, lens, W, H, n_gpus, world_seen, value, elapsed, times, kernel_ms, launches,
+                              stages, build_s)
+            out["stage_events"] = {"regions": args.stage_events, "region": ev_rep, "region_ms_per_step": round(times[ev_rep] * 1e3 / args.steps, 4),
+                                   "is": "the timed region whose launches carried HIP event pairs (fspt_target_set_stage_timing): roofline.kernels.* "
+                                         "and roofline.avg_launch_ms are that region's; `value` is the median of all regions"}
+            out["parity_check"] = check
         if dumped is not None:
             out["dump_outputs"] = dumped
         if n_gpus > 1:
@@ -561,12 +576,12 @@ def main():
     if args.dry_run:
         return dry_run(args, rank, local_rank, world)
 
-    # The request-rate peak the trace kernel is priced against is measured first, by a child process started BEFORE this
+    # --full: the request-rate peak the trace kernel is priced against is measured first, by a child process started BEFORE this
     # process touches the GPU (no fork of a process that holds a HIP context).  Under a profiler the preloaded library
     # has initialised the GPU before main() runs: such runs pass --l1-peak (tools/prof_session.sh measures it once, outside
     # rocprofv3) or --no-l1-microbench, and no child is ever started from this process.
     global _L1_PEAK
-    if rank == 0 and _L1_PEAK is None:
+    if args.full and rank == 0 and _L1_PEAK is None:
         if args.l1_peak is not None:
             _L1_PEAK = (float(args.l1_peak), {"source": "--l1-peak (tools/microbench/l1_peak, measured outside this run)",
                                               "gather_lane_requests_per_s": float(args.l1_peak)})
@@ -609,14 +624,14 @@ def main():
         sys.stderr.write("[bench rank] " + json.dumps(rank_info) + "\n"); sys.stderr.flush()
 
     env = Env(rank=rank, local_rank=local_rank, n_gpus=n_gpus, dist=dist, world_seen=world_seen, rank_info=rank_info)
-    # ---- the timed regions of every workload first.  The headline, then the other BASELINE configs on the same record
-    # (VERDICT r4 item 2): N = 1: configs[2] (1 M triangles) and configs[4] (aperture 0.1 + small sun) as extra_configs.c3 /
-    # .c5; N > 1 on the weak-scaled default: configs[3] (3840x2160 cut over the N ranks, strong scaling) as
-    # extra_configs.strong_c4.  Each with its own regions, per-kernel times and parity check.
+    # ---- the timed regions of every workload first.  The headline, then (--full) the other BASELINE configs on the same
+    # record: N = 1: configs[2] (1 M triangles) and configs[4] (aperture 0.1 + small sun) as
+    # extra_configs.c3 / .c5; N > 1 on the weak-scaled default: configs[3] (3840x2160 cut over the N ranks, strong scaling)
+    # as extra_configs.strong_c4.  Each with its own regions, per-kernel times and parity check.
     t_h = time.perf_counter()
     pending = [("headline", run_workload(args, env), time.perf_counter() - t_h)]
     extras = []
-    if not args.no_extra_configs and args.config == "c2" and args.pipeline == "wavefront" and not args.textured:
+    if args.full and not args.no_extra_configs and args.config == "c2" and args.pipeline == "wavefront" and not args.textured:
         if n_gpus == 1:
             # configs[2] and [4]; the workload shaped like the reference's real scene (scene/bunny.json:18-41 image-maps both
             # quads: 2048^2 atlas layers); and the interactive form - 128 single tick() calls, each observed before the next
@@ -709,7 +724,32 @@ def _prof_key(prof, name):
     return max(cand, key=lambda k: prof["kernels"][k].get("launches", 0)) if cand else None
 
 
-def report(args, pt, arrays, cam, lens, W, H, n_gpus, world_seen, value, elapsed, times, kernel_ms, launches, stages, build_s):
+def report(args, pt, arrays, cam, W, H, n_gpus, world_seen, value, elapsed, times, build_s):
+    """The result line of a workload: the headline figure and what describes the run (nothing is run on the GPU here)."""
+    # BASELINE.json's wording for the two benchmark meshes ("70k tri" = 69 316, "1M" = 1 002 256); the count otherwise
+    tri_k = {76: "70k", 289: "1M"}.get(args.mesh_n) or (f"{arrays.n_tris / 1e3:.0f}k" if arrays.n_tris < 1e6 else f"{arrays.n_tris / 1e6:.1f}M")
+    return {
+        "metric": f"Msamples/s at {W}x{H} depth {args.bounces} (bunny, {tri_k} tri)",
+        "value": round(value, 3), "unit": "Msamples/s", "n_gpus": n_gpus, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed * 1e3 / args.steps, 4), "higher_is_better": True,
+        "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "reps": args.reps, "rep_ms_per_step": [round(t * 1e3 / args.steps, 4) for t in times],
+        "config": {"workload": f"{args.config}: bunny-synthetic {arrays.n_tris} tri{' + 2048^2 image maps' if args.textured else ''}, "
+                               f"{W}x{H}, depth {args.bounces}, 1 spp/step, aperture {cam['aperture']}, sun {args.sun_deg} deg x{args.sun_gain:g}"
+                               + (", every step = one tick() call + sync (the interactive form, main.js:838-857)" if args.tick_mode else ""),
+                   "scene_bytes": arrays.nbytes(), "bvh_nodes": arrays.n_nodes, "bvh_depth": arrays.depth,
+                   "env_bins": int(arrays.bins.size // 4), "atlas": f"{arrays.atlas_res}^2 x {arrays.atlas_layers}",
+                   "sharding": f"32x32 tiles round-robin over {n_gpus}", "world_size_seen": world_seen,
+                   "exchange": ((args.exchange + (" (gloo through host memory: --share-gpu, all ranks on ONE device - a plumbing check, not a scaling figure)" if args.share_gpu else "")) if n_gpus > 1 else "none"), "pipeline": args.pipeline,
+                   "batch_ticks": args.batch, "path_state_bytes": pt.path_state_bytes()[0],
+                   "primary_form": (dict(zip(("form", "ms_per_Msample"), (lambda f, ms: (f, [round(m * 1e6, 4) if m >= 0 else None for m in ms]))(*pt.primary_form(min(args.batch, args.steps)))))
+                                    if args.pipeline == "wavefront" else None),
+                   "scene_build_s": round(build_s, 2), "source_sha": source_sha()},
+    }
+
+
+def full_report(args, pt, arrays, cam, lens, W, H, n_gpus, world_seen, value, elapsed, times, kernel_ms, launches, stages, build_s):
+    """--full: the result line with the roofline and per-kernel figures (counting ticks of their own) and the CPU baselines."""
     import fspt_amd
     ref = count_work(pt, 1)   # reference algorithm (SURVEY 8d's S, L, H, E)
     bps = fspt_amd.bytes_per_sample(ref)
@@ -903,27 +943,8 @@ def report(args, pt, arrays, cam, lens, W, H, n_gpus, world_seen, value, elapsed
                     "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None, "kernel": "fspt::k_trace<true, false>",
                     "avg_launch_ms": round(avg_launch_ms, 4), "launches": launches, "bytes_per_sample": round(bps, 1),
                     "per_sample": per_sample}
-    # BASELINE.json's wording for the two benchmark meshes ("70k tri" = 69 316, "1M" = 1 002 256); the count otherwise
-    tri_k = {76: "70k", 289: "1M"}.get(args.mesh_n) or (f"{arrays.n_tris / 1e3:.0f}k" if arrays.n_tris < 1e6 else f"{arrays.n_tris / 1e6:.1f}M")
-    out = {
-        "metric": f"Msamples/s at {W}x{H} depth {args.bounces} (bunny, {tri_k} tri)",
-        "value": round(value, 3), "unit": "Msamples/s", "n_gpus": n_gpus, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(elapsed * 1e3 / args.steps, 4), "higher_is_better": True,
-        "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "reps": args.reps, "rep_ms_per_step": [round(t * 1e3 / args.steps, 4) for t in times],
-        "config": {"workload": f"{args.config}: bunny-synthetic {arrays.n_tris} tri{' + 2048^2 image maps' if args.textured else ''}, "
-                               f"{W}x{H}, depth {args.bounces}, 1 spp/step, aperture {cam['aperture']}, sun {args.sun_deg} deg x{args.sun_gain:g}"
-                               + (", every step = one tick() call + sync (the interactive form, main.js:838-857)" if args.tick_mode else ""),
-                   "scene_bytes": arrays.nbytes(), "bvh_nodes": arrays.n_nodes, "bvh_depth": arrays.depth,
-                   "env_bins": int(arrays.bins.size // 4), "atlas": f"{arrays.atlas_res}^2 x {arrays.atlas_layers}",
-                   "sharding": f"32x32 tiles round-robin over {n_gpus}", "world_size_seen": world_seen,
-                   "exchange": ((args.exchange + (" (gloo through host memory: --share-gpu, all ranks on ONE device - a plumbing check, not a scaling figure)" if args.share_gpu else "")) if n_gpus > 1 else "none"), "pipeline": args.pipeline,
-                   "batch_ticks": args.batch, "path_state_bytes": pt.path_state_bytes()[0],
-                   "primary_form": (dict(zip(("form", "ms_per_Msample"), (lambda f, ms: (f, [round(m * 1e6, 4) if m >= 0 else None for m in ms]))(*pt.primary_form(min(args.batch, args.steps)))))
-                                    if args.pipeline == "wavefront" else None),
-                   "scene_build_s": round(build_s, 2), "source_sha": sha},
-        "roofline": roofline,
-    }
+    out = report(args, pt, arrays, cam, W, H, n_gpus, world_seen, value, elapsed, times, build_s)
+    out["roofline"] = roofline
     if n_gpus == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(arrays, W, H, cam, lens, args.bounces)
         out["reference_glsl_baseline"] = reference_glsl_baseline()

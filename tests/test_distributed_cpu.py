@@ -209,3 +209,16 @@ def test_bench_dump_outputs_layout(tmp_path):
     a2 = bench.parse_args(bench._extra_argv(["--steps", "7", "--dump-outputs", "out"], {"config": "c3"}, 5, 2))
     assert a2.dump_outputs is None and a2.config == "c3" and a2.steps == 5
     assert bench.parse_args(["--dump-outputs", "out"]).dump_outputs == "out"
+
+
+def test_bench_full_is_opt_in_and_reaches_the_extra_configs():
+    """A plain bench.py run is the headline alone; --full (off by default) asks for everything else, and the extra configs
+    it times are --full runs of their own (parity check and roofline each), never with further extra configs."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    assert bench.parse_args([]).full is False
+    assert bench.parse_args(["--full"]).full is True
+    a2 = bench.parse_args(bench._extra_argv(["--steps", "7", "--full"], {"config": "c5"}, 5, 2))
+    assert a2.full and a2.no_extra_configs and a2.no_cpu_baseline and a2.config == "c5" and a2.steps == 5
+    assert not bench.parse_args(bench._extra_argv(["--steps", "7"], {"config": "c5"}, 5, 2)).full

@@ -1482,7 +1482,7 @@ def test_bench_two_ranks_share_the_gpu(exchange):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--exchange", exchange,
                         "--steps", "3", "--warmup", "2", "--reps", "2", "--width", "640", "--height", "360", "--mesh-n", "24",
-                        "--no-l1-microbench", "--rendezvous-timeout", "120"],
+                        "--no-l1-microbench", "--rendezvous-timeout", "120", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1507,7 +1507,7 @@ def test_bench_c4_four_ranks_share_the_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--share-gpu", "--config", "c4",
-                        "--steps", "3", "--warmup", "1", "--reps", "1", "--no-l1-microbench", "--rendezvous-timeout", "300"],
+                        "--steps", "3", "--warmup", "1", "--reps", "1", "--no-l1-microbench", "--rendezvous-timeout", "300", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -1546,6 +1546,34 @@ def test_bench_dump_outputs_are_the_timed_radiance(tmp_path):
     assert got.dtype == np.float32 and np.array_equal(got, want)
 
 
+def test_bench_plain_line_is_the_headline_and_full_adds_the_rest():
+    """bench.py without --full prints the headline figure and what describes the run, and does nothing else: no oracle
+    check, no roofline (counting ticks of its own), no CPU baseline, no extra configs.  --full adds the parity check and the
+    roofline to the same workload's line; the headline keys mean the same in both."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--reps", "2", "--width", "160",
+            "--height", "96", "--mesh-n", "12"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-extra-configs", "--no-l1-microbench"])):
+        r = subprocess.run(base + extra, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines[mode] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for d in (plain, full):
+        assert d["metric"].startswith("Msamples/s at 160x96 depth 8 ") and d["unit"] == "Msamples/s" and d["dtype"] == "f32"
+        assert d["higher_is_better"] is True and d["steps"] == 3 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert len(d["rep_ms_per_step"]) == 2 and d["config"]["source_sha"]
+    assert plain["metric"] == full["metric"]
+    assert not {"parity_check", "roofline", "cpu_baseline", "reference_glsl_baseline", "extra_configs", "stage_events"} & set(plain)
+    assert full["parity_check"]["equal"] is True and set(full["roofline"]["kernels"]) >= {"primary", "trace", "logic", "resolve"}
+    assert "cpu_baseline" not in full and "extra_configs" not in full
+
+
 @pytest.mark.parametrize("exchange", ["gather", "reduce"])
 def test_bench_two_ranks_over_rccl(exchange):
     """bench.py's two-rank run as the driver starts it (python -m torch.distributed.run: the ranks come from the
@@ -1563,7 +1591,7 @@ def test_bench_two_ranks_over_rccl(exchange):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--exchange", exchange,
                         "--steps", "3", "--warmup", "2", "--reps", "2", "--width", "640", "--height", "360", "--mesh-n", "24",
-                        "--no-l1-microbench", "--rendezvous-timeout", "120"] + (["--share-gpu"] if share else []),
+                        "--no-l1-microbench", "--rendezvous-timeout", "120", "--full"] + (["--share-gpu"] if share else []),
                        capture_output=True, text=True, timeout=900, cwd=root, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -16,10 +16,10 @@ for set in \
  "SQ_INST_LEVEL_VMEM SQ_LEVEL_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_ANY SQ_ACTIVE_INST_VMEM" \
  "GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_INSTS_SALU SQ_INSTS_LDS"; do
   i=$((i+1))
-  timeout 300 rocprofv3 --pmc $set --output-format csv -d $O/p$i -- python3 $R/bench.py --steps 32 --warmup 32 --no-cpu-baseline "$@" > $O/p$i.log 2>&1
+  timeout 300 rocprofv3 --pmc $set --output-format csv -d $O/p$i -- python3 $R/bench.py --steps 32 --warmup 32 --full --no-cpu-baseline "$@" > $O/p$i.log 2>&1
   grep -il "error\|invalid\|not found" $O/p$i.log | head -1
 done
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/kt -- python3 $R/bench.py --steps 32 --warmup 32 --no-cpu-baseline "$@" > $O/kt.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/kt -- python3 $R/bench.py --steps 32 --warmup 32 --full --no-cpu-baseline "$@" > $O/kt.log 2>&1
 python3 - "$O" <<'PY'
 import csv,glob,sys,collections,re
 O=sys.argv[1]

@@ -18,7 +18,7 @@ L1ARG=${L1:+--l1-peak $L1}
 [ -z "$L1" ] && L1ARG=--no-l1-microbench
 echo "l1_peak: $L1" > $O/${T}_l1_peak.txt
 set -- $L1ARG "$@"
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_kt -- python3 $R/bench.py --no-cpu-baseline --no-extra-configs ${KT_ARGS:---steps 20 --warmup 5} "$@" > $O/${T}_kt.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_kt -- python3 $R/bench.py --full --no-cpu-baseline --no-extra-configs ${KT_ARGS:---steps 20 --warmup 5} "$@" > $O/${T}_kt.log 2>&1
 find $O/${T}_kt -name "*kernel_trace.csv" -size +8M -delete
 # the counter passes run the primary launch in the form this (lightly profiled) run settled on: under --pmc the kernels'
 # timings are distorted and the library's form tuner would measure the profiler, not the kernels

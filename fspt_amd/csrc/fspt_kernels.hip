@@ -638,12 +638,12 @@ FM_DEV void tri_point(float u2, float u3, V3 v1, V3 e1, V3 e2, float uv0x, float
   s = fma_(b2, uv2x, fma_(b1, uv1x, b0 * uv0x));
   t = fma_(b2, uv2y, fma_(b1, uv1y, b0 * uv0y));
 }
-// One emitter sample seen from ro: entry e (alias table: slot floor(u1 n), coin = the fraction), the point x on its
+// One emitter sample seen from ro: entry e (alias table: slot floor(v n), coin = the fraction), the point x on its
 // triangle, the unit direction w from ro, the distance, pdf_L = p_e dist^2 / (A |cos_l|) (solid angle; 0 when the
 // triangle is seen edge-on) and Le
 struct LightSample { uint32_t e; V3 x, w, le; float dist, pdf; };
-FM_DEV void light_sample(const DScene &S, V3 ro, float u1, float u2, float u3, LightSample &ls) {
-  const float fn = u1 * (float)S.n_lights;
+FM_DEV void light_sample(const DScene &S, V3 ro, float v, float u2, float u3, LightSample &ls) {
+  const float fn = v * (float)S.n_lights;
   uint32_t i = (uint32_t)fn;
   if (i > S.n_lights - 1u) i = S.n_lights - 1u;
   const uint2 al = S.light_alias[i];
@@ -934,8 +934,11 @@ FM_DEV void shade_hit(const DScene &S, Path &ps, float tHit, int ti, float randB
       const float u0 = rng.next(), u1 = rng.next(), u2 = rng.next(), u3 = rng.next();
       ps.lq = bsdfPdf > 0.0f ? q / bsdfPdf : 0.0f;
       if (u0 < q) { // an emitter: thr f(w) Le cos w_L / (q pdf_L)
+        // the alias draw v = fract(u1 + (u0 / q) 2^-8): u0 / q is uniform given this branch and fills in the bits below
+        // rnd()'s resolution (as coarse as 2^-8), which slot floor(v n) and coin fract(v n) would otherwise lack
+        const float v = fract_(fma_(u0 / q, 0.00390625f, u1));
         LightSample ls;
-        light_sample(S, ro, u1, u2, u3, ls);
+        light_sample(S, ro, v, u2, u3, ls);
         const float cn = dot(macroNormal, ls.w);
         V3 f;
         float pB;
@@ -2752,7 +2755,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_light_weights(const DScene S,
     r[3] = make_float4(h9.w, h10.x, h10.y, h10.z);
   }
 }
-// test hook: light_sample for n queries (ro.xyz, n.xyz, u0..u3; u0 is the strategy value, unused here)
+// test hook: light_sample for n queries (ro.xyz, n.xyz, u0..u3; u0 is the strategy value, unused here; u1 is the alias draw v)
 __global__ __launch_bounds__(BLOCK_THREADS) void k_light_eval(const DScene S, const float *in, uint32_t n, int *entry, float *out) {
   const uint32_t i = blockIdx.x * BLOCK_THREADS + threadIdx.x;
   if (i >= n) return;

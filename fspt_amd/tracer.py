@@ -125,8 +125,9 @@ class Scene:
         return r
 
     def light_sample_eval(self, queries):
-        """The device's emitter sample for queries float32 [n, 10] = (ro.xyz, n.xyz, u0, u1, u2, u3) (fspt_light_sample_eval,
-        a test hook) -> tri int32 [n], out float32 [n, 8] = (point.xyz, pdf_L, Le.rgb, n . w)."""
+        """The device's emitter sample for queries float32 [n, 10] = (ro.xyz, n.xyz, u0, u1, u2, u3; u1 is the
+        alias draw v, u0 is unused) (fspt_light_sample_eval, a test hook) -> tri int32 [n], out float32 [n, 8] =
+        (point.xyz, pdf_L, Le.rgb, n . w)."""
         q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 10)
         tri = np.zeros(q.shape[0], np.int32)
         out = np.zeros((q.shape[0], 8), np.float32)

@@ -157,7 +157,7 @@ int fspt_sampler_eval(int device, uint32_t seed, const uint32_t *pixel, const ui
 int fspt_scene_light_table(fspt_scene *scene, uint32_t *n_tris, uint32_t *n_lights, uint32_t *n_slots, float *weights,
                            float *prob, uint32_t *alias, uint32_t *tris, float *pick, uint32_t *slot_tri);
 /* the device's emitter sample for n queries of 10 floats (ro.xyz, n.xyz, u0, u1, u2, u3; u0 - the strategy value - is not
- * used): tri[i] = the sampled entry's triangle, out[8 i ..] = point.xyz, pdf_L (solid angle, realised selection
+ * used, u1 is the alias draw v itself): tri[i] = the sampled entry's triangle, out[8 i ..] = point.xyz, pdf_L (solid angle, realised selection
  * probability), Le.rgb, n . w.  FSPT_E_STATE when the scene has no emitter. */
 int fspt_light_sample_eval(fspt_scene *scene, const float *in, uint32_t n, int32_t *tri, float *out);
 /* pure host function: the Vose alias table (float64, stored float32) of n weights (finite, >= 0, some > 0) */

@@ -154,9 +154,10 @@ static inline float ray_box(const float *bmin, const float *bmax, vec3 o, vec3 i
 /* ---- intersectScene (tracer.fs:366-404) + processLeaf (355-364) --------- */
 typedef struct { float t; int index; } hit_t;
 
+/* t_start: MAX_T, or (an emitter shadow ray) the bound below which a triangle occludes */
 static hit_t intersect_scene(const oracle_scene *s, vec3 o, vec3 d, oracle_counters *c,
-                             uint32_t *steps_out, uint32_t *leaves_out) {
-  hit_t result = {MAX_T, -1};
+                             uint32_t *steps_out, uint32_t *leaves_out, float t_start) {
+  hit_t result = {t_start, -1};
   int stack[64];
   int ptr = 0;
   stack[ptr++] = -1;
@@ -394,6 +395,7 @@ typedef struct {
   vec3 bsdfThroughput, envThroughput;
   float bsdfPdf; vec2 weights;
   float dielectric;
+  vec3 incident; float metallic, rough; /* (rough: squared, as the lobes see it) */
   float seed0;             /* tracer.fs:458 */
   int inside, specular, refracted;
 } bounce_t;
@@ -517,7 +519,160 @@ static inline void bounce_body(const oracle_scene *s, vec3 ro, vec3 rd, hit_t re
   o->bsdfThroughput = bsdfThroughput; o->envThroughput = envThroughput;
   o->bsdfPdf = bsdfPdf; o->weights = mis_weights(envPdf, bsdfPdf);
   o->dielectric = dielectric;
+  o->incident = incident; o->metallic = metallic; o->rough = rough;
   o->inside = inside; o->specular = specular; o->refracted = refracted;
+}
+
+/* ---- next-event estimation of emissive triangles (FSPT_LIGHTS_EMITTERS) --------------------------
+ * Written from 8.3's definition.  The light table is the caller's (the device's, or one built on the host from the same
+ * weights): per entry its triangle, float32 alias prob / alias and the probability the stored table realises (light_p);
+ * per triangle pick (0 outside the table); q the scene's emitter fraction.  The light record (v1, e1, e2, uvs, texture
+ * layers) is rebuilt from the scene's own arrays. */
+typedef struct {
+  const uint32_t *tris; const float *prob; const uint32_t *alias; const float *light_p; /* per entry */
+  const float *pick;                                                                    /* per triangle */
+  uint32_t n; float q;
+} oracle_lights;
+#define LIGHT_T_SCALE (1.0f - 1.0e-4f) /* the emitter shadow ray ends at dist * LIGHT_T_SCALE */
+
+static inline void tri_edges(const oracle_scene *s, int ti, vec3 *v1, vec3 *e1, vec3 *e2) {
+  vec3 a, b, cc;
+  fetch_tri(s, ti, &a, &b, &cc);
+  *v1 = a; *e1 = v_sub(b, a); *e2 = v_sub(cc, a);
+}
+/* diffuse and emissive layers of triangle ti at uv (u, v): bounce_body's first two texture() taps */
+static void light_tex(const oracle_scene *s, int ti, float u, float v, vec3 *td, vec3 *te) {
+  const float *m = s->mat + (size_t)ti * 12;
+  float a[4], b[4];
+  vec2 tc = {u, v};
+  atlas_fetch(s, tc, m[0], a);
+  atlas_fetch(s, tc, m[1], b);
+  *td = v3(a[0], a[1], a[2]); *te = v3(b[0], b[1], b[2]);
+}
+/* Le = 30 * texEmissive * texDiffuse (tracer.fs:467) */
+static inline vec3 light_le(vec3 td, vec3 te) {
+  return v3((te.x * td.x) * 30.0f, (te.y * td.y) * 30.0f, (te.z * td.z) * 30.0f);
+}
+/* the point of triangle ti at the warped square sample (u2, u3): b0 = 1 - sqrt(u2), b1 = u3 sqrt(u2), b2 = the rest */
+static void tri_point(const oracle_scene *s, int ti, float u2, float u3, vec3 *x, float *tu, float *tv) {
+  vec3 v1, e1, e2;
+  tri_edges(s, ti, &v1, &e1, &e2);
+  const float *uv = s->uv + (size_t)ti * 6;
+  float su = sqrtf(u2), b1 = u3 * su, b2 = su - b1, b0 = 1.0f - su;
+  *x = v_fma(e2, b2, v_fma(e1, b1, v1));
+  *tu = om_fma(b2, uv[4], om_fma(b1, uv[2], b0 * uv[0]));
+  *tv = om_fma(b2, uv[5], om_fma(b1, uv[3], b0 * uv[1]));
+}
+/* k_light_weights: A * mean luma(Le) over the 4 x 4 cell centres of the warped square, summed in order */
+static float light_weight(const oracle_scene *s, int ti) {
+  float sum = 0.0f;
+  for (int k = 0; k < 16; ++k) {
+    vec3 x, td, te; float tu, tv;
+    tri_point(s, ti, ((float)(k & 3) + 0.5f) * 0.25f, ((float)(k >> 2) + 0.5f) * 0.25f, &x, &tu, &tv);
+    light_tex(s, ti, tu, tv, &td, &te);
+    vec3 le = light_le(td, te);
+    sum += om_fma(0.0722f, le.z, om_fma(0.7152f, le.y, 0.2126f * le.x));
+  }
+  vec3 v1, e1, e2;
+  tri_edges(s, ti, &v1, &e1, &e2);
+  vec3 cr = v_cross(e1, e2);
+  return (0.5f * sqrtf(v_dot(cr, cr))) * (sum * 0.0625f);
+}
+typedef struct { uint32_t e; int tri; vec3 x, w, le; float dist, pdf; } light_sample_t;
+/* one emitter sample seen from ro: entry (slot floor(v n), coin = its fraction against prob), point, direction,
+ * pdf_L = p_e dist^2 / (A |n_g . w|) (0 edge-on), Le */
+static void light_sample(const oracle_scene *s, const oracle_lights *L, vec3 ro, float v, float u2, float u3,
+                         light_sample_t *ls) {
+  float fn = v * (float)L->n;
+  uint32_t i = (uint32_t)fn;
+  if (i > L->n - 1u) i = L->n - 1u;
+  ls->e = (fn - (float)i) < L->prob[i] ? i : L->alias[i];
+  ls->tri = (int)L->tris[ls->e];
+  float tu, tv;
+  tri_point(s, ls->tri, u2, u3, &ls->x, &tu, &tv);
+  vec3 td, te;
+  light_tex(s, ls->tri, tu, tv, &td, &te);
+  ls->le = light_le(td, te);
+  vec3 dv = v_sub(ls->x, ro);
+  float d2 = v_dot(dv, dv);
+  ls->dist = sqrtf(d2);
+  ls->w = v_scale(dv, 1.0f / ls->dist);
+  vec3 v1, e1, e2;
+  tri_edges(s, ls->tri, &v1, &e1, &e2);
+  float gl = om_abs(v_dot(v_cross(e1, e2), ls->w)); /* 2 A |cos_l| */
+  ls->pdf = gl > 0.0f ? ((L->light_p[ls->e] * d2) * 2.0f) / gl : 0.0f;
+}
+/* The weight of the emission of the hit (index, t) of ray direction rd against emitter sampling at the vertex that cast
+ * it: pb^2 / (pb^2 + (q pick t^2 / (A |n_g . rd|))^2) with lq = q / pb; exactly 1 for lq = 0 or pick = 0 */
+static float emission_weight(const oracle_scene *s, const oracle_lights *L, float lq, int index, float t, vec3 rd) {
+  if (!L || !(lq > 0.0f)) return 1.0f;
+  float pk = L->pick[index];
+  if (!(pk > 0.0f)) return 1.0f;
+  vec3 v1, e1, e2;
+  tri_edges(s, index, &v1, &e1, &e2);
+  float den = 0.5f * om_abs(v_dot(v_cross(e1, e2), rd)); /* A |cos_l| */
+  float x = den > 0.0f ? ((lq * pk) * (t * t)) / den : INFINITY;
+  return 1.0f / om_fma(x, x, 1.0f);
+}
+/* What a vertex's one shadow ray carries: with q = 0 the reference's environment NEE (tracer.fs:500-505);
+ * with q > 0 the strategy u0 picks - an emitter point (contribution thr f Le cos w_L / (q pdf_L), ray bound lt) or the
+ * environment (contribution / (1 - q)).  lq = q / pb weights the emission the extension ray finds. */
+typedef struct {
+  int hasShadow, strategy; /* strategy 0: q = 0, 1: environment, 2: emitter */
+  vec3 dir, pend; float wx, lt, lq, q;
+  float u[4], v; light_sample_t ls; float cn, pdfB, wL;
+} nee_t;
+static void vertex_nee(const oracle_scene *s, const oracle_lights *L, const bounce_t *b, vec3 thr, int i, int iters,
+                       uint32_t numBounces, rng_t *g, nee_t *n) {
+  memset(n, 0, sizeof(*n));
+  n->hasShadow = b->dielectric < 0.0f && b->cosEnv > 0.0f;
+  n->dir = b->envDir;
+  n->pend = v_mul(thr, b->envThroughput);
+  n->wx = b->weights.x;
+  n->lt = MAX_T;
+  n->ls.tri = -1;
+  if (!L) return;
+  /* the q rules: the extension ray's hit is shaded, the vertex reflects from outside a non-dielectric, and the lobe's
+   * direction density is its own pdf (Lambert, or the specular lobe at metallic = 1) */
+  int lobe_ok = !b->specular || b->metallic >= 1.0f;
+  float q = (L->q > 0.0f && L->n > 0u && lobe_ok && !b->inside && b->dielectric < 0.0f && i + 1 < (int)numBounces &&
+             iters + 1 < ORACLE_MAX_PATH_ITERS) ? L->q : 0.0f;
+  n->q = q;
+  if (!(q > 0.0f)) return;
+  for (int k = 0; k < 4; ++k) n->u[k] = rnd(g);
+  n->lq = b->bsdfPdf > 0.0f ? q / b->bsdfPdf : 0.0f;
+  if (n->u[0] < q) {
+    n->strategy = 2;
+    /* the alias draw v = fract(u1 + (u0 / q) 2^-8): given u0 < q, u0 / q is uniform and supplies the bits below the
+     * resolution of rnd() (2^-8 at worst), without which slot and coin misrealise the table's probabilities */
+    float v = om_fma(n->u[0] / q, 0.00390625f, n->u[1]);
+    n->v = v - om_floor(v);
+    light_sample(s, L, b->ro, n->v, n->u[2], n->u[3], &n->ls);
+    vec3 w = n->ls.w;
+    n->cn = v_dot(b->macroNormal, w);
+    vec3 f;
+    if (b->specular) {
+      f = eval_specular(b->incident, b->macroNormal, b->texDiffuse, b->metallic, b->rough, w);
+      n->pdfB = gtr2_pdf(b->incident, b->macroNormal, b->rough, w);
+    } else {
+      f = v3(b->texDiffuse.x * INV_PI_F, b->texDiffuse.y * INV_PI_F, b->texDiffuse.z * INV_PI_F);
+      n->pdfB = om_abs(n->cn) * INV_PI_F;
+    }
+    float qp = q * n->ls.pdf, a2 = qp * qp;
+    float den = om_fma(n->pdfB, n->pdfB, a2);
+    n->wL = a2 / den;
+    float sc = ((n->cn * a2) / den) / qp; /* cos w_L / (q pdf_L) */
+    n->hasShadow = n->cn > 0.0f && n->ls.pdf > 0.0f && sc < INFINITY;
+    n->dir = w;
+    n->pend = v3(((thr.x * f.x) * n->ls.le.x) * sc, ((thr.y * f.y) * n->ls.le.y) * sc, ((thr.z * f.z) * n->ls.le.z) * sc);
+    n->wx = 1.0f;
+    n->lt = n->ls.dist * LIGHT_T_SCALE;
+  } else {
+    n->strategy = 1;
+    float sc = n->wx / (1.0f - q);
+    n->pend = v_scale(n->pend, sc);
+    n->wx = 1.0f;
+  }
 }
 
 /* ---- the rest of the iteration, tracer.fs:467 and 500-512: emission, NEE shadow ray, extension ray ------
@@ -540,24 +695,25 @@ static inline vec3 env_sample_rp(const oracle_scene *s, vec3 dir, float envTheta
   }
   return own;
 }
-static inline int bounce_tail(const oracle_scene *s, const bounce_t *b, float envTheta, oracle_counters *c,
-                              vec3 *thr_io, vec3 *color_io, hit_t *result, replay_t *sig) {
+/* emw: the emission's MIS weight (emission_weight; 1 - the reference's bits - without emitter NEE), n: the shadow ray */
+static inline int bounce_tail(const oracle_scene *s, const bounce_t *b, float envTheta, oracle_counters *c, float emw,
+                              const nee_t *n, vec3 *thr_io, vec3 *color_io, hit_t *result, replay_t *sig) {
   vec3 thr = *thr_io, color = *color_io;
   /* tracer.fs:467 */
-  color = v3(om_fma((thr.x * b->texEmissive.x) * b->texDiffuse.x, 30.0f, color.x),
-             om_fma((thr.y * b->texEmissive.y) * b->texDiffuse.y, 30.0f, color.y),
-             om_fma((thr.z * b->texEmissive.z) * b->texDiffuse.z, 30.0f, color.z));
-  if (b->dielectric < 0.0f && b->cosEnv > 0.0f) {
-    hit_t shadow = intersect_scene(s, b->ro, b->envDir, c, NULL, NULL);
+  color = v3(om_fma(((thr.x * b->texEmissive.x) * b->texDiffuse.x) * emw, 30.0f, color.x),
+             om_fma(((thr.y * b->texEmissive.y) * b->texDiffuse.y) * emw, 30.0f, color.y),
+             om_fma(((thr.z * b->texEmissive.z) * b->texDiffuse.z) * emw, 30.0f, color.z));
+  if (n->hasShadow) {
+    hit_t shadow = intersect_scene(s, b->ro, n->dir, c, NULL, NULL, n->lt);
     sig_add(sig, shadow.index);
     if (shadow.index == -1) {
-      vec3 es = env_sample_rp(s, b->envDir, envTheta, c, sig);
-      color = v3(om_fma((thr.x * b->envThroughput.x) * es.x, b->weights.x, color.x),
-                 om_fma((thr.y * b->envThroughput.y) * es.y, b->weights.x, color.y),
-                 om_fma((thr.z * b->envThroughput.z) * es.z, b->weights.x, color.z));
+      /* (an emitter's contribution is all in pend) */
+      vec3 es = n->lt < MAX_T ? v3(1.0f, 1.0f, 1.0f) : env_sample_rp(s, n->dir, envTheta, c, sig);
+      color = v3(om_fma(n->pend.x * es.x, n->wx, color.x), om_fma(n->pend.y * es.y, n->wx, color.y),
+                 om_fma(n->pend.z * es.z, n->wx, color.z));
     }
   }
-  *result = intersect_scene(s, b->ro, b->rd, c, NULL, NULL);
+  *result = intersect_scene(s, b->ro, b->rd, c, NULL, NULL, MAX_T);
   sig_add(sig, result->index);
   thr = v_mul(thr, b->bsdfThroughput);
   int left = 0;
@@ -574,10 +730,11 @@ static inline int bounce_tail(const oracle_scene *s, const bounce_t *b, float en
 /* ---- tracer.fs main (436-518) for one pixel ----------------------------- */
 /* ... the path itself (tracer.fs:439-514): the sample's colour before the clamp of tracer.fs:515.  `g`: the tracer's
  * random numbers - its own sin-hash, or (whole-path replay) the values the reference GLSL's rnd() returned. */
+/* L: emitter NEE, NULL: off. */
 static vec3 trace_path(const oracle_scene *s, vec3 ro, vec3 rd, float randBase, float envTheta, uint32_t numBounces,
-                       rng_t *gp, oracle_counters *c, oracle_first_hit *fh, replay_t *sig) {
+                       rng_t *gp, oracle_counters *c, oracle_first_hit *fh, replay_t *sig, const oracle_lights *L) {
   rng_t g = *gp;
-  hit_t result = intersect_scene(s, ro, rd, c, NULL, NULL);
+  hit_t result = intersect_scene(s, ro, rd, c, NULL, NULL, MAX_T);
   sig_add(sig, result.index);
   vec3 color = v3(0.0f, 0.0f, 0.0f);
   if (fh) { memset(fh, 0, sizeof(*fh)); fh->t = result.t; fh->index = result.index; }
@@ -586,14 +743,19 @@ static vec3 trace_path(const oracle_scene *s, vec3 ro, vec3 rd, float randBase, 
   } else {
     vec3 thr = v3(1.0f, 1.0f, 1.0f);
     int iters = 0;
+    float lq = 0.0f; /* q / pb of the vertex that cast rd (0: a camera ray, or q = 0) */
     for (int i = 0; i < (int)numBounces && iters < ORACLE_MAX_PATH_ITERS; ++i, ++iters) {
       if (c) c->shades++;
+      const float emw = emission_weight(s, L, lq, result.index, result.t, rd);
       bounce_t b;
       bounce_body(s, ro, rd, result, randBase, envTheta, &g, (fh && iters == 0) ? fh : NULL,
                   (sig && sig->tex && (uint32_t)iters < sig->tex_limit) ? sig->tex + (size_t)iters * 12 : NULL, &b);
+      nee_t n;
+      vertex_nee(s, L, &b, thr, i, iters, numBounces, &g, &n);
+      lq = n.lq;
       ro = b.ro; rd = b.rd;
       if (b.refracted) i--; /* tracer.fs:488 */
-      if (bounce_tail(s, &b, envTheta, c, &thr, &color, &result, sig)) break;
+      if (bounce_tail(s, &b, envTheta, c, emw, &n, &thr, &color, &result, sig)) break;
     }
   }
   *gp = g;
@@ -601,10 +763,10 @@ static vec3 trace_path(const oracle_scene *s, vec3 ro, vec3 rd, float randBase, 
 }
 static void trace_pixel(const oracle_scene *s, vec3 ro, vec3 rd, uint32_t tick, float randBase,
                         float envTheta, uint32_t numBounces, float *accum /*rgba*/,
-                        oracle_counters *c, oracle_first_hit *fh) {
+                        oracle_counters *c, oracle_first_hit *fh, const oracle_lights *L) {
   rng_t g = {0.0f, NULL, 0, 0};
   if (c) c->samples++;
-  vec3 color = trace_path(s, ro, rd, randBase, envTheta, numBounces, &g, c, fh, NULL);
+  vec3 color = trace_path(s, ro, rd, randBase, envTheta, numBounces, &g, c, fh, NULL, L);
   color = v3(om_clamp(color.x, 0.0f, 1024.0f), om_clamp(color.y, 0.0f, 1024.0f), om_clamp(color.z, 0.0f, 1024.0f));
   float ft = (float)tick;
   float den = ft + 1.0f;
@@ -681,10 +843,10 @@ void oracle_camera_probe(uint32_t W, uint32_t H, const float P[3], const float I
 
 /* One tick of drawTracer (main.js:758-807): every pixel whose tile belongs to
  * this shard (tile index % n_shards == shard; n_shards = 1 -> all). */
-void oracle_trace(const oracle_scene *s, uint32_t W, uint32_t H, const float *pos, const float *dir,
-                  uint32_t tick, float randBase, float envTheta, uint32_t numBounces, float *accum,
-                  oracle_counters *counters, oracle_first_hit *first_hits, uint32_t shard,
-                  uint32_t n_shards, uint32_t tile) {
+static void trace_tick(const oracle_scene *s, uint32_t W, uint32_t H, const float *pos, const float *dir,
+                       uint32_t tick, float randBase, float envTheta, uint32_t numBounces, float *accum,
+                       oracle_counters *counters, oracle_first_hit *first_hits, uint32_t shard,
+                       uint32_t n_shards, uint32_t tile, const oracle_lights *L) {
   oracle_counters total;
   memset(&total, 0, sizeof(total));
   if (n_shards == 0) n_shards = 1;
@@ -703,7 +865,7 @@ void oracle_trace(const oracle_scene *s, uint32_t W, uint32_t H, const float *po
         vec3 ro = v3(pos[p * 4], pos[p * 4 + 1], pos[p * 4 + 2]);
         vec3 rd = v3(dir[p * 4], dir[p * 4 + 1], dir[p * 4 + 2]);
         trace_pixel(s, ro, rd, tick, randBase, envTheta, numBounces, accum + p * 4,
-                    counters ? &local : NULL, first_hits ? first_hits + p : NULL);
+                    counters ? &local : NULL, first_hits ? first_hits + p : NULL, L);
       }
 #pragma omp critical
     {
@@ -716,6 +878,13 @@ void oracle_trace(const oracle_scene *s, uint32_t W, uint32_t H, const float *po
     counters->leaves += total.leaves; counters->shades += total.shades;
     counters->env_lookups += total.env_lookups;
   }
+}
+void oracle_trace(const oracle_scene *s, uint32_t W, uint32_t H, const float *pos, const float *dir,
+                  uint32_t tick, float randBase, float envTheta, uint32_t numBounces, float *accum,
+                  oracle_counters *counters, oracle_first_hit *first_hits, uint32_t shard,
+                  uint32_t n_shards, uint32_t tile) {
+  trace_tick(s, W, H, pos, dir, tick, randBase, envTheta, numBounces, accum, counters, first_hits, shard, n_shards, tile,
+             NULL);
 }
 
 /* bvh_test.fs main (224-232), the reference's `mode=test` replacement of tracer.fs (main.js:879-883): the
@@ -735,7 +904,7 @@ void oracle_trace_test(const oracle_scene *s, uint32_t W, uint32_t H, const floa
       vec3 ro = v3(pos[p * 4], pos[p * 4 + 1], pos[p * 4 + 2]);
       vec3 rd = v3(dir[p * 4], dir[p * 4 + 1], dir[p * 4 + 2]);
       uint32_t st, lv;
-      (void)intersect_scene(s, ro, rd, NULL, &st, &lv);
+      (void)intersect_scene(s, ro, rd, NULL, &st, &lv, MAX_T);
       float c = (float)st * 0.001f;
       float ft = (float)tick, den = ft + 1.0f;
       float *a = accum + p * 4;
@@ -753,7 +922,7 @@ void oracle_intersect(const oracle_scene *s, const float *rays, uint32_t n, floa
     vec3 o = v3(rays[i * 6], rays[i * 6 + 1], rays[i * 6 + 2]);
     vec3 d = v3(rays[i * 6 + 3], rays[i * 6 + 4], rays[i * 6 + 5]);
     uint32_t st, lv;
-    hit_t h = intersect_scene(s, o, d, NULL, &st, &lv);
+    hit_t h = intersect_scene(s, o, d, NULL, &st, &lv, MAX_T);
     t_out[i] = h.t; index_out[i] = h.index;
     if (steps_out) steps_out[i] = st;
     if (leaves_out) leaves_out[i] = lv;
@@ -769,11 +938,12 @@ float oracle_rand_base_next(uint64_t *state) {
   return ((float)(r >> 40) * (1.0f / 16777216.0f)) * 10000.0f;
 }
 
-/* n_ticks x (drawCamera + drawTracer), the reference tick() loop (main.js:838-857). */
-void oracle_render(const oracle_scene *s, uint32_t W, uint32_t H, const float P[3], const float I[3],
-                   float fovScale, const float lens[2], float envTheta, uint32_t numBounces,
-                   uint32_t first_tick, uint32_t n_ticks, uint64_t seed, float *accum,
-                   oracle_counters *counters, uint32_t shard, uint32_t n_shards, uint32_t tile) {
+/* n_ticks x (drawCamera + drawTracer), the reference tick() loop (main.js:838-857); L: emitter NEE (NULL: off). */
+void oracle_render_lights(const oracle_scene *s, uint32_t W, uint32_t H, const float P[3], const float I[3],
+                          float fovScale, const float lens[2], float envTheta, uint32_t numBounces,
+                          uint32_t first_tick, uint32_t n_ticks, uint64_t seed, float *accum,
+                          oracle_counters *counters, uint32_t shard, uint32_t n_shards, uint32_t tile,
+                          const oracle_lights *L) {
   float *pos = (float *)malloc((size_t)W * H * 4 * sizeof(float));
   float *dir = (float *)malloc((size_t)W * H * 4 * sizeof(float));
   uint64_t st = seed;
@@ -781,10 +951,17 @@ void oracle_render(const oracle_scene *s, uint32_t W, uint32_t H, const float P[
     float rb_cam = oracle_rand_base_next(&st);
     float rb_trace = oracle_rand_base_next(&st);
     oracle_camera(W, H, P, I, fovScale, lens, rb_cam, pos, dir);
-    oracle_trace(s, W, H, pos, dir, first_tick + k, rb_trace, envTheta, numBounces, accum, counters, NULL,
-                 shard, n_shards, tile);
+    trace_tick(s, W, H, pos, dir, first_tick + k, rb_trace, envTheta, numBounces, accum, counters, NULL,
+               shard, n_shards, tile, L);
   }
   free(pos); free(dir);
+}
+void oracle_render(const oracle_scene *s, uint32_t W, uint32_t H, const float P[3], const float I[3],
+                   float fovScale, const float lens[2], float envTheta, uint32_t numBounces,
+                   uint32_t first_tick, uint32_t n_ticks, uint64_t seed, float *accum,
+                   oracle_counters *counters, uint32_t shard, uint32_t n_shards, uint32_t tile) {
+  oracle_render_lights(s, W, H, P, I, fovScale, lens, envTheta, numBounces, first_tick, n_ticks, seed, accum, counters,
+                       shard, n_shards, tile, NULL);
 }
 
 /* math primitives for bitwise comparison with the device (fspt_math_eval) */
@@ -914,7 +1091,9 @@ void oracle_bounce_probe(const oracle_scene *s, const float *rays, const float *
     o[32] = b.macroNormal.x; o[33] = b.macroNormal.y; o[34] = b.macroNormal.z; o[35] = b.dielectric;
     vec3 thr = v3(1.0f, 1.0f, 1.0f), color = v3(0.0f, 0.0f, 0.0f);
     hit_t next;
-    (void)bounce_tail(s, &b, envTheta, NULL, &thr, &color, &next, NULL);
+    nee_t nn;
+    vertex_nee(s, NULL, &b, thr, 0, 0, 0u, &g, &nn);
+    (void)bounce_tail(s, &b, envTheta, NULL, 1.0f, &nn, &thr, &color, &next, NULL);
     o[36] = color.x; o[37] = color.y; o[38] = color.z; o[39] = (float)next.index;
     o[40] = thr.x; o[41] = thr.y; o[42] = thr.z; o[43] = next.t;
   }
@@ -929,11 +1108,12 @@ void oracle_bounce_probe(const oracle_scene *s, const float *rays, const float *
  * were recorded - it took another branch somewhere), out_sig = {hash, calls} as sig_add defines them.  env_rec: also
  * replay what the GLSL's envSample returned for the path's k-th environment lookup, tex_rec: the four texture() results
  * of its k-th loop iteration (replay_t) - with all three the comparison is of the path LOGIC and its arithmetic alone. */
-void oracle_path_replay(const oracle_scene *s, const float *pos /* n x 4 */, const float *dir /* n x 4 */, uint32_t n,
+void oracle_path_replay_lights(const oracle_scene *s, const float *pos /* n x 4 */, const float *dir /* n x 4 */, uint32_t n,
                         const float *rec, uint32_t rec_stride, const uint32_t *rec_count, float randBase, float envTheta,
                         uint32_t numBounces, const float *env_rec /* n x env_stride x 3, or NULL */, uint32_t env_stride,
                         const float *tex_rec /* n x tex_stride x 12, or NULL */, uint32_t tex_stride,
-                        float *out_color /* n x 3 */, uint32_t *out_used, uint32_t *out_sig /* n x 2 */, uint32_t *out_env_used) {
+                        float *out_color /* n x 3 */, uint32_t *out_used, uint32_t *out_sig /* n x 2 */, uint32_t *out_env_used,
+                        const oracle_lights *L) {
 #pragma omp parallel for schedule(dynamic, 64)
   for (int64_t i = 0; i < (int64_t)n; ++i) {
     rng_t g = {0.0f, rec + (size_t)i * rec_stride, 0, rec_count[i] < rec_stride ? rec_count[i] : rec_stride};
@@ -941,7 +1121,7 @@ void oracle_path_replay(const oracle_scene *s, const float *pos /* n x 4 */, con
     replay_t rp = {{0u, 0u}, env_rec ? env_rec + (size_t)i * env_stride * 3 : NULL, 0u, env_stride,
                    tex_rec ? tex_rec + (size_t)i * tex_stride * 12 : NULL, tex_stride};
     vec3 color = trace_path(s, v3(pos[i * 4], pos[i * 4 + 1], pos[i * 4 + 2]), v3(dir[i * 4], dir[i * 4 + 1], dir[i * 4 + 2]),
-                            randBase, envTheta, numBounces, &g, NULL, NULL, &rp);
+                            randBase, envTheta, numBounces, &g, NULL, NULL, &rp, L);
     if (rec_count[i] == 0 && g.used) g.used = 0xFFFFFFFFu;
     out_color[i * 3] = om_clamp(color.x, 0.0f, 1024.0f);
     out_color[i * 3 + 1] = om_clamp(color.y, 0.0f, 1024.0f);
@@ -950,6 +1130,14 @@ void oracle_path_replay(const oracle_scene *s, const float *pos /* n x 4 */, con
     out_sig[i * 2] = rp.sig[0]; out_sig[i * 2 + 1] = rp.sig[1];
     if (out_env_used) out_env_used[i] = rp.env_used;
   }
+}
+
+void oracle_path_replay(const oracle_scene *s, const float *pos, const float *dir, uint32_t n, const float *rec,
+                        uint32_t rec_stride, const uint32_t *rec_count, float randBase, float envTheta, uint32_t numBounces,
+                        const float *env_rec, uint32_t env_stride, const float *tex_rec, uint32_t tex_stride,
+                        float *out_color, uint32_t *out_used, uint32_t *out_sig, uint32_t *out_env_used) {
+  oracle_path_replay_lights(s, pos, dir, n, rec, rec_stride, rec_count, randBase, envTheta, numBounces, env_rec, env_stride,
+                            tex_rec, tex_stride, out_color, out_used, out_sig, out_env_used, NULL);
 }
 
 /* rnd() k times from a seed (tracer.fs:181): the sequence the probes above are replayed against. */
@@ -1025,4 +1213,75 @@ void oracle_draw_scaled(const float *acc, uint32_t W, uint32_t H, float exposure
       for (int k = 0; k < 3; ++k) o[k] = (uint8_t)om_floor(om_fma(om_clamp(g[k], 0.0f, 1.0f), 255.0f, 0.5f));
       o[3] = 255;
     }
+}
+
+/* ---- emitter NEE probes ---------------------------------------------------------------------------- */
+/* k_light_weights for triangles tris[0..n) */
+void oracle_light_weights(const oracle_scene *s, const uint32_t *tris, uint32_t n, float *w) {
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < (int64_t)n; ++i) w[i] = light_weight(s, (int)tris[i]);
+}
+
+/* fspt_light_sample_eval's layout: queries n x 10 (ro.xyz, n.xyz, u0..u3; u0 unused) -> tri[n] (the entry's triangle),
+ * out n x 8 (x.xyz, pdf_L, Le.rgb, n . w) */
+void oracle_light_sample(const oracle_scene *s, const oracle_lights *L, const float *in, uint32_t n, int32_t *tri,
+                         float *out) {
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < (int64_t)n; ++i) {
+    const float *q = in + (size_t)i * 10;
+    light_sample_t ls;
+    light_sample(s, L, v3(q[0], q[1], q[2]), q[7], q[8], q[9], &ls);
+    tri[i] = ls.tri;
+    float *o = out + (size_t)i * 8;
+    o[0] = ls.x.x; o[1] = ls.x.y; o[2] = ls.x.z; o[3] = ls.pdf;
+    o[4] = ls.le.x; o[5] = ls.le.y; o[6] = ls.le.z; o[7] = v_dot(v3(q[3], q[4], q[5]), ls.w);
+  }
+}
+
+/* One vertex of a path with emitter NEE: the hit (t, index) of ray (ro, rd) is shaded as bounce `bounce` of a path of
+ * num_bounces (iteration bounce, throughput 1), its random numbers replayed from rec (rec_stride per item, call order:
+ * the reference's draws, then u0..u3) or, rec NULL, the tracer's own from randBase.  out n x ORACLE_VERTEX_FLOATS:
+ *   0 strategy (0 q = 0, 1 environment, 2 emitter)  1 entry (-1)  2 pdf_L  3 pdf_B  4 w_L  5-7 pend  8 lt  9 lq  10 q
+ *   11 hasShadow  12-14 shadow direction  15 wx  16 specular  17 metallic  18 rough (squared)  19 rnd() calls
+ *   20-22 ro  23-25 macroNormal  26-28 incident  29-31 texDiffuse  32-34 light point  35-37 Le  38 dist  39 n . w
+ *   40 bsdfPdf  41 light triangle (-1)  42-45 u0..u3  46 inside  47 dielectric */
+#define ORACLE_VERTEX_FLOATS 48
+void oracle_light_vertex_probe(const oracle_scene *s, const oracle_lights *L, const float *rays, const float *t_in,
+                               const int32_t *index_in, const float *rec, uint32_t rec_stride, float randBase,
+                               float envTheta, uint32_t bounce, uint32_t numBounces, uint32_t n, float *out) {
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < (int64_t)n; ++i) {
+    float *o = out + (size_t)i * ORACLE_VERTEX_FLOATS;
+    for (int k = 0; k < ORACLE_VERTEX_FLOATS; ++k) o[k] = 0.0f;
+    if (index_in[i] < 0) continue;
+    vec3 ro = v3(rays[i * 6], rays[i * 6 + 1], rays[i * 6 + 2]);
+    vec3 rd = v3(rays[i * 6 + 3], rays[i * 6 + 4], rays[i * 6 + 5]);
+    hit_t h = {t_in[i], index_in[i]};
+    rng_t g = {0.0f, rec ? rec + (size_t)i * rec_stride : NULL, 0, rec ? rec_stride : 0};
+    bounce_t b;
+    bounce_body(s, ro, rd, h, randBase, envTheta, &g, NULL, NULL, &b);
+    nee_t nn;
+    vertex_nee(s, L, &b, v3(1.0f, 1.0f, 1.0f), (int)bounce, (int)bounce, numBounces, &g, &nn);
+    o[0] = (float)nn.strategy; o[1] = nn.strategy == 2 ? (float)nn.ls.e : -1.0f;
+    o[2] = nn.ls.pdf; o[3] = nn.pdfB; o[4] = nn.wL;
+    o[5] = nn.pend.x; o[6] = nn.pend.y; o[7] = nn.pend.z; o[8] = nn.lt; o[9] = nn.lq; o[10] = nn.q;
+    o[11] = (float)nn.hasShadow; o[12] = nn.dir.x; o[13] = nn.dir.y; o[14] = nn.dir.z; o[15] = nn.wx;
+    o[16] = (float)b.specular; o[17] = b.metallic; o[18] = b.rough; o[19] = (float)g.used;
+    o[20] = b.ro.x; o[21] = b.ro.y; o[22] = b.ro.z;
+    o[23] = b.macroNormal.x; o[24] = b.macroNormal.y; o[25] = b.macroNormal.z;
+    o[26] = b.incident.x; o[27] = b.incident.y; o[28] = b.incident.z;
+    o[29] = b.texDiffuse.x; o[30] = b.texDiffuse.y; o[31] = b.texDiffuse.z;
+    o[32] = nn.ls.x.x; o[33] = nn.ls.x.y; o[34] = nn.ls.x.z;
+    o[35] = nn.ls.le.x; o[36] = nn.ls.le.y; o[37] = nn.ls.le.z; o[38] = nn.ls.dist; o[39] = nn.cn;
+    o[40] = b.bsdfPdf; o[41] = (float)nn.ls.tri;
+    for (int k = 0; k < 4; ++k) o[42 + k] = nn.u[k];
+    o[46] = (float)b.inside; o[47] = b.dielectric;
+  }
+}
+
+/* emission_weight for n hits (index, t) of rays rd (n x 3) cast by vertices with lq[n] */
+void oracle_emission_weight_probe(const oracle_scene *s, const oracle_lights *L, const float *lq, const float *rd,
+                                  const float *t_in, const int32_t *index_in, uint32_t n, float *emw) {
+  for (uint32_t i = 0; i < n; ++i)
+    emw[i] = index_in[i] < 0 ? 0.0f : emission_weight(s, L, lq[i], index_in[i], t_in[i], v3(rd[i * 3], rd[i * 3 + 1], rd[i * 3 + 2]));
 }

@@ -12,7 +12,7 @@ import pytest
 
 import lights_ref as R
 import oracle as O
-from fspt_amd import PathTracer, Scene
+from fspt_amd import PathTracer, Scene, light_alias_table
 from fspt_amd import scene as S
 
 pytestmark = pytest.mark.gpu
@@ -28,6 +28,11 @@ def e1():
 @pytest.fixture(scope="module")
 def e2():
     return R.scene_e2()
+
+
+@pytest.fixture(scope="module")
+def e3():
+    return R.scene_e3()
 
 
 def make_pt(arrays, W, H, nb=4, lights=True, sampler=None, fraction=0.5, seed=7):
@@ -333,3 +338,170 @@ def test_node_set_lights_matches_python(e1, tmp_path):
                           timeout=300)
     got = np.fromfile(os.path.join(d, "out.bin"), np.float32).reshape(H, W, 4)
     assert np.array_equal(got, want)
+
+
+# ---- 9: the hooks, bit for bit against the oracle ------------------------------------------------------------------
+@pytest.mark.parametrize("scene", ["e1", "e2", "e3"])
+def test_light_weights_match_oracle(request, scene):
+    arrays = request.getfixturevalue(scene)
+    sc = Scene(arrays)
+    t = sc.light_table()
+    sc.close()
+    T = arrays.tri.size // 9
+    in_leaf = np.zeros(T, bool)
+    in_leaf[t["slot_tri"][t["slot_tri"] < T]] = True
+    want = np.where(in_leaf, O.light_weights(arrays, np.arange(T)), np.float32(0))
+    assert np.array_equal(t["weights"].view(np.uint32), want.view(np.uint32))
+    prob, alias = light_alias_table(t["weights"][t["tris"]])
+    assert np.array_equal(t["prob"], prob) and np.array_equal(t["alias"], alias)
+    assert np.array_equal(R.device_table(t)["light_p"], O.realised_p(prob, alias))
+    if scene == "e3":
+        assert (t["alias"] != np.arange(t["tris"].size)).any()
+
+
+def edge_queries(t, n, seed):
+    """queries(): then edge values of u1 (0, k / n, prevfloat(1)), the alias coin exactly at prob, and u2 / u3 at 0 and
+    prevfloat(1)."""
+    q = queries(n, seed)
+    m = t["tris"].size
+    one = np.nextafter(np.float32(1), np.float32(0))
+    k = np.arange(m, dtype=np.float32)
+    edge_u1 = np.concatenate([[0.0, one], k / np.float32(m), (k + t["prob"]) / np.float32(m)]).astype(np.float32)
+    rows = []
+    for u1 in edge_u1:
+        for u2 in (0.0, one, 0.5):
+            for u3 in (0.0, one, 0.25):
+                rows.append((u1, u2, u3))
+    r = np.array(rows, np.float32)
+    q[:len(r), 7:10] = r
+    return q
+
+
+@pytest.mark.parametrize("scene", ["e2", "e3"])
+def test_light_sample_matches_oracle(request, scene):
+    arrays = request.getfixturevalue(scene)
+    sc = Scene(arrays)
+    t = sc.light_table()
+    q = edge_queries(t, 1 << 15, 6)
+    tri, out = sc.light_sample_eval(q)
+    sc.close()
+    otri, oout = O.light_sample(arrays, R.device_table(t), q)
+    assert np.array_equal(tri, otri)
+    assert np.array_equal(out.view(np.uint32), oout.view(np.uint32))
+
+
+# ---- 10: whole frames, bit for bit against the oracle --------------------------------------------------------------
+def oracle_table(arrays, fraction):
+    sc = Scene(arrays)
+    t = R.device_table(sc.light_table())
+    sc.close()
+    return t, R.env_q(arrays, fraction)
+
+
+@pytest.mark.parametrize("scene", ["e1", "e2", "e3"])
+@pytest.mark.parametrize("nb", [2, 3, 4, 8, 70])
+def test_frames_match_oracle(request, scene, nb):
+    """rnd(): per tick (tick 0) and accumulated (ticks 1..3 on top, first_tick 1), every fraction, three pipelines."""
+    arrays = request.getfixturevalue(scene)
+    W, H = 64, 48
+    for fraction in (0.25, 0.5, 1.0):
+        lights = oracle_table(arrays, fraction)
+        for pipeline in ("megakernel", "wavefront", "stream"):
+            pt = make_pt(arrays, W, H, nb=nb, fraction=fraction)
+            pt.set_pipeline(pipeline)
+            want = np.zeros((H, W, 4), np.float32)
+            O.render(arrays, W, H, pt.eye, pt.dir, pt.fovScale, pt.lensFeatures, pt.envTheta, nb, 0, 1, 7, want, lights=lights)
+            pt.render(1)
+            got = pt.readRadiance()
+            assert np.array_equal(got, want), (scene, nb, fraction, pipeline, "tick 0", int((got != want).any(-1).sum()))
+            state = pt._rng.value
+            pt.render(3)
+            O.render(arrays, W, H, pt.eye, pt.dir, pt.fovScale, pt.lensFeatures, pt.envTheta, nb, 1, 3, state, want,
+                     lights=lights)
+            got = pt.readRadiance()
+            pt.close()
+            assert np.array_equal(got, want), (scene, nb, fraction, pipeline, "ticks 1-3", int((got != want).any(-1).sum()))
+
+
+SOBOL_SEED = 11
+SOBOL_DIMS = 4 + 12 * 64  # every dimension a path with emitter NEE can reach
+
+
+@pytest.mark.parametrize("scene", ["e1", "e2", "e3"])
+@pytest.mark.parametrize("nb", [2, 4, 70])
+def test_sobol_frames_match_oracle(request, scene, nb):
+    """Sobol: each tick equals path_replay fed the sampler's values (dims 4..4 + 12 x 64) with the oracle's light table."""
+    import sobol_ref as SR
+    arrays = request.getfixturevalue(scene)
+    W, H = 64, 48
+    pix = np.arange(W * H, dtype=np.uint64)[:, None]
+    for fraction in (0.25, 1.0):
+        lights = oracle_table(arrays, fraction)
+        for pipeline in ("megakernel", "wavefront", "stream"):
+            pt = make_pt(arrays, W, H, nb=nb, fraction=fraction, sampler="sobol")
+            pt.set_pipeline(pipeline)
+            for tick in (0, 5):
+                pt.clear()
+                pt.pingpong = tick
+                pt.render(1)
+                got = pt.readRadiance().reshape(-1, 4)[:, :3]
+                cam = SR.value(SOBOL_SEED, pix, np.uint64(tick), np.arange(4, dtype=np.uint64)[None, :]).reshape(H, W, 4)
+                pos, d = O.camera_probe(W, H, pt.eye, pt.dir, pt.fovScale, pt.lensFeatures, cam)
+                rec = SR.value(SOBOL_SEED, pix, np.uint64(tick), np.arange(4, 4 + SOBOL_DIMS, dtype=np.uint64)[None, :])
+                col, used, _, _, _ = O.path_replay(arrays, pos, d, rec, np.full(W * H, SOBOL_DIMS, np.uint32), 1.0,
+                                                   pt.envTheta, nb, lights=lights)
+                assert used.max() <= SOBOL_DIMS
+                want = (col / np.float32(tick + 1)).astype(np.float32)
+                assert np.array_equal(got, want), (scene, nb, fraction, pipeline, tick, int((got != want).any(-1).sum()))
+            pt.close()
+
+
+# ---- 11: no bias, block by block -----------------------------------------------------------------------------------
+# spp per seed (16 seeds per mode): enough that a 3 % shift of one 8x8 block of median noise stands > 5 standard errors out
+REGION_SPP = {"e1": 16384, "e2": 4096, "e3": 4096}
+REGION_SEEDS = 16
+REGION_Z = 5.0
+
+
+def block_means(arrays, nb, spp, seeds, lights):
+    W, H = 96, 64
+    out = []
+    for s in seeds:
+        pt = make_pt(arrays, W, H, nb=nb, seed=s, lights=lights)
+        pt.render(spp)
+        img = pt.readRadiance()[..., :3].astype(np.float64)
+        pt.close()
+        out.append(img.reshape(H // 8, 8, W // 8, 8, 3).mean((1, 3)) @ R.LUMA)
+    return np.array(out)  # [seeds, 8, 12]
+
+
+def block_z(a, b):
+    se = np.sqrt(a.var(0, ddof=1) / len(a) + b.var(0, ddof=1) / len(b))
+    d = a.mean(0) - b.mean(0)
+    return np.where(se > 0, d / np.where(se > 0, se, 1.0), np.where(d == 0, 0.0, np.inf)), se
+
+
+@pytest.mark.parametrize("scene", ["e1", "e2", "e3"])
+@pytest.mark.parametrize("nb", [2, 4])
+def test_no_bias_per_region(request, scene, nb):
+    arrays = request.getfixturevalue(scene)
+    spp = REGION_SPP[scene]
+    n = REGION_SEEDS
+    off = block_means(arrays, nb, spp, range(1, n + 1), False)
+    off2 = block_means(arrays, nb, spp, range(101, n + 101), False)
+    on = block_means(arrays, nb, spp, range(201, n + 201), True)
+    z_on, se = block_z(on, off)
+    z_off, _ = block_z(off2, off)
+    m = off.mean(0)
+    lit = m > 1e-3 * m.max()
+    rel_se = se[lit] / m[lit]
+    k = np.flatnonzero(lit.ravel())[np.argsort(rel_se)[len(rel_se) // 2]]  # the block of median relative noise
+    shifted = on.copy()
+    shifted.reshape(n, -1)[:, k] *= 1.03
+    z_shift, _ = block_z(shifted, off)
+    print("%s nb %d spp %d: max |z| on %.2f, off-off %.2f; 3%% on block %d -> z %.1f; median rel SE %.4f, 3%% detectable "
+          "in %d of %d lit blocks" % (scene, nb, spp, np.abs(z_on).max(), np.abs(z_off).max(), k, z_shift.ravel()[k],
+                                    np.median(rel_se), int((0.03 / rel_se > REGION_Z).sum()), lit.sum()))
+    assert np.abs(z_off).max() < REGION_Z  # the statistic itself is calibrated
+    assert abs(z_shift.ravel()[k]) >= REGION_Z  # ... and has the power to see 3 % in a typical block
+    assert np.abs(z_on).max() < REGION_Z, np.unravel_index(np.abs(z_on).argmax(), z_on.shape)

@@ -126,6 +126,7 @@ SIGNATURES = {
     "fspt_get_trace_lds_steps": (C.c_int, [_VP, C.POINTER(C.c_uint64)]),
     "fspt_math_eval": (C.c_int, [C.c_int, C.c_int, _F, _F, C.c_uint32, _F]),
     "fspt_sampler_eval": (C.c_int, [C.c_int, C.c_uint32, _U32, _U32, _U32, C.c_uint32, _F]),
+    "fspt_denoise_eval": (C.c_int, [C.c_int, _F, _F, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), _F]),
     "fspt_scene_light_table": (C.c_int, [_VP, _U32, _U32, _U32, _F, _F, _U32, _U32, _F, _U32]),
     "fspt_light_sample_eval": (C.c_int, [_VP, _F, C.c_uint32, C.POINTER(C.c_int32), _F]),
     "fspt_light_alias_table": (C.c_int, [_F, C.c_uint32, _F, _U32]),

@@ -1264,6 +1264,36 @@ static int dn_alloc(float4 **buf, size_t bytes) {
   if (!*buf) HIP_TRY(hipMalloc((void **)buf, bytes));
   return FSPT_OK;
 }
+// sigma_color, sigma_depth: +inf switches the weight off; sigma_normal: 0 switches it off (it is an exponent)
+static int dn_check_params(const fspt_denoise_params &q, const char *fn) {
+  if (q.iterations > 16u || !(q.sigma_color >= 0.0f) || !(q.sigma_depth > 0.0f) || !(q.sigma_normal >= 0.0f && q.sigma_normal < INFINITY)) {
+    fspt_set_error("%s: need iterations <= 16, sigma_color >= 0, sigma_normal in [0, inf), sigma_depth > 0", fn);
+    return FSPT_E_INVALID;
+  }
+  return FSPT_OK;
+}
+// The K launches of k_atrous (fspt_denoise and its test hook fspt_denoise_eval): accum -> out (W*H float4 each) guided by
+// feat (2 W*H float4), ping-ponging through tmp[0..1] (needed when K > 1); K = 0 copies accum
+static hipError_t dn_run(const fspt_denoise_params &q, const float4 *accum, const float4 *feat, uint32_t W, uint32_t H,
+                         float4 *const tmp[2], float4 *out, hipStream_t stream) {
+  const size_t px = (size_t)W * H;
+  if (q.iterations == 0) return hipMemcpyAsync(out, accum, px * 16, hipMemcpyDeviceToDevice, stream);
+  for (uint32_t k = 0; k < q.iterations; ++k) {
+    fspt::AtrousP p{};
+    p.src = k == 0 ? accum : tmp[(k - 1) & 1u];
+    p.dst = k + 1 == q.iterations ? out : tmp[k & 1u];
+    p.feat = feat;
+    p.W = W; p.H = H;
+    p.step = 1 << k;
+    p.demod = k == 0; p.remod = k + 1 == q.iterations;
+    p.sc_step = std::ldexp(q.sigma_color, -(int)k);
+    p.sn = q.sigma_normal;
+    p.sz_step = std::ldexp(q.sigma_depth, (int)k);
+    hipError_t e = fspt::launch_atrous(p, stream);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 
 int fspt_features(fspt_target *t, const fspt_camera_params *cam, uint32_t samples, uint64_t seed) {
   int rc = dn_enter(t, cam != nullptr, "fspt_features");
@@ -1299,33 +1329,13 @@ int fspt_denoise(fspt_target *t, const fspt_denoise_params *prm, float *out) {
   if (rc) return rc;
   fspt_denoise_params q = {FSPT_DENOISE_ITERATIONS, FSPT_DENOISE_SIGMA_COLOR, FSPT_DENOISE_SIGMA_NORMAL, FSPT_DENOISE_SIGMA_DEPTH};
   if (prm) q = *prm;
-  // sigma_color, sigma_depth: +inf switches the weight off; sigma_normal: 0 switches it off (it is an exponent)
-  if (q.iterations > 16u || !(q.sigma_color >= 0.0f) || !(q.sigma_depth > 0.0f) || !(q.sigma_normal >= 0.0f && q.sigma_normal < INFINITY)) {
-    fspt_set_error("fspt_denoise: need iterations <= 16, sigma_color >= 0, sigma_normal in [0, inf), sigma_depth > 0");
-    return FSPT_E_INVALID;
-  }
+  if ((rc = dn_check_params(q, "fspt_denoise"))) return rc;
   if (!t->feat_valid) { fspt_set_error("fspt_denoise: no fspt_features call yet"); return FSPT_E_STATE; }
   const size_t px = (size_t)t->W * t->H;
   if ((rc = dn_alloc(&t->dn_out, px * 16))) return rc;
   t->dn_valid = false;
-  if (q.iterations == 0) {
-    HIP_TRY(hipMemcpyAsync(t->dn_out, t->accum, px * 16, hipMemcpyDeviceToDevice, t->stream));
-  } else {
-    if (q.iterations > 1u && ((rc = dn_alloc(&t->dn_tmp[0], px * 16)) || (rc = dn_alloc(&t->dn_tmp[1], px * 16)))) return rc;
-    for (uint32_t k = 0; k < q.iterations; ++k) {
-      fspt::AtrousP p{};
-      p.src = k == 0 ? t->accum : t->dn_tmp[(k - 1) & 1u];
-      p.dst = k + 1 == q.iterations ? t->dn_out : t->dn_tmp[k & 1u];
-      p.feat = t->feat;
-      p.W = t->W; p.H = t->H;
-      p.step = 1 << k;
-      p.demod = k == 0; p.remod = k + 1 == q.iterations;
-      p.sc_step = std::ldexp(q.sigma_color, -(int)k);
-      p.sn = q.sigma_normal;
-      p.sz_step = std::ldexp(q.sigma_depth, (int)k);
-      HIP_TRY(fspt::launch_atrous(p, t->stream));
-    }
-  }
+  if (q.iterations > 1u && ((rc = dn_alloc(&t->dn_tmp[0], px * 16)) || (rc = dn_alloc(&t->dn_tmp[1], px * 16)))) return rc;
+  HIP_TRY(dn_run(q, t->accum, t->feat, t->W, t->H, t->dn_tmp, t->dn_out, t->stream));
   t->dn_valid = true;
   if (out) {
     HIP_TRY(hipMemcpyAsync(out, t->dn_out, px * 16, hipMemcpyDeviceToHost, t->stream));
@@ -1652,6 +1662,32 @@ int fspt_math_eval(int device, int op, const float *a, const float *b, uint32_t 
   if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost);
   hipFree(da); hipFree(db); hipFree(dout);
   if (e != hipSuccess) { fspt_set_error("fspt_math_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
+  return FSPT_OK;
+}
+
+
+int fspt_denoise_eval(int device, const float *accum, const float *features, uint32_t W, uint32_t H,
+                      const fspt_denoise_params *prm, float *out) {
+  if (!accum || !features || !out) { fspt_set_error("fspt_denoise_eval: NULL argument"); return FSPT_E_INVALID; }
+  int rc = check_device(device);
+  if (rc) return rc;
+  fspt_denoise_params q = {FSPT_DENOISE_ITERATIONS, FSPT_DENOISE_SIGMA_COLOR, FSPT_DENOISE_SIGMA_NORMAL, FSPT_DENOISE_SIGMA_DEPTH};
+  if (prm) q = *prm;
+  if ((rc = dn_check_params(q, "fspt_denoise_eval"))) return rc;
+  const size_t px = (size_t)W * H;
+  if (px == 0) return FSPT_OK;
+  HIP_TRY(hipSetDevice(device));
+  // one allocation: accum, out, tmp[0], tmp[1] (W*H float4 each), then the features (2 W*H float4)
+  float4 *d = nullptr;
+  hipError_t e = hipMalloc((void **)&d, px * 16 * 6);
+  float4 *const tmp[2] = {d + 2 * px, d + 3 * px};
+  if (e == hipSuccess) e = hipMemcpy(d, accum, px * 16, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + 4 * px, features, px * 32, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = dn_run(q, d, d + 4 * px, W, H, tmp, d + px, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, d + px, px * 16, hipMemcpyDeviceToHost);
+  hipFree(d);
+  if (e != hipSuccess) { fspt_set_error("fspt_denoise_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
   return FSPT_OK;
 }
 

@@ -2707,12 +2707,16 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_atrous(const AtrousP p) {
           const float lenq = sqrt_(fma_(fq1.z, fq1.z, fma_(fq1.y, fq1.y, fq1.x * fq1.x)));
           if (hp != hq || lenp == 0.0f || lenq == 0.0f) w = 0.0f;
           else {
-            const float c = fma_(fp1.z, fq1.z, fma_(fp1.y, fq1.y, fp1.x * fq1.x)) / (lenp * lenq);
+            // clamped: for two equal normals the float32 cosine rounds to 1 + 2^-23 about one time in five, and
+            // (1 + 2^-23)^sn exceeds 1 (inf from sn ~ 1e9 on: sw = inf, the pixel NaN)
+            const float c = min_(fma_(fp1.z, fq1.z, fma_(fp1.y, fq1.y, fp1.x * fq1.x)) / (lenp * lenq), 1.0f);
             w *= c > 0.0f ? exp2f(p.sn * log2f(c)) : 0.0f;
           }
         }
       }
-      if (p.sz_step != INFINITY) w *= exp2f(-(abs_(fp0.w - fq0.w) / zden) * 1.44269504f);
+      // equal depths weigh 1: zden underflows to 0 for a tiny sigma_depth, and 0 / 0 would make the centre tap NaN
+      const float dz = abs_(fp0.w - fq0.w);
+      if (p.sz_step != INFINITY && dz != 0.0f) w *= exp2f(-(dz / zden) * 1.44269504f);
       sr = fma_(w, uq.x, sr); sg = fma_(w, uq.y, sg); sb = fma_(w, uq.z, sb);
       sw += w;
     }

@@ -42,6 +42,25 @@ def sampler_eval(seed, pixel, sample, dim, device=0):
     return out
 
 
+def denoise_eval(accum, features, device=0, **params):
+    """fspt_denoise's k_atrous launches on host arrays (fspt_denoise_eval, a test hook): accum float32 [H, W, 4], features
+    float32 [H, W, 8] (readFeatures' layout) -> the denoised float32 [H, W, 4].  params: iterations, sigma_color,
+    sigma_normal, sigma_depth; one left out takes the library's default (DENOISE_DEFAULTS)."""
+    unknown = set(params) - set(DENOISE_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown denoise parameters {sorted(unknown)}")
+    accum = np.ascontiguousarray(accum, dtype=np.float32)
+    features = np.ascontiguousarray(features, dtype=np.float32)
+    if accum.ndim != 3 or accum.shape[2] != 4 or features.shape != accum.shape[:2] + (8,):
+        raise ValueError(f"need accum [H, W, 4] and features [H, W, 8], got {accum.shape} and {features.shape}")
+    H, W = accum.shape[:2]
+    v = {**DENOISE_DEFAULTS, **params}
+    prm = L.DenoiseParams(int(v["iterations"]), float(v["sigma_color"]), float(v["sigma_normal"]), float(v["sigma_depth"]))
+    out = np.empty((H, W, 4), np.float32)
+    L.check(L.lib().fspt_denoise_eval(int(device), L.fptr(accum), L.fptr(features), W, H, C.byref(prm), L.fptr(out)))
+    return out
+
+
 def light_alias_table(weights):
     """The Vose alias table (float32 prob, uint32 alias) the light table stores for these weights (fspt_light_alias_table,
     a pure host function: no device needed)."""

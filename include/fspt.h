@@ -190,8 +190,8 @@ int fspt_present(fspt_target *t, float exposure, float saturation, int denoise, 
  * with the features a, n, z, h:  u = c / max(a, 1e-3);  u'(p) = sum_q w u(q) / sum_q w over q = p + 2^k (i, j), i, j in
  * -2..2 inside the image;  w = B[i] B[j] wc wn wz, B = (1,4,6,4,1)/16;  wc = exp(-|L(u_p) - L(u_q)| / (sc 2^-k (L(u_p) +
  * L(u_q)) + 1e-4)), L = Rec.709 luma;  wn = 1 if sn = 0, q = p or h_p = h_q = 0, else 0 if one h or one |n| is 0, else
- * max(0, n_p.n_q / |n_p||n_q|)^sn;  wz = exp(-|z_p - z_q| / (sz 2^k max(z_p, 1e-3)));  out = (a u_K, 1) (K = 0: c).
- * sc = sz = +inf switch wc, wz off.  fspt_draw_denoised = fspt_draw of the last denoised frame (denoise 0, scale 1). */
+ * clamp(n_p.n_q / |n_p||n_q|, 0, 1)^sn;  wz = 1 if z_p = z_q, else exp(-|z_p - z_q| / (sz 2^k max(z_p, 1e-3)));  out =
+ * (a u_K, 1) (K = 0: c).  sc = sz = +inf switch wc, wz off.  fspt_draw_denoised: fspt_draw (denoise 0, scale 1) of it. */
 typedef struct fspt_denoise_params { uint32_t iterations; float sigma_color, sigma_normal, sigma_depth; } fspt_denoise_params;
 #define FSPT_DENOISE_ITERATIONS 4    /* defaults (params NULL): the best of a 78-setting scan on the MI355X (DESIGN 8.1) */
 #define FSPT_DENOISE_SIGMA_COLOR 4.0f

@@ -141,6 +141,11 @@ int fspt_math_eval(int device, int op, const float *a, const float *b, uint32_t 
  * Test hook: the FSPT_SAMPLER_SOBOL device function value(seed, pixel[i], sample[i], dim[i]) for n triples (host arrays). */
 int fspt_sampler_eval(int device, uint32_t seed, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim,
                       uint32_t n, float *out);
+/* fspt_denoise (fspt.h) test hook: the same k_atrous launches, on host arrays in the library's layouts - accum
+ * W*H*4 floats, features W*H*8 floats (fspt_read_features) - instead of a target's; out: the W*H*4 denoised floats.
+ * p NULL = defaults; the parameters fspt_denoise refuses are refused here too, with the same codes. */
+int fspt_denoise_eval(int device, const float *accum, const float *features, uint32_t W, uint32_t H,
+                      const fspt_denoise_params *p, float *out);
 /* fspt_target_set_lights (fspt.h): FSPT_LIGHTS_EMITTERS lets each shading vertex spend its shadow ray on a
  * point of an emissive triangle (probability q = emitter_fraction, in (0, 1]; at most 0.875 with an environment map, 1
  * when the scene has none)

@@ -1,5 +1,7 @@
 """CPU checks of the guided denoiser: its C-ABI entry points are exported, bound and refuse to run without a device or
-with NULL handles, and the float64 reference of the filter (tests/atrous_ref.py) behaves as its definition says."""
+with NULL handles, the float64 reference of the filter (tests/atrous_ref.py) behaves as its definition says, and the
+synthetic inputs the GPU sweep runs k_atrous on (tests/atrous_inputs.py) reach every edge and tell each of a list of
+deliberately wrong filters from the right one by more than the sweep's tolerance."""
 import ctypes as C
 import os
 import re
@@ -12,7 +14,7 @@ from fspt_amd import tracer as T
 import atrous_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("fspt_features", "fspt_read_features", "fspt_denoise", "fspt_draw_denoised")
+NEW = ("fspt_features", "fspt_read_features", "fspt_denoise", "fspt_draw_denoised", "fspt_denoise_eval")
 
 
 def test_symbols_exported_and_bound():
@@ -39,6 +41,11 @@ def test_null_handles_invalid():
     assert lib.fspt_read_features(None, L.fptr(buf)) == -1
     assert lib.fspt_denoise(None, None, None) == -1
     assert lib.fspt_draw_denoised(None, 1.0, 1.0, buf.ctypes.data_as(C.POINTER(C.c_uint8))) == -1
+    prm = L.DenoiseParams(4, 4.0, 32.0, 0.05)
+    for args in ((None, L.fptr(buf)), (L.fptr(buf), None)):  # NULL accumulator, NULL features
+        assert lib.fspt_denoise_eval(0, *args, 2, 2, C.byref(prm), L.fptr(buf)) == -1
+    assert lib.fspt_denoise_eval(0, L.fptr(buf), L.fptr(buf), 2, 2, None, None) == -1  # NULL out
+    assert b"fspt_denoise_eval: NULL argument" in lib.fspt_last_error()
 
 
 def test_no_device():
@@ -55,6 +62,25 @@ def test_no_device():
     assert lib.fspt_denoise(fake, None, None) == -2
     assert lib.fspt_draw_denoised(fake, 1.0, 1.0, buf.ctypes.data_as(C.POINTER(C.c_uint8))) == -2
     assert b"no CPU fallback" in lib.fspt_last_error()
+    # the test hook: the same code as fspt_denoise for the parameters it would refuse on a device (there the device
+    # check comes first too), and for the defaults
+    for prm in (None, L.DenoiseParams(4, 4.0, 32.0, 0.05), L.DenoiseParams(17, 1, 128, 0.1), L.DenoiseParams(5, 1, np.inf, 0.1)):
+        assert lib.fspt_denoise_eval(0, L.fptr(buf), L.fptr(buf), 2, 2, C.byref(prm) if prm else None, L.fptr(buf)) == -2
+        assert b"no CPU fallback" in lib.fspt_last_error()
+    with pytest.raises(L.FsptError) as e:
+        T.denoise_eval(np.zeros((3, 2, 4), np.float32), np.zeros((3, 2, 8), np.float32), iterations=2)
+    assert e.value.code == -2
+
+
+def test_denoise_eval_python_arguments_validated():
+    """Shapes and parameter names are checked before the library is called (no device needed to get there)."""
+    from fspt_amd import denoise_eval
+    acc, f = np.zeros((3, 2, 4), np.float32), np.zeros((3, 2, 8), np.float32)
+    for a, b in ((acc[..., :3], f), (acc, f[..., :7]), (acc, f[:2]), (acc[0], f[0])):
+        with pytest.raises(ValueError):
+            denoise_eval(a, b)
+    with pytest.raises(TypeError):
+        denoise_eval(acc, f, sigma=1.0)
 
 
 def random_inputs(H=12, W=10, seed=0):
@@ -126,3 +152,65 @@ def test_reference_never_crosses_hit_miss_boundary(sigma_normal):
     other = acc.copy(); other[:, :8, :3] *= 7.0
     moved = R.atrous(other, f, 4, sigma_color=np.inf, sigma_normal=sigma_normal, sigma_depth=np.inf)
     assert np.array_equal(base[:, 8:], moved[:, 8:])  # and the other way round
+
+
+# ---- the synthetic inputs of the GPU sweep (tests/atrous_inputs.py) ----------------------------------------------------
+import atrous_inputs as I  # noqa: E402
+
+
+def excess(got, ref, rtol=1e-4, atol=1e-6):
+    """How many times the GPU tests' bound (rtol where |ref| > 1e-3, atol elsewhere) |got - ref| reaches at its
+    worst pixel; inf where got is not finite."""
+    if not np.isfinite(got).all():
+        return np.inf
+    big = np.abs(ref) > 1e-3
+    rel = (np.abs(got[big] - ref[big]) / np.abs(ref[big])).max(initial=0.0)
+    return max(rel / rtol, np.abs(got[~big] - ref[~big]).max(initial=0.0) / atol)
+
+
+def test_synthetic_inputs_reach_every_edge():
+    acc, f = I.synthetic(80, 120)
+    acc2, f2 = I.synthetic(80, 120)
+    assert np.array_equal(acc, acc2) and np.array_equal(f, f2)  # deterministic
+    h, n, z, a = f[..., 7], f[..., 4:7], f[..., 3], f[..., 0:3]
+    nlen = np.linalg.norm(n, axis=-1)
+    hit, miss = h > 0, h == 0
+    assert (miss & (nlen == 0) & (z == 1e5) & (a == 1).all(-1)).sum() > 100  # misses as k_features writes them
+    assert (miss & (nlen > 0)).sum() > 50                                   # misses with a normal (the cut on h alone)
+    assert ((h > 0) & (h < 1)).sum() > 100                                  # seams with fractional coverage
+    assert (hit & (nlen == 0)).sum() > 50                                   # hits with a zero-length normal
+    assert (hit & (a == 0).all(-1)).sum() > 50 and (hit & (a == 0).any(-1) & (a > 0).any(-1)).sum() > 50  # black albedo
+    assert (hit & (z == 0)).sum() > 50                                      # z = 0 exactly
+    assert acc[..., :3].max() > 512 and (acc[..., :3] == 0).all(-1).sum() > 100  # fireflies and exact zeros
+    # equal neighbouring normals whose float32 cosine rounds above 1 (what the clamp is for), and smooth-field pairs
+    c = I.cosine_f32(n[:, 1:], n[:, :-1])
+    both = hit[:, 1:] & hit[:, :-1] & (nlen[:, 1:] > 0) & (nlen[:, :-1] > 0)
+    assert ((c > 1) & both).sum() > 100 and ((c < 0.9999) & (c > 0.99) & both).sum() > 100
+    # depth discontinuities between neighbouring hits
+    assert ((np.abs(z[:, 1:] - z[:, :-1]) > 0.5) & hit[:, 1:] & hit[:, :-1]).sum() > 50
+
+
+MUTATION_CASES = [(80, 120, {}), (80, 120, dict(sigma_color=np.inf)), (17, 16, dict(iterations=2))]
+
+
+@pytest.mark.parametrize("mutant", R.MUTANTS)
+def test_inputs_detect_each_mutant(mutant):
+    """Each deliberate defect of the reference (atrous_ref.MUTANTS) moves some pixel of one of the GPU sweep's inputs by
+    more than the sweep's bound: the sweep would catch the same defect in the kernel."""
+    worst = []
+    for H, W, kw in MUTATION_CASES:
+        acc, f = I.synthetic(H, W)
+        ref = R.atrous(acc, f, **kw)
+        assert np.isfinite(ref).all()
+        worst.append(excess(R.atrous(acc, f, **kw, mutant=mutant), ref))
+    print(f"{mutant}: largest deviation {max(worst):.3g} x the tolerance; per case {[f'{w:.3g}' for w in worst]}")
+    assert max(worst) > 1, (mutant, worst)
+
+
+def test_reference_finite_at_every_accepted_edge():
+    """The reference itself: finite for every parameter edge the GPU sweep uses, the centre tap's weight 1 included when
+    sigma_depth is the smallest float32 (its scaled denominator underflows in float32, not here)."""
+    acc, f = I.synthetic(17, 16)
+    for kw in (dict(sigma_normal=1e9), dict(sigma_depth=float(np.finfo(np.float32).smallest_subnormal)),
+               dict(sigma_depth=1e-6), dict(sigma_color=0.0), dict(iterations=16)):
+        assert np.isfinite(R.atrous(acc, f, **kw)).all(), kw

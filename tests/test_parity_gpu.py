@@ -8,7 +8,7 @@ import pytest
 
 import oracle as O
 from conftest import random_rays
-from rays import fuzz_scene as _fuzz_scene
+from rays import chain_scene, fuzz_scene as _fuzz_scene
 from fspt_amd import PathTracer, Scene, _lib as L
 
 pytestmark = pytest.mark.gpu
@@ -1078,46 +1078,6 @@ def test_bvh_deeper_than_the_reference_stack_is_rejected():
     with pytest.raises(L.FsptError) as e:
         Scene(arr)
     assert e.value.code == -1 and "depth" in str(e.value)
-
-
-def chain_scene(n_leaves, env_from):
-    """A chain-shaped BVH of depth n_leaves - 1 in the reference layout (pre-order; interior i: left = a one-triangle
-    leaf, right = the next interior), small randomly placed triangles along +x, flat normals, a grey diffuse material
-    and the environment (incl. importance bins) of `env_from`."""
-    from fspt_amd import scene as S
-    rng = np.random.default_rng(n_leaves)
-    tri = np.zeros((n_leaves, 3, 3), np.float32)
-    for k in range(n_leaves):
-        c = np.array([k, rng.uniform(-0.2, 0.2), rng.uniform(-0.2, 0.2)])
-        tri[k] = c + rng.uniform(-0.9, 0.9, (3, 3)) * [0.3, 1, 1]  # boxes overlap the chain's axis: rays along it visit every level
-    lo = tri.min(1); hi = tri.max(1)
-    n_nodes = 2 * n_leaves - 1
-    bvh = np.zeros((n_nodes, 9), np.float32)
-    iv = bvh.view(np.int32)
-    idx = 0
-    for i in range(n_leaves - 1):  # interior i (covers leaves i..), then its left child: leaf i
-        iv[idx, 0] = idx + 1; iv[idx, 1] = idx + 2; iv[idx, 2] = -1
-        bvh[idx, 3:6] = lo[i:].min(0); bvh[idx, 6:9] = hi[i:].max(0)
-        idx += 1
-        iv[idx, 0] = 0; iv[idx, 1] = 0; iv[idx, 2] = i
-        bvh[idx, 3:6] = lo[i]; bvh[idx, 6:9] = hi[i]
-        idx += 1
-    iv[idx, 0] = 0; iv[idx, 1] = 0; iv[idx, 2] = n_leaves - 1
-    bvh[idx, 3:6] = lo[-1]; bvh[idx, 6:9] = hi[-1]
-    nrm = np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
-    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
-    tan = tri[:, 1] - tri[:, 0]
-    tan /= np.linalg.norm(tan, axis=1, keepdims=True)
-    bit = np.cross(nrm, tan)
-    norm = np.zeros((n_leaves, 3, 3, 3), np.float32)  # per vertex: n, t, bt
-    norm[:, :, 0] = nrm[:, None]; norm[:, :, 1] = tan[:, None]; norm[:, :, 2] = bit[:, None]
-    mat = np.zeros((n_leaves, 12), np.float32)
-    mat[:, 0:4] = [0, 1, 2, 3]   # diffuse / emissive / normal / metallic-roughness layers
-    mat[:, 9:11] = [1.4, -1.0]   # ior, dielectric
-    atlas = np.array([[200, 190, 180, 255], [0, 0, 0, 255], [128, 128, 255, 255], [0, 140, 0, 255]], np.uint8)
-    return S.SceneArrays(bvh=bvh.reshape(-1), tri=tri.reshape(-1), mat=mat.reshape(-1), norm=norm.reshape(-1),
-                         uv=np.zeros(n_leaves * 6, np.float32), atlas=atlas.reshape(-1), atlas_res=1, atlas_layers=4,
-                         env=env_from.env, env_w=env_from.env_w, env_h=env_from.env_h, bins=env_from.bins)
 
 
 @pytest.mark.parametrize("n_leaves", [41, 64])

@@ -598,37 +598,67 @@ FM_DEV V3 eval_specular(V3 incident, V3 normal, V3 diffuse, float metallic, floa
 }
 
 // ---------------------------------------------------------------------------
-// Emitter sampling (fspt.h FSPT_LIGHTS_EMITTERS, DESIGN 8.3)
+// Materials: texture(texArray, vec3(uv, layer)) x 4 (tracer.fs:453-456)
 // ---------------------------------------------------------------------------
-// The diffuse and emissive layers of material texture set `set` at uv (s, t): shade_hit's taps and decode for those two layers
-FM_DEV void light_tex(const DScene &S, uint32_t set, float s, float t, V3 &td, V3 &te) {
+FM_DEV V3 unorm8_rgb(uint32_t q) { return v3(unorm8(q & 255u), unorm8((q >> 8) & 255u), unorm8((q >> 16) & 255u)); }
+FM_DEV V3 tap_rgb(const Tap4 &q) { return v3(tap_channel(q, 0), tap_channel(q, 1), tap_channel(q, 2)); }
+// The layers of material texture set `set` (hit record word 42; fspt_device.hpp TexSet) at uv (s, t), the four layers'
+// texels of ONE footprint: D texDiffuse, E texEmissive, R metallic and rough (not yet squared), N texNormal.  A layer
+// that is not asked for issues no load; the outputs of the others are left alone.
+template <bool D, bool E, bool R, bool N>
+FM_DEV void material(const DScene &S, uint32_t set, float s, float t, V3 &texDiffuse, V3 &texEmissive, float &metallic,
+                     float &rough, V3 &texNormal) {
   const uint4 *tset = S.tex_sets + (size_t)set * 3;
   const uint4 ts0 = tset[0], ts1 = tset[1];
   if (ts0.x == TEXSET_CONST) {
-    td = v3(unorm8(ts1.x & 255u), unorm8((ts1.x >> 8) & 255u), unorm8((ts1.x >> 16) & 255u));
-    te = v3(unorm8(ts1.y & 255u), unorm8((ts1.y >> 8) & 255u), unorm8((ts1.y >> 16) & 255u));
+    // four flat colours (texture_packer.js:36-42; every material of a colours-only atlas): the four bilinear taps are
+    // the same texel and lerp(x, x, a) = fma(a, 0, x) = x exactly, so the filter arithmetic is skipped (bit-identical)
+    if (D) texDiffuse = unorm8_rgb(ts1.x);
+    if (E) texEmissive = unorm8_rgb(ts1.y);
+    if (R) { metallic = unorm8(ts1.z & 255u); rough = unorm8((ts1.z >> 8) & 255u); }
+    if (N) texNormal = v3((unorm8(ts1.w & 255u) - 0.5f) * 2.0f, (unorm8((ts1.w >> 8) & 255u) - 0.5f) * 2.0f,
+                          (unorm8((ts1.w >> 16) & 255u) - 0.0f) * 1.0f);
     return;
   }
   const TexCoord tc = bilinear_coord((int)S.atlas_res, (int)S.atlas_res, s, t, true);
-  Tap4 qd, qe;
+  Tap4 qd, qe, qr, qn;
   if (ts0.x == TEXSET_QUAD) {
+    // the four layers interleaved texel by texel (4 x 2-texel tiles of 16-byte texels): one 16-byte load per tap
+    // brings all four layers, and the footprint lies in 1.9 lines instead of 4 x 1.4
     const uint4 *img = S.atlas4 + (size_t)ts0.y * 8u;
     const int tiles_x = ((int)S.atlas_res + 3) >> 2;
     const uint4 t00 = img[tile_offset<2, 1>(tc.i0, tc.j0, tiles_x)], t10 = img[tile_offset<2, 1>(tc.i1, tc.j0, tiles_x)];
     const uint4 t01 = img[tile_offset<2, 1>(tc.i0, tc.j1, tiles_x)], t11 = img[tile_offset<2, 1>(tc.i1, tc.j1, tiles_x)];
     qd = Tap4{t00.x, t10.x, t01.x, t11.x, tc.a, tc.b};
     qe = Tap4{t00.y, t10.y, t01.y, t11.y, tc.a, tc.b};
+    qr = Tap4{t00.z, t10.z, t01.z, t11.z, tc.a, tc.b};
+    qn = Tap4{t00.w, t10.w, t01.w, t11.w, tc.a, tc.b};
   } else {
+    // separate single-layer images (a set with one image layer, or sets beyond the interleaving budget): all loads
+    // of the image layers are issued before the first texel is decoded
     const uint4 ts2 = tset[2];
     const TapGeom tg = tap_geom(tc, (int)S.atlas_res);
-    qd = layer_taps(S, tg, ts2.x, ts1.x);
-    qe = layer_taps(S, tg, ts2.y, ts1.y);
+    if (D) qd = layer_taps(S, tg, ts2.x, ts1.x);
+    if (E) qe = layer_taps(S, tg, ts2.y, ts1.y);
+    if (R) qr = layer_taps(S, tg, ts2.z, ts1.z);
+    if (N) qn = layer_taps(S, tg, ts2.w, ts1.w);
   }
-  td = v3(tap_channel(qd, 0), tap_channel(qd, 1), tap_channel(qd, 2));
-  te = v3(tap_channel(qe, 0), tap_channel(qe, 1), tap_channel(qe, 2));
+  if (D) texDiffuse = tap_rgb(qd);
+  if (E) texEmissive = tap_rgb(qe);
+  if (R) { metallic = tap_channel(qr, 0); rough = tap_channel(qr, 1); }
+  if (N) texNormal = v3((tap_channel(qn, 0) - 0.5f) * 2.0f, (tap_channel(qn, 1) - 0.5f) * 2.0f, (tap_channel(qn, 2) - 0.0f) * 1.0f);
 }
-// emitted radiance 30 * texEmissive * texDiffuse (tracer.fs:467)
-FM_DEV V3 light_le(V3 td, V3 te) { return v3((te.x * td.x) * 30.0f, (te.y * td.y) * 30.0f, (te.z * td.z) * 30.0f); }
+
+// ---------------------------------------------------------------------------
+// Emitter sampling (fspt.h FSPT_LIGHTS_EMITTERS, DESIGN 8.3)
+// ---------------------------------------------------------------------------
+// emitted radiance 30 * texEmissive * texDiffuse (tracer.fs:467) of material texture set `set` at uv (s, t)
+FM_DEV V3 light_le(const DScene &S, uint32_t set, float s, float t) {
+  V3 td, te, tn;
+  float metallic, rough;
+  material<true, true, false, false>(S, set, s, t, td, te, metallic, rough, tn);
+  return v3((te.x * td.x) * 30.0f, (te.y * td.y) * 30.0f, (te.z * td.z) * 30.0f);
+}
 // The point of a triangle at the warped square sample (u2, u3): barycentrics b0 = 1 - sqrt(u2), b1 = u3 sqrt(u2), b2 = the
 // rest (uniform in area); the same map places the 16 stratified points of the table's weights
 FM_DEV void tri_point(float u2, float u3, V3 v1, V3 e1, V3 e2, float uv0x, float uv0y, float uv1x, float uv1y, float uv2x,
@@ -653,9 +683,7 @@ FM_DEV void light_sample(const DScene &S, V3 ro, float v, float u2, float u3, Li
   const V3 v1 = v3(a.x, a.y, a.z), e1 = v3(a.w, b.x, b.y), e2 = v3(b.z, b.w, c.x);
   float s, t;
   tri_point(u2, u3, v1, e1, e2, c.y, c.z, c.w, d.x, d.y, d.z, ls.x, s, t);
-  V3 td, te;
-  light_tex(S, __float_as_uint(d.w), s, t, td, te);
-  ls.le = light_le(td, te);
+  ls.le = light_le(S, __float_as_uint(d.w), s, t);
   const V3 dv = ls.x - ro;
   const float d2 = dot(dv, dv);
   ls.dist = sqrt_(d2);
@@ -731,6 +759,48 @@ struct Path {
   float lt;       // LIGHTS: t bound of the pending shadow ray (MAX_T: environment, below: an emitter point)
 };
 
+// The hit record of slot ti (192 B = 3 whole cache lines) and what shade_hit and first_hit_guides compute from it before
+// shading: the hit point of ray (ro, rd) at tHit, its barycentric weights and its texture coordinates
+struct HitGeom {
+  V3 v1, e1, e2;                         // the triangle: its first vertex and two edges
+  V3 n1, t1, b1, n2, t2, b2, n3, t3, b3; // the vertices' normal, tangent and bitangent
+  uint32_t set;                          // the triangle's material texture set (hit record word 42)
+  float ior, dielectric;
+  V3 origin, w;                          // the hit point and its barycentric weights
+  float tcx, tcy;                        // its texture coordinates
+};
+FM_DEV void hit_geom(const DScene &S, int ti, V3 ro, V3 rd, float tHit, HitGeom &g) {
+  const float4 *hp = S.hitrec + (size_t)ti * HITREC_F4;
+  const float4 h0 = hp[0], h1 = hp[1], h2 = hp[2], h3 = hp[3], h4 = hp[4], h5 = hp[5], h6 = hp[6], h7 = hp[7], h8 = hp[8],
+               h9 = hp[9], h10 = hp[10], h11 = hp[11];
+  g.v1 = v3(h0.x, h0.y, h0.z); g.e1 = v3(h0.w, h1.x, h1.y); g.e2 = v3(h1.z, h1.w, h2.x);
+  g.n1 = v3(h2.y, h2.z, h2.w); g.t1 = v3(h3.x, h3.y, h3.z); g.b1 = v3(h3.w, h4.x, h4.y);
+  g.n2 = v3(h4.z, h4.w, h5.x); g.t2 = v3(h5.y, h5.z, h5.w); g.b2 = v3(h6.x, h6.y, h6.z);
+  g.n3 = v3(h6.w, h7.x, h7.y); g.t3 = v3(h7.z, h7.w, h8.x); g.b3 = v3(h8.y, h8.z, h8.w);
+  g.set = __float_as_uint(h10.z); g.ior = h11.z; g.dielectric = h11.w;
+  g.origin = vfma(rd, tHit, ro);
+  // barycentricWeights (tracer.fs:339-353); v0 = e1, v1 = e2
+  const V3 vv2 = g.origin - g.v1;
+  const float d00 = dot(g.e1, g.e1), d01 = dot(g.e1, g.e2), d11 = dot(g.e2, g.e2);
+  const float d20 = dot(vv2, g.e1), d21 = dot(vv2, g.e2);
+  const float invDenom = 1.0f / fma_(d00, d11, -(d01 * d01));
+  const float bv = fma_(d11, d20, -(d01 * d21)) * invDenom;
+  const float bw = fma_(d00, d21, -(d01 * d20)) * invDenom;
+  g.w = v3((1.0f - bv) - bw, bv, bw);
+  g.tcx = fma_(g.w.z, h10.x, fma_(g.w.y, h9.z, g.w.x * h9.x));
+  g.tcy = fma_(g.w.z, h10.y, fma_(g.w.y, h9.w, g.w.x * h9.y));
+}
+// macroNormal: texNormal in the interpolated tangent frame (tracer.fs:457-460), before the `inside` flip; baryNormal is
+// the interpolated vertex normal
+FM_DEV V3 macro_normal(const HitGeom &g, V3 texNormal, V3 &baryNormal) {
+  baryNormal = bary3(g.w, g.n1, g.n2, g.n3);
+  const V3 baryTangent = bary3(g.w, g.t1, g.t2, g.t3);
+  const V3 baryBitangent = bary3(g.w, g.b1, g.b2, g.b3);
+  return normalize(v3(fma_(texNormal.z, baryNormal.x, fma_(texNormal.y, baryBitangent.x, texNormal.x * baryTangent.x)),
+                      fma_(texNormal.z, baryNormal.y, fma_(texNormal.y, baryBitangent.y, texNormal.x * baryTangent.y)),
+                      fma_(texNormal.z, baryNormal.z, fma_(texNormal.y, baryBitangent.z, texNormal.x * baryTangent.z))));
+}
+
 // tracer.fs:447-499: shade the hit (t, tri) of ray (ro, rd); sets up the next
 // shadow + extension rays in `ps`.
 // SMP_SOBOL: ps.pix is the full-target pixel, `sample` the tick, `sseed` the sampler seed (randBase is unused)
@@ -741,92 +811,19 @@ template <bool COUNT, int SMP, bool LIGHTS = false>
 FM_DEV void shade_hit(const DScene &S, Path &ps, float tHit, int ti, float randBase, uint32_t sseed, uint32_t sample,
                       float envTheta, Counters &cnt, float lightQ = 0.0f, uint32_t numBounces = 0u) {
   if (COUNT) cnt.shades++;
-  const float4 *hp = S.hitrec + (size_t)ti * HITREC_F4; // 192 B = 3 whole cache lines
-  const float4 h0 = hp[0], h1 = hp[1], h2 = hp[2], h3 = hp[3], h4 = hp[4], h5 = hp[5], h6 = hp[6], h7 = hp[7], h8 = hp[8],
-               h9 = hp[9], h10 = hp[10], h11 = hp[11];
-  V3 v1 = v3(h0.x, h0.y, h0.z), e1 = v3(h0.w, h1.x, h1.y), e2 = v3(h1.z, h1.w, h2.x);
-  V3 n1 = v3(h2.y, h2.z, h2.w), t1 = v3(h3.x, h3.y, h3.z), b1 = v3(h3.w, h4.x, h4.y);
-  V3 n2 = v3(h4.z, h4.w, h5.x), t2 = v3(h5.y, h5.z, h5.w), b2 = v3(h6.x, h6.y, h6.z);
-  V3 n3 = v3(h6.w, h7.x, h7.y), t3 = v3(h7.z, h7.w, h8.x), b3 = v3(h8.y, h8.z, h8.w);
-  float uv0x = h9.x, uv0y = h9.y, uv1x = h9.z, uv1y = h9.w, uv2x = h10.x, uv2y = h10.y;
-  float layDiffuse = h10.z; // (bits) the triangle's material texture set
-  float ior = h11.z, dielectric = h11.w;
-
   V3 rd = ps.rd;
-  V3 origin = vfma(rd, tHit, ps.ro);
-  // barycentricWeights (tracer.fs:339-353); v0 = e1, v1 = e2
-  V3 w;
-  {
-    V3 vv2 = origin - v1;
-    float d00 = dot(e1, e1), d01 = dot(e1, e2), d11 = dot(e2, e2);
-    float d20 = dot(vv2, e1), d21 = dot(vv2, e2);
-    float invDenom = 1.0f / fma_(d00, d11, -(d01 * d01));
-    float bv = fma_(d11, d20, -(d01 * d21)) * invDenom;
-    float bw = fma_(d00, d21, -(d01 * d20)) * invDenom;
-    w = v3((1.0f - bv) - bw, bv, bw);
-  }
-  float tcx = fma_(w.z, uv2x, fma_(w.y, uv1x, w.x * uv0x));
-  float tcy = fma_(w.z, uv2y, fma_(w.y, uv1y, w.x * uv0y));
+  HitGeom g;
+  hit_geom(S, ti, ps.ro, rd, tHit, g);
+  const V3 origin = g.origin, e1 = g.e1, e2 = g.e2;
+  const float ior = g.ior, dielectric = g.dielectric;
   V3 texDiffuse, texEmissive, texNormal;
   float metallic, rough;
-  // texture(texArray, vec3(uv, layer)) x 4 (tracer.fs:453-456) through the triangle's material texture set (hit
-  // record word 42; fspt_device.hpp TexSet): the four layers' texels of ONE footprint
-  const uint4 *tset = S.tex_sets + (size_t)__float_as_uint(layDiffuse) * 3;
-  const uint4 ts0 = tset[0], ts1 = tset[1];
-  if (ts0.x == TEXSET_CONST) {
-    // four flat colours (texture_packer.js:36-42; every material of a colours-only atlas): the four bilinear taps are
-    // the same texel and lerp(x, x, a) = fma(a, 0, x) = x exactly, so the filter arithmetic is skipped (bit-identical)
-    uint32_t q = ts1.x;
-    texDiffuse = v3(unorm8(q & 255u), unorm8((q >> 8) & 255u), unorm8((q >> 16) & 255u));
-    q = ts1.y;
-    texEmissive = v3(unorm8(q & 255u), unorm8((q >> 8) & 255u), unorm8((q >> 16) & 255u));
-    q = ts1.z;
-    metallic = unorm8(q & 255u);
-    rough = unorm8((q >> 8) & 255u);
-    q = ts1.w;
-    texNormal = v3((unorm8(q & 255u) - 0.5f) * 2.0f, (unorm8((q >> 8) & 255u) - 0.5f) * 2.0f,
-                   (unorm8((q >> 16) & 255u) - 0.0f) * 1.0f);
-  } else {
-    const TexCoord tc = bilinear_coord((int)S.atlas_res, (int)S.atlas_res, tcx, tcy, true);
-    Tap4 qd, qe, qr, qn;
-    if (ts0.x == TEXSET_QUAD) {
-      // the four layers interleaved texel by texel (4 x 2-texel tiles of 16-byte texels): one 16-byte load per tap
-      // brings all four layers, and the footprint lies in 1.9 lines instead of 4 x 1.4
-      const uint4 *img = S.atlas4 + (size_t)ts0.y * 8u;
-      const int tiles_x = ((int)S.atlas_res + 3) >> 2;
-      const uint4 t00 = img[tile_offset<2, 1>(tc.i0, tc.j0, tiles_x)], t10 = img[tile_offset<2, 1>(tc.i1, tc.j0, tiles_x)];
-      const uint4 t01 = img[tile_offset<2, 1>(tc.i0, tc.j1, tiles_x)], t11 = img[tile_offset<2, 1>(tc.i1, tc.j1, tiles_x)];
-      qd = Tap4{t00.x, t10.x, t01.x, t11.x, tc.a, tc.b};
-      qe = Tap4{t00.y, t10.y, t01.y, t11.y, tc.a, tc.b};
-      qr = Tap4{t00.z, t10.z, t01.z, t11.z, tc.a, tc.b};
-      qn = Tap4{t00.w, t10.w, t01.w, t11.w, tc.a, tc.b};
-    } else {
-      // separate single-layer images (a set with one image layer, or sets beyond the interleaving budget): all loads
-      // of the image layers are issued before the first texel is decoded
-      const uint4 ts2 = tset[2];
-      const TapGeom tg = tap_geom(tc, (int)S.atlas_res);
-      qd = layer_taps(S, tg, ts2.x, ts1.x);
-      qe = layer_taps(S, tg, ts2.y, ts1.y);
-      qr = layer_taps(S, tg, ts2.z, ts1.z);
-      qn = layer_taps(S, tg, ts2.w, ts1.w);
-    }
-    texDiffuse = v3(tap_channel(qd, 0), tap_channel(qd, 1), tap_channel(qd, 2));
-    texEmissive = v3(tap_channel(qe, 0), tap_channel(qe, 1), tap_channel(qe, 2));
-    metallic = tap_channel(qr, 0);
-    rough = tap_channel(qr, 1);
-    texNormal = v3((tap_channel(qn, 0) - 0.5f) * 2.0f, (tap_channel(qn, 1) - 0.5f) * 2.0f,
-                   (tap_channel(qn, 2) - 0.0f) * 1.0f);
-  }
+  material<true, true, true, true>(S, g.set, g.tcx, g.tcy, texDiffuse, texEmissive, metallic, rough, texNormal);
   rough = rough * rough;
   Rng<SMP> rng{fma_(origin.z, 4761.52835f, ((origin.x * randBase) * origin.y) * 1.396529836f), sseed, (uint32_t)ps.pix, sample,
                ps.dim};
-  V3 baryNormal = bary3(w, n1, n2, n3);
-  V3 baryTangent = bary3(w, t1, t2, t3);
-  V3 baryBitangent = bary3(w, b1, b2, b3);
-  V3 macroNormal = normalize(
-      v3(fma_(texNormal.z, baryNormal.x, fma_(texNormal.y, baryBitangent.x, texNormal.x * baryTangent.x)),
-         fma_(texNormal.z, baryNormal.y, fma_(texNormal.y, baryBitangent.y, texNormal.x * baryTangent.y)),
-         fma_(texNormal.z, baryNormal.z, fma_(texNormal.y, baryBitangent.z, texNormal.x * baryTangent.z))));
+  V3 baryNormal;
+  V3 macroNormal = macro_normal(g, texNormal, baryNormal);
   bool inside = dot(-rd, baryNormal) < 0.0f;
   float nsx = inside ? ior : 1.0f, nsy = inside ? 1.0f : ior;
   if (inside) macroNormal = -macroNormal;
@@ -1044,6 +1041,31 @@ FM_DEV bool work_to_pixel(const P &p, uint32_t idx, uint32_t &x, uint32_t &y) {
 // Sample number g of a run (pixel-major: n_batch ticks per work index) -> work index.
 FM_DEV uint32_t wf_work_index(const WfP &p, uint32_t g) { return g / p.n_batch; }
 
+// counters[first..5] += the wave's sums of cnt's fields (lane: the lane's index in its wave)
+template <bool COUNT>
+FM_DEV void flush_counters(const Counters &cnt, unsigned long long *counters, int first, int lane) {
+  if (!COUNT) return;
+  unsigned long long v[6] = {cnt.samples, cnt.rays, cnt.steps, cnt.leaves, cnt.shades, cnt.envs};
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    if (i < first) continue;
+    unsigned long long x = v[i];
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, WAVE);
+    if (lane == 0 && x) atomicAdd(counters + i, x);
+  }
+}
+
+// A fresh path: the primary ray (ro, rd) of a sample of pixel `pix` (SMP_SOBOL: the full-target pixel; otherwise what the
+// kernel marks a live lane with).  The NEE fields (envDir, pend, wx, wy) are left alone: a path without a shadow ray
+// reads none of them, and shade_hit writes them all before the first one is cast.
+FM_DEV void path_begin(Path &ps, V3 ro, V3 rd, int pix) {
+  ps.ro = ro; ps.rd = rd; ps.thr = v3(1.0f, 1.0f, 1.0f);
+  ps.color = v3(0.0f, 0.0f, 0.0f);
+  ps.lq = 0.0f; ps.lt = MAX_T;
+  ps.bounce = 0; ps.iters = 0; ps.pix = pix; ps.lag = 0u; ps.dim = 4u;
+  ps.hasShadow = false; ps.primary = true;
+}
+
 // ---------------------------------------------------------------------------
 // The path-trace kernel: tracer.fs main() (436-518) over the whole frame.
 // ---------------------------------------------------------------------------
@@ -1108,23 +1130,17 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_trace(const TraceP p) {
       if (need_pixel && rank < take) {
         uint32_t x, y;
         if (work_to_pixel(p, pool_next + rank, x, y)) {
-          ps.pix = (int)(y * p.W + x);
+          const int pix = (int)(y * p.W + x);
           if (COUNT) cnt.samples++;
+          V3 ro, rd;
           if (GEN_RAYS) {
-            camera_ray<SMP>(x, y, p.W, p.H, p.cam, p.rand_base_cam, p.smp_seed, p.tick, ps.ro, ps.rd);
+            camera_ray<SMP>(x, y, p.W, p.H, p.cam, p.rand_base_cam, p.smp_seed, p.tick, ro, rd);
           } else {
-            float4 po = p.ray_pos[ps.pix], di = p.ray_dir[ps.pix];
-            ps.ro = v3(po.x, po.y, po.z);
-            ps.rd = v3(di.x, di.y, di.z);
+            float4 po = p.ray_pos[pix], di = p.ray_dir[pix];
+            ro = v3(po.x, po.y, po.z);
+            rd = v3(di.x, di.y, di.z);
           }
-          ps.thr = v3(1.0f, 1.0f, 1.0f);
-          ps.color = v3(0.0f, 0.0f, 0.0f);
-          ps.bounce = 0;
-          ps.iters = 0;
-          ps.dim = 4u;
-          ps.lq = 0.0f;
-          ps.primary = true;
-          ps.hasShadow = false;
+          path_begin(ps, ro, rd, pix);
           need_pixel = false;
         }
       }
@@ -1138,15 +1154,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_trace(const TraceP p) {
     }
   }
 
-  if (COUNT) {
-    unsigned long long v[6] = {cnt.samples, cnt.rays, cnt.steps, cnt.leaves, cnt.shades, cnt.envs};
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      unsigned long long x = v[i];
-      for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, WAVE);
-      if (lane == 0) atomicAdd(p.counters + i, x);
-    }
-  }
+  flush_counters<COUNT>(cnt, p.counters, 0, lane);
 }
 
 // ===========================================================================
@@ -1690,19 +1698,6 @@ FM_DEV LdsTables stage_tables(void *base, const DScene &S, const float *rb_trace
 #define WF_LIGHTS_WAVES 3 // the FSPT_LIGHTS_EMITTERS logic and tail kernels: at 128 VGPRs the emitter sample spilled 2-3 registers to scratch
 #endif
 
-template <bool COUNT>
-FM_DEV void flush_counters(const Counters &cnt, unsigned long long *counters, int first, int lane) {
-  if (!COUNT) return;
-  unsigned long long v[6] = {cnt.samples, cnt.rays, cnt.steps, cnt.leaves, cnt.shades, cnt.envs};
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    if (i < first) continue;
-    unsigned long long x = v[i];
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, WAVE);
-    if (lane == 0 && x) atomicAdd(counters + i, x);
-  }
-}
-
 // ---- primary: round 1 of a batch ---------------------------------------------------------------
 // camera.fs (or the injected ray buffers), the camera ray's intersectScene (in place, stack in LDS, no refill: the 64
 // lanes of a wave are 64 ticks of one pixel, so their traversals have similar lengths) and its shading, for every
@@ -1927,22 +1922,15 @@ __global__ __launch_bounds__(WF_PRIMARY_THREADS, WF_LOGIC_WAVES) void k_wf_prima
       if (valid) {
         uint32_t slot = ring0 + i; // < 2 * ring_slots: a launch is shorter than the ring
         if (slot >= p.ring_slots) slot -= p.ring_slots;
-        Path ps;
-        ps.ro = ro; ps.rd = rd;
-        ps.thr = v3(1.0f, 1.0f, 1.0f);
-        ps.color = v3(0.0f, 0.0f, 0.0f);
-        ps.envDir = v3(0.0f, 0.0f, 0.0f);
-        ps.pend = v3(0.0f, 0.0f, 0.0f);
-        ps.wx = ps.wy = 0.0f;
-        ps.bounce = 0; ps.iters = 0; ps.pix = 0; ps.lag = 0u; ps.dim = 4u;
-        ps.lq = 0.0f; ps.lt = MAX_T;
-        ps.hasShadow = false; ps.primary = true;
         const uint32_t j = (first + i) % p.n_batch;
+        int pix = 0;
         if constexpr (SMP == SMP_SOBOL) {
           uint32_t fx = 0, fy = 0;
           work_to_pixel(p, wf_work_index(p, first + i), fx, fy);
-          ps.pix = (int)(fy * p.W + fx);
+          pix = (int)(fy * p.W + fx);
         }
+        Path ps{}; // (its NEE fields zero, as store_path may write them)
+        path_begin(ps, ro, rd, pix);
         const bool finished = advance_path<COUNT, SMP, LIGHTS>(S, ps, -1, tB, hitB, s_rb[j], p.smp_seed, p.first_tick + j, p.env_theta,
                                                                p.num_bounces, cnt, p.light_q);
         if (finished) st3(p.fin + 3 * (size_t)slot, ps.color);
@@ -2218,22 +2206,15 @@ __global__ __launch_bounds__(BLOCK_THREADS, LIGHTS ? WF_LIGHTS_WAVES : WF_TAIL_W
       // ---- pairs that own a pixel and have no path: the pixel's next tick ----
       if (is_main && ps.pix < 0 && g_w >= 0) {
         const uint32_t fx = g_pix % p.W, fy = g_pix / p.W;
+        V3 ro, rd;
         if (p.gen_rays) {
-          camera_ray<SMP>(fx, fy, p.W, p.H, p.cam, p.rb_cam[g_j], p.smp_seed, p.first_tick + g_j, ps.ro, ps.rd);
+          camera_ray<SMP>(fx, fy, p.W, p.H, p.cam, p.rb_cam[g_j], p.smp_seed, p.first_tick + g_j, ro, rd);
         } else {
           const float4 po = p.ray_pos[g_pix], di = p.ray_dir[g_pix];
-          ps.ro = v3(po.x, po.y, po.z);
-          ps.rd = v3(di.x, di.y, di.z);
+          ro = v3(po.x, po.y, po.z);
+          rd = v3(di.x, di.y, di.z);
         }
-        ps.thr = v3(1.0f, 1.0f, 1.0f);
-        ps.color = v3(0.0f, 0.0f, 0.0f);
-        ps.envDir = v3(0.0f, 0.0f, 1.0f);
-        ps.pend = v3(0.0f, 0.0f, 0.0f);
-        ps.wx = ps.wy = 0.0f;
-        ps.bounce = 0; ps.iters = 0; ps.dim = 4u;
-        ps.lq = 0.0f; ps.lt = MAX_T;
-        ps.hasShadow = false; ps.primary = true;
-        ps.pix = SMP == SMP_SOBOL ? (int)g_pix : 0;
+        path_begin(ps, ro, rd, SMP == SMP_SOBOL ? (int)g_pix : 0);
         slot = g_j; // (only its tick is used: slot % n_batch)
         g_path = true;
         if (COUNT) cnt.samples++;
@@ -2554,64 +2535,14 @@ __global__ void k_math(int op, const float *a, const float *b, uint32_t n, float
 // Guided denoiser: the guide buffers of the first hit and the edge-avoiding a-trous filter.
 // ---------------------------------------------------------------------------
 // What shade_hit computes at hit (tHit, slot ti) of ray (ro, rd) before the `inside` flip: texDiffuse and macroNormal
-// (tracer.fs:447-470), with the same helpers and the same arithmetic; only the diffuse and normal layers are fetched.
+// (tracer.fs:447-470), through shade_hit's own helpers; only the diffuse and normal layers are fetched.
 FM_DEV void first_hit_guides(const DScene &S, V3 ro, V3 rd, float tHit, int ti, V3 &albedo, V3 &normal) {
-  const float4 *hp = S.hitrec + (size_t)ti * HITREC_F4;
-  const float4 h0 = hp[0], h1 = hp[1], h2 = hp[2], h3 = hp[3], h4 = hp[4], h5 = hp[5], h6 = hp[6], h7 = hp[7], h8 = hp[8],
-               h9 = hp[9], h10 = hp[10];
-  V3 v1 = v3(h0.x, h0.y, h0.z), e1 = v3(h0.w, h1.x, h1.y), e2 = v3(h1.z, h1.w, h2.x);
-  V3 n1 = v3(h2.y, h2.z, h2.w), t1 = v3(h3.x, h3.y, h3.z), b1 = v3(h3.w, h4.x, h4.y);
-  V3 n2 = v3(h4.z, h4.w, h5.x), t2 = v3(h5.y, h5.z, h5.w), b2 = v3(h6.x, h6.y, h6.z);
-  V3 n3 = v3(h6.w, h7.x, h7.y), t3 = v3(h7.z, h7.w, h8.x), b3 = v3(h8.y, h8.z, h8.w);
-  V3 origin = vfma(rd, tHit, ro);
-  V3 w;
-  {
-    V3 vv2 = origin - v1;
-    float d00 = dot(e1, e1), d01 = dot(e1, e2), d11 = dot(e2, e2);
-    float d20 = dot(vv2, e1), d21 = dot(vv2, e2);
-    float invDenom = 1.0f / fma_(d00, d11, -(d01 * d01));
-    float bv = fma_(d11, d20, -(d01 * d21)) * invDenom;
-    float bw = fma_(d00, d21, -(d01 * d20)) * invDenom;
-    w = v3((1.0f - bv) - bw, bv, bw);
-  }
-  float tcx = fma_(w.z, h10.x, fma_(w.y, h9.z, w.x * h9.x));
-  float tcy = fma_(w.z, h10.y, fma_(w.y, h9.w, w.x * h9.y));
-  V3 texNormal;
-  const uint4 *tset = S.tex_sets + (size_t)__float_as_uint(h10.z) * 3;
-  const uint4 ts0 = tset[0], ts1 = tset[1];
-  if (ts0.x == TEXSET_CONST) {
-    uint32_t q = ts1.x;
-    albedo = v3(unorm8(q & 255u), unorm8((q >> 8) & 255u), unorm8((q >> 16) & 255u));
-    q = ts1.w;
-    texNormal = v3((unorm8(q & 255u) - 0.5f) * 2.0f, (unorm8((q >> 8) & 255u) - 0.5f) * 2.0f,
-                   (unorm8((q >> 16) & 255u) - 0.0f) * 1.0f);
-  } else {
-    const TexCoord tc = bilinear_coord((int)S.atlas_res, (int)S.atlas_res, tcx, tcy, true);
-    Tap4 qd, qn;
-    if (ts0.x == TEXSET_QUAD) {
-      const uint4 *img = S.atlas4 + (size_t)ts0.y * 8u;
-      const int tiles_x = ((int)S.atlas_res + 3) >> 2;
-      const uint4 t00 = img[tile_offset<2, 1>(tc.i0, tc.j0, tiles_x)], t10 = img[tile_offset<2, 1>(tc.i1, tc.j0, tiles_x)];
-      const uint4 t01 = img[tile_offset<2, 1>(tc.i0, tc.j1, tiles_x)], t11 = img[tile_offset<2, 1>(tc.i1, tc.j1, tiles_x)];
-      qd = Tap4{t00.x, t10.x, t01.x, t11.x, tc.a, tc.b};
-      qn = Tap4{t00.w, t10.w, t01.w, t11.w, tc.a, tc.b};
-    } else {
-      const uint4 ts2 = tset[2];
-      const TapGeom tg = tap_geom(tc, (int)S.atlas_res);
-      qd = layer_taps(S, tg, ts2.x, ts1.x);
-      qn = layer_taps(S, tg, ts2.w, ts1.w);
-    }
-    albedo = v3(tap_channel(qd, 0), tap_channel(qd, 1), tap_channel(qd, 2));
-    texNormal = v3((tap_channel(qn, 0) - 0.5f) * 2.0f, (tap_channel(qn, 1) - 0.5f) * 2.0f,
-                   (tap_channel(qn, 2) - 0.0f) * 1.0f);
-  }
-  V3 baryNormal = bary3(w, n1, n2, n3);
-  V3 baryTangent = bary3(w, t1, t2, t3);
-  V3 baryBitangent = bary3(w, b1, b2, b3);
-  normal = normalize(
-      v3(fma_(texNormal.z, baryNormal.x, fma_(texNormal.y, baryBitangent.x, texNormal.x * baryTangent.x)),
-         fma_(texNormal.z, baryNormal.y, fma_(texNormal.y, baryBitangent.y, texNormal.x * baryTangent.y)),
-         fma_(texNormal.z, baryNormal.z, fma_(texNormal.y, baryBitangent.z, texNormal.x * baryTangent.z))));
+  HitGeom g;
+  hit_geom(S, ti, ro, rd, tHit, g);
+  V3 texEmissive, texNormal, baryNormal;
+  float metallic, rough;
+  material<true, false, false, true>(S, g.set, g.tcx, g.tcy, albedo, texEmissive, metallic, rough, texNormal);
+  normal = macro_normal(g, texNormal, baryNormal);
 }
 
 // fspt_rand_base_next on the device: the s-th value of the host stream seeded with `seed` (same integer steps, same one
@@ -2742,11 +2673,10 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_light_weights(const DScene S,
   const uint32_t set = __float_as_uint(h10.z);
   float sum = 0.0f;
   for (int k = 0; k < 16; ++k) {
-    V3 x, td, te;
+    V3 x;
     float s, t;
     tri_point(((float)(k & 3) + 0.5f) * 0.25f, ((float)(k >> 2) + 0.5f) * 0.25f, v1, e1, e2, h9.x, h9.y, h9.z, h9.w, h10.x, h10.y, x, s, t);
-    light_tex(S, set, s, t, td, te);
-    const V3 le = light_le(td, te);
+    const V3 le = light_le(S, set, s, t);
     sum += fma_(0.0722f, le.z, fma_(0.7152f, le.y, 0.2126f * le.x));
   }
   const V3 cr = cross(e1, e2);
@@ -2777,7 +2707,36 @@ static hipError_t allow_lds(K kernel, size_t bytes) {
   if (bytes <= 48u * 1024u) return hipSuccess;
   return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
+// `kernel` with `lds` bytes of dynamic LDS; the caller collects the launch's error with hipGetLastError
+template <class K, class P>
+static hipError_t launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const P &p) {
+  const hipError_t e = allow_lds(kernel, lds);
+  if (e == hipSuccess) hipLaunchKernelGGL(kernel, grid, block, lds, stream, p);
+  return e;
+}
 static size_t stack_bytes(const DScene &S) { return (size_t)WAVES_PER_BLOCK * S.stack_n * WAVE * sizeof(int); }
+
+// Variant dispatch: a runtime choice becomes the compile-time argument of f (a std::integral_constant, usable as a
+// template argument), and only the instantiations f names are compiled.
+template <bool B> using bool_c = std::integral_constant<bool, B>;
+template <int I> using int_c = std::integral_constant<int, I>;
+template <class F> static hipError_t with_flag(bool b, F &&f) { return b ? f(bool_c<true>{}) : f(bool_c<false>{}); }
+template <class F> static hipError_t with_sampler(uint32_t sampler, F &&f) {
+  return sampler ? f(int_c<SMP_SOBOL>{}) : f(int_c<SMP_REF>{});
+}
+// the shading variant of a path kernel: f(SMP, LIGHTS)
+template <class P, class F> static hipError_t with_shading(const P &p, F &&f) {
+  return with_sampler(p.sampler, [&](auto M) { return with_flag(p.lights, [&](auto L) { return f(M, L); }); });
+}
+// the traversal form of a wavefront launch: f(COUNT, ANYHIT, WIDE).  count: 0 production, 1 counters, 2 counters with
+// any-hit shadow rays; wide (production only): 0 the 64-byte nodes, 1 the two-level nodes, 2 adaptive (k_wf_tail)
+template <class F> static hipError_t with_form(int count, int wide, F &&f) {
+  if (count == 1) return f(bool_c<true>{}, bool_c<false>{}, int_c<0>{});
+  if (count == 2) return f(bool_c<true>{}, bool_c<true>{}, int_c<0>{});
+  if (wide == 2) return f(bool_c<false>{}, bool_c<true>{}, int_c<2>{});
+  if (wide == 1) return f(bool_c<false>{}, bool_c<true>{}, int_c<1>{});
+  return f(bool_c<false>{}, bool_c<true>{}, int_c<0>{});
+}
 
 hipError_t launch_trace(const TraceP &p, bool gen_rays, bool count, int num_cus, hipStream_t stream) {
   size_t lds = stack_bytes(p.scene);
@@ -2788,20 +2747,12 @@ hipError_t launch_trace(const TraceP &p, bool gen_rays, bool count, int num_cus,
   uint32_t grid = (uint32_t)(num_cus * blocks_per_cu);
   if (grid > max_useful) grid = max_useful;
   if (grid == 0) return hipSuccess;
-  dim3 g(grid), b(BLOCK_THREADS);
-  hipError_t e;
-#define FSPT_LAUNCH_MEGA_SL(G, C, M, L)                                                      \
-  do {                                                                                        \
-    if ((e = allow_lds(k_trace<G, C, M, L>, lds)) != hipSuccess) return e;                    \
-    hipLaunchKernelGGL((k_trace<G, C, M, L>), g, b, lds, stream, p);                          \
-  } while (0)
-#define FSPT_LAUNCH_MEGA_S(G, C, M) do { if (p.lights) FSPT_LAUNCH_MEGA_SL(G, C, M, true); else FSPT_LAUNCH_MEGA_SL(G, C, M, false); } while (0)
-#define FSPT_LAUNCH_MEGA(G, C) do { if (p.sampler) FSPT_LAUNCH_MEGA_S(G, C, SMP_SOBOL); else FSPT_LAUNCH_MEGA_S(G, C, SMP_REF); } while (0)
-  if (gen_rays) { if (count) FSPT_LAUNCH_MEGA(true, true); else FSPT_LAUNCH_MEGA(true, false); }
-  else { if (count) FSPT_LAUNCH_MEGA(false, true); else FSPT_LAUNCH_MEGA(false, false); }
-#undef FSPT_LAUNCH_MEGA
-#undef FSPT_LAUNCH_MEGA_S
-#undef FSPT_LAUNCH_MEGA_SL
+  const hipError_t e = with_flag(gen_rays, [&](auto G) {
+    return with_flag(count, [&](auto C) {
+      return with_shading(p, [&](auto M, auto L) { return launch(k_trace<G, C, M, L>, dim3(grid), dim3(BLOCK_THREADS), lds, stream, p); });
+    });
+  });
+  if (e != hipSuccess) return e;
   return hipGetLastError();
 }
 
@@ -2853,43 +2804,24 @@ hipError_t launch_wf(int kernel, const WfP &p, int count, int num_cus, hipStream
       grid = min(grid, (uint32_t)num_cus * min((uint32_t)blocks, (uint32_t)WF_TRACE_GRID_RESIDENT));
 #endif
     }
-#define FSPT_LAUNCH_TRACE_L(C, A, Wd, L)                                                                   \
-    do {                                                                                                     \
-      if ((e = allow_lds(k_wf_trace<C, A, Wd, L>, lds)) != hipSuccess) return e;                             \
-      hipLaunchKernelGGL((k_wf_trace<C, A, Wd, L>), dim3(grid), dim3(BLOCK_THREADS), lds, stream, q);        \
-    } while (0)
-#define FSPT_LAUNCH_TRACE(C, A, Wd) do { if (p.lights) FSPT_LAUNCH_TRACE_L(C, A, Wd, true); else FSPT_LAUNCH_TRACE_L(C, A, Wd, false); } while (0)
-    if (count == 1) FSPT_LAUNCH_TRACE(true, false, false);
-    else if (count == 2) FSPT_LAUNCH_TRACE(true, true, false);
-    else if (wide) FSPT_LAUNCH_TRACE(false, true, true);
-    else FSPT_LAUNCH_TRACE(false, true, false);
-#undef FSPT_LAUNCH_TRACE
-#undef FSPT_LAUNCH_TRACE_L
+    e = with_form(count, wide ? 1 : 0, [&](auto C, auto A, auto Wd) {
+      return with_flag(p.lights, [&](auto L) {
+        return launch(k_wf_trace<C, A, (Wd != 0), L>, dim3(grid), dim3(BLOCK_THREADS), lds, stream, q);
+      });
+    });
   } else if (kernel == WF_K_TAIL) {
     // paths a block holds at a time (two lanes per path; one pair per wave when the kernel spreads a small launch's paths)
     const uint32_t per_block = WAVES_PER_BLOCK * (WF_TAIL_PAIRS_AUTO && !(p.ctl && p.finish) ? 1u : (uint32_t)WF_TAIL_PAIRS);
     uint32_t grid = min((total + per_block - 1) / per_block, (uint32_t)num_cus * (WF_TAIL_WAVES > 4 ? WF_TAIL_WAVES : 4));
     size_t lds = stack_bytes(p.scene);
-#define FSPT_LAUNCH_TAIL_SL(C, A, Wd, M, L)                                                                      \
-    do {                                                                                                           \
-      if (p.ctl && p.finish) {                                                                                     \
-        if ((e = allow_lds(k_wf_tail<C, A, true, Wd, M, L>, lds)) != hipSuccess) return e;                         \
-        hipLaunchKernelGGL((k_wf_tail<C, A, true, Wd, M, L>), dim3(grid), dim3(BLOCK_THREADS), lds, stream, p);    \
-      } else {                                                                                                     \
-        if ((e = allow_lds(k_wf_tail<C, A, false, Wd, M, L>, lds)) != hipSuccess) return e;                        \
-        hipLaunchKernelGGL((k_wf_tail<C, A, false, Wd, M, L>), dim3(grid), dim3(BLOCK_THREADS), lds, stream, p);   \
-      }                                                                                                            \
-    } while (0)
-#define FSPT_LAUNCH_TAIL_S(C, A, Wd, M) do { if (p.lights) FSPT_LAUNCH_TAIL_SL(C, A, Wd, M, true); else FSPT_LAUNCH_TAIL_SL(C, A, Wd, M, false); } while (0)
-#define FSPT_LAUNCH_TAIL(C, A, Wd) do { if (p.sampler) FSPT_LAUNCH_TAIL_S(C, A, Wd, SMP_SOBOL); else FSPT_LAUNCH_TAIL_S(C, A, Wd, SMP_REF); } while (0)
-    if (count == 1) FSPT_LAUNCH_TAIL(true, false, 0);
-    else if (count == 2) FSPT_LAUNCH_TAIL(true, true, 0);
-    else if (wide && p.tail_adaptive) FSPT_LAUNCH_TAIL(false, true, 2);
-    else if (wide) FSPT_LAUNCH_TAIL(false, true, 1);
-    else FSPT_LAUNCH_TAIL(false, true, 0);
-#undef FSPT_LAUNCH_TAIL
-#undef FSPT_LAUNCH_TAIL_S
-#undef FSPT_LAUNCH_TAIL_SL
+    // GEN: the last launch of a stream run (k_wf_tail)
+    e = with_form(count, wide ? (p.tail_adaptive ? 2 : 1) : 0, [&](auto C, auto A, auto Wd) {
+      return with_flag(p.ctl && p.finish, [&](auto G) {
+        return with_shading(p, [&](auto M, auto L) {
+          return launch(k_wf_tail<C, A, G, Wd, M, L>, dim3(grid), dim3(BLOCK_THREADS), lds, stream, p);
+        });
+      });
+    });
   } else if (kernel == WF_K_LOGIC || kernel == WF_K_PRIMARY) {
     // resident blocks per CU at WF_LOGIC_WAVES waves per SIMD (4 SIMDs): 2 blocks of 512 threads at 4 waves; twice that many in flight
     const uint32_t threads = kernel == WF_K_PRIMARY ? (uint32_t)WF_PRIMARY_THREADS : (uint32_t)WF_LOGIC_THREADS;
@@ -2903,36 +2835,29 @@ hipError_t launch_wf(int kernel, const WfP &p, int count, int num_cus, hipStream
     if (kernel == WF_K_PRIMARY) {
       const size_t dyn = (size_t)(WF_PRIMARY_THREADS / WAVE) * p.scene.stack_n * WAVE * sizeof(int) + (tab ? tab_bytes : 0u) +
                          (prim_r > 1u ? (size_t)prim_r * WF_PRIMARY_THREADS * 32u : 0u); // + ray and hit of every sample of a block iteration
-#define FSPT_LAUNCH_PRIMARY_SL(C, T, RR, Wd, M, L)                                                                   \
-      do {                                                                                                             \
-        if ((e = allow_lds(k_wf_primary<C, T, RR, Wd, M, L>, dyn)) != hipSuccess) return e;                            \
-        hipLaunchKernelGGL((k_wf_primary<C, T, RR, Wd, M, L>), dim3(grid), dim3(WF_PRIMARY_THREADS), dyn, stream, p);  \
-      } while (0)
-#define FSPT_LAUNCH_PRIMARY_S(C, T, RR, Wd, M) do { if (p.lights) FSPT_LAUNCH_PRIMARY_SL(C, T, RR, Wd, M, true); else FSPT_LAUNCH_PRIMARY_SL(C, T, RR, Wd, M, false); } while (0)
-#define FSPT_LAUNCH_PRIMARY(C, T, RR, Wd) do { if (p.sampler) FSPT_LAUNCH_PRIMARY_S(C, T, RR, Wd, SMP_SOBOL); else FSPT_LAUNCH_PRIMARY_S(C, T, RR, Wd, SMP_REF); } while (0)
-#define FSPT_LAUNCH_PRIMARY_R(C, T, Wd) do { if (prim_r > 1u) FSPT_LAUNCH_PRIMARY(C, T, 2, Wd); else FSPT_LAUNCH_PRIMARY(C, T, 1, Wd); } while (0)
-      if (count) { if (tab) FSPT_LAUNCH_PRIMARY_R(true, true, false); else FSPT_LAUNCH_PRIMARY_R(true, false, false); }
-      else if (wide) { if (tab) FSPT_LAUNCH_PRIMARY_R(false, true, true); else FSPT_LAUNCH_PRIMARY_R(false, false, true); }
-      else { if (tab) FSPT_LAUNCH_PRIMARY_R(false, true, false); else FSPT_LAUNCH_PRIMARY_R(false, false, false); }
-#undef FSPT_LAUNCH_PRIMARY_R
-#undef FSPT_LAUNCH_PRIMARY
-#undef FSPT_LAUNCH_PRIMARY_S
-#undef FSPT_LAUNCH_PRIMARY_SL
+      // (the primary kernel casts no shadow rays: no ANYHIT)
+      e = with_form(count, wide ? 1 : 0, [&](auto C, auto, auto Wd) {
+        return with_flag(tab, [&](auto T) {
+          return with_flag(prim_r > 1u, [&](auto R2) {
+            return with_shading(p, [&](auto M, auto L) {
+              return launch(k_wf_primary<C, T, (R2 ? 2 : 1), (Wd != 0), M, L>, dim3(grid), dim3(WF_PRIMARY_THREADS), dyn, stream, p);
+            });
+          });
+        });
+      });
     } else {
       const size_t dyn = tab ? tab_bytes : 0u;
-#define FSPT_LAUNCH_LOGIC_SL(C, T, M, L) hipLaunchKernelGGL((k_wf_logic<C, T, M, L>), dim3(grid), dim3(WF_LOGIC_THREADS), dyn, stream, p)
-#define FSPT_LAUNCH_LOGIC_S(C, T, M) do { if (p.lights) FSPT_LAUNCH_LOGIC_SL(C, T, M, true); else FSPT_LAUNCH_LOGIC_SL(C, T, M, false); } while (0)
-#define FSPT_LAUNCH_LOGIC(C, T) do { if (p.sampler) FSPT_LAUNCH_LOGIC_S(C, T, SMP_SOBOL); else FSPT_LAUNCH_LOGIC_S(C, T, SMP_REF); } while (0)
-      if (count) { if (tab) FSPT_LAUNCH_LOGIC(true, true); else FSPT_LAUNCH_LOGIC(true, false); }
-      else { if (tab) FSPT_LAUNCH_LOGIC(false, true); else FSPT_LAUNCH_LOGIC(false, false); }
-#undef FSPT_LAUNCH_LOGIC
-#undef FSPT_LAUNCH_LOGIC_S
-#undef FSPT_LAUNCH_LOGIC_SL
+      e = with_flag(count != 0, [&](auto C) {
+        return with_flag(tab, [&](auto T) {
+          return with_shading(p, [&](auto M, auto L) { return launch(k_wf_logic<C, T, M, L>, dim3(grid), dim3(WF_LOGIC_THREADS), dyn, stream, p); });
+        });
+      });
     }
   } else {
     uint32_t grid = min((p.work_total + BLOCK_THREADS - 1) / BLOCK_THREADS, (uint32_t)num_cus * WF_RESOLVE_BLOCKS_PER_CU);
     hipLaunchKernelGGL(k_wf_resolve, dim3(grid), dim3(BLOCK_THREADS), 0, stream, p);
   }
+  if (e != hipSuccess) return e;
   return hipGetLastError();
 }
 
@@ -2949,8 +2874,11 @@ hipError_t launch_camera(uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const
                          hipStream_t stream, uint32_t sampler, uint32_t smp_seed, uint32_t sample) {
   uint32_t n = W * H;
   const dim3 g((n + BLOCK_THREADS - 1) / BLOCK_THREADS), b(BLOCK_THREADS);
-  if (sampler) hipLaunchKernelGGL(k_camera<SMP_SOBOL>, g, b, 0, stream, W, H, vw, vh, cam, rand_base, smp_seed, sample, pos, dir);
-  else hipLaunchKernelGGL(k_camera<SMP_REF>, g, b, 0, stream, W, H, vw, vh, cam, rand_base, 0u, 0u, pos, dir);
+  with_sampler(sampler, [&](auto M) {
+    const bool sobol = M == SMP_SOBOL; // (the reference sampler takes no seed and no sample number)
+    hipLaunchKernelGGL(k_camera<M>, g, b, 0, stream, W, H, vw, vh, cam, rand_base, sobol ? smp_seed : 0u, sobol ? sample : 0u, pos, dir);
+    return hipSuccess;
+  });
   return hipGetLastError();
 }
 

@@ -43,6 +43,10 @@ class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
 
 
+class AdaptiveParams(C.Structure):
+    _fields_ = [("target_rel_mse", C.c_double), ("max_ticks", C.c_uint32), ("min_ticks", C.c_uint32), ("round_ticks", C.c_uint32)]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "steps", "leaves", "shades", "env_lookups")]
 
@@ -105,6 +109,9 @@ SIGNATURES = {
     "fspt_trace": (C.c_int, [_VP, C.c_uint32, C.c_float, C.c_float, C.c_uint32]),
     "fspt_trace_test": (C.c_int, [_VP, C.c_uint32]),
     "fspt_render": (C.c_int, [_VP, C.POINTER(CameraParams), C.c_uint32, C.c_uint32, C.c_uint64]),
+    "fspt_render_adaptive": (C.c_int, [_VP, C.POINTER(CameraParams), C.POINTER(AdaptiveParams), C.c_uint64]),
+    "fspt_read_sample_counts": (C.c_int, [_VP, _U32]),
+    "fspt_adaptive_last_stats": (C.c_int, [_VP, _U32, C.POINTER(C.c_uint64), C.POINTER(C.c_double), _U32, C.c_uint32]),
     "fspt_rand_base_next": (C.c_float, [C.POINTER(C.c_uint64)]),
     "fspt_clear": (C.c_int, [_VP]),
     "fspt_sync": (C.c_int, [_VP]),

@@ -700,6 +700,7 @@ int fspt_target_destroy(fspt_target *t) {
   }
   hipFree(t->accum_own); hipFree(t->ray_pos); hipFree(t->ray_dir); hipFree(t->work_counters); hipFree(t->counters);
   hipFree(t->feat); hipFree(t->dn_tmp[0]); hipFree(t->dn_tmp[1]); hipFree(t->dn_out);
+  hipFree(t->ad_snap); hipFree(t->ad_list[0]); hipFree(t->ad_list[1]); hipFree(t->ad_count); hipFree(t->ad_err);
   {
     fspt_target::WfLane &ln = t->wf;
     for (void *m : ln.mem) hipFree(m);
@@ -996,6 +997,134 @@ int fspt_render(fspt_target *t, const fspt_camera_params *cam_in, uint32_t first
   uint64_t st0 = seed;
   for (uint32_t k = 0; k < n_ticks; ++k) { rbc[k] = fspt_rand_base_next(&st0); rbt[k] = fspt_rand_base_next(&st0); }
   return render_ticks(t, &cam_c, first_tick, n_ticks, rbc.data(), rbt.data());
+}
+
+// ---- adaptive sampling (include/fspt.h) -----------------------------------------------------------------
+// Rounds of round_ticks ticks through render_ticks with the active tile list set (every pipeline traces only those
+// tiles), then k_adaptive_error (E_T; the snapshot in the same pass) and, from min_ticks on, k_adaptive_select (the next
+// list).  All active tiles share one tick count, so the running mean of a tile retired after n ticks is fspt_render's
+// after n ticks.  One 4-byte read-back per decided round: the new list length.
+static int ad_alloc(fspt_target *t, uint32_t n_tiles) {
+  if (!t->ad_snap) HIP_TRY(hipMalloc((void **)&t->ad_snap, (size_t)t->W * t->H * 16));
+  if (t->ad_tiles == n_tiles) return FSPT_OK;
+  for (uint32_t *&b : t->ad_list) { hipFree(b); b = nullptr; }
+  hipFree(t->ad_count); hipFree(t->ad_err);
+  t->ad_count = nullptr; t->ad_err = nullptr; t->ad_tiles = 0;
+  HIP_TRY(hipMalloc((void **)&t->ad_list[0], (size_t)n_tiles * 4));
+  HIP_TRY(hipMalloc((void **)&t->ad_list[1], (size_t)n_tiles * 4));
+  HIP_TRY(hipMalloc((void **)&t->ad_count, ((size_t)n_tiles + 1) * 4));
+  HIP_TRY(hipMalloc((void **)&t->ad_err, (size_t)n_tiles * 8));
+  t->ad_tiles = n_tiles;
+  return FSPT_OK;
+}
+
+static int ad_rounds(fspt_target *t, const fspt_camera_params *cam, const fspt_adaptive_params *q, const float *rbc,
+                     const float *rbt, uint32_t n_tiles, uint32_t tiles_x, uint32_t n_active) {
+  const uint32_t R = q->round_ticks;
+  fspt::AdaptiveP a{};
+  a.accum = t->accum; a.snap = t->ad_snap; a.count = t->ad_count; a.err = t->ad_err; a.n_out = t->ad_count + n_tiles;
+  a.W = t->W; a.vw = t->vw; a.vh = t->vh; a.tile = t->tile; a.tiles_x = tiles_x;
+  a.min_ticks = q->min_ticks; a.max_ticks = q->max_ticks; a.target = q->target_rel_mse;
+  uint32_t cur = 0, n = 0, m = 0;
+  t->ad_rounds = 0;
+  while (n < q->max_ticks && n_active > 0) {
+    t->tile_list = t->ad_list[cur]; t->n_listed = n_active;
+    int rc = render_ticks(t, cam, n, R, rbc + n, rbt + n);
+    t->tile_list = nullptr; t->n_listed = 0;
+    if (rc) return rc;
+    n += R;
+    t->ad_rounds++;
+    a.list_in = t->ad_list[cur]; a.list_out = t->ad_list[cur ^ 1]; a.n_in = n_active; a.n = n;
+    const bool decide = m != 0 && n >= q->min_ticks, refresh = m == 0 || n >= 2 * m;
+    if (decide || refresh) {
+      a.m = decide ? m : 0u; // (m = 0: the snapshot alone)
+      a.refresh = refresh ? 1u : 0u;
+      HIP_TRY(fspt::launch_adaptive_error(a, t->stream));
+    }
+    if (refresh) m = n;
+    if (decide) {
+      HIP_TRY(fspt::launch_adaptive_select(a, t->stream));
+      HIP_TRY(hipMemcpyAsync(&n_active, a.n_out, 4, hipMemcpyDeviceToHost, t->stream));
+      HIP_TRY(hipStreamSynchronize(t->stream));
+      cur ^= 1;
+    }
+  }
+  return FSPT_OK;
+}
+
+int fspt_render_adaptive(fspt_target *t, const fspt_camera_params *cam_in, const fspt_adaptive_params *q, uint64_t seed) {
+  if (!t || !cam_in || !q) { fspt_set_error("fspt_render_adaptive: NULL argument"); return FSPT_E_INVALID; }
+  const uint32_t R = q->round_ticks;
+  if (R < 2 || R > 128) { fspt_set_error("fspt_render_adaptive: round_ticks %u not in [2, 128]", R); return FSPT_E_INVALID; }
+  if (q->min_ticks % R || q->min_ticks < 2 * R) {
+    fspt_set_error("fspt_render_adaptive: min_ticks %u must be a multiple of round_ticks %u, at least 2 rounds", q->min_ticks, R);
+    return FSPT_E_INVALID;
+  }
+  if (q->max_ticks % R || q->max_ticks < q->min_ticks) {
+    fspt_set_error("fspt_render_adaptive: max_ticks %u must be a multiple of round_ticks %u, at least min_ticks %u", q->max_ticks, R, q->min_ticks);
+    return FSPT_E_INVALID;
+  }
+  if (!std::isfinite(q->target_rel_mse) || q->target_rel_mse < 0.0) {
+    fspt_set_error("fspt_render_adaptive: target_rel_mse must be finite and >= 0");
+    return FSPT_E_INVALID;
+  }
+  { int rc = check_device(t->scene ? t->scene->device : 0); if (rc) return rc; }
+  if (t->n_shards > 1) { fspt_set_error("fspt_render_adaptive: not on a sharded target (%u shards)", t->n_shards); return FSPT_E_STATE; }
+  FLUSH_OR_RETURN(t);
+  fspt_camera_params cam_c = *cam_in;
+  cam_c.num_bounces = clamp_bounces(cam_c.num_bounces);
+  const uint32_t tile = t->tile, tiles_x = (t->W + tile - 1) / tile, tiles_y = (t->H + tile - 1) / tile, n_tiles = tiles_x * tiles_y;
+  { int rc = ad_alloc(t, n_tiles); if (rc) return rc; }
+  std::vector<uint32_t> list;
+  for (uint32_t g = 0; g < n_tiles; ++g)
+    if ((g % tiles_x) * tile < t->vw && (g / tiles_x) * tile < t->vh) list.push_back(g);
+  t->ad_valid = false;
+  HIP_TRY(hipMemsetAsync(t->ad_count, 0, (size_t)n_tiles * 4, t->stream));
+  HIP_TRY(hipMemsetAsync(t->ad_err, 0, (size_t)n_tiles * 8, t->stream));
+  if (!list.empty()) HIP_TRY(hipMemcpyAsync(t->ad_list[0], list.data(), list.size() * 4, hipMemcpyHostToDevice, t->stream));
+  HIP_TRY(hipMemsetAsync(t->accum, 0, (size_t)t->W * t->H * 16, t->stream)); // (fspt_clear)
+  t->acc_ticks = 0;
+  std::vector<float> rbc(q->max_ticks), rbt(q->max_ticks);
+  uint64_t st0 = seed;
+  for (uint32_t k = 0; k < q->max_ticks; ++k) { rbc[k] = fspt_rand_base_next(&st0); rbt[k] = fspt_rand_base_next(&st0); }
+  int rc = ad_rounds(t, &cam_c, q, rbc.data(), rbt.data(), n_tiles, tiles_x, (uint32_t)list.size());
+  if (rc) return rc;
+  t->ad_count_host.assign(n_tiles, 0u);
+  t->ad_err_host.assign(n_tiles, 0.0);
+  HIP_TRY(hipMemcpyAsync(t->ad_count_host.data(), t->ad_count, (size_t)n_tiles * 4, hipMemcpyDeviceToHost, t->stream));
+  HIP_TRY(hipMemcpyAsync(t->ad_err_host.data(), t->ad_err, (size_t)n_tiles * 8, hipMemcpyDeviceToHost, t->stream));
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  t->ad_samples = 0;
+  for (uint32_t g = 0; g < n_tiles; ++g) {
+    const uint32_t x0 = (g % tiles_x) * tile, y0 = (g / tiles_x) * tile;
+    if (x0 >= t->vw || y0 >= t->vh) continue;
+    t->ad_samples += (uint64_t)t->ad_count_host[g] * std::min(tile, t->vw - x0) * std::min(tile, t->vh - y0);
+  }
+  t->ad_vw = t->vw; t->ad_vh = t->vh; t->ad_tile = tile;
+  t->ad_valid = true;
+  return FSPT_OK;
+}
+
+int fspt_read_sample_counts(fspt_target *t, uint32_t *out) {
+  if (!t || !out) { fspt_set_error("fspt_read_sample_counts: NULL argument"); return FSPT_E_INVALID; }
+  if (!t->ad_valid) { fspt_set_error("fspt_read_sample_counts: no fspt_render_adaptive run yet"); return FSPT_E_STATE; }
+  const uint32_t tile = t->ad_tile, tiles_x = (t->W + tile - 1) / tile;
+  for (uint32_t y = 0; y < t->H; ++y)
+    for (uint32_t x = 0; x < t->W; ++x)
+      out[(size_t)y * t->W + x] = (x < t->ad_vw && y < t->ad_vh) ? t->ad_count_host[(y / tile) * tiles_x + x / tile] : 0u;
+  return FSPT_OK;
+}
+
+int fspt_adaptive_last_stats(fspt_target *t, uint32_t *rounds, uint64_t *samples, double *tile_err, uint32_t *tile_ticks, uint32_t cap) {
+  if (!t) { fspt_set_error("fspt_adaptive_last_stats: NULL target"); return FSPT_E_INVALID; }
+  if (!t->ad_valid) { fspt_set_error("fspt_adaptive_last_stats: no fspt_render_adaptive run yet"); return FSPT_E_STATE; }
+  const uint32_t n_tiles = (uint32_t)t->ad_count_host.size();
+  if ((tile_err || tile_ticks) && cap < n_tiles) { fspt_set_error("fspt_adaptive_last_stats: cap %u < %u tiles", cap, n_tiles); return FSPT_E_INVALID; }
+  if (rounds) *rounds = t->ad_rounds;
+  if (samples) *samples = t->ad_samples;
+  if (tile_err) std::memcpy(tile_err, t->ad_err_host.data(), (size_t)n_tiles * 8);
+  if (tile_ticks) std::memcpy(tile_ticks, t->ad_count_host.data(), (size_t)n_tiles * 4);
+  return FSPT_OK;
 }
 
 int fspt_target_set_deferred(fspt_target *t, int enable) {

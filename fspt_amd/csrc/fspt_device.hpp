@@ -131,6 +131,7 @@ struct TraceP {
   // sharding
   uint32_t shard, n_shards, tile;
   uint32_t tiles_x, tiles_y, n_owned_tiles;
+  const uint32_t *tile_list; // NULL: the shard's tiles round-robin; else n_owned_tiles tile indices (fspt_render_adaptive)
   uint32_t sampler;  // FSPT_SAMPLER_*: which instantiation launch_trace picks
   uint32_t smp_seed; // FSPT_SAMPLER_SOBOL's seed
   uint32_t lights;   // 1: the FSPT_LIGHTS_EMITTERS instantiations (only when scene.n_lights > 0)
@@ -301,6 +302,7 @@ struct WfP {
   float4 *accum;
   unsigned long long *counters;
   uint32_t shard, n_shards, tile, tiles_x, tiles_y, n_owned_tiles;
+  const uint32_t *tile_list; // as in TraceP
   uint32_t sampler;  // as in TraceP; a slot's sample index is first_tick + slot % n_batch
   uint32_t smp_seed;
   uint32_t lights;   // as in TraceP
@@ -320,6 +322,7 @@ struct TilePackP {
   uint32_t channels; // 0 / 4: RGBA, 3: RGB
   uint32_t W, H, vw, vh;
   uint32_t shard, n_shards, tile, tiles_x, tiles_y, n_owned_tiles;
+  const uint32_t *tile_list; // always NULL (work_to_pixel reads it)
 };
 hipError_t launch_tile_pack(const TilePackP &p, bool unpack, hipStream_t stream);
 
@@ -345,6 +348,27 @@ struct AtrousP {
 };
 hipError_t launch_features(const FeatureP &p, hipStream_t stream);
 hipError_t launch_atrous(const AtrousP &p, hipStream_t stream);
+
+// adaptive sampling (fspt_render_adaptive): after n ticks, with the snapshot S taken after m < n ticks
+struct AdaptiveP {
+  const float4 *accum; // I = the mean of n ticks
+  float4 *snap;        // S = the mean of the first m
+  const uint32_t *list_in; // the n_in active tiles, ascending
+  uint32_t *list_out;
+  uint32_t n_in;
+  uint32_t *n_out;     // the length of list_out (one word)
+  uint32_t *count;     // per tile: the tick count it retired with (written when it retires)
+  double *err;         // per tile: E_T (k_adaptive_error) / the E_T that retired it
+  uint32_t W, vw, vh, tile, tiles_x;
+  uint32_t n, m;       // m = 0: only the snapshot (S := I)
+  uint32_t refresh;    // 1: S := I for the tiles of the list in the same pass
+  uint32_t min_ticks, max_ticks;
+  double target;
+};
+// one workgroup per active tile: E_T = mean over the tile's viewport pixels and 3 channels of m (I - S)^2 / ((n - m)(I^2 + 0.01))
+hipError_t launch_adaptive_error(const AdaptiveP &p, hipStream_t stream);
+// one workgroup: retire the tiles of list_in whose E_T decides it, list the rest in list_out (same order), *n_out
+hipError_t launch_adaptive_select(const AdaptiveP &p, hipStream_t stream);
 
 // launchers (fspt_kernels.hip)
 hipError_t launch_trace(const TraceP &p, bool gen_rays, bool count, int num_cus, hipStream_t stream);

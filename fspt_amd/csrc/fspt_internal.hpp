@@ -16,6 +16,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <array>
 #include <atomic>
 #include <cmath>
@@ -228,6 +229,21 @@ struct fspt_target {
   int pr_slot = -1;                  // slot of the frame the last present enqueued (-1: none since the last join)
   uint32_t acc_ticks = 0;            // 1 + the index of the most recent tick traced into the accumulator (0: none since
                                      // create / fspt_clear; fspt_target_bind_accumulator does not reset it)
+  // fspt_render_adaptive: while tile_list is set (only inside that call) every pipeline traces the n_listed
+  // tiles it names instead of the shard's round-robin.  The device buffers are allocated on the first call.
+  const uint32_t *tile_list = nullptr;
+  uint32_t n_listed = 0;
+  float4 *ad_snap = nullptr;                 // S: W*H
+  uint32_t *ad_list[2] = {nullptr, nullptr}; // active tiles, ping-pong
+  uint32_t *ad_count = nullptr;              // per tile: retired count; [n_tiles] = the select kernel's list length
+  double *ad_err = nullptr;                  // per tile: E_T
+  uint32_t ad_tiles = 0;                     // tiles the buffers hold
+  // the last run (fspt_read_sample_counts, fspt_adaptive_last_stats)
+  bool ad_valid = false;
+  uint32_t ad_rounds = 0, ad_vw = 0, ad_vh = 0, ad_tile = 0;
+  uint64_t ad_samples = 0;
+  std::vector<uint32_t> ad_count_host;
+  std::vector<double> ad_err_host;
 };
 
 static const uint32_t WORK_RING = 4096;

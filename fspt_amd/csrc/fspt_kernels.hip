@@ -1020,14 +1020,23 @@ FM_DEV float4 accumulate_sample(float4 prev, V3 color, uint32_t tick) {
 }
 
 // Work index -> pixel.  The frame is cut into tile x tile pixel tiles dealt
-// round-robin to shards; inside a tile pixels are enumerated in 8x8 blocks so
-// that the 64 lanes of a wave start on a compact screen patch.
-template <class P>
+// round-robin to shards - or, with a tile list (fspt_render_adaptive), the
+// listed tiles in list order; inside a tile pixels are enumerated in 8x8 blocks so
+// that the 64 lanes of a wave start on a compact screen patch.  LIST = false: the
+// list is never looked at (k_wf_primary / k_wf_tail: the launch picks the
+// instantiation, so that the production kernels' registers stay as they were).
+template <bool LIST = true, class P>
 FM_DEV bool work_to_pixel(const P &p, uint32_t idx, uint32_t &x, uint32_t &y) {
   uint32_t tile = p.tile;
   uint32_t per_tile = tile * tile;
   uint32_t k = idx / per_tile, local = idx - k * per_tile;
-  uint32_t g = p.shard + k * p.n_shards;
+  uint32_t g;
+  if (LIST && p.tile_list) {
+    if (k >= p.n_owned_tiles) return false;
+    g = p.tile_list[k];
+  } else {
+    g = p.shard + k * p.n_shards;
+  }
   if (g >= p.tiles_x * p.tiles_y) return false;
   uint32_t tx = g % p.tiles_x, ty = g / p.tiles_x;
   uint32_t sub = local >> 6, l = local & 63u;
@@ -1730,7 +1739,7 @@ FM_DEV LdsTables stage_tables(void *base, const DScene &S, const float *rb_trace
 #ifndef WF_PRIMARY_SLICE
 #define WF_PRIMARY_SLICE 8u // traversal steps between two looks at the wave's sample counter
 #endif
-template <bool COUNT, bool LDSTAB, int R, bool WIDE, int SMP, bool LIGHTS = false>
+template <bool COUNT, bool LDSTAB, int R, bool WIDE, int SMP, bool LIGHTS = false, bool LIST = false>
 __global__ __launch_bounds__(WF_PRIMARY_THREADS, WF_LOGIC_WAVES) void k_wf_primary(const WfP p) {
   extern __shared__ int lds_dyn[]; // the waves' traversal stacks | [tables] | [camera rays and hits of the block iteration]
   constexpr int NW = WF_PRIMARY_THREADS / WAVE;
@@ -1795,7 +1804,7 @@ __global__ __launch_bounds__(WF_PRIMARY_THREADS, WF_LOGIC_WAVES) void k_wf_prima
       const uint32_t i = base + threadIdx.x;
       const uint32_t g = first + i;
       uint32_t fx = 0, fy = 0;
-      valid1 = i < n_in && work_to_pixel(p, wf_work_index(p, g), fx, fy);
+      valid1 = i < n_in && work_to_pixel<LIST>(p, wf_work_index(p, g), fx, fy);
       if (valid1) {
         if (p.gen_rays) {
           camera_ray<SMP>(fx, fy, p.W, p.H, p.cam, p.rb_cam[g % p.n_batch], p.smp_seed, p.first_tick + g % p.n_batch, o1, d1);
@@ -1824,7 +1833,7 @@ __global__ __launch_bounds__(WF_PRIMARY_THREADS, WF_LOGIC_WAVES) void k_wf_prima
         uint32_t fx = 0, fy = 0;
         V3 o = v3(0.0f, 0.0f, 0.0f), d = v3(0.0f, 0.0f, 1.0f);
         int h = -2; // -2: the sample does not exist (outside the viewport / beyond the launch)
-        if (i < n_in && work_to_pixel(p, wf_work_index(p, g), fx, fy)) {
+        if (i < n_in && work_to_pixel<LIST>(p, wf_work_index(p, g), fx, fy)) {
           if (p.gen_rays) {
             camera_ray<SMP>(fx, fy, p.W, p.H, p.cam, p.rb_cam[g % p.n_batch], p.smp_seed, p.first_tick + g % p.n_batch, o, d);
           } else {
@@ -1926,7 +1935,7 @@ __global__ __launch_bounds__(WF_PRIMARY_THREADS, WF_LOGIC_WAVES) void k_wf_prima
         int pix = 0;
         if constexpr (SMP == SMP_SOBOL) {
           uint32_t fx = 0, fy = 0;
-          work_to_pixel(p, wf_work_index(p, first + i), fx, fy);
+          work_to_pixel<LIST>(p, wf_work_index(p, first + i), fx, fy);
           pix = (int)(fy * p.W + fx);
         }
         Path ps{}; // (its NEE fields zero, as store_path may write them)
@@ -2098,7 +2107,7 @@ FM_DEV V3 shfl3(V3 v, int src) { return v3(__shfl(v.x, src, WAVE), __shfl(v.y, s
 // dependent chains of the paths still alive, walked by a few lanes on a mostly idle chip - there a step costs a cache-miss
 // latency, and two levels per round trip shorten the chain (profiles/r05/launch_list_*.txt: the tail launch is 0.8 ms of a
 // 9.9 ms batch on the 70 k-triangle scene, 2.4 of 13.3 ms on the 1 M-triangle one, most of it this end phase).
-template <bool COUNT, bool ANYHIT, bool GEN, int WIDE, int SMP, bool LIGHTS = false>
+template <bool COUNT, bool ANYHIT, bool GEN, int WIDE, int SMP, bool LIGHTS = false, bool LIST = false>
 __global__ __launch_bounds__(BLOCK_THREADS, LIGHTS ? WF_LIGHTS_WAVES : WF_TAIL_WAVES) void k_wf_tail(const WfP p) {
   extern __shared__ int lds_stack[];
   const int lane = threadIdx.x & (WAVE - 1);
@@ -2193,7 +2202,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, LIGHTS ? WF_LIGHTS_WAVES : WF_TAIL_W
         if (is_main && ps.pix < 0 && g_w < 0 && rank < take) {
           uint32_t fx = 0, fy = 0;
           const uint32_t w = gen_next + rank;
-          if (work_to_pixel(p, w, fx, fy)) { // (a pixel outside the viewport does not exist)
+          if (work_to_pixel<LIST>(p, w, fx, fy)) { // (a pixel outside the viewport does not exist)
             g_w = (int)w;
             g_j = 0;
             g_pix = fy * p.W + fx;
@@ -2376,7 +2385,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_tile_pack(const TilePackP p) 
   const uint32_t n = p.n_owned_tiles * p.tile * p.tile;
   for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < n; w += gridDim.x * blockDim.x) {
     uint32_t x, y;
-    if (!work_to_pixel(p, w, x, y)) continue;
+    if (!work_to_pixel<false>(p, w, x, y)) continue; // (no tile list here)
     if (p.channels == 3u) {
       float *q = reinterpret_cast<float *>(p.packed) + 3 * (size_t)w;
       if (UNPACK) { const V3 c = ld3(q); p.accum[(size_t)y * p.W + x] = make_float4(c.x, c.y, c.z, 1.0f); }
@@ -2657,6 +2666,80 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_atrous(const AtrousP p) {
   p.dst[ip] = o;
 }
 
+// ---- adaptive sampling (fspt_render_adaptive) -------------------------------------------------------------
+// One workgroup per active tile (list order).  Every thread sums its pixels (j = thread, thread + 256, ... of the tile,
+// row-major) in float64, the wave folds its 64 sums by shuffles and the four wave sums are added in wave order: the same
+// bits on every run.  E_T = sum over the tile's viewport pixels and 3 channels of r / (3 pixels), with
+// r = v / (I^2 + 0.01) and v = (B - S)^2 m (n - m) / n^2 = m (I - S)^2 / (n - m)  (B = (n I - m S) / (n - m)).
+// m = 0: no estimate, only S := I;  refresh: S := I as well (read once, written in the same pass).
+__global__ __launch_bounds__(BLOCK_THREADS) void k_adaptive_error(const AdaptiveP p) {
+  __shared__ double wsum[BLOCK_THREADS / WAVE];
+  const uint32_t g = p.list_in[blockIdx.x];
+  const uint32_t x0 = (g % p.tiles_x) * p.tile, y0 = (g / p.tiles_x) * p.tile;
+  const uint32_t wx = min(p.tile, p.vw - x0), wy = min(p.tile, p.vh - y0); // (listed tiles meet the viewport)
+  const bool est = p.m != 0u, store = p.refresh != 0u || !est;
+  const double scale = est ? (double)p.m / (double)(p.n - p.m) : 0.0;
+  double acc = 0.0;
+  for (uint32_t j = threadIdx.x; j < wx * wy; j += BLOCK_THREADS) {
+    const uint32_t y = y0 + j / wx, x = x0 + j % wx;
+    const size_t i = (size_t)y * p.W + x;
+    const float4 I = p.accum[i];
+    if (est) {
+      const float4 S = p.snap[i];
+      const double c[3] = {(double)I.x, (double)I.y, (double)I.z}, d[3] = {(double)I.x - (double)S.x, (double)I.y - (double)S.y,
+                                                                          (double)I.z - (double)S.z};
+#pragma unroll
+      for (int k = 0; k < 3; ++k) acc += (scale * (d[k] * d[k])) / (c[k] * c[k] + 0.01);
+    }
+    if (store) p.snap[i] = I;
+  }
+  if (!est) return;
+  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+  for (int off = WAVE / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off, WAVE);
+  if (lane == 0) wsum[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int w = 0; w < BLOCK_THREADS / WAVE; ++w) t += wsum[w];
+    p.err[g] = t / (3.0 * (double)(wx * wy));
+  }
+}
+
+// One workgroup of ADAPTIVE_SELECT_THREADS walks list_in in chunks: a tile retires when n = max_ticks or (n >= min_ticks
+// and E_T < target) - count[g] = n, err[g] keeps the E_T that retired it - and every other tile goes to list_out at its
+// rank among the kept ones (ballot + mbcnt inside a wave, the wave totals from LDS in wave order): ascending order, no
+// atomics.  *n_out = the kept tiles.
+#define ADAPTIVE_SELECT_THREADS 1024
+__global__ __launch_bounds__(ADAPTIVE_SELECT_THREADS) void k_adaptive_select(const AdaptiveP p) {
+  __shared__ uint32_t wcount[ADAPTIVE_SELECT_THREADS / WAVE];
+  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+  uint32_t base_out = 0;
+  for (uint32_t base = 0; base < p.n_in; base += ADAPTIVE_SELECT_THREADS) {
+    const uint32_t i = base + threadIdx.x;
+    bool keep = false;
+    uint32_t g = 0;
+    if (i < p.n_in) {
+      g = p.list_in[i];
+      const bool retire = p.n >= p.max_ticks || (p.n >= p.min_ticks && p.err[g] < p.target);
+      if (retire) p.count[g] = p.n;
+      keep = !retire;
+    }
+    const unsigned long long mask = __ballot(keep);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    if (lane == 0) wcount[wave] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+    for (int w = 0; w < ADAPTIVE_SELECT_THREADS / WAVE; ++w) {
+      if (w < wave) before += wcount[w];
+      total += wcount[w];
+    }
+    if (keep) p.list_out[base_out + before + rank] = g;
+    base_out += total;
+    __syncthreads(); // (wcount is rewritten by the next chunk)
+  }
+  if (threadIdx.x == 0) *p.n_out = base_out;
+}
+
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
@@ -2818,7 +2901,9 @@ hipError_t launch_wf(int kernel, const WfP &p, int count, int num_cus, hipStream
     e = with_form(count, wide ? (p.tail_adaptive ? 2 : 1) : 0, [&](auto C, auto A, auto Wd) {
       return with_flag(p.ctl && p.finish, [&](auto G) {
         return with_shading(p, [&](auto M, auto L) {
-          return launch(k_wf_tail<C, A, G, Wd, M, L>, dim3(grid), dim3(BLOCK_THREADS), lds, stream, p);
+          return with_flag(p.tile_list != nullptr, [&](auto LS) {
+            return launch(k_wf_tail<C, A, G, Wd, M, L, LS>, dim3(grid), dim3(BLOCK_THREADS), lds, stream, p);
+          });
         });
       });
     });
@@ -2840,7 +2925,9 @@ hipError_t launch_wf(int kernel, const WfP &p, int count, int num_cus, hipStream
         return with_flag(tab, [&](auto T) {
           return with_flag(prim_r > 1u, [&](auto R2) {
             return with_shading(p, [&](auto M, auto L) {
-              return launch(k_wf_primary<C, T, (R2 ? 2 : 1), (Wd != 0), M, L>, dim3(grid), dim3(WF_PRIMARY_THREADS), dyn, stream, p);
+              return with_flag(p.tile_list != nullptr, [&](auto LS) {
+                return launch(k_wf_primary<C, T, (R2 ? 2 : 1), (Wd != 0), M, L, LS>, dim3(grid), dim3(WF_PRIMARY_THREADS), dyn, stream, p);
+              });
             });
           });
         });
@@ -2944,6 +3031,17 @@ hipError_t launch_features(const FeatureP &p, hipStream_t stream) {
 
 hipError_t launch_atrous(const AtrousP &p, hipStream_t stream) {
   hipLaunchKernelGGL(k_atrous, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), 0, stream, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_adaptive_error(const AdaptiveP &p, hipStream_t stream) {
+  if (p.n_in == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_adaptive_error, dim3(p.n_in), dim3(BLOCK_THREADS), 0, stream, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_adaptive_select(const AdaptiveP &p, hipStream_t stream) {
+  hipLaunchKernelGGL(k_adaptive_select, dim3(1), dim3(ADAPTIVE_SELECT_THREADS), 0, stream, p);
   return hipGetLastError();
 }
 

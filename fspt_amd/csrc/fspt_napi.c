@@ -738,6 +738,32 @@ static napi_value SetLights(napi_env env, napi_callback_info info) {
   FSPT_OK_OR_THROW(fspt_target_set_lights((fspt_target *)h, mode, (float)f));
   return undefined(env);
 }
+/* renderAdaptive(target, params, targetRelMse, maxTicks, minTicks, roundTicks, seed) -> the largest count run:
+ * fspt_render_adaptive (include/fspt.h) */
+static napi_value RenderAdaptive(napi_env env, napi_callback_info info) {
+  napi_value a[7], r; void *h; fspt_camera_params cp; fspt_adaptive_params q; uint64_t seed64 = 0; uint32_t rounds = 0;
+  if (get_args(env, info, 7, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  if (parse_camera_params(env, a[1], &cp)) return NULL;
+  NAPI_OK(napi_get_value_double(env, a[2], &q.target_rel_mse));
+  NAPI_OK(napi_get_value_uint32(env, a[3], &q.max_ticks));
+  NAPI_OK(napi_get_value_uint32(env, a[4], &q.min_ticks));
+  NAPI_OK(napi_get_value_uint32(env, a[5], &q.round_ticks));
+  if (parse_seed(env, a[6], &seed64)) return NULL;
+  FSPT_OK_OR_THROW(fspt_render_adaptive((fspt_target *)h, &cp, &q, seed64));
+  FSPT_OK_OR_THROW(fspt_adaptive_last_stats((fspt_target *)h, &rounds, NULL, NULL, NULL, 0));
+  NAPI_OK(napi_create_uint32(env, rounds * q.round_ticks, &r));
+  return r;
+}
+/* readSampleCounts(target, Uint32Array(W*H)): fspt_read_sample_counts */
+static napi_value ReadSampleCounts(napi_env env, napi_callback_info info) {
+  napi_value a[2]; void *h, *p; size_t n; uint32_t W, H;
+  if (get_args(env, info, 2, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  if (typed(env, a[1], napi_uint32_array, 0, &p, &n)) return NULL;
+  FSPT_OK_OR_THROW(fspt_target_size((fspt_target *)h, &W, &H));
+  if (n != (size_t)W * H) { napi_throw_range_error(env, NULL, "readSampleCounts: the array must hold W*H counts"); return NULL; }
+  FSPT_OK_OR_THROW(fspt_read_sample_counts((fspt_target *)h, (uint32_t *)p));
+  return a[1];
+}
 static napi_value SetShard(napi_env env, napi_callback_info info) {
   napi_value a[4]; void *h; uint32_t s, n, tile;
   if (get_args(env, info, 4, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
@@ -1102,7 +1128,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
       {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
-      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
+      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},
       {"renderAsync", RenderAsync}, {"multiCreate", MultiCreate}, {"multiDestroy", MultiDestroy}, {"multiTarget", MultiTarget},
       {"multiCamera", MultiCamera}, {"multiTrace", MultiTrace}, {"multiRender", MultiRender}, {"multiRenderAsync", MultiRenderAsync},

@@ -16,6 +16,8 @@ void fill_trace_params(fspt_target *t, fspt::TraceP &p) {
   p.tiles_y = (t->H + t->tile - 1) / t->tile;
   uint32_t n_tiles = p.tiles_x * p.tiles_y;
   p.n_owned_tiles = (n_tiles > t->shard) ? (n_tiles - t->shard + t->n_shards - 1) / t->n_shards : 0;
+  p.tile_list = t->tile_list; // (fspt_render_adaptive's rounds: only the listed tiles)
+  if (p.tile_list) p.n_owned_tiles = t->n_listed;
   p.sampler = (uint32_t)t->sampler;
   p.smp_seed = t->sampler_seed;
   // the emitter instantiations only where there is an emitter to sample (a scene without one: the default kernels, same bits)
@@ -396,7 +398,7 @@ static int wf_run(fspt_target *t, fspt_target::WfLane &ln, hipStream_t st, bool 
   p.accum = t->accum;
   p.counters = t->count ? t->counters : nullptr;
   p.shard = tp.shard; p.n_shards = tp.n_shards; p.tile = tp.tile; p.tiles_x = tp.tiles_x; p.tiles_y = tp.tiles_y;
-  p.n_owned_tiles = tp.n_owned_tiles;
+  p.n_owned_tiles = tp.n_owned_tiles; p.tile_list = tp.tile_list;
   p.sampler = tp.sampler; p.smp_seed = tp.smp_seed;
   p.lights = tp.lights; p.light_q = tp.light_q;
   const int cus = t->scene->num_cus;

@@ -119,7 +119,7 @@ int render_stream(fspt_target *t, const fspt_camera_params *cam, uint32_t first_
   base.accum = t->accum;
   base.counters = t->count ? t->counters : nullptr;
   base.shard = tp.shard; base.n_shards = tp.n_shards; base.tile = tp.tile; base.tiles_x = tp.tiles_x; base.tiles_y = tp.tiles_y;
-  base.n_owned_tiles = tp.n_owned_tiles;
+  base.n_owned_tiles = tp.n_owned_tiles; base.tile_list = tp.tile_list;
   base.sampler = tp.sampler; base.smp_seed = tp.smp_seed;
   base.lights = tp.lights; base.light_q = tp.light_q;
   base.gen_rays = rays_from_buffers ? 0u : 1u;

@@ -353,6 +353,29 @@ class PathTracer {
     return p;
   }
   clear() { addon.clear(this._target); this.pingpong = 0; }                                  // main.js:826-836
+  /** Adaptive sampling (include/fspt.h fspt_render_adaptive, DESIGN 8.5): clear, then rounds of roundTicks ticks over the
+   *  32x32 tiles whose estimated relative MSE is still >= targetRelMse, each at least minTicks and at most maxTicks ticks.
+   *  Returns the largest count run; pingpong and the randBase stream then stand where render(that count) leaves them. */
+  renderAdaptive(opts) {
+    const o = opts || {};
+    const t = o.targetRelMse, maxT = o.maxTicks === undefined ? 1024 : o.maxTicks;
+    const minT = o.minTicks === undefined ? 64 : o.minTicks, r = o.roundTicks === undefined ? 32 : o.roundTicks;
+    if (typeof t !== 'number' || !Number.isFinite(t) || t < 0) throw new RangeError('renderAdaptive: targetRelMse must be a finite number >= 0');
+    for (const [name, v] of [['maxTicks', maxT], ['minTicks', minT], ['roundTicks', r]]) {
+      if (!Number.isInteger(v) || v < 0 || v > 0xFFFFFFFF) throw new RangeError(`renderAdaptive: ${name} must be an integer in [0, 2^32)`);
+    }
+    const n = addon.renderAdaptive(this._target, { P: this.eye, I: this.dir, fovScale: this.fovScale, lens: this.lensFeatures,
+      envTheta: this.envTheta, numBounces: this.numBounces }, t, maxT, minT, r, this._rng[0]);
+    for (let k = 0; k < 2 * n; k++) this._randBase();
+    this.pingpong = n;
+    return n;
+  }
+  /** the last renderAdaptive()'s ticks per pixel: Uint32Array(W*H), rows bottom-up, 0 outside its viewport */
+  readSampleCounts(out) {
+    out = out || new Uint32Array(this.resolution[0] * this.resolution[1]);
+    if (!(out instanceof Uint32Array) || out.length !== this.resolution[0] * this.resolution[1]) throw new RangeError('readSampleCounts: need a Uint32Array of W*H counts');
+    return addon.readSampleCounts(this._target, out);
+  }
   /** wait until every enqueued (and recorded) tick is on the accumulator (gl.finish) */
   sync() { addon.sync(this._target); }
   readRadiance(out) {

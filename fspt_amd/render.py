@@ -46,7 +46,19 @@ def main():
     ap.add_argument("--lights", action="store_true", help="next-event estimation of emissive triangles (fspt_target_set_lights)")
     ap.add_argument("--emitter-fraction", type=float, default=0.5,
                     help="with --lights: probability a vertex samples an emitter rather than the environment, in (0, 1]")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="REL_MSE",
+                    help="adaptive sampling: stop a 32x32 tile once its estimated relative MSE is below REL_MSE (--spp = the most)")
+    ap.add_argument("--sample-map", default=None, help="with --adaptive: write the ticks per pixel as a grey PNG")
     args = ap.parse_args()
+    if args.adaptive is not None:
+        if not (np.isfinite(args.adaptive) and args.adaptive >= 0.0):
+            ap.error("--adaptive must be a finite relative MSE >= 0")
+        if args.spp < 64 or args.spp % 32:
+            ap.error("--adaptive needs --spp a multiple of 32, at least 64")
+        if args.frames:
+            ap.error("--adaptive renders a single frame")
+    if args.sample_map and args.adaptive is None:
+        ap.error("--sample-map needs --adaptive")
     if not 0.0 < args.emitter_fraction <= 1.0:
         ap.error("--emitter-fraction must lie in (0, 1]")
     if args.emitter_fraction != 0.5 and not args.lights:
@@ -63,6 +75,8 @@ def main():
         kw = dict(samples=spp, bounces=args.bounces, seed=args.seed, saturation=args.saturation, denoise=args.denoise)
         if args.lights:
             kw.update(lights="emitters", emitter_fraction=args.emitter_fraction)
+        if args.adaptive is not None:
+            kw.update(samples=args.spp, adaptive=args.adaptive, sample_map=args.sample_map)
         if args.frames:
             a, b = (int(x) for x in args.frames.split(":"))
             t0 = time.perf_counter()
@@ -89,16 +103,27 @@ def main():
     if args.lights:
         pt.set_lights("emitters", args.emitter_fraction)
     t0 = time.perf_counter()
-    pt.render(args.spp)
+    if args.adaptive is None:
+        pt.render(args.spp)
+    else:
+        pt.render_adaptive(args.adaptive, max_ticks=args.spp)
     pt.sync()
     dt = time.perf_counter() - t0
+    samples = args.width * args.height * args.spp
+    if args.adaptive is not None:
+        samples = pt.adaptive_stats()["samples"]
+        print(f"adaptive: {samples / (args.width * args.height):.1f} spp on average (at most {args.spp})")
+        if args.sample_map:
+            from .scene_file import write_sample_map
+            write_sample_map(args.sample_map, pt.sample_counts(), args.spp)
+            print("wrote", args.sample_map)
     if args.atrous > 0:
         pt.features(args.feature_samples, args.seed)
         pt.denoise(iterations=args.atrous)
         rgba = pt.drawDenoised(args.exposure, args.saturation)
     else:
         rgba = pt.draw(args.exposure, args.saturation, args.denoise)
-    print(f"{args.width}x{args.height} x {args.spp} spp in {dt:.3f} s = {args.width * args.height * args.spp / dt / 1e6:.0f} Msamples/s")
+    print(f"{args.width}x{args.height} x {args.spp} spp in {dt:.3f} s = {samples / dt / 1e6:.0f} Msamples/s")
     if args.hdr:
         np.save(args.hdr, pt.readRadiance())
     from PIL import Image

@@ -89,11 +89,13 @@ def load_scene_file(scene_path, asset_root=None, leaf_size=4, bvh="sah", device=
 
 
 def render_frame(arrays, settings, width, height, samples=None, bounces=4, seed=1, saturation=1.0, denoise=False,
-                 max_sigma=3.0, device=0, lights=None, emitter_fraction=0.5):
+                 max_sigma=3.0, device=0, lights=None, emitter_fraction=0.5, adaptive=None, sample_map=None):
     """One frame as the reference produces it in frame mode: `samples` ticks from a cleared accumulator
     (main.js:838-857; its very first, discarded tick is not reproduced), then drawQuad.  Returns
     (rgba8 [H, W, 4] top row first - what canvas.toBlob encodes -, radiance [H, W, 4] bottom row first).
-    lights="emitters": next-event estimation of emissive triangles (PathTracer.set_lights)."""
+    lights="emitters": next-event estimation of emissive triangles (PathTracer.set_lights).  adaptive=REL_MSE:
+    adaptive sampling with `samples` as the most ticks a tile gets (PathTracer.render_adaptive); sample_map:
+    then also write its ticks per pixel as a grey PNG there (white = `samples`)."""
     from .tracer import PathTracer
     pt = PathTracer(arrays, width, height, device=device, num_bounces=bounces)
     try:
@@ -103,13 +105,27 @@ def render_frame(arrays, settings, width, height, samples=None, bounces=4, seed=
         if lights is not None:
             pt.set_lights(lights, emitter_fraction)
         pt.seed(seed)
-        pt.render(int(samples if samples is not None else settings["samples"]))
+        n = int(samples if samples is not None else settings["samples"])
+        if adaptive is None:
+            pt.render(n)
+        else:
+            pt.render_adaptive(adaptive, max_ticks=n)
+            if sample_map:
+                write_sample_map(sample_map, pt.sample_counts(), n)
         rgba = pt.draw(settings["exposure"], saturation, denoise, max_sigma)
         rad = pt.readRadiance()
     finally:
         pt.close()
         pt.scene.close()
     return rgba[::-1].copy(), rad
+
+
+def write_sample_map(path, counts, max_ticks):
+    """Ticks per pixel (PathTracer.sample_counts(), rows bottom-up) as an 8-bit grey PNG, top row first: 255 = max_ticks."""
+    import numpy as np
+    from PIL import Image
+    grey = np.round(counts[::-1].astype(np.float64) * (255.0 / max(int(max_ticks), 1))).clip(0, 255).astype(np.uint8)
+    Image.fromarray(grey, mode="L").save(path)
 
 
 def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", **kw):

@@ -191,6 +191,7 @@ class PathTracer:
         self.pingpong = 0
         self._rng = C.c_uint64(1)
         self._keep = None
+        self._tile = 32  # set_shard's tile (adaptive_stats)
 
     # ---- configuration -----------------------------------------------------
     def set_camera(self, P, I, fov_scale=0.5, env_theta=0.0, focal_depth=2.0, aperture=0.02, **_):
@@ -211,6 +212,7 @@ class PathTracer:
 
     def set_shard(self, shard, n_shards, tile=32):
         L.check(L.lib().fspt_target_set_shard(self._t, shard, n_shards, tile))
+        self._tile = int(tile)
 
     def set_viewport(self, w=0, h=0):
         """gl.viewport(0, 0, w, h) of drawCamera / drawTracer (main.js:744,761); 0, 0 = the whole target.  The
@@ -379,6 +381,56 @@ class PathTracer:
         for _ in range(2 * int(n_ticks)):  # advance the host stream like the kernel did
             self.next_rand_base()
         self.pingpong += int(n_ticks)
+
+    def _camera_params(self):
+        cp = L.CameraParams()
+        cp.P = (C.c_float * 3)(*self.eye); cp.I = (C.c_float * 3)(*self.dir)
+        cp.fov_scale = self.fovScale; cp.lens = (C.c_float * 2)(*self.lensFeatures)
+        cp.env_theta = self.envTheta; cp.num_bounces = self.num_bounces
+        return cp
+
+    def render_adaptive(self, target_rel_mse, max_ticks=1024, min_ticks=64, round_ticks=32):
+        """Adaptive sampling (fspt_render_adaptive): clear, then rounds of round_ticks ticks over the tiles whose
+        estimated relative MSE is still >= target_rel_mse (each tile at least min_ticks, at most max_ticks ticks).  A tile
+        retired after n ticks holds render(n)'s pixels of a cleared tracer bit for bit.  Returns the largest count run;
+        pingpong and the host randBase stream then stand where render(that count) after clear() leaves them."""
+        for name, v in (("max_ticks", max_ticks), ("min_ticks", min_ticks), ("round_ticks", round_ticks)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"render_adaptive: {name} must be an int")
+            if not 0 <= int(v) < 2 ** 32:
+                raise ValueError(f"render_adaptive: {name} out of range")
+        if isinstance(target_rel_mse, bool) or not isinstance(target_rel_mse, (int, float, np.floating, np.integer)):
+            raise TypeError("render_adaptive: target_rel_mse must be a number")
+        if not (np.isfinite(target_rel_mse) and target_rel_mse >= 0):
+            raise ValueError("render_adaptive: target_rel_mse must be finite and >= 0")
+        prm = L.AdaptiveParams(float(target_rel_mse), int(max_ticks), int(min_ticks), int(round_ticks))
+        L.check(L.lib().fspt_render_adaptive(self._t, C.byref(self._camera_params()), C.byref(prm), self._rng.value))
+        rounds = C.c_uint32()
+        L.check(L.lib().fspt_adaptive_last_stats(self._t, C.byref(rounds), None, None, None, 0))
+        n = int(rounds.value) * int(round_ticks)
+        for _ in range(2 * n):  # the host stream advances like fspt_render's for the largest count
+            self.next_rand_base()
+        self.pingpong = n
+        return n
+
+    def sample_counts(self):
+        """The last render_adaptive()'s ticks per pixel: uint32 [H, W], row 0 = bottom, 0 outside its viewport."""
+        W, H = self.resolution
+        out = np.zeros((H, W), np.uint32)
+        L.check(L.lib().fspt_read_sample_counts(self._t, L.u32ptr(out)))
+        return out
+
+    def adaptive_stats(self):
+        """The last render_adaptive(): {"rounds", "samples", "tile_ticks" [tiles_y, tiles_x] uint32, "tile_err" (the E_T that
+        retired each tile) float64}, tiles row-major from the bottom row (fspt_adaptive_last_stats)."""
+        W, H = self.resolution
+        tile = self._tile
+        tx, ty = (W + tile - 1) // tile, (H + tile - 1) // tile
+        rounds, samples = C.c_uint32(), C.c_uint64()
+        ticks = np.zeros((ty, tx), np.uint32); err = np.zeros((ty, tx), np.float64)
+        L.check(L.lib().fspt_adaptive_last_stats(self._t, C.byref(rounds), C.byref(samples), err.ctypes.data_as(C.POINTER(C.c_double)),
+                                                 L.u32ptr(ticks), tx * ty))
+        return {"rounds": int(rounds.value), "samples": int(samples.value), "tile_ticks": ticks, "tile_err": err}
 
     def clear(self):
         L.check(L.lib().fspt_clear(self._t))

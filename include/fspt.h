@@ -93,11 +93,9 @@ int fspt_scene_depth(const fspt_scene *scene, uint32_t *depth);
  * Sharding (SURVEY 8e): tile x tile pixel tiles dealt round-robin (tile index % n_shards == shard); a target traces
  * only its own tiles and leaves every other pixel of its full-size accumulator at zero (a sum over shards = the frame).
  * ---------------------------------------------------------------------- */
-int fspt_target_create(fspt_scene *scene, uint32_t width, uint32_t height,
-                       fspt_target **out);
+int fspt_target_create(fspt_scene *scene, uint32_t width, uint32_t height, fspt_target **out);
 int fspt_target_destroy(fspt_target *target);
-int fspt_target_set_shard(fspt_target *target, uint32_t shard, uint32_t n_shards,
-                          uint32_t tile);
+int fspt_target_set_shard(fspt_target *target, uint32_t shard, uint32_t n_shards, uint32_t tile);
 /* Use caller-owned device memory (W*H*4 floats, e.g. a torch tensor) as the accumulator so that a collective can run
  * on it in place; NULL restores the library's own buffer.  The bound buffer is only current after fspt_sync,
  * fspt_read_radiance or fspt_draw (recorded ticks, the library's own streams); re-binding flushes the recorded ticks
@@ -114,8 +112,7 @@ int fspt_target_accumulator(fspt_target *target, void **device_ptr);
  * observes or changes what they depend on (fspt_read_*, fspt_draw, fspt_sync, fspt_clear, fspt_get_counters, every
  * setter, fspt_render, fspt_set_rays) or when a batch of them has accumulated.  Results are bit-identical; an error of
  * a deferred tick is reported by the call that flushes it.  (fspt_tuning.h: fspt_target_set_deferred.) */
-int fspt_camera(fspt_target *target, const float P[3], const float I[3],
-                float fov_scale, const float lens[2], float rand_base);
+int fspt_camera(fspt_target *target, const float P[3], const float I[3], float fov_scale, const float lens[2], float rand_base);
 /* Inject ray buffers instead (W*H*4 floats each, rows bottom-up; traced at once, from the buffers). */
 int fspt_set_rays(fspt_target *target, const float *pos, const float *dir);
 int fspt_read_rays(fspt_target *target, float *pos, float *dir);
@@ -124,8 +121,7 @@ int fspt_read_rays(fspt_target *target, float *pos, float *dir);
  * pixel from the current ray buffers, running-mean accumulate with weight
  * tick.  num_bounces is tracer.fs:9's compile-time NUM_BOUNCES made a
  * run-time argument (reference value 4).                                     */
-int fspt_trace(fspt_target *target, uint32_t tick, float rand_base,
-               float env_theta, uint32_t num_bounces);
+int fspt_trace(fspt_target *target, uint32_t tick, float rand_base, float env_theta, uint32_t num_bounces);
 /* Refraction does not advance the bounce counter (tracer.fs:488 `i--`: the reference's loop is unbounded); libfspt
  * ends every path after FSPT_MAX_BOUNCES loop iterations, and treats a larger num_bounces as that. */
 #define FSPT_MAX_BOUNCES 64
@@ -145,8 +141,7 @@ typedef struct fspt_camera_params {
   float env_theta;
   uint32_t num_bounces;
 } fspt_camera_params;
-int fspt_render(fspt_target *target, const fspt_camera_params *cam,
-                uint32_t first_tick, uint32_t n_ticks, uint64_t seed);
+int fspt_render(fspt_target *target, const fspt_camera_params *cam, uint32_t first_tick, uint32_t n_ticks, uint64_t seed);
 /* The host PRNG of fspt_render: state' = xorshift64*(state); returns float(u >> 40) * 2^-24 * 10000 in [0, 10000). */
 float fspt_rand_base_next(uint64_t *state);
 
@@ -160,8 +155,19 @@ enum { FSPT_LIGHTS_OFF = 0, FSPT_LIGHTS_EMITTERS = 1 }; /* NEE of emissive trian
  * lists "Tiled rendering" as a TODO): include/fspt_multi.h, included at the end of this file. */
 
 /* clear() (main.js:826-836). */
-int fspt_clear(fspt_target *target);
-int fspt_sync(fspt_target *target);
+int fspt_clear(fspt_target *target); int fspt_sync(fspt_target *target);
+/* Adaptive sampling (DESIGN 8.5): fspt_clear, then ticks 0, 1, ... in rounds of round_ticks (fspt_render's randBase
+ * stream from `seed`) over the ACTIVE tiles (tile x tile pixels meeting the viewport; all at first).  S = the means after
+ * m ticks (m = round_ticks, then n whenever n >= 2m); after n > m ticks a tile's E_T = mean over its pixels and channels
+ * of m (I - S)^2 / ((n - m)(I^2 + 0.01)); it retires with count n when n >= min_ticks and E_T < target_rel_mse, or at
+ * n = max_ticks.  A tile retired after n ticks holds fspt_render(t, cam, 0, n, seed)'s pixels bit for bit; target 0
+ * = fspt_render(max_ticks).  Afterwards the target is as fspt_render leaves it for the largest count run (rounds x
+ * round_ticks, fspt_adaptive_last_stats).  Ranges: round_ticks in [2, 128], min_ticks a multiple >= 2 round_ticks,
+ * max_ticks a multiple >= min_ticks, target finite >= 0 (else FSPT_E_INVALID); sharded target: FSPT_E_STATE. */
+typedef struct fspt_adaptive_params { double target_rel_mse; uint32_t max_ticks, min_ticks, round_ticks; } fspt_adaptive_params;
+int fspt_render_adaptive(fspt_target *target, const fspt_camera_params *cam, const fspt_adaptive_params *params, uint64_t seed);
+/* The last fspt_render_adaptive's ticks per pixel: W*H counts, rows bottom-up, 0 outside its viewport (FSPT_E_STATE before one). */
+int fspt_read_sample_counts(fspt_target *target, uint32_t *out);
 /* What draw.fs:87 reads: RGBA32F, W*H*4 floats, row 0 = bottom, a = 1.
  * Blocking (syncs the stream first). */
 int fspt_read_radiance(fspt_target *target, float *out);
@@ -169,19 +175,16 @@ int fspt_read_radiance(fspt_target *target, float *out);
 /* drawQuad (main.js:809-824) -> draw.fs:82-93: exposure, ACES fit, saturation, gamma 1/2.2 and the
  * optional 5x5 firefly filter (draw.fs:52-80, max_sigma = the `sigma` slider) on the current
  * accumulator; writes what the canvas would hold: RGBA8, W*H*4 bytes, row 0 = bottom.  Blocking. */
-int fspt_draw(fspt_target *target, float exposure, float saturation, int denoise, float max_sigma,
-              uint8_t *out_rgba8);
+int fspt_draw(fspt_target *target, float exposure, float saturation, int denoise, float max_sigma, uint8_t *out_rgba8);
 /* The same with draw.fs's `scale` uniform (draw.fs:59,87: texel = ivec2(gl_FragCoord * scale)); the reference
  * draws with scale 0.25 while the camera is being dragged (main.js:819,840), 1.0 otherwise. */
-int fspt_draw_scaled(fspt_target *target, float exposure, float saturation, int denoise,
-                     float max_sigma, float scale, uint8_t *out_rgba8);
+int fspt_draw_scaled(fspt_target *target, float exposure, float saturation, int denoise, float max_sigma, float scale, uint8_t *out_rgba8);
 /* drawQuad inside tick() (main.js:838-857), pipelined with one frame of latency: enqueues the ticks
  * recorded since the last flush and fspt_draw_scaled's k_draw of the result, then writes the frame the PREVIOUS call
  * enqueued to out_rgba8 and its sample count (1 + its newest tick index) to *ticks_out, blocking only for that frame.
  * *ticks_out = 0: nothing to present (first call after a join; out untouched).  Every entry but fspt_camera and
  * fspt_trace joins. */
-int fspt_present(fspt_target *t, float exposure, float saturation, int denoise, float max_sigma, float scale,
-                 uint8_t *out_rgba8, uint32_t *ticks_out);
+int fspt_present(fspt_target *t, float exposure, float saturation, int denoise, float max_sigma, float scale, uint8_t *out_rgba8, uint32_t *ticks_out);
 
 /* Guided denoiser (DESIGN.md 8; the reference lists "denoising" under post processing).  fspt_features: `samples` camera
  * rays per pixel of the whole target (k_camera's ray for randBase r_s, the s-th fspt_rand_base_next value from `seed`) to
@@ -205,8 +208,7 @@ int fspt_draw_denoised(fspt_target *t, float exposure, float saturation, uint8_t
 
 /* intersectScene (tracer.fs:366-404) as a stand-alone entry: n rays (origin xyz, dir xyz) -> closest hit t and
  * triangle index (-1 = miss, t = 1e5), optionally loop-iteration and leaf-visit counts per ray.  Host pointers. */
-int fspt_intersect(fspt_scene *scene, const float *rays, uint32_t n, float *t_out,
-                   int32_t *index_out, uint32_t *steps_out, uint32_t *leaves_out);
+int fspt_intersect(fspt_scene *scene, const float *rays, uint32_t n, float *t_out, int32_t *index_out, uint32_t *steps_out, uint32_t *leaves_out);
 
 /* Work counters for the byte accounting of SURVEY 8d, summed since the last fspt_clear / fspt_counters_reset while
  * counting is enabled (slower kernel variants).  enable = 1 counts the REFERENCE's work (NEE shadow rays traced to
@@ -268,8 +270,7 @@ int fspt_builder_add_obj(fspt_builder *b, const char *obj_text, size_t len, cons
 int fspt_builder_parse_obj(fspt_builder *b, const char *obj_text, size_t len, const fspt_prop_desc *prop,
                            const fspt_world_transform *world, uint32_t n_world,
                            const char *const *skips, uint32_t n_skips, uint32_t *n_groups);
-int fspt_builder_group_info(const fspt_builder *b, uint32_t group, const char **name,
-                            uint32_t *n_tris, int32_t *mtllib);
+int fspt_builder_group_info(const fspt_builder *b, uint32_t group, const char **name, uint32_t *n_tris, int32_t *mtllib);
 int fspt_builder_mtllib_name(const fspt_builder *b, uint32_t index, const char **name);
 int fspt_builder_commit_obj(fspt_builder *b, const fspt_group_material *mats, uint32_t n_groups);
 /* scene.normalize (main.js:337-348): centre on the scene bounds and scale the longest side to 2*size. */
@@ -284,8 +285,7 @@ int fspt_builder_autofocus(const fspt_builder *b, const double eye[3], const dou
 int fspt_builder_get(const fspt_builder *b, float *bvh, float *tri, float *mat, float *norm, float *uv);
 /* ProcessEnvRadiance (env_sampler.js:1-74) on raw RGBE bytes.  Writes up to
  * cap bins (4 uint32 each) and the real count to *n_bins. */
-int fspt_env_bins(const uint8_t *rgbe, uint32_t w, uint32_t h, uint32_t *bins,
-                  uint32_t cap, uint32_t *n_bins);
+int fspt_env_bins(const uint8_t *rgbe, uint32_t w, uint32_t h, uint32_t *bins, uint32_t cap, uint32_t *n_bins);
 
 const char *fspt_last_error(void);
 int fspt_abi_version(void);

@@ -89,6 +89,10 @@ int fspt_target_prepare(fspt_target *target);
 /* Live paths after wavefront round r (r = 1: the primary launch) as a fraction of the batch's samples, from the most
  * recent batch: frac[r] for r < n_rounds (frac[0] unused).  Blocking. */
 int fspt_target_live_paths(fspt_target *target, double *frac, uint32_t n_rounds);
+/* The last fspt_render_adaptive (FSPT_E_STATE before one): its rounds, the samples it traced (sum over tiles of count x
+ * viewport pixels), and per tile (row-major, tiles_x = ceil(W / 32) by default) the count and the E_T that retired it (0, 0
+ * for a tile outside the viewport).  The arrays may be NULL; otherwise they hold `cap` >= the tile count entries. */
+int fspt_adaptive_last_stats(fspt_target *target, uint32_t *rounds, uint64_t *samples, double *tile_err, uint32_t *tile_ticks, uint32_t cap);
 /* Memory fspt_scene_create may spend on INTERLEAVED material textures (process-wide; scenes created afterwards;
  * default 8 GiB): a material that samples two or more image layers at one uv (tracer.fs:453-456) gets one image with
  * 16-byte texels, so that a shading event's 16 taps lie in ~2 cache lines instead of ~6; materials beyond the budget

@@ -1,0 +1,23 @@
+'use strict';
+// Driven by tests/test_adaptive_gpu.py: node adaptive_node_check.js <dir with fspt.js> <job dir>
+// The JS host's renderAdaptive() on the scene arrays the test wrote; radiance, counts and the count run go to the job dir.
+const fs = require('fs');
+const path = require('path');
+const F = require(path.join(process.argv[2], 'fspt.js'));
+const dir = process.argv[3];
+const job = JSON.parse(fs.readFileSync(path.join(dir, 'meta.json'), 'utf8'));
+const rd = (name, T) => { const b = fs.readFileSync(path.join(dir, name + '.bin')); return new T(b.buffer, b.byteOffset, b.byteLength / T.BYTES_PER_ELEMENT); };
+const desc = { bvh: rd('bvh', Float32Array), tri: rd('tri', Float32Array), mat: rd('mat', Float32Array), norm: rd('norm', Float32Array),
+  uv: rd('uv', Float32Array), atlas: rd('atlas', Uint8Array), atlasRes: job.atlasRes, atlasLayers: job.atlasLayers, env: rd('env', Uint8Array),
+  envW: job.envW, envH: job.envH, bins: rd('bins', Uint32Array), leafSize: job.leafSize };
+const pt = new F.PathTracer(desc, job.W, job.H, 0);
+pt.eye = job.cam.P; pt.dir = job.cam.I; pt.fovScale = job.cam.fov_scale; pt.envTheta = job.cam.env_theta;
+pt.lensFeatures = job.lens; pt.numBounces = 4;
+pt.seed(job.seed);
+const n = pt.renderAdaptive({ targetRelMse: job.target, maxTicks: job.max_ticks, minTicks: job.min_ticks, roundTicks: job.round_ticks });
+const out = new Float32Array(job.W * job.H * 4);
+pt.readRadiance(out);
+fs.writeFileSync(path.join(dir, 'out.bin'), Buffer.from(out.buffer));
+fs.writeFileSync(path.join(dir, 'counts.bin'), Buffer.from(pt.readSampleCounts().buffer));
+fs.writeFileSync(path.join(dir, 'n.json'), JSON.stringify(n));
+Promise.resolve(pt.close()).then(() => {});

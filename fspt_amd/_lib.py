@@ -91,6 +91,11 @@ SIGNATURES = {
     "fspt_scene_destroy": (C.c_int, [_VP]),
     "fspt_set_texture_interleave_budget": (C.c_int, [C.c_uint64]),
     "fspt_scene_depth": (C.c_int, [_VP, _U32]),
+    "fspt_scene_update_geometry": (C.c_int, [_VP, _F, _F]),
+    "fspt_scene_update_geometry_device": (C.c_int, [_VP, _VP, _VP]),
+    "fspt_scene_sah_cost": (C.c_int, [_VP, C.POINTER(C.c_double)]),
+    "fspt_scene_last_update_ms": (C.c_int, [_VP, _F, _U32]),
+    "fspt_multi_update_geometry": (C.c_int, [_VP, _F, _F]),
     "fspt_target_create": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(_VP)]),
     "fspt_target_destroy": (C.c_int, [_VP]),
     "fspt_target_set_viewport": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
@@ -182,6 +187,7 @@ SIGNATURES = {
     "fspt_builder_build_gpu": (C.c_int, [_VP, C.c_uint32, C.c_int]),
     "fspt_builder_gpu_stats": (C.c_int, [_VP, _F, _U32, _U32]),
     "fspt_builder_tri_order": (C.c_int, [_VP, _U32]),
+    "fspt_builder_geometry": (C.c_int, [_VP, _U32, _F, _F, _F, _F]),
     "fspt_builder_counts": (C.c_int, [_VP, _U32, _U32, _U32]),
     "fspt_builder_autofocus": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "fspt_builder_get": (C.c_int, [_VP, _F, _F, _F, _F, _F]),

@@ -606,6 +606,46 @@ int fspt_scene_create(const fspt_scene_desc *desc, int device, fspt_scene **out)
   s->n_interior = n_interior;
   s->has_dielectric = has_dielectric;
   s->n_slots = n_slots;
+  // ---- what fspt_scene_update_geometry needs of this tree (host memory; fspt_internal.hpp) ----
+  {
+    fspt_scene::Refit &R = s->rf;
+    const uint32_t NO = fspt_scene::Refit::NO_DST;
+    R.ok = true;
+    R.node_dst.assign(N, NO);
+    R.node_owned.assign(N, NO);
+    for (uint32_t i = 0; i < N; ++i) {
+      if (word(i, 2) > -1) continue;
+      const uint32_t ch[2] = {(uint32_t)word(i, 0), (uint32_t)word(i, 1)};
+      for (uint32_t k = 0; k < 2; ++k) {
+        if (R.node_dst[ch[k]] != NO || (k == 1 && ch[1] == ch[0])) R.ok = false; // a node with two parents
+        R.node_dst[ch[k]] = 2u * (uint32_t)ref[i] + k;
+      }
+    }
+    // ownership: a leaf owns [triStart, the next larger triStart among the leaves, or n_tris)
+    std::vector<uint32_t> by_first(n_leaves);
+    for (size_t L = 0; L < n_leaves; ++L) by_first[L] = (uint32_t)L;
+    std::sort(by_first.begin(), by_first.end(), [&](uint32_t a, uint32_t b) { return leaf_first[a] < leaf_first[b]; });
+    R.leaf_first = leaf_first;
+    R.leaf_cnt.assign(n_leaves, 0u);
+    R.leaf_dst.assign(n_leaves, NO);
+    for (size_t q = 0; q < n_leaves; ++q) {
+      const uint32_t a = leaf_first[by_first[q]], b = q + 1 < n_leaves ? leaf_first[by_first[q + 1]] : T;
+      if (q + 1 < n_leaves && a == b) R.ok = false; // two leaves with the same range
+      R.leaf_cnt[by_first[q]] = b - a;
+    }
+    if (!n_leaves || leaf_first[by_first[0]] != 0u) R.ok = false; // triangles below the first triStart belong to no leaf
+    std::vector<std::vector<uint32_t>> levels(max_depth + 1);
+    for (uint32_t i = 0; i < N; ++i) {
+      if (word(i, 2) > -1) { const uint32_t L = (uint32_t)~ref[i]; R.leaf_dst[L] = R.node_dst[i]; R.node_owned[i] = R.leaf_cnt[L]; }
+      else if (i > 0 && R.node_dst[i] != NO) { levels[depth[i]].push_back((uint32_t)ref[i]); levels[depth[i]].push_back(R.node_dst[i]); }
+    }
+    R.lvl_off.assign(1, 0u);
+    for (size_t dpt = levels.size(); dpt-- > 0;) {
+      if (levels[dpt].empty()) continue;
+      R.lvl_nodes.insert(R.lvl_nodes.end(), levels[dpt].begin(), levels[dpt].end());
+      R.lvl_off.push_back((uint32_t)(R.lvl_nodes.size() / 2));
+    }
+  }
   *out = s;
   return FSPT_OK;
 }
@@ -615,6 +655,7 @@ int fspt_scene_destroy(fspt_scene *s) {
   hipSetDevice(s->device);
   hipFree(s->nodes); hipFree(s->quads); hipFree(s->tris); hipFree(s->slot_tri); hipFree(s->shade); hipFree(s->atlas); hipFree(s->atlas4); hipFree(s->tex_sets); hipFree(s->env); hipFree(s->bins);
   hipFree(s->l_alias); hipFree(s->l_rec); hipFree(s->l_p); hipFree(s->l_pick);
+  fspt::refit_release(s);
   delete s;
   return FSPT_OK;
 }
@@ -670,6 +711,7 @@ int fspt_target_create(fspt_scene *scene, uint32_t W, uint32_t H, fspt_target **
     return FSPT_E_HIP;
   }
   t->accum = t->accum_own;
+  scene->targets.push_back(t); // (fspt_scene_update_geometry orders itself against every live target)
   *out = t;
   return FSPT_OK;
 }
@@ -677,6 +719,7 @@ int fspt_target_create(fspt_scene *scene, uint32_t W, uint32_t H, fspt_target **
 int fspt_target_destroy(fspt_target *t) {
   if (!t) return FSPT_OK;
   hipSetDevice(t->scene->device);
+  { auto &v = t->scene->targets; v.erase(std::remove(v.begin(), v.end(), t), v.end()); }
   // Recorded ticks are dropped: nothing can observe the library's own accumulator any more, and a caller-owned one
   // (fspt_target_bind_accumulator) may already have been freed by its owner - destroy never writes to it.  A caller
   // that wants the recorded ticks in its buffer calls fspt_sync (or re-binds, which flushes) first.
@@ -1345,6 +1388,115 @@ static int present_flush(fspt_target *t) {
 
 extern "C" {
 
+// ---------------------------------------------------------------------------
+// in-place geometry update (kernels in fspt_refit.hip)
+// ---------------------------------------------------------------------------
+static int update_geometry(fspt_scene *s, const float *tri, const float *norm, bool on_device, const char *fn) {
+  if (!s || !tri) { fspt_set_error("%s: NULL scene or tri", fn); return FSPT_E_INVALID; }
+  if (!on_device) { // the host form's check needs no device: refuse before anything is touched
+    const size_t n = (size_t)s->n_tris * 9, m = norm ? (size_t)s->n_tris * 27 : 0;
+    for (size_t i = 0; i < n; ++i) if (!std::isfinite(tri[i])) { fspt_set_error("%s: tri[%zu] is not finite", fn, i); return FSPT_E_INVALID; }
+    for (size_t i = 0; i < m; ++i) if (!std::isfinite(norm[i])) { fspt_set_error("%s: norm[%zu] is not finite", fn, i); return FSPT_E_INVALID; }
+  }
+  if (!s->rf.ok) {
+    fspt_set_error("%s: scene is not refittable (the leaves' triStarts must be distinct and tile [0, n_tris), every node have one parent)", fn);
+    return FSPT_E_STATE;
+  }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  // every earlier call on any target of the scene sees the old geometry: run the recorded ticks (which joins a present
+  // frame in flight), then wait for the device - the update's kernels run on the NULL stream and are waited for, so every
+  // later call sees the new one
+  // (a target under fspt_present keeps its frame in flight: its recorded ticks are enqueued the present way, without a
+  // join, so the next fspt_present still returns the pre-update frame)
+  for (fspt_target *t : s->targets) {
+    if (t->pr_active) { t->pr_dirty = true; rc = present_flush(t); if (rc) return rc; }
+    else FLUSH_OR_RETURN(t);
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  rc = fspt::refit_prepare(s);
+  if (rc) return rc;
+  const size_t T = s->n_tris;
+  if (!on_device) {
+    if (!s->rf.stage) HIP_TRY(hipMalloc((void **)&s->rf.stage, T * 36 * 4));
+    HIP_TRY(hipMemcpy(s->rf.stage, tri, T * 9 * 4, hipMemcpyHostToDevice));
+    if (norm) HIP_TRY(hipMemcpy(s->rf.stage + T * 9, norm, T * 27 * 4, hipMemcpyHostToDevice));
+    tri = s->rf.stage;
+    if (norm) norm = s->rf.stage + T * 9;
+  }
+  if (!s->quads && s->n_interior) { // a scene created from refitted boxes may have two-level nodes where this one had none
+    HIP_TRY(hipMalloc(&s->quads, (size_t)s->n_interior * fspt::QUAD_F4 * 16u));
+  }
+  int finite = 1, quads_ok = 0;
+  rc = fspt::refit_run(s, tri, norm, &finite, &quads_ok);
+  if (rc) return rc;
+  if (!finite) { fspt_set_error("%s: a value of tri / norm is not finite (scene unchanged)", fn); return FSPT_E_INVALID; }
+  s->d.quads = quads_ok ? (const float4 *)s->quads : nullptr;
+  // the emitter light table depends on the triangles' areas: release it; light_table_ensure rebuilds it from the device arrays
+  if (s->lights_built) {
+    hipFree(s->l_alias); hipFree(s->l_rec); hipFree(s->l_p); hipFree(s->l_pick);
+    s->l_alias = s->l_rec = s->l_p = s->l_pick = nullptr;
+    s->d.light_alias = nullptr; s->d.light_rec = nullptr; s->d.light_p = nullptr; s->d.light_pick = nullptr;
+    s->d.n_lights = 0;
+    s->lights_built = false;
+  }
+  for (fspt_target *t : s->targets)
+    if (t->lights == FSPT_LIGHTS_EMITTERS) { rc = light_table_ensure(s); if (rc) return rc; break; }
+  return FSPT_OK;
+}
+
+int fspt_scene_update_geometry(fspt_scene *s, const float *tri, const float *norm) {
+  return update_geometry(s, tri, norm, false, "fspt_scene_update_geometry");
+}
+
+int fspt_scene_update_geometry_device(fspt_scene *s, const float *tri, const float *norm) {
+  return update_geometry(s, tri, norm, true, "fspt_scene_update_geometry_device");
+}
+
+int fspt_scene_last_update_ms(fspt_scene *s, float *ms, uint32_t *launches) {
+  if (!s) { fspt_set_error("fspt_scene_last_update_ms: NULL scene"); return FSPT_E_INVALID; }
+  if (ms) *ms = s->rf.last_ms;
+  if (launches) *launches = s->rf.last_launches;
+  return FSPT_OK;
+}
+
+// sum over the leaves of SA / SA(root) x triangles owned + sum over the interior nodes of SA / SA(root), float64, in the
+// reference's node order, from the boxes the device holds now (a node's box sits in its parent's record; the root's is
+// the union of its children's)
+int fspt_scene_sah_cost(fspt_scene *s, double *cost) {
+  if (!s || !cost) { fspt_set_error("fspt_scene_sah_cost: NULL argument"); return FSPT_E_INVALID; }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  if (!s->n_interior) { *cost = (double)s->n_tris; return FSPT_OK; } // the root is the one leaf
+  std::vector<float> nodes((size_t)s->n_interior * 16); // (only an update writes the boxes, and it has finished when it returns)
+  HIP_TRY(hipMemcpy(nodes.data(), s->nodes, nodes.size() * 4, hipMemcpyDeviceToHost));
+  auto area = [](const float lo[3], const float hi[3]) {
+    const double e0 = (double)hi[0] - (double)lo[0], e1 = (double)hi[1] - (double)lo[1], e2 = (double)hi[2] - (double)lo[2];
+    return (e0 * e1 + e0 * e2 + e1 * e2) * 2.0;
+  };
+  auto box_at = [&](uint32_t slot, float lo[3], float hi[3]) {
+    const float *f = &nodes[(size_t)(slot >> 1) * 16];
+    const uint32_t k = slot & 1u;
+    lo[0] = f[4 * k]; lo[1] = f[4 * k + 1]; lo[2] = f[8 + 2 * k];
+    hi[0] = f[4 * k + 2]; hi[1] = f[4 * k + 3]; hi[2] = f[9 + 2 * k];
+  };
+  const uint32_t NO = fspt_scene::Refit::NO_DST;
+  float lo[3], hi[3], l2[3], h2[3];
+  box_at(2u * (uint32_t)s->d.root_ref, lo, hi);
+  box_at(2u * (uint32_t)s->d.root_ref + 1u, l2, h2);
+  for (int a = 0; a < 3; ++a) { lo[a] = l2[a] < lo[a] ? l2[a] : lo[a]; hi[a] = h2[a] > hi[a] ? h2[a] : hi[a]; }
+  const double root = area(lo, hi);
+  double sum = root; // the root itself
+  for (uint32_t i = 1; i < s->n_nodes; ++i) {
+    if (s->rf.node_dst[i] == NO) continue; // not reachable from the root
+    box_at(s->rf.node_dst[i], lo, hi);
+    const double sa = area(lo, hi);
+    sum += s->rf.node_owned[i] == NO ? sa : sa * (double)s->rf.node_owned[i];
+  }
+  *cost = sum / root;
+  return FSPT_OK;
+}
+
 int fspt_present(fspt_target *t, float exposure, float saturation, int denoise, float max_sigma, float scale,
                  uint8_t *out_rgba8, uint32_t *ticks_out) {
   if (!t || !out_rgba8 || !ticks_out) { fspt_set_error("fspt_present: NULL argument"); return FSPT_E_INVALID; }
@@ -1716,15 +1868,15 @@ int fspt_intersect(fspt_scene *s, const float *rays, uint32_t n, float *t_out, i
 
 int fspt_scene_two_level_nodes(const fspt_scene *s, int *present, uint64_t *bytes) {
   if (!s) { fspt_set_error("fspt_scene_two_level_nodes: NULL argument"); return FSPT_E_INVALID; }
-  if (present) *present = s->quads != nullptr;
-  if (bytes) *bytes = s->quads ? (uint64_t)s->n_interior * fspt::QUAD_F4 * 16u : 0u;
+  if (present) *present = s->d.quads != nullptr; // (after an update: what a scene created from the same data would have)
+  if (bytes) *bytes = s->d.quads ? (uint64_t)s->n_interior * fspt::QUAD_F4 * 16u : 0u;
   return FSPT_OK;
 }
 
 int fspt_intersect_form(fspt_scene *s, int two_level, const float *rays, uint32_t n, float *t_out, int32_t *index_out, uint32_t *steps_out,
                         uint32_t *leaves_out) {
   if (!s || (n && (!rays || !t_out || !index_out))) { fspt_set_error("fspt_intersect: NULL argument"); return FSPT_E_INVALID; }
-  if (two_level && !s->quads) { fspt_set_error("fspt_intersect_form: the scene has no two-level nodes (its boxes are not the unions of their children's)"); return FSPT_E_INVALID; }
+  if (two_level && !s->d.quads) { fspt_set_error("fspt_intersect_form: the scene has no two-level nodes (its boxes are not the unions of their children's)"); return FSPT_E_INVALID; }
   if (n == 0) return FSPT_OK;
   HIP_TRY(hipSetDevice(s->device));
   float *d_rays = nullptr, *d_t = nullptr;

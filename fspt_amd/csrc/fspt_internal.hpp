@@ -53,7 +53,38 @@ struct fspt_scene {
   std::vector<uint32_t> l_alias_h;  // per entry
   std::vector<float> l_pick_h;      // per leaf slot
   std::vector<uint32_t> l_slot_tri; // per leaf slot: its triangle
+  // fspt_scene_update_geometry.  The scene knows its live targets (fspt_target_create / _destroy), so that an
+  // update is ordered against their recorded ticks and their streams.  `rf` is what a refit needs of the reference tree and
+  // fspt_scene_create no longer has when it returns: host memory until the first update, which makes the device copies
+  // (fspt_refit.hip) - a scene that is never updated allocates nothing for it on the GPU.
+  std::vector<fspt_target *> targets;
+  struct Refit {
+    static const uint32_t NO_DST = 0xFFFFFFFFu;
+    bool ok = false;                  // the leaves' triStarts are distinct and tile [0, n_tris); every node has one parent
+    // per leaf record: first triangle, triangles owned ([first, next larger first or n_tris)), and where its box lives:
+    // box slot 2 * (parent's native index) + side in `nodes` (NO_DST: the root, whose box is stored nowhere)
+    std::vector<uint32_t> leaf_first, leaf_cnt, leaf_dst;
+    // interior nodes but the root, deepest level first: (own native index, box slot); lvl_off[k] .. lvl_off[k + 1] = level k
+    std::vector<uint32_t> lvl_nodes, lvl_off;
+    // per reference node, pre-order (fspt_scene_sah_cost): box slot, triangles owned (interior: NO_DST)
+    std::vector<uint32_t> node_dst, node_owned;
+    // device side, made by the first update
+    uint32_t *d_leaf = nullptr;       // leaf_first | leaf_cnt | leaf_dst
+    uint32_t *d_lvl = nullptr;        // lvl_nodes
+    uint32_t *d_flag = nullptr;       // [0] non-finite input seen, [1] the two-level nodes are not usable
+    float *stage = nullptr;           // the host form's upload: 9 + 27 floats per triangle
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    float last_ms = 0.0f;             // kernels of the last update, first to last
+    uint32_t last_launches = 0;
+  } rf;
 };
+namespace fspt { // fspt_refit.hip
+int refit_prepare(fspt_scene *s);  // the device copies of s->rf (idempotent)
+void refit_release(fspt_scene *s);
+// tri / norm (may be NULL): device memory.  *finite = 0: a non-finite value, nothing written.  *quads_ok: the rebuilt
+// two-level nodes (s->quads, must be allocated) are usable.  Runs on the NULL stream and waits for it.
+int refit_run(fspt_scene *s, const float *tri, const float *norm, int *finite, int *quads_ok);
+}
 int light_table_ensure(fspt_scene *s); // (fspt_api.cpp) builds the table once; FSPT_OK when it exists
 #ifndef FSPT_LIGHTS_ENV_Q_MAX
 #define FSPT_LIGHTS_ENV_Q_MAX 0.875f // largest q of a scene with an environment map (fspt_sched_batch.cpp fill_trace_params)

@@ -209,6 +209,15 @@ int fspt_multi_trace(fspt_multi *m, uint32_t tick, float rand_base, float env_th
 int fspt_multi_render(fspt_multi *m, const fspt_camera_params *cam, uint32_t first_tick, uint32_t n_ticks, uint64_t seed) {
   MULTI_EACH(fspt_render(t, cam, first_tick, n_ticks, seed));
 }
+int fspt_multi_update_geometry(fspt_multi *m, const float *tri, const float *norm) {
+  if (!m) { fspt_set_error("fspt_multi_update_geometry: NULL handle"); return FSPT_E_INVALID; }
+  for (fspt_scene *s : m->scenes) { // (a bad array is refused by the first scene, before anything is written)
+    const int rc = fspt_scene_update_geometry(s, tri, norm);
+    if (rc) return rc;
+  }
+  return FSPT_OK;
+}
+
 int fspt_multi_clear(fspt_multi *m) { MULTI_EACH(fspt_clear(t)); }
 int fspt_multi_sync(fspt_multi *m) { MULTI_EACH(fspt_sync(t)); }
 

@@ -283,6 +283,29 @@ static napi_value SceneDestroy(napi_env env, napi_callback_info info) {
   return undefined(env);
 }
 
+/* sceneUpdateGeometry(scene, nTris, tri Float32Array, norm Float32Array | null): fspt_scene_update_geometry.
+ * nTris is the count the scene was created with (the JS host knows it): the arrays must hold 9 / 27 floats per triangle.
+ * Guarded like every scene call: a renderAsync job on a target of the scene counts on the scene ('render in flight'). */
+static napi_value SceneUpdateGeometry(napi_env env, napi_callback_info info) {
+  napi_value a[4]; void *h, *tri = NULL, *norm = NULL; size_t nt = 0, nn = 0; uint32_t n = 0;
+  if (get_args(env, info, 4, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[1], &n));
+  if (typed(env, a[2], napi_float32_array, 0, &tri, &nt) || typed(env, a[3], napi_float32_array, 1, &norm, &nn)) return NULL;
+  if (nt != (size_t)n * 9 || (norm && nn != (size_t)n * 27)) {
+    napi_throw_range_error(env, NULL, "fspt_napi: updateGeometry needs 9 floats (tri) and 27 floats (norm) per triangle of the scene");
+    return NULL;
+  }
+  FSPT_OK_OR_THROW(fspt_scene_update_geometry((fspt_scene *)h, (const float *)tri, (const float *)norm));
+  return undefined(env);
+}
+static napi_value SceneSahCost(napi_env env, napi_callback_info info) {
+  napi_value a[1], v; void *h; double cost = 0.0;
+  if (get_args(env, info, 1, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  FSPT_OK_OR_THROW(fspt_scene_sah_cost((fspt_scene *)h, &cost));
+  NAPI_OK(napi_create_double(env, cost, &v));
+  return v;
+}
+
 /* ----------------------------------------------------------------- target */
 static napi_value TargetCreate(napi_env env, napi_callback_info info) {
   napi_value a[3]; void *h; uint32_t W, H;
@@ -1126,7 +1149,7 @@ static napi_value AbiVersion(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
-      {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"targetCreate", TargetCreate},
+      {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneSahCost", SceneSahCost}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
       {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},

@@ -286,7 +286,7 @@ uint32_t wf_tail_slice(const fspt_target *t) { return t->scene->n_tris >= (1u <<
 
 // Which node form a launch of kernel class `kind` over (an expected) `paths` paths walks: WfP::wide's bit for it.
 uint32_t wide_bit(const fspt_target *t, int kind, double paths) {
-  if (!t->scene->quads || t->count) return 0u;
+  if (!t->scene->d.quads || t->count) return 0u;
   const int slot = kind == fspt::WF_K_PRIMARY ? 0 : kind == fspt::WF_K_TRACE ? 1 : kind == fspt::WF_K_TAIL ? 2 : -1;
   if (slot < 0) return 0u;
   bool on;

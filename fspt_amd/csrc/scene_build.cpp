@@ -538,6 +538,22 @@ struct BvhBuilder {
   }
 };
 
+// one triangle's records as main.js:360-392 packs them: 9 vertex floats, 12 material floats, 27 normTex floats, 6 uv floats
+void push_tri(const Tri &t, std::vector<float> &tri, std::vector<float> &mat, std::vector<float> &norm, std::vector<float> &uv) {
+  for (int v = 0; v < 3; ++v) {
+    tri.push_back((float)t.v[v].x); tri.push_back((float)t.v[v].y); tri.push_back((float)t.v[v].z);
+  }
+  for (int q = 0; q < 12; ++q) mat.push_back((float)t.mat[q]);
+  for (int v = 0; v < 3; ++v) {
+    D3 tg = t.tangents.size() > (size_t)v ? t.tangents[v] : d3(NAN, NAN, NAN);
+    D3 bt = t.bitangents.size() > (size_t)v ? t.bitangents[v] : d3(NAN, NAN, NAN);
+    norm.push_back((float)t.n[v].x); norm.push_back((float)t.n[v].y); norm.push_back((float)t.n[v].z);
+    norm.push_back((float)tg.x); norm.push_back((float)tg.y); norm.push_back((float)tg.z);
+    norm.push_back((float)bt.x); norm.push_back((float)bt.y); norm.push_back((float)bt.z);
+  }
+  for (int v = 0; v < 3; ++v) { uv.push_back((float)t.uv[v][0]); uv.push_back((float)t.uv[v][1]); }
+}
+
 // packing loops, main.js:360-392, shared by both builders.  `nodes` in pre-order (serializeTree, bvh.js:33-50), a leaf's
 // triangles are order[lo..hi); fbox: the float32 boxes to store (6 per node), or NULL for (float) of the float64 boxes.
 void pack_tree(fspt_builder *b, const std::vector<BuildNode> &nodes, const std::vector<uint32_t> &order, const float *fbox,
@@ -562,19 +578,7 @@ void pack_tree(fspt_builder *b, const std::vector<BuildNode> &nodes, const std::
     }
     if (nd.leaf) {
       for (uint32_t k = nd.lo; k < nd.hi; ++k) {  // getTriangles = indices[0] order
-        const Tri &t = b->geometry[order[k]];
-        for (int v = 0; v < 3; ++v) {
-          b->tri.push_back((float)t.v[v].x); b->tri.push_back((float)t.v[v].y); b->tri.push_back((float)t.v[v].z);
-        }
-        for (int q = 0; q < 12; ++q) b->mat.push_back((float)t.mat[q]);
-        for (int v = 0; v < 3; ++v) {
-          D3 tg = t.tangents.size() > (size_t)v ? t.tangents[v] : d3(NAN, NAN, NAN);
-          D3 bt = t.bitangents.size() > (size_t)v ? t.bitangents[v] : d3(NAN, NAN, NAN);
-          b->norm.push_back((float)t.n[v].x); b->norm.push_back((float)t.n[v].y); b->norm.push_back((float)t.n[v].z);
-          b->norm.push_back((float)tg.x); b->norm.push_back((float)tg.y); b->norm.push_back((float)tg.z);
-          b->norm.push_back((float)bt.x); b->norm.push_back((float)bt.y); b->norm.push_back((float)bt.z);
-        }
-        for (int v = 0; v < 3; ++v) { b->uv.push_back((float)t.uv[v][0]); b->uv.push_back((float)t.uv[v][1]); }
+        push_tri(b->geometry[order[k]], b->tri, b->mat, b->norm, b->uv);
       }
     }
   }
@@ -798,7 +802,7 @@ int fspt_builder_gpu_stats(const fspt_builder *b, float *kernel_ms, uint32_t *la
 // shootAutoFocusRay (main.js:447-546): the distance along (eye, dir) to the first triangle, found on the host
 // BVH in float64; main.js then sets lensFeatures[0] = 1 - 1 / dist.  1e6 (maxT) when nothing is hit.
 int fspt_builder_autofocus(const fspt_builder *b, const double eye_[3], const double dir_[3], double *dist) {
-  if (!b || !b->built) { fspt_set_error("fspt_builder_autofocus: builder not built"); return FSPT_E_STATE; }
+  if (!b) { fspt_set_error("fspt_builder_autofocus: NULL builder"); return FSPT_E_STATE; }
   if (!eye_ || !dir_ || !dist) { fspt_set_error("fspt_builder_autofocus: NULL argument"); return FSPT_E_INVALID; }
   const double maxT = 1e6;
   const D3 eye = d3(eye_[0], eye_[1], eye_[2]), dir = d3(dir_[0], dir_[1], dir_[2]);
@@ -829,6 +833,12 @@ int fspt_builder_autofocus(const fspt_builder *b, const double eye_[3], const do
     tmin = jsmax(tmin, jsmin(tz1, tz2)); tmax = jsmin(tmax, jsmax(tz1, tz2));
     return (tmax >= tmin && tmax >= 0) ? tmin : maxT;
   };
+  if (!b->built) { // no tree (geometry that is refitted, not rebuilt: DESIGN 8.6): the closest of all triangles, same arithmetic
+    double res = maxT;
+    for (const Tri &tri : b->geometry) { const double tmp = ray_tri(tri); if (tmp < res) res = tmp; }
+    *dist = res;
+    return FSPT_OK;
+  }
   // findTriangles (main.js:531-542), explicit stack instead of recursion; `closest` is threaded through
   struct Frame { int node; int stage; int ord[2]; double t[2]; };
   std::vector<Frame> st;
@@ -871,6 +881,20 @@ int fspt_builder_counts(const fspt_builder *b, uint32_t *n_nodes, uint32_t *n_tr
   if (n_nodes) *n_nodes = b->n_nodes;
   if (n_tris) *n_tris = b->n_tris;
   if (depth) *depth = b->depth;
+  return FSPT_OK;
+}
+
+// the triangles in PARSE order (the order they were added), packed as fspt_builder_get packs them; needs no tree
+int fspt_builder_geometry(const fspt_builder *b, uint32_t *n_tris, float *tri, float *mat, float *norm, float *uv) {
+  if (!b) { fspt_set_error("fspt_builder_geometry: NULL builder"); return FSPT_E_INVALID; }
+  if (n_tris) *n_tris = (uint32_t)b->geometry.size();
+  if (!tri && !mat && !norm && !uv) return FSPT_OK;
+  std::vector<float> vt, vm, vn, vu;
+  for (const Tri &t : b->geometry) push_tri(t, vt, vm, vn, vu);
+  if (tri) std::memcpy(tri, vt.data(), vt.size() * 4);
+  if (mat) std::memcpy(mat, vm.data(), vm.size() * 4);
+  if (norm) std::memcpy(norm, vn.data(), vn.size() * 4);
+  if (uv) std::memcpy(uv, vu.data(), vu.size() * 4);
   return FSPT_OK;
 }
 

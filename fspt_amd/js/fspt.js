@@ -318,6 +318,7 @@ class PathTracer {
   constructor(scene, width, height, device) {
     this.resolution = [width, height];
     this._scene = addon.sceneCreate(scene, device || 0);
+    this._nTris = scene.tri.length / 9;       // updateGeometry checks its arrays against it
     this._target = addon.targetCreate(this._scene, width, height);
     // main.js:67-74
     this.fovScale = 0.5; this.envTheta = 0; this.dir = [0, 0, -1]; this.eye = [0, 0, 2];
@@ -437,6 +438,16 @@ class PathTracer {
     if (typeof f !== 'number' || !(f > 0 && f <= 1)) throw new RangeError('setLights: emitterFraction must be a number in (0, 1]');
     addon.setLights(this._target, code, f);
   }
+  /** new vertices (Float32Array, 9 per triangle) and optionally normTex records (27 per triangle) for the scene's triangles
+   *  in leaf order: the BVH is refitted on the GPU, nothing else changes (include/fspt.h fspt_scene_update_geometry, DESIGN
+   *  8.6).  The accumulator is not cleared: call clear().  Throws Error('render in flight') during a renderAsync. */
+  updateGeometry(tri, norm) {
+    if (!(tri instanceof Float32Array) || tri.length !== this._nTris * 9) throw new RangeError('updateGeometry: tri must be a Float32Array of ' + this._nTris + ' x 9 floats');
+    if (norm != null && (!(norm instanceof Float32Array) || norm.length !== this._nTris * 27)) throw new RangeError('updateGeometry: norm must be a Float32Array of ' + this._nTris + ' x 27 floats');
+    addon.sceneUpdateGeometry(this._scene, this._nTris, tri, norm == null ? null : norm);
+  }
+  /** SAH cost of the tree with its current boxes relative to the root's area (fspt_scene_sah_cost) */
+  sahCost() { return addon.sceneSahCost(this._scene); }
   /** 'wavefront' (batches of ticks), 'stream' (fixed pool of live paths), 'megakernel' (include/fspt_tuning.h) */
   setPipeline(name, batch) { addon.setPipeline(this._target, pipelineCode(name), batch || 0); }
   /** traversal steps a starved trace wave walks on before it suspends its rays (0 = never; include/fspt.h) */

@@ -8,6 +8,7 @@ reference's format (scene/<name>.json with props / static_props / animated_props
     python -m fspt_amd.render --out bunny.png --spp 16 --sampler sobol --sampler-seed 3  # Owen-scrambled Sobol sampler
     python -m fspt_amd.render --scene web/scene/bunny.json --lights --emitter-fraction 0.5  # sample emissive triangles
     python -m fspt_amd.render --mesh-n 289 --bvh gpu --spp 16 --out c3.png  # binned-SAH tree built on the GPU
+    python -m fspt_amd.render --scene 'web/scene/anim_{frame}.json' --frames 0:24 --bvh refit --out 'out/{frame}.png'  # build once, refit
 
 Path tracing runs in the HIP kernels (fspt_render), tone mapping in the draw.fs kernel (fspt_draw); --atrous K runs
 the guided a-trous denoiser (fspt_features + fspt_denoise, K iterations) before tone mapping (fspt_draw_denoised).
@@ -38,8 +39,9 @@ def main():
     ap.add_argument("--assets", default=None, help="web root the JSON's paths are relative to (default: parent of the scene folder)")
     ap.add_argument("--frames", default=None, help="A:B = frames A..B-1 (the reference's ?frame=N loop, main.js:851-866)")
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--bvh", choices=("sah", "gpu"), default="sah",
-                    help="BVH builder: the reference's full-sweep SAH on the CPU, or binned SAH on the GPU (DESIGN 8.4)")
+    ap.add_argument("--bvh", choices=("sah", "gpu", "refit"), default="sah",
+                    help="BVH builder: the reference's full-sweep SAH on the CPU, or binned SAH on the GPU (DESIGN 8.4); refit (with "
+                         "--frames): build the first frame, then refit the tree for frames that only move triangles (DESIGN 8.6)")
     ap.add_argument("--sampler", choices=("reference", "sobol"), default="reference",
                     help="the paths' random numbers (fspt_target_set_sampler; built-in scene)")
     ap.add_argument("--sampler-seed", type=int, default=0, help="seed of --sampler sobol, in [0, 2^32)")
@@ -50,6 +52,8 @@ def main():
                     help="adaptive sampling: stop a 32x32 tile once its estimated relative MSE is below REL_MSE (--spp = the most)")
     ap.add_argument("--sample-map", default=None, help="with --adaptive: write the ticks per pixel as a grey PNG")
     args = ap.parse_args()
+    if args.bvh == "refit" and not (args.scene and args.frames):
+        ap.error("--bvh refit needs --scene and --frames (it reuses one scene across a frame sequence)")
     if args.adaptive is not None:
         if not (np.isfinite(args.adaptive) and args.adaptive >= 0.0):
             ap.error("--adaptive must be a finite relative MSE >= 0")

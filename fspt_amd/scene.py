@@ -313,7 +313,7 @@ BVH_BUILDERS = ("sah", "gpu")
 
 def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas_res=2048, images=None,
                 world_transforms=None, normalize=None, mtl_texts=None, focus_rays=None, bvh="sah", device=0,
-                keep_order=False):
+                keep_order=False, geometry_only=False):
     """initBVH (main.js:284-445) for props = list of scene-JSON prop dicts and obj_texts = {path: OBJ text}.
     env = RGBE uint8 [h*w*4] or None; world_transforms = scene.worldTransforms; normalize = scene.normalize;
     mtl_texts = {url: MTL text} for `mtllib` lines (url = <dir of the OBJ>/<name>, obj_loader.js:186);
@@ -321,7 +321,10 @@ def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas
     meta["focus"] = shootAutoFocusRay's lensFeatures[0] = 1 - 1/dist for each (main.js:447-546).
     bvh = "sah": the reference's full-sweep SAH tree (bvh.js, on the CPU); "gpu": the binned-SAH tree built on HIP device
     `device` (fspt_builder_build_gpu; leaf_size 1..64).  meta["bvh"] names the builder; keep_order=True adds
-    meta["tri_order"]: packed triangle k is the k'th triangle of the OBJs in the order they were added."""
+    meta["tri_order"]: packed triangle k is the k'th triangle of the OBJs in the order they were added.
+    geometry_only=True: parse and transform the props but build NO tree: tri / mat / norm / uv come back in PARSE order, bvh is
+    empty (meta["geometry_only"]); focus_rays are answered by the float64 closest hit over all triangles.  What a host of
+    moving geometry needs per frame (geometry_in_leaf_order, Scene.update_geometry)."""
     if bvh not in BVH_BUILDERS:
         raise ValueError(f"bvh must be one of {BVH_BUILDERS}, not {bvh!r}")
     lib = L.lib()
@@ -380,17 +383,23 @@ def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas
             L.check(lib.fspt_builder_commit_obj(b, mats, ng.value))
         if normalize:
             L.check(lib.fspt_builder_normalize(b, float(normalize)))
-        if bvh == "gpu":
-            L.check(lib.fspt_builder_build_gpu(b, leaf_size, int(device)))
-        else:
-            L.check(lib.fspt_builder_build(b, leaf_size))
         nn, nt, dp = C.c_uint32(), C.c_uint32(), C.c_uint32()
-        L.check(lib.fspt_builder_counts(b, C.byref(nn), C.byref(nt), C.byref(dp)))
+        if geometry_only:
+            L.check(lib.fspt_builder_geometry(b, C.byref(nt), None, None, None, None))
+        else:
+            if bvh == "gpu":
+                L.check(lib.fspt_builder_build_gpu(b, leaf_size, int(device)))
+            else:
+                L.check(lib.fspt_builder_build(b, leaf_size))
+            L.check(lib.fspt_builder_counts(b, C.byref(nn), C.byref(nt), C.byref(dp)))
         bvh_arr = np.zeros(nn.value * 9, np.float32); tri = np.zeros(nt.value * 9, np.float32)
         mat = np.zeros(nt.value * 12, np.float32); norm = np.zeros(nt.value * 27, np.float32)
         uv = np.zeros(nt.value * 6, np.float32)
-        L.check(lib.fspt_builder_get(b, L.fptr(bvh_arr), L.fptr(tri), L.fptr(mat), L.fptr(norm), L.fptr(uv)))
-        if keep_order:
+        if geometry_only:
+            L.check(lib.fspt_builder_geometry(b, None, L.fptr(tri), L.fptr(mat), L.fptr(norm), L.fptr(uv)))
+        else:
+            L.check(lib.fspt_builder_get(b, L.fptr(bvh_arr), L.fptr(tri), L.fptr(mat), L.fptr(norm), L.fptr(uv)))
+        if keep_order and not geometry_only:
             order = np.zeros(nt.value, np.uint32)
             L.check(lib.fspt_builder_tri_order(b, L.u32ptr(order)))
         for eye, d in (focus_rays or []):
@@ -407,21 +416,61 @@ def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas
     else:
         bins = np.array([0, 0, 1, 2048], dtype=np.uint32)  # main.js:292
     meta = {"layers": packer.describe(), "focus": focus, "bvh": bvh}
-    if keep_order:
+    if geometry_only:
+        meta["geometry_only"] = True
+    elif keep_order:
         meta["tri_order"] = order
     return SceneArrays(bvh=bvh_arr, tri=tri, mat=mat, norm=norm, uv=uv, atlas=atlas, atlas_res=packer.res,
                        atlas_layers=len(packer.image_set), env=env, env_w=env_w, env_h=env_h, bins=bins,
                        leaf_size=leaf_size, depth=dp.value, meta=meta)
 
 
+def sah_cost(arrays):
+    """SAH cost of reference-layout arrays relative to the root's area, float64: sum over the interior nodes of SA / SA(root)
+    + sum over the leaves of SA / SA(root) x the triangles the leaf owns ([triStart, the next larger triStart or n_tris)).
+    The number fspt_scene_sah_cost computes from the device's boxes."""
+    b = arrays.bvh.reshape(-1, 9)
+    w = b[:, :3].view(np.int32)
+    e = b[:, 6:9].astype(np.float64) - b[:, 3:6].astype(np.float64)
+    sa = (e[:, 0] * e[:, 1] + e[:, 0] * e[:, 2] + e[:, 1] * e[:, 2]) * 2
+    leaf = w[:, 2] > -1
+    first = w[leaf, 2].astype(np.int64)
+    srt = np.argsort(first, kind="stable")
+    cnt = np.zeros(first.size, np.int64)
+    cnt[srt] = np.diff(np.concatenate([first[srt], [arrays.n_tris]]))
+    return float((sa[~leaf].sum() + (sa[leaf] * cnt).sum()) / sa[0])
+
+
+def geometry_in_leaf_order(arrays_or_order, tri_in, norm_in=None):
+    """Triangles a host holds in PARSE order (the order the OBJs' faces were added) -> the leaf order Scene.update_geometry
+    and fspt_scene_desc take: packed triangle k is parse-order triangle order[k] (fspt_builder_tri_order).  The order comes
+    from a SceneArrays built with keep_order=True (meta["tri_order"]) or is given as an array.  Returns (tri, norm) float32,
+    flat; norm is None when norm_in is."""
+    order = arrays_or_order.meta.get("tri_order") if isinstance(arrays_or_order, SceneArrays) else arrays_or_order
+    if order is None:
+        raise ValueError("geometry_in_leaf_order: the arrays carry no meta['tri_order'] (build_scene(..., keep_order=True))")
+    order = np.asarray(order, dtype=np.int64).reshape(-1)
+    tri = np.asarray(tri_in, dtype=np.float32).reshape(-1, 9)
+    if tri.shape[0] != order.size:
+        raise ValueError(f"geometry_in_leaf_order: {tri.shape[0]} triangles, the order names {order.size}")
+    out_n = None
+    if norm_in is not None:
+        nrm = np.asarray(norm_in, dtype=np.float32).reshape(-1, 27)
+        if nrm.shape[0] != order.size:
+            raise ValueError(f"geometry_in_leaf_order: {nrm.shape[0]} normal records, the order names {order.size}")
+        out_n = np.ascontiguousarray(nrm[order]).reshape(-1)
+    return np.ascontiguousarray(tri[order]).reshape(-1), out_n
+
+
 def build_scene_json(scene, obj_texts, mtl_texts=None, images=None, env=None, env_w=0, env_h=0, leaf_size=4,
-                     focus_rays=None, bvh="sah", device=0):
+                     focus_rays=None, bvh="sah", device=0, keep_order=False, geometry_only=False):
     """build_scene for a whole scene JSON (props / static_props / animated_props, worldTransforms, normalize,
     atlasRes: main.js:284-445,869-871,944)."""
     return build_scene(merge_scene_props(scene), obj_texts, env=env, env_w=env_w, env_h=env_h, leaf_size=leaf_size,
                        atlas_res=scene.get("atlasRes") or 2048, images=images,
                        world_transforms=scene.get("worldTransforms"), normalize=scene.get("normalize"),
-                       mtl_texts=mtl_texts, focus_rays=focus_rays, bvh=bvh, device=device)
+                       mtl_texts=mtl_texts, focus_rays=focus_rays, bvh=bvh, device=device, keep_order=keep_order,
+                       geometry_only=geometry_only)
 
 
 def merge_scene_props(scene):

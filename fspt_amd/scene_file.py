@@ -40,10 +40,11 @@ def mtllib_urls(obj_text, base_path):
     return urls
 
 
-def load_scene_file(scene_path, asset_root=None, leaf_size=4, bvh="sah", device=0):
+def load_scene_file(scene_path, asset_root=None, leaf_size=4, bvh="sah", device=0, keep_order=False, geometry_only=False):
     """Returns (SceneArrays, settings).  settings = camera and display values with the reference's defaults
     (initGlobals, main.js:50-75): eye, dir, fov_scale, env_theta, exposure, samples, focus (lensFeatures[0]
-    after shootAutoFocusRay), aperture (index.html default 0.02).  bvh / device: scene.build_scene's builder choice."""
+    after shootAutoFocusRay), aperture (index.html default 0.02).  bvh / device: scene.build_scene's builder choice;
+    keep_order / geometry_only: as scene.build_scene (the latter: triangles in parse order, no tree)."""
     with open(scene_path, "r", encoding="utf-8") as fh:
         scene = json.load(fh)
     root = asset_root or os.path.dirname(os.path.dirname(os.path.abspath(scene_path)))
@@ -81,7 +82,8 @@ def load_scene_file(scene_path, asset_root=None, leaf_size=4, bvh="sah", device=
     eye = [float(x) for x in (scene.get("cameraPos") or [0, 0, 2])]
     d = [float(x) for x in (scene.get("cameraDir") or [0, 0, -1])]
     arrays = S.build_scene_json(scene, obj_texts, mtl_texts, images, env=env, env_w=env_w, env_h=env_h,
-                                leaf_size=leaf_size, focus_rays=[(eye, d)], bvh=bvh, device=device)
+                                leaf_size=leaf_size, focus_rays=[(eye, d)], bvh=bvh, device=device, keep_order=keep_order,
+                                geometry_only=geometry_only)
     settings = dict(eye=eye, dir=d, fov_scale=float(scene.get("fovScale") or 0.5),
                     env_theta=float(scene.get("environmentTheta") or 0), exposure=float(scene.get("exposure") or 1.0),
                     samples=int(scene.get("samples") or 2000), focus=arrays.meta["focus"][0], aperture=0.02)
@@ -99,25 +101,33 @@ def render_frame(arrays, settings, width, height, samples=None, bounces=4, seed=
     from .tracer import PathTracer
     pt = PathTracer(arrays, width, height, device=device, num_bounces=bounces)
     try:
-        pt.eye, pt.dir = list(settings["eye"]), list(settings["dir"])
-        pt.fovScale, pt.envTheta = settings["fov_scale"], settings["env_theta"]
-        pt.lensFeatures = [settings["focus"], settings["aperture"]]
-        if lights is not None:
-            pt.set_lights(lights, emitter_fraction)
-        pt.seed(seed)
-        n = int(samples if samples is not None else settings["samples"])
-        if adaptive is None:
-            pt.render(n)
-        else:
-            pt.render_adaptive(adaptive, max_ticks=n)
-            if sample_map:
-                write_sample_map(sample_map, pt.sample_counts(), n)
-        rgba = pt.draw(settings["exposure"], saturation, denoise, max_sigma)
-        rad = pt.readRadiance()
+        rgba, rad = _render_on(pt, settings, samples, seed, saturation, denoise, max_sigma, lights, emitter_fraction, adaptive,
+                               sample_map)
     finally:
         pt.close()
         pt.scene.close()
     return rgba[::-1].copy(), rad
+
+
+def _render_on(pt, settings, samples, seed, saturation, denoise, max_sigma, lights, emitter_fraction, adaptive, sample_map):
+    """render_frame's work on an existing tracer, from a cleared accumulator (bottom row first)"""
+    pt.clear()
+    pt.eye, pt.dir = list(settings["eye"]), list(settings["dir"])
+    pt.fovScale, pt.envTheta = settings["fov_scale"], settings["env_theta"]
+    pt.lensFeatures = [settings["focus"], settings["aperture"]]
+    if lights is not None:
+        pt.set_lights(lights, emitter_fraction)
+    pt.seed(seed)
+    n = int(samples if samples is not None else settings["samples"])
+    if adaptive is None:
+        pt.render(n)
+    else:
+        pt.render_adaptive(adaptive, max_ticks=n)
+        if sample_map:
+            write_sample_map(sample_map, pt.sample_counts(), n)
+    rgba = pt.draw(settings["exposure"], saturation, denoise, max_sigma)
+    rad = pt.readRadiance()
+    return rgba, rad
 
 
 def write_sample_map(path, counts, max_ticks):
@@ -128,18 +138,74 @@ def write_sample_map(path, counts, max_ticks):
     Image.fromarray(grey, mode="L").save(path)
 
 
-def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", **kw):
+def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", rebuild_above=None,
+                    on_frame=None, **kw):
     """frame=N sequencing (main.js:851-866, 966-969): for every N in `frames` load `scene_pattern.format(frame=N)`
     (the per-frame scene JSON the reference's server hands out for `?frame=N`), render it, write
     `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1.
-    bvh="gpu" builds every frame's tree on the render device."""
+    bvh="gpu" builds every frame's tree on the render device.
+    bvh="refit" (DESIGN 8.6): the first frame builds ("sah"); a later frame with the same triangle count, materials, uvs,
+    atlas and environment keeps scene and tracer: its props are parsed without building a tree, the moved triangles go to
+    Scene.update_geometry in the first tree's leaf order, the accumulator is cleared and the auto-focus ray is shot
+    against the new triangles.  Any other frame rebuilds, and so does one whose Scene.sah_cost() exceeds `rebuild_above` x
+    the cost at the last build (None, the default: never - no threshold has been measured).  on_frame(N, "build" | "refit")
+    reports what a frame did."""
     from PIL import Image
     written = []
-    for n in frames:
-        arrays, settings = load_scene_file(scene_pattern.format(frame=n), asset_root, bvh=bvh, device=kw.get("device", 0))
-        rgba, _ = render_frame(arrays, settings, width, height, **kw)
+    device = kw.get("device", 0)
+
+    def save(n, rgba):
         out = out_pattern.format(frame=n)
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         Image.fromarray(rgba[:, :, :3]).save(out)
         written.append(out)
+
+    if bvh != "refit":
+        for n in frames:
+            arrays, settings = load_scene_file(scene_pattern.format(frame=n), asset_root, bvh=bvh, device=device)
+            rgba, _ = render_frame(arrays, settings, width, height, **kw)
+            if on_frame:
+                on_frame(n, "build")
+            save(n, rgba)
+        return written
+
+    from .tracer import PathTracer
+    opt = dict(samples=None, seed=1, saturation=1.0, denoise=False, max_sigma=3.0, lights=None, emitter_fraction=0.5,
+               adaptive=None, sample_map=None)
+    bounces = kw.get("bounces", 4)
+    opt.update({k: v for k, v in kw.items() if k in opt})
+    base, pt, cost0 = None, None, None
+
+    def same_scene(a, g):
+        eq = lambda x, y: (x is None and y is None) or (x is not None and y is not None and np.array_equal(x, y))
+        order = a.meta["tri_order"]
+        return (g.n_tris == a.n_tris and np.array_equal(g.mat.reshape(-1, 12)[order], a.mat.reshape(-1, 12))
+                and np.array_equal(g.uv.reshape(-1, 6)[order], a.uv.reshape(-1, 6)) and g.atlas_res == a.atlas_res
+                and g.atlas_layers == a.atlas_layers and eq(g.atlas, a.atlas) and eq(g.env, a.env) and eq(g.bins, a.bins))
+
+    try:
+        for n in frames:
+            path = scene_pattern.format(frame=n)
+            how = "build"
+            if base is not None:
+                g, settings = load_scene_file(path, asset_root, geometry_only=True)
+                if same_scene(base, g):
+                    tri, norm = S.geometry_in_leaf_order(base, g.tri, g.norm)
+                    pt.update_geometry(tri, norm)
+                    how = "refit"
+                    if rebuild_above is not None and pt.scene.sah_cost() > rebuild_above * cost0:
+                        how = "build"
+            if how == "build":
+                if pt is not None:
+                    pt.close(); pt.scene.close()
+                base, settings = load_scene_file(path, asset_root, bvh="sah", device=device, keep_order=True)
+                pt = PathTracer(base, width, height, device=device, num_bounces=bounces)
+                cost0 = pt.scene.sah_cost() if rebuild_above is not None else None
+            rgba, _ = _render_on(pt, settings, **opt)
+            if on_frame:
+                on_frame(n, how)
+            save(n, rgba[::-1].copy())
+    finally:
+        if pt is not None:
+            pt.close(); pt.scene.close()
     return written

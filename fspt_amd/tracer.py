@@ -161,6 +161,54 @@ class Scene:
         L.check(L.lib().fspt_scene_two_level_nodes(self._h, C.byref(yes), C.byref(b)))
         return bool(yes.value), int(b.value)
 
+    def update_geometry(self, tri, norm=None):
+        """New vertices (9 floats per triangle) and, unless norm is None, normTex records (27 per triangle) for the scene's
+        n_tris triangles in LEAF order (scene.geometry_in_leaf_order): the tree is refitted on the GPU, nothing else changes
+        (fspt_scene_update_geometry).  numpy arrays are uploaded; float32 torch tensors on the scene's device
+        are read where they are (the `_device` form, no copy).  Accumulators are not cleared; `self.arrays` is not touched."""
+        n = int(self.arrays.n_tris)
+        on_dev = [hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) for a in (tri, norm) if a is not None]
+        if any(on_dev):
+            if not all(on_dev):
+                raise TypeError("update_geometry: tri and norm must both be device tensors or both host arrays")
+            import torch
+            ptrs = []
+            for name, a, k in (("tri", tri, 9), ("norm", norm, 27)):
+                if a is None:
+                    ptrs.append(None)
+                    continue
+                if a.dtype != torch.float32 or not a.is_contiguous():
+                    raise TypeError(f"update_geometry: {name} must be a contiguous float32 tensor")
+                if a.device.index != self.device:
+                    raise ValueError(f"update_geometry: {name} lives on {a.device}, the scene on device {self.device}")
+                if a.numel() != n * k:
+                    raise ValueError(f"update_geometry: {name} has {a.numel()} elements, the scene needs {n} x {k}")
+                ptrs.append(C.c_void_p(a.data_ptr()))
+            torch.cuda.current_stream(self.device).synchronize()  # whatever wrote the tensors has finished
+            L.check(L.lib().fspt_scene_update_geometry_device(self._h, ptrs[0], ptrs[1]))
+            return
+        tri = np.ascontiguousarray(tri, dtype=np.float32)
+        if tri.size != n * 9:
+            raise ValueError(f"update_geometry: tri has {tri.size} elements, the scene needs {n} x 9")
+        if norm is not None:
+            norm = np.ascontiguousarray(norm, dtype=np.float32)
+            if norm.size != n * 27:
+                raise ValueError(f"update_geometry: norm has {norm.size} elements, the scene needs {n} x 27")
+        L.check(L.lib().fspt_scene_update_geometry(self._h, L.fptr(tri), None if norm is None else L.fptr(norm)))
+
+    def sah_cost(self):
+        """SAH cost of the tree with the boxes the device holds now, relative to the root's area (fspt_scene_sah_cost): what
+        tools/bvh_build_bench.py prints for a built tree; grows as a refitted tree degrades."""
+        c = C.c_double()
+        L.check(L.lib().fspt_scene_sah_cost(self._h, C.byref(c)))
+        return float(c.value)
+
+    def last_update_ms(self):
+        """(GPU ms first kernel to last, kernels launched) of the most recent update_geometry."""
+        ms, n = C.c_float(), C.c_uint32()
+        L.check(L.lib().fspt_scene_last_update_ms(self._h, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
+
     def close(self):
         if self._h:
             L.lib().fspt_scene_destroy(self._h)
@@ -432,6 +480,10 @@ class PathTracer:
                                                  L.u32ptr(ticks), tx * ty))
         return {"rounds": int(rounds.value), "samples": int(samples.value), "tile_ticks": ticks, "tile_err": err}
 
+    def update_geometry(self, tri, norm=None):
+        """Scene.update_geometry on this tracer's scene (every tracer of the scene sees it); call clear() to restart the mean."""
+        self.scene.update_geometry(tri, norm)
+
     def clear(self):
         L.check(L.lib().fspt_clear(self._t))
         self.pingpong = 0
@@ -614,6 +666,18 @@ class MultiPathTracer:
         for _ in range(2 * int(n_ticks)):
             self.next_rand_base()
         self.pingpong += int(n_ticks)
+
+    def update_geometry(self, tri, norm=None):
+        """Scene.update_geometry (host arrays) on every device's copy of the scene (fspt_multi_update_geometry)."""
+        n = int(self.arrays.n_tris)
+        tri = np.ascontiguousarray(tri, dtype=np.float32)
+        if tri.size != n * 9:
+            raise ValueError(f"update_geometry: tri has {tri.size} elements, the scene needs {n} x 9")
+        if norm is not None:
+            norm = np.ascontiguousarray(norm, dtype=np.float32)
+            if norm.size != n * 27:
+                raise ValueError(f"update_geometry: norm has {norm.size} elements, the scene needs {n} x 27")
+        L.check(L.lib().fspt_multi_update_geometry(self._m, L.fptr(tri), None if norm is None else L.fptr(norm)))
 
     def clear(self):
         L.check(L.lib().fspt_multi_clear(self._m))

@@ -70,11 +70,9 @@ typedef struct fspt_scene_desc {
   const float *norm;      /* normTex (main.js:383-385): 27 floats per triangle, per vertex n, t, bt                    */
   const float *uv;        /* uvTex (main.js:386): 6 floats per triangle                                                */
   const uint8_t *atlas;   /* texArray (main.js:548-559): RGBA8, atlas_res^2 * atlas_layers texels, layer-major, GL rows */
-  uint32_t atlas_res;
-  uint32_t atlas_layers;
+  uint32_t atlas_res, atlas_layers;
   const uint8_t *env;     /* envTex (main.js:170-180): RGBE in RGBA8, env_w * env_h texels; NULL = black (main.js:303-307) */
-  uint32_t env_w;
-  uint32_t env_h;
+  uint32_t env_w, env_h;
   const uint32_t *bins;   /* radianceBins (tracer.fs:21, env_sampler.js:73): n_bins x (x0,y0,x1,y1); n_bins >= 1       */
   uint32_t n_bins;
   uint32_t leaf_size;     /* '#define LEAF_SIZE' spliced into the shader (main.js:45,895)                              */
@@ -82,10 +80,16 @@ typedef struct fspt_scene_desc {
 
 /* device = HIP device ordinal.  Builds the MI355X-native layouts (64-byte
  * two-child nodes, 144-byte leaf records, 192-byte hit records, material texture sets in 128-byte tiles). */
-int fspt_scene_create(const fspt_scene_desc *desc, int device, fspt_scene **out);
-int fspt_scene_destroy(fspt_scene *scene);
+int fspt_scene_create(const fspt_scene_desc *desc, int device, fspt_scene **out); int fspt_scene_destroy(fspt_scene *scene);
 /* Maximum depth of the uploaded tree (root = 0); sizes the LDS stacks. */
 int fspt_scene_depth(const fspt_scene *scene, uint32_t *depth);
+/* Moving geometry: new vertices (9 floats) and, unless norm is NULL, normTex records (27 floats) for the n_tris
+ * triangles in leaf order; the tree is REFITTED on the GPU (leaf and hit records, every box bottom-up, two-level nodes, light
+ * table) exactly as fspt_scene_create would build it from the same topology.  Non-finite input: FSPT_E_INVALID, scene unchanged;
+ * leaves that do not tile [0, n_tris): FSPT_E_STATE.  Blocking; ordered against every target; accumulators are not cleared. */
+int fspt_scene_update_geometry(fspt_scene *s, const float *tri, const float *norm); /* host pointers */
+int fspt_scene_update_geometry_device(fspt_scene *s, const float *tri, const float *norm); /* memory of the scene's device */
+int fspt_scene_sah_cost(fspt_scene *s, double *cost); /* SAH cost of the current boxes relative to the root's area, float64 */
 
 /* ------------------------------------------------------------------------
  * Render target.  Replaces initBuffers (main.js:598-617): the RGBA32F screen textures (a single accumulator here: each
@@ -93,8 +97,7 @@ int fspt_scene_depth(const fspt_scene *scene, uint32_t *depth);
  * Sharding (SURVEY 8e): tile x tile pixel tiles dealt round-robin (tile index % n_shards == shard); a target traces
  * only its own tiles and leaves every other pixel of its full-size accumulator at zero (a sum over shards = the frame).
  * ---------------------------------------------------------------------- */
-int fspt_target_create(fspt_scene *scene, uint32_t width, uint32_t height, fspt_target **out);
-int fspt_target_destroy(fspt_target *target);
+int fspt_target_create(fspt_scene *scene, uint32_t width, uint32_t height, fspt_target **out); int fspt_target_destroy(fspt_target *target);
 int fspt_target_set_shard(fspt_target *target, uint32_t shard, uint32_t n_shards, uint32_t tile);
 /* Use caller-owned device memory (W*H*4 floats, e.g. a torch tensor) as the accumulator so that a collective can run
  * on it in place; NULL restores the library's own buffer.  The bound buffer is only current after fspt_sync,
@@ -258,8 +261,7 @@ typedef struct fspt_group_material {
   double ior, dielectric;
 } fspt_group_material;
 
-int fspt_builder_create(fspt_builder **out);
-int fspt_builder_destroy(fspt_builder *b);
+int fspt_builder_create(fspt_builder **out); int fspt_builder_destroy(fspt_builder *b);
 /* parseMesh (obj_loader.js:6-215) for one prop: v / vt / vn / f, fan triangulation, negative indices, transforms,
  * normals, tangents. */
 int fspt_builder_add_obj(fspt_builder *b, const char *obj_text, size_t len, const fspt_prop_desc *prop);
@@ -287,10 +289,8 @@ int fspt_builder_get(const fspt_builder *b, float *bvh, float *tri, float *mat, 
  * cap bins (4 uint32 each) and the real count to *n_bins. */
 int fspt_env_bins(const uint8_t *rgbe, uint32_t w, uint32_t h, uint32_t *bins, uint32_t cap, uint32_t *n_bins);
 
-const char *fspt_last_error(void);
-int fspt_abi_version(void);
-/* Number of visible HIP devices (0 when none / no driver). */
-int fspt_device_count(void);
+const char *fspt_last_error(void); int fspt_abi_version(void);
+int fspt_device_count(void); /* visible HIP devices (0 when none / no driver) */
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,8 @@ int fspt_multi_trace(fspt_multi *m, uint32_t tick, float rand_base, float env_th
 int fspt_multi_render(fspt_multi *m, const fspt_camera_params *cam, uint32_t first_tick, uint32_t n_ticks,
                       uint64_t seed);                                       /* fspt_render on every device  */
 int fspt_multi_clear(fspt_multi *m);
+/* fspt_scene_update_geometry (host pointers) on every device's copy of the scene */
+int fspt_multi_update_geometry(fspt_multi *m, const float *tri, const float *norm);
 int fspt_multi_sync(fspt_multi *m);
 /* Gather (see above), then what fspt_read_radiance / fspt_draw do on the assembled frame.  Blocking. */
 int fspt_multi_read_radiance(fspt_multi *m, float *out);

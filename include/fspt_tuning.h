@@ -57,6 +57,9 @@ int fspt_target_set_tail(fspt_target *target, int round);
 int fspt_target_set_node_form(fspt_target *target, int primary, int trace, int tail, int64_t trace_below);
 /* Whether the scene has two-level nodes, and their size in bytes (either pointer may be NULL). */
 int fspt_scene_two_level_nodes(const fspt_scene *scene, int *present, uint64_t *bytes);
+/* The most recent fspt_scene_update_geometry[_device]: GPU time from its first kernel to its last (HIP events; the 4-byte
+ * readback of the finite check lies between them) and the kernels it launched (one per tree level among them). */
+int fspt_scene_last_update_ms(fspt_scene *scene, float *ms, uint32_t *launches);
 /* fspt_intersect (fspt.h) walking the two-level nodes (two_level != 0; FSPT_E_INVALID when the scene has none): t, index
  * and the per-ray step / leaf counts must equal the one-level walk's (tests). */
 int fspt_intersect_form(fspt_scene *scene, int two_level, const float *rays, uint32_t n, float *t_out, int32_t *index_out,
@@ -124,6 +127,9 @@ int fspt_builder_gpu_stats(const fspt_builder *b, float *kernel_ms, uint32_t *la
 /* The built tree's triangle order (n_tris): packed triangle k (fspt_builder_get) is the builder's triangle order[k], in the
  * order the OBJs added them - what a second builder's tree is compared against triangle by triangle. */
 int fspt_builder_tri_order(const fspt_builder *b, uint32_t *order);
+/* The builder's triangles in PARSE order, packed like fspt_builder_get's arrays (9 / 12 / 27 / 6 floats each; NULL = skip);
+ * works before a build: what a host moves and hands to fspt_scene_update_geometry through fspt_builder_tri_order's order. */
+int fspt_builder_geometry(const fspt_builder *b, uint32_t *n_tris, float *tri, float *mat, float *norm, float *uv);
 
 /* ---- test hook ------------------------------------------------------------------------------------------------------ */
 /* Device-side evaluation of the deterministic math primitives (DESIGN.md

@@ -30,14 +30,8 @@ CONFIGS = {"c2": 76, "c3": 289}
 
 
 def sah_cost(arrays):
-    b = arrays.bvh.reshape(-1, 9)
-    w = b[:, :3].view(np.int32)
-    e = b[:, 6:9].astype(np.float64) - b[:, 3:6].astype(np.float64)
-    sa = (e[:, 0] * e[:, 1] + e[:, 0] * e[:, 2] + e[:, 1] * e[:, 2]) * 2
-    leaf = w[:, 2] > -1
-    first = w[leaf, 2]
-    cnt = np.diff(np.concatenate([first, [arrays.n_tris]]))
-    return float((sa[~leaf].sum() + (sa[leaf] * cnt).sum()) / sa[0])
+    from fspt_amd import scene as S
+    return S.sah_cost(arrays)  # (one place: fspt_scene_sah_cost computes the same from a scene's device boxes)
 
 
 def timed_build(n, bvh, device):

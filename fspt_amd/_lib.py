@@ -96,6 +96,10 @@ SIGNATURES = {
     "fspt_scene_sah_cost": (C.c_int, [_VP, C.POINTER(C.c_double)]),
     "fspt_scene_last_update_ms": (C.c_int, [_VP, _F, _U32]),
     "fspt_multi_update_geometry": (C.c_int, [_VP, _F, _F]),
+    "fspt_scene_rebuild_geometry": (C.c_int, [_VP, _F, _F, _U32]),
+    "fspt_scene_rebuild_geometry_device": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "fspt_scene_last_rebuild_ms": (C.c_int, [_VP, _F, _F, _F, _U32, _U32]),
+    "fspt_multi_rebuild_geometry": (C.c_int, [_VP, _F, _F, _U32]),
     "fspt_target_create": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(_VP)]),
     "fspt_target_destroy": (C.c_int, [_VP]),
     "fspt_target_set_viewport": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),

@@ -162,6 +162,146 @@ int light_table_ensure(fspt_scene *s) {
   return FSPT_OK;
 }
 
+// ---- the integer part of fspt_scene_create: what follows from the tree's (left, right, triStart) words alone ----
+namespace {
+struct TreeWords {
+  const char *base; size_t stride;
+  int32_t operator()(uint32_t node, int w) const { int32_t v; std::memcpy(&v, base + (size_t)node * stride + (size_t)w * 4, 4); return v; }
+};
+}
+
+int tree_topology(const void *words, size_t stride_bytes, uint32_t N, uint32_t T, TreeTopology &tp) {
+  const TreeWords word{(const char *)words, stride_bytes};
+  // ---- validate + renumber interior nodes ------------------------------------------
+  // The first TOP_BFS interior nodes in breadth-first order get the lowest numbers (every ray walks the top of
+  // the tree: the traversal kernel keeps a prefix of them in LDS); the rest keep their pre-order.
+  std::vector<int32_t> &ref = tp.ref;
+  std::vector<uint32_t> &leaf_first = tp.leaf_first; // first triangle of every leaf, in node order
+  uint32_t &n_interior = tp.n_interior;
+  ref.assign(N, 0); leaf_first.clear(); n_interior = 0;
+  for (uint32_t i = 0; i < N; ++i) {
+    int32_t l = word(i, 0), r = word(i, 1), ts = word(i, 2);
+    if (ts > -1) {
+      if ((uint32_t)ts > T) { fspt_set_error("node %u: triStart %d > n_tris %u", i, ts, T); return FSPT_E_INVALID; }
+      ref[i] = ~(int32_t)leaf_first.size(); // leaf record index
+      leaf_first.push_back((uint32_t)ts);
+    } else {
+      // serializeTree is pre-order (bvh.js:33-50): children come after their parent.
+      if (l <= (int32_t)i || r <= (int32_t)i || (uint32_t)l >= N || (uint32_t)r >= N) {
+        fspt_set_error("node %u: child indices (%d,%d) violate pre-order / range [%u,%u)", i, l, r, i + 1, N);
+        return FSPT_E_INVALID;
+      }
+      ref[i] = INT32_MAX; // interior, numbered below
+      n_interior++;
+    }
+  }
+  {
+    const uint32_t TOP_BFS = 256;
+    uint32_t next = 0;
+    std::vector<uint32_t> queue;
+    if (N && word(0, 2) <= -1) queue.push_back(0);
+    for (size_t q = 0; q < queue.size() && next < TOP_BFS; ++q) {
+      uint32_t i = queue[q];
+      ref[i] = (int32_t)next++;
+      uint32_t l = (uint32_t)word(i, 0), r = (uint32_t)word(i, 1);
+      if (word(l, 2) <= -1) queue.push_back(l);
+      if (word(r, 2) <= -1) queue.push_back(r);
+    }
+#if FSPT_NODE_TREELET > 1
+    // Below the breadth-first top: TREELETS.  A treelet = a subtree root and its descendants in breadth-first order, up to
+    // FSPT_NODE_TREELET nodes, stored contiguously; the treelets hanging off it follow, depth-first.  A ray that enters
+    // a treelet finds the next few levels of its descent - and the sibling it will pop later - in the same or the next
+    // 128-byte lines, instead of one line per level (pre-order keeps only the LEFT child next to its parent).  Only the
+    // numbering changes: same nodes, same boxes, same traversal order, bit-identical results.
+    {
+      std::vector<uint32_t> roots; // subtree roots waiting to be laid out (a stack: depth-first over treelets)
+      for (size_t q = queue.size(); q-- > 0;)
+        if (ref[queue[q]] == INT32_MAX) roots.push_back(queue[q]); // discovered by the top's BFS but beyond its budget
+      std::vector<uint32_t> local;
+      while (!roots.empty()) {
+        const uint32_t root = roots.back();
+        roots.pop_back();
+        local.assign(1, root);
+        for (size_t q = 0; q < local.size(); ++q) {
+          const uint32_t i = local[q];
+          ref[i] = (int32_t)next++;
+          const uint32_t ch[2] = {(uint32_t)word(i, 0), (uint32_t)word(i, 1)};
+          for (uint32_t c : ch)
+            if (word(c, 2) <= -1 && local.size() < (size_t)FSPT_NODE_TREELET) local.push_back(c);
+        }
+        // children of the treelet's nodes that did not fit: roots of the next treelets (right before left on the
+        // stack, so the left subtree is laid out first, like pre-order)
+        for (size_t q = local.size(); q-- > 0;) {
+          const uint32_t i = local[q];
+          const uint32_t ch[2] = {(uint32_t)word(i, 1), (uint32_t)word(i, 0)};
+          for (uint32_t c : ch)
+            if (word(c, 2) <= -1 && ref[c] == INT32_MAX) roots.push_back(c);
+        }
+      }
+    }
+#endif
+    for (uint32_t i = 0; i < N; ++i)
+      if (ref[i] == INT32_MAX) ref[i] = (int32_t)next++; // (pre-order for whatever is left: nothing, with treelets)
+  }
+  // depth of every node (root 0); a child's depth = parent's + 1
+  tp.depth.assign(N, 0);
+  tp.max_depth = 0;
+  for (uint32_t i = 0; i < N; ++i) {
+    if (word(i, 2) > -1) continue;
+    const int32_t l = word(i, 0), r = word(i, 1);
+    tp.depth[l] = tp.depth[i] + 1;
+    tp.depth[r] = tp.depth[i] + 1;
+    if (tp.depth[i] + 1 > tp.max_depth) tp.max_depth = tp.depth[i] + 1;
+  }
+  return FSPT_OK;
+}
+
+// ---- what fspt_scene_update_geometry needs of a tree (host memory; fspt_internal.hpp) ----
+void tree_refit_tables(const void *words, size_t stride_bytes, uint32_t N, uint32_t T, const TreeTopology &tp, fspt_scene::Refit &R) {
+  const TreeWords word{(const char *)words, stride_bytes};
+  const std::vector<int32_t> &ref = tp.ref;
+  const std::vector<uint32_t> &leaf_first = tp.leaf_first, &depth = tp.depth;
+  const size_t n_leaves = leaf_first.size();
+  const uint32_t max_depth = tp.max_depth;
+  R.lvl_nodes.clear();
+  const uint32_t NO = fspt_scene::Refit::NO_DST;
+  R.ok = true;
+  R.node_dst.assign(N, NO);
+  R.node_owned.assign(N, NO);
+  for (uint32_t i = 0; i < N; ++i) {
+    if (word(i, 2) > -1) continue;
+    const uint32_t ch[2] = {(uint32_t)word(i, 0), (uint32_t)word(i, 1)};
+    for (uint32_t k = 0; k < 2; ++k) {
+      if (R.node_dst[ch[k]] != NO || (k == 1 && ch[1] == ch[0])) R.ok = false; // a node with two parents
+      R.node_dst[ch[k]] = 2u * (uint32_t)ref[i] + k;
+    }
+  }
+  // ownership: a leaf owns [triStart, the next larger triStart among the leaves, or n_tris)
+  std::vector<uint32_t> by_first(n_leaves);
+  for (size_t L = 0; L < n_leaves; ++L) by_first[L] = (uint32_t)L;
+  std::sort(by_first.begin(), by_first.end(), [&](uint32_t a, uint32_t b) { return leaf_first[a] < leaf_first[b]; });
+  R.leaf_first = leaf_first;
+  R.leaf_cnt.assign(n_leaves, 0u);
+  R.leaf_dst.assign(n_leaves, NO);
+  for (size_t q = 0; q < n_leaves; ++q) {
+    const uint32_t a = leaf_first[by_first[q]], b = q + 1 < n_leaves ? leaf_first[by_first[q + 1]] : T;
+    if (q + 1 < n_leaves && a == b) R.ok = false; // two leaves with the same range
+    R.leaf_cnt[by_first[q]] = b - a;
+  }
+  if (!n_leaves || leaf_first[by_first[0]] != 0u) R.ok = false; // triangles below the first triStart belong to no leaf
+  std::vector<std::vector<uint32_t>> levels(max_depth + 1);
+  for (uint32_t i = 0; i < N; ++i) {
+    if (word(i, 2) > -1) { const uint32_t L = (uint32_t)~ref[i]; R.leaf_dst[L] = R.node_dst[i]; R.node_owned[i] = R.leaf_cnt[L]; }
+    else if (i > 0 && R.node_dst[i] != NO) { levels[depth[i]].push_back((uint32_t)ref[i]); levels[depth[i]].push_back(R.node_dst[i]); }
+  }
+  R.lvl_off.assign(1, 0u);
+  for (size_t dpt = levels.size(); dpt-- > 0;) {
+    if (levels[dpt].empty()) continue;
+    R.lvl_nodes.insert(R.lvl_nodes.end(), levels[dpt].begin(), levels[dpt].end());
+    R.lvl_off.push_back((uint32_t)(R.lvl_nodes.size() / 2));
+  }
+}
+
 extern "C" {
 
 int fspt_light_alias_table(const float *weights, uint32_t n, float *prob, uint32_t *alias) {
@@ -243,87 +383,16 @@ int fspt_scene_create(const fspt_scene_desc *desc, int device, fspt_scene **out)
     std::memcpy(&v, desc->bvh + (size_t)node * 9 + w, 4);
     return v;
   };
-  // ---- validate + renumber interior nodes ------------------------------------------
-  // The first TOP_BFS interior nodes in breadth-first order get the lowest numbers (every ray walks the top of
-  // the tree: the traversal kernel keeps a prefix of them in LDS); the rest keep their pre-order.
-  std::vector<int32_t> ref(N);
-  std::vector<uint32_t> leaf_first; // first triangle of every leaf, in node order
-  uint32_t n_interior = 0;
-  for (uint32_t i = 0; i < N; ++i) {
-    int32_t l = word(i, 0), r = word(i, 1), ts = word(i, 2);
-    if (ts > -1) {
-      if ((uint32_t)ts > T) { fspt_set_error("node %u: triStart %d > n_tris %u", i, ts, T); return FSPT_E_INVALID; }
-      ref[i] = ~(int32_t)leaf_first.size(); // leaf record index
-      leaf_first.push_back((uint32_t)ts);
-    } else {
-      // serializeTree is pre-order (bvh.js:33-50): children come after their parent.
-      if (l <= (int32_t)i || r <= (int32_t)i || (uint32_t)l >= N || (uint32_t)r >= N) {
-        fspt_set_error("node %u: child indices (%d,%d) violate pre-order / range [%u,%u)", i, l, r, i + 1, N);
-        return FSPT_E_INVALID;
-      }
-      ref[i] = INT32_MAX; // interior, numbered below
-      n_interior++;
-    }
-  }
-  {
-    const uint32_t TOP_BFS = 256;
-    uint32_t next = 0;
-    std::vector<uint32_t> queue;
-    if (N && word(0, 2) <= -1) queue.push_back(0);
-    for (size_t q = 0; q < queue.size() && next < TOP_BFS; ++q) {
-      uint32_t i = queue[q];
-      ref[i] = (int32_t)next++;
-      uint32_t l = (uint32_t)word(i, 0), r = (uint32_t)word(i, 1);
-      if (word(l, 2) <= -1) queue.push_back(l);
-      if (word(r, 2) <= -1) queue.push_back(r);
-    }
-#if FSPT_NODE_TREELET > 1
-    // Below the breadth-first top: TREELETS.  A treelet = a subtree root and its descendants in breadth-first order, up to
-    // FSPT_NODE_TREELET nodes, stored contiguously; the treelets hanging off it follow, depth-first.  A ray that enters
-    // a treelet finds the next few levels of its descent - and the sibling it will pop later - in the same or the next
-    // 128-byte lines, instead of one line per level (pre-order keeps only the LEFT child next to its parent).  Only the
-    // numbering changes: same nodes, same boxes, same traversal order, bit-identical results.
-    {
-      std::vector<uint32_t> roots; // subtree roots waiting to be laid out (a stack: depth-first over treelets)
-      for (size_t q = queue.size(); q-- > 0;)
-        if (ref[queue[q]] == INT32_MAX) roots.push_back(queue[q]); // discovered by the top's BFS but beyond its budget
-      std::vector<uint32_t> local;
-      while (!roots.empty()) {
-        const uint32_t root = roots.back();
-        roots.pop_back();
-        local.assign(1, root);
-        for (size_t q = 0; q < local.size(); ++q) {
-          const uint32_t i = local[q];
-          ref[i] = (int32_t)next++;
-          const uint32_t ch[2] = {(uint32_t)word(i, 0), (uint32_t)word(i, 1)};
-          for (uint32_t c : ch)
-            if (word(c, 2) <= -1 && local.size() < (size_t)FSPT_NODE_TREELET) local.push_back(c);
-        }
-        // children of the treelet's nodes that did not fit: roots of the next treelets (right before left on the
-        // stack, so the left subtree is laid out first, like pre-order)
-        for (size_t q = local.size(); q-- > 0;) {
-          const uint32_t i = local[q];
-          const uint32_t ch[2] = {(uint32_t)word(i, 1), (uint32_t)word(i, 0)};
-          for (uint32_t c : ch)
-            if (word(c, 2) <= -1 && ref[c] == INT32_MAX) roots.push_back(c);
-        }
-      }
-    }
-#endif
-    for (uint32_t i = 0; i < N; ++i)
-      if (ref[i] == INT32_MAX) ref[i] = (int32_t)next++; // (pre-order for whatever is left: nothing, with treelets)
-  }
+  TreeTopology tp;
+  { int rc_t = tree_topology(desc->bvh, 36, N, T, tp); if (rc_t) return rc_t; }
+  const std::vector<int32_t> &ref = tp.ref;
+  const std::vector<uint32_t> &leaf_first = tp.leaf_first;
+  const uint32_t n_interior = tp.n_interior, max_depth = tp.max_depth;
   std::vector<float> nodes((size_t)(n_interior ? n_interior : 1) * 16, 0.0f);
-  // depth of every node (root 0); a child's depth = parent's + 1
-  std::vector<uint32_t> depth(N, 0);
-  uint32_t max_depth = 0;
   for (uint32_t i = 0; i < N; ++i) {
     int32_t ts = word(i, 2);
     if (ts > -1) continue;
     int32_t l = word(i, 0), r = word(i, 1);
-    depth[l] = depth[i] + 1;
-    depth[r] = depth[i] + 1;
-    if (depth[i] + 1 > max_depth) max_depth = depth[i] + 1;
     float *n = &nodes[(size_t)ref[i] * 16];
     const float *lb = desc->bvh + (size_t)l * 9 + 3, *rb = desc->bvh + (size_t)r * 9 + 3;
     n[0] = lb[0]; n[1] = lb[1]; n[2] = lb[3]; n[3] = lb[4];   // lmin.xy lmax.xy
@@ -606,46 +675,7 @@ int fspt_scene_create(const fspt_scene_desc *desc, int device, fspt_scene **out)
   s->n_interior = n_interior;
   s->has_dielectric = has_dielectric;
   s->n_slots = n_slots;
-  // ---- what fspt_scene_update_geometry needs of this tree (host memory; fspt_internal.hpp) ----
-  {
-    fspt_scene::Refit &R = s->rf;
-    const uint32_t NO = fspt_scene::Refit::NO_DST;
-    R.ok = true;
-    R.node_dst.assign(N, NO);
-    R.node_owned.assign(N, NO);
-    for (uint32_t i = 0; i < N; ++i) {
-      if (word(i, 2) > -1) continue;
-      const uint32_t ch[2] = {(uint32_t)word(i, 0), (uint32_t)word(i, 1)};
-      for (uint32_t k = 0; k < 2; ++k) {
-        if (R.node_dst[ch[k]] != NO || (k == 1 && ch[1] == ch[0])) R.ok = false; // a node with two parents
-        R.node_dst[ch[k]] = 2u * (uint32_t)ref[i] + k;
-      }
-    }
-    // ownership: a leaf owns [triStart, the next larger triStart among the leaves, or n_tris)
-    std::vector<uint32_t> by_first(n_leaves);
-    for (size_t L = 0; L < n_leaves; ++L) by_first[L] = (uint32_t)L;
-    std::sort(by_first.begin(), by_first.end(), [&](uint32_t a, uint32_t b) { return leaf_first[a] < leaf_first[b]; });
-    R.leaf_first = leaf_first;
-    R.leaf_cnt.assign(n_leaves, 0u);
-    R.leaf_dst.assign(n_leaves, NO);
-    for (size_t q = 0; q < n_leaves; ++q) {
-      const uint32_t a = leaf_first[by_first[q]], b = q + 1 < n_leaves ? leaf_first[by_first[q + 1]] : T;
-      if (q + 1 < n_leaves && a == b) R.ok = false; // two leaves with the same range
-      R.leaf_cnt[by_first[q]] = b - a;
-    }
-    if (!n_leaves || leaf_first[by_first[0]] != 0u) R.ok = false; // triangles below the first triStart belong to no leaf
-    std::vector<std::vector<uint32_t>> levels(max_depth + 1);
-    for (uint32_t i = 0; i < N; ++i) {
-      if (word(i, 2) > -1) { const uint32_t L = (uint32_t)~ref[i]; R.leaf_dst[L] = R.node_dst[i]; R.node_owned[i] = R.leaf_cnt[L]; }
-      else if (i > 0 && R.node_dst[i] != NO) { levels[depth[i]].push_back((uint32_t)ref[i]); levels[depth[i]].push_back(R.node_dst[i]); }
-    }
-    R.lvl_off.assign(1, 0u);
-    for (size_t dpt = levels.size(); dpt-- > 0;) {
-      if (levels[dpt].empty()) continue;
-      R.lvl_nodes.insert(R.lvl_nodes.end(), levels[dpt].begin(), levels[dpt].end());
-      R.lvl_off.push_back((uint32_t)(R.lvl_nodes.size() / 2));
-    }
-  }
+  tree_refit_tables(desc->bvh, 36, N, T, tp, s->rf);
   *out = s;
   return FSPT_OK;
 }
@@ -1391,6 +1421,37 @@ extern "C" {
 // ---------------------------------------------------------------------------
 // in-place geometry update (kernels in fspt_refit.hip)
 // ---------------------------------------------------------------------------
+// Orders a geometry call against every target of the scene, then leaves the device idle.
+static int geometry_order_targets(fspt_scene *s) {
+  int rc = FSPT_OK;
+  // every earlier call on any target of the scene sees the old geometry: run the recorded ticks (which joins a present
+  // frame in flight), then wait for the device - the update's kernels run on the NULL stream and are waited for, so every
+  // later call sees the new one
+  // (a target under fspt_present keeps its frame in flight: its recorded ticks are enqueued the present way, without a
+  // join, so the next fspt_present still returns the pre-update frame)
+  for (fspt_target *t : s->targets) {
+    if (t->pr_active) { t->pr_dirty = true; rc = present_flush(t); if (rc) return rc; }
+    else FLUSH_OR_RETURN(t);
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  return FSPT_OK;
+}
+
+static int geometry_changed_lights(fspt_scene *s) {
+  int rc = FSPT_OK;
+  // the emitter light table depends on the triangles' areas: release it; light_table_ensure rebuilds it from the device arrays
+  if (s->lights_built) {
+    hipFree(s->l_alias); hipFree(s->l_rec); hipFree(s->l_p); hipFree(s->l_pick);
+    s->l_alias = s->l_rec = s->l_p = s->l_pick = nullptr;
+    s->d.light_alias = nullptr; s->d.light_rec = nullptr; s->d.light_p = nullptr; s->d.light_pick = nullptr;
+    s->d.n_lights = 0;
+    s->lights_built = false;
+  }
+  for (fspt_target *t : s->targets)
+    if (t->lights == FSPT_LIGHTS_EMITTERS) { rc = light_table_ensure(s); if (rc) return rc; break; }
+  return FSPT_OK;
+}
+
 static int update_geometry(fspt_scene *s, const float *tri, const float *norm, bool on_device, const char *fn) {
   if (!s || !tri) { fspt_set_error("%s: NULL scene or tri", fn); return FSPT_E_INVALID; }
   if (!on_device) { // the host form's check needs no device: refuse before anything is touched
@@ -1404,16 +1465,8 @@ static int update_geometry(fspt_scene *s, const float *tri, const float *norm, b
   }
   int rc = check_device(s->device);
   if (rc) return rc;
-  // every earlier call on any target of the scene sees the old geometry: run the recorded ticks (which joins a present
-  // frame in flight), then wait for the device - the update's kernels run on the NULL stream and are waited for, so every
-  // later call sees the new one
-  // (a target under fspt_present keeps its frame in flight: its recorded ticks are enqueued the present way, without a
-  // join, so the next fspt_present still returns the pre-update frame)
-  for (fspt_target *t : s->targets) {
-    if (t->pr_active) { t->pr_dirty = true; rc = present_flush(t); if (rc) return rc; }
-    else FLUSH_OR_RETURN(t);
-  }
-  HIP_TRY(hipDeviceSynchronize());
+  rc = geometry_order_targets(s);
+  if (rc) return rc;
   rc = fspt::refit_prepare(s);
   if (rc) return rc;
   const size_t T = s->n_tris;
@@ -1432,17 +1485,7 @@ static int update_geometry(fspt_scene *s, const float *tri, const float *norm, b
   if (rc) return rc;
   if (!finite) { fspt_set_error("%s: a value of tri / norm is not finite (scene unchanged)", fn); return FSPT_E_INVALID; }
   s->d.quads = quads_ok ? (const float4 *)s->quads : nullptr;
-  // the emitter light table depends on the triangles' areas: release it; light_table_ensure rebuilds it from the device arrays
-  if (s->lights_built) {
-    hipFree(s->l_alias); hipFree(s->l_rec); hipFree(s->l_p); hipFree(s->l_pick);
-    s->l_alias = s->l_rec = s->l_p = s->l_pick = nullptr;
-    s->d.light_alias = nullptr; s->d.light_rec = nullptr; s->d.light_p = nullptr; s->d.light_pick = nullptr;
-    s->d.n_lights = 0;
-    s->lights_built = false;
-  }
-  for (fspt_target *t : s->targets)
-    if (t->lights == FSPT_LIGHTS_EMITTERS) { rc = light_table_ensure(s); if (rc) return rc; break; }
-  return FSPT_OK;
+  return geometry_changed_lights(s);
 }
 
 int fspt_scene_update_geometry(fspt_scene *s, const float *tri, const float *norm) {
@@ -1457,6 +1500,77 @@ int fspt_scene_last_update_ms(fspt_scene *s, float *ms, uint32_t *launches) {
   if (!s) { fspt_set_error("fspt_scene_last_update_ms: NULL scene"); return FSPT_E_INVALID; }
   if (ms) *ms = s->rf.last_ms;
   if (launches) *launches = s->rf.last_launches;
+  return FSPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// in-place rebuild (fspt_refit.hip rebuild_run)
+// ---------------------------------------------------------------------------
+static int rebuild_geometry(fspt_scene *s, const float *tri, const float *norm, uint32_t *order_out, bool on_device, const char *fn) {
+  if (!s || !tri) { fspt_set_error("%s: NULL scene or tri", fn); return FSPT_E_INVALID; }
+  if (!on_device) {
+    const size_t n = (size_t)s->n_tris * 9, m = norm ? (size_t)s->n_tris * 27 : 0;
+    for (size_t i = 0; i < n; ++i) if (!std::isfinite(tri[i])) { fspt_set_error("%s: tri[%zu] is not finite", fn, i); return FSPT_E_INVALID; }
+    for (size_t i = 0; i < m; ++i) if (!std::isfinite(norm[i])) { fspt_set_error("%s: norm[%zu] is not finite", fn, i); return FSPT_E_INVALID; }
+  }
+  // the triangle -> old slot map needs every triangle in a slot of the leaf that owns it
+  bool mapped = s->rf.ok;
+  for (size_t L = 0; mapped && L < s->rf.leaf_cnt.size(); ++L) mapped = s->rf.leaf_cnt[L] <= s->d.leaf_size;
+  if (!mapped) {
+    fspt_set_error("%s: scene is not refittable (the leaves' triStarts must be distinct and tile [0, n_tris) in steps of at most leaf_size, every node have one parent)", fn);
+    return FSPT_E_STATE;
+  }
+  struct Restore { int prev = -1; ~Restore() { if (prev >= 0) (void)hipSetDevice(prev); } } restore; // the caller's current device stays
+  if (hipGetDevice(&restore.prev) != hipSuccess) restore.prev = -1;
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  rc = geometry_order_targets(s);
+  if (rc) return rc;
+  rc = fspt::refit_prepare(s);
+  if (rc) return rc;
+  const size_t T = s->n_tris;
+  if (!on_device) {
+    if (!s->rf.stage) HIP_TRY(hipMalloc((void **)&s->rf.stage, T * 36 * 4));
+    HIP_TRY(hipMemcpy(s->rf.stage, tri, T * 9 * 4, hipMemcpyHostToDevice));
+    if (norm) HIP_TRY(hipMemcpy(s->rf.stage + T * 9, norm, T * 27 * 4, hipMemcpyHostToDevice));
+    tri = s->rf.stage;
+    if (norm) norm = s->rf.stage + T * 9;
+  } else {
+    int finite = 1;
+    rc = fspt::refit_check(s, tri, norm, &finite);
+    if (rc) return rc;
+    if (!finite) { fspt_set_error("%s: a value of tri / norm is not finite (scene unchanged)", fn); return FSPT_E_INVALID; }
+  }
+  rc = fspt::rebuild_run(s, tri, norm, order_out, on_device);
+  if (rc) return rc;
+  // Every target now behaves like one created after the rebuild.  The DScene (arrays, root_ref, stack_n, n_top, quads) is
+  // copied from the scene at every launch, and the LDS stack, the launch shapes and the node form are computed from it
+  // there; the suspended-traversal records are re-made by susp_ensure when stack_n changed their stride.  What a target
+  // MEASURED on the old tree is forgotten: the primary-form timings, the live-path fractions behind the tail hand-over and
+  // the stream scheduler's run statistics.  Accumulators, path state and settings stay.
+  for (fspt_target *t : s->targets) {
+    prim_reset(t);
+    t->live_known = false;
+    for (fspt_target::WfLane *ln : {&t->wf, &t->pr_lane}) { ln->counts_pending = false; ln->ctl_pending = false; ln->stat_key = 0; ln->stat_gen_iters = 0; }
+  }
+  return geometry_changed_lights(s);
+}
+
+int fspt_scene_rebuild_geometry(fspt_scene *s, const float *tri, const float *norm, uint32_t *order_out) {
+  return rebuild_geometry(s, tri, norm, order_out, false, "fspt_scene_rebuild_geometry");
+}
+
+int fspt_scene_rebuild_geometry_device(fspt_scene *s, const float *tri, const float *norm, uint32_t *order_out) {
+  return rebuild_geometry(s, tri, norm, order_out, true, "fspt_scene_rebuild_geometry_device");
+}
+
+int fspt_scene_last_rebuild_ms(fspt_scene *s, float *build_ms, float *install_ms, float *host_ms, uint32_t *launches, uint32_t *readbacks) {
+  if (!s) { fspt_set_error("fspt_scene_last_rebuild_ms: NULL scene"); return FSPT_E_INVALID; }
+  if (build_ms) *build_ms = s->rb.build_ms;
+  if (install_ms) *install_ms = s->rb.install_ms;
+  if (host_ms) *host_ms = s->rb.host_ms;
+  if (launches) *launches = s->rb.launches;
+  if (readbacks) *readbacks = s->rb.readbacks;
   return FSPT_OK;
 }
 

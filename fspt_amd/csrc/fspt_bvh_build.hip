@@ -537,26 +537,17 @@ struct StreamGuard {
 
 }  // namespace
 
-int bvh_build_gpu(const float *verts, uint32_t n, uint32_t leaf_size, int device, BvhGpuResult &out) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-    fspt_set_error("fspt_builder_build_gpu: no HIP device available");
-    return FSPT_E_NO_DEVICE;
-  }
-  if (device >= count) { fspt_set_error("fspt_builder_build_gpu: device %d out of range (have %d)", device, count); return FSPT_E_INVALID; }
-  DeviceRestore restore;
-  HIP_TRY(hipGetDevice(&restore.prev));
-  HIP_TRY(hipSetDevice(device));
+// The build proper, on the current device: vertices from host memory (uploaded on the build's stream) or already on the
+// device; the tree stays in B's buffers (D) with *nn nodes.  One stream, waited for before it returns.
+static int build_core(const float *verts_host, const float *verts_dev, uint32_t n, uint32_t leaf_size, DevBufs &B, StreamGuard &G, Dev &D,
+                      uint32_t *nn_out, float *kernel_ms, uint32_t *launches_out, uint32_t *readbacks_out) {
   const uint32_t max_depth = bvh_max_depth();
-  out.launches = 0;
-  out.readbacks = 0;
-  DevBufs B;
-  Dev D{};
+  uint32_t launches = 0, readbacks = 0;
   const size_t N = n, NN = 2 * N;  // a binary tree with at most n leaves has fewer than 2n nodes
   const size_t max_large = N / SMALL + 1, max_chunks = (N + CHUNK - 1) / CHUNK + max_large;
   Prim *prim;
-  float *verts_d;
-  HIP_TRY(B.alloc(&verts_d, N * 9));
+  float *verts_d = nullptr;
+  if (verts_host) HIP_TRY(B.alloc(&verts_d, N * 9));
   HIP_TRY(B.alloc(&prim, N));
   HIP_TRY(B.alloc(&D.order[0], N));
   HIP_TRY(B.alloc(&D.order[1], N));
@@ -576,20 +567,19 @@ int bvh_build_gpu(const float *verts, uint32_t n, uint32_t leaf_size, int device
   HIP_TRY(B.alloc(&D.chunk_left, max_chunks));
   HIP_TRY(B.alloc(&D.dec, max_large));
   HIP_TRY(B.alloc(&D.ctr, 4));
-  D.verts = verts_d;
+  D.verts = verts_host ? verts_d : verts_dev;
   D.prim = prim;
   D.n = n;
   D.leaf_size = leaf_size;
   D.max_depth = max_depth;
-  StreamGuard G;
   HIP_TRY(hipStreamCreateWithFlags(&G.s, hipStreamNonBlocking));
   HIP_TRY(hipEventCreate(&G.ev[0]));
   HIP_TRY(hipEventCreate(&G.ev[1]));
-  HIP_TRY(hipMemcpyAsync(verts_d, verts, N * 9 * sizeof(float), hipMemcpyHostToDevice, G.s));
+  if (verts_host) HIP_TRY(hipMemcpyAsync(verts_d, verts_host, N * 9 * sizeof(float), hipMemcpyHostToDevice, G.s));
   HIP_TRY(hipEventRecord(G.ev[0], G.s));
   hipLaunchKernelGGL(k_prep, dim3((unsigned)((N + BT - 1) / BT)), dim3(BT), 0, G.s, D);
   HIP_TRY(hipGetLastError());
-  out.launches++;
+  launches++;
   uint32_t m_count = n > SMALL ? 1u : 0u;
   int cur = 0;
   while (m_count > 0) {
@@ -601,28 +591,54 @@ int bvh_build_gpu(const float *verts, uint32_t n, uint32_t leaf_size, int device
     hipLaunchKernelGGL(k_chunk_count, dim3(grid_c), dim3(BT), 0, G.s, D, cur, m_count);
     hipLaunchKernelGGL(k_chunk_scatter, dim3(grid_c), dim3(BT), 0, G.s, D, cur, m_count);
     HIP_TRY(hipGetLastError());
-    out.launches += 6;
+    launches += 6;
     HIP_TRY(hipMemcpyAsync(&m_count, D.ctr + 2, 4, hipMemcpyDeviceToHost, G.s));
     HIP_TRY(hipStreamSynchronize(G.s));
-    out.readbacks++;
+    readbacks++;
     if (m_count > max_large) { fspt_set_error("fspt_builder_build_gpu: level list overflow (%u)", m_count); return FSPT_E_HIP; }
     cur ^= 1;
   }
   uint32_t ctr[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(ctr, D.ctr, 8, hipMemcpyDeviceToHost, G.s));
   HIP_TRY(hipStreamSynchronize(G.s));
-  out.readbacks++;
+  readbacks++;
   if (ctr[1] > 0) {
     hipLaunchKernelGGL(k_finish, dim3(ctr[1]), dim3(BT), 0, G.s, D);
     HIP_TRY(hipGetLastError());
-    out.launches++;
+    launches++;
   }
   HIP_TRY(hipEventRecord(G.ev[1], G.s));
   HIP_TRY(hipMemcpyAsync(ctr, D.ctr, 4, hipMemcpyDeviceToHost, G.s));
   HIP_TRY(hipStreamSynchronize(G.s));
-  out.readbacks++;
+  readbacks++;
   const uint32_t nn = ctr[0];
   if (nn == 0 || nn >= NN) { fspt_set_error("fspt_builder_build_gpu: node count %u out of range", nn); return FSPT_E_HIP; }
+  HIP_TRY(hipEventElapsedTime(kernel_ms, G.ev[0], G.ev[1]));
+  *nn_out = nn;
+  *launches_out = launches;
+  *readbacks_out = readbacks;
+  return FSPT_OK;
+}
+
+int bvh_build_gpu(const float *verts, uint32_t n, uint32_t leaf_size, int device, BvhGpuResult &out) {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
+    fspt_set_error("fspt_builder_build_gpu: no HIP device available");
+    return FSPT_E_NO_DEVICE;
+  }
+  if (device >= count) { fspt_set_error("fspt_builder_build_gpu: device %d out of range (have %d)", device, count); return FSPT_E_INVALID; }
+  DeviceRestore restore;
+  HIP_TRY(hipGetDevice(&restore.prev));
+  HIP_TRY(hipSetDevice(device));
+  out.launches = 0;
+  out.readbacks = 0;
+  DevBufs B;
+  Dev D{};
+  StreamGuard G;
+  uint32_t nn = 0;
+  const int rc = build_core(verts, nullptr, n, leaf_size, B, G, D, &nn, &out.kernel_ms, &out.launches, &out.readbacks);
+  if (rc) return rc;
+  const size_t N = n;
   out.left.resize(nn); out.right.resize(nn); out.lo.resize(nn); out.cnt.resize(nn); out.box_keys.resize((size_t)nn * 12);
   out.order.resize(N);
   HIP_TRY(hipMemcpyAsync(out.left.data(), D.node_left, nn * 4, hipMemcpyDeviceToHost, G.s));
@@ -633,8 +649,56 @@ int bvh_build_gpu(const float *verts, uint32_t n, uint32_t leaf_size, int device
   HIP_TRY(hipMemcpyAsync(out.order.data(), D.order_final, N * 4, hipMemcpyDeviceToHost, G.s));
   HIP_TRY(hipStreamSynchronize(G.s));
   out.readbacks++;
-  HIP_TRY(hipEventElapsedTime(&out.kernel_ms, G.ev[0], G.ev[1]));
   return FSPT_OK;
+}
+
+int bvh_build_device(const float *verts_dev, uint32_t n, uint32_t leaf_size, BvhGpuDevice &out) {
+  DevBufs *B = new DevBufs();
+  Dev D{};
+  StreamGuard G;
+  const int rc = build_core(nullptr, verts_dev, n, leaf_size, *B, G, D, &out.n_nodes, &out.kernel_ms, &out.launches, &out.readbacks);
+  if (rc) { delete B; return rc; }
+  out.order = D.order_final; out.lo = D.node_lo; out.cnt = D.node_n; out.left = D.node_left; out.right = D.node_right;
+  out.bufs = B;
+  return FSPT_OK;
+}
+
+void bvh_device_release(BvhGpuDevice &t) {
+  delete (DevBufs *)t.bufs;
+  t = BvhGpuDevice{};
+}
+
+const char *bvh_preorder(const int32_t *left, const int32_t *right, const uint32_t *lo, const uint32_t *cnt, size_t nn, size_t nt,
+                         uint32_t leaf_size, std::vector<int32_t> &pre, std::vector<uint32_t> &gid, std::vector<uint32_t> &node_depth,
+                         uint32_t *depth_out) {
+  pre.assign(nn, -1);
+  gid.clear(); node_depth.clear();
+  gid.reserve(nn); node_depth.reserve(nn);
+  std::vector<std::pair<uint32_t, uint32_t>> st{{0u, 0u}};
+  uint32_t depth = 0, next_lo = 0;
+  while (!st.empty()) {
+    const uint32_t g = st.back().first, d = st.back().second;
+    st.pop_back();
+    if (g >= nn || pre[g] >= 0) return "node visited twice or out of range";
+    pre[g] = (int32_t)gid.size();
+    gid.push_back(g);
+    node_depth.push_back(d);
+    depth = std::max(depth, d);
+    const uint32_t hi = lo[g] + cnt[g];
+    if (hi < lo[g] || hi > nt) return "range";
+    if (left[g] < 0) {
+      if (lo[g] != next_lo || cnt[g] == 0 || cnt[g] > leaf_size) return "leaf range";
+      next_lo = hi;
+    } else {
+      if (right[g] < 0) return "children";
+      st.push_back({(uint32_t)right[g], d + 1});
+      st.push_back({(uint32_t)left[g], d + 1});
+    }
+  }
+  if (gid.size() != nn || next_lo != nt) return "coverage";
+  if (depth > bvh_max_depth()) return "depth";
+  *depth_out = depth;
+  return nullptr;
 }
 
 float bvh_key_float(uint32_t k) { return kfloat(k); }

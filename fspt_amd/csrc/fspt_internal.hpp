@@ -77,13 +77,32 @@ struct fspt_scene {
     float last_ms = 0.0f;             // kernels of the last update, first to last
     uint32_t last_launches = 0;
   } rf;
+  // the most recent fspt_scene_rebuild_geometry (fspt_scene_last_rebuild_ms)
+  struct Rebuild { float build_ms = 0.0f, install_ms = 0.0f, host_ms = 0.0f; uint32_t launches = 0, readbacks = 0; } rb;
 };
+// What fspt_scene_create derives from the reference tree's three integer words per node (left, right, triStart; a node
+// with triStart > -1 is a leaf) and nothing else: shared with fspt_scene_rebuild_geometry, which gets its words from the
+// GPU builder.  `words` + i * stride = node i's words (any alignment).
+struct TreeTopology {
+  std::vector<int32_t> ref;         // per reference node: its native index (interior: breadth-first top, then treelets) or ~(leaf record)
+  std::vector<uint32_t> leaf_first; // per leaf record: its first triangle
+  std::vector<uint32_t> depth;      // per reference node (root 0)
+  uint32_t n_interior = 0, max_depth = 0;
+};
+int tree_topology(const void *words, size_t stride_bytes, uint32_t N, uint32_t T, TreeTopology &tp); // validates; FSPT_E_INVALID
+void tree_refit_tables(const void *words, size_t stride_bytes, uint32_t N, uint32_t T, const TreeTopology &tp, fspt_scene::Refit &R);
 namespace fspt { // fspt_refit.hip
 int refit_prepare(fspt_scene *s);  // the device copies of s->rf (idempotent)
 void refit_release(fspt_scene *s);
 // tri / norm (may be NULL): device memory.  *finite = 0: a non-finite value, nothing written.  *quads_ok: the rebuilt
 // two-level nodes (s->quads, must be allocated) are usable.  Runs on the NULL stream and waits for it.
 int refit_run(fspt_scene *s, const float *tri, const float *norm, int *finite, int *quads_ok);
+// k_refit_check alone (s->rf prepared): *finite = 0 when a word of tri / norm (device memory) is inf or NaN
+int refit_check(fspt_scene *s, const float *tri, const float *norm, int *finite);
+// fspt_scene_rebuild_geometry's device side: a new tree over tri (device memory, the scene's leaf order), built
+// by fspt_bvh_build.hip's kernels and installed in `s`; the scene is untouched unless FSPT_OK comes back.  The caller has
+// ordered the call against the targets, prepared s->rf and checked tri / norm.  order_out: NULL, host or device memory.
+int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *order_out, bool order_on_device);
 }
 int light_table_ensure(fspt_scene *s); // (fspt_api.cpp) builds the table once; FSPT_OK when it exists
 #ifndef FSPT_LIGHTS_ENV_Q_MAX
@@ -343,6 +362,24 @@ struct BvhGpuResult {
 };
 // n > 0 triangles of 9 finite floats, 1 <= leaf_size <= 64, device >= 0; leaves the calling thread's device as it was.
 int bvh_build_gpu(const float *verts, uint32_t n, uint32_t leaf_size, int device, BvhGpuResult &out);
+// The same kernels from vertices that are already on the CURRENT device, the result left there: `order` (n words) and, per
+// node, left / right / lo / cnt (n_nodes words each; node 0 is the root).  bvh_device_release frees it.
+struct BvhGpuDevice {
+  const uint32_t *order = nullptr, *lo = nullptr, *cnt = nullptr;
+  const int32_t *left = nullptr, *right = nullptr;
+  uint32_t n_nodes = 0;
+  float kernel_ms = 0.0f;
+  uint32_t launches = 0, readbacks = 0;
+  void *bufs = nullptr;
+};
+int bvh_build_device(const float *verts_dev, uint32_t n, uint32_t leaf_size, BvhGpuDevice &out);
+void bvh_device_release(BvhGpuDevice &t);
+// Pre-order numbering (left child first) of a builder tree of nn nodes over nt triangles: gid[p] = the builder's id of
+// pre-order node p, pre[] its inverse, node_depth[p], *depth the deepest.  Checks that it is one tree whose leaves hold
+// 1 .. leaf_size triangles and tile [0, nt) in pre-order; returns what is wrong, or NULL.
+const char *bvh_preorder(const int32_t *left, const int32_t *right, const uint32_t *lo, const uint32_t *cnt, size_t nn, size_t nt,
+                         uint32_t leaf_size, std::vector<int32_t> &pre, std::vector<uint32_t> &gid, std::vector<uint32_t> &node_depth,
+                         uint32_t *depth);
 float bvh_key_float(uint32_t k);
 uint32_t bvh_max_depth(); // deepest node depth fspt_scene_create accepts: min(64, wf_max_stack_entries()) - 1
 }  // namespace fspt

@@ -217,6 +217,19 @@ int fspt_multi_update_geometry(fspt_multi *m, const float *tri, const float *nor
   }
   return FSPT_OK;
 }
+int fspt_multi_rebuild_geometry(fspt_multi *m, const float *tri, const float *norm, uint32_t *order_out) {
+  if (!m) { fspt_set_error("fspt_multi_rebuild_geometry: NULL handle"); return FSPT_E_INVALID; }
+  std::vector<uint32_t> first, other;
+  for (fspt_scene *s : m->scenes) { // (a bad array is refused by the first scene, before anything is written)
+    std::vector<uint32_t> &o = first.empty() ? first : other;
+    o.assign(s->n_tris, 0u);
+    const int rc = fspt_scene_rebuild_geometry(s, tri, norm, o.data());
+    if (rc) return rc;
+    if (&o == &other && other != first) { fspt_set_error("fspt_multi_rebuild_geometry: the devices built different trees"); return FSPT_E_STATE; }
+  }
+  if (order_out && !first.empty()) std::memcpy(order_out, first.data(), first.size() * 4);
+  return FSPT_OK;
+}
 
 int fspt_multi_clear(fspt_multi *m) { MULTI_EACH(fspt_clear(t)); }
 int fspt_multi_sync(fspt_multi *m) { MULTI_EACH(fspt_sync(t)); }

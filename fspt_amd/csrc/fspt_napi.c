@@ -298,6 +298,22 @@ static napi_value SceneUpdateGeometry(napi_env env, napi_callback_info info) {
   FSPT_OK_OR_THROW(fspt_scene_update_geometry((fspt_scene *)h, (const float *)tri, (const float *)norm));
   return undefined(env);
 }
+/* sceneRebuildGeometry(scene, nTris, tri, norm | null) -> Uint32Array order: fspt_scene_rebuild_geometry; the
+ * arguments and the guard of sceneUpdateGeometry. */
+static napi_value SceneRebuildGeometry(napi_env env, napi_callback_info info) {
+  napi_value a[4], ab, ta; void *h, *tri = NULL, *norm = NULL, *order = NULL; size_t nt = 0, nn = 0; uint32_t n = 0;
+  if (get_args(env, info, 4, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[1], &n));
+  if (typed(env, a[2], napi_float32_array, 0, &tri, &nt) || typed(env, a[3], napi_float32_array, 1, &norm, &nn)) return NULL;
+  if (nt != (size_t)n * 9 || (norm && nn != (size_t)n * 27)) {
+    napi_throw_range_error(env, NULL, "fspt_napi: rebuildGeometry needs 9 floats (tri) and 27 floats (norm) per triangle of the scene");
+    return NULL;
+  }
+  NAPI_OK(napi_create_arraybuffer(env, (size_t)n * 4, &order, &ab));
+  NAPI_OK(napi_create_typedarray(env, napi_uint32_array, (size_t)n, ab, 0, &ta));
+  FSPT_OK_OR_THROW(fspt_scene_rebuild_geometry((fspt_scene *)h, (const float *)tri, (const float *)norm, (uint32_t *)order));
+  return ta;
+}
 static napi_value SceneSahCost(napi_env env, napi_callback_info info) {
   napi_value a[1], v; void *h; double cost = 0.0;
   if (get_args(env, info, 1, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
@@ -1149,7 +1165,7 @@ static napi_value AbiVersion(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
-      {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneSahCost", SceneSahCost}, {"targetCreate", TargetCreate},
+      {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
       {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},

@@ -5,10 +5,18 @@
 //   k_refit_leaf_boxes  a leaf's box = min / max over the vertices of the triangles it OWNS
 //   k_refit_level       one tree level: a node's box = the union of its children's, written into its parent's record
 //   k_refit_quads       the two-level nodes from the refitted 64-byte nodes + fspt_scene_create's usability test
+// and what installs a NEW tree over the same triangles (fspt_scene_rebuild_geometry; rebuild_run below):
+//   k_rebuild_slot_map  triangle -> the old leaf slot of the leaf that owns it (one writer per triangle)
+//   k_rebuild_permute   the caller's tri / norm in the new leaf order (what refit_run is then fed)
+//   k_rebuild_gather    per NEW leaf slot: the 192-byte hit record of its triangle's old slot (12 lanes x 16 bytes), slot_tri,
+//                       and the "-1" padding of the leaf records
+//   k_rebuild_nodes     the interior nodes' child references
 // Schedule: one launch per tree level, deepest first (depth - 1 launches, no atomics on box words: a level only reads what
 // the launches before it wrote, and two siblings write different words of their parent's record).  Min and max are taken on
 // the order-preserving integer keys of fspt_bvh_build.hip (-0 < +0), which is the rule tests/refit_ref.py restates.
 #include "fspt_internal.hpp"
+
+#include <chrono>
 
 namespace fspt {
 namespace {
@@ -134,6 +142,58 @@ __global__ void k_refit_quads(const float *__restrict__ nodes, uint32_t n_interi
   if (!ok) atomicOr(flag, 1u);
 }
 
+// ---- a new tree over the same triangles ----
+// one thread per old leaf slot: the owning leaf's slot of triangle leaf_first[L] + k, k < leaf_cnt[L] (the owned ranges tile
+// [0, T): every triangle has one writer)
+__global__ void k_rebuild_slot_map(const uint32_t *__restrict__ leaf_first, const uint32_t *__restrict__ leaf_cnt, uint32_t n_leaves,
+                                   uint32_t LS, uint32_t T, uint32_t *__restrict__ map) {
+  const size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (sl >= (size_t)n_leaves * LS) return;
+  const uint32_t L = (uint32_t)(sl / LS), k = (uint32_t)(sl % LS);
+  const uint32_t ti = leaf_first[L] + k;
+  if (k < leaf_cnt[L] && ti < T) map[ti] = (uint32_t)sl;
+}
+
+// dst[i * W + c] = src[order[i] * W + c]: one thread per output word
+__global__ void k_rebuild_permute(const float *__restrict__ src, const uint32_t *__restrict__ order, uint32_t T, uint32_t W, float *__restrict__ dst) {
+  const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= (size_t)T * W) return;
+  const uint32_t i = (uint32_t)(id / W), c = (uint32_t)(id % W);
+  const uint32_t o = order[i];
+  dst[id] = o < T ? src[(size_t)o * W + c] : 0.0f;
+}
+
+// 12 lanes per new leaf slot (L, k), one float4 of its hit record each: the record of the old slot of triangle
+// order[leaf_first[L] + k] (refit_run then rewrites floats 0-8, and 9-35 when the caller gave normals); zeros, and the
+// leaf record's "-1" triangle, where the slot lies beyond the last triangle
+__global__ void k_rebuild_gather(const float4 *__restrict__ old_rec, size_t old_slots, const uint32_t *__restrict__ map,
+                                 const uint32_t *__restrict__ order, const uint32_t *__restrict__ leaf_first, uint32_t n_leaves, uint32_t LS,
+                                 uint32_t T, float4 *__restrict__ rec, uint32_t *__restrict__ slot_tri, float *__restrict__ leaves) {
+  const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t sl = id / 12;
+  const uint32_t j = (uint32_t)(id % 12);
+  if (sl >= (size_t)n_leaves * LS) return;
+  const uint32_t L = (uint32_t)(sl / LS), k = (uint32_t)(sl % LS);
+  const uint32_t ti = leaf_first[L] + k;
+  float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (ti < T) {
+    const uint32_t o = order[ti];
+    const uint32_t src = o < T ? map[o] : 0xFFFFFFFFu;
+    if ((size_t)src < old_slots) v = old_rec[(size_t)src * 12 + j];
+  } else if (j < 9) {
+    leaves[(size_t)L * LS * 9 + (size_t)j * LS + k] = j < 3 ? -1.0f : 0.0f; // v1 = (-1, -1, -1), e1 = e2 = 0
+  }
+  rec[sl * 12 + j] = v;
+  if (j == 0) slot_tri[sl] = ti;
+}
+
+// node r's words 12-15: its children's references (cref[2 r], cref[2 r + 1]), 0, 0; the boxes are the refit's
+__global__ void k_rebuild_nodes(const int32_t *__restrict__ cref, uint32_t n_interior, int4 *__restrict__ nodes) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_interior) return;
+  nodes[(size_t)r * 4 + 3] = make_int4(cref[2 * r], cref[2 * r + 1], 0, 0);
+}
+
 inline uint32_t blocks_for(size_t n, uint32_t bs) { return (uint32_t)((n + bs - 1) / bs); }
 
 } // namespace
@@ -212,6 +272,162 @@ int refit_run(fspt_scene *s, const float *tri, const float *norm, int *finite, i
   HIP_TRY(hipEventElapsedTime(&R.last_ms, R.ev[0], R.ev[1]));
   R.last_launches = launches;
   *quads_ok = s->quads && NI > 0 && flags[1] == 0u;
+  return FSPT_OK;
+}
+
+int refit_check(fspt_scene *s, const float *tri, const float *norm, int *finite) {
+  fspt_scene::Refit &R = s->rf;
+  const uint32_t BS = 256;
+  uint32_t flag = 0u;
+  HIP_TRY(hipMemsetAsync(R.d_flag, 0, 4, nullptr));
+  const size_t n = (size_t)s->n_tris * 9, m = (size_t)s->n_tris * 27;
+  hipLaunchKernelGGL(k_refit_check, dim3(std::min<uint32_t>(blocks_for(n, BS), 4096u)), dim3(BS), 0, nullptr, (const uint32_t *)tri, n, R.d_flag);
+  if (norm) hipLaunchKernelGGL(k_refit_check, dim3(std::min<uint32_t>(blocks_for(m, BS), 4096u)), dim3(BS), 0, nullptr, (const uint32_t *)norm, m, R.d_flag);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(&flag, R.d_flag, 4, hipMemcpyDeviceToHost));
+  *finite = flag == 0u;
+  return FSPT_OK;
+}
+
+namespace {
+// the new tree until it is installed: freed unless `keep` is set
+struct RebuildGuard {
+  fspt_scene ns;
+  BvhGpuDevice bt;
+  uint32_t *d_map = nullptr;
+  int32_t *d_cref = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  bool keep = false;
+  ~RebuildGuard() {
+    bvh_device_release(bt);
+    hipFree(d_map); hipFree(d_cref);
+    for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
+    if (keep) return;
+    hipFree(ns.nodes); hipFree(ns.quads); hipFree(ns.tris); hipFree(ns.slot_tri); hipFree(ns.shade);
+    refit_release(&ns);
+  }
+};
+int rebuild_alloc(void **p, size_t bytes) {
+  const hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+  if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); fspt_set_error("fspt_scene_rebuild_geometry: out of device memory (%zu bytes)", bytes); return FSPT_E_NOMEM; }
+  HIP_TRY(e);
+  return FSPT_OK;
+}
+#define REBUILD_ALLOC(p, bytes) do { int rc_a = rebuild_alloc((void **)(p), (bytes)); if (rc_a) return rc_a; } while (0)
+} // namespace
+
+int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *order_out, bool order_on_device) {
+  const uint32_t T = s->n_tris, LS = s->d.leaf_size, BS = 256;
+  RebuildGuard G;
+  fspt_scene &ns = G.ns;
+  // 1. the build kernels, from the caller's device array; the tree stays on the device
+  int rc = bvh_build_device(tri, T, LS, G.bt);
+  if (rc) return rc;
+  // 2. topology only comes back: 16 bytes per node
+  const uint32_t nn = G.bt.n_nodes;
+  std::vector<int32_t> left(nn), right(nn);
+  std::vector<uint32_t> lo(nn), cnt(nn);
+  HIP_TRY(hipMemcpy(left.data(), G.bt.left, (size_t)nn * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(right.data(), G.bt.right, (size_t)nn * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(lo.data(), G.bt.lo, (size_t)nn * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(cnt.data(), G.bt.cnt, (size_t)nn * 4, hipMemcpyDeviceToHost));
+  // 3. the host's integer work: pre-order words as fspt_scene_create would be handed them, then its own numbering
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<int32_t> pre;
+  std::vector<uint32_t> gid, node_depth;
+  uint32_t depth = 0;
+  if (const char *what = bvh_preorder(left.data(), right.data(), lo.data(), cnt.data(), nn, T, LS, pre, gid, node_depth, &depth)) {
+    fspt_set_error("fspt_scene_rebuild_geometry: inconsistent tree from the device (%s)", what);
+    return FSPT_E_HIP;
+  }
+  std::vector<int32_t> words((size_t)nn * 3);
+  for (uint32_t i = 0; i < nn; ++i) {
+    const uint32_t g = gid[i];
+    int32_t *w = &words[(size_t)i * 3];
+    if (left[g] < 0) { w[0] = -1; w[1] = -1; w[2] = (int32_t)lo[g]; }
+    else { w[0] = pre[(size_t)left[g]]; w[1] = pre[(size_t)right[g]]; w[2] = -1; }
+  }
+  TreeTopology tp;
+  rc = tree_topology(words.data(), 12, nn, T, tp);
+  if (rc) return rc;
+  tree_refit_tables(words.data(), 12, nn, T, tp, ns.rf);
+  const uint32_t NI = tp.n_interior, nl = (uint32_t)tp.leaf_first.size();
+  std::vector<int32_t> cref(2 * (size_t)(NI ? NI : 1), 0);
+  for (uint32_t i = 0; i < nn; ++i)
+    if (words[(size_t)i * 3 + 2] <= -1) {
+      cref[2 * (size_t)tp.ref[i]] = tp.ref[(size_t)words[(size_t)i * 3]];
+      cref[2 * (size_t)tp.ref[i] + 1] = tp.ref[(size_t)words[(size_t)i * 3 + 1]];
+    }
+  const float host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (!ns.rf.ok || !nl) { fspt_set_error("fspt_scene_rebuild_geometry: the built tree is not refittable"); return FSPT_E_HIP; }
+  // 4. the new arrays - every allocation before the first change to `s`
+  ns.device = s->device;
+  ns.n_tris = T;
+  ns.d.leaf_size = LS;
+  ns.n_interior = NI;
+  const size_t n_slots = (size_t)nl * LS, old_slots = s->n_slots;
+  REBUILD_ALLOC(&ns.nodes, (size_t)(NI ? NI : 1) * 64);
+  if (NI) REBUILD_ALLOC(&ns.quads, (size_t)NI * fspt::QUAD_F4 * 16u);
+  REBUILD_ALLOC(&ns.tris, n_slots * 9 * 4);
+  REBUILD_ALLOC(&ns.slot_tri, n_slots * 4);
+  REBUILD_ALLOC(&ns.shade, n_slots * 192);
+  REBUILD_ALLOC(&ns.rf.stage, (size_t)T * 36 * 4); // tri | norm in the new leaf order; the scene's staging array from now on
+  REBUILD_ALLOC(&G.d_map, (size_t)T * 4);
+  REBUILD_ALLOC(&G.d_cref, cref.size() * 4);
+  rc = refit_prepare(&ns);
+  if (rc) return rc;
+  HIP_TRY(hipEventCreate(&G.ev[0]));
+  HIP_TRY(hipEventCreate(&G.ev[1]));
+  // 5. the install kernels (NULL stream, like refit_run, which finishes the job: leaf records, hit floats 0-8 / 9-35, boxes, quads)
+  hipStream_t st = nullptr;
+  uint32_t launches = 0;
+  HIP_TRY(hipMemcpy(G.d_cref, cref.data(), cref.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipEventRecord(G.ev[0], st));
+  HIP_TRY(hipMemsetAsync(ns.nodes, 0, (size_t)(NI ? NI : 1) * 64, st));
+  HIP_TRY(hipMemsetAsync(G.d_map, 0xFF, (size_t)T * 4, st));
+  const uint32_t old_nl = (uint32_t)s->rf.leaf_first.size();
+  hipLaunchKernelGGL(k_rebuild_slot_map, dim3(blocks_for((size_t)old_nl * LS, BS)), dim3(BS), 0, st, s->rf.d_leaf, s->rf.d_leaf + old_nl, old_nl, LS, T, G.d_map);
+  float *ptri = ns.rf.stage, *pnorm = norm ? ns.rf.stage + (size_t)T * 9 : nullptr;
+  hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 9, BS)), dim3(BS), 0, st, tri, G.bt.order, T, 9u, ptri);
+  launches += 2;
+  if (norm) { hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 27, BS)), dim3(BS), 0, st, norm, G.bt.order, T, 27u, pnorm); ++launches; }
+  hipLaunchKernelGGL(k_rebuild_gather, dim3(blocks_for(n_slots * 12, BS)), dim3(BS), 0, st, (const float4 *)s->shade, old_slots, G.d_map, G.bt.order,
+                     ns.rf.d_leaf, nl, LS, T, (float4 *)ns.shade, (uint32_t *)ns.slot_tri, (float *)ns.tris);
+  ++launches;
+  if (NI) { hipLaunchKernelGGL(k_rebuild_nodes, dim3(blocks_for(NI, BS)), dim3(BS), 0, st, G.d_cref, NI, (int4 *)ns.nodes); ++launches; }
+  HIP_TRY(hipGetLastError());
+  int finite = 1, quads_ok = 0;
+  rc = refit_run(&ns, ptri, pnorm, &finite, &quads_ok);
+  if (rc) return rc;
+  if (!finite) { fspt_set_error("fspt_scene_rebuild_geometry: a value of tri / norm is not finite (scene unchanged)"); return FSPT_E_INVALID; }
+  HIP_TRY(hipEventRecord(G.ev[1], st));
+  if (order_out) HIP_TRY(hipMemcpy(order_out, G.bt.order, (size_t)T * 4, order_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+  HIP_TRY(hipDeviceSynchronize());
+  float install_ms = 0.0f;
+  HIP_TRY(hipEventElapsedTime(&install_ms, G.ev[0], G.ev[1]));
+  // 6. everything has succeeded: swap, then free the old tree
+  G.keep = true;
+  hipFree(s->nodes); hipFree(s->quads); hipFree(s->tris); hipFree(s->slot_tri); hipFree(s->shade);
+  refit_release(s);
+  s->rf = std::move(ns.rf);
+  s->nodes = ns.nodes; s->quads = ns.quads; s->tris = ns.tris; s->slot_tri = ns.slot_tri; s->shade = ns.shade;
+  s->d.nodes = (const float4 *)s->nodes;
+  s->d.quads = quads_ok ? (const float4 *)s->quads : nullptr;
+  s->d.leaves = (const float *)s->tris;
+  s->d.slot_tri = (const uint32_t *)s->slot_tri;
+  s->d.hitrec = (const float4 *)s->shade;
+  s->d.root_ref = tp.ref[0];
+  s->d.stack_n = tp.max_depth + 1;
+  s->d.n_top = NI < 256u ? NI : 256u;
+  s->depth = tp.max_depth;
+  s->n_nodes = nn;
+  s->n_interior = NI;
+  s->n_slots = n_slots;
+  s->rb.build_ms = G.bt.kernel_ms;
+  s->rb.install_ms = install_ms;
+  s->rb.host_ms = host_ms;
+  s->rb.launches = G.bt.launches + launches + s->rf.last_launches;
+  s->rb.readbacks = G.bt.readbacks + 1;
   return FSPT_OK;
 }
 

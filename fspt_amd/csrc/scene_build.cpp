@@ -721,37 +721,18 @@ int fspt_builder_build_gpu(fspt_builder *b, uint32_t leaf_size, int device) {
   // pre-order renumbering (left first), checking that the device handed back one tree over every triangle
   const size_t nn = r.left.size();
   auto bad = [](const char *what) { fspt_set_error("fspt_builder_build_gpu: inconsistent tree from the device (%s)", what); return FSPT_E_HIP; };
-  std::vector<int32_t> pre(nn, -1);
+  std::vector<int32_t> pre;
   std::vector<uint32_t> gid, node_depth;
-  std::vector<BuildNode> nodes;
-  gid.reserve(nn); node_depth.reserve(nn); nodes.reserve(nn);
-  std::vector<std::pair<uint32_t, uint32_t>> st{{0u, 0u}};
-  uint32_t depth = 0, next_lo = 0;
-  while (!st.empty()) {
-    const uint32_t g = st.back().first, d = st.back().second;
-    st.pop_back();
-    if (g >= nn || pre[g] >= 0) return bad("node visited twice or out of range");
-    pre[g] = (int32_t)nodes.size();
-    gid.push_back(g);
-    node_depth.push_back(d);
-    depth = std::max(depth, d);
-    BuildNode nd;
-    nd.lo = r.lo[g];
-    nd.hi = r.lo[g] + r.cnt[g];
-    nd.leaf = r.left[g] < 0;
-    if (nd.hi < nd.lo || nd.hi > nt) return bad("range");
-    if (nd.leaf) {
-      if (nd.lo != next_lo || r.cnt[g] == 0 || r.cnt[g] > leaf_size) return bad("leaf range");
-      next_lo = nd.hi;
-    } else {
-      if (r.right[g] < 0) return bad("children");
-      st.push_back({(uint32_t)r.right[g], d + 1});
-      st.push_back({(uint32_t)r.left[g], d + 1});
-    }
-    nodes.push_back(nd);
+  uint32_t depth = 0;
+  if (const char *what = fspt::bvh_preorder(r.left.data(), r.right.data(), r.lo.data(), r.cnt.data(), nn, nt, leaf_size, pre, gid, node_depth, &depth))
+    return bad(what);
+  std::vector<BuildNode> nodes(nn);
+  for (size_t i = 0; i < nn; ++i) {
+    const uint32_t g = gid[i];
+    nodes[i].lo = r.lo[g];
+    nodes[i].hi = r.lo[g] + r.cnt[g];
+    nodes[i].leaf = r.left[g] < 0;
   }
-  if (nodes.size() != nn || next_lo != nt) return bad("coverage");
-  if (depth > fspt::bvh_max_depth()) return bad("depth");
   std::vector<uint8_t> seen(nt, 0);
   for (uint32_t t : r.order) {
     if (t >= nt || seen[t]) return bad("triangle order");

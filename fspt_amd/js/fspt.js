@@ -446,6 +446,15 @@ class PathTracer {
     if (norm != null && (!(norm instanceof Float32Array) || norm.length !== this._nTris * 27)) throw new RangeError('updateGeometry: norm must be a Float32Array of ' + this._nTris + ' x 27 floats');
     addon.sceneUpdateGeometry(this._scene, this._nTris, tri, norm == null ? null : norm);
   }
+  /** The arguments of updateGeometry, but the scene gets a NEW tree - the binned SAH of the GPU builder over `tri` in the
+   *  order given - built on the GPU and installed in place (fspt_scene_rebuild_geometry, DESIGN 8.7).  Returns a Uint32Array:
+   *  order[k] = index in `tri` of the triangle now at leaf position k; later updateGeometry / rebuildGeometry calls take
+   *  their triangles in that order.  clear() restarts the mean. */
+  rebuildGeometry(tri, norm) {
+    if (!(tri instanceof Float32Array) || tri.length !== this._nTris * 9) throw new RangeError('rebuildGeometry: tri must be a Float32Array of ' + this._nTris + ' x 9 floats');
+    if (norm != null && (!(norm instanceof Float32Array) || norm.length !== this._nTris * 27)) throw new RangeError('rebuildGeometry: norm must be a Float32Array of ' + this._nTris + ' x 27 floats');
+    return addon.sceneRebuildGeometry(this._scene, this._nTris, tri, norm == null ? null : norm);
+  }
   /** SAH cost of the tree with its current boxes relative to the root's area (fspt_scene_sah_cost) */
   sahCost() { return addon.sceneSahCost(this._scene); }
   /** 'wavefront' (batches of ticks), 'stream' (fixed pool of live paths), 'megakernel' (include/fspt_tuning.h) */

@@ -42,6 +42,9 @@ def main():
     ap.add_argument("--bvh", choices=("sah", "gpu", "refit"), default="sah",
                     help="BVH builder: the reference's full-sweep SAH on the CPU, or binned SAH on the GPU (DESIGN 8.4); refit (with "
                          "--frames): build the first frame, then refit the tree for frames that only move triangles (DESIGN 8.6)")
+    ap.add_argument("--rebuild-above", type=float, default=None, metavar="R",
+                    help="--bvh refit: rebuild the tree in place on the GPU when a refitted frame's SAH cost exceeds R x the cost at "
+                         "the last build (DESIGN 8.7; default: never)")
     ap.add_argument("--sampler", choices=("reference", "sobol"), default="reference",
                     help="the paths' random numbers (fspt_target_set_sampler; built-in scene)")
     ap.add_argument("--sampler-seed", type=int, default=0, help="seed of --sampler sobol, in [0, 2^32)")
@@ -84,7 +87,8 @@ def main():
         if args.frames:
             a, b = (int(x) for x in args.frames.split(":"))
             t0 = time.perf_counter()
-            out = F.render_sequence(args.scene, range(a, b), args.out, args.width, args.height, args.assets, bvh=args.bvh, **kw)
+            out = F.render_sequence(args.scene, range(a, b), args.out, args.width, args.height, args.assets, bvh=args.bvh,
+                                    rebuild_above=args.rebuild_above, **kw)
             print(f"{len(out)} frames in {time.perf_counter() - t0:.2f} s:", *out)
         else:
             arrays, settings = F.load_scene_file(args.scene, args.assets, bvh=args.bvh)

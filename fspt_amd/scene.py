@@ -462,6 +462,17 @@ def geometry_in_leaf_order(arrays_or_order, tri_in, norm_in=None):
     return np.ascontiguousarray(tri[order]).reshape(-1), out_n
 
 
+def compose_order(base_order, order):
+    """The parse-order map after Scene.rebuild_geometry: base_order[k] = parse-order index of the triangle at leaf position
+    k BEFORE the rebuild (meta["tri_order"], or an earlier compose_order), order = what rebuild_geometry returned.  The
+    result goes where base_order went: geometry_in_leaf_order(compose_order(base_order, order), tri_in_parse_order)."""
+    base_order = np.asarray(base_order).reshape(-1)
+    order = np.asarray(order, dtype=np.int64).reshape(-1)
+    if order.size != base_order.size:
+        raise ValueError(f"compose_order: {order.size} entries against {base_order.size}")
+    return np.ascontiguousarray(base_order[order])
+
+
 def build_scene_json(scene, obj_texts, mtl_texts=None, images=None, env=None, env_w=0, env_h=0, leaf_size=4,
                      focus_rays=None, bvh="sah", device=0, keep_order=False, geometry_only=False):
     """build_scene for a whole scene JSON (props / static_props / animated_props, worldTransforms, normalize,

@@ -147,9 +147,11 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     bvh="refit" (DESIGN 8.6): the first frame builds ("sah"); a later frame with the same triangle count, materials, uvs,
     atlas and environment keeps scene and tracer: its props are parsed without building a tree, the moved triangles go to
     Scene.update_geometry in the first tree's leaf order, the accumulator is cleared and the auto-focus ray is shot
-    against the new triangles.  Any other frame rebuilds, and so does one whose Scene.sah_cost() exceeds `rebuild_above` x
-    the cost at the last build (None, the default: never - no threshold has been measured).  on_frame(N, "build" | "refit")
-    reports what a frame did."""
+    against the new triangles.  A refitted frame whose Scene.sah_cost() exceeds `rebuild_above` x the cost at the last
+    (re)build gets a new tree IN PLACE (Scene.rebuild_geometry, DESIGN 8.7: scene and tracer stay; the tree is the binned
+    SAH of bvh="gpu" from then on, which renders 0.94-0.95x as fast as the sweep's); None, the default: never.  Any other
+    frame - another triangle count, other materials, uvs, atlas or environment - builds a new scene.
+    on_frame(N, "build" | "refit" | "rebuild") reports what a frame did."""
     from PIL import Image
     written = []
     device = kw.get("device", 0)
@@ -174,7 +176,7 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                adaptive=None, sample_map=None)
     bounces = kw.get("bounces", 4)
     opt.update({k: v for k, v in kw.items() if k in opt})
-    base, pt, cost0 = None, None, None
+    base, pt, cost0, leaf_order = None, None, None, None
 
     def same_scene(a, g):
         eq = lambda x, y: (x is None and y is None) or (x is not None and y is not None and np.array_equal(x, y))
@@ -190,17 +192,20 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
             if base is not None:
                 g, settings = load_scene_file(path, asset_root, geometry_only=True)
                 if same_scene(base, g):
-                    tri, norm = S.geometry_in_leaf_order(base, g.tri, g.norm)
+                    tri, norm = S.geometry_in_leaf_order(leaf_order, g.tri, g.norm)
                     pt.update_geometry(tri, norm)
                     how = "refit"
                     if rebuild_above is not None and pt.scene.sah_cost() > rebuild_above * cost0:
-                        how = "build"
+                        leaf_order = S.compose_order(leaf_order, pt.rebuild_geometry(tri, norm))
+                        cost0 = pt.scene.sah_cost()
+                        how = "rebuild"
             if how == "build":
                 if pt is not None:
                     pt.close(); pt.scene.close()
                 base, settings = load_scene_file(path, asset_root, bvh="sah", device=device, keep_order=True)
                 pt = PathTracer(base, width, height, device=device, num_bounces=bounces)
                 cost0 = pt.scene.sah_cost() if rebuild_above is not None else None
+                leaf_order = base.meta["tri_order"]
             rgba, _ = _render_on(pt, settings, **opt)
             if on_frame:
                 on_frame(n, how)

@@ -161,16 +161,14 @@ class Scene:
         L.check(L.lib().fspt_scene_two_level_nodes(self._h, C.byref(yes), C.byref(b)))
         return bool(yes.value), int(b.value)
 
-    def update_geometry(self, tri, norm=None):
-        """New vertices (9 floats per triangle) and, unless norm is None, normTex records (27 per triangle) for the scene's
-        n_tris triangles in LEAF order (scene.geometry_in_leaf_order): the tree is refitted on the GPU, nothing else changes
-        (fspt_scene_update_geometry, DESIGN 8.6).  numpy arrays are uploaded; float32 torch tensors on the scene's device
-        are read where they are (the `_device` form, no copy).  Accumulators are not cleared; `self.arrays` is not touched."""
+    def _geometry_args(self, fn, tri, norm):
+        """(on device, tri, norm) checked for update_geometry / rebuild_geometry: ctypes pointers of device tensors, or
+        contiguous float32 numpy arrays"""
         n = int(self.arrays.n_tris)
         on_dev = [hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) for a in (tri, norm) if a is not None]
         if any(on_dev):
             if not all(on_dev):
-                raise TypeError("update_geometry: tri and norm must both be device tensors or both host arrays")
+                raise TypeError(f"{fn}: tri and norm must both be device tensors or both host arrays")
             import torch
             ptrs = []
             for name, a, k in (("tri", tri, 9), ("norm", norm, 27)):
@@ -178,23 +176,61 @@ class Scene:
                     ptrs.append(None)
                     continue
                 if a.dtype != torch.float32 or not a.is_contiguous():
-                    raise TypeError(f"update_geometry: {name} must be a contiguous float32 tensor")
+                    raise TypeError(f"{fn}: {name} must be a contiguous float32 tensor")
                 if a.device.index != self.device:
-                    raise ValueError(f"update_geometry: {name} lives on {a.device}, the scene on device {self.device}")
+                    raise ValueError(f"{fn}: {name} lives on {a.device}, the scene on device {self.device}")
                 if a.numel() != n * k:
-                    raise ValueError(f"update_geometry: {name} has {a.numel()} elements, the scene needs {n} x {k}")
+                    raise ValueError(f"{fn}: {name} has {a.numel()} elements, the scene needs {n} x {k}")
                 ptrs.append(C.c_void_p(a.data_ptr()))
             torch.cuda.current_stream(self.device).synchronize()  # whatever wrote the tensors has finished
-            L.check(L.lib().fspt_scene_update_geometry_device(self._h, ptrs[0], ptrs[1]))
-            return
+            return True, ptrs[0], ptrs[1]
         tri = np.ascontiguousarray(tri, dtype=np.float32)
         if tri.size != n * 9:
-            raise ValueError(f"update_geometry: tri has {tri.size} elements, the scene needs {n} x 9")
+            raise ValueError(f"{fn}: tri has {tri.size} elements, the scene needs {n} x 9")
         if norm is not None:
             norm = np.ascontiguousarray(norm, dtype=np.float32)
             if norm.size != n * 27:
-                raise ValueError(f"update_geometry: norm has {norm.size} elements, the scene needs {n} x 27")
-        L.check(L.lib().fspt_scene_update_geometry(self._h, L.fptr(tri), None if norm is None else L.fptr(norm)))
+                raise ValueError(f"{fn}: norm has {norm.size} elements, the scene needs {n} x 27")
+        return False, tri, norm
+
+    def update_geometry(self, tri, norm=None):
+        """New vertices (9 floats per triangle) and, unless norm is None, normTex records (27 per triangle) for the scene's
+        n_tris triangles in LEAF order (scene.geometry_in_leaf_order): the tree is refitted on the GPU, nothing else changes
+        (fspt_scene_update_geometry, DESIGN 8.6).  numpy arrays are uploaded; float32 torch tensors on the scene's device
+        are read where they are (the `_device` form, no copy).  Accumulators are not cleared; `self.arrays` is not touched."""
+        on_dev, tri, norm = self._geometry_args("update_geometry", tri, norm)
+        if on_dev:
+            L.check(L.lib().fspt_scene_update_geometry_device(self._h, tri, norm))
+        else:
+            L.check(L.lib().fspt_scene_update_geometry(self._h, L.fptr(tri), None if norm is None else L.fptr(norm)))
+
+    def rebuild_geometry(self, tri, norm=None):
+        """The same input as update_geometry, but the scene gets a NEW tree: the binned-SAH tree of build_scene(bvh="gpu")
+        over `tri` in the order given, built on the GPU and installed in this scene - tracers stay valid, accumulators are
+        not cleared (fspt_scene_rebuild_geometry).  Returns the permutation `order`: the triangle now at leaf
+        position k is input triangle order[k]; "leaf order" means the new order from here on, so the next update_geometry /
+        rebuild_geometry takes tri[order] (scene.compose_order keeps a parse-order map current).  numpy in, numpy uint32
+        out; float32 torch tensors on the scene's device in, an int64 tensor on that device out.  A scene first built by the
+        reference's sweep (bvh="sah") becomes a binned-SAH tree, which renders 0.94-0.95x as fast; rebuilding
+        a bvh="gpu" scene with its own triangles changes nothing (order = arange).  Any error leaves the scene as it was."""
+        n = int(self.arrays.n_tris)
+        on_dev, tri, norm = self._geometry_args("rebuild_geometry", tri, norm)
+        if on_dev:
+            import torch
+            order = torch.empty(n, dtype=torch.int32, device=f"cuda:{self.device}")
+            L.check(L.lib().fspt_scene_rebuild_geometry_device(self._h, tri, norm, C.c_void_p(order.data_ptr())))
+            return order.to(torch.int64)
+        order = np.zeros(n, np.uint32)
+        L.check(L.lib().fspt_scene_rebuild_geometry(self._h, L.fptr(tri), None if norm is None else L.fptr(norm), L.u32ptr(order)))
+        return order
+
+    def last_rebuild_ms(self):
+        """The most recent rebuild_geometry as a dict: build_ms (GPU, the build kernels), install_ms (GPU, gather + refit),
+        host_ms (the numbering), launches, readbacks (fspt_scene_last_rebuild_ms)."""
+        b, i, h, nl, nr = C.c_float(), C.c_float(), C.c_float(), C.c_uint32(), C.c_uint32()
+        L.check(L.lib().fspt_scene_last_rebuild_ms(self._h, C.byref(b), C.byref(i), C.byref(h), C.byref(nl), C.byref(nr)))
+        return dict(build_ms=float(b.value), install_ms=float(i.value), host_ms=float(h.value), launches=int(nl.value),
+                    readbacks=int(nr.value))
 
     def sah_cost(self):
         """SAH cost of the tree with the boxes the device holds now, relative to the root's area (fspt_scene_sah_cost): what
@@ -484,6 +520,10 @@ class PathTracer:
         """Scene.update_geometry on this tracer's scene (every tracer of the scene sees it); call clear() to restart the mean."""
         self.scene.update_geometry(tri, norm)
 
+    def rebuild_geometry(self, tri, norm=None):
+        """Scene.rebuild_geometry on this tracer's scene: a new tree in place; returns the new leaf order."""
+        return self.scene.rebuild_geometry(tri, norm)
+
     def clear(self):
         L.check(L.lib().fspt_clear(self._t))
         self.pingpong = 0
@@ -678,6 +718,21 @@ class MultiPathTracer:
             if norm.size != n * 27:
                 raise ValueError(f"update_geometry: norm has {norm.size} elements, the scene needs {n} x 27")
         L.check(L.lib().fspt_multi_update_geometry(self._m, L.fptr(tri), None if norm is None else L.fptr(norm)))
+
+    def rebuild_geometry(self, tri, norm=None):
+        """Scene.rebuild_geometry (host arrays) on every device's copy of the scene (fspt_multi_rebuild_geometry); every
+        device builds the same tree, the one order is returned."""
+        n = int(self.arrays.n_tris)
+        tri = np.ascontiguousarray(tri, dtype=np.float32)
+        if tri.size != n * 9:
+            raise ValueError(f"rebuild_geometry: tri has {tri.size} elements, the scene needs {n} x 9")
+        if norm is not None:
+            norm = np.ascontiguousarray(norm, dtype=np.float32)
+            if norm.size != n * 27:
+                raise ValueError(f"rebuild_geometry: norm has {norm.size} elements, the scene needs {n} x 27")
+        order = np.zeros(n, np.uint32)
+        L.check(L.lib().fspt_multi_rebuild_geometry(self._m, L.fptr(tri), None if norm is None else L.fptr(norm), L.u32ptr(order)))
+        return order
 
     def clear(self):
         L.check(L.lib().fspt_multi_clear(self._m))

@@ -78,17 +78,17 @@ typedef struct fspt_scene_desc {
   uint32_t leaf_size;     /* '#define LEAF_SIZE' spliced into the shader (main.js:45,895)                              */
 } fspt_scene_desc;
 
-/* device = HIP device ordinal.  Builds the MI355X-native layouts (64-byte
- * two-child nodes, 144-byte leaf records, 192-byte hit records, material texture sets in 128-byte tiles). */
+/* device = HIP device ordinal.  Builds the MI355X-native layouts (64-byte two-child nodes, 144-byte leaf records, 192-byte hit records, material texture sets in 128-byte tiles; DESIGN.md 3). */
 int fspt_scene_create(const fspt_scene_desc *desc, int device, fspt_scene **out); int fspt_scene_destroy(fspt_scene *scene);
-/* Maximum depth of the uploaded tree (root = 0); sizes the LDS stacks. */
-int fspt_scene_depth(const fspt_scene *scene, uint32_t *depth);
+int fspt_scene_depth(const fspt_scene *scene, uint32_t *depth); /* Maximum depth of the uploaded tree (root = 0); sizes the LDS stacks. */
 /* Moving geometry: new vertices (9 floats) and, unless norm is NULL, normTex records (27 floats) for the n_tris
  * triangles in leaf order; the tree is REFITTED on the GPU (leaf and hit records, every box bottom-up, two-level nodes, light
  * table) exactly as fspt_scene_create would build it from the same topology.  Non-finite input: FSPT_E_INVALID, scene unchanged;
- * leaves that do not tile [0, n_tris): FSPT_E_STATE.  Blocking; ordered against every target; accumulators are not cleared. */
-int fspt_scene_update_geometry(fspt_scene *s, const float *tri, const float *norm); /* host pointers */
-int fspt_scene_update_geometry_device(fspt_scene *s, const float *tri, const float *norm); /* memory of the scene's device */
+ * leaves that do not tile [0, n_tris): FSPT_E_STATE.  Blocking; ordered against every target; accumulators are not cleared.  _rebuild_
+ * (DESIGN 8.7): same input, a NEW tree - fspt_builder_build_gpu's binned SAH over tri in the order given - built on the GPU, installed in the same
+ * scene (targets stay valid; errors leave it as it was); order_out (or NULL)[k] = input index of the triangle now at leaf position k: the leaf order of later calls */
+int fspt_scene_update_geometry(fspt_scene *s, const float *tri, const float *norm); int fspt_scene_rebuild_geometry(fspt_scene *s, const float *tri, const float *norm, uint32_t *order_out); /* host pointers */
+int fspt_scene_update_geometry_device(fspt_scene *s, const float *tri, const float *norm); int fspt_scene_rebuild_geometry_device(fspt_scene *s, const float *tri, const float *norm, uint32_t *order_out); /* memory of the scene's device */
 int fspt_scene_sah_cost(fspt_scene *s, double *cost); /* SAH cost of the current boxes relative to the root's area, float64 */
 
 /* ------------------------------------------------------------------------

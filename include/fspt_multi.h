@@ -39,6 +39,9 @@ int fspt_multi_render(fspt_multi *m, const fspt_camera_params *cam, uint32_t fir
 int fspt_multi_clear(fspt_multi *m);
 /* fspt_scene_update_geometry (host pointers) on every device's copy of the scene */
 int fspt_multi_update_geometry(fspt_multi *m, const float *tri, const float *norm);
+/* fspt_scene_rebuild_geometry (host pointers) on every device's copy of the scene.  The build is deterministic: every device
+ * must return the same order (checked; FSPT_E_STATE otherwise).  order_out may be NULL. */
+int fspt_multi_rebuild_geometry(fspt_multi *m, const float *tri, const float *norm, uint32_t *order_out);
 int fspt_multi_sync(fspt_multi *m);
 /* Gather (see above), then what fspt_read_radiance / fspt_draw do on the assembled frame.  Blocking. */
 int fspt_multi_read_radiance(fspt_multi *m, float *out);

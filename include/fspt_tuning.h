@@ -60,6 +60,10 @@ int fspt_scene_two_level_nodes(const fspt_scene *scene, int *present, uint64_t *
 /* The most recent fspt_scene_update_geometry[_device]: GPU time from its first kernel to its last (HIP events; the 4-byte
  * readback of the finite check lies between them) and the kernels it launched (one per tree level among them). */
 int fspt_scene_last_update_ms(fspt_scene *scene, float *ms, uint32_t *launches);
+/* The most recent fspt_scene_rebuild_geometry[_device]: GPU ms of the build kernels (their per-level readbacks
+ * included), GPU ms of the install kernels (slot map, permute, gather, child references, the refit), host ms of the
+ * numbering, kernels launched, readbacks (the builder's 4-byte ones + the one of the topology).  Any pointer may be NULL. */
+int fspt_scene_last_rebuild_ms(fspt_scene *scene, float *build_ms, float *install_ms, float *host_ms, uint32_t *launches, uint32_t *readbacks);
 /* fspt_intersect (fspt.h) walking the two-level nodes (two_level != 0; FSPT_E_INVALID when the scene has none): t, index
  * and the per-ray step / leaf counts must equal the one-level walk's (tests). */
 int fspt_intersect_form(fspt_scene *scene, int two_level, const float *rays, uint32_t n, float *t_out, int32_t *index_out,

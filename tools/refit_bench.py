@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/refit_bench.py - fspt_scene_update_geometry against rebuilding the scene.
+"""tools/refit_bench.py - fspt_scene_update_geometry and fspt_scene_rebuild_geometry against rebuilding the scene.
 
     python tools/refit_bench.py --reps 3 [--configs c2,c3]
 
@@ -12,8 +12,13 @@ process, interleaved rep by rep:
   rebuild_s, rebuild_parts_s        the only way to do the same without the feature: fspt_builder_build_gpu on the moved
                                     triangles + fspt_scene_create + a new target + prepare() (OBJ parsing NOT counted:
                                     the builder is fed before the clock starts)
-  sah_before / sah_refit / sah_fresh   Scene.sah_cost() of the base tree, the refitted one, a tree built on the moved triangles
-  msamples_refit / msamples_fresh   1920 x 1080, 8 bounces, 20-tick regions, on the refitted and on the freshly built tree
+  inplace_host_s / inplace_device_s  Scene.rebuild_geometry on a second scene with a live, prepared target: a new
+                                    tree in place from numpy arrays / from a torch tensor on the device; inplace_split =
+                                    the device form's fspt_scene_last_rebuild_ms (build_ms, install_ms, host_ms, launches,
+                                    readbacks); rebuild_over_inplace_device = rebuild_s / inplace_device_s
+  sah_before / sah_refit / sah_inplace / sah_fresh   Scene.sah_cost() of the base tree, the refitted one, the one rebuilt in
+                                    place, a tree built on the moved triangles by the rebuild path
+  msamples_refit / msamples_inplace / msamples_fresh   1920 x 1080, 8 bounces, 20-tick regions, on those three trees
 Bytes per triangle, counted from the kernels: check 36 x 4 read; records 36 x 4 read + per leaf slot 9 x 4 (leaf record)
 + 36 x 4 (hit record) written; leaf boxes 9 x 4 read + 24 written per leaf; levels 48 read + 24 written per interior node;
 two-level nodes 2 x 64 read + 128 written per interior node."""
@@ -144,6 +149,12 @@ def main():
             d_tri = torch.from_numpy(tri).to(f"cuda:{args.device}")
             d_norm = None if norm is None else torch.from_numpy(norm).to(f"cuda:{args.device}")
             sc.update_geometry(base.tri, base.norm)  # the first update makes the device copies: not timed
+            sc2 = Scene(base, args.device)  # the scene that is rebuilt in place, with a target that lives through it
+            pt2 = PathTracer(sc2, W, H, device=args.device, num_bounces=8)
+            pt2.prepare()
+            leaf = np.arange(base.n_tris, dtype=np.int64)  # sc2's leaf order in terms of the base's
+            in_order = lambda a, k: None if a is None else np.ascontiguousarray(a.reshape(-1, k)[leaf]).reshape(-1)
+            ih, idv, split = [], [], {}
             th, td, km, rb, parts, launches = [], [], [], [], [], 0
             fresh, text = None, obj_of(tri).encode()
             for _ in range(args.reps):
@@ -151,6 +162,15 @@ def main():
                 t0 = time.perf_counter(); sc.update_geometry(d_tri, d_norm); td.append(time.perf_counter() - t0)
                 ms, launches = sc.last_update_ms()
                 km.append(ms)
+                t2h, n2h = in_order(tri, 9), in_order(norm, 27)
+                t0 = time.perf_counter(); o = sc2.rebuild_geometry(t2h, n2h); ih.append(time.perf_counter() - t0)
+                leaf = leaf[o.astype(np.int64)]
+                t2d = torch.from_numpy(in_order(tri, 9)).to(f"cuda:{args.device}")
+                n2d = None if norm is None else torch.from_numpy(in_order(norm, 27)).to(f"cuda:{args.device}")
+                torch.cuda.synchronize(args.device)
+                t0 = time.perf_counter(); o = sc2.rebuild_geometry(t2d, n2d); idv.append(time.perf_counter() - t0)
+                leaf = leaf[o.cpu().numpy()]
+                split = sc2.last_rebuild_ms()
                 if fresh:
                     fresh[2].close(); fresh[1].close()
                 fresh = rebuild(base, text, args.device, W, H)
@@ -160,11 +180,15 @@ def main():
                    "update_host_s": med(th), "update_device_s": med(td), "update_kernel_ms": med(km), "launches": launches,
                    "bytes": nbytes, "gb_s": nbytes / (med(km) * 1e-3) / 1e9, "hbm_frac": nbytes / (med(km) * 1e-3) / 1e9 / HBM_PEAK_GBS,
                    "rebuild_s": med(rb), "rebuild_parts_s": [round(float(x), 4) for x in np.median(np.array(parts), axis=0)], "rebuild_over_update_device": med(rb) / med(td),
-                   "sah_before": sah0, "sah_refit": sc.sah_cost(), "sah_fresh": fresh[1].sah_cost()}
+                   "inplace_host_s": med(ih), "inplace_device_s": med(idv), "inplace_split": split,
+                   "inplace_device_range_s": [min(idv), max(idv)], "rebuild_range_s": [min(rb), max(rb)],
+                   "rebuild_over_inplace_device": med(rb) / med(idv),
+                   "sah_before": sah0, "sah_refit": sc.sah_cost(), "sah_inplace": sc2.sah_cost(), "sah_fresh": fresh[1].sah_cost()}
             if not args.no_rate:
                 out["msamples_refit"] = rate(pt)
+                out["msamples_inplace"] = rate(pt2)
                 out["msamples_fresh"] = rate(fresh[2])
-            fresh[2].close(); fresh[1].close(); pt.close(); sc.close()
+            fresh[2].close(); fresh[1].close(); pt.close(); sc.close(); pt2.close(); sc2.close()
             print(json.dumps(out), flush=True)
 
 

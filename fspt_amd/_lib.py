@@ -43,6 +43,10 @@ class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
 
 
+class TemporalParams(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("max_history", C.c_float), ("depth_tol", C.c_float), ("normal_cos", C.c_float)]
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("target_rel_mse", C.c_double), ("max_ticks", C.c_uint32), ("min_ticks", C.c_uint32), ("round_ticks", C.c_uint32)]
 
@@ -132,6 +136,16 @@ SIGNATURES = {
     "fspt_read_features": (C.c_int, [_VP, _F]),
     "fspt_denoise": (C.c_int, [_VP, C.POINTER(DenoiseParams), _F]),
     "fspt_draw_denoised": (C.c_int, [_VP, C.c_float, C.c_float, C.POINTER(C.c_uint8)]),
+    "fspt_temporal_accumulate": (C.c_int, [_VP, C.POINTER(CameraParams), C.POINTER(TemporalParams), _F]),
+    "fspt_temporal_reset": (C.c_int, [_VP]),
+    "fspt_temporal_denoise": (C.c_int, [_VP, C.POINTER(DenoiseParams), _F]),
+    "fspt_temporal_draw": (C.c_int, [_VP, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_uint8)]),
+    "fspt_temporal_read_gbuffer": (C.c_int, [_VP, _F, _F]),
+    "fspt_temporal_last_ms": (C.c_int, [_VP, _F]),
+    "fspt_temporal_eval": (C.c_int, [C.c_int, _F, _F, _F, _F, _F, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(TemporalParams), _F]),
+    "fspt_scene_slot_triangles": (C.c_int, [_VP, _U32, _U32]),
+    "fspt_scene_motion_begin": (C.c_int, [_VP]),
+    "fspt_scene_motion_end": (C.c_int, [_VP]),
     "fspt_intersect": (C.c_int, [_VP, _F, C.c_uint32, _F, C.POINTER(C.c_int32), _U32, _U32]),
     "fspt_intersect_form": (C.c_int, [_VP, C.c_int, _F, C.c_uint32, _F, C.POINTER(C.c_int32), _U32, _U32]),
     "fspt_scene_two_level_nodes": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),

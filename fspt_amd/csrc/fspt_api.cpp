@@ -684,7 +684,7 @@ int fspt_scene_destroy(fspt_scene *s) {
   if (!s) return FSPT_OK;
   hipSetDevice(s->device);
   hipFree(s->nodes); hipFree(s->quads); hipFree(s->tris); hipFree(s->slot_tri); hipFree(s->shade); hipFree(s->atlas); hipFree(s->atlas4); hipFree(s->tex_sets); hipFree(s->env); hipFree(s->bins);
-  hipFree(s->l_alias); hipFree(s->l_rec); hipFree(s->l_p); hipFree(s->l_pick);
+  hipFree(s->l_alias); hipFree(s->l_rec); hipFree(s->l_p); hipFree(s->l_pick); hipFree(s->motion);
   fspt::refit_release(s);
   delete s;
   return FSPT_OK;
@@ -773,6 +773,8 @@ int fspt_target_destroy(fspt_target *t) {
   }
   hipFree(t->accum_own); hipFree(t->ray_pos); hipFree(t->ray_dir); hipFree(t->work_counters); hipFree(t->counters);
   hipFree(t->feat); hipFree(t->dn_tmp[0]); hipFree(t->dn_tmp[1]); hipFree(t->dn_out);
+  hipFree(t->tm_hist[0]); hipFree(t->tm_hist[1]); hipFree(t->tm_g[0]); hipFree(t->tm_g[1]); hipFree(t->tm_m);
+  for (hipEvent_t ev : t->tm_ev) if (ev) hipEventDestroy(ev);
   hipFree(t->ad_snap); hipFree(t->ad_list[0]); hipFree(t->ad_list[1]); hipFree(t->ad_count); hipFree(t->ad_err);
   {
     fspt_target::WfLane &ln = t->wf;
@@ -1730,6 +1732,7 @@ int fspt_denoise(fspt_target *t, const fspt_denoise_params *prm, float *out) {
   if ((rc = dn_alloc(&t->dn_out, px * 16))) return rc;
   t->dn_valid = false;
   if (q.iterations > 1u && ((rc = dn_alloc(&t->dn_tmp[0], px * 16)) || (rc = dn_alloc(&t->dn_tmp[1], px * 16)))) return rc;
+  t->tm_dn_valid = false; // (dn_out is shared with fspt_temporal_denoise)
   HIP_TRY(dn_run(q, t->accum, t->feat, t->W, t->H, t->dn_tmp, t->dn_out, t->stream));
   t->dn_valid = true;
   if (out) {
@@ -1751,6 +1754,206 @@ int fspt_draw_denoised(fspt_target *t, float exposure, float saturation, uint8_t
   if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
   hipFree(d);
   if (e != hipSuccess) { fspt_set_error("fspt_draw_denoised: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
+  return FSPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// temporal accumulation (k_temporal_gbuffer / k_temporal_blend)
+// ---------------------------------------------------------------------------
+static int tm_check_params(const fspt_temporal_params &q, const char *fn) {
+  if (!(q.alpha >= 0.0f && q.alpha <= 1.0f) || !(q.max_history >= 1.0f) || !(q.depth_tol >= 0.0f) || !(q.normal_cos >= -1.0f && q.normal_cos <= 1.0f)) {
+    fspt_set_error("%s: need alpha in [0, 1], max_history >= 1, depth_tol >= 0, normal_cos in [-1, 1]", fn);
+    return FSPT_E_INVALID;
+  }
+  return FSPT_OK;
+}
+static const fspt_temporal_params TM_DEFAULTS = {FSPT_TEMPORAL_ALPHA, FSPT_TEMPORAL_MAX_HISTORY, FSPT_TEMPORAL_DEPTH_TOL, FSPT_TEMPORAL_NORMAL_COS};
+static void tm_fill_blend(fspt::TemporalBP &b, const fspt_temporal_params &q, uint32_t W, uint32_t H, float n) {
+  b.W = W; b.H = H; b.n = n;
+  b.alpha = q.alpha; b.max_history = q.max_history; b.depth_tol = q.depth_tol; b.normal_cos = q.normal_cos;
+}
+
+int fspt_temporal_accumulate(fspt_target *t, const fspt_camera_params *cam, const fspt_temporal_params *prm, float *out) {
+  if (!t || !cam) { fspt_set_error("fspt_temporal_accumulate: NULL argument"); return FSPT_E_INVALID; }
+  fspt_temporal_params q = TM_DEFAULTS;
+  if (prm) q = *prm;
+  int rc = tm_check_params(q, "fspt_temporal_accumulate");
+  if (rc) return rc;
+  if ((rc = dn_enter(t, true, "fspt_temporal_accumulate"))) return rc;
+  if (t->n_shards > 1) { fspt_set_error("fspt_temporal_accumulate: sharded target (its accumulator holds a part of the frame)"); return FSPT_E_STATE; }
+  if (t->vw != t->W || t->vh != t->H) { fspt_set_error("fspt_temporal_accumulate: the viewport %ux%u is smaller than the target", t->vw, t->vh); return FSPT_E_STATE; }
+  if (t->acc_ticks == 0) { fspt_set_error("fspt_temporal_accumulate: the accumulator holds no sample (render first)"); return FSPT_E_STATE; }
+  const size_t px = (size_t)t->W * t->H;
+  for (int k = 0; k < 2; ++k) {
+    if ((rc = dn_alloc(&t->tm_hist[k], px * 16)) || (rc = dn_alloc(&t->tm_g[k], px * 32))) return rc;
+  }
+  if ((rc = dn_alloc(&t->tm_m, px * 16))) return rc;
+  for (hipEvent_t &ev : t->tm_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
+  const int cur = t->tm_cur, nx = cur ^ 1;
+  fspt::TemporalGP g{};
+  g.scene = t->scene->d;
+  g.W = t->W; g.H = t->H;
+  std::memcpy(g.cam.P, cam->P, 12); std::memcpy(g.cam.I, cam->I, 12);
+  g.cam.fov_scale = cam->fov_scale;
+  g.prev = t->tm_cam;
+  g.has_prev = t->tm_valid ? 1u : 0u;
+  g.origin = (const float *)t->scene->motion;
+  g.g = t->tm_g[nx]; g.m = t->tm_m;
+  fspt::TemporalBP b{};
+  tm_fill_blend(b, q, t->W, t->H, (float)t->acc_ticks);
+  b.accum = t->accum; b.m = t->tm_m; b.g = t->tm_g[nx];
+  b.hist = t->tm_hist[cur]; b.g_prev = t->tm_g[cur];
+  b.out = t->tm_hist[nx];
+  b.has_hist = g.has_prev;
+  t->tm_gm_valid = false; t->tm_timed = false;
+  t->tm_dn_valid = false; // (a denoised frame of the previous history is not this one's)
+  t->tm_valid = false; // (an error below leaves no half-written history behind)
+  HIP_TRY(hipEventRecord(t->tm_ev[0], t->stream));
+  HIP_TRY(fspt::launch_temporal_gbuffer(g, t->stream));
+  HIP_TRY(hipEventRecord(t->tm_ev[1], t->stream));
+  HIP_TRY(fspt::launch_temporal_blend(b, t->stream));
+  HIP_TRY(hipEventRecord(t->tm_ev[2], t->stream));
+  t->tm_cur = nx;
+  t->tm_cam = g.cam;
+  t->tm_valid = true; t->tm_gm_valid = true; t->tm_timed = true;
+  if (out) {
+    HIP_TRY(hipMemcpyAsync(out, t->tm_hist[nx], px * 16, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+  }
+  return FSPT_OK;
+}
+
+int fspt_temporal_reset(fspt_target *t) {
+  if (!t) { fspt_set_error("fspt_temporal_reset: NULL target"); return FSPT_E_INVALID; }
+  FLUSH_OR_RETURN(t);
+  t->tm_valid = false;
+  t->tm_dn_valid = false;
+  return FSPT_OK;
+}
+
+int fspt_temporal_denoise(fspt_target *t, const fspt_denoise_params *prm, float *out) {
+  int rc = dn_enter(t, true, "fspt_temporal_denoise");
+  if (rc) return rc;
+  fspt_denoise_params q = {FSPT_DENOISE_ITERATIONS, FSPT_DENOISE_SIGMA_COLOR, FSPT_DENOISE_SIGMA_NORMAL, FSPT_DENOISE_SIGMA_DEPTH};
+  if (prm) q = *prm;
+  if ((rc = dn_check_params(q, "fspt_temporal_denoise"))) return rc;
+  if (!t->tm_valid) { fspt_set_error("fspt_temporal_denoise: no fspt_temporal_accumulate call yet"); return FSPT_E_STATE; }
+  if (!t->feat_valid) { fspt_set_error("fspt_temporal_denoise: no fspt_features call yet"); return FSPT_E_STATE; }
+  const size_t px = (size_t)t->W * t->H;
+  if ((rc = dn_alloc(&t->dn_out, px * 16))) return rc;
+  t->dn_valid = false;
+  if (q.iterations > 1u && ((rc = dn_alloc(&t->dn_tmp[0], px * 16)) || (rc = dn_alloc(&t->dn_tmp[1], px * 16)))) return rc;
+  t->tm_dn_valid = false;
+  HIP_TRY(dn_run(q, t->tm_hist[t->tm_cur], t->feat, t->W, t->H, t->dn_tmp, t->dn_out, t->stream));
+  t->dn_valid = true; t->tm_dn_valid = true;
+  if (out) {
+    HIP_TRY(hipMemcpyAsync(out, t->dn_out, px * 16, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+  }
+  return FSPT_OK;
+}
+
+int fspt_temporal_draw(fspt_target *t, float exposure, float saturation, int denoised, uint8_t *out_rgba8) {
+  int rc = dn_enter(t, out_rgba8 != nullptr, "fspt_temporal_draw");
+  if (rc) return rc;
+  if (!t->tm_valid) { fspt_set_error("fspt_temporal_draw: no fspt_temporal_accumulate call yet"); return FSPT_E_STATE; }
+  if (denoised && !t->tm_dn_valid) { fspt_set_error("fspt_temporal_draw: no fspt_temporal_denoise call since the last fspt_temporal_accumulate / fspt_denoise"); return FSPT_E_STATE; }
+  size_t n = (size_t)t->W * t->H;
+  uint32_t *d = nullptr;
+  HIP_TRY(hipMalloc((void **)&d, n * 4));
+  hipError_t e = fspt::launch_draw(denoised ? t->dn_out : t->tm_hist[t->tm_cur], t->W, t->H, exposure, saturation, 0, 0.0f, 1.0f, d, t->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_rgba8, d, n * 4, hipMemcpyDeviceToHost, t->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  hipFree(d);
+  if (e != hipSuccess) { fspt_set_error("fspt_temporal_draw: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
+  return FSPT_OK;
+}
+
+int fspt_temporal_read_gbuffer(fspt_target *t, float *g_out, float *m_out) {
+  int rc = dn_enter(t, g_out || m_out, "fspt_temporal_read_gbuffer");
+  if (rc) return rc;
+  if (!t->tm_gm_valid) { fspt_set_error("fspt_temporal_read_gbuffer: no fspt_temporal_accumulate call yet"); return FSPT_E_STATE; }
+  const size_t px = (size_t)t->W * t->H;
+  if (g_out) HIP_TRY(hipMemcpyAsync(g_out, t->tm_g[t->tm_cur], px * 32, hipMemcpyDeviceToHost, t->stream));
+  if (m_out) HIP_TRY(hipMemcpyAsync(m_out, t->tm_m, px * 16, hipMemcpyDeviceToHost, t->stream));
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  return FSPT_OK;
+}
+
+int fspt_temporal_last_ms(fspt_target *t, float ms[2]) {
+  if (!t || !ms) { fspt_set_error("fspt_temporal_last_ms: NULL argument"); return FSPT_E_INVALID; }
+  FLUSH_OR_RETURN(t);
+  if (!t->tm_timed) { fspt_set_error("fspt_temporal_last_ms: no fspt_temporal_accumulate call yet"); return FSPT_E_STATE; }
+  HIP_TRY(hipSetDevice(t->scene->device));
+  HIP_TRY(hipEventSynchronize(t->tm_ev[2]));
+  HIP_TRY(hipEventElapsedTime(&ms[0], t->tm_ev[0], t->tm_ev[1]));
+  HIP_TRY(hipEventElapsedTime(&ms[1], t->tm_ev[1], t->tm_ev[2]));
+  return FSPT_OK;
+}
+
+int fspt_temporal_eval(int device, const float *accum, const float *motion, const float *g, const float *hist, const float *g_prev,
+                       uint32_t W, uint32_t H, uint32_t n, const fspt_temporal_params *prm, float *out) {
+  if (!accum || !motion || !g || !out || (hist && !g_prev)) { fspt_set_error("fspt_temporal_eval: NULL argument"); return FSPT_E_INVALID; }
+  fspt_temporal_params q = TM_DEFAULTS;
+  if (prm) q = *prm;
+  int rc = tm_check_params(q, "fspt_temporal_eval");
+  if (rc) return rc;
+  if (n == 0) { fspt_set_error("fspt_temporal_eval: n must be >= 1"); return FSPT_E_INVALID; }
+  if ((rc = check_device(device))) return rc;
+  const size_t px = (size_t)W * H;
+  if (px == 0) return FSPT_OK;
+  HIP_TRY(hipSetDevice(device));
+  // one allocation, in float4: accum | motion | out | hist (px each) | g | g_prev (2 px each)
+  float4 *d = nullptr;
+  hipError_t e = hipMalloc((void **)&d, px * 16 * 8);
+  if (e == hipSuccess) e = hipMemcpy(d, accum, px * 16, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + px, motion, px * 16, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + 4 * px, g, px * 32, hipMemcpyHostToDevice);
+  if (e == hipSuccess && hist) e = hipMemcpy(d + 3 * px, hist, px * 16, hipMemcpyHostToDevice);
+  if (e == hipSuccess && hist) e = hipMemcpy(d + 6 * px, g_prev, px * 32, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    fspt::TemporalBP b{};
+    tm_fill_blend(b, q, W, H, (float)n);
+    b.accum = d; b.m = d + px; b.out = d + 2 * px; b.hist = d + 3 * px; b.g = d + 4 * px; b.g_prev = d + 6 * px;
+    b.has_hist = hist ? 1u : 0u;
+    e = fspt::launch_temporal_blend(b, nullptr);
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, d + 2 * px, px * 16, hipMemcpyDeviceToHost);
+  hipFree(d);
+  if (e != hipSuccess) { fspt_set_error("fspt_temporal_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
+  return FSPT_OK;
+}
+
+// Motion origin: floats 0-8 (v1, e1, e2) of every leaf slot's hit record as they are now.
+int fspt_scene_motion_begin(fspt_scene *s) {
+  if (!s) { fspt_set_error("fspt_scene_motion_begin: NULL scene"); return FSPT_E_INVALID; }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  if ((rc = geometry_order_targets(s))) return rc; // (an accumulate in flight reads the old snapshot)
+  if (!s->motion) HIP_TRY(hipMalloc(&s->motion, (s->n_slots ? s->n_slots : 1) * 36));
+  if (s->n_slots) HIP_TRY(hipMemcpy2D(s->motion, 36, s->shade, 192, 36, s->n_slots, hipMemcpyDeviceToDevice));
+  return FSPT_OK;
+}
+
+int fspt_scene_slot_triangles(fspt_scene *s, uint32_t *n_slots, uint32_t *slot_tri) {
+  if (!s || (!n_slots && !slot_tri)) { fspt_set_error("fspt_scene_slot_triangles: NULL argument"); return FSPT_E_INVALID; }
+  if (n_slots) *n_slots = (uint32_t)s->n_slots;
+  if (!slot_tri) return FSPT_OK;
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(slot_tri, s->slot_tri, s->n_slots * 4, hipMemcpyDeviceToHost));
+  return FSPT_OK;
+}
+
+int fspt_scene_motion_end(fspt_scene *s) {
+  if (!s) { fspt_set_error("fspt_scene_motion_end: NULL scene"); return FSPT_E_INVALID; }
+  if (!s->motion) return FSPT_OK;
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  if ((rc = geometry_order_targets(s))) return rc;
+  HIP_TRY(hipFree(s->motion));
+  s->motion = nullptr;
   return FSPT_OK;
 }
 

@@ -349,6 +349,35 @@ struct AtrousP {
 hipError_t launch_features(const FeatureP &p, hipStream_t stream);
 hipError_t launch_atrous(const AtrousP &p, hipStream_t stream);
 
+// temporal accumulation (fspt_temporal_*)
+constexpr int MOTION_FLOATS = 9;      // motion-origin snapshot: floats 0-8 (v1 e1 e2) of a slot's hit record
+constexpr float TM_KIND_NONE = 0.0f;  // M.w: no previous frame, or the point lies behind the previous camera
+constexpr float TM_KIND_HIT = 1.0f;
+constexpr float TM_KIND_MISS = 2.0f;
+constexpr float TM_SNAP = 1.0f / 128.0f; // a sample coordinate this close to an integer IS that integer
+struct TemporalGP {
+  DScene scene;
+  uint32_t W, H;
+  CameraP cam;          // this frame's camera (lens unused: the centre ray is a pinhole ray)
+  CameraP prev;         // the previous frame's
+  uint32_t has_prev;    // 0: first frame after create / reset - M.w = TM_KIND_NONE everywhere
+  const float *origin;  // motion-origin snapshot (MOTION_FLOATS floats per leaf slot) or NULL: static geometry
+  float4 *g;            // 2 x float4 per pixel: (t, slot bits, bv, bw), (macroNormal.xyz, hit)
+  float4 *m;            // float4 per pixel: (sx, sy, |v| or 0, kind)
+};
+struct TemporalBP {
+  const float4 *accum;  // I: the mean of n samples of this frame
+  const float4 *m, *g;  // this frame's motion and G-buffer
+  const float4 *hist, *g_prev; // the previous frame's result and G-buffer (unused when has_hist = 0)
+  float4 *out;          // the new history: rgb, length
+  uint32_t W, H;
+  uint32_t has_hist;
+  float n;              // acc_ticks
+  float alpha, max_history, depth_tol, normal_cos;
+};
+hipError_t launch_temporal_gbuffer(const TemporalGP &p, hipStream_t stream);
+hipError_t launch_temporal_blend(const TemporalBP &p, hipStream_t stream);
+
 // adaptive sampling (fspt_render_adaptive): after n ticks, with the snapshot S taken after m < n ticks
 struct AdaptiveP {
   const float4 *accum; // I = the mean of n ticks

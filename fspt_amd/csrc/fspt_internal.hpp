@@ -79,6 +79,9 @@ struct fspt_scene {
   } rf;
   // the most recent fspt_scene_rebuild_geometry (fspt_scene_last_rebuild_ms)
   struct Rebuild { float build_ms = 0.0f, install_ms = 0.0f, host_ms = 0.0f; uint32_t launches = 0, readbacks = 0; } rb;
+  // motion origin (fspt_scene_motion_begin): floats 0-8 of every leaf slot's hit record as they were at the
+  // last motion_begin (n_slots x 36 bytes; NULL: the scene is static).  A refit leaves it alone, a rebuild permutes it.
+  void *motion = nullptr;
 };
 // What fspt_scene_create derives from the reference tree's three integer words per node (left, right, triStart; a node
 // with triStart > -1 is a leaf) and nothing else: shared with fspt_scene_rebuild_geometry, which gets its words from the
@@ -294,6 +297,17 @@ struct fspt_target {
   uint64_t ad_samples = 0;
   std::vector<uint32_t> ad_count_host;
   std::vector<double> ad_err_host;
+  // temporal accumulation (fspt_temporal_*): allocated on the first accumulate, 112 bytes per pixel
+  float4 *tm_hist[2] = {nullptr, nullptr}; // history ping-pong (rgb, length); tm_cur = the current one
+  float4 *tm_g[2] = {nullptr, nullptr};    // G-buffer ping-pong: [tm_cur] = the last call's (the next call's g_prev)
+  float4 *tm_m = nullptr;                  // the last call's motion buffer
+  int tm_cur = 0;
+  bool tm_valid = false;                   // there is a history (an accumulate since create / fspt_temporal_reset)
+  bool tm_dn_valid = false;                // dn_out holds fspt_temporal_denoise's result of the CURRENT history (not fspt_denoise's)
+  bool tm_gm_valid = false;                // tm_g[tm_cur] / tm_m hold a call's buffers (fspt_temporal_read_gbuffer)
+  fspt::CameraP tm_cam{};                  // the previous frame's camera
+  hipEvent_t tm_ev[3] = {nullptr, nullptr, nullptr}; // around the two passes of the last call
+  bool tm_timed = false;
 };
 
 static const uint32_t WORK_RING = 4096;

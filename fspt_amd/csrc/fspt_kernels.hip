@@ -2666,6 +2666,130 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_atrous(const AtrousP p) {
   p.dst[ip] = o;
 }
 
+// ---- temporal accumulation (fspt_temporal_accumulate) ------------------------------------------------------
+// camera.fs's basis of a camera: basisX, basisY as camera_ray computes them (same float32 operations)
+FM_DEV void camera_basis(const CameraP &cam, V3 &Iv, V3 &Pv, V3 &basisX, V3 &basisY) {
+  Iv = v3(cam.I[0], cam.I[1], cam.I[2]); Pv = v3(cam.P[0], cam.P[1], cam.P[2]);
+  basisX = normalize(cross(Iv, v3(0.0f, 1.0f, 0.0f)));
+  basisY = normalize(cross(basisX, Iv));
+}
+// The G-buffer and motion pass: one thread per pixel of the whole target, 16 x 16-pixel blocks and the wave's LDS stack
+// like k_features.  The CENTRE ray - camera_ray without pixel jitter and without lens offset: o = P, d = normalize(screen -
+// P), `screen` by camera_ray's own operations - is traced to its closest hit; G = (t, slot bits, bv, bw), (macroNormal, hit).
+// The hit point's position in the PREVIOUS frame (the motion-origin snapshot's triangle of the same slot at the same
+// barycentric weights, or the point itself) is projected into the previous camera: M = (sx, sy, |v|, kind).
+__global__ __launch_bounds__(BLOCK_THREADS) void k_temporal_gbuffer(const TemporalGP p) {
+  extern __shared__ int lds_stack[];
+  const uint32_t tid = threadIdx.y * blockDim.x + threadIdx.x;
+  const int lane = (int)(tid & (WAVE - 1));
+  const int wave = (int)(tid / WAVE);
+  const DScene &S = p.scene;
+  int *stack = lds_stack + (size_t)wave * S.stack_n * WAVE + lane;
+  const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+  if (x >= p.W || y >= p.H) return;
+  const float fx = (float)x + 0.5f, fy = (float)y + 0.5f;
+  const float resx = (float)p.W, resy = (float)p.H;
+  const float uvx = fma_(fx / resx, 2.0f, -1.0f), uvy = fma_(fy / resy, 2.0f, -1.0f);
+  V3 Iv, Pv, basisX, basisY;
+  camera_basis(p.cam, Iv, Pv, basisX, basisY);
+  const float fov = p.cam.fov_scale;
+  const float icx = uvx * (resx / resy), icy = uvy * 1.0f;
+  V3 screen;
+  screen.x = (fma_(icy * basisY.x, fov, (icx * basisX.x) * fov) + Iv.x) + Pv.x;
+  screen.y = (fma_(icy * basisY.y, fov, (icx * basisX.y) * fov) + Iv.y) + Pv.y;
+  screen.z = (fma_(icy * basisY.z, fov, (icx * basisX.z) * fov) + Iv.z) + Pv.z;
+  const V3 o = Pv, d = normalize(screen - Pv);
+  Counters cnt = {0, 0, 0, 0, 0, 0};
+  int hitA, hitB;
+  float tB;
+  trace_rays<false, false>(S, stack, o, false, d, d, hitA, tB, hitB, cnt);
+  const size_t i = (size_t)y * p.W + x;
+  V3 n = v3(0.0f, 0.0f, 0.0f), xp = d;
+  float bv = 0.0f, bw = 0.0f;
+  const bool hit = hitB >= 0;
+  if (hit) {
+    HitGeom g;
+    hit_geom(S, hitB, o, d, tB, g);
+    V3 albedo, texEmissive, texNormal, baryNormal;
+    float metallic, rough;
+    material<true, false, false, true>(S, g.set, g.tcx, g.tcy, albedo, texEmissive, metallic, rough, texNormal);
+    n = macro_normal(g, texNormal, baryNormal);
+    bv = g.w.y; bw = g.w.z;
+    xp = g.origin; // o + t d
+    if (p.origin) { // where the same point of the same triangle was when fspt_scene_motion_begin took the snapshot
+      const float *mp = p.origin + (size_t)hitB * MOTION_FLOATS; // v1.xyz e1.xyz e2.xyz
+      xp = v3(fma_(bw, mp[6], fma_(bv, mp[3], mp[0])), fma_(bw, mp[7], fma_(bv, mp[4], mp[1])), fma_(bw, mp[8], fma_(bv, mp[5], mp[2])));
+    }
+  }
+  p.g[2 * i] = make_float4(hit ? tB : MAX_T, __int_as_float(hit ? hitB : -1), bv, bw);
+  p.g[2 * i + 1] = make_float4(n.x, n.y, n.z, hit ? 1.0f : 0.0f);
+  float4 m = make_float4(0.0f, 0.0f, 0.0f, TM_KIND_NONE);
+  if (p.has_prev) {
+    V3 I2, P2, bX, bY;
+    camera_basis(p.prev, I2, P2, bX, bY);
+    const V3 v = hit ? xp - P2 : d;
+    const float a = dot(v, I2) / dot(I2, I2);
+    if (a > 0.0f) {
+      const float den = a * p.prev.fov_scale;
+      const float jcx = dot(v, bX) / den, jcy = dot(v, bY) / den;
+      float sx = ((jcx * (resy / resx)) + 1.0f) * (resx * 0.5f) - 0.5f;
+      float sy = (jcy + 1.0f) * (resy * 0.5f) - 0.5f;
+      const float rx = floor_(sx + 0.5f), ry = floor_(sy + 0.5f);
+      if (abs_(sx - rx) <= TM_SNAP) sx = rx;
+      if (abs_(sy - ry) <= TM_SNAP) sy = ry;
+      m = make_float4(sx, sy, hit ? sqrt_(dot(v, v)) : 0.0f, hit ? TM_KIND_HIT : TM_KIND_MISS);
+    }
+  }
+  p.m[i] = m;
+}
+
+// The blend pass (image space only): the history at M's sample position - four bilinear taps, each tested against this
+// pixel's surface - blended with the accumulator.  One writer per pixel, vector stores, no atomics.
+__global__ __launch_bounds__(BLOCK_THREADS) void k_temporal_blend(const TemporalBP p) {
+  const int x = (int)(blockIdx.x * blockDim.x + threadIdx.x), y = (int)(blockIdx.y * blockDim.y + threadIdx.y);
+  const int W = (int)p.W, H = (int)p.H;
+  if (x >= W || y >= H) return;
+  const size_t ip = (size_t)y * W + x;
+  const float4 I = p.accum[ip];
+  const float4 m = p.m[ip];
+  float sr = 0.0f, sg = 0.0f, sb = 0.0f, sn = 0.0f, sw = 0.0f;
+  // (a position further than a pixel outside the image has no tap inside it: refused before the float -> int conversion)
+  if (p.has_hist && m.w != TM_KIND_NONE && m.x > -1.0f && m.y > -1.0f && m.x < (float)W && m.y < (float)H) {
+    const float4 g1 = p.g[2 * ip + 1];
+    const float flx = floor_(m.x), fly = floor_(m.y);
+    const float ax = m.x - flx, ay = m.y - fly;
+    const int x0 = (int)flx, y0 = (int)fly;
+    const float ztol = p.depth_tol * m.z;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = k & 1, j = k >> 1;
+      const int xx = x0 + i, yy = y0 + j;
+      const float w = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
+      if (xx < 0 || yy < 0 || xx >= W || yy >= H || !(w > 0.0f)) continue;
+      const size_t iq = (size_t)yy * W + xx;
+      const float4 q0 = p.g_prev[2 * iq], q1 = p.g_prev[2 * iq + 1];
+      if (q1.w != g1.w) continue;
+      if (g1.w != 0.0f) {
+        if (!(abs_(q0.x - m.z) <= ztol)) continue;
+        if (!(fma_(g1.z, q1.z, fma_(g1.y, q1.y, g1.x * q1.x)) >= p.normal_cos)) continue;
+      }
+      const float4 h = p.hist[iq];
+      sr = fma_(w, h.x, sr); sg = fma_(w, h.y, sg); sb = fma_(w, h.z, sb); sn = fma_(w, h.w, sn);
+      sw += w;
+    }
+  }
+  float4 o;
+  if (sw > 0.0f) {
+    const float Hr = sr / sw, Hg = sg / sw, Hb = sb / sw;
+    const float N = min_(sn / sw, p.max_history);
+    const float a = max_(p.n / (N + p.n), p.alpha);
+    o = make_float4(Hr + (I.x - Hr) * a, Hg + (I.y - Hg) * a, Hb + (I.z - Hb) * a, min_(N + p.n, p.max_history));
+  } else {
+    o = make_float4(I.x, I.y, I.z, min_(p.n, p.max_history));
+  }
+  p.out[ip] = o;
+}
+
 // ---- adaptive sampling (fspt_render_adaptive) -------------------------------------------------------------
 // One workgroup per active tile (list order).  Every thread sums its pixels (j = thread, thread + 256, ... of the tile,
 // row-major) in float64, the wave folds its 64 sums by shuffles and the four wave sums are added in wave order: the same
@@ -3031,6 +3155,19 @@ hipError_t launch_features(const FeatureP &p, hipStream_t stream) {
 
 hipError_t launch_atrous(const AtrousP &p, hipStream_t stream) {
   hipLaunchKernelGGL(k_atrous, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), 0, stream, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_temporal_gbuffer(const TemporalGP &p, hipStream_t stream) {
+  const size_t lds = stack_bytes(p.scene);
+  hipError_t e = allow_lds(k_temporal_gbuffer, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_temporal_gbuffer, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), lds, stream, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_temporal_blend(const TemporalBP &p, hipStream_t stream) {
+  hipLaunchKernelGGL(k_temporal_blend, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), 0, stream, p);
   return hipGetLastError();
 }
 

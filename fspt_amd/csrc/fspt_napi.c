@@ -751,6 +751,84 @@ static napi_value DrawDenoised(napi_env env, napi_callback_info info) {
   FSPT_OK_OR_THROW(fspt_draw_denoised((fspt_target *)h, (float)ex, (float)sat, (uint8_t *)p));
   return a[3];
 }
+/* temporal accumulation (include/fspt.h fspt_temporal_*, fspt_scene_motion_*) */
+static napi_value TemporalAccumulate(napi_env env, napi_callback_info info) {
+  /* temporalAccumulate(target, params (as render), {alpha, maxHistory, depthTol, normalCos} | null = defaults, Float32Array(W*H*4) | null) */
+  napi_value a[4]; void *h, *p = NULL; size_t n = 0; napi_valuetype vt;
+  if (get_args(env, info, 4, a)) return NULL;
+  fspt_camera_params cp;
+  if (parse_camera_params(env, a[1], &cp)) return NULL;
+  if (unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  fspt_temporal_params tp = {FSPT_TEMPORAL_ALPHA, FSPT_TEMPORAL_MAX_HISTORY, FSPT_TEMPORAL_DEPTH_TOL, FSPT_TEMPORAL_NORMAL_COS};
+  NAPI_OK(napi_typeof(env, a[2], &vt));
+  const int given = vt == napi_object;
+  if (given) {
+    double al, mh, dt, nc;
+    if (prop_f64(env, a[2], "alpha", tp.alpha, &al) || prop_f64(env, a[2], "maxHistory", tp.max_history, &mh) ||
+        prop_f64(env, a[2], "depthTol", tp.depth_tol, &dt) || prop_f64(env, a[2], "normalCos", tp.normal_cos, &nc)) return NULL;
+    if (!(al >= 0.0 && al <= 1.0 && mh >= 1.0 && dt >= 0.0 && nc >= -1.0 && nc <= 1.0)) {
+      napi_throw_range_error(env, NULL, "fspt_napi: temporalAccumulate needs alpha in [0, 1], maxHistory >= 1, depthTol >= 0, normalCos in [-1, 1]");
+      return NULL;
+    }
+    tp.alpha = (float)al; tp.max_history = (float)mh; tp.depth_tol = (float)dt; tp.normal_cos = (float)nc;
+  }
+  NAPI_OK(napi_typeof(env, a[3], &vt));
+  if (vt != napi_null && vt != napi_undefined) {
+    if (typed(env, a[3], napi_float32_array, 0, &p, &n) || check_target_len(env, h, n)) return NULL;
+  }
+  FSPT_OK_OR_THROW(fspt_temporal_accumulate((fspt_target *)h, &cp, given ? &tp : NULL, (float *)p));
+  return p ? a[3] : undefined(env);
+}
+static napi_value TemporalReset(napi_env env, napi_callback_info info) {
+  napi_value a[1]; void *h;
+  if (get_args(env, info, 1, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  FSPT_OK_OR_THROW(fspt_temporal_reset((fspt_target *)h));
+  return undefined(env);
+}
+static napi_value TemporalDenoise(napi_env env, napi_callback_info info) {
+  /* temporalDenoise(target, opts | null, Float32Array(W*H*4) | null): denoise's arguments, fspt_temporal_denoise */
+  napi_value a[3]; void *h, *p = NULL; size_t n = 0; napi_valuetype vt;
+  if (get_args(env, info, 3, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  fspt_denoise_params dp = {FSPT_DENOISE_ITERATIONS, FSPT_DENOISE_SIGMA_COLOR, FSPT_DENOISE_SIGMA_NORMAL, FSPT_DENOISE_SIGMA_DEPTH};
+  NAPI_OK(napi_typeof(env, a[1], &vt));
+  const int given = vt == napi_object;
+  if (given) {
+    double k, c, nn, z;
+    if (prop_f64(env, a[1], "iterations", dp.iterations, &k) || prop_f64(env, a[1], "sigmaColor", dp.sigma_color, &c) ||
+        prop_f64(env, a[1], "sigmaNormal", dp.sigma_normal, &nn) || prop_f64(env, a[1], "sigmaDepth", dp.sigma_depth, &z)) return NULL;
+    if (!(k >= 0.0 && k <= 16.0 && k == (double)(uint32_t)k)) { napi_throw_range_error(env, NULL, "fspt_napi: iterations must be an integer in [0, 16]"); return NULL; }
+    dp.iterations = (uint32_t)k; dp.sigma_color = (float)c; dp.sigma_normal = (float)nn; dp.sigma_depth = (float)z;
+  }
+  NAPI_OK(napi_typeof(env, a[2], &vt));
+  if (vt != napi_null && vt != napi_undefined) {
+    if (typed(env, a[2], napi_float32_array, 0, &p, &n) || check_target_len(env, h, n)) return NULL;
+  }
+  FSPT_OK_OR_THROW(fspt_temporal_denoise((fspt_target *)h, given ? &dp : NULL, (float *)p));
+  return p ? a[2] : undefined(env);
+}
+static napi_value TemporalDraw(napi_env env, napi_callback_info info) {
+  /* temporalDraw(target, exposure, saturation, denoised, Uint8Array(W*H*4)) */
+  napi_value a[5]; void *h, *p; size_t n; double ex, sat; bool den;
+  if (get_args(env, info, 5, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  if (get_f64(env, a[1], &ex) || get_f64(env, a[2], &sat)) return NULL;
+  NAPI_OK(napi_get_value_bool(env, a[3], &den));
+  if (typed(env, a[4], napi_uint8_array, 0, &p, &n) || check_target_len(env, h, n)) return NULL;
+  FSPT_OK_OR_THROW(fspt_temporal_draw((fspt_target *)h, (float)ex, (float)sat, den ? 1 : 0, (uint8_t *)p));
+  return a[4];
+}
+/* sceneMotionBegin(scene) / sceneMotionEnd(scene): guarded like every scene call */
+static napi_value SceneMotionBegin(napi_env env, napi_callback_info info) {
+  napi_value a[1]; void *h;
+  if (get_args(env, info, 1, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  FSPT_OK_OR_THROW(fspt_scene_motion_begin((fspt_scene *)h));
+  return undefined(env);
+}
+static napi_value SceneMotionEnd(napi_env env, napi_callback_info info) {
+  napi_value a[1]; void *h;
+  if (get_args(env, info, 1, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  FSPT_OK_OR_THROW(fspt_scene_motion_end((fspt_scene *)h));
+  return undefined(env);
+}
 static napi_value SetViewport(napi_env env, napi_callback_info info) {
   napi_value a[3]; void *h; uint32_t w, hh;
   if (get_args(env, info, 3, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
@@ -1167,7 +1245,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
       {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
-      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
+      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},
       {"renderAsync", RenderAsync}, {"multiCreate", MultiCreate}, {"multiDestroy", MultiDestroy}, {"multiTarget", MultiTarget},
       {"multiCamera", MultiCamera}, {"multiTrace", MultiTrace}, {"multiRender", MultiRender}, {"multiRenderAsync", MultiRenderAsync},

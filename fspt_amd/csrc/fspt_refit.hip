@@ -187,6 +187,24 @@ __global__ void k_rebuild_gather(const float4 *__restrict__ old_rec, size_t old_
   if (j == 0) slot_tri[sl] = ti;
 }
 
+// the motion-origin snapshot through the same map as k_rebuild_gather: 9 lanes per new leaf slot, one float each
+__global__ void k_rebuild_gather_motion(const float *__restrict__ old_mo, size_t old_slots, const uint32_t *__restrict__ map,
+                                        const uint32_t *__restrict__ order, const uint32_t *__restrict__ leaf_first, uint32_t n_leaves,
+                                        uint32_t LS, uint32_t T, float *__restrict__ mo) {
+  const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t sl = id / 9;
+  const uint32_t j = (uint32_t)(id % 9);
+  if (sl >= (size_t)n_leaves * LS) return;
+  const uint32_t ti = leaf_first[(uint32_t)(sl / LS)] + (uint32_t)(sl % LS);
+  float v = 0.0f;
+  if (ti < T) {
+    const uint32_t o = order[ti];
+    const uint32_t src = o < T ? map[o] : 0xFFFFFFFFu;
+    if ((size_t)src < old_slots) v = old_mo[(size_t)src * 9 + j];
+  }
+  mo[sl * 9 + j] = v;
+}
+
 // node r's words 12-15: its children's references (cref[2 r], cref[2 r + 1]), 0, 0; the boxes are the refit's
 __global__ void k_rebuild_nodes(const int32_t *__restrict__ cref, uint32_t n_interior, int4 *__restrict__ nodes) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -303,7 +321,7 @@ struct RebuildGuard {
     hipFree(d_map); hipFree(d_cref);
     for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
     if (keep) return;
-    hipFree(ns.nodes); hipFree(ns.quads); hipFree(ns.tris); hipFree(ns.slot_tri); hipFree(ns.shade);
+    hipFree(ns.nodes); hipFree(ns.quads); hipFree(ns.tris); hipFree(ns.slot_tri); hipFree(ns.shade); hipFree(ns.motion);
     refit_release(&ns);
   }
 };
@@ -371,6 +389,7 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
   REBUILD_ALLOC(&ns.tris, n_slots * 9 * 4);
   REBUILD_ALLOC(&ns.slot_tri, n_slots * 4);
   REBUILD_ALLOC(&ns.shade, n_slots * 192);
+  if (s->motion) REBUILD_ALLOC(&ns.motion, n_slots * 36);
   REBUILD_ALLOC(&ns.rf.stage, (size_t)T * 36 * 4); // tri | norm in the new leaf order; the scene's staging array from now on
   REBUILD_ALLOC(&G.d_map, (size_t)T * 4);
   REBUILD_ALLOC(&G.d_cref, cref.size() * 4);
@@ -394,6 +413,11 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
   hipLaunchKernelGGL(k_rebuild_gather, dim3(blocks_for(n_slots * 12, BS)), dim3(BS), 0, st, (const float4 *)s->shade, old_slots, G.d_map, G.bt.order,
                      ns.rf.d_leaf, nl, LS, T, (float4 *)ns.shade, (uint32_t *)ns.slot_tri, (float *)ns.tris);
   ++launches;
+  if (s->motion) { // slot s of the snapshot stays the triangle in slot s
+    hipLaunchKernelGGL(k_rebuild_gather_motion, dim3(blocks_for(n_slots * 9, BS)), dim3(BS), 0, st, (const float *)s->motion, old_slots, G.d_map,
+                       G.bt.order, ns.rf.d_leaf, nl, LS, T, (float *)ns.motion);
+    ++launches;
+  }
   if (NI) { hipLaunchKernelGGL(k_rebuild_nodes, dim3(blocks_for(NI, BS)), dim3(BS), 0, st, G.d_cref, NI, (int4 *)ns.nodes); ++launches; }
   HIP_TRY(hipGetLastError());
   int finite = 1, quads_ok = 0;
@@ -407,9 +431,10 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
   HIP_TRY(hipEventElapsedTime(&install_ms, G.ev[0], G.ev[1]));
   // 6. everything has succeeded: swap, then free the old tree
   G.keep = true;
-  hipFree(s->nodes); hipFree(s->quads); hipFree(s->tris); hipFree(s->slot_tri); hipFree(s->shade);
+  hipFree(s->nodes); hipFree(s->quads); hipFree(s->tris); hipFree(s->slot_tri); hipFree(s->shade); hipFree(s->motion);
   refit_release(s);
   s->rf = std::move(ns.rf);
+  s->motion = ns.motion;
   s->nodes = ns.nodes; s->quads = ns.quads; s->tris = ns.tris; s->slot_tri = ns.slot_tri; s->shade = ns.shade;
   s->d.nodes = (const float4 *)s->nodes;
   s->d.quads = quads_ok ? (const float4 *)s->quads : nullptr;

@@ -417,6 +417,40 @@ class PathTracer {
     if (out.length !== this.resolution[0] * this.resolution[1] * 4) throw new RangeError('drawDenoised: need W*H*4 bytes');
     return addon.drawDenoised(this._target, exposure === undefined ? 1 : exposure, saturation === undefined ? 1 : saturation, out);
   }
+  /** Temporal accumulation (include/fspt.h fspt_temporal_*, DESIGN.md 8.8), one call per frame after the frame's ticks:
+   *  temporalAccumulate(): the previous call's result reprojected through every pixel's first hit and blended with the
+   *  accumulator, {alpha, maxHistory, depthTol, normalCos} (omitted = the library's defaults) -> Float32Array(W*H*4) (rgb,
+   *  history length; out === null: nothing is read back); temporalReset(): the next call is a first one; temporalDenoise() / temporalDraw(): denoise() /
+   *  drawQuad() of the temporal result (denoised: of the last temporalDenoise); motionBegin(): snapshot the triangles -
+   *  what updateGeometry moves until the next temporalAccumulate is reprojected from there; motionEnd(): drop it. */
+  temporalAccumulate(opts, out) {
+    if (opts != null) {
+      const d = { alpha: 0, maxHistory: 64, depthTol: 0.05, normalCos: 0.95 };  // include/fspt_tuning.h FSPT_TEMPORAL_* (tests/test_temporal_cpu.py ties them)
+      for (const k of Object.keys(opts)) if (!(k in d)) throw new RangeError('temporalAccumulate: unknown parameter ' + k);
+      const v = Object.assign(d, opts);
+      if (!(v.alpha >= 0 && v.alpha <= 1 && v.maxHistory >= 1 && v.depthTol >= 0 && v.normalCos >= -1 && v.normalCos <= 1))
+        throw new RangeError('temporalAccumulate: need alpha in [0, 1], maxHistory >= 1, depthTol >= 0, normalCos in [-1, 1]');
+    }
+    if (out !== null) {  // (null: keep the result on the device, nothing is read back)
+      out = out || new Float32Array(this.resolution[0] * this.resolution[1] * 4);
+      if (out.length !== this.resolution[0] * this.resolution[1] * 4) throw new RangeError('temporalAccumulate: need W*H*4 floats');
+    }
+    return addon.temporalAccumulate(this._target, { P: this.eye, I: this.dir, fovScale: this.fovScale, lens: this.lensFeatures,
+      envTheta: this.envTheta, numBounces: this.numBounces }, opts || null, out);
+  }
+  temporalReset() { addon.temporalReset(this._target); }
+  temporalDenoise(opts, out) {
+    out = out || new Float32Array(this.resolution[0] * this.resolution[1] * 4);
+    if (out.length !== this.resolution[0] * this.resolution[1] * 4) throw new RangeError('temporalDenoise: need W*H*4 floats');
+    return addon.temporalDenoise(this._target, opts || null, out);
+  }
+  temporalDraw(exposure, saturation, denoised, out) {
+    out = out || new Uint8Array(this.resolution[0] * this.resolution[1] * 4);
+    if (out.length !== this.resolution[0] * this.resolution[1] * 4) throw new RangeError('temporalDraw: need W*H*4 bytes');
+    return addon.temporalDraw(this._target, exposure === undefined ? 1 : exposure, saturation === undefined ? 1 : saturation, !!denoised, out);
+  }
+  motionBegin() { addon.sceneMotionBegin(this._scene); }
+  motionEnd() { addon.sceneMotionEnd(this._scene); }
   /** gl.viewport(0, 0, w, h) of drawCamera / drawTracer (main.js:744,761); the reference: resolution * resScale. */
   setViewport(w, h) { addon.setViewport(this._target, w || 0, h || 0); }
   setShard(shard, nShards, tile) { addon.setShard(this._target, shard, nShards, tile || 32); }

@@ -45,6 +45,9 @@ def main():
     ap.add_argument("--rebuild-above", type=float, default=None, metavar="R",
                     help="--bvh refit: rebuild the tree in place on the GPU when a refitted frame's SAH cost exceeds R x the cost at "
                          "the last build (DESIGN 8.7; default: never)")
+    ap.add_argument("--temporal", action="store_true",
+                    help="--bvh refit --frames: reproject and blend every frame with the frames before it (DESIGN 8.8); with "
+                         "--atrous K the a-trous filter runs on the temporal result")
     ap.add_argument("--sampler", choices=("reference", "sobol"), default="reference",
                     help="the paths' random numbers (fspt_target_set_sampler; built-in scene)")
     ap.add_argument("--sampler-seed", type=int, default=0, help="seed of --sampler sobol, in [0, 2^32)")
@@ -70,8 +73,12 @@ def main():
         ap.error("--emitter-fraction must lie in (0, 1]")
     if args.emitter_fraction != 0.5 and not args.lights:
         ap.error("--emitter-fraction needs --lights")
-    if args.atrous and args.scene:
-        ap.error("--atrous is available for the built-in scene")
+    if args.temporal and args.adaptive is not None:
+        ap.error("--temporal cannot be combined with --adaptive")
+    if args.temporal and not (args.bvh == "refit" and args.frames):
+        ap.error("--temporal needs --bvh refit and --frames")
+    if args.atrous and args.scene and not args.temporal:
+        ap.error("--atrous is available for the built-in scene, or with --temporal")
     if args.scene and args.sampler != "reference":
         ap.error("--sampler is available for the built-in scene")
     if not 0 <= args.sampler_seed <= 0xFFFFFFFF:
@@ -88,7 +95,8 @@ def main():
             a, b = (int(x) for x in args.frames.split(":"))
             t0 = time.perf_counter()
             out = F.render_sequence(args.scene, range(a, b), args.out, args.width, args.height, args.assets, bvh=args.bvh,
-                                    rebuild_above=args.rebuild_above, **kw)
+                                    rebuild_above=args.rebuild_above,
+                                    temporal={"atrous": args.atrous} if args.temporal else None, **kw)
             print(f"{len(out)} frames in {time.perf_counter() - t0:.2f} s:", *out)
         else:
             arrays, settings = F.load_scene_file(args.scene, args.assets, bvh=args.bvh)

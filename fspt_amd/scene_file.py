@@ -139,7 +139,7 @@ def write_sample_map(path, counts, max_ticks):
 
 
 def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", rebuild_above=None,
-                    on_frame=None, **kw):
+                    on_frame=None, temporal=None, **kw):
     """frame=N sequencing (main.js:851-866, 966-969): for every N in `frames` load `scene_pattern.format(frame=N)`
     (the per-frame scene JSON the reference's server hands out for `?frame=N`), render it, write
     `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1.
@@ -151,10 +151,27 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     (re)build gets a new tree IN PLACE (Scene.rebuild_geometry, DESIGN 8.7: scene and tracer stay; the tree is the binned
     SAH of bvh="gpu" from then on, which renders 0.94-0.95x as fast as the sweep's); None, the default: never.  Any other
     frame - another triangle count, other materials, uvs, atlas or environment - builds a new scene.
-    on_frame(N, "build" | "refit" | "rebuild") reports what a frame did."""
+    on_frame(N, "build" | "refit" | "rebuild") reports what a frame did.
+    temporal (bvh="refit" only): True or a dict of PathTracer.temporal_accumulate's parameters, plus "atrous": K
+    for K a-trous iterations on the result.  Every frame then follows the protocol motion_begin, update_geometry, clear and
+    render, temporal_accumulate, and the picture written is temporal_draw of the result (`denoise`, the firefly filter of
+    draw(), does not apply to it; `adaptive` is refused); frame k renders with seed + k, so that the frames' noise is
+    independent.  A frame that builds a new scene starts a new history."""
     from PIL import Image
     written = []
     device = kw.get("device", 0)
+    if temporal is not None and temporal is not False:
+        if bvh != "refit":
+            raise ValueError('render_sequence: temporal needs bvh="refit" (one scene and tracer across the frames)')
+        temporal = {} if temporal is True else dict(temporal)
+        atrous = int(temporal.pop("atrous", 0))
+        from .tracer import _temporal_params
+        _temporal_params(temporal)  # (refuse bad parameters before the first frame renders)
+        if kw.get("adaptive") is not None:
+            # (tiles retire at different tick counts, the blend weighs every pixel with one n = the accumulator's ticks)
+            raise ValueError("render_sequence: temporal cannot be combined with adaptive sampling")
+    else:
+        temporal = None
 
     def save(n, rgba):
         out = out_pattern.format(frame=n)
@@ -193,6 +210,8 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                 g, settings = load_scene_file(path, asset_root, geometry_only=True)
                 if same_scene(base, g):
                     tri, norm = S.geometry_in_leaf_order(leaf_order, g.tri, g.norm)
+                    if temporal is not None:
+                        pt.scene.motion_begin()
                     pt.update_geometry(tri, norm)
                     how = "refit"
                     if rebuild_above is not None and pt.scene.sah_cost() > rebuild_above * cost0:
@@ -206,7 +225,15 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                 pt = PathTracer(base, width, height, device=device, num_bounces=bounces)
                 cost0 = pt.scene.sah_cost() if rebuild_above is not None else None
                 leaf_order = base.meta["tri_order"]
-            rgba, _ = _render_on(pt, settings, **opt)
+            if temporal is None:
+                rgba, _ = _render_on(pt, settings, **opt)
+            else:
+                _render_on(pt, settings, **{**opt, "seed": opt["seed"] + len(written), "denoise": False})  # (its draw is not the frame)
+                pt.temporal_accumulate(read=False, **temporal)
+                if atrous > 0:
+                    pt.features(8, opt["seed"])
+                    pt.temporal_denoise(iterations=atrous)
+                rgba = pt.temporal_draw(settings["exposure"], opt["saturation"], denoised=atrous > 0)
             if on_frame:
                 on_frame(n, how)
             save(n, rgba[::-1].copy())

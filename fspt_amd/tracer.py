@@ -61,6 +61,48 @@ def denoise_eval(accum, features, device=0, **params):
     return out
 
 
+TEMPORAL_DEFAULTS = {"alpha": 0.0, "max_history": 64.0, "depth_tol": 0.05, "normal_cos": 0.95}  # include/fspt_tuning.h FSPT_TEMPORAL_*
+
+
+def _temporal_params(params):
+    """fspt_temporal_params from keyword arguments (None: all defaults), validated like the library does."""
+    unknown = set(params) - set(TEMPORAL_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown temporal parameters {sorted(unknown)}")
+    if not params:
+        return None
+    v = {k: float(x) for k, x in {**TEMPORAL_DEFAULTS, **params}.items()}
+    if not (0.0 <= v["alpha"] <= 1.0 and v["max_history"] >= 1.0 and v["depth_tol"] >= 0.0 and -1.0 <= v["normal_cos"] <= 1.0):
+        raise ValueError("temporal parameters: need alpha in [0, 1], max_history >= 1, depth_tol >= 0, normal_cos in [-1, 1]")
+    return L.TemporalParams(v["alpha"], v["max_history"], v["depth_tol"], v["normal_cos"])
+
+
+def temporal_eval(accum, motion, g, hist=None, g_prev=None, n=1, device=0, **params):
+    """fspt_temporal_accumulate's blend pass on host arrays (fspt_temporal_eval, a test hook): accum, motion, hist float32
+    [H, W, 4], g, g_prev float32 [H, W, 8] (temporal_gbuffer's layouts), n = the accumulator's ticks -> the new history
+    float32 [H, W, 4] (rgb, length).  hist None: no history.  params: alpha, max_history, depth_tol, normal_cos."""
+    prm = _temporal_params(params)
+    accum = np.ascontiguousarray(accum, dtype=np.float32)
+    if accum.ndim != 3 or accum.shape[2] != 4:
+        raise ValueError(f"need accum [H, W, 4], got {accum.shape}")
+    H, W = accum.shape[:2]
+    arrs = {"motion": (motion, 4), "g": (g, 8)}
+    if hist is not None:
+        arrs.update({"hist": (hist, 4), "g_prev": (g_prev, 8)})
+    a = {}
+    for name, (x, c) in arrs.items():
+        if x is None or np.shape(x) != (H, W, c):
+            raise ValueError(f"need {name} [{H}, {W}, {c}], got {None if x is None else np.shape(x)}")
+        a[name] = np.ascontiguousarray(x, dtype=np.float32)
+    if int(n) < 1:
+        raise ValueError("n must be >= 1")
+    out = np.empty((H, W, 4), np.float32)
+    L.check(L.lib().fspt_temporal_eval(int(device), L.fptr(accum), L.fptr(a["motion"]), L.fptr(a["g"]),
+                                       L.fptr(a["hist"]) if hist is not None else None, L.fptr(a["g_prev"]) if hist is not None else None,
+                                       W, H, int(n), C.byref(prm) if prm is not None else None, L.fptr(out)))
+    return out
+
+
 def light_alias_table(weights):
     """The Vose alias table (float32 prob, uint32 alias) the light table stores for these weights (fspt_light_alias_table,
     a pure host function: no device needed)."""
@@ -238,6 +280,24 @@ class Scene:
         c = C.c_double()
         L.check(L.lib().fspt_scene_sah_cost(self._h, C.byref(c)))
         return float(c.value)
+
+    def slot_triangles(self):
+        """uint32 [n_slots]: the triangle (current leaf order) every leaf slot holds (fspt_scene_slot_triangles); values
+        >= n_tris mark empty slots.  What temporal_gbuffer's slot numbers index."""
+        n = C.c_uint32()
+        L.check(L.lib().fspt_scene_slot_triangles(self._h, C.byref(n), None))
+        out = np.zeros(n.value, np.uint32)
+        L.check(L.lib().fspt_scene_slot_triangles(self._h, None, L.u32ptr(out)))
+        return out
+
+    def motion_begin(self):
+        """Motion origin (fspt_scene_motion_begin): snapshot every triangle as it is now; what update_geometry moves
+        until the next temporal_accumulate is reprojected from there.  rebuild_geometry keeps the snapshot's slots in step."""
+        L.check(L.lib().fspt_scene_motion_begin(self._h))
+
+    def motion_end(self):
+        """Drop the motion origin: temporal_accumulate treats the scene as static again (fspt_scene_motion_end)."""
+        L.check(L.lib().fspt_scene_motion_end(self._h))
 
     def last_update_ms(self):
         """(GPU ms first kernel to last, kernels launched) of the most recent update_geometry."""
@@ -612,6 +672,57 @@ class PathTracer:
         out = np.zeros((H, W, 4), np.uint8)
         L.check(L.lib().fspt_draw_denoised(self._t, float(exposure), float(saturation), L.u8ptr(out)))
         return out
+
+    # ---- temporal accumulation (include/fspt.h fspt_temporal_*) ------------------------------------
+    def temporal_accumulate(self, read=True, **params):
+        """One frame of temporal accumulation: the previous call's result, reprojected through the first hit of every pixel's
+        centre ray of the set_camera() view, blended with the current accumulator (which is only read).  Returns the new
+        history float32 [H, W, 4] (rgb, history length), or None with read=False.  params: alpha, max_history, depth_tol,
+        normal_cos (TEMPORAL_DEFAULTS)."""
+        prm = _temporal_params(params)
+        W, H = self.resolution
+        out = np.zeros((H, W, 4), np.float32) if read else None
+        cp = self._camera_params()
+        L.check(L.lib().fspt_temporal_accumulate(self._t, C.byref(cp), C.byref(prm) if prm is not None else None,
+                                                 L.fptr(out) if read else None))
+        return out
+
+    def temporal_reset(self):
+        """Drop the history: the next temporal_accumulate behaves as the first (fspt_temporal_reset)."""
+        L.check(L.lib().fspt_temporal_reset(self._t))
+
+    def temporal_denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None):
+        """denoise() with the temporal result in the accumulator's place (fspt_temporal_denoise) -> float32 [H, W, 4]."""
+        W, H = self.resolution
+        out = np.zeros((H, W, 4), np.float32)
+        given = {"iterations": iterations, "sigma_color": sigma_color, "sigma_normal": sigma_normal, "sigma_depth": sigma_depth}
+        prm = None
+        if any(v is not None for v in given.values()):
+            v = {k: DENOISE_DEFAULTS[k] if x is None else x for k, x in given.items()}
+            prm = L.DenoiseParams(int(v["iterations"]), float(v["sigma_color"]), float(v["sigma_normal"]), float(v["sigma_depth"]))
+        L.check(L.lib().fspt_temporal_denoise(self._t, C.byref(prm) if prm is not None else None, L.fptr(out)))
+        return out
+
+    def temporal_draw(self, exposure=1.0, saturation=1.0, denoised=False):
+        """draw() of the temporal result, or of the last temporal_denoise() (fspt_temporal_draw): RGBA8 [H, W, 4]."""
+        W, H = self.resolution
+        out = np.zeros((H, W, 4), np.uint8)
+        L.check(L.lib().fspt_temporal_draw(self._t, float(exposure), float(saturation), 1 if denoised else 0, L.u8ptr(out)))
+        return out
+
+    def temporal_gbuffer(self):
+        """(G float32 [H, W, 8], M float32 [H, W, 4]) of the last temporal_accumulate (fspt_temporal_read_gbuffer): G = t, leaf
+        slot (int32 bits), bv, bw, macroNormal.xyz, hit; M = sx, sy, distance, kind (0 none / behind, 1 hit, 2 miss)."""
+        W, H = self.resolution
+        g, m = np.zeros((H, W, 8), np.float32), np.zeros((H, W, 4), np.float32)
+        L.check(L.lib().fspt_temporal_read_gbuffer(self._t, L.fptr(g), L.fptr(m)))
+        return g, m
+
+    def temporal_last_ms(self):
+        """(G-buffer and motion pass ms, blend pass ms) of the last temporal_accumulate, from HIP events."""
+        ms = (C.c_float * 2)()
+        L.check(L.lib().fspt_temporal_last_ms(self._t, ms))
+        return float(ms[0]), float(ms[1])
 
     def counters(self):
         c = L.Counters()

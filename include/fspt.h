@@ -104,10 +104,8 @@ int fspt_target_set_shard(fspt_target *target, uint32_t shard, uint32_t n_shards
  * fspt_read_radiance or fspt_draw (recorded ticks, the library's own streams); re-binding flushes the recorded ticks
  * into the old buffer, fspt_target_destroy DROPS them and never writes to a caller-owned buffer. */
 int fspt_target_bind_accumulator(fspt_target *target, void *device_ptr);
-/* The size the target was created with (fspt_read_radiance / fspt_draw write W*H*4 elements). */
-int fspt_target_size(fspt_target *target, uint32_t *width, uint32_t *height);
-/* Device pointer of the accumulator currently in use (W*H*4 floats). */
-int fspt_target_accumulator(fspt_target *target, void **device_ptr);
+int fspt_target_size(fspt_target *target, uint32_t *width, uint32_t *height); /* as created (fspt_read_radiance / fspt_draw write W*H*4 elements) */
+int fspt_target_accumulator(fspt_target *target, void **device_ptr); /* device pointer of the accumulator in use (W*H*4 floats) */
 
 /* drawCamera (main.js:741-756) -> camera.fs:37-46.  lens = lensFeatures = [1 - 1/focalDepth, apertureSize].
  * Like WebGL's draw calls the two-call form is DEFERRED: fspt_camera records its arguments, fspt_trace records the
@@ -125,12 +123,10 @@ int fspt_read_rays(fspt_target *target, float *pos, float *dir);
  * tick.  num_bounces is tracer.fs:9's compile-time NUM_BOUNCES made a
  * run-time argument (reference value 4).                                     */
 int fspt_trace(fspt_target *target, uint32_t tick, float rand_base, float env_theta, uint32_t num_bounces);
-/* Refraction does not advance the bounce counter (tracer.fs:488 `i--`: the reference's loop is unbounded); libfspt
- * ends every path after FSPT_MAX_BOUNCES loop iterations, and treats a larger num_bounces as that. */
+/* tracer.fs:488 `i--` (refraction) makes the reference's loop unbounded: libfspt ends a path after FSPT_MAX_BOUNCES iterations; a larger num_bounces means that. */
 #define FSPT_MAX_BOUNCES 64
 
-/* drawTracer in the reference's `mode=test` (main.js:879-883: bvh_test.fs): the camera ray's traversal-loop
- * iterations x 0.001 folded into the running mean (bvh_test.fs:224-232; no clamp). */
+/* drawTracer in `mode=test` (main.js:879-883, bvh_test.fs:224-232): the camera ray's traversal-loop iterations x 0.001 folded into the mean, no clamp. */
 int fspt_trace_test(fspt_target *target, uint32_t tick);
 
 /* tick() loop (main.js:838-857): n_ticks x (drawCamera + drawTracer) from tick first_tick, Math.random()*10000
@@ -148,8 +144,7 @@ int fspt_render(fspt_target *target, const fspt_camera_params *cam, uint32_t fir
 /* The host PRNG of fspt_render: state' = xorshift64*(state); returns float(u >> 40) * 2^-24 * 10000 in [0, 10000). */
 float fspt_rand_base_next(uint64_t *state);
 
-/* gl.viewport(0, 0, w, h) of drawCamera / drawTracer (main.js:744,761; resScale 0.25 while dragging, main.js:840):
- * only pixels x < w, y < h are traced, the rest keeps its contents.  0, 0 restores the whole target. */
+/* gl.viewport(0, 0, w, h) (main.js:744,761; resScale 0.25 while dragging, main.js:840): only pixels x < w, y < h are traced; 0, 0 = the whole target. */
 int fspt_target_set_viewport(fspt_target *target, uint32_t w, uint32_t h);
 enum { FSPT_SAMPLER_REFERENCE = 0, FSPT_SAMPLER_SOBOL = 1 }; /* the paths' random numbers: rnd() bit for bit (default) | Owen-scrambled Sobol (DESIGN 8.2) */
 int fspt_target_set_sampler(fspt_target *target, int sampler, uint32_t seed); int fspt_target_get_sampler(fspt_target *target, int *sampler, uint32_t *seed);
@@ -171,16 +166,14 @@ typedef struct fspt_adaptive_params { double target_rel_mse; uint32_t max_ticks,
 int fspt_render_adaptive(fspt_target *target, const fspt_camera_params *cam, const fspt_adaptive_params *params, uint64_t seed);
 /* The last fspt_render_adaptive's ticks per pixel: W*H counts, rows bottom-up, 0 outside its viewport (FSPT_E_STATE before one). */
 int fspt_read_sample_counts(fspt_target *target, uint32_t *out);
-/* What draw.fs:87 reads: RGBA32F, W*H*4 floats, row 0 = bottom, a = 1.
- * Blocking (syncs the stream first). */
+/* What draw.fs:87 reads: RGBA32F, W*H*4 floats, row 0 = bottom, a = 1.  Blocking (syncs the stream first). */
 int fspt_read_radiance(fspt_target *target, float *out);
 
 /* drawQuad (main.js:809-824) -> draw.fs:82-93: exposure, ACES fit, saturation, gamma 1/2.2 and the
  * optional 5x5 firefly filter (draw.fs:52-80, max_sigma = the `sigma` slider) on the current
  * accumulator; writes what the canvas would hold: RGBA8, W*H*4 bytes, row 0 = bottom.  Blocking. */
 int fspt_draw(fspt_target *target, float exposure, float saturation, int denoise, float max_sigma, uint8_t *out_rgba8);
-/* The same with draw.fs's `scale` uniform (draw.fs:59,87: texel = ivec2(gl_FragCoord * scale)); the reference
- * draws with scale 0.25 while the camera is being dragged (main.js:819,840), 1.0 otherwise. */
+/* The same with draw.fs's `scale` uniform (draw.fs:59,87: texel = ivec2(gl_FragCoord * scale)): 0.25 while the camera is dragged (main.js:819,840), else 1. */
 int fspt_draw_scaled(fspt_target *target, float exposure, float saturation, int denoise, float max_sigma, float scale, uint8_t *out_rgba8);
 /* drawQuad inside tick() (main.js:838-857), pipelined with one frame of latency: enqueues the ticks
  * recorded since the last flush and fspt_draw_scaled's k_draw of the result, then writes the frame the PREVIOUS call
@@ -205,9 +198,16 @@ typedef struct fspt_denoise_params { uint32_t iterations; float sigma_color, sig
 #define FSPT_DENOISE_SIGMA_DEPTH 0.05f
 int fspt_features(fspt_target *t, const fspt_camera_params *cam, uint32_t samples, uint64_t seed); /* samples >= 1 */
 int fspt_read_features(fspt_target *t, float *out);              /* W*H*8 floats, rows bottom-up; blocking */
-int fspt_denoise(fspt_target *t, const fspt_denoise_params *p,    /* NULL = defaults; iterations <= 16 */
-                 float *out);                                      /* W*H*4 floats, or NULL: keep on the device */
+int fspt_denoise(fspt_target *t, const fspt_denoise_params *p, float *out); /* p NULL = defaults, iterations <= 16; out W*H*4 floats or NULL: keep on the device */
 int fspt_draw_denoised(fspt_target *t, float exposure, float saturation, uint8_t *out_rgba8);
+/* Temporal accumulation (DESIGN 8.8; the rule, defaults and ranges: fspt_tuning.h).  One call = one frame: the previous call's result, reprojected through the first hit of
+ * every pixel's centre ray, is blended with the accumulator (only read).  fspt_scene_motion_begin snapshots the triangles: what moves until the next accumulate is reprojected from there. */
+typedef struct fspt_temporal_params { float alpha, max_history, depth_tol, normal_cos; } fspt_temporal_params;
+int fspt_temporal_accumulate(fspt_target *t, const fspt_camera_params *cam, const fspt_temporal_params *p, float *out); /* p NULL = defaults; out W*H*4 (rgb, length) or NULL */
+int fspt_temporal_reset(fspt_target *t);                                                    /* the next accumulate is a first one */
+int fspt_temporal_denoise(fspt_target *t, const fspt_denoise_params *p, float *out);        /* fspt_denoise of the temporal result */
+int fspt_temporal_draw(fspt_target *t, float exposure, float saturation, int denoised, uint8_t *out_rgba8); /* fspt_draw / fspt_draw_denoised of it */
+int fspt_scene_motion_begin(fspt_scene *s); int fspt_scene_motion_end(fspt_scene *s);       /* snapshot (a rebuild permutes it) | drop it: static scene */
 
 /* intersectScene (tracer.fs:366-404) as a stand-alone entry: n rays (origin xyz, dir xyz) -> closest hit t and
  * triangle index (-1 = miss, t = 1e5), optionally loop-iteration and leaf-visit counts per ray.  Host pointers. */

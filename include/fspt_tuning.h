@@ -160,6 +160,33 @@ int fspt_sampler_eval(int device, uint32_t seed, const uint32_t *pixel, const ui
  * p NULL = defaults; the parameters fspt_denoise refuses are refused here too, with the same codes. */
 int fspt_denoise_eval(int device, const float *accum, const float *features, uint32_t W, uint32_t H,
                       const fspt_denoise_params *p, float *out);
+/* fspt_temporal_accumulate (fspt.h).  Pass 1, per pixel p: the CENTRE ray (fspt_camera's ray without pixel jitter and
+ * lens offset) to its closest hit: G(p) = (t, leaf slot as int bits, bv, bw), (macroNormal.xyz, hit); a miss: (1e5, -1, 0, 0), (0, 0, 0, 0).
+ * X' = the hit point (static scene) or v1' + bv e1' + bw e2' of the same slot in fspt_scene_motion_begin's snapshot; v = X' - P_prev
+ * (a miss: v = the ray direction); with the previous call's camera (bX, bY, I, fov): a = v.I / I.I (a <= 0: behind), icx = v.bX / (a fov),
+ * icy = v.bY / (a fov), sx = (icx H / W + 1) W / 2 - 0.5, sy = (icy + 1) H / 2 - 0.5, each SNAPPED to the nearest integer when within
+ * 1/128 of it; M(p) = (sx, sy, |v| or 0 for a miss, kind), kind 0 = no previous call or behind, 1 = hit, 2 = miss.
+ * Pass 2: taps q = floor(sx, sy) + {0, 1}^2 with bilinear weights w_q; a tap counts when w_q > 0, q lies in the image, hit(q) = hit(p),
+ * and for hits |t_prev(q) - M.z| <= depth_tol M.z and n(p) . n_prev(q) >= normal_cos.  H = sum w_q hist(q).rgb / sum w_q,
+ * N = min(sum w_q hist(q).w / sum w_q, max_history), a = max(n / (N + n), alpha), n = the accumulator's ticks:
+ * out = (H + (I - H) a, min(N + n, max_history)); no tap counts: out = (I.rgb, min(n, max_history)).  Then out is the history, G the
+ * previous G-buffer, cam the previous camera.  Ranges: alpha in [0, 1], max_history >= 1, depth_tol >= 0, normal_cos in [-1, 1] (else
+ * FSPT_E_INVALID); FSPT_E_STATE: no tick in the accumulator, a sharded target, a viewport smaller than the target. */
+#define FSPT_TEMPORAL_ALPHA 0.0f         /* defaults (params NULL): the best row of DESIGN 8.8's scan */
+#define FSPT_TEMPORAL_MAX_HISTORY 64.0f
+#define FSPT_TEMPORAL_DEPTH_TOL 0.05f
+#define FSPT_TEMPORAL_NORMAL_COS 0.95f
+/* G (W*H*8 floats) and M (W*H*4 floats) of the last fspt_temporal_accumulate, rows bottom-up; either may be NULL.  Blocking. */
+int fspt_temporal_read_gbuffer(fspt_target *t, float *g_out, float *m_out);
+/* The scene's leaf slots (what G's slot and the traversal's hit index address) and, per slot, the triangle it holds in the scene's
+ * current leaf order (0xFFFFFFFF-style values beyond n_tris: an empty slot).  Either pointer may be NULL; sizes first. */
+int fspt_scene_slot_triangles(fspt_scene *s, uint32_t *n_slots, uint32_t *slot_tri);
+/* GPU ms of the last call's two passes, from HIP events: ms[0] the G-buffer and motion pass, ms[1] the blend pass.  Blocking. */
+int fspt_temporal_last_ms(fspt_target *t, float ms[2]);
+/* Test hook: the blend pass alone on host arrays in the library's layouts - accum, motion, hist W*H*4 floats, g, g_prev W*H*8
+ * floats, n = the accumulator's ticks (>= 1) - out: W*H*4.  hist NULL (then g_prev may be NULL): no history. */
+int fspt_temporal_eval(int device, const float *accum, const float *motion, const float *g, const float *hist, const float *g_prev,
+                       uint32_t W, uint32_t H, uint32_t n, const fspt_temporal_params *p, float *out);
 /* fspt_target_set_lights (fspt.h): FSPT_LIGHTS_EMITTERS lets each shading vertex spend its shadow ray on a
  * point of an emissive triangle (probability q = emitter_fraction, in (0, 1]; at most 0.875 with an environment map, 1
  * when the scene has none)

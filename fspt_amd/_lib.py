@@ -144,6 +144,11 @@ SIGNATURES = {
     "fspt_temporal_last_ms": (C.c_int, [_VP, _F]),
     "fspt_temporal_eval": (C.c_int, [C.c_int, _F, _F, _F, _F, _F, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(TemporalParams), _F]),
     "fspt_scene_slot_triangles": (C.c_int, [_VP, _U32, _U32]),
+    "fspt_temporal_set_moments": (C.c_int, [_VP, C.c_int]),
+    "fspt_temporal_denoise_variance": (C.c_int, [_VP, C.POINTER(DenoiseParams), _F]),
+    "fspt_temporal_read_variance": (C.c_int, [_VP, _F, _F]),
+    "fspt_svgf_last_ms": (C.c_int, [_VP, _F]),
+    "fspt_svgf_eval": (C.c_int, [C.c_int, _F, _F, _F, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), _F, _F, _F]),
     "fspt_scene_motion_begin": (C.c_int, [_VP]),
     "fspt_scene_motion_end": (C.c_int, [_VP]),
     "fspt_intersect": (C.c_int, [_VP, _F, C.c_uint32, _F, C.POINTER(C.c_int32), _U32, _U32]),

@@ -775,6 +775,8 @@ int fspt_target_destroy(fspt_target *t) {
   hipFree(t->feat); hipFree(t->dn_tmp[0]); hipFree(t->dn_tmp[1]); hipFree(t->dn_out);
   hipFree(t->tm_hist[0]); hipFree(t->tm_hist[1]); hipFree(t->tm_g[0]); hipFree(t->tm_g[1]); hipFree(t->tm_m);
   for (hipEvent_t ev : t->tm_ev) if (ev) hipEventDestroy(ev);
+  hipFree(t->tm_mom[0]); hipFree(t->tm_mom[1]); hipFree(t->tm_var);
+  for (hipEvent_t ev : t->sv_ev) if (ev) hipEventDestroy(ev);
   hipFree(t->ad_snap); hipFree(t->ad_list[0]); hipFree(t->ad_list[1]); hipFree(t->ad_count); hipFree(t->ad_err);
   {
     fspt_target::WfLane &ln = t->wf;
@@ -1783,6 +1785,7 @@ int fspt_temporal_accumulate(fspt_target *t, const fspt_camera_params *cam, cons
   if (t->n_shards > 1) { fspt_set_error("fspt_temporal_accumulate: sharded target (its accumulator holds a part of the frame)"); return FSPT_E_STATE; }
   if (t->vw != t->W || t->vh != t->H) { fspt_set_error("fspt_temporal_accumulate: the viewport %ux%u is smaller than the target", t->vw, t->vh); return FSPT_E_STATE; }
   if (t->acc_ticks == 0) { fspt_set_error("fspt_temporal_accumulate: the accumulator holds no sample (render first)"); return FSPT_E_STATE; }
+  if (t->tm_moments && !t->feat_valid) { fspt_set_error("fspt_temporal_accumulate: moments are on and there is no fspt_features call yet (the input is demodulated by its albedo)"); return FSPT_E_STATE; }
   const size_t px = (size_t)t->W * t->H;
   for (int k = 0; k < 2; ++k) {
     if ((rc = dn_alloc(&t->tm_hist[k], px * 16)) || (rc = dn_alloc(&t->tm_g[k], px * 32))) return rc;
@@ -1805,6 +1808,11 @@ int fspt_temporal_accumulate(fspt_target *t, const fspt_camera_params *cam, cons
   b.hist = t->tm_hist[cur]; b.g_prev = t->tm_g[cur];
   b.out = t->tm_hist[nx];
   b.has_hist = g.has_prev;
+  if (t->tm_moments) { // the moments instantiation: the same taps also carry (M1, M2)
+    b.feat = t->feat; b.mom_hist = t->tm_mom[cur]; b.mom_out = t->tm_mom[nx];
+    b.has_mom = b.has_hist; // (the two histories start together: fspt_temporal_set_moments, fspt_temporal_reset)
+  }
+  t->tm_mom_valid = false; t->tm_var_valid = false;
   t->tm_gm_valid = false; t->tm_timed = false;
   t->tm_dn_valid = false; // (a denoised frame of the previous history is not this one's)
   t->tm_valid = false; // (an error below leaves no half-written history behind)
@@ -1816,6 +1824,8 @@ int fspt_temporal_accumulate(fspt_target *t, const fspt_camera_params *cam, cons
   t->tm_cur = nx;
   t->tm_cam = g.cam;
   t->tm_valid = true; t->tm_gm_valid = true; t->tm_timed = true;
+  t->tm_mom_valid = t->tm_moments;
+  t->tm_n = (float)t->acc_ticks;
   if (out) {
     HIP_TRY(hipMemcpyAsync(out, t->tm_hist[nx], px * 16, hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
@@ -1828,6 +1838,7 @@ int fspt_temporal_reset(fspt_target *t) {
   FLUSH_OR_RETURN(t);
   t->tm_valid = false;
   t->tm_dn_valid = false;
+  t->tm_mom_valid = false; t->tm_var_valid = false; // (the moments go with the history they describe)
   return FSPT_OK;
 }
 
@@ -1922,6 +1933,149 @@ int fspt_temporal_eval(int device, const float *accum, const float *motion, cons
   if (e == hipSuccess) e = hipMemcpy(out, d + 2 * px, px * 16, hipMemcpyDeviceToHost);
   hipFree(d);
   if (e != hipSuccess) { fspt_set_error("fspt_temporal_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
+  return FSPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// SVGF variance guidance (k_temporal_blend<true> / k_svgf_variance / k_atrous<true>)
+// ---------------------------------------------------------------------------
+int fspt_temporal_set_moments(fspt_target *t, int on) {
+  int rc = dn_enter(t, true, "fspt_temporal_set_moments");
+  if (rc) return rc;
+  if (!on) {
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    hipFree(t->tm_mom[0]); hipFree(t->tm_mom[1]); hipFree(t->tm_var);
+    t->tm_mom[0] = t->tm_mom[1] = nullptr; t->tm_var = nullptr;
+    t->tm_moments = t->tm_mom_valid = t->tm_var_valid = false;
+    return FSPT_OK;
+  }
+  if (t->n_shards > 1) { fspt_set_error("fspt_temporal_set_moments: sharded target"); return FSPT_E_STATE; }
+  if (t->tm_moments) return FSPT_OK;
+  const size_t px = (size_t)t->W * t->H;
+  for (int k = 0; k < 2; ++k) {
+    if (!t->tm_mom[k]) HIP_TRY(hipMalloc((void **)&t->tm_mom[k], px * 8));
+  }
+  t->tm_moments = true;
+  // off -> on drops the colour history with it, as fspt_temporal_reset does: moments of one frame beside a colour history
+  // of N would blend at the colour's n / (N + n), stay one sample's (M2 - M1 M1 = 0) and leave the guided filter a delta
+  t->tm_mom_valid = false; t->tm_var_valid = false;
+  t->tm_valid = false; t->tm_dn_valid = false;
+  return FSPT_OK;
+}
+
+static const fspt_denoise_params SV_DEFAULTS = {FSPT_SVGF_ITERATIONS, FSPT_SVGF_SIGMA_L, FSPT_SVGF_SIGMA_NORMAL, FSPT_SVGF_SIGMA_DEPTH};
+// k_svgf_variance, then the K variance-guided launches of k_atrous: hist -> out as dn_run, the variance from `var` into
+// the first iteration and in the .w lane between them; var_out (test hook; may be NULL): the last iteration's variance
+static hipError_t sv_run(const fspt_denoise_params &q, const float4 *hist, const float2 *mom, const float4 *feat, uint32_t W, uint32_t H,
+                         float n, float4 *const tmp[2], float4 *out, float *var, float *var_out, hipStream_t stream, hipEvent_t mid) {
+  const size_t px = (size_t)W * H;
+  fspt::SvgfVarP v{};
+  v.hist = hist; v.mom = mom; v.feat = feat; v.var = var;
+  v.W = W; v.H = H; v.n = n;
+  v.sn = q.sigma_normal; v.sz = q.sigma_depth;
+  hipError_t e = fspt::launch_svgf_variance(v, stream);
+  if (e == hipSuccess && mid) e = hipEventRecord(mid, stream);
+  if (e != hipSuccess) return e;
+  if (q.iterations == 0) {
+    if (var_out && (e = hipMemcpyAsync(var_out, var, px * 4, hipMemcpyDeviceToDevice, stream)) != hipSuccess) return e;
+    return hipMemcpyAsync(out, hist, px * 16, hipMemcpyDeviceToDevice, stream);
+  }
+  for (uint32_t k = 0; k < q.iterations; ++k) {
+    fspt::AtrousP p{};
+    p.src = k == 0 ? hist : tmp[(k - 1) & 1u];
+    p.dst = k + 1 == q.iterations ? out : tmp[k & 1u];
+    p.feat = feat;
+    p.W = W; p.H = H;
+    p.step = 1 << k;
+    p.demod = k == 0; p.remod = k + 1 == q.iterations;
+    p.sn = q.sigma_normal;
+    p.sz_step = std::ldexp(q.sigma_depth, (int)k);
+    p.var = var; p.sl = q.sigma_color;
+    p.var_dst = p.remod ? var_out : nullptr;
+    if ((e = fspt::launch_atrous_variance(p, stream)) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+int fspt_temporal_denoise_variance(fspt_target *t, const fspt_denoise_params *prm, float *out) {
+  int rc = dn_enter(t, true, "fspt_temporal_denoise_variance");
+  if (rc) return rc;
+  fspt_denoise_params q = SV_DEFAULTS;
+  if (prm) q = *prm;
+  if ((rc = dn_check_params(q, "fspt_temporal_denoise_variance"))) return rc;
+  if (t->n_shards > 1) { fspt_set_error("fspt_temporal_denoise_variance: sharded target"); return FSPT_E_STATE; }
+  if (!t->tm_moments) { fspt_set_error("fspt_temporal_denoise_variance: moments are off (fspt_temporal_set_moments)"); return FSPT_E_STATE; }
+  if (!t->tm_valid || !t->tm_mom_valid) { fspt_set_error("fspt_temporal_denoise_variance: no fspt_temporal_accumulate call since the moments were switched on / the last reset"); return FSPT_E_STATE; }
+  if (!t->feat_valid) { fspt_set_error("fspt_temporal_denoise_variance: no fspt_features call yet"); return FSPT_E_STATE; }
+  const size_t px = (size_t)t->W * t->H;
+  if ((rc = dn_alloc(&t->dn_out, px * 16))) return rc;
+  t->dn_valid = false;
+  if (q.iterations > 1u && ((rc = dn_alloc(&t->dn_tmp[0], px * 16)) || (rc = dn_alloc(&t->dn_tmp[1], px * 16)))) return rc;
+  if (!t->tm_var) HIP_TRY(hipMalloc((void **)&t->tm_var, px * 4));
+  for (hipEvent_t &ev : t->sv_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
+  t->tm_dn_valid = false; t->tm_var_valid = false; t->sv_timed = false;
+  HIP_TRY(hipEventRecord(t->sv_ev[0], t->stream));
+  HIP_TRY(sv_run(q, t->tm_hist[t->tm_cur], t->tm_mom[t->tm_cur], t->feat, t->W, t->H, t->tm_n, t->dn_tmp, t->dn_out, t->tm_var, nullptr, t->stream, t->sv_ev[1]));
+  HIP_TRY(hipEventRecord(t->sv_ev[2], t->stream));
+  t->dn_valid = true; t->tm_dn_valid = true; t->tm_var_valid = true; t->sv_timed = true;
+  if (out) {
+    HIP_TRY(hipMemcpyAsync(out, t->dn_out, px * 16, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+  }
+  return FSPT_OK;
+}
+
+int fspt_temporal_read_variance(fspt_target *t, float *var_out, float *mom_out) {
+  int rc = dn_enter(t, var_out || mom_out, "fspt_temporal_read_variance");
+  if (rc) return rc;
+  if (!t->tm_moments || !t->tm_valid || !t->tm_mom_valid) { fspt_set_error("fspt_temporal_read_variance: no fspt_temporal_accumulate call with moments on yet"); return FSPT_E_STATE; }
+  if (var_out && !t->tm_var_valid) { fspt_set_error("fspt_temporal_read_variance: no fspt_temporal_denoise_variance call since the last fspt_temporal_accumulate"); return FSPT_E_STATE; }
+  const size_t px = (size_t)t->W * t->H;
+  if (var_out) HIP_TRY(hipMemcpyAsync(var_out, t->tm_var, px * 4, hipMemcpyDeviceToHost, t->stream));
+  if (mom_out) HIP_TRY(hipMemcpyAsync(mom_out, t->tm_mom[t->tm_cur], px * 8, hipMemcpyDeviceToHost, t->stream));
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  return FSPT_OK;
+}
+
+int fspt_svgf_last_ms(fspt_target *t, float ms[2]) {
+  if (!t || !ms) { fspt_set_error("fspt_svgf_last_ms: NULL argument"); return FSPT_E_INVALID; }
+  FLUSH_OR_RETURN(t);
+  if (!t->sv_timed) { fspt_set_error("fspt_svgf_last_ms: no fspt_temporal_denoise_variance call yet"); return FSPT_E_STATE; }
+  HIP_TRY(hipSetDevice(t->scene->device));
+  HIP_TRY(hipEventSynchronize(t->sv_ev[2]));
+  HIP_TRY(hipEventElapsedTime(&ms[0], t->sv_ev[0], t->sv_ev[1]));
+  HIP_TRY(hipEventElapsedTime(&ms[1], t->sv_ev[1], t->sv_ev[2]));
+  return FSPT_OK;
+}
+
+int fspt_svgf_eval(int device, const float *hist, const float *moments, const float *features, uint32_t W, uint32_t H, uint32_t n,
+                   const fspt_denoise_params *prm, float *out, float *var_in, float *var_out) {
+  if (!hist || !moments || !features || !out) { fspt_set_error("fspt_svgf_eval: NULL argument"); return FSPT_E_INVALID; }
+  fspt_denoise_params q = SV_DEFAULTS;
+  if (prm) q = *prm;
+  int rc = dn_check_params(q, "fspt_svgf_eval");
+  if (rc) return rc;
+  if (n == 0) { fspt_set_error("fspt_svgf_eval: n must be >= 1"); return FSPT_E_INVALID; }
+  if ((rc = check_device(device))) return rc;
+  const size_t px = (size_t)W * H;
+  if (px == 0) return FSPT_OK;
+  HIP_TRY(hipSetDevice(device));
+  // one allocation, in float4: hist | out | tmp[0] | tmp[1] (px each) | features (2 px) | moments (px / 2) | var, var' (px / 4 each)
+  float4 *d = nullptr;
+  hipError_t e = hipMalloc((void **)&d, px * 16 * 7 + 64);
+  float4 *const tmp[2] = {d + 2 * px, d + 3 * px};
+  float2 *const mom = (float2 *)(d + 6 * px);
+  float *const var = (float *)(mom + px), *const var2 = var + px;
+  if (e == hipSuccess) e = hipMemcpy(d, hist, px * 16, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + 4 * px, features, px * 32, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(mom, moments, px * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = sv_run(q, d, mom, d + 4 * px, W, H, (float)n, tmp, d + px, var, var2, nullptr, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, d + px, px * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && var_in) e = hipMemcpy(var_in, var, px * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && var_out) e = hipMemcpy(var_out, var2, px * 4, hipMemcpyDeviceToHost);
+  hipFree(d);
+  if (e != hipSuccess) { fspt_set_error("fspt_svgf_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
   return FSPT_OK;
 }
 

@@ -345,9 +345,14 @@ struct AtrousP {
   float sc_step;     // sigma_c * 2^-k (INFINITY: w_c = 1)
   float sn;          // sigma_n (0: w_n = 1)
   float sz_step;     // sigma_z * 2^k (INFINITY: w_z = 1)
+  // variance-guided instantiation only (fspt_temporal_denoise_variance)
+  const float *var;  // k_svgf_variance's output, read by the FIRST iteration; later ones carry the variance in src.w
+  float sl;          // sigma_l in standard deviations (INFINITY: w_l = 1); sc_step is unused
+  float *var_dst;    // the LAST iteration's output variance, which its (a u, 1) has no lane for (test hook), or NULL
 };
 hipError_t launch_features(const FeatureP &p, hipStream_t stream);
 hipError_t launch_atrous(const AtrousP &p, hipStream_t stream);
+hipError_t launch_atrous_variance(const AtrousP &p, hipStream_t stream);
 
 // temporal accumulation (fspt_temporal_*)
 constexpr int MOTION_FLOATS = 9;      // motion-origin snapshot: floats 0-8 (v1 e1 e2) of a slot's hit record
@@ -374,9 +379,27 @@ struct TemporalBP {
   uint32_t has_hist;
   float n;              // acc_ticks
   float alpha, max_history, depth_tol, normal_cos;
+  // moments instantiation only (fspt_temporal_set_moments)
+  const float4 *feat;      // the features: feat[2 i].xyz = the albedo the input is demodulated by
+  const float2 *mom_hist;  // the previous call's (M1, M2) (unused when has_mom = 0)
+  float2 *mom_out;
+  uint32_t has_mom;
+};
+// SVGF variance estimate (k_svgf_variance)
+constexpr float SVGF_MIN_HISTORY = 4.0f; // effective frames from which the temporal moments alone give the variance
+constexpr int SVGF_WINDOW = 3;           // the spatial fallback's window reaches this far: 7 x 7
+struct SvgfVarP {
+  const float4 *hist;  // the history after the blend: .w = its length
+  const float2 *mom;   // (M1, M2)
+  const float4 *feat;
+  float *var;          // W*H
+  uint32_t W, H;
+  float n;             // acc_ticks of the accumulate that wrote hist
+  float sn, sz;        // sigma_normal, sigma_depth (step 1)
 };
 hipError_t launch_temporal_gbuffer(const TemporalGP &p, hipStream_t stream);
-hipError_t launch_temporal_blend(const TemporalBP &p, hipStream_t stream);
+hipError_t launch_temporal_blend(const TemporalBP &p, hipStream_t stream); // (p.mom_out != NULL: the moments instantiation)
+hipError_t launch_svgf_variance(const SvgfVarP &p, hipStream_t stream);
 
 // adaptive sampling (fspt_render_adaptive): after n ticks, with the snapshot S taken after m < n ticks
 struct AdaptiveP {

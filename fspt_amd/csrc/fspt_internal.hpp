@@ -308,6 +308,15 @@ struct fspt_target {
   fspt::CameraP tm_cam{};                  // the previous frame's camera
   hipEvent_t tm_ev[3] = {nullptr, nullptr, nullptr}; // around the two passes of the last call
   bool tm_timed = false;
+  // SVGF variance guidance (fspt_temporal_set_moments / _denoise_variance): allocated on enable, 16 bytes per pixel
+  float2 *tm_mom[2] = {nullptr, nullptr};  // luminance-moment ping-pong (M1, M2), indexed like tm_hist
+  float *tm_var = nullptr;                 // k_svgf_variance's output (allocated by the first fspt_temporal_denoise_variance)
+  bool tm_moments = false;                 // the mode
+  bool tm_mom_valid = false;               // tm_mom[tm_cur] belongs to tm_hist[tm_cur] (an accumulate since enable / reset)
+  bool tm_var_valid = false;               // tm_var is the variance of the CURRENT history
+  float tm_n = 0.0f;                       // acc_ticks of the last accumulate (Fe = length / n)
+  hipEvent_t sv_ev[3] = {nullptr, nullptr, nullptr}; // around k_svgf_variance and the guided iterations of the last call
+  bool sv_timed = false;
 };
 
 static const uint32_t WORK_RING = 4096;

@@ -2614,6 +2614,12 @@ FM_DEV float4 atrous_load(const AtrousP &p, size_t q, float4 f0) {
   if (p.demod) u = make_float4(u.x / max_(f0.x, 1e-3f), u.y / max_(f0.y, 1e-3f), u.z / max_(f0.z, 1e-3f), 1.0f);
   return u;
 }
+// the variance a tap of the variance-guided instantiation reads: the first iteration's from k_svgf_variance's buffer, a
+// later one's from the .w lane the iteration before wrote
+FM_DEV float atrous_var(const AtrousP &p, size_t q) { return p.demod ? p.var[q] : p.src[q].w; }
+// VAR: the luminance weight is exp(-|Lp - Lq| / (sl sqrt(gv_p) + 1e-4)), gv_p the 3 x 3 binomial blur of the
+// input variance around p, and the variance is filtered along (sum w^2 var / (sum w)^2) in the .w lane
+template <bool VAR>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_atrous(const AtrousP p) {
   const int x = (int)(blockIdx.x * blockDim.x + threadIdx.x), y = (int)(blockIdx.y * blockDim.y + threadIdx.y);
   const int W = (int)p.W, H = (int)p.H;
@@ -2627,6 +2633,23 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_atrous(const AtrousP p) {
   const bool hp = fp1.w != 0.0f;
   const float zden = p.sz_step * max_(fp0.w, 1e-3f); // sigma_z * step * max(z_p, 1e-3)
   float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f;
+  float sv = 0.0f, lden = 0.0f;
+  if (VAR && p.sl != INFINITY) {
+    const float G[3] = {0.25f, 0.5f, 0.25f};
+    float gs = 0.0f, gw = 0.0f;
+    for (int j = -1; j <= 1; ++j) {
+      const int yy = y + j;
+      if (yy < 0 || yy >= H) continue;
+      for (int i = -1; i <= 1; ++i) {
+        const int xx = x + i;
+        if (xx < 0 || xx >= W) continue;
+        const float g = G[i + 1] * G[j + 1];
+        gs = fma_(g, atrous_var(p, (size_t)yy * W + xx), gs);
+        gw += g;
+      }
+    }
+    lden = p.sl * sqrt_(gs / gw) + 1e-4f;
+  }
   for (int j = -2; j <= 2; ++j) {
     const int yy = y + j * p.step;
     if (yy < 0 || yy >= H) continue;
@@ -2637,7 +2660,9 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_atrous(const AtrousP p) {
       const float4 fq0 = p.feat[2 * iq], fq1 = p.feat[2 * iq + 1];
       const float4 uq = atrous_load(p, iq, fq0);
       float w = B[i + 2] * B[j + 2];
-      if (p.sc_step != INFINITY) {
+      if (VAR) {
+        if (p.sl != INFINITY) w *= exp2f(-(abs_(Lp - luma(uq)) / lden) * 1.44269504f);
+      } else if (p.sc_step != INFINITY) {
         const float Lq = luma(uq);
         w *= exp2f(-(abs_(Lp - Lq) / (p.sc_step * (Lp + Lq) + 1e-4f)) * 1.44269504f);
       }
@@ -2659,9 +2684,11 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_atrous(const AtrousP p) {
       if (p.sz_step != INFINITY && dz != 0.0f) w *= exp2f(-(dz / zden) * 1.44269504f);
       sr = fma_(w, uq.x, sr); sg = fma_(w, uq.y, sg); sb = fma_(w, uq.z, sb);
       sw += w;
+      if (VAR) sv = fma_(w * w, atrous_var(p, iq), sv);
     }
   }
-  float4 o = make_float4(sr / sw, sg / sw, sb / sw, 1.0f);
+  float4 o = make_float4(sr / sw, sg / sw, sb / sw, VAR ? sv / (sw * sw) : 1.0f);
+  if (VAR && p.var_dst) p.var_dst[ip] = o.w;
   if (p.remod) o = make_float4(fp0.x * o.x, fp0.y * o.y, fp0.z * o.z, 1.0f);
   p.dst[ip] = o;
 }
@@ -2745,6 +2772,9 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_temporal_gbuffer(const Tempor
 
 // The blend pass (image space only): the history at M's sample position - four bilinear taps, each tested against this
 // pixel's surface - blended with the accumulator.  One writer per pixel, vector stores, no atomics.
+// MOM: the same taps, tests, weights and blend factor also carry the two luminance moments (l, l^2) of the
+// DEMODULATED input, u = I.rgb / max(albedo, 1e-3) as atrous_load divides; the colour written is the same bit for bit.
+template <bool MOM>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_temporal_blend(const TemporalBP p) {
   const int x = (int)(blockIdx.x * blockDim.x + threadIdx.x), y = (int)(blockIdx.y * blockDim.y + threadIdx.y);
   const int W = (int)p.W, H = (int)p.H;
@@ -2753,6 +2783,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_temporal_blend(const Temporal
   const float4 I = p.accum[ip];
   const float4 m = p.m[ip];
   float sr = 0.0f, sg = 0.0f, sb = 0.0f, sn = 0.0f, sw = 0.0f;
+  float s1 = 0.0f, s2 = 0.0f;
   // (a position further than a pixel outside the image has no tap inside it: refused before the float -> int conversion)
   if (p.has_hist && m.w != TM_KIND_NONE && m.x > -1.0f && m.y > -1.0f && m.x < (float)W && m.y < (float)H) {
     const float4 g1 = p.g[2 * ip + 1];
@@ -2776,18 +2807,89 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_temporal_blend(const Temporal
       const float4 h = p.hist[iq];
       sr = fma_(w, h.x, sr); sg = fma_(w, h.y, sg); sb = fma_(w, h.z, sb); sn = fma_(w, h.w, sn);
       sw += w;
+      if (MOM && p.has_mom) {
+        const float2 hm = p.mom_hist[iq];
+        s1 = fma_(w, hm.x, s1); s2 = fma_(w, hm.y, s2);
+      }
     }
   }
   float4 o;
+  float2 mo;
+  if (MOM) {
+    const float4 a0 = p.feat[2 * ip];
+    const float l = luma(make_float4(I.x / max_(a0.x, 1e-3f), I.y / max_(a0.y, 1e-3f), I.z / max_(a0.z, 1e-3f), 1.0f));
+    mo = make_float2(l, l * l);
+  }
   if (sw > 0.0f) {
     const float Hr = sr / sw, Hg = sg / sw, Hb = sb / sw;
     const float N = min_(sn / sw, p.max_history);
     const float a = max_(p.n / (N + p.n), p.alpha);
     o = make_float4(Hr + (I.x - Hr) * a, Hg + (I.y - Hg) * a, Hb + (I.z - Hb) * a, min_(N + p.n, p.max_history));
+    if (MOM && p.has_mom) {
+      const float H1 = s1 / sw, H2 = s2 / sw;
+      mo = make_float2(H1 + (mo.x - H1) * a, H2 + (mo.y - H2) * a);
+    }
   } else {
     o = make_float4(I.x, I.y, I.z, min_(p.n, p.max_history));
   }
   p.out[ip] = o;
+  if (MOM) p.mom_out[ip] = mo;
+}
+
+// The variance of the luminance the guided filter is about to read: from the temporal moments where the
+// history is at least SVGF_MIN_HISTORY effective frames long, else from the moments of the 7 x 7 neighbourhood weighted by
+// k_atrous's own normal and depth weights at step 1 (centre weight 1).  Every tap is read through the caches: only pixels
+// with a short history walk the window (a wave whose lanes all have a long one skips it), so a 22 x 22 LDS tile of moments
+// and features - 19 KB a block, loaded by every block - would be paid where nothing reads it.
+__global__ __launch_bounds__(BLOCK_THREADS) void k_svgf_variance(const SvgfVarP p) {
+  const int x = (int)(blockIdx.x * blockDim.x + threadIdx.x), y = (int)(blockIdx.y * blockDim.y + threadIdx.y);
+  const int W = (int)p.W, H = (int)p.H;
+  if (x >= W || y >= H) return;
+  const size_t ip = (size_t)y * W + x;
+  const float Fe = p.hist[ip].w / p.n;
+  const float2 mp = p.mom[ip];
+  float v;
+  if (Fe >= SVGF_MIN_HISTORY) {
+    v = max_(0.0f, mp.y - mp.x * mp.x) / Fe;
+  } else {
+    const float4 fp0 = p.feat[2 * ip], fp1 = p.feat[2 * ip + 1];
+    const float lenp = sqrt_(fma_(fp1.z, fp1.z, fma_(fp1.y, fp1.y, fp1.x * fp1.x)));
+    const bool hp = fp1.w != 0.0f;
+    const float zden = p.sz * max_(fp0.w, 1e-3f);
+    float s1 = 0.0f, s2 = 0.0f, sw = 0.0f;
+    for (int j = -SVGF_WINDOW; j <= SVGF_WINDOW; ++j) {
+      const int yy = y + j;
+      if (yy < 0 || yy >= H) continue;
+      for (int i = -SVGF_WINDOW; i <= SVGF_WINDOW; ++i) {
+        const int xx = x + i;
+        if (xx < 0 || xx >= W) continue;
+        const size_t iq = (size_t)yy * W + xx;
+        float w = 1.0f;
+        if (i != 0 || j != 0) {
+          const float4 fq0 = p.feat[2 * iq], fq1 = p.feat[2 * iq + 1];
+          if (p.sn != 0.0f) {
+            const bool hq = fq1.w != 0.0f;
+            if (hp || hq) {
+              const float lenq = sqrt_(fma_(fq1.z, fq1.z, fma_(fq1.y, fq1.y, fq1.x * fq1.x)));
+              if (hp != hq || lenp == 0.0f || lenq == 0.0f) w = 0.0f;
+              else {
+                const float c = min_(fma_(fp1.z, fq1.z, fma_(fp1.y, fq1.y, fp1.x * fq1.x)) / (lenp * lenq), 1.0f);
+                w *= c > 0.0f ? exp2f(p.sn * log2f(c)) : 0.0f;
+              }
+            }
+          }
+          const float dz = abs_(fp0.w - fq0.w);
+          if (p.sz != INFINITY && dz != 0.0f) w *= exp2f(-(dz / zden) * 1.44269504f);
+        }
+        const float2 mq = p.mom[iq];
+        s1 = fma_(w, mq.x, s1); s2 = fma_(w, mq.y, s2);
+        sw += w;
+      }
+    }
+    const float S1 = s1 / sw, S2 = s2 / sw;
+    v = max_(0.0f, S2 - S1 * S1) / max_(Fe, 1.0f);
+  }
+  p.var[ip] = v;
 }
 
 // ---- adaptive sampling (fspt_render_adaptive) -------------------------------------------------------------
@@ -3154,7 +3256,12 @@ hipError_t launch_features(const FeatureP &p, hipStream_t stream) {
 }
 
 hipError_t launch_atrous(const AtrousP &p, hipStream_t stream) {
-  hipLaunchKernelGGL(k_atrous, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), 0, stream, p);
+  hipLaunchKernelGGL(k_atrous<false>, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), 0, stream, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_atrous_variance(const AtrousP &p, hipStream_t stream) {
+  hipLaunchKernelGGL(k_atrous<true>, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), 0, stream, p);
   return hipGetLastError();
 }
 
@@ -3167,7 +3274,13 @@ hipError_t launch_temporal_gbuffer(const TemporalGP &p, hipStream_t stream) {
 }
 
 hipError_t launch_temporal_blend(const TemporalBP &p, hipStream_t stream) {
-  hipLaunchKernelGGL(k_temporal_blend, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), 0, stream, p);
+  if (p.mom_out) hipLaunchKernelGGL(k_temporal_blend<true>, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), 0, stream, p);
+  else hipLaunchKernelGGL(k_temporal_blend<false>, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), 0, stream, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_svgf_variance(const SvgfVarP &p, hipStream_t stream) {
+  hipLaunchKernelGGL(k_svgf_variance, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), 0, stream, p);
   return hipGetLastError();
 }
 

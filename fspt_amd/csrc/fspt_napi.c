@@ -806,6 +806,34 @@ static napi_value TemporalDenoise(napi_env env, napi_callback_info info) {
   FSPT_OK_OR_THROW(fspt_temporal_denoise((fspt_target *)h, given ? &dp : NULL, (float *)p));
   return p ? a[2] : undefined(env);
 }
+/* temporalSetMoments(target, on) / temporalDenoiseVariance(target, opts | null, Float32Array(W*H*4) | null): SVGF variance guidance */
+static napi_value TemporalSetMoments(napi_env env, napi_callback_info info) {
+  napi_value a[2]; void *h; bool on;
+  if (get_args(env, info, 2, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  NAPI_OK(napi_get_value_bool(env, a[1], &on));
+  FSPT_OK_OR_THROW(fspt_temporal_set_moments((fspt_target *)h, on ? 1 : 0));
+  return undefined(env);
+}
+static napi_value TemporalDenoiseVariance(napi_env env, napi_callback_info info) {
+  napi_value a[3]; void *h, *p = NULL; size_t n = 0; napi_valuetype vt;
+  if (get_args(env, info, 3, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  fspt_denoise_params dp = {FSPT_SVGF_ITERATIONS, FSPT_SVGF_SIGMA_L, FSPT_SVGF_SIGMA_NORMAL, FSPT_SVGF_SIGMA_DEPTH};
+  NAPI_OK(napi_typeof(env, a[1], &vt));
+  const int given = vt == napi_object;
+  if (given) {
+    double k, c, nn, z;
+    if (prop_f64(env, a[1], "iterations", dp.iterations, &k) || prop_f64(env, a[1], "sigmaColor", dp.sigma_color, &c) ||
+        prop_f64(env, a[1], "sigmaNormal", dp.sigma_normal, &nn) || prop_f64(env, a[1], "sigmaDepth", dp.sigma_depth, &z)) return NULL;
+    if (!(k >= 0.0 && k <= 16.0 && k == (double)(uint32_t)k)) { napi_throw_range_error(env, NULL, "fspt_napi: iterations must be an integer in [0, 16]"); return NULL; }
+    dp.iterations = (uint32_t)k; dp.sigma_color = (float)c; dp.sigma_normal = (float)nn; dp.sigma_depth = (float)z;
+  }
+  NAPI_OK(napi_typeof(env, a[2], &vt));
+  if (vt != napi_null && vt != napi_undefined) {
+    if (typed(env, a[2], napi_float32_array, 0, &p, &n) || check_target_len(env, h, n)) return NULL;
+  }
+  FSPT_OK_OR_THROW(fspt_temporal_denoise_variance((fspt_target *)h, given ? &dp : NULL, (float *)p));
+  return p ? a[2] : undefined(env);
+}
 static napi_value TemporalDraw(napi_env env, napi_callback_info info) {
   /* temporalDraw(target, exposure, saturation, denoised, Uint8Array(W*H*4)) */
   napi_value a[5]; void *h, *p; size_t n; double ex, sat; bool den;
@@ -1245,7 +1273,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
       {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
-      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
+      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},
       {"renderAsync", RenderAsync}, {"multiCreate", MultiCreate}, {"multiDestroy", MultiDestroy}, {"multiTarget", MultiTarget},
       {"multiCamera", MultiCamera}, {"multiTrace", MultiTrace}, {"multiRender", MultiRender}, {"multiRenderAsync", MultiRenderAsync},

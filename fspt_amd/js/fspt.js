@@ -444,6 +444,15 @@ class PathTracer {
     if (out.length !== this.resolution[0] * this.resolution[1] * 4) throw new RangeError('temporalDenoise: need W*H*4 floats');
     return addon.temporalDenoise(this._target, opts || null, out);
   }
+  /** SVGF variance guidance (include/fspt.h, DESIGN.md 8.9): temporalSetMoments(true) makes temporalAccumulate() carry two
+   *  luminance moments (it then needs features() first); temporalDenoiseVariance() is temporalDenoise() guided by the variance
+   *  estimate ({iterations, sigmaColor = sigma_l in standard deviations, sigmaNormal, sigmaDepth}; omitted = the library's defaults). */
+  temporalSetMoments(on) { addon.temporalSetMoments(this._target, on === undefined ? true : !!on); }
+  temporalDenoiseVariance(opts, out) {
+    out = out || new Float32Array(this.resolution[0] * this.resolution[1] * 4);
+    if (out.length !== this.resolution[0] * this.resolution[1] * 4) throw new RangeError('temporalDenoiseVariance: need W*H*4 floats');
+    return addon.temporalDenoiseVariance(this._target, opts || null, out);
+  }
   temporalDraw(exposure, saturation, denoised, out) {
     out = out || new Uint8Array(this.resolution[0] * this.resolution[1] * 4);
     if (out.length !== this.resolution[0] * this.resolution[1] * 4) throw new RangeError('temporalDraw: need W*H*4 bytes');

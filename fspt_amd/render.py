@@ -48,6 +48,8 @@ def main():
     ap.add_argument("--temporal", action="store_true",
                     help="--bvh refit --frames: reproject and blend every frame with the frames before it (DESIGN 8.8); with "
                          "--atrous K the a-trous filter runs on the temporal result")
+    ap.add_argument("--variance-guided", action="store_true",
+                    help="--temporal --atrous K: the K iterations are guided by the per-pixel variance estimate (DESIGN 8.9)")
     ap.add_argument("--sampler", choices=("reference", "sobol"), default="reference",
                     help="the paths' random numbers (fspt_target_set_sampler; built-in scene)")
     ap.add_argument("--sampler-seed", type=int, default=0, help="seed of --sampler sobol, in [0, 2^32)")
@@ -77,6 +79,8 @@ def main():
         ap.error("--temporal cannot be combined with --adaptive")
     if args.temporal and not (args.bvh == "refit" and args.frames):
         ap.error("--temporal needs --bvh refit and --frames")
+    if args.variance_guided and not (args.temporal and args.atrous):
+        ap.error("--variance-guided needs --temporal and --atrous K")
     if args.atrous and args.scene and not args.temporal:
         ap.error("--atrous is available for the built-in scene, or with --temporal")
     if args.scene and args.sampler != "reference":
@@ -96,7 +100,8 @@ def main():
             t0 = time.perf_counter()
             out = F.render_sequence(args.scene, range(a, b), args.out, args.width, args.height, args.assets, bvh=args.bvh,
                                     rebuild_above=args.rebuild_above,
-                                    temporal={"atrous": args.atrous} if args.temporal else None, **kw)
+                                    temporal={"atrous": args.atrous} if args.temporal else None,
+                                    variance=args.variance_guided, **kw)
             print(f"{len(out)} frames in {time.perf_counter() - t0:.2f} s:", *out)
         else:
             arrays, settings = F.load_scene_file(args.scene, args.assets, bvh=args.bvh)

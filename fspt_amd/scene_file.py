@@ -139,7 +139,7 @@ def write_sample_map(path, counts, max_ticks):
 
 
 def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", rebuild_above=None,
-                    on_frame=None, temporal=None, **kw):
+                    on_frame=None, temporal=None, variance=False, **kw):
     """frame=N sequencing (main.js:851-866, 966-969): for every N in `frames` load `scene_pattern.format(frame=N)`
     (the per-frame scene JSON the reference's server hands out for `?frame=N`), render it, write
     `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1.
@@ -156,7 +156,10 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     for K a-trous iterations on the result.  Every frame then follows the protocol motion_begin, update_geometry, clear and
     render, temporal_accumulate, and the picture written is temporal_draw of the result (`denoise`, the firefly filter of
     draw(), does not apply to it; `adaptive` is refused); frame k renders with seed + k, so that the frames' noise is
-    independent.  A frame that builds a new scene starts a new history."""
+    independent.  A frame that builds a new scene starts a new history.
+    variance (with temporal and "atrous" >= 1): the a-trous iterations are the variance-guided ones - every tracer
+    gets temporal_set_moments(), a frame's features() come before its temporal_accumulate (which demodulates by them) and the
+    filter is temporal_denoise(iterations=K, variance=True)."""
     from PIL import Image
     written = []
     device = kw.get("device", 0)
@@ -172,6 +175,8 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
             raise ValueError("render_sequence: temporal cannot be combined with adaptive sampling")
     else:
         temporal = None
+    if variance and (temporal is None or atrous < 1):
+        raise ValueError('render_sequence: variance needs temporal with "atrous" >= 1 (the variance guides the a-trous filter)')
 
     def save(n, rgba):
         out = out_pattern.format(frame=n)
@@ -225,12 +230,18 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                 pt = PathTracer(base, width, height, device=device, num_bounces=bounces)
                 cost0 = pt.scene.sah_cost() if rebuild_above is not None else None
                 leaf_order = base.meta["tri_order"]
+                if variance:
+                    pt.temporal_set_moments(True)
             if temporal is None:
                 rgba, _ = _render_on(pt, settings, **opt)
             else:
                 _render_on(pt, settings, **{**opt, "seed": opt["seed"] + len(written), "denoise": False})  # (its draw is not the frame)
+                if variance:
+                    pt.features(8, opt["seed"])
                 pt.temporal_accumulate(read=False, **temporal)
-                if atrous > 0:
+                if variance:
+                    pt.temporal_denoise(iterations=atrous, variance=True)
+                elif atrous > 0:
                     pt.features(8, opt["seed"])
                     pt.temporal_denoise(iterations=atrous)
                 rgba = pt.temporal_draw(settings["exposure"], opt["saturation"], denoised=atrous > 0)

@@ -103,6 +103,46 @@ def temporal_eval(accum, motion, g, hist=None, g_prev=None, n=1, device=0, **par
     return out
 
 
+SVGF_DEFAULTS = {"iterations": 4, "sigma_color": 8.0, "sigma_normal": 32.0, "sigma_depth": 0.05}  # include/fspt_tuning.h FSPT_SVGF_* (sigma_color = sigma_l)
+
+
+def _svgf_params(given):
+    """fspt_denoise_params of the variance-guided filter from keyword arguments (None values and an empty dict: the
+    library's defaults), validated like the library does."""
+    unknown = set(given) - set(SVGF_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown denoise parameters {sorted(unknown)}")
+    if all(x is None for x in given.values()):
+        return None
+    v = {k: SVGF_DEFAULTS[k] if given.get(k) is None else given[k] for k in SVGF_DEFAULTS}
+    k, sl, sn, sz = int(v["iterations"]), float(v["sigma_color"]), float(v["sigma_normal"]), float(v["sigma_depth"])
+    if not (0 <= k <= 16 and k == v["iterations"] and sl >= 0.0 and 0.0 <= sn < float("inf") and sz > 0.0):
+        raise ValueError("variance-guided denoise parameters: need iterations <= 16, sigma_color >= 0, sigma_normal in [0, inf), sigma_depth > 0")
+    return L.DenoiseParams(k, sl, sn, sz)
+
+
+def svgf_eval(hist, moments, features, n=1, device=0, **params):
+    """k_svgf_variance and the variance-guided a-trous iterations on host arrays (fspt_svgf_eval, a test hook): hist float32
+    [H, W, 4] (rgb, history length), moments float32 [H, W, 2] (M1, M2), features float32 [H, W, 8], n = the accumulator's
+    ticks -> (filtered float32 [H, W, 4], input variance [H, W], output variance [H, W]).  params: iterations, sigma_color
+    (sigma_l, in standard deviations), sigma_normal, sigma_depth (SVGF_DEFAULTS)."""
+    prm = _svgf_params(params)
+    hist = np.ascontiguousarray(hist, dtype=np.float32)
+    if hist.ndim != 3 or hist.shape[2] != 4:
+        raise ValueError(f"need hist [H, W, 4], got {hist.shape}")
+    H, W = hist.shape[:2]
+    if np.shape(moments) != (H, W, 2) or np.shape(features) != (H, W, 8):
+        raise ValueError(f"need moments [{H}, {W}, 2] and features [{H}, {W}, 8], got {np.shape(moments)} and {np.shape(features)}")
+    moments = np.ascontiguousarray(moments, dtype=np.float32)
+    features = np.ascontiguousarray(features, dtype=np.float32)
+    if int(n) < 1:
+        raise ValueError("n must be >= 1")
+    out, vin, vout = np.empty((H, W, 4), np.float32), np.empty((H, W), np.float32), np.empty((H, W), np.float32)
+    L.check(L.lib().fspt_svgf_eval(int(device), L.fptr(hist), L.fptr(moments), L.fptr(features), W, H, int(n),
+                                   C.byref(prm) if prm is not None else None, L.fptr(out), L.fptr(vin), L.fptr(vout)))
+    return out, vin, vout
+
+
 def light_alias_table(weights):
     """The Vose alias table (float32 prob, uint32 alias) the light table stores for these weights (fspt_light_alias_table,
     a pure host function: no device needed)."""
@@ -691,17 +731,44 @@ class PathTracer:
         """Drop the history: the next temporal_accumulate behaves as the first (fspt_temporal_reset)."""
         L.check(L.lib().fspt_temporal_reset(self._t))
 
-    def temporal_denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None):
-        """denoise() with the temporal result in the accumulator's place (fspt_temporal_denoise) -> float32 [H, W, 4]."""
+    def temporal_denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None, variance=False):
+        """denoise() with the temporal result in the accumulator's place (fspt_temporal_denoise) -> float32 [H, W, 4].
+        variance=True (after temporal_set_moments()): the variance-guided filter (fspt_temporal_denoise_variance, DESIGN 8.9;
+        sigma_color is sigma_l, in standard deviations; SVGF_DEFAULTS)."""
         W, H = self.resolution
         out = np.zeros((H, W, 4), np.float32)
         given = {"iterations": iterations, "sigma_color": sigma_color, "sigma_normal": sigma_normal, "sigma_depth": sigma_depth}
+        if variance:
+            prm = _svgf_params(given)
+            L.check(L.lib().fspt_temporal_denoise_variance(self._t, C.byref(prm) if prm is not None else None, L.fptr(out)))
+            return out
         prm = None
         if any(v is not None for v in given.values()):
             v = {k: DENOISE_DEFAULTS[k] if x is None else x for k, x in given.items()}
             prm = L.DenoiseParams(int(v["iterations"]), float(v["sigma_color"]), float(v["sigma_normal"]), float(v["sigma_depth"]))
         L.check(L.lib().fspt_temporal_denoise(self._t, C.byref(prm) if prm is not None else None, L.fptr(out)))
         return out
+
+    def temporal_set_moments(self, on=True):
+        """SVGF variance guidance (fspt_temporal_set_moments): temporal_accumulate() also carries two luminance
+        moments of the demodulated input (it then needs features() first); what temporal_denoise(variance=True) reads."""
+        L.check(L.lib().fspt_temporal_set_moments(self._t, 1 if on else 0))
+
+    def temporal_variance(self, variance=True):
+        """(v float32 [H, W], moments float32 [H, W, 2]) (fspt_temporal_read_variance): the variance estimate of the last
+        temporal_denoise(variance=True) - None with variance=False, which needs no such call - and (M1, M2) of the last
+        temporal_accumulate."""
+        W, H = self.resolution
+        v = np.zeros((H, W), np.float32) if variance else None
+        m = np.zeros((H, W, 2), np.float32)
+        L.check(L.lib().fspt_temporal_read_variance(self._t, L.fptr(v) if variance else None, L.fptr(m)))
+        return v, m
+
+    def svgf_last_ms(self):
+        """(k_svgf_variance ms, guided iterations ms) of the last temporal_denoise(variance=True), from HIP events."""
+        ms = (C.c_float * 2)()
+        L.check(L.lib().fspt_svgf_last_ms(self._t, ms))
+        return float(ms[0]), float(ms[1])
 
     def temporal_draw(self, exposure=1.0, saturation=1.0, denoised=False):
         """draw() of the temporal result, or of the last temporal_denoise() (fspt_temporal_draw): RGBA8 [H, W, 4]."""

@@ -175,11 +175,9 @@ int fspt_read_radiance(fspt_target *target, float *out);
 int fspt_draw(fspt_target *target, float exposure, float saturation, int denoise, float max_sigma, uint8_t *out_rgba8);
 /* The same with draw.fs's `scale` uniform (draw.fs:59,87: texel = ivec2(gl_FragCoord * scale)): 0.25 while the camera is dragged (main.js:819,840), else 1. */
 int fspt_draw_scaled(fspt_target *target, float exposure, float saturation, int denoise, float max_sigma, float scale, uint8_t *out_rgba8);
-/* drawQuad inside tick() (main.js:838-857), pipelined with one frame of latency: enqueues the ticks
- * recorded since the last flush and fspt_draw_scaled's k_draw of the result, then writes the frame the PREVIOUS call
- * enqueued to out_rgba8 and its sample count (1 + its newest tick index) to *ticks_out, blocking only for that frame.
- * *ticks_out = 0: nothing to present (first call after a join; out untouched).  Every entry but fspt_camera and
- * fspt_trace joins. */
+/* drawQuad inside tick() (main.js:838-857), pipelined with one frame of latency (DESIGN.md 4.3): enqueues the ticks recorded since the last flush and
+ * fspt_draw_scaled's k_draw of the result, then writes the frame the PREVIOUS call enqueued to out_rgba8 and its sample count (1 + its newest tick index) to
+ * *ticks_out, blocking only for that frame.  *ticks_out = 0: nothing to present (first call after a join; out untouched).  Every entry but fspt_camera and fspt_trace joins. */
 int fspt_present(fspt_target *t, float exposure, float saturation, int denoise, float max_sigma, float scale, uint8_t *out_rgba8, uint32_t *ticks_out);
 
 /* Guided denoiser (DESIGN.md 8; the reference lists "denoising" under post processing).  fspt_features: `samples` camera
@@ -208,6 +206,8 @@ int fspt_temporal_reset(fspt_target *t);                                        
 int fspt_temporal_denoise(fspt_target *t, const fspt_denoise_params *p, float *out);        /* fspt_denoise of the temporal result */
 int fspt_temporal_draw(fspt_target *t, float exposure, float saturation, int denoised, uint8_t *out_rgba8); /* fspt_draw / fspt_draw_denoised of it */
 int fspt_scene_motion_begin(fspt_scene *s); int fspt_scene_motion_end(fspt_scene *s);       /* snapshot (a rebuild permutes it) | drop it: static scene */
+int fspt_temporal_set_moments(fspt_target *t, int on); /* SVGF variance guidance (DESIGN 8.9; rule and defaults: fspt_tuning.h): accumulate also carries luminance moments; default off */
+int fspt_temporal_denoise_variance(fspt_target *t, const fspt_denoise_params *p, float *out); /* fspt_temporal_denoise guided by the variance estimate; sigma_color = sigma_l */
 
 /* intersectScene (tracer.fs:366-404) as a stand-alone entry: n rays (origin xyz, dir xyz) -> closest hit t and
  * triangle index (-1 = miss, t = 1e5), optionally loop-iteration and leaf-visit counts per ray.  Host pointers. */

@@ -187,6 +187,33 @@ int fspt_temporal_last_ms(fspt_target *t, float ms[2]);
  * floats, n = the accumulator's ticks (>= 1) - out: W*H*4.  hist NULL (then g_prev may be NULL): no history. */
 int fspt_temporal_eval(int device, const float *accum, const float *motion, const float *g, const float *hist, const float *g_prev,
                        uint32_t W, uint32_t H, uint32_t n, const fspt_temporal_params *p, float *out);
+/* SVGF variance guidance (fspt.h fspt_temporal_set_moments / fspt_temporal_denoise_variance).  With moments on (16 bytes per
+ * pixel, a ping-pong pair of (M1, M2); FSPT_E_STATE from fspt_temporal_accumulate before any fspt_features) the blend pass also carries two
+ * luminance moments of the DEMODULATED input: u = I.rgb / max(albedo, 1e-3), l = L(u) (Rec.709 luma), m = (l, l l); with the colour's taps,
+ * tests, weights w_q and blend factor a: Hm = sum w_q mom(q) / sum w_q, Mout = Hm + (m - Hm) a; no tap counts or no moments history:
+ * Mout = m.  The colour is the same bit for bit.  Variance (k_svgf_variance): Fe = out.w / n; Fe >= 4: v = max(0, M2 - M1 M1) / Fe; else over
+ * the 7 x 7 window inside the image with fspt_denoise's wn wz at step 1 (k = 0; the centre weighs 1): S1 = sum w M1 / sum w, S2 likewise,
+ * v = max(0, S2 - S1 S1) / max(Fe, 1): the variance of the luminance of the temporal MEAN the filter reads.  Filter: fspt_denoise's
+ * iterations on the history with wc replaced by wl = exp(-|L(u_p) - L(u_q)| / (sl sqrt(gv_p) + 1e-4)), gv_p = the (1,2,1) x (1,2,1) / 16 blur
+ * (renormalised inside the image) of the iteration's input variance at p's 3 x 3 neighbours one pixel apart, sl = sigma_color = +inf:
+ * wl = 1; the variance goes along, var'(p) = sum w w var(q) / (sum w)^2, v into iteration 0; out = (a u_K, 1) into fspt_denoise's buffer
+ * (fspt_temporal_draw(denoised = 1) draws it; K = 0: the history).  FSPT_E_INVALID: NULL, fspt_denoise's parameter ranges; FSPT_E_STATE:
+ * moments off, no accumulate since they were switched on or since fspt_temporal_reset, no features, a sharded target. */
+#define FSPT_SVGF_ITERATIONS 4    /* defaults (params NULL): the best row of DESIGN 8.9's scan (the SVGF paper's sigma_l = 4 loses on a moving camera) */
+#define FSPT_SVGF_SIGMA_L 8.0f
+#define FSPT_SVGF_SIGMA_NORMAL 32.0f
+#define FSPT_SVGF_SIGMA_DEPTH 0.05f
+/* v of the last fspt_temporal_denoise_variance (W*H floats) and (M1, M2) of the last accumulate (W*H*2 floats), rows bottom-up; either may be
+ * NULL (the moments alone need no denoise call).  Blocking. */
+int fspt_temporal_read_variance(fspt_target *t, float *var_out, float *moments_out);
+/* GPU ms of the last fspt_temporal_denoise_variance, from HIP events: ms[0] k_svgf_variance, ms[1] the guided iterations (the moments blend
+ * is fspt_temporal_last_ms's ms[1]).  Blocking. */
+int fspt_svgf_last_ms(fspt_target *t, float ms[2]);
+/* Test hook: k_svgf_variance and the guided iterations on host arrays in the library's layouts - hist W*H*4 floats (rgb, length), moments
+ * W*H*2, features W*H*8, n = the accumulator's ticks (>= 1) - out: the W*H*4 filtered floats; var_in, var_out (W*H each, may be NULL): v and
+ * the variance the last iteration leaves (K = 0: v).  p NULL = the defaults above. */
+int fspt_svgf_eval(int device, const float *hist, const float *moments, const float *features, uint32_t W, uint32_t H, uint32_t n,
+                   const fspt_denoise_params *p, float *out, float *var_in, float *var_out);
 /* fspt_target_set_lights (fspt.h): FSPT_LIGHTS_EMITTERS lets each shading vertex spend its shadow ray on a
  * point of an emissive triangle (probability q = emitter_fraction, in (0, 1]; at most 0.875 with an environment map, 1
  * when the scene has none)

@@ -10,7 +10,14 @@
   timing              both passes at 1920 x 1080 (HIP events) beside a one-sample fspt_features (host clock around a
                       synchronised call, best of 5) and the same host clock around a whole accumulate, in the same process; the snap's margin
 
-usage: python tools/temporal_quality.py [--scan] [--timing]
+  --variance          DESIGN 8.9: the variance-guided filter (fspt_temporal_denoise_variance) against fspt_temporal_denoise on the same
+                      frames in the same process, each at its best scanned setting (VARIANCE_BEST / FIXED_BEST), on the two sequences
+                      above and on the EDGE sequence - tests/lights_ref.py's scene E3 (an occluder under a lamp, emitters standing on
+                      and facing the floor: shadow edges and thin bright shapes), 16 frames of 4 spp = 64 samples from a camera that
+                      orbits 0.25 degrees per frame, so that most pixels keep a long history; with --scan the settings scanned; with
+                      --timing the moments blend, k_svgf_variance and the guided iterations at 1920 x 1080 beside the parent's passes
+
+usage: python tools/temporal_quality.py [--scan] [--timing] [--variance]
 tests/test_temporal_gpu.py::test_quality runs the two sequences and holds them to MEASURED x 1.5."""
 import argparse
 import os
@@ -22,6 +29,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from fspt_amd import _lib as L  # noqa: E402
 
 W, H, FRAMES, SPP, STEP_DEG, GT_SPP, ATROUS = 320, 240, 8, 4, 2.0, 4096, 4
 # ratios to the raw last frame measured on the MI355X with the shipped defaults (DESIGN 8.8 has the table)
@@ -96,6 +104,109 @@ def geometry_sequence(arrays, camera, params=None, frames=FRAMES, spp=SPP):
     return out
 
 
+# ---- variance guidance --------------------------------------------------------------------------------------
+EDGE_FRAMES, EDGE_SPP, EDGE_STEP_DEG = 16, 4, 0.25
+FIXED_BEST = dict(iterations=4, sigma_color=4.0, sigma_normal=32.0, sigma_depth=0.05)      # the library's defaults; the comparison takes the minimum over FIXED_SCAN too
+VARIANCE_BEST = dict(iterations=4, sigma_color=8.0, sigma_normal=32.0, sigma_depth=0.05)   # the library's defaults, chosen by DESIGN 8.9's scan on these same sequences
+FIXED_SCAN = [dict(iterations=k, sigma_color=sc) for k in (3, 4, 5) for sc in (1.0, 2.0, 4.0, 8.0)]
+VARIANCE_SCAN = [dict(iterations=k, sigma_color=sl) for k in (3, 4, 5) for sl in (1.0, 2.0, 4.0, 8.0, 16.0)]
+
+
+def variance_sequence(arrays, camera, frames, spp, step_deg=0.0, geometry_deg=0.0, fixed=(FIXED_BEST,), variance=(VARIANCE_BEST,), gt=None):
+    """One sequence with moments on (the colour history is the same bit for bit); after the last frame every setting of
+    `fixed` through temporal_denoise and every setting of `variance` through temporal_denoise(variance=True), on that one
+    history.  Returns relative MSEs of the last frame: raw, temporal, lists fixed / variance, and gt."""
+    from fspt_amd import PathTracer
+    from refit_moves import rotated
+    pt = PathTracer(arrays, W, H, num_bounces=4)
+    pt.temporal_set_moments(True)
+    set_cam(pt, orbit(camera, step_deg * (frames - 1)))
+    if gt is None:
+        if geometry_deg:
+            pt.update_geometry(*rotated(arrays.tri, arrays.norm, deg=geometry_deg))
+        gt = reference(pt)
+        if geometry_deg:
+            pt.update_geometry(arrays.tri, arrays.norm)
+    for k in range(frames):
+        set_cam(pt, orbit(camera, step_deg * k))
+        if k and geometry_deg:
+            pt.scene.motion_begin()
+            pt.update_geometry(*rotated(arrays.tri, arrays.norm, deg=geometry_deg * k / (frames - 1)))
+        pt.clear(); pt.seed(7 + k); pt.render(spp)
+        pt.features(8, 1)
+        hist = pt.temporal_accumulate()
+    out = {"raw": rel_mse(pt.readRadiance(), gt), "temporal": rel_mse(hist, gt), "gt": gt,
+           "fixed": [rel_mse(pt.temporal_denoise(**q), gt) for q in fixed],
+           "variance": [rel_mse(pt.temporal_denoise(variance=True, **q), gt) for q in variance]}
+    pt.close(); pt.scene.close()
+    return out
+
+
+def variance_sequences(arrays, camera):
+    """name -> (arrays, camera, keyword arguments of variance_sequence) of the three sequences"""
+    import lights_ref as LR
+    return {"camera": (arrays, camera, dict(frames=FRAMES, spp=SPP, step_deg=STEP_DEG)),
+            "geometry": (arrays, camera, dict(frames=FRAMES, spp=SPP, geometry_deg=7.0)),
+            "edges": (LR.scene_e3(), camera, dict(frames=EDGE_FRAMES, spp=EDGE_SPP, step_deg=EDGE_STEP_DEG))}
+
+
+def variance_comparison(arrays, camera, scan=False):
+    """name -> {raw, temporal, fixed, fixed_best, variance}: the fixed rule at the library's defaults and at the best of
+    FIXED_SCAN FOR THAT SEQUENCE (it always runs its whole scan: the strongest opponent), the variance-guided filter at ONE
+    setting, VARIANCE_BEST = the library's defaults (scan: also the lists fixed_scan / variance_scan)"""
+    out = {}
+    for name, (a, c, kw) in variance_sequences(arrays, camera).items():
+        fx = [FIXED_BEST] + FIXED_SCAN
+        vr = [VARIANCE_BEST] + (VARIANCE_SCAN if scan else [])
+        r = variance_sequence(a, c, fixed=fx, variance=vr, **kw)
+        out[name] = {"raw": r["raw"], "temporal": r["temporal"], "fixed": r["fixed"][0], "fixed_best": min(r["fixed"]), "variance": r["variance"][0]}
+        if scan:
+            out[name]["fixed_scan"], out[name]["variance_scan"] = r["fixed"][1:], r["variance"][1:]
+    return out
+
+
+def variance_timing(arrays, camera, w=1920, h=1080):
+    """HIP-event ms, best of 5, in one process: the blend pass with moments off and on, the parent's filter (host clock around
+    a synchronised temporal_denoise: it has no events of its own; the guided one the same way beside its events), k_svgf_variance
+    on a first frame (every pixel takes the 7 x 7 window) and on a long history (none does)."""
+    from fspt_amd import PathTracer
+    pt = PathTracer(arrays, w, h, num_bounces=4)
+    set_cam(pt, camera)
+    pt.render(1); pt.features(1, 1)
+    out = {}
+
+    def host(fn):
+        best = 1e9
+        for _ in range(6):
+            pt.sync(); t0 = time.perf_counter(); fn(); pt.sync()
+            best = min(best, (time.perf_counter() - t0) * 1e3)
+        return best
+    for on in (False, True):
+        pt.temporal_set_moments(on)
+        best = 1e9
+        for k in range(6):
+            pt.temporal_accumulate(read=False)
+            if k:
+                best = min(best, pt.temporal_last_ms()[1])
+        out["blend_moments_%s_ms" % ("on" if on else "off")] = best
+    pt.temporal_reset(); pt.temporal_accumulate(read=False)
+    for name in ("first_frame", "long_history"):
+        if name == "long_history":
+            for _ in range(6):
+                pt.temporal_accumulate(read=False)
+        bv, bi = 1e9, 1e9
+        for k in range(6):
+            L.check(L.lib().fspt_temporal_denoise_variance(pt._t, None, None))
+            ms = pt.svgf_last_ms()
+            if k:
+                bv, bi = min(bv, ms[0]), min(bi, ms[1])
+        out["svgf_variance_%s_ms" % name], out["guided_4_iterations_%s_ms" % name] = bv, bi
+    out["guided_host_ms"] = host(lambda: L.check(L.lib().fspt_temporal_denoise_variance(pt._t, None, None)))
+    out["fixed_4_iterations_host_ms"] = host(lambda: L.check(L.lib().fspt_temporal_denoise(pt._t, None, None)))
+    pt.close(); pt.scene.close()
+    return out
+
+
 def timing(arrays, camera, w=1920, h=1080):
     from fspt_amd import PathTracer
     pt = PathTracer(arrays, w, h, num_bounces=4)
@@ -158,10 +269,24 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scan", action="store_true")
     ap.add_argument("--timing", action="store_true")
+    ap.add_argument("--variance", action="store_true", help="the variance-guided filter against the fixed rule (DESIGN 8.9)")
     args = ap.parse_args()
     from fspt_amd import scene as S
     arrays = S.bunny_scene(n=24, env_size=(256, 128), sun_deg=3.0)  # the tests' medium scene
     cam = dict(S.BUNNY_CAMERA)
+    if args.variance:
+        r = variance_comparison(arrays, cam, scan=args.scan)
+        print("| sequence | raw | temporal | + a-trous, fixed rule (defaults) | fixed rule (its best scanned row) | + variance-guided a-trous (defaults) | guided / best fixed |")
+        print("|---|---|---|---|---|---|---|")
+        for name, v in r.items():
+            print("| %s | %.5f | %.5f | %.5f | %.5f | %.5f | %.3f |" % (name, v["raw"], v["temporal"], v["fixed"], v["fixed_best"], v["variance"], v["variance"] / v["fixed_best"]))
+        if args.scan:
+            for name, v in r.items():
+                print(name, "fixed rule:", " ".join("K%d/sc%g:%.5f" % (q["iterations"], q["sigma_color"], x) for q, x in zip(FIXED_SCAN, v["fixed_scan"])))
+                print(name, "variance-guided:", " ".join("K%d/sl%g:%.5f" % (q["iterations"], q["sigma_color"], x) for q, x in zip(VARIANCE_SCAN, v["variance_scan"])))
+        if args.timing:
+            print("variance timing 1920 x 1080:", {k: round(v, 4) for k, v in variance_timing(arrays, cam).items()})
+        return
     q = camera_sequence(arrays, cam)
     gt = q.pop("gt")
     print("camera sequence (defaults):", {k: round(v, 5) for k, v in q.items()})

@@ -149,6 +149,10 @@ SIGNATURES = {
     "fspt_temporal_read_variance": (C.c_int, [_VP, _F, _F]),
     "fspt_svgf_last_ms": (C.c_int, [_VP, _F]),
     "fspt_svgf_eval": (C.c_int, [C.c_int, _F, _F, _F, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), _F, _F, _F]),
+    "fspt_temporal_set_clamp": (C.c_int, [_VP, C.c_int, C.c_float, C.c_float]),
+    "fspt_temporal_read_fast": (C.c_int, [_VP, _F]),
+    "fspt_temporal_clamp_last_ms": (C.c_int, [_VP, _F]),
+    "fspt_temporal_clamp_eval": (C.c_int, [C.c_int, _F, _F, C.c_uint32, C.c_uint32, C.c_float, _F, _F, _F]),
     "fspt_scene_motion_begin": (C.c_int, [_VP]),
     "fspt_scene_motion_end": (C.c_int, [_VP]),
     "fspt_intersect": (C.c_int, [_VP, _F, C.c_uint32, _F, C.POINTER(C.c_int32), _U32, _U32]),

@@ -777,6 +777,8 @@ int fspt_target_destroy(fspt_target *t) {
   for (hipEvent_t ev : t->tm_ev) if (ev) hipEventDestroy(ev);
   hipFree(t->tm_mom[0]); hipFree(t->tm_mom[1]); hipFree(t->tm_var);
   for (hipEvent_t ev : t->sv_ev) if (ev) hipEventDestroy(ev);
+  hipFree(t->tm_fast[0]); hipFree(t->tm_fast[1]);
+  for (hipEvent_t ev : t->cl_ev) if (ev) hipEventDestroy(ev);
   hipFree(t->ad_snap); hipFree(t->ad_list[0]); hipFree(t->ad_list[1]); hipFree(t->ad_count); hipFree(t->ad_err);
   {
     fspt_target::WfLane &ln = t->wf;
@@ -1812,6 +1814,13 @@ int fspt_temporal_accumulate(fspt_target *t, const fspt_camera_params *cam, cons
     b.feat = t->feat; b.mom_hist = t->tm_mom[cur]; b.mom_out = t->tm_mom[nx];
     b.has_mom = b.has_hist; // (the two histories start together: fspt_temporal_set_moments, fspt_temporal_reset)
   }
+  if (t->tm_clamp) { // the fast-history instantiation: the same taps also carry F, capped at fast_history
+    b.fast_hist = t->tm_fast[cur]; b.fast_out = t->tm_fast[nx];
+    b.has_fast = b.has_hist && t->tm_fast_valid ? 1u : 0u; // (the two histories start together: fspt_temporal_set_clamp, fspt_temporal_reset)
+    b.fast_history = t->tm_fast_history;
+    for (hipEvent_t &ev : t->cl_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
+  }
+  t->tm_fast_valid = false; t->cl_timed = false;
   t->tm_mom_valid = false; t->tm_var_valid = false;
   t->tm_gm_valid = false; t->tm_timed = false;
   t->tm_dn_valid = false; // (a denoised frame of the previous history is not this one's)
@@ -1821,6 +1830,17 @@ int fspt_temporal_accumulate(fspt_target *t, const fspt_camera_params *cam, cons
   HIP_TRY(hipEventRecord(t->tm_ev[1], t->stream));
   HIP_TRY(fspt::launch_temporal_blend(b, t->stream));
   HIP_TRY(hipEventRecord(t->tm_ev[2], t->stream));
+  if (t->tm_clamp) { // pass 3: the long history into the fast one's box, in place (sigma_scale = +inf: no launch, never inf * 0)
+    HIP_TRY(hipEventRecord(t->cl_ev[0], t->stream));
+    if (t->tm_sigma_scale != INFINITY) {
+      fspt::ClampP c{};
+      c.hist = t->tm_hist[nx]; c.fast = t->tm_fast[nx];
+      c.W = t->W; c.H = t->H; c.sigma_scale = t->tm_sigma_scale;
+      HIP_TRY(fspt::launch_temporal_clamp(c, t->stream));
+    }
+    HIP_TRY(hipEventRecord(t->cl_ev[1], t->stream));
+    t->tm_fast_valid = true; t->cl_timed = true;
+  }
   t->tm_cur = nx;
   t->tm_cam = g.cam;
   t->tm_valid = true; t->tm_gm_valid = true; t->tm_timed = true;
@@ -1839,6 +1859,7 @@ int fspt_temporal_reset(fspt_target *t) {
   t->tm_valid = false;
   t->tm_dn_valid = false;
   t->tm_mom_valid = false; t->tm_var_valid = false; // (the moments go with the history they describe)
+  t->tm_fast_valid = false;                         // (and so does the fast history)
   return FSPT_OK;
 }
 
@@ -2076,6 +2097,100 @@ int fspt_svgf_eval(int device, const float *hist, const float *moments, const fl
   if (e == hipSuccess && var_out) e = hipMemcpy(var_out, var2, px * 4, hipMemcpyDeviceToHost);
   hipFree(d);
   if (e != hipSuccess) { fspt_set_error("fspt_svgf_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
+  return FSPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// temporal history clamp (k_temporal_blend<*, true> / k_temporal_clamp)
+// ---------------------------------------------------------------------------
+static int cl_check_params(float fast_history, float sigma_scale, const char *fn) {
+  if (!(fast_history >= 1.0f && fast_history < INFINITY) || !(sigma_scale >= 0.0f)) {
+    fspt_set_error("%s: need a finite fast_history >= 1 and sigma_scale >= 0 (+inf: the clamp never binds)", fn);
+    return FSPT_E_INVALID;
+  }
+  return FSPT_OK;
+}
+
+int fspt_temporal_set_clamp(fspt_target *t, int on, float fast_history, float sigma_scale) {
+  if (!t) { fspt_set_error("fspt_temporal_set_clamp: NULL argument"); return FSPT_E_INVALID; }
+  int rc;
+  if (on && (rc = cl_check_params(fast_history, sigma_scale, "fspt_temporal_set_clamp"))) return rc;
+  if ((rc = dn_enter(t, true, "fspt_temporal_set_clamp"))) return rc;
+  if (!on) {
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    hipFree(t->tm_fast[0]); hipFree(t->tm_fast[1]);
+    t->tm_fast[0] = t->tm_fast[1] = nullptr;
+    t->tm_clamp = t->tm_fast_valid = t->cl_timed = false;
+    return FSPT_OK;
+  }
+  if (t->n_shards > 1) { fspt_set_error("fspt_temporal_set_clamp: sharded target"); return FSPT_E_STATE; }
+  t->tm_fast_history = fast_history; t->tm_sigma_scale = sigma_scale; // (a change of the parameters alone keeps both histories)
+  if (t->tm_clamp) return FSPT_OK;
+  const size_t px = (size_t)t->W * t->H;
+  for (int k = 0; k < 2; ++k) {
+    if ((rc = dn_alloc(&t->tm_fast[k], px * 16))) return rc;
+  }
+  t->tm_clamp = true;
+  // off -> on drops the long history with it, as fspt_temporal_set_moments does: the two histories start together
+  t->tm_fast_valid = false;
+  t->tm_valid = false; t->tm_dn_valid = false;
+  t->tm_mom_valid = false; t->tm_var_valid = false;
+  return FSPT_OK;
+}
+
+int fspt_temporal_read_fast(fspt_target *t, float *out) {
+  int rc = dn_enter(t, out != nullptr, "fspt_temporal_read_fast");
+  if (rc) return rc;
+  if (!t->tm_clamp || !t->tm_valid || !t->tm_fast_valid) { fspt_set_error("fspt_temporal_read_fast: no fspt_temporal_accumulate call with the clamp on yet"); return FSPT_E_STATE; }
+  HIP_TRY(hipMemcpyAsync(out, t->tm_fast[t->tm_cur], (size_t)t->W * t->H * 16, hipMemcpyDeviceToHost, t->stream));
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  return FSPT_OK;
+}
+
+int fspt_temporal_clamp_last_ms(fspt_target *t, float *ms) {
+  if (!t || !ms) { fspt_set_error("fspt_temporal_clamp_last_ms: NULL argument"); return FSPT_E_INVALID; }
+  FLUSH_OR_RETURN(t);
+  if (!t->cl_timed) { fspt_set_error("fspt_temporal_clamp_last_ms: no fspt_temporal_accumulate call with the clamp on yet"); return FSPT_E_STATE; }
+  HIP_TRY(hipSetDevice(t->scene->device));
+  HIP_TRY(hipEventSynchronize(t->cl_ev[1]));
+  HIP_TRY(hipEventElapsedTime(ms, t->cl_ev[0], t->cl_ev[1]));
+  return FSPT_OK;
+}
+
+int fspt_temporal_clamp_eval(int device, const float *hist, const float *fast, uint32_t W, uint32_t H, float sigma_scale,
+                             float *out, float *lo_out, float *hi_out) {
+  if (!hist || !fast || !out) { fspt_set_error("fspt_temporal_clamp_eval: NULL argument"); return FSPT_E_INVALID; }
+  int rc = cl_check_params(1.0f, sigma_scale, "fspt_temporal_clamp_eval");
+  if (rc) return rc;
+  if ((rc = check_device(device))) return rc;
+  const size_t px = (size_t)W * H;
+  if (px == 0) return FSPT_OK;
+  if (sigma_scale == INFINITY) { // the clamp never binds: no launch, the box is everything
+    std::memcpy(out, hist, px * 16);
+    for (size_t i = 0; i < px * 4; ++i) {
+      if (lo_out) lo_out[i] = (i & 3) == 3 ? 0.0f : -INFINITY;
+      if (hi_out) hi_out[i] = (i & 3) == 3 ? 0.0f : INFINITY;
+    }
+    return FSPT_OK;
+  }
+  HIP_TRY(hipSetDevice(device));
+  // one allocation, in float4: hist | fast | out | lo | hi (px each)
+  float4 *d = nullptr;
+  hipError_t e = hipMalloc((void **)&d, px * 16 * 5);
+  if (e == hipSuccess) e = hipMemcpy(d, hist, px * 16, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + px, fast, px * 16, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    fspt::ClampP c{};
+    c.hist = d; c.fast = d + px; c.out = d + 2 * px; c.lo = d + 3 * px; c.hi = d + 4 * px;
+    c.W = W; c.H = H; c.sigma_scale = sigma_scale;
+    e = fspt::launch_temporal_clamp(c, nullptr);
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, d + 2 * px, px * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && lo_out) e = hipMemcpy(lo_out, d + 3 * px, px * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && hi_out) e = hipMemcpy(hi_out, d + 4 * px, px * 16, hipMemcpyDeviceToHost);
+  hipFree(d);
+  if (e != hipSuccess) { fspt_set_error("fspt_temporal_clamp_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
   return FSPT_OK;
 }
 

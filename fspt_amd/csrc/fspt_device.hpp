@@ -384,6 +384,11 @@ struct TemporalBP {
   const float2 *mom_hist;  // the previous call's (M1, M2) (unused when has_mom = 0)
   float2 *mom_out;
   uint32_t has_mom;
+  // fast-history instantiations only (fspt_temporal_set_clamp)
+  const float4 *fast_hist; // the previous call's fast history: rgb, length (unused when has_fast = 0)
+  float4 *fast_out;
+  uint32_t has_fast;
+  float fast_history;      // its cap, in samples: takes max_history's place in the colour's recursion
 };
 // SVGF variance estimate (k_svgf_variance)
 constexpr float SVGF_MIN_HISTORY = 4.0f; // effective frames from which the temporal moments alone give the variance
@@ -397,8 +402,19 @@ struct SvgfVarP {
   float n;             // acc_ticks of the accumulate that wrote hist
   float sn, sz;        // sigma_normal, sigma_depth (step 1)
 };
+// history clamp (k_temporal_clamp): hist.rgb into mu +- sigma_scale sd of the fast history's 5 x 5 window
+constexpr int CLAMP_RADIUS = 2;
+struct ClampP {
+  float4 *hist;        // the long history after the blend, clamped IN PLACE (.w untouched) - or, with out != NULL, only read
+  const float4 *fast;  // the fast history after the blend
+  float4 *out;         // test hook: the result goes here instead, and (lo.rgb, 0) / (hi.rgb, 0) to lo / hi where not NULL
+  float4 *lo, *hi;
+  uint32_t W, H;
+  float sigma_scale;   // finite (+inf never launches)
+};
 hipError_t launch_temporal_gbuffer(const TemporalGP &p, hipStream_t stream);
-hipError_t launch_temporal_blend(const TemporalBP &p, hipStream_t stream); // (p.mom_out != NULL: the moments instantiation)
+hipError_t launch_temporal_blend(const TemporalBP &p, hipStream_t stream); // (p.mom_out != NULL: the moments instantiations; p.fast_out != NULL: the fast-history ones)
+hipError_t launch_temporal_clamp(const ClampP &p, hipStream_t stream);
 hipError_t launch_svgf_variance(const SvgfVarP &p, hipStream_t stream);
 
 // adaptive sampling (fspt_render_adaptive): after n ticks, with the snapshot S taken after m < n ticks

@@ -317,6 +317,13 @@ struct fspt_target {
   float tm_n = 0.0f;                       // acc_ticks of the last accumulate (Fe = length / n)
   hipEvent_t sv_ev[3] = {nullptr, nullptr, nullptr}; // around k_svgf_variance and the guided iterations of the last call
   bool sv_timed = false;
+  // history clamp (fspt_temporal_set_clamp): allocated on enable, 32 bytes per pixel
+  float4 *tm_fast[2] = {nullptr, nullptr}; // fast-history ping-pong (rgb, length), indexed like tm_hist
+  bool tm_clamp = false;                   // the mode
+  bool tm_fast_valid = false;              // tm_fast[tm_cur] belongs to tm_hist[tm_cur] (an accumulate since enable / reset)
+  float tm_fast_history = 0.0f, tm_sigma_scale = 0.0f;
+  hipEvent_t cl_ev[2] = {nullptr, nullptr}; // around k_temporal_clamp of the last accumulate
+  bool cl_timed = false;
 };
 
 static const uint32_t WORK_RING = 4096;

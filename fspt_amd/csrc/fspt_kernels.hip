@@ -2774,7 +2774,10 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_temporal_gbuffer(const Tempor
 // pixel's surface - blended with the accumulator.  One writer per pixel, vector stores, no atomics.
 // MOM: the same taps, tests, weights and blend factor also carry the two luminance moments (l, l^2) of the
 // DEMODULATED input, u = I.rgb / max(albedo, 1e-3) as atrous_load divides; the colour written is the same bit for bit.
-template <bool MOM>
+// FAST: the same taps, tests and weights also carry a second colour history whose length is capped at
+// fast_history - the colour's own recursion with that cap, never reading the long history: one more 16-byte load per
+// accepted tap and one more 16-byte store.  Colour and moments written are the same bit for bit.
+template <bool MOM, bool FAST>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_temporal_blend(const TemporalBP p) {
   const int x = (int)(blockIdx.x * blockDim.x + threadIdx.x), y = (int)(blockIdx.y * blockDim.y + threadIdx.y);
   const int W = (int)p.W, H = (int)p.H;
@@ -2784,6 +2787,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_temporal_blend(const Temporal
   const float4 m = p.m[ip];
   float sr = 0.0f, sg = 0.0f, sb = 0.0f, sn = 0.0f, sw = 0.0f;
   float s1 = 0.0f, s2 = 0.0f;
+  float fr = 0.0f, fg = 0.0f, fb = 0.0f, fn = 0.0f;
   // (a position further than a pixel outside the image has no tap inside it: refused before the float -> int conversion)
   if (p.has_hist && m.w != TM_KIND_NONE && m.x > -1.0f && m.y > -1.0f && m.x < (float)W && m.y < (float)H) {
     const float4 g1 = p.g[2 * ip + 1];
@@ -2811,6 +2815,10 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_temporal_blend(const Temporal
         const float2 hm = p.mom_hist[iq];
         s1 = fma_(w, hm.x, s1); s2 = fma_(w, hm.y, s2);
       }
+      if (FAST && p.has_fast) {
+        const float4 f = p.fast_hist[iq];
+        fr = fma_(w, f.x, fr); fg = fma_(w, f.y, fg); fb = fma_(w, f.z, fb); fn = fma_(w, f.w, fn);
+      }
     }
   }
   float4 o;
@@ -2834,6 +2842,68 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_temporal_blend(const Temporal
   }
   p.out[ip] = o;
   if (MOM) p.mom_out[ip] = mo;
+  if (FAST) {
+    float4 f;
+    if (sw > 0.0f && p.has_fast) {
+      const float Hr = fr / sw, Hg = fg / sw, Hb = fb / sw;
+      const float N = min_(fn / sw, p.fast_history);
+      const float a = max_(p.n / (N + p.n), p.alpha);
+      f = make_float4(Hr + (I.x - Hr) * a, Hg + (I.y - Hg) * a, Hb + (I.z - Hb) * a, min_(N + p.n, p.fast_history));
+    } else {
+      f = make_float4(I.x, I.y, I.z, min_(p.n, p.fast_history));
+    }
+    p.fast_out[ip] = f;
+  }
+}
+
+// The history clamp: per channel the mean and spread of the fast history over the 5 x 5 window inside the
+// image, the long history clamped into mean +- sigma_scale spread, in place (one reader and one writer per pixel; .w, the
+// length, untouched).  Every pixel reads all 25 taps every frame, so the block stages its 20 x 20 footprint of the fast
+// history in LDS once (6.4 KB; a tap outside the image is staged as zero and left out of the count) and sums the window
+// directly from there, row-major, with one fma per tap and moment.  Vector stores, no atomics, no scratch.
+constexpr int CLAMP_TILE = 16 + 2 * CLAMP_RADIUS;
+__global__ __launch_bounds__(BLOCK_THREADS) void k_temporal_clamp(const ClampP p) {
+  __shared__ float4 tile[CLAMP_TILE * CLAMP_TILE];
+  const int W = (int)p.W, H = (int)p.H;
+  const int bx = (int)(blockIdx.x * 16) - CLAMP_RADIUS, by = (int)(blockIdx.y * 16) - CLAMP_RADIUS;
+  const int tid = (int)(threadIdx.y * 16 + threadIdx.x);
+  for (int k = tid; k < CLAMP_TILE * CLAMP_TILE; k += 256) {
+    const int xx = bx + k % CLAMP_TILE, yy = by + k / CLAMP_TILE;
+    float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (xx >= 0 && yy >= 0 && xx < W && yy < H) f = p.fast[(size_t)yy * W + xx];
+    tile[k] = f;
+  }
+  __syncthreads();
+  const int x = (int)(blockIdx.x * 16 + threadIdx.x), y = (int)(blockIdx.y * 16 + threadIdx.y);
+  if (x >= W || y >= H) return;
+  const int x0 = x - CLAMP_RADIUS < 0 ? 0 : x - CLAMP_RADIUS, x1 = x + CLAMP_RADIUS >= W ? W - 1 : x + CLAMP_RADIUS;
+  const int y0 = y - CLAMP_RADIUS < 0 ? 0 : y - CLAMP_RADIUS, y1 = y + CLAMP_RADIUS >= H ? H - 1 : y + CLAMP_RADIUS;
+  const float cnt = (float)((x1 - x0 + 1) * (y1 - y0 + 1));
+  float sr = 0.0f, sg = 0.0f, sb = 0.0f, qr = 0.0f, qg = 0.0f, qb = 0.0f;
+#pragma unroll
+  for (int j = 0; j <= 2 * CLAMP_RADIUS; ++j) {
+#pragma unroll
+    for (int i = 0; i <= 2 * CLAMP_RADIUS; ++i) {
+      const float4 f = tile[((int)threadIdx.y + j) * CLAMP_TILE + (int)threadIdx.x + i]; // (zero outside the image)
+      sr += f.x; sg += f.y; sb += f.z;
+      qr = fma_(f.x, f.x, qr); qg = fma_(f.y, f.y, qg); qb = fma_(f.z, f.z, qb);
+    }
+  }
+  const float mr = sr / cnt, mg = sg / cnt, mb = sb / cnt;
+  const float dr = sqrt_(max_(0.0f, qr / cnt - mr * mr)), dg = sqrt_(max_(0.0f, qg / cnt - mg * mg)), db = sqrt_(max_(0.0f, qb / cnt - mb * mb));
+  const float s = p.sigma_scale;
+  const float4 lo = make_float4(fma_(-s, dr, mr), fma_(-s, dg, mg), fma_(-s, db, mb), 0.0f);
+  const float4 hi = make_float4(fma_(s, dr, mr), fma_(s, dg, mg), fma_(s, db, mb), 0.0f);
+  const size_t ip = (size_t)y * W + x;
+  const float4 h = p.hist[ip];
+  const float4 o = make_float4(min_(max_(h.x, lo.x), hi.x), min_(max_(h.y, lo.y), hi.y), min_(max_(h.z, lo.z), hi.z), h.w);
+  if (p.out) {
+    p.out[ip] = o;
+    if (p.lo) p.lo[ip] = lo;
+    if (p.hi) p.hi[ip] = hi;
+  } else {
+    p.hist[ip] = o;
+  }
 }
 
 // The variance of the luminance the guided filter is about to read: from the temporal moments where the
@@ -3274,8 +3344,19 @@ hipError_t launch_temporal_gbuffer(const TemporalGP &p, hipStream_t stream) {
 }
 
 hipError_t launch_temporal_blend(const TemporalBP &p, hipStream_t stream) {
-  if (p.mom_out) hipLaunchKernelGGL(k_temporal_blend<true>, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), 0, stream, p);
-  else hipLaunchKernelGGL(k_temporal_blend<false>, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), 0, stream, p);
+  const dim3 grid((p.W + 15) / 16, (p.H + 15) / 16), block(16, 16);
+  if (p.fast_out) {
+    if (p.mom_out) hipLaunchKernelGGL((k_temporal_blend<true, true>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((k_temporal_blend<false, true>), grid, block, 0, stream, p);
+  } else {
+    if (p.mom_out) hipLaunchKernelGGL((k_temporal_blend<true, false>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((k_temporal_blend<false, false>), grid, block, 0, stream, p);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_temporal_clamp(const ClampP &p, hipStream_t stream) {
+  hipLaunchKernelGGL(k_temporal_clamp, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), 0, stream, p);
   return hipGetLastError();
 }
 

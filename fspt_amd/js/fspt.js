@@ -453,6 +453,18 @@ class PathTracer {
     if (out.length !== this.resolution[0] * this.resolution[1] * 4) throw new RangeError('temporalDenoiseVariance: need W*H*4 floats');
     return addon.temporalDenoiseVariance(this._target, opts || null, out);
   }
+  /** History clamp (include/fspt.h, DESIGN.md 8.10): temporalSetClamp(true, {fastHistory, sigmaScale}) makes temporalAccumulate() carry a
+   *  fast history and clamp the long one into mean +- sigmaScale spread of its 5 x 5 window (omitted = the library's defaults; sigmaScale
+   *  Infinity: never binds).  Switching it on drops an existing history; a call that changes only the parameters keeps it. */
+  temporalSetClamp(on, opts) {
+    const d = { fastHistory: 32, sigmaScale: 1 };  // include/fspt_tuning.h FSPT_TEMPORAL_CLAMP_* (tests/test_clamp_cpu.py ties them)
+    if (opts != null) {
+      for (const k of Object.keys(opts)) if (!(k in d)) throw new RangeError('temporalSetClamp: unknown parameter ' + k);
+      Object.assign(d, opts);
+    }
+    if (typeof d.fastHistory !== 'number' || typeof d.sigmaScale !== 'number') throw new TypeError('temporalSetClamp: fastHistory and sigmaScale must be numbers');
+    addon.temporalSetClamp(this._target, on === undefined ? true : !!on, d.fastHistory, d.sigmaScale);
+  }
   temporalDraw(exposure, saturation, denoised, out) {
     out = out || new Uint8Array(this.resolution[0] * this.resolution[1] * 4);
     if (out.length !== this.resolution[0] * this.resolution[1] * 4) throw new RangeError('temporalDraw: need W*H*4 bytes');

@@ -48,6 +48,9 @@ def main():
     ap.add_argument("--temporal", action="store_true",
                     help="--bvh refit --frames: reproject and blend every frame with the frames before it (DESIGN 8.8); with "
                          "--atrous K the a-trous filter runs on the temporal result")
+    ap.add_argument("--temporal-clamp", nargs="?", type=float, const=True, default=None, metavar="SIGMA",
+                    help="--temporal: a fast history bounds the long one, so that a change of the light is followed within a few "
+                         "frames (DESIGN 8.10); SIGMA = the box's half width in standard deviations (default: the library's)")
     ap.add_argument("--variance-guided", action="store_true",
                     help="--temporal --atrous K: the K iterations are guided by the per-pixel variance estimate (DESIGN 8.9)")
     ap.add_argument("--sampler", choices=("reference", "sobol"), default="reference",
@@ -79,6 +82,10 @@ def main():
         ap.error("--temporal cannot be combined with --adaptive")
     if args.temporal and not (args.bvh == "refit" and args.frames):
         ap.error("--temporal needs --bvh refit and --frames")
+    if args.temporal_clamp is not None and not args.temporal:
+        ap.error("--temporal-clamp needs --temporal")
+    if args.temporal_clamp is not None and args.temporal_clamp is not True and not args.temporal_clamp >= 0.0:
+        ap.error("--temporal-clamp SIGMA must be >= 0")
     if args.variance_guided and not (args.temporal and args.atrous):
         ap.error("--variance-guided needs --temporal and --atrous K")
     if args.atrous and args.scene and not args.temporal:
@@ -100,7 +107,8 @@ def main():
             t0 = time.perf_counter()
             out = F.render_sequence(args.scene, range(a, b), args.out, args.width, args.height, args.assets, bvh=args.bvh,
                                     rebuild_above=args.rebuild_above,
-                                    temporal={"atrous": args.atrous} if args.temporal else None,
+                                    temporal=({"atrous": args.atrous, "clamp": None if args.temporal_clamp is None else True if args.temporal_clamp is True
+                                               else {"sigma_scale": args.temporal_clamp}} if args.temporal else None),
                                     variance=args.variance_guided, **kw)
             print(f"{len(out)} frames in {time.perf_counter() - t0:.2f} s:", *out)
         else:

@@ -156,7 +156,9 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     for K a-trous iterations on the result.  Every frame then follows the protocol motion_begin, update_geometry, clear and
     render, temporal_accumulate, and the picture written is temporal_draw of the result (`denoise`, the firefly filter of
     draw(), does not apply to it; `adaptive` is refused); frame k renders with seed + k, so that the frames' noise is
-    independent.  A frame that builds a new scene starts a new history.
+    independent.  A frame that builds a new scene starts a new history.  "clamp": True or a dict of
+    PathTracer.temporal_set_clamp's fast_history / sigma_scale: every tracer gets temporal_set_clamp() before
+    its first frame, and every frame's history is clamped into its fast history's box.
     variance (with temporal and "atrous" >= 1): the a-trous iterations are the variance-guided ones - every tracer
     gets temporal_set_moments(), a frame's features() come before its temporal_accumulate (which demodulates by them) and the
     filter is temporal_denoise(iterations=K, variance=True)."""
@@ -168,6 +170,15 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
             raise ValueError('render_sequence: temporal needs bvh="refit" (one scene and tracer across the frames)')
         temporal = {} if temporal is True else dict(temporal)
         atrous = int(temporal.pop("atrous", 0))
+        clamp = temporal.pop("clamp", None)
+        if clamp is not None and clamp is not False:
+            from .tracer import _clamp_params
+            clamp = {} if clamp is True else dict(clamp)
+            if set(clamp) - {"fast_history", "sigma_scale"}:
+                raise TypeError(f"unknown clamp parameters {sorted(set(clamp) - {'fast_history', 'sigma_scale'})}")
+            _clamp_params(**clamp)
+        else:
+            clamp = None
         from .tracer import _temporal_params
         _temporal_params(temporal)  # (refuse bad parameters before the first frame renders)
         if kw.get("adaptive") is not None:
@@ -232,6 +243,8 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                 leaf_order = base.meta["tri_order"]
                 if variance:
                     pt.temporal_set_moments(True)
+                if temporal is not None and clamp is not None:
+                    pt.temporal_set_clamp(True, **clamp)
             if temporal is None:
                 rgba, _ = _render_on(pt, settings, **opt)
             else:

@@ -143,6 +143,35 @@ def svgf_eval(hist, moments, features, n=1, device=0, **params):
     return out, vin, vout
 
 
+CLAMP_DEFAULTS = {"fast_history": 32.0, "sigma_scale": 1.0}  # include/fspt_tuning.h FSPT_TEMPORAL_CLAMP_*
+
+
+def _clamp_params(fast_history=None, sigma_scale=None):
+    """(fast_history, sigma_scale) of the history clamp (None: CLAMP_DEFAULTS), validated like the library does."""
+    fh = float(CLAMP_DEFAULTS["fast_history"] if fast_history is None else fast_history)
+    ss = float(CLAMP_DEFAULTS["sigma_scale"] if sigma_scale is None else sigma_scale)
+    if not (1.0 <= fh < float("inf")) or not ss >= 0.0:
+        raise ValueError("history clamp: need a finite fast_history >= 1 and sigma_scale >= 0 (+inf: the clamp never binds)")
+    return fh, ss
+
+
+def temporal_clamp_eval(hist, fast, sigma_scale=None, device=0):
+    """k_temporal_clamp on host arrays (fspt_temporal_clamp_eval, a test hook): hist, fast float32 [H, W, 4] (rgb, length)
+    -> (out, lo, hi) float32 [H, W, 4]: hist.rgb clamped into the box lo..hi of fast's 5 x 5 window, .w of out = hist's,
+    of lo / hi = 0.  sigma_scale None: CLAMP_DEFAULTS; +inf: out = hist, the box is -inf..+inf."""
+    _, ss = _clamp_params(None, sigma_scale)
+    hist = np.ascontiguousarray(hist, dtype=np.float32)
+    if hist.ndim != 3 or hist.shape[2] != 4:
+        raise ValueError(f"need hist [H, W, 4], got {hist.shape}")
+    H, W = hist.shape[:2]
+    if np.shape(fast) != (H, W, 4):
+        raise ValueError(f"need fast [{H}, {W}, 4], got {np.shape(fast)}")
+    fast = np.ascontiguousarray(fast, dtype=np.float32)
+    out, lo, hi = (np.empty((H, W, 4), np.float32) for _ in range(3))
+    L.check(L.lib().fspt_temporal_clamp_eval(int(device), L.fptr(hist), L.fptr(fast), W, H, ss, L.fptr(out), L.fptr(lo), L.fptr(hi)))
+    return out, lo, hi
+
+
 def light_alias_table(weights):
     """The Vose alias table (float32 prob, uint32 alias) the light table stores for these weights (fspt_light_alias_table,
     a pure host function: no device needed)."""
@@ -769,6 +798,28 @@ class PathTracer:
         ms = (C.c_float * 2)()
         L.check(L.lib().fspt_svgf_last_ms(self._t, ms))
         return float(ms[0]), float(ms[1])
+
+    def temporal_set_clamp(self, on=True, fast_history=None, sigma_scale=None):
+        """History clamp (fspt_temporal_set_clamp): temporal_accumulate() also carries a fast history capped at
+        fast_history samples and clamps the long one into mean +- sigma_scale spread of its 5 x 5 window, so that a change of
+        the light is not averaged over max_history samples.  None: CLAMP_DEFAULTS; sigma_scale inf: the clamp never binds.
+        Switching it on drops an existing history; a call that changes only the parameters keeps it."""
+        fh, ss = _clamp_params(fast_history, sigma_scale) if on else (0.0, 0.0)
+        L.check(L.lib().fspt_temporal_set_clamp(self._t, 1 if on else 0, fh, ss))
+
+    def temporal_fast(self):
+        """The fast history of the last temporal_accumulate with the clamp on (fspt_temporal_read_fast): float32 [H, W, 4]
+        (rgb, length)."""
+        W, H = self.resolution
+        out = np.zeros((H, W, 4), np.float32)
+        L.check(L.lib().fspt_temporal_read_fast(self._t, L.fptr(out)))
+        return out
+
+    def temporal_clamp_last_ms(self):
+        """k_temporal_clamp ms of the last temporal_accumulate with the clamp on, from HIP events."""
+        ms = C.c_float()
+        L.check(L.lib().fspt_temporal_clamp_last_ms(self._t, C.byref(ms)))
+        return float(ms.value)
 
     def temporal_draw(self, exposure=1.0, saturation=1.0, denoised=False):
         """draw() of the temporal result, or of the last temporal_denoise() (fspt_temporal_draw): RGBA8 [H, W, 4]."""

@@ -209,8 +209,8 @@ int fspt_scene_motion_begin(fspt_scene *s); int fspt_scene_motion_end(fspt_scene
 int fspt_temporal_set_moments(fspt_target *t, int on); /* SVGF variance guidance (DESIGN 8.9; rule and defaults: fspt_tuning.h): accumulate also carries luminance moments; default off */
 int fspt_temporal_denoise_variance(fspt_target *t, const fspt_denoise_params *p, float *out); /* fspt_temporal_denoise guided by the variance estimate; sigma_color = sigma_l */
 
-/* intersectScene (tracer.fs:366-404) as a stand-alone entry: n rays (origin xyz, dir xyz) -> closest hit t and
- * triangle index (-1 = miss, t = 1e5), optionally loop-iteration and leaf-visit counts per ray.  Host pointers. */
+int fspt_temporal_set_clamp(fspt_target *t, int on, float fast_history, float sigma_scale); /* history clamp (DESIGN 8.10; rule and defaults: fspt_tuning.h): a fast history bounds the long one; default off */
+/* intersectScene (tracer.fs:366-404) as a stand-alone entry: n rays (origin xyz, dir xyz) -> closest hit t and triangle index (-1 = miss, t = 1e5), optionally loop-iteration and leaf-visit counts per ray.  Host pointers. */
 int fspt_intersect(fspt_scene *scene, const float *rays, uint32_t n, float *t_out, int32_t *index_out, uint32_t *steps_out, uint32_t *leaves_out);
 
 /* Work counters for the byte accounting of SURVEY 8d, summed since the last fspt_clear / fspt_counters_reset while

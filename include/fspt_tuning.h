@@ -214,6 +214,32 @@ int fspt_svgf_last_ms(fspt_target *t, float ms[2]);
  * the variance the last iteration leaves (K = 0: v).  p NULL = the defaults above. */
 int fspt_svgf_eval(int device, const float *hist, const float *moments, const float *features, uint32_t W, uint32_t H, uint32_t n,
                    const fspt_denoise_params *p, float *out, float *var_in, float *var_out);
+/* Temporal history clamp (fspt.h fspt_temporal_set_clamp): k_temporal_blend rejects history on geometry only, so a change of the
+ * LIGHT enters a long history at n / (max_history + n) per frame.  With the mode on (32 bytes per pixel, a ping-pong pair of float4) pass 2
+ * also carries a FAST history F (rgb, length) through the colour's own four taps, acceptance tests and bilinear weights w_q, with the colour's
+ * recursion and fast_history (in samples, like max_history; finite, >= 1) in max_history's place: Hf = sum w_q F(q).rgb / sum w_q,
+ * Nf = min(sum w_q F(q).w / sum w_q, fast_history), af = max(n / (Nf + n), alpha), Fout = (Hf + (I - Hf) af, min(Nf + n, fast_history)); no tap
+ * counts or no fast history: Fout = (I.rgb, min(n, fast_history)).  F never reads the long history: it is what fspt_temporal_accumulate with
+ * max_history = fast_history computes, bit for bit; the colour and the moments of pass 2 are the same bit for bit.  Pass 3 (k_temporal_clamp),
+ * per pixel p and channel c over the taps of the 5 x 5 window around p that lie inside the image (cnt of them): mu = sum Fout_c / cnt,
+ * m2 = sum Fout_c Fout_c / cnt, sd = sqrt(max(0, m2 - mu mu)), lo = mu - sigma_scale sd, hi = mu + sigma_scale sd,
+ * out_c = min(max(hist_c, lo), hi); .w, the length, is untouched.  sigma_scale >= 0; +inf: the clamp never binds (pass 3 is skipped; no
+ * inf * 0).  The clamped value IS the history: out, fspt_temporal_denoise[_variance], fspt_temporal_draw and the next call's taps read it;
+ * the moments of 8.9 are not clamped.  Where the light is stable the box holds the long history and nothing changes; where it changed the long
+ * history is pulled to what the last fast_history samples saw.  Switching the mode on drops an existing history (both start together, as
+ * fspt_temporal_set_moments does); a call that changes only the two parameters keeps both; fspt_temporal_reset drops both; off frees the
+ * pair.  FSPT_E_INVALID: NULL, a non-finite or below-1 fast_history, a negative or NaN sigma_scale; FSPT_E_STATE: a sharded target. */
+#define FSPT_TEMPORAL_CLAMP_FAST_HISTORY 32.0f /* defaults of the hosts (the C call takes both): the best row of DESIGN 8.10's scan, which started from 16 and 2 */
+#define FSPT_TEMPORAL_CLAMP_SIGMA_SCALE 1.0f
+/* Fout of the last fspt_temporal_accumulate with the clamp on: W*H*4 floats (rgb, length), rows bottom-up.  Blocking. */
+int fspt_temporal_read_fast(fspt_target *t, float *out);
+/* GPU ms of pass 3 of the last fspt_temporal_accumulate with the clamp on, from HIP events (sigma_scale = +inf: an empty interval);
+ * fspt_temporal_last_ms keeps its two values.  Blocking. */
+int fspt_temporal_clamp_last_ms(fspt_target *t, float *ms);
+/* Test hook: k_temporal_clamp on host arrays - hist, fast, out: W*H*4 floats (rgb, length); lo_out, hi_out (W*H*4 each, may be NULL): the
+ * box per channel, .w = 0 (sigma_scale = +inf: -inf / +inf and out = hist, without a launch). */
+int fspt_temporal_clamp_eval(int device, const float *hist, const float *fast, uint32_t W, uint32_t H, float sigma_scale,
+                             float *out, float *lo_out, float *hi_out);
 /* fspt_target_set_lights (fspt.h): FSPT_LIGHTS_EMITTERS lets each shading vertex spend its shadow ray on a
  * point of an emissive triangle (probability q = emitter_fraction, in (0, 1]; at most 0.875 with an environment map, 1
  * when the scene has none)

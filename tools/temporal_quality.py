@@ -17,7 +17,13 @@
                       orbits 0.25 degrees per frame, so that most pixels keep a long history; with --scan the settings scanned; with
                       --timing the moments blend, k_svgf_variance and the guided iterations at 1920 x 1080 beside the parent's passes
 
-usage: python tools/temporal_quality.py [--scan] [--timing] [--variance]
+  --clamp             DESIGN 8.10: the history clamp (fspt_temporal_set_clamp) off and on, from the same inputs in the same process, on
+                      the LIGHT sequence - tests/lights_ref.py's scene E3 (it has an environment map) from a fixed camera, 16 frames
+                      of 4 spp at env_theta t0, until the history is full, then 8 frames at t0 + 90 degrees; relative MSE of the last
+                      frame against 4 096 spp at t0 + 90 - and, as the clamp's cost where the light is stable, on the camera sequence
+                      above; with --scan sigma_scale {1, 2, 3, 4} x fast_history {8, 16, 32} on both; with --timing the blend pass with the mode off and on and k_temporal_clamp at 1920 x 1080
+
+usage: python tools/temporal_quality.py [--scan] [--timing] [--variance | --clamp]
 tests/test_temporal_gpu.py::test_quality runs the two sequences and holds them to MEASURED x 1.5."""
 import argparse
 import os
@@ -207,6 +213,83 @@ def variance_timing(arrays, camera, w=1920, h=1080):
     return out
 
 
+# ---- history clamp -----------------------------------------------------------------------------------------
+LIGHT_BEFORE, LIGHT_AFTER, LIGHT_DEG = 16, 8, 90.0
+CLAMP_BEST = dict(fast_history=32.0, sigma_scale=1.0)  # the library's defaults (DESIGN 8.10's scan)
+CLAMP_SCAN = [dict(fast_history=float(f), sigma_scale=float(s)) for s in (1, 2, 3, 4) for f in (8, 16, 32)]
+# on / off of the LIGHT sequence's last frame measured on the MI355X with the shipped defaults (DESIGN 8.10 has the table)
+CLAMP_MEASURED = {"light_on_over_off": 0.557}
+
+
+def light_sequence(arrays, camera, settings, step_deg=0.0, before=LIGHT_BEFORE, after_frames=LIGHT_AFTER, gt=None):
+    """One sequence per entry of `settings` (None = the clamp off, else temporal_set_clamp's parameters), all from the same
+    frames: LIGHT_BEFORE frames, then the change (env_theta + LIGHT_DEG), then LIGHT_AFTER frames.  step_deg != 0: no change
+    of light, the camera orbits instead (the clamp's cost).  -> ([rel MSE of the last frame], raw, gt)"""
+    from fspt_amd import PathTracer
+    frames = before + after_frames
+    after = dict(camera) if step_deg else dict(camera, env_theta=camera["env_theta"] + np.radians(LIGHT_DEG))
+    pts = []
+    for q in settings:
+        pt = PathTracer(arrays, W, H, num_bounces=4)
+        if q is not None:
+            pt.temporal_set_clamp(True, **q)
+        pts.append(pt)
+    if gt is None:
+        pt = pts[0]
+        set_cam(pt, orbit(after, step_deg * (frames - 1)))
+        gt = reference(pt)
+    res, raw = [], None
+    for pt in pts:
+        for k in range(frames):
+            changed = k >= before
+            set_cam(pt, orbit(after if changed else camera, step_deg * k))
+            pt.clear(); pt.seed(7 + k); pt.render(SPP)
+            hist = pt.temporal_accumulate()
+        res.append(rel_mse(hist, gt))
+        raw = rel_mse(pt.readRadiance(), gt)
+        pt.close(); pt.scene.close()
+    return res, raw, gt
+
+
+def clamp_comparison(camera, scan=False, cost_arrays=None):
+    """name -> {raw, off, on[, scan]}: "light" always; "camera" - DESIGN 8.8's camera sequence on cost_arrays, where the light
+    is stable and the clamp can only cost - on request"""
+    import lights_ref as LR
+    settings = [None, CLAMP_BEST] + (CLAMP_SCAN if scan else [])
+    out = {}
+    for name, a, kw in (("light", LR.scene_e3(), {}), ("camera", cost_arrays, dict(step_deg=STEP_DEG, before=FRAMES, after_frames=0))):
+        if a is None:
+            continue
+        r, raw, _ = light_sequence(a, camera, settings, **kw)
+        out[name] = {"raw": raw, "off": r[0], "on": r[1]}
+        if scan:
+            out[name]["scan"] = r[2:]
+    return out
+
+
+def clamp_timing(arrays, camera, w=1920, h=1080):
+    """HIP-event ms, best of 5 after a warm-up, in one process: the blend pass with the mode off and on, k_temporal_clamp"""
+    from fspt_amd import PathTracer
+    pt = PathTracer(arrays, w, h, num_bounces=4)
+    set_cam(pt, camera)
+    pt.render(1)
+    out = {}
+    for on in (False, True):
+        pt.temporal_set_clamp(on)
+        bb, bc = 1e9, 1e9
+        for k in range(6):
+            pt.temporal_accumulate(read=False)
+            if k:
+                bb = min(bb, pt.temporal_last_ms()[1])
+                if on:
+                    bc = min(bc, pt.temporal_clamp_last_ms())
+        out["blend_clamp_%s_ms" % ("on" if on else "off")] = bb
+        if on:
+            out["temporal_clamp_ms"] = bc
+    pt.close(); pt.scene.close()
+    return out
+
+
 def timing(arrays, camera, w=1920, h=1080):
     from fspt_amd import PathTracer
     pt = PathTracer(arrays, w, h, num_bounces=4)
@@ -270,10 +353,23 @@ def main():
     ap.add_argument("--scan", action="store_true")
     ap.add_argument("--timing", action="store_true")
     ap.add_argument("--variance", action="store_true", help="the variance-guided filter against the fixed rule (DESIGN 8.9)")
+    ap.add_argument("--clamp", action="store_true", help="the history clamp off and on over a change of light (DESIGN 8.10)")
     args = ap.parse_args()
     from fspt_amd import scene as S
     arrays = S.bunny_scene(n=24, env_size=(256, 128), sun_deg=3.0)  # the tests' medium scene
     cam = dict(S.BUNNY_CAMERA)
+    if args.clamp:
+        r = clamp_comparison(cam, scan=args.scan, cost_arrays=arrays)
+        print("| sequence | raw last frame | clamp off | clamp on (defaults) | on / off |")
+        print("|---|---|---|---|---|")
+        for name, v in r.items():
+            print("| %s | %.5f | %.5f | %.5f | %.3f |" % (name, v["raw"], v["off"], v["on"], v["on"] / v["off"]))
+        if args.scan:
+            for name, v in r.items():
+                print(name, "scan:", " ".join("s%g/f%g:%.5f" % (q["sigma_scale"], q["fast_history"], x) for q, x in zip(CLAMP_SCAN, v["scan"])))
+        if args.timing:
+            print("clamp timing 1920 x 1080:", {k: round(v, 4) for k, v in clamp_timing(arrays, cam).items()})
+        return
     if args.variance:
         r = variance_comparison(arrays, cam, scan=args.scan)
         print("| sequence | raw | temporal | + a-trous, fixed rule (defaults) | fixed rule (its best scanned row) | + variance-guided a-trous (defaults) | guided / best fixed |")

@@ -47,6 +47,15 @@ class TemporalParams(C.Structure):
     _fields_ = [("alpha", C.c_float), ("max_history", C.c_float), ("depth_tol", C.c_float), ("normal_cos", C.c_float)]
 
 
+class ExposureParams(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("key", "low", "high", "adapt_up", "adapt_down", "min_log2", "max_log2")]
+
+
+class ExposureState(C.Structure):
+    _fields_ = [("exposure", C.c_float), ("valid", C.c_uint32), ("metered", C.c_uint32), ("reserved", C.c_uint32),
+                ("log2_exposure", C.c_double), ("log2_mean", C.c_double)]
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("target_rel_mse", C.c_double), ("max_ticks", C.c_uint32), ("min_ticks", C.c_uint32), ("round_ticks", C.c_uint32)]
 
@@ -153,6 +162,14 @@ SIGNATURES = {
     "fspt_temporal_read_fast": (C.c_int, [_VP, _F]),
     "fspt_temporal_clamp_last_ms": (C.c_int, [_VP, _F]),
     "fspt_temporal_clamp_eval": (C.c_int, [C.c_int, _F, _F, C.c_uint32, C.c_uint32, C.c_float, _F, _F, _F]),
+    "fspt_target_set_auto_exposure": (C.c_int, [_VP, C.c_int, C.POINTER(ExposureParams)]),
+    "fspt_exposure_reset": (C.c_int, [_VP]),
+    "fspt_exposure_get": (C.c_int, [_VP, _F, _F, _U32]),
+    "fspt_exposure_last_ms": (C.c_int, [_VP, _F]),
+    "fspt_exposure_last_draw_ms": (C.c_int, [_VP, _F]),
+    "fspt_exposure_set_form": (C.c_int, [C.c_int]),
+    "fspt_exposure_eval": (C.c_int, [C.c_int, _F, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ExposureParams),
+                                     C.POINTER(ExposureState), _U32, C.POINTER(ExposureState)]),
     "fspt_scene_motion_begin": (C.c_int, [_VP]),
     "fspt_scene_motion_end": (C.c_int, [_VP]),
     "fspt_intersect": (C.c_int, [_VP, _F, C.c_uint32, _F, C.POINTER(C.c_int32), _U32, _U32]),

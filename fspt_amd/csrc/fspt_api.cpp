@@ -779,6 +779,8 @@ int fspt_target_destroy(fspt_target *t) {
   for (hipEvent_t ev : t->sv_ev) if (ev) hipEventDestroy(ev);
   hipFree(t->tm_fast[0]); hipFree(t->tm_fast[1]);
   for (hipEvent_t ev : t->cl_ev) if (ev) hipEventDestroy(ev);
+  hipFree(t->ax_hist);
+  for (hipEvent_t ev : t->ax_ev) if (ev) hipEventDestroy(ev);
   hipFree(t->ad_snap); hipFree(t->ad_list[0]); hipFree(t->ad_list[1]); hipFree(t->ad_count); hipFree(t->ad_err);
   {
     fspt_target::WfLane &ln = t->wf;
@@ -1329,6 +1331,23 @@ int fspt_read_radiance(fspt_target *t, float *out) {
   return FSPT_OK;
 }
 
+// k_draw of `src` on `st`.  With auto-exposure on the buffer is metered first, on the same stream - histogram,
+// resolve - and k_draw_auto multiplies the caller's exposure by the value the resolve left in device memory: no host read.
+static hipError_t draw_launch(fspt_target *t, const float4 *src, float exposure, float saturation, int denoise, float max_sigma,
+                              float scale, uint32_t *out, hipStream_t st) {
+  if (!t->ax_on) return fspt::launch_draw(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, st);
+  hipError_t e = hipEventRecord(t->ax_ev[0], st);
+  if (e == hipSuccess) e = fspt::launch_exposure_histogram(src, t->W, t->vw, t->vh, t->ax_hist, fspt::g_exposure_form, st);
+  if (e == hipSuccess) e = hipEventRecord(t->ax_ev[1], st);
+  if (e == hipSuccess) e = fspt::launch_exposure_resolve(t->ax_hist, t->ax_state, t->ax_p, st);
+  if (e == hipSuccess) e = hipEventRecord(t->ax_ev[2], st);
+  if (e != hipSuccess) return e;
+  t->ax_timed = true;
+  e = fspt::launch_draw_auto(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, t->ax_state, st);
+  if (e == hipSuccess) e = hipEventRecord(t->ax_ev[3], st);
+  return e;
+}
+
 int fspt_draw(fspt_target *t, float exposure, float saturation, int denoise, float max_sigma, uint8_t *out_rgba8) {
   return fspt_draw_scaled(t, exposure, saturation, denoise, max_sigma, 1.0f, out_rgba8);
 }
@@ -1342,7 +1361,7 @@ int fspt_draw_scaled(fspt_target *t, float exposure, float saturation, int denoi
   size_t n = (size_t)t->W * t->H;
   uint32_t *d = nullptr;
   HIP_TRY(hipMalloc((void **)&d, n * 4));
-  hipError_t e = fspt::launch_draw(t->accum, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, d, t->stream);
+  hipError_t e = draw_launch(t, t->accum, exposure, saturation, denoise, max_sigma, scale, d, t->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(out_rgba8, d, n * 4, hipMemcpyDeviceToHost, t->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
   hipFree(d);
@@ -1633,7 +1652,7 @@ int fspt_present(fspt_target *t, float exposure, float saturation, int denoise, 
   // pinned memory
   const size_t n = (size_t)t->W * t->H;
   const int slot = t->pr_slot < 0 ? 0 : t->pr_slot ^ 1;
-  HIP_TRY(fspt::launch_draw(t->accum, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, t->pr_dev[slot], ds));
+  HIP_TRY(draw_launch(t, t->accum, exposure, saturation, denoise, max_sigma, scale, t->pr_dev[slot], ds)); // (metered on ds too: DESIGN 8.11, ordering)
   HIP_TRY(hipEventRecord(t->pr_acc, ds)); // the next resolve writes the accumulator only after this draw has read it
   t->pr_acc_stream = ds;
   HIP_TRY(hipMemcpyAsync(t->pr_host[slot], t->pr_dev[slot], n * 4, hipMemcpyDeviceToHost, ds));
@@ -1753,7 +1772,7 @@ int fspt_draw_denoised(fspt_target *t, float exposure, float saturation, uint8_t
   size_t n = (size_t)t->W * t->H;
   uint32_t *d = nullptr;
   HIP_TRY(hipMalloc((void **)&d, n * 4));
-  hipError_t e = fspt::launch_draw(t->dn_out, t->W, t->H, exposure, saturation, 0, 0.0f, 1.0f, d, t->stream);
+  hipError_t e = draw_launch(t, t->dn_out, exposure, saturation, 0, 0.0f, 1.0f, d, t->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(out_rgba8, d, n * 4, hipMemcpyDeviceToHost, t->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
   hipFree(d);
@@ -1893,7 +1912,7 @@ int fspt_temporal_draw(fspt_target *t, float exposure, float saturation, int den
   size_t n = (size_t)t->W * t->H;
   uint32_t *d = nullptr;
   HIP_TRY(hipMalloc((void **)&d, n * 4));
-  hipError_t e = fspt::launch_draw(denoised ? t->dn_out : t->tm_hist[t->tm_cur], t->W, t->H, exposure, saturation, 0, 0.0f, 1.0f, d, t->stream);
+  hipError_t e = draw_launch(t, denoised ? t->dn_out : t->tm_hist[t->tm_cur], exposure, saturation, 0, 0.0f, 1.0f, d, t->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(out_rgba8, d, n * 4, hipMemcpyDeviceToHost, t->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
   hipFree(d);
@@ -2191,6 +2210,139 @@ int fspt_temporal_clamp_eval(int device, const float *hist, const float *fast, u
   if (e == hipSuccess && hi_out) e = hipMemcpy(hi_out, d + 4 * px, px * 16, hipMemcpyDeviceToHost);
   hipFree(d);
   if (e != hipSuccess) { fspt_set_error("fspt_temporal_clamp_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
+  return FSPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// auto-exposure (k_exposure_histogram / k_exposure_resolve / k_draw_auto)
+// ---------------------------------------------------------------------------
+static int ax_check_params(const fspt_exposure_params *p, fspt::ExposureP &q, const char *fn) {
+  static const fspt_exposure_params dflt = {FSPT_EXPOSURE_KEY, FSPT_EXPOSURE_LOW, FSPT_EXPOSURE_HIGH, FSPT_EXPOSURE_ADAPT_UP, FSPT_EXPOSURE_ADAPT_DOWN,
+                                            FSPT_EXPOSURE_MIN_LOG2, FSPT_EXPOSURE_MAX_LOG2};
+  if (!p) p = &dflt;
+  const float f[7] = {p->key, p->low, p->high, p->adapt_up, p->adapt_down, p->min_log2, p->max_log2};
+  bool ok = true;
+  for (float v : f) ok = ok && std::isfinite(v);
+  ok = ok && p->key > 0.0f && p->low >= 0.0f && p->low < p->high && p->high <= 1.0f && p->adapt_up > 0.0f && p->adapt_up <= 1.0f &&
+       p->adapt_down > 0.0f && p->adapt_down <= 1.0f && p->min_log2 <= p->max_log2;
+  if (!ok) {
+    fspt_set_error("%s: need finite parameters with key > 0, 0 <= low < high <= 1, adapt_up and adapt_down in (0, 1], min_log2 <= max_log2", fn);
+    return FSPT_E_INVALID;
+  }
+  q = fspt::ExposureP{p->key, p->low, p->high, p->adapt_up, p->adapt_down, p->min_log2, p->max_log2};
+  return FSPT_OK;
+}
+static const fspt::ExposureState AX_FIRST = {1.0f, 0u, 0u, 0u, 0.0, 0.0}; // never metered: exposure 1, nothing to adapt from
+static_assert(sizeof(fspt::ExposureState) == sizeof(fspt_exposure_state) && sizeof(fspt_exposure_state) == 32, "fspt_exposure_state is the device's record");
+
+int fspt_exposure_set_form(int form) {
+  if (form != 0 && form != 1) { fspt_set_error("fspt_exposure_set_form: form must be 0 or 1"); return FSPT_E_INVALID; }
+  fspt::g_exposure_form = form;
+  return FSPT_OK;
+}
+
+int fspt_target_set_auto_exposure(fspt_target *t, int on, const fspt_exposure_params *p) {
+  if (!t) { fspt_set_error("fspt_target_set_auto_exposure: NULL argument"); return FSPT_E_INVALID; }
+  fspt::ExposureP q{};
+  int rc;
+  if (on && (rc = ax_check_params(p, q, "fspt_target_set_auto_exposure"))) return rc;
+  if ((rc = dn_enter(t, true, "fspt_target_set_auto_exposure"))) return rc;
+  if (!on) {
+    HIP_TRY(hipStreamSynchronize(t->stream)); // (dn_enter joined a present: nothing reads the state any more)
+    hipFree(t->ax_hist);
+    t->ax_hist = nullptr; t->ax_state = nullptr;
+    t->ax_on = t->ax_timed = false;
+    return FSPT_OK;
+  }
+  if (t->n_shards > 1) { fspt_set_error("fspt_target_set_auto_exposure: sharded target"); return FSPT_E_STATE; }
+  t->ax_p = q; // (a change of the parameters alone keeps the adapted state)
+  if (t->ax_on) return FSPT_OK;
+  const size_t hist_bytes = fspt::EXPOSURE_BINS * sizeof(uint32_t);
+  if (!t->ax_hist) HIP_TRY(hipMalloc((void **)&t->ax_hist, hist_bytes + sizeof(fspt::ExposureState)));
+  t->ax_state = (fspt::ExposureState *)(t->ax_hist + fspt::EXPOSURE_BINS);
+  HIP_TRY(hipMemsetAsync(t->ax_hist, 0, hist_bytes, t->stream));
+  HIP_TRY(hipMemcpyAsync(t->ax_state, &AX_FIRST, sizeof AX_FIRST, hipMemcpyHostToDevice, t->stream));
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  for (hipEvent_t &ev : t->ax_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
+  t->ax_on = true; t->ax_timed = false;
+  return FSPT_OK;
+}
+
+int fspt_exposure_reset(fspt_target *t) {
+  int rc = dn_enter(t, true, "fspt_exposure_reset");
+  if (rc) return rc;
+  if (!t->ax_on) { fspt_set_error("fspt_exposure_reset: auto-exposure is off"); return FSPT_E_STATE; }
+  HIP_TRY(hipMemcpyAsync(t->ax_state, &AX_FIRST, sizeof AX_FIRST, hipMemcpyHostToDevice, t->stream));
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  return FSPT_OK;
+}
+
+int fspt_exposure_get(fspt_target *t, float *exposure, float *log2_mean, uint32_t *metered) {
+  int rc = dn_enter(t, exposure || log2_mean || metered, "fspt_exposure_get");
+  if (rc) return rc;
+  if (!t->ax_on) { fspt_set_error("fspt_exposure_get: auto-exposure is off"); return FSPT_E_STATE; }
+  fspt::ExposureState s;
+  HIP_TRY(hipMemcpyAsync(&s, t->ax_state, sizeof s, hipMemcpyDeviceToHost, t->stream));
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  if (exposure) *exposure = s.exposure;
+  if (log2_mean) *log2_mean = (float)s.log2_mean;
+  if (metered) *metered = s.metered;
+  return FSPT_OK;
+}
+
+int fspt_exposure_last_ms(fspt_target *t, float ms[2]) {
+  if (!t || !ms) { fspt_set_error("fspt_exposure_last_ms: NULL argument"); return FSPT_E_INVALID; }
+  FLUSH_OR_RETURN(t);
+  if (!t->ax_timed) { fspt_set_error("fspt_exposure_last_ms: no draw with auto-exposure on yet"); return FSPT_E_STATE; }
+  HIP_TRY(hipSetDevice(t->scene->device));
+  HIP_TRY(hipEventSynchronize(t->ax_ev[2]));
+  HIP_TRY(hipEventElapsedTime(&ms[0], t->ax_ev[0], t->ax_ev[1]));
+  HIP_TRY(hipEventElapsedTime(&ms[1], t->ax_ev[1], t->ax_ev[2]));
+  return FSPT_OK;
+}
+
+int fspt_exposure_last_draw_ms(fspt_target *t, float *ms) {
+  if (!t || !ms) { fspt_set_error("fspt_exposure_last_draw_ms: NULL argument"); return FSPT_E_INVALID; }
+  FLUSH_OR_RETURN(t);
+  if (!t->ax_timed) { fspt_set_error("fspt_exposure_last_draw_ms: no draw with auto-exposure on yet"); return FSPT_E_STATE; }
+  HIP_TRY(hipSetDevice(t->scene->device));
+  HIP_TRY(hipEventSynchronize(t->ax_ev[3]));
+  HIP_TRY(hipEventElapsedTime(ms, t->ax_ev[2], t->ax_ev[3]));
+  return FSPT_OK;
+}
+
+int fspt_exposure_eval(int device, const float *rgba, uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const fspt_exposure_params *p,
+                       const fspt_exposure_state *prev, uint32_t *hist_out, fspt_exposure_state *state_out) {
+  if (!rgba || !hist_out || !state_out) { fspt_set_error("fspt_exposure_eval: NULL argument"); return FSPT_E_INVALID; }
+  fspt::ExposureP q{};
+  int rc = ax_check_params(p, q, "fspt_exposure_eval");
+  if (rc) return rc;
+  if (vw == 0 && vh == 0) { vw = W; vh = H; } // (as fspt_target_set_viewport: 0, 0 = the whole image)
+  if (W == 0 || H == 0 || vw == 0 || vh == 0 || vw > W || vh > H || (uint64_t)W * H > 0xFFFFFFFFull) {
+    fspt_set_error("fspt_exposure_eval: need 1 <= vw <= W, 1 <= vh <= H and fewer than 2^32 pixels"); return FSPT_E_INVALID;
+  }
+  if ((rc = check_device(device))) return rc;
+  HIP_TRY(hipSetDevice(device));
+  const size_t px = (size_t)W * H, hist_bytes = fspt::EXPOSURE_BINS * sizeof(uint32_t);
+  // one allocation: image | histogram | state
+  char *d = nullptr;
+  hipError_t e = hipMalloc((void **)&d, px * 16 + hist_bytes + sizeof(fspt::ExposureState));
+  uint32_t *hist = (uint32_t *)(d + px * 16);
+  fspt::ExposureState *state = (fspt::ExposureState *)(d + px * 16 + hist_bytes);
+  if (e == hipSuccess) e = hipMemcpy(d, rgba, px * 16, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(hist, 0, hist_bytes);
+  if (e == hipSuccess) e = hipMemcpy(state, prev ? (const void *)prev : (const void *)&AX_FIRST, sizeof(fspt::ExposureState), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = fspt::launch_exposure_histogram((const float4 *)d, W, vw, vh, hist, fspt::g_exposure_form, nullptr);
+  if (e == hipSuccess) e = hipMemcpy(hist_out, hist, hist_bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = fspt::launch_exposure_resolve(hist, state, q, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(state_out, state, sizeof(fspt::ExposureState), hipMemcpyDeviceToHost);
+  // reserved = the counts the resolve left behind, summed: 0 (it clears the histogram for the next metering)
+  uint32_t left[fspt::EXPOSURE_BINS];
+  if (e == hipSuccess) e = hipMemcpy(left, hist, hist_bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) { uint32_t any = 0; for (uint32_t c : left) any |= c; state_out->reserved = any; }
+  hipFree(d);
+  if (e != hipSuccess) { fspt_set_error("fspt_exposure_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
   return FSPT_OK;
 }
 

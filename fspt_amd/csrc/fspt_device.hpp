@@ -455,6 +455,21 @@ hipError_t launch_light_eval(const DScene &S, const float *in, uint32_t n, int *
 hipError_t launch_bvh_test(const TraceP &p, hipStream_t stream);
 hipError_t launch_draw(const float4 *acc, uint32_t W, uint32_t H, float exposure, float saturation, int denoise,
                        float max_sigma, float scale, uint32_t *out, hipStream_t stream);
+// auto-exposure (fspt_target_set_auto_exposure)
+constexpr uint32_t EXPOSURE_BINS = 256; // 32 octaves from 2^-16, 8 sub-bins each
+struct ExposureP { float key, low, high, adapt_up, adapt_down, min_log2, max_log2; }; // fspt_exposure_params, validated
+struct ExposureState {      // 32 bytes of device memory (fspt_exposure_state): what k_exposure_resolve writes and k_draw_auto reads
+  float exposure;           // (float)exp2(log2_exposure); 1 until the first metering that saw a pixel
+  uint32_t valid;           // there is a previous state to adapt from
+  uint32_t metered, pad;    // N of the last metering with N > 0
+  double log2_exposure, log2_mean;
+};
+extern int g_exposure_form; // the shipped form, or fspt_exposure_set_form's (a measurement switch)
+// form 0: one LDS atomic per pixel; 1: the first active lane's bin is counted by a ballot (same histogram bit for bit)
+hipError_t launch_exposure_histogram(const float4 *src, uint32_t W, uint32_t vw, uint32_t vh, uint32_t *hist, int form, hipStream_t stream);
+hipError_t launch_exposure_resolve(uint32_t *hist, ExposureState *state, const ExposureP &p, hipStream_t stream); // (zeroes hist)
+hipError_t launch_draw_auto(const float4 *acc, uint32_t W, uint32_t H, float exposure, float saturation, int denoise,
+                            float max_sigma, float scale, uint32_t *out, const ExposureState *state, hipStream_t stream);
 hipError_t launch_math(int op, const float *a, const float *b, uint32_t n, float *out, hipStream_t stream);
 
 } // namespace fspt

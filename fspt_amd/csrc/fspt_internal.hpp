@@ -324,6 +324,13 @@ struct fspt_target {
   float tm_fast_history = 0.0f, tm_sigma_scale = 0.0f;
   hipEvent_t cl_ev[2] = {nullptr, nullptr}; // around k_temporal_clamp of the last accumulate
   bool cl_timed = false;
+  // auto-exposure (fspt_target_set_auto_exposure): allocated on enable, 1 KiB of histogram + 32 bytes of state
+  uint32_t *ax_hist = nullptr;             // 256 counts, zero between meterings (k_exposure_resolve clears them)
+  fspt::ExposureState *ax_state = nullptr; // behind the histogram, in the same allocation
+  bool ax_on = false;                      // the mode
+  fspt::ExposureP ax_p{};
+  hipEvent_t ax_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the two kernels of the last metering and its k_draw_auto
+  bool ax_timed = false;
 };
 
 static const uint32_t WORK_RING = 4096;

@@ -824,6 +824,36 @@ static napi_value TemporalSetClamp(napi_env env, napi_callback_info info) {
   FSPT_OK_OR_THROW(fspt_temporal_set_clamp((fspt_target *)h, on ? 1 : 0, (float)fh, (float)ss));
   return undefined(env);
 }
+/* setAutoExposure(target, on, key, low, high, adaptUp, adaptDown, minLog2, maxLog2) / exposure(target) -> {exposure, log2Mean, metered} /
+ * exposureReset(target): auto-exposure; the numbers are the library's to refuse */
+static napi_value SetAutoExposure(napi_env env, napi_callback_info info) {
+  napi_value a[9]; void *h; bool on; double v[7];
+  if (get_args(env, info, 9, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  NAPI_OK(napi_get_value_bool(env, a[1], &on));
+  for (int k = 0; k < 7; ++k) NAPI_OK(napi_get_value_double(env, a[2 + k], &v[k]));
+  fspt_exposure_params p = {(float)v[0], (float)v[1], (float)v[2], (float)v[3], (float)v[4], (float)v[5], (float)v[6]};
+  FSPT_OK_OR_THROW(fspt_target_set_auto_exposure((fspt_target *)h, on ? 1 : 0, &p));
+  return undefined(env);
+}
+static napi_value Exposure(napi_env env, napi_callback_info info) {
+  napi_value a[1], o, v; void *h; float e = 0.0f, m = 0.0f; uint32_t n = 0;
+  if (get_args(env, info, 1, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  FSPT_OK_OR_THROW(fspt_exposure_get((fspt_target *)h, &e, &m, &n));
+  NAPI_OK(napi_create_object(env, &o));
+  NAPI_OK(napi_create_double(env, (double)e, &v));
+  NAPI_OK(napi_set_named_property(env, o, "exposure", v));
+  NAPI_OK(napi_create_double(env, (double)m, &v));
+  NAPI_OK(napi_set_named_property(env, o, "log2Mean", v));
+  NAPI_OK(napi_create_uint32(env, n, &v));
+  NAPI_OK(napi_set_named_property(env, o, "metered", v));
+  return o;
+}
+static napi_value ExposureReset(napi_env env, napi_callback_info info) {
+  napi_value a[1]; void *h;
+  if (get_args(env, info, 1, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  FSPT_OK_OR_THROW(fspt_exposure_reset((fspt_target *)h));
+  return undefined(env);
+}
 static napi_value TemporalDenoiseVariance(napi_env env, napi_callback_info info) {
   napi_value a[3]; void *h, *p = NULL; size_t n = 0; napi_valuetype vt;
   if (get_args(env, info, 3, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
@@ -1283,7 +1313,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
       {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
-      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
+      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},
       {"renderAsync", RenderAsync}, {"multiCreate", MultiCreate}, {"multiDestroy", MultiDestroy}, {"multiTarget", MultiTarget},
       {"multiCamera", MultiCamera}, {"multiTrace", MultiTrace}, {"multiRender", MultiRender}, {"multiRenderAsync", MultiRenderAsync},

@@ -465,6 +465,21 @@ class PathTracer {
     if (typeof d.fastHistory !== 'number' || typeof d.sigmaScale !== 'number') throw new TypeError('temporalSetClamp: fastHistory and sigmaScale must be numbers');
     addon.temporalSetClamp(this._target, on === undefined ? true : !!on, d.fastHistory, d.sigmaScale);
   }
+  /** Auto-exposure (include/fspt.h, DESIGN.md 8.11): setAutoExposure(true, {key, low, high, adaptUp, adaptDown, minLog2, maxLog2}) makes every
+   *  drawQuad(), present(), drawDenoised() and temporalDraw() meter the buffer it draws on the GPU; their exposure argument becomes a compensation
+   *  (omitted parameters = the library's defaults).  A call that changes only the parameters keeps the adapted state.  exposure(): {exposure,
+   *  log2Mean, metered} of the last metering (blocking); exposureReset(): the next metering is a first one. */
+  setAutoExposure(on, opts) {
+    const d = { key: 0.18, low: 0.10, high: 0.90, adaptUp: 1, adaptDown: 1, minLog2: -8, maxLog2: 8 };  // include/fspt_tuning.h FSPT_EXPOSURE_*
+    if (opts != null) {
+      for (const k of Object.keys(opts)) if (!(k in d)) throw new RangeError('setAutoExposure: unknown parameter ' + k);
+      Object.assign(d, opts);
+    }
+    for (const k of Object.keys(d)) if (typeof d[k] !== 'number') throw new TypeError('setAutoExposure: ' + k + ' must be a number');
+    addon.setAutoExposure(this._target, on === undefined ? true : !!on, d.key, d.low, d.high, d.adaptUp, d.adaptDown, d.minLog2, d.maxLog2);
+  }
+  exposure() { return addon.exposure(this._target); }
+  exposureReset() { addon.exposureReset(this._target); }
   temporalDraw(exposure, saturation, denoised, out) {
     out = out || new Uint8Array(this.resolution[0] * this.resolution[1] * 4);
     if (out.length !== this.resolution[0] * this.resolution[1] * 4) throw new RangeError('temporalDraw: need W*H*4 bytes');

@@ -51,6 +51,9 @@ def main():
     ap.add_argument("--temporal-clamp", nargs="?", type=float, const=True, default=None, metavar="SIGMA",
                     help="--temporal: a fast history bounds the long one, so that a change of the light is followed within a few "
                          "frames (DESIGN 8.10); SIGMA = the box's half width in standard deviations (default: the library's)")
+    ap.add_argument("--auto-exposure", nargs="?", type=float, const=True, default=None, metavar="KEY",
+                    help="meter every frame on the GPU and expose its mean log luminance to KEY (default 0.18; DESIGN 8.11); "
+                         "--exposure and the scene file's `exposure` then act as compensation")
     ap.add_argument("--variance-guided", action="store_true",
                     help="--temporal --atrous K: the K iterations are guided by the per-pixel variance estimate (DESIGN 8.9)")
     ap.add_argument("--sampler", choices=("reference", "sobol"), default="reference",
@@ -86,6 +89,10 @@ def main():
         ap.error("--temporal-clamp needs --temporal")
     if args.temporal_clamp is not None and args.temporal_clamp is not True and not args.temporal_clamp >= 0.0:
         ap.error("--temporal-clamp SIGMA must be >= 0")
+    if args.auto_exposure is not None and args.auto_exposure is not True and not (np.isfinite(args.auto_exposure) and args.auto_exposure > 0.0):
+        ap.error("--auto-exposure KEY must be a finite value > 0")
+    if args.auto_exposure is not None and args.exposure != 1.0 and args.scene and args.frames:
+        ap.error("--auto-exposure with --frames takes its compensation from the scene files' `exposure`, not from --exposure")
     if args.variance_guided and not (args.temporal and args.atrous):
         ap.error("--variance-guided needs --temporal and --atrous K")
     if args.atrous and args.scene and not args.temporal:
@@ -102,6 +109,8 @@ def main():
             kw.update(lights="emitters", emitter_fraction=args.emitter_fraction)
         if args.adaptive is not None:
             kw.update(samples=args.spp, adaptive=args.adaptive, sample_map=args.sample_map)
+        if args.auto_exposure is not None:
+            kw.update(auto_exposure=True if args.auto_exposure is True else {"key": args.auto_exposure})
         if args.frames:
             a, b = (int(x) for x in args.frames.split(":"))
             t0 = time.perf_counter()
@@ -131,6 +140,8 @@ def main():
         pt.set_sampler(args.sampler, args.sampler_seed)
     if args.lights:
         pt.set_lights("emitters", args.emitter_fraction)
+    if args.auto_exposure is not None:
+        pt.set_auto_exposure(True, **({} if args.auto_exposure is True else {"key": args.auto_exposure}))
     t0 = time.perf_counter()
     if args.adaptive is None:
         pt.render(args.spp)

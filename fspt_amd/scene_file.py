@@ -91,16 +91,21 @@ def load_scene_file(scene_path, asset_root=None, leaf_size=4, bvh="sah", device=
 
 
 def render_frame(arrays, settings, width, height, samples=None, bounces=4, seed=1, saturation=1.0, denoise=False,
-                 max_sigma=3.0, device=0, lights=None, emitter_fraction=0.5, adaptive=None, sample_map=None):
+                 max_sigma=3.0, device=0, lights=None, emitter_fraction=0.5, adaptive=None, sample_map=None, auto_exposure=None):
     """One frame as the reference produces it in frame mode: `samples` ticks from a cleared accumulator
     (main.js:838-857; its very first, discarded tick is not reproduced), then drawQuad.  Returns
     (rgba8 [H, W, 4] top row first - what canvas.toBlob encodes -, radiance [H, W, 4] bottom row first).
     lights="emitters": next-event estimation of emissive triangles (PathTracer.set_lights).  adaptive=REL_MSE:
     adaptive sampling with `samples` as the most ticks a tile gets (PathTracer.render_adaptive); sample_map:
-    then also write its ticks per pixel as a grey PNG there (white = `samples`)."""
+    then also write its ticks per pixel as a grey PNG there (white = `samples`).  auto_exposure: True or a dict of
+    PathTracer.set_auto_exposure's parameters (DESIGN 8.11): the frame is metered on the GPU and the scene's `exposure`
+    becomes a compensation; a still adapts instantly."""
     from .tracer import PathTracer
+    auto_exposure = _auto_exposure_params(auto_exposure)
     pt = PathTracer(arrays, width, height, device=device, num_bounces=bounces)
     try:
+        if auto_exposure is not None:
+            pt.set_auto_exposure(True, **auto_exposure)
         rgba, rad = _render_on(pt, settings, samples, seed, saturation, denoise, max_sigma, lights, emitter_fraction, adaptive,
                                sample_map)
     finally:
@@ -109,8 +114,25 @@ def render_frame(arrays, settings, width, height, samples=None, bounces=4, seed=
     return rgba[::-1].copy(), rad
 
 
-def _render_on(pt, settings, samples, seed, saturation, denoise, max_sigma, lights, emitter_fraction, adaptive, sample_map):
-    """render_frame's work on an existing tracer, from a cleared accumulator (bottom row first)"""
+SEQUENCE_ADAPT = 0.25  # render_sequence's auto-exposure step per frame, in log2 (1 = instant): within 10 % of a new light in 8 frames
+
+
+def _auto_exposure_params(auto_exposure, adapt=None):
+    """None (off) or PathTracer.set_auto_exposure's keyword arguments from True / a dict, refused here if the library would;
+    adapt: the adapt_up / adapt_down a dict that names neither gets."""
+    if auto_exposure is None or auto_exposure is False:
+        return None
+    from .tracer import _exposure_params
+    params = {} if auto_exposure is True else dict(auto_exposure)
+    if adapt is not None and "adapt_up" not in params and "adapt_down" not in params:
+        params.update(adapt_up=adapt, adapt_down=adapt)
+    _exposure_params(params)
+    return params
+
+
+def _render_on(pt, settings, samples, seed, saturation, denoise, max_sigma, lights, emitter_fraction, adaptive, sample_map, draw=True):
+    """render_frame's work on an existing tracer, from a cleared accumulator (bottom row first); draw=False: no picture
+    (None comes back in its place; a draw under auto-exposure would adapt the exposure once more)"""
     pt.clear()
     pt.eye, pt.dir = list(settings["eye"]), list(settings["dir"])
     pt.fovScale, pt.envTheta = settings["fov_scale"], settings["env_theta"]
@@ -125,7 +147,7 @@ def _render_on(pt, settings, samples, seed, saturation, denoise, max_sigma, ligh
         pt.render_adaptive(adaptive, max_ticks=n)
         if sample_map:
             write_sample_map(sample_map, pt.sample_counts(), n)
-    rgba = pt.draw(settings["exposure"], saturation, denoise, max_sigma)
+    rgba = pt.draw(settings["exposure"], saturation, denoise, max_sigma) if draw else None
     rad = pt.readRadiance()
     return rgba, rad
 
@@ -139,7 +161,7 @@ def write_sample_map(path, counts, max_ticks):
 
 
 def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", rebuild_above=None,
-                    on_frame=None, temporal=None, variance=False, **kw):
+                    on_frame=None, temporal=None, variance=False, auto_exposure=None, **kw):
     """frame=N sequencing (main.js:851-866, 966-969): for every N in `frames` load `scene_pattern.format(frame=N)`
     (the per-frame scene JSON the reference's server hands out for `?frame=N`), render it, write
     `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1.
@@ -161,8 +183,14 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     its first frame, and every frame's history is clamped into its fast history's box.
     variance (with temporal and "atrous" >= 1): the a-trous iterations are the variance-guided ones - every tracer
     gets temporal_set_moments(), a frame's features() come before its temporal_accumulate (which demodulates by them) and the
-    filter is temporal_denoise(iterations=K, variance=True)."""
+    filter is temporal_denoise(iterations=K, variance=True).
+    auto_exposure: True or a dict of PathTracer.set_auto_exposure's parameters; every tracer gets
+    set_auto_exposure() before its first frame, each frame's one drawing meters what it draws (the accumulator, or under
+    temporal the history or its filtered form) and the scene's `exposure` becomes a compensation.  With bvh="refit" the
+    tracer lives across the frames and the exposure ADAPTS: adapt_up = adapt_down = SEQUENCE_ADAPT per frame unless the
+    dict names one; every other bvh builds a tracer per frame, which meters instantly.  A new scene starts from a first metering."""
     from PIL import Image
+    auto_exposure = _auto_exposure_params(auto_exposure, SEQUENCE_ADAPT if bvh == "refit" else None)
     written = []
     device = kw.get("device", 0)
     if temporal is not None and temporal is not False:
@@ -198,7 +226,7 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     if bvh != "refit":
         for n in frames:
             arrays, settings = load_scene_file(scene_pattern.format(frame=n), asset_root, bvh=bvh, device=device)
-            rgba, _ = render_frame(arrays, settings, width, height, **kw)
+            rgba, _ = render_frame(arrays, settings, width, height, auto_exposure=auto_exposure, **kw)
             if on_frame:
                 on_frame(n, "build")
             save(n, rgba)
@@ -245,10 +273,13 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                     pt.temporal_set_moments(True)
                 if temporal is not None and clamp is not None:
                     pt.temporal_set_clamp(True, **clamp)
+                if auto_exposure is not None:
+                    pt.set_auto_exposure(True, **auto_exposure)
             if temporal is None:
                 rgba, _ = _render_on(pt, settings, **opt)
             else:
-                _render_on(pt, settings, **{**opt, "seed": opt["seed"] + len(written), "denoise": False})  # (its draw is not the frame)
+                _render_on(pt, settings, **{**opt, "seed": opt["seed"] + len(written), "denoise": False},
+                           draw=auto_exposure is None)  # (its draw is not the frame; under auto-exposure it would adapt twice a frame)
                 if variance:
                     pt.features(8, opt["seed"])
                 pt.temporal_accumulate(read=False, **temporal)

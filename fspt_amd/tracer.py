@@ -172,6 +172,52 @@ def temporal_clamp_eval(hist, fast, sigma_scale=None, device=0):
     return out, lo, hi
 
 
+# include/fspt_tuning.h FSPT_EXPOSURE_*: conventions, not measurements (Reinhard's middle grey, UE4's percentiles)
+EXPOSURE_DEFAULTS = {"key": 0.18, "low": 0.10, "high": 0.90, "adapt_up": 1.0, "adapt_down": 1.0, "min_log2": -8.0, "max_log2": 8.0}
+
+
+def _exposure_params(params):
+    """fspt_exposure_params from keyword arguments (missing ones: EXPOSURE_DEFAULTS), validated like the library does."""
+    unknown = set(params) - set(EXPOSURE_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown auto-exposure parameters {sorted(unknown)}")
+    v = {k: float(np.float32(x)) for k, x in {**EXPOSURE_DEFAULTS, **params}.items()}
+    if not (all(np.isfinite(x) for x in v.values()) and v["key"] > 0.0 and 0.0 <= v["low"] < v["high"] <= 1.0
+            and 0.0 < v["adapt_up"] <= 1.0 and 0.0 < v["adapt_down"] <= 1.0 and v["min_log2"] <= v["max_log2"]):
+        raise ValueError("auto-exposure: need finite parameters with key > 0, 0 <= low < high <= 1, adapt_up and adapt_down in (0, 1], "
+                         "min_log2 <= max_log2")
+    return L.ExposureParams(*(v[k] for k in EXPOSURE_DEFAULTS))
+
+
+def exposure_eval(rgba, viewport=None, prev=None, device=0, **params):
+    """The two metering kernels on a host array (fspt_exposure_eval, a test hook): rgba float32 [H, W, 4], viewport (vw, vh) or
+    None = the whole image, prev = a state dict as returned (None: never metered) -> (hist uint32 [256], state dict with
+    exposure (numpy float32), valid, metered, cleared (the histogram was zero after the resolve), log2_exposure, log2_mean)."""
+    prm = _exposure_params(params)
+    rgba = np.ascontiguousarray(rgba, dtype=np.float32)
+    if rgba.ndim != 3 or rgba.shape[2] != 4:
+        raise ValueError(f"need rgba [H, W, 4], got {rgba.shape}")
+    H, W = rgba.shape[:2]
+    vw, vh = (W, H) if viewport is None else (int(viewport[0]), int(viewport[1]))
+    if not (1 <= vw <= W and 1 <= vh <= H):
+        raise ValueError(f"viewport {vw}x{vh} does not fit the image {W}x{H}")
+    st = None
+    if prev is not None:
+        st = L.ExposureState(float(prev["exposure"]), int(prev["valid"]), int(prev["metered"]), 0, float(prev["log2_exposure"]), float(prev["log2_mean"]))
+    hist = np.zeros(256, np.uint32)
+    out = L.ExposureState()
+    L.check(L.lib().fspt_exposure_eval(int(device), L.fptr(rgba), W, H, vw, vh, C.byref(prm), C.byref(st) if st is not None else None,
+                                       hist.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(out)))
+    return hist, {"exposure": np.float32(out.exposure), "valid": int(out.valid), "metered": int(out.metered), "cleared": out.reserved == 0,
+                  "log2_exposure": float(out.log2_exposure), "log2_mean": float(out.log2_mean)}
+
+
+def exposure_set_form(form):
+    """k_exposure_histogram's form, process-wide (fspt_exposure_set_form, a measurement switch): 0 = one LDS atomic per pixel
+    (shipped), 1 = same-bin lanes combined by a ballot.  The histogram is the same."""
+    L.check(L.lib().fspt_exposure_set_form(int(form)))
+
+
 def light_alias_table(weights):
     """The Vose alias table (float32 prob, uint32 alias) the light table stores for these weights (fspt_light_alias_table,
     a pure host function: no device needed)."""
@@ -820,6 +866,34 @@ class PathTracer:
         ms = C.c_float()
         L.check(L.lib().fspt_temporal_clamp_last_ms(self._t, C.byref(ms)))
         return float(ms.value)
+
+    # ---- auto-exposure (include/fspt.h fspt_target_set_auto_exposure) --------------------------------
+    def set_auto_exposure(self, on=True, **params):
+        """Auto-exposure (fspt_target_set_auto_exposure): every draw(), present(), drawDenoised() and temporal_draw() first meters
+        the buffer it draws on the GPU, and its `exposure` argument becomes a compensation of the metered value.  params: key,
+        low, high, adapt_up, adapt_down, min_log2, max_log2 (missing ones: EXPOSURE_DEFAULTS).  A call that changes only the
+        parameters keeps the adapted state; off frees it."""
+        prm = _exposure_params(params) if on else None
+        L.check(L.lib().fspt_target_set_auto_exposure(self._t, 1 if on else 0, C.byref(prm) if on else None))
+
+    def exposure(self):
+        """(exposure, log2_mean, metered) of the last metering (fspt_exposure_get): the float32 factor the draws multiply by,
+        the mean log2 luminance of the kept pixels, the pixels counted.  Blocking; joins a present."""
+        e, m, n = C.c_float(), C.c_float(), C.c_uint32()
+        L.check(L.lib().fspt_exposure_get(self._t, C.byref(e), C.byref(m), C.byref(n)))
+        return np.float32(e.value), float(m.value), int(n.value)
+
+    def exposure_reset(self):
+        """The next metering is a first one: no adaptation from the state so far (fspt_exposure_reset)."""
+        L.check(L.lib().fspt_exposure_reset(self._t))
+
+    def exposure_last_ms(self):
+        """(histogram ms, resolve ms, k_draw_auto ms) of the last metered draw, from HIP events (fspt_exposure_last_ms,
+        fspt_exposure_last_draw_ms)."""
+        ms, d = (C.c_float * 2)(), C.c_float()
+        L.check(L.lib().fspt_exposure_last_ms(self._t, ms))
+        L.check(L.lib().fspt_exposure_last_draw_ms(self._t, C.byref(d)))
+        return float(ms[0]), float(ms[1]), float(d.value)
 
     def temporal_draw(self, exposure=1.0, saturation=1.0, denoised=False):
         """draw() of the temporal result, or of the last temporal_denoise() (fspt_temporal_draw): RGBA8 [H, W, 4]."""

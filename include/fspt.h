@@ -208,8 +208,10 @@ int fspt_temporal_draw(fspt_target *t, float exposure, float saturation, int den
 int fspt_scene_motion_begin(fspt_scene *s); int fspt_scene_motion_end(fspt_scene *s);       /* snapshot (a rebuild permutes it) | drop it: static scene */
 int fspt_temporal_set_moments(fspt_target *t, int on); /* SVGF variance guidance (DESIGN 8.9; rule and defaults: fspt_tuning.h): accumulate also carries luminance moments; default off */
 int fspt_temporal_denoise_variance(fspt_target *t, const fspt_denoise_params *p, float *out); /* fspt_temporal_denoise guided by the variance estimate; sigma_color = sigma_l */
-
 int fspt_temporal_set_clamp(fspt_target *t, int on, float fast_history, float sigma_scale); /* history clamp (DESIGN 8.10; rule and defaults: fspt_tuning.h): a fast history bounds the long one; default off */
+/* Auto-exposure (DESIGN 8.11; rule and defaults: fspt_tuning.h): every drawing entry first meters the buffer it draws (a luminance histogram of the viewport, on the GPU, no host read) and its `exposure` argument becomes a compensation of the metered value. */ typedef struct fspt_exposure_params { float key, low, high, adapt_up, adapt_down, min_log2, max_log2; } fspt_exposure_params;
+int fspt_target_set_auto_exposure(fspt_target *t, int on, const fspt_exposure_params *p); /* p NULL = defaults; default off */ int fspt_exposure_reset(fspt_target *t); /* the next metering is a first one */
+int fspt_exposure_get(fspt_target *t, float *exposure, float *log2_mean, uint32_t *metered); /* blocking; joins a present */
 /* intersectScene (tracer.fs:366-404) as a stand-alone entry: n rays (origin xyz, dir xyz) -> closest hit t and triangle index (-1 = miss, t = 1e5), optionally loop-iteration and leaf-visit counts per ray.  Host pointers. */
 int fspt_intersect(fspt_scene *scene, const float *rays, uint32_t n, float *t_out, int32_t *index_out, uint32_t *steps_out, uint32_t *leaves_out);
 
@@ -225,9 +227,7 @@ typedef struct fspt_counters {
   uint64_t shades;      /* bounce-loop iterations          (tracer.fs:446)   */
   uint64_t env_lookups; /* envSample calls                 (tracer.fs:416)   */
 } fspt_counters;
-int fspt_enable_counters(fspt_target *target, int enable);
-int fspt_get_counters(fspt_target *target, fspt_counters *out);
-int fspt_counters_reset(fspt_target *target);
+int fspt_enable_counters(fspt_target *target, int enable); int fspt_get_counters(fspt_target *target, fspt_counters *out); int fspt_counters_reset(fspt_target *target);
 
 /* ------------------------------------------------------------------------
  * Scene pipeline (host side, CPU; SURVEY 8f-1/8f-2): obj_loader.js + bvh.js + the packing loops of initBVH with the

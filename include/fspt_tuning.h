@@ -240,6 +240,40 @@ int fspt_temporal_clamp_last_ms(fspt_target *t, float *ms);
  * box per channel, .w = 0 (sigma_scale = +inf: -inf / +inf and out = hist, without a launch). */
 int fspt_temporal_clamp_eval(int device, const float *hist, const float *fast, uint32_t W, uint32_t H, float sigma_scale,
                              float *out, float *lo_out, float *hi_out);
+/* Auto-exposure (fspt.h fspt_target_set_auto_exposure).  Luma: L = fma(b, 0.0722, fma(g, 0.7152, r 0.2126)) in float32 (k_draw's own).  Bin:
+ * a pixel with !(L >= 2^-16) (zero, negatives, NaN, denormals) is left out; else bin = min((float_bits(L) >> 20) - ((127 - 16) << 3), 255): 32 octaves
+ * from 2^-16 with 8 sub-bins each, piecewise-linear in log2, no log2 per pixel; +inf and everything from 2^16 up: bin 255.  The target's viewport is
+ * metered.  Resolve (one block, float64): N = the sum of the counts; N = 0 leaves the state untouched (never set: exposure 1).  Of the pixels sorted by
+ * bin the ranks [floor(low N), ceil(high N)) are kept, kept_b = the overlap of bin b's rank range with it, K = sum kept_b;
+ * v_b = (b >> 3) - 16 + log2(1 + ((b & 7) + 0.5) / 8); mean = (sum over b ascending of kept_b v_b) / K; target = log2(key) - mean; in log2 of the exposure:
+ * no valid previous state: e = target, else e = prev + (target - prev) a, a = adapt_up when the scene got brighter (target < prev), else adapt_down, both in
+ * (0, 1], 1 = instant (a host with a clock passes 1 - exp(-dt speed)); e clamped to [min_log2, max_log2]; exposure = (float)exp2(e).  A draw with the mode on
+ * multiplies its exposure argument by that float32, in float32; the rest is k_draw.  State: 1 KiB of histogram + 32 bytes, allocated on enable, freed on
+ * disable and with the target; a call that changes only the parameters keeps the adapted state.  No drawing entry gains a host synchronisation.
+ * FSPT_E_INVALID: NULL, non-finite fields, key <= 0, low / high outside 0 <= low < high <= 1, adapt_* outside (0, 1], min_log2 > max_log2; FSPT_E_STATE: a
+ * sharded target, fspt_exposure_reset / _get with the mode off.  fspt_multi_* targets are not metered.
+ * The defaults are conventions, not measurements: the key is Reinhard's middle grey, the percentiles are UE4's histogram metering; instant adaptation
+ * suits a still (render_sequence picks a slower one). */
+#define FSPT_EXPOSURE_KEY 0.18f
+#define FSPT_EXPOSURE_LOW 0.10f
+#define FSPT_EXPOSURE_HIGH 0.90f
+#define FSPT_EXPOSURE_ADAPT_UP 1.0f
+#define FSPT_EXPOSURE_ADAPT_DOWN 1.0f
+#define FSPT_EXPOSURE_MIN_LOG2 -8.0f
+#define FSPT_EXPOSURE_MAX_LOG2 8.0f
+/* The device's exposure record.  reserved: 0 on the device; fspt_exposure_eval stores the OR of the histogram's words AFTER the resolve there (0: cleared). */
+typedef struct fspt_exposure_state { float exposure; uint32_t valid, metered, reserved; double log2_exposure, log2_mean; } fspt_exposure_state;
+/* Test hook: the two production kernels on a host array - rgba W*H*4 floats, metered over x < vw, y < vh (0, 0 = the whole image); prev NULL = never
+ * metered; hist_out = the 256 counts k_exposure_histogram left (before the resolve cleared them), state_out = what the resolve wrote.  p NULL = defaults. */
+int fspt_exposure_eval(int device, const float *rgba, uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const fspt_exposure_params *p,
+                       const fspt_exposure_state *prev, uint32_t *hist_out, fspt_exposure_state *state_out);
+/* GPU ms of the last metering on this target, from HIP events: ms[0] k_exposure_histogram, ms[1] k_exposure_resolve.  Blocking. */
+int fspt_exposure_last_ms(fspt_target *t, float ms[2]);
+/* ... and of the k_draw_auto behind it: what the metering's cost is set against.  Blocking. */
+int fspt_exposure_last_draw_ms(fspt_target *t, float *ms);
+/* Measurement switch, process-wide: k_exposure_histogram's form, 0 (shipped) = one LDS atomic per pixel, 1 = the lanes that share the first active lane's
+ * bin are counted by a ballot and added once.  The histogram is the same bit for bit. */
+int fspt_exposure_set_form(int form);
 /* fspt_target_set_lights (fspt.h): FSPT_LIGHTS_EMITTERS lets each shading vertex spend its shadow ray on a
  * point of an emissive triangle (probability q = emitter_fraction, in (0, 1]; at most 0.875 with an environment map, 1
  * when the scene has none)

@@ -56,6 +56,10 @@ class ExposureState(C.Structure):
                 ("log2_exposure", C.c_double), ("log2_mean", C.c_double)]
 
 
+class BloomParams(C.Structure):
+    _fields_ = [("intensity", C.c_float), ("scatter", C.c_float), ("levels", C.c_uint32)]
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("target_rel_mse", C.c_double), ("max_ticks", C.c_uint32), ("min_ticks", C.c_uint32), ("round_ticks", C.c_uint32)]
 
@@ -170,6 +174,13 @@ SIGNATURES = {
     "fspt_exposure_set_form": (C.c_int, [C.c_int]),
     "fspt_exposure_eval": (C.c_int, [C.c_int, _F, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ExposureParams),
                                      C.POINTER(ExposureState), _U32, C.POINTER(ExposureState)]),
+    "fspt_target_set_bloom": (C.c_int, [_VP, C.c_int, C.POINTER(BloomParams)]),
+    "fspt_target_get_bloom": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(BloomParams)]),
+    "fspt_bloom_eval": (C.c_int, [C.c_int, _F, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(BloomParams), _U32, _F, _F, _F, _F]),
+    "fspt_bloom_texels": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, _U32]),
+    "fspt_bloom_set_form": (C.c_int, [C.c_int]),
+    "fspt_bloom_set_tail_texels": (C.c_int, [C.c_uint32]),
+    "fspt_bloom_last_ms": (C.c_int, [_VP, _F]),
     "fspt_scene_motion_begin": (C.c_int, [_VP]),
     "fspt_scene_motion_end": (C.c_int, [_VP]),
     "fspt_intersect": (C.c_int, [_VP, _F, C.c_uint32, _F, C.POINTER(C.c_int32), _U32, _U32]),

@@ -781,6 +781,8 @@ int fspt_target_destroy(fspt_target *t) {
   for (hipEvent_t ev : t->cl_ev) if (ev) hipEventDestroy(ev);
   hipFree(t->ax_hist);
   for (hipEvent_t ev : t->ax_ev) if (ev) hipEventDestroy(ev);
+  hipFree(t->bl_pyr);
+  for (hipEvent_t ev : t->bl_ev) if (ev) hipEventDestroy(ev);
   hipFree(t->ad_snap); hipFree(t->ad_list[0]); hipFree(t->ad_list[1]); hipFree(t->ad_count); hipFree(t->ad_err);
   {
     fspt_target::WfLane &ln = t->wf;
@@ -1331,16 +1333,48 @@ int fspt_read_radiance(fspt_target *t, float *out) {
   return FSPT_OK;
 }
 
-// k_draw of `src` on `st`.  With auto-exposure on (DESIGN 8.11) the buffer is metered first, on the same stream - histogram,
-// resolve - and k_draw_auto multiplies the caller's exposure by the value the resolve left in device memory: no host read.
-static hipError_t draw_launch(fspt_target *t, const float4 *src, float exposure, float saturation, int denoise, float max_sigma,
-                              float scale, uint32_t *out, hipStream_t st) {
-  if (!t->ax_on) return fspt::launch_draw(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, st);
+// Auto-exposure's metering of `src` on `st`: histogram, resolve, the events around them.
+static hipError_t draw_meter(fspt_target *t, const float4 *src, hipStream_t st) {
   hipError_t e = hipEventRecord(t->ax_ev[0], st);
   if (e == hipSuccess) e = fspt::launch_exposure_histogram(src, t->W, t->vw, t->vh, t->ax_hist, fspt::g_exposure_form, st);
   if (e == hipSuccess) e = hipEventRecord(t->ax_ev[1], st);
   if (e == hipSuccess) e = fspt::launch_exposure_resolve(t->ax_hist, t->ax_state, t->ax_p, st);
   if (e == hipSuccess) e = hipEventRecord(t->ax_ev[2], st);
+  return e;
+}
+// The draw with bloom on: after the metering when that is on (it meters the source buffer), the pyramid chain on
+// the same stream - down, tail or not, up, all into t->bl_pyr - and k_draw_bloom, which mixes up(U_1) into the texel in front of
+// the exposure.  n = 0 (a viewport one texel wide or high): the plain draw.  No host read, no synchronisation.
+static hipError_t draw_launch_bloom(fspt_target *t, const float4 *src, float exposure, float saturation, int denoise, float max_sigma,
+                                    float scale, uint32_t *out, hipStream_t st) {
+  hipError_t e = hipSuccess;
+  if (t->ax_on) {
+    if ((e = draw_meter(t, src, st)) != hipSuccess) return e;
+    t->ax_timed = true;
+  }
+  const fspt::BloomPlan q = fspt::bloom_plan(t->vw, t->vh, t->bl_p.levels, fspt::g_bloom_form, fspt::g_bloom_tail_texels);
+  t->bl_timed = false;
+  if (q.n == 0) {
+    e = t->ax_on ? fspt::launch_draw_auto(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, t->ax_state, st)
+                 : fspt::launch_draw(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, st);
+  } else {
+    e = fspt::launch_bloom_chain(src, t->W, q, t->bl_p.scatter, t->bl_pyr, t->bl_ev, nullptr, nullptr, st);
+    const fspt::BloomDraw bl{t->bl_pyr + q.off[1], q.w[1], q.h[1], t->vw, t->vh, t->bl_p.intensity};
+    if (e == hipSuccess) e = fspt::launch_draw_bloom(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, t->ax_on ? t->ax_state : nullptr, bl, st);
+    if (e == hipSuccess) e = hipEventRecord(t->bl_ev[4], st);
+    if (e == hipSuccess) t->bl_timed = true;
+  }
+  if (e == hipSuccess && t->ax_on) e = hipEventRecord(t->ax_ev[3], st);
+  return e;
+}
+
+// k_draw of `src` on `st`.  With auto-exposure on (DESIGN 8.11) the buffer is metered first, on the same stream - histogram,
+// resolve - and k_draw_auto multiplies the caller's exposure by the value the resolve left in device memory: no host read.
+static hipError_t draw_launch(fspt_target *t, const float4 *src, float exposure, float saturation, int denoise, float max_sigma,
+                              float scale, uint32_t *out, hipStream_t st) {
+  if (t->bl_on) return draw_launch_bloom(t, src, exposure, saturation, denoise, max_sigma, scale, out, st);
+  if (!t->ax_on) return fspt::launch_draw(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, st);
+  hipError_t e = draw_meter(t, src, st);
   if (e != hipSuccess) return e;
   t->ax_timed = true;
   e = fspt::launch_draw_auto(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, t->ax_state, st);
@@ -2343,6 +2377,119 @@ int fspt_exposure_eval(int device, const float *rgba, uint32_t W, uint32_t H, ui
   if (e == hipSuccess) { uint32_t any = 0; for (uint32_t c : left) any |= c; state_out->reserved = any; }
   hipFree(d);
   if (e != hipSuccess) { fspt_set_error("fspt_exposure_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
+  return FSPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// bloom (k_bloom_down / k_bloom_up / k_bloom_tail / k_draw_bloom)
+// ---------------------------------------------------------------------------
+static int bl_check_params(const fspt_bloom_params *p, fspt::BloomP &q, const char *fn) {
+  static const fspt_bloom_params dflt = {FSPT_BLOOM_INTENSITY, FSPT_BLOOM_SCATTER, FSPT_BLOOM_LEVELS};
+  if (!p) p = &dflt;
+  if (!(std::isfinite(p->intensity) && std::isfinite(p->scatter) && p->intensity >= 0.0f && p->intensity <= 1.0f && p->scatter >= 0.0f &&
+        p->scatter <= 1.0f && p->levels >= 1u && p->levels <= (uint32_t)FSPT_BLOOM_MAX_LEVELS)) {
+    fspt_set_error("%s: need finite intensity and scatter in [0, 1] and levels in [1, %d]", fn, FSPT_BLOOM_MAX_LEVELS);
+    return FSPT_E_INVALID;
+  }
+  q = fspt::BloomP{p->intensity, p->scatter, p->levels};
+  return FSPT_OK;
+}
+static_assert(FSPT_BLOOM_MAX_LEVELS == fspt::BLOOM_MAX_LEVELS && FSPT_BLOOM_TAIL_TEXELS == fspt::BLOOM_TAIL_TEXELS, "fspt_tuning.h names the device's constants");
+
+int fspt_bloom_set_form(int form) {
+  if (form != 0 && form != 1) { fspt_set_error("fspt_bloom_set_form: form must be 0 or 1"); return FSPT_E_INVALID; }
+  fspt::g_bloom_form = form;
+  return FSPT_OK;
+}
+
+int fspt_bloom_set_tail_texels(uint32_t n) {
+  fspt::g_bloom_tail_texels = n ? n : fspt::BLOOM_TAIL_TEXELS;
+  return FSPT_OK;
+}
+
+uint64_t fspt_bloom_texels(uint32_t vw, uint32_t vh, uint32_t levels, uint32_t *n_out) {
+  if (vw == 0 || vh == 0) { if (n_out) *n_out = 0; return 0; }
+  const fspt::BloomPlan q = fspt::bloom_plan(vw, vh, levels, 0, 0);
+  if (n_out) *n_out = q.n;
+  return q.texels;
+}
+
+int fspt_target_set_bloom(fspt_target *t, int on, const fspt_bloom_params *p) {
+  if (!t) { fspt_set_error("fspt_target_set_bloom: NULL argument"); return FSPT_E_INVALID; }
+  fspt::BloomP q{};
+  int rc;
+  if (on && (rc = bl_check_params(p, q, "fspt_target_set_bloom"))) return rc;
+  if ((rc = dn_enter(t, true, "fspt_target_set_bloom"))) return rc;
+  if (!on) {
+    HIP_TRY(hipStreamSynchronize(t->stream)); // (dn_enter joined a present: nothing reads the pyramid any more)
+    hipFree(t->bl_pyr);
+    t->bl_pyr = nullptr;
+    t->bl_on = t->bl_timed = false;
+    return FSPT_OK;
+  }
+  if (t->n_shards > 1) { fspt_set_error("fspt_target_set_bloom: sharded target"); return FSPT_E_STATE; }
+  t->bl_p = q; // (a change of the parameters alone keeps the allocation: it is sized for W x H at the most levels)
+  if (t->bl_on) return FSPT_OK;
+  const size_t texels = fspt::bloom_plan(t->W, t->H, fspt::BLOOM_MAX_LEVELS, 0, 0).texels;
+  if (!t->bl_pyr) HIP_TRY(hipMalloc((void **)&t->bl_pyr, (texels ? texels : 1) * sizeof(float4)));
+  for (hipEvent_t &ev : t->bl_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
+  t->bl_on = true; t->bl_timed = false;
+  return FSPT_OK;
+}
+
+int fspt_target_get_bloom(fspt_target *t, int *on, fspt_bloom_params *p) {
+  if (!t || !on || !p) { fspt_set_error("fspt_target_get_bloom: NULL argument"); return FSPT_E_INVALID; }
+  *on = t->bl_on ? 1 : 0;
+  if (t->bl_on) *p = fspt_bloom_params{t->bl_p.intensity, t->bl_p.scatter, t->bl_p.levels};
+  else *p = fspt_bloom_params{FSPT_BLOOM_INTENSITY, FSPT_BLOOM_SCATTER, FSPT_BLOOM_LEVELS};
+  return FSPT_OK;
+}
+
+int fspt_bloom_last_ms(fspt_target *t, float ms[4]) {
+  if (!t || !ms) { fspt_set_error("fspt_bloom_last_ms: NULL argument"); return FSPT_E_INVALID; }
+  FLUSH_OR_RETURN(t);
+  if (!t->bl_on || !t->bl_timed) { fspt_set_error("fspt_bloom_last_ms: no bloomed draw yet"); return FSPT_E_STATE; }
+  HIP_TRY(hipSetDevice(t->scene->device));
+  HIP_TRY(hipEventSynchronize(t->bl_ev[4]));
+  for (int k = 0; k < 4; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], t->bl_ev[k], t->bl_ev[k + 1]));
+  return FSPT_OK;
+}
+
+int fspt_bloom_eval(int device, const float *rgba, uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const fspt_bloom_params *p, uint32_t *n_out,
+                    float *down_out, float *up_out, float *bloom_out, float *mix_out) {
+  if (!rgba) { fspt_set_error("fspt_bloom_eval: NULL argument"); return FSPT_E_INVALID; }
+  fspt::BloomP bp{};
+  int rc = bl_check_params(p, bp, "fspt_bloom_eval");
+  if (rc) return rc;
+  if (vw == 0 && vh == 0) { vw = W; vh = H; } // (as fspt_target_set_viewport: 0, 0 = the whole image)
+  if (W == 0 || H == 0 || vw == 0 || vh == 0 || vw > W || vh > H || (uint64_t)W * H > 0x7FFFFFFFull) {
+    fspt_set_error("fspt_bloom_eval: need 1 <= vw <= W, 1 <= vh <= H and fewer than 2^31 pixels"); return FSPT_E_INVALID;
+  }
+  if ((rc = check_device(device))) return rc;
+  HIP_TRY(hipSetDevice(device));
+  const fspt::BloomPlan q = fspt::bloom_plan(vw, vh, bp.levels, fspt::g_bloom_form, fspt::g_bloom_tail_texels);
+  if (n_out) *n_out = q.n;
+  const size_t px = (size_t)W * H, vpx = (size_t)vw * vh;
+  if (q.n == 0) { // the plain draw: nothing is built, the draw multiplies the source by the exposure
+    if (mix_out) memcpy(mix_out, rgba, px * 16);
+    if (bloom_out) for (uint32_t y = 0; y < vh; ++y) memcpy(bloom_out + (size_t)y * vw * 4, rgba + (size_t)y * W * 4, (size_t)vw * 16);
+    return FSPT_OK;
+  }
+  // one allocation: image | pyramid (U in the end) | the D levels as the down chain left them | B | c'
+  float4 *d = nullptr;
+  hipError_t e = hipMalloc((void **)&d, (px + 2 * q.texels + vpx + px) * sizeof(float4));
+  float4 *pyr = d + px, *snap = pyr + q.texels, *B = snap + q.texels, *mix = B + vpx;
+  if (e == hipSuccess) e = hipMemcpy(d, rgba, px * 16, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = fspt::launch_bloom_chain(d, W, q, bp.scatter, pyr, nullptr, snap, pyr, nullptr);
+  const fspt::BloomDraw bl{pyr + q.off[1], q.w[1], q.h[1], vw, vh, bp.intensity};
+  if (e == hipSuccess) e = fspt::launch_bloom_mix(d, W, H, bl, B, mix, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess && down_out) e = hipMemcpy(down_out, snap, q.texels * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && up_out) e = hipMemcpy(up_out, pyr, q.texels * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && bloom_out) e = hipMemcpy(bloom_out, B, vpx * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && mix_out) e = hipMemcpy(mix_out, mix, px * 16, hipMemcpyDeviceToHost);
+  hipFree(d);
+  if (e != hipSuccess) { fspt_set_error("fspt_bloom_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
   return FSPT_OK;
 }
 

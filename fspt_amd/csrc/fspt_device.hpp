@@ -470,6 +470,30 @@ hipError_t launch_exposure_histogram(const float4 *src, uint32_t W, uint32_t vw,
 hipError_t launch_exposure_resolve(uint32_t *hist, ExposureState *state, const ExposureP &p, hipStream_t stream); // (zeroes hist)
 hipError_t launch_draw_auto(const float4 *acc, uint32_t W, uint32_t H, float exposure, float saturation, int denoise,
                             float max_sigma, float scale, uint32_t *out, const ExposureState *state, hipStream_t stream);
+// bloom (fspt_target_set_bloom; the rule: fspt_tuning.h)
+constexpr uint32_t BLOOM_MAX_LEVELS = 8;          // FSPT_BLOOM_MAX_LEVELS
+constexpr size_t BLOOM_TAIL_LDS_MAX = 160 * 1024; // what one workgroup may hold on gfx950
+constexpr int BLOOM_FORM = 0;                     // shipped: 0 = one launch per level, 1 = the fused tail (cost table)
+constexpr uint32_t BLOOM_TAIL_TEXELS = 2048;      // FSPT_BLOOM_TAIL_TEXELS: 60 x 34 of 1920 x 1080 and below, 30 KiB of LDS
+struct BloomP { float intensity, scatter; uint32_t levels; }; // fspt_bloom_params, validated
+struct BloomDraw { const float4 *u1; uint32_t w1, h1, vw, vh; float intensity; }; // what k_draw_bloom needs: U_1, its size, the viewport
+struct BloomTailP { float4 *lvl; uint32_t w, h, below; float scatter; float4 *dbg_down, *dbg_up; };
+struct BloomPlan {          // the pyramid of a vw x vh viewport
+  uint32_t n;               // levels below level 0: min(levels, the first level with a side of 1); 0 = the plain draw
+  uint32_t w[BLOOM_MAX_LEVELS + 1], h[BLOOM_MAX_LEVELS + 1];
+  size_t off[BLOOM_MAX_LEVELS + 2]; // level k's first texel in the pyramid, k >= 1
+  size_t texels;            // of levels 1 .. n
+  uint32_t tail;            // the level k_bloom_tail starts at, 0 = no tail
+  size_t tail_lds;          // its LDS bytes
+};
+extern int g_bloom_form;
+extern uint32_t g_bloom_tail_texels;
+BloomPlan bloom_plan(uint32_t vw, uint32_t vh, uint32_t levels, int form, uint32_t tail_texels);
+hipError_t launch_bloom_chain(const float4 *src, uint32_t pitch, const BloomPlan &q, float scatter, float4 *pyr, hipEvent_t *ev,
+                              float4 *down_snapshot, float4 *dbg_up, hipStream_t stream);
+hipError_t launch_bloom_mix(const float4 *src, uint32_t W, uint32_t H, const BloomDraw &bl, float4 *bloom_out, float4 *mix_out, hipStream_t stream);
+hipError_t launch_draw_bloom(const float4 *acc, uint32_t W, uint32_t H, float exposure, float saturation, int denoise, float max_sigma,
+                             float scale, uint32_t *out, const ExposureState *state, const BloomDraw &bl, hipStream_t stream);
 hipError_t launch_math(int op, const float *a, const float *b, uint32_t n, float *out, hipStream_t stream);
 
 } // namespace fspt

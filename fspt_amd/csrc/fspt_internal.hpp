@@ -331,6 +331,12 @@ struct fspt_target {
   fspt::ExposureP ax_p{};
   hipEvent_t ax_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the two kernels of the last metering and its k_draw_auto
   bool ax_timed = false;
+  // bloom (fspt_target_set_bloom): the pyramid, allocated on enable for W x H at 8 levels, read-modify-write state of every bloomed draw
+  float4 *bl_pyr = nullptr;
+  bool bl_on = false;
+  fspt::BloomP bl_p{};
+  hipEvent_t bl_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // down chain | tail | up chain | draw of the last bloomed draw
+  bool bl_timed = false;
 };
 
 static const uint32_t WORK_RING = 4096;

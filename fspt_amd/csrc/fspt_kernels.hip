@@ -2427,8 +2427,31 @@ FM_DEV float rrt_odt(float v) {
   float b = fma_(v, fma_(0.983729f, v, 0.4329510f), 0.238081f);
   return a / b;
 }
+// Bloom, the two pieces the draw and the pyramid kernels share.  s(v) = v >= 0 ? min(v, 1024) : 0: NaN and
+// negatives become 0, +inf the path kernels' own per-sample clamp.  up(U)(x, y): the 2 x 2 tent over the coarser level U
+// (w x h), 3/4 on the texel under (x, y) and 1/4 on its neighbour towards (x, y)'s side, clamped; horizontal first:
+// fma(3/4, fma(3/4, U00, U10 / 4), fma(3/4, U01, U11 / 4) / 4).  The weights are dyadic: the three fma round, nothing else.
+constexpr float BLOOM_CLAMP = 1024.0f;
+FM_DEV float bloom_s(float v) { return v >= 0.0f ? (v < BLOOM_CLAMP ? v : BLOOM_CLAMP) : 0.0f; }
+FM_DEV V3 bloom_s3(V3 c) { return v3(bloom_s(c.x), bloom_s(c.y), bloom_s(c.z)); }
+FM_DEV float bloom_tent(float u00, float u10, float u01, float u11) {
+  return fma_(0.75f, fma_(0.75f, u00, 0.25f * u10), 0.25f * fma_(0.75f, u01, 0.25f * u11));
+}
+FM_DEV V3 bloom_up(const float4 *U, uint32_t w, uint32_t h, uint32_t x, uint32_t y) {
+  const uint32_t cx0 = x >> 1, cy0 = y >> 1;
+  const uint32_t cx1 = (x & 1u) ? (cx0 + 1u < w ? cx0 + 1u : w - 1u) : (cx0 ? cx0 - 1u : 0u);
+  const uint32_t cy1 = (y & 1u) ? (cy0 + 1u < h ? cy0 + 1u : h - 1u) : (cy0 ? cy0 - 1u : 0u);
+  const float4 a = U[(size_t)cy0 * w + cx0], b = U[(size_t)cy0 * w + cx1], c = U[(size_t)cy1 * w + cx0], d = U[(size_t)cy1 * w + cx1];
+  return v3(bloom_tent(a.x, b.x, c.x, d.x), bloom_tent(a.y, b.y, c.y, d.y), bloom_tent(a.z, b.z, c.z, d.z));
+}
+// what the draw multiplies by the exposure: c' = fma(intensity, B - s(c), s(c)), B = up(U_1) at the source texel (x, y)
+FM_DEV V3 bloom_mix(V3 c, V3 B, float intensity) {
+  const V3 c0 = bloom_s3(c);
+  return v3(fma_(intensity, B.x - c0.x, c0.x), fma_(intensity, B.y - c0.y, c0.y), fma_(intensity, B.z - c0.z, c0.z));
+}
+template <bool BLOOM>
 FM_DEV void draw_pixel(const float4 *acc, uint32_t W, uint32_t H, float exposure, float saturation, int denoise, float maxSigma,
-                       float scale, uint32_t *out) {
+                       float scale, uint32_t *out, const BloomDraw &bl) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= W * H) return;
   // ivec2(gl_FragCoord * scale) (draw.fs:59,87): the reference draws with scale 0.25 while the camera moves
@@ -2450,10 +2473,14 @@ FM_DEV void draw_pixel(const float4 *acc, uint32_t W, uint32_t H, float exposure
     float variance = fma_(-mean, mean, sq / 24.0f);
     float sigma = sqrt_(variance);
     if (abs_(middleLuma - mean) > maxSigma * sigma) middle = middle * (mean / middleLuma);
-    c = middle * exposure;
+    c = middle;
   } else {
-    c = draw_fetch(acc, (int)W, (int)H, x, y) * exposure;
+    c = draw_fetch(acc, (int)W, (int)H, x, y);
   }
+  if (BLOOM) { // (a source texel outside the viewport is drawn plain)
+    if (x >= 0 && y >= 0 && (uint32_t)x < bl.vw && (uint32_t)y < bl.vh) c = bloom_mix(c, bloom_up(bl.u1, bl.w1, bl.h1, (uint32_t)x, (uint32_t)y), bl.intensity);
+  }
+  c = c * exposure;
   V3 a = v3(dot(c, v3(0.59719f, 0.35458f, 0.04823f)), dot(c, v3(0.07600f, 0.90834f, 0.01566f)),
             dot(c, v3(0.02840f, 0.13383f, 0.83777f)));
   a = v3(rrt_odt(a.x), rrt_odt(a.y), rrt_odt(a.z));
@@ -2472,14 +2499,172 @@ FM_DEV void draw_pixel(const float4 *acc, uint32_t W, uint32_t H, float exposure
 __global__ __launch_bounds__(BLOCK_THREADS) void k_draw(const float4 *acc, uint32_t W, uint32_t H, float exposure,
                                                        float saturation, int denoise, float maxSigma, float scale,
                                                        uint32_t *out) {
-  draw_pixel(acc, W, H, exposure, saturation, denoise, maxSigma, scale, out);
+  draw_pixel<false>(acc, W, H, exposure, saturation, denoise, maxSigma, scale, out, BloomDraw{});
 }
 // Auto-exposure: the caller's exposure becomes a compensation of the metered one, read from device memory
 // (k_exposure_resolve wrote it on this stream, or on one ordered before it); everything after the product is k_draw.
 __global__ __launch_bounds__(BLOCK_THREADS) void k_draw_auto(const float4 *acc, uint32_t W, uint32_t H, float exposure,
                                                             float saturation, int denoise, float maxSigma, float scale,
                                                             uint32_t *out, const ExposureState *state) {
-  draw_pixel(acc, W, H, exposure * state->exposure, saturation, denoise, maxSigma, scale, out);
+  draw_pixel<false>(acc, W, H, exposure * state->exposure, saturation, denoise, maxSigma, scale, out, BloomDraw{});
+}
+// Bloom (the rule in full: fspt_tuning.h).  k_draw_bloom is draw_pixel with the mix in front of the exposure:
+// c' = fma(intensity, up(U_1)(x, y) - s(c), s(c)) at the source texel, c the texel or the firefly-filtered middle.  AUTO reads
+// the exposure record as k_draw_auto does.
+template <bool AUTO>
+__global__ __launch_bounds__(BLOCK_THREADS) void k_draw_bloom(const float4 *acc, uint32_t W, uint32_t H, float exposure,
+                                                             float saturation, int denoise, float maxSigma, float scale,
+                                                             uint32_t *out, const ExposureState *state, const BloomDraw bl) {
+  draw_pixel<true>(acc, W, H, AUTO ? exposure * state->exposure : exposure, saturation, denoise, maxSigma, scale, out, bl);
+}
+// B and c' of every viewport texel with denoise = 0, through the draw's own device functions (fspt_bloom_eval, a test hook):
+// bloom_out is vw x vh, mix_out W x H (outside the viewport: the source, as the draw draws it plain); .w = the source's
+__global__ __launch_bounds__(BLOCK_THREADS) void k_bloom_mix(const float4 *src, uint32_t W, uint32_t H, const BloomDraw bl,
+                                                            float4 *bloom_out, float4 *mix_out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= W * H) return;
+  const uint32_t x = i % W, y = i / W;
+  const float4 p = src[i];
+  if (x >= bl.vw || y >= bl.vh) { mix_out[i] = p; return; }
+  const V3 B = bloom_up(bl.u1, bl.w1, bl.h1, x, y);
+  const V3 m = bloom_mix(v3(p.x, p.y, p.z), B, bl.intensity);
+  bloom_out[(size_t)y * bl.vw + x] = make_float4(B.x, B.y, B.z, p.w);
+  mix_out[i] = make_float4(m.x, m.y, m.z, p.w);
+}
+
+// One 1-D pass of the down filter, w = (1, 3, 3, 1) / 8: ((a1 + a2) 3 + (a0 + a3)) / 8 - three additions and the product by 3
+// round (3 m is m + 2 m rounded once), the division by 8 is exact.
+FM_DEV float bloom_down4(float a0, float a1, float a2, float a3) {
+  const float m = a1 + a2;
+  return (3.0f * m + (a0 + a3)) * 0.125f;
+}
+// D_{k+1} from S_k (ws x hs texels at a pitch of `pitch`), separable, horizontal first.  A workgroup makes a 32 x 8 tile of
+// outputs: it stages the 66 x 18 source texels the tile needs (coordinates clamped to the level: every load is in bounds) with
+// 16-byte loads into three planes of LDS, FIRST sanitising them; the horizontal pass of the 18 rows goes into LDS, the vertical
+// pass out of it.  Without the staging a source texel would be fetched up to four times through the caches.  LDS: a plane's
+// rows are 66 floats (even, so a row starts 8-byte aligned); in the horizontal pass lane x reads columns 2 x .. 2 x + 3 as two
+// 8-byte reads - 32 lanes at a stride of 8 bytes cover the 64 banks once, and the wave's other half reads another row in its
+// own group; in the vertical pass lane x reads column x: consecutive dwords.
+constexpr uint32_t BLOOM_TX = 32, BLOOM_TY = 8, BLOOM_SX = 2 * BLOOM_TX + 2, BLOOM_SY = 2 * BLOOM_TY + 2;
+static_assert(BLOOM_TX * BLOOM_TY == BLOCK_THREADS && BLOOM_SX % 2 == 0, "one output per thread; 8-byte aligned rows");
+template <bool FIRST>
+__global__ __launch_bounds__(BLOCK_THREADS) void k_bloom_down(const float4 *src, uint32_t pitch, uint32_t ws, uint32_t hs, float4 *dst,
+                                                             uint32_t wd, uint32_t hd) {
+  __shared__ __attribute__((aligned(16))) float s[3][BLOOM_SY][BLOOM_SX];
+  __shared__ float t[3][BLOOM_SY][BLOOM_TX];
+  const int x0 = 2 * (int)(blockIdx.x * BLOOM_TX) - 1, y0 = 2 * (int)(blockIdx.y * BLOOM_TY) - 1;
+  for (uint32_t k = threadIdx.x; k < BLOOM_SX * BLOOM_SY; k += BLOCK_THREADS) {
+    const uint32_t i = k % BLOOM_SX, j = k / BLOOM_SX;
+    int sx = x0 + (int)i, sy = y0 + (int)j;
+    sx = sx < 0 ? 0 : (sx > (int)ws - 1 ? (int)ws - 1 : sx);
+    sy = sy < 0 ? 0 : (sy > (int)hs - 1 ? (int)hs - 1 : sy);
+    const float4 p = src[(size_t)sy * pitch + sx];
+    s[0][j][i] = FIRST ? bloom_s(p.x) : p.x;
+    s[1][j][i] = FIRST ? bloom_s(p.y) : p.y;
+    s[2][j][i] = FIRST ? bloom_s(p.z) : p.z;
+  }
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < BLOOM_TX * BLOOM_SY; k += BLOCK_THREADS) {
+    const uint32_t x = k % BLOOM_TX, j = k / BLOOM_TX;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float2 a = *(const float2 *)&s[c][j][2 * x], b = *(const float2 *)&s[c][j][2 * x + 2];
+      t[c][j][x] = bloom_down4(a.x, a.y, b.x, b.y);
+    }
+  }
+  __syncthreads();
+  const uint32_t tx = threadIdx.x % BLOOM_TX, ty = threadIdx.x / BLOOM_TX;
+  const uint32_t x = blockIdx.x * BLOOM_TX + tx, y = blockIdx.y * BLOOM_TY + ty;
+  if (x >= wd || y >= hd) return;
+  float o[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) o[c] = bloom_down4(t[c][2 * ty][tx], t[c][2 * ty + 1][tx], t[c][2 * ty + 2][tx], t[c][2 * ty + 3][tx]);
+  dst[(size_t)y * wd + x] = make_float4(o[0], o[1], o[2], 0.0f);
+}
+
+// U_k = fma(scatter, up(U_{k+1}) - D_k, D_k), one thread per texel, in place over D_k (a thread reads only its own D_k texel)
+__global__ __launch_bounds__(BLOCK_THREADS) void k_bloom_up(float4 *dk, uint32_t w, uint32_t h, const float4 *up, uint32_t wu, uint32_t hu,
+                                                           float scatter) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= w * h) return;
+  const V3 u = bloom_up(up, wu, hu, i % w, i / w);
+  const float4 d = dk[i];
+  dk[i] = make_float4(fma_(scatter, u.x - d.x, d.x), fma_(scatter, u.y - d.y, d.y), fma_(scatter, u.z - d.z, d.z), 0.0f);
+}
+
+// The pyramid's small end in one workgroup: level k (w x h, in global memory) is loaded into LDS, every lower level is built
+// there, combined back up in place, and U_k is written over D_k.  2 (n - k) launches become one.  LDS holds the levels one
+// behind the other, three floats a texel (a stride of three dwords: no bank conflict); the host sizes it (bloom_plan) and
+// starts the tail only where it fits.  The operations and their order are the per-level kernels': a texel's four horizontal
+// passes are recomputed per output instead of stored, which gives the same bits.  dbg_down / dbg_up (NULL in a draw): where
+// D_j and U_j of the levels below k go, one behind the other, for fspt_bloom_eval.
+constexpr uint32_t BLOOM_TAIL_THREADS = 1024;
+FM_DEV uint32_t bloom_cl(int v, uint32_t n) { return v < 0 ? 0u : ((uint32_t)v > n - 1u ? n - 1u : (uint32_t)v); }
+__global__ __launch_bounds__(BLOOM_TAIL_THREADS) void k_bloom_tail(const BloomTailP p) {
+  extern __shared__ float lds[];
+  const uint32_t n0 = p.w * p.h;
+  for (uint32_t i = threadIdx.x; i < n0; i += BLOOM_TAIL_THREADS) {
+    const float4 v = p.lvl[i];
+    lds[3 * i] = v.x; lds[3 * i + 1] = v.y; lds[3 * i + 2] = v.z;
+  }
+  __syncthreads();
+  // down: level j at `at` (ws x hs) -> level j + 1 behind it
+  uint32_t at = 0, ws = p.w, hs = p.h, dbg = 0;
+  for (uint32_t j = 0; j < p.below; ++j) {
+    const uint32_t wd = (ws + 1u) >> 1, hd = (hs + 1u) >> 1, to = at + ws * hs;
+    const float *S = lds + 3 * (size_t)at;
+    for (uint32_t i = threadIdx.x; i < wd * hd; i += BLOOM_TAIL_THREADS) {
+      const uint32_t x = i % wd, y = i / wd;
+      uint32_t cx[4], cy[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { cx[q] = bloom_cl(2 * (int)x - 1 + q, ws); cy[q] = bloom_cl(2 * (int)y - 1 + q, hs); }
+      float o[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        float r[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float *row = S + 3 * (size_t)(cy[q] * ws) + c;
+          r[q] = bloom_down4(row[3 * cx[0]], row[3 * cx[1]], row[3 * cx[2]], row[3 * cx[3]]);
+        }
+        o[c] = bloom_down4(r[0], r[1], r[2], r[3]);
+        lds[3 * (size_t)(to + i) + c] = o[c];
+      }
+      if (p.dbg_down) p.dbg_down[dbg + i] = make_float4(o[0], o[1], o[2], 0.0f);
+    }
+    __syncthreads();
+    dbg += wd * hd;
+    at = to; ws = wd; hs = hd;
+  }
+  // U of the last level is its D
+  if (p.dbg_up && p.below)
+    for (uint32_t i = threadIdx.x; i < ws * hs; i += BLOOM_TAIL_THREADS)
+      p.dbg_up[dbg - ws * hs + i] = make_float4(lds[3 * (size_t)(at + i)], lds[3 * (size_t)(at + i) + 1], lds[3 * (size_t)(at + i) + 2], 0.0f);
+  // up: level j + 1 at `at` (ws x hs) -> level j in front of it, whose size comes from walking down from the top again
+  for (uint32_t j = p.below; j-- > 0;) {
+    uint32_t wf = p.w, hf = p.h, af = 0, df = 0; // level j of the tail: size, LDS offset, debug offset of its END
+    for (uint32_t q = 0; q < j; ++q) { af += wf * hf; wf = (wf + 1u) >> 1; hf = (hf + 1u) >> 1; df += wf * hf; }
+    const float *U = lds + 3 * (size_t)at;
+    for (uint32_t i = threadIdx.x; i < wf * hf; i += BLOOM_TAIL_THREADS) {
+      const uint32_t x = i % wf, y = i / wf;
+      const uint32_t cx0 = x >> 1, cy0 = y >> 1;
+      const uint32_t cx1 = (x & 1u) ? (cx0 + 1u < ws ? cx0 + 1u : ws - 1u) : (cx0 ? cx0 - 1u : 0u);
+      const uint32_t cy1 = (y & 1u) ? (cy0 + 1u < hs ? cy0 + 1u : hs - 1u) : (cy0 ? cy0 - 1u : 0u);
+      float o[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float u = bloom_tent(U[3 * (size_t)(cy0 * ws + cx0) + c], U[3 * (size_t)(cy0 * ws + cx1) + c], U[3 * (size_t)(cy1 * ws + cx0) + c],
+                                   U[3 * (size_t)(cy1 * ws + cx1) + c]);
+        const float d = lds[3 * (size_t)(af + i) + c];
+        o[c] = fma_(p.scatter, u - d, d);
+        lds[3 * (size_t)(af + i) + c] = o[c];
+      }
+      if (j == 0) p.lvl[i] = make_float4(o[0], o[1], o[2], 0.0f);
+      else if (p.dbg_up) p.dbg_up[df - wf * hf + i] = make_float4(o[0], o[1], o[2], 0.0f);
+    }
+    __syncthreads();
+    at = af; ws = wf; hs = hf;
+  }
 }
 
 // The luminance histogram of the viewport: 256 bins, piecewise-linear in log2 and taken from the float's bits -
@@ -3383,6 +3568,90 @@ hipError_t launch_draw_auto(const float4 *acc, uint32_t W, uint32_t H, float exp
   uint32_t n = W * H;
   hipLaunchKernelGGL(k_draw_auto, dim3((n + BLOCK_THREADS - 1) / BLOCK_THREADS), dim3(BLOCK_THREADS), 0, stream, acc, W, H,
                      exposure, saturation, denoise, max_sigma, scale, out, state);
+  return hipGetLastError();
+}
+
+hipError_t launch_draw_bloom(const float4 *acc, uint32_t W, uint32_t H, float exposure, float saturation, int denoise, float max_sigma,
+                             float scale, uint32_t *out, const ExposureState *state, const BloomDraw &bl, hipStream_t stream) {
+  const dim3 grid((W * H + BLOCK_THREADS - 1) / BLOCK_THREADS), block(BLOCK_THREADS);
+  if (state) hipLaunchKernelGGL(k_draw_bloom<true>, grid, block, 0, stream, acc, W, H, exposure, saturation, denoise, max_sigma, scale, out, state, bl);
+  else hipLaunchKernelGGL(k_draw_bloom<false>, grid, block, 0, stream, acc, W, H, exposure, saturation, denoise, max_sigma, scale, out, state, bl);
+  return hipGetLastError();
+}
+
+// ---- bloom ----
+int g_bloom_form = BLOOM_FORM;                    // the shipped form, or fspt_bloom_set_form's
+uint32_t g_bloom_tail_texels = BLOOM_TAIL_TEXELS; // ... fspt_bloom_set_tail_texels'
+
+BloomPlan bloom_plan(uint32_t vw, uint32_t vh, uint32_t levels, int form, uint32_t tail_texels) {
+  BloomPlan q{};
+  q.w[0] = vw; q.h[0] = vh;
+  uint32_t n = 0;
+  size_t off = 0;
+  while (n < levels && n < BLOOM_MAX_LEVELS && (q.w[n] < q.h[n] ? q.w[n] : q.h[n]) > 1u) {
+    q.w[n + 1] = (q.w[n] + 1u) >> 1; q.h[n + 1] = (q.h[n] + 1u) >> 1;
+    q.off[n + 1] = off;
+    off += (size_t)q.w[n + 1] * q.h[n + 1];
+    ++n;
+  }
+  q.n = n; q.texels = off;
+  // the tail: from the first level whose texels are few enough AND whose levels, three floats a texel, fit the LDS
+  if (form == 1)
+    for (uint32_t k = 1; k < n; ++k) {
+      const size_t bytes = (off - q.off[k]) * 12;
+      if ((size_t)q.w[k] * q.h[k] <= tail_texels && bytes <= BLOOM_TAIL_LDS_MAX) { q.tail = k; q.tail_lds = bytes; break; }
+    }
+  return q;
+}
+
+hipError_t launch_bloom_down(const float4 *src, uint32_t pitch, uint32_t ws, uint32_t hs, float4 *dst, uint32_t wd, uint32_t hd, bool first,
+                             hipStream_t stream) {
+  const dim3 grid((wd + BLOOM_TX - 1) / BLOOM_TX, (hd + BLOOM_TY - 1) / BLOOM_TY), block(BLOCK_THREADS);
+  if (first) hipLaunchKernelGGL(k_bloom_down<true>, grid, block, 0, stream, src, pitch, ws, hs, dst, wd, hd);
+  else hipLaunchKernelGGL(k_bloom_down<false>, grid, block, 0, stream, src, pitch, ws, hs, dst, wd, hd);
+  return hipGetLastError();
+}
+
+hipError_t launch_bloom_up(float4 *dk, uint32_t w, uint32_t h, const float4 *up, uint32_t wu, uint32_t hu, float scatter, hipStream_t stream) {
+  hipLaunchKernelGGL(k_bloom_up, dim3((w * h + BLOCK_THREADS - 1) / BLOCK_THREADS), dim3(BLOCK_THREADS), 0, stream, dk, w, h, up, wu, hu, scatter);
+  return hipGetLastError();
+}
+
+hipError_t launch_bloom_tail(const BloomTailP &p, size_t lds_bytes, hipStream_t stream) {
+  if (lds_bytes > BLOOM_TAIL_LDS_MAX) return hipErrorInvalidValue;
+  if (lds_bytes > 65536) { // (above the 64 KiB every kernel may have the limit is raised per function)
+    hipError_t e = hipFuncSetAttribute((const void *)k_bloom_tail, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BLOOM_TAIL_LDS_MAX);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_bloom_tail, dim3(1), dim3(BLOOM_TAIL_THREADS), lds_bytes, stream, p);
+  return hipGetLastError();
+}
+
+// the whole chain in front of a draw: D_1 .. D_n into `pyr` (the levels one behind the other, q.off), combined in place to U_1 .. ;
+// ev (NULL or 4 events): before the down chain, behind it, behind the tail, behind the up chain.  dbg_*: see k_bloom_tail;
+// down_snapshot (NULL in a draw): the D levels as the down chain left them are copied there before anything is combined.
+hipError_t launch_bloom_chain(const float4 *src, uint32_t pitch, const BloomPlan &q, float scatter, float4 *pyr, hipEvent_t *ev,
+                              float4 *down_snapshot, float4 *dbg_up, hipStream_t stream) {
+  hipError_t e = ev ? hipEventRecord(ev[0], stream) : hipSuccess;
+  const uint32_t last = q.tail ? q.tail : q.n; // the last level the down chain makes
+  for (uint32_t k = 0; k < last && e == hipSuccess; ++k)
+    e = launch_bloom_down(k ? pyr + q.off[k] : src, k ? q.w[k] : pitch, q.w[k], q.h[k], pyr + q.off[k + 1], q.w[k + 1], q.h[k + 1], k == 0, stream);
+  if (e == hipSuccess && down_snapshot) e = hipMemcpyAsync(down_snapshot, pyr, q.texels * sizeof(float4), hipMemcpyDeviceToDevice, stream);
+  if (e == hipSuccess && ev) e = hipEventRecord(ev[1], stream);
+  if (e == hipSuccess && q.tail) {
+    const BloomTailP p{pyr + q.off[q.tail], q.w[q.tail], q.h[q.tail], q.n - q.tail, scatter,
+                       down_snapshot ? down_snapshot + q.off[q.tail + 1] : nullptr, dbg_up ? dbg_up + q.off[q.tail + 1] : nullptr};
+    e = launch_bloom_tail(p, q.tail_lds, stream);
+  }
+  if (e == hipSuccess && ev) e = hipEventRecord(ev[2], stream);
+  for (uint32_t k = last; k-- > 1 && e == hipSuccess;)
+    e = launch_bloom_up(pyr + q.off[k], q.w[k], q.h[k], pyr + q.off[k + 1], q.w[k + 1], q.h[k + 1], scatter, stream);
+  if (e == hipSuccess && ev) e = hipEventRecord(ev[3], stream);
+  return e;
+}
+
+hipError_t launch_bloom_mix(const float4 *src, uint32_t W, uint32_t H, const BloomDraw &bl, float4 *bloom_out, float4 *mix_out, hipStream_t stream) {
+  hipLaunchKernelGGL(k_bloom_mix, dim3((W * H + BLOCK_THREADS - 1) / BLOCK_THREADS), dim3(BLOCK_THREADS), 0, stream, src, W, H, bl, bloom_out, mix_out);
   return hipGetLastError();
 }
 

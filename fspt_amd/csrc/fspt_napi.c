@@ -854,6 +854,32 @@ static napi_value ExposureReset(napi_env env, napi_callback_info info) {
   FSPT_OK_OR_THROW(fspt_exposure_reset((fspt_target *)h));
   return undefined(env);
 }
+/* setBloom(target, on, intensity, scatter, levels) / bloom(target) -> {intensity, scatter, levels} or null (off): bloom; the numbers
+ * are the library's to refuse */
+static napi_value SetBloom(napi_env env, napi_callback_info info) {
+  napi_value a[5]; void *h; bool on; double v[3];
+  if (get_args(env, info, 5, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  NAPI_OK(napi_get_value_bool(env, a[1], &on));
+  for (int k = 0; k < 3; ++k) NAPI_OK(napi_get_value_double(env, a[2 + k], &v[k]));
+  if (!(v[2] >= 0.0 && v[2] <= 4294967295.0) || v[2] != (double)(uint32_t)v[2]) { napi_throw_range_error(env, NULL, "setBloom: levels must be a whole number"); return NULL; }
+  fspt_bloom_params p = {(float)v[0], (float)v[1], (uint32_t)v[2]};
+  FSPT_OK_OR_THROW(fspt_target_set_bloom((fspt_target *)h, on ? 1 : 0, &p));
+  return undefined(env);
+}
+static napi_value Bloom(napi_env env, napi_callback_info info) {
+  napi_value a[1], o, v; void *h; int on = 0; fspt_bloom_params p;
+  if (get_args(env, info, 1, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  FSPT_OK_OR_THROW(fspt_target_get_bloom((fspt_target *)h, &on, &p));
+  if (!on) { NAPI_OK(napi_get_null(env, &o)); return o; }
+  NAPI_OK(napi_create_object(env, &o));
+  NAPI_OK(napi_create_double(env, (double)p.intensity, &v));
+  NAPI_OK(napi_set_named_property(env, o, "intensity", v));
+  NAPI_OK(napi_create_double(env, (double)p.scatter, &v));
+  NAPI_OK(napi_set_named_property(env, o, "scatter", v));
+  NAPI_OK(napi_create_uint32(env, p.levels, &v));
+  NAPI_OK(napi_set_named_property(env, o, "levels", v));
+  return o;
+}
 static napi_value TemporalDenoiseVariance(napi_env env, napi_callback_info info) {
   napi_value a[3]; void *h, *p = NULL; size_t n = 0; napi_valuetype vt;
   if (get_args(env, info, 3, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
@@ -1313,7 +1339,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
       {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
-      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
+      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},
       {"renderAsync", RenderAsync}, {"multiCreate", MultiCreate}, {"multiDestroy", MultiDestroy}, {"multiTarget", MultiTarget},
       {"multiCamera", MultiCamera}, {"multiTrace", MultiTrace}, {"multiRender", MultiRender}, {"multiRenderAsync", MultiRenderAsync},

@@ -478,6 +478,20 @@ class PathTracer {
     for (const k of Object.keys(d)) if (typeof d[k] !== 'number') throw new TypeError('setAutoExposure: ' + k + ' must be a number');
     addon.setAutoExposure(this._target, on === undefined ? true : !!on, d.key, d.low, d.high, d.adaptUp, d.adaptDown, d.minLog2, d.maxLog2);
   }
+  /** Bloom (include/fspt.h, DESIGN.md 8.12): setBloom(true, {intensity, scatter, levels}) makes every drawQuad(), present(), drawDenoised() and
+   *  temporalDraw() build an HDR pyramid of the buffer it draws on the GPU and mix its glow in before the exposure (omitted parameters = the
+   *  library's defaults).  A call that changes only the parameters keeps the allocation.  bloom: the parameters in force, or null (off). */
+  setBloom(on, opts) {
+    const d = { intensity: 0.05, scatter: 0.7, levels: 6 };  // include/fspt_tuning.h FSPT_BLOOM_*
+    if (opts != null) {
+      for (const k of Object.keys(opts)) if (!(k in d)) throw new RangeError('setBloom: unknown parameter ' + k);
+      Object.assign(d, opts);
+    }
+    for (const k of Object.keys(d)) if (typeof d[k] !== 'number') throw new TypeError('setBloom: ' + k + ' must be a number');
+    if (!Number.isInteger(d.levels)) throw new RangeError('setBloom: levels must be a whole number');
+    addon.setBloom(this._target, on === undefined ? true : !!on, d.intensity, d.scatter, d.levels);
+  }
+  get bloom() { return addon.bloom(this._target); }
   exposure() { return addon.exposure(this._target); }
   exposureReset() { addon.exposureReset(this._target); }
   temporalDraw(exposure, saturation, denoised, out) {

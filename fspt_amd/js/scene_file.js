@@ -187,6 +187,7 @@ function renderFrame(scene, settings, width, height, opts) {
     pt.lensFeatures = [settings.focus, settings.aperture];
     pt.numBounces = opts.bounces === undefined ? 4 : opts.bounces;
     if (opts.autoExposure) pt.setAutoExposure(true, opts.autoExposure === true ? null : opts.autoExposure);  // (settings.exposure: a compensation)
+    if (opts.bloom) pt.setBloom(true, opts.bloom === true ? null : opts.bloom);
     pt.seed(opts.seed === undefined ? 1 : opts.seed);
     pt.render(opts.samples === undefined ? settings.samples : opts.samples);
     const canvas = pt.drawQuad(settings.exposure, opts.saturation, opts.denoise, opts.maxSigma);
@@ -226,7 +227,7 @@ function renderSequence(scenePattern, frames, outPattern, width, height, opts) {
 module.exports = { decodePng, encodePng, decodeJpeg, mtllibUrls, loadSceneFile, renderFrame, renderToPng, renderSequence };
 
 // node fspt_amd/js/scene_file.js scene/bunny.json out.png [--width W] [--height H] [--samples N] [--bounces B] [--seed S]
-//                                [--asset-root DIR] [--denoise] [--frames A:B] [--bvh sah|gpu] [--auto-exposure [KEY]]   (mirrors `python -m fspt_amd.render`;
+//                                [--asset-root DIR] [--denoise] [--frames A:B] [--bvh sah|gpu] [--auto-exposure [KEY]] [--bloom [INTENSITY]]   (mirrors `python -m fspt_amd.render`;
 //                                with --frames both paths contain {frame}: the reference's ?frame=N loop)
 if (require.main === module) {
   const argv = process.argv.slice(2), pos = [], o = { width: 960, height: 540 };
@@ -240,13 +241,20 @@ if (require.main === module) {
         o.autoExposure = { key };
       } else o.autoExposure = true;
     }
+    else if (a === '--bloom') {  // (INTENSITY is optional: the next word is taken only if it is a number)
+      if (i + 1 < argv.length && argv[i + 1] !== '' && Number.isFinite(Number(argv[i + 1]))) {
+        const intensity = Number(argv[++i]);
+        if (!(intensity >= 0 && intensity <= 1)) { console.error('--bloom INTENSITY must be a finite value in [0, 1]'); process.exit(2); }
+        o.bloom = { intensity };
+      } else o.bloom = true;
+    }
     else if (a.startsWith('--')) o[a.slice(2).replace(/-([a-z])/g, (m, c) => c.toUpperCase())] = argv[++i];
     else pos.push(a);
   }
-  if (pos.length !== 2) { console.error('usage: node scene_file.js <scene.json> <out.png> [--width W] [--height H] [--samples N] [--bounces B] [--seed S] [--asset-root DIR] [--denoise] [--frames A:B] [--bvh sah|gpu] [--auto-exposure [KEY]]'); process.exit(2); }
+  if (pos.length !== 2) { console.error('usage: node scene_file.js <scene.json> <out.png> [--width W] [--height H] [--samples N] [--bounces B] [--seed S] [--asset-root DIR] [--denoise] [--frames A:B] [--bvh sah|gpu] [--auto-exposure [KEY]] [--bloom [INTENSITY]]'); process.exit(2); }
   const num = (k) => (o[k] === undefined ? undefined : Number(o[k]));
   const t0 = Date.now();
-  const ro = { samples: num('samples'), bounces: num('bounces'), seed: num('seed'), assetRoot: o.assetRoot, denoise: !!o.denoise, bvh: o.bvh, autoExposure: o.autoExposure };
+  const ro = { samples: num('samples'), bounces: num('bounces'), seed: num('seed'), assetRoot: o.assetRoot, denoise: !!o.denoise, bvh: o.bvh, autoExposure: o.autoExposure, bloom: o.bloom };
   if (o.frames) {
     const [a, b] = String(o.frames).split(':').map(Number), frames = [];
     for (let n = a; n < b; n++) frames.push(n);

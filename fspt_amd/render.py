@@ -54,6 +54,9 @@ def main():
     ap.add_argument("--auto-exposure", nargs="?", type=float, const=True, default=None, metavar="KEY",
                     help="meter every frame on the GPU and expose its mean log luminance to KEY (default 0.18; DESIGN 8.11); "
                          "--exposure and the scene file's `exposure` then act as compensation")
+    ap.add_argument("--bloom", nargs="?", type=float, const=True, default=None, metavar="INTENSITY",
+                    help="mix the glow of an HDR pyramid of every drawn frame in before the exposure (DESIGN 8.12); INTENSITY in [0, 1] "
+                         "(default 0.05)")
     ap.add_argument("--variance-guided", action="store_true",
                     help="--temporal --atrous K: the K iterations are guided by the per-pixel variance estimate (DESIGN 8.9)")
     ap.add_argument("--sampler", choices=("reference", "sobol"), default="reference",
@@ -93,6 +96,8 @@ def main():
         ap.error("--auto-exposure KEY must be a finite value > 0")
     if args.auto_exposure is not None and args.exposure != 1.0 and args.scene and args.frames:
         ap.error("--auto-exposure with --frames takes its compensation from the scene files' `exposure`, not from --exposure")
+    if args.bloom is not None and args.bloom is not True and not (np.isfinite(args.bloom) and 0.0 <= args.bloom <= 1.0):
+        ap.error("--bloom INTENSITY must be a finite value in [0, 1]")
     if args.variance_guided and not (args.temporal and args.atrous):
         ap.error("--variance-guided needs --temporal and --atrous K")
     if args.atrous and args.scene and not args.temporal:
@@ -111,6 +116,8 @@ def main():
             kw.update(samples=args.spp, adaptive=args.adaptive, sample_map=args.sample_map)
         if args.auto_exposure is not None:
             kw.update(auto_exposure=True if args.auto_exposure is True else {"key": args.auto_exposure})
+        if args.bloom is not None:
+            kw.update(bloom=True if args.bloom is True else {"intensity": args.bloom})
         if args.frames:
             a, b = (int(x) for x in args.frames.split(":"))
             t0 = time.perf_counter()
@@ -142,6 +149,8 @@ def main():
         pt.set_lights("emitters", args.emitter_fraction)
     if args.auto_exposure is not None:
         pt.set_auto_exposure(True, **({} if args.auto_exposure is True else {"key": args.auto_exposure}))
+    if args.bloom is not None:
+        pt.set_bloom(True, **({} if args.bloom is True else {"intensity": args.bloom}))
     t0 = time.perf_counter()
     if args.adaptive is None:
         pt.render(args.spp)

@@ -91,7 +91,8 @@ def load_scene_file(scene_path, asset_root=None, leaf_size=4, bvh="sah", device=
 
 
 def render_frame(arrays, settings, width, height, samples=None, bounces=4, seed=1, saturation=1.0, denoise=False,
-                 max_sigma=3.0, device=0, lights=None, emitter_fraction=0.5, adaptive=None, sample_map=None, auto_exposure=None):
+                 max_sigma=3.0, device=0, lights=None, emitter_fraction=0.5, adaptive=None, sample_map=None, auto_exposure=None,
+                 bloom=None):
     """One frame as the reference produces it in frame mode: `samples` ticks from a cleared accumulator
     (main.js:838-857; its very first, discarded tick is not reproduced), then drawQuad.  Returns
     (rgba8 [H, W, 4] top row first - what canvas.toBlob encodes -, radiance [H, W, 4] bottom row first).
@@ -99,13 +100,17 @@ def render_frame(arrays, settings, width, height, samples=None, bounces=4, seed=
     adaptive sampling with `samples` as the most ticks a tile gets (PathTracer.render_adaptive); sample_map:
     then also write its ticks per pixel as a grey PNG there (white = `samples`).  auto_exposure: True or a dict of
     PathTracer.set_auto_exposure's parameters (DESIGN 8.11): the frame is metered on the GPU and the scene's `exposure`
-    becomes a compensation; a still adapts instantly."""
+    becomes a compensation; a still adapts instantly.  bloom: True or a dict of PathTracer.set_bloom's parameters (DESIGN
+    8.12): the drawing mixes the HDR pyramid's glow in before the exposure."""
     from .tracer import PathTracer
     auto_exposure = _auto_exposure_params(auto_exposure)
+    bloom = _bloom_params(bloom)
     pt = PathTracer(arrays, width, height, device=device, num_bounces=bounces)
     try:
         if auto_exposure is not None:
             pt.set_auto_exposure(True, **auto_exposure)
+        if bloom is not None:
+            pt.set_bloom(True, **bloom)
         rgba, rad = _render_on(pt, settings, samples, seed, saturation, denoise, max_sigma, lights, emitter_fraction, adaptive,
                                sample_map)
     finally:
@@ -127,6 +132,16 @@ def _auto_exposure_params(auto_exposure, adapt=None):
     if adapt is not None and "adapt_up" not in params and "adapt_down" not in params:
         params.update(adapt_up=adapt, adapt_down=adapt)
     _exposure_params(params)
+    return params
+
+
+def _bloom_params(bloom):
+    """None (off) or PathTracer.set_bloom's keyword arguments from True / a dict, refused here if the library would"""
+    if bloom is None or bloom is False:
+        return None
+    from .tracer import _bloom_params as check
+    params = {} if bloom is True else dict(bloom)
+    check(params)
     return params
 
 
@@ -161,7 +176,7 @@ def write_sample_map(path, counts, max_ticks):
 
 
 def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", rebuild_above=None,
-                    on_frame=None, temporal=None, variance=False, auto_exposure=None, **kw):
+                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, **kw):
     """frame=N sequencing (main.js:851-866, 966-969): for every N in `frames` load `scene_pattern.format(frame=N)`
     (the per-frame scene JSON the reference's server hands out for `?frame=N`), render it, write
     `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1.
@@ -188,9 +203,12 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     set_auto_exposure() before its first frame, each frame's one drawing meters what it draws (the accumulator, or under
     temporal the history or its filtered form) and the scene's `exposure` becomes a compensation.  With bvh="refit" the
     tracer lives across the frames and the exposure ADAPTS: adapt_up = adapt_down = SEQUENCE_ADAPT per frame unless the
-    dict names one; every other bvh builds a tracer per frame, which meters instantly.  A new scene starts from a first metering."""
+    dict names one; every other bvh builds a tracer per frame, which meters instantly.  A new scene starts from a first metering.
+    bloom: True or a dict of PathTracer.set_bloom's parameters; every tracer gets set_bloom() before its first
+    frame, and each frame's one drawing blooms what it draws."""
     from PIL import Image
     auto_exposure = _auto_exposure_params(auto_exposure, SEQUENCE_ADAPT if bvh == "refit" else None)
+    bloom = _bloom_params(bloom)
     written = []
     device = kw.get("device", 0)
     if temporal is not None and temporal is not False:
@@ -226,7 +244,7 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     if bvh != "refit":
         for n in frames:
             arrays, settings = load_scene_file(scene_pattern.format(frame=n), asset_root, bvh=bvh, device=device)
-            rgba, _ = render_frame(arrays, settings, width, height, auto_exposure=auto_exposure, **kw)
+            rgba, _ = render_frame(arrays, settings, width, height, auto_exposure=auto_exposure, bloom=bloom, **kw)
             if on_frame:
                 on_frame(n, "build")
             save(n, rgba)
@@ -275,6 +293,8 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                     pt.temporal_set_clamp(True, **clamp)
                 if auto_exposure is not None:
                     pt.set_auto_exposure(True, **auto_exposure)
+                if bloom is not None:
+                    pt.set_bloom(True, **bloom)
             if temporal is None:
                 rgba, _ = _render_on(pt, settings, **opt)
             else:

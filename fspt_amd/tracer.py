@@ -218,6 +218,73 @@ def exposure_set_form(form):
     L.check(L.lib().fspt_exposure_set_form(int(form)))
 
 
+# include/fspt_tuning.h FSPT_BLOOM_*: conventions, not measurements (the scatter form of Jimenez / Unity)
+BLOOM_DEFAULTS = {"intensity": 0.05, "scatter": 0.7, "levels": 6}
+BLOOM_MAX_LEVELS = 8
+
+
+def _bloom_params(params):
+    """fspt_bloom_params from keyword arguments (missing ones: BLOOM_DEFAULTS), validated like the library does."""
+    unknown = set(params) - set(BLOOM_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown bloom parameters {sorted(unknown)}")
+    v = {**BLOOM_DEFAULTS, **params}
+    i, s, n = float(np.float32(v["intensity"])), float(np.float32(v["scatter"])), v["levels"]
+    if not (np.isfinite(i) and np.isfinite(s) and 0.0 <= i <= 1.0 and 0.0 <= s <= 1.0 and isinstance(n, (int, np.integer)) and not isinstance(n, bool)
+            and 1 <= n <= BLOOM_MAX_LEVELS):
+        raise ValueError(f"bloom: need finite intensity and scatter in [0, 1] and an integer levels in [1, {BLOOM_MAX_LEVELS}]")
+    return L.BloomParams(i, s, int(n))
+
+
+def bloom_levels(vw, vh, levels=BLOOM_DEFAULTS["levels"]):
+    """[(w_1, h_1), .. (w_n, h_n)] of a vw x vh viewport (the size rule of fspt_tuning.h; n from fspt_bloom_texels, host arithmetic)"""
+    n = C.c_uint32()
+    L.lib().fspt_bloom_texels(int(vw), int(vh), int(levels), C.byref(n))
+    out, w, h = [], int(vw), int(vh)
+    for _ in range(n.value):
+        w, h = (w + 1) >> 1, (h + 1) >> 1
+        out.append((w, h))
+    return out
+
+
+def bloom_eval(rgba, viewport=None, device=0, **params):
+    """The bloom kernels on a host array (fspt_bloom_eval, a test hook): rgba float32 [H, W, 4], viewport (vw, vh) or None = the
+    whole image -> (down, up, bloom, mix): down = [D_1 .. D_n] and up = [U_1 .. U_n] as float32 [h_k, w_k, 4] arrays, bloom = B
+    [vh, vw, 4], mix = c' [H, W, 4], the float32 a draw with denoise = 0 multiplies by the exposure (n = 0: no levels, the source)."""
+    prm = _bloom_params(params)
+    rgba = np.ascontiguousarray(rgba, dtype=np.float32)
+    if rgba.ndim != 3 or rgba.shape[2] != 4:
+        raise ValueError(f"need rgba [H, W, 4], got {rgba.shape}")
+    H, W = rgba.shape[:2]
+    vw, vh = (W, H) if viewport is None else (int(viewport[0]), int(viewport[1]))
+    if not (1 <= vw <= W and 1 <= vh <= H):
+        raise ValueError(f"viewport {vw}x{vh} does not fit the image {W}x{H}")
+    sizes = bloom_levels(vw, vh, prm.levels)
+    total = sum(w * h for w, h in sizes)
+    down, up = np.zeros((max(total, 1), 4), np.float32), np.zeros((max(total, 1), 4), np.float32)
+    bloom, mix = np.zeros((vh, vw, 4), np.float32), np.zeros((H, W, 4), np.float32)
+    n = C.c_uint32()
+    L.check(L.lib().fspt_bloom_eval(int(device), L.fptr(rgba), W, H, vw, vh, C.byref(prm), C.byref(n), L.fptr(down), L.fptr(up), L.fptr(bloom), L.fptr(mix)))
+    assert n.value == len(sizes)
+    ds, us, at = [], [], 0
+    for w, h in sizes:
+        ds.append(down[at:at + w * h].reshape(h, w, 4).copy())
+        us.append(up[at:at + w * h].reshape(h, w, 4).copy())
+        at += w * h
+    return ds, us, bloom, mix
+
+
+def bloom_set_form(form):
+    """The pyramid's form, process-wide (fspt_bloom_set_form, a measurement switch): 0 = one launch per level, 1 = the small
+    levels in one workgroup (k_bloom_tail).  The bits are the same."""
+    L.check(L.lib().fspt_bloom_set_form(int(form)))
+
+
+def bloom_set_tail_texels(n):
+    """Where form 1's tail takes over: the first level with at most n texels (fspt_bloom_set_tail_texels; 0 = the shipped value)"""
+    L.check(L.lib().fspt_bloom_set_tail_texels(int(n)))
+
+
 def light_alias_table(weights):
     """The Vose alias table (float32 prob, uint32 alias) the light table stores for these weights (fspt_light_alias_table,
     a pure host function: no device needed)."""
@@ -894,6 +961,27 @@ class PathTracer:
         L.check(L.lib().fspt_exposure_last_ms(self._t, ms))
         L.check(L.lib().fspt_exposure_last_draw_ms(self._t, C.byref(d)))
         return float(ms[0]), float(ms[1]), float(d.value)
+
+    # ---- bloom (include/fspt.h fspt_target_set_bloom) -------------------------------------------------
+    def set_bloom(self, on=True, **params):
+        """Bloom (fspt_target_set_bloom): every draw(), present(), drawDenoised() and temporal_draw() first builds an HDR pyramid of
+        the buffer it draws, on the GPU, and mixes its glow into every texel in front of the exposure.  params: intensity, scatter,
+        levels (missing ones: BLOOM_DEFAULTS).  A call that changes only the parameters keeps the allocation; off frees it."""
+        prm = _bloom_params(params) if on else None
+        L.check(L.lib().fspt_target_set_bloom(self._t, 1 if on else 0, C.byref(prm) if on else None))
+
+    @property
+    def bloom(self):
+        """None (off) or {"intensity", "scatter", "levels"} as the library holds them (fspt_target_get_bloom)"""
+        on, p = C.c_int(), L.BloomParams()
+        L.check(L.lib().fspt_target_get_bloom(self._t, C.byref(on), C.byref(p)))
+        return {"intensity": float(p.intensity), "scatter": float(p.scatter), "levels": int(p.levels)} if on.value else None
+
+    def bloom_last_ms(self):
+        """(down chain ms, tail ms, up chain ms, k_draw_bloom ms) of the last bloomed draw, from HIP events (fspt_bloom_last_ms)"""
+        ms = (C.c_float * 4)()
+        L.check(L.lib().fspt_bloom_last_ms(self._t, ms))
+        return tuple(float(x) for x in ms)
 
     def temporal_draw(self, exposure=1.0, saturation=1.0, denoised=False):
         """draw() of the temporal result, or of the last temporal_denoise() (fspt_temporal_draw): RGBA8 [H, W, 4]."""

@@ -211,7 +211,7 @@ int fspt_temporal_denoise_variance(fspt_target *t, const fspt_denoise_params *p,
 int fspt_temporal_set_clamp(fspt_target *t, int on, float fast_history, float sigma_scale); /* history clamp (DESIGN 8.10; rule and defaults: fspt_tuning.h): a fast history bounds the long one; default off */
 /* Auto-exposure (DESIGN 8.11; rule and defaults: fspt_tuning.h): every drawing entry first meters the buffer it draws (a luminance histogram of the viewport, on the GPU, no host read) and its `exposure` argument becomes a compensation of the metered value. */ typedef struct fspt_exposure_params { float key, low, high, adapt_up, adapt_down, min_log2, max_log2; } fspt_exposure_params;
 int fspt_target_set_auto_exposure(fspt_target *t, int on, const fspt_exposure_params *p); /* p NULL = defaults; default off */ int fspt_exposure_reset(fspt_target *t); /* the next metering is a first one */
-int fspt_exposure_get(fspt_target *t, float *exposure, float *log2_mean, uint32_t *metered); /* blocking; joins a present */
+int fspt_exposure_get(fspt_target *t, float *exposure, float *log2_mean, uint32_t *metered); /* blocking; joins a present */ /* Bloom (DESIGN 8.12; rule and defaults: fspt_tuning.h): every drawing entry first builds an HDR pyramid of the buffer it draws and mixes its glow in before the exposure. */ typedef struct fspt_bloom_params { float intensity, scatter; uint32_t levels; } fspt_bloom_params; int fspt_target_set_bloom(fspt_target *t, int on, const fspt_bloom_params *p); /* p NULL = defaults; default off */ int fspt_target_get_bloom(fspt_target *t, int *on, fspt_bloom_params *p);
 /* intersectScene (tracer.fs:366-404) as a stand-alone entry: n rays (origin xyz, dir xyz) -> closest hit t and triangle index (-1 = miss, t = 1e5), optionally loop-iteration and leaf-visit counts per ray.  Host pointers. */
 int fspt_intersect(fspt_scene *scene, const float *rays, uint32_t n, float *t_out, int32_t *index_out, uint32_t *steps_out, uint32_t *leaves_out);
 

@@ -274,6 +274,50 @@ int fspt_exposure_last_draw_ms(fspt_target *t, float *ms);
 /* Measurement switch, process-wide: k_exposure_histogram's form, 0 (shipped) = one LDS atomic per pixel, 1 = the lanes that share the first active lane's
  * bin are counted by a ballot and added once.  The histogram is the same bit for bit. */
 int fspt_exposure_set_form(int form);
+/* Bloom (fspt.h fspt_target_set_bloom): the threshold-free, energy-conserving "scatter" pyramid, taken from the HDR buffer a drawing entry is
+ * about to draw, before the exposure.  All of it in float32, in exactly this order (both kernel forms and the draw follow it; tests/bloom_ref.py restates it).
+ * Sanitise, per channel: s(v) = v >= 0 ? min(v, FSPT_BLOOM_CLAMP) : 0 - NaN and negatives become 0, +inf the clamp (the path kernels' own per-sample clamp),
+ * so one bad texel cannot poison the frame through the pyramid.  Level 0 is the drawn buffer restricted to the viewport vw x vh; nothing outside it is read.
+ * Sizes: w_{k+1} = (w_k + 1) >> 1, the same for h; j = the smallest k with min(w_k, h_k) == 1; n = min(levels, j) levels are built; n = 0 (a 1 x N or N x 1
+ * viewport): the draw is the plain draw.
+ * Down: D_{k+1}(x, y) = sum_{j,i in 0..3} w_j w_i S_k(clamp(2x - 1 + i, 0, w_k - 1), clamp(2y - 1 + j, 0, h_k - 1)), w = (1, 3, 3, 1) / 8, S_0 = s(level 0),
+ * S_k = D_k; separable, horizontal first; one pass of taps a0..a3 is ((a1 + a2) * 3 + (a0 + a3)) * 0.125, evaluated as written: a1 + a2, its product by 3,
+ * a0 + a3 and the sum of the two round (four roundings, three deep), the product by 1/8 is exact.
+ * Up: up(U)(x, y), the 2 x 2 tent over the coarser level U (w x h): cx0 = x >> 1, cx1 = clamp(cx0 + ((x & 1) ? 1 : -1), 0, w - 1), weights 3/4 on cx0 and 1/4
+ * on cx1, the same in y; horizontal first: up = fma(3/4, fma(3/4, U(cx0, cy0), U(cx1, cy0) / 4), fma(3/4, U(cx0, cy1), U(cx1, cy1) / 4) / 4): two roundings deep.
+ * Combine: U_n = D_n; for k = n - 1 .. 1: U_k = fma(scatter, up(U_{k+1}) - D_k, D_k) (the difference rounds, the fma rounds), in place over D_k;
+ * B = up(U_1) at level-0 coordinates.
+ * Draw: the source texel (x, y) = ivec2(frag * scale) as before; c = that texel, or the firefly-filtered `middle` under `denoise`; c0 = s(c);
+ * c' = fma(intensity, B(x, y) - c0, c0) per channel; c' * exposure goes into the rest of the draw unchanged.  A source texel outside the viewport is drawn plain.
+ * Consequences: the weights are dyadic, so only additions (and the two parameter fma) round; scaling the input by a power of two scales every level by exactly
+ * that power, away from the clamp and from denormals; on a finite, non-negative buffer under the clamp intensity = 0 gives the mode-off bytes; auto-exposure
+ * (8.11) meters the source buffer, not the bloomed one.  Roundings on the deepest path: D_k 6 k, U_k 6 n + 4 (n - k), B 10 n - 2, c' 10 n.
+ * State: the pyramid, allocated on enable for the target's W x H at FSPT_BLOOM_MAX_LEVELS (16 bytes a texel, at most a third of the accumulator), freed on disable
+ * and with the target; a call that changes only the parameters keeps it.  No drawing entry gains a host synchronisation.  FSPT_E_INVALID: NULL, non-finite
+ * fields, intensity or scatter outside [0, 1], levels outside [1, FSPT_BLOOM_MAX_LEVELS]; FSPT_E_STATE: a sharded target.  fspt_multi_* targets are not bloomed.
+ * The defaults are conventions, not measurements (Jimenez' / Unity's scatter form). */
+#define FSPT_BLOOM_INTENSITY 0.05f
+#define FSPT_BLOOM_SCATTER 0.7f
+#define FSPT_BLOOM_LEVELS 6
+#define FSPT_BLOOM_MAX_LEVELS 8
+#define FSPT_BLOOM_CLAMP 1024.0f
+/* k_bloom_tail (form 1) takes over at the first level k >= 1 with w_k h_k <= this many texels (and whose levels fit the LDS at 12 bytes a texel: about
+ * 4/3 of the first one's).  2048: 60 x 34 of 1920 x 1080 and below, 30 KiB; the other candidate, 8192, adds 120 x 68 and needs 126 KiB of the 160. */
+#define FSPT_BLOOM_TAIL_TEXELS 2048
+/* Test hook: the production kernels on a host array - rgba W*H*4 floats, viewport vw x vh (0, 0 = the whole image), p NULL = defaults.  *n_out = n;
+ * down_out = D_1 .. D_n and up_out = U_1 .. U_n, each level w_k*h_k*4 floats (.w = 0), one behind the other (room for fspt_bloom_texels(vw, vh, levels)
+ * texels each); bloom_out = B, vw*vh*4 floats; mix_out = c' with denoise = 0, W*H*4 floats: the float32 the draw multiplies by the exposure (outside the
+ * viewport and with n = 0: the source; .w = the source's).  Any output may be NULL. */
+int fspt_bloom_eval(int device, const float *rgba, uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const fspt_bloom_params *p, uint32_t *n_out,
+                    float *down_out, float *up_out, float *bloom_out, float *mix_out);
+/* Host arithmetic, no device: n of a vw x vh viewport (*n_out, may be NULL); returns the texels of levels 1 .. n. */
+uint64_t fspt_bloom_texels(uint32_t vw, uint32_t vh, uint32_t levels, uint32_t *n_out);
+/* Measurement switches, process-wide: the form, 0 = one launch per level, 1 = k_bloom_tail below the threshold; and the threshold (0 = FSPT_BLOOM_TAIL_TEXELS
+ * again), so that small shapes can run wholly in the tail or wholly outside it.  The bits are the same. */
+int fspt_bloom_set_form(int form);
+int fspt_bloom_set_tail_texels(uint32_t n);
+/* GPU ms of the last bloomed draw on this target, from HIP events: ms[0] the down chain, ms[1] the tail, ms[2] the up chain, ms[3] k_draw_bloom.  Blocking. */
+int fspt_bloom_last_ms(fspt_target *t, float ms[4]);
 /* fspt_target_set_lights (fspt.h): FSPT_LIGHTS_EMITTERS lets each shading vertex spend its shadow ray on a
  * point of an emissive triangle (probability q = emitter_fraction, in (0, 1]; at most 0.875 with an environment map, 1
  * when the scene has none)

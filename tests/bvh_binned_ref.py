@@ -77,7 +77,8 @@ def prims(verts):
     v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3, 3)
     k = key(v)
     bk = np.concatenate([k.min(1), k.max(1)], 1)
-    c = (unkey(bk[:, :3]) + unkey(bk[:, 3:])) * np.float32(0.5)
+    with np.errstate(over="ignore"):  # min + max beyond float32's range is +-inf, as on the device
+        c = (unkey(bk[:, :3]) + unkey(bk[:, 3:])) * np.float32(0.5)
     return bk, c.astype(np.float32)
 
 

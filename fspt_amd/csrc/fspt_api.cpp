@@ -772,17 +772,7 @@ int fspt_target_destroy(fspt_target *t) {
     for (hipEvent_t ev : {t->pr_acc, t->pr_hop}) if (ev) hipEventDestroy(ev);
   }
   hipFree(t->accum_own); hipFree(t->ray_pos); hipFree(t->ray_dir); hipFree(t->work_counters); hipFree(t->counters);
-  hipFree(t->feat); hipFree(t->dn_tmp[0]); hipFree(t->dn_tmp[1]); hipFree(t->dn_out);
-  hipFree(t->tm_hist[0]); hipFree(t->tm_hist[1]); hipFree(t->tm_g[0]); hipFree(t->tm_g[1]); hipFree(t->tm_m);
-  for (hipEvent_t ev : t->tm_ev) if (ev) hipEventDestroy(ev);
-  hipFree(t->tm_mom[0]); hipFree(t->tm_mom[1]); hipFree(t->tm_var);
-  for (hipEvent_t ev : t->sv_ev) if (ev) hipEventDestroy(ev);
-  hipFree(t->tm_fast[0]); hipFree(t->tm_fast[1]);
-  for (hipEvent_t ev : t->cl_ev) if (ev) hipEventDestroy(ev);
-  hipFree(t->ax_hist);
-  for (hipEvent_t ev : t->ax_ev) if (ev) hipEventDestroy(ev);
-  hipFree(t->bl_pyr);
-  for (hipEvent_t ev : t->bl_ev) if (ev) hipEventDestroy(ev);
+  post_release(t);
   hipFree(t->ad_snap); hipFree(t->ad_list[0]); hipFree(t->ad_list[1]); hipFree(t->ad_count); hipFree(t->ad_err);
   {
     fspt_target::WfLane &ln = t->wf;
@@ -1291,18 +1281,17 @@ int fspt_light_sample_eval(fspt_scene *s, const float *in, uint32_t n, int32_t *
   if (rc) return rc;
   if (s->d.n_lights == 0) { fspt_set_error("fspt_light_sample_eval: the scene has no emitter"); return FSPT_E_STATE; }
   if (n == 0) return FSPT_OK;
-  float *d_in = nullptr, *d_out = nullptr;
-  int *d_e = nullptr;
-  hipError_t e = hipMalloc((void **)&d_in, (size_t)n * 40);
-  if (e == hipSuccess) e = hipMalloc((void **)&d_out, (size_t)n * 32);
-  if (e == hipSuccess) e = hipMalloc((void **)&d_e, (size_t)n * 4);
-  if (e == hipSuccess) e = hipMemcpy(d_in, in, (size_t)n * 40, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = fspt::launch_light_eval(s->d, d_in, n, d_e, d_out, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out, d_out, (size_t)n * 32, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(tri, d_e, (size_t)n * 4, hipMemcpyDeviceToHost);
-  hipFree(d_in); hipFree(d_out); hipFree(d_e);
-  if (e != hipSuccess) { fspt_set_error("fspt_light_sample_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
+  // one allocation, in floats: in (10 n) | out (8 n) | entry (n)
+  Staging st((size_t)n * 76);
+  if (!st.ok()) return st.done("fspt_light_sample_eval");
+  float *const d_in = (float *)st.base, *const d_out = d_in + (size_t)n * 10;
+  int *const d_e = (int *)(d_out + (size_t)n * 8);
+  st.up(d_in, in, (size_t)n * 40);
+  if (st.ok()) st.e = fspt::launch_light_eval(s->d, d_in, n, d_e, d_out, nullptr);
+  st.sync();
+  st.down(out, d_out, (size_t)n * 32);
+  st.down(tri, d_e, (size_t)n * 4);
+  if ((rc = st.done("fspt_light_sample_eval"))) return rc;
   for (uint32_t i = 0; i < n; ++i) tri[i] = (int32_t)s->l_tri[(uint32_t)tri[i]];
   return FSPT_OK;
 }
@@ -1330,76 +1319,6 @@ int fspt_read_radiance(fspt_target *t, float *out) {
   FLUSH_OR_RETURN(t);
   HIP_TRY(hipMemcpyAsync(out, t->accum, (size_t)t->W * t->H * 16, hipMemcpyDeviceToHost, t->stream));
   HIP_TRY(hipStreamSynchronize(t->stream));
-  return FSPT_OK;
-}
-
-// Auto-exposure's metering of `src` on `st`: histogram, resolve, the events around them.
-static hipError_t draw_meter(fspt_target *t, const float4 *src, hipStream_t st) {
-  hipError_t e = hipEventRecord(t->ax_ev[0], st);
-  if (e == hipSuccess) e = fspt::launch_exposure_histogram(src, t->W, t->vw, t->vh, t->ax_hist, fspt::g_exposure_form, st);
-  if (e == hipSuccess) e = hipEventRecord(t->ax_ev[1], st);
-  if (e == hipSuccess) e = fspt::launch_exposure_resolve(t->ax_hist, t->ax_state, t->ax_p, st);
-  if (e == hipSuccess) e = hipEventRecord(t->ax_ev[2], st);
-  return e;
-}
-// The draw with bloom on: after the metering when that is on (it meters the source buffer), the pyramid chain on
-// the same stream - down, tail or not, up, all into t->bl_pyr - and k_draw_bloom, which mixes up(U_1) into the texel in front of
-// the exposure.  n = 0 (a viewport one texel wide or high): the plain draw.  No host read, no synchronisation.
-static hipError_t draw_launch_bloom(fspt_target *t, const float4 *src, float exposure, float saturation, int denoise, float max_sigma,
-                                    float scale, uint32_t *out, hipStream_t st) {
-  hipError_t e = hipSuccess;
-  if (t->ax_on) {
-    if ((e = draw_meter(t, src, st)) != hipSuccess) return e;
-    t->ax_timed = true;
-  }
-  const fspt::BloomPlan q = fspt::bloom_plan(t->vw, t->vh, t->bl_p.levels, fspt::g_bloom_form, fspt::g_bloom_tail_texels);
-  t->bl_timed = false;
-  if (q.n == 0) {
-    e = t->ax_on ? fspt::launch_draw_auto(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, t->ax_state, st)
-                 : fspt::launch_draw(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, st);
-  } else {
-    e = fspt::launch_bloom_chain(src, t->W, q, t->bl_p.scatter, t->bl_pyr, t->bl_ev, nullptr, nullptr, st);
-    const fspt::BloomDraw bl{t->bl_pyr + q.off[1], q.w[1], q.h[1], t->vw, t->vh, t->bl_p.intensity};
-    if (e == hipSuccess) e = fspt::launch_draw_bloom(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, t->ax_on ? t->ax_state : nullptr, bl, st);
-    if (e == hipSuccess) e = hipEventRecord(t->bl_ev[4], st);
-    if (e == hipSuccess) t->bl_timed = true;
-  }
-  if (e == hipSuccess && t->ax_on) e = hipEventRecord(t->ax_ev[3], st);
-  return e;
-}
-
-// k_draw of `src` on `st`.  With auto-exposure on the buffer is metered first, on the same stream - histogram,
-// resolve - and k_draw_auto multiplies the caller's exposure by the value the resolve left in device memory: no host read.
-static hipError_t draw_launch(fspt_target *t, const float4 *src, float exposure, float saturation, int denoise, float max_sigma,
-                              float scale, uint32_t *out, hipStream_t st) {
-  if (t->bl_on) return draw_launch_bloom(t, src, exposure, saturation, denoise, max_sigma, scale, out, st);
-  if (!t->ax_on) return fspt::launch_draw(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, st);
-  hipError_t e = draw_meter(t, src, st);
-  if (e != hipSuccess) return e;
-  t->ax_timed = true;
-  e = fspt::launch_draw_auto(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, t->ax_state, st);
-  if (e == hipSuccess) e = hipEventRecord(t->ax_ev[3], st);
-  return e;
-}
-
-int fspt_draw(fspt_target *t, float exposure, float saturation, int denoise, float max_sigma, uint8_t *out_rgba8) {
-  return fspt_draw_scaled(t, exposure, saturation, denoise, max_sigma, 1.0f, out_rgba8);
-}
-
-int fspt_draw_scaled(fspt_target *t, float exposure, float saturation, int denoise, float max_sigma, float scale,
-                     uint8_t *out_rgba8) {
-  if (!t || !out_rgba8) { fspt_set_error("fspt_draw: NULL argument"); return FSPT_E_INVALID; }
-  if (!(scale > 0.0f && scale <= 1.0f)) { fspt_set_error("fspt_draw: scale must be in (0, 1]"); return FSPT_E_INVALID; }
-  HIP_TRY(hipSetDevice(t->scene->device));
-  FLUSH_OR_RETURN(t);
-  size_t n = (size_t)t->W * t->H;
-  uint32_t *d = nullptr;
-  HIP_TRY(hipMalloc((void **)&d, n * 4));
-  hipError_t e = draw_launch(t, t->accum, exposure, saturation, denoise, max_sigma, scale, d, t->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_rgba8, d, n * 4, hipMemcpyDeviceToHost, t->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  hipFree(d);
-  if (e != hipSuccess) { fspt_set_error("fspt_draw: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
   return FSPT_OK;
 }
 
@@ -1700,796 +1619,6 @@ int fspt_present(fspt_target *t, float exposure, float saturation, int denoise, 
     HIP_TRY(hipEventSynchronize(t->pr_copied[prev]));
     if (t->pr_ticks[prev]) { std::memcpy(out_rgba8, t->pr_host[prev], n * 4); *ticks_out = t->pr_ticks[prev]; }
   }
-  return FSPT_OK;
-}
-
-// ---------------------------------------------------------------------------
-// guided denoiser
-// ---------------------------------------------------------------------------
-// NULL arguments first, then the device: every call fails with FSPT_E_NO_DEVICE where no HIP device is visible
-static int dn_enter(fspt_target *t, bool args_ok, const char *fn) {
-  if (!t || !args_ok) { fspt_set_error("%s: NULL argument", fn); return FSPT_E_INVALID; }
-  if (fspt_device_count() <= 0) { fspt_set_error("%s: no HIP device available; libfspt has no CPU fallback", fn); return FSPT_E_NO_DEVICE; }
-  HIP_TRY(hipSetDevice(t->scene->device));
-  FLUSH_OR_RETURN(t);
-  return FSPT_OK;
-}
-static int dn_alloc(float4 **buf, size_t bytes) {
-  if (!*buf) HIP_TRY(hipMalloc((void **)buf, bytes));
-  return FSPT_OK;
-}
-// sigma_color, sigma_depth: +inf switches the weight off; sigma_normal: 0 switches it off (it is an exponent)
-static int dn_check_params(const fspt_denoise_params &q, const char *fn) {
-  if (q.iterations > 16u || !(q.sigma_color >= 0.0f) || !(q.sigma_depth > 0.0f) || !(q.sigma_normal >= 0.0f && q.sigma_normal < INFINITY)) {
-    fspt_set_error("%s: need iterations <= 16, sigma_color >= 0, sigma_normal in [0, inf), sigma_depth > 0", fn);
-    return FSPT_E_INVALID;
-  }
-  return FSPT_OK;
-}
-// The K launches of k_atrous (fspt_denoise and its test hook fspt_denoise_eval): accum -> out (W*H float4 each) guided by
-// feat (2 W*H float4), ping-ponging through tmp[0..1] (needed when K > 1); K = 0 copies accum
-static hipError_t dn_run(const fspt_denoise_params &q, const float4 *accum, const float4 *feat, uint32_t W, uint32_t H,
-                         float4 *const tmp[2], float4 *out, hipStream_t stream) {
-  const size_t px = (size_t)W * H;
-  if (q.iterations == 0) return hipMemcpyAsync(out, accum, px * 16, hipMemcpyDeviceToDevice, stream);
-  for (uint32_t k = 0; k < q.iterations; ++k) {
-    fspt::AtrousP p{};
-    p.src = k == 0 ? accum : tmp[(k - 1) & 1u];
-    p.dst = k + 1 == q.iterations ? out : tmp[k & 1u];
-    p.feat = feat;
-    p.W = W; p.H = H;
-    p.step = 1 << k;
-    p.demod = k == 0; p.remod = k + 1 == q.iterations;
-    p.sc_step = std::ldexp(q.sigma_color, -(int)k);
-    p.sn = q.sigma_normal;
-    p.sz_step = std::ldexp(q.sigma_depth, (int)k);
-    hipError_t e = fspt::launch_atrous(p, stream);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-int fspt_features(fspt_target *t, const fspt_camera_params *cam, uint32_t samples, uint64_t seed) {
-  int rc = dn_enter(t, cam != nullptr, "fspt_features");
-  if (rc) return rc;
-  if (samples == 0) { fspt_set_error("fspt_features: samples must be >= 1"); return FSPT_E_INVALID; }
-  const size_t px = (size_t)t->W * t->H;
-  if ((rc = dn_alloc(&t->feat, px * 32))) return rc;
-  fspt::FeatureP p{};
-  p.scene = t->scene->d;
-  p.W = t->W; p.H = t->H;
-  std::memcpy(p.cam.P, cam->P, 12); std::memcpy(p.cam.I, cam->I, 12);
-  p.cam.fov_scale = cam->fov_scale; p.cam.lens[0] = cam->lens[0]; p.cam.lens[1] = cam->lens[1];
-  p.samples = samples;
-  p.seed = seed;
-  p.feat = t->feat;
-  t->feat_valid = false;
-  HIP_TRY(fspt::launch_features(p, t->stream));
-  t->feat_valid = true;
-  return FSPT_OK;
-}
-
-int fspt_read_features(fspt_target *t, float *out) {
-  int rc = dn_enter(t, out != nullptr, "fspt_read_features");
-  if (rc) return rc;
-  if (!t->feat_valid) { fspt_set_error("fspt_read_features: no fspt_features call yet"); return FSPT_E_STATE; }
-  HIP_TRY(hipMemcpyAsync(out, t->feat, (size_t)t->W * t->H * 32, hipMemcpyDeviceToHost, t->stream));
-  HIP_TRY(hipStreamSynchronize(t->stream));
-  return FSPT_OK;
-}
-
-int fspt_denoise(fspt_target *t, const fspt_denoise_params *prm, float *out) {
-  int rc = dn_enter(t, true, "fspt_denoise");
-  if (rc) return rc;
-  fspt_denoise_params q = {FSPT_DENOISE_ITERATIONS, FSPT_DENOISE_SIGMA_COLOR, FSPT_DENOISE_SIGMA_NORMAL, FSPT_DENOISE_SIGMA_DEPTH};
-  if (prm) q = *prm;
-  if ((rc = dn_check_params(q, "fspt_denoise"))) return rc;
-  if (!t->feat_valid) { fspt_set_error("fspt_denoise: no fspt_features call yet"); return FSPT_E_STATE; }
-  const size_t px = (size_t)t->W * t->H;
-  if ((rc = dn_alloc(&t->dn_out, px * 16))) return rc;
-  t->dn_valid = false;
-  if (q.iterations > 1u && ((rc = dn_alloc(&t->dn_tmp[0], px * 16)) || (rc = dn_alloc(&t->dn_tmp[1], px * 16)))) return rc;
-  t->tm_dn_valid = false; // (dn_out is shared with fspt_temporal_denoise)
-  HIP_TRY(dn_run(q, t->accum, t->feat, t->W, t->H, t->dn_tmp, t->dn_out, t->stream));
-  t->dn_valid = true;
-  if (out) {
-    HIP_TRY(hipMemcpyAsync(out, t->dn_out, px * 16, hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipStreamSynchronize(t->stream));
-  }
-  return FSPT_OK;
-}
-
-int fspt_draw_denoised(fspt_target *t, float exposure, float saturation, uint8_t *out_rgba8) {
-  int rc = dn_enter(t, out_rgba8 != nullptr, "fspt_draw_denoised");
-  if (rc) return rc;
-  if (!t->dn_valid) { fspt_set_error("fspt_draw_denoised: no fspt_denoise call yet"); return FSPT_E_STATE; }
-  size_t n = (size_t)t->W * t->H;
-  uint32_t *d = nullptr;
-  HIP_TRY(hipMalloc((void **)&d, n * 4));
-  hipError_t e = draw_launch(t, t->dn_out, exposure, saturation, 0, 0.0f, 1.0f, d, t->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_rgba8, d, n * 4, hipMemcpyDeviceToHost, t->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  hipFree(d);
-  if (e != hipSuccess) { fspt_set_error("fspt_draw_denoised: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
-  return FSPT_OK;
-}
-
-// ---------------------------------------------------------------------------
-// temporal accumulation (k_temporal_gbuffer / k_temporal_blend)
-// ---------------------------------------------------------------------------
-static int tm_check_params(const fspt_temporal_params &q, const char *fn) {
-  if (!(q.alpha >= 0.0f && q.alpha <= 1.0f) || !(q.max_history >= 1.0f) || !(q.depth_tol >= 0.0f) || !(q.normal_cos >= -1.0f && q.normal_cos <= 1.0f)) {
-    fspt_set_error("%s: need alpha in [0, 1], max_history >= 1, depth_tol >= 0, normal_cos in [-1, 1]", fn);
-    return FSPT_E_INVALID;
-  }
-  return FSPT_OK;
-}
-static const fspt_temporal_params TM_DEFAULTS = {FSPT_TEMPORAL_ALPHA, FSPT_TEMPORAL_MAX_HISTORY, FSPT_TEMPORAL_DEPTH_TOL, FSPT_TEMPORAL_NORMAL_COS};
-static void tm_fill_blend(fspt::TemporalBP &b, const fspt_temporal_params &q, uint32_t W, uint32_t H, float n) {
-  b.W = W; b.H = H; b.n = n;
-  b.alpha = q.alpha; b.max_history = q.max_history; b.depth_tol = q.depth_tol; b.normal_cos = q.normal_cos;
-}
-
-int fspt_temporal_accumulate(fspt_target *t, const fspt_camera_params *cam, const fspt_temporal_params *prm, float *out) {
-  if (!t || !cam) { fspt_set_error("fspt_temporal_accumulate: NULL argument"); return FSPT_E_INVALID; }
-  fspt_temporal_params q = TM_DEFAULTS;
-  if (prm) q = *prm;
-  int rc = tm_check_params(q, "fspt_temporal_accumulate");
-  if (rc) return rc;
-  if ((rc = dn_enter(t, true, "fspt_temporal_accumulate"))) return rc;
-  if (t->n_shards > 1) { fspt_set_error("fspt_temporal_accumulate: sharded target (its accumulator holds a part of the frame)"); return FSPT_E_STATE; }
-  if (t->vw != t->W || t->vh != t->H) { fspt_set_error("fspt_temporal_accumulate: the viewport %ux%u is smaller than the target", t->vw, t->vh); return FSPT_E_STATE; }
-  if (t->acc_ticks == 0) { fspt_set_error("fspt_temporal_accumulate: the accumulator holds no sample (render first)"); return FSPT_E_STATE; }
-  if (t->tm_moments && !t->feat_valid) { fspt_set_error("fspt_temporal_accumulate: moments are on and there is no fspt_features call yet (the input is demodulated by its albedo)"); return FSPT_E_STATE; }
-  const size_t px = (size_t)t->W * t->H;
-  for (int k = 0; k < 2; ++k) {
-    if ((rc = dn_alloc(&t->tm_hist[k], px * 16)) || (rc = dn_alloc(&t->tm_g[k], px * 32))) return rc;
-  }
-  if ((rc = dn_alloc(&t->tm_m, px * 16))) return rc;
-  for (hipEvent_t &ev : t->tm_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
-  const int cur = t->tm_cur, nx = cur ^ 1;
-  fspt::TemporalGP g{};
-  g.scene = t->scene->d;
-  g.W = t->W; g.H = t->H;
-  std::memcpy(g.cam.P, cam->P, 12); std::memcpy(g.cam.I, cam->I, 12);
-  g.cam.fov_scale = cam->fov_scale;
-  g.prev = t->tm_cam;
-  g.has_prev = t->tm_valid ? 1u : 0u;
-  g.origin = (const float *)t->scene->motion;
-  g.g = t->tm_g[nx]; g.m = t->tm_m;
-  fspt::TemporalBP b{};
-  tm_fill_blend(b, q, t->W, t->H, (float)t->acc_ticks);
-  b.accum = t->accum; b.m = t->tm_m; b.g = t->tm_g[nx];
-  b.hist = t->tm_hist[cur]; b.g_prev = t->tm_g[cur];
-  b.out = t->tm_hist[nx];
-  b.has_hist = g.has_prev;
-  if (t->tm_moments) { // the moments instantiation: the same taps also carry (M1, M2)
-    b.feat = t->feat; b.mom_hist = t->tm_mom[cur]; b.mom_out = t->tm_mom[nx];
-    b.has_mom = b.has_hist; // (the two histories start together: fspt_temporal_set_moments, fspt_temporal_reset)
-  }
-  if (t->tm_clamp) { // the fast-history instantiation: the same taps also carry F, capped at fast_history
-    b.fast_hist = t->tm_fast[cur]; b.fast_out = t->tm_fast[nx];
-    b.has_fast = b.has_hist && t->tm_fast_valid ? 1u : 0u; // (the two histories start together: fspt_temporal_set_clamp, fspt_temporal_reset)
-    b.fast_history = t->tm_fast_history;
-    for (hipEvent_t &ev : t->cl_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
-  }
-  t->tm_fast_valid = false; t->cl_timed = false;
-  t->tm_mom_valid = false; t->tm_var_valid = false;
-  t->tm_gm_valid = false; t->tm_timed = false;
-  t->tm_dn_valid = false; // (a denoised frame of the previous history is not this one's)
-  t->tm_valid = false; // (an error below leaves no half-written history behind)
-  HIP_TRY(hipEventRecord(t->tm_ev[0], t->stream));
-  HIP_TRY(fspt::launch_temporal_gbuffer(g, t->stream));
-  HIP_TRY(hipEventRecord(t->tm_ev[1], t->stream));
-  HIP_TRY(fspt::launch_temporal_blend(b, t->stream));
-  HIP_TRY(hipEventRecord(t->tm_ev[2], t->stream));
-  if (t->tm_clamp) { // pass 3: the long history into the fast one's box, in place (sigma_scale = +inf: no launch, never inf * 0)
-    HIP_TRY(hipEventRecord(t->cl_ev[0], t->stream));
-    if (t->tm_sigma_scale != INFINITY) {
-      fspt::ClampP c{};
-      c.hist = t->tm_hist[nx]; c.fast = t->tm_fast[nx];
-      c.W = t->W; c.H = t->H; c.sigma_scale = t->tm_sigma_scale;
-      HIP_TRY(fspt::launch_temporal_clamp(c, t->stream));
-    }
-    HIP_TRY(hipEventRecord(t->cl_ev[1], t->stream));
-    t->tm_fast_valid = true; t->cl_timed = true;
-  }
-  t->tm_cur = nx;
-  t->tm_cam = g.cam;
-  t->tm_valid = true; t->tm_gm_valid = true; t->tm_timed = true;
-  t->tm_mom_valid = t->tm_moments;
-  t->tm_n = (float)t->acc_ticks;
-  if (out) {
-    HIP_TRY(hipMemcpyAsync(out, t->tm_hist[nx], px * 16, hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipStreamSynchronize(t->stream));
-  }
-  return FSPT_OK;
-}
-
-int fspt_temporal_reset(fspt_target *t) {
-  if (!t) { fspt_set_error("fspt_temporal_reset: NULL target"); return FSPT_E_INVALID; }
-  FLUSH_OR_RETURN(t);
-  t->tm_valid = false;
-  t->tm_dn_valid = false;
-  t->tm_mom_valid = false; t->tm_var_valid = false; // (the moments go with the history they describe)
-  t->tm_fast_valid = false;                         // (and so does the fast history)
-  return FSPT_OK;
-}
-
-int fspt_temporal_denoise(fspt_target *t, const fspt_denoise_params *prm, float *out) {
-  int rc = dn_enter(t, true, "fspt_temporal_denoise");
-  if (rc) return rc;
-  fspt_denoise_params q = {FSPT_DENOISE_ITERATIONS, FSPT_DENOISE_SIGMA_COLOR, FSPT_DENOISE_SIGMA_NORMAL, FSPT_DENOISE_SIGMA_DEPTH};
-  if (prm) q = *prm;
-  if ((rc = dn_check_params(q, "fspt_temporal_denoise"))) return rc;
-  if (!t->tm_valid) { fspt_set_error("fspt_temporal_denoise: no fspt_temporal_accumulate call yet"); return FSPT_E_STATE; }
-  if (!t->feat_valid) { fspt_set_error("fspt_temporal_denoise: no fspt_features call yet"); return FSPT_E_STATE; }
-  const size_t px = (size_t)t->W * t->H;
-  if ((rc = dn_alloc(&t->dn_out, px * 16))) return rc;
-  t->dn_valid = false;
-  if (q.iterations > 1u && ((rc = dn_alloc(&t->dn_tmp[0], px * 16)) || (rc = dn_alloc(&t->dn_tmp[1], px * 16)))) return rc;
-  t->tm_dn_valid = false;
-  HIP_TRY(dn_run(q, t->tm_hist[t->tm_cur], t->feat, t->W, t->H, t->dn_tmp, t->dn_out, t->stream));
-  t->dn_valid = true; t->tm_dn_valid = true;
-  if (out) {
-    HIP_TRY(hipMemcpyAsync(out, t->dn_out, px * 16, hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipStreamSynchronize(t->stream));
-  }
-  return FSPT_OK;
-}
-
-int fspt_temporal_draw(fspt_target *t, float exposure, float saturation, int denoised, uint8_t *out_rgba8) {
-  int rc = dn_enter(t, out_rgba8 != nullptr, "fspt_temporal_draw");
-  if (rc) return rc;
-  if (!t->tm_valid) { fspt_set_error("fspt_temporal_draw: no fspt_temporal_accumulate call yet"); return FSPT_E_STATE; }
-  if (denoised && !t->tm_dn_valid) { fspt_set_error("fspt_temporal_draw: no fspt_temporal_denoise call since the last fspt_temporal_accumulate / fspt_denoise"); return FSPT_E_STATE; }
-  size_t n = (size_t)t->W * t->H;
-  uint32_t *d = nullptr;
-  HIP_TRY(hipMalloc((void **)&d, n * 4));
-  hipError_t e = draw_launch(t, denoised ? t->dn_out : t->tm_hist[t->tm_cur], exposure, saturation, 0, 0.0f, 1.0f, d, t->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_rgba8, d, n * 4, hipMemcpyDeviceToHost, t->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  hipFree(d);
-  if (e != hipSuccess) { fspt_set_error("fspt_temporal_draw: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
-  return FSPT_OK;
-}
-
-int fspt_temporal_read_gbuffer(fspt_target *t, float *g_out, float *m_out) {
-  int rc = dn_enter(t, g_out || m_out, "fspt_temporal_read_gbuffer");
-  if (rc) return rc;
-  if (!t->tm_gm_valid) { fspt_set_error("fspt_temporal_read_gbuffer: no fspt_temporal_accumulate call yet"); return FSPT_E_STATE; }
-  const size_t px = (size_t)t->W * t->H;
-  if (g_out) HIP_TRY(hipMemcpyAsync(g_out, t->tm_g[t->tm_cur], px * 32, hipMemcpyDeviceToHost, t->stream));
-  if (m_out) HIP_TRY(hipMemcpyAsync(m_out, t->tm_m, px * 16, hipMemcpyDeviceToHost, t->stream));
-  HIP_TRY(hipStreamSynchronize(t->stream));
-  return FSPT_OK;
-}
-
-int fspt_temporal_last_ms(fspt_target *t, float ms[2]) {
-  if (!t || !ms) { fspt_set_error("fspt_temporal_last_ms: NULL argument"); return FSPT_E_INVALID; }
-  FLUSH_OR_RETURN(t);
-  if (!t->tm_timed) { fspt_set_error("fspt_temporal_last_ms: no fspt_temporal_accumulate call yet"); return FSPT_E_STATE; }
-  HIP_TRY(hipSetDevice(t->scene->device));
-  HIP_TRY(hipEventSynchronize(t->tm_ev[2]));
-  HIP_TRY(hipEventElapsedTime(&ms[0], t->tm_ev[0], t->tm_ev[1]));
-  HIP_TRY(hipEventElapsedTime(&ms[1], t->tm_ev[1], t->tm_ev[2]));
-  return FSPT_OK;
-}
-
-int fspt_temporal_eval(int device, const float *accum, const float *motion, const float *g, const float *hist, const float *g_prev,
-                       uint32_t W, uint32_t H, uint32_t n, const fspt_temporal_params *prm, float *out) {
-  if (!accum || !motion || !g || !out || (hist && !g_prev)) { fspt_set_error("fspt_temporal_eval: NULL argument"); return FSPT_E_INVALID; }
-  fspt_temporal_params q = TM_DEFAULTS;
-  if (prm) q = *prm;
-  int rc = tm_check_params(q, "fspt_temporal_eval");
-  if (rc) return rc;
-  if (n == 0) { fspt_set_error("fspt_temporal_eval: n must be >= 1"); return FSPT_E_INVALID; }
-  if ((rc = check_device(device))) return rc;
-  const size_t px = (size_t)W * H;
-  if (px == 0) return FSPT_OK;
-  HIP_TRY(hipSetDevice(device));
-  // one allocation, in float4: accum | motion | out | hist (px each) | g | g_prev (2 px each)
-  float4 *d = nullptr;
-  hipError_t e = hipMalloc((void **)&d, px * 16 * 8);
-  if (e == hipSuccess) e = hipMemcpy(d, accum, px * 16, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + px, motion, px * 16, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + 4 * px, g, px * 32, hipMemcpyHostToDevice);
-  if (e == hipSuccess && hist) e = hipMemcpy(d + 3 * px, hist, px * 16, hipMemcpyHostToDevice);
-  if (e == hipSuccess && hist) e = hipMemcpy(d + 6 * px, g_prev, px * 32, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    fspt::TemporalBP b{};
-    tm_fill_blend(b, q, W, H, (float)n);
-    b.accum = d; b.m = d + px; b.out = d + 2 * px; b.hist = d + 3 * px; b.g = d + 4 * px; b.g_prev = d + 6 * px;
-    b.has_hist = hist ? 1u : 0u;
-    e = fspt::launch_temporal_blend(b, nullptr);
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out, d + 2 * px, px * 16, hipMemcpyDeviceToHost);
-  hipFree(d);
-  if (e != hipSuccess) { fspt_set_error("fspt_temporal_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
-  return FSPT_OK;
-}
-
-// ---------------------------------------------------------------------------
-// SVGF variance guidance (k_temporal_blend<true> / k_svgf_variance / k_atrous<true>)
-// ---------------------------------------------------------------------------
-int fspt_temporal_set_moments(fspt_target *t, int on) {
-  int rc = dn_enter(t, true, "fspt_temporal_set_moments");
-  if (rc) return rc;
-  if (!on) {
-    HIP_TRY(hipStreamSynchronize(t->stream));
-    hipFree(t->tm_mom[0]); hipFree(t->tm_mom[1]); hipFree(t->tm_var);
-    t->tm_mom[0] = t->tm_mom[1] = nullptr; t->tm_var = nullptr;
-    t->tm_moments = t->tm_mom_valid = t->tm_var_valid = false;
-    return FSPT_OK;
-  }
-  if (t->n_shards > 1) { fspt_set_error("fspt_temporal_set_moments: sharded target"); return FSPT_E_STATE; }
-  if (t->tm_moments) return FSPT_OK;
-  const size_t px = (size_t)t->W * t->H;
-  for (int k = 0; k < 2; ++k) {
-    if (!t->tm_mom[k]) HIP_TRY(hipMalloc((void **)&t->tm_mom[k], px * 8));
-  }
-  t->tm_moments = true;
-  // off -> on drops the colour history with it, as fspt_temporal_reset does: moments of one frame beside a colour history
-  // of N would blend at the colour's n / (N + n), stay one sample's (M2 - M1 M1 = 0) and leave the guided filter a delta
-  t->tm_mom_valid = false; t->tm_var_valid = false;
-  t->tm_valid = false; t->tm_dn_valid = false;
-  return FSPT_OK;
-}
-
-static const fspt_denoise_params SV_DEFAULTS = {FSPT_SVGF_ITERATIONS, FSPT_SVGF_SIGMA_L, FSPT_SVGF_SIGMA_NORMAL, FSPT_SVGF_SIGMA_DEPTH};
-// k_svgf_variance, then the K variance-guided launches of k_atrous: hist -> out as dn_run, the variance from `var` into
-// the first iteration and in the .w lane between them; var_out (test hook; may be NULL): the last iteration's variance
-static hipError_t sv_run(const fspt_denoise_params &q, const float4 *hist, const float2 *mom, const float4 *feat, uint32_t W, uint32_t H,
-                         float n, float4 *const tmp[2], float4 *out, float *var, float *var_out, hipStream_t stream, hipEvent_t mid) {
-  const size_t px = (size_t)W * H;
-  fspt::SvgfVarP v{};
-  v.hist = hist; v.mom = mom; v.feat = feat; v.var = var;
-  v.W = W; v.H = H; v.n = n;
-  v.sn = q.sigma_normal; v.sz = q.sigma_depth;
-  hipError_t e = fspt::launch_svgf_variance(v, stream);
-  if (e == hipSuccess && mid) e = hipEventRecord(mid, stream);
-  if (e != hipSuccess) return e;
-  if (q.iterations == 0) {
-    if (var_out && (e = hipMemcpyAsync(var_out, var, px * 4, hipMemcpyDeviceToDevice, stream)) != hipSuccess) return e;
-    return hipMemcpyAsync(out, hist, px * 16, hipMemcpyDeviceToDevice, stream);
-  }
-  for (uint32_t k = 0; k < q.iterations; ++k) {
-    fspt::AtrousP p{};
-    p.src = k == 0 ? hist : tmp[(k - 1) & 1u];
-    p.dst = k + 1 == q.iterations ? out : tmp[k & 1u];
-    p.feat = feat;
-    p.W = W; p.H = H;
-    p.step = 1 << k;
-    p.demod = k == 0; p.remod = k + 1 == q.iterations;
-    p.sn = q.sigma_normal;
-    p.sz_step = std::ldexp(q.sigma_depth, (int)k);
-    p.var = var; p.sl = q.sigma_color;
-    p.var_dst = p.remod ? var_out : nullptr;
-    if ((e = fspt::launch_atrous_variance(p, stream)) != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-int fspt_temporal_denoise_variance(fspt_target *t, const fspt_denoise_params *prm, float *out) {
-  int rc = dn_enter(t, true, "fspt_temporal_denoise_variance");
-  if (rc) return rc;
-  fspt_denoise_params q = SV_DEFAULTS;
-  if (prm) q = *prm;
-  if ((rc = dn_check_params(q, "fspt_temporal_denoise_variance"))) return rc;
-  if (t->n_shards > 1) { fspt_set_error("fspt_temporal_denoise_variance: sharded target"); return FSPT_E_STATE; }
-  if (!t->tm_moments) { fspt_set_error("fspt_temporal_denoise_variance: moments are off (fspt_temporal_set_moments)"); return FSPT_E_STATE; }
-  if (!t->tm_valid || !t->tm_mom_valid) { fspt_set_error("fspt_temporal_denoise_variance: no fspt_temporal_accumulate call since the moments were switched on / the last reset"); return FSPT_E_STATE; }
-  if (!t->feat_valid) { fspt_set_error("fspt_temporal_denoise_variance: no fspt_features call yet"); return FSPT_E_STATE; }
-  const size_t px = (size_t)t->W * t->H;
-  if ((rc = dn_alloc(&t->dn_out, px * 16))) return rc;
-  t->dn_valid = false;
-  if (q.iterations > 1u && ((rc = dn_alloc(&t->dn_tmp[0], px * 16)) || (rc = dn_alloc(&t->dn_tmp[1], px * 16)))) return rc;
-  if (!t->tm_var) HIP_TRY(hipMalloc((void **)&t->tm_var, px * 4));
-  for (hipEvent_t &ev : t->sv_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
-  t->tm_dn_valid = false; t->tm_var_valid = false; t->sv_timed = false;
-  HIP_TRY(hipEventRecord(t->sv_ev[0], t->stream));
-  HIP_TRY(sv_run(q, t->tm_hist[t->tm_cur], t->tm_mom[t->tm_cur], t->feat, t->W, t->H, t->tm_n, t->dn_tmp, t->dn_out, t->tm_var, nullptr, t->stream, t->sv_ev[1]));
-  HIP_TRY(hipEventRecord(t->sv_ev[2], t->stream));
-  t->dn_valid = true; t->tm_dn_valid = true; t->tm_var_valid = true; t->sv_timed = true;
-  if (out) {
-    HIP_TRY(hipMemcpyAsync(out, t->dn_out, px * 16, hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipStreamSynchronize(t->stream));
-  }
-  return FSPT_OK;
-}
-
-int fspt_temporal_read_variance(fspt_target *t, float *var_out, float *mom_out) {
-  int rc = dn_enter(t, var_out || mom_out, "fspt_temporal_read_variance");
-  if (rc) return rc;
-  if (!t->tm_moments || !t->tm_valid || !t->tm_mom_valid) { fspt_set_error("fspt_temporal_read_variance: no fspt_temporal_accumulate call with moments on yet"); return FSPT_E_STATE; }
-  if (var_out && !t->tm_var_valid) { fspt_set_error("fspt_temporal_read_variance: no fspt_temporal_denoise_variance call since the last fspt_temporal_accumulate"); return FSPT_E_STATE; }
-  const size_t px = (size_t)t->W * t->H;
-  if (var_out) HIP_TRY(hipMemcpyAsync(var_out, t->tm_var, px * 4, hipMemcpyDeviceToHost, t->stream));
-  if (mom_out) HIP_TRY(hipMemcpyAsync(mom_out, t->tm_mom[t->tm_cur], px * 8, hipMemcpyDeviceToHost, t->stream));
-  HIP_TRY(hipStreamSynchronize(t->stream));
-  return FSPT_OK;
-}
-
-int fspt_svgf_last_ms(fspt_target *t, float ms[2]) {
-  if (!t || !ms) { fspt_set_error("fspt_svgf_last_ms: NULL argument"); return FSPT_E_INVALID; }
-  FLUSH_OR_RETURN(t);
-  if (!t->sv_timed) { fspt_set_error("fspt_svgf_last_ms: no fspt_temporal_denoise_variance call yet"); return FSPT_E_STATE; }
-  HIP_TRY(hipSetDevice(t->scene->device));
-  HIP_TRY(hipEventSynchronize(t->sv_ev[2]));
-  HIP_TRY(hipEventElapsedTime(&ms[0], t->sv_ev[0], t->sv_ev[1]));
-  HIP_TRY(hipEventElapsedTime(&ms[1], t->sv_ev[1], t->sv_ev[2]));
-  return FSPT_OK;
-}
-
-int fspt_svgf_eval(int device, const float *hist, const float *moments, const float *features, uint32_t W, uint32_t H, uint32_t n,
-                   const fspt_denoise_params *prm, float *out, float *var_in, float *var_out) {
-  if (!hist || !moments || !features || !out) { fspt_set_error("fspt_svgf_eval: NULL argument"); return FSPT_E_INVALID; }
-  fspt_denoise_params q = SV_DEFAULTS;
-  if (prm) q = *prm;
-  int rc = dn_check_params(q, "fspt_svgf_eval");
-  if (rc) return rc;
-  if (n == 0) { fspt_set_error("fspt_svgf_eval: n must be >= 1"); return FSPT_E_INVALID; }
-  if ((rc = check_device(device))) return rc;
-  const size_t px = (size_t)W * H;
-  if (px == 0) return FSPT_OK;
-  HIP_TRY(hipSetDevice(device));
-  // one allocation, in float4: hist | out | tmp[0] | tmp[1] (px each) | features (2 px) | moments (px / 2) | var, var' (px / 4 each)
-  float4 *d = nullptr;
-  hipError_t e = hipMalloc((void **)&d, px * 16 * 7 + 64);
-  float4 *const tmp[2] = {d + 2 * px, d + 3 * px};
-  float2 *const mom = (float2 *)(d + 6 * px);
-  float *const var = (float *)(mom + px), *const var2 = var + px;
-  if (e == hipSuccess) e = hipMemcpy(d, hist, px * 16, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + 4 * px, features, px * 32, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(mom, moments, px * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = sv_run(q, d, mom, d + 4 * px, W, H, (float)n, tmp, d + px, var, var2, nullptr, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out, d + px, px * 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && var_in) e = hipMemcpy(var_in, var, px * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && var_out) e = hipMemcpy(var_out, var2, px * 4, hipMemcpyDeviceToHost);
-  hipFree(d);
-  if (e != hipSuccess) { fspt_set_error("fspt_svgf_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
-  return FSPT_OK;
-}
-
-// ---------------------------------------------------------------------------
-// temporal history clamp (k_temporal_blend<*, true> / k_temporal_clamp)
-// ---------------------------------------------------------------------------
-static int cl_check_params(float fast_history, float sigma_scale, const char *fn) {
-  if (!(fast_history >= 1.0f && fast_history < INFINITY) || !(sigma_scale >= 0.0f)) {
-    fspt_set_error("%s: need a finite fast_history >= 1 and sigma_scale >= 0 (+inf: the clamp never binds)", fn);
-    return FSPT_E_INVALID;
-  }
-  return FSPT_OK;
-}
-
-int fspt_temporal_set_clamp(fspt_target *t, int on, float fast_history, float sigma_scale) {
-  if (!t) { fspt_set_error("fspt_temporal_set_clamp: NULL argument"); return FSPT_E_INVALID; }
-  int rc;
-  if (on && (rc = cl_check_params(fast_history, sigma_scale, "fspt_temporal_set_clamp"))) return rc;
-  if ((rc = dn_enter(t, true, "fspt_temporal_set_clamp"))) return rc;
-  if (!on) {
-    HIP_TRY(hipStreamSynchronize(t->stream));
-    hipFree(t->tm_fast[0]); hipFree(t->tm_fast[1]);
-    t->tm_fast[0] = t->tm_fast[1] = nullptr;
-    t->tm_clamp = t->tm_fast_valid = t->cl_timed = false;
-    return FSPT_OK;
-  }
-  if (t->n_shards > 1) { fspt_set_error("fspt_temporal_set_clamp: sharded target"); return FSPT_E_STATE; }
-  t->tm_fast_history = fast_history; t->tm_sigma_scale = sigma_scale; // (a change of the parameters alone keeps both histories)
-  if (t->tm_clamp) return FSPT_OK;
-  const size_t px = (size_t)t->W * t->H;
-  for (int k = 0; k < 2; ++k) {
-    if ((rc = dn_alloc(&t->tm_fast[k], px * 16))) return rc;
-  }
-  t->tm_clamp = true;
-  // off -> on drops the long history with it, as fspt_temporal_set_moments does: the two histories start together
-  t->tm_fast_valid = false;
-  t->tm_valid = false; t->tm_dn_valid = false;
-  t->tm_mom_valid = false; t->tm_var_valid = false;
-  return FSPT_OK;
-}
-
-int fspt_temporal_read_fast(fspt_target *t, float *out) {
-  int rc = dn_enter(t, out != nullptr, "fspt_temporal_read_fast");
-  if (rc) return rc;
-  if (!t->tm_clamp || !t->tm_valid || !t->tm_fast_valid) { fspt_set_error("fspt_temporal_read_fast: no fspt_temporal_accumulate call with the clamp on yet"); return FSPT_E_STATE; }
-  HIP_TRY(hipMemcpyAsync(out, t->tm_fast[t->tm_cur], (size_t)t->W * t->H * 16, hipMemcpyDeviceToHost, t->stream));
-  HIP_TRY(hipStreamSynchronize(t->stream));
-  return FSPT_OK;
-}
-
-int fspt_temporal_clamp_last_ms(fspt_target *t, float *ms) {
-  if (!t || !ms) { fspt_set_error("fspt_temporal_clamp_last_ms: NULL argument"); return FSPT_E_INVALID; }
-  FLUSH_OR_RETURN(t);
-  if (!t->cl_timed) { fspt_set_error("fspt_temporal_clamp_last_ms: no fspt_temporal_accumulate call with the clamp on yet"); return FSPT_E_STATE; }
-  HIP_TRY(hipSetDevice(t->scene->device));
-  HIP_TRY(hipEventSynchronize(t->cl_ev[1]));
-  HIP_TRY(hipEventElapsedTime(ms, t->cl_ev[0], t->cl_ev[1]));
-  return FSPT_OK;
-}
-
-int fspt_temporal_clamp_eval(int device, const float *hist, const float *fast, uint32_t W, uint32_t H, float sigma_scale,
-                             float *out, float *lo_out, float *hi_out) {
-  if (!hist || !fast || !out) { fspt_set_error("fspt_temporal_clamp_eval: NULL argument"); return FSPT_E_INVALID; }
-  int rc = cl_check_params(1.0f, sigma_scale, "fspt_temporal_clamp_eval");
-  if (rc) return rc;
-  if ((rc = check_device(device))) return rc;
-  const size_t px = (size_t)W * H;
-  if (px == 0) return FSPT_OK;
-  if (sigma_scale == INFINITY) { // the clamp never binds: no launch, the box is everything
-    std::memcpy(out, hist, px * 16);
-    for (size_t i = 0; i < px * 4; ++i) {
-      if (lo_out) lo_out[i] = (i & 3) == 3 ? 0.0f : -INFINITY;
-      if (hi_out) hi_out[i] = (i & 3) == 3 ? 0.0f : INFINITY;
-    }
-    return FSPT_OK;
-  }
-  HIP_TRY(hipSetDevice(device));
-  // one allocation, in float4: hist | fast | out | lo | hi (px each)
-  float4 *d = nullptr;
-  hipError_t e = hipMalloc((void **)&d, px * 16 * 5);
-  if (e == hipSuccess) e = hipMemcpy(d, hist, px * 16, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + px, fast, px * 16, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    fspt::ClampP c{};
-    c.hist = d; c.fast = d + px; c.out = d + 2 * px; c.lo = d + 3 * px; c.hi = d + 4 * px;
-    c.W = W; c.H = H; c.sigma_scale = sigma_scale;
-    e = fspt::launch_temporal_clamp(c, nullptr);
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out, d + 2 * px, px * 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && lo_out) e = hipMemcpy(lo_out, d + 3 * px, px * 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && hi_out) e = hipMemcpy(hi_out, d + 4 * px, px * 16, hipMemcpyDeviceToHost);
-  hipFree(d);
-  if (e != hipSuccess) { fspt_set_error("fspt_temporal_clamp_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
-  return FSPT_OK;
-}
-
-// ---------------------------------------------------------------------------
-// auto-exposure (k_exposure_histogram / k_exposure_resolve / k_draw_auto)
-// ---------------------------------------------------------------------------
-static int ax_check_params(const fspt_exposure_params *p, fspt::ExposureP &q, const char *fn) {
-  static const fspt_exposure_params dflt = {FSPT_EXPOSURE_KEY, FSPT_EXPOSURE_LOW, FSPT_EXPOSURE_HIGH, FSPT_EXPOSURE_ADAPT_UP, FSPT_EXPOSURE_ADAPT_DOWN,
-                                            FSPT_EXPOSURE_MIN_LOG2, FSPT_EXPOSURE_MAX_LOG2};
-  if (!p) p = &dflt;
-  const float f[7] = {p->key, p->low, p->high, p->adapt_up, p->adapt_down, p->min_log2, p->max_log2};
-  bool ok = true;
-  for (float v : f) ok = ok && std::isfinite(v);
-  ok = ok && p->key > 0.0f && p->low >= 0.0f && p->low < p->high && p->high <= 1.0f && p->adapt_up > 0.0f && p->adapt_up <= 1.0f &&
-       p->adapt_down > 0.0f && p->adapt_down <= 1.0f && p->min_log2 <= p->max_log2;
-  if (!ok) {
-    fspt_set_error("%s: need finite parameters with key > 0, 0 <= low < high <= 1, adapt_up and adapt_down in (0, 1], min_log2 <= max_log2", fn);
-    return FSPT_E_INVALID;
-  }
-  q = fspt::ExposureP{p->key, p->low, p->high, p->adapt_up, p->adapt_down, p->min_log2, p->max_log2};
-  return FSPT_OK;
-}
-static const fspt::ExposureState AX_FIRST = {1.0f, 0u, 0u, 0u, 0.0, 0.0}; // never metered: exposure 1, nothing to adapt from
-static_assert(sizeof(fspt::ExposureState) == sizeof(fspt_exposure_state) && sizeof(fspt_exposure_state) == 32, "fspt_exposure_state is the device's record");
-
-int fspt_exposure_set_form(int form) {
-  if (form != 0 && form != 1) { fspt_set_error("fspt_exposure_set_form: form must be 0 or 1"); return FSPT_E_INVALID; }
-  fspt::g_exposure_form = form;
-  return FSPT_OK;
-}
-
-int fspt_target_set_auto_exposure(fspt_target *t, int on, const fspt_exposure_params *p) {
-  if (!t) { fspt_set_error("fspt_target_set_auto_exposure: NULL argument"); return FSPT_E_INVALID; }
-  fspt::ExposureP q{};
-  int rc;
-  if (on && (rc = ax_check_params(p, q, "fspt_target_set_auto_exposure"))) return rc;
-  if ((rc = dn_enter(t, true, "fspt_target_set_auto_exposure"))) return rc;
-  if (!on) {
-    HIP_TRY(hipStreamSynchronize(t->stream)); // (dn_enter joined a present: nothing reads the state any more)
-    hipFree(t->ax_hist);
-    t->ax_hist = nullptr; t->ax_state = nullptr;
-    t->ax_on = t->ax_timed = false;
-    return FSPT_OK;
-  }
-  if (t->n_shards > 1) { fspt_set_error("fspt_target_set_auto_exposure: sharded target"); return FSPT_E_STATE; }
-  t->ax_p = q; // (a change of the parameters alone keeps the adapted state)
-  if (t->ax_on) return FSPT_OK;
-  const size_t hist_bytes = fspt::EXPOSURE_BINS * sizeof(uint32_t);
-  if (!t->ax_hist) HIP_TRY(hipMalloc((void **)&t->ax_hist, hist_bytes + sizeof(fspt::ExposureState)));
-  t->ax_state = (fspt::ExposureState *)(t->ax_hist + fspt::EXPOSURE_BINS);
-  HIP_TRY(hipMemsetAsync(t->ax_hist, 0, hist_bytes, t->stream));
-  HIP_TRY(hipMemcpyAsync(t->ax_state, &AX_FIRST, sizeof AX_FIRST, hipMemcpyHostToDevice, t->stream));
-  HIP_TRY(hipStreamSynchronize(t->stream));
-  for (hipEvent_t &ev : t->ax_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
-  t->ax_on = true; t->ax_timed = false;
-  return FSPT_OK;
-}
-
-int fspt_exposure_reset(fspt_target *t) {
-  int rc = dn_enter(t, true, "fspt_exposure_reset");
-  if (rc) return rc;
-  if (!t->ax_on) { fspt_set_error("fspt_exposure_reset: auto-exposure is off"); return FSPT_E_STATE; }
-  HIP_TRY(hipMemcpyAsync(t->ax_state, &AX_FIRST, sizeof AX_FIRST, hipMemcpyHostToDevice, t->stream));
-  HIP_TRY(hipStreamSynchronize(t->stream));
-  return FSPT_OK;
-}
-
-int fspt_exposure_get(fspt_target *t, float *exposure, float *log2_mean, uint32_t *metered) {
-  int rc = dn_enter(t, exposure || log2_mean || metered, "fspt_exposure_get");
-  if (rc) return rc;
-  if (!t->ax_on) { fspt_set_error("fspt_exposure_get: auto-exposure is off"); return FSPT_E_STATE; }
-  fspt::ExposureState s;
-  HIP_TRY(hipMemcpyAsync(&s, t->ax_state, sizeof s, hipMemcpyDeviceToHost, t->stream));
-  HIP_TRY(hipStreamSynchronize(t->stream));
-  if (exposure) *exposure = s.exposure;
-  if (log2_mean) *log2_mean = (float)s.log2_mean;
-  if (metered) *metered = s.metered;
-  return FSPT_OK;
-}
-
-int fspt_exposure_last_ms(fspt_target *t, float ms[2]) {
-  if (!t || !ms) { fspt_set_error("fspt_exposure_last_ms: NULL argument"); return FSPT_E_INVALID; }
-  FLUSH_OR_RETURN(t);
-  if (!t->ax_timed) { fspt_set_error("fspt_exposure_last_ms: no draw with auto-exposure on yet"); return FSPT_E_STATE; }
-  HIP_TRY(hipSetDevice(t->scene->device));
-  HIP_TRY(hipEventSynchronize(t->ax_ev[2]));
-  HIP_TRY(hipEventElapsedTime(&ms[0], t->ax_ev[0], t->ax_ev[1]));
-  HIP_TRY(hipEventElapsedTime(&ms[1], t->ax_ev[1], t->ax_ev[2]));
-  return FSPT_OK;
-}
-
-int fspt_exposure_last_draw_ms(fspt_target *t, float *ms) {
-  if (!t || !ms) { fspt_set_error("fspt_exposure_last_draw_ms: NULL argument"); return FSPT_E_INVALID; }
-  FLUSH_OR_RETURN(t);
-  if (!t->ax_timed) { fspt_set_error("fspt_exposure_last_draw_ms: no draw with auto-exposure on yet"); return FSPT_E_STATE; }
-  HIP_TRY(hipSetDevice(t->scene->device));
-  HIP_TRY(hipEventSynchronize(t->ax_ev[3]));
-  HIP_TRY(hipEventElapsedTime(ms, t->ax_ev[2], t->ax_ev[3]));
-  return FSPT_OK;
-}
-
-int fspt_exposure_eval(int device, const float *rgba, uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const fspt_exposure_params *p,
-                       const fspt_exposure_state *prev, uint32_t *hist_out, fspt_exposure_state *state_out) {
-  if (!rgba || !hist_out || !state_out) { fspt_set_error("fspt_exposure_eval: NULL argument"); return FSPT_E_INVALID; }
-  fspt::ExposureP q{};
-  int rc = ax_check_params(p, q, "fspt_exposure_eval");
-  if (rc) return rc;
-  if (vw == 0 && vh == 0) { vw = W; vh = H; } // (as fspt_target_set_viewport: 0, 0 = the whole image)
-  if (W == 0 || H == 0 || vw == 0 || vh == 0 || vw > W || vh > H || (uint64_t)W * H > 0xFFFFFFFFull) {
-    fspt_set_error("fspt_exposure_eval: need 1 <= vw <= W, 1 <= vh <= H and fewer than 2^32 pixels"); return FSPT_E_INVALID;
-  }
-  if ((rc = check_device(device))) return rc;
-  HIP_TRY(hipSetDevice(device));
-  const size_t px = (size_t)W * H, hist_bytes = fspt::EXPOSURE_BINS * sizeof(uint32_t);
-  // one allocation: image | histogram | state
-  char *d = nullptr;
-  hipError_t e = hipMalloc((void **)&d, px * 16 + hist_bytes + sizeof(fspt::ExposureState));
-  uint32_t *hist = (uint32_t *)(d + px * 16);
-  fspt::ExposureState *state = (fspt::ExposureState *)(d + px * 16 + hist_bytes);
-  if (e == hipSuccess) e = hipMemcpy(d, rgba, px * 16, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(hist, 0, hist_bytes);
-  if (e == hipSuccess) e = hipMemcpy(state, prev ? (const void *)prev : (const void *)&AX_FIRST, sizeof(fspt::ExposureState), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = fspt::launch_exposure_histogram((const float4 *)d, W, vw, vh, hist, fspt::g_exposure_form, nullptr);
-  if (e == hipSuccess) e = hipMemcpy(hist_out, hist, hist_bytes, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = fspt::launch_exposure_resolve(hist, state, q, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(state_out, state, sizeof(fspt::ExposureState), hipMemcpyDeviceToHost);
-  // reserved = the counts the resolve left behind, summed: 0 (it clears the histogram for the next metering)
-  uint32_t left[fspt::EXPOSURE_BINS];
-  if (e == hipSuccess) e = hipMemcpy(left, hist, hist_bytes, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) { uint32_t any = 0; for (uint32_t c : left) any |= c; state_out->reserved = any; }
-  hipFree(d);
-  if (e != hipSuccess) { fspt_set_error("fspt_exposure_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
-  return FSPT_OK;
-}
-
-// ---------------------------------------------------------------------------
-// bloom (k_bloom_down / k_bloom_up / k_bloom_tail / k_draw_bloom)
-// ---------------------------------------------------------------------------
-static int bl_check_params(const fspt_bloom_params *p, fspt::BloomP &q, const char *fn) {
-  static const fspt_bloom_params dflt = {FSPT_BLOOM_INTENSITY, FSPT_BLOOM_SCATTER, FSPT_BLOOM_LEVELS};
-  if (!p) p = &dflt;
-  if (!(std::isfinite(p->intensity) && std::isfinite(p->scatter) && p->intensity >= 0.0f && p->intensity <= 1.0f && p->scatter >= 0.0f &&
-        p->scatter <= 1.0f && p->levels >= 1u && p->levels <= (uint32_t)FSPT_BLOOM_MAX_LEVELS)) {
-    fspt_set_error("%s: need finite intensity and scatter in [0, 1] and levels in [1, %d]", fn, FSPT_BLOOM_MAX_LEVELS);
-    return FSPT_E_INVALID;
-  }
-  q = fspt::BloomP{p->intensity, p->scatter, p->levels};
-  return FSPT_OK;
-}
-static_assert(FSPT_BLOOM_MAX_LEVELS == fspt::BLOOM_MAX_LEVELS && FSPT_BLOOM_TAIL_TEXELS == fspt::BLOOM_TAIL_TEXELS, "fspt_tuning.h names the device's constants");
-
-int fspt_bloom_set_form(int form) {
-  if (form != 0 && form != 1) { fspt_set_error("fspt_bloom_set_form: form must be 0 or 1"); return FSPT_E_INVALID; }
-  fspt::g_bloom_form = form;
-  return FSPT_OK;
-}
-
-int fspt_bloom_set_tail_texels(uint32_t n) {
-  fspt::g_bloom_tail_texels = n ? n : fspt::BLOOM_TAIL_TEXELS;
-  return FSPT_OK;
-}
-
-uint64_t fspt_bloom_texels(uint32_t vw, uint32_t vh, uint32_t levels, uint32_t *n_out) {
-  if (vw == 0 || vh == 0) { if (n_out) *n_out = 0; return 0; }
-  const fspt::BloomPlan q = fspt::bloom_plan(vw, vh, levels, 0, 0);
-  if (n_out) *n_out = q.n;
-  return q.texels;
-}
-
-int fspt_target_set_bloom(fspt_target *t, int on, const fspt_bloom_params *p) {
-  if (!t) { fspt_set_error("fspt_target_set_bloom: NULL argument"); return FSPT_E_INVALID; }
-  fspt::BloomP q{};
-  int rc;
-  if (on && (rc = bl_check_params(p, q, "fspt_target_set_bloom"))) return rc;
-  if ((rc = dn_enter(t, true, "fspt_target_set_bloom"))) return rc;
-  if (!on) {
-    HIP_TRY(hipStreamSynchronize(t->stream)); // (dn_enter joined a present: nothing reads the pyramid any more)
-    hipFree(t->bl_pyr);
-    t->bl_pyr = nullptr;
-    t->bl_on = t->bl_timed = false;
-    return FSPT_OK;
-  }
-  if (t->n_shards > 1) { fspt_set_error("fspt_target_set_bloom: sharded target"); return FSPT_E_STATE; }
-  t->bl_p = q; // (a change of the parameters alone keeps the allocation: it is sized for W x H at the most levels)
-  if (t->bl_on) return FSPT_OK;
-  const size_t texels = fspt::bloom_plan(t->W, t->H, fspt::BLOOM_MAX_LEVELS, 0, 0).texels;
-  if (!t->bl_pyr) HIP_TRY(hipMalloc((void **)&t->bl_pyr, (texels ? texels : 1) * sizeof(float4)));
-  for (hipEvent_t &ev : t->bl_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
-  t->bl_on = true; t->bl_timed = false;
-  return FSPT_OK;
-}
-
-int fspt_target_get_bloom(fspt_target *t, int *on, fspt_bloom_params *p) {
-  if (!t || !on || !p) { fspt_set_error("fspt_target_get_bloom: NULL argument"); return FSPT_E_INVALID; }
-  *on = t->bl_on ? 1 : 0;
-  if (t->bl_on) *p = fspt_bloom_params{t->bl_p.intensity, t->bl_p.scatter, t->bl_p.levels};
-  else *p = fspt_bloom_params{FSPT_BLOOM_INTENSITY, FSPT_BLOOM_SCATTER, FSPT_BLOOM_LEVELS};
-  return FSPT_OK;
-}
-
-int fspt_bloom_last_ms(fspt_target *t, float ms[4]) {
-  if (!t || !ms) { fspt_set_error("fspt_bloom_last_ms: NULL argument"); return FSPT_E_INVALID; }
-  FLUSH_OR_RETURN(t);
-  if (!t->bl_on || !t->bl_timed) { fspt_set_error("fspt_bloom_last_ms: no bloomed draw yet"); return FSPT_E_STATE; }
-  HIP_TRY(hipSetDevice(t->scene->device));
-  HIP_TRY(hipEventSynchronize(t->bl_ev[4]));
-  for (int k = 0; k < 4; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], t->bl_ev[k], t->bl_ev[k + 1]));
-  return FSPT_OK;
-}
-
-int fspt_bloom_eval(int device, const float *rgba, uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const fspt_bloom_params *p, uint32_t *n_out,
-                    float *down_out, float *up_out, float *bloom_out, float *mix_out) {
-  if (!rgba) { fspt_set_error("fspt_bloom_eval: NULL argument"); return FSPT_E_INVALID; }
-  fspt::BloomP bp{};
-  int rc = bl_check_params(p, bp, "fspt_bloom_eval");
-  if (rc) return rc;
-  if (vw == 0 && vh == 0) { vw = W; vh = H; } // (as fspt_target_set_viewport: 0, 0 = the whole image)
-  if (W == 0 || H == 0 || vw == 0 || vh == 0 || vw > W || vh > H || (uint64_t)W * H > 0x7FFFFFFFull) {
-    fspt_set_error("fspt_bloom_eval: need 1 <= vw <= W, 1 <= vh <= H and fewer than 2^31 pixels"); return FSPT_E_INVALID;
-  }
-  if ((rc = check_device(device))) return rc;
-  HIP_TRY(hipSetDevice(device));
-  const fspt::BloomPlan q = fspt::bloom_plan(vw, vh, bp.levels, fspt::g_bloom_form, fspt::g_bloom_tail_texels);
-  if (n_out) *n_out = q.n;
-  const size_t px = (size_t)W * H, vpx = (size_t)vw * vh;
-  if (q.n == 0) { // the plain draw: nothing is built, the draw multiplies the source by the exposure
-    if (mix_out) memcpy(mix_out, rgba, px * 16);
-    if (bloom_out) for (uint32_t y = 0; y < vh; ++y) memcpy(bloom_out + (size_t)y * vw * 4, rgba + (size_t)y * W * 4, (size_t)vw * 16);
-    return FSPT_OK;
-  }
-  // one allocation: image | pyramid (U in the end) | the D levels as the down chain left them | B | c'
-  float4 *d = nullptr;
-  hipError_t e = hipMalloc((void **)&d, (px + 2 * q.texels + vpx + px) * sizeof(float4));
-  float4 *pyr = d + px, *snap = pyr + q.texels, *B = snap + q.texels, *mix = B + vpx;
-  if (e == hipSuccess) e = hipMemcpy(d, rgba, px * 16, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = fspt::launch_bloom_chain(d, W, q, bp.scatter, pyr, nullptr, snap, pyr, nullptr);
-  const fspt::BloomDraw bl{pyr + q.off[1], q.w[1], q.h[1], vw, vh, bp.intensity};
-  if (e == hipSuccess) e = fspt::launch_bloom_mix(d, W, H, bl, B, mix, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess && down_out) e = hipMemcpy(down_out, snap, q.texels * 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && up_out) e = hipMemcpy(up_out, pyr, q.texels * 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && bloom_out) e = hipMemcpy(bloom_out, B, vpx * 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && mix_out) e = hipMemcpy(mix_out, mix, px * 16, hipMemcpyDeviceToHost);
-  hipFree(d);
-  if (e != hipSuccess) { fspt_set_error("fspt_bloom_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
   return FSPT_OK;
 }
 
@@ -2797,19 +1926,17 @@ int fspt_sampler_eval(int device, uint32_t seed, const uint32_t *pixel, const ui
   if (rc) return rc;
   if (n == 0) return FSPT_OK;
   const size_t bytes = (size_t)n * 4;
-  uint32_t *d_in = nullptr;
-  float *d_out = nullptr;
-  hipError_t e = hipMalloc((void **)&d_in, 3 * bytes);
-  if (e == hipSuccess) e = hipMalloc((void **)&d_out, bytes);
-  if (e == hipSuccess) e = hipMemcpy(d_in, pixel, bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_in + n, sample, bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_in + 2 * (size_t)n, dim, bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = fspt::launch_sampler_eval(seed, d_in, d_in + n, d_in + 2 * (size_t)n, n, d_out, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
-  hipFree(d_in); hipFree(d_out);
-  if (e != hipSuccess) { fspt_set_error("fspt_sampler_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
-  return FSPT_OK;
+  // one allocation, in words: pixel | sample | dim | out (n each)
+  Staging s(4 * bytes);
+  if (!s.ok()) return s.done("fspt_sampler_eval");
+  uint32_t *const d = (uint32_t *)s.base;
+  s.up(d, pixel, bytes);
+  s.up(d + n, sample, bytes);
+  s.up(d + 2 * (size_t)n, dim, bytes);
+  if (s.ok()) s.e = fspt::launch_sampler_eval(seed, d, d + n, d + 2 * (size_t)n, n, (float *)(d + 3 * (size_t)n), nullptr);
+  s.sync();
+  s.down(out, d + 3 * (size_t)n, bytes);
+  return s.done("fspt_sampler_eval");
 }
 
 int fspt_math_eval(int device, int op, const float *a, const float *b, uint32_t n, float *out) {
@@ -2817,44 +1944,16 @@ int fspt_math_eval(int device, int op, const float *a, const float *b, uint32_t 
   int rc = check_device(device);
   if (rc) return rc;
   if (n == 0) return FSPT_OK;
-  float *da = nullptr, *db = nullptr, *dout = nullptr;
-  hipError_t e = hipMalloc((void **)&da, (size_t)n * 4);
-  if (e == hipSuccess) e = hipMalloc((void **)&dout, (size_t)n * 4);
-  if (e == hipSuccess && b) e = hipMalloc((void **)&db, (size_t)n * 4);
-  if (e == hipSuccess) e = hipMemcpy(da, a, (size_t)n * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess && b) e = hipMemcpy(db, b, (size_t)n * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = fspt::launch_math(op, da, db, n, dout, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost);
-  hipFree(da); hipFree(db); hipFree(dout);
-  if (e != hipSuccess) { fspt_set_error("fspt_math_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
-  return FSPT_OK;
-}
-
-
-int fspt_denoise_eval(int device, const float *accum, const float *features, uint32_t W, uint32_t H,
-                      const fspt_denoise_params *prm, float *out) {
-  if (!accum || !features || !out) { fspt_set_error("fspt_denoise_eval: NULL argument"); return FSPT_E_INVALID; }
-  int rc = check_device(device);
-  if (rc) return rc;
-  fspt_denoise_params q = {FSPT_DENOISE_ITERATIONS, FSPT_DENOISE_SIGMA_COLOR, FSPT_DENOISE_SIGMA_NORMAL, FSPT_DENOISE_SIGMA_DEPTH};
-  if (prm) q = *prm;
-  if ((rc = dn_check_params(q, "fspt_denoise_eval"))) return rc;
-  const size_t px = (size_t)W * H;
-  if (px == 0) return FSPT_OK;
-  HIP_TRY(hipSetDevice(device));
-  // one allocation: accum, out, tmp[0], tmp[1] (W*H float4 each), then the features (2 W*H float4)
-  float4 *d = nullptr;
-  hipError_t e = hipMalloc((void **)&d, px * 16 * 6);
-  float4 *const tmp[2] = {d + 2 * px, d + 3 * px};
-  if (e == hipSuccess) e = hipMemcpy(d, accum, px * 16, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + 4 * px, features, px * 32, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = dn_run(q, d, d + 4 * px, W, H, tmp, d + px, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out, d + px, px * 16, hipMemcpyDeviceToHost);
-  hipFree(d);
-  if (e != hipSuccess) { fspt_set_error("fspt_denoise_eval: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
-  return FSPT_OK;
+  // one allocation, in floats: a | out | b (n each; no b: the kernel gets NULL)
+  Staging s((size_t)n * 12);
+  if (!s.ok()) return s.done("fspt_math_eval");
+  float *const da = (float *)s.base, *const dout = da + n, *const db = b ? dout + n : nullptr;
+  s.up(da, a, (size_t)n * 4);
+  s.up(db, b, (size_t)n * 4);
+  if (s.ok()) s.e = fspt::launch_math(op, da, db, n, dout, nullptr);
+  s.sync();
+  s.down(out, dout, (size_t)n * 4);
+  return s.done("fspt_math_eval");
 }
 
 } // extern "C"

@@ -1,6 +1,7 @@
 // fspt_internal.hpp - what the translation units of libfspt's host side share: the scene and target objects behind the
 // opaque handles of include/fspt.h, the tuning defaults, and the helpers that cross file boundaries.
-//   fspt_api.cpp           scene and target objects, every entry point that is not a scheduler (include/fspt.h order)
+//   fspt_api.cpp           scene and target objects, every entry point that is neither a scheduler nor the image chain (include/fspt.h order)
+//   fspt_post.cpp          the image chain behind the accumulator: draw, denoiser, temporal stages, auto-exposure, bloom
 //   fspt_sched_batch.cpp   the batch scheduler of the wavefront pipeline (render_wavefront) and its path state
 //   fspt_sched_stream.cpp  the stream scheduler (render_stream): a fixed pool of live paths
 //   fspt_multi.cpp         one frame over several devices (fspt_multi_*), tile pack / unpack, the optional RCCL exchange
@@ -366,6 +367,33 @@ int flush_pending(fspt_target *t);     // execute the recorded two-call ticks (a
 int present_join(fspt_target *t);      // wait for everything fspt_present enqueued on the lane streams
 int materialise_rays(fspt_target *t);  // the ray buffers as the most recent fspt_camera call left them
 uint32_t clamp_bounces(uint32_t nb);
+// ---- fspt_post.cpp
+// k_draw of `src` on `st` into `out` (device memory), through the target's auto-exposure and bloom when they are on
+hipError_t draw_launch(fspt_target *t, const float4 *src, float exposure, float saturation, int denoise, float max_sigma,
+                       float scale, uint32_t *out, hipStream_t st);
+void post_release(fspt_target *t); // fspt_target_destroy: the image chain's buffers and events (the streams are idle)
+// ---- the *_eval test hooks (fspt_api.cpp, fspt_post.cpp)
+// A hook's device memory: ONE allocation, freed when the scope ends.  The first HIP error sticks in `e`: up, down and sync
+// are no-ops behind it, and a hook launches with `if (s.ok()) s.e = launch(..)`.  `base` is NULL when the allocation
+// failed: a hook returns done() at once then, before it forms a pointer into the block.  sync() stands apart from done()
+// because the downloads lie between them.
+struct Staging {
+  char *base = nullptr;
+  hipError_t e;
+  explicit Staging(size_t bytes) { e = hipMalloc((void **)&base, bytes); if (e != hipSuccess) base = nullptr; }
+  ~Staging() { hipFree(base); }
+  Staging(const Staging &) = delete;
+  Staging &operator=(const Staging &) = delete;
+  bool ok() const { return e == hipSuccess; }
+  void up(void *dst, const void *host, size_t bytes) { if (ok() && host) e = hipMemcpy(dst, host, bytes, hipMemcpyHostToDevice); }
+  void down(void *host, const void *src, size_t bytes) { if (ok() && host) e = hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost); }
+  void sync() { if (ok()) e = hipDeviceSynchronize(); }
+  int done(const char *fn) const {
+    if (ok()) return FSPT_OK;
+    fspt_set_error("%s: %s", fn, hipGetErrorString(e));
+    return FSPT_E_HIP;
+  }
+};
 // ---- fspt_sched_batch.cpp
 void fill_trace_params(fspt_target *t, fspt::TraceP &p);
 uint64_t susp_need(const fspt_target *t, uint64_t max_paths, uint32_t *stride_out, size_t *recs_out);

@@ -261,6 +261,48 @@ def test_states_reset_and_reenable(small_scene, camera):
     pt.close()
 
 
+def test_dropping_the_history_drops_everything_that_describes_it(small_scene, camera):
+    """The moments, the variance, the fast history and the denoised frame mean something only beside the history they were
+    made from: whichever call drops the history - the other mode switched on, or a reset - every reader of them refuses
+    with FSPT_E_STATE until the next accumulate, which starts all of them together."""
+    from fspt_amd import FsptError
+    pt = make_pt(small_scene, 16, 12, camera)
+    pt.features(2, 1)
+
+    def frame():
+        pt.clear(); pt.render(2)
+        return pt.temporal_accumulate()
+
+    def all_refuse():
+        for read in (pt.temporal_fast, lambda: pt.temporal_draw(1.0, 1.0, denoised=True),
+                     lambda: pt.temporal_denoise(variance=True), pt.temporal_variance):
+            with pytest.raises(FsptError) as e:
+                read()
+            assert e.value.code == -6  # FSPT_E_STATE
+
+    def restarts():  # a first frame again: every length is the frame's 2 samples
+        assert np.all(frame()[..., 3] == 2.0) and np.all(pt.temporal_fast()[..., 3] == 2.0)
+
+    # A: the clamp on, a history, a denoised frame of it; then the moments on
+    pt.temporal_set_clamp(True)
+    frame(); pt.temporal_denoise(iterations=1); pt.temporal_fast()
+    pt.temporal_set_moments(True)
+    all_refuse()
+    restarts()
+    # C: both modes on, everything valid; then a reset
+    pt.temporal_denoise(variance=True); pt.temporal_variance(); pt.temporal_draw(1.0, 1.0, denoised=True)
+    pt.temporal_reset()
+    all_refuse()
+    restarts()
+    # B: the moments on, a history and its variance; then the clamp on
+    pt.temporal_set_clamp(False)
+    frame(); pt.temporal_denoise(variance=True); pt.temporal_variance()
+    pt.temporal_set_clamp(True)
+    all_refuse()
+    restarts()
+    pt.close()
+
+
 def test_no_memory_growth(small_scene, camera):
     from fspt_amd import device_memory
     pt = make_pt(small_scene, 128, 96, camera)

@@ -1,5 +1,6 @@
-// fspt_device.hpp — device data layouts + launch parameter blocks shared by
-// fspt_kernels.hip (device code) and fspt_api.cpp (host side of the C ABI).
+// fspt_device.hpp — device data layouts, launch parameter blocks and launcher declarations shared by the two kernel
+// files (fspt_kernels.hip: whatever reads a DScene; fspt_post.hip: whatever reads only images) and the host side of the
+// C ABI (fspt_api.cpp, fspt_post.cpp, the schedulers, fspt_multi.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -311,9 +312,6 @@ struct WfP {
 
 // kernel classes; also the slots of fspt_last_stage_ms
 enum { WF_K_PRIMARY = 0, WF_K_TRACE = 1, WF_K_LOGIC = 2, WF_K_RESOLVE = 3, WF_K_TAIL = 4, WF_K_KINDS = 5 /* timed classes */, WF_K_PLAN = 6 /* not timed */, WF_K_CARRY = 7 /* not timed */ };
-// count: 0 = production kernels; 1 = counting variants doing the reference's work (NEE shadow rays traced to the closest
-// hit, tracer.fs:501); 2 = counting variants of the production work (shadow rays stop at the first hit)
-hipError_t launch_wf(int kernel, const WfP &p, int count, int num_cus, hipStream_t stream);
 
 // multi-device read-out: a shard's own pixels <-> a packed array in work-index order (work_to_pixel)
 struct TilePackP {
@@ -324,7 +322,6 @@ struct TilePackP {
   uint32_t shard, n_shards, tile, tiles_x, tiles_y, n_owned_tiles;
   const uint32_t *tile_list; // always NULL (work_to_pixel reads it)
 };
-hipError_t launch_tile_pack(const TilePackP &p, bool unpack, hipStream_t stream);
 
 // guided denoiser (fspt_denoise.*)
 struct FeatureP {
@@ -350,9 +347,6 @@ struct AtrousP {
   float sl;          // sigma_l in standard deviations (INFINITY: w_l = 1); sc_step is unused
   float *var_dst;    // the LAST iteration's output variance, which its (a u, 1) has no lane for (test hook), or NULL
 };
-hipError_t launch_features(const FeatureP &p, hipStream_t stream);
-hipError_t launch_atrous(const AtrousP &p, hipStream_t stream);
-hipError_t launch_atrous_variance(const AtrousP &p, hipStream_t stream);
 
 // temporal accumulation (fspt_temporal_*)
 constexpr int MOTION_FLOATS = 9;      // motion-origin snapshot: floats 0-8 (v1 e1 e2) of a slot's hit record
@@ -412,10 +406,6 @@ struct ClampP {
   uint32_t W, H;
   float sigma_scale;   // finite (+inf never launches)
 };
-hipError_t launch_temporal_gbuffer(const TemporalGP &p, hipStream_t stream);
-hipError_t launch_temporal_blend(const TemporalBP &p, hipStream_t stream); // (p.mom_out != NULL: the moments instantiations; p.fast_out != NULL: the fast-history ones)
-hipError_t launch_temporal_clamp(const ClampP &p, hipStream_t stream);
-hipError_t launch_svgf_variance(const SvgfVarP &p, hipStream_t stream);
 
 // adaptive sampling (fspt_render_adaptive): after n ticks, with the snapshot S taken after m < n ticks
 struct AdaptiveP {
@@ -433,28 +423,7 @@ struct AdaptiveP {
   uint32_t min_ticks, max_ticks;
   double target;
 };
-// one workgroup per active tile: E_T = mean over the tile's viewport pixels and 3 channels of m (I - S)^2 / ((n - m)(I^2 + 0.01))
-hipError_t launch_adaptive_error(const AdaptiveP &p, hipStream_t stream);
-// one workgroup: retire the tiles of list_in whose E_T decides it, list the rest in list_out (same order), *n_out
-hipError_t launch_adaptive_select(const AdaptiveP &p, hipStream_t stream);
 
-// launchers (fspt_kernels.hip)
-hipError_t launch_trace(const TraceP &p, bool gen_rays, bool count, int num_cus, hipStream_t stream);
-size_t wf_max_stack_entries(); // deepest tree (entries per lane) whose traversal stacks fit the LDS of every kernel
-hipError_t launch_camera(uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const CameraP &cam, float rand_base, float4 *pos, float4 *dir,
-                         hipStream_t stream, uint32_t sampler = 0, uint32_t smp_seed = 0, uint32_t sample = 0);
-// the Sobol sampler's value for n (pixel, sample, dim) triples (fspt_sampler_eval)
-hipError_t launch_sampler_eval(uint32_t seed, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim, uint32_t n,
-                               float *out, hipStream_t stream);
-hipError_t launch_intersect(const IntersectP &p, hipStream_t stream);
-// light table build (fspt_target_set_lights): w[i] for the triangle in leaf slot slots[i] (DESIGN 8.3); with rec != NULL
-// also its 64-byte light record rec[4 i .. 4 i + 3]
-hipError_t launch_light_weights(const DScene &S, const uint32_t *slots, uint32_t n, float *w, float4 *rec, hipStream_t stream);
-// fspt_light_sample_eval: 10 floats per query (ro.xyz, n.xyz, u0..u3) -> entry index, 8 floats (x.xyz, pdf_L, Le.rgb, n . w)
-hipError_t launch_light_eval(const DScene &S, const float *in, uint32_t n, int *entry, float *out, hipStream_t stream);
-hipError_t launch_bvh_test(const TraceP &p, hipStream_t stream);
-hipError_t launch_draw(const float4 *acc, uint32_t W, uint32_t H, float exposure, float saturation, int denoise,
-                       float max_sigma, float scale, uint32_t *out, hipStream_t stream);
 // auto-exposure (fspt_target_set_auto_exposure)
 constexpr uint32_t EXPOSURE_BINS = 256; // 32 octaves from 2^-16, 8 sub-bins each
 struct ExposureP { float key, low, high, adapt_up, adapt_down, min_log2, max_log2; }; // fspt_exposure_params, validated
@@ -464,12 +433,6 @@ struct ExposureState {      // 32 bytes of device memory (fspt_exposure_state): 
   uint32_t metered, pad;    // N of the last metering with N > 0
   double log2_exposure, log2_mean;
 };
-extern int g_exposure_form; // the shipped form, or fspt_exposure_set_form's (a measurement switch)
-// form 0: one LDS atomic per pixel; 1: the first active lane's bin is counted by a ballot (same histogram bit for bit)
-hipError_t launch_exposure_histogram(const float4 *src, uint32_t W, uint32_t vw, uint32_t vh, uint32_t *hist, int form, hipStream_t stream);
-hipError_t launch_exposure_resolve(uint32_t *hist, ExposureState *state, const ExposureP &p, hipStream_t stream); // (zeroes hist)
-hipError_t launch_draw_auto(const float4 *acc, uint32_t W, uint32_t H, float exposure, float saturation, int denoise,
-                            float max_sigma, float scale, uint32_t *out, const ExposureState *state, hipStream_t stream);
 // bloom (fspt_target_set_bloom; the rule: fspt_tuning.h)
 constexpr uint32_t BLOOM_MAX_LEVELS = 8;          // FSPT_BLOOM_MAX_LEVELS
 constexpr size_t BLOOM_TAIL_LDS_MAX = 160 * 1024; // what one workgroup may hold on gfx950
@@ -486,14 +449,56 @@ struct BloomPlan {          // the pyramid of a vw x vh viewport
   uint32_t tail;            // the level k_bloom_tail starts at, 0 = no tail
   size_t tail_lds;          // its LDS bytes
 };
+
+// ---------------------------------------------------------------------------
+// launchers of fspt_kernels.hip: whatever reads a DScene
+// ---------------------------------------------------------------------------
+hipError_t launch_trace(const TraceP &p, bool gen_rays, bool count, int num_cus, hipStream_t stream);
+// count: 0 = production kernels; 1 = counting variants doing the reference's work (NEE shadow rays traced to the closest
+// hit, tracer.fs:501); 2 = counting variants of the production work (shadow rays stop at the first hit)
+hipError_t launch_wf(int kernel, const WfP &p, int count, int num_cus, hipStream_t stream);
+size_t wf_max_stack_entries(); // deepest tree (entries per lane) whose traversal stacks fit the LDS of every kernel
+hipError_t launch_tile_pack(const TilePackP &p, bool unpack, hipStream_t stream);
+hipError_t launch_camera(uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const CameraP &cam, float rand_base, float4 *pos, float4 *dir,
+                         hipStream_t stream, uint32_t sampler = 0, uint32_t smp_seed = 0, uint32_t sample = 0);
+// the Sobol sampler's value for n (pixel, sample, dim) triples (fspt_sampler_eval)
+hipError_t launch_sampler_eval(uint32_t seed, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim, uint32_t n,
+                               float *out, hipStream_t stream);
+hipError_t launch_intersect(const IntersectP &p, hipStream_t stream);
+hipError_t launch_bvh_test(const TraceP &p, hipStream_t stream);
+hipError_t launch_math(int op, const float *a, const float *b, uint32_t n, float *out, hipStream_t stream);
+// light table build (fspt_target_set_lights): w[i] for the triangle in leaf slot slots[i] (DESIGN 8.3); with rec != NULL
+// also its 64-byte light record rec[4 i .. 4 i + 3]
+hipError_t launch_light_weights(const DScene &S, const uint32_t *slots, uint32_t n, float *w, float4 *rec, hipStream_t stream);
+// fspt_light_sample_eval: 10 floats per query (ro.xyz, n.xyz, u0..u3) -> entry index, 8 floats (x.xyz, pdf_L, Le.rgb, n . w)
+hipError_t launch_light_eval(const DScene &S, const float *in, uint32_t n, int *entry, float *out, hipStream_t stream);
+// one workgroup per active tile: E_T = mean over the tile's viewport pixels and 3 channels of m (I - S)^2 / ((n - m)(I^2 + 0.01))
+hipError_t launch_adaptive_error(const AdaptiveP &p, hipStream_t stream);
+// one workgroup: retire the tiles of list_in whose E_T decides it, list the rest in list_out (same order), *n_out
+hipError_t launch_adaptive_select(const AdaptiveP &p, hipStream_t stream);
+// the two passes of the image chain that trace rays (fspt_post.cpp launches them)
+hipError_t launch_features(const FeatureP &p, hipStream_t stream);
+hipError_t launch_temporal_gbuffer(const TemporalGP &p, hipStream_t stream);
+
+// ---------------------------------------------------------------------------
+// launchers of fspt_post.hip: whatever reads only images
+// ---------------------------------------------------------------------------
+// k_draw, or with state != NULL k_draw_auto, with bloom != NULL k_draw_bloom (<true> where state != NULL too)
+hipError_t launch_draw(const float4 *acc, uint32_t W, uint32_t H, float exposure, float saturation, int denoise, float max_sigma,
+                       float scale, uint32_t *out, const ExposureState *state, const BloomDraw *bloom, hipStream_t stream);
+hipError_t launch_atrous(const AtrousP &p, bool var, hipStream_t stream); // (var: the variance-guided instantiation)
+hipError_t launch_temporal_blend(const TemporalBP &p, hipStream_t stream); // (p.mom_out != NULL: the moments instantiations; p.fast_out != NULL: the fast-history ones)
+hipError_t launch_temporal_clamp(const ClampP &p, hipStream_t stream);
+hipError_t launch_svgf_variance(const SvgfVarP &p, hipStream_t stream);
+extern int g_exposure_form; // the shipped form, or fspt_exposure_set_form's (a measurement switch)
+// form 0: one LDS atomic per pixel; 1: the first active lane's bin is counted by a ballot (same histogram bit for bit)
+hipError_t launch_exposure_histogram(const float4 *src, uint32_t W, uint32_t vw, uint32_t vh, uint32_t *hist, int form, hipStream_t stream);
+hipError_t launch_exposure_resolve(uint32_t *hist, ExposureState *state, const ExposureP &p, hipStream_t stream); // (zeroes hist)
 extern int g_bloom_form;
 extern uint32_t g_bloom_tail_texels;
 BloomPlan bloom_plan(uint32_t vw, uint32_t vh, uint32_t levels, int form, uint32_t tail_texels);
 hipError_t launch_bloom_chain(const float4 *src, uint32_t pitch, const BloomPlan &q, float scatter, float4 *pyr, hipEvent_t *ev,
                               float4 *down_snapshot, float4 *dbg_up, hipStream_t stream);
 hipError_t launch_bloom_mix(const float4 *src, uint32_t W, uint32_t H, const BloomDraw &bl, float4 *bloom_out, float4 *mix_out, hipStream_t stream);
-hipError_t launch_draw_bloom(const float4 *acc, uint32_t W, uint32_t H, float exposure, float saturation, int denoise, float max_sigma,
-                             float scale, uint32_t *out, const ExposureState *state, const BloomDraw &bl, hipStream_t stream);
-hipError_t launch_math(int op, const float *a, const float *b, uint32_t n, float *out, hipStream_t stream);
 
 } // namespace fspt

@@ -6,6 +6,10 @@
 //   fspt_sched_stream.cpp  the stream scheduler (render_stream): a fixed pool of live paths
 //   fspt_multi.cpp         one frame over several devices (fspt_multi_*), tile pack / unpack, the optional RCCL exchange
 //   scene_build.cpp        the native scene builder (OBJ / MTL / SAH BVH; no GPU)
+// and the device side, declared in fspt_device.hpp:
+//   fspt_kernels.hip       every kernel that reads a DScene: the path tracer, the test passes, k_features, k_temporal_gbuffer
+//   fspt_post.hip          every kernel that reads only images: what fspt_post.cpp launches, but for those two
+//   fspt_bvh_build.hip     the GPU BVH builder;  fspt_refit.hip  in-place refit and rebuild
 #pragma once
 #include "../../include/fspt.h"
 #include "../../include/fspt_tuning.h"

@@ -55,15 +55,15 @@ hipError_t draw_launch(fspt_target *t, const float4 *src, float exposure, float 
     q = fspt::bloom_plan(t->vw, t->vh, t->bl_p.levels, fspt::g_bloom_form, fspt::g_bloom_tail_texels);
     t->bl_timed = false;
   }
+  const fspt::ExposureState *state = t->ax_on ? t->ax_state : nullptr;
   if (q.n) {
     e = fspt::launch_bloom_chain(src, t->W, q, t->bl_p.scatter, t->bl_pyr, t->bl_ev, nullptr, nullptr, st);
     const fspt::BloomDraw bl{t->bl_pyr + q.off[1], q.w[1], q.h[1], t->vw, t->vh, t->bl_p.intensity};
-    if (e == hipSuccess) e = fspt::launch_draw_bloom(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, t->ax_on ? t->ax_state : nullptr, bl, st);
+    if (e == hipSuccess) e = fspt::launch_draw(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, state, &bl, st);
     if (e == hipSuccess) e = hipEventRecord(t->bl_ev[4], st);
     if (e == hipSuccess) t->bl_timed = true;
   } else {
-    e = t->ax_on ? fspt::launch_draw_auto(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, t->ax_state, st)
-                 : fspt::launch_draw(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, st);
+    e = fspt::launch_draw(src, t->W, t->H, exposure, saturation, denoise, max_sigma, scale, out, state, nullptr, st);
   }
   if (e == hipSuccess && t->ax_on) e = hipEventRecord(t->ax_ev[3], st);
   return e;
@@ -172,7 +172,7 @@ static hipError_t atrous_run(const fspt_denoise_params &q, const float4 *src, co
     } else {
       p.sc_step = std::ldexp(q.sigma_color, -(int)k);
     }
-    if ((e = var ? fspt::launch_atrous_variance(p, stream) : fspt::launch_atrous(p, stream)) != hipSuccess) return e;
+    if ((e = fspt::launch_atrous(p, var != nullptr, stream)) != hipSuccess) return e;
   }
   return hipSuccess;
 }

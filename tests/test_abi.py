@@ -53,6 +53,17 @@ def test_abi_version():
     assert L.lib().fspt_abi_version() == hdr == L.ABI_VERSION == js == 4
 
 
+def test_build_lists_agree():
+    """every source of libfspt.so (__graft_entry__.LIB_SOURCES) exists and is also on tools/build_ab.sh's compile line:
+    an A/B library built from a shorter list does not load"""
+    import __graft_entry__ as g
+    ab = open(os.path.join(ROOT, "tools", "build_ab.sh")).read().split()
+    assert len(g.LIB_SOURCES) >= 10 and len(set(g.LIB_SOURCES)) == len(g.LIB_SOURCES)
+    for f in g.LIB_SOURCES:
+        assert os.path.isfile(os.path.join(ROOT, "fspt_amd", "csrc", f)), f
+        assert "fspt_amd/csrc/" + f in ab, f"{f} is in LIB_SOURCES but not in tools/build_ab.sh"
+
+
 def test_rand_base_stream_range():
     st = C.c_uint64(1)
     vals = [L.lib().fspt_rand_base_next(C.byref(st)) for _ in range(1000)]

@@ -1,16 +1,19 @@
 #!/bin/bash
-# Per-kernel register / scratch / occupancy table of fspt_kernels.hip (hipcc -Rpass-analysis=kernel-resource-usage), demangled.
+# Per-kernel register / scratch / occupancy table of the two kernel files, fspt_kernels.hip and fspt_post.hip
+# (hipcc -Rpass-analysis=kernel-resource-usage), demangled, in one table.
 # usage: tools/kernel_resources.sh [extra -D flags]
 cd "$(dirname "$0")/.." || exit 1
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off ${AB_SLP:--fno-slp-vectorize} -std=c++17 -Wno-unused-value -c --cuda-device-only \
-  -Rpass-analysis=kernel-resource-usage "$@" fspt_amd/csrc/fspt_kernels.hip -o /tmp/fspt_kernels_res.o 2>&1 |
+for f in fspt_kernels fspt_post; do
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off ${AB_SLP:--fno-slp-vectorize} -std=c++17 -Wno-unused-value -c --cuda-device-only \
+    -Rpass-analysis=kernel-resource-usage "$@" fspt_amd/csrc/$f.hip -o /tmp/${f}_res.o 2>&1
+done |
 python3 -c '
 import re, sys, subprocess
 rows, cur = [], None
 for line in sys.stdin:
     m = re.search(r"Function Name: (\S+)", line)
     if m: cur = {"name": m.group(1)}; rows.append(cur); continue
-    for key, pat in (("sgpr", r" SGPRs: (\d+)"), ("vgpr", r" VGPRs: (\d+)"), ("agpr", r"AGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
+    for key, pat in (("sgpr", r"SGPRs: (\d+)"), ("vgpr", r" VGPRs: (\d+)"), ("agpr", r"AGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
                      ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("sspill", r"SGPRs Spill: (\d+)"), ("vspill", r"VGPRs Spill: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
         m = re.search(pat, line)
         if m and cur is not None: cur[key] = int(m.group(1))

@@ -117,6 +117,13 @@ SIGNATURES = {
     "fspt_scene_rebuild_geometry_device": (C.c_int, [_VP, _VP, _VP, _VP]),
     "fspt_scene_last_rebuild_ms": (C.c_int, [_VP, _F, _F, _F, _U32, _U32]),
     "fspt_multi_rebuild_geometry": (C.c_int, [_VP, _F, _F, _U32]),
+    "fspt_scene_update_materials": (C.c_int, [_VP, _F, _F, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]),
+    "fspt_scene_update_environment": (C.c_int, [_VP, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, _U32, C.c_uint32]),
+    "fspt_multi_update_materials": (C.c_int, [_VP, _F, _F, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]),
+    "fspt_multi_update_environment": (C.c_int, [_VP, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, _U32, C.c_uint32]),
+    "fspt_scene_read_appearance": (C.c_int, [_VP, C.c_int, _VP, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "fspt_scene_last_appearance_ms": (C.c_int, [_VP, _F, _U32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fspt_texset_classify_eval": (C.c_int, [_F, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), _U32, _U32, _U32, _U32, C.c_uint32]),
     "fspt_target_create": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(_VP)]),
     "fspt_target_destroy": (C.c_int, [_VP]),
     "fspt_target_set_viewport": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),

@@ -302,6 +302,98 @@ void tree_refit_tables(const void *words, size_t stride_bytes, uint32_t N, uint3
   }
 }
 
+// ---- material texture sets: the four atlas layers a triangle samples at one uv (tracer.fs:453-456) ----
+// layer = clamp(floor(id + 0.5), 0, layers - 1) as texture(sampler2DArray) selects it; same binary32 arithmetic here
+uint32_t texset_layer_of(float id, uint32_t n_layers) {
+  const float x = std::floor(id + 0.5f);
+  if (!(x >= 0.0f)) return 0u; // negative, NaN (the device's float -> int conversion gives 0 for NaN)
+  if (x >= (float)(n_layers - 1u)) return n_layers - 1u;
+  return (uint32_t)x;
+}
+
+// A layer whose texels are all equal - every flat colour: TexturePacker fills whole layers with them
+// (texture_packer.js:36-42), and a colours-only atlas is 1 x 1 - is never stored: its texel sits in the sets that use
+// it.  A set with two or more image layers gets ONE interleaved image (16-byte texels: diffuse, emissive, mr, normal;
+// 4 x 2-texel tiles = 128 bytes), as long as the interleaving budget lasts; the image layers of the other sets are
+// stored once each as single-layer images in 8 x 4-texel tiles.
+int texset_classify(const float *mat, uint32_t T, uint32_t n_layers, uint32_t res, const uint8_t *is_const, const uint32_t *first, TexSetPlan &pl) {
+  std::map<std::array<uint32_t, 4>, uint32_t> set_ids;
+  std::vector<std::array<uint32_t, 4>> &set_keys = pl.keys;
+  set_keys.clear();
+  pl.tri_set.assign(T, 0u);
+  for (uint32_t i = 0; i < T; ++i) {
+    const float *m = mat + (size_t)i * 12;
+    const std::array<uint32_t, 4> key = {texset_layer_of(m[0], n_layers), texset_layer_of(m[1], n_layers), texset_layer_of(m[3], n_layers), texset_layer_of(m[2], n_layers)}; // diffuse, emissive, mr, normal
+    auto it = set_ids.find(key);
+    if (it == set_ids.end()) {
+      it = set_ids.emplace(key, (uint32_t)set_keys.size()).first;
+      set_keys.push_back(key);
+    }
+    pl.tri_set[i] = it->second;
+  }
+  const uint32_t n_sets = (uint32_t)set_keys.size();
+  const uint32_t qtx = (res + 3u) / 4u, qty = (res + 1u) / 2u;
+  const size_t quad_tiles = (size_t)qtx * qty;             // 128-byte tiles per interleaved image
+  std::vector<uint32_t> &tab = pl.tab, &kind = pl.kind;
+  tab.assign((size_t)n_sets * 12, 0u); kind.assign(n_sets, fspt::TEXSET_CONST);
+  std::vector<int64_t> &layer_base = pl.layer_base;         // single-layer image of a layer, in tiles (-1: not stored)
+  layer_base.assign(n_layers, -1);
+  pl.single_layers.clear();
+  uint64_t quad_bytes = 0;
+  uint32_t n_quad = 0;
+  for (uint32_t si = 0; si < n_sets; ++si) {
+    const auto &key = set_keys[si];
+    uint32_t n_img = 0, distinct[4];
+    for (int k = 0; k < 4; ++k) {
+      if (is_const[key[k]]) continue;
+      bool seen = false;
+      for (uint32_t q = 0; q < n_img; ++q) seen = seen || distinct[q] == key[k];
+      if (!seen) distinct[n_img++] = key[k];
+    }
+    if (n_img >= 2 && quad_bytes + quad_tiles * 128u <= g_texset_budget && (n_quad + 1ull) * quad_tiles < 0xFFFFFFFFull) {
+      kind[si] = fspt::TEXSET_QUAD;
+      quad_bytes += quad_tiles * 128u;
+      n_quad++;
+    } else if (n_img >= 1) {
+      kind[si] = fspt::TEXSET_SEPARATE;
+    }
+  }
+  // single-layer images: the image layers of SEPARATE sets
+  std::vector<uint32_t> none;
+  const size_t layer_texels = tile_image(nullptr, res, res, none);
+  size_t single = 0; // texels
+  for (uint32_t si = 0; si < n_sets; ++si) {
+    if (kind[si] != fspt::TEXSET_SEPARATE) continue;
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t l = set_keys[si][k];
+      if (is_const[l] || layer_base[l] >= 0) continue;
+      layer_base[l] = (int64_t)(single / (fspt::TEX_TILE_W * fspt::TEX_TILE_H));
+      pl.single_layers.push_back(l);
+      single += layer_texels;
+    }
+  }
+  pl.quad_bytes = quad_bytes;
+  pl.single_texels = single;
+  if (single / (fspt::TEX_TILE_W * fspt::TEX_TILE_H) >= 0xFFFFFFFFull) {
+    fspt_set_error("atlas too large: %zu texels of image layers", single);
+    return FSPT_E_INVALID;
+  }
+  uint32_t qi = 0;
+  for (uint32_t si = 0; si < n_sets; ++si) {
+    const auto &key = set_keys[si];
+    uint32_t *q = &tab[(size_t)si * 12];
+    q[0] = kind[si];
+    for (int k = 0; k < 4; ++k) {
+      q[4 + k] = first[key[k]];
+      q[8 + k] = (kind[si] == fspt::TEXSET_SEPARATE && !is_const[key[k]]) ? (uint32_t)layer_base[key[k]] : fspt::LAYER_CONST;
+    }
+    if (kind[si] != fspt::TEXSET_QUAD) continue;
+    q[1] = (uint32_t)(qi * quad_tiles);
+    qi++;
+  }
+  return FSPT_OK;
+}
+
 extern "C" {
 
 int fspt_light_alias_table(const float *weights, uint32_t n, float *prob, uint32_t *alias) {
@@ -474,28 +566,22 @@ int fspt_scene_create(const fspt_scene_desc *desc, int device, fspt_scene **out)
       slot_tri[L * LS + k] = ti;
     }
   }
-  // ---- material texture sets: the four atlas layers a triangle samples at one uv (tracer.fs:453-456) ----
-  // layer = clamp(floor(id + 0.5), 0, layers - 1) as texture(sampler2DArray) selects it; same binary32 arithmetic here
+  // ---- material texture sets (texset_classify): which layers are flat colours, then the sets, their forms and table ----
   const uint32_t n_layers = desc->atlas_layers;
-  auto layer_of = [&](float id) -> uint32_t {
-    const float x = std::floor(id + 0.5f);
-    if (!(x >= 0.0f)) return 0u; // negative, NaN (the device's float -> int conversion gives 0 for NaN)
-    if (x >= (float)(n_layers - 1u)) return n_layers - 1u;
-    return (uint32_t)x;
-  };
-  std::map<std::array<uint32_t, 4>, uint32_t> set_ids;
-  std::vector<std::array<uint32_t, 4>> set_keys;
-  std::vector<uint32_t> tri_set(T);
-  for (uint32_t i = 0; i < T; ++i) {
-    const float *m = desc->mat + (size_t)i * 12;
-    const std::array<uint32_t, 4> key = {layer_of(m[0]), layer_of(m[1]), layer_of(m[3]), layer_of(m[2])}; // diffuse, emissive, mr, normal
-    auto it = set_ids.find(key);
-    if (it == set_ids.end()) {
-      it = set_ids.emplace(key, (uint32_t)set_keys.size()).first;
-      set_keys.push_back(key);
+  std::vector<uint8_t> is_const(n_layers, 1);
+  std::vector<uint32_t> first(n_layers, 0u);
+  {
+    const size_t per_layer = (size_t)desc->atlas_res * desc->atlas_res;
+    for (uint32_t l = 0; l < n_layers; ++l) {
+      const uint8_t *src = desc->atlas + (size_t)l * per_layer * 4;
+      std::memcpy(&first[l], src, 4);
+      for (size_t k = 1; k < per_layer && is_const[l]; ++k) is_const[l] = std::memcmp(src + k * 4, &first[l], 4) == 0;
     }
-    tri_set[i] = it->second;
   }
+  TexSetPlan pl;
+  { int rc_c = texset_classify(desc->mat, T, n_layers, desc->atlas_res, is_const.data(), first.data(), pl); if (rc_c) return rc_c; }
+  const std::vector<std::array<uint32_t, 4>> &set_keys = pl.keys;
+  const std::vector<uint32_t> &tri_set = pl.tri_set;
   // ---- 192-byte hit records, one per leaf SLOT (what the traversal reports): slot (L, k) holds triangle leaf_first[L] + k ----
   bool has_dielectric = false;
   const size_t n_slots = (n_leaves ? n_leaves : 1) * (size_t)LS;
@@ -532,77 +618,30 @@ int fspt_scene_create(const fspt_scene_desc *desc, int device, fspt_scene **out)
   if (e == hipSuccess) e = upload(&s->tris, leaves.data(), leaves.size() * 4);
   if (e == hipSuccess) e = upload(&s->slot_tri, slot_tri.data(), slot_tri.size() * 4);
   if (e == hipSuccess) e = upload(&s->shade, shade.data(), shade.size() * 4);
-  // Atlas.  A layer whose texels are all equal - every flat colour: TexturePacker fills whole layers with them
-  // (texture_packer.js:36-42), and a colours-only atlas is 1 x 1 - is never stored: its texel sits in the sets that use
-  // it.  A set with two or more image layers gets ONE interleaved image (16-byte texels: diffuse, emissive, mr, normal;
-  // 4 x 2-texel tiles = 128 bytes), as long as the interleaving budget lasts; the image layers of the other sets are
-  // stored once each as single-layer images in 8 x 4-texel tiles.
+  // Atlas: the single-layer images and the interleaved images texset_classify planned, tiled here on the host (the
+  // independent statement fspt_appearance.hip's kernels are tested against byte for byte)
   uint32_t n_sets = (uint32_t)set_keys.size();
   if (e == hipSuccess) {
     const uint32_t res = desc->atlas_res;
     const size_t per_layer = (size_t)res * res;
-    std::vector<uint8_t> is_const(n_layers, 1);
-    std::vector<uint32_t> first(n_layers, 0u);
-    for (uint32_t l = 0; l < n_layers; ++l) {
-      const uint8_t *src = desc->atlas + (size_t)l * per_layer * 4;
-      std::memcpy(&first[l], src, 4);
-      for (size_t k = 1; k < per_layer && is_const[l]; ++k) is_const[l] = std::memcmp(src + k * 4, &first[l], 4) == 0;
-    }
     const uint32_t qtx = (res + 3u) / 4u, qty = (res + 1u) / 2u;
     const size_t quad_tiles = (size_t)qtx * qty;             // 128-byte tiles per interleaved image
-    std::vector<uint32_t> tab((size_t)n_sets * 12, 0u), kind(n_sets, fspt::TEXSET_CONST);
-    std::vector<int64_t> layer_base(n_layers, -1);            // single-layer image of a layer, in tiles (-1: not stored)
+    const std::vector<uint32_t> &tab = pl.tab, &kind = pl.kind;
+    const uint64_t quad_bytes = pl.quad_bytes;
     std::vector<uint32_t> single;                              // the single-layer images, tiled
     std::vector<uint32_t> tiled;
-    uint64_t quad_bytes = 0;
-    uint32_t n_quad = 0;
-    for (uint32_t si = 0; si < n_sets; ++si) {
-      const auto &key = set_keys[si];
-      uint32_t n_img = 0, distinct[4];
-      for (int k = 0; k < 4; ++k) {
-        if (is_const[key[k]]) continue;
-        bool seen = false;
-        for (uint32_t q = 0; q < n_img; ++q) seen = seen || distinct[q] == key[k];
-        if (!seen) distinct[n_img++] = key[k];
-      }
-      if (n_img >= 2 && quad_bytes + quad_tiles * 128u <= g_texset_budget && (n_quad + 1ull) * quad_tiles < 0xFFFFFFFFull) {
-        kind[si] = fspt::TEXSET_QUAD;
-        quad_bytes += quad_tiles * 128u;
-        n_quad++;
-      } else if (n_img >= 1) {
-        kind[si] = fspt::TEXSET_SEPARATE;
-      }
-    }
-    // single-layer images: the image layers of SEPARATE sets
-    for (uint32_t si = 0; si < n_sets; ++si) {
-      if (kind[si] != fspt::TEXSET_SEPARATE) continue;
-      for (int k = 0; k < 4; ++k) {
-        const uint32_t l = set_keys[si][k];
-        if (is_const[l] || layer_base[l] >= 0) continue;
-        layer_base[l] = (int64_t)(single.size() / (fspt::TEX_TILE_W * fspt::TEX_TILE_H));
-        tile_image(desc->atlas + (size_t)l * per_layer * 4, res, res, tiled);
-        single.insert(single.end(), tiled.begin(), tiled.end());
-      }
-    }
-    if (single.size() / (fspt::TEX_TILE_W * fspt::TEX_TILE_H) >= 0xFFFFFFFFull) {
-      fspt_set_error("atlas too large: %zu texels of image layers", single.size());
-      fspt_scene_destroy(s);
-      return FSPT_E_INVALID;
+    for (uint32_t l : pl.single_layers) {
+      tile_image(desc->atlas + (size_t)l * per_layer * 4, res, res, tiled);
+      single.insert(single.end(), tiled.begin(), tiled.end());
     }
     if (e == hipSuccess) e = upload(&s->atlas, single.data(), single.size() * 4);
     if (e == hipSuccess) e = hipMalloc(&s->atlas4, quad_bytes ? quad_bytes : 16);
+    s->atlas_bytes = single.size() * 4; s->atlas4_bytes = quad_bytes;
     std::vector<uint32_t> quad;
     uint32_t qi = 0;
     for (uint32_t si = 0; si < n_sets && e == hipSuccess; ++si) {
       const auto &key = set_keys[si];
-      uint32_t *q = &tab[(size_t)si * 12];
-      q[0] = kind[si];
-      for (int k = 0; k < 4; ++k) {
-        q[4 + k] = first[key[k]];
-        q[8 + k] = (kind[si] == fspt::TEXSET_SEPARATE && !is_const[key[k]]) ? (uint32_t)layer_base[key[k]] : fspt::LAYER_CONST;
-      }
       if (kind[si] != fspt::TEXSET_QUAD) continue;
-      q[1] = (uint32_t)(qi * quad_tiles);
       quad.assign(quad_tiles * 32, 0u);
       for (int k = 0; k < 4; ++k) {
         const uint32_t l = key[k];
@@ -638,6 +677,7 @@ int fspt_scene_create(const fspt_scene_desc *desc, int device, fspt_scene **out)
     tile_image(desc->env, desc->env_w, desc->env_h, tiled);
 #endif
     e = upload(&s->env, tiled.data(), tiled.size() * 4);
+    s->env_bytes = tiled.size() * 4;
   }
   if (e == hipSuccess) e = upload(&s->bins, desc->bins, (size_t)desc->n_bins * 16);
   if (e != hipSuccess) {
@@ -686,6 +726,7 @@ int fspt_scene_destroy(fspt_scene *s) {
   hipFree(s->nodes); hipFree(s->quads); hipFree(s->tris); hipFree(s->slot_tri); hipFree(s->shade); hipFree(s->atlas); hipFree(s->atlas4); hipFree(s->tex_sets); hipFree(s->env); hipFree(s->bins);
   hipFree(s->l_alias); hipFree(s->l_rec); hipFree(s->l_p); hipFree(s->l_pick); hipFree(s->motion);
   fspt::refit_release(s);
+  fspt::appearance_release(s);
   delete s;
   return FSPT_OK;
 }
@@ -1394,13 +1435,11 @@ static int present_flush(fspt_target *t) {
   return FSPT_OK;
 }
 
-extern "C" {
-
 // ---------------------------------------------------------------------------
 // in-place geometry update (kernels in fspt_refit.hip)
 // ---------------------------------------------------------------------------
 // Orders a geometry call against every target of the scene, then leaves the device idle.
-static int geometry_order_targets(fspt_scene *s) {
+int geometry_order_targets(fspt_scene *s) {
   int rc = FSPT_OK;
   // every earlier call on any target of the scene sees the old geometry: run the recorded ticks (which joins a present
   // frame in flight), then wait for the device - the update's kernels run on the NULL stream and are waited for, so every
@@ -1415,7 +1454,7 @@ static int geometry_order_targets(fspt_scene *s) {
   return FSPT_OK;
 }
 
-static int geometry_changed_lights(fspt_scene *s) {
+int geometry_changed_lights(fspt_scene *s) {
   int rc = FSPT_OK;
   // the emitter light table depends on the triangles' areas: release it; light_table_ensure rebuilds it from the device arrays
   if (s->lights_built) {
@@ -1429,6 +1468,8 @@ static int geometry_changed_lights(fspt_scene *s) {
     if (t->lights == FSPT_LIGHTS_EMITTERS) { rc = light_table_ensure(s); if (rc) return rc; break; }
   return FSPT_OK;
 }
+
+extern "C" {
 
 static int update_geometry(fspt_scene *s, const float *tri, const float *norm, bool on_device, const char *fn) {
   if (!s || !tri) { fspt_set_error("%s: NULL scene or tri", fn); return FSPT_E_INVALID; }
@@ -1549,6 +1590,87 @@ int fspt_scene_last_rebuild_ms(fspt_scene *s, float *build_ms, float *install_ms
   if (host_ms) *host_ms = s->rb.host_ms;
   if (launches) *launches = s->rb.launches;
   if (readbacks) *readbacks = s->rb.readbacks;
+  return FSPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// in-place appearance update (kernels in fspt_appearance.hip)
+// ---------------------------------------------------------------------------
+int fspt_scene_update_materials(fspt_scene *s, const float *mat, const float *uv, const uint8_t *atlas, uint32_t atlas_res, uint32_t atlas_layers) {
+  if (!s || !mat) { fspt_set_error("fspt_scene_update_materials: NULL scene or mat"); return FSPT_E_INVALID; }
+  if (atlas && (atlas_res == 0 || atlas_layers == 0)) {
+    fspt_set_error("fspt_scene_update_materials: atlas must have at least one layer");
+    return FSPT_E_INVALID;
+  }
+  if (!atlas && !s->ap.raw) {
+    fspt_set_error("fspt_scene_update_materials: atlas is NULL and no earlier call of this scene carried one");
+    return FSPT_E_STATE;
+  }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  if ((rc = geometry_order_targets(s))) return rc;
+  const bool was = s->has_dielectric;
+  if ((rc = fspt::appearance_materials(s, mat, uv, atlas, atlas_res, atlas_layers))) return rc;
+  if (was != s->has_dielectric) {
+    // the stream scheduler's horizon and the batch scheduler's tail rule read has_dielectric at every launch; what a lane
+    // measured under the other horizon (iterations a run needed, live-path fractions) is forgotten with it
+    for (fspt_target *t : s->targets) {
+      t->live_known = false;
+      for (fspt_target::WfLane *ln : {&t->wf, &t->pr_lane}) { ln->counts_pending = false; ln->ctl_pending = false; ln->stat_key = 0; ln->stat_gen_iters = 0; }
+    }
+  }
+  return geometry_changed_lights(s); // the table depends on the emissive layers and their texels
+}
+
+int fspt_scene_update_environment(fspt_scene *s, const uint8_t *env, uint32_t env_w, uint32_t env_h, const uint32_t *bins, uint32_t n_bins) {
+  if (!s) { fspt_set_error("fspt_scene_update_environment: NULL scene"); return FSPT_E_INVALID; }
+  if (!bins || n_bins == 0) {
+    fspt_set_error("fspt_scene_update_environment: radianceBins must hold at least one bin (main.js:292)");
+    return FSPT_E_INVALID;
+  }
+  if (env && (env_w == 0 || env_h == 0)) {
+    fspt_set_error("fspt_scene_update_environment: env given with zero size");
+    return FSPT_E_INVALID;
+  }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  if ((rc = geometry_order_targets(s))) return rc;
+  return fspt::appearance_environment(s, env, env_w, env_h, bins, n_bins);
+}
+
+int fspt_scene_read_appearance(fspt_scene *s, int what, void *out, uint64_t cap, uint64_t *bytes) {
+  if (!s || what < 0 || what > 5) { fspt_set_error("fspt_scene_read_appearance: NULL scene or what not in [0, 5]"); return FSPT_E_INVALID; }
+  const void *src[6] = {s->tex_sets, s->atlas, s->atlas4, s->env, s->bins, s->shade};
+  const uint64_t size[6] = {(uint64_t)s->d.n_tex_sets * 48u, s->atlas_bytes, s->atlas4_bytes, s->env_bytes, (uint64_t)s->d.n_bins * 16u, (uint64_t)s->n_slots * 192u};
+  if (bytes) *bytes = size[what];
+  const uint64_t n = cap < size[what] ? cap : size[what];
+  if (!out || !n) return FSPT_OK;
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, src[what], n, hipMemcpyDeviceToHost));
+  return FSPT_OK;
+}
+
+int fspt_scene_last_appearance_ms(fspt_scene *s, float *ms, uint32_t *launches, uint64_t *uploaded, uint64_t *retained) {
+  if (!s) { fspt_set_error("fspt_scene_last_appearance_ms: NULL scene"); return FSPT_E_INVALID; }
+  if (ms) *ms = s->ap.last_ms;
+  if (launches) *launches = s->ap.last_launches;
+  if (uploaded) *uploaded = s->ap.last_uploaded;
+  if (retained) *retained = s->ap.raw ? (uint64_t)s->ap.raw_res * s->ap.raw_res * s->ap.raw_layers * 4u : 0u;
+  return FSPT_OK;
+}
+
+// texset_classify as a host-only hook (tests): set of every triangle, the sets' 12-word rows (up to cap_sets of them)
+int fspt_texset_classify_eval(const float *mat, uint32_t n_tris, uint32_t n_layers, uint32_t res, const uint8_t *is_const, const uint32_t *first,
+                              uint32_t *tri_set, uint32_t *n_sets, uint32_t *tab, uint32_t cap_sets) {
+  if (!mat || !is_const || !first || !n_sets || n_tris == 0 || n_layers == 0 || res == 0) { fspt_set_error("fspt_texset_classify_eval: NULL/empty argument"); return FSPT_E_INVALID; }
+  TexSetPlan pl;
+  const int rc = texset_classify(mat, n_tris, n_layers, res, is_const, first, pl);
+  if (rc) return rc;
+  *n_sets = (uint32_t)pl.keys.size();
+  if (tri_set) std::memcpy(tri_set, pl.tri_set.data(), (size_t)n_tris * 4);
+  if (tab) std::memcpy(tab, pl.tab.data(), (size_t)std::min<uint32_t>(cap_sets, *n_sets) * 48);
   return FSPT_OK;
 }
 

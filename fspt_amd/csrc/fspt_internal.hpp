@@ -10,6 +10,7 @@
 //   fspt_kernels.hip       every kernel that reads a DScene: the path tracer, the test passes, k_features, k_temporal_gbuffer
 //   fspt_post.hip          every kernel that reads only images: what fspt_post.cpp launches, but for those two
 //   fspt_bvh_build.hip     the GPU BVH builder;  fspt_refit.hip  in-place refit and rebuild
+//   fspt_appearance.hip    in-place appearance update: the texture-set, atlas and environment layouts and the material part of the hit records
 #pragma once
 #include "../../include/fspt.h"
 #include "../../include/fspt_tuning.h"
@@ -87,7 +88,40 @@ struct fspt_scene {
   // motion origin (fspt_scene_motion_begin): floats 0-8 of every leaf slot's hit record as they were at the
   // last motion_begin (n_slots x 36 bytes; NULL: the scene is static).  A refit leaves it alone, a rebuild permutes it.
   void *motion = nullptr;
+  // bytes of atlas (single-layer images), atlas4 (interleaved images) and env as laid out (fspt_scene_read_appearance)
+  uint64_t atlas_bytes = 0, atlas4_bytes = 0, env_bytes = 0;
+  // fspt_scene_update_materials / _environment (fspt_appearance.hip).  `raw` is the atlas the most recent
+  // update_materials call carried, as given (RGBA8, layer-major): what a later call with atlas == NULL lays out again.  Like
+  // rf.stage it is made by the first such call - a scene whose appearance is never updated allocates nothing for it.
+  struct Appearance {
+    void *raw = nullptr;
+    uint32_t raw_res = 0, raw_layers = 0;
+    std::vector<uint8_t> is_const;  // per layer of `raw` (k_ap_layer_const's answer, kept with it)
+    std::vector<uint32_t> first;    // per layer: its texel 0
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    float last_ms = 0.0f;           // kernels of the last update, first to last
+    uint32_t last_launches = 0;
+    uint64_t last_uploaded = 0;     // host -> device bytes of the last update
+  } ap;
 };
+// Material texture sets: what fspt_scene_create and fspt_scene_update_materials derive from matTex's layer ids and
+// the per-layer "every texel equal" flags - the sets in first-appearance order, each triangle's set, a set's form under the
+// interleaving budget, where the single-layer images go, and the 12-word table rows.  Host only; one statement for both.
+struct TexSetPlan {
+  std::vector<std::array<uint32_t, 4>> keys; // per set: diffuse, emissive, mr, normal layer
+  std::vector<uint32_t> tri_set;             // per triangle
+  std::vector<uint32_t> kind;                // per set: fspt::TEXSET_*
+  std::vector<int64_t> layer_base;           // per layer: base of its single-layer image in 128-byte tiles (-1: not stored)
+  std::vector<uint32_t> single_layers;       // the layers stored as single-layer images, in storage order
+  std::vector<uint32_t> tab;                 // 12 words per set (fspt_device.hpp)
+  uint64_t quad_bytes = 0;                   // bytes of the interleaved images (a QUAD set's base: tab[12 si + 1] tiles)
+  uint64_t single_texels = 0;                // texels of the single-layer images, tiled
+};
+uint32_t texset_layer_of(float id, uint32_t n_layers); // clamp(floor(id + 0.5), 0, n_layers - 1), NaN -> 0
+// is_const / first: n_layers entries.  FSPT_E_INVALID: the single-layer images exceed 2^32 tiles.
+int texset_classify(const float *mat, uint32_t n_tris, uint32_t n_layers, uint32_t res, const uint8_t *is_const, const uint32_t *first, TexSetPlan &pl);
+int geometry_order_targets(fspt_scene *s);  // (fspt_api.cpp) orders a scene-changing call against every target, leaves the device idle
+int geometry_changed_lights(fspt_scene *s); // (fspt_api.cpp) releases the emitter light table and rebuilds it if a target uses it
 // What fspt_scene_create derives from the reference tree's three integer words per node (left, right, triStart; a node
 // with triStart > -1 is a leaf) and nothing else: shared with fspt_scene_rebuild_geometry, which gets its words from the
 // GPU builder.  `words` + i * stride = node i's words (any alignment).
@@ -111,6 +145,10 @@ int refit_check(fspt_scene *s, const float *tri, const float *norm, int *finite)
 // by fspt_bvh_build.hip's kernels and installed in `s`; the scene is untouched unless FSPT_OK comes back.  The caller has
 // ordered the call against the targets, prepared s->rf and checked tri / norm.  order_out: NULL, host or device memory.
 int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *order_out, bool order_on_device);
+// fspt_appearance.hip: the callers have validated their arguments and ordered the call against the targets.
+int appearance_materials(fspt_scene *s, const float *mat, const float *uv, const uint8_t *atlas, uint32_t res, uint32_t layers);
+int appearance_environment(fspt_scene *s, const uint8_t *env, uint32_t w, uint32_t h, const uint32_t *bins, uint32_t n_bins);
+void appearance_release(fspt_scene *s);
 }
 int light_table_ensure(fspt_scene *s); // (fspt_api.cpp) builds the table once; FSPT_OK when it exists
 #ifndef FSPT_LIGHTS_ENV_Q_MAX

@@ -217,6 +217,22 @@ int fspt_multi_update_geometry(fspt_multi *m, const float *tri, const float *nor
   }
   return FSPT_OK;
 }
+int fspt_multi_update_materials(fspt_multi *m, const float *mat, const float *uv, const uint8_t *atlas, uint32_t atlas_res, uint32_t atlas_layers) {
+  if (!m) { fspt_set_error("fspt_multi_update_materials: NULL handle"); return FSPT_E_INVALID; }
+  for (fspt_scene *s : m->scenes) { // (bad arguments are refused by the first scene, before anything is written)
+    const int rc = fspt_scene_update_materials(s, mat, uv, atlas, atlas_res, atlas_layers);
+    if (rc) return rc;
+  }
+  return FSPT_OK;
+}
+int fspt_multi_update_environment(fspt_multi *m, const uint8_t *env, uint32_t env_w, uint32_t env_h, const uint32_t *bins, uint32_t n_bins) {
+  if (!m) { fspt_set_error("fspt_multi_update_environment: NULL handle"); return FSPT_E_INVALID; }
+  for (fspt_scene *s : m->scenes) {
+    const int rc = fspt_scene_update_environment(s, env, env_w, env_h, bins, n_bins);
+    if (rc) return rc;
+  }
+  return FSPT_OK;
+}
 int fspt_multi_rebuild_geometry(fspt_multi *m, const float *tri, const float *norm, uint32_t *order_out) {
   if (!m) { fspt_set_error("fspt_multi_rebuild_geometry: NULL handle"); return FSPT_E_INVALID; }
   std::vector<uint32_t> first, other;

@@ -314,6 +314,44 @@ static napi_value SceneRebuildGeometry(napi_env env, napi_callback_info info) {
   FSPT_OK_OR_THROW(fspt_scene_rebuild_geometry((fspt_scene *)h, (const float *)tri, (const float *)norm, (uint32_t *)order));
   return ta;
 }
+/* sceneUpdateMaterials(scene, nTris, mat Float32Array, uv Float32Array | null, atlas Uint8Array | null, atlasRes, atlasLayers):
+ * fspt_scene_update_materials.  12 / 6 floats per triangle of the scene; an atlas holds atlasRes^2 * atlasLayers
+ * RGBA8 texels (null: the atlas of the scene's last call that carried one).  The guard of sceneUpdateGeometry. */
+static napi_value SceneUpdateMaterials(napi_env env, napi_callback_info info) {
+  napi_value a[7]; void *h, *mat = NULL, *uv = NULL, *atlas = NULL; size_t nm = 0, nu = 0, na = 0; uint32_t n = 0, res = 0, layers = 0;
+  if (get_args(env, info, 7, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[1], &n));
+  if (typed(env, a[2], napi_float32_array, 0, &mat, &nm) || typed(env, a[3], napi_float32_array, 1, &uv, &nu) ||
+      typed(env, a[4], napi_uint8_array, 1, &atlas, &na)) return NULL;
+  if (atlas) { NAPI_OK(napi_get_value_uint32(env, a[5], &res)); NAPI_OK(napi_get_value_uint32(env, a[6], &layers)); }
+  if (nm != (size_t)n * 12 || (uv && nu != (size_t)n * 6)) {
+    napi_throw_range_error(env, NULL, "fspt_napi: updateMaterials needs 12 floats (mat) and 6 floats (uv) per triangle of the scene");
+    return NULL;
+  }
+  if (atlas && (uint64_t)na != (uint64_t)res * res * layers * 4u) {
+    napi_throw_range_error(env, NULL, "fspt_napi: updateMaterials needs atlasRes * atlasRes * atlasLayers RGBA8 texels (atlas)");
+    return NULL;
+  }
+  FSPT_OK_OR_THROW(fspt_scene_update_materials((fspt_scene *)h, (const float *)mat, (const float *)uv, (const uint8_t *)atlas, res, layers));
+  return undefined(env);
+}
+/* sceneUpdateEnvironment(scene, env Uint8Array | null, envW, envH, bins Uint32Array): fspt_scene_update_environment. */
+static napi_value SceneUpdateEnvironment(napi_env env, napi_callback_info info) {
+  napi_value a[5]; void *h, *map = NULL, *bins = NULL; size_t ne = 0, nb = 0; uint32_t w = 0, hh = 0;
+  if (get_args(env, info, 5, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  if (typed(env, a[1], napi_uint8_array, 1, &map, &ne) || typed(env, a[4], napi_uint32_array, 0, &bins, &nb)) return NULL;
+  if (map) { NAPI_OK(napi_get_value_uint32(env, a[2], &w)); NAPI_OK(napi_get_value_uint32(env, a[3], &hh)); }
+  if (map && (uint64_t)ne != (uint64_t)w * hh * 4u) {
+    napi_throw_range_error(env, NULL, "fspt_napi: updateEnvironment needs envW * envH RGBE texels (env)");
+    return NULL;
+  }
+  if (nb % 4) {
+    napi_throw_range_error(env, NULL, "fspt_napi: updateEnvironment needs 4 words per bin (bins)");
+    return NULL;
+  }
+  FSPT_OK_OR_THROW(fspt_scene_update_environment((fspt_scene *)h, (const uint8_t *)map, w, hh, (const uint32_t *)bins, (uint32_t)(nb / 4)));
+  return undefined(env);
+}
 static napi_value SceneSahCost(napi_env env, napi_callback_info info) {
   napi_value a[1], v; void *h; double cost = 0.0;
   if (get_args(env, info, 1, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
@@ -1337,7 +1375,7 @@ static napi_value AbiVersion(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
-      {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"targetCreate", TargetCreate},
+      {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
       {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},

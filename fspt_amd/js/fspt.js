@@ -539,6 +539,34 @@ class PathTracer {
     if (norm != null && (!(norm instanceof Float32Array) || norm.length !== this._nTris * 27)) throw new RangeError('rebuildGeometry: norm must be a Float32Array of ' + this._nTris + ' x 27 floats');
     return addon.sceneRebuildGeometry(this._scene, this._nTris, tri, norm == null ? null : norm);
   }
+  /** new materials for the scene's triangles in leaf order: {mat (Float32Array, 12 per triangle), uv (Float32Array, 6 per
+   *  triangle; omitted: kept), atlas (Uint8Array, atlasRes^2 * atlasLayers RGBA8 texels; omitted: the atlas of the last call
+   *  that carried one), atlasRes, atlasLayers}.  Laid out again on the GPU; the scene then renders like one created from the
+   *  same arrays (include/fspt.h fspt_scene_update_materials, DESIGN 8.13).  Accumulator, history and exposure stay: call
+   *  clear().  Throws Error('render in flight') during a renderAsync. */
+  updateMaterials(o) {
+    if (o == null || typeof o !== 'object') throw new TypeError('updateMaterials: expected {mat, uv, atlas, atlasRes, atlasLayers}');
+    const { mat, uv, atlas, atlasRes, atlasLayers } = o;
+    if (!(mat instanceof Float32Array) || mat.length !== this._nTris * 12) throw new RangeError('updateMaterials: mat must be a Float32Array of ' + this._nTris + ' x 12 floats');
+    if (uv != null && (!(uv instanceof Float32Array) || uv.length !== this._nTris * 6)) throw new RangeError('updateMaterials: uv must be a Float32Array of ' + this._nTris + ' x 6 floats');
+    if (atlas != null) {
+      if (!Number.isInteger(atlasRes) || !Number.isInteger(atlasLayers) || atlasRes < 1 || atlasLayers < 1) throw new RangeError('updateMaterials: an atlas needs atlasRes >= 1 and atlasLayers >= 1');
+      if (!(atlas instanceof Uint8Array) || atlas.length !== atlasRes * atlasRes * atlasLayers * 4) throw new RangeError('updateMaterials: atlas must be a Uint8Array of ' + atlasRes + ' x ' + atlasRes + ' x ' + atlasLayers + ' x 4 bytes');
+    }
+    addon.sceneUpdateMaterials(this._scene, this._nTris, mat, uv == null ? null : uv, atlas == null ? null : atlas, atlas == null ? 0 : atlasRes, atlas == null ? 0 : atlasLayers);
+  }
+  /** a new environment: {env (Uint8Array RGBE, envW * envH texels; null: black), envW, envH, bins (Uint32Array, 4 per bin,
+   *  required)} (fspt_scene_update_environment, DESIGN 8.13); state stays as for updateMaterials */
+  updateEnvironment(o) {
+    if (o == null || typeof o !== 'object') throw new TypeError('updateEnvironment: expected {env, envW, envH, bins}');
+    const { env, envW, envH, bins } = o;
+    if (!(bins instanceof Uint32Array) || bins.length < 4 || bins.length % 4 !== 0) throw new RangeError('updateEnvironment: bins must be a Uint32Array of 4 words per bin, at least one bin');
+    if (env != null) {
+      if (!Number.isInteger(envW) || !Number.isInteger(envH) || envW < 1 || envH < 1) throw new RangeError('updateEnvironment: an env needs envW >= 1 and envH >= 1');
+      if (!(env instanceof Uint8Array) || env.length !== envW * envH * 4) throw new RangeError('updateEnvironment: env must be a Uint8Array of ' + envW + ' x ' + envH + ' x 4 bytes');
+    }
+    addon.sceneUpdateEnvironment(this._scene, env == null ? null : env, env == null ? 0 : envW, env == null ? 0 : envH, bins);
+  }
   /** SAH cost of the tree with its current boxes relative to the root's area (fspt_scene_sah_cost) */
   sahCost() { return addon.sceneSahCost(this._scene); }
   /** 'wavefront' (batches of ticks), 'stream' (fixed pool of live paths), 'megakernel' (include/fspt_tuning.h) */

@@ -175,20 +175,54 @@ def write_sample_map(path, counts, max_ticks):
     Image.fromarray(grey, mode="L").save(path)
 
 
+APPEARANCE_FIELDS = ("mat", "uv", "atlas", "env", "bins")
+
+
+def held_appearance(a):
+    """What a scene created from SceneArrays `a` holds of its appearance: mat / uv in a's own (leaf) order, the atlas with
+    its shape, the environment with its size, the bins - the record sequence_frame_changes compares later frames with."""
+    return dict(n_tris=int(a.n_tris), mat=np.array(a.mat, np.float32).reshape(-1, 12), uv=np.array(a.uv, np.float32).reshape(-1, 6),
+                atlas=(int(a.atlas_res), int(a.atlas_layers), None if a.atlas is None else np.array(a.atlas)),
+                env=(0, 0, None) if a.env is None else (int(a.env_w), int(a.env_h), np.array(a.env)),
+                bins=np.array(a.bins, np.uint32).reshape(-1))
+
+
+def sequence_frame_changes(held, g, order):
+    """render_sequence(bvh="refit")'s classification of a frame, as a pure function.  `held` = held_appearance of what the
+    live scene holds now, `g` = the frame's arrays in parse order, `order` = the base tree's leaf order (parse index per leaf
+    position).  None: another triangle count - the frame builds a new scene.  Else a dict with the fields of
+    APPEARANCE_FIELDS that differ from `held`, each in `held`'s form (mat / uv in the base's leaf order): empty = a plain
+    refit, anything else = an "appearance" frame that uploads exactly those."""
+    if int(g.n_tris) != held["n_tris"]:
+        return None
+    order = np.asarray(order)
+    new = held_appearance(g)
+    new["mat"], new["uv"] = new["mat"][order], new["uv"][order]
+
+    def same(x, y):
+        if isinstance(x, tuple):
+            return x[:2] == y[:2] and same(x[2], y[2])
+        return (x is None and y is None) or (x is not None and y is not None and x.shape == y.shape and np.array_equal(x.view(np.uint8), y.view(np.uint8)))
+
+    return {k: new[k] for k in APPEARANCE_FIELDS if not same(held[k], new[k])}
+
+
 def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", rebuild_above=None,
                     on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, **kw):
     """frame=N sequencing (main.js:851-866, 966-969): for every N in `frames` load `scene_pattern.format(frame=N)`
     (the per-frame scene JSON the reference's server hands out for `?frame=N`), render it, write
     `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1.
     bvh="gpu" builds every frame's tree on the render device.
-    bvh="refit" (DESIGN 8.6): the first frame builds ("sah"); a later frame with the same triangle count, materials, uvs,
-    atlas and environment keeps scene and tracer: its props are parsed without building a tree, the moved triangles go to
+    bvh="refit" (DESIGN 8.6): the first frame builds ("sah"); a later frame with the same triangle count keeps scene and
+    tracer: its props are parsed without building a tree, the moved triangles go to
     Scene.update_geometry in the first tree's leaf order, the accumulator is cleared and the auto-focus ray is shot
     against the new triangles.  A refitted frame whose Scene.sah_cost() exceeds `rebuild_above` x the cost at the last
     (re)build gets a new tree IN PLACE (Scene.rebuild_geometry, DESIGN 8.7: scene and tracer stay; the tree is the binned
-    SAH of bvh="gpu" from then on, which renders 0.94-0.95x as fast as the sweep's); None, the default: never.  Any other
-    frame - another triangle count, other materials, uvs, atlas or environment - builds a new scene.
-    on_frame(N, "build" | "refit" | "rebuild") reports what a frame did.
+    SAH of bvh="gpu" from then on, which renders 0.94-0.95x as fast as the sweep's); None, the default: never.  A kept frame
+    whose materials, uvs, atlas, environment or bins differ from what the live scene holds gets exactly those updated in place
+    after its refit (Scene.update_materials / update_environment) and reports "appearance".  A frame with another
+    triangle count builds a new scene.
+    on_frame(N, "build" | "refit" | "rebuild" | "appearance") reports what a frame did.
     temporal (bvh="refit" only): True or a dict of PathTracer.temporal_accumulate's parameters, plus "atrous": K
     for K a-trous iterations on the result.  Every frame then follows the protocol motion_begin, update_geometry, clear and
     render, temporal_accumulate, and the picture written is temporal_draw of the result (`denoise`, the firefly filter of
@@ -257,12 +291,8 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     opt.update({k: v for k, v in kw.items() if k in opt})
     base, pt, cost0, leaf_order = None, None, None, None
 
-    def same_scene(a, g):
-        eq = lambda x, y: (x is None and y is None) or (x is not None and y is not None and np.array_equal(x, y))
-        order = a.meta["tri_order"]
-        return (g.n_tris == a.n_tris and np.array_equal(g.mat.reshape(-1, 12)[order], a.mat.reshape(-1, 12))
-                and np.array_equal(g.uv.reshape(-1, 6)[order], a.uv.reshape(-1, 6)) and g.atlas_res == a.atlas_res
-                and g.atlas_layers == a.atlas_layers and eq(g.atlas, a.atlas) and eq(g.env, a.env) and eq(g.bins, a.bins))
+    atlas_sent = False
+    held = None  # the appearance the live scene holds now (not the base's: a change that persists is uploaded once)
 
     try:
         for n in frames:
@@ -270,7 +300,8 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
             how = "build"
             if base is not None:
                 g, settings = load_scene_file(path, asset_root, geometry_only=True)
-                if same_scene(base, g):
+                changes = sequence_frame_changes(held, g, base.meta["tri_order"])
+                if changes is not None:
                     tri, norm = S.geometry_in_leaf_order(leaf_order, g.tri, g.norm)
                     if temporal is not None:
                         pt.scene.motion_begin()
@@ -280,6 +311,19 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                         leaf_order = S.compose_order(leaf_order, pt.rebuild_geometry(tri, norm))
                         cost0 = pt.scene.sah_cost()
                         how = "rebuild"
+                    if changes:
+                        #  what differs goes to the live scene in place: tracer, history and exposure stay
+                        if {"mat", "uv", "atlas"} & set(changes):
+                            # the atlas goes along when it changed - and once at the scene's first update, which retains it
+                            res, layers, atlas = changes["atlas"] if "atlas" in changes else (None, None, None) if atlas_sent else held["atlas"]
+                            atlas_sent = True
+                            cur = np.asarray(leaf_order)  # mat / uv go in the CURRENT leaf order (a rebuild composed it)
+                            pt.update_materials(g.mat.reshape(-1, 12)[cur], g.uv.reshape(-1, 6)[cur] if "uv" in changes else None,
+                                                atlas, res, layers)
+                        if {"env", "bins"} & set(changes):
+                            pt.update_environment(g.env, g.env_w, g.env_h, g.bins)
+                        held.update(changes)
+                        how = "appearance"
             if how == "build":
                 if pt is not None:
                     pt.close(); pt.scene.close()
@@ -287,6 +331,7 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                 pt = PathTracer(base, width, height, device=device, num_bounces=bounces)
                 cost0 = pt.scene.sah_cost() if rebuild_above is not None else None
                 leaf_order = base.meta["tri_order"]
+                held, atlas_sent = held_appearance(base), False
                 if variance:
                     pt.temporal_set_moments(True)
                 if temporal is not None and clamp is not None:

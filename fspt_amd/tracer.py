@@ -448,6 +448,77 @@ class Scene:
         L.check(L.lib().fspt_scene_rebuild_geometry(self._h, L.fptr(tri), None if norm is None else L.fptr(norm), L.u32ptr(order)))
         return order
 
+    def _materials_args(self, fn, mat, uv, atlas, atlas_res, atlas_layers):
+        n = int(self.arrays.n_tris)
+        mat = np.ascontiguousarray(mat, dtype=np.float32)
+        if mat.size != n * 12:
+            raise ValueError(f"{fn}: mat has {mat.size} elements, the scene needs {n} x 12")
+        if uv is not None:
+            uv = np.ascontiguousarray(uv, dtype=np.float32)
+            if uv.size != n * 6:
+                raise ValueError(f"{fn}: uv has {uv.size} elements, the scene needs {n} x 6")
+        res = layers = 0
+        if atlas is not None:
+            atlas = np.ascontiguousarray(atlas, dtype=np.uint8)
+            if atlas_res is None or atlas_layers is None:
+                raise ValueError(f"{fn}: an atlas needs atlas_res and atlas_layers")
+            res, layers = int(atlas_res), int(atlas_layers)
+            if res < 0 or layers < 0 or atlas.size != res * res * layers * 4:
+                raise ValueError(f"{fn}: atlas has {atlas.size} bytes, {res} x {res} x {layers} RGBA8 texels need {res * res * layers * 4}")
+        return (L.fptr(mat), None if uv is None else L.fptr(uv), None if atlas is None else L.u8ptr(atlas), res, layers), (mat, uv, atlas)
+
+    def update_materials(self, mat, uv=None, atlas=None, atlas_res=None, atlas_layers=None):
+        """New matTex records (12 floats per triangle) and, unless None, uvs (6 per triangle) in the scene's current LEAF
+        order, and a new atlas (RGBA8, atlas_res^2 * atlas_layers texels; any resolution and layer count) - or None: the atlas
+        of this scene's most recent update_materials call that carried one.  The texture sets, the tiled and interleaved
+        images and the material part of the hit records are laid out again on the GPU; afterwards the scene renders bit for
+        bit like a Scene created from the same arrays (fspt_scene_update_materials).  Tracers stay valid and
+        keep their accumulators, histories and exposure; `self.arrays` is not touched."""
+        args, keep = self._materials_args("update_materials", mat, uv, atlas, atlas_res, atlas_layers)
+        L.check(L.lib().fspt_scene_update_materials(self._h, *args))
+
+    @staticmethod
+    def _environment_args(fn, env, env_w, env_h, bins):
+        if bins is None:
+            raise ValueError(f"{fn}: bins are required (scene.env_bins)")
+        bins = np.ascontiguousarray(_u32_array(bins, "bins"), dtype=np.uint32)
+        if bins.size % 4:
+            raise ValueError(f"{fn}: bins has {bins.size} elements, not a multiple of 4")
+        w = h = 0
+        if env is not None:
+            env = np.ascontiguousarray(env, dtype=np.uint8)
+            w, h = int(env_w), int(env_h)
+            if w < 0 or h < 0 or env.size != w * h * 4:
+                raise ValueError(f"{fn}: env has {env.size} bytes, {w} x {h} RGBE texels need {w * h * 4}")
+        return (None if env is None else L.u8ptr(env), w, h, L.u32ptr(bins), bins.size // 4), (env, bins)
+
+    def update_environment(self, env, env_w, env_h, bins):
+        """A new environment map (RGBE in RGBA8, env_w * env_h texels; None = black) and its importance bins (scene.env_bins),
+        tiled on the GPU (fspt_scene_update_environment); everything else as update_materials."""
+        args, keep = self._environment_args("update_environment", env, env_w, env_h, bins)
+        L.check(L.lib().fspt_scene_update_environment(self._h, *args))
+
+    APPEARANCE = ("tex_sets", "atlas", "atlas4", "env", "bins", "hitrec")  # read_appearance's `what`
+
+    def read_appearance(self, what):
+        """The bytes of one of the buffers an appearance update writes, as the device holds them (uint8;
+        fspt_scene_read_appearance): 0 texture-set table, 1 single-layer tiled images, 2 interleaved images, 3 environment
+        tiles, 4 bins, 5 hit records - or its name in Scene.APPEARANCE."""
+        what = self.APPEARANCE.index(what) if isinstance(what, str) else int(what)
+        n = C.c_uint64()
+        L.check(L.lib().fspt_scene_read_appearance(self._h, what, None, 0, C.byref(n)))
+        out = np.zeros(int(n.value), np.uint8)
+        if out.size:
+            L.check(L.lib().fspt_scene_read_appearance(self._h, what, C.c_void_p(out.ctypes.data), out.size, C.byref(n)))
+        return out
+
+    def last_appearance(self):
+        """The most recent update_materials / update_environment as a dict: ms (GPU, first kernel to last), launches,
+        uploaded (bytes), retained (bytes of the raw atlas kept on the device; 0 for a scene never updated)."""
+        ms, nl, up, rt = C.c_float(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+        L.check(L.lib().fspt_scene_last_appearance_ms(self._h, C.byref(ms), C.byref(nl), C.byref(up), C.byref(rt)))
+        return dict(ms=float(ms.value), launches=int(nl.value), uploaded=int(up.value), retained=int(rt.value))
+
     def last_rebuild_ms(self):
         """The most recent rebuild_geometry as a dict: build_ms (GPU, the build kernels), install_ms (GPU, gather + refit),
         host_ms (the numbering), launches, readbacks (fspt_scene_last_rebuild_ms)."""
@@ -761,6 +832,15 @@ class PathTracer:
     def update_geometry(self, tri, norm=None):
         """Scene.update_geometry on this tracer's scene (every tracer of the scene sees it); call clear() to restart the mean."""
         self.scene.update_geometry(tri, norm)
+
+    def update_materials(self, mat, uv=None, atlas=None, atlas_res=None, atlas_layers=None):
+        """Scene.update_materials on this tracer's scene (every tracer of the scene sees it); the accumulator, the temporal
+        history, the exposure and the bloom state stay - call clear() to restart the mean."""
+        self.scene.update_materials(mat, uv, atlas, atlas_res, atlas_layers)
+
+    def update_environment(self, env, env_w, env_h, bins):
+        """Scene.update_environment on this tracer's scene; state stays as for update_materials."""
+        self.scene.update_environment(env, env_w, env_h, bins)
 
     def rebuild_geometry(self, tri, norm=None):
         """Scene.rebuild_geometry on this tracer's scene: a new tree in place; returns the new leaf order."""
@@ -1109,6 +1189,16 @@ class MultiPathTracer:
             if norm.size != n * 27:
                 raise ValueError(f"update_geometry: norm has {norm.size} elements, the scene needs {n} x 27")
         L.check(L.lib().fspt_multi_update_geometry(self._m, L.fptr(tri), None if norm is None else L.fptr(norm)))
+
+    def update_materials(self, mat, uv=None, atlas=None, atlas_res=None, atlas_layers=None):
+        """Scene.update_materials (host arrays) on every device's copy of the scene (fspt_multi_update_materials)."""
+        args, keep = Scene._materials_args(self, "update_materials", mat, uv, atlas, atlas_res, atlas_layers)
+        L.check(L.lib().fspt_multi_update_materials(self._m, *args))
+
+    def update_environment(self, env, env_w, env_h, bins):
+        """Scene.update_environment on every device's copy of the scene (fspt_multi_update_environment)."""
+        args, keep = Scene._environment_args("update_environment", env, env_w, env_h, bins)
+        L.check(L.lib().fspt_multi_update_environment(self._m, *args))
 
     def rebuild_geometry(self, tri, norm=None):
         """Scene.rebuild_geometry (host arrays) on every device's copy of the scene (fspt_multi_rebuild_geometry); every

@@ -89,7 +89,7 @@ int fspt_scene_depth(const fspt_scene *scene, uint32_t *depth); /* Maximum depth
  * scene (targets stay valid; errors leave it as it was); order_out (or NULL)[k] = input index of the triangle now at leaf position k: the leaf order of later calls */
 int fspt_scene_update_geometry(fspt_scene *s, const float *tri, const float *norm); int fspt_scene_rebuild_geometry(fspt_scene *s, const float *tri, const float *norm, uint32_t *order_out); /* host pointers */
 int fspt_scene_update_geometry_device(fspt_scene *s, const float *tri, const float *norm); int fspt_scene_rebuild_geometry_device(fspt_scene *s, const float *tri, const float *norm, uint32_t *order_out); /* memory of the scene's device */
-int fspt_scene_sah_cost(fspt_scene *s, double *cost); /* SAH cost of the current boxes relative to the root's area, float64 */
+int fspt_scene_sah_cost(fspt_scene *s, double *cost); /* SAH cost of the current boxes relative to the root's area, float64 */ /* Appearance: new matTex (12 floats per triangle, current leaf order), uvs (or NULL: kept) and atlas (or NULL: the one the scene's last update_materials call carried, FSPT_E_STATE when none did; res / layers may differ from the scene's) | new environment (NULL = black) and bins.  Laid out on the GPU; afterwards the scene renders bit for bit like fspt_scene_create of the same arrays.  Blocking; ordered against every target like fspt_scene_update_geometry; validated like fspt_scene_create; an error leaves the scene as it was; accumulators and per-target state are not touched. */ int fspt_scene_update_materials(fspt_scene *s, const float *mat, const float *uv, const uint8_t *atlas, uint32_t atlas_res, uint32_t atlas_layers); int fspt_scene_update_environment(fspt_scene *s, const uint8_t *env, uint32_t env_w, uint32_t env_h, const uint32_t *bins, uint32_t n_bins);
 
 /* ------------------------------------------------------------------------
  * Render target.  Replaces initBuffers (main.js:598-617): the RGBA32F screen textures (a single accumulator here: each

@@ -64,6 +64,18 @@ int fspt_scene_last_update_ms(fspt_scene *scene, float *ms, uint32_t *launches);
  * included), GPU ms of the install kernels (slot map, permute, gather, child references, the refit), host ms of the
  * numbering, kernels launched, readbacks (the builder's 4-byte ones + the one of the topology).  Any pointer may be NULL. */
 int fspt_scene_last_rebuild_ms(fspt_scene *scene, float *build_ms, float *install_ms, float *host_ms, uint32_t *launches, uint32_t *readbacks);
+/* Appearance update, test and measurement hooks.
+ * what: 0 texture-set table, 1 single-layer tiled images, 2 interleaved images, 3 environment tiles, 4 bins, 5 hit records.
+ * Copies min(cap, size) bytes and writes the size to *bytes (out NULL: only that).  Blocking. */
+int fspt_scene_read_appearance(fspt_scene *s, int what, void *out, uint64_t cap, uint64_t *bytes);
+/* the last appearance update: kernels first to last (HIP events; the read-back of the per-layer flags and the host's set
+ * classification lie between them), launches, bytes uploaded, raw-atlas bytes retained on the device (0: never updated) */
+int fspt_scene_last_appearance_ms(fspt_scene *s, float *ms, uint32_t *launches, uint64_t *uploaded, uint64_t *retained);
+/* The set classification fspt_scene_create and fspt_scene_update_materials share, on the host alone: per triangle its
+ * texture set, *n_sets, and the first min(cap_sets, *n_sets) 12-word rows of the set table, from matTex, the per-layer
+ * "every texel equal" flags and first texels, under the current interleaving budget.  No device. */
+int fspt_texset_classify_eval(const float *mat, uint32_t n_tris, uint32_t n_layers, uint32_t res, const uint8_t *is_const, const uint32_t *first,
+                              uint32_t *tri_set, uint32_t *n_sets, uint32_t *tab, uint32_t cap_sets);
 /* fspt_intersect (fspt.h) walking the two-level nodes (two_level != 0; FSPT_E_INVALID when the scene has none): t, index
  * and the per-ray step / leaf counts must equal the one-level walk's (tests). */
 int fspt_intersect_form(fspt_scene *scene, int two_level, const float *rays, uint32_t n, float *t_out, int32_t *index_out,

@@ -113,6 +113,13 @@ SIGNATURES = {
     "fspt_scene_sah_cost": (C.c_int, [_VP, C.POINTER(C.c_double)]),
     "fspt_scene_last_update_ms": (C.c_int, [_VP, _F, _U32]),
     "fspt_multi_update_geometry": (C.c_int, [_VP, _F, _F]),
+    "fspt_scene_set_pose": (C.c_int, [_VP, _U32, C.c_uint32, _F, _F]),
+    "fspt_scene_update_transforms": (C.c_int, [_VP, _F, C.c_uint32]),
+    "fspt_multi_set_pose": (C.c_int, [_VP, _U32, C.c_uint32, _F, _F]),
+    "fspt_multi_update_transforms": (C.c_int, [_VP, _F, C.c_uint32]),
+    "fspt_scene_read_pose": (C.c_int, [_VP, _F, _F]),
+    "fspt_scene_last_pose_ms": (C.c_int, [_VP, _F, _F, _U32]),
+    "fspt_pose_matrices_eval": (C.c_int, [_F, C.c_uint32, _F, _U32]),
     "fspt_scene_rebuild_geometry": (C.c_int, [_VP, _F, _F, _U32]),
     "fspt_scene_rebuild_geometry_device": (C.c_int, [_VP, _VP, _VP, _VP]),
     "fspt_scene_last_rebuild_ms": (C.c_int, [_VP, _F, _F, _F, _U32, _U32]),

@@ -727,6 +727,7 @@ int fspt_scene_destroy(fspt_scene *s) {
   hipFree(s->l_alias); hipFree(s->l_rec); hipFree(s->l_p); hipFree(s->l_pick); hipFree(s->motion);
   fspt::refit_release(s);
   fspt::appearance_release(s);
+  fspt::pose_release(s);
   delete s;
   return FSPT_OK;
 }
@@ -1471,6 +1472,20 @@ int geometry_changed_lights(fspt_scene *s) {
 
 extern "C" {
 
+// the refit of update_geometry / update_transforms proper: tri / norm are device memory, the call is ordered and s->rf prepared
+static int refit_device_arrays(fspt_scene *s, const float *tri, const float *norm, const char *fn) {
+  int rc = FSPT_OK;
+  if (!s->quads && s->n_interior) { // a scene created from refitted boxes may have two-level nodes where this one had none
+    HIP_TRY(hipMalloc(&s->quads, (size_t)s->n_interior * fspt::QUAD_F4 * 16u));
+  }
+  int finite = 1, quads_ok = 0;
+  rc = fspt::refit_run(s, tri, norm, &finite, &quads_ok);
+  if (rc) return rc;
+  if (!finite) { fspt_set_error("%s: a value of tri / norm is not finite (scene unchanged)", fn); return FSPT_E_INVALID; }
+  s->d.quads = quads_ok ? (const float4 *)s->quads : nullptr;
+  return geometry_changed_lights(s);
+}
+
 static int update_geometry(fspt_scene *s, const float *tri, const float *norm, bool on_device, const char *fn) {
   if (!s || !tri) { fspt_set_error("%s: NULL scene or tri", fn); return FSPT_E_INVALID; }
   if (!on_device) { // the host form's check needs no device: refuse before anything is touched
@@ -1491,20 +1506,13 @@ static int update_geometry(fspt_scene *s, const float *tri, const float *norm, b
   const size_t T = s->n_tris;
   if (!on_device) {
     if (!s->rf.stage) HIP_TRY(hipMalloc((void **)&s->rf.stage, T * 36 * 4));
+    s->pose.posed = false; // (the staging array no longer holds a pose's output)
     HIP_TRY(hipMemcpy(s->rf.stage, tri, T * 9 * 4, hipMemcpyHostToDevice));
     if (norm) HIP_TRY(hipMemcpy(s->rf.stage + T * 9, norm, T * 27 * 4, hipMemcpyHostToDevice));
     tri = s->rf.stage;
     if (norm) norm = s->rf.stage + T * 9;
   }
-  if (!s->quads && s->n_interior) { // a scene created from refitted boxes may have two-level nodes where this one had none
-    HIP_TRY(hipMalloc(&s->quads, (size_t)s->n_interior * fspt::QUAD_F4 * 16u));
-  }
-  int finite = 1, quads_ok = 0;
-  rc = fspt::refit_run(s, tri, norm, &finite, &quads_ok);
-  if (rc) return rc;
-  if (!finite) { fspt_set_error("%s: a value of tri / norm is not finite (scene unchanged)", fn); return FSPT_E_INVALID; }
-  s->d.quads = quads_ok ? (const float4 *)s->quads : nullptr;
-  return geometry_changed_lights(s);
+  return refit_device_arrays(s, tri, norm, fn);
 }
 
 int fspt_scene_update_geometry(fspt_scene *s, const float *tri, const float *norm) {
@@ -1519,6 +1527,137 @@ int fspt_scene_last_update_ms(fspt_scene *s, float *ms, uint32_t *launches) {
   if (!s) { fspt_set_error("fspt_scene_last_update_ms: NULL scene"); return FSPT_E_INVALID; }
   if (ms) *ms = s->rf.last_ms;
   if (launches) *launches = s->rf.last_launches;
+  return FSPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// GPU part transforms (kernel in fspt_pose.hip)
+// ---------------------------------------------------------------------------
+// The rule's host part, float64 in the stated order (tests/pose_ref.py restates it): per part a (12) | D (9) | N (9).
+// NULL: every part is fine; else the reason, with *bad = the part.
+static const char *pose_matrices(const float *xf, uint32_t n_parts, float *out, uint32_t *bad) {
+  for (uint32_t p = 0; p < n_parts; ++p) {
+    const float *x = xf + (size_t)p * 12;
+    float *o = out + (size_t)p * 30;
+    *bad = p;
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(x[i])) return "an entry is not finite";
+    double A[3][3], Cf[3][3];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) A[i][j] = (double)x[4 * i + j];
+    double q = 0.0;
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) q = q + A[i][j] * A[i][j];
+    const double g = std::sqrt(q / 3.0);
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+        Cf[i][j] = A[i1][j1] * A[i2][j2] - A[i1][j2] * A[i2][j1];
+      }
+    const double det = (A[0][0] * Cf[0][0] + A[0][1] * Cf[0][1]) + A[0][2] * Cf[0][2];
+    if (det == 0.0) return "the matrix is singular";
+    const double gg = g * g;
+    for (int i = 0; i < 12; ++i) o[i] = x[i];
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        o[12 + 3 * i + j] = (float)(A[i][j] / g);
+        o[21 + 3 * i + j] = (float)(Cf[i][j] / gg);
+      }
+    for (int i = 12; i < 30; ++i) if (!std::isfinite(o[i])) return "a derived matrix is not finite";
+  }
+  return nullptr;
+}
+
+int fspt_pose_matrices_eval(const float *xf, uint32_t n_parts, float *out, uint32_t *bad_part) {
+  if (!xf || !out || n_parts == 0) { fspt_set_error("fspt_pose_matrices_eval: NULL/empty argument"); return FSPT_E_INVALID; }
+  uint32_t bad = 0;
+  if (const char *why = pose_matrices(xf, n_parts, out, &bad)) {
+    if (bad_part) *bad_part = bad;
+    fspt_set_error("fspt_pose_matrices_eval: part %u: %s", bad, why);
+    return FSPT_E_INVALID;
+  }
+  return FSPT_OK;
+}
+
+int fspt_scene_set_pose(fspt_scene *s, const uint32_t *part, uint32_t n_parts, const float *tri, const float *norm) {
+  if (!s) { fspt_set_error("fspt_scene_set_pose: NULL scene"); return FSPT_E_INVALID; }
+  if (!part) { // drop the pose
+    if (!s->pose.part && !s->pose.mats) return FSPT_OK;
+    int rc = check_device(s->device);
+    if (rc) return rc;
+    fspt::pose_release(s);
+    return FSPT_OK;
+  }
+  if (!tri || n_parts == 0) { fspt_set_error("fspt_scene_set_pose: tri is NULL or n_parts is 0"); return FSPT_E_INVALID; }
+  const size_t T = s->n_tris;
+  for (size_t i = 0; i < T; ++i) if (part[i] >= n_parts) { fspt_set_error("fspt_scene_set_pose: part[%zu] = %u, n_parts = %u", i, part[i], n_parts); return FSPT_E_INVALID; }
+  for (size_t i = 0; i < T * 9; ++i) if (!std::isfinite(tri[i])) { fspt_set_error("fspt_scene_set_pose: tri[%zu] is not finite", i); return FSPT_E_INVALID; }
+  for (size_t i = 0; norm && i < T * 27; ++i) if (!std::isfinite(norm[i])) { fspt_set_error("fspt_scene_set_pose: norm[%zu] is not finite", i); return FSPT_E_INVALID; }
+  if (!s->rf.ok) {
+    fspt_set_error("fspt_scene_set_pose: scene is not refittable (the leaves' triStarts must be distinct and tile [0, n_tris), every node have one parent)");
+    return FSPT_E_STATE;
+  }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  // the new arrays first: an allocation that fails leaves the old pose
+  uint32_t *d_part = nullptr;
+  float *d_rest = nullptr;
+  hipError_t e = hipMalloc((void **)&d_part, (T ? T : 1) * 4);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_rest, (T ? T : 1) * (norm ? 36 : 9) * 4);
+  if (e == hipSuccess) e = hipMemcpy(d_part, part, T * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_rest, tri, T * 9 * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess && norm) e = hipMemcpy(d_rest + T * 9, norm, T * 27 * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    hipFree(d_part); hipFree(d_rest);
+    (void)hipGetLastError();
+    fspt_set_error("fspt_scene_set_pose: %s (%zu triangles)", hipGetErrorString(e), T);
+    return e == hipErrorOutOfMemory ? FSPT_E_NOMEM : FSPT_E_HIP;
+  }
+  hipFree(s->pose.part); hipFree(s->pose.rest);
+  s->pose.part = d_part; s->pose.rest = d_rest;
+  s->pose.has_norm = norm != nullptr;
+  s->pose.n_parts = n_parts;
+  s->pose.posed = false;
+  return FSPT_OK;
+}
+
+int fspt_scene_update_transforms(fspt_scene *s, const float *xf, uint32_t n_parts) {
+  if (!s || !xf) { fspt_set_error("fspt_scene_update_transforms: NULL scene or xf"); return FSPT_E_INVALID; }
+  if (!s->pose.part) { fspt_set_error("fspt_scene_update_transforms: the scene has no pose (fspt_scene_set_pose)"); return FSPT_E_STATE; }
+  if (n_parts != s->pose.n_parts) { fspt_set_error("fspt_scene_update_transforms: %u matrices, the pose has %u parts", n_parts, s->pose.n_parts); return FSPT_E_INVALID; }
+  std::vector<float> mats((size_t)n_parts * 30);
+  uint32_t bad = 0;
+  if (const char *why = pose_matrices(xf, n_parts, mats.data(), &bad)) {
+    fspt_set_error("fspt_scene_update_transforms: part %u: %s (scene unchanged)", bad, why);
+    return FSPT_E_INVALID;
+  }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  rc = geometry_order_targets(s);
+  if (rc) return rc;
+  rc = fspt::refit_prepare(s);
+  if (rc) return rc;
+  const size_t T = s->n_tris;
+  if (!s->rf.stage) HIP_TRY(hipMalloc((void **)&s->rf.stage, T * 36 * 4));
+  rc = fspt::pose_run(s, mats.data());
+  if (rc) return rc;
+  return refit_device_arrays(s, s->rf.stage, s->pose.has_norm ? s->rf.stage + T * 9 : nullptr, "fspt_scene_update_transforms");
+}
+
+int fspt_scene_read_pose(fspt_scene *s, float *tri, float *norm) {
+  if (!s || (!tri && !norm)) { fspt_set_error("fspt_scene_read_pose: NULL argument"); return FSPT_E_INVALID; }
+  if (!s->pose.part || !s->pose.posed) { fspt_set_error("fspt_scene_read_pose: no fspt_scene_update_transforms since the pose was set, the scene rebuilt or its geometry uploaded"); return FSPT_E_STATE; }
+  if (norm && !s->pose.has_norm) { fspt_set_error("fspt_scene_read_pose: the pose has no rest norm"); return FSPT_E_STATE; }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  const size_t T = s->n_tris;
+  if (tri) HIP_TRY(hipMemcpy(tri, s->rf.stage, T * 9 * 4, hipMemcpyDeviceToHost));
+  if (norm) HIP_TRY(hipMemcpy(norm, s->rf.stage + T * 9, T * 27 * 4, hipMemcpyDeviceToHost));
+  return FSPT_OK;
+}
+
+int fspt_scene_last_pose_ms(fspt_scene *s, float *transform_ms, float *refit_ms, uint32_t *launches) {
+  if (!s) { fspt_set_error("fspt_scene_last_pose_ms: NULL scene"); return FSPT_E_INVALID; }
+  if (transform_ms) *transform_ms = s->pose.last_ms;
+  if (refit_ms) *refit_ms = s->rf.last_ms;
+  if (launches) *launches = s->rf.last_launches + 1u;
   return FSPT_OK;
 }
 

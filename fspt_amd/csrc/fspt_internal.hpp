@@ -9,7 +9,7 @@
 // and the device side, declared in fspt_device.hpp:
 //   fspt_kernels.hip       every kernel that reads a DScene: the path tracer, the test passes, k_features, k_temporal_gbuffer
 //   fspt_post.hip          every kernel that reads only images: what fspt_post.cpp launches, but for those two
-//   fspt_bvh_build.hip     the GPU BVH builder;  fspt_refit.hip  in-place refit and rebuild
+//   fspt_bvh_build.hip     the GPU BVH builder;  fspt_refit.hip  in-place refit and rebuild;  fspt_pose.hip  part transforms
 //   fspt_appearance.hip    in-place appearance update: the texture-set, atlas and environment layouts and the material part of the hit records
 #pragma once
 #include "../../include/fspt.h"
@@ -103,6 +103,20 @@ struct fspt_scene {
     uint32_t last_launches = 0;
     uint64_t last_uploaded = 0;     // host -> device bytes of the last update
   } ap;
+  // fspt_scene_set_pose / fspt_scene_update_transforms (fspt_pose.hip): per triangle (current leaf order) a part
+  // id and the rest mesh, on the device; a rebuild permutes them with the triangles.  A scene that never sets a pose
+  // allocates nothing for it; the posed arrays go to rf.stage.
+  struct Pose {
+    uint32_t *part = nullptr;       // n_tris ids < n_parts (NULL: no pose)
+    float *rest = nullptr;          // n_tris x 9 rest vertices | n_tris x 27 rest normTex records when has_norm
+    bool has_norm = false;
+    uint32_t n_parts = 0;
+    float *mats = nullptr;          // the last call's n_parts x 30 floats (a | D | N); grows as needed
+    uint32_t mats_cap = 0;          // parts it holds
+    bool posed = false;             // rf.stage holds the last update_transforms' output (fspt_scene_read_pose)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    float last_ms = 0.0f;           // k_pose_transform of the last call
+  } pose;
 };
 // Material texture sets: what fspt_scene_create and fspt_scene_update_materials derive from matTex's layer ids and
 // the per-layer "every texel equal" flags - the sets in first-appearance order, each triangle's set, a set's form under the
@@ -149,6 +163,10 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
 int appearance_materials(fspt_scene *s, const float *mat, const float *uv, const uint8_t *atlas, uint32_t res, uint32_t layers);
 int appearance_environment(fspt_scene *s, const uint8_t *env, uint32_t w, uint32_t h, const uint32_t *bins, uint32_t n_bins);
 void appearance_release(fspt_scene *s);
+// fspt_pose.hip.  pose_run: s->pose set, s->rf.stage allocated, the call ordered against the targets;
+// mats_host = n_parts x 30 floats (a | D | N).  Uploads them, runs k_pose_transform into s->rf.stage and waits.
+int pose_run(fspt_scene *s, const float *mats_host);
+void pose_release(fspt_scene *s);
 }
 int light_table_ensure(fspt_scene *s); // (fspt_api.cpp) builds the table once; FSPT_OK when it exists
 #ifndef FSPT_LIGHTS_ENV_Q_MAX

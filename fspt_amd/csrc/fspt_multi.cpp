@@ -217,6 +217,22 @@ int fspt_multi_update_geometry(fspt_multi *m, const float *tri, const float *nor
   }
   return FSPT_OK;
 }
+int fspt_multi_set_pose(fspt_multi *m, const uint32_t *part, uint32_t n_parts, const float *tri, const float *norm) {
+  if (!m) { fspt_set_error("fspt_multi_set_pose: NULL handle"); return FSPT_E_INVALID; }
+  for (fspt_scene *s : m->scenes) { // (bad arguments are refused by the first scene, before anything is written)
+    const int rc = fspt_scene_set_pose(s, part, n_parts, tri, norm);
+    if (rc) return rc;
+  }
+  return FSPT_OK;
+}
+int fspt_multi_update_transforms(fspt_multi *m, const float *xf, uint32_t n_parts) {
+  if (!m) { fspt_set_error("fspt_multi_update_transforms: NULL handle"); return FSPT_E_INVALID; }
+  for (fspt_scene *s : m->scenes) { // (a bad matrix is refused by the first scene, before anything is written)
+    const int rc = fspt_scene_update_transforms(s, xf, n_parts);
+    if (rc) return rc;
+  }
+  return FSPT_OK;
+}
 int fspt_multi_update_materials(fspt_multi *m, const float *mat, const float *uv, const uint8_t *atlas, uint32_t atlas_res, uint32_t atlas_layers) {
   if (!m) { fspt_set_error("fspt_multi_update_materials: NULL handle"); return FSPT_E_INVALID; }
   for (fspt_scene *s : m->scenes) { // (bad arguments are refused by the first scene, before anything is written)

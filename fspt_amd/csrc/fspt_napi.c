@@ -314,6 +314,33 @@ static napi_value SceneRebuildGeometry(napi_env env, napi_callback_info info) {
   FSPT_OK_OR_THROW(fspt_scene_rebuild_geometry((fspt_scene *)h, (const float *)tri, (const float *)norm, (uint32_t *)order));
   return ta;
 }
+/* sceneSetPose(scene, nTris, part Uint32Array | null, nParts, tri Float32Array | null, norm Float32Array | null):
+ * fspt_scene_set_pose.  part null drops the pose; else one id < nParts per triangle and the rest mesh, 9 / 27
+ * floats per triangle.  The guard of sceneUpdateGeometry. */
+static napi_value SceneSetPose(napi_env env, napi_callback_info info) {
+  napi_value a[6]; void *h, *part = NULL, *tri = NULL, *norm = NULL; size_t np = 0, nt = 0, nn = 0; uint32_t n = 0, parts = 0;
+  if (get_args(env, info, 6, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[1], &n));
+  if (typed(env, a[2], napi_uint32_array, 1, &part, &np)) return NULL;
+  if (!part) { FSPT_OK_OR_THROW(fspt_scene_set_pose((fspt_scene *)h, NULL, 0, NULL, NULL)); return undefined(env); }
+  NAPI_OK(napi_get_value_uint32(env, a[3], &parts));
+  if (typed(env, a[4], napi_float32_array, 0, &tri, &nt) || typed(env, a[5], napi_float32_array, 1, &norm, &nn)) return NULL;
+  if (np != (size_t)n || nt != (size_t)n * 9 || (norm && nn != (size_t)n * 27)) {
+    napi_throw_range_error(env, NULL, "fspt_napi: setPose needs 1 id (part), 9 floats (tri) and 27 floats (norm) per triangle of the scene");
+    return NULL;
+  }
+  FSPT_OK_OR_THROW(fspt_scene_set_pose((fspt_scene *)h, (const uint32_t *)part, parts, (const float *)tri, (const float *)norm));
+  return undefined(env);
+}
+/* sceneUpdateTransforms(scene, xf Float32Array): fspt_scene_update_transforms with xf.length / 12 parts. */
+static napi_value SceneUpdateTransforms(napi_env env, napi_callback_info info) {
+  napi_value a[2]; void *h, *xf = NULL; size_t nx = 0;
+  if (get_args(env, info, 2, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  if (typed(env, a[1], napi_float32_array, 0, &xf, &nx)) return NULL;
+  if (nx == 0 || nx % 12) { napi_throw_range_error(env, NULL, "fspt_napi: updateTransforms needs 12 floats per part"); return NULL; }
+  FSPT_OK_OR_THROW(fspt_scene_update_transforms((fspt_scene *)h, (const float *)xf, (uint32_t)(nx / 12)));
+  return undefined(env);
+}
 /* sceneUpdateMaterials(scene, nTris, mat Float32Array, uv Float32Array | null, atlas Uint8Array | null, atlasRes, atlasLayers):
  * fspt_scene_update_materials.  12 / 6 floats per triangle of the scene; an atlas holds atlasRes^2 * atlasLayers
  * RGBA8 texels (null: the atlas of the scene's last call that carried one).  The guard of sceneUpdateGeometry. */
@@ -1375,7 +1402,7 @@ static napi_value AbiVersion(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
-      {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"targetCreate", TargetCreate},
+      {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"sceneSetPose", SceneSetPose}, {"sceneUpdateTransforms", SceneUpdateTransforms}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
       {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},

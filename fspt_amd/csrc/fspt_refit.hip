@@ -7,7 +7,7 @@
 //   k_refit_quads       the two-level nodes from the refitted 64-byte nodes + fspt_scene_create's usability test
 // and what installs a NEW tree over the same triangles (fspt_scene_rebuild_geometry; rebuild_run below):
 //   k_rebuild_slot_map  triangle -> the old leaf slot of the leaf that owns it (one writer per triangle)
-//   k_rebuild_permute   the caller's tri / norm in the new leaf order (what refit_run is then fed)
+//   k_rebuild_permute   the caller's tri / norm in the new leaf order (what refit_run is then fed); the pose of DESIGN 8.14
 //   k_rebuild_gather    per NEW leaf slot: the 192-byte hit record of its triangle's old slot (12 lanes x 16 bytes), slot_tri,
 //                       and the "-1" padding of the leaf records
 //   k_rebuild_nodes     the interior nodes' child references
@@ -314,6 +314,8 @@ struct RebuildGuard {
   BvhGpuDevice bt;
   uint32_t *d_map = nullptr;
   int32_t *d_cref = nullptr;
+  uint32_t *p_part = nullptr; // the pose in the new leaf order
+  float *p_rest = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};
   bool keep = false;
   ~RebuildGuard() {
@@ -322,6 +324,7 @@ struct RebuildGuard {
     for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
     if (keep) return;
     hipFree(ns.nodes); hipFree(ns.quads); hipFree(ns.tris); hipFree(ns.slot_tri); hipFree(ns.shade); hipFree(ns.motion);
+    hipFree(p_part); hipFree(p_rest);
     refit_release(&ns);
   }
 };
@@ -393,6 +396,11 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
   REBUILD_ALLOC(&ns.rf.stage, (size_t)T * 36 * 4); // tri | norm in the new leaf order; the scene's staging array from now on
   REBUILD_ALLOC(&G.d_map, (size_t)T * 4);
   REBUILD_ALLOC(&G.d_cref, cref.size() * 4);
+  const fspt_scene::Pose &P = s->pose;
+  if (P.part) {
+    REBUILD_ALLOC(&G.p_part, (size_t)T * 4);
+    REBUILD_ALLOC(&G.p_rest, (size_t)T * (P.has_norm ? 36 : 9) * 4);
+  }
   rc = refit_prepare(&ns);
   if (rc) return rc;
   HIP_TRY(hipEventCreate(&G.ev[0]));
@@ -410,6 +418,15 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
   hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 9, BS)), dim3(BS), 0, st, tri, G.bt.order, T, 9u, ptri);
   launches += 2;
   if (norm) { hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 27, BS)), dim3(BS), 0, st, norm, G.bt.order, T, 27u, pnorm); ++launches; }
+  if (P.part) { // the pose follows its triangles: part ids (as words), rest vertices, rest normTex records
+    hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T, BS)), dim3(BS), 0, st, (const float *)P.part, G.bt.order, T, 1u, (float *)G.p_part);
+    hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 9, BS)), dim3(BS), 0, st, P.rest, G.bt.order, T, 9u, G.p_rest);
+    launches += 2;
+    if (P.has_norm) {
+      hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 27, BS)), dim3(BS), 0, st, P.rest + (size_t)T * 9, G.bt.order, T, 27u, G.p_rest + (size_t)T * 9);
+      ++launches;
+    }
+  }
   hipLaunchKernelGGL(k_rebuild_gather, dim3(blocks_for(n_slots * 12, BS)), dim3(BS), 0, st, (const float4 *)s->shade, old_slots, G.d_map, G.bt.order,
                      ns.rf.d_leaf, nl, LS, T, (float4 *)ns.shade, (uint32_t *)ns.slot_tri, (float *)ns.tris);
   ++launches;
@@ -433,6 +450,11 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
   G.keep = true;
   hipFree(s->nodes); hipFree(s->quads); hipFree(s->tris); hipFree(s->slot_tri); hipFree(s->shade); hipFree(s->motion);
   refit_release(s);
+  if (s->pose.part) { // (rf.stage is a new array: what read_pose would return is gone)
+    hipFree(s->pose.part); hipFree(s->pose.rest);
+    s->pose.part = G.p_part; s->pose.rest = G.p_rest;
+    s->pose.posed = false;
+  }
   s->rf = std::move(ns.rf);
   s->motion = ns.motion;
   s->nodes = ns.nodes; s->quads = ns.quads; s->tris = ns.tris; s->slot_tri = ns.slot_tri; s->shade = ns.shade;

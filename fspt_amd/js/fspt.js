@@ -530,6 +530,28 @@ class PathTracer {
     if (norm != null && (!(norm instanceof Float32Array) || norm.length !== this._nTris * 27)) throw new RangeError('updateGeometry: norm must be a Float32Array of ' + this._nTris + ' x 27 floats');
     addon.sceneUpdateGeometry(this._scene, this._nTris, tri, norm == null ? null : norm);
   }
+  /** Hand the scene a pose (fspt_scene_set_pose, DESIGN 8.14): part = Uint32Array, one part id per triangle in the current leaf
+   *  order; tri / norm = the rest mesh in that order (norm null: updateTransforms leaves the normals alone); nParts defaults
+   *  to max(part) + 1.  setPose(null) drops the pose.  Nothing renders differently until updateTransforms. */
+  setPose(part, tri, norm, nParts) {
+    if (part == null) { addon.sceneSetPose(this._scene, this._nTris, null, 0, null, null); return; }
+    if (!(part instanceof Uint32Array) || part.length !== this._nTris) throw new RangeError('setPose: part must be a Uint32Array of ' + this._nTris + ' ids');
+    if (!(tri instanceof Float32Array) || tri.length !== this._nTris * 9) throw new RangeError('setPose: tri must be a Float32Array of ' + this._nTris + ' x 9 floats');
+    if (norm != null && (!(norm instanceof Float32Array) || norm.length !== this._nTris * 27)) throw new RangeError('setPose: norm must be a Float32Array of ' + this._nTris + ' x 27 floats');
+    let n = 0;
+    for (let i = 0; i < part.length; i++) if (part[i] >= n) n = part[i] + 1;
+    if (nParts != null) {
+      if (!Number.isInteger(nParts) || nParts < Math.max(n, 1)) throw new RangeError('setPose: nParts must be an integer >= max(part) + 1');
+      n = nParts;
+    }
+    addon.sceneSetPose(this._scene, this._nTris, part, Math.max(n, 1), tri, norm == null ? null : norm);
+  }
+  /** One row-major 3 x 4 matrix per part (Float32Array, 12 floats each): a kernel poses the rest mesh and the tree is refitted
+   *  exactly as updateGeometry on the posed arrays would (fspt_scene_update_transforms, DESIGN 8.14). */
+  updateTransforms(xf) {
+    if (!(xf instanceof Float32Array) || xf.length === 0 || xf.length % 12 !== 0) throw new RangeError('updateTransforms: xf must be a Float32Array of n_parts x 12 floats');
+    addon.sceneUpdateTransforms(this._scene, xf);
+  }
   /** The arguments of updateGeometry, but the scene gets a NEW tree - the binned SAH of the GPU builder over `tri` in the
    *  order given - built on the GPU and installed in place (fspt_scene_rebuild_geometry, DESIGN 8.7).  Returns a Uint32Array:
    *  order[k] = index in `tri` of the triangle now at leaf position k; later updateGeometry / rebuildGeometry calls take

@@ -9,6 +9,7 @@ reference's format (scene/<name>.json with props / static_props / animated_props
     python -m fspt_amd.render --scene web/scene/bunny.json --lights --emitter-fraction 0.5  # sample emissive triangles
     python -m fspt_amd.render --mesh-n 289 --bvh gpu --spp 16 --out c3.png  # binned-SAH tree built on the GPU
     python -m fspt_amd.render --scene 'web/scene/anim_{frame}.json' --frames 0:24 --bvh refit --out 'out/{frame}.png'  # build once, refit
+    python -m fspt_amd.render --scene 'web/scene/anim_{frame}.json' --frames 0:24 --bvh refit --pose --out 'out/{frame}.png'  # one matrix per prop per frame
 
 Path tracing runs in the HIP kernels (fspt_render), tone mapping in the draw.fs kernel (fspt_draw); --atrous K runs
 the guided a-trous denoiser (fspt_features + fspt_denoise, K iterations) before tone mapping (fspt_draw_denoised).
@@ -45,6 +46,10 @@ def main():
     ap.add_argument("--rebuild-above", type=float, default=None, metavar="R",
                     help="--bvh refit: rebuild the tree in place on the GPU when a refitted frame's SAH cost exceeds R x the cost at "
                          "the last build (DESIGN 8.7; default: never)")
+    ap.add_argument("--pose", action="store_true",
+                    help="--bvh refit --frames: a frame that only moves its props rigidly parses no OBJ; one matrix per prop goes to "
+                         "the GPU, which poses the first frame's triangles and refits (DESIGN 8.14; float32 matrices: not bit-equal "
+                         "to the parse path)")
     ap.add_argument("--temporal", action="store_true",
                     help="--bvh refit --frames: reproject and blend every frame with the frames before it (DESIGN 8.8); with "
                          "--atrous K the a-trous filter runs on the temporal result")
@@ -88,6 +93,8 @@ def main():
         ap.error("--temporal cannot be combined with --adaptive")
     if args.temporal and not (args.bvh == "refit" and args.frames):
         ap.error("--temporal needs --bvh refit and --frames")
+    if args.pose and not (args.bvh == "refit" and args.frames):
+        ap.error("--pose needs --bvh refit and --frames")
     if args.temporal_clamp is not None and not args.temporal:
         ap.error("--temporal-clamp needs --temporal")
     if args.temporal_clamp is not None and args.temporal_clamp is not True and not args.temporal_clamp >= 0.0:
@@ -125,7 +132,7 @@ def main():
                                     rebuild_above=args.rebuild_above,
                                     temporal=({"atrous": args.atrous, "clamp": None if args.temporal_clamp is None else True if args.temporal_clamp is True
                                                else {"sigma_scale": args.temporal_clamp}} if args.temporal else None),
-                                    variance=args.variance_guided, **kw)
+                                    variance=args.variance_guided, pose=args.pose, **kw)
             print(f"{len(out)} frames in {time.perf_counter() - t0:.2f} s:", *out)
         else:
             arrays, settings = F.load_scene_file(args.scene, args.assets, bvh=args.bvh)

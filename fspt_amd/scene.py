@@ -321,7 +321,8 @@ def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas
     meta["focus"] = shootAutoFocusRay's lensFeatures[0] = 1 - 1/dist for each (main.js:447-546).
     bvh = "sah": the reference's full-sweep SAH tree (bvh.js, on the CPU); "gpu": the binned-SAH tree built on HIP device
     `device` (fspt_builder_build_gpu; leaf_size 1..64).  meta["bvh"] names the builder; keep_order=True adds
-    meta["tri_order"]: packed triangle k is the k'th triangle of the OBJs in the order they were added.
+    meta["tri_order"]: packed triangle k is the k'th triangle of the OBJs in the order they were added, and meta["tri_part"]:
+    the index in `props` of the prop packed triangle k came from.
     geometry_only=True: parse and transform the props but build NO tree: tri / mat / norm / uv come back in PARSE order, bvh is
     empty (meta["geometry_only"]); focus_rays are answered by the float64 closest hit over all triangles.  What a host of
     moving geometry needs per frame (geometry_in_leaf_order, Scene.update_geometry)."""
@@ -344,6 +345,7 @@ def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas
                 wt[i].rotate = C.cast(arr, C.POINTER(C.c_double)); wt[i].n_rotate = n; wt[i].has_rotate = 1
             elif t.get("translate"):
                 wt[i].translate = (C.c_double * 3)(*[float(x) for x in t["translate"]]); wt[i].has_translate = 1
+        prop_end = []
         for prop in props:
             pd = L.PropDesc()
             rot_arr, n_rot = _rot_array(prop.get("rotate", []))
@@ -381,6 +383,9 @@ def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas
                 mats[g].emittance = (C.c_double * 3)(*[float(x) for x in m["emittance"]])
                 mats[g].ior = m["ior"]; mats[g].dielectric = m["dielectric"]
             L.check(lib.fspt_builder_commit_obj(b, mats, ng.value))
+            done = C.c_uint32()
+            L.check(lib.fspt_builder_geometry(b, C.byref(done), None, None, None, None))
+            prop_end.append(done.value)  # triangles added so far, in parse order
         if normalize:
             L.check(lib.fspt_builder_normalize(b, float(normalize)))
         nn, nt, dp = C.c_uint32(), C.c_uint32(), C.c_uint32()
@@ -420,6 +425,8 @@ def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas
         meta["geometry_only"] = True
     elif keep_order:
         meta["tri_order"] = order
+        # the prop (index into `props`) of every packed triangle: the part ids of Scene.set_pose
+        meta["tri_part"] = np.searchsorted(np.asarray(prop_end, np.int64), order.astype(np.int64), side="right").astype(np.uint32)
     return SceneArrays(bvh=bvh_arr, tri=tri, mat=mat, norm=norm, uv=uv, atlas=atlas, atlas_res=packer.res,
                        atlas_layers=len(packer.image_set), env=env, env_w=env_w, env_h=env_h, bins=bins,
                        leaf_size=leaf_size, depth=dp.value, meta=meta)
@@ -460,6 +467,43 @@ def geometry_in_leaf_order(arrays_or_order, tri_in, norm_in=None):
             raise ValueError(f"geometry_in_leaf_order: {nrm.shape[0]} normal records, the order names {order.size}")
         out_n = np.ascontiguousarray(nrm[order]).reshape(-1)
     return np.ascontiguousarray(tri[order]).reshape(-1), out_n
+
+
+def _rotation_matrix(axis, angle):
+    """vector.js:86-101 rotateArbitrary as a matrix (the axis is used as given, not normalised), float64"""
+    x, y, z = (float(a) for a in axis)
+    s, c = math.sin(float(angle)), math.cos(float(angle))
+    oc = 1.0 - c
+    return np.array([[oc * x * x + c, oc * x * y - z * s, oc * z * x + y * s],
+                     [oc * x * y + z * s, oc * y * y + c, oc * y * z - x * s],
+                     [oc * z * x - y * s, oc * y * z + x * s, oc * z * z + c]], np.float64)
+
+
+def prop_matrix(prop, world_transforms=None):
+    """What obj_loader.js:19-38 does to a prop's vertices, composed in float64 into one 3 x 4 matrix [A | t]: the prop's
+    rotations in order, its scalar scale, its translate, then scene.worldTransforms in order with the loader's
+    `if (rotate) ... else if (translate)`.  v' = A v + t.  (Normals take the rotations alone: for these matrices that is what
+    Scene.update_transforms derives)"""
+    m = np.eye(4, dtype=np.float64)
+
+    def then(a, t=(0.0, 0.0, 0.0)):
+        nonlocal m
+        step = np.eye(4, dtype=np.float64)
+        step[:3, :3] = a
+        step[:3, 3] = t
+        m = step @ m
+
+    for r in prop.get("rotate") or []:
+        then(_rotation_matrix(r["axis"], r["angle"]))
+    then(np.eye(3) * float(prop.get("scale", 1.0)))
+    then(np.eye(3), [float(x) for x in prop.get("translate", [0, 0, 0])])
+    for w in world_transforms or []:
+        if "rotate" in w and w["rotate"] is not None:
+            for r in w["rotate"]:
+                then(_rotation_matrix(r["axis"], r["angle"]))
+        elif w.get("translate"):
+            then(np.eye(3), [float(x) for x in w["translate"]])
+    return m[:3].copy()
 
 
 def compose_order(base_order, order):
@@ -570,9 +614,9 @@ def synthetic_env(w=2048, h=1024, sun_deg=1.5, sun_gain=60.0, sun_dir=(0.35, 0.5
     return out.reshape(-1), w, h
 
 
-def textured_test_scene(res=16):
+def textured_test_scene(res=16, keep_order=False):
     """Two image-mapped quads + a flat-colour sphere: exercises the bilinear RGBA8 atlas path (atlas res > 1),
-    tangent-space normal mapping and emissive maps with procedurally generated images."""
+    tangent-space normal mapping and emissive maps with procedurally generated images.  keep_order: as build_scene."""
     rng = np.random.default_rng(5)
     yy, xx = np.mgrid[0:res, 0:res]
     checker = (((xx // 2) + (yy // 2)) % 2).astype(np.uint8)
@@ -593,9 +637,13 @@ def textured_test_scene(res=16):
     ]
     texts = {"synthetic/cube_sphere.obj": cube_sphere_obj(6), "synthetic/quad.obj": QUAD_OBJ}
     env, w, h = synthetic_env(64, 32)
-    s = build_scene(props, texts, env=env, env_w=w, env_h=h, images=images)
-    s.meta = dict(kind="textured-test")
+    s = build_scene(props, texts, env=env, env_w=w, env_h=h, images=images, keep_order=keep_order)
+    s.meta = dict(kind="textured-test", **_kept_order(s.meta))
     return s
+
+
+def _kept_order(meta):
+    return {k: meta[k] for k in ("tri_order", "tri_part") if k in meta}
 
 
 def bunny_props():
@@ -695,11 +743,11 @@ def lens_features(focal_depth, aperture):
     return [1.0 - 1.0 / focal_depth, aperture]
 
 
-def bunny_scene(n=76, env_size=(2048, 1024), sun_deg=1.5, sun_gain=60.0, bvh="sah", device=0):
+def bunny_scene(n=76, env_size=(2048, 1024), sun_deg=1.5, sun_gain=60.0, bvh="sah", device=0, keep_order=False):
     """The BASELINE 'bunny' configs: n=76 -> 69 312 + 4 triangles (C1/C2/C5),
-    n=289 -> 1 002 252 + 4 (C3)."""
+    n=289 -> 1 002 252 + 4 (C3).  keep_order: as build_scene (meta["tri_order"], meta["tri_part"])."""
     texts = {"synthetic/cube_sphere.obj": cube_sphere_obj(n), "synthetic/quad.obj": QUAD_OBJ}
     env, w, h = synthetic_env(env_size[0], env_size[1], sun_deg=sun_deg, sun_gain=sun_gain)
-    s = build_scene(bunny_props(), texts, env=env, env_w=w, env_h=h, bvh=bvh, device=device)
-    s.meta = dict(kind="bunny-synthetic", n=n, bvh=bvh)
+    s = build_scene(bunny_props(), texts, env=env, env_w=w, env_h=h, bvh=bvh, device=device, keep_order=keep_order)
+    s.meta = dict(kind="bunny-synthetic", n=n, bvh=bvh, **_kept_order(s.meta))
     return s

@@ -79,15 +79,22 @@ def load_scene_file(scene_path, asset_root=None, leaf_size=4, bvh="sah", device=
     elif e:
         # array-of-stops skies (main.js:182-204) are broken in the reference itself
         raise ValueError("array-of-stops environments are not supported; use an RGBE image or none")
-    eye = [float(x) for x in (scene.get("cameraPos") or [0, 0, 2])]
-    d = [float(x) for x in (scene.get("cameraDir") or [0, 0, -1])]
+    eye, d = _camera_ray(scene)
     arrays = S.build_scene_json(scene, obj_texts, mtl_texts, images, env=env, env_w=env_w, env_h=env_h,
                                 leaf_size=leaf_size, focus_rays=[(eye, d)], bvh=bvh, device=device, keep_order=keep_order,
                                 geometry_only=geometry_only)
-    settings = dict(eye=eye, dir=d, fov_scale=float(scene.get("fovScale") or 0.5),
-                    env_theta=float(scene.get("environmentTheta") or 0), exposure=float(scene.get("exposure") or 1.0),
-                    samples=int(scene.get("samples") or 2000), focus=arrays.meta["focus"][0], aperture=0.02)
-    return arrays, settings
+    return arrays, _settings(scene, arrays.meta["focus"][0])
+
+
+def _camera_ray(scene):
+    return ([float(x) for x in (scene.get("cameraPos") or [0, 0, 2])], [float(x) for x in (scene.get("cameraDir") or [0, 0, -1])])
+
+
+def _settings(scene, focus):
+    eye, d = _camera_ray(scene)
+    return dict(eye=eye, dir=d, fov_scale=float(scene.get("fovScale") or 0.5),
+                env_theta=float(scene.get("environmentTheta") or 0), exposure=float(scene.get("exposure") or 1.0),
+                samples=int(scene.get("samples") or 2000), focus=focus, aperture=0.02)
 
 
 def render_frame(arrays, settings, width, height, samples=None, bounces=4, seed=1, saturation=1.0, denoise=False,
@@ -207,8 +214,47 @@ def sequence_frame_changes(held, g, order):
     return {k: new[k] for k in APPEARANCE_FIELDS if not same(held[k], new[k])}
 
 
+POSE_KEYS = ("rotate", "scale", "translate")  # of a prop: what obj_loader.js:19-38 applies to a fixed mesh
+
+
+def sequence_pose_frame(base_scene, frame_scene):
+    """render_sequence(bvh="refit", pose=True)'s classification of a frame, as a pure function of two scene JSONs (dicts): True
+    when the frame is the base frame with its props moved rigidly - the two are equal once every prop's rotate / scale /
+    translate and the scenes' worldTransforms are removed - and neither has a `normalize` (which rescales by the bounds of
+    the moved scene).  Such a frame is fully described by sequence_pose_matrices; its OBJs need not be parsed."""
+    def stripped(scene):
+        out = {k: v for k, v in scene.items() if k not in ("worldTransforms", "props", "static_props", "animated_props")}
+        out["props"] = [{k: v for k, v in p.items() if k not in POSE_KEYS} for p in S.merge_scene_props(scene)]
+        return out
+
+    if base_scene.get("normalize") or frame_scene.get("normalize"):
+        return False
+    return stripped(base_scene) == stripped(frame_scene)
+
+
+def sequence_pose_matrices(base_scene, frame_scene):
+    """float32 [n_props, 12]: per prop (merge_scene_props order) the matrix that takes the BASE frame's triangles to this
+    frame's, float32(prop_matrix(frame) @ inverse(prop_matrix(base))) - what Scene.update_transforms is handed when the
+    rest mesh is the base frame's."""
+    def m4(prop, world):
+        m = np.eye(4, dtype=np.float64)
+        m[:3] = S.prop_matrix(prop, world)
+        return m
+
+    pb, pf = S.merge_scene_props(base_scene), S.merge_scene_props(frame_scene)
+    out = [(m4(f, frame_scene.get("worldTransforms")) @ np.linalg.inv(m4(b, base_scene.get("worldTransforms"))))[:3] for b, f in zip(pb, pf)]
+    return np.asarray(out, np.float64).reshape(-1, 12).astype(np.float32)
+
+
+def _parse_order_parts(base):
+    """part id per PARSE-order triangle from a base built with keep_order (the inverse of meta["tri_part"]'s gather)"""
+    out = np.zeros(base.n_tris, np.uint32)
+    out[np.asarray(base.meta["tri_order"], np.int64)] = base.meta["tri_part"]
+    return out
+
+
 def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", rebuild_above=None,
-                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, **kw):
+                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, **kw):
     """frame=N sequencing (main.js:851-866, 966-969): for every N in `frames` load `scene_pattern.format(frame=N)`
     (the per-frame scene JSON the reference's server hands out for `?frame=N`), render it, write
     `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1.
@@ -222,7 +268,14 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     whose materials, uvs, atlas, environment or bins differ from what the live scene holds gets exactly those updated in place
     after its refit (Scene.update_materials / update_environment) and reports "appearance".  A frame with another
     triangle count builds a new scene.
-    on_frame(N, "build" | "refit" | "rebuild" | "appearance") reports what a frame did.
+    pose=True (bvh="refit" only): the scene also keeps its triangles as the rest mesh of a pose, one part per
+    prop (Scene.set_pose).  A frame that sequence_pose_frame finds to be the rest frame with its props moved rigidly parses
+    NO OBJ: its sequence_pose_matrices go to Scene.update_transforms, a kernel poses the triangles and the tree is refitted;
+    its auto-focus ray is shot through Scene.intersect on the live scene; it reports "pose".  Any other frame takes the path
+    above, and the pose is re-set from what that frame uploaded.  The pictures are NOT bit-equal to the parse path's: there
+    the transform is applied in float64 to the OBJ's vertices and rounded once, here a float32 matrix is applied in float32
+    to the rest frame's float32 triangles - which is why it is opt-in.
+    on_frame(N, "build" | "refit" | "rebuild" | "appearance" | "pose") reports what a frame did.
     temporal (bvh="refit" only): True or a dict of PathTracer.temporal_accumulate's parameters, plus "atrous": K
     for K a-trous iterations on the result.  Every frame then follows the protocol motion_begin, update_geometry, clear and
     render, temporal_accumulate, and the picture written is temporal_draw of the result (`denoise`, the firefly filter of
@@ -266,6 +319,8 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
             raise ValueError("render_sequence: temporal cannot be combined with adaptive sampling")
     else:
         temporal = None
+    if pose and bvh != "refit":
+        raise ValueError('render_sequence: pose needs bvh="refit" (one scene across the frames)')
     if variance and (temporal is None or atrous < 1):
         raise ValueError('render_sequence: variance needs temporal with "atrous" >= 1 (the variance guides the a-trous filter)')
 
@@ -293,12 +348,27 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
 
     atlas_sent = False
     held = None  # the appearance the live scene holds now (not the base's: a change that persists is uploaded once)
+    rest_json = None  # pose=True: the scene JSON of the frame whose triangles are the live scene's rest mesh
+
+    def read_json(p):
+        with open(p, "r", encoding="utf-8") as fh:
+            return json.load(fh)
 
     try:
         for n in frames:
             path = scene_pattern.format(frame=n)
             how = "build"
-            if base is not None:
+            frame_json = read_json(path) if pose else None
+            if base is not None and rest_json is not None and sequence_pose_frame(rest_json, frame_json):
+                if temporal is not None:
+                    pt.scene.motion_begin()
+                pt.update_transforms(sequence_pose_matrices(rest_json, frame_json))
+                eye, d = _camera_ray(frame_json)
+                t, hit, _, _ = pt.scene.intersect(np.float32([eye + d]))
+                dist = float(t[0]) if hit[0] >= 0 else 1e6  # shootAutoFocusRay's maxT (main.js:447-546)
+                settings = _settings(frame_json, 1 - 1 / dist)
+                how = "pose"
+            elif base is not None:
                 g, settings = load_scene_file(path, asset_root, geometry_only=True)
                 changes = sequence_frame_changes(held, g, base.meta["tri_order"])
                 if changes is not None:
@@ -311,6 +381,11 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                         leaf_order = S.compose_order(leaf_order, pt.rebuild_geometry(tri, norm))
                         cost0 = pt.scene.sah_cost()
                         how = "rebuild"
+                    if pose:  # what this frame uploaded is the rest mesh from here on, in the current leaf order
+                        rest_json = None if frame_json.get("normalize") else frame_json
+                        if rest_json is not None:
+                            part = _parse_order_parts(base)[np.asarray(leaf_order, np.int64)]
+                            pt.scene.set_pose(part, *S.geometry_in_leaf_order(leaf_order, g.tri, g.norm), n_parts=len(S.merge_scene_props(frame_json)))
                     if changes:
                         #  what differs goes to the live scene in place: tracer, history and exposure stay
                         if {"mat", "uv", "atlas"} & set(changes):
@@ -332,6 +407,10 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                 cost0 = pt.scene.sah_cost() if rebuild_above is not None else None
                 leaf_order = base.meta["tri_order"]
                 held, atlas_sent = held_appearance(base), False
+                rest_json = None
+                if pose and not frame_json.get("normalize"):
+                    pt.scene.set_pose(base.meta["tri_part"], n_parts=len(S.merge_scene_props(frame_json)))
+                    rest_json = frame_json
                 if variance:
                     pt.temporal_set_moments(True)
                 if temporal is not None and clamp is not None:

@@ -427,6 +427,7 @@ class Scene:
             L.check(L.lib().fspt_scene_update_geometry_device(self._h, tri, norm))
         else:
             L.check(L.lib().fspt_scene_update_geometry(self._h, L.fptr(tri), None if norm is None else L.fptr(norm)))
+        self._moved = True  # (set_pose's default rest mesh is self.arrays: no longer what the scene holds)
 
     def rebuild_geometry(self, tri, norm=None):
         """The same input as update_geometry, but the scene gets a NEW tree: the binned-SAH tree of build_scene(bvh="gpu")
@@ -439,6 +440,7 @@ class Scene:
         a bvh="gpu" scene with its own triangles changes nothing (order = arange).  Any error leaves the scene as it was."""
         n = int(self.arrays.n_tris)
         on_dev, tri, norm = self._geometry_args("rebuild_geometry", tri, norm)
+        self._moved = True
         if on_dev:
             import torch
             order = torch.empty(n, dtype=torch.int32, device=f"cuda:{self.device}")
@@ -447,6 +449,56 @@ class Scene:
         order = np.zeros(n, np.uint32)
         L.check(L.lib().fspt_scene_rebuild_geometry(self._h, L.fptr(tri), None if norm is None else L.fptr(norm), L.u32ptr(order)))
         return order
+
+    def set_pose(self, part, tri=None, norm=None, n_parts=None):
+        """Hand the scene a pose (fspt_scene_set_pose): `part` = one part id per triangle in the current LEAF
+        order (meta["tri_part"] of build_scene(keep_order=True)), tri / norm = the rest mesh in that order.  The default
+        is the scene's own arrays - tri AND norm of `self.arrays`; it is refused once update_geometry /
+        rebuild_geometry has given the scene other triangles or another order.  With tri given and norm None the pose has no rest normals:
+        update_transforms then leaves the normal part of the hit records alone.  part=None drops the pose and frees it.
+        n_parts: the number of parts when it is more than max(part) + 1.  Nothing renders differently until update_transforms."""
+        if part is None:
+            L.check(L.lib().fspt_scene_set_pose(self._h, None, 0, None, None))
+            return
+        n = int(self.arrays.n_tris)
+        if tri is None:
+            if norm is not None:
+                raise ValueError("set_pose: norm given without tri")
+            if getattr(self, "_moved", False):
+                raise ValueError("set_pose: the scene's geometry is no longer that of its arrays; pass tri (and norm) in the current leaf order")
+            tri, norm = self.arrays.tri, self.arrays.norm
+        part = np.ascontiguousarray(_u32_array(part, "part"), dtype=np.uint32).reshape(-1)
+        if part.size != n:
+            raise ValueError(f"set_pose: part has {part.size} elements, the scene has {n} triangles")
+        _, tri, norm = self._geometry_args("set_pose", np.asarray(tri), None if norm is None else np.asarray(norm))
+        n_parts = int(n_parts) if n_parts is not None else int(part.max()) + 1 if n else 1
+        L.check(L.lib().fspt_scene_set_pose(self._h, L.u32ptr(part), n_parts, L.fptr(tri), None if norm is None else L.fptr(norm)))
+
+    def update_transforms(self, xf):
+        """One 3 x 4 matrix per part (float32 [n_parts, 12] or [n_parts, 3, 4], row-major: a00 a01 a02 tx | ...): the rest
+        mesh is posed by a kernel - vertices by the matrix, tangents and bitangents by its 3 x 3 part and normals by its
+        cofactor matrix, both scaled to the matrix's rms - and the tree refitted exactly as update_geometry on the posed
+        arrays would (fspt_scene_update_transforms).  n_parts is set_pose's: max(part) + 1 unless given."""
+        xf = np.ascontiguousarray(xf, dtype=np.float32).reshape(-1)
+        if xf.size % 12:
+            raise ValueError(f"update_transforms: xf has {xf.size} elements, not n_parts x 12")
+        L.check(L.lib().fspt_scene_update_transforms(self._h, L.fptr(xf), xf.size // 12))
+
+    def read_pose(self):
+        """(tri [n, 9], norm [n, 27] or None) as the most recent update_transforms posed them (fspt_scene_read_pose)."""
+        n = int(self.arrays.n_tris)
+        tri = np.zeros((n, 9), np.float32)
+        norm = np.zeros((n, 27), np.float32)
+        if L.lib().fspt_scene_read_pose(self._h, L.fptr(tri), L.fptr(norm)) == 0:
+            return tri, norm
+        L.check(L.lib().fspt_scene_read_pose(self._h, L.fptr(tri), None))  # (a pose without rest normals)
+        return tri, None
+
+    def last_pose_ms(self):
+        """The most recent update_transforms as a dict: transform_ms (k_pose_transform), refit_ms, launches."""
+        a, b, n = C.c_float(), C.c_float(), C.c_uint32()
+        L.check(L.lib().fspt_scene_last_pose_ms(self._h, C.byref(a), C.byref(b), C.byref(n)))
+        return dict(transform_ms=float(a.value), refit_ms=float(b.value), launches=int(n.value))
 
     def _materials_args(self, fn, mat, uv, atlas, atlas_res, atlas_layers):
         n = int(self.arrays.n_tris)
@@ -833,6 +885,14 @@ class PathTracer:
         """Scene.update_geometry on this tracer's scene (every tracer of the scene sees it); call clear() to restart the mean."""
         self.scene.update_geometry(tri, norm)
 
+    def set_pose(self, part, tri=None, norm=None):
+        """Scene.set_pose on this tracer's scene."""
+        self.scene.set_pose(part, tri, norm)
+
+    def update_transforms(self, xf):
+        """Scene.update_transforms on this tracer's scene (every tracer of the scene sees it); call clear() to restart the mean."""
+        self.scene.update_transforms(xf)
+
     def update_materials(self, mat, uv=None, atlas=None, atlas_res=None, atlas_layers=None):
         """Scene.update_materials on this tracer's scene (every tracer of the scene sees it); the accumulator, the temporal
         history, the exposure and the bloom state stay - call clear() to restart the mean."""
@@ -1189,6 +1249,31 @@ class MultiPathTracer:
             if norm.size != n * 27:
                 raise ValueError(f"update_geometry: norm has {norm.size} elements, the scene needs {n} x 27")
         L.check(L.lib().fspt_multi_update_geometry(self._m, L.fptr(tri), None if norm is None else L.fptr(norm)))
+
+    def set_pose(self, part, tri=None, norm=None):
+        """Scene.set_pose on every device's copy of the scene (fspt_multi_set_pose); tri is required once the scene has moved."""
+        if part is None:
+            L.check(L.lib().fspt_multi_set_pose(self._m, None, 0, None, None))
+            return
+        n = int(self.arrays.n_tris)
+        if tri is None:
+            if norm is not None:
+                raise ValueError("set_pose: norm given without tri")
+            tri, norm = self.arrays.tri, self.arrays.norm
+        part = np.ascontiguousarray(_u32_array(part, "part"), dtype=np.uint32).reshape(-1)
+        tri = np.ascontiguousarray(tri, dtype=np.float32)
+        norm = None if norm is None else np.ascontiguousarray(norm, dtype=np.float32)
+        if part.size != n or tri.size != n * 9 or (norm is not None and norm.size != n * 27):
+            raise ValueError(f"set_pose: the scene needs {n} part ids, {n} x 9 tri and {n} x 27 norm elements")
+        L.check(L.lib().fspt_multi_set_pose(self._m, L.u32ptr(part), int(part.max()) + 1 if n else 1, L.fptr(tri),
+                                            None if norm is None else L.fptr(norm)))
+
+    def update_transforms(self, xf):
+        """Scene.update_transforms on every device's copy of the scene (fspt_multi_update_transforms)."""
+        xf = np.ascontiguousarray(xf, dtype=np.float32).reshape(-1)
+        if xf.size % 12:
+            raise ValueError(f"update_transforms: xf has {xf.size} elements, not n_parts x 12")
+        L.check(L.lib().fspt_multi_update_transforms(self._m, L.fptr(xf), xf.size // 12))
 
     def update_materials(self, mat, uv=None, atlas=None, atlas_res=None, atlas_layers=None):
         """Scene.update_materials (host arrays) on every device's copy of the scene (fspt_multi_update_materials)."""

@@ -64,6 +64,15 @@ int fspt_scene_last_update_ms(fspt_scene *scene, float *ms, uint32_t *launches);
  * included), GPU ms of the install kernels (slot map, permute, gather, child references, the refit), host ms of the
  * numbering, kernels launched, readbacks (the builder's 4-byte ones + the one of the topology).  Any pointer may be NULL. */
 int fspt_scene_last_rebuild_ms(fspt_scene *scene, float *build_ms, float *install_ms, float *host_ms, uint32_t *launches, uint32_t *readbacks);
+/* Part transforms, test and measurement hooks.
+ * read_pose: the posed tri (n_tris x 9) / norm (n_tris x 27; either may be NULL) the most recent fspt_scene_update_transforms
+ * wrote to the staging array the refit read (FSPT_E_STATE when another call has reused the array since).
+ * last_pose_ms: GPU ms of k_pose_transform, GPU ms of the refit behind it (as fspt_scene_last_update_ms), kernels launched.
+ * pose_matrices_eval: the host part of the rule alone, no device: out = n_parts x 30 floats (a | D | N);
+ * FSPT_E_INVALID and *bad_part for a non-finite or singular matrix. */
+int fspt_scene_read_pose(fspt_scene *s, float *tri, float *norm);
+int fspt_scene_last_pose_ms(fspt_scene *s, float *transform_ms, float *refit_ms, uint32_t *launches);
+int fspt_pose_matrices_eval(const float *xf, uint32_t n_parts, float *out, uint32_t *bad_part);
 /* Appearance update, test and measurement hooks.
  * what: 0 texture-set table, 1 single-layer tiled images, 2 interleaved images, 3 environment tiles, 4 bins, 5 hit records.
  * Copies min(cap, size) bytes and writes the size to *bytes (out NULL: only that).  Blocking. */

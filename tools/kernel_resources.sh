@@ -1,9 +1,10 @@
 #!/bin/bash
-# Per-kernel register / scratch / occupancy table of the two kernel files, fspt_kernels.hip and fspt_post.hip
+# Per-kernel register / scratch / occupancy table of the two kernel files, fspt_kernels.hip and fspt_post.hip, and of
+# fspt_pose.hip (k_pose_transform)
 # (hipcc -Rpass-analysis=kernel-resource-usage), demangled, in one table.
 # usage: tools/kernel_resources.sh [extra -D flags]
 cd "$(dirname "$0")/.." || exit 1
-for f in fspt_kernels fspt_post; do
+for f in fspt_kernels fspt_post fspt_pose; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off ${AB_SLP:--fno-slp-vectorize} -std=c++17 -Wno-unused-value -c --cuda-device-only \
     -Rpass-analysis=kernel-resource-usage "$@" fspt_amd/csrc/$f.hip -o /tmp/${f}_res.o 2>&1
 done |
@@ -20,6 +21,6 @@ for line in sys.stdin:
 names = subprocess.run(["c++filt"] + [r["name"] for r in rows], capture_output=True, text=True).stdout.split("\n")
 print("%-62s %5s %5s %7s %6s %4s %6s" % ("kernel", "VGPR", "SGPR", "scratch", "vspill", "occ", "LDS"))
 for r, n in zip(rows, names):
-    n = re.sub(r"^void fspt::", "", n); n = re.sub(r"\(.*$", "", n)
+    n = re.sub(r"^void fspt::", "", n.replace("(anonymous namespace)::", "")); n = re.sub(r"\(.*$", "", n)
     print("%-62s %5d %5d %7d %6d %4d %6d" % (n, r.get("vgpr", -1), r.get("sgpr", -1), r.get("scratch", -1), r.get("vspill", -1), r.get("occ", -1), r.get("lds", -1)))
 '

@@ -60,6 +60,10 @@ class BloomParams(C.Structure):
     _fields_ = [("intensity", C.c_float), ("scatter", C.c_float), ("levels", C.c_uint32)]
 
 
+class CameraModelParams(C.Structure):
+    _fields_ = [("model", C.c_int), ("angle", C.c_float), ("ipd", C.c_float)]
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("target_rel_mse", C.c_double), ("max_ticks", C.c_uint32), ("min_ticks", C.c_uint32), ("round_ticks", C.c_uint32)]
 
@@ -146,6 +150,10 @@ SIGNATURES = {
     "fspt_camera": (C.c_int, [_VP, _F, _F, C.c_float, _F, C.c_float]),
     "fspt_set_rays": (C.c_int, [_VP, _F, _F]),
     "fspt_read_rays": (C.c_int, [_VP, _F, _F]),
+    "fspt_set_rays_device": (C.c_int, [_VP, _VP, _VP]),
+    "fspt_target_set_camera_model": (C.c_int, [_VP, C.POINTER(CameraModelParams)]),
+    "fspt_target_get_camera_model": (C.c_int, [_VP, C.POINTER(CameraModelParams)]),
+    "fspt_camera_model_time": (C.c_int, [_VP, C.POINTER(CameraParams), C.c_uint32, _F]),
     "fspt_trace": (C.c_int, [_VP, C.c_uint32, C.c_float, C.c_float, C.c_uint32]),
     "fspt_trace_test": (C.c_int, [_VP, C.c_uint32]),
     "fspt_render": (C.c_int, [_VP, C.POINTER(CameraParams), C.c_uint32, C.c_uint32, C.c_uint64]),

@@ -394,6 +394,11 @@ int texset_classify(const float *mat, uint32_t T, uint32_t n_layers, uint32_t re
   return FSPT_OK;
 }
 
+const char *camera_model_name(int model) {
+  static const char *const names[] = {"pinhole", "ortho", "fisheye", "equirect", "stereo"};
+  return model >= 0 && model <= 4 ? names[model] : "?";
+}
+
 extern "C" {
 
 int fspt_light_alias_table(const float *weights, uint32_t n, float *prob, uint32_t *alias) {
@@ -905,6 +910,19 @@ int fspt_set_rays(fspt_target *t, const float *pos, const float *dir) {
   return FSPT_OK;
 }
 
+int fspt_set_rays_device(fspt_target *t, const float *pos, const float *dir) {
+  if (!t || !pos || !dir) { fspt_set_error("fspt_set_rays_device: NULL argument"); return FSPT_E_INVALID; }
+  HIP_TRY(hipSetDevice(t->scene->device));
+  FLUSH_OR_RETURN(t);
+  t->cam_recorded = false;
+  t->rays_injected = true;
+  size_t bytes = (size_t)t->W * t->H * 16;
+  HIP_TRY(hipMemcpyAsync(t->ray_pos, pos, bytes, hipMemcpyDeviceToDevice, t->stream));
+  HIP_TRY(hipMemcpyAsync(t->ray_dir, dir, bytes, hipMemcpyDeviceToDevice, t->stream));
+  t->rays_valid = true;
+  return FSPT_OK;
+}
+
 int fspt_read_rays(fspt_target *t, float *pos, float *dir) {
   if (!t || !pos || !dir) { fspt_set_error("fspt_read_rays: NULL argument"); return FSPT_E_INVALID; }
   if (!t->rays_valid) { fspt_set_error("fspt_read_rays: no rays generated yet"); return FSPT_E_STATE; }
@@ -926,8 +944,47 @@ int fspt_read_rays(fspt_target *t, float *pos, float *dir) {
 uint32_t clamp_bounces(uint32_t nb) { return nb > (uint32_t)FSPT_MAX_BOUNCES ? (uint32_t)FSPT_MAX_BOUNCES : nb; }
 
 // n_ticks ticks with ray generation in the path kernels and explicit per-tick randBase values, on either pipeline
+static int trace_from_buffers(fspt_target *t, uint32_t tick, float rand_base, float env_theta, uint32_t num_bounces, bool inner);
+static fspt::CameraP camera_p(const fspt_camera_params &c) {
+  fspt::CameraP p;
+  std::memcpy(p.P, c.P, 12); std::memcpy(p.I, c.I, 12);
+  p.fov_scale = c.fov_scale; p.lens[0] = c.lens[0]; p.lens[1] = c.lens[1];
+  return p;
+}
+// k_camera_model has overwritten the target's one pair of ray buffers with rays nobody asked to see.  What they held
+// before: a recorded fspt_camera call not yet materialised (nothing to do), that call's materialised rays (made again when
+// somebody looks at them: cam_recorded), or injected rays, which are gone - fspt_trace then answers FSPT_E_STATE rather than
+// trace foreign rays, until the caller injects again.
+static void ray_buffers_overwritten(fspt_target *t) {
+  if (t->cam_recorded) return;
+  if (t->rays_valid && !t->rays_injected) t->cam_recorded = true;
+  else { t->rays_valid = false; t->rays_injected = false; }
+}
+// The same under a camera model: per tick k_camera_model into the ray buffers, then the single-tick trace from
+// the buffers (either pipeline, either scheduler), all on the target's stream in order - the trace of tick k has read the
+// buffers before the camera kernel of tick k + 1 writes them, and nothing waits on the host.  Not batched.
+static int render_ticks_model(fspt_target *t, const fspt_camera_params *cam, uint32_t first_tick, uint32_t n_ticks,
+                              const float *rbc, const float *rbt) {
+  if (t->tile_list) { fspt_set_error("camera model '%s': tile lists are not supported", camera_model_name(t->cam_model.model)); return FSPT_E_STATE; }
+  const fspt::CameraP c = camera_p(*cam);
+  t->ev_used = 0; t->ev_overflow = false;
+  HIP_TRY(hipEventRecord(t->ev0, t->stream));
+  ray_buffers_overwritten(t);
+  for (uint32_t k = 0; k < n_ticks; ++k) {
+    HIP_TRY(fspt::launch_camera_model(t->W, t->H, t->vw, t->vh, c, t->cam_model, rbc[k], t->ray_pos, t->ray_dir, t->stream,
+                                      (uint32_t)t->sampler, t->sampler_seed, first_tick + k));
+    int rc = trace_from_buffers(t, first_tick + k, rbt[k], cam->env_theta, cam->num_bounces, true);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipEventRecord(t->ev1, t->stream));
+  t->timed = true; t->last_launches = n_ticks;
+  t->acc_ticks = first_tick + n_ticks;
+  return FSPT_OK;
+}
+
 static int render_ticks(fspt_target *t, const fspt_camera_params *cam, uint32_t first_tick, uint32_t n_ticks,
                         const float *rbc, const float *rbt) {
+  if (t->cam_model.model != FSPT_CAMERA_PINHOLE) return render_ticks_model(t, cam, first_tick, n_ticks, rbc, rbt);
   t->ev_used = 0; t->ev_overflow = false;
   if (t->pipeline == 1) {
     HIP_TRY(hipEventRecord(t->ev0, t->stream));
@@ -1006,6 +1063,12 @@ int materialise_rays(fspt_target *t) {
   std::memcpy(c.P, t->last_cam.P, 12); std::memcpy(c.I, t->last_cam.I, 12);
   c.fov_scale = t->last_cam.fov_scale; c.lens[0] = t->last_cam.lens[0]; c.lens[1] = t->last_cam.lens[1];
   // (the Sobol sampler: sample index acc_ticks - the tick that would trace these rays next)
+  if (t->cam_model.model != FSPT_CAMERA_PINHOLE) {
+    HIP_TRY(fspt::launch_camera_model(t->W, t->H, t->vw, t->vh, c, t->cam_model, t->last_rb_cam, t->ray_pos, t->ray_dir, t->stream,
+                                      (uint32_t)t->sampler, t->sampler_seed, t->acc_ticks));
+    t->cam_recorded = false;
+    return FSPT_OK;
+  }
   HIP_TRY(fspt::launch_camera(t->W, t->H, t->vw, t->vh, c, t->last_rb_cam, t->ray_pos, t->ray_dir, t->stream, (uint32_t)t->sampler,
                               t->sampler_seed, t->acc_ticks));
   t->cam_recorded = false;
@@ -1017,12 +1080,15 @@ static int present_flush(fspt_target *t); // (fspt_present: the recorded ticks w
 extern "C" {
 
 // a tick traced from the ray buffers (fspt_set_rays), on the target's stream
-static int trace_from_buffers(fspt_target *t, uint32_t tick, float rand_base, float env_theta, uint32_t num_bounces) {
+// (inner: one tick of render_ticks_model's loop, which keeps the timing events around the whole run)
+static int trace_from_buffers(fspt_target *t, uint32_t tick, float rand_base, float env_theta, uint32_t num_bounces, bool inner) {
   if (t->pipeline == 1) {
     fspt_camera_params cp{};
     cp.env_theta = env_theta; cp.num_bounces = num_bounces;
-    t->ev_used = 0; t->ev_overflow = false;
-    HIP_TRY(hipEventRecord(t->ev0, t->stream));
+    if (!inner) {
+      t->ev_used = 0; t->ev_overflow = false;
+      HIP_TRY(hipEventRecord(t->ev0, t->stream));
+    }
     int rc;
     if (t->sched == 1 || t->stream_fallback) {
       rc = render_stream(t, &cp, tick, 1, nullptr, &rand_base, true);
@@ -1034,20 +1100,20 @@ static int trace_from_buffers(fspt_target *t, uint32_t tick, float rand_base, fl
       }
     }
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(t->ev1, t->stream));
+    if (!inner) HIP_TRY(hipEventRecord(t->ev1, t->stream));
     t->timed = true; t->last_launches = 1;
     t->acc_ticks = tick + 1;
     return FSPT_OK;
   }
-  t->ev_used = 0;
+  if (!inner) t->ev_used = 0;
   fspt::TraceP p{};
   fill_trace_params(t, p);
   p.tick = tick; p.rand_base = rand_base; p.rand_base_cam = 0.0f; p.env_theta = env_theta; p.num_bounces = num_bounces;
   HIP_TRY(hipMemsetAsync(t->work_counters, 0, 4, t->stream));
   p.work_counter = t->work_counters;
-  HIP_TRY(hipEventRecord(t->ev0, t->stream));
+  if (!inner) HIP_TRY(hipEventRecord(t->ev0, t->stream));
   HIP_TRY(fspt::launch_trace(p, false, t->count != 0, t->scene->num_cus, t->stream));
-  HIP_TRY(hipEventRecord(t->ev1, t->stream));
+  if (!inner) HIP_TRY(hipEventRecord(t->ev1, t->stream));
   t->timed = true; t->last_launches = 1;
   t->acc_ticks = tick + 1;
   return FSPT_OK;
@@ -1073,13 +1139,13 @@ int fspt_trace(fspt_target *t, uint32_t tick, float rand_base, float env_theta, 
     int rc = present_flush(t);
     if (rc) return rc;
     if (t->pr_acc_stream && t->pr_acc_stream != t->stream) HIP_TRY(hipStreamWaitEvent(t->stream, t->pr_acc, 0));
-    if ((rc = trace_from_buffers(t, tick, rand_base, env_theta, num_bounces))) return rc;
+    if ((rc = trace_from_buffers(t, tick, rand_base, env_theta, num_bounces, false))) return rc;
     HIP_TRY(hipEventRecord(t->pr_acc, t->stream));
     t->pr_acc_stream = t->stream;
     return FSPT_OK;
   }
   FLUSH_OR_RETURN(t);
-  return trace_from_buffers(t, tick, rand_base, env_theta, num_bounces);
+  return trace_from_buffers(t, tick, rand_base, env_theta, num_bounces, false);
 }
 
 int fspt_trace_test(fspt_target *t, uint32_t tick) {
@@ -1183,6 +1249,10 @@ int fspt_render_adaptive(fspt_target *t, const fspt_camera_params *cam_in, const
     fspt_set_error("fspt_render_adaptive: target_rel_mse must be finite and >= 0");
     return FSPT_E_INVALID;
   }
+  if (t->cam_model.model != FSPT_CAMERA_PINHOLE) {
+    fspt_set_error("fspt_render_adaptive: not under camera model '%s' (tile lists through the per-tick route are a follow-up)", camera_model_name(t->cam_model.model));
+    return FSPT_E_STATE;
+  }
   { int rc = check_device(t->scene ? t->scene->device : 0); if (rc) return rc; }
   if (t->n_shards > 1) { fspt_set_error("fspt_render_adaptive: not on a sharded target (%u shards)", t->n_shards); return FSPT_E_STATE; }
   FLUSH_OR_RETURN(t);
@@ -1265,6 +1335,58 @@ int fspt_target_get_sampler(fspt_target *t, int *sampler, uint32_t *seed) {
   if (!t) { fspt_set_error("fspt_target_get_sampler: NULL target"); return FSPT_E_INVALID; }
   if (sampler) *sampler = t->sampler;
   if (seed) *seed = t->sampler_seed;
+  return FSPT_OK;
+}
+
+int fspt_target_set_camera_model(fspt_target *t, const fspt_camera_model_params *p) {
+  if (!t) { fspt_set_error("fspt_target_set_camera_model: NULL target"); return FSPT_E_INVALID; }
+  fspt::CameraModelP m{fspt::CAM_PINHOLE, 3.14159265f, 0.064f};
+  if (p) { m.model = p->model; m.angle = p->angle; m.ipd = p->ipd; }
+  if (m.model < FSPT_CAMERA_PINHOLE || m.model > FSPT_CAMERA_STEREO) {
+    fspt_set_error("fspt_target_set_camera_model: unknown model %d (0 pinhole, 1 ortho, 2 fisheye, 3 equirect, 4 stereo)", m.model);
+    return FSPT_E_INVALID;
+  }
+  if (m.model == FSPT_CAMERA_FISHEYE && !(std::isfinite(m.angle) && m.angle > 0.0f && m.angle <= 6.2831855f)) {
+    fspt_set_error("fspt_target_set_camera_model: fisheye angle must lie in (0, 2 pi] radians, got %g", (double)m.angle);
+    return FSPT_E_INVALID;
+  }
+  if (m.model == FSPT_CAMERA_STEREO && !(std::isfinite(m.ipd) && m.ipd >= 0.0f)) {
+    fspt_set_error("fspt_target_set_camera_model: stereo ipd must be finite and >= 0, got %g", (double)m.ipd);
+    return FSPT_E_INVALID;
+  }
+  if (m.model == FSPT_CAMERA_STEREO && (t->H & 1u)) {
+    fspt_set_error("fspt_target_set_camera_model: stereo (over-under) needs an even target height, got %u", t->H);
+    return FSPT_E_INVALID;
+  }
+  FLUSH_OR_RETURN(t); // recorded ticks run under the old model
+  // a recorded fspt_camera call stays recorded: its rays are made under the new model when somebody looks at them
+  t->cam_model = m;
+  return FSPT_OK;
+}
+
+int fspt_target_get_camera_model(fspt_target *t, fspt_camera_model_params *p) {
+  if (!t || !p) { fspt_set_error("fspt_target_get_camera_model: NULL argument"); return FSPT_E_INVALID; }
+  p->model = t->cam_model.model; p->angle = t->cam_model.angle; p->ipd = t->cam_model.ipd;
+  return FSPT_OK;
+}
+
+int fspt_camera_model_time(fspt_target *t, const fspt_camera_params *cam, uint32_t reps, float *ms_per_launch) {
+  if (!t || !cam || !ms_per_launch || reps == 0) { fspt_set_error("fspt_camera_model_time: NULL argument or reps == 0"); return FSPT_E_INVALID; }
+  if (t->cam_model.model == FSPT_CAMERA_PINHOLE) { fspt_set_error("fspt_camera_model_time: the pinhole camera has no kernel of its own"); return FSPT_E_STATE; }
+  HIP_TRY(hipSetDevice(t->scene->device));
+  FLUSH_OR_RETURN(t);
+  const fspt::CameraP c = camera_p(*cam);
+  HIP_TRY(hipEventRecord(t->ev0, t->stream));
+  for (uint32_t k = 0; k < reps; ++k)
+    HIP_TRY(fspt::launch_camera_model(t->W, t->H, t->vw, t->vh, c, t->cam_model, (float)k, t->ray_pos, t->ray_dir, t->stream,
+                                      (uint32_t)t->sampler, t->sampler_seed, k));
+  HIP_TRY(hipEventRecord(t->ev1, t->stream));
+  HIP_TRY(hipEventSynchronize(t->ev1));
+  float ms = 0.0f;
+  HIP_TRY(hipEventElapsedTime(&ms, t->ev0, t->ev1));
+  *ms_per_launch = ms / (float)reps;
+  t->timed = false; // (ev0 / ev1 no longer bracket a render)
+  ray_buffers_overwritten(t);
   return FSPT_OK;
 }
 
@@ -1398,7 +1520,8 @@ static int present_alloc(fspt_target *t) {
 // stream behind the last accumulator access, in order.  Either way pr_acc / pr_acc_stream end behind the run's last write.
 static int present_run(fspt_target *t, const fspt_camera_params *cam, uint32_t first_tick, uint32_t n_ticks,
                        const float *rbc, const float *rbt) {
-  if (t->pipeline == 1 && t->sched == 0 && !t->stream_fallback) {
+  // (under a camera model every tick goes through the one pair of ray buffers: serially on the target's stream, below)
+  if (t->pipeline == 1 && t->sched == 0 && !t->stream_fallback && t->cam_model.model == FSPT_CAMERA_PINHOLE) {
     uint32_t lane = t->pr_next;
     int rc = render_wavefront_present(t, lane, cam, first_tick, n_ticks, rbc, rbt);
     if (rc == FSPT_E_NOMEM && lane == 1) { lane = 0; rc = render_wavefront_present(t, 0, cam, first_tick, n_ticks, rbc, rbt); }

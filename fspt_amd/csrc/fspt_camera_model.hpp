@@ -1,0 +1,100 @@
+// fspt_camera_model.hpp - the opt-in camera models (fspt_target_set_camera_model): the ray of pixel (x, y) under
+// FSPT_CAMERA_ORTHO / _FISHEYE / _EQUIRECT / _STEREO (CAM_* here).  The rule of DESIGN 8.15 and nothing else; tests/camera_model_ref.py
+// restates it in numpy from that text.  Arithmetic: the contract of DESIGN 2 - float32, an fma exactly where one is written.
+// The pinhole camera is not here: it stays camera_ray in fspt_kernels.hip, fused into the path kernels.
+#pragma once
+#include "fspt_device.hpp"
+#include "fspt_math.hpp"
+
+namespace fspt {
+
+// SMP: FSPT_SAMPLER_REFERENCE (0) - the reference's rnd() from the seed fma(fx, resy, randBase) + fy - or FSPT_SAMPLER_SOBOL
+// (1) - dims 0..3 of sample `sample` of pixel y * W + x.  The four draws are camera_ray's, in its order.
+template <int SMP, int MODEL>
+FM_DEV void model_ray(uint32_t x, uint32_t y, uint32_t W, uint32_t H, const CameraP &cam, const CameraModelP &cm, float randBase,
+                      uint32_t sseed, uint32_t sample, fm::V3 &o, fm::V3 &d) {
+  using namespace fm;
+  const float fx = (float)x + 0.5f, fy = (float)y + 0.5f;
+  const float resx = (float)W, resy = (float)H;
+  float u0, u1, u2, u3;
+  if constexpr (SMP == 1) {
+    const uint32_t pixel = y * W + x;
+    u0 = sobol_value(sseed, pixel, sample, 0u); u1 = sobol_value(sseed, pixel, sample, 1u);
+    u2 = sobol_value(sseed, pixel, sample, 2u); u3 = sobol_value(sseed, pixel, sample, 3u);
+  } else {
+    float seed = fma_(fx, resy, randBase) + fy;
+    u0 = rnd(seed); u1 = rnd(seed); u2 = rnd(seed); u3 = rnd(seed);
+  }
+  const V3 Iv = v3(cam.I[0], cam.I[1], cam.I[2]), Pv = v3(cam.P[0], cam.P[1], cam.P[2]);
+  const V3 basisX = normalize(cross(Iv, v3(0.0f, 1.0f, 0.0f)));
+  const V3 basisY = normalize(cross(basisX, Iv));
+  const V3 F = normalize(Iv);
+  const float aspect = resx / resy;
+  // the jitter: a disc of radius 0.707 pixels around the pixel centre, in pixel units
+  const float theta = (u0 * M_PI_F) * 2.0f;
+  const float r = sqrt_(u1) * 0.707f;
+  float st, ct;
+  sincos_(theta, st, ct);
+  const float px = fma_(r, ct, fx), py = fma_(r, st, fy);
+  const float u = fma_(px / resx, 2.0f, -1.0f);
+  float v;
+  bool upper = false;
+  if constexpr (MODEL == CAM_STEREO) {
+    const uint32_t half = H / 2u;
+    upper = y >= half;
+    const float y_half = upper ? (float)half : 0.0f;
+    v = fma_((py - y_half) / (resy * 0.5f), 2.0f, -1.0f);
+  } else {
+    v = fma_(py / resy, 2.0f, -1.0f);
+  }
+  V3 o0 = Pv, d0 = F;
+  if constexpr (MODEL == CAM_ORTHO) {
+    const float a = u * aspect, fov = cam.fov_scale;
+    o0.x = fma_(v * basisY.x, fov, (a * basisX.x) * fov) + Pv.x;
+    o0.y = fma_(v * basisY.y, fov, (a * basisX.y) * fov) + Pv.y;
+    o0.z = fma_(v * basisY.z, fov, (a * basisX.z) * fov) + Pv.z;
+  } else if constexpr (MODEL == CAM_FISHEYE) {
+    const float sx = u * aspect, sy = v;
+    const float rho = sqrt_(fma_(sy, sy, sx * sx));
+    const float phi = min_(rho * (cm.angle * 0.5f), M_PI_F);
+    float sp, cp;
+    sincos_(phi, sp, cp);
+    if (rho != 0.0f) {
+      const float ex = sx / rho, ey = sy / rho;
+      d0.x = fma_(sp, fma_(ey, basisY.x, ex * basisX.x), cp * F.x);
+      d0.y = fma_(sp, fma_(ey, basisY.y, ex * basisX.y), cp * F.y);
+      d0.z = fma_(sp, fma_(ey, basisY.z, ex * basisX.z), cp * F.z);
+    }
+  } else { // EQUIRECT, STEREO
+    const float lon = u * M_PI_F, lat = v * (M_PI_F * 0.5f);
+    float sl, cl, sa, ca;
+    sincos_(lon, sl, cl);
+    sincos_(lat, sa, ca);
+    d0.x = fma_(sa, basisY.x, ca * fma_(sl, basisX.x, cl * F.x));
+    d0.y = fma_(sa, basisY.y, ca * fma_(sl, basisX.y, cl * F.y));
+    d0.z = fma_(sa, basisY.z, ca * fma_(sl, basisX.z, cl * F.z));
+    if constexpr (MODEL == CAM_STEREO) {
+      const float e = upper ? -(cm.ipd * 0.5f) : cm.ipd * 0.5f; // the upper half of the picture is the left eye
+      o0.x = fma_(e, fma_(-sl, F.x, cl * basisX.x), Pv.x);
+      o0.y = fma_(e, fma_(-sl, F.y, cl * basisX.y), Pv.y);
+      o0.z = fma_(e, fma_(-sl, F.z, cl * basisX.z), Pv.z);
+    }
+  }
+  const float lx = cam.lens[0], ly = cam.lens[1];
+  if (ly == 0.0f || lx >= 1.0f) { o = o0; d = d0; return; }
+  // thin lens: the aperture disc in the basisX / basisY plane, the focus at distance f along the unlensed ray
+  const float f = 1.0f / (1.0f - lx);
+  const float theta2 = (u2 * M_PI_F) * 2.0f;
+  float s2, c2;
+  sincos_(theta2, s2, c2);
+  const float sq = sqrt_(u3);
+  V3 dof;
+  dof.x = (fma_(s2, basisY.x, c2 * basisX.x) * ly) * sq;
+  dof.y = (fma_(s2, basisY.y, c2 * basisX.y) * ly) * sq;
+  dof.z = (fma_(s2, basisY.z, c2 * basisX.z) * ly) * sq;
+  o = o0 + dof;
+  const V3 tgt = v3(fma_(f, d0.x, o0.x), fma_(f, d0.y, o0.y), fma_(f, d0.z, o0.z));
+  d = normalize(tgt - o);
+}
+
+} // namespace fspt

@@ -114,6 +114,10 @@ struct CameraP {
   float lens[2];
 };
 
+// the opt-in camera models (fspt.h fspt_camera_model_params; the rule: fspt_camera_model.hpp); CAM_* = FSPT_CAMERA_*
+enum { CAM_PINHOLE = 0, CAM_ORTHO = 1, CAM_FISHEYE = 2, CAM_EQUIRECT = 3, CAM_STEREO = 4 };
+struct CameraModelP { int model; float angle; float ipd; };
+
 struct TraceP {
   DScene scene;
   uint32_t W, H;
@@ -332,6 +336,7 @@ struct FeatureP {
   uint64_t seed;  // the camera rays' randBase values: fspt_rand_base_next's stream from this state
   float4 *feat;   // 2 x float4 per pixel: (albedo.rgb, depth), (normal.xyz, coverage)
 };
+struct FeatureModelP { FeatureP f; CameraModelP cm; }; // k_features_model: the guides under a camera model
 struct AtrousP {
   const float4 *src; // u^k, or (demod) the accumulator
   float4 *dst;
@@ -478,7 +483,14 @@ hipError_t launch_adaptive_error(const AdaptiveP &p, hipStream_t stream);
 hipError_t launch_adaptive_select(const AdaptiveP &p, hipStream_t stream);
 // the two passes of the image chain that trace rays (fspt_post.cpp launches them)
 hipError_t launch_features(const FeatureP &p, hipStream_t stream);
+hipError_t launch_features_model(const FeatureModelP &p, hipStream_t stream); // p.cm.model != CAM_PINHOLE
 hipError_t launch_temporal_gbuffer(const TemporalGP &p, hipStream_t stream);
+
+// ---------------------------------------------------------------------------
+// launcher of fspt_camera.hip: the ray buffers of a tick under a camera model (cm.model != CAM_PINHOLE: hipErrorInvalidValue)
+// ---------------------------------------------------------------------------
+hipError_t launch_camera_model(uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const CameraP &cam, const CameraModelP &cm, float rand_base,
+                               float4 *pos, float4 *dir, hipStream_t stream, uint32_t sampler, uint32_t smp_seed, uint32_t sample);
 
 // ---------------------------------------------------------------------------
 // launchers of fspt_post.hip: whatever reads only images

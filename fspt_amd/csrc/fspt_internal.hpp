@@ -10,6 +10,7 @@
 //   fspt_kernels.hip       every kernel that reads a DScene: the path tracer, the test passes, k_features, k_temporal_gbuffer
 //   fspt_post.hip          every kernel that reads only images: what fspt_post.cpp launches, but for those two
 //   fspt_bvh_build.hip     the GPU BVH builder;  fspt_refit.hip  in-place refit and rebuild;  fspt_pose.hip  part transforms
+//   fspt_camera.hip        ray generation under an opt-in camera model (the rule: fspt_camera_model.hpp)
 //   fspt_appearance.hip    in-place appearance update: the texture-set, atlas and environment layouts and the material part of the hit records
 #pragma once
 #include "../../include/fspt.h"
@@ -292,6 +293,9 @@ struct fspt_target {
   bool cam_recorded = false;     // last_cam is valid and newer than the ray buffers' contents
   bool rays_injected = false;    // the ray buffers hold caller-supplied rays (fspt_set_rays): trace them as they are
   bool defer = true;             // fspt_target_set_deferred
+  // fspt_target_set_camera_model: model != FSPT_CAMERA_PINHOLE sends every tick through k_camera_model
+  // (fspt_camera.hip) into the ray buffers and the single-tick trace from them (render_ticks)
+  fspt::CameraModelP cam_model{fspt::CAM_PINHOLE, 3.14159265f, 0.064f};
   // Primary-form tuner (batch scheduler): k_wf_primary has two forms of its traversal phase with identical results
   // (fspt_kernels.hip).  Which is faster depends on the scene and the batch size, so the target measures: HIP events
   // around the primary launch of a batch, read back without waiting at the start of a later batch.  Per batch size: the
@@ -426,6 +430,7 @@ int flush_pending(fspt_target *t);     // execute the recorded two-call ticks (a
                                        // own flushes do not join: under present they go through present_flush)
 int present_join(fspt_target *t);      // wait for everything fspt_present enqueued on the lane streams
 int materialise_rays(fspt_target *t);  // the ray buffers as the most recent fspt_camera call left them
+const char *camera_model_name(int model); // "pinhole", "ortho", ... (error messages)
 uint32_t clamp_bounces(uint32_t nb);
 // ---- fspt_post.cpp
 // k_draw of `src` on `st` into `out` (device memory), through the target's auto-exposure and bloom when they are on

@@ -25,6 +25,7 @@
 // reference's, so results equal the CPU restatement (oracle/) bit for bit.
 #include "fspt_device.hpp"
 #include "fspt_math.hpp"
+#include "fspt_camera_model.hpp" // model_ray: k_features_model alone uses it
 
 namespace fspt {
 using namespace fm;
@@ -2511,7 +2512,7 @@ FM_DEV float rand_base_step(uint64_t &st) {
 // One thread per pixel of the whole target (16 x 16-pixel blocks: a wave's camera rays start on a 16 x 4 patch), `samples`
 // camera rays each - exactly k_camera's ray for randBase r_s - traced to their closest hit with the wave's LDS stack like
 // k_intersect.  Per pixel: the float32 sums in sample order / samples of (texDiffuse, t) and (macroNormal, hit); a miss
-// counts as albedo (1, 1, 1), normal 0, depth MAX_T, hit 0.
+// counts as albedo (1, 1, 1), normal 0, depth MAX_T, hit 0.  (k_features_model below is a copy under a camera model: edit both.)
 __global__ __launch_bounds__(BLOCK_THREADS) void k_features(const FeatureP p) {
   extern __shared__ int lds_stack[];
   const uint32_t tid = threadIdx.y * blockDim.x + threadIdx.x;
@@ -2528,6 +2529,46 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_features(const FeatureP p) {
     const float rb = rand_base_step(st);
     V3 o, d;
     camera_ray(x, y, p.W, p.H, p.cam, rb, o, d);
+    int hitA, hitB;
+    float tB;
+    trace_rays<false, false>(S, stack, o, false, d, d, hitA, tB, hitB, cnt);
+    V3 a = v3(1.0f, 1.0f, 1.0f), n = v3(0.0f, 0.0f, 0.0f);
+    float h = 0.0f;
+    if (hitB >= 0) {
+      first_hit_guides(S, o, d, tB, hitB, a, n);
+      h = 1.0f;
+    }
+    ar += a.x; ag += a.y; ab += a.z; z += tB;
+    nx += n.x; ny += n.y; nz += n.z; hits += h;
+  }
+  const float fs = (float)p.samples;
+  const size_t i = (size_t)y * p.W + x;
+  p.feat[2 * i] = make_float4(ar / fs, ag / fs, ab / fs, z / fs);
+  p.feat[2 * i + 1] = make_float4(nx / fs, ny / fs, nz / fs, hits / fs);
+}
+
+// k_features under a camera model (fspt_target_set_camera_model): the same pass, its `samples` rays per pixel
+// from model_ray<SMP_REF, MODEL> (fspt_camera_model.hpp) instead of camera_ray, so that the guides follow the camera.
+// A COPY of k_features but for that one call (k_features itself stays byte for byte what it was): whatever changes in one
+// of the two kernels must change in the other.
+template <int MODEL>
+__global__ __launch_bounds__(BLOCK_THREADS) void k_features_model(const FeatureModelP pm) {
+  extern __shared__ int lds_stack[];
+  const FeatureP &p = pm.f;
+  const uint32_t tid = threadIdx.y * blockDim.x + threadIdx.x;
+  const int lane = (int)(tid & (WAVE - 1));
+  const int wave = (int)(tid / WAVE);
+  const DScene &S = p.scene;
+  int *stack = lds_stack + (size_t)wave * S.stack_n * WAVE + lane;
+  const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+  if (x >= p.W || y >= p.H) return;
+  Counters cnt = {0, 0, 0, 0, 0, 0};
+  uint64_t st = p.seed;
+  float ar = 0.0f, ag = 0.0f, ab = 0.0f, z = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f, hits = 0.0f;
+  for (uint32_t s = 0; s < p.samples; ++s) {
+    const float rb = rand_base_step(st);
+    V3 o, d;
+    model_ray<SMP_REF, MODEL>(x, y, p.W, p.H, p.cam, pm.cm, rb, 0u, 0u, o, d);
     int hitA, hitB;
     float tB;
     trace_rays<false, false>(S, stack, o, false, d, d, hitA, tB, hitB, cnt);
@@ -2976,6 +3017,24 @@ hipError_t launch_features(const FeatureP &p, hipStream_t stream) {
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_features, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), lds, stream, p);
   return hipGetLastError();
+}
+
+template <int MODEL>
+static hipError_t launch_features_model_as(const FeatureModelP &p, hipStream_t stream) {
+  const size_t lds = stack_bytes(p.f.scene);
+  hipError_t e = allow_lds(k_features_model<MODEL>, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_features_model<MODEL>, dim3((p.f.W + 15) / 16, (p.f.H + 15) / 16), dim3(16, 16), lds, stream, p);
+  return hipGetLastError();
+}
+hipError_t launch_features_model(const FeatureModelP &p, hipStream_t stream) {
+  switch (p.cm.model) {
+    case CAM_ORTHO: return launch_features_model_as<CAM_ORTHO>(p, stream);
+    case CAM_FISHEYE: return launch_features_model_as<CAM_FISHEYE>(p, stream);
+    case CAM_EQUIRECT: return launch_features_model_as<CAM_EQUIRECT>(p, stream);
+    case CAM_STEREO: return launch_features_model_as<CAM_STEREO>(p, stream);
+    default: return hipErrorInvalidValue; // (the pinhole camera: launch_features)
+  }
 }
 
 hipError_t launch_temporal_gbuffer(const TemporalGP &p, hipStream_t stream) {

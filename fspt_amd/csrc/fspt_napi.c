@@ -1014,6 +1014,44 @@ static napi_value SetLights(napi_env env, napi_callback_info info) {
   FSPT_OK_OR_THROW(fspt_target_set_lights((fspt_target *)h, mode, (float)f));
   return undefined(env);
 }
+/* setCameraModel(target, model, angle, ipd): fspt_target_set_camera_model (model: FSPT_CAMERA_*).  fspt.js has
+ * checked the arguments; they are checked again here (the target's height for STEREO: by the library). */
+static napi_value SetCameraModel(napi_env env, napi_callback_info info) {
+  napi_value a[4]; void *h; int32_t model; double angle, ipd; fspt_camera_model_params p;
+  if (get_args(env, info, 4, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  NAPI_OK(napi_get_value_int32(env, a[1], &model));
+  NAPI_OK(napi_get_value_double(env, a[2], &angle));
+  NAPI_OK(napi_get_value_double(env, a[3], &ipd));
+  if (model < FSPT_CAMERA_PINHOLE || model > FSPT_CAMERA_STEREO) {
+    napi_throw_range_error(env, NULL, "fspt_napi: setCameraModel: unknown model");
+    return NULL;
+  }
+  if (model == FSPT_CAMERA_FISHEYE && !((float)angle > 0.0f && (float)angle <= 6.2831855f)) {
+    napi_throw_range_error(env, NULL, "fspt_napi: setCameraModel: angle must lie in (0, 2 pi]");
+    return NULL;
+  }
+  if (model == FSPT_CAMERA_STEREO && !((float)ipd >= 0.0f && (float)ipd <= 3.0e38f)) {
+    napi_throw_range_error(env, NULL, "fspt_napi: setCameraModel: ipd must be finite and >= 0");
+    return NULL;
+  }
+  p.model = model; p.angle = (float)angle; p.ipd = (float)ipd;
+  FSPT_OK_OR_THROW(fspt_target_set_camera_model((fspt_target *)h, &p));
+  return undefined(env);
+}
+/* cameraModel(target) -> { model, angle, ipd }: fspt_target_get_camera_model */
+static napi_value CameraModel(napi_env env, napi_callback_info info) {
+  napi_value a[1], o, v; void *h; fspt_camera_model_params p;
+  if (get_args(env, info, 1, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  FSPT_OK_OR_THROW(fspt_target_get_camera_model((fspt_target *)h, &p));
+  NAPI_OK(napi_create_object(env, &o));
+  NAPI_OK(napi_create_int32(env, p.model, &v));
+  NAPI_OK(napi_set_named_property(env, o, "model", v));
+  NAPI_OK(napi_create_double(env, (double)p.angle, &v));
+  NAPI_OK(napi_set_named_property(env, o, "angle", v));
+  NAPI_OK(napi_create_double(env, (double)p.ipd, &v));
+  NAPI_OK(napi_set_named_property(env, o, "ipd", v));
+  return o;
+}
 /* renderAdaptive(target, params, targetRelMse, maxTicks, minTicks, roundTicks, seed) -> the largest count run:
  * fspt_render_adaptive (include/fspt.h) */
 static napi_value RenderAdaptive(napi_env env, napi_callback_info info) {
@@ -1404,7 +1442,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
       {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"sceneSetPose", SceneSetPose}, {"sceneUpdateTransforms", SceneUpdateTransforms}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
-      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
+      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setCameraModel", SetCameraModel}, {"cameraModel", CameraModel}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},
       {"renderAsync", RenderAsync}, {"multiCreate", MultiCreate}, {"multiDestroy", MultiDestroy}, {"multiTarget", MultiTarget},
       {"multiCamera", MultiCamera}, {"multiTrace", MultiTrace}, {"multiRender", MultiRender}, {"multiRenderAsync", MultiRenderAsync},

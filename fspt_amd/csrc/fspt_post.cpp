@@ -192,6 +192,10 @@ int fspt_features(fspt_target *t, const fspt_camera_params *cam, uint32_t sample
   p.seed = seed;
   p.feat = t->feat;
   t->feat_valid = false;
+  if (t->cam_model.model != FSPT_CAMERA_PINHOLE) { // the sibling kernel: the guides follow the camera
+    fspt::FeatureModelP pm{p, t->cam_model};
+    HIP_TRY(fspt::launch_features_model(pm, t->stream));
+  } else
   HIP_TRY(fspt::launch_features(p, t->stream));
   t->feat_valid = true;
   return FSPT_OK;
@@ -281,6 +285,10 @@ int fspt_temporal_accumulate(fspt_target *t, const fspt_camera_params *cam, cons
   if (rc) return rc;
   if ((rc = dn_enter(t, true, "fspt_temporal_accumulate"))) return rc;
   if (t->n_shards > 1) { fspt_set_error("fspt_temporal_accumulate: sharded target (its accumulator holds a part of the frame)"); return FSPT_E_STATE; }
+  if (t->cam_model.model != FSPT_CAMERA_PINHOLE) {
+    fspt_set_error("fspt_temporal_accumulate: not under camera model '%s' (reprojection through a non-pinhole projection is a follow-up)", camera_model_name(t->cam_model.model));
+    return FSPT_E_STATE;
+  }
   if (t->vw != t->W || t->vh != t->H) { fspt_set_error("fspt_temporal_accumulate: the viewport %ux%u is smaller than the target", t->vw, t->vh); return FSPT_E_STATE; }
   if (t->acc_ticks == 0) { fspt_set_error("fspt_temporal_accumulate: the accumulator holds no sample (render first)"); return FSPT_E_STATE; }
   if (t->tm_moments && !t->feat_valid) { fspt_set_error("fspt_temporal_accumulate: moments are on and there is no fspt_features call yet (the input is demodulated by its albedo)"); return FSPT_E_STATE; }

@@ -307,6 +307,21 @@ function loadBlob(path) {
 const PIPELINE_CODES = { megakernel: 0, wavefront: 1, stream: 2 };
 
 // a pipeline name (or a code of include/fspt_tuning.h's fspt_target_set_pipeline); anything else is an error, as in the Python host
+const CAMERA_MODELS = ['pinhole', 'ortho', 'fisheye', 'equirect', 'stereo'];  // include/fspt.h FSPT_CAMERA_*
+/** setCameraModel's { model, angle, ipd } checked -> [code, angle, ipd] for the addon (which checks them again) */
+function cameraModelArgs(params) {
+  const p = params === undefined || params === null ? {} : params;
+  if (typeof p !== 'object') throw new TypeError('setCameraModel: expects { model, angle, ipd }');
+  const name = p.model === undefined || p.model === null ? 'pinhole' : p.model;
+  const code = CAMERA_MODELS.indexOf(name);
+  if (code < 0) throw new RangeError("setCameraModel: model must be one of 'pinhole', 'ortho', 'fisheye', 'equirect', 'stereo'");
+  if (p.angle !== undefined && name !== 'fisheye') throw new RangeError("setCameraModel: angle only goes with 'fisheye'");
+  if (p.ipd !== undefined && name !== 'stereo') throw new RangeError("setCameraModel: ipd only goes with 'stereo'");
+  const angle = p.angle === undefined ? f(Math.PI) : p.angle, ipd = p.ipd === undefined ? f(0.064) : p.ipd;
+  if (typeof angle !== 'number' || !(f(angle) > 0 && f(angle) <= f(2 * Math.PI))) throw new RangeError('setCameraModel: angle must be a number in (0, 2 pi] radians');
+  if (typeof ipd !== 'number' || !(f(ipd) >= 0 && Number.isFinite(f(ipd)))) throw new RangeError('setCameraModel: ipd must be a finite number >= 0');
+  return [code, angle, ipd];
+}
 function pipelineCode(name) {
   if (PIPELINE_CODES[name] !== undefined) return PIPELINE_CODES[name];
   if (Number.isInteger(name) && name >= 0 && name <= 2) return name;
@@ -522,6 +537,17 @@ class PathTracer {
     if (typeof f !== 'number' || !(f > 0 && f <= 1)) throw new RangeError('setLights: emitterFraction must be a number in (0, 1]');
     addon.setLights(this._target, code, f);
   }
+  /** the camera model (include/fspt.h fspt_target_set_camera_model, DESIGN 8.15): { model: 'pinhole' (default) | 'ortho' |
+   *  'fisheye' | 'equirect' | 'stereo', angle (fisheye: field of view over the frame height in radians, in (0, 2 pi],
+   *  default pi), ipd (stereo: scene units, >= 0, default 0.064; the height must be even) }.  Runs the recorded ticks
+   *  first, does not clear.  Throws Error('render in flight') during a renderAsync. */
+  setCameraModel(params) {
+    addon.setCameraModel(this._target, ...cameraModelArgs(params));
+  }
+  get cameraModel() {
+    const p = addon.cameraModel(this._target);
+    return { model: CAMERA_MODELS[p.model], angle: p.angle, ipd: p.ipd };
+  }
   /** new vertices (Float32Array, 9 per triangle) and optionally normTex records (27 per triangle) for the scene's triangles
    *  in leaf order: the BVH is refitted on the GPU, nothing else changes (include/fspt.h fspt_scene_update_geometry, DESIGN
    *  8.6).  The accumulator is not cleared: call clear().  Throws Error('render in flight') during a renderAsync. */
@@ -681,6 +707,11 @@ class MultiPathTracer {
   setPipeline(name, batch) {
     const code = pipelineCode(name);
     for (let i = 0; i < this.devices.length; i++) addon.setPipeline(addon.multiTarget(this._multi, i), code, batch || 0);
+  }
+  /** PathTracer.setCameraModel on every device's target (a ray depends on its pixel only) */
+  setCameraModel(params) {
+    const args = cameraModelArgs(params);
+    for (let i = 0; i < this.devices.length; i++) addon.setCameraModel(addon.multiTarget(this._multi, i), ...args);
   }
   close() {
     if (this._inflight) return this._inflight.then(() => this.close());

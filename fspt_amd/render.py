@@ -10,6 +10,7 @@ reference's format (scene/<name>.json with props / static_props / animated_props
     python -m fspt_amd.render --mesh-n 289 --bvh gpu --spp 16 --out c3.png  # binned-SAH tree built on the GPU
     python -m fspt_amd.render --scene 'web/scene/anim_{frame}.json' --frames 0:24 --bvh refit --out 'out/{frame}.png'  # build once, refit
     python -m fspt_amd.render --scene 'web/scene/anim_{frame}.json' --frames 0:24 --bvh refit --pose --out 'out/{frame}.png'  # one matrix per prop per frame
+    python -m fspt_amd.render --out pano.png --width 1024 --height 512 --camera equirect  # 360-degree panorama (also: ortho, fisheye:180, stereo:0.064)
 
 Path tracing runs in the HIP kernels (fspt_render), tone mapping in the draw.fs kernel (fspt_draw); --atrous K runs
 the guided a-trous denoiser (fspt_features + fspt_denoise, K iterations) before tone mapping (fspt_draw_denoised).
@@ -22,8 +23,36 @@ import numpy as np
 from . import PathTracer, scene as S
 
 
-def main():
+def parse_camera(spec):
+    """--camera pinhole|ortho|fisheye[:DEGREES]|equirect|stereo[:IPD] -> PathTracer.set_camera_model's keyword arguments
+    (the fisheye's field of view over the frame height in degrees, in (0, 360]; the stereo pair's ipd in scene units)."""
+    name, _, arg = spec.partition(":")
+    if name not in ("pinhole", "ortho", "fisheye", "equirect", "stereo"):
+        raise ValueError(f"--camera: unknown model {name!r} (pinhole, ortho, fisheye[:DEGREES], equirect, stereo[:IPD])")
+    kw = {"model": name}
+    if _ and name not in ("fisheye", "stereo"):
+        raise ValueError(f"--camera {name} takes no argument")
+    if _:
+        try:
+            v = float(arg)
+        except ValueError:
+            raise ValueError(f"--camera {name}: {arg!r} is not a number") from None
+        if name == "fisheye":
+            if not (np.isfinite(v) and 0.0 < v <= 360.0):
+                raise ValueError("--camera fisheye:DEGREES must lie in (0, 360]")
+            kw["angle"] = min(float(np.float32(np.deg2rad(v))), float(np.float32(2.0 * np.pi)))
+        else:
+            if not (np.isfinite(v) and v >= 0.0):
+                raise ValueError("--camera stereo:IPD must be finite and >= 0")
+            kw["ipd"] = v
+    return kw
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--camera", default="pinhole", metavar="MODEL",
+                    help="camera model (DESIGN 8.15): pinhole | ortho | fisheye[:DEGREES over the frame height, default 180] | equirect | "
+                         "stereo[:IPD in scene units, default 0.064; over-under, needs an even --height]")
     ap.add_argument("--out", default="fspt.png")
     ap.add_argument("--width", type=int, default=960)
     ap.add_argument("--height", type=int, default=540)
@@ -73,7 +102,13 @@ def main():
     ap.add_argument("--adaptive", type=float, default=None, metavar="REL_MSE",
                     help="adaptive sampling: stop a 32x32 tile once its estimated relative MSE is below REL_MSE (--spp = the most)")
     ap.add_argument("--sample-map", default=None, help="with --adaptive: write the ticks per pixel as a grey PNG")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    try:
+        camera = parse_camera(args.camera)
+    except ValueError as e:
+        ap.error(str(e))
+    if camera["model"] != "pinhole" and (args.adaptive is not None or args.temporal):
+        ap.error("--camera other than pinhole cannot be combined with --adaptive or --temporal")
     if args.bvh == "refit" and not (args.scene and args.frames):
         ap.error("--bvh refit needs --scene and --frames (it reuses one scene across a frame sequence)")
     if args.adaptive is not None:
@@ -115,7 +150,7 @@ def main():
         ap.error("--sampler-seed must lie in [0, 2^32)")
     if args.scene:
         from . import scene_file as F
-        spp = args.spp if "--spp" in " ".join(__import__("sys").argv) else None  # default: the scene's `samples`
+        spp = args.spp if "--spp" in " ".join(__import__("sys").argv if argv is None else argv) else None  # default: the scene's `samples`
         kw = dict(samples=spp, bounces=args.bounces, seed=args.seed, saturation=args.saturation, denoise=args.denoise)
         if args.lights:
             kw.update(lights="emitters", emitter_fraction=args.emitter_fraction)
@@ -125,6 +160,8 @@ def main():
             kw.update(auto_exposure=True if args.auto_exposure is True else {"key": args.auto_exposure})
         if args.bloom is not None:
             kw.update(bloom=True if args.bloom is True else {"intensity": args.bloom})
+        if camera["model"] != "pinhole":
+            kw.update(camera=camera)
         if args.frames:
             a, b = (int(x) for x in args.frames.split(":"))
             t0 = time.perf_counter()
@@ -150,6 +187,12 @@ def main():
           f"{time.perf_counter() - t0:.2f} s")
     pt = PathTracer(arrays, args.width, args.height, num_bounces=args.bounces)
     pt.set_camera(**S.BUNNY_CAMERA)
+    if camera["model"] != "pinhole":
+        from . import FsptError
+        try:
+            pt.set_camera_model(**camera)
+        except FsptError as e:  # (stereo on an odd --height: the library's message)
+            ap.error(str(e))
     if args.sampler != "reference":
         pt.set_sampler(args.sampler, args.sampler_seed)
     if args.lights:

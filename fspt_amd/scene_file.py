@@ -99,7 +99,7 @@ def _settings(scene, focus):
 
 def render_frame(arrays, settings, width, height, samples=None, bounces=4, seed=1, saturation=1.0, denoise=False,
                  max_sigma=3.0, device=0, lights=None, emitter_fraction=0.5, adaptive=None, sample_map=None, auto_exposure=None,
-                 bloom=None):
+                 bloom=None, camera=None):
     """One frame as the reference produces it in frame mode: `samples` ticks from a cleared accumulator
     (main.js:838-857; its very first, discarded tick is not reproduced), then drawQuad.  Returns
     (rgba8 [H, W, 4] top row first - what canvas.toBlob encodes -, radiance [H, W, 4] bottom row first).
@@ -108,12 +108,16 @@ def render_frame(arrays, settings, width, height, samples=None, bounces=4, seed=
     then also write its ticks per pixel as a grey PNG there (white = `samples`).  auto_exposure: True or a dict of
     PathTracer.set_auto_exposure's parameters (DESIGN 8.11): the frame is metered on the GPU and the scene's `exposure`
     becomes a compensation; a still adapts instantly.  bloom: True or a dict of PathTracer.set_bloom's parameters (DESIGN
-    8.12): the drawing mixes the HDR pyramid's glow in before the exposure."""
+    8.12): the drawing mixes the HDR pyramid's glow in before the exposure.  camera: None or a dict of
+    PathTracer.set_camera_model's arguments (not with adaptive)."""
     from .tracer import PathTracer
     auto_exposure = _auto_exposure_params(auto_exposure)
     bloom = _bloom_params(bloom)
+    camera = _camera_model_params(camera, adaptive)
     pt = PathTracer(arrays, width, height, device=device, num_bounces=bounces)
     try:
+        if camera is not None:
+            pt.set_camera_model(**camera)
         if auto_exposure is not None:
             pt.set_auto_exposure(True, **auto_exposure)
         if bloom is not None:
@@ -140,6 +144,22 @@ def _auto_exposure_params(auto_exposure, adapt=None):
         params.update(adapt_up=adapt, adapt_down=adapt)
     _exposure_params(params)
     return params
+
+
+def _camera_model_params(camera, adaptive=None, temporal=None):
+    """None (pinhole) or PathTracer.set_camera_model's keyword arguments, refused here if the library would (but for the
+    target's height, which it checks)"""
+    if camera is None:
+        return None
+    from .tracer import camera_model_params
+    camera = dict(camera)
+    if set(camera) - {"model", "angle", "ipd"}:
+        raise TypeError(f"unknown camera parameters {sorted(set(camera) - {'model', 'angle', 'ipd'})}")
+    if camera_model_params(**camera).model == 0:
+        return None
+    if adaptive is not None or temporal is not None:
+        raise ValueError("a camera model other than pinhole cannot be combined with adaptive sampling or temporal accumulation")
+    return camera
 
 
 def _bloom_params(bloom):
@@ -254,7 +274,7 @@ def _parse_order_parts(base):
 
 
 def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", rebuild_above=None,
-                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, **kw):
+                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, camera=None, **kw):
     """frame=N sequencing (main.js:851-866, 966-969): for every N in `frames` load `scene_pattern.format(frame=N)`
     (the per-frame scene JSON the reference's server hands out for `?frame=N`), render it, write
     `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1.
@@ -292,8 +312,11 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     tracer lives across the frames and the exposure ADAPTS: adapt_up = adapt_down = SEQUENCE_ADAPT per frame unless the
     dict names one; every other bvh builds a tracer per frame, which meters instantly.  A new scene starts from a first metering.
     bloom: True or a dict of PathTracer.set_bloom's parameters; every tracer gets set_bloom() before its first
-    frame, and each frame's one drawing blooms what it draws."""
+    frame, and each frame's one drawing blooms what it draws.
+    camera: None or a dict of PathTracer.set_camera_model's arguments; every tracer gets set_camera_model()
+    before its first frame (not with temporal or adaptive)."""
     from PIL import Image
+    camera = _camera_model_params(camera, kw.get("adaptive"), None if temporal is None or temporal is False else temporal)
     auto_exposure = _auto_exposure_params(auto_exposure, SEQUENCE_ADAPT if bvh == "refit" else None)
     bloom = _bloom_params(bloom)
     written = []
@@ -333,7 +356,7 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     if bvh != "refit":
         for n in frames:
             arrays, settings = load_scene_file(scene_pattern.format(frame=n), asset_root, bvh=bvh, device=device)
-            rgba, _ = render_frame(arrays, settings, width, height, auto_exposure=auto_exposure, bloom=bloom, **kw)
+            rgba, _ = render_frame(arrays, settings, width, height, auto_exposure=auto_exposure, bloom=bloom, camera=camera, **kw)
             if on_frame:
                 on_frame(n, "build")
             save(n, rgba)
@@ -408,6 +431,8 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                 leaf_order = base.meta["tri_order"]
                 held, atlas_sent = held_appearance(base), False
                 rest_json = None
+                if camera is not None:
+                    pt.set_camera_model(**camera)
                 if pose and not frame_json.get("normalize"):
                     pt.scene.set_pose(base.meta["tri_part"], n_parts=len(S.merge_scene_props(frame_json)))
                     rest_json = frame_json

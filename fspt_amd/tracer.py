@@ -317,6 +317,30 @@ def _sampler_seed(seed):
 PIPELINES = {"megakernel": 0, "wavefront": 1, "stream": 2}  # fspt_target_set_pipeline codes
 SAMPLERS = {"reference": 0, "sobol": 1}  # fspt_target_set_sampler codes
 LIGHTS = {"off": 0, "emitters": 1}  # fspt_target_set_lights codes
+CAMERA_MODELS = {"pinhole": 0, "ortho": 1, "fisheye": 2, "equirect": 3, "stereo": 4}  # fspt_target_set_camera_model codes
+
+
+def camera_model_params(model="pinhole", angle=None, ipd=None):
+    """set_camera_model's arguments, checked, as the fspt_camera_model_params the library takes (it checks them again,
+    and the target's height for "stereo").  angle (radians) only goes with "fisheye", ipd only with "stereo"."""
+    if model is None:
+        model = "pinhole"
+    if model not in CAMERA_MODELS:
+        raise ValueError("camera model must be one of %s, got %r" % (sorted(CAMERA_MODELS), model))
+    for name, v, owner in (("angle", angle, "fisheye"), ("ipd", ipd, "stereo")):
+        if v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise TypeError("%s must be a number, got %r" % (name, v))
+        if model != owner:
+            raise ValueError("%s only goes with the %r camera model, got %r" % (name, owner, model))
+    a = np.float32(np.pi) if angle is None else np.float32(angle)
+    d = np.float32(0.064) if ipd is None else np.float32(ipd)
+    if model == "fisheye" and not (np.isfinite(a) and 0.0 < a <= np.float32(2.0 * np.pi)):
+        raise ValueError("fisheye angle must lie in (0, 2 pi] radians, got %r" % (angle,))
+    if model == "stereo" and not (np.isfinite(d) and d >= 0.0):
+        raise ValueError("stereo ipd must be finite and >= 0, got %r" % (ipd,))
+    return L.CameraModelParams(CAMERA_MODELS[model], float(a), float(d))
 # fspt_denoise's defaults (include/fspt.h FSPT_DENOISE_*; tests/test_denoise_cpu.py pins the two)
 DENOISE_DEFAULTS = {"iterations": 4, "sigma_color": 4.0, "sigma_normal": 32.0, "sigma_depth": 0.05}
 
@@ -640,6 +664,7 @@ class PathTracer:
         self.pingpong = 0
         self._rng = C.c_uint64(1)
         self._keep = None
+        self._rays_keep = []  # set_rays_device's tensors, held until this tracer's stream has been synchronised
         self._tile = 32  # set_shard's tile (adaptive_stats)
 
     # ---- configuration -----------------------------------------------------
@@ -675,6 +700,20 @@ class PathTracer:
         if kind not in SAMPLERS:
             raise ValueError("sampler must be one of %s, got %r" % (sorted(SAMPLERS), kind))
         L.check(L.lib().fspt_target_set_sampler(self._t, SAMPLERS[kind], _sampler_seed(seed)))
+
+    def set_camera_model(self, model="pinhole", angle=None, ipd=None):
+        """The camera model (fspt_target_set_camera_model): "pinhole" (the default, or None), "ortho", "fisheye"
+        (angle: the full field of view over the frame height in radians, in (0, 2 pi], default pi), "equirect" or "stereo"
+        (over-under, the upper half is the left eye; ipd in scene units, >= 0, default 0.064; the height must be even).
+        Runs the recorded ticks first; does not clear the accumulator."""
+        L.check(L.lib().fspt_target_set_camera_model(self._t, camera_model_params(model, angle, ipd)))
+
+    @property
+    def camera_model(self):
+        """{"model", "angle", "ipd"} of fspt_target_get_camera_model."""
+        p = L.CameraModelParams()
+        L.check(L.lib().fspt_target_get_camera_model(self._t, C.byref(p)))
+        return {"model": {v: n for n, v in CAMERA_MODELS.items()}[p.model], "angle": float(p.angle), "ipd": float(p.ipd)}
 
     def set_lights(self, mode="emitters", emitter_fraction=0.5):
         """Next-event estimation of emissive triangles (fspt_target_set_lights): "emitters" lets a shading
@@ -913,6 +952,7 @@ class PathTracer:
 
     def sync(self):
         L.check(L.lib().fspt_sync(self._t))
+        self._rays_keep = []
 
     # ---- read-back -------------------------------------------------------------
     def setRays(self, pos, dir):
@@ -922,6 +962,23 @@ class PathTracer:
         if pos.size != n or dir.size != n:
             raise ValueError("ray buffers must be W*H*4 floats")
         L.check(L.lib().fspt_set_rays(self._t, L.fptr(pos), L.fptr(dir)))
+
+    def set_rays_device(self, pos, dir):
+        """setRays with torch tensors on the tracer's device (fspt_set_rays_device): float32, contiguous, W*H*4 elements
+        each; copied on the tracer's stream without a host synchronisation.  The tensors' producer must have finished
+        (e.g. torch.cuda.synchronize()) before the call, and their memory must stay unmodified until the copy has run: the
+        tracer holds a reference to both until its next sync() or readRadiance(), so that dropping them is safe; writing
+        new rays into the SAME tensors needs a sync() first."""
+        n = self.resolution[0] * self.resolution[1] * 4
+        for name, a in (("pos", pos), ("dir", dir)):
+            if not (hasattr(a, "data_ptr") and hasattr(a, "is_cuda")):
+                raise TypeError(f"set_rays_device: {name} must be a torch tensor")
+            if not a.is_cuda or a.device.index != self.scene.device:
+                raise ValueError(f"set_rays_device: {name} must live on device {self.scene.device}, got {a.device}")
+            if str(a.dtype) != "torch.float32" or not a.is_contiguous() or a.numel() != n:
+                raise ValueError(f"set_rays_device: {name} must be a contiguous float32 tensor of W*H*4 elements")
+        L.check(L.lib().fspt_set_rays_device(self._t, C.c_void_p(pos.data_ptr()), C.c_void_p(dir.data_ptr())))
+        self._rays_keep.append((pos, dir))
 
     def readRays(self):
         W, H = self.resolution
@@ -933,6 +990,7 @@ class PathTracer:
         W, H = self.resolution
         out = np.zeros((H, W, 4), np.float32)
         L.check(L.lib().fspt_read_radiance(self._t, L.fptr(out)))
+        self._rays_keep = []  # (the read waited for the stream)
         return out
 
     def draw(self, exposure=1.0, saturation=1.0, denoise=False, max_sigma=3.0, scale=1.0):
@@ -1163,6 +1221,7 @@ class PathTracer:
             L.lib().fspt_target_destroy(self._t)
             self._t = C.c_void_p()
             self._keep = None
+            self._rays_keep = []
 
     def __del__(self):
         try:
@@ -1214,6 +1273,12 @@ class MultiPathTracer:
     def set_tail(self, round=-1):
         for t in self._targets():
             L.check(L.lib().fspt_target_set_tail(t, int(round)))
+
+    def set_camera_model(self, model="pinhole", angle=None, ipd=None):
+        """PathTracer.set_camera_model on every device's target (a ray depends on its pixel only: DESIGN 9)."""
+        p = camera_model_params(model, angle, ipd)
+        for t in self._targets():
+            L.check(L.lib().fspt_target_set_camera_model(t, p))
 
     def prepare(self):
         for t in self._targets():

@@ -1,26 +1,17 @@
 /*
- * fspt.h — C ABI of libfspt, the MI355X-native replacement for the WebGL2
- * draw-call boundary of apbodnar/FSPT's path-trace hot path.
+ * fspt.h — C ABI of libfspt, the MI355X-native replacement for the WebGL2 draw-call boundary of apbodnar/FSPT's path-trace hot path.
  *
- * The reference has no plugin/FFI interface: its hot path (shader/tracer.fs)
- * sits behind the WebGL2 calls issued by main.js. Every entry point below
- * names the reference call site it replaces (file:line in /root/reference).
- * INTEGRATION.md shows the N-API stub a maintainer of the reference would add
- * to main.js to call these instead of gl.*.
+ * The reference has no plugin/FFI interface: its hot path (shader/tracer.fs) sits behind the WebGL2 calls issued by main.js.
+ * Every entry point below names the reference call site it replaces (file:line in /root/reference).  INTEGRATION.md shows
+ * the N-API stub a maintainer of the reference would add to main.js to call these instead of gl.*.
  *
  * Conventions
  *   - plain C, no C++/torch/HIP types in any signature;
- *   - every function returns 0 on success, <0 (FSPT_E_*) on error;
- *     fspt_last_error() returns a thread-local message (reference just
- *     console.log()s / throws: main.js:91-94, 564-569);
- *   - the library COPIES every host array it is given (caller may free after
- *     the call returns);
- *   - all calls for one target come from one host thread at a time (the reference
- *     is a single JS thread: main.js:838-857); work is enqueued on HIP streams -
- *     the two-call ticks even later, see fspt_camera - and only fspt_read_*,
- *     fspt_draw*, fspt_sync, fspt_get_counters and the fspt_last_* timers block;
- *   - there is NO CPU fallback: without a HIP device every device entry point
- *     fails with FSPT_E_NO_DEVICE.
+ *   - every function returns 0 on success, <0 (FSPT_E_*) on error; fspt_last_error() returns a thread-local message (reference: console.log / throw);
+ *   - the library COPIES every host array it is given (caller may free after the call returns);
+ *   - all calls for one target come from one host thread at a time (the reference is a single JS thread: main.js:838-857); work is enqueued on HIP
+ *     streams - the two-call ticks even later, see fspt_camera - and only fspt_read_*, fspt_draw*, fspt_sync, fspt_get_counters and the fspt_last_* timers block;
+ *   - there is NO CPU fallback: without a HIP device every device entry point fails with FSPT_E_NO_DEVICE.
  */
 #ifndef FSPT_H
 #define FSPT_H
@@ -117,6 +108,8 @@ int fspt_camera(fspt_target *target, const float P[3], const float I[3], float f
 /* Inject ray buffers instead (W*H*4 floats each, rows bottom-up; traced at once, from the buffers). */
 int fspt_set_rays(fspt_target *target, const float *pos, const float *dir);
 int fspt_read_rays(fspt_target *target, float *pos, float *dir);
+/* fspt_set_rays from memory of the scene's device: copied on the target's stream, no host sync; pos / dir must be complete, and stay allocated and unmodified until the target is next synchronised. */
+int fspt_set_rays_device(fspt_target *target, const float *pos, const float *dir);
 
 /* drawTracer(i) (main.js:758-807) -> tracer.fs:436-518.  One sample for every
  * pixel from the current ray buffers, running-mean accumulate with weight
@@ -148,6 +141,13 @@ float fspt_rand_base_next(uint64_t *state);
 int fspt_target_set_viewport(fspt_target *target, uint32_t w, uint32_t h);
 enum { FSPT_SAMPLER_REFERENCE = 0, FSPT_SAMPLER_SOBOL = 1 }; /* the paths' random numbers: rnd() bit for bit (default) | Owen-scrambled Sobol (DESIGN 8.2) */
 int fspt_target_set_sampler(fspt_target *target, int sampler, uint32_t seed); int fspt_target_get_sampler(fspt_target *target, int *sampler, uint32_t *seed);
+/* Camera models (DESIGN.md 8.15, INTEGRATION.md).  PINHOLE (default): camera.fs, fused into the path kernels.  ORTHO: parallel rays along I.  FISHEYE: equidistant,
+ * angle = field of view over the frame height in radians, in (0, 2 pi].  EQUIRECT: 360 x 180 degrees.  STEREO: over-under omnidirectional stereo, ipd in scene units >= 0,
+ * even height.  A flush point, does not clear; NULL = pinhole; FSPT_E_INVALID changes nothing.  Ticks are not batched under a model; adaptive / temporal: FSPT_E_STATE. */
+enum { FSPT_CAMERA_PINHOLE = 0, FSPT_CAMERA_ORTHO = 1, FSPT_CAMERA_FISHEYE = 2, FSPT_CAMERA_EQUIRECT = 3, FSPT_CAMERA_STEREO = 4 };
+typedef struct fspt_camera_model_params { int model; float angle; float ipd; } fspt_camera_model_params;
+int fspt_target_set_camera_model(fspt_target *target, const fspt_camera_model_params *params);
+int fspt_target_get_camera_model(fspt_target *target, fspt_camera_model_params *params);
 enum { FSPT_LIGHTS_OFF = 0, FSPT_LIGHTS_EMITTERS = 1 }; /* NEE of emissive triangles: off (default, the reference bit for bit) | emitters (fspt_tuning.h) */ int fspt_target_set_lights(fspt_target *target, int mode, float emitter_fraction); int fspt_target_get_lights(fspt_target *target, int *mode, float *emitter_fraction); int fspt_scene_light_count(fspt_scene *scene, uint32_t *n_lights);
 /* Several GPUs (one frame cut into 32x32 tiles over the devices of a node; the reference has nothing here - README.md:28
  * lists "Tiled rendering" as a TODO): include/fspt_multi.h, included at the end of this file. */

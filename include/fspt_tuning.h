@@ -73,6 +73,11 @@ int fspt_scene_last_rebuild_ms(fspt_scene *scene, float *build_ms, float *instal
 int fspt_scene_read_pose(fspt_scene *s, float *tri, float *norm);
 int fspt_scene_last_pose_ms(fspt_scene *s, float *transform_ms, float *refit_ms, uint32_t *launches);
 int fspt_pose_matrices_eval(const float *xf, uint32_t n_parts, float *out, uint32_t *bad_part);
+/* Camera models, measurement hook: k_camera_model of the target's model (FSPT_E_STATE under pinhole) `reps` times
+ * into the ray buffers on the target's stream between two HIP events; *ms_per_launch = their distance / reps.  Blocking; a flush
+ * point; the ray buffers are overwritten (a recorded fspt_camera call's rays are made again on demand; injected rays are gone:
+ * fspt_set_rays again before the next fspt_trace). */
+int fspt_camera_model_time(fspt_target *target, const fspt_camera_params *cam, uint32_t reps, float *ms_per_launch);
 /* Appearance update, test and measurement hooks.
  * what: 0 texture-set table, 1 single-layer tiled images, 2 interleaved images, 3 environment tiles, 4 bins, 5 hit records.
  * Copies min(cap, size) bytes and writes the size to *bytes (out NULL: only that).  Blocking. */

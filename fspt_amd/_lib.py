@@ -64,6 +64,13 @@ class CameraModelParams(C.Structure):
     _fields_ = [("model", C.c_int), ("angle", C.c_float), ("ipd", C.c_float)]
 
 
+class SkinDesc(C.Structure):
+    """fspt_skin_desc: host pointers"""
+    _fields_ = [("joints", C.POINTER(C.c_uint16)), ("weights", C.POINTER(C.c_float)), ("n_joints", C.c_uint32),
+                ("tri", C.POINTER(C.c_float)), ("norm", C.POINTER(C.c_float)), ("morph", C.POINTER(C.c_float)),
+                ("morph_norm", C.POINTER(C.c_float)), ("n_morph", C.c_uint32)]
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("target_rel_mse", C.c_double), ("max_ticks", C.c_uint32), ("min_ticks", C.c_uint32), ("round_ticks", C.c_uint32)]
 
@@ -124,6 +131,15 @@ SIGNATURES = {
     "fspt_scene_read_pose": (C.c_int, [_VP, _F, _F]),
     "fspt_scene_last_pose_ms": (C.c_int, [_VP, _F, _F, _U32]),
     "fspt_pose_matrices_eval": (C.c_int, [_F, C.c_uint32, _F, _U32]),
+    "fspt_scene_set_skin": (C.c_int, [_VP, C.POINTER(SkinDesc)]),
+    "fspt_scene_update_skin": (C.c_int, [_VP, _F, C.c_uint32, _F, C.c_uint32]),
+    "fspt_scene_update_skin_device": (C.c_int, [_VP, _VP, C.c_uint32, _VP, C.c_uint32]),
+    "fspt_multi_set_skin": (C.c_int, [_VP, C.POINTER(SkinDesc)]),
+    "fspt_multi_update_skin": (C.c_int, [_VP, _F, C.c_uint32, _F, C.c_uint32]),
+    "fspt_scene_read_skin": (C.c_int, [_VP, _F, _F]),
+    "fspt_scene_last_skin_ms": (C.c_int, [_VP, _F, _F, _U32, C.POINTER(C.c_uint64)]),
+    "fspt_skin_check_eval": (C.c_int, [C.POINTER(SkinDesc), C.c_uint32, C.POINTER(C.c_uint64)]),
+    "fspt_skin_set_form": (C.c_int, [C.c_int]),
     "fspt_scene_rebuild_geometry": (C.c_int, [_VP, _F, _F, _U32]),
     "fspt_scene_rebuild_geometry_device": (C.c_int, [_VP, _VP, _VP, _VP]),
     "fspt_scene_last_rebuild_ms": (C.c_int, [_VP, _F, _F, _F, _U32, _U32]),

@@ -733,6 +733,7 @@ int fspt_scene_destroy(fspt_scene *s) {
   fspt::refit_release(s);
   fspt::appearance_release(s);
   fspt::pose_release(s);
+  fspt::skin_release(s);
   delete s;
   return FSPT_OK;
 }
@@ -1630,6 +1631,7 @@ static int update_geometry(fspt_scene *s, const float *tri, const float *norm, b
   if (!on_device) {
     if (!s->rf.stage) HIP_TRY(hipMalloc((void **)&s->rf.stage, T * 36 * 4));
     s->pose.posed = false; // (the staging array no longer holds a pose's output)
+    s->skin.skinned = false;
     HIP_TRY(hipMemcpy(s->rf.stage, tri, T * 9 * 4, hipMemcpyHostToDevice));
     if (norm) HIP_TRY(hipMemcpy(s->rf.stage + T * 9, norm, T * 27 * 4, hipMemcpyHostToDevice));
     tri = s->rf.stage;
@@ -1781,6 +1783,155 @@ int fspt_scene_last_pose_ms(fspt_scene *s, float *transform_ms, float *refit_ms,
   if (transform_ms) *transform_ms = s->pose.last_ms;
   if (refit_ms) *refit_ms = s->rf.last_ms;
   if (launches) *launches = s->rf.last_launches + 1u;
+  return FSPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// GPU skinning (kernel in fspt_pose.hip)
+// ---------------------------------------------------------------------------
+// fspt_scene_set_skin's validation: host only.  FSPT_OK, or FSPT_E_INVALID with the error set and *bad = the index.
+static int skin_check(const fspt_skin_desc *d, size_t T, const char *fn, uint64_t *bad) {
+  if (!d || !d->joints || !d->weights || !d->tri) { fspt_set_error("%s: joints, weights or tri is NULL", fn); return FSPT_E_INVALID; }
+  if (d->n_joints < 1 || d->n_joints > 65535) { fspt_set_error("%s: n_joints = %u, must lie in [1, 65535]", fn, d->n_joints); return FSPT_E_INVALID; }
+  if (d->n_morph > FSPT_SKIN_MAX_MORPH) { fspt_set_error("%s: n_morph = %u, at most %d", fn, d->n_morph, FSPT_SKIN_MAX_MORPH); return FSPT_E_INVALID; }
+  if (d->n_morph && !d->morph) { fspt_set_error("%s: n_morph = %u but morph is NULL", fn, d->n_morph); return FSPT_E_INVALID; }
+  if (d->morph_norm && !d->norm) { fspt_set_error("%s: morph_norm needs a rest norm", fn); return FSPT_E_INVALID; }
+  if (d->morph_norm && !d->n_morph) { fspt_set_error("%s: morph_norm given with n_morph = 0", fn); return FSPT_E_INVALID; }
+  const size_t slots = T * 12;
+  for (size_t i = 0; i < slots; ++i)
+    if (d->joints[i] >= d->n_joints) { *bad = i; fspt_set_error("%s: joints[%zu] = %u, n_joints = %u", fn, i, (unsigned)d->joints[i], d->n_joints); return FSPT_E_INVALID; }
+  const struct { const char *name; const float *p; size_t n; } arrays[] = {
+      {"weights", d->weights, slots}, {"tri", d->tri, T * 9}, {"norm", d->norm, T * 27},
+      {"morph", d->n_morph ? d->morph : nullptr, (size_t)d->n_morph * T * 9}, {"morph_norm", d->morph_norm, (size_t)d->n_morph * T * 27}};
+  for (const auto &a : arrays)
+    for (size_t i = 0; a.p && i < a.n; ++i)
+      if (!std::isfinite(a.p[i])) { *bad = i; fspt_set_error("%s: %s[%zu] is not finite", fn, a.name, i); return FSPT_E_INVALID; }
+  return FSPT_OK;
+}
+
+int fspt_skin_check_eval(const fspt_skin_desc *d, uint32_t n_tris, uint64_t *bad_index) {
+  uint64_t bad = 0;
+  const int rc = skin_check(d, n_tris, "fspt_skin_check_eval", &bad);
+  if (rc && bad_index) *bad_index = bad;
+  return rc;
+}
+
+int fspt_skin_set_form(int form) {
+  if (form != 0 && form != 1) { fspt_set_error("fspt_skin_set_form: form must be 0 or 1"); return FSPT_E_INVALID; }
+  fspt::g_skin_form = form;
+  return FSPT_OK;
+}
+
+static uint64_t skin_bytes(const fspt_scene *s) {
+  const fspt_scene::Skin &K = s->skin;
+  if (!K.joints) return 0;
+  const uint64_t T = s->n_tris;
+  return T * (24 + 48 + 36 + (K.has_norm ? 108 : 0)) + (uint64_t)K.n_morph * T * (36 + (K.morph_norm ? 108 : 0)) + (uint64_t)K.n_joints * 48 + (uint64_t)K.n_morph * 4;
+}
+
+int fspt_scene_set_skin(fspt_scene *s, const fspt_skin_desc *d) {
+  if (!s) { fspt_set_error("fspt_scene_set_skin: NULL scene"); return FSPT_E_INVALID; }
+  if (!d) { // drop the skin
+    if (!s->skin.joints) return FSPT_OK;
+    int rc = check_device(s->device);
+    if (rc) return rc;
+    fspt::skin_release(s);
+    return FSPT_OK;
+  }
+  const size_t T = s->n_tris;
+  uint64_t bad = 0;
+  int rc = skin_check(d, T, "fspt_scene_set_skin", &bad);
+  if (rc) return rc;
+  if (!s->rf.ok) {
+    fspt_set_error("fspt_scene_set_skin: scene is not refittable (the leaves' triStarts must be distinct and tile [0, n_tris), every node have one parent)");
+    return FSPT_E_STATE;
+  }
+  rc = check_device(s->device);
+  if (rc) return rc;
+  // the new arrays first: an allocation that fails leaves the old skin
+  fspt_scene::Skin N;
+  const size_t T1 = T ? T : 1, M = d->n_morph;
+  const struct { void **dst; const void *src; size_t bytes, alloc; } parts[] = {
+      {(void **)&N.joints, d->joints, T * 24, T1 * 24}, {(void **)&N.weights, d->weights, T * 48, T1 * 48},
+      {(void **)&N.rest, d->tri, T * 36, T1 * (d->norm ? 144 : 36)},
+      {(void **)&N.morph, M ? d->morph : nullptr, M * T * 36, M * T1 * 36}, {(void **)&N.morph_norm, d->morph_norm, M * T * 108, M * T1 * 108},
+      {(void **)&N.frame, nullptr, 0, (size_t)d->n_joints * 48 + M * 4}};
+  hipError_t e = hipSuccess;
+  for (const auto &p : parts) {
+    if (e != hipSuccess || (!p.src && p.dst != (void **)&N.frame)) continue;
+    e = hipMalloc(p.dst, p.alloc);
+    if (e == hipSuccess && p.bytes) e = hipMemcpy(*p.dst, p.src, p.bytes, hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess && d->norm) e = hipMemcpy(N.rest + T * 9, d->norm, T * 108, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    for (const auto &p : parts) hipFree(*p.dst);
+    (void)hipGetLastError();
+    fspt_set_error("fspt_scene_set_skin: %s (%zu triangles, %u joints, %u morph targets)", hipGetErrorString(e), T, d->n_joints, d->n_morph);
+    return e == hipErrorOutOfMemory ? FSPT_E_NOMEM : FSPT_E_HIP;
+  }
+  N.has_norm = d->norm != nullptr;
+  N.n_joints = d->n_joints;
+  N.n_morph = d->n_morph;
+  fspt::skin_release(s);
+  s->skin = N;
+  return FSPT_OK;
+}
+
+static int update_skin(fspt_scene *s, const float *xf, uint32_t n_joints, const float *morph_w, uint32_t n_morph, bool on_device, const char *fn) {
+  if (!s || !xf) { fspt_set_error("%s: NULL scene or xf", fn); return FSPT_E_INVALID; }
+  const fspt_scene::Skin &K = s->skin;
+  if (!K.joints) { fspt_set_error("%s: the scene has no skin (fspt_scene_set_skin)", fn); return FSPT_E_STATE; }
+  if (n_joints != K.n_joints) { fspt_set_error("%s: %u matrices, the skin has %u joints", fn, n_joints, K.n_joints); return FSPT_E_INVALID; }
+  if (n_morph != K.n_morph) { fspt_set_error("%s: %u morph weights, the skin has %u targets", fn, n_morph, K.n_morph); return FSPT_E_INVALID; }
+  if (n_morph && !morph_w) { fspt_set_error("%s: morph_w is NULL, the skin has %u targets", fn, n_morph); return FSPT_E_INVALID; }
+  if (on_device) {
+    if ((uintptr_t)xf % 16) { fspt_set_error("%s: xf must be 16-byte aligned", fn); return FSPT_E_INVALID; }
+  } else { // the host form's check needs no device: refuse before anything is touched
+    for (uint32_t j = 0; j < n_joints; ++j)
+      for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(xf[(size_t)j * 12 + i])) { fspt_set_error("%s: joint %u: an entry is not finite (scene unchanged)", fn, j); return FSPT_E_INVALID; }
+    for (uint32_t m = 0; m < n_morph; ++m)
+      if (!std::isfinite(morph_w[m])) { fspt_set_error("%s: morph target %u: its weight is not finite (scene unchanged)", fn, m); return FSPT_E_INVALID; }
+  }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  rc = geometry_order_targets(s);
+  if (rc) return rc;
+  rc = fspt::refit_prepare(s);
+  if (rc) return rc;
+  const size_t T = s->n_tris;
+  if (!s->rf.stage) HIP_TRY(hipMalloc((void **)&s->rf.stage, T * 36 * 4));
+  rc = fspt::skin_run(s, xf, morph_w, on_device);
+  if (rc) return rc;
+  return refit_device_arrays(s, s->rf.stage, K.has_norm ? s->rf.stage + T * 9 : nullptr, fn);
+}
+
+int fspt_scene_update_skin(fspt_scene *s, const float *xf, uint32_t n_joints, const float *morph_w, uint32_t n_morph) {
+  return update_skin(s, xf, n_joints, morph_w, n_morph, false, "fspt_scene_update_skin");
+}
+
+int fspt_scene_update_skin_device(fspt_scene *s, const float *xf, uint32_t n_joints, const float *morph_w, uint32_t n_morph) {
+  return update_skin(s, xf, n_joints, morph_w, n_morph, true, "fspt_scene_update_skin_device");
+}
+
+int fspt_scene_read_skin(fspt_scene *s, float *tri, float *norm) {
+  if (!s || (!tri && !norm)) { fspt_set_error("fspt_scene_read_skin: NULL argument"); return FSPT_E_INVALID; }
+  if (!s->skin.joints || !s->skin.skinned) { fspt_set_error("fspt_scene_read_skin: no fspt_scene_update_skin since the skin was set, the scene rebuilt, posed or its geometry uploaded"); return FSPT_E_STATE; }
+  if (norm && !s->skin.has_norm) { fspt_set_error("fspt_scene_read_skin: the skin has no rest norm"); return FSPT_E_STATE; }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  const size_t T = s->n_tris;
+  if (tri) HIP_TRY(hipMemcpy(tri, s->rf.stage, T * 9 * 4, hipMemcpyDeviceToHost));
+  if (norm) HIP_TRY(hipMemcpy(norm, s->rf.stage + T * 9, T * 27 * 4, hipMemcpyDeviceToHost));
+  return FSPT_OK;
+}
+
+int fspt_scene_last_skin_ms(fspt_scene *s, float *skin_ms, float *refit_ms, uint32_t *launches, uint64_t *bytes) {
+  if (!s) { fspt_set_error("fspt_scene_last_skin_ms: NULL scene"); return FSPT_E_INVALID; }
+  if (skin_ms) *skin_ms = s->skin.last_ms;
+  if (refit_ms) *refit_ms = s->rf.last_ms;
+  if (launches) *launches = s->rf.last_launches + 1u;
+  if (bytes) *bytes = skin_bytes(s);
   return FSPT_OK;
 }
 

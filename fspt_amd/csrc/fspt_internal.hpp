@@ -9,7 +9,7 @@
 // and the device side, declared in fspt_device.hpp:
 //   fspt_kernels.hip       every kernel that reads a DScene: the path tracer, the test passes, k_features, k_temporal_gbuffer
 //   fspt_post.hip          every kernel that reads only images: what fspt_post.cpp launches, but for those two
-//   fspt_bvh_build.hip     the GPU BVH builder;  fspt_refit.hip  in-place refit and rebuild;  fspt_pose.hip  part transforms
+//   fspt_bvh_build.hip     the GPU BVH builder;  fspt_refit.hip  in-place refit and rebuild;  fspt_pose.hip  part transforms and skinning
 //   fspt_camera.hip        ray generation under an opt-in camera model (the rule: fspt_camera_model.hpp)
 //   fspt_appearance.hip    in-place appearance update: the texture-set, atlas and environment layouts and the material part of the hit records
 #pragma once
@@ -118,6 +118,22 @@ struct fspt_scene {
     hipEvent_t ev[2] = {nullptr, nullptr};
     float last_ms = 0.0f;           // k_pose_transform of the last call
   } pose;
+  // fspt_scene_set_skin / fspt_scene_update_skin (fspt_pose.hip): per triangle corner (current leaf order) four
+  // joint ids and weights, the rest mesh and the morph targets, on the device; a rebuild permutes them with the triangles.
+  // A scene that never sets a skin allocates nothing for it; the skinned arrays go to rf.stage.
+  struct Skin {
+    uint16_t *joints = nullptr;     // n_tris x 3 x 4 ids < n_joints (NULL: no skin)
+    float *weights = nullptr;       // n_tris x 3 x 4
+    float *rest = nullptr;          // n_tris x 9 rest vertices | n_tris x 27 rest normTex records when has_norm
+    float *morph = nullptr;         // n_morph x n_tris x 9 deltas (NULL: n_morph == 0)
+    float *morph_norm = nullptr;    // n_morph x n_tris x 27 deltas, or NULL
+    float *frame = nullptr;         // the host form's upload: n_joints x 12 floats | n_morph weights
+    bool has_norm = false;
+    uint32_t n_joints = 0, n_morph = 0;
+    bool skinned = false;           // rf.stage holds the last update_skin's output (fspt_scene_read_skin)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    float last_ms = 0.0f;           // k_skin_transform of the last call
+  } skin;
 };
 // Material texture sets: what fspt_scene_create and fspt_scene_update_materials derive from matTex's layer ids and
 // the per-layer "every texel equal" flags - the sets in first-appearance order, each triangle's set, a set's form under the
@@ -168,6 +184,17 @@ void appearance_release(fspt_scene *s);
 // mats_host = n_parts x 30 floats (a | D | N).  Uploads them, runs k_pose_transform into s->rf.stage and waits.
 int pose_run(fspt_scene *s, const float *mats_host);
 void pose_release(fspt_scene *s);
+// fspt_pose.hip.  skin_run: s->skin set, s->rf.stage allocated, the call ordered against the targets; xf =
+// n_joints x 12 floats (16-byte aligned when on the device), morph_w = n_morph floats, host memory (uploaded to
+// skin.frame) or the scene's device memory.  Runs k_skin_transform into s->rf.stage and waits.
+int skin_run(fspt_scene *s, const float *xf, const float *morph_w, bool on_device);
+void skin_release(fspt_scene *s);
+// the joint table's form: 0 = read from global memory, 1 = staged once per block in LDS when it fits SKIN_LDS_MAX_BYTES
+extern int g_skin_form;
+#ifndef SKIN_FORM
+#define SKIN_FORM 0
+#endif
+static const size_t SKIN_LDS_MAX_BYTES = 64u << 10; // 1 365 joints
 }
 int light_table_ensure(fspt_scene *s); // (fspt_api.cpp) builds the table once; FSPT_OK when it exists
 #ifndef FSPT_LIGHTS_ENV_Q_MAX

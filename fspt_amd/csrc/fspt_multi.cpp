@@ -233,6 +233,22 @@ int fspt_multi_update_transforms(fspt_multi *m, const float *xf, uint32_t n_part
   }
   return FSPT_OK;
 }
+int fspt_multi_set_skin(fspt_multi *m, const fspt_skin_desc *d) {
+  if (!m) { fspt_set_error("fspt_multi_set_skin: NULL handle"); return FSPT_E_INVALID; }
+  for (fspt_scene *s : m->scenes) { // (bad arguments are refused by the first scene, before anything is written)
+    const int rc = fspt_scene_set_skin(s, d);
+    if (rc) return rc;
+  }
+  return FSPT_OK;
+}
+int fspt_multi_update_skin(fspt_multi *m, const float *xf, uint32_t n_joints, const float *morph_w, uint32_t n_morph) {
+  if (!m) { fspt_set_error("fspt_multi_update_skin: NULL handle"); return FSPT_E_INVALID; }
+  for (fspt_scene *s : m->scenes) { // (a bad frame is refused by the first scene, before anything is written)
+    const int rc = fspt_scene_update_skin(s, xf, n_joints, morph_w, n_morph);
+    if (rc) return rc;
+  }
+  return FSPT_OK;
+}
 int fspt_multi_update_materials(fspt_multi *m, const float *mat, const float *uv, const uint8_t *atlas, uint32_t atlas_res, uint32_t atlas_layers) {
   if (!m) { fspt_set_error("fspt_multi_update_materials: NULL handle"); return FSPT_E_INVALID; }
   for (fspt_scene *s : m->scenes) { // (bad arguments are refused by the first scene, before anything is written)

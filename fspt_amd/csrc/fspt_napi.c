@@ -341,6 +341,46 @@ static napi_value SceneUpdateTransforms(napi_env env, napi_callback_info info) {
   FSPT_OK_OR_THROW(fspt_scene_update_transforms((fspt_scene *)h, (const float *)xf, (uint32_t)(nx / 12)));
   return undefined(env);
 }
+/* sceneSetSkin(scene, nTris, joints Uint16Array | null, weights Float32Array, nJoints, tri Float32Array, norm Float32Array | null,
+ * morph Float32Array | null, morphNorm Float32Array | null): fspt_scene_set_skin.  joints null drops the skin; else
+ * per triangle 12 ids and 12 weights (4 per corner), the rest mesh (9 / 27 floats) and nMorph = morph.length / (nTris * 9)
+ * targets of 9 / 27 floats per triangle.  The guard of sceneUpdateGeometry. */
+static napi_value SceneSetSkin(napi_env env, napi_callback_info info) {
+  napi_value a[9]; void *h, *joints = NULL, *weights = NULL, *tri = NULL, *norm = NULL, *morph = NULL, *mnorm = NULL;
+  size_t nj = 0, nw = 0, nt = 0, nn = 0, nm = 0, nmn = 0; uint32_t n = 0, n_joints = 0;
+  fspt_skin_desc d;
+  if (get_args(env, info, 9, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[1], &n));
+  if (typed(env, a[2], napi_uint16_array, 1, &joints, &nj)) return NULL;
+  if (!joints) { FSPT_OK_OR_THROW(fspt_scene_set_skin((fspt_scene *)h, NULL)); return undefined(env); }
+  if (typed(env, a[3], napi_float32_array, 0, &weights, &nw)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[4], &n_joints));
+  if (typed(env, a[5], napi_float32_array, 0, &tri, &nt) || typed(env, a[6], napi_float32_array, 1, &norm, &nn) ||
+      typed(env, a[7], napi_float32_array, 1, &morph, &nm) || typed(env, a[8], napi_float32_array, 1, &mnorm, &nmn)) return NULL;
+  if (nj != (size_t)n * 12 || nw != (size_t)n * 12 || nt != (size_t)n * 9 || (norm && nn != (size_t)n * 27)) {
+    napi_throw_range_error(env, NULL, "fspt_napi: setSkin needs 12 ids (joints), 12 floats (weights), 9 floats (tri) and 27 floats (norm) per triangle of the scene");
+    return NULL;
+  }
+  if ((morph && (n == 0 || nm == 0 || nm % ((size_t)n * 9))) || (mnorm && (!morph || nmn != nm * 3))) {
+    napi_throw_range_error(env, NULL, "fspt_napi: setSkin needs 9 floats (morph) and 27 floats (morphNorm) per triangle and morph target");
+    return NULL;
+  }
+  d.joints = (const uint16_t *)joints; d.weights = (const float *)weights; d.n_joints = n_joints;
+  d.tri = (const float *)tri; d.norm = (const float *)norm; d.morph = (const float *)morph; d.morph_norm = (const float *)mnorm;
+  d.n_morph = morph ? (uint32_t)(nm / ((size_t)n * 9)) : 0;
+  FSPT_OK_OR_THROW(fspt_scene_set_skin((fspt_scene *)h, &d));
+  return undefined(env);
+}
+/* sceneUpdateSkin(scene, xf Float32Array, morphWeights Float32Array | null): fspt_scene_update_skin with xf.length / 12 joints
+ * and morphWeights.length targets. */
+static napi_value SceneUpdateSkin(napi_env env, napi_callback_info info) {
+  napi_value a[3]; void *h, *xf = NULL, *mw = NULL; size_t nx = 0, nm = 0;
+  if (get_args(env, info, 3, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  if (typed(env, a[1], napi_float32_array, 0, &xf, &nx) || typed(env, a[2], napi_float32_array, 1, &mw, &nm)) return NULL;
+  if (nx == 0 || nx % 12) { napi_throw_range_error(env, NULL, "fspt_napi: updateSkin needs 12 floats per joint"); return NULL; }
+  FSPT_OK_OR_THROW(fspt_scene_update_skin((fspt_scene *)h, (const float *)xf, (uint32_t)(nx / 12), nm ? (const float *)mw : NULL, (uint32_t)nm));
+  return undefined(env);
+}
 /* sceneUpdateMaterials(scene, nTris, mat Float32Array, uv Float32Array | null, atlas Uint8Array | null, atlasRes, atlasLayers):
  * fspt_scene_update_materials.  12 / 6 floats per triangle of the scene; an atlas holds atlasRes^2 * atlasLayers
  * RGBA8 texels (null: the atlas of the scene's last call that carried one).  The guard of sceneUpdateGeometry. */
@@ -1440,7 +1480,7 @@ static napi_value AbiVersion(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
-      {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"sceneSetPose", SceneSetPose}, {"sceneUpdateTransforms", SceneUpdateTransforms}, {"targetCreate", TargetCreate},
+      {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"sceneSetPose", SceneSetPose}, {"sceneUpdateTransforms", SceneUpdateTransforms}, {"sceneSetSkin", SceneSetSkin}, {"sceneUpdateSkin", SceneUpdateSkin}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
       {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setCameraModel", SetCameraModel}, {"cameraModel", CameraModel}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},

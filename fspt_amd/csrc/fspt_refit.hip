@@ -7,7 +7,7 @@
 //   k_refit_quads       the two-level nodes from the refitted 64-byte nodes + fspt_scene_create's usability test
 // and what installs a NEW tree over the same triangles (fspt_scene_rebuild_geometry; rebuild_run below):
 //   k_rebuild_slot_map  triangle -> the old leaf slot of the leaf that owns it (one writer per triangle)
-//   k_rebuild_permute   the caller's tri / norm in the new leaf order (what refit_run is then fed); the pose of DESIGN 8.14
+//   k_rebuild_permute   the caller's tri / norm in the new leaf order (what refit_run is then fed); the pose of DESIGN 8.14, the skin of 8.16
 //   k_rebuild_gather    per NEW leaf slot: the 192-byte hit record of its triangle's old slot (12 lanes x 16 bytes), slot_tri,
 //                       and the "-1" padding of the leaf records
 //   k_rebuild_nodes     the interior nodes' child references
@@ -316,6 +316,7 @@ struct RebuildGuard {
   int32_t *d_cref = nullptr;
   uint32_t *p_part = nullptr; // the pose in the new leaf order
   float *p_rest = nullptr;
+  void *k_new[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // the skin in the new leaf order: joints, weights, rest, morph, morph_norm
   hipEvent_t ev[2] = {nullptr, nullptr};
   bool keep = false;
   ~RebuildGuard() {
@@ -325,6 +326,7 @@ struct RebuildGuard {
     if (keep) return;
     hipFree(ns.nodes); hipFree(ns.quads); hipFree(ns.tris); hipFree(ns.slot_tri); hipFree(ns.shade); hipFree(ns.motion);
     hipFree(p_part); hipFree(p_rest);
+    for (void *p : k_new) hipFree(p);
     refit_release(&ns);
   }
 };
@@ -401,6 +403,12 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
     REBUILD_ALLOC(&G.p_part, (size_t)T * 4);
     REBUILD_ALLOC(&G.p_rest, (size_t)T * (P.has_norm ? 36 : 9) * 4);
   }
+  // the skin's arrays as (array, words per triangle, slices of T triangles): a morph array is one slice per target
+  const fspt_scene::Skin &K = s->skin;
+  const struct { const void *src; uint32_t words; size_t slices; } k_old[5] = {
+      {K.joints, 6u, 1}, {K.weights, 12u, 1}, {K.rest, K.has_norm ? 36u : 9u, 1}, {K.morph, 9u, K.n_morph}, {K.morph_norm, 27u, K.n_morph}};
+  for (int a = 0; K.joints && a < 5; ++a)
+    if (k_old[a].src) REBUILD_ALLOC(&G.k_new[a], (size_t)T * k_old[a].words * 4 * k_old[a].slices);
   rc = refit_prepare(&ns);
   if (rc) return rc;
   HIP_TRY(hipEventCreate(&G.ev[0]));
@@ -426,6 +434,20 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
       hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 27, BS)), dim3(BS), 0, st, P.rest + (size_t)T * 9, G.bt.order, T, 27u, G.p_rest + (size_t)T * 9);
       ++launches;
     }
+  }
+  for (int a = 0; K.joints && a < 5; ++a) { // the skin follows its triangles (ids as words); rest = 9 T vertices | 27 T records
+    if (!k_old[a].src) continue;
+    const float *src = (const float *)k_old[a].src;
+    float *dst = (float *)G.k_new[a];
+    if (a == 2) {
+      hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 9, BS)), dim3(BS), 0, st, src, G.bt.order, T, 9u, dst);
+      ++launches;
+      if (K.has_norm) { hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 27, BS)), dim3(BS), 0, st, src + (size_t)T * 9, G.bt.order, T, 27u, dst + (size_t)T * 9); ++launches; }
+      continue;
+    }
+    const uint32_t W = k_old[a].words;
+    for (size_t m = 0; m < k_old[a].slices; ++m, ++launches)
+      hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * W, BS)), dim3(BS), 0, st, src + m * T * W, G.bt.order, T, W, dst + m * T * W);
   }
   hipLaunchKernelGGL(k_rebuild_gather, dim3(blocks_for(n_slots * 12, BS)), dim3(BS), 0, st, (const float4 *)s->shade, old_slots, G.d_map, G.bt.order,
                      ns.rf.d_leaf, nl, LS, T, (float4 *)ns.shade, (uint32_t *)ns.slot_tri, (float *)ns.tris);
@@ -454,6 +476,13 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
     hipFree(s->pose.part); hipFree(s->pose.rest);
     s->pose.part = G.p_part; s->pose.rest = G.p_rest;
     s->pose.posed = false;
+  }
+  if (s->skin.joints) {
+    fspt_scene::Skin &Ks = s->skin;
+    hipFree(Ks.joints); hipFree(Ks.weights); hipFree(Ks.rest); hipFree(Ks.morph); hipFree(Ks.morph_norm);
+    Ks.joints = (uint16_t *)G.k_new[0]; Ks.weights = (float *)G.k_new[1]; Ks.rest = (float *)G.k_new[2];
+    Ks.morph = (float *)G.k_new[3]; Ks.morph_norm = (float *)G.k_new[4];
+    Ks.skinned = false;
   }
   s->rf = std::move(ns.rf);
   s->motion = ns.motion;

@@ -578,6 +578,47 @@ class PathTracer {
     if (!(xf instanceof Float32Array) || xf.length === 0 || xf.length % 12 !== 0) throw new RangeError('updateTransforms: xf must be a Float32Array of n_parts x 12 floats');
     addon.sceneUpdateTransforms(this._scene, xf);
   }
+  /** Hand the scene a skin (fspt_scene_set_skin, DESIGN 8.16): { joints: Uint16Array, weights: Float32Array } hold 4 ids and
+   *  4 weights per triangle corner (12 per triangle, current leaf order; weights are used as given), tri / norm the rest mesh
+   *  in that order (norm null: updateSkin leaves the normals alone), morph / morphNorm the morph targets as deltas, target
+   *  after target (9 / 27 floats per triangle each; morphNorm needs norm), nJoints the joint count (default max(joints) + 1).
+   *  setSkin(null) drops the skin.  Nothing renders differently until updateSkin. */
+  setSkin(skin) {
+    if (skin == null) { addon.sceneSetSkin(this._scene, this._nTris, null, null, 0, null, null, null, null); return; }
+    const { joints, weights, tri, norm, morph, morphNorm, nJoints } = skin;
+    const n = this._nTris;
+    if (!(joints instanceof Uint16Array) || joints.length !== n * 12) throw new RangeError('setSkin: joints must be a Uint16Array of ' + n + ' x 12 ids');
+    if (!(weights instanceof Float32Array) || weights.length !== n * 12) throw new RangeError('setSkin: weights must be a Float32Array of ' + n + ' x 12 floats');
+    if (!(tri instanceof Float32Array) || tri.length !== n * 9) throw new RangeError('setSkin: tri must be a Float32Array of ' + n + ' x 9 floats');
+    if (norm != null && (!(norm instanceof Float32Array) || norm.length !== n * 27)) throw new RangeError('setSkin: norm must be a Float32Array of ' + n + ' x 27 floats');
+    let nMorph = 0;
+    if (morph != null) {
+      if (!(morph instanceof Float32Array) || n === 0 || morph.length === 0 || morph.length % (n * 9) !== 0) throw new RangeError('setSkin: morph must be a Float32Array of nMorph x ' + n + ' x 9 floats');
+      nMorph = morph.length / (n * 9);
+      if (nMorph > 64) throw new RangeError('setSkin: at most 64 morph targets, got ' + nMorph);
+    }
+    if (morphNorm != null) {
+      if (norm == null) throw new RangeError('setSkin: morphNorm needs norm');
+      if (!(morphNorm instanceof Float32Array) || nMorph === 0 || morphNorm.length !== nMorph * n * 27) throw new RangeError('setSkin: morphNorm must be a Float32Array of ' + nMorph + ' x ' + n + ' x 27 floats');
+    }
+    let nj = 0;
+    for (let i = 0; i < joints.length; i++) if (joints[i] >= nj) nj = joints[i] + 1;
+    nj = Math.max(nj, 1);
+    if (nJoints != null) {
+      if (!Number.isInteger(nJoints) || nJoints < nj || nJoints > 65535) throw new RangeError('setSkin: nJoints must be an integer in [max(joints) + 1, 65535]');
+      nj = nJoints;
+    }
+    if (nj > 65535) throw new RangeError('setSkin: joint ids must be < 65535');
+    addon.sceneSetSkin(this._scene, n, joints, weights, nj, tri, norm == null ? null : norm, morph == null ? null : morph, morphNorm == null ? null : morphNorm);
+  }
+  /** One frame of the skin: xf = one row-major 3 x 4 matrix per joint (Float32Array, 12 floats each), morphWeights = one float
+   *  per morph target (Float32Array; null when the skin has none).  A kernel morphs, blends and poses every corner and the
+   *  tree is refitted exactly as updateGeometry on the result would (fspt_scene_update_skin, DESIGN 8.16). */
+  updateSkin(xf, morphWeights) {
+    if (!(xf instanceof Float32Array) || xf.length === 0 || xf.length % 12 !== 0) throw new RangeError('updateSkin: xf must be a Float32Array of n_joints x 12 floats');
+    if (morphWeights != null && !(morphWeights instanceof Float32Array)) throw new RangeError('updateSkin: morphWeights must be a Float32Array of n_morph floats');
+    addon.sceneUpdateSkin(this._scene, xf, morphWeights == null || morphWeights.length === 0 ? null : morphWeights);
+  }
   /** The arguments of updateGeometry, but the scene gets a NEW tree - the binned SAH of the GPU builder over `tri` in the
    *  order given - built on the GPU and installed in place (fspt_scene_rebuild_geometry, DESIGN 8.7).  Returns a Uint32Array:
    *  order[k] = index in `tri` of the triangle now at leaf position k; later updateGeometry / rebuildGeometry calls take

@@ -274,6 +274,12 @@ def bloom_eval(rgba, viewport=None, device=0, **params):
     return ds, us, bloom, mix
 
 
+def skin_set_form(form):
+    """Where k_skin_transform reads the joint table from, process-wide (fspt_skin_set_form, a measurement switch): 0 = global
+    memory, 1 = staged once per block in LDS.  The bits are the same."""
+    L.check(L.lib().fspt_skin_set_form(int(form)))
+
+
 def bloom_set_form(form):
     """The pyramid's form, process-wide (fspt_bloom_set_form, a measurement switch): 0 = one launch per level, 1 = the small
     levels in one workgroup (k_bloom_tail).  The bits are the same."""
@@ -523,6 +529,130 @@ class Scene:
         a, b, n = C.c_float(), C.c_float(), C.c_uint32()
         L.check(L.lib().fspt_scene_last_pose_ms(self._h, C.byref(a), C.byref(b), C.byref(n)))
         return dict(transform_ms=float(a.value), refit_ms=float(b.value), launches=int(n.value))
+
+    @staticmethod
+    def _skin_desc(fn, n, joints, weights, tri, norm, morph, morph_norm, n_joints):
+        """(fspt_skin_desc, the arrays it points into) for n triangles; sizes and types checked here, values by the library"""
+        joints = _u32_array(joints, "joints")
+        if joints.size and joints.max() > 0xFFFF:
+            raise ValueError(f"{fn}: joint ids must lie in [0, 65535], got {int(joints.max())}")
+        joints = np.ascontiguousarray(joints, dtype=np.uint16).reshape(-1)
+        weights = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        if joints.size != n * 12 or weights.size != n * 12:
+            raise ValueError(f"{fn}: joints has {joints.size} and weights {weights.size} elements, the scene needs {n} x 3 x 4 of each")
+        tri = np.ascontiguousarray(tri, dtype=np.float32).reshape(-1)
+        if tri.size != n * 9:
+            raise ValueError(f"{fn}: tri has {tri.size} elements, the scene needs {n} x 9")
+        if norm is not None:
+            norm = np.ascontiguousarray(norm, dtype=np.float32).reshape(-1)
+            if norm.size != n * 27:
+                raise ValueError(f"{fn}: norm has {norm.size} elements, the scene needs {n} x 27")
+        n_morph = 0
+        if morph is not None:
+            morph = np.ascontiguousarray(morph, dtype=np.float32).reshape(-1)
+            if n == 0 or morph.size % (n * 9):
+                raise ValueError(f"{fn}: morph has {morph.size} elements, not n_morph x {n} x 9")
+            n_morph = morph.size // (n * 9)
+            if n_morph == 0:
+                morph = None
+        if morph_norm is not None:
+            morph_norm = np.ascontiguousarray(morph_norm, dtype=np.float32).reshape(-1)
+            if norm is None:
+                raise ValueError(f"{fn}: morph_norm needs a rest norm")
+            if n_morph == 0 or morph_norm.size != n_morph * n * 27:
+                raise ValueError(f"{fn}: morph_norm has {morph_norm.size} elements, {n_morph} morph targets need {n_morph} x {n} x 27")
+        if n_joints is None:
+            n_joints = int(joints.max()) + 1 if joints.size else 1
+        n_joints = int(n_joints)
+        if not 1 <= n_joints <= 65535:
+            raise ValueError(f"{fn}: n_joints must lie in [1, 65535], got {n_joints}")
+        f = lambda a: None if a is None else L.fptr(a)
+        d = L.SkinDesc(joints.ctypes.data_as(C.POINTER(C.c_uint16)), L.fptr(weights), n_joints, L.fptr(tri), f(norm), f(morph), f(morph_norm), n_morph)
+        return d, (joints, weights, tri, norm, morph, morph_norm)
+
+    @staticmethod
+    def _skin_frame(fn, xf, morph_weights, device):
+        """(on device, xf, n_joints, morph weights, n_morph, what to keep alive) for update_skin: contiguous float32 numpy
+        arrays, or data pointers of float32 torch tensors on `device` (None: device tensors are refused)"""
+        on_dev = [hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) for a in (xf, morph_weights) if a is not None]
+        if any(on_dev):
+            if device is None or not all(on_dev):
+                raise TypeError(f"{fn}: xf and morph_weights must both be device tensors or both host arrays")
+            import torch
+            for name, a in (("xf", xf), ("morph_weights", morph_weights)):
+                if a is None:
+                    continue
+                if a.dtype != torch.float32 or not a.is_contiguous():
+                    raise TypeError(f"{fn}: {name} must be a contiguous float32 tensor")
+                if a.device.index != device:
+                    raise ValueError(f"{fn}: {name} lives on {a.device}, the scene on device {device}")
+            if xf.numel() == 0 or xf.numel() % 12:
+                raise ValueError(f"{fn}: xf has {xf.numel()} elements, not n_joints x 12")
+            if xf.data_ptr() % 16:
+                raise ValueError(f"{fn}: xf must be 16-byte aligned")
+            torch.cuda.current_stream(device).synchronize()  # whatever wrote the tensors has finished
+            nm = 0 if morph_weights is None else morph_weights.numel()
+            return True, C.c_void_p(xf.data_ptr()), xf.numel() // 12, None if not nm else C.c_void_p(morph_weights.data_ptr()), nm, (xf, morph_weights)
+        xf = np.ascontiguousarray(xf, dtype=np.float32).reshape(-1)
+        if xf.size == 0 or xf.size % 12:
+            raise ValueError(f"{fn}: xf has {xf.size} elements, not n_joints x 12")
+        mw = None if morph_weights is None else np.ascontiguousarray(morph_weights, dtype=np.float32).reshape(-1)
+        nm = 0 if mw is None else mw.size
+        return False, L.fptr(xf), xf.size // 12, None if not nm else L.fptr(mw), nm, (xf, mw)
+
+    def set_skin(self, joints, weights=None, tri=None, norm=None, morph=None, morph_norm=None, n_joints=None):
+        """Hand the scene a skin (fspt_scene_set_skin).  Per triangle CORNER in the current LEAF order: joints
+        [n, 3, 4] ids (< n_joints <= 65535) and weights [n, 3, 4] float32, used as given (not normalised).  tri / norm = the
+        rest mesh in that order; the default is the scene's own arrays - tri AND norm of `self.arrays` - refused once
+        update_geometry / rebuild_geometry has given the scene other triangles or another order.  With tri given and norm
+        None the skin has no rest normals: update_skin then leaves the normal part of the hit records alone.  morph
+        [n_morph, n, 9] / morph_norm [n_morph, n, 27]: morph targets as deltas (at most 64; morph_norm needs norm).
+        n_joints: the number of joints when it is more than max(joints) + 1.  joints=None drops the skin and frees it.
+        Nothing renders differently until update_skin."""
+        if joints is None:
+            L.check(L.lib().fspt_scene_set_skin(self._h, None))
+            return
+        if weights is None:
+            raise ValueError("set_skin: joints given without weights")
+        if tri is None:
+            if norm is not None:
+                raise ValueError("set_skin: norm given without tri")
+            if getattr(self, "_moved", False):
+                raise ValueError("set_skin: the scene's geometry is no longer that of its arrays; pass tri (and norm) in the current leaf order")
+            tri, norm = self.arrays.tri, self.arrays.norm
+        d, keep = self._skin_desc("set_skin", int(self.arrays.n_tris), joints, weights, tri, norm, morph, morph_norm, n_joints)
+        L.check(L.lib().fspt_scene_set_skin(self._h, C.byref(d)))
+
+    def update_skin(self, xf, morph_weights=None):
+        """One frame of the skin: xf = one 3 x 4 matrix per joint (float32 [n_joints, 12] or [n_joints, 3, 4], row-major as
+        update_transforms takes them), morph_weights = one float32 per morph target (None when the skin has none).  A kernel
+        applies the morphs, blends each corner's four matrices by its weights, poses the vertex by the blend, tangent and
+        bitangent by its 3 x 3 part and the normal by its cofactor matrix (both scaled to the blend's rms), and the tree is
+        refitted exactly as update_geometry on those arrays would (fspt_scene_update_skin).  numpy arrays take
+        the host form (checked: a non-finite entry is refused naming the joint / target); float32 torch tensors on the
+        scene's device are read where they are (the `_device` form; xf 16-byte aligned; no host check - non-finite results
+        are refused by the refit's check).  Any error leaves the scene as it was."""
+        on_dev, pxf, nj, pmw, nm, keep = self._skin_frame("update_skin", xf, morph_weights, self.device)
+        fn = L.lib().fspt_scene_update_skin_device if on_dev else L.lib().fspt_scene_update_skin
+        L.check(fn(self._h, pxf, nj, pmw, nm))
+
+    def read_skin(self):
+        """(tri [n, 9], norm [n, 27] or None) as the most recent update_skin wrote them (fspt_scene_read_skin)."""
+        n = int(self.arrays.n_tris)
+        tri = np.zeros((n, 9), np.float32)
+        norm = np.zeros((n, 27), np.float32)
+        if L.lib().fspt_scene_read_skin(self._h, L.fptr(tri), L.fptr(norm)) == 0:
+            return tri, norm
+        L.check(L.lib().fspt_scene_read_skin(self._h, L.fptr(tri), None))  # (a skin without rest normals)
+        return tri, None
+
+    @property
+    def last_skin(self):
+        """The most recent update_skin as a dict: skin_ms (k_skin_transform), refit_ms, launches, and bytes - what the skin
+        holds on the device by the library's accounting (fspt_scene_last_skin_ms; 0 without a skin)."""
+        a, b, n, by = C.c_float(), C.c_float(), C.c_uint32(), C.c_uint64()
+        L.check(L.lib().fspt_scene_last_skin_ms(self._h, C.byref(a), C.byref(b), C.byref(n), C.byref(by)))
+        return dict(skin_ms=float(a.value), refit_ms=float(b.value), launches=int(n.value), bytes=int(by.value))
 
     def _materials_args(self, fn, mat, uv, atlas, atlas_res, atlas_layers):
         n = int(self.arrays.n_tris)
@@ -932,6 +1062,23 @@ class PathTracer:
         """Scene.update_transforms on this tracer's scene (every tracer of the scene sees it); call clear() to restart the mean."""
         self.scene.update_transforms(xf)
 
+    def set_skin(self, joints, weights=None, tri=None, norm=None, morph=None, morph_norm=None, n_joints=None):
+        """Scene.set_skin on this tracer's scene."""
+        self.scene.set_skin(joints, weights, tri, norm, morph, morph_norm, n_joints)
+
+    def update_skin(self, xf, morph_weights=None):
+        """Scene.update_skin on this tracer's scene (every tracer of the scene sees it); call clear() to restart the mean."""
+        self.scene.update_skin(xf, morph_weights)
+
+    def read_skin(self):
+        """Scene.read_skin of this tracer's scene."""
+        return self.scene.read_skin()
+
+    @property
+    def last_skin(self):
+        """Scene.last_skin of this tracer's scene."""
+        return self.scene.last_skin
+
     def update_materials(self, mat, uv=None, atlas=None, atlas_res=None, atlas_layers=None):
         """Scene.update_materials on this tracer's scene (every tracer of the scene sees it); the accumulator, the temporal
         history, the exposure and the bloom state stay - call clear() to restart the mean."""
@@ -1339,6 +1486,25 @@ class MultiPathTracer:
         if xf.size % 12:
             raise ValueError(f"update_transforms: xf has {xf.size} elements, not n_parts x 12")
         L.check(L.lib().fspt_multi_update_transforms(self._m, L.fptr(xf), xf.size // 12))
+
+    def set_skin(self, joints, weights=None, tri=None, norm=None, morph=None, morph_norm=None, n_joints=None):
+        """Scene.set_skin on every device's copy of the scene (fspt_multi_set_skin); tri is required once the scene has moved."""
+        if joints is None:
+            L.check(L.lib().fspt_multi_set_skin(self._m, None))
+            return
+        if weights is None:
+            raise ValueError("set_skin: joints given without weights")
+        if tri is None:
+            if norm is not None:
+                raise ValueError("set_skin: norm given without tri")
+            tri, norm = self.arrays.tri, self.arrays.norm
+        d, keep = Scene._skin_desc("set_skin", int(self.arrays.n_tris), joints, weights, tri, norm, morph, morph_norm, n_joints)
+        L.check(L.lib().fspt_multi_set_skin(self._m, C.byref(d)))
+
+    def update_skin(self, xf, morph_weights=None):
+        """Scene.update_skin (host arrays) on every device's copy of the scene (fspt_multi_update_skin)."""
+        _, pxf, nj, pmw, nm, keep = Scene._skin_frame("update_skin", xf, morph_weights, None)
+        L.check(L.lib().fspt_multi_update_skin(self._m, pxf, nj, pmw, nm))
 
     def update_materials(self, mat, uv=None, atlas=None, atlas_res=None, atlas_layers=None):
         """Scene.update_materials (host arrays) on every device's copy of the scene (fspt_multi_update_materials)."""

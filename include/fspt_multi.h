@@ -42,6 +42,9 @@ int fspt_multi_update_geometry(fspt_multi *m, const float *tri, const float *nor
 /* fspt_scene_set_pose / fspt_scene_update_transforms on every device's copy of the scene */
 int fspt_multi_set_pose(fspt_multi *m, const uint32_t *part, uint32_t n_parts, const float *tri, const float *norm);
 int fspt_multi_update_transforms(fspt_multi *m, const float *xf, uint32_t n_parts);
+/* fspt_scene_set_skin / fspt_scene_update_skin (the host form) on every device's copy of the scene */
+int fspt_multi_set_skin(fspt_multi *m, const fspt_skin_desc *d);
+int fspt_multi_update_skin(fspt_multi *m, const float *xf, uint32_t n_joints, const float *morph_w, uint32_t n_morph);
 /* fspt_scene_update_materials / _environment on every device's copy of the scene; arguments the first device refuses change nothing */
 int fspt_multi_update_materials(fspt_multi *m, const float *mat, const float *uv, const uint8_t *atlas, uint32_t atlas_res, uint32_t atlas_layers);
 int fspt_multi_update_environment(fspt_multi *m, const uint8_t *env, uint32_t env_w, uint32_t env_h, const uint32_t *bins, uint32_t n_bins);

@@ -73,6 +73,22 @@ int fspt_scene_last_rebuild_ms(fspt_scene *scene, float *build_ms, float *instal
 int fspt_scene_read_pose(fspt_scene *s, float *tri, float *norm);
 int fspt_scene_last_pose_ms(fspt_scene *s, float *transform_ms, float *refit_ms, uint32_t *launches);
 int fspt_pose_matrices_eval(const float *xf, uint32_t n_parts, float *out, uint32_t *bad_part);
+/* Skinning, test and measurement hooks.
+ * read_skin: the tri' (n_tris x 9) / norm' (n_tris x 27; either may be NULL) the most recent fspt_scene_update_skin[_device]
+ * wrote to the staging array the refit read (FSPT_E_STATE when another call has reused the array since).
+ * last_skin_ms: GPU ms of k_skin_transform, GPU ms of the refit behind it, kernels launched, and the bytes the skin holds on
+ * the device by the library's accounting: n_tris x (24 + 48 + 36 [+ 108 with norm]) + n_morph x n_tris x (36 [+ 108 with
+ * morph_norm]) + n_joints x 48 + n_morph x 4 (the host form's frame); 0 without a skin.  Any pointer may be NULL.
+ * skin_check_eval: fspt_scene_set_skin's validation alone, no device and no scene: FSPT_E_INVALID with the reason and the
+ * offending index in fspt_last_error and in *bad_index (the corner-slot index into joints / weights, the element index into
+ * tri / norm / morph / morph_norm; untouched for a refused count or pointer).
+ * skin_set_form: measurement switch, process-wide: where k_skin_transform reads the joint table from, 0 = global memory,
+ * 1 = staged once per block in LDS (tables of up to 64 KiB; larger ones are read from global memory).  The bits are the same. */
+#define FSPT_SKIN_MAX_MORPH 64
+int fspt_scene_read_skin(fspt_scene *s, float *tri, float *norm);
+int fspt_scene_last_skin_ms(fspt_scene *s, float *skin_ms, float *refit_ms, uint32_t *launches, uint64_t *bytes);
+int fspt_skin_check_eval(const fspt_skin_desc *d, uint32_t n_tris, uint64_t *bad_index);
+int fspt_skin_set_form(int form);
 /* Camera models, measurement hook: k_camera_model of the target's model (FSPT_E_STATE under pinhole) `reps` times
  * into the ray buffers on the target's stream between two HIP events; *ms_per_launch = their distance / reps.  Blocking; a flush
  * point; the ray buffers are overwritten (a recorded fspt_camera call's rays are made again on demand; injected rays are gone:

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Per-kernel register / scratch / occupancy table of the two kernel files, fspt_kernels.hip and fspt_post.hip, and of
-# fspt_pose.hip (k_pose_transform) and fspt_camera.hip (k_camera_model)
+# fspt_pose.hip (k_pose_transform; k_skin_transform) and fspt_camera.hip (k_camera_model)
 # (hipcc -Rpass-analysis=kernel-resource-usage), demangled, in one table.
 # usage: tools/kernel_resources.sh [extra -D flags]
 cd "$(dirname "$0")/.." || exit 1

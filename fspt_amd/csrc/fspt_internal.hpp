@@ -1,6 +1,7 @@
 // fspt_internal.hpp - what the translation units of libfspt's host side share: the scene and target objects behind the
 // opaque handles of include/fspt.h, the tuning defaults, and the helpers that cross file boundaries.
-//   fspt_api.cpp           scene and target objects, every entry point that is neither a scheduler nor the image chain (include/fspt.h order)
+//   fspt_api.cpp           scene and target objects, every entry point that is neither a scheduler, the image chain nor a live-scene update (include/fspt.h order)
+//   fspt_scene_update.cpp  what changes a live scene or reports on such a change: refit, rebuild, pose, skin, appearance, motion origin
 //   fspt_post.cpp          the image chain behind the accumulator: draw, denoiser, temporal stages, auto-exposure, bloom
 //   fspt_sched_batch.cpp   the batch scheduler of the wavefront pipeline (render_wavefront) and its path state
 //   fspt_sched_stream.cpp  the stream scheduler (render_stream): a fixed pool of live paths
@@ -459,12 +460,14 @@ int present_join(fspt_target *t);      // wait for everything fspt_present enque
 int materialise_rays(fspt_target *t);  // the ray buffers as the most recent fspt_camera call left them
 const char *camera_model_name(int model); // "pinhole", "ortho", ... (error messages)
 uint32_t clamp_bounces(uint32_t nb);
+// ---- fspt_scene_update.cpp: entry points and *_eval / set_form hooks only; what it needs of fspt_api.cpp (geometry_order_targets,
+// geometry_changed_lights) and of the .hip files is declared with the scene object above
 // ---- fspt_post.cpp
 // k_draw of `src` on `st` into `out` (device memory), through the target's auto-exposure and bloom when they are on
 hipError_t draw_launch(fspt_target *t, const float4 *src, float exposure, float saturation, int denoise, float max_sigma,
                        float scale, uint32_t *out, hipStream_t st);
 void post_release(fspt_target *t); // fspt_target_destroy: the image chain's buffers and events (the streams are idle)
-// ---- the *_eval test hooks (fspt_api.cpp, fspt_post.cpp)
+// ---- the *_eval test hooks (fspt_api.cpp, fspt_scene_update.cpp, fspt_post.cpp)
 // A hook's device memory: ONE allocation, freed when the scope ends.  The first HIP error sticks in `e`: up, down and sync
 // are no-ops behind it, and a hook launches with `if (s.ok()) s.e = launch(..)`.  `base` is NULL when the allocation
 // failed: a hook returns done() at once then, before it forms a pointer into the block.  sync() stands apart from done()

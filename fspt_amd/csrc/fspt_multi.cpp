@@ -209,61 +209,35 @@ int fspt_multi_trace(fspt_multi *m, uint32_t tick, float rand_base, float env_th
 int fspt_multi_render(fspt_multi *m, const fspt_camera_params *cam, uint32_t first_tick, uint32_t n_ticks, uint64_t seed) {
   MULTI_EACH(fspt_render(t, cam, first_tick, n_ticks, seed));
 }
+// ... and for the scenes: the live-scene update entries on every device's copy (a bad argument is refused by the first
+// scene, before anything is written)
+#define MULTI_EACH_SCENE(entry, call)                                        \
+  do {                                                                       \
+    if (!m) { fspt_set_error(#entry ": NULL handle"); return FSPT_E_INVALID; } \
+    for (fspt_scene *s : m->scenes) { const int rc_ = (call); if (rc_) return rc_; } \
+    return FSPT_OK;                                                          \
+  } while (0)
+
 int fspt_multi_update_geometry(fspt_multi *m, const float *tri, const float *norm) {
-  if (!m) { fspt_set_error("fspt_multi_update_geometry: NULL handle"); return FSPT_E_INVALID; }
-  for (fspt_scene *s : m->scenes) { // (a bad array is refused by the first scene, before anything is written)
-    const int rc = fspt_scene_update_geometry(s, tri, norm);
-    if (rc) return rc;
-  }
-  return FSPT_OK;
+  MULTI_EACH_SCENE(fspt_multi_update_geometry, fspt_scene_update_geometry(s, tri, norm));
 }
 int fspt_multi_set_pose(fspt_multi *m, const uint32_t *part, uint32_t n_parts, const float *tri, const float *norm) {
-  if (!m) { fspt_set_error("fspt_multi_set_pose: NULL handle"); return FSPT_E_INVALID; }
-  for (fspt_scene *s : m->scenes) { // (bad arguments are refused by the first scene, before anything is written)
-    const int rc = fspt_scene_set_pose(s, part, n_parts, tri, norm);
-    if (rc) return rc;
-  }
-  return FSPT_OK;
+  MULTI_EACH_SCENE(fspt_multi_set_pose, fspt_scene_set_pose(s, part, n_parts, tri, norm));
 }
 int fspt_multi_update_transforms(fspt_multi *m, const float *xf, uint32_t n_parts) {
-  if (!m) { fspt_set_error("fspt_multi_update_transforms: NULL handle"); return FSPT_E_INVALID; }
-  for (fspt_scene *s : m->scenes) { // (a bad matrix is refused by the first scene, before anything is written)
-    const int rc = fspt_scene_update_transforms(s, xf, n_parts);
-    if (rc) return rc;
-  }
-  return FSPT_OK;
+  MULTI_EACH_SCENE(fspt_multi_update_transforms, fspt_scene_update_transforms(s, xf, n_parts));
 }
 int fspt_multi_set_skin(fspt_multi *m, const fspt_skin_desc *d) {
-  if (!m) { fspt_set_error("fspt_multi_set_skin: NULL handle"); return FSPT_E_INVALID; }
-  for (fspt_scene *s : m->scenes) { // (bad arguments are refused by the first scene, before anything is written)
-    const int rc = fspt_scene_set_skin(s, d);
-    if (rc) return rc;
-  }
-  return FSPT_OK;
+  MULTI_EACH_SCENE(fspt_multi_set_skin, fspt_scene_set_skin(s, d));
 }
 int fspt_multi_update_skin(fspt_multi *m, const float *xf, uint32_t n_joints, const float *morph_w, uint32_t n_morph) {
-  if (!m) { fspt_set_error("fspt_multi_update_skin: NULL handle"); return FSPT_E_INVALID; }
-  for (fspt_scene *s : m->scenes) { // (a bad frame is refused by the first scene, before anything is written)
-    const int rc = fspt_scene_update_skin(s, xf, n_joints, morph_w, n_morph);
-    if (rc) return rc;
-  }
-  return FSPT_OK;
+  MULTI_EACH_SCENE(fspt_multi_update_skin, fspt_scene_update_skin(s, xf, n_joints, morph_w, n_morph));
 }
 int fspt_multi_update_materials(fspt_multi *m, const float *mat, const float *uv, const uint8_t *atlas, uint32_t atlas_res, uint32_t atlas_layers) {
-  if (!m) { fspt_set_error("fspt_multi_update_materials: NULL handle"); return FSPT_E_INVALID; }
-  for (fspt_scene *s : m->scenes) { // (bad arguments are refused by the first scene, before anything is written)
-    const int rc = fspt_scene_update_materials(s, mat, uv, atlas, atlas_res, atlas_layers);
-    if (rc) return rc;
-  }
-  return FSPT_OK;
+  MULTI_EACH_SCENE(fspt_multi_update_materials, fspt_scene_update_materials(s, mat, uv, atlas, atlas_res, atlas_layers));
 }
 int fspt_multi_update_environment(fspt_multi *m, const uint8_t *env, uint32_t env_w, uint32_t env_h, const uint32_t *bins, uint32_t n_bins) {
-  if (!m) { fspt_set_error("fspt_multi_update_environment: NULL handle"); return FSPT_E_INVALID; }
-  for (fspt_scene *s : m->scenes) {
-    const int rc = fspt_scene_update_environment(s, env, env_w, env_h, bins, n_bins);
-    if (rc) return rc;
-  }
-  return FSPT_OK;
+  MULTI_EACH_SCENE(fspt_multi_update_environment, fspt_scene_update_environment(s, env, env_w, env_h, bins, n_bins));
 }
 int fspt_multi_rebuild_geometry(fspt_multi *m, const float *tri, const float *norm, uint32_t *order_out) {
   if (!m) { fspt_set_error("fspt_multi_rebuild_geometry: NULL handle"); return FSPT_E_INVALID; }

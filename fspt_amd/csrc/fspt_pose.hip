@@ -11,7 +11,7 @@
 //   vertex   p'_c = fma(a_c2, z, fma(a_c1, y, fma(a_c0, x, t_c)))
 //   t, bt    d'_c = fma(D_c2, z, fma(D_c1, y, D_c0 * x))          D = float32(A / g),       g = sqrt(sum of squares / 3)
 //   n        the same with N                                      N = float32(cof(A) / g^2)
-// D and N come from the host in float64 (fspt_api.cpp pose_matrices); nothing is normalised here.
+// D and N come from the host in float64 (fspt_scene_update.cpp pose_matrices); nothing is normalised here.
 // Shape: one work item per float3.  The vectors of tri (3 T) and of norm (9 T) are numbered one array after the other, so a
 // wave's 64 lanes read one contiguous 768-byte span and write another one: its three dword loads touch the same six
 // 128-byte lines, every byte of which the wave uses (the second and third load hit what the first brought into the L1),

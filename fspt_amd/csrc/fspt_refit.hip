@@ -241,29 +241,34 @@ void refit_release(fspt_scene *s) {
   R.d_leaf = R.d_lvl = R.d_flag = nullptr; R.stage = nullptr;
 }
 
+// k_refit_check over tri and norm (may be NULL) on the NULL stream, behind the caller's memset of the flag, and the flag's
+// read-back, which waits for it: *finite = 0 when a word is inf or NaN.  *launches grows by the kernels launched.
+static int check_finite_launch(fspt_scene *s, const float *tri, const float *norm, int *finite, uint32_t *launches) {
+  const uint32_t BS = 256;
+  uint32_t *flag = s->rf.d_flag, got = 0u;
+  const struct { const float *p; size_t n; } arrays[] = {{tri, (size_t)s->n_tris * 9}, {norm, (size_t)s->n_tris * 27}};
+  for (const auto &a : arrays) {
+    if (!a.p) continue;
+    hipLaunchKernelGGL(k_refit_check, dim3(std::min<uint32_t>(blocks_for(a.n, BS), 4096u)), dim3(BS), 0, nullptr, (const uint32_t *)a.p, a.n, flag);
+    ++*launches;
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(&got, flag, 4, hipMemcpyDeviceToHost));
+  *finite = got == 0u;
+  return FSPT_OK;
+}
+
 int refit_run(fspt_scene *s, const float *tri, const float *norm, int *finite, int *quads_ok) {
   fspt_scene::Refit &R = s->rf;
   const uint32_t T = s->n_tris, LS = s->d.leaf_size, nl = (uint32_t)R.leaf_first.size(), NI = s->n_interior;
   const uint32_t BS = 256;
   hipStream_t st = nullptr;
-  uint32_t flags[2] = {0u, 0u};
+  uint32_t quads_bad = 0u;
   HIP_TRY(hipMemsetAsync(R.d_flag, 0, 8, st));
   HIP_TRY(hipEventRecord(R.ev[0], st));
   uint32_t launches = 0;
-  {
-    const size_t n = (size_t)T * 9;
-    hipLaunchKernelGGL(k_refit_check, dim3(std::min<uint32_t>(blocks_for(n, BS), 4096u)), dim3(BS), 0, st, (const uint32_t *)tri, n, R.d_flag);
-    ++launches;
-    if (norm) {
-      const size_t m = (size_t)T * 27;
-      hipLaunchKernelGGL(k_refit_check, dim3(std::min<uint32_t>(blocks_for(m, BS), 4096u)), dim3(BS), 0, st, (const uint32_t *)norm, m, R.d_flag);
-      ++launches;
-    }
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(flags, R.d_flag, 4, hipMemcpyDeviceToHost)); // (waits for the check)
-  *finite = flags[0] == 0u;
-  if (flags[0]) return FSPT_OK;
+  const int rc = check_finite_launch(s, tri, norm, finite, &launches);
+  if (rc || !*finite) return rc;
   const uint32_t *lf = R.d_leaf, *lc = R.d_leaf + nl, *ld = R.d_leaf + 2 * (size_t)nl;
   if (nl) {
     hipLaunchKernelGGL(k_refit_records, dim3(blocks_for((size_t)nl * LS, BS)), dim3(BS), 0, st, tri, norm, lf, nl, LS, T, (float *)s->tris, (float *)s->shade);
@@ -285,26 +290,18 @@ int refit_run(fspt_scene *s, const float *tri, const float *norm, int *finite, i
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(R.ev[1], st));
-  HIP_TRY(hipMemcpy(flags + 1, R.d_flag + 1, 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&quads_bad, R.d_flag + 1, 4, hipMemcpyDeviceToHost));
   HIP_TRY(hipEventSynchronize(R.ev[1]));
   HIP_TRY(hipEventElapsedTime(&R.last_ms, R.ev[0], R.ev[1]));
   R.last_launches = launches;
-  *quads_ok = s->quads && NI > 0 && flags[1] == 0u;
+  *quads_ok = s->quads && NI > 0 && quads_bad == 0u;
   return FSPT_OK;
 }
 
 int refit_check(fspt_scene *s, const float *tri, const float *norm, int *finite) {
-  fspt_scene::Refit &R = s->rf;
-  const uint32_t BS = 256;
-  uint32_t flag = 0u;
-  HIP_TRY(hipMemsetAsync(R.d_flag, 0, 4, nullptr));
-  const size_t n = (size_t)s->n_tris * 9, m = (size_t)s->n_tris * 27;
-  hipLaunchKernelGGL(k_refit_check, dim3(std::min<uint32_t>(blocks_for(n, BS), 4096u)), dim3(BS), 0, nullptr, (const uint32_t *)tri, n, R.d_flag);
-  if (norm) hipLaunchKernelGGL(k_refit_check, dim3(std::min<uint32_t>(blocks_for(m, BS), 4096u)), dim3(BS), 0, nullptr, (const uint32_t *)norm, m, R.d_flag);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(&flag, R.d_flag, 4, hipMemcpyDeviceToHost));
-  *finite = flag == 0u;
-  return FSPT_OK;
+  uint32_t launches = 0;
+  HIP_TRY(hipMemsetAsync(s->rf.d_flag, 0, 4, nullptr));
+  return check_finite_launch(s, tri, norm, finite, &launches);
 }
 
 namespace {

@@ -1,0 +1,572 @@
+// fspt_scene_update.cpp - every entry that changes a live scene, or reports on such a change: in-place geometry update
+// (DESIGN 8.6), rebuild (8.7), appearance update (8.13), part transforms (8.14), skinning (8.16), the motion origin (8.8)
+// and the read-outs that go with them.  What the families share stands once, first; every refusal names the calling entry.
+#include "fspt_internal.hpp"
+
+// ---------------------------------------------------------------------------
+// the shared steps
+// ---------------------------------------------------------------------------
+// A host array's finite check (p may be NULL: nothing to check).  FSPT_E_INVALID with the error set and *bad = the index.
+static int check_finite(const char *fn, const char *name, const float *p, size_t n, uint64_t *bad = nullptr) {
+  for (size_t i = 0; p && i < n; ++i)
+    if (!std::isfinite(p[i])) {
+      if (bad) *bad = i;
+      fspt_set_error("%s: %s[%zu] is not finite", fn, name, i);
+      return FSPT_E_INVALID;
+    }
+  return FSPT_OK;
+}
+
+// ... of host tri (T x 9) and norm (T x 27, may be NULL).  It needs no device: the entries refuse before anything is touched.
+static int check_geometry_finite(const char *fn, size_t T, const float *tri, const float *norm) {
+  const int rc = check_finite(fn, "tri", tri, T * 9);
+  return rc ? rc : check_finite(fn, "norm", norm, T * 27);
+}
+
+static int refuse_not_finite_on_device(const char *fn) {
+  fspt_set_error("%s: a value of tri / norm is not finite (scene unchanged)", fn);
+  return FSPT_E_INVALID;
+}
+
+// (rebuild_geometry asks more of the leaves and says so in a text of its own)
+static int refuse_not_refittable(const char *fn) {
+  fspt_set_error("%s: scene is not refittable (the leaves' triStarts must be distinct and tile [0, n_tris), every node have one parent)", fn);
+  return FSPT_E_STATE;
+}
+
+// Begin a scene change: the scene's device current, every target's earlier work done, the device idle.
+static int begin_scene_change(fspt_scene *s) {
+  const int rc = check_device(s->device);
+  return rc ? rc : geometry_order_targets(s);
+}
+
+// Begin a refit: a scene change with the device copies of s->rf in place.
+static int begin_refit(fspt_scene *s) {
+  const int rc = begin_scene_change(s);
+  return rc ? rc : fspt::refit_prepare(s);
+}
+
+// The staging array, tri (T x 9) | norm (T x 27): made by the first call that fills it - a host-form upload, a pose or a skin.
+// (Not a part of begin_refit: the device forms of update_geometry / rebuild_geometry never fill it and allocate nothing for it.)
+static int stage_ensure(fspt_scene *s) {
+  const size_t T = s->n_tris;
+  if (!s->rf.stage) HIP_TRY(hipMalloc((void **)&s->rf.stage, T * 36 * 4));
+  return FSPT_OK;
+}
+
+// Host tri / norm into the staging array; the arguments are re-pointed at the copies.
+static int stage_upload(fspt_scene *s, const float *&tri, const float *&norm) {
+  const int rc = stage_ensure(s);
+  if (rc) return rc;
+  const size_t T = s->n_tris;
+  s->pose.posed = false; // (the staging array no longer holds a pose's or a skin's output)
+  s->skin.skinned = false;
+  HIP_TRY(hipMemcpy(s->rf.stage, tri, T * 9 * 4, hipMemcpyHostToDevice));
+  if (norm) HIP_TRY(hipMemcpy(s->rf.stage + T * 9, norm, T * 27 * 4, hipMemcpyHostToDevice));
+  tri = s->rf.stage;
+  if (norm) norm = s->rf.stage + T * 9;
+  return FSPT_OK;
+}
+
+// The staging array's tri / norm (either may be NULL) to the host: what the last pose or skin wrote.
+static int stage_download(fspt_scene *s, float *tri, float *norm) {
+  const int rc = check_device(s->device);
+  if (rc) return rc;
+  const size_t T = s->n_tris;
+  if (tri) HIP_TRY(hipMemcpy(tri, s->rf.stage, T * 9 * 4, hipMemcpyDeviceToHost));
+  if (norm) HIP_TRY(hipMemcpy(norm, s->rf.stage + T * 9, T * 27 * 4, hipMemcpyDeviceToHost));
+  return FSPT_OK;
+}
+
+// What the scene's targets MEASURED is forgotten: the live-path fractions behind the tail hand-over and the stream
+// scheduler's run statistics; with `primary_form` the primary-form timings too.  Accumulators, path state and settings stay.
+static void targets_forget_measurements(fspt_scene *s, bool primary_form) {
+  for (fspt_target *t : s->targets) {
+    if (primary_form) prim_reset(t);
+    t->live_known = false;
+    for (fspt_target::WfLane *ln : {&t->wf, &t->pr_lane}) { ln->counts_pending = false; ln->ctl_pending = false; ln->stat_key = 0; ln->stat_gen_iters = 0; }
+  }
+}
+
+// New device arrays first, so that a failure leaves what the scene had: the caller swaps on hipSuccess.  An entry with
+// `alloc` allocates *dst; one with `src` uploads `bytes` to *dst + at.  On an error every allocation made here is freed.
+struct DevicePart { void **dst; const void *src; size_t bytes, alloc, at; };
+static hipError_t alloc_and_upload(const DevicePart *parts, size_t n) {
+  hipError_t e = hipSuccess;
+  for (size_t i = 0; i < n && e == hipSuccess; ++i) {
+    const DevicePart &p = parts[i];
+    if (p.alloc) e = hipMalloc(p.dst, p.alloc);
+    if (e == hipSuccess && p.src && p.bytes) e = hipMemcpy((char *)*p.dst + p.at, p.src, p.bytes, hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) return e;
+  for (size_t i = 0; i < n; ++i) if (parts[i].alloc) hipFree(*parts[i].dst);
+  (void)hipGetLastError();
+  return e;
+}
+
+extern "C" {
+
+// ---------------------------------------------------------------------------
+// in-place geometry update (kernels in fspt_refit.hip)
+// ---------------------------------------------------------------------------
+// the refit of update_geometry / update_transforms proper: tri / norm are device memory, the call is ordered and s->rf prepared
+static int refit_device_arrays(fspt_scene *s, const float *tri, const float *norm, const char *fn) {
+  int rc = FSPT_OK;
+  if (!s->quads && s->n_interior) { // a scene created from refitted boxes may have two-level nodes where this one had none
+    HIP_TRY(hipMalloc(&s->quads, (size_t)s->n_interior * fspt::QUAD_F4 * 16u));
+  }
+  int finite = 1, quads_ok = 0;
+  rc = fspt::refit_run(s, tri, norm, &finite, &quads_ok);
+  if (rc) return rc;
+  if (!finite) return refuse_not_finite_on_device(fn);
+  s->d.quads = quads_ok ? (const float4 *)s->quads : nullptr;
+  return geometry_changed_lights(s);
+}
+
+static int update_geometry(fspt_scene *s, const float *tri, const float *norm, bool on_device, const char *fn) {
+  if (!s || !tri) { fspt_set_error("%s: NULL scene or tri", fn); return FSPT_E_INVALID; }
+  int rc = FSPT_OK;
+  if (!on_device && (rc = check_geometry_finite(fn, s->n_tris, tri, norm))) return rc;
+  if (!s->rf.ok) return refuse_not_refittable(fn);
+  if ((rc = begin_refit(s))) return rc;
+  if (!on_device && (rc = stage_upload(s, tri, norm))) return rc;
+  return refit_device_arrays(s, tri, norm, fn);
+}
+
+int fspt_scene_update_geometry(fspt_scene *s, const float *tri, const float *norm) {
+  return update_geometry(s, tri, norm, false, "fspt_scene_update_geometry");
+}
+
+int fspt_scene_update_geometry_device(fspt_scene *s, const float *tri, const float *norm) {
+  return update_geometry(s, tri, norm, true, "fspt_scene_update_geometry_device");
+}
+
+int fspt_scene_last_update_ms(fspt_scene *s, float *ms, uint32_t *launches) {
+  if (!s) { fspt_set_error("fspt_scene_last_update_ms: NULL scene"); return FSPT_E_INVALID; }
+  if (ms) *ms = s->rf.last_ms;
+  if (launches) *launches = s->rf.last_launches;
+  return FSPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// GPU part transforms (kernel in fspt_pose.hip)
+// ---------------------------------------------------------------------------
+// The rule's host part, float64 in the stated order (tests/pose_ref.py restates it): per part a (12) | D (9) | N (9).
+// NULL: every part is fine; else the reason, with *bad = the part.
+static const char *pose_matrices(const float *xf, uint32_t n_parts, float *out, uint32_t *bad) {
+  for (uint32_t p = 0; p < n_parts; ++p) {
+    const float *x = xf + (size_t)p * 12;
+    float *o = out + (size_t)p * 30;
+    *bad = p;
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(x[i])) return "an entry is not finite";
+    double A[3][3], Cf[3][3];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) A[i][j] = (double)x[4 * i + j];
+    double q = 0.0;
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) q = q + A[i][j] * A[i][j];
+    const double g = std::sqrt(q / 3.0);
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+        Cf[i][j] = A[i1][j1] * A[i2][j2] - A[i1][j2] * A[i2][j1];
+      }
+    const double det = (A[0][0] * Cf[0][0] + A[0][1] * Cf[0][1]) + A[0][2] * Cf[0][2];
+    if (det == 0.0) return "the matrix is singular";
+    const double gg = g * g;
+    for (int i = 0; i < 12; ++i) o[i] = x[i];
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        o[12 + 3 * i + j] = (float)(A[i][j] / g);
+        o[21 + 3 * i + j] = (float)(Cf[i][j] / gg);
+      }
+    for (int i = 12; i < 30; ++i) if (!std::isfinite(o[i])) return "a derived matrix is not finite";
+  }
+  return nullptr;
+}
+
+int fspt_pose_matrices_eval(const float *xf, uint32_t n_parts, float *out, uint32_t *bad_part) {
+  if (!xf || !out || n_parts == 0) { fspt_set_error("fspt_pose_matrices_eval: NULL/empty argument"); return FSPT_E_INVALID; }
+  uint32_t bad = 0;
+  if (const char *why = pose_matrices(xf, n_parts, out, &bad)) {
+    if (bad_part) *bad_part = bad;
+    fspt_set_error("fspt_pose_matrices_eval: part %u: %s", bad, why);
+    return FSPT_E_INVALID;
+  }
+  return FSPT_OK;
+}
+
+int fspt_scene_set_pose(fspt_scene *s, const uint32_t *part, uint32_t n_parts, const float *tri, const float *norm) {
+  if (!s) { fspt_set_error("fspt_scene_set_pose: NULL scene"); return FSPT_E_INVALID; }
+  if (!part) { // drop the pose
+    if (!s->pose.part && !s->pose.mats) return FSPT_OK;
+    int rc = check_device(s->device);
+    if (rc) return rc;
+    fspt::pose_release(s);
+    return FSPT_OK;
+  }
+  if (!tri || n_parts == 0) { fspt_set_error("fspt_scene_set_pose: tri is NULL or n_parts is 0"); return FSPT_E_INVALID; }
+  const size_t T = s->n_tris;
+  for (size_t i = 0; i < T; ++i) if (part[i] >= n_parts) { fspt_set_error("fspt_scene_set_pose: part[%zu] = %u, n_parts = %u", i, part[i], n_parts); return FSPT_E_INVALID; }
+  int rc = check_geometry_finite("fspt_scene_set_pose", T, tri, norm);
+  if (rc) return rc;
+  if (!s->rf.ok) return refuse_not_refittable("fspt_scene_set_pose");
+  if ((rc = check_device(s->device))) return rc;
+  // the new arrays first: an allocation that fails leaves the old pose
+  uint32_t *d_part = nullptr;
+  float *d_rest = nullptr;
+  const size_t T1 = T ? T : 1;
+  const DevicePart parts[] = {{(void **)&d_part, part, T * 4, T1 * 4, 0}, {(void **)&d_rest, tri, T * 36, T1 * (norm ? 144 : 36), 0},
+                              {(void **)&d_rest, norm, T * 108, 0, T * 36}};
+  const hipError_t e = alloc_and_upload(parts, 3);
+  if (e != hipSuccess) {
+    fspt_set_error("fspt_scene_set_pose: %s (%zu triangles)", hipGetErrorString(e), T);
+    return e == hipErrorOutOfMemory ? FSPT_E_NOMEM : FSPT_E_HIP;
+  }
+  hipFree(s->pose.part); hipFree(s->pose.rest);
+  s->pose.part = d_part; s->pose.rest = d_rest;
+  s->pose.has_norm = norm != nullptr;
+  s->pose.n_parts = n_parts;
+  s->pose.posed = false;
+  return FSPT_OK;
+}
+
+int fspt_scene_update_transforms(fspt_scene *s, const float *xf, uint32_t n_parts) {
+  if (!s || !xf) { fspt_set_error("fspt_scene_update_transforms: NULL scene or xf"); return FSPT_E_INVALID; }
+  if (!s->pose.part) { fspt_set_error("fspt_scene_update_transforms: the scene has no pose (fspt_scene_set_pose)"); return FSPT_E_STATE; }
+  if (n_parts != s->pose.n_parts) { fspt_set_error("fspt_scene_update_transforms: %u matrices, the pose has %u parts", n_parts, s->pose.n_parts); return FSPT_E_INVALID; }
+  std::vector<float> mats((size_t)n_parts * 30);
+  uint32_t bad = 0;
+  if (const char *why = pose_matrices(xf, n_parts, mats.data(), &bad)) {
+    fspt_set_error("fspt_scene_update_transforms: part %u: %s (scene unchanged)", bad, why);
+    return FSPT_E_INVALID;
+  }
+  int rc = begin_refit(s);
+  if (rc || (rc = stage_ensure(s)) || (rc = fspt::pose_run(s, mats.data()))) return rc;
+  const size_t T = s->n_tris;
+  return refit_device_arrays(s, s->rf.stage, s->pose.has_norm ? s->rf.stage + T * 9 : nullptr, "fspt_scene_update_transforms");
+}
+
+int fspt_scene_read_pose(fspt_scene *s, float *tri, float *norm) {
+  if (!s || (!tri && !norm)) { fspt_set_error("fspt_scene_read_pose: NULL argument"); return FSPT_E_INVALID; }
+  if (!s->pose.part || !s->pose.posed) { fspt_set_error("fspt_scene_read_pose: no fspt_scene_update_transforms since the pose was set, the scene rebuilt or its geometry uploaded"); return FSPT_E_STATE; }
+  if (norm && !s->pose.has_norm) { fspt_set_error("fspt_scene_read_pose: the pose has no rest norm"); return FSPT_E_STATE; }
+  return stage_download(s, tri, norm);
+}
+
+int fspt_scene_last_pose_ms(fspt_scene *s, float *transform_ms, float *refit_ms, uint32_t *launches) {
+  if (!s) { fspt_set_error("fspt_scene_last_pose_ms: NULL scene"); return FSPT_E_INVALID; }
+  if (transform_ms) *transform_ms = s->pose.last_ms;
+  if (refit_ms) *refit_ms = s->rf.last_ms;
+  if (launches) *launches = s->rf.last_launches + 1u;
+  return FSPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// GPU skinning (kernel in fspt_pose.hip)
+// ---------------------------------------------------------------------------
+// fspt_scene_set_skin's validation: host only.  FSPT_OK, or FSPT_E_INVALID with the error set and *bad = the index.
+static int skin_check(const fspt_skin_desc *d, size_t T, const char *fn, uint64_t *bad) {
+  if (!d || !d->joints || !d->weights || !d->tri) { fspt_set_error("%s: joints, weights or tri is NULL", fn); return FSPT_E_INVALID; }
+  if (d->n_joints < 1 || d->n_joints > 65535) { fspt_set_error("%s: n_joints = %u, must lie in [1, 65535]", fn, d->n_joints); return FSPT_E_INVALID; }
+  if (d->n_morph > FSPT_SKIN_MAX_MORPH) { fspt_set_error("%s: n_morph = %u, at most %d", fn, d->n_morph, FSPT_SKIN_MAX_MORPH); return FSPT_E_INVALID; }
+  if (d->n_morph && !d->morph) { fspt_set_error("%s: n_morph = %u but morph is NULL", fn, d->n_morph); return FSPT_E_INVALID; }
+  if (d->morph_norm && !d->norm) { fspt_set_error("%s: morph_norm needs a rest norm", fn); return FSPT_E_INVALID; }
+  if (d->morph_norm && !d->n_morph) { fspt_set_error("%s: morph_norm given with n_morph = 0", fn); return FSPT_E_INVALID; }
+  const size_t slots = T * 12;
+  for (size_t i = 0; i < slots; ++i)
+    if (d->joints[i] >= d->n_joints) { *bad = i; fspt_set_error("%s: joints[%zu] = %u, n_joints = %u", fn, i, (unsigned)d->joints[i], d->n_joints); return FSPT_E_INVALID; }
+  const struct { const char *name; const float *p; size_t n; } arrays[] = {
+      {"weights", d->weights, slots}, {"tri", d->tri, T * 9}, {"norm", d->norm, T * 27},
+      {"morph", d->n_morph ? d->morph : nullptr, (size_t)d->n_morph * T * 9}, {"morph_norm", d->morph_norm, (size_t)d->n_morph * T * 27}};
+  for (const auto &a : arrays)
+    if (const int rc = check_finite(fn, a.name, a.p, a.n, bad)) return rc;
+  return FSPT_OK;
+}
+
+int fspt_skin_check_eval(const fspt_skin_desc *d, uint32_t n_tris, uint64_t *bad_index) {
+  uint64_t bad = 0;
+  const int rc = skin_check(d, n_tris, "fspt_skin_check_eval", &bad);
+  if (rc && bad_index) *bad_index = bad;
+  return rc;
+}
+
+int fspt_skin_set_form(int form) {
+  if (form != 0 && form != 1) { fspt_set_error("fspt_skin_set_form: form must be 0 or 1"); return FSPT_E_INVALID; }
+  fspt::g_skin_form = form;
+  return FSPT_OK;
+}
+
+static uint64_t skin_bytes(const fspt_scene *s) {
+  const fspt_scene::Skin &K = s->skin;
+  if (!K.joints) return 0;
+  const uint64_t T = s->n_tris;
+  return T * (24 + 48 + 36 + (K.has_norm ? 108 : 0)) + (uint64_t)K.n_morph * T * (36 + (K.morph_norm ? 108 : 0)) + (uint64_t)K.n_joints * 48 + (uint64_t)K.n_morph * 4;
+}
+
+int fspt_scene_set_skin(fspt_scene *s, const fspt_skin_desc *d) {
+  if (!s) { fspt_set_error("fspt_scene_set_skin: NULL scene"); return FSPT_E_INVALID; }
+  if (!d) { // drop the skin
+    if (!s->skin.joints) return FSPT_OK;
+    int rc = check_device(s->device);
+    if (rc) return rc;
+    fspt::skin_release(s);
+    return FSPT_OK;
+  }
+  const size_t T = s->n_tris;
+  uint64_t bad = 0;
+  int rc = skin_check(d, T, "fspt_scene_set_skin", &bad);
+  if (rc) return rc;
+  if (!s->rf.ok) return refuse_not_refittable("fspt_scene_set_skin");
+  rc = check_device(s->device);
+  if (rc) return rc;
+  // the new arrays first: an allocation that fails leaves the old skin
+  fspt_scene::Skin N;
+  const size_t T1 = T ? T : 1, M = d->n_morph;
+  const DevicePart parts[] = {
+      {(void **)&N.joints, d->joints, T * 24, T1 * 24, 0}, {(void **)&N.weights, d->weights, T * 48, T1 * 48, 0},
+      {(void **)&N.rest, d->tri, T * 36, T1 * (d->norm ? 144 : 36), 0},
+      {(void **)&N.morph, d->morph, M * T * 36, M * T1 * 36, 0}, {(void **)&N.morph_norm, d->morph_norm, M * T * 108, d->morph_norm ? M * T1 * 108 : 0, 0},
+      {(void **)&N.frame, nullptr, 0, (size_t)d->n_joints * 48 + M * 4, 0}, {(void **)&N.rest, d->norm, T * 108, 0, T * 36}};
+  const hipError_t e = alloc_and_upload(parts, sizeof(parts) / sizeof(parts[0]));
+  if (e != hipSuccess) {
+    fspt_set_error("fspt_scene_set_skin: %s (%zu triangles, %u joints, %u morph targets)", hipGetErrorString(e), T, d->n_joints, d->n_morph);
+    return e == hipErrorOutOfMemory ? FSPT_E_NOMEM : FSPT_E_HIP;
+  }
+  N.has_norm = d->norm != nullptr;
+  N.n_joints = d->n_joints;
+  N.n_morph = d->n_morph;
+  fspt::skin_release(s);
+  s->skin = N;
+  return FSPT_OK;
+}
+
+static int update_skin(fspt_scene *s, const float *xf, uint32_t n_joints, const float *morph_w, uint32_t n_morph, bool on_device, const char *fn) {
+  if (!s || !xf) { fspt_set_error("%s: NULL scene or xf", fn); return FSPT_E_INVALID; }
+  const fspt_scene::Skin &K = s->skin;
+  if (!K.joints) { fspt_set_error("%s: the scene has no skin (fspt_scene_set_skin)", fn); return FSPT_E_STATE; }
+  if (n_joints != K.n_joints) { fspt_set_error("%s: %u matrices, the skin has %u joints", fn, n_joints, K.n_joints); return FSPT_E_INVALID; }
+  if (n_morph != K.n_morph) { fspt_set_error("%s: %u morph weights, the skin has %u targets", fn, n_morph, K.n_morph); return FSPT_E_INVALID; }
+  if (n_morph && !morph_w) { fspt_set_error("%s: morph_w is NULL, the skin has %u targets", fn, n_morph); return FSPT_E_INVALID; }
+  if (on_device) {
+    if ((uintptr_t)xf % 16) { fspt_set_error("%s: xf must be 16-byte aligned", fn); return FSPT_E_INVALID; }
+  } else { // the host form's check needs no device: refuse before anything is touched
+    for (uint32_t j = 0; j < n_joints; ++j)
+      for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(xf[(size_t)j * 12 + i])) { fspt_set_error("%s: joint %u: an entry is not finite (scene unchanged)", fn, j); return FSPT_E_INVALID; }
+    for (uint32_t m = 0; m < n_morph; ++m)
+      if (!std::isfinite(morph_w[m])) { fspt_set_error("%s: morph target %u: its weight is not finite (scene unchanged)", fn, m); return FSPT_E_INVALID; }
+  }
+  int rc = begin_refit(s);
+  if (rc || (rc = stage_ensure(s)) || (rc = fspt::skin_run(s, xf, morph_w, on_device))) return rc;
+  const size_t T = s->n_tris;
+  return refit_device_arrays(s, s->rf.stage, K.has_norm ? s->rf.stage + T * 9 : nullptr, fn);
+}
+
+int fspt_scene_update_skin(fspt_scene *s, const float *xf, uint32_t n_joints, const float *morph_w, uint32_t n_morph) {
+  return update_skin(s, xf, n_joints, morph_w, n_morph, false, "fspt_scene_update_skin");
+}
+
+int fspt_scene_update_skin_device(fspt_scene *s, const float *xf, uint32_t n_joints, const float *morph_w, uint32_t n_morph) {
+  return update_skin(s, xf, n_joints, morph_w, n_morph, true, "fspt_scene_update_skin_device");
+}
+
+int fspt_scene_read_skin(fspt_scene *s, float *tri, float *norm) {
+  if (!s || (!tri && !norm)) { fspt_set_error("fspt_scene_read_skin: NULL argument"); return FSPT_E_INVALID; }
+  if (!s->skin.joints || !s->skin.skinned) { fspt_set_error("fspt_scene_read_skin: no fspt_scene_update_skin since the skin was set, the scene rebuilt, posed or its geometry uploaded"); return FSPT_E_STATE; }
+  if (norm && !s->skin.has_norm) { fspt_set_error("fspt_scene_read_skin: the skin has no rest norm"); return FSPT_E_STATE; }
+  return stage_download(s, tri, norm);
+}
+
+int fspt_scene_last_skin_ms(fspt_scene *s, float *skin_ms, float *refit_ms, uint32_t *launches, uint64_t *bytes) {
+  if (!s) { fspt_set_error("fspt_scene_last_skin_ms: NULL scene"); return FSPT_E_INVALID; }
+  if (skin_ms) *skin_ms = s->skin.last_ms;
+  if (refit_ms) *refit_ms = s->rf.last_ms;
+  if (launches) *launches = s->rf.last_launches + 1u;
+  if (bytes) *bytes = skin_bytes(s);
+  return FSPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// in-place rebuild (fspt_refit.hip rebuild_run)
+// ---------------------------------------------------------------------------
+static int rebuild_geometry(fspt_scene *s, const float *tri, const float *norm, uint32_t *order_out, bool on_device, const char *fn) {
+  if (!s || !tri) { fspt_set_error("%s: NULL scene or tri", fn); return FSPT_E_INVALID; }
+  int rc = FSPT_OK;
+  if (!on_device && (rc = check_geometry_finite(fn, s->n_tris, tri, norm))) return rc;
+  // the triangle -> old slot map needs every triangle in a slot of the leaf that owns it
+  bool mapped = s->rf.ok;
+  for (size_t L = 0; mapped && L < s->rf.leaf_cnt.size(); ++L) mapped = s->rf.leaf_cnt[L] <= s->d.leaf_size;
+  if (!mapped) {
+    fspt_set_error("%s: scene is not refittable (the leaves' triStarts must be distinct and tile [0, n_tris) in steps of at most leaf_size, every node have one parent)", fn);
+    return FSPT_E_STATE;
+  }
+  struct Restore { int prev = -1; ~Restore() { if (prev >= 0) (void)hipSetDevice(prev); } } restore; // the caller's current device stays
+  if (hipGetDevice(&restore.prev) != hipSuccess) restore.prev = -1;
+  if ((rc = begin_refit(s))) return rc;
+  if (!on_device) {
+    // (the upload drops the pose's / the skin's claim on the staging array at once: a rebuild that fails behind it must
+    // not leave fspt_scene_read_pose / fspt_scene_read_skin handing out the uploaded arrays)
+    if ((rc = stage_upload(s, tri, norm))) return rc;
+  } else {
+    int finite = 1;
+    rc = fspt::refit_check(s, tri, norm, &finite);
+    if (rc) return rc;
+    if (!finite) return refuse_not_finite_on_device(fn);
+  }
+  rc = fspt::rebuild_run(s, tri, norm, order_out, on_device);
+  if (rc) return rc;
+  // Every target now behaves like one created after the rebuild.  The DScene (arrays, root_ref, stack_n, n_top, quads) is
+  // copied from the scene at every launch, and the LDS stack, the launch shapes and the node form are computed from it
+  // there; the suspended-traversal records are re-made by susp_ensure when stack_n changed their stride.  What a target
+  // measured on the old tree is forgotten, the primary-form timings included.
+  targets_forget_measurements(s, true);
+  return geometry_changed_lights(s);
+}
+
+int fspt_scene_rebuild_geometry(fspt_scene *s, const float *tri, const float *norm, uint32_t *order_out) {
+  return rebuild_geometry(s, tri, norm, order_out, false, "fspt_scene_rebuild_geometry");
+}
+
+int fspt_scene_rebuild_geometry_device(fspt_scene *s, const float *tri, const float *norm, uint32_t *order_out) {
+  return rebuild_geometry(s, tri, norm, order_out, true, "fspt_scene_rebuild_geometry_device");
+}
+
+int fspt_scene_last_rebuild_ms(fspt_scene *s, float *build_ms, float *install_ms, float *host_ms, uint32_t *launches, uint32_t *readbacks) {
+  if (!s) { fspt_set_error("fspt_scene_last_rebuild_ms: NULL scene"); return FSPT_E_INVALID; }
+  if (build_ms) *build_ms = s->rb.build_ms;
+  if (install_ms) *install_ms = s->rb.install_ms;
+  if (host_ms) *host_ms = s->rb.host_ms;
+  if (launches) *launches = s->rb.launches;
+  if (readbacks) *readbacks = s->rb.readbacks;
+  return FSPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// in-place appearance update (kernels in fspt_appearance.hip)
+// ---------------------------------------------------------------------------
+int fspt_scene_update_materials(fspt_scene *s, const float *mat, const float *uv, const uint8_t *atlas, uint32_t atlas_res, uint32_t atlas_layers) {
+  if (!s || !mat) { fspt_set_error("fspt_scene_update_materials: NULL scene or mat"); return FSPT_E_INVALID; }
+  if (atlas && (atlas_res == 0 || atlas_layers == 0)) {
+    fspt_set_error("fspt_scene_update_materials: atlas must have at least one layer");
+    return FSPT_E_INVALID;
+  }
+  if (!atlas && !s->ap.raw) {
+    fspt_set_error("fspt_scene_update_materials: atlas is NULL and no earlier call of this scene carried one");
+    return FSPT_E_STATE;
+  }
+  int rc = begin_scene_change(s);
+  if (rc) return rc;
+  const bool was = s->has_dielectric;
+  if ((rc = fspt::appearance_materials(s, mat, uv, atlas, atlas_res, atlas_layers))) return rc;
+  // the stream scheduler's horizon and the batch scheduler's tail rule read has_dielectric at every launch; what a lane
+  // measured under the other horizon (iterations a run needed, live-path fractions) is forgotten with it
+  if (was != s->has_dielectric) targets_forget_measurements(s, false);
+  return geometry_changed_lights(s); // the table depends on the emissive layers and their texels
+}
+
+int fspt_scene_update_environment(fspt_scene *s, const uint8_t *env, uint32_t env_w, uint32_t env_h, const uint32_t *bins, uint32_t n_bins) {
+  if (!s) { fspt_set_error("fspt_scene_update_environment: NULL scene"); return FSPT_E_INVALID; }
+  if (!bins || n_bins == 0) {
+    fspt_set_error("fspt_scene_update_environment: radianceBins must hold at least one bin (main.js:292)");
+    return FSPT_E_INVALID;
+  }
+  if (env && (env_w == 0 || env_h == 0)) {
+    fspt_set_error("fspt_scene_update_environment: env given with zero size");
+    return FSPT_E_INVALID;
+  }
+  const int rc = begin_scene_change(s);
+  if (rc) return rc;
+  return fspt::appearance_environment(s, env, env_w, env_h, bins, n_bins);
+}
+
+int fspt_scene_read_appearance(fspt_scene *s, int what, void *out, uint64_t cap, uint64_t *bytes) {
+  if (!s || what < 0 || what > 5) { fspt_set_error("fspt_scene_read_appearance: NULL scene or what not in [0, 5]"); return FSPT_E_INVALID; }
+  const void *src[6] = {s->tex_sets, s->atlas, s->atlas4, s->env, s->bins, s->shade};
+  const uint64_t size[6] = {(uint64_t)s->d.n_tex_sets * 48u, s->atlas_bytes, s->atlas4_bytes, s->env_bytes, (uint64_t)s->d.n_bins * 16u, (uint64_t)s->n_slots * 192u};
+  if (bytes) *bytes = size[what];
+  const uint64_t n = cap < size[what] ? cap : size[what];
+  if (!out || !n) return FSPT_OK;
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, src[what], n, hipMemcpyDeviceToHost));
+  return FSPT_OK;
+}
+
+int fspt_scene_last_appearance_ms(fspt_scene *s, float *ms, uint32_t *launches, uint64_t *uploaded, uint64_t *retained) {
+  if (!s) { fspt_set_error("fspt_scene_last_appearance_ms: NULL scene"); return FSPT_E_INVALID; }
+  if (ms) *ms = s->ap.last_ms;
+  if (launches) *launches = s->ap.last_launches;
+  if (uploaded) *uploaded = s->ap.last_uploaded;
+  if (retained) *retained = s->ap.raw ? (uint64_t)s->ap.raw_res * s->ap.raw_res * s->ap.raw_layers * 4u : 0u;
+  return FSPT_OK;
+}
+
+
+// sum over the leaves of SA / SA(root) x triangles owned + sum over the interior nodes of SA / SA(root), float64, in the
+// reference's node order, from the boxes the device holds now (a node's box sits in its parent's record; the root's is
+// the union of its children's)
+int fspt_scene_sah_cost(fspt_scene *s, double *cost) {
+  if (!s || !cost) { fspt_set_error("fspt_scene_sah_cost: NULL argument"); return FSPT_E_INVALID; }
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  if (!s->n_interior) { *cost = (double)s->n_tris; return FSPT_OK; } // the root is the one leaf
+  std::vector<float> nodes((size_t)s->n_interior * 16); // (only an update writes the boxes, and it has finished when it returns)
+  HIP_TRY(hipMemcpy(nodes.data(), s->nodes, nodes.size() * 4, hipMemcpyDeviceToHost));
+  auto area = [](const float lo[3], const float hi[3]) {
+    const double e0 = (double)hi[0] - (double)lo[0], e1 = (double)hi[1] - (double)lo[1], e2 = (double)hi[2] - (double)lo[2];
+    return (e0 * e1 + e0 * e2 + e1 * e2) * 2.0;
+  };
+  auto box_at = [&](uint32_t slot, float lo[3], float hi[3]) {
+    const float *f = &nodes[(size_t)(slot >> 1) * 16];
+    const uint32_t k = slot & 1u;
+    lo[0] = f[4 * k]; lo[1] = f[4 * k + 1]; lo[2] = f[8 + 2 * k];
+    hi[0] = f[4 * k + 2]; hi[1] = f[4 * k + 3]; hi[2] = f[9 + 2 * k];
+  };
+  const uint32_t NO = fspt_scene::Refit::NO_DST;
+  float lo[3], hi[3], l2[3], h2[3];
+  box_at(2u * (uint32_t)s->d.root_ref, lo, hi);
+  box_at(2u * (uint32_t)s->d.root_ref + 1u, l2, h2);
+  for (int a = 0; a < 3; ++a) { lo[a] = l2[a] < lo[a] ? l2[a] : lo[a]; hi[a] = h2[a] > hi[a] ? h2[a] : hi[a]; }
+  const double root = area(lo, hi);
+  double sum = root; // the root itself
+  for (uint32_t i = 1; i < s->n_nodes; ++i) {
+    if (s->rf.node_dst[i] == NO) continue; // not reachable from the root
+    box_at(s->rf.node_dst[i], lo, hi);
+    const double sa = area(lo, hi);
+    sum += s->rf.node_owned[i] == NO ? sa : sa * (double)s->rf.node_owned[i];
+  }
+  *cost = sum / root;
+  return FSPT_OK;
+}
+
+// Motion origin: floats 0-8 (v1, e1, e2) of every leaf slot's hit record as they are now.
+int fspt_scene_motion_begin(fspt_scene *s) {
+  if (!s) { fspt_set_error("fspt_scene_motion_begin: NULL scene"); return FSPT_E_INVALID; }
+  const int rc = begin_scene_change(s); // (an accumulate in flight reads the old snapshot)
+  if (rc) return rc;
+  if (!s->motion) HIP_TRY(hipMalloc(&s->motion, (s->n_slots ? s->n_slots : 1) * 36));
+  if (s->n_slots) HIP_TRY(hipMemcpy2D(s->motion, 36, s->shade, 192, 36, s->n_slots, hipMemcpyDeviceToDevice));
+  return FSPT_OK;
+}
+
+int fspt_scene_slot_triangles(fspt_scene *s, uint32_t *n_slots, uint32_t *slot_tri) {
+  if (!s || (!n_slots && !slot_tri)) { fspt_set_error("fspt_scene_slot_triangles: NULL argument"); return FSPT_E_INVALID; }
+  if (n_slots) *n_slots = (uint32_t)s->n_slots;
+  if (!slot_tri) return FSPT_OK;
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(slot_tri, s->slot_tri, s->n_slots * 4, hipMemcpyDeviceToHost));
+  return FSPT_OK;
+}
+
+int fspt_scene_motion_end(fspt_scene *s) {
+  if (!s) { fspt_set_error("fspt_scene_motion_end: NULL scene"); return FSPT_E_INVALID; }
+  if (!s->motion) return FSPT_OK;
+  const int rc = begin_scene_change(s);
+  if (rc) return rc;
+  HIP_TRY(hipFree(s->motion));
+  s->motion = nullptr;
+  return FSPT_OK;
+}
+
+} // extern "C"

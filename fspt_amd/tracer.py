@@ -351,6 +351,18 @@ def camera_model_params(model="pinhole", angle=None, ipd=None):
 DENOISE_DEFAULTS = {"iterations": 4, "sigma_color": 4.0, "sigma_normal": 32.0, "sigma_depth": 0.05}
 
 
+def _host_geometry(fn, n, tri, norm):
+    """(tri, norm) as contiguous float32 host arrays of n x 9 and n x 27 elements (norm may be None)"""
+    tri = np.ascontiguousarray(tri, dtype=np.float32)
+    if tri.size != n * 9:
+        raise ValueError(f"{fn}: tri has {tri.size} elements, the scene needs {n} x 9")
+    if norm is not None:
+        norm = np.ascontiguousarray(norm, dtype=np.float32)
+        if norm.size != n * 27:
+            raise ValueError(f"{fn}: norm has {norm.size} elements, the scene needs {n} x 27")
+    return tri, norm
+
+
 class Scene:
     """Device-resident scene (initBVH's texture uploads, main.js:408-437,548-560)."""
 
@@ -438,14 +450,7 @@ class Scene:
                 ptrs.append(C.c_void_p(a.data_ptr()))
             torch.cuda.current_stream(self.device).synchronize()  # whatever wrote the tensors has finished
             return True, ptrs[0], ptrs[1]
-        tri = np.ascontiguousarray(tri, dtype=np.float32)
-        if tri.size != n * 9:
-            raise ValueError(f"{fn}: tri has {tri.size} elements, the scene needs {n} x 9")
-        if norm is not None:
-            norm = np.ascontiguousarray(norm, dtype=np.float32)
-            if norm.size != n * 27:
-                raise ValueError(f"{fn}: norm has {norm.size} elements, the scene needs {n} x 27")
-        return False, tri, norm
+        return (False,) + _host_geometry(fn, n, tri, norm)
 
     def update_geometry(self, tri, norm=None):
         """New vertices (9 floats per triangle) and, unless norm is None, normTex records (27 per triangle) for the scene's
@@ -540,13 +545,7 @@ class Scene:
         weights = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
         if joints.size != n * 12 or weights.size != n * 12:
             raise ValueError(f"{fn}: joints has {joints.size} and weights {weights.size} elements, the scene needs {n} x 3 x 4 of each")
-        tri = np.ascontiguousarray(tri, dtype=np.float32).reshape(-1)
-        if tri.size != n * 9:
-            raise ValueError(f"{fn}: tri has {tri.size} elements, the scene needs {n} x 9")
-        if norm is not None:
-            norm = np.ascontiguousarray(norm, dtype=np.float32).reshape(-1)
-            if norm.size != n * 27:
-                raise ValueError(f"{fn}: norm has {norm.size} elements, the scene needs {n} x 27")
+        tri, norm = _host_geometry(fn, n, tri, norm)
         n_morph = 0
         if morph is not None:
             morph = np.ascontiguousarray(morph, dtype=np.float32).reshape(-1)
@@ -1453,13 +1452,7 @@ class MultiPathTracer:
     def update_geometry(self, tri, norm=None):
         """Scene.update_geometry (host arrays) on every device's copy of the scene (fspt_multi_update_geometry)."""
         n = int(self.arrays.n_tris)
-        tri = np.ascontiguousarray(tri, dtype=np.float32)
-        if tri.size != n * 9:
-            raise ValueError(f"update_geometry: tri has {tri.size} elements, the scene needs {n} x 9")
-        if norm is not None:
-            norm = np.ascontiguousarray(norm, dtype=np.float32)
-            if norm.size != n * 27:
-                raise ValueError(f"update_geometry: norm has {norm.size} elements, the scene needs {n} x 27")
+        tri, norm = _host_geometry("update_geometry", n, tri, norm)
         L.check(L.lib().fspt_multi_update_geometry(self._m, L.fptr(tri), None if norm is None else L.fptr(norm)))
 
     def set_pose(self, part, tri=None, norm=None):
@@ -1473,10 +1466,9 @@ class MultiPathTracer:
                 raise ValueError("set_pose: norm given without tri")
             tri, norm = self.arrays.tri, self.arrays.norm
         part = np.ascontiguousarray(_u32_array(part, "part"), dtype=np.uint32).reshape(-1)
-        tri = np.ascontiguousarray(tri, dtype=np.float32)
-        norm = None if norm is None else np.ascontiguousarray(norm, dtype=np.float32)
-        if part.size != n or tri.size != n * 9 or (norm is not None and norm.size != n * 27):
-            raise ValueError(f"set_pose: the scene needs {n} part ids, {n} x 9 tri and {n} x 27 norm elements")
+        if part.size != n:
+            raise ValueError(f"set_pose: part has {part.size} elements, the scene has {n} triangles")
+        tri, norm = _host_geometry("set_pose", n, tri, norm)
         L.check(L.lib().fspt_multi_set_pose(self._m, L.u32ptr(part), int(part.max()) + 1 if n else 1, L.fptr(tri),
                                             None if norm is None else L.fptr(norm)))
 
@@ -1520,13 +1512,7 @@ class MultiPathTracer:
         """Scene.rebuild_geometry (host arrays) on every device's copy of the scene (fspt_multi_rebuild_geometry); every
         device builds the same tree, the one order is returned."""
         n = int(self.arrays.n_tris)
-        tri = np.ascontiguousarray(tri, dtype=np.float32)
-        if tri.size != n * 9:
-            raise ValueError(f"rebuild_geometry: tri has {tri.size} elements, the scene needs {n} x 9")
-        if norm is not None:
-            norm = np.ascontiguousarray(norm, dtype=np.float32)
-            if norm.size != n * 27:
-                raise ValueError(f"rebuild_geometry: norm has {norm.size} elements, the scene needs {n} x 27")
+        tri, norm = _host_geometry("rebuild_geometry", n, tri, norm)
         order = np.zeros(n, np.uint32)
         L.check(L.lib().fspt_multi_rebuild_geometry(self._m, L.fptr(tri), None if norm is None else L.fptr(norm), L.u32ptr(order)))
         return order

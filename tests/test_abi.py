@@ -112,6 +112,25 @@ def test_scene_validation_errors(small_scene):
     assert b"pre-order" in lib.fspt_last_error()
 
 
+def test_multi_update_forwarders_refuse_a_null_handle():
+    """the live-scene update entries of fspt_multi_*: no device is touched before the handle is looked at, and the text
+    names the entry"""
+    lib = L.lib()
+    calls = {
+        "fspt_multi_update_geometry": (None, None),
+        "fspt_multi_set_pose": (None, 0, None, None),
+        "fspt_multi_update_transforms": (None, 0),
+        "fspt_multi_set_skin": (None,),
+        "fspt_multi_update_skin": (None, 0, None, 0),
+        "fspt_multi_update_materials": (None, None, None, 0, 0),
+        "fspt_multi_update_environment": (None, 0, 0, None, 0),
+        "fspt_multi_rebuild_geometry": (None, None, None),
+    }
+    for name, args in calls.items():
+        assert getattr(lib, name)(None, *args) == -1, name
+        assert lib.fspt_last_error() == f"{name}: NULL handle".encode(), name
+
+
 def test_builder_errors():
     lib = L.lib()
     b = C.c_void_p()

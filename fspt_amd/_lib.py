@@ -71,6 +71,12 @@ class SkinDesc(C.Structure):
                 ("morph_norm", C.POINTER(C.c_float)), ("n_morph", C.c_uint32)]
 
 
+class SkyParams(C.Structure):
+    """fspt_sky_params"""
+    _fields_ = [("sun_dir", C.c_float * 3), ("turbidity", C.c_float), ("sun_intensity", C.c_float), ("sun_radius", C.c_float),
+                ("gain", C.c_float), ("ground_albedo", C.c_float * 3), ("view_samples", C.c_uint32), ("light_samples", C.c_uint32)]
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("target_rel_mse", C.c_double), ("max_ticks", C.c_uint32), ("min_ticks", C.c_uint32), ("round_ticks", C.c_uint32)]
 
@@ -285,6 +291,15 @@ SIGNATURES = {
     "fspt_builder_autofocus": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "fspt_builder_get": (C.c_int, [_VP, _F, _F, _F, _F, _F]),
     "fspt_env_bins": (C.c_int, [C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, _U32, C.c_uint32, _U32]),
+    "fspt_env_bins_gpu": (C.c_int, [C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_int, _U32, C.c_uint32, _U32]),
+    "fspt_sky_generate": (C.c_int, [C.c_int, C.POINTER(SkyParams), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), _F]),
+    "fspt_scene_update_environment_auto": (C.c_int, [_VP, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]),
+    "fspt_scene_update_environment_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32]),
+    "fspt_scene_update_sky": (C.c_int, [_VP, C.POINTER(SkyParams), C.c_uint32, C.c_uint32]),
+    "fspt_scene_last_sky_ms": (C.c_int, [_VP, _F, _F, _F, _U32, _U32, _U32]),
+    "fspt_multi_update_environment_auto": (C.c_int, [_VP, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]),
+    "fspt_multi_update_sky": (C.c_int, [_VP, C.POINTER(SkyParams), C.c_uint32, C.c_uint32]),
+    "fspt_env_box_sums_eval": (C.c_int, [C.c_int, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, _U32, C.c_uint32, C.POINTER(C.c_double)]),
     "fspt_multi_last_stage_ms": (C.c_int, [_VP, _F, C.c_uint32]),
     "fspt_device_memory": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fspt_last_error": (C.c_char_p, []),

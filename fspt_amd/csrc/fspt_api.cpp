@@ -734,6 +734,7 @@ int fspt_scene_destroy(fspt_scene *s) {
   fspt::appearance_release(s);
   fspt::pose_release(s);
   fspt::skin_release(s);
+  fspt::sky_release(s);
   delete s;
   return FSPT_OK;
 }

@@ -96,25 +96,6 @@ __global__ void k_ap_records(const float *__restrict__ mat, const float *__restr
   }
 }
 
-// device buffers of a transaction: freed unless taken
-struct Hold {
-  std::vector<void *> p;
-  ~Hold() { for (void *q : p) hipFree(q); }
-  hipError_t make(void **dst, size_t bytes) {
-    *dst = nullptr;
-    const hipError_t e = hipMalloc(dst, bytes ? bytes : 16);
-    if (e == hipSuccess) p.push_back(*dst); else *dst = nullptr;
-    return e;
-  }
-  void take(void *q) { p.erase(std::remove(p.begin(), p.end(), q), p.end()); }
-};
-
-int ap_fail(const char *fn, hipError_t e) {
-  (void)hipGetLastError();
-  fspt_set_error("%s: %s (scene unchanged)", fn, hipGetErrorString(e));
-  return e == hipErrorOutOfMemory ? FSPT_E_NOMEM : FSPT_E_HIP;
-}
-
 int ap_events(fspt_scene *s) {
   for (hipEvent_t &e : s->ap.ev) if (!e) HIP_TRY(hipEventCreate(&e));
   return FSPT_OK;
@@ -242,6 +223,33 @@ int appearance_materials(fspt_scene *s, const float *mat, const float *uv, const
   return FSPT_OK;
 }
 
+size_t env_tiled_texels(uint32_t w, uint32_t h) {
+#if FSPT_ENV_APRON
+  const uint32_t tx = (w + 6u) / 7u, ty = (h + 2u) / 3u;
+#else
+  const uint32_t tx = (w + TEX_TILE_W - 1) / TEX_TILE_W, ty = (h + TEX_TILE_H - 1) / TEX_TILE_H;
+#endif
+  return (size_t)tx * ty * 32u;
+}
+
+hipError_t env_tile_launch(const uint32_t *raw, uint32_t w, uint32_t h, uint32_t *dst, hipStream_t st) {
+  const size_t n_out = env_tiled_texels(w, h);
+#if FSPT_ENV_APRON
+  hipLaunchKernelGGL(k_ap_env_tile, dim3(ap_blocks(n_out)), dim3(AP_BS), 0, st, raw, w, h, (w + 6u) / 7u, n_out, dst);
+#else
+  hipLaunchKernelGGL(k_ap_tile_layer, dim3(ap_blocks(n_out)), dim3(AP_BS), 0, st, raw, w, h, (w + TEX_TILE_W - 1) / TEX_TILE_W, n_out, dst);
+#endif
+  return hipGetLastError();
+}
+
+void environment_swap(fspt_scene *s, void *n_env, uint64_t env_bytes, uint32_t w, uint32_t h, void *n_bins_d, uint32_t n_bins) {
+  void *old[2] = {s->env, s->bins};
+  s->env = n_env; s->bins = n_bins_d; s->env_bytes = env_bytes;
+  s->d.env = (const uint32_t *)s->env; s->d.bins = (const uint4 *)s->bins;
+  s->d.env_w = n_env ? w : 0; s->d.env_h = n_env ? h : 0; s->d.n_bins = n_bins;
+  for (void *o : old) hipFree(o);
+}
+
 int appearance_environment(fspt_scene *s, const uint8_t *env, uint32_t w, uint32_t h, const uint32_t *bins, uint32_t n_bins) {
   const char *fn = "fspt_scene_update_environment";
   fspt_scene::Appearance &A = s->ap;
@@ -256,38 +264,24 @@ int appearance_environment(fspt_scene *s, const uint8_t *env, uint32_t w, uint32
   if (e == hipSuccess) e = hipMemcpy(n_bins_d, bins, (size_t)n_bins * 16, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipEventRecord(A.ev[0], st);
   if (e == hipSuccess && env) {
-#if FSPT_ENV_APRON
-    const uint32_t tx = (w + 6u) / 7u, ty = (h + 2u) / 3u;
-#else
-    const uint32_t tx = (w + TEX_TILE_W - 1) / TEX_TILE_W, ty = (h + TEX_TILE_H - 1) / TEX_TILE_H;
-#endif
-    const size_t n_out = (size_t)tx * ty * 32u, raw_bytes = (size_t)w * h * 4;
-    env_bytes = n_out * 4;
+    const size_t raw_bytes = (size_t)w * h * 4;
+    env_bytes = env_tiled_texels(w, h) * 4;
     e = hold.make(&raw, raw_bytes);
     if (e == hipSuccess) e = hold.make(&n_env, env_bytes);
     if (e == hipSuccess) e = hipMemcpy(raw, env, raw_bytes, hipMemcpyHostToDevice);
     uploaded += raw_bytes;
     if (e == hipSuccess) {
-#if FSPT_ENV_APRON
-      hipLaunchKernelGGL(k_ap_env_tile, dim3(ap_blocks(n_out)), dim3(AP_BS), 0, st, (const uint32_t *)raw, w, h, tx, n_out, (uint32_t *)n_env);
-#else
-      hipLaunchKernelGGL(k_ap_tile_layer, dim3(ap_blocks(n_out)), dim3(AP_BS), 0, st, (const uint32_t *)raw, w, h, tx, n_out, (uint32_t *)n_env);
-#endif
+      e = env_tile_launch((const uint32_t *)raw, w, h, (uint32_t *)n_env, st);
       ++launches;
-      e = hipGetLastError();
     }
   }
   if (e == hipSuccess) e = hipEventRecord(A.ev[1], st);
   if (e == hipSuccess) e = hipEventSynchronize(A.ev[1]);
   if (e == hipSuccess) e = hipEventElapsedTime(&A.last_ms, A.ev[0], A.ev[1]);
   if (e != hipSuccess) return ap_fail(fn, e);
-  void *old[2] = {s->env, s->bins};
   hold.take(n_bins_d);
   if (n_env) hold.take(n_env);
-  s->env = n_env; s->bins = n_bins_d; s->env_bytes = env_bytes;
-  s->d.env = (const uint32_t *)s->env; s->d.bins = (const uint4 *)s->bins;
-  s->d.env_w = env ? w : 0; s->d.env_h = env ? h : 0; s->d.n_bins = n_bins;
-  for (void *o : old) hipFree(o);
+  environment_swap(s, n_env, env_bytes, w, h, n_bins_d, n_bins);
   A.last_launches = launches;
   A.last_uploaded = uploaded;
   return FSPT_OK;

@@ -13,6 +13,7 @@
 //   fspt_bvh_build.hip     the GPU BVH builder;  fspt_refit.hip  in-place refit and rebuild;  fspt_pose.hip  part transforms and skinning
 //   fspt_camera.hip        ray generation under an opt-in camera model (the rule: fspt_camera_model.hpp)
 //   fspt_appearance.hip    in-place appearance update: the texture-set, atlas and environment layouts and the material part of the hit records
+//   fspt_sky.hip           the sky generator and the environment's importance bins, built on the GPU
 #pragma once
 #include "../../include/fspt.h"
 #include "../../include/fspt_tuning.h"
@@ -135,6 +136,12 @@ struct fspt_scene {
     hipEvent_t ev[2] = {nullptr, nullptr};
     float last_ms = 0.0f;           // k_skin_transform of the last call
   } skin;
+  // fspt_scene_update_sky / _environment_auto / _environment_device (fspt_sky.hip): the last such call
+  struct Sky {
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    float sky_ms = 0.0f, bins_ms = 0.0f, tile_ms = 0.0f; // the generator | radiance, table, tree and the n_bins read-back | the tiling
+    uint32_t launches = 0, readbacks = 0, n_bins = 0;
+  } sky;
 };
 // Material texture sets: what fspt_scene_create and fspt_scene_update_materials derive from matTex's layer ids and
 // the per-layer "every texel equal" flags - the sets in first-appearance order, each triangle's set, a set's form under the
@@ -181,6 +188,39 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
 int appearance_materials(fspt_scene *s, const float *mat, const float *uv, const uint8_t *atlas, uint32_t res, uint32_t layers);
 int appearance_environment(fspt_scene *s, const uint8_t *env, uint32_t w, uint32_t h, const uint32_t *bins, uint32_t n_bins);
 void appearance_release(fspt_scene *s);
+// device buffers of a transaction: freed unless taken
+struct Hold {
+  std::vector<void *> p;
+  ~Hold() { for (void *q : p) hipFree(q); }
+  hipError_t make(void **dst, size_t bytes) {
+    *dst = nullptr;
+    const hipError_t e = hipMalloc(dst, bytes ? bytes : 16);
+    if (e == hipSuccess) p.push_back(*dst); else *dst = nullptr;
+    return e;
+  }
+  void take(void *q) { p.erase(std::remove(p.begin(), p.end(), q), p.end()); }
+};
+inline int ap_fail(const char *fn, hipError_t e) {
+  (void)hipGetLastError();
+  fspt_set_error("%s: %s (scene unchanged)", fn, hipGetErrorString(e));
+  return e == hipErrorOutOfMemory ? FSPT_E_NOMEM : FSPT_E_HIP;
+}
+// the environment's last two steps, shared by fspt_scene_update_environment and the GPU sky entries (fspt_sky.hip): the
+// tiled form of a raw w x h RGBE map (device memory; dst holds env_tiled_texels words), and the swap of the scene's
+// environment and bins for new device buffers (n_env NULL = no map), which frees the old ones
+size_t env_tiled_texels(uint32_t w, uint32_t h);
+hipError_t env_tile_launch(const uint32_t *raw, uint32_t w, uint32_t h, uint32_t *dst, hipStream_t st);
+void environment_swap(fspt_scene *s, void *n_env, uint64_t env_bytes, uint32_t w, uint32_t h, void *n_bins_d, uint32_t n_bins);
+// fspt_sky.hip.  Arguments are validated by the callers; `p` has a unit sun_dir.
+// sky_generate_run / env_bins_run / env_box_sums_run: the stand-alone entries' device side on the current device, host pointers.
+int sky_generate_run(const fspt_sky_params *p, uint32_t w, uint32_t h, uint8_t *rgbe_out, float *linear_out);
+int env_bins_run(const uint8_t *rgbe, uint32_t w, uint32_t h, uint32_t *bins, uint32_t cap, uint32_t *n_bins);
+int env_box_sums_run(const uint8_t *rgbe, uint32_t w, uint32_t h, const uint32_t *boxes, uint32_t n, double *out);
+// The scene entries' transaction (the call is ordered against the targets): the raw map is `env` (host memory, or the scene's
+// device memory when env_on_device) or, with `sky`, generated; bins are built from it on the device, it is tiled, and only
+// then are the scene's buffers swapped and s->sky filled in.
+int environment_gpu(fspt_scene *s, const char *fn, const uint8_t *env, bool env_on_device, const fspt_sky_params *sky, uint32_t w, uint32_t h);
+void sky_release(fspt_scene *s);
 // fspt_pose.hip.  pose_run: s->pose set, s->rf.stage allocated, the call ordered against the targets;
 // mats_host = n_parts x 30 floats (a | D | N).  Uploads them, runs k_pose_transform into s->rf.stage and waits.
 int pose_run(fspt_scene *s, const float *mats_host);

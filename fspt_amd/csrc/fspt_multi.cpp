@@ -239,6 +239,12 @@ int fspt_multi_update_materials(fspt_multi *m, const float *mat, const float *uv
 int fspt_multi_update_environment(fspt_multi *m, const uint8_t *env, uint32_t env_w, uint32_t env_h, const uint32_t *bins, uint32_t n_bins) {
   MULTI_EACH_SCENE(fspt_multi_update_environment, fspt_scene_update_environment(s, env, env_w, env_h, bins, n_bins));
 }
+int fspt_multi_update_environment_auto(fspt_multi *m, const uint8_t *env, uint32_t w, uint32_t h) {
+  MULTI_EACH_SCENE(fspt_multi_update_environment_auto, fspt_scene_update_environment_auto(s, env, w, h));
+}
+int fspt_multi_update_sky(fspt_multi *m, const fspt_sky_params *p, uint32_t w, uint32_t h) {
+  MULTI_EACH_SCENE(fspt_multi_update_sky, fspt_scene_update_sky(s, p, w, h));
+}
 int fspt_multi_rebuild_geometry(fspt_multi *m, const float *tri, const float *norm, uint32_t *order_out) {
   if (!m) { fspt_set_error("fspt_multi_rebuild_geometry: NULL handle"); return FSPT_E_INVALID; }
   std::vector<uint32_t> first, other;

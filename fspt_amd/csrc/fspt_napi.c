@@ -419,6 +419,65 @@ static napi_value SceneUpdateEnvironment(napi_env env, napi_callback_info info) 
   FSPT_OK_OR_THROW(fspt_scene_update_environment((fspt_scene *)h, (const uint8_t *)map, w, hh, (const uint32_t *)bins, (uint32_t)(nb / 4)));
   return undefined(env);
 }
+/* GPU sky.  A sky's parameters cross as a Float32Array(10) - sun_dir.xyz, turbidity, sun_intensity, sun_radius, gain,
+ * ground_albedo.rgb - and two counts; the library checks the ranges. */
+static int sky_params_arg(napi_env env, napi_value f, napi_value vs, napi_value ls, fspt_sky_params *p) {
+  void *d = NULL; size_t n = 0; uint32_t v = 0, l = 0;
+  if (typed(env, f, napi_float32_array, 0, &d, &n)) return -1;
+  if (n != 10) { napi_throw_range_error(env, NULL, "fspt_napi: a sky needs 10 floats (sun_dir, turbidity, sun_intensity, sun_radius, gain, ground_albedo)"); return -1; }
+  if (napi_get_value_uint32(env, vs, &v) != napi_ok || napi_get_value_uint32(env, ls, &l) != napi_ok) { napi_throw_type_error(env, NULL, "fspt_napi: a sky needs viewSamples and lightSamples"); return -1; }
+  const float *q = (const float *)d;
+  p->sun_dir[0] = q[0]; p->sun_dir[1] = q[1]; p->sun_dir[2] = q[2];
+  p->turbidity = q[3]; p->sun_intensity = q[4]; p->sun_radius = q[5]; p->gain = q[6];
+  p->ground_albedo[0] = q[7]; p->ground_albedo[1] = q[8]; p->ground_albedo[2] = q[9];
+  p->view_samples = v; p->light_samples = l;
+  return 0;
+}
+/* sceneUpdateSky(scene, params Float32Array(10), viewSamples, lightSamples, w, h): fspt_scene_update_sky.  The guard of sceneUpdateGeometry. */
+static napi_value SceneUpdateSky(napi_env env, napi_callback_info info) {
+  napi_value a[6]; void *h; uint32_t w = 0, hh = 0; fspt_sky_params p;
+  if (get_args(env, info, 6, a) || unwrap_k(env, a[0], H_SCENE, &h) || sky_params_arg(env, a[1], a[2], a[3], &p)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[4], &w)); NAPI_OK(napi_get_value_uint32(env, a[5], &hh));
+  FSPT_OK_OR_THROW(fspt_scene_update_sky((fspt_scene *)h, &p, w, hh));
+  return undefined(env);
+}
+/* sceneUpdateEnvironmentAuto(scene, env Uint8Array, envW, envH): fspt_scene_update_environment_auto - the bins are built on the GPU. */
+static napi_value SceneUpdateEnvironmentAuto(napi_env env, napi_callback_info info) {
+  napi_value a[4]; void *h, *map = NULL; size_t ne = 0; uint32_t w = 0, hh = 0;
+  if (get_args(env, info, 4, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  if (typed(env, a[1], napi_uint8_array, 0, &map, &ne)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[2], &w)); NAPI_OK(napi_get_value_uint32(env, a[3], &hh));
+  if ((uint64_t)ne != (uint64_t)w * hh * 4u) {
+    napi_throw_range_error(env, NULL, "fspt_napi: updateEnvironmentAuto needs envW * envH RGBE texels (env)");
+    return NULL;
+  }
+  FSPT_OK_OR_THROW(fspt_scene_update_environment_auto((fspt_scene *)h, (const uint8_t *)map, w, hh));
+  return undefined(env);
+}
+/* skyGenerate(device, params Float32Array(10), viewSamples, lightSamples, w, h) -> Uint8Array RGBE: fspt_sky_generate. */
+static napi_value SkyGenerate(napi_env env, napi_callback_info info) {
+  napi_value a[6], ab, ta; void *data; int32_t device = 0; uint32_t w = 0, hh = 0; fspt_sky_params p;
+  if (get_args(env, info, 6, a) || sky_params_arg(env, a[1], a[2], a[3], &p)) return NULL;
+  NAPI_OK(napi_get_value_int32(env, a[0], &device));
+  NAPI_OK(napi_get_value_uint32(env, a[4], &w)); NAPI_OK(napi_get_value_uint32(env, a[5], &hh));
+  FSPT_OK_OR_THROW(fspt_sky_generate(device, &p, w, hh, NULL, NULL)); /* (the refusals, before anything is allocated) */
+  NAPI_OK(napi_create_arraybuffer(env, (size_t)w * hh * 4, &data, &ab));
+  NAPI_OK(napi_create_typedarray(env, napi_uint8_array, (size_t)w * hh * 4, ab, 0, &ta));
+  FSPT_OK_OR_THROW(fspt_sky_generate(device, &p, w, hh, (uint8_t *)data, NULL));
+  return ta;
+}
+/* envBinsGpu(rgbe Uint8Array, w, h, device) -> Uint32Array: fspt_env_bins_gpu. */
+static napi_value EnvBinsGpu(napi_env env, napi_callback_info info) {
+  napi_value a[4], ab, ta; void *p, *data; size_t n; uint32_t w, h, nb = 0; int32_t device = 0;
+  if (get_args(env, info, 4, a) || typed(env, a[0], napi_uint8_array, 0, &p, &n)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[1], &w)); NAPI_OK(napi_get_value_uint32(env, a[2], &h)); NAPI_OK(napi_get_value_int32(env, a[3], &device));
+  if (n != (size_t)w * h * 4) { napi_throw_range_error(env, NULL, "fspt_napi: rgbe length != w*h*4"); return NULL; }
+  FSPT_OK_OR_THROW(fspt_env_bins_gpu((const uint8_t *)p, w, h, device, NULL, 0, &nb));
+  NAPI_OK(napi_create_arraybuffer(env, (size_t)nb * 16, &data, &ab));
+  NAPI_OK(napi_create_typedarray(env, napi_uint32_array, (size_t)nb * 4, ab, 0, &ta));
+  FSPT_OK_OR_THROW(fspt_env_bins_gpu((const uint8_t *)p, w, h, device, (uint32_t *)data, nb, &nb));
+  return ta;
+}
 static napi_value SceneSahCost(napi_env env, napi_callback_info info) {
   napi_value a[1], v; void *h; double cost = 0.0;
   if (get_args(env, info, 1, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
@@ -1480,7 +1539,7 @@ static napi_value AbiVersion(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
-      {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"sceneSetPose", SceneSetPose}, {"sceneUpdateTransforms", SceneUpdateTransforms}, {"sceneSetSkin", SceneSetSkin}, {"sceneUpdateSkin", SceneUpdateSkin}, {"targetCreate", TargetCreate},
+      {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"sceneUpdateSky", SceneUpdateSky}, {"sceneUpdateEnvironmentAuto", SceneUpdateEnvironmentAuto}, {"skyGenerate", SkyGenerate}, {"envBinsGpu", EnvBinsGpu}, {"sceneSetPose", SceneSetPose}, {"sceneUpdateTransforms", SceneUpdateTransforms}, {"sceneSetSkin", SceneSetSkin}, {"sceneUpdateSkin", SceneUpdateSkin}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
       {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setCameraModel", SetCameraModel}, {"cameraModel", CameraModel}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},

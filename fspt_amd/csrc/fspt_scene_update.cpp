@@ -1,5 +1,5 @@
 // fspt_scene_update.cpp - every entry that changes a live scene, or reports on such a change: in-place geometry update
-// (DESIGN 8.6), rebuild (8.7), appearance update (8.13), part transforms (8.14), skinning (8.16), the motion origin (8.8)
+// (DESIGN 8.6), rebuild (8.7), appearance update (8.13), part transforms (8.14), skinning (8.16), the GPU sky (8.17), the motion origin (8.8)
 // and the read-outs that go with them.  What the families share stands once, first; every refusal names the calling entry.
 #include "fspt_internal.hpp"
 
@@ -476,6 +476,104 @@ int fspt_scene_update_environment(fspt_scene *s, const uint8_t *env, uint32_t en
   const int rc = begin_scene_change(s);
   if (rc) return rc;
   return fspt::appearance_environment(s, env, env_w, env_h, bins, n_bins);
+}
+
+// ---------------------------------------------------------------------------
+// GPU sky and GPU-built bins (kernels in fspt_sky.hip)
+// ---------------------------------------------------------------------------
+static int check_map_size(const char *fn, uint32_t w, uint32_t h) {
+  if (w < 1 || w > 65535 || h < 1 || h > 65535) { fspt_set_error("%s: a map of %u x %u texels, each side must lie in [1, 65535]", fn, w, h); return FSPT_E_INVALID; }
+  return FSPT_OK;
+}
+
+// fspt_tuning.h's rule, on the host alone.  *out = the parameters with a unit sun_dir (normalised in float64).
+static int sky_check(const char *fn, const fspt_sky_params *p, uint32_t w, uint32_t h, fspt_sky_params *out) {
+  if (!p) { fspt_set_error("%s: NULL params", fn); return FSPT_E_INVALID; }
+  if (const int rc = check_map_size(fn, w, h)) return rc;
+  double q = 0.0;
+  for (int i = 0; i < 3; ++i) {
+    if (!std::isfinite(p->sun_dir[i])) { fspt_set_error("%s: sun_dir[%d] is not finite", fn, i); return FSPT_E_INVALID; }
+    q += (double)p->sun_dir[i] * (double)p->sun_dir[i];
+  }
+  if (!(q > 0.0)) { fspt_set_error("%s: sun_dir is zero", fn); return FSPT_E_INVALID; }
+  if (!(p->turbidity >= 0.0f && p->turbidity <= 64.0f)) { fspt_set_error("%s: turbidity = %g, must lie in [0, 64]", fn, (double)p->turbidity); return FSPT_E_INVALID; }
+  if (!(p->sun_intensity >= 0.0f) || !std::isfinite(p->sun_intensity)) { fspt_set_error("%s: sun_intensity = %g, must be finite and >= 0", fn, (double)p->sun_intensity); return FSPT_E_INVALID; }
+  if (!(p->sun_radius > 0.0f && p->sun_radius <= 0.5f)) { fspt_set_error("%s: sun_radius = %g, must lie in (0, 0.5]", fn, (double)p->sun_radius); return FSPT_E_INVALID; }
+  if (!(p->gain >= 0.0f) || !std::isfinite(p->gain)) { fspt_set_error("%s: gain = %g, must be finite and >= 0", fn, (double)p->gain); return FSPT_E_INVALID; }
+  for (int i = 0; i < 3; ++i)
+    if (!(p->ground_albedo[i] >= 0.0f && p->ground_albedo[i] <= 1.0f)) { fspt_set_error("%s: ground_albedo[%d] = %g, must lie in [0, 1]", fn, i, (double)p->ground_albedo[i]); return FSPT_E_INVALID; }
+  if (p->view_samples < 1 || p->view_samples > FSPT_SKY_MAX_VIEW_SAMPLES) { fspt_set_error("%s: view_samples = %u, must lie in [1, %d]", fn, p->view_samples, FSPT_SKY_MAX_VIEW_SAMPLES); return FSPT_E_INVALID; }
+  if (p->light_samples < 1 || p->light_samples > FSPT_SKY_MAX_LIGHT_SAMPLES) { fspt_set_error("%s: light_samples = %u, must lie in [1, %d]", fn, p->light_samples, FSPT_SKY_MAX_LIGHT_SAMPLES); return FSPT_E_INVALID; }
+  *out = *p;
+  const double len = std::sqrt(q);
+  for (int i = 0; i < 3; ++i) out->sun_dir[i] = (float)((double)p->sun_dir[i] / len);
+  return FSPT_OK;
+}
+
+int fspt_sky_generate(int device, const fspt_sky_params *p, uint32_t w, uint32_t h, uint8_t *rgbe_out, float *linear_out) {
+  fspt_sky_params n;
+  int rc = sky_check("fspt_sky_generate", p, w, h, &n);
+  if (rc || (rc = check_device(device))) return rc;
+  if (!rgbe_out && !linear_out) return FSPT_OK;
+  return fspt::sky_generate_run(&n, w, h, rgbe_out, linear_out);
+}
+
+int fspt_env_bins_gpu(const uint8_t *rgbe, uint32_t w, uint32_t h, int device, uint32_t *bins, uint32_t cap, uint32_t *n_bins) {
+  if (!rgbe || !w || !h || !n_bins) { fspt_set_error("fspt_env_bins_gpu: NULL/empty argument"); return FSPT_E_INVALID; }
+  int rc = check_map_size("fspt_env_bins_gpu", w, h);
+  if (rc || (rc = check_device(device))) return rc;
+  return fspt::env_bins_run(rgbe, w, h, bins, cap, n_bins);
+}
+
+int fspt_env_box_sums_eval(int device, const uint8_t *rgbe, uint32_t w, uint32_t h, const uint32_t *boxes, uint32_t n, double *out) {
+  if (!rgbe || !boxes || !out || !n) { fspt_set_error("fspt_env_box_sums_eval: NULL/empty argument"); return FSPT_E_INVALID; }
+  int rc = check_map_size("fspt_env_box_sums_eval", w, h);
+  if (rc) return rc;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t *b = boxes + (size_t)i * 4;
+    if (b[0] > b[2] || b[2] > w || b[1] > b[3] || b[3] > h) { fspt_set_error("fspt_env_box_sums_eval: box %u = (%u, %u, %u, %u) is not inside the %u x %u map", i, b[0], b[1], b[2], b[3], w, h); return FSPT_E_INVALID; }
+  }
+  if ((rc = check_device(device))) return rc;
+  return fspt::env_box_sums_run(rgbe, w, h, boxes, n, out);
+}
+
+static int update_environment_gpu(fspt_scene *s, const uint8_t *env, bool on_device, const fspt_sky_params *sky, uint32_t w, uint32_t h, const char *fn) {
+  if (!s) { fspt_set_error("%s: NULL scene", fn); return FSPT_E_INVALID; }
+  fspt_sky_params n;
+  int rc = FSPT_OK;
+  if (sky) {
+    if ((rc = sky_check(fn, sky, w, h, &n))) return rc;
+  } else {
+    if (!env) { fspt_set_error("%s: env is NULL (fspt_scene_update_environment takes a scene's map away)", fn); return FSPT_E_INVALID; }
+    if ((rc = check_map_size(fn, w, h))) return rc;
+    if (on_device && (uintptr_t)env % 4) { fspt_set_error("%s: env must be 4-byte aligned", fn); return FSPT_E_INVALID; }
+  }
+  if ((rc = begin_scene_change(s))) return rc;
+  return fspt::environment_gpu(s, fn, env, on_device, sky ? &n : nullptr, w, h);
+}
+
+int fspt_scene_update_environment_auto(fspt_scene *s, const uint8_t *env, uint32_t w, uint32_t h) {
+  return update_environment_gpu(s, env, false, nullptr, w, h, "fspt_scene_update_environment_auto");
+}
+
+int fspt_scene_update_environment_device(fspt_scene *s, const uint8_t *env, uint32_t w, uint32_t h) {
+  return update_environment_gpu(s, env, true, nullptr, w, h, "fspt_scene_update_environment_device");
+}
+
+int fspt_scene_update_sky(fspt_scene *s, const fspt_sky_params *p, uint32_t w, uint32_t h) {
+  if (!p) { fspt_set_error("fspt_scene_update_sky: NULL params"); return FSPT_E_INVALID; }
+  return update_environment_gpu(s, nullptr, false, p, w, h, "fspt_scene_update_sky");
+}
+
+int fspt_scene_last_sky_ms(fspt_scene *s, float *sky_ms, float *bins_ms, float *tile_ms, uint32_t *launches, uint32_t *readbacks, uint32_t *n_bins) {
+  if (!s) { fspt_set_error("fspt_scene_last_sky_ms: NULL scene"); return FSPT_E_INVALID; }
+  if (sky_ms) *sky_ms = s->sky.sky_ms;
+  if (bins_ms) *bins_ms = s->sky.bins_ms;
+  if (tile_ms) *tile_ms = s->sky.tile_ms;
+  if (launches) *launches = s->sky.launches;
+  if (readbacks) *readbacks = s->sky.readbacks;
+  if (n_bins) *n_bins = s->sky.n_bins;
+  return FSPT_OK;
 }
 
 int fspt_scene_read_appearance(fspt_scene *s, int what, void *out, uint64_t cap, uint64_t *bytes) {

@@ -322,6 +322,27 @@ function cameraModelArgs(params) {
   if (typeof ipd !== 'number' || !(f(ipd) >= 0 && Number.isFinite(f(ipd)))) throw new RangeError('setCameraModel: ipd must be a finite number >= 0');
   return [code, angle, ipd];
 }
+/** fspt_tuning.h FSPT_SKY_*: the defaults of the sky model (DESIGN 8.17) */
+const SKY_DEFAULTS = { turbidity: 1, sunIntensity: 20, sunRadius: 0.02, gain: 1, groundAlbedo: 0.3, viewSamples: 16, lightSamples: 8, width: 1024, height: 512 };
+/** {sunDir, ...} -> what the addon takes: the ten floats of fspt_sky_params, the two counts and the size (ranges: the library's) */
+function skyArgs(fn, o) {
+  if (o == null || typeof o !== 'object' || !Array.isArray(o.sunDir) && !(o.sunDir instanceof Float32Array) || o.sunDir.length !== 3) throw new TypeError(fn + ': expected {sunDir: [x, y, z], ...}');
+  for (const key of Object.keys(o)) if (key !== 'sunDir' && !(key in SKY_DEFAULTS)) throw new TypeError(fn + ': unknown parameter ' + key);
+  const p = Object.assign({}, SKY_DEFAULTS, o);
+  const alb = typeof p.groundAlbedo === 'number' ? [p.groundAlbedo, p.groundAlbedo, p.groundAlbedo] : p.groundAlbedo;
+  if (!alb || alb.length !== 3) throw new RangeError(fn + ': groundAlbedo must be a number or [r, g, b]');
+  for (const key of ['viewSamples', 'lightSamples', 'width', 'height']) if (!Number.isInteger(p[key]) || p[key] < 0 || p[key] > 0xFFFFFFFF) throw new RangeError(fn + ': ' + key + ' must be a count');
+  const params = Float32Array.of(p.sunDir[0], p.sunDir[1], p.sunDir[2], p.turbidity, p.sunIntensity, p.sunRadius, p.gain, alb[0], alb[1], alb[2]);
+  return { params, viewSamples: p.viewSamples, lightSamples: p.lightSamples, width: p.width, height: p.height };
+}
+/** a generated sky as {rgbe Uint8Array, width, height} on HIP device `device` (fspt_sky_generate): what buildScene takes as env */
+function skyGenerate(o, device) {
+  const k = skyArgs('skyGenerate', o);
+  return { rgbe: addon.skyGenerate(device || 0, k.params, k.viewSamples, k.lightSamples, k.width, k.height), width: k.width, height: k.height };
+}
+/** env_sampler.js's bins of an RGBE map, built on HIP device `device` (fspt_env_bins_gpu; addon.envBins is the CPU's) */
+function envBinsGpu(rgbe, w, h, device) { return addon.envBinsGpu(rgbe, w, h, device || 0); }
+
 function pipelineCode(name) {
   if (PIPELINE_CODES[name] !== undefined) return PIPELINE_CODES[name];
   if (Number.isInteger(name) && name >= 0 && name <= 2) return name;
@@ -656,6 +677,23 @@ class PathTracer {
     }
     addon.sceneUpdateEnvironment(this._scene, env == null ? null : env, env == null ? 0 : envW, env == null ? 0 : envH, bins);
   }
+  /** a new environment whose bins the GPU builds from the uploaded map: {env (Uint8Array RGBE, envW * envH texels), envW, envH}
+   *  (fspt_scene_update_environment_auto, DESIGN 8.17); state stays as for updateMaterials.  (updateEnvironment keeps asking for
+   *  bins: a host that forgot them is told so.) */
+  updateEnvironmentAuto(o) {
+    if (o == null || typeof o !== 'object') throw new TypeError('updateEnvironmentAuto: expected {env, envW, envH}');
+    const { env, envW, envH } = o;
+    if (!Number.isInteger(envW) || !Number.isInteger(envH) || envW < 1 || envH < 1) throw new RangeError('updateEnvironmentAuto: an env needs envW >= 1 and envH >= 1');
+    if (!(env instanceof Uint8Array) || env.length !== envW * envH * 4) throw new RangeError('updateEnvironmentAuto: env must be a Uint8Array of ' + envW + ' x ' + envH + ' x 4 bytes');
+    addon.sceneUpdateEnvironmentAuto(this._scene, env, envW, envH);
+  }
+  /** the environment replaced by a sky generated, binned and tiled on the GPU: {sunDir [x, y, z], width (1024), height (512),
+   *  turbidity, sunIntensity, sunRadius, gain, groundAlbedo (a number or [r, g, b]), viewSamples, lightSamples} (skyArgs'
+   *  defaults; fspt_scene_update_sky, DESIGN 8.17); state stays as for updateMaterials */
+  updateSky(o) {
+    const k = skyArgs('updateSky', o);
+    addon.sceneUpdateSky(this._scene, k.params, k.viewSamples, k.lightSamples, k.width, k.height);
+  }
   /** SAH cost of the tree with its current boxes relative to the root's area (fspt_scene_sah_cost) */
   sahCost() { return addon.sceneSahCost(this._scene); }
   /** 'wavefront' (batches of ticks), 'stream' (fixed pool of live paths), 'megakernel' (include/fspt_tuning.h) */
@@ -764,5 +802,5 @@ class MultiPathTracer {
 // memory later scenes may spend on interleaved material textures (fspt_set_texture_interleave_budget; results do not depend on it)
 function setTextureInterleaveBudget(bytes) { addon.setTextureInterleaveBudget(bytes); }
 
-module.exports = { addon, setTextureInterleaveBudget, MultiPathTracer, AtlasLayers, resolveMaterial, readMtl, mergeSceneProps, resampleImage, packReferenceScene, buildScene,
+module.exports = { addon, setTextureInterleaveBudget, skyGenerate, envBinsGpu, SKY_DEFAULTS, MultiPathTracer, AtlasLayers, resolveMaterial, readMtl, mergeSceneProps, resampleImage, packReferenceScene, buildScene,
   PathTracer, saveBlob, loadBlob };

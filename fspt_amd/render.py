@@ -48,6 +48,35 @@ def parse_camera(spec):
     return kw
 
 
+def parse_sky(sky, sky_to=None, size="1024x512"):
+    """--sky AZIMUTH,ELEVATION[,TURBIDITY] (degrees; azimuth from +x towards +z), --sky-to AZIMUTH,ELEVATION and --sky-size WxH
+    as a function of s in [0, 1] - the position in the sequence - that returns Scene.update_sky's arguments; None without --sky"""
+    if sky is None:
+        return None
+
+    def numbers(text, flag, counts):
+        try:
+            v = [float(x) for x in text.split(",")]
+        except ValueError:
+            v = []
+        if len(v) not in counts or not all(np.isfinite(v)):
+            raise ValueError(f"{flag} takes {' or '.join(str(c) for c in counts)} finite numbers separated by commas, got {text!r}")
+        return v
+
+    a = numbers(sky, "--sky", (2, 3))
+    b = numbers(sky_to, "--sky-to", (2,)) if sky_to is not None else a[:2]
+    try:
+        w, h = (int(x) for x in size.lower().split("x"))
+    except ValueError:
+        raise ValueError(f"--sky-size takes WxH, got {size!r}") from None
+    turbidity = a[2] if len(a) == 3 else 1.0
+
+    def at(s):
+        az, el = a[0] + (b[0] - a[0]) * s, a[1] + (b[1] - a[1]) * s
+        return dict(sun_dir=S.sun_direction(az, el), width=w, height=h, turbidity=turbidity)
+    return at
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--camera", default="pinhole", metavar="MODEL",
@@ -102,7 +131,19 @@ def main(argv=None):
     ap.add_argument("--adaptive", type=float, default=None, metavar="REL_MSE",
                     help="adaptive sampling: stop a 32x32 tile once its estimated relative MSE is below REL_MSE (--spp = the most)")
     ap.add_argument("--sample-map", default=None, help="with --adaptive: write the ticks per pixel as a grey PNG")
+    ap.add_argument("--sky", default=None, metavar="AZIMUTH,ELEVATION[,TURBIDITY]",
+                    help="replace the scene's environment by a sky generated on the GPU (DESIGN 8.17): the sun's azimuth (from +x "
+                         "towards +z) and elevation in degrees, and the turbidity (default 1)")
+    ap.add_argument("--sky-to", default=None, metavar="AZIMUTH,ELEVATION",
+                    help="with --sky and --frames: the sun moves linearly to here over the sequence")
+    ap.add_argument("--sky-size", default="1024x512", metavar="WxH", help="texels of the generated sky")
     args = ap.parse_args(argv)
+    try:
+        sky_at = parse_sky(args.sky, args.sky_to, args.sky_size)
+    except ValueError as e:
+        ap.error(str(e))
+    if args.sky_to is not None and not (args.sky and args.scene and args.frames):
+        ap.error("--sky-to needs --sky, --scene and --frames")
     try:
         camera = parse_camera(args.camera)
     except ValueError as e:
@@ -164,6 +205,8 @@ def main(argv=None):
             kw.update(camera=camera)
         if args.frames:
             a, b = (int(x) for x in args.frames.split(":"))
+            if sky_at is not None:
+                kw.update(sky=lambda n: sky_at((n - a) / max(b - 1 - a, 1)))
             t0 = time.perf_counter()
             out = F.render_sequence(args.scene, range(a, b), args.out, args.width, args.height, args.assets, bvh=args.bvh,
                                     rebuild_above=args.rebuild_above,
@@ -173,6 +216,8 @@ def main(argv=None):
             print(f"{len(out)} frames in {time.perf_counter() - t0:.2f} s:", *out)
         else:
             arrays, settings = F.load_scene_file(args.scene, args.assets, bvh=args.bvh)
+            if sky_at is not None:
+                arrays = F.arrays_with_sky(arrays, **sky_at(0.0))
             settings["exposure"] = settings["exposure"] * args.exposure
             rgba, rad = F.render_frame(arrays, settings, args.width, args.height, **kw)
             if args.hdr:
@@ -195,6 +240,9 @@ def main(argv=None):
             ap.error(str(e))
     if args.sampler != "reference":
         pt.set_sampler(args.sampler, args.sampler_seed)
+    if sky_at is not None:
+        pt.update_sky(**sky_at(0.0))
+        print("sky: {n_bins} bins; generated in {sky_ms:.2f} ms, binned in {bins_ms:.2f} ms, tiled in {tile_ms:.2f} ms".format(**pt.last_sky()))
     if args.lights:
         pt.set_lights("emitters", args.emitter_fraction)
     if args.auto_exposure is not None:

@@ -289,15 +289,76 @@ def get_material(prop, packer, images=None, group_material=None, base_path=""):
 _NORMALS_MODE = {None: 0, "flat": 0, "smooth": 1, "mesh": 2}
 
 
-def env_bins(env_rgbe, w, h):
-    """ProcessEnvRadiance (env_sampler.js) through the native builder."""
+def env_bins(env_rgbe, w, h, device=None):
+    """ProcessEnvRadiance (env_sampler.js) through the native builder; with a HIP device ordinal the same bins from the GPU's
+    summed-area table (fspt_env_bins_gpu)."""
     lib = L.lib()
     env_rgbe = np.ascontiguousarray(env_rgbe, dtype=np.uint8).reshape(-1)
+    w, h = int(w), int(h)
+    if w < 0 or h < 0 or env_rgbe.size != w * h * 4:
+        raise ValueError(f"env_bins: env has {env_rgbe.size} bytes, {w} x {h} RGBE texels need {w * h * 4}")
     n = C.c_uint32(0)
+    if device is not None:
+        # one build: leaves are disjoint boxes of area >= 1, so w * h bins always fit; a typical map has a few dozen
+        cap = min(w * h, 1 << 16)
+        bins = np.zeros(max(cap, 1) * 4, dtype=np.uint32)
+        L.check(lib.fspt_env_bins_gpu(L.u8ptr(env_rgbe), w, h, int(device), L.u32ptr(bins), cap, C.byref(n)))
+        if n.value > cap:
+            bins = np.zeros(n.value * 4, dtype=np.uint32)
+            L.check(lib.fspt_env_bins_gpu(L.u8ptr(env_rgbe), w, h, int(device), L.u32ptr(bins), n.value, C.byref(n)))
+        return bins[:n.value * 4].copy()
     L.check(lib.fspt_env_bins(L.u8ptr(env_rgbe), w, h, None, 0, C.byref(n)))
     bins = np.zeros(n.value * 4, dtype=np.uint32)
     L.check(lib.fspt_env_bins(L.u8ptr(env_rgbe), w, h, L.u32ptr(bins), n.value, C.byref(n)))
     return bins
+
+
+# fspt_tuning.h FSPT_SKY_*: the defaults of the sky model (DESIGN 8.17)
+SKY_DEFAULTS = dict(turbidity=1.0, sun_intensity=20.0, sun_radius=0.02, gain=1.0, ground_albedo=(0.3, 0.3, 0.3),
+                    view_samples=16, light_samples=8)
+
+
+def sky_params(sun_dir, **params):
+    """fspt_sky_params from a sun direction (any length; the library normalises it) and SKY_DEFAULTS overridden by `params`;
+    ground_albedo may be one number.  Ranges are checked by the library."""
+    unknown = set(params) - set(SKY_DEFAULTS)
+    if unknown:
+        raise TypeError(f"sky: unknown parameter(s) {sorted(unknown)}; known: {sorted(SKY_DEFAULTS)}")
+    p = dict(SKY_DEFAULTS, **params)
+    sun = np.asarray(sun_dir, dtype=np.float32).reshape(-1)
+    if sun.size != 3:
+        raise ValueError(f"sky: sun_dir has {sun.size} components, not 3")
+    alb = np.asarray(p["ground_albedo"], dtype=np.float32).reshape(-1)
+    if alb.size == 1:
+        alb = np.repeat(alb, 3)
+    if alb.size != 3:
+        raise ValueError(f"sky: ground_albedo has {alb.size} components, not 1 or 3")
+    for k in ("view_samples", "light_samples"):
+        if int(p[k]) != p[k] or not 0 <= int(p[k]) < 2 ** 32:
+            raise ValueError(f"sky: {k} = {p[k]!r} is not a count")
+    return L.SkyParams((C.c_float * 3)(*sun), float(p["turbidity"]), float(p["sun_intensity"]), float(p["sun_radius"]),
+                       float(p["gain"]), (C.c_float * 3)(*alb), int(p["view_samples"]), int(p["light_samples"]))
+
+
+def sun_direction(azimuth_deg, elevation_deg):
+    """The unit vector towards a sun at `azimuth_deg` (from +x towards +z) and `elevation_deg` above the horizon."""
+    a, e = math.radians(float(azimuth_deg)), math.radians(float(elevation_deg))
+    return (math.cos(a) * math.cos(e), math.sin(e), math.sin(a) * math.cos(e))
+
+
+def sky(sun_dir, w, h, device=0, linear=False, **params):
+    """A physically based sky as a w x h equirect environment, generated on HIP device `device` (fspt_sky_generate, DESIGN
+    8.17): single-scattering Rayleigh + Mie for a sun towards `sun_dir`, plus the lit ground and the sun's disc.  Returns
+    (rgbe uint8 [w*h*4], w, h) like synthetic_env; with linear=True (rgbe, w, h, radiance float32 [h, w, 3])."""
+    p = sky_params(sun_dir, **params)
+    w, h = int(w), int(h)
+    if not (0 <= w < 2 ** 32 and 0 <= h < 2 ** 32):
+        raise ValueError(f"sky: {w} x {h} is not a map size")
+    n = w * h if 1 <= w <= 65535 and 1 <= h <= 65535 else 0  # (the library refuses other sizes before it writes)
+    rgbe = np.zeros(n * 4, np.uint8)
+    lin = np.zeros((h if n else 0, w if n else 0, 3), np.float32) if linear else None
+    L.check(L.lib().fspt_sky_generate(int(device), C.byref(p), w, h, L.u8ptr(rgbe), None if lin is None else L.fptr(lin)))
+    return (rgbe, w, h, lin) if linear else (rgbe, w, h)
 
 
 def _rot_array(rot):

@@ -273,8 +273,25 @@ def _parse_order_parts(base):
     return out
 
 
+def arrays_with_sky(arrays, sun_dir, width=1024, height=512, device=0, **params):
+    """`arrays` under a generated sky instead of its environment: scene.sky's bytes and the GPU's bins of them -
+    what Scene.update_sky makes of a live scene, for a scene that is yet to be created"""
+    import dataclasses
+    rgbe, w, h = S.sky(sun_dir, width, height, device=device, **params)
+    return dataclasses.replace(arrays, env=rgbe, env_w=w, env_h=h, bins=S.env_bins(rgbe, w, h, device=device))
+
+
+def _sequence_sky(sky, k, n):
+    """frame n's sky (the k-th frame of the sequence): `sky` is a list of parameter dicts, one per frame, or a callable of the
+    frame number; a dict holds Scene.update_sky's arguments (sun_dir, width, height and the model's parameters)"""
+    d = sky(n) if callable(sky) else sky[k]
+    if not isinstance(d, dict) or "sun_dir" not in d:
+        raise ValueError(f"render_sequence: the sky of frame {n} must be a dict with a sun_dir, got {d!r}")
+    return dict(d)
+
+
 def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", rebuild_above=None,
-                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, camera=None, **kw):
+                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, camera=None, sky=None, **kw):
     """frame=N sequencing (main.js:851-866, 966-969): for every N in `frames` load `scene_pattern.format(frame=N)`
     (the per-frame scene JSON the reference's server hands out for `?frame=N`), render it, write
     `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1.
@@ -295,7 +312,7 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     above, and the pose is re-set from what that frame uploaded.  The pictures are NOT bit-equal to the parse path's: there
     the transform is applied in float64 to the OBJ's vertices and rounded once, here a float32 matrix is applied in float32
     to the rest frame's float32 triangles - which is why it is opt-in.
-    on_frame(N, "build" | "refit" | "rebuild" | "appearance" | "pose") reports what a frame did.
+    on_frame(N, "build" | "refit" | "rebuild" | "appearance" | "pose" | "sky") reports what a frame did.
     temporal (bvh="refit" only): True or a dict of PathTracer.temporal_accumulate's parameters, plus "atrous": K
     for K a-trous iterations on the result.  Every frame then follows the protocol motion_begin, update_geometry, clear and
     render, temporal_accumulate, and the picture written is temporal_draw of the result (`denoise`, the firefly filter of
@@ -314,7 +331,11 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     bloom: True or a dict of PathTracer.set_bloom's parameters; every tracer gets set_bloom() before its first
     frame, and each frame's one drawing blooms what it draws.
     camera: None or a dict of PathTracer.set_camera_model's arguments; every tracer gets set_camera_model()
-    before its first frame (not with temporal or adaptive)."""
+    before its first frame (not with temporal or adaptive).
+    sky: None, a list of dicts (one per frame) or a callable of the frame number that returns one: Scene.update_sky's
+    arguments (sun_dir, width, height, the model's parameters).  Every frame's environment is then that generated sky, whatever
+    the scene file names.  With bvh="refit" the kept tracer's scene gets update_sky once per frame - nothing but the light is
+    made again, on the GPU - and a kept frame reports "sky"; every other bvh builds each frame's scene under arrays_with_sky."""
     from PIL import Image
     camera = _camera_model_params(camera, kw.get("adaptive"), None if temporal is None or temporal is False else temporal)
     auto_exposure = _auto_exposure_params(auto_exposure, SEQUENCE_ADAPT if bvh == "refit" else None)
@@ -356,6 +377,8 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     if bvh != "refit":
         for n in frames:
             arrays, settings = load_scene_file(scene_pattern.format(frame=n), asset_root, bvh=bvh, device=device)
+            if sky is not None:
+                arrays = arrays_with_sky(arrays, device=device, **_sequence_sky(sky, len(written), n))
             rgba, _ = render_frame(arrays, settings, width, height, auto_exposure=auto_exposure, bloom=bloom, camera=camera, **kw)
             if on_frame:
                 on_frame(n, "build")
@@ -409,6 +432,8 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                         if rest_json is not None:
                             part = _parse_order_parts(base)[np.asarray(leaf_order, np.int64)]
                             pt.scene.set_pose(part, *S.geometry_in_leaf_order(leaf_order, g.tri, g.norm), n_parts=len(S.merge_scene_props(frame_json)))
+                    if sky is not None:  # (the scene file's environment is not this sequence's light)
+                        changes = {k: v for k, v in changes.items() if k not in ("env", "bins")}
                     if changes:
                         #  what differs goes to the live scene in place: tracer, history and exposure stay
                         if {"mat", "uv", "atlas"} & set(changes):
@@ -444,6 +469,9 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                     pt.set_auto_exposure(True, **auto_exposure)
                 if bloom is not None:
                     pt.set_bloom(True, **bloom)
+            if sky is not None:
+                pt.update_sky(**_sequence_sky(sky, len(written), n))
+                how = "sky" if how != "build" else how
             if temporal is None:
                 rgba, _ = _render_on(pt, settings, **opt)
             else:

@@ -351,6 +351,13 @@ def camera_model_params(model="pinhole", angle=None, ipd=None):
 DENOISE_DEFAULTS = {"iterations": 4, "sigma_color": 4.0, "sigma_normal": 32.0, "sigma_depth": 0.05}
 
 
+def _map_side(fn, v):
+    """A map's width or height as the uint32 the library takes (it checks the range 1..65535 itself)"""
+    if int(v) != v or not 0 <= int(v) < 2 ** 32:
+        raise ValueError(f"{fn}: {v!r} is not a map size")
+    return int(v)
+
+
 def _host_geometry(fn, n, tri, norm):
     """(tri, norm) as contiguous float32 host arrays of n x 9 and n x 27 elements (norm may be None)"""
     tri = np.ascontiguousarray(tri, dtype=np.float32)
@@ -697,11 +704,61 @@ class Scene:
                 raise ValueError(f"{fn}: env has {env.size} bytes, {w} x {h} RGBE texels need {w * h * 4}")
         return (None if env is None else L.u8ptr(env), w, h, L.u32ptr(bins), bins.size // 4), (env, bins)
 
-    def update_environment(self, env, env_w, env_h, bins):
+    @staticmethod
+    def _environment_auto_args(fn, env, env_w, env_h, device):
+        """(on device, pointer, w, h, keep) of an environment whose bins the GPU builds: host RGBE bytes, or - `device` not
+        None - a contiguous uint8 tensor on that device"""
+        w, h = int(env_w), int(env_h)
+        if env is None:
+            raise ValueError(f"{fn}: bins are required (scene.env_bins) when there is no map to build them from")
+        if not (0 <= w < 2 ** 32 and 0 <= h < 2 ** 32):
+            raise ValueError(f"{fn}: {w} x {h} is not a map size")
+        if hasattr(env, "data_ptr") and getattr(env, "is_cuda", False):
+            import torch
+            if device is None:
+                raise TypeError(f"{fn}: a device tensor needs a single scene; this host takes host arrays")
+            if env.dtype != torch.uint8 or not env.is_contiguous():
+                raise TypeError(f"{fn}: env must be a contiguous uint8 tensor")
+            if env.device.index != device:
+                raise ValueError(f"{fn}: env lives on {env.device}, the scene on device {device}")
+            if env.numel() != w * h * 4:
+                raise ValueError(f"{fn}: env has {env.numel()} bytes, {w} x {h} RGBE texels need {w * h * 4}")
+            torch.cuda.current_stream(device).synchronize()  # whatever wrote the tensor has finished
+            return True, C.c_void_p(env.data_ptr()), w, h, env
+        env = np.ascontiguousarray(env, dtype=np.uint8)
+        if env.size != w * h * 4:
+            raise ValueError(f"{fn}: env has {env.size} bytes, {w} x {h} RGBE texels need {w * h * 4}")
+        return False, L.u8ptr(env), w, h, env
+
+    def update_environment(self, env, env_w, env_h, bins=None):
         """A new environment map (RGBE in RGBA8, env_w * env_h texels; None = black) and its importance bins (scene.env_bins),
-        tiled on the GPU (fspt_scene_update_environment); everything else as update_materials."""
+        tiled on the GPU (fspt_scene_update_environment); everything else as update_materials.  bins=None: the
+        bins are built on the GPU from the uploaded map (fspt_scene_update_environment_auto), and `env` may be a
+        uint8 torch tensor on the scene's device, which is then read in place (fspt_scene_update_environment_device)."""
+        if bins is None:
+            on_dev, ptr, w, h, keep = self._environment_auto_args("update_environment", env, env_w, env_h, getattr(self, "device", None))
+            fn = L.lib().fspt_scene_update_environment_device if on_dev else L.lib().fspt_scene_update_environment_auto
+            L.check(fn(self._h, ptr, w, h))
+            return
         args, keep = self._environment_args("update_environment", env, env_w, env_h, bins)
         L.check(L.lib().fspt_scene_update_environment(self._h, *args))
+
+    def update_sky(self, sun_dir, width=1024, height=512, **params):
+        """Replace the environment by a generated sky (scene.sky's model and parameters) of width x height texels: generated,
+        encoded, binned and tiled on the GPU, no texel crosses the bus (fspt_scene_update_sky).  Afterwards the
+        scene renders bit for bit like one created from scene.sky's bytes and scene.env_bins of them; everything else as
+        update_materials."""
+        from . import scene as S
+        p = S.sky_params(sun_dir, **params)
+        L.check(L.lib().fspt_scene_update_sky(self._h, C.byref(p), _map_side("update_sky", width), _map_side("update_sky", height)))
+
+    def last_sky(self):
+        """The most recent update_sky / update_environment(bins=None) as a dict: sky_ms, bins_ms, tile_ms (GPU, HIP events;
+        bins_ms includes the read-back of n_bins), launches, readbacks, n_bins (fspt_scene_last_sky_ms)."""
+        a, b, c, nl, nr, nb = C.c_float(), C.c_float(), C.c_float(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        L.check(L.lib().fspt_scene_last_sky_ms(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(nl), C.byref(nr), C.byref(nb)))
+        return dict(sky_ms=float(a.value), bins_ms=float(b.value), tile_ms=float(c.value), launches=int(nl.value),
+                    readbacks=int(nr.value), n_bins=int(nb.value))
 
     APPEARANCE = ("tex_sets", "atlas", "atlas4", "env", "bins", "hitrec")  # read_appearance's `what`
 
@@ -1083,9 +1140,17 @@ class PathTracer:
         history, the exposure and the bloom state stay - call clear() to restart the mean."""
         self.scene.update_materials(mat, uv, atlas, atlas_res, atlas_layers)
 
-    def update_environment(self, env, env_w, env_h, bins):
-        """Scene.update_environment on this tracer's scene; state stays as for update_materials."""
+    def update_environment(self, env, env_w, env_h, bins=None):
+        """Scene.update_environment on this tracer's scene (bins=None: built on the GPU); state stays as for update_materials."""
         self.scene.update_environment(env, env_w, env_h, bins)
+
+    def update_sky(self, sun_dir, width=1024, height=512, **params):
+        """Scene.update_sky on this tracer's scene; state stays as for update_materials."""
+        self.scene.update_sky(sun_dir, width, height, **params)
+
+    def last_sky(self):
+        """Scene.last_sky of this tracer's scene"""
+        return self.scene.last_sky()
 
     def rebuild_geometry(self, tri, norm=None):
         """Scene.rebuild_geometry on this tracer's scene: a new tree in place; returns the new leaf order."""
@@ -1503,10 +1568,21 @@ class MultiPathTracer:
         args, keep = Scene._materials_args(self, "update_materials", mat, uv, atlas, atlas_res, atlas_layers)
         L.check(L.lib().fspt_multi_update_materials(self._m, *args))
 
-    def update_environment(self, env, env_w, env_h, bins):
-        """Scene.update_environment on every device's copy of the scene (fspt_multi_update_environment)."""
+    def update_environment(self, env, env_w, env_h, bins=None):
+        """Scene.update_environment on every device's copy of the scene (fspt_multi_update_environment; bins=None: each
+        device builds them from its copy of the map, fspt_multi_update_environment_auto - host arrays only)."""
+        if bins is None:
+            _, ptr, w, h, keep = Scene._environment_auto_args("update_environment", env, env_w, env_h, None)
+            L.check(L.lib().fspt_multi_update_environment_auto(self._m, ptr, w, h))
+            return
         args, keep = Scene._environment_args("update_environment", env, env_w, env_h, bins)
         L.check(L.lib().fspt_multi_update_environment(self._m, *args))
+
+    def update_sky(self, sun_dir, width=1024, height=512, **params):
+        """Scene.update_sky on every device's copy of the scene: each device generates its own map (fspt_multi_update_sky)."""
+        from . import scene as S
+        p = S.sky_params(sun_dir, **params)
+        L.check(L.lib().fspt_multi_update_sky(self._m, C.byref(p), _map_side("update_sky", width), _map_side("update_sky", height)))
 
     def rebuild_geometry(self, tri, norm=None):
         """Scene.rebuild_geometry (host arrays) on every device's copy of the scene (fspt_multi_rebuild_geometry); every

@@ -287,7 +287,7 @@ int fspt_builder_autofocus(const fspt_builder *b, const double eye[3], const dou
 int fspt_builder_get(const fspt_builder *b, float *bvh, float *tri, float *mat, float *norm, float *uv);
 /* ProcessEnvRadiance (env_sampler.js:1-74) on raw RGBE bytes.  Writes up to
  * cap bins (4 uint32 each) and the real count to *n_bins. */
-int fspt_env_bins(const uint8_t *rgbe, uint32_t w, uint32_t h, uint32_t *bins, uint32_t cap, uint32_t *n_bins);
+int fspt_env_bins(const uint8_t *rgbe, uint32_t w, uint32_t h, uint32_t *bins, uint32_t cap, uint32_t *n_bins); /* The same bins, built on HIP device `device` from a summed-area table of the map (DESIGN 8.17): same contract, host pointers. */ int fspt_env_bins_gpu(const uint8_t *rgbe, uint32_t w, uint32_t h, int device, uint32_t *bins, uint32_t cap, uint32_t *n_bins); /* GPU sky (DESIGN 8.17; the model, defaults and ranges: fspt_tuning.h): single-scattering Rayleigh + Mie seen from the ground, as a w x h equirect map in envSample's mapping (row 0 = straight up), 1..65535 texels per side.  sun_dir: finite, non-zero, normalised by the library; below the horizon is night.  A value out of range: FSPT_E_INVALID, before a device is touched. */ typedef struct fspt_sky_params { float sun_dir[3]; float turbidity, sun_intensity, sun_radius, gain; float ground_albedo[3]; uint32_t view_samples, light_samples; } fspt_sky_params; /* rgbe_out: w*h*4 bytes (RGBE as the environment takes it); linear_out: w*h*3 floats, the radiance before the encode.  Either may be NULL.  Host pointers. */ int fspt_sky_generate(int device, const fspt_sky_params *p, uint32_t w, uint32_t h, uint8_t *rgbe_out, float *linear_out); /* fspt_scene_update_environment without the host's bins: _auto takes host RGBE, _device RGBE in the scene's device memory, and the bins are built on the GPU from the uploaded map; _sky generates the map there too, so that no texel crosses the bus. Afterwards the scene renders bit for bit like fspt_scene_create of the same bytes and fspt_env_bins of them.  Blocking; ordered against every target; an error leaves the scene as it was; accumulators and per-target state are not touched. */ int fspt_scene_update_environment_auto(fspt_scene *s, const uint8_t *env, uint32_t w, uint32_t h); int fspt_scene_update_environment_device(fspt_scene *s, const uint8_t *env, uint32_t w, uint32_t h); int fspt_scene_update_sky(fspt_scene *s, const fspt_sky_params *p, uint32_t w, uint32_t h);
 
 const char *fspt_last_error(void); int fspt_abi_version(void);
 int fspt_device_count(void); /* visible HIP devices (0 when none / no driver) */

@@ -48,6 +48,9 @@ int fspt_multi_update_skin(fspt_multi *m, const float *xf, uint32_t n_joints, co
 /* fspt_scene_update_materials / _environment on every device's copy of the scene; arguments the first device refuses change nothing */
 int fspt_multi_update_materials(fspt_multi *m, const float *mat, const float *uv, const uint8_t *atlas, uint32_t atlas_res, uint32_t atlas_layers);
 int fspt_multi_update_environment(fspt_multi *m, const uint8_t *env, uint32_t env_w, uint32_t env_h, const uint32_t *bins, uint32_t n_bins);
+/* fspt_scene_update_environment_auto / _sky on every device's copy: each device builds its own map and bins */
+int fspt_multi_update_environment_auto(fspt_multi *m, const uint8_t *env, uint32_t w, uint32_t h);
+int fspt_multi_update_sky(fspt_multi *m, const fspt_sky_params *p, uint32_t w, uint32_t h);
 /* fspt_scene_rebuild_geometry (host pointers) on every device's copy of the scene.  The build is deterministic: every device
  * must return the same order (checked; FSPT_E_STATE otherwise).  order_out may be NULL. */
 int fspt_multi_rebuild_geometry(fspt_multi *m, const float *tri, const float *norm, uint32_t *order_out);

@@ -106,6 +106,33 @@ int fspt_scene_last_appearance_ms(fspt_scene *s, float *ms, uint32_t *launches, 
  * "every texel equal" flags and first texels, under the current interleaving budget.  No device. */
 int fspt_texset_classify_eval(const float *mat, uint32_t n_tris, uint32_t n_layers, uint32_t res, const uint8_t *is_const, const uint32_t *first,
                               uint32_t *tri_set, uint32_t *n_sets, uint32_t *tab, uint32_t cap_sets);
+/* GPU sky (fspt.h: fspt_sky_generate, fspt_scene_update_sky).  A planet of radius Re = 6 360 km under an atmosphere
+ * up to Ra = 6 420 km; Rayleigh scale height 7994 m, betaR = (5.8, 13.5, 33.1)e-6 / m; Mie scale height 1200 m, betaM =
+ * turbidity x 21e-6 / m on every channel, extinction 1.1 betaM, g = 0.76; the observer stands 1 m above the ground.  Per texel
+ * the view ray (to the ground or the top of the atmosphere) is cut into view_samples midpoint samples; from each a light ray to
+ * the top of the atmosphere in light_samples midpoint samples (one below the ground: that view sample is in the planet's
+ * shadow); L = sun_intensity (sumR betaR pR + sumM betaM pM), plus the lit ground (albedo / pi x the transmitted irradiance)
+ * where the ray ends on it, plus the disc (sun_intensity T / (pi sun_radius^2)) where mu >= cos(sun_radius) and it does
+ * not; all times gain.  The encode: non-finite or negative -> 0; e = the smallest integer with 2^e >= max(r, g, b, 1e-6),
+ * clamped to [-127, 127]; bytes floor(c 2^-e 255 + 0.5) clamped to [0, 255], e + 128.  tests/sky_ref.py restates both.
+ * Ranges (else FSPT_E_INVALID): turbidity [0, 64], sun_intensity >= 0, sun_radius (0, 0.5], gain >= 0, ground_albedo [0, 1],
+ * view_samples [1, 64], light_samples [1, 32], all finite.  The defaults are conventions (Nishita's constants), not measurements. */
+#define FSPT_SKY_TURBIDITY 1.0f
+#define FSPT_SKY_SUN_INTENSITY 20.0f
+#define FSPT_SKY_SUN_RADIUS 0.02f
+#define FSPT_SKY_GAIN 1.0f
+#define FSPT_SKY_GROUND_ALBEDO 0.3f
+#define FSPT_SKY_VIEW_SAMPLES 16
+#define FSPT_SKY_LIGHT_SAMPLES 8
+#define FSPT_SKY_MAX_VIEW_SAMPLES 64
+#define FSPT_SKY_MAX_LIGHT_SAMPLES 32
+/* the last update_sky / update_environment_auto / _device of the scene, from HIP events: the generator (0 without one); the
+ * bins - radiance, the two table scans, the tree levels, the count, the read-back of n_bins and the emit; the tiling.
+ * launches and readbacks count kernel launches and device -> host copies; n_bins what was built. */
+int fspt_scene_last_sky_ms(fspt_scene *s, float *sky_ms, float *bins_ms, float *tile_ms, uint32_t *launches, uint32_t *readbacks, uint32_t *n_bins);
+/* Test hook: the device's summed-area-table sum of the map's per-texel radiance (env_sampler.js getRadiance, float64) over n
+ * integer boxes (x0, y0, x1, y1), x0 <= x1 <= w, y0 <= y1 <= h: what the tree build reads.  Host pointers. */
+int fspt_env_box_sums_eval(int device, const uint8_t *rgbe, uint32_t w, uint32_t h, const uint32_t *boxes, uint32_t n, double *out);
 /* fspt_intersect (fspt.h) walking the two-level nodes (two_level != 0; FSPT_E_INVALID when the scene has none): t, index
  * and the per-ray step / leaf counts must equal the one-level walk's (tests). */
 int fspt_intersect_form(fspt_scene *scene, int two_level, const float *rays, uint32_t n, float *t_out, int32_t *index_out,

@@ -2,11 +2,11 @@
 // uvs, atlas texels and environment for an unchanged tree.  The layouts fspt_scene_create makes with host loops are made
 // here on the GPU, from the raw arrays as the caller holds them:
 //   k_ap_layer_const  per atlas layer: does every texel equal texel 0?  (one flag + the first texel per layer come back)
-//   k_ap_tile_layer   a raw image -> 8 x 4-texel tiles (fspt_api.cpp tile_image): the single-layer images of SEPARATE sets
+//   k_ap_tile_layer   a raw image -> 8 x 4-texel tiles (fspt_scene.cpp tile_image): the single-layer images of SEPARATE sets
 //   k_ap_interleave   four layers -> one image of 16-byte texels in 4 x 2-texel tiles: a QUAD set
 //   k_ap_env_tile     the environment in the form FSPT_ENV_APRON selects
 //   k_ap_records      floats 36..47 of every leaf slot's hit record: uv, texture set, ior, dielectric
-// Which layers form which set, and in which form, is decided on the host by texset_classify (fspt_api.cpp), the function
+// Which layers form which set, and in which form, is decided on the host by texset_classify (fspt_scene.cpp), the function
 // fspt_scene_create uses: the set numbering is creation's.  Every kernel is one thread per OUTPUT element in output order,
 // so a wave's stores are one contiguous run (16 bytes per lane in k_ap_interleave, 4 elsewhere) and its loads are runs of
 // a tile row; nothing is shared between lanes, so there is no LDS and no atomic but the one "differs" flag per layer.
@@ -205,19 +205,16 @@ int appearance_materials(fspt_scene *s, const float *mat, const float *uv, const
   HIP_TRY(hipEventRecord(A.ev[1], st));
   HIP_TRY(hipEventSynchronize(A.ev[1]));
   HIP_TRY(hipEventElapsedTime(&A.last_ms, A.ev[0], A.ev[1]));
-  void *old[4] = {s->atlas, s->atlas4, s->tex_sets, atlas ? A.raw : nullptr};
   hold.take(n_atlas); hold.take(n_atlas4); hold.take(n_tab);
-  s->atlas = n_atlas; s->atlas4 = n_atlas4; s->tex_sets = n_tab;
-  s->atlas_bytes = single_bytes; s->atlas4_bytes = pl.quad_bytes;
-  s->d.atlas = (const uint32_t *)s->atlas; s->d.atlas4 = (const uint4 *)s->atlas4; s->d.tex_sets = (const uint4 *)s->tex_sets;
-  s->d.n_tex_sets = n_sets; s->d.atlas_res = res; s->d.atlas_layers = layers;
+  atlas_install(s, n_atlas, single_bytes, n_atlas4, pl.quad_bytes, n_tab, n_sets, res, layers); // (frees the old three)
   s->has_dielectric = has_dielectric;
-  if (atlas) {
+  if (atlas) { // ... and the retained raw atlas after them
+    void *old_raw = A.raw;
     hold.take(raw);
     A.raw = raw; A.raw_res = res; A.raw_layers = layers;
     A.is_const.swap(is_const); A.first.swap(first);
+    hipFree(old_raw);
   }
-  for (void *o : old) hipFree(o);
   A.last_launches = launches;
   A.last_uploaded = uploaded;
   return FSPT_OK;

@@ -1,6 +1,7 @@
 // fspt_internal.hpp - what the translation units of libfspt's host side share: the scene and target objects behind the
 // opaque handles of include/fspt.h, the tuning defaults, and the helpers that cross file boundaries.
-//   fspt_api.cpp           scene and target objects, every entry point that is neither a scheduler, the image chain nor a live-scene update (include/fspt.h order)
+//   fspt_api.cpp           the target object, every entry point that is neither the scene, a scheduler, the image chain nor a live-scene update (include/fspt.h order)
+//   fspt_scene.cpp         the scene object: fspt_scene_create's host layouts, the one install and release of every scene part, the emitter light table
 //   fspt_scene_update.cpp  what changes a live scene or reports on such a change: refit, rebuild, pose, skin, appearance, motion origin
 //   fspt_post.cpp          the image chain behind the accumulator: draw, denoiser, temporal stages, auto-exposure, bloom
 //   fspt_sched_batch.cpp   the batch scheduler of the wavefront pipeline (render_wavefront) and its path state
@@ -160,7 +161,7 @@ uint32_t texset_layer_of(float id, uint32_t n_layers); // clamp(floor(id + 0.5),
 // is_const / first: n_layers entries.  FSPT_E_INVALID: the single-layer images exceed 2^32 tiles.
 int texset_classify(const float *mat, uint32_t n_tris, uint32_t n_layers, uint32_t res, const uint8_t *is_const, const uint32_t *first, TexSetPlan &pl);
 int geometry_order_targets(fspt_scene *s);  // (fspt_api.cpp) orders a scene-changing call against every target, leaves the device idle
-int geometry_changed_lights(fspt_scene *s); // (fspt_api.cpp) releases the emitter light table and rebuilds it if a target uses it
+int geometry_changed_lights(fspt_scene *s); // (fspt_scene.cpp) releases the emitter light table and rebuilds it if a target uses it
 // What fspt_scene_create derives from the reference tree's three integer words per node (left, right, triStart; a node
 // with triStart > -1 is a leaf) and nothing else: shared with fspt_scene_rebuild_geometry, which gets its words from the
 // GPU builder.  `words` + i * stride = node i's words (any alignment).
@@ -172,6 +173,12 @@ struct TreeTopology {
 };
 int tree_topology(const void *words, size_t stride_bytes, uint32_t N, uint32_t T, TreeTopology &tp); // validates; FSPT_E_INVALID
 void tree_refit_tables(const void *words, size_t stride_bytes, uint32_t N, uint32_t T, const TreeTopology &tp, fspt_scene::Refit &R);
+// (fspt_scene.cpp) The one install and one release per scene part, shared by fspt_scene_create and the live-scene updates (the
+// environment's: fspt::environment_swap below).  geometry_publish: every geometry field of s->d and the scene's counts, from s->nodes /
+// quads / tris / slot_tri / shade (set by the caller) and their tree.  geometry_free: those five and s->motion.  atlas_install frees the old.
+void geometry_publish(fspt_scene *s, const TreeTopology &tp, uint32_t n_nodes, size_t n_slots, bool quads_ok);
+inline void geometry_free(fspt_scene &s) { for (void **p : {&s.nodes, &s.quads, &s.tris, &s.slot_tri, &s.shade, &s.motion}) { hipFree(*p); *p = nullptr; } }
+void atlas_install(fspt_scene *s, void *n_atlas, uint64_t atlas_bytes, void *n_atlas4, uint64_t atlas4_bytes, void *n_tab, uint32_t n_sets, uint32_t res, uint32_t layers);
 namespace fspt { // fspt_refit.hip
 int refit_prepare(fspt_scene *s);  // the device copies of s->rf (idempotent)
 void refit_release(fspt_scene *s);
@@ -237,7 +244,7 @@ extern int g_skin_form;
 #endif
 static const size_t SKIN_LDS_MAX_BYTES = 64u << 10; // 1 365 joints
 }
-int light_table_ensure(fspt_scene *s); // (fspt_api.cpp) builds the table once; FSPT_OK when it exists
+int light_table_ensure(fspt_scene *s); // (fspt_scene.cpp) builds the table once; FSPT_OK when it exists
 #ifndef FSPT_LIGHTS_ENV_Q_MAX
 #define FSPT_LIGHTS_ENV_Q_MAX 0.875f // largest q of a scene with an environment map (fspt_sched_batch.cpp fill_trace_params)
 #endif
@@ -500,14 +507,14 @@ int present_join(fspt_target *t);      // wait for everything fspt_present enque
 int materialise_rays(fspt_target *t);  // the ray buffers as the most recent fspt_camera call left them
 const char *camera_model_name(int model); // "pinhole", "ortho", ... (error messages)
 uint32_t clamp_bounces(uint32_t nb);
-// ---- fspt_scene_update.cpp: entry points and *_eval / set_form hooks only; what it needs of fspt_api.cpp (geometry_order_targets,
-// geometry_changed_lights) and of the .hip files is declared with the scene object above
+// ---- fspt_scene_update.cpp: entry points and *_eval / set_form hooks only; what it needs of fspt_api.cpp (geometry_order_targets),
+// of fspt_scene.cpp (geometry_changed_lights) and of the .hip files is declared with the scene object above
 // ---- fspt_post.cpp
 // k_draw of `src` on `st` into `out` (device memory), through the target's auto-exposure and bloom when they are on
 hipError_t draw_launch(fspt_target *t, const float4 *src, float exposure, float saturation, int denoise, float max_sigma,
                        float scale, uint32_t *out, hipStream_t st);
 void post_release(fspt_target *t); // fspt_target_destroy: the image chain's buffers and events (the streams are idle)
-// ---- the *_eval test hooks (fspt_api.cpp, fspt_scene_update.cpp, fspt_post.cpp)
+// ---- the *_eval test hooks (fspt_api.cpp, fspt_scene.cpp, fspt_scene_update.cpp, fspt_post.cpp)
 // A hook's device memory: ONE allocation, freed when the scope ends.  The first HIP error sticks in `e`: up, down and sync
 // are no-ops behind it, and a hook launches with `if (s.ok()) s.e = launch(..)`.  `base` is NULL when the allocation
 // failed: a hook returns done() at once then, before it forms a pointer into the block.  sync() stands apart from done()

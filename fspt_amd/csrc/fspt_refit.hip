@@ -321,7 +321,7 @@ struct RebuildGuard {
     hipFree(d_map); hipFree(d_cref);
     for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
     if (keep) return;
-    hipFree(ns.nodes); hipFree(ns.quads); hipFree(ns.tris); hipFree(ns.slot_tri); hipFree(ns.shade); hipFree(ns.motion);
+    geometry_free(ns);
     hipFree(p_part); hipFree(p_rest);
     for (void *p : k_new) hipFree(p);
     refit_release(&ns);
@@ -467,7 +467,7 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
   HIP_TRY(hipEventElapsedTime(&install_ms, G.ev[0], G.ev[1]));
   // 6. everything has succeeded: swap, then free the old tree
   G.keep = true;
-  hipFree(s->nodes); hipFree(s->quads); hipFree(s->tris); hipFree(s->slot_tri); hipFree(s->shade); hipFree(s->motion);
+  geometry_free(*s);
   refit_release(s);
   if (s->pose.part) { // (rf.stage is a new array: what read_pose would return is gone)
     hipFree(s->pose.part); hipFree(s->pose.rest);
@@ -482,20 +482,8 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
     Ks.skinned = false;
   }
   s->rf = std::move(ns.rf);
-  s->motion = ns.motion;
-  s->nodes = ns.nodes; s->quads = ns.quads; s->tris = ns.tris; s->slot_tri = ns.slot_tri; s->shade = ns.shade;
-  s->d.nodes = (const float4 *)s->nodes;
-  s->d.quads = quads_ok ? (const float4 *)s->quads : nullptr;
-  s->d.leaves = (const float *)s->tris;
-  s->d.slot_tri = (const uint32_t *)s->slot_tri;
-  s->d.hitrec = (const float4 *)s->shade;
-  s->d.root_ref = tp.ref[0];
-  s->d.stack_n = tp.max_depth + 1;
-  s->d.n_top = NI < 256u ? NI : 256u;
-  s->depth = tp.max_depth;
-  s->n_nodes = nn;
-  s->n_interior = NI;
-  s->n_slots = n_slots;
+  s->motion = ns.motion; s->nodes = ns.nodes; s->quads = ns.quads; s->tris = ns.tris; s->slot_tri = ns.slot_tri; s->shade = ns.shade;
+  geometry_publish(s, tp, nn, n_slots, quads_ok != 0);
   s->rb.build_ms = G.bt.kernel_ms;
   s->rb.install_ms = install_ms;
   s->rb.host_ms = host_ms;

@@ -129,7 +129,7 @@ class OLights(C.Structure):
 
 
 def realised_p(prob, alias):
-    """light_p as the host computes it (fspt_api.cpp light_table_ensure): (prob_i + sum_{alias_j = i, j != i} (1 - prob_j))
+    """light_p as the host computes it (fspt_scene.cpp light_table_ensure): (prob_i + sum_{alias_j = i, j != i} (1 - prob_j))
     / n, summed in float64 in entry order, rounded to float32."""
     prob = np.asarray(prob, np.float32); alias = np.asarray(alias, np.uint32)
     n = prob.size

@@ -274,7 +274,7 @@ static fspt::CameraP camera_p(const fspt_camera_params &c) {
   p.fov_scale = c.fov_scale; p.lens[0] = c.lens[0]; p.lens[1] = c.lens[1];
   return p;
 }
-// k_camera_model has overwritten the target's one pair of ray buffers with rays nobody asked to see.  What they held
+// k_camera under a camera model has overwritten the target's one pair of ray buffers with rays nobody asked to see.  What they held
 // before: a recorded fspt_camera call not yet materialised (nothing to do), that call's materialised rays (made again when
 // somebody looks at them: cam_recorded), or injected rays, which are gone - fspt_trace then answers FSPT_E_STATE rather than
 // trace foreign rays, until the caller injects again.
@@ -283,7 +283,7 @@ static void ray_buffers_overwritten(fspt_target *t) {
   if (t->rays_valid && !t->rays_injected) t->cam_recorded = true;
   else { t->rays_valid = false; t->rays_injected = false; }
 }
-// The same under a camera model: per tick k_camera_model into the ray buffers, then the single-tick trace from
+// The same under a camera model: per tick the model's k_camera into the ray buffers, then the single-tick trace from
 // the buffers (either pipeline, either scheduler), all on the target's stream in order - the trace of tick k has read the
 // buffers before the camera kernel of tick k + 1 writes them, and nothing waits on the host.  Not batched.
 static int render_ticks_model(fspt_target *t, const fspt_camera_params *cam, uint32_t first_tick, uint32_t n_ticks,
@@ -294,8 +294,8 @@ static int render_ticks_model(fspt_target *t, const fspt_camera_params *cam, uin
   HIP_TRY(hipEventRecord(t->ev0, t->stream));
   ray_buffers_overwritten(t);
   for (uint32_t k = 0; k < n_ticks; ++k) {
-    HIP_TRY(fspt::launch_camera_model(t->W, t->H, t->vw, t->vh, c, t->cam_model, rbc[k], t->ray_pos, t->ray_dir, t->stream,
-                                      (uint32_t)t->sampler, t->sampler_seed, first_tick + k));
+    HIP_TRY(fspt::launch_camera(t->W, t->H, t->vw, t->vh, c, t->cam_model, rbc[k], t->ray_pos, t->ray_dir, t->stream,
+                                (uint32_t)t->sampler, t->sampler_seed, first_tick + k));
     int rc = trace_from_buffers(t, first_tick + k, rbt[k], cam->env_theta, cam->num_bounces, true);
     if (rc) return rc;
   }
@@ -386,14 +386,8 @@ int materialise_rays(fspt_target *t) {
   std::memcpy(c.P, t->last_cam.P, 12); std::memcpy(c.I, t->last_cam.I, 12);
   c.fov_scale = t->last_cam.fov_scale; c.lens[0] = t->last_cam.lens[0]; c.lens[1] = t->last_cam.lens[1];
   // (the Sobol sampler: sample index acc_ticks - the tick that would trace these rays next)
-  if (t->cam_model.model != FSPT_CAMERA_PINHOLE) {
-    HIP_TRY(fspt::launch_camera_model(t->W, t->H, t->vw, t->vh, c, t->cam_model, t->last_rb_cam, t->ray_pos, t->ray_dir, t->stream,
-                                      (uint32_t)t->sampler, t->sampler_seed, t->acc_ticks));
-    t->cam_recorded = false;
-    return FSPT_OK;
-  }
-  HIP_TRY(fspt::launch_camera(t->W, t->H, t->vw, t->vh, c, t->last_rb_cam, t->ray_pos, t->ray_dir, t->stream, (uint32_t)t->sampler,
-                              t->sampler_seed, t->acc_ticks));
+  HIP_TRY(fspt::launch_camera(t->W, t->H, t->vw, t->vh, c, t->cam_model, t->last_rb_cam, t->ray_pos, t->ray_dir, t->stream,
+                              (uint32_t)t->sampler, t->sampler_seed, t->acc_ticks));
   t->cam_recorded = false;
   return FSPT_OK;
 }
@@ -701,8 +695,8 @@ int fspt_camera_model_time(fspt_target *t, const fspt_camera_params *cam, uint32
   const fspt::CameraP c = camera_p(*cam);
   HIP_TRY(hipEventRecord(t->ev0, t->stream));
   for (uint32_t k = 0; k < reps; ++k)
-    HIP_TRY(fspt::launch_camera_model(t->W, t->H, t->vw, t->vh, c, t->cam_model, (float)k, t->ray_pos, t->ray_dir, t->stream,
-                                      (uint32_t)t->sampler, t->sampler_seed, k));
+    HIP_TRY(fspt::launch_camera(t->W, t->H, t->vw, t->vh, c, t->cam_model, (float)k, t->ray_pos, t->ray_dir, t->stream,
+                                (uint32_t)t->sampler, t->sampler_seed, k));
   HIP_TRY(hipEventRecord(t->ev1, t->stream));
   HIP_TRY(hipEventSynchronize(t->ev1));
   float ms = 0.0f;

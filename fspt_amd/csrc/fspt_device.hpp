@@ -336,7 +336,7 @@ struct FeatureP {
   uint64_t seed;  // the camera rays' randBase values: fspt_rand_base_next's stream from this state
   float4 *feat;   // 2 x float4 per pixel: (albedo.rgb, depth), (normal.xyz, coverage)
 };
-struct FeatureModelP { FeatureP f; CameraModelP cm; }; // k_features_model: the guides under a camera model
+struct FeatureModelP { FeatureP f; CameraModelP cm; }; // k_features under a camera model (the pinhole camera's block is FeatureP)
 struct AtrousP {
   const float4 *src; // u^k, or (demod) the accumulator
   float4 *dst;
@@ -456,7 +456,7 @@ struct BloomPlan {          // the pyramid of a vw x vh viewport
 };
 
 // ---------------------------------------------------------------------------
-// launchers of fspt_kernels.hip: whatever reads a DScene
+// launchers of fspt_kernels.hip: the renderers, their draw and read-out helpers, the light table
 // ---------------------------------------------------------------------------
 hipError_t launch_trace(const TraceP &p, bool gen_rays, bool count, int num_cus, hipStream_t stream);
 // count: 0 = production kernels; 1 = counting variants doing the reference's work (NEE shadow rays traced to the closest
@@ -464,33 +464,31 @@ hipError_t launch_trace(const TraceP &p, bool gen_rays, bool count, int num_cus,
 hipError_t launch_wf(int kernel, const WfP &p, int count, int num_cus, hipStream_t stream);
 size_t wf_max_stack_entries(); // deepest tree (entries per lane) whose traversal stacks fit the LDS of every kernel
 hipError_t launch_tile_pack(const TilePackP &p, bool unpack, hipStream_t stream);
-hipError_t launch_camera(uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const CameraP &cam, float rand_base, float4 *pos, float4 *dir,
-                         hipStream_t stream, uint32_t sampler = 0, uint32_t smp_seed = 0, uint32_t sample = 0);
-// the Sobol sampler's value for n (pixel, sample, dim) triples (fspt_sampler_eval)
-hipError_t launch_sampler_eval(uint32_t seed, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim, uint32_t n,
-                               float *out, hipStream_t stream);
-hipError_t launch_intersect(const IntersectP &p, hipStream_t stream);
 hipError_t launch_bvh_test(const TraceP &p, hipStream_t stream);
-hipError_t launch_math(int op, const float *a, const float *b, uint32_t n, float *out, hipStream_t stream);
 // light table build (fspt_target_set_lights): w[i] for the triangle in leaf slot slots[i]; with rec != NULL
 // also its 64-byte light record rec[4 i .. 4 i + 3]
 hipError_t launch_light_weights(const DScene &S, const uint32_t *slots, uint32_t n, float *w, float4 *rec, hipStream_t stream);
 // fspt_light_sample_eval: 10 floats per query (ro.xyz, n.xyz, u0..u3) -> entry index, 8 floats (x.xyz, pdf_L, Le.rgb, n . w)
 hipError_t launch_light_eval(const DScene &S, const float *in, uint32_t n, int *entry, float *out, hipStream_t stream);
+
+// ---------------------------------------------------------------------------
+// launchers of fspt_passes.hip: the stand-alone passes and test hooks, which no renderer calls
+// ---------------------------------------------------------------------------
+// the ray buffers of a tick under camera model cm.model (CAM_PINHOLE: camera.fs as a pass; a missing model or sampler: hipErrorInvalidValue)
+hipError_t launch_camera(uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const CameraP &cam, const CameraModelP &cm, float rand_base,
+                         float4 *pos, float4 *dir, hipStream_t stream, uint32_t sampler, uint32_t smp_seed, uint32_t sample);
+// the Sobol sampler's value for n (pixel, sample, dim) triples (fspt_sampler_eval)
+hipError_t launch_sampler_eval(uint32_t seed, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim, uint32_t n,
+                               float *out, hipStream_t stream);
+hipError_t launch_intersect(const IntersectP &p, hipStream_t stream);
+hipError_t launch_math(int op, const float *a, const float *b, uint32_t n, float *out, hipStream_t stream);
 // one workgroup per active tile: E_T = mean over the tile's viewport pixels and 3 channels of m (I - S)^2 / ((n - m)(I^2 + 0.01))
 hipError_t launch_adaptive_error(const AdaptiveP &p, hipStream_t stream);
 // one workgroup: retire the tiles of list_in whose E_T decides it, list the rest in list_out (same order), *n_out
 hipError_t launch_adaptive_select(const AdaptiveP &p, hipStream_t stream);
 // the two passes of the image chain that trace rays (fspt_post.cpp launches them)
-hipError_t launch_features(const FeatureP &p, hipStream_t stream);
-hipError_t launch_features_model(const FeatureModelP &p, hipStream_t stream); // p.cm.model != CAM_PINHOLE
+hipError_t launch_features(const FeatureP &p, const CameraModelP &cm, hipStream_t stream); // (the guides follow the camera model)
 hipError_t launch_temporal_gbuffer(const TemporalGP &p, hipStream_t stream);
-
-// ---------------------------------------------------------------------------
-// launcher of fspt_camera.hip: the ray buffers of a tick under a camera model (cm.model != CAM_PINHOLE: hipErrorInvalidValue)
-// ---------------------------------------------------------------------------
-hipError_t launch_camera_model(uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const CameraP &cam, const CameraModelP &cm, float rand_base,
-                               float4 *pos, float4 *dir, hipStream_t stream, uint32_t sampler, uint32_t smp_seed, uint32_t sample);
 
 // ---------------------------------------------------------------------------
 // launchers of fspt_post.hip: whatever reads only images

@@ -9,10 +9,11 @@
 //   fspt_multi.cpp         one frame over several devices (fspt_multi_*), tile pack / unpack, the optional RCCL exchange
 //   scene_build.cpp        the native scene builder (OBJ / MTL / SAH BVH; no GPU)
 // and the device side, declared in fspt_device.hpp:
-//   fspt_kernels.hip       every kernel that reads a DScene: the path tracer, the test passes, k_features, k_temporal_gbuffer
-//   fspt_post.hip          every kernel that reads only images: what fspt_post.cpp launches, but for those two
+//   fspt_kernels.hip       the renderers: the path tracer's two execution strategies, k_bvh_test, k_tile_pack, the light table
+//   fspt_passes.hip        the passes no renderer calls: k_camera (every camera model), k_intersect, k_features, k_temporal_gbuffer,
+//                          k_adaptive_*, the test hooks; both on fspt_traverse.hpp, fspt_surface.hpp, fspt_camera_model.hpp
+//   fspt_post.hip          every kernel that reads only images: what fspt_post.cpp launches, but for k_features and k_temporal_gbuffer
 //   fspt_bvh_build.hip     the GPU BVH builder;  fspt_refit.hip  in-place refit and rebuild;  fspt_pose.hip  part transforms and skinning
-//   fspt_camera.hip        ray generation under an opt-in camera model (the rule: fspt_camera_model.hpp)
 //   fspt_appearance.hip    in-place appearance update: the texture-set, atlas and environment layouts and the material part of the hit records
 //   fspt_sky.hip           the sky generator and the environment's importance bins, built on the GPU
 #pragma once
@@ -368,8 +369,8 @@ struct fspt_target {
   bool cam_recorded = false;     // last_cam is valid and newer than the ray buffers' contents
   bool rays_injected = false;    // the ray buffers hold caller-supplied rays (fspt_set_rays): trace them as they are
   bool defer = true;             // fspt_target_set_deferred
-  // fspt_target_set_camera_model: model != FSPT_CAMERA_PINHOLE sends every tick through k_camera_model
-  // (fspt_camera.hip) into the ray buffers and the single-tick trace from them (render_ticks)
+  // fspt_target_set_camera_model: model != FSPT_CAMERA_PINHOLE sends every tick through k_camera
+  // (fspt_passes.hip) into the ray buffers and the single-tick trace from them (render_ticks)
   fspt::CameraModelP cam_model{fspt::CAM_PINHOLE, 3.14159265f, 0.064f};
   // Primary-form tuner (batch scheduler): k_wf_primary has two forms of its traversal phase with identical results
   // (fspt_kernels.hip).  Which is faster depends on the scene and the batch size, so the target measures: HIP events

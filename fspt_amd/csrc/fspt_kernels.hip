@@ -1,7 +1,9 @@
-// fspt_kernels.hip — the gfx950 kernels of libfspt that read a DScene or belong to the renderers: traversal, shading, the
-// two execution strategies, their helpers and test hooks, and the two passes of the image chain that trace rays
-// (k_features, k_temporal_gbuffer).  Whatever reads only images - draw, bloom, auto-exposure, the a-trous filter, the
-// temporal blend, clamp and variance - is fspt_post.hip.
+// fspt_kernels.hip — the renderers of libfspt on gfx950: shading, environment and emitter sampling, the two execution
+// strategies, their draw and read-out helpers (k_bvh_test, k_tile_pack) and the light table's kernels.  The device code
+// they share with the stand-alone passes is in headers - the BVH walk and the LDS stack (fspt_traverse.hpp), from a hit to
+// surface data (fspt_surface.hpp), the cameras and the samplers (fspt_camera_model.hpp); the passes no renderer calls are
+// fspt_passes.hip; whatever reads only images - draw, bloom, auto-exposure, the a-trous filter, the temporal blend, clamp
+// and variance - is fspt_post.hip.
 //
 // The reference's hot path is one fragment-shader invocation per pixel (shader/tracer.fs:436-518).  Two execution
 // strategies run the same per-path arithmetic (advance_path / shade_hit / trace loops below), bit-identical results:
@@ -23,17 +25,12 @@
 //      T  trace the lane's one or two pending rays (shadow, then extension).
 // Arithmetic is "fspt-math" (fspt_math.hpp); traversal order, pruning rule and the 4-triangle leaf over-read are the
 // reference's, so results equal the CPU restatement (oracle/) bit for bit.
-#include "fspt_device.hpp"
-#include "fspt_math.hpp"
-#include "fspt_camera_model.hpp" // model_ray: k_features_model alone uses it
+#include "fspt_traverse.hpp"
+#include "fspt_surface.hpp"
+#include "fspt_camera_model.hpp" // camera_ray, Rng
 
 namespace fspt {
-using namespace fm;
 
-#define WAVE 64
-#ifndef FSPT_TAP2
-#define FSPT_TAP2 1
-#endif
 #ifndef WF_LOGIC_LDSTAB
 #define WF_LOGIC_LDSTAB 1
 #endif
@@ -41,378 +38,8 @@ using namespace fm;
 #define WF_TRACE_LDS_TOP 31 // top-of-tree nodes (breadth-first) k_wf_trace keeps in LDS: measured best of {0, 31, 77} (profiles/r01)
 #endif
 #define WF_TRACE_BLOCKS_PER_CU 7u // most 256-thread blocks per CU the LDS split is computed for (the registers - 80 since the suspended traversals - allow 6)
-#define BLOCK_THREADS 256
-#define WAVES_PER_BLOCK (BLOCK_THREADS / WAVE)
 #define WORK_CHUNK 256u
 
-// ---------------------------------------------------------------------------
-// rayBoxIntersect (tracer.fs:317-326) for BOTH child boxes of a node; 1/dir hoisted (same value every call).
-// Packed FP32: gfx950 issues v_pk_add_f32 / v_pk_mul_f32 (two IEEE binary32 operations per lane) at the rate of one
-// scalar operation, and the traversal kernels are bound by VALU issue (profiles/r02: 0.85-0.98 of the issue rate), so
-// the node stores the slab bounds in the pairs the arithmetic wants (fspt_device.hpp): the 12 subtractions and 12
-// multiplications of a step are 6 + 6 instructions.  Same operations on the same operands as the scalar form:
-// bit-identical results.
-// ---------------------------------------------------------------------------
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef float f4u __attribute__((ext_vector_type(4)));
-FM_DEV f2 mk2(float a, float b) { return (f2){a, b}; }
-FM_DEV f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-FM_DEV float slab(f2 txy1, f2 txy2, f2 tz) {
-  float tMax = min_(min_(max_(txy1.x, txy2.x), max_(txy1.y, txy2.y)), max_(tz.x, tz.y));
-  float tMin = max_(max_(min_(txy1.x, txy2.x), min_(txy1.y, txy2.y)), min_(tz.x, tz.y));
-  return (tMax >= tMin && tMax > 0.0f) ? tMin : MAX_T;
-}
-FM_DEV void node_test(float4 n0, float4 n1, float4 n2, V3 o, V3 inv, float &tl, float &tr) {
-  const f2 oxy = mk2(o.x, o.y), ixy = mk2(inv.x, inv.y), oz = mk2(o.z, o.z), iz = mk2(inv.z, inv.z);
-  const f2 l1 = (mk2(n0.x, n0.y) - oxy) * ixy, l2 = (mk2(n0.z, n0.w) - oxy) * ixy; // left: (t1x, t1y), (t2x, t2y)
-  const f2 r1 = (mk2(n1.x, n1.y) - oxy) * ixy, r2 = (mk2(n1.z, n1.w) - oxy) * ixy; // right
-  const f2 lz = (mk2(n2.x, n2.y) - oz) * iz, rz = (mk2(n2.z, n2.w) - oz) * iz;     // (t1z, t2z) left, right
-  tl = slab(l1, l2, lz);
-  tr = slab(r1, r2, rz);
-}
-// The two child references of a node (f4[3].xy): ONE 8-byte load.  (Written as an int2 / int4 access the compiler
-// widens it to 16 bytes.)
-FM_DEV int2 node_refs(const float4 *n) {
-  const long long rr = *reinterpret_cast<const long long *>(n + 3);
-  return make_int2((int)(rr & 0xffffffffll), (int)(rr >> 32));
-}
-
-// One step of intersectScene at an interior node (tracer.fs:382-401) once the two entry distances are known: descend
-// into the nearer child that is hit (the other one, if hit too, goes on the stack), or pop.  Returns which child the
-// walk descends into: 0 left, 1 right, -1 neither (cur then holds the popped reference).
-FM_DEV int node_decide(float tl, float tr, int refL, int refR, float t, int *stack, int &sp, int &cur) {
-  const bool hl = tl < t, hr = tr < t;
-  const bool swap = tl > tr; // tracer.fs:384: right first only when strictly nearer
-  if (hl && hr) {
-    stack[sp * WAVE] = swap ? refL : refR;
-    sp++;
-    cur = swap ? refR : refL;
-    return swap ? 1 : 0;
-  }
-  if (hl) { cur = refL; return 0; }
-  if (hr) { cur = refR; return 1; }
-  if (sp > 0) { sp--; cur = stack[sp * WAVE]; }
-  else cur = REF_SENTINEL;
-  return -1;
-}
-// TWO steps on one two-level node (fspt_device.hpp "quad"; the eight loads are the caller's: global or LDS): the step at
-// the node itself - its children's boxes are the unions of the stored grandchildren's, derived exactly - and, when the
-// walk descends into a child that is an interior node, that child's step right away: result.t has not changed in
-// between (no leaf was visited), so it is the test the one-level walk makes after its next fetch.  `steps` counts the
-// reference's loop iterations exactly as the one-level walk does.
-template <bool COUNT>
-FM_DEV void quad_step(float4 a0, float4 a1, float4 a2, int4 ar, float4 b0, float4 b1, float4 b2, int2 br, V3 o, V3 inv, float t,
-                      int *stack, int &sp, int &cur, uint32_t &steps) {
-  const float4 n0 = make_float4(min_(a0.x, a1.x), min_(a0.y, a1.y), max_(a0.z, a1.z), max_(a0.w, a1.w)); // box(L) = box(LL) U box(LR)
-  const float4 n1 = make_float4(min_(b0.x, b1.x), min_(b0.y, b1.y), max_(b0.z, b1.z), max_(b0.w, b1.w)); // box(R)
-  const float4 n2 = make_float4(min_(a2.x, a2.z), max_(a2.y, a2.w), min_(b2.x, b2.z), max_(b2.y, b2.w));
-  float tl, tr;
-  node_test(n0, n1, n2, o, inv, tl, tr);
-  const int side = node_decide(tl, tr, ar.z, ar.w, t, stack, sp, cur);
-  if (side < 0 || cur < 0) return; // popped, or the child is a leaf (its record is the next fetch)
-  if (COUNT) steps++;
-  const bool right = side != 0;
-  const float4 c0 = right ? b0 : a0, c1 = right ? b1 : a1, c2 = right ? b2 : a2;
-  node_test(c0, c1, c2, o, inv, tl, tr);
-  node_decide(tl, tr, right ? br.x : ar.x, right ? br.y : ar.y, t, stack, sp, cur);
-}
-FM_DEV void quad_load(const float4 *q, float4 &a0, float4 &a1, float4 &a2, int4 &ar, float4 &b0, float4 &b1, float4 &b2, int2 &br) {
-  a0 = q[0]; a1 = q[1]; a2 = q[2];
-  const float4 r = q[3];
-  ar = make_int4(__float_as_int(r.x), __float_as_int(r.y), __float_as_int(r.z), __float_as_int(r.w));
-  b0 = q[4]; b1 = q[5]; b2 = q[6];
-  br = node_refs(q + 4);
-}
-
-// rayTriangleIntersect (tracer.fs:300-315) on a pre-edged triangle; the early
-// returns become one predicate with the same NaN behaviour.
-FM_DEV float ray_tri(V3 o, V3 d, V3 v1, V3 e1, V3 e2) {
-  V3 p = cross(d, e2);
-  float det = dot(e1, p);
-  float invDet = 1.0f / det;
-  V3 t = o - v1;
-  float u = dot(t, p) * invDet;
-  V3 q = cross(t, e1);
-  float v = dot(d, q) * invDet;
-  float dist = dot(e2, q) * invDet;
-  bool miss = (abs_(det) < EPSILON) || (u < 0.0f) || (u > 1.0f) || (v < 0.0f) || (u + v > 1.0f) || !(dist > EPSILON);
-  return miss ? MAX_T : dist;
-}
-
-// Two triangles at once (packed FP32, see node_test): component c of the pair is (tri_a.c, tri_b.c).  Every
-// operation is ray_tri's, on the same operands, in the same order.
-FM_DEV f2 ray_tri2(V3 o, V3 d, f2 v1x, f2 v1y, f2 v1z, f2 e1x, f2 e1y, f2 e1z, f2 e2x, f2 e2y, f2 e2z) {
-  const f2 dx = mk2(d.x, d.x), dy = mk2(d.y, d.y), dz = mk2(d.z, d.z);
-  const f2 px = fma2(dy, e2z, -(dz * e2y)), py = fma2(dz, e2x, -(dx * e2z)), pz = fma2(dx, e2y, -(dy * e2x)); // cross(d, e2)
-  const f2 det = fma2(e1z, pz, fma2(e1y, py, e1x * px));
-  const f2 invDet = mk2(1.0f / det.x, 1.0f / det.y);
-  const f2 tx = mk2(o.x, o.x) - v1x, ty = mk2(o.y, o.y) - v1y, tz = mk2(o.z, o.z) - v1z;
-  const f2 u = fma2(tz, pz, fma2(ty, py, tx * px)) * invDet;
-  const f2 qx = fma2(ty, e1z, -(tz * e1y)), qy = fma2(tz, e1x, -(tx * e1z)), qz = fma2(tx, e1y, -(ty * e1x)); // cross(t, e1)
-  const f2 v = fma2(dz, qz, fma2(dy, qy, dx * qx)) * invDet;
-  const f2 dist = fma2(e2z, qz, fma2(e2y, qy, e2x * qx)) * invDet;
-  const f2 uv = u + v;
-  const bool m0 = (abs_(det.x) < EPSILON) || (u.x < 0.0f) || (u.x > 1.0f) || (v.x < 0.0f) || (uv.x > 1.0f) || !(dist.x > EPSILON);
-  const bool m1 = (abs_(det.y) < EPSILON) || (u.y < 0.0f) || (u.y > 1.0f) || (v.y < 0.0f) || (uv.y > 1.0f) || !(dist.y > EPSILON);
-  return mk2(m0 ? MAX_T : dist.x, m1 ? MAX_T : dist.y);
-}
-
-// ---------------------------------------------------------------------------
-// processLeaf (tracer.fs:355-364): always LEAF_SIZE triangles from the leaf's first one, strict `<` update in
-// triangle order.  Leaf record `leaf` (fspt_device.hpp): the LEAF_SIZE pre-edged triangles the reference would read,
-// component-major - for LEAF_SIZE = 4 nine 16-byte loads whose halves are the operand pairs of ray_tri2.
-// `hit` becomes the leaf SLOT (leaf * LEAF_SIZE + i): the index the hit records are stored under; slot_to_tri gives
-// the reference's triangle index where one is reported (fspt_intersect).
-// ---------------------------------------------------------------------------
-FM_DEV void process_leaf(const float *__restrict__ leaves, uint32_t leaf_size, int leaf, V3 o, V3 d, float &t, int &hit) {
-  if (leaf_size == 4) {
-    const f4u *q = reinterpret_cast<const f4u *>(leaves) + (size_t)leaf * TRI_FLOATS;
-    const f4u c0 = q[0], c1 = q[1], c2 = q[2], c3 = q[3], c4 = q[4], c5 = q[5], c6 = q[6], c7 = q[7], c8 = q[8];
-    const f2 a = ray_tri2(o, d, c0.xy, c1.xy, c2.xy, c3.xy, c4.xy, c5.xy, c6.xy, c7.xy, c8.xy);
-    const f2 b = ray_tri2(o, d, c0.zw, c1.zw, c2.zw, c3.zw, c4.zw, c5.zw, c6.zw, c7.zw, c8.zw);
-    const int s0 = leaf * 4;
-    if (a.x < t) { t = a.x; hit = s0; }
-    if (a.y < t) { t = a.y; hit = s0 + 1; }
-    if (b.x < t) { t = b.x; hit = s0 + 2; }
-    if (b.y < t) { t = b.y; hit = s0 + 3; }
-  } else {
-    const float *a = leaves + (size_t)leaf * leaf_size * TRI_FLOATS;
-    for (uint32_t i = 0; i < leaf_size; ++i) {
-      float res = ray_tri(o, d, v3(a[i], a[leaf_size + i], a[2 * leaf_size + i]),
-                          v3(a[3 * leaf_size + i], a[4 * leaf_size + i], a[5 * leaf_size + i]),
-                          v3(a[6 * leaf_size + i], a[7 * leaf_size + i], a[8 * leaf_size + i]));
-      if (res < t) { t = res; hit = leaf * (int)leaf_size + (int)i; }
-    }
-  }
-}
-// leaf slot -> the reference's triangle index (first triangle of the leaf + i, tracer.fs:360); -1 stays -1
-FM_DEV int slot_to_tri(const DScene &S, int slot) { return slot < 0 ? -1 : (int)S.slot_tri[slot]; }
-
-struct Counters {
-  uint32_t samples, rays, steps, leaves, shades, envs;
-};
-
-// ---------------------------------------------------------------------------
-// intersectScene (tracer.fs:366-404) for up to two rays sharing an origin:
-// ray A (optional: the NEE shadow ray, tracer.fs:501) then ray B (primary or
-// extension ray, tracer.fs:440,507).  `stack` points at this lane's column of
-// the wave's LDS stack (entry k at stack[k*64]).
-// ---------------------------------------------------------------------------
-// ANYHIT: ray A stops at its first hit (only `shadow.index == -1` is consumed, tracer.fs:502).
-// WIDE: walk the two-level nodes (S.quads, must be non-NULL): two steps per memory round trip, same walk.
-// tA: ray A's t bound (an emitter shadow ray ends short of its light point; MAX_T otherwise)
-template <bool COUNT, bool ANYHIT, bool WIDE = false>
-FM_DEV void trace_rays(const DScene &S, int *stack, V3 o, bool hasA, V3 dA, V3 dB, int &hitA, float &tB, int &hitB,
-                       Counters &cnt, float tA = MAX_T) {
-  int slot = hasA ? 0 : 1;
-  V3 d = hasA ? dA : dB;
-  V3 inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-  float t = hasA ? tA : MAX_T;
-  int hit = -1;
-  int cur = S.root_ref;
-  int sp = 0;
-  hitA = -1;
-  if (COUNT) cnt.rays++;
-  const float4 *__restrict__ nodes = WIDE ? S.quads : S.nodes;
-  const float *__restrict__ leaves = S.leaves;
-  const uint32_t leaf_size = S.leaf_size;
-  while (true) {
-    // ---- interior nodes ----------------------------------------------------
-    while (cur >= 0) {
-      if (COUNT) cnt.steps++;
-      if constexpr (WIDE) {
-        float4 a0, a1, a2, b0, b1, b2; int4 ar; int2 br;
-        quad_load(nodes + (size_t)cur * QUAD_F4, a0, a1, a2, ar, b0, b1, b2, br);
-        quad_step<COUNT>(a0, a1, a2, ar, b0, b1, b2, br, o, inv, t, stack, sp, cur, cnt.steps);
-        continue;
-      }
-      const float4 *n = nodes + (size_t)cur * NODE_F4;
-      float4 n0 = n[0], n1 = n[1], n2 = n[2];
-      const int2 n3 = node_refs(n);
-      float tl, tr;
-      node_test(n0, n1, n2, o, inv, tl, tr);
-      bool hl = tl < t, hr = tr < t;
-      bool swap = tl > tr; // tracer.fs:384: right first only when strictly nearer
-      int nearRef = swap ? n3.y : n3.x;
-      int farRef = swap ? n3.x : n3.y;
-      if (hl && hr) {
-        stack[sp * WAVE] = farRef;
-        sp++;
-        cur = nearRef;
-      } else if (hl) {
-        cur = n3.x;
-      } else if (hr) {
-        cur = n3.y;
-      } else if (sp > 0) {
-        sp--;
-        cur = stack[sp * WAVE];
-      } else {
-        cur = REF_SENTINEL;
-      }
-    }
-    if (cur == REF_SENTINEL) {
-      if (slot == 0) { // shadow ray done: only its hit/miss is consumed (tracer.fs:502)
-        hitA = hit;
-        slot = 1;
-        d = dB;
-        inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-        t = MAX_T;
-        hit = -1;
-        cur = S.root_ref;
-        if (COUNT) cnt.rays++;
-        continue;
-      }
-      break;
-    }
-    // ---- leaf: processLeaf (tracer.fs:355-364), always leaf_size triangles ----
-    {
-      if (COUNT) { cnt.steps++; cnt.leaves++; }
-      int ts = ~cur;
-      process_leaf(leaves, leaf_size, ts, o, d, t, hit);
-      if (sp > 0) { sp--; cur = stack[sp * WAVE]; }
-      else cur = REF_SENTINEL;
-      if (ANYHIT && slot == 0 && hit != -1) cur = REF_SENTINEL;
-    }
-  }
-  tB = t;
-  hitB = hit;
-}
-
-// intersectScene (tracer.fs:366-404) for ONE ray per lane, in SLICES: the traversal state (node reference, stack depth,
-// t, hit; the stack itself is the lane's LDS column) is the caller's and survives the call.  A lane walks on from
-// where it stands until its ray is finished (cur == REF_SENTINEL) or it has done `budget` loop iterations in this call;
-// the call returns when no lane has anything left to do within its budget.  `anyhit`: stop at the first hit (NEE
-// shadow rays, tracer.fs:502).  Same node sequence and arithmetic as trace_rays, whatever the slicing.
-// WIDE: 0 the 64-byte nodes, 1 the two-level nodes, 2 the caller says per call (`wide_now`, wave-uniform): the traversal
-// state - node reference, stack entries - means the same in both walks (the two arrays are indexed alike), so a ray can
-// change form between any two steps.
-template <bool COUNT, int WIDE = 0>
-FM_DEV void trace_slice(const DScene &S, int *stack, V3 o, V3 d, V3 inv /* 1 / d */, bool anyhit, int &cur, int &sp, float &t, int &hit,
-                        uint32_t budget, uint32_t &n /* loop iterations (memory round trips) this lane has used of the budget */, Counters &cnt,
-                        bool wide_now = false) {
-  const float4 *__restrict__ nodes = S.nodes;
-  const float4 *__restrict__ quads = S.quads;
-  const float *__restrict__ leaves = S.leaves;
-  const uint32_t leaf_size = S.leaf_size;
-  while (cur != REF_SENTINEL && n < budget) {
-    while (cur >= 0 && n < budget) {
-      if (COUNT) cnt.steps++;
-      ++n;
-      if (WIDE == 1 || (WIDE == 2 && wide_now)) {
-        float4 a0, a1, a2, b0, b1, b2; int4 ar; int2 br;
-        quad_load(quads + (size_t)cur * QUAD_F4, a0, a1, a2, ar, b0, b1, b2, br);
-        quad_step<COUNT>(a0, a1, a2, ar, b0, b1, b2, br, o, inv, t, stack, sp, cur, cnt.steps);
-        continue;
-      }
-      const float4 *nd = nodes + (size_t)cur * NODE_F4;
-      float4 n0 = nd[0], n1 = nd[1], n2 = nd[2];
-      const int2 n3 = node_refs(nd);
-      float tl, tr;
-      node_test(n0, n1, n2, o, inv, tl, tr);
-      bool hl = tl < t, hr = tr < t;
-      bool swap = tl > tr; // tracer.fs:384: right first only when strictly nearer
-      int nearRef = swap ? n3.y : n3.x;
-      int farRef = swap ? n3.x : n3.y;
-      if (hl && hr) {
-        stack[sp * WAVE] = farRef;
-        sp++;
-        cur = nearRef;
-      } else if (hl) {
-        cur = n3.x;
-      } else if (hr) {
-        cur = n3.y;
-      } else if (sp > 0) {
-        sp--;
-        cur = stack[sp * WAVE];
-      } else {
-        cur = REF_SENTINEL;
-      }
-    }
-    if (cur >= 0 || cur == REF_SENTINEL) break; // out of budget on an interior node / finished
-    if (COUNT) { cnt.steps++; cnt.leaves++; }
-    ++n;
-    process_leaf(leaves, leaf_size, ~cur, o, d, t, hit);
-    if (sp > 0) { sp--; cur = stack[sp * WAVE]; }
-    else cur = REF_SENTINEL;
-    if (anyhit && hit != -1) cur = REF_SENTINEL;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Texture fetches (sampler state: main.js:170-180, 548-559)
-// ---------------------------------------------------------------------------
-// (float)b / 255.0f, exactly (verified for all 256 bytes: one Newton step on
-// the rounded reciprocal is correctly rounded for these operands)
-FM_DEV float unorm8(uint32_t b) {
-  const float rc = 1.0f / 255.0f;
-  float x = (float)b;
-  float q = x * rc;
-  float r = fma_(-q, 255.0f, x);
-  return fma_(r, rc, q);
-}
-FM_DEV int wrap_repeat(int i, int n) { int m = i % n; return m < 0 ? m + n : m; }
-FM_DEV int wrap_clamp(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
-FM_DEV float safe_floor_coord(float u) {
-  float f = floor_(u);
-  if (!(f > -1.0e9f && f < 1.0e9f)) f = 0.0f;
-  return f;
-}
-struct Tap4 { uint32_t t00, t10, t01, t11; float a, b; };
-// Texel (i, j) of a w-wide image stored in tiles of 2^WL2 x 2^HL2 texels (fspt_device.hpp): one tile = one 128-byte
-// cache line, so the 2 x 2 footprint of a bilinear fetch lies in 1.4 lines on average (8 x 4 tiles) instead of 2 rows = 2 lines.
-template <int WL2, int HL2>
-FM_DEV uint32_t tile_offset(int i, int j, int tiles_x) {
-  return (uint32_t)(((j >> HL2) * tiles_x + (i >> WL2)) << (WL2 + HL2)) + (uint32_t)(((j & ((1 << HL2) - 1)) << WL2) + (i & ((1 << WL2) - 1)));
-}
-// Footprint of a bilinear fetch at (s, t): the wrapped texel coordinates and the two weights.  Shared by the four atlas
-// layers a shading event reads at the same uv (tracer.fs:453-456): the wrap / floor arithmetic is done once.
-struct TexCoord { int i0, i1, j0, j1; float a, b; };
-FM_DEV TexCoord bilinear_coord(int w, int h, float s, float t, bool repeat_t) {
-  TexCoord c;
-  float u = fma_(s, (float)w, -0.5f), v = fma_(t, (float)h, -0.5f);
-  float fu = safe_floor_coord(u), fv = safe_floor_coord(v);
-  float a = u - fu, b = v - fv;
-  if (!(a >= 0.0f && a <= 1.0f)) a = 0.0f;
-  if (!(b >= 0.0f && b <= 1.0f)) b = 0.0f;
-  int i0 = (int)fu, j0 = (int)fv;
-  c.i1 = wrap_repeat(i0 + 1, w);
-  c.i0 = wrap_repeat(i0, w);
-  if (repeat_t) { c.j1 = wrap_repeat(j0 + 1, h); c.j0 = wrap_repeat(j0, h); }
-  else { c.j1 = wrap_clamp(j0 + 1, h); c.j0 = wrap_clamp(j0, h); }
-  c.a = a; c.b = b;
-  return c;
-}
-// ... and its four texel offsets in a single-layer image (8 x 4-texel tiles)
-struct TapGeom { uint32_t o00, o10, o01, o11; float a, b; bool pair; };
-FM_DEV TapGeom tap_geom(const TexCoord &c, int w) {
-  TapGeom g;
-  const int tiles_x = (w + TEX_TILE_W - 1) >> TEX_TILE_W_LOG2;
-  g.o00 = tile_offset<TEX_TILE_W_LOG2, TEX_TILE_H_LOG2>(c.i0, c.j0, tiles_x);
-  g.o01 = tile_offset<TEX_TILE_W_LOG2, TEX_TILE_H_LOG2>(c.i0, c.j1, tiles_x);
-  g.o10 = tile_offset<TEX_TILE_W_LOG2, TEX_TILE_H_LOG2>(c.i1, c.j0, tiles_x);
-  g.o11 = tile_offset<TEX_TILE_W_LOG2, TEX_TILE_H_LOG2>(c.i1, c.j1, tiles_x);
-  // the two taps of a row are neighbours unless the column wraps or leaves the tile: one 8-byte load (dword-aligned)
-  // instead of two 4-byte loads - half the lane-requests on the vector-memory pipeline, same texel values
-  g.pair = FSPT_TAP2 && c.i1 == c.i0 + 1 && (TEX_TILE_W == 1 || (c.i0 & (TEX_TILE_W - 1)) != TEX_TILE_W - 1);
-  g.a = c.a; g.b = c.b;
-  return g;
-}
-FM_DEV Tap4 fetch_taps(const uint32_t *texels, const TapGeom &g) {
-  Tap4 r;
-  typedef uint32_t u2a __attribute__((ext_vector_type(2), aligned(4)));
-  if (g.pair) {
-    u2a q0 = *reinterpret_cast<const u2a *>(texels + g.o00), q1 = *reinterpret_cast<const u2a *>(texels + g.o01);
-    r.t00 = q0.x; r.t10 = q0.y; r.t01 = q1.x; r.t11 = q1.y;
-  } else {
-    r.t00 = texels[g.o00]; r.t10 = texels[g.o10];
-    r.t01 = texels[g.o01]; r.t11 = texels[g.o11];
-  }
-  r.a = g.a; r.b = g.b;
-  return r;
-}
-FM_DEV Tap4 bilinear_taps(const uint32_t *texels, int w, int h, float s, float t, bool repeat_t) {
-  return fetch_taps(texels, tap_geom(bilinear_coord(w, h, s, t, repeat_t), w));
-}
 // The environment map (REPEAT in s, CLAMP in t) in OVERLAPPING 8 x 4-texel tiles: tile (a, b) holds texels
 // [7a, 7a + 8) x [3b, 3b + 4), columns wrapped and rows clamped when it was built, so the 2 x 2 footprint of EVERY lookup
 // lies in one 128-byte line (1.4 lines with disjoint tiles; the lookups are random, each line it touches is a miss more
@@ -437,24 +64,6 @@ FM_DEV Tap4 env_taps(const uint32_t *texels, int w, int h, float s, float t) {
   const u2a q0 = *reinterpret_cast<const u2a *>(texels + off), q1 = *reinterpret_cast<const u2a *>(texels + off + 8u);
   return Tap4{q0.x, q0.y, q1.x, q1.y, a, b};
 }
-FM_DEV float tap_channel(const Tap4 &tp, int ch) {
-  float t00 = unorm8((tp.t00 >> (8 * ch)) & 255u), t10 = unorm8((tp.t10 >> (8 * ch)) & 255u);
-  float t01 = unorm8((tp.t01 >> (8 * ch)) & 255u), t11 = unorm8((tp.t11 >> (8 * ch)) & 255u);
-  return lerp_(lerp_(t00, t10, tp.a), lerp_(t01, t11, tp.a), tp.b);
-}
-// One atlas layer of a material texture set in SEPARATE form: its tiled image, or - a layer whose texels are all equal
-// (TexturePacker fills a whole res x res layer for every flat colour once one image is in the atlas,
-// texture_packer.js:36-42) is not stored - its one texel: lerp(x, x, a) = fma(a, 0, x) = x exactly, so four equal taps
-// give the same bits as the fetch would.
-FM_DEV Tap4 layer_taps(const DScene &S, const TapGeom &g, uint32_t base_tiles, uint32_t texel) {
-  if (base_tiles == LAYER_CONST) {
-    Tap4 r;
-    r.t00 = r.t10 = r.t01 = r.t11 = texel;
-    r.a = g.a; r.b = g.b;
-    return r;
-  }
-  return fetch_taps(S.atlas + (size_t)base_tiles * (TEX_TILE_W * TEX_TILE_H), g);
-}
 // envSample + envColor (tracer.fs:410-419)
 template <bool COUNT>
 FM_DEV V3 env_sample(const DScene &S, V3 dir, float envTheta, Counters &cnt) {
@@ -471,20 +80,6 @@ FM_DEV V3 env_sample(const DScene &S, V3 dir, float envTheta, Counters &cnt) {
   float sc = exp2_(fma_(e, 255.0f, -128.0f));
   return v3(r * sc, g * sc, b * sc);
 }
-// The random numbers of a path (compile-time choice, fspt.h fspt_target_set_sampler): SMP_REF is the reference's rnd()
-// from its running float seed; SMP_SOBOL the Owen-scrambled Sobol sampler (fspt_math.hpp), whose dimension is the number
-// of values the sample has drawn so far - camera_ray dims 0..3, then shade_hit's calls in order.
-enum { SMP_REF = 0, SMP_SOBOL = 1 };
-template <int SMP>
-struct Rng {
-  float ref;                         // SMP_REF
-  uint32_t seed, pixel, sample, dim; // SMP_SOBOL
-  FM_DEV float next() {
-    if constexpr (SMP == SMP_SOBOL) return sobol_value(seed, pixel, sample, dim++);
-    else return rnd(ref);
-  }
-};
-
 // sampleEnv (tracer.fs:421-434)
 template <class R>
 FM_DEV void sample_env(const DScene &S, float envTheta, R &rng, V3 &dir, float &pdf) {
@@ -597,58 +192,6 @@ FM_DEV V3 eval_specular(V3 incident, V3 normal, V3 diffuse, float metallic, floa
 }
 
 // ---------------------------------------------------------------------------
-// Materials: texture(texArray, vec3(uv, layer)) x 4 (tracer.fs:453-456)
-// ---------------------------------------------------------------------------
-FM_DEV V3 unorm8_rgb(uint32_t q) { return v3(unorm8(q & 255u), unorm8((q >> 8) & 255u), unorm8((q >> 16) & 255u)); }
-FM_DEV V3 tap_rgb(const Tap4 &q) { return v3(tap_channel(q, 0), tap_channel(q, 1), tap_channel(q, 2)); }
-// The layers of material texture set `set` (hit record word 42; fspt_device.hpp TexSet) at uv (s, t), the four layers'
-// texels of ONE footprint: D texDiffuse, E texEmissive, R metallic and rough (not yet squared), N texNormal.  A layer
-// that is not asked for issues no load; the outputs of the others are left alone.
-template <bool D, bool E, bool R, bool N>
-FM_DEV void material(const DScene &S, uint32_t set, float s, float t, V3 &texDiffuse, V3 &texEmissive, float &metallic,
-                     float &rough, V3 &texNormal) {
-  const uint4 *tset = S.tex_sets + (size_t)set * 3;
-  const uint4 ts0 = tset[0], ts1 = tset[1];
-  if (ts0.x == TEXSET_CONST) {
-    // four flat colours (texture_packer.js:36-42; every material of a colours-only atlas): the four bilinear taps are
-    // the same texel and lerp(x, x, a) = fma(a, 0, x) = x exactly, so the filter arithmetic is skipped (bit-identical)
-    if (D) texDiffuse = unorm8_rgb(ts1.x);
-    if (E) texEmissive = unorm8_rgb(ts1.y);
-    if (R) { metallic = unorm8(ts1.z & 255u); rough = unorm8((ts1.z >> 8) & 255u); }
-    if (N) texNormal = v3((unorm8(ts1.w & 255u) - 0.5f) * 2.0f, (unorm8((ts1.w >> 8) & 255u) - 0.5f) * 2.0f,
-                          (unorm8((ts1.w >> 16) & 255u) - 0.0f) * 1.0f);
-    return;
-  }
-  const TexCoord tc = bilinear_coord((int)S.atlas_res, (int)S.atlas_res, s, t, true);
-  Tap4 qd, qe, qr, qn;
-  if (ts0.x == TEXSET_QUAD) {
-    // the four layers interleaved texel by texel (4 x 2-texel tiles of 16-byte texels): one 16-byte load per tap
-    // brings all four layers, and the footprint lies in 1.9 lines instead of 4 x 1.4
-    const uint4 *img = S.atlas4 + (size_t)ts0.y * 8u;
-    const int tiles_x = ((int)S.atlas_res + 3) >> 2;
-    const uint4 t00 = img[tile_offset<2, 1>(tc.i0, tc.j0, tiles_x)], t10 = img[tile_offset<2, 1>(tc.i1, tc.j0, tiles_x)];
-    const uint4 t01 = img[tile_offset<2, 1>(tc.i0, tc.j1, tiles_x)], t11 = img[tile_offset<2, 1>(tc.i1, tc.j1, tiles_x)];
-    qd = Tap4{t00.x, t10.x, t01.x, t11.x, tc.a, tc.b};
-    qe = Tap4{t00.y, t10.y, t01.y, t11.y, tc.a, tc.b};
-    qr = Tap4{t00.z, t10.z, t01.z, t11.z, tc.a, tc.b};
-    qn = Tap4{t00.w, t10.w, t01.w, t11.w, tc.a, tc.b};
-  } else {
-    // separate single-layer images (a set with one image layer, or sets beyond the interleaving budget): all loads
-    // of the image layers are issued before the first texel is decoded
-    const uint4 ts2 = tset[2];
-    const TapGeom tg = tap_geom(tc, (int)S.atlas_res);
-    if (D) qd = layer_taps(S, tg, ts2.x, ts1.x);
-    if (E) qe = layer_taps(S, tg, ts2.y, ts1.y);
-    if (R) qr = layer_taps(S, tg, ts2.z, ts1.z);
-    if (N) qn = layer_taps(S, tg, ts2.w, ts1.w);
-  }
-  if (D) texDiffuse = tap_rgb(qd);
-  if (E) texEmissive = tap_rgb(qe);
-  if (R) { metallic = tap_channel(qr, 0); rough = tap_channel(qr, 1); }
-  if (N) texNormal = v3((tap_channel(qn, 0) - 0.5f) * 2.0f, (tap_channel(qn, 1) - 0.5f) * 2.0f, (tap_channel(qn, 2) - 0.0f) * 1.0f);
-}
-
-// ---------------------------------------------------------------------------
 // Emitter sampling (fspt.h FSPT_LIGHTS_EMITTERS)
 // ---------------------------------------------------------------------------
 // emitted radiance 30 * texEmissive * texDiffuse (tracer.fs:467) of material texture set `set` at uv (s, t)
@@ -695,50 +238,6 @@ FM_DEV void light_sample(const DScene &S, V3 ro, float v, float u2, float u3, Li
 constexpr float LIGHT_T_SCALE = 1.0f - 1.0e-4f;
 
 // ---------------------------------------------------------------------------
-// camera.fs main (37-46) for pixel (x, y); SMP_SOBOL: sample `sample` of the sampler seeded `sseed`, dims 0..3
-// ---------------------------------------------------------------------------
-template <int SMP>
-FM_DEV void camera_ray(uint32_t x, uint32_t y, uint32_t W, uint32_t H, const CameraP &cam, float randBase, uint32_t sseed,
-                       uint32_t sample, V3 &o, V3 &d) {
-  float fx = (float)x + 0.5f, fy = (float)y + 0.5f;
-  float resx = (float)W, resy = (float)H;
-  float uvx = fma_(fx / resx, 2.0f, -1.0f), uvy = fma_(fy / resy, 2.0f, -1.0f);
-  Rng<SMP> rng{fma_(fx, resy, randBase) + fy, sseed, y * W + x, sample, 0u};
-  V3 Iv = v3(cam.I[0], cam.I[1], cam.I[2]), Pv = v3(cam.P[0], cam.P[1], cam.P[2]);
-  V3 basisX = normalize(cross(Iv, v3(0.0f, 1.0f, 0.0f)));
-  V3 basisY = normalize(cross(basisX, Iv));
-  float fov = cam.fov_scale;
-  float icx = uvx * (resx / resy), icy = uvy * 1.0f;
-  V3 screen;
-  screen.x = (fma_(icy * basisY.x, fov, (icx * basisX.x) * fov) + Iv.x) + Pv.x;
-  screen.y = (fma_(icy * basisY.y, fov, (icx * basisX.y) * fov) + Iv.y) + Pv.y;
-  screen.z = (fma_(icy * basisY.z, fov, (icx * basisX.z) * fov) + Iv.z) + Pv.z;
-  float theta = (rng.next() * M_PI_F) * 2.0f;
-  float r = sqrt_(rng.next()) * 1.414f;
-  float st, ct;
-  sincos_(theta, st, ct);
-  V3 aa;
-  aa.x = (r * ((basisX.x * ct) / resx + (basisY.x * st) / resy)) * fov;
-  aa.y = (r * ((basisX.y * ct) / resx + (basisY.y * st) / resy)) * fov;
-  aa.z = (r * ((basisX.z * ct) / resx + (basisY.z * st) / resy)) * fov;
-  float theta2 = (rng.next() * M_PI_F) * 2.0f;
-  float s2, c2;
-  sincos_(theta2, s2, c2);
-  float sq = sqrt_(rng.next());
-  float lx = cam.lens[0], ly = cam.lens[1];
-  V3 dof;
-  dof.x = (fma_(s2, basisY.x, c2 * basisX.x) * ly) * sq;
-  dof.y = (fma_(s2, basisY.y, c2 * basisX.y) * ly) * sq;
-  dof.z = (fma_(s2, basisY.z, c2 * basisX.z) * ly) * sq;
-  o = Pv + dof;
-  V3 tgt = v3(fma_(dof.x, lx, screen.x + aa.x), fma_(dof.y, lx, screen.y + aa.y), fma_(dof.z, lx, screen.z + aa.z));
-  d = normalize(tgt - o);
-}
-FM_DEV void camera_ray(uint32_t x, uint32_t y, uint32_t W, uint32_t H, const CameraP &cam, float randBase, V3 &o, V3 &d) {
-  camera_ray<SMP_REF>(x, y, W, H, cam, randBase, 0u, 0u, o, d);
-}
-
-// ---------------------------------------------------------------------------
 // Per-lane path state
 // ---------------------------------------------------------------------------
 struct Path {
@@ -757,48 +256,6 @@ struct Path {
   float lq;       // LIGHTS: q / pb of the vertex that cast the pending extension ray (0: its hit gets emission weight 1)
   float lt;       // LIGHTS: t bound of the pending shadow ray (MAX_T: environment, below: an emitter point)
 };
-
-// The hit record of slot ti (192 B = 3 whole cache lines) and what shade_hit and first_hit_guides compute from it before
-// shading: the hit point of ray (ro, rd) at tHit, its barycentric weights and its texture coordinates
-struct HitGeom {
-  V3 v1, e1, e2;                         // the triangle: its first vertex and two edges
-  V3 n1, t1, b1, n2, t2, b2, n3, t3, b3; // the vertices' normal, tangent and bitangent
-  uint32_t set;                          // the triangle's material texture set (hit record word 42)
-  float ior, dielectric;
-  V3 origin, w;                          // the hit point and its barycentric weights
-  float tcx, tcy;                        // its texture coordinates
-};
-FM_DEV void hit_geom(const DScene &S, int ti, V3 ro, V3 rd, float tHit, HitGeom &g) {
-  const float4 *hp = S.hitrec + (size_t)ti * HITREC_F4;
-  const float4 h0 = hp[0], h1 = hp[1], h2 = hp[2], h3 = hp[3], h4 = hp[4], h5 = hp[5], h6 = hp[6], h7 = hp[7], h8 = hp[8],
-               h9 = hp[9], h10 = hp[10], h11 = hp[11];
-  g.v1 = v3(h0.x, h0.y, h0.z); g.e1 = v3(h0.w, h1.x, h1.y); g.e2 = v3(h1.z, h1.w, h2.x);
-  g.n1 = v3(h2.y, h2.z, h2.w); g.t1 = v3(h3.x, h3.y, h3.z); g.b1 = v3(h3.w, h4.x, h4.y);
-  g.n2 = v3(h4.z, h4.w, h5.x); g.t2 = v3(h5.y, h5.z, h5.w); g.b2 = v3(h6.x, h6.y, h6.z);
-  g.n3 = v3(h6.w, h7.x, h7.y); g.t3 = v3(h7.z, h7.w, h8.x); g.b3 = v3(h8.y, h8.z, h8.w);
-  g.set = __float_as_uint(h10.z); g.ior = h11.z; g.dielectric = h11.w;
-  g.origin = vfma(rd, tHit, ro);
-  // barycentricWeights (tracer.fs:339-353); v0 = e1, v1 = e2
-  const V3 vv2 = g.origin - g.v1;
-  const float d00 = dot(g.e1, g.e1), d01 = dot(g.e1, g.e2), d11 = dot(g.e2, g.e2);
-  const float d20 = dot(vv2, g.e1), d21 = dot(vv2, g.e2);
-  const float invDenom = 1.0f / fma_(d00, d11, -(d01 * d01));
-  const float bv = fma_(d11, d20, -(d01 * d21)) * invDenom;
-  const float bw = fma_(d00, d21, -(d01 * d20)) * invDenom;
-  g.w = v3((1.0f - bv) - bw, bv, bw);
-  g.tcx = fma_(g.w.z, h10.x, fma_(g.w.y, h9.z, g.w.x * h9.x));
-  g.tcy = fma_(g.w.z, h10.y, fma_(g.w.y, h9.w, g.w.x * h9.y));
-}
-// macroNormal: texNormal in the interpolated tangent frame (tracer.fs:457-460), before the `inside` flip; baryNormal is
-// the interpolated vertex normal
-FM_DEV V3 macro_normal(const HitGeom &g, V3 texNormal, V3 &baryNormal) {
-  baryNormal = bary3(g.w, g.n1, g.n2, g.n3);
-  const V3 baryTangent = bary3(g.w, g.t1, g.t2, g.t3);
-  const V3 baryBitangent = bary3(g.w, g.b1, g.b2, g.b3);
-  return normalize(v3(fma_(texNormal.z, baryNormal.x, fma_(texNormal.y, baryBitangent.x, texNormal.x * baryTangent.x)),
-                      fma_(texNormal.z, baryNormal.y, fma_(texNormal.y, baryBitangent.y, texNormal.x * baryTangent.y)),
-                      fma_(texNormal.z, baryNormal.z, fma_(texNormal.y, baryBitangent.z, texNormal.x * baryTangent.z))));
-}
 
 // tracer.fs:447-499: shade the hit (t, tri) of ray (ro, rd); sets up the next
 // shadow + extension rays in `ps`.
@@ -2394,53 +1851,10 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_tile_pack(const TilePackP p) 
   }
 }
 
-// camera.fs as a stand-alone pass (drawCamera, main.js:741-756)
-template <int SMP>
-__global__ __launch_bounds__(BLOCK_THREADS) void k_camera(uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, CameraP cam,
-                                                         float randBase, uint32_t sseed, uint32_t sample, float4 *pos, float4 *dir) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= W * H) return;
-  uint32_t x = i % W, y = i / W;
-  if (x >= vw || y >= vh) return; // outside gl.viewport: the ray textures keep their old texels
-  V3 o, d;
-  camera_ray<SMP>(x, y, W, H, cam, randBase, sseed, sample, o, d);
-  pos[i] = make_float4(o.x, o.y, o.z, 1.0f);
-  dir[i] = make_float4(d.x, d.y, d.z, 1.0f);
-}
-
-// the Sobol sampler's device function for n (pixel, sample, dim) triples (fspt_sampler_eval, a test hook)
-__global__ void k_sampler_eval(uint32_t seed, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim, uint32_t n, float *out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = sobol_value(seed, pixel[i], sample[i], dim[i]);
-}
-
-// intersectScene as a stand-alone pass
-__global__ __launch_bounds__(BLOCK_THREADS) void k_intersect(const IntersectP p) {
-  extern __shared__ int lds_stack[];
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wave = threadIdx.x / WAVE;
-  int *stack = lds_stack + (size_t)wave * p.scene.stack_n * WAVE + lane;
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= p.n) return;
-  V3 o = v3(p.rays[i * 6], p.rays[i * 6 + 1], p.rays[i * 6 + 2]);
-  V3 d = v3(p.rays[i * 6 + 3], p.rays[i * 6 + 4], p.rays[i * 6 + 5]);
-  Counters cnt = {0, 0, 0, 0, 0, 0};
-  int hitA, hitB;
-  float tB;
-  if (p.wide) trace_rays<true, false, true>(p.scene, stack, o, false, d, d, hitA, tB, hitB, cnt);
-  else trace_rays<true, false>(p.scene, stack, o, false, d, d, hitA, tB, hitB, cnt);
-  p.t_out[i] = tB;
-  p.index_out[i] = slot_to_tri(p.scene, hitB); // the reference's triangle index (tracer.fs:360)
-  if (p.steps_out) p.steps_out[i] = cnt.steps;
-  if (p.leaves_out) p.leaves_out[i] = cnt.leaves;
-}
-
 // bvh_test.fs main (224-232): traversal-step heat map of the camera rays, the reference's `mode=test`
 __global__ __launch_bounds__(BLOCK_THREADS) void k_bvh_test(const TraceP p) {
   extern __shared__ int lds_stack[];
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wave = threadIdx.x / WAVE;
-  int *stack = lds_stack + (size_t)wave * p.scene.stack_n * WAVE + lane;
+  int *stack = lane_stack(lds_stack, threadIdx.x, p.scene.stack_n);
   const uint32_t work_total = p.n_owned_tiles * p.tile * p.tile;
   uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
   uint32_t x, y;
@@ -2462,287 +1876,9 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_bvh_test(const TraceP p) {
   p.accum[pix] = o4;
 }
 
-__global__ void k_math(int op, const float *a, const float *b, uint32_t n, float *out) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float x = a[i], y = b ? b[i] : 0.0f, r = 0.0f;
-  switch (op) {
-    case 0: r = sin_(x); break;
-    case 1: r = cos_(x); break;
-    case 2: r = atan2_(x, y); break;
-    case 3: r = asin_(x); break;
-    case 4: r = exp2_(x); break;
-    case 5: r = x / y; break;
-    case 6: r = sqrt_(x); break;
-    case 7: { float sd = x; r = rnd(sd); break; }
-    case 8: r = fract_(x); break;
-    case 9: r = log2_(x); break;
-    case 10: r = pow_(x, y); break;
-    default: r = 0.0f;
-  }
-  out[i] = r;
-}
-
-// ---------------------------------------------------------------------------
-// Guided denoiser: the guide buffers of the first hit (the a-trous filter that reads them: fspt_post.hip).
-// ---------------------------------------------------------------------------
-// What shade_hit computes at hit (tHit, slot ti) of ray (ro, rd) before the `inside` flip: texDiffuse and macroNormal
-// (tracer.fs:447-470), through shade_hit's own helpers; only the diffuse and normal layers are fetched.
-FM_DEV void first_hit_guides(const DScene &S, V3 ro, V3 rd, float tHit, int ti, V3 &albedo, V3 &normal) {
-  HitGeom g;
-  hit_geom(S, ti, ro, rd, tHit, g);
-  V3 texEmissive, texNormal, baryNormal;
-  float metallic, rough;
-  material<true, false, false, true>(S, g.set, g.tcx, g.tcy, albedo, texEmissive, metallic, rough, texNormal);
-  normal = macro_normal(g, texNormal, baryNormal);
-}
-
-// fspt_rand_base_next on the device: the s-th value of the host stream seeded with `seed` (same integer steps, same one
-// rounding in the float multiply: bit-identical)
-FM_DEV float rand_base_step(uint64_t &st) {
-  uint64_t x = st;
-  x ^= x >> 12;
-  x ^= x << 25;
-  x ^= x >> 27;
-  st = x;
-  const uint64_t r = x * 2685821657736338717ULL;
-  return ((float)(r >> 40) * (1.0f / 16777216.0f)) * 10000.0f;
-}
-
-// One thread per pixel of the whole target (16 x 16-pixel blocks: a wave's camera rays start on a 16 x 4 patch), `samples`
-// camera rays each - exactly k_camera's ray for randBase r_s - traced to their closest hit with the wave's LDS stack like
-// k_intersect.  Per pixel: the float32 sums in sample order / samples of (texDiffuse, t) and (macroNormal, hit); a miss
-// counts as albedo (1, 1, 1), normal 0, depth MAX_T, hit 0.  (k_features_model below is a copy under a camera model: edit both.)
-__global__ __launch_bounds__(BLOCK_THREADS) void k_features(const FeatureP p) {
-  extern __shared__ int lds_stack[];
-  const uint32_t tid = threadIdx.y * blockDim.x + threadIdx.x;
-  const int lane = (int)(tid & (WAVE - 1));
-  const int wave = (int)(tid / WAVE);
-  const DScene &S = p.scene;
-  int *stack = lds_stack + (size_t)wave * S.stack_n * WAVE + lane;
-  const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-  if (x >= p.W || y >= p.H) return;
-  Counters cnt = {0, 0, 0, 0, 0, 0};
-  uint64_t st = p.seed;
-  float ar = 0.0f, ag = 0.0f, ab = 0.0f, z = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f, hits = 0.0f;
-  for (uint32_t s = 0; s < p.samples; ++s) {
-    const float rb = rand_base_step(st);
-    V3 o, d;
-    camera_ray(x, y, p.W, p.H, p.cam, rb, o, d);
-    int hitA, hitB;
-    float tB;
-    trace_rays<false, false>(S, stack, o, false, d, d, hitA, tB, hitB, cnt);
-    V3 a = v3(1.0f, 1.0f, 1.0f), n = v3(0.0f, 0.0f, 0.0f);
-    float h = 0.0f;
-    if (hitB >= 0) {
-      first_hit_guides(S, o, d, tB, hitB, a, n);
-      h = 1.0f;
-    }
-    ar += a.x; ag += a.y; ab += a.z; z += tB;
-    nx += n.x; ny += n.y; nz += n.z; hits += h;
-  }
-  const float fs = (float)p.samples;
-  const size_t i = (size_t)y * p.W + x;
-  p.feat[2 * i] = make_float4(ar / fs, ag / fs, ab / fs, z / fs);
-  p.feat[2 * i + 1] = make_float4(nx / fs, ny / fs, nz / fs, hits / fs);
-}
-
-// k_features under a camera model (fspt_target_set_camera_model): the same pass, its `samples` rays per pixel
-// from model_ray<SMP_REF, MODEL> (fspt_camera_model.hpp) instead of camera_ray, so that the guides follow the camera.
-// A COPY of k_features but for that one call (k_features itself stays byte for byte what it was): whatever changes in one
-// of the two kernels must change in the other.
-template <int MODEL>
-__global__ __launch_bounds__(BLOCK_THREADS) void k_features_model(const FeatureModelP pm) {
-  extern __shared__ int lds_stack[];
-  const FeatureP &p = pm.f;
-  const uint32_t tid = threadIdx.y * blockDim.x + threadIdx.x;
-  const int lane = (int)(tid & (WAVE - 1));
-  const int wave = (int)(tid / WAVE);
-  const DScene &S = p.scene;
-  int *stack = lds_stack + (size_t)wave * S.stack_n * WAVE + lane;
-  const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-  if (x >= p.W || y >= p.H) return;
-  Counters cnt = {0, 0, 0, 0, 0, 0};
-  uint64_t st = p.seed;
-  float ar = 0.0f, ag = 0.0f, ab = 0.0f, z = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f, hits = 0.0f;
-  for (uint32_t s = 0; s < p.samples; ++s) {
-    const float rb = rand_base_step(st);
-    V3 o, d;
-    model_ray<SMP_REF, MODEL>(x, y, p.W, p.H, p.cam, pm.cm, rb, 0u, 0u, o, d);
-    int hitA, hitB;
-    float tB;
-    trace_rays<false, false>(S, stack, o, false, d, d, hitA, tB, hitB, cnt);
-    V3 a = v3(1.0f, 1.0f, 1.0f), n = v3(0.0f, 0.0f, 0.0f);
-    float h = 0.0f;
-    if (hitB >= 0) {
-      first_hit_guides(S, o, d, tB, hitB, a, n);
-      h = 1.0f;
-    }
-    ar += a.x; ag += a.y; ab += a.z; z += tB;
-    nx += n.x; ny += n.y; nz += n.z; hits += h;
-  }
-  const float fs = (float)p.samples;
-  const size_t i = (size_t)y * p.W + x;
-  p.feat[2 * i] = make_float4(ar / fs, ag / fs, ab / fs, z / fs);
-  p.feat[2 * i + 1] = make_float4(nx / fs, ny / fs, nz / fs, hits / fs);
-}
-
-// ---- temporal accumulation (fspt_temporal_accumulate): the G-buffer pass (blend, clamp, variance: fspt_post.hip) ----
-// camera.fs's basis of a camera: basisX, basisY as camera_ray computes them (same float32 operations)
-FM_DEV void camera_basis(const CameraP &cam, V3 &Iv, V3 &Pv, V3 &basisX, V3 &basisY) {
-  Iv = v3(cam.I[0], cam.I[1], cam.I[2]); Pv = v3(cam.P[0], cam.P[1], cam.P[2]);
-  basisX = normalize(cross(Iv, v3(0.0f, 1.0f, 0.0f)));
-  basisY = normalize(cross(basisX, Iv));
-}
-// The G-buffer and motion pass: one thread per pixel of the whole target, 16 x 16-pixel blocks and the wave's LDS stack
-// like k_features.  The CENTRE ray - camera_ray without pixel jitter and without lens offset: o = P, d = normalize(screen -
-// P), `screen` by camera_ray's own operations - is traced to its closest hit; G = (t, slot bits, bv, bw), (macroNormal, hit).
-// The hit point's position in the PREVIOUS frame (the motion-origin snapshot's triangle of the same slot at the same
-// barycentric weights, or the point itself) is projected into the previous camera: M = (sx, sy, |v|, kind).
-__global__ __launch_bounds__(BLOCK_THREADS) void k_temporal_gbuffer(const TemporalGP p) {
-  extern __shared__ int lds_stack[];
-  const uint32_t tid = threadIdx.y * blockDim.x + threadIdx.x;
-  const int lane = (int)(tid & (WAVE - 1));
-  const int wave = (int)(tid / WAVE);
-  const DScene &S = p.scene;
-  int *stack = lds_stack + (size_t)wave * S.stack_n * WAVE + lane;
-  const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-  if (x >= p.W || y >= p.H) return;
-  const float fx = (float)x + 0.5f, fy = (float)y + 0.5f;
-  const float resx = (float)p.W, resy = (float)p.H;
-  const float uvx = fma_(fx / resx, 2.0f, -1.0f), uvy = fma_(fy / resy, 2.0f, -1.0f);
-  V3 Iv, Pv, basisX, basisY;
-  camera_basis(p.cam, Iv, Pv, basisX, basisY);
-  const float fov = p.cam.fov_scale;
-  const float icx = uvx * (resx / resy), icy = uvy * 1.0f;
-  V3 screen;
-  screen.x = (fma_(icy * basisY.x, fov, (icx * basisX.x) * fov) + Iv.x) + Pv.x;
-  screen.y = (fma_(icy * basisY.y, fov, (icx * basisX.y) * fov) + Iv.y) + Pv.y;
-  screen.z = (fma_(icy * basisY.z, fov, (icx * basisX.z) * fov) + Iv.z) + Pv.z;
-  const V3 o = Pv, d = normalize(screen - Pv);
-  Counters cnt = {0, 0, 0, 0, 0, 0};
-  int hitA, hitB;
-  float tB;
-  trace_rays<false, false>(S, stack, o, false, d, d, hitA, tB, hitB, cnt);
-  const size_t i = (size_t)y * p.W + x;
-  V3 n = v3(0.0f, 0.0f, 0.0f), xp = d;
-  float bv = 0.0f, bw = 0.0f;
-  const bool hit = hitB >= 0;
-  if (hit) {
-    HitGeom g;
-    hit_geom(S, hitB, o, d, tB, g);
-    V3 albedo, texEmissive, texNormal, baryNormal;
-    float metallic, rough;
-    material<true, false, false, true>(S, g.set, g.tcx, g.tcy, albedo, texEmissive, metallic, rough, texNormal);
-    n = macro_normal(g, texNormal, baryNormal);
-    bv = g.w.y; bw = g.w.z;
-    xp = g.origin; // o + t d
-    if (p.origin) { // where the same point of the same triangle was when fspt_scene_motion_begin took the snapshot
-      const float *mp = p.origin + (size_t)hitB * MOTION_FLOATS; // v1.xyz e1.xyz e2.xyz
-      xp = v3(fma_(bw, mp[6], fma_(bv, mp[3], mp[0])), fma_(bw, mp[7], fma_(bv, mp[4], mp[1])), fma_(bw, mp[8], fma_(bv, mp[5], mp[2])));
-    }
-  }
-  p.g[2 * i] = make_float4(hit ? tB : MAX_T, __int_as_float(hit ? hitB : -1), bv, bw);
-  p.g[2 * i + 1] = make_float4(n.x, n.y, n.z, hit ? 1.0f : 0.0f);
-  float4 m = make_float4(0.0f, 0.0f, 0.0f, TM_KIND_NONE);
-  if (p.has_prev) {
-    V3 I2, P2, bX, bY;
-    camera_basis(p.prev, I2, P2, bX, bY);
-    const V3 v = hit ? xp - P2 : d;
-    const float a = dot(v, I2) / dot(I2, I2);
-    if (a > 0.0f) {
-      const float den = a * p.prev.fov_scale;
-      const float jcx = dot(v, bX) / den, jcy = dot(v, bY) / den;
-      float sx = ((jcx * (resy / resx)) + 1.0f) * (resx * 0.5f) - 0.5f;
-      float sy = (jcy + 1.0f) * (resy * 0.5f) - 0.5f;
-      const float rx = floor_(sx + 0.5f), ry = floor_(sy + 0.5f);
-      if (abs_(sx - rx) <= TM_SNAP) sx = rx;
-      if (abs_(sy - ry) <= TM_SNAP) sy = ry;
-      m = make_float4(sx, sy, hit ? sqrt_(dot(v, v)) : 0.0f, hit ? TM_KIND_HIT : TM_KIND_MISS);
-    }
-  }
-  p.m[i] = m;
-}
-
-// ---- adaptive sampling (fspt_render_adaptive) -------------------------------------------------------------
-// One workgroup per active tile (list order).  Every thread sums its pixels (j = thread, thread + 256, ... of the tile,
-// row-major) in float64, the wave folds its 64 sums by shuffles and the four wave sums are added in wave order: the same
-// bits on every run.  E_T = sum over the tile's viewport pixels and 3 channels of r / (3 pixels), with
-// r = v / (I^2 + 0.01) and v = (B - S)^2 m (n - m) / n^2 = m (I - S)^2 / (n - m)  (B = (n I - m S) / (n - m)).
-// m = 0: no estimate, only S := I;  refresh: S := I as well (read once, written in the same pass).
-__global__ __launch_bounds__(BLOCK_THREADS) void k_adaptive_error(const AdaptiveP p) {
-  __shared__ double wsum[BLOCK_THREADS / WAVE];
-  const uint32_t g = p.list_in[blockIdx.x];
-  const uint32_t x0 = (g % p.tiles_x) * p.tile, y0 = (g / p.tiles_x) * p.tile;
-  const uint32_t wx = min(p.tile, p.vw - x0), wy = min(p.tile, p.vh - y0); // (listed tiles meet the viewport)
-  const bool est = p.m != 0u, store = p.refresh != 0u || !est;
-  const double scale = est ? (double)p.m / (double)(p.n - p.m) : 0.0;
-  double acc = 0.0;
-  for (uint32_t j = threadIdx.x; j < wx * wy; j += BLOCK_THREADS) {
-    const uint32_t y = y0 + j / wx, x = x0 + j % wx;
-    const size_t i = (size_t)y * p.W + x;
-    const float4 I = p.accum[i];
-    if (est) {
-      const float4 S = p.snap[i];
-      const double c[3] = {(double)I.x, (double)I.y, (double)I.z}, d[3] = {(double)I.x - (double)S.x, (double)I.y - (double)S.y,
-                                                                          (double)I.z - (double)S.z};
-#pragma unroll
-      for (int k = 0; k < 3; ++k) acc += (scale * (d[k] * d[k])) / (c[k] * c[k] + 0.01);
-    }
-    if (store) p.snap[i] = I;
-  }
-  if (!est) return;
-  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-  for (int off = WAVE / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off, WAVE);
-  if (lane == 0) wsum[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int w = 0; w < BLOCK_THREADS / WAVE; ++w) t += wsum[w];
-    p.err[g] = t / (3.0 * (double)(wx * wy));
-  }
-}
-
-// One workgroup of ADAPTIVE_SELECT_THREADS walks list_in in chunks: a tile retires when n = max_ticks or (n >= min_ticks
-// and E_T < target) - count[g] = n, err[g] keeps the E_T that retired it - and every other tile goes to list_out at its
-// rank among the kept ones (ballot + mbcnt inside a wave, the wave totals from LDS in wave order): ascending order, no
-// atomics.  *n_out = the kept tiles.
-#define ADAPTIVE_SELECT_THREADS 1024
-__global__ __launch_bounds__(ADAPTIVE_SELECT_THREADS) void k_adaptive_select(const AdaptiveP p) {
-  __shared__ uint32_t wcount[ADAPTIVE_SELECT_THREADS / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-  uint32_t base_out = 0;
-  for (uint32_t base = 0; base < p.n_in; base += ADAPTIVE_SELECT_THREADS) {
-    const uint32_t i = base + threadIdx.x;
-    bool keep = false;
-    uint32_t g = 0;
-    if (i < p.n_in) {
-      g = p.list_in[i];
-      const bool retire = p.n >= p.max_ticks || (p.n >= p.min_ticks && p.err[g] < p.target);
-      if (retire) p.count[g] = p.n;
-      keep = !retire;
-    }
-    const unsigned long long mask = __ballot(keep);
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-    if (lane == 0) wcount[wave] = (uint32_t)__popcll(mask);
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-    for (int w = 0; w < ADAPTIVE_SELECT_THREADS / WAVE; ++w) {
-      if (w < wave) before += wcount[w];
-      total += wcount[w];
-    }
-    if (keep) p.list_out[base_out + before + rank] = g;
-    base_out += total;
-    __syncthreads(); // (wcount is rewritten by the next chunk)
-  }
-  if (threadIdx.x == 0) *p.n_out = base_out;
-}
-
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-// Stacks deeper than the default 64 KB of dynamic LDS (trees deeper than ~31 levels under a 512-thread block) need the
-// per-kernel opt-in; gfx950 has 160 KB per CU.
 // ---- light table (fspt_target_set_lights) ----------------------------------------------------------------
 // w = A * mean over 16 stratified points (the 4 x 4 cell centres of the warped square, tri_point) of luma(Le), Rec. 709
 __global__ __launch_bounds__(BLOCK_THREADS) void k_light_weights(const DScene S, const uint32_t *slots, uint32_t n, float *w, float4 *rec) {
@@ -2782,20 +1918,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_light_eval(const DScene S, co
   o[0] = ls.x.x; o[1] = ls.x.y; o[2] = ls.x.z; o[3] = ls.pdf;
   o[4] = ls.le.x; o[5] = ls.le.y; o[6] = ls.le.z; o[7] = dot(v3(q[3], q[4], q[5]), ls.w);
 }
-
-template <class K>
-static hipError_t allow_lds(K kernel, size_t bytes) {
-  if (bytes <= 48u * 1024u) return hipSuccess;
-  return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-// `kernel` with `lds` bytes of dynamic LDS; the caller collects the launch's error with hipGetLastError
-template <class K, class P>
-static hipError_t launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const P &p) {
-  const hipError_t e = allow_lds(kernel, lds);
-  if (e == hipSuccess) hipLaunchKernelGGL(kernel, grid, block, lds, stream, p);
-  return e;
-}
-static size_t stack_bytes(const DScene &S) { return (size_t)WAVES_PER_BLOCK * S.stack_n * WAVE * sizeof(int); }
 
 // Variant dispatch: a runtime choice becomes the compile-time argument of f (a std::integral_constant, usable as a
 // template argument), and only the instantiations f names are compiled.
@@ -2955,25 +2077,6 @@ hipError_t launch_tile_pack(const TilePackP &p, bool unpack, hipStream_t stream)
   return hipGetLastError();
 }
 
-hipError_t launch_camera(uint32_t W, uint32_t H, uint32_t vw, uint32_t vh, const CameraP &cam, float rand_base, float4 *pos, float4 *dir,
-                         hipStream_t stream, uint32_t sampler, uint32_t smp_seed, uint32_t sample) {
-  uint32_t n = W * H;
-  const dim3 g((n + BLOCK_THREADS - 1) / BLOCK_THREADS), b(BLOCK_THREADS);
-  with_sampler(sampler, [&](auto M) {
-    const bool sobol = M == SMP_SOBOL; // (the reference sampler takes no seed and no sample number)
-    hipLaunchKernelGGL(k_camera<M>, g, b, 0, stream, W, H, vw, vh, cam, rand_base, sobol ? smp_seed : 0u, sobol ? sample : 0u, pos, dir);
-    return hipSuccess;
-  });
-  return hipGetLastError();
-}
-
-hipError_t launch_sampler_eval(uint32_t seed, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim, uint32_t n,
-                               float *out, hipStream_t stream) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_sampler_eval, dim3((n + 255) / 256), dim3(256), 0, stream, seed, pixel, sample, dim, n, out);
-  return hipGetLastError();
-}
-
 hipError_t launch_light_weights(const DScene &S, const uint32_t *slots, uint32_t n, float *w, float4 *rec, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_light_weights, dim3((n + BLOCK_THREADS - 1) / BLOCK_THREADS), dim3(BLOCK_THREADS), 0, stream, S, slots, n, w, rec);
@@ -2989,71 +2092,8 @@ hipError_t launch_light_eval(const DScene &S, const float *in, uint32_t n, int *
 hipError_t launch_bvh_test(const TraceP &p, hipStream_t stream) {
   uint32_t n = p.n_owned_tiles * p.tile * p.tile;
   if (n == 0) return hipSuccess;
-  hipError_t e = allow_lds(k_bvh_test, stack_bytes(p.scene));
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_bvh_test, dim3((n + BLOCK_THREADS - 1) / BLOCK_THREADS), dim3(BLOCK_THREADS), stack_bytes(p.scene),
-                     stream, p);
-  return hipGetLastError();
-}
-
-hipError_t launch_intersect(const IntersectP &p, hipStream_t stream) {
-  if (p.n == 0) return hipSuccess;
-  hipError_t e = allow_lds(k_intersect, stack_bytes(p.scene));
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_intersect, dim3((p.n + BLOCK_THREADS - 1) / BLOCK_THREADS), dim3(BLOCK_THREADS),
-                     stack_bytes(p.scene), stream, p);
-  return hipGetLastError();
-}
-
-hipError_t launch_math(int op, const float *a, const float *b, uint32_t n, float *out, hipStream_t stream) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_math, dim3((n + 255) / 256), dim3(256), 0, stream, op, a, b, n, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_features(const FeatureP &p, hipStream_t stream) {
-  const size_t lds = stack_bytes(p.scene);
-  hipError_t e = allow_lds(k_features, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_features, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), lds, stream, p);
-  return hipGetLastError();
-}
-
-template <int MODEL>
-static hipError_t launch_features_model_as(const FeatureModelP &p, hipStream_t stream) {
-  const size_t lds = stack_bytes(p.f.scene);
-  hipError_t e = allow_lds(k_features_model<MODEL>, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_features_model<MODEL>, dim3((p.f.W + 15) / 16, (p.f.H + 15) / 16), dim3(16, 16), lds, stream, p);
-  return hipGetLastError();
-}
-hipError_t launch_features_model(const FeatureModelP &p, hipStream_t stream) {
-  switch (p.cm.model) {
-    case CAM_ORTHO: return launch_features_model_as<CAM_ORTHO>(p, stream);
-    case CAM_FISHEYE: return launch_features_model_as<CAM_FISHEYE>(p, stream);
-    case CAM_EQUIRECT: return launch_features_model_as<CAM_EQUIRECT>(p, stream);
-    case CAM_STEREO: return launch_features_model_as<CAM_STEREO>(p, stream);
-    default: return hipErrorInvalidValue; // (the pinhole camera: launch_features)
-  }
-}
-
-hipError_t launch_temporal_gbuffer(const TemporalGP &p, hipStream_t stream) {
-  const size_t lds = stack_bytes(p.scene);
-  hipError_t e = allow_lds(k_temporal_gbuffer, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_temporal_gbuffer, dim3((p.W + 15) / 16, (p.H + 15) / 16), dim3(16, 16), lds, stream, p);
-  return hipGetLastError();
-}
-
-hipError_t launch_adaptive_error(const AdaptiveP &p, hipStream_t stream) {
-  if (p.n_in == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_adaptive_error, dim3(p.n_in), dim3(BLOCK_THREADS), 0, stream, p);
-  return hipGetLastError();
-}
-
-hipError_t launch_adaptive_select(const AdaptiveP &p, hipStream_t stream) {
-  hipLaunchKernelGGL(k_adaptive_select, dim3(1), dim3(ADAPTIVE_SELECT_THREADS), 0, stream, p);
-  return hipGetLastError();
+  const hipError_t e = launch(k_bvh_test, dim3((n + BLOCK_THREADS - 1) / BLOCK_THREADS), dim3(BLOCK_THREADS), stack_bytes(p.scene), stream, p);
+  return e != hipSuccess ? e : hipGetLastError();
 }
 
 } // namespace fspt

@@ -192,11 +192,7 @@ int fspt_features(fspt_target *t, const fspt_camera_params *cam, uint32_t sample
   p.seed = seed;
   p.feat = t->feat;
   t->feat_valid = false;
-  if (t->cam_model.model != FSPT_CAMERA_PINHOLE) { // the sibling kernel: the guides follow the camera
-    fspt::FeatureModelP pm{p, t->cam_model};
-    HIP_TRY(fspt::launch_features_model(pm, t->stream));
-  } else
-  HIP_TRY(fspt::launch_features(p, t->stream));
+  HIP_TRY(fspt::launch_features(p, t->cam_model, t->stream)); // (the guides follow the camera model)
   t->feat_valid = true;
   return FSPT_OK;
 }

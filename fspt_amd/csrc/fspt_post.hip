@@ -1,6 +1,6 @@
-// fspt_post.hip - the image-space kernels of libfspt: the device side of fspt_post.cpp.  The rule that divides the two
-// kernel files: fspt_kernels.hip holds whatever reads a DScene (traversal, shading, the renderers, and the two passes of
-// the image chain that trace rays: k_features, k_temporal_gbuffer); this file holds whatever reads only images - the draw,
+// fspt_post.hip - the image-space kernels of libfspt: the device side of fspt_post.cpp.  The rule that divides the kernel
+// files: whatever reads a DScene is fspt_kernels.hip (the renderers) or fspt_passes.hip (the stand-alone passes, among them
+// the two of the image chain that trace rays: k_features, k_temporal_gbuffer); this file holds whatever reads only images - the draw,
 // bloom, auto-exposure, the a-trous filter, the temporal blend, the history clamp and the SVGF variance estimate - with
 // their launchers.  Nothing the path tracer's benchmark times lives here.
 #include "fspt_device.hpp"
@@ -351,7 +351,7 @@ __global__ __launch_bounds__(EXPOSURE_BINS) void k_exposure_resolve(uint32_t *hi
   state->valid = 1u;
 }
 
-// ---- guided denoiser: the a-trous filter; its guide buffers come from k_features (fspt_kernels.hip) -----------------
+// ---- guided denoiser: the a-trous filter; its guide buffers come from k_features (fspt_passes.hip) -----------------
 // One iteration of the edge-avoiding a-trous filter (include/fspt.h): 5 x 5 B3 taps `step` pixels apart,
 // weighted by luminance, normal and depth similarity; 16 x 16-pixel blocks, every tap read through the caches.  The first
 // iteration reads the accumulator and divides the albedo out on the fly (u0 = c / max(a, 1e-3)); the last multiplies

@@ -89,7 +89,7 @@ int fspt_scene_read_skin(fspt_scene *s, float *tri, float *norm);
 int fspt_scene_last_skin_ms(fspt_scene *s, float *skin_ms, float *refit_ms, uint32_t *launches, uint64_t *bytes);
 int fspt_skin_check_eval(const fspt_skin_desc *d, uint32_t n_tris, uint64_t *bad_index);
 int fspt_skin_set_form(int form);
-/* Camera models, measurement hook: k_camera_model of the target's model (FSPT_E_STATE under pinhole) `reps` times
+/* Camera models, measurement hook: k_camera of the target's model (FSPT_E_STATE under pinhole) `reps` times
  * into the ray buffers on the target's stream between two HIP events; *ms_per_launch = their distance / reps.  Blocking; a flush
  * point; the ray buffers are overwritten (a recorded fspt_camera call's rays are made again on demand; injected rays are gone:
  * fspt_set_rays again before the next fspt_trace). */

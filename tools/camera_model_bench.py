@@ -8,9 +8,9 @@ is a warm-up and not timed).  One JSON line, medians of --reps:
   msamples_s           render(ticks) + sync in Msamples/s for "pinhole" (batched, today's default), "pinhole_per_tick" (the
                        two-call form undeferred, tick(): one fused tick per launch sequence - what the per-tick route is expected to
                        sit near) and the
-                       four models (k_camera_model + the single-tick trace from the ray buffers, per tick)
+                       four models (k_camera + the single-tick trace from the ray buffers, per tick)
   over_per_tick        a model's rate / pinhole_per_tick's;  over_batched: / pinhole's (the gap batched ray buffers would close)
-  camera_ms, gb_s      k_camera_model alone (fspt_camera_model_time: HIP events around 64 launches) and its store rate at 32
+  camera_ms, gb_s      the model's k_camera alone (fspt_camera_model_time: HIP events around 64 launches) and its store rate at 32
                        bytes per pixel; hbm_frac against bench.py's 8 TB/s"""
 import argparse
 import ctypes as C

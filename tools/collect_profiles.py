@@ -2,7 +2,9 @@
 """Derive the committed profile files from a tools/prof_session.sh session.
     python tools/collect_profiles.py <tag> <workload-key> [<tag> <workload-key> ...]
  -> profiles/<round>/<tag>_kernel_stats.csv, <tag>_bench.json.log, <tag>_pmc_summary.txt and profiles/hbm_traffic.json
-    (bytes per sample per kernel, stamped with the hash of the kernel sources the numbers were measured on)."""
+    (bytes per sample per kernel, stamped with the hash of the kernel sources the numbers were measured on).
+The stamp (bench.source_sha) hashes a fixed list of files that does not name the device headers fspt_kernels.hip includes:
+re-collect after editing fspt_traverse.hpp, fspt_surface.hpp or fspt_camera_model.hpp - the old numbers would stay attached."""
 import collections, csv, glob, json, os, re, shutil, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench

@@ -1,10 +1,11 @@
 #!/bin/bash
-# Per-kernel register / scratch / occupancy table of the two kernel files, fspt_kernels.hip and fspt_post.hip, and of
-# fspt_pose.hip (k_pose_transform; k_skin_transform) and fspt_camera.hip (k_camera_model)
+# Per-kernel register / scratch / occupancy table of the three kernel files - fspt_kernels.hip (the renderers), fspt_passes.hip
+# (the stand-alone passes: k_camera, k_intersect, k_features, k_temporal_gbuffer, k_adaptive_*, the test hooks) and
+# fspt_post.hip (the image chain) - and of fspt_pose.hip (k_pose_transform; k_skin_transform)
 # (hipcc -Rpass-analysis=kernel-resource-usage), demangled, in one table.
 # usage: tools/kernel_resources.sh [extra -D flags]
 cd "$(dirname "$0")/.." || exit 1
-for f in fspt_kernels fspt_post fspt_pose fspt_camera; do
+for f in fspt_kernels fspt_passes fspt_post fspt_pose; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off ${AB_SLP:--fno-slp-vectorize} -std=c++17 -Wno-unused-value -c --cuda-device-only \
     -Rpass-analysis=kernel-resource-usage "$@" fspt_amd/csrc/$f.hip -o /tmp/${f}_res.o 2>&1
 done |

@@ -77,6 +77,23 @@ class SkyParams(C.Structure):
                 ("gain", C.c_float), ("ground_albedo", C.c_float * 3), ("view_samples", C.c_uint32), ("light_samples", C.c_uint32)]
 
 
+class TextureImage(C.Structure):
+    """fspt_texture_image: RGBA8, row 0 = top; host memory, or the scene's device memory in the _device entries"""
+    _fields_ = [("rgba", C.c_void_p), ("w", C.c_uint32), ("h", C.c_uint32)]
+
+
+class TextureLayer(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("color", C.c_float * 3), ("image", C.c_uint32), ("corrected", C.c_uint32), ("swizzle", C.c_uint8 * 4)]
+
+
+class TexturePack(C.Structure):
+    _fields_ = [("images", C.POINTER(TextureImage)), ("n_images", C.c_uint32), ("layers", C.POINTER(TextureLayer)), ("n_layers", C.c_uint32),
+                ("res", C.c_uint32)]
+
+
+TEXLAYER_COLOR, TEXLAYER_IMAGE, TEXLAYER_PIXELS = 0, 1, 2
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("target_rel_mse", C.c_double), ("max_ticks", C.c_uint32), ("min_ticks", C.c_uint32), ("round_ticks", C.c_uint32)]
 
@@ -154,6 +171,16 @@ SIGNATURES = {
     "fspt_scene_update_environment": (C.c_int, [_VP, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, _U32, C.c_uint32]),
     "fspt_multi_update_materials": (C.c_int, [_VP, _F, _F, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]),
     "fspt_multi_update_environment": (C.c_int, [_VP, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, _U32, C.c_uint32]),
+    "fspt_texture_decode_tables": (C.c_int, [_F, _F]),
+    "fspt_atlas_pack_gpu": (C.c_int, [C.c_int, C.POINTER(TexturePack), C.POINTER(C.c_uint8)]),
+    "fspt_atlas_pack_last_ms": (C.c_int, [_F, _F, _F]),
+    "fspt_texture_pack_check_eval": (C.c_int, [C.POINTER(TexturePack), _U32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "fspt_scene_update_textures": (C.c_int, [_VP, _F, _F, C.POINTER(TexturePack)]),
+    "fspt_scene_update_textures_device": (C.c_int, [_VP, _F, _F, C.POINTER(TexturePack)]),
+    "fspt_scene_patch_textures": (C.c_int, [_VP, _U32, C.c_uint32, C.POINTER(TexturePack)]),
+    "fspt_scene_patch_textures_device": (C.c_int, [_VP, _U32, C.c_uint32, C.POINTER(TexturePack)]),
+    "fspt_multi_update_textures": (C.c_int, [_VP, _F, _F, C.POINTER(TexturePack)]),
+    "fspt_multi_patch_textures": (C.c_int, [_VP, _U32, C.c_uint32, C.POINTER(TexturePack)]),
     "fspt_scene_read_appearance": (C.c_int, [_VP, C.c_int, _VP, C.c_uint64, C.POINTER(C.c_uint64)]),
     "fspt_scene_last_appearance_ms": (C.c_int, [_VP, _F, _U32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fspt_texset_classify_eval": (C.c_int, [_F, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), _U32, _U32, _U32, _U32, C.c_uint32]),

@@ -109,10 +109,41 @@ void appearance_release(fspt_scene *s) {
   for (hipEvent_t &e : s->ap.ev) if (e) { hipEventDestroy(e); e = nullptr; }
 }
 
-int appearance_materials(fspt_scene *s, const float *mat, const float *uv, const uint8_t *atlas, uint32_t res, uint32_t layers) {
-  const char *fn = "fspt_scene_update_materials";
+// The scene's current matTex as far as an appearance update reads it, in the current leaf order, from what the device
+// holds: the four layer ids of every triangle's set (A.keys, the sets of the last materials call, behind the set index in
+// its hit record), ior and dielectric (floats 46, 47).  A rebuild moves the records with their triangles, so this is the
+// current order whatever happened since.
+static int ap_current_mat(fspt_scene *s, const char *fn, std::vector<float> &mat) {
+  const fspt_scene::Appearance &A = s->ap;
+  const uint32_t T = s->n_tris;
+  std::vector<uint32_t> slot_tri(s->n_slots);
+  std::vector<float> rec(s->n_slots * 12);
+  HIP_TRY(hipMemcpy(slot_tri.data(), s->slot_tri, s->n_slots * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy2D(rec.data(), 48, (const char *)s->shade + 144, 192, 48, s->n_slots, hipMemcpyDeviceToHost));
+  mat.assign((size_t)T * 12, 0.0f);
+  for (size_t sl = 0; sl < s->n_slots; ++sl) {
+    const uint32_t ti = slot_tri[sl];
+    if (ti >= T) continue;
+    uint32_t set = 0;
+    std::memcpy(&set, &rec[sl * 12 + 6], 4);
+    if (set >= A.keys.size()) { fspt_set_error("%s: a hit record names texture set %u, the last materials call made %zu", fn, set, A.keys.size()); return FSPT_E_STATE; }
+    float *m = &mat[(size_t)ti * 12];
+    m[0] = (float)A.keys[set][0]; m[1] = (float)A.keys[set][1]; m[3] = (float)A.keys[set][2]; m[2] = (float)A.keys[set][3];
+    m[9] = rec[sl * 12 + 10]; m[10] = rec[sl * 12 + 11];
+  }
+  return FSPT_OK;
+}
+
+int appearance_materials(fspt_scene *s, const float *mat, const float *uv, const uint8_t *atlas, uint32_t res, uint32_t layers, const ApTextures *tx) {
+  const char *fn = tx ? tx->fn : "fspt_scene_update_materials";
   fspt_scene::Appearance &A = s->ap;
   const uint32_t T = s->n_tris;
+  const bool patch = tx && tx->layer_ids;
+  std::vector<float> cur_mat;
+  if (patch) { // (the retained atlas exists: the caller has looked)
+    if (const int rc = ap_current_mat(s, fn, cur_mat)) return rc;
+    mat = cur_mat.data();
+  }
   hipStream_t st = nullptr;
   int rc = ap_events(s);
   if (rc) return rc;
@@ -126,29 +157,48 @@ int appearance_materials(fspt_scene *s, const float *mat, const float *uv, const
   void *raw = A.raw;
   std::vector<uint8_t> is_const = A.is_const;
   std::vector<uint32_t> first = A.first;
-  if (atlas) {
+  if (tx) { res = tx->p->res; layers = patch ? A.raw_layers : tx->p->n_layers; }
+  if (atlas || tx) {
+    // a new raw atlas of this call's own: the caller's bytes, or packed here on the device from the caller's
+    // sources - a patch packs its layers into a copy of the retained one, and only their flags are asked for again
     const size_t per_layer = (size_t)res * res, bytes = per_layer * layers * 4;
+    const uint32_t n_flag = patch ? tx->p->n_layers : layers;
     uint32_t *d_flag = nullptr;
     e = hold.make(&raw, bytes);
-    if (e == hipSuccess) e = hold.make((void **)&d_flag, (size_t)layers * 8);
-    if (e == hipSuccess) e = hipMemcpy(raw, atlas, bytes, hipMemcpyHostToDevice);
-    uploaded += bytes;
-    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, (size_t)layers * 8, st);
+    if (e == hipSuccess) e = hold.make((void **)&d_flag, (size_t)n_flag * 8);
+    if (atlas) {
+      if (e == hipSuccess) e = hipMemcpy(raw, atlas, bytes, hipMemcpyHostToDevice);
+      uploaded += bytes;
+    } else {
+      if (e == hipSuccess && patch) e = hipMemcpyAsync(raw, A.raw, bytes, hipMemcpyDeviceToDevice, st);
+      if (e == hipSuccess) {
+        e = texpack_launch(hold, tx->p, tx->on_device, tx->layer_ids, (uint32_t *)raw, st, A.ev[0], &uploaded, &launches);
+        ev0 = e == hipSuccess;
+      }
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, (size_t)n_flag * 8, st);
     begin();
     if (e == hipSuccess) {
       const uint32_t bx = std::min<uint32_t>(ap_blocks(per_layer), 1024u);
-      for (uint32_t l0 = 0; l0 < layers; l0 += 65535u) { // (grid.y <= 65535)
+      for (uint32_t l0 = 0; !patch && l0 < layers; l0 += 65535u) { // (grid.y <= 65535)
         const uint32_t nl = std::min<uint32_t>(layers - l0, 65535u);
         hipLaunchKernelGGL(k_ap_layer_const, dim3(bx, nl), dim3(AP_BS), 0, st, (const uint32_t *)raw + (size_t)l0 * per_layer, per_layer, d_flag + 2 * (size_t)l0);
         ++launches;
       }
+      for (uint32_t k = 0; patch && k < n_flag; ++k) {
+        hipLaunchKernelGGL(k_ap_layer_const, dim3(bx, 1), dim3(AP_BS), 0, st, (const uint32_t *)raw + (size_t)tx->layer_ids[k] * per_layer, per_layer, d_flag + 2 * (size_t)k);
+        ++launches;
+      }
       e = hipGetLastError();
     }
-    std::vector<uint32_t> flags((size_t)layers * 2, 0u);
+    std::vector<uint32_t> flags((size_t)n_flag * 2, 0u);
     if (e == hipSuccess) e = hipMemcpy(flags.data(), d_flag, flags.size() * 4, hipMemcpyDeviceToHost); // (waits for the kernel)
-    if (e != hipSuccess) return ap_fail(fn, e);
-    is_const.assign(layers, 0); first.assign(layers, 0u);
-    for (uint32_t l = 0; l < layers; ++l) { is_const[l] = flags[2 * l] == 0u; first[l] = flags[2 * l + 1]; }
+    if (e != hipSuccess) { (void)hipStreamSynchronize(st); return ap_fail(fn, e); } // (nothing in flight reads a buffer `hold` frees)
+    if (!patch) { is_const.assign(layers, 0); first.assign(layers, 0u); }
+    for (uint32_t k = 0; k < n_flag; ++k) {
+      const uint32_t l = patch ? tx->layer_ids[k] : k;
+      is_const[l] = flags[2 * k] == 0u; first[l] = flags[2 * k + 1];
+    }
   } else {
     res = A.raw_res; layers = A.raw_layers;
   }
@@ -208,7 +258,8 @@ int appearance_materials(fspt_scene *s, const float *mat, const float *uv, const
   hold.take(n_atlas); hold.take(n_atlas4); hold.take(n_tab);
   atlas_install(s, n_atlas, single_bytes, n_atlas4, pl.quad_bytes, n_tab, n_sets, res, layers); // (frees the old three)
   s->has_dielectric = has_dielectric;
-  if (atlas) { // ... and the retained raw atlas after them
+  A.keys = pl.keys;
+  if (atlas || tx) { // ... and the retained raw atlas after them
     void *old_raw = A.raw;
     hold.take(raw);
     A.raw = raw; A.raw_res = res; A.raw_layers = layers;

@@ -103,6 +103,7 @@ struct fspt_scene {
     uint32_t raw_res = 0, raw_layers = 0;
     std::vector<uint8_t> is_const;  // per layer of `raw` (k_ap_layer_const's answer, kept with it)
     std::vector<uint32_t> first;    // per layer: its texel 0
+    std::vector<std::array<uint32_t, 4>> keys; // per texture set of the last materials call: its four layers (fspt_scene_patch_textures)
     hipEvent_t ev[2] = {nullptr, nullptr};
     float last_ms = 0.0f;           // kernels of the last update, first to last
     uint32_t last_launches = 0;
@@ -193,7 +194,11 @@ int refit_check(fspt_scene *s, const float *tri, const float *norm, int *finite)
 // ordered the call against the targets, prepared s->rf and checked tri / norm.  order_out: NULL, host or device memory.
 int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *order_out, bool order_on_device);
 // fspt_appearance.hip: the callers have validated their arguments and ordered the call against the targets.
-int appearance_materials(fspt_scene *s, const float *mat, const float *uv, const uint8_t *atlas, uint32_t res, uint32_t layers);
+// tx (atlas NULL): the raw atlas is packed on the device from tx->p - all of it, or, with layer_ids, those
+// layers of a copy of the retained one (mat is then ignored: the scene's current materials are read back) - and becomes the
+// retained atlas like an uploaded one.  fn names the entry in errors.
+struct ApTextures { const fspt_texture_pack *p; bool on_device; const uint32_t *layer_ids; const char *fn; };
+int appearance_materials(fspt_scene *s, const float *mat, const float *uv, const uint8_t *atlas, uint32_t res, uint32_t layers, const ApTextures *tx = nullptr);
 int appearance_environment(fspt_scene *s, const uint8_t *env, uint32_t w, uint32_t h, const uint32_t *bins, uint32_t n_bins);
 void appearance_release(fspt_scene *s);
 // device buffers of a transaction: freed unless taken
@@ -213,6 +218,14 @@ inline int ap_fail(const char *fn, hipError_t e) {
   fspt_set_error("%s: %s (scene unchanged)", fn, hipGetErrorString(e));
   return e == hipErrorOutOfMemory ? FSPT_E_NOMEM : FSPT_E_HIP;
 }
+// fspt_texpack.hip.  texpack_launch: a checked description's layers into `raw` (device memory, res^2 texels per
+// layer; layer l, or layer_ids[l]) on `st`: uploads the records and - host form - the sources into buffers of `hold`, records
+// ev_begin (may be NULL) and launches k_tex_resample; does not wait.  atlas_pack_run: fspt_atlas_pack_gpu's device side on the
+// current device; atlas_pack_times: its last split (host clock around the uploads and the read-back, events around the kernel).
+hipError_t texpack_launch(Hold &hold, const fspt_texture_pack *p, bool on_device, const uint32_t *layer_ids, uint32_t *raw, hipStream_t st,
+                          hipEvent_t ev_begin, uint64_t *uploaded, uint32_t *launches);
+int atlas_pack_run(const fspt_texture_pack *p, uint8_t *atlas_out);
+void atlas_pack_times(float *upload_ms, float *kernel_ms, float *readback_ms);
 // the environment's last two steps, shared by fspt_scene_update_environment and the GPU sky entries (fspt_sky.hip): the
 // tiled form of a raw w x h RGBE map (device memory; dst holds env_tiled_texels words), and the swap of the scene's
 // environment and bins for new device buffers (n_env NULL = no map), which frees the old ones

@@ -236,6 +236,12 @@ int fspt_multi_update_skin(fspt_multi *m, const float *xf, uint32_t n_joints, co
 int fspt_multi_update_materials(fspt_multi *m, const float *mat, const float *uv, const uint8_t *atlas, uint32_t atlas_res, uint32_t atlas_layers) {
   MULTI_EACH_SCENE(fspt_multi_update_materials, fspt_scene_update_materials(s, mat, uv, atlas, atlas_res, atlas_layers));
 }
+int fspt_multi_update_textures(fspt_multi *m, const float *mat, const float *uv, const fspt_texture_pack *p) {
+  MULTI_EACH_SCENE(fspt_multi_update_textures, fspt_scene_update_textures(s, mat, uv, p));
+}
+int fspt_multi_patch_textures(fspt_multi *m, const uint32_t *layer_ids, uint32_t n, const fspt_texture_pack *p) {
+  MULTI_EACH_SCENE(fspt_multi_patch_textures, fspt_scene_patch_textures(s, layer_ids, n, p));
+}
 int fspt_multi_update_environment(fspt_multi *m, const uint8_t *env, uint32_t env_w, uint32_t env_h, const uint32_t *bins, uint32_t n_bins) {
   MULTI_EACH_SCENE(fspt_multi_update_environment, fspt_scene_update_environment(s, env, env_w, env_h, bins, n_bins));
 }

@@ -419,6 +419,100 @@ static napi_value SceneUpdateEnvironment(napi_env env, napi_callback_info info) 
   FSPT_OK_OR_THROW(fspt_scene_update_environment((fspt_scene *)h, (const uint8_t *)map, w, hh, (const uint32_t *)bins, (uint32_t)(nb / 4)));
   return undefined(env);
 }
+/* Texture packing on the GPU.  A description crosses as: images - an Array of Uint8Array (RGBA8, row 0 = top) -,
+ * dims - a Uint32Array of (w, h) per image -, layers - a Float32Array of 10 per layer: kind, colour.rgb, image, corrected,
+ * swizzle x 4 -, and res.  The sizes are checked here (every image holds w * h * 4 bytes); the values are the library's to
+ * refuse.  tex_desc_free() after the call, whatever it returned. */
+typedef struct { fspt_texture_pack p; fspt_texture_image *images; fspt_texture_layer *layers; } tex_desc;
+static void tex_desc_free(tex_desc *d) { free(d->images); free(d->layers); d->images = NULL; d->layers = NULL; }
+static int tex_desc_args(napi_env env, napi_value images, napi_value dims, napi_value layers, napi_value res, tex_desc *d) {
+  void *dm = NULL, *ly = NULL; size_t nd = 0, nl = 0; uint32_t n_images = 0, r = 0; bool is_array = false;
+  memset(d, 0, sizeof *d);
+  if (napi_is_array(env, images, &is_array) != napi_ok || !is_array || napi_get_array_length(env, images, &n_images) != napi_ok) {
+    napi_throw_type_error(env, NULL, "fspt_napi: a texture description needs an Array of Uint8Array (images)"); return -1;
+  }
+  if (typed(env, dims, napi_uint32_array, 0, &dm, &nd) || typed(env, layers, napi_float32_array, 0, &ly, &nl)) return -1;
+  if (napi_get_value_uint32(env, res, &r) != napi_ok) { napi_throw_type_error(env, NULL, "fspt_napi: a texture description needs res"); return -1; }
+  if (nd != (size_t)n_images * 2) { napi_throw_range_error(env, NULL, "fspt_napi: a texture description needs 2 words (w, h) per image (dims)"); return -1; }
+  if (nl % 10) { napi_throw_range_error(env, NULL, "fspt_napi: a texture description needs 10 floats per layer (layers)"); return -1; }
+  d->images = (fspt_texture_image *)calloc(n_images ? n_images : 1, sizeof *d->images);
+  d->layers = (fspt_texture_layer *)calloc(nl / 10 ? nl / 10 : 1, sizeof *d->layers);
+  if (!d->images || !d->layers) { tex_desc_free(d); napi_throw_error(env, NULL, "fspt_napi: out of memory"); return -1; }
+  for (uint32_t i = 0; i < n_images; ++i) {
+    napi_value v; void *px = NULL; size_t np = 0;
+    const uint32_t w = ((const uint32_t *)dm)[2 * i], h = ((const uint32_t *)dm)[2 * i + 1];
+    if (napi_get_element(env, images, i, &v) != napi_ok || typed(env, v, napi_uint8_array, 0, &px, &np)) { tex_desc_free(d); return -1; }
+    if ((uint64_t)np != (uint64_t)w * h * 4u) {
+      tex_desc_free(d);
+      napi_throw_range_error(env, NULL, "fspt_napi: a texture description needs w * h RGBA8 texels per image (images, dims)"); return -1;
+    }
+    d->images[i].rgba = (const uint8_t *)px; d->images[i].w = w; d->images[i].h = h;
+  }
+  for (size_t l = 0; l < nl / 10; ++l) {
+    const float *q = (const float *)ly + l * 10;
+    fspt_texture_layer *y = &d->layers[l];
+    y->kind = (q[0] >= -1.0f && q[0] <= 1024.0f) ? (int32_t)q[0] : -1;        /* (NaN and what no int32 holds: no kind) */
+    y->color[0] = q[1]; y->color[1] = q[2]; y->color[2] = q[3];
+    y->image = (q[4] >= 0.0f && q[4] < 4294967040.0f) ? (uint32_t)q[4] : 0xFFFFFFFFu;
+    y->corrected = q[5] != 0.0f;
+    for (int k = 0; k < 4; ++k) y->swizzle[k] = (q[6 + k] >= 0.0f && q[6 + k] <= 255.0f) ? (uint8_t)q[6 + k] : 255;
+  }
+  d->p.images = d->images; d->p.n_images = n_images; d->p.layers = d->layers; d->p.n_layers = (uint32_t)(nl / 10); d->p.res = r;
+  return 0;
+}
+static napi_value tex_throw(napi_env env, int rc) {
+  char msg[640];
+  snprintf(msg, sizeof msg, "libfspt error %d: %s", rc, fspt_last_error());
+  napi_throw_error(env, NULL, msg);
+  return NULL;
+}
+/* atlasPackGpu(device, images, dims, layers, res) -> Uint8Array of res^2 * nLayers RGBA8 texels: fspt_atlas_pack_gpu. */
+static napi_value AtlasPackGpu(napi_env env, napi_callback_info info) {
+  napi_value a[5], ab, ta; void *data = NULL; int32_t device = 0; tex_desc d; int rc;
+  if (get_args(env, info, 5, a)) return NULL;
+  NAPI_OK(napi_get_value_int32(env, a[0], &device));
+  if (tex_desc_args(env, a[1], a[2], a[3], a[4], &d)) return NULL;
+  if ((rc = fspt_texture_pack_check_eval(&d.p, NULL, 0, 0, 0))) { tex_desc_free(&d); return tex_throw(env, rc); } /* (the refusals, before anything is allocated) */
+  const size_t bytes = (size_t)d.p.res * d.p.res * d.p.n_layers * 4;
+  if (napi_create_arraybuffer(env, bytes, &data, &ab) != napi_ok || napi_create_typedarray(env, napi_uint8_array, bytes, ab, 0, &ta) != napi_ok) {
+    tex_desc_free(&d); napi_throw_error(env, NULL, "fspt_napi: N-API call failed: the atlas"); return NULL;
+  }
+  rc = fspt_atlas_pack_gpu(device, &d.p, (uint8_t *)data);
+  tex_desc_free(&d);
+  return rc ? tex_throw(env, rc) : ta;
+}
+/* sceneUpdateTextures(scene, nTris, mat Float32Array, uv Float32Array | null, images, dims, layers, res): fspt_scene_update_textures.
+ * 12 / 6 floats per triangle of the scene.  The guard of sceneUpdateGeometry. */
+static napi_value SceneUpdateTextures(napi_env env, napi_callback_info info) {
+  napi_value a[8]; void *h, *mat = NULL, *uv = NULL; size_t nm = 0, nu = 0; uint32_t n = 0; tex_desc d; int rc;
+  if (get_args(env, info, 8, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[1], &n));
+  if (typed(env, a[2], napi_float32_array, 0, &mat, &nm) || typed(env, a[3], napi_float32_array, 1, &uv, &nu)) return NULL;
+  if (nm != (size_t)n * 12 || (uv && nu != (size_t)n * 6)) {
+    napi_throw_range_error(env, NULL, "fspt_napi: updateTextures needs 12 floats (mat) and 6 floats (uv) per triangle of the scene");
+    return NULL;
+  }
+  if (tex_desc_args(env, a[4], a[5], a[6], a[7], &d)) return NULL;
+  rc = fspt_scene_update_textures((fspt_scene *)h, (const float *)mat, (const float *)uv, &d.p);
+  tex_desc_free(&d);
+  return rc ? tex_throw(env, rc) : undefined(env);
+}
+/* scenePatchTextures(scene, layerIds Uint32Array, images, dims, layers, res): fspt_scene_patch_textures - one id per layer of the
+ * description.  The guard of sceneUpdateGeometry. */
+static napi_value ScenePatchTextures(napi_env env, napi_callback_info info) {
+  napi_value a[6]; void *h, *ids = NULL; size_t ni = 0; tex_desc d; int rc;
+  if (get_args(env, info, 6, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  if (typed(env, a[1], napi_uint32_array, 0, &ids, &ni)) return NULL;
+  if (tex_desc_args(env, a[2], a[3], a[4], a[5], &d)) return NULL;
+  if (ni != d.p.n_layers) {
+    tex_desc_free(&d);
+    napi_throw_range_error(env, NULL, "fspt_napi: patchTextures needs one layer id per layer of the description");
+    return NULL;
+  }
+  rc = fspt_scene_patch_textures((fspt_scene *)h, (const uint32_t *)ids, (uint32_t)ni, &d.p);
+  tex_desc_free(&d);
+  return rc ? tex_throw(env, rc) : undefined(env);
+}
 /* GPU sky.  A sky's parameters cross as a Float32Array(10) - sun_dir.xyz, turbidity, sun_intensity, sun_radius, gain,
  * ground_albedo.rgb - and two counts; the library checks the ranges. */
 static int sky_params_arg(napi_env env, napi_value f, napi_value vs, napi_value ls, fspt_sky_params *p) {
@@ -1539,7 +1633,7 @@ static napi_value AbiVersion(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
-      {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"sceneUpdateSky", SceneUpdateSky}, {"sceneUpdateEnvironmentAuto", SceneUpdateEnvironmentAuto}, {"skyGenerate", SkyGenerate}, {"envBinsGpu", EnvBinsGpu}, {"sceneSetPose", SceneSetPose}, {"sceneUpdateTransforms", SceneUpdateTransforms}, {"sceneSetSkin", SceneSetSkin}, {"sceneUpdateSkin", SceneUpdateSkin}, {"targetCreate", TargetCreate},
+      {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"sceneUpdateSky", SceneUpdateSky}, {"sceneUpdateEnvironmentAuto", SceneUpdateEnvironmentAuto}, {"skyGenerate", SkyGenerate}, {"atlasPackGpu", AtlasPackGpu}, {"sceneUpdateTextures", SceneUpdateTextures}, {"scenePatchTextures", ScenePatchTextures}, {"envBinsGpu", EnvBinsGpu}, {"sceneSetPose", SceneSetPose}, {"sceneUpdateTransforms", SceneUpdateTransforms}, {"sceneSetSkin", SceneSetSkin}, {"sceneUpdateSkin", SceneUpdateSkin}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
       {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setCameraModel", SetCameraModel}, {"cameraModel", CameraModel}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},

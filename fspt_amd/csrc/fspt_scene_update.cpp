@@ -2,6 +2,7 @@
 // (DESIGN 8.6), rebuild (8.7), appearance update (8.13), part transforms (8.14), skinning (8.16), the GPU sky (8.17), the motion origin (8.8)
 // and the read-outs that go with them.  What the families share stands once, first; every refusal names the calling entry.
 #include "fspt_internal.hpp"
+#include "fspt_texpack_check.hpp"
 
 // ---------------------------------------------------------------------------
 // the shared steps
@@ -461,6 +462,64 @@ int fspt_scene_update_materials(fspt_scene *s, const float *mat, const float *uv
   // measured under the other horizon (iterations a run needed, live-path fractions) is forgotten with it
   if (was != s->has_dielectric) targets_forget_measurements(s, false);
   return geometry_changed_lights(s); // the table depends on the emissive layers and their texels
+}
+
+// ---------------------------------------------------------------------------
+// texture packing on the GPU (kernel in fspt_texpack.hip, checks in fspt_texpack_check.hpp)
+// ---------------------------------------------------------------------------
+int fspt_atlas_pack_gpu(int device, const fspt_texture_pack *p, uint8_t *atlas_out) {
+  int rc = fspt::texpack_check("fspt_atlas_pack_gpu", p, false);
+  if (rc) return rc;
+  if (!atlas_out) { fspt_set_error("fspt_atlas_pack_gpu: NULL atlas_out"); return FSPT_E_INVALID; }
+  if ((rc = check_device(device))) return rc;
+  return fspt::atlas_pack_run(p, atlas_out);
+}
+
+int fspt_atlas_pack_last_ms(float *upload_ms, float *kernel_ms, float *readback_ms) {
+  fspt::atlas_pack_times(upload_ms, kernel_ms, readback_ms);
+  return FSPT_OK;
+}
+
+// the argument checks as a host-only hook (tests): a whole description (layer_ids NULL), or a patch of n layers against a
+// retained atlas of raw_layers layers of raw_res^2 texels (raw_layers 0: none, FSPT_E_STATE)
+int fspt_texture_pack_check_eval(const fspt_texture_pack *p, const uint32_t *layer_ids, uint32_t n, uint32_t raw_layers, uint32_t raw_res) {
+  const char *fn = "fspt_texture_pack_check_eval";
+  const bool patch = layer_ids || n;
+  const int rc = fspt::texpack_check(fn, p, false, layer_ids, n, raw_layers, raw_res, patch);
+  if (rc || !patch || raw_layers) return rc;
+  fspt_set_error("%s: no earlier call of this scene carried an atlas to patch", fn);
+  return FSPT_E_STATE;
+}
+
+// fspt_scene_update_materials with the atlas packed on the device: the same order against the targets, transaction,
+// retained atlas, light table and has_dielectric handling
+static int update_textures(fspt_scene *s, const float *mat, const float *uv, const uint32_t *layer_ids, uint32_t n_ids, const fspt_texture_pack *p, bool patch, bool on_device, const char *fn) {
+  if (!s || (!patch && !mat)) { fspt_set_error("%s: NULL scene%s", fn, patch ? "" : " or mat"); return FSPT_E_INVALID; }
+  int rc = fspt::texpack_check(fn, p, on_device, layer_ids, n_ids, s->ap.raw ? s->ap.raw_layers : 0u, s->ap.raw_res, patch);
+  if (rc) return rc;
+  if (patch && !s->ap.raw) {
+    fspt_set_error("%s: no earlier call of this scene carried an atlas to patch", fn);
+    return FSPT_E_STATE;
+  }
+  if ((rc = begin_scene_change(s))) return rc;
+  const bool was = s->has_dielectric;
+  const fspt::ApTextures tx = {p, on_device, patch ? layer_ids : nullptr, fn};
+  if ((rc = fspt::appearance_materials(s, mat, uv, nullptr, 0, 0, &tx))) return rc;
+  if (was != s->has_dielectric) targets_forget_measurements(s, false);
+  return geometry_changed_lights(s);
+}
+
+int fspt_scene_update_textures(fspt_scene *s, const float *mat, const float *uv, const fspt_texture_pack *p) {
+  return update_textures(s, mat, uv, nullptr, 0, p, false, false, "fspt_scene_update_textures");
+}
+int fspt_scene_update_textures_device(fspt_scene *s, const float *mat, const float *uv, const fspt_texture_pack *p) {
+  return update_textures(s, mat, uv, nullptr, 0, p, false, true, "fspt_scene_update_textures_device");
+}
+int fspt_scene_patch_textures(fspt_scene *s, const uint32_t *layer_ids, uint32_t n, const fspt_texture_pack *p) {
+  return update_textures(s, nullptr, nullptr, layer_ids, n, p, true, false, "fspt_scene_patch_textures");
+}
+int fspt_scene_patch_textures_device(fspt_scene *s, const uint32_t *layer_ids, uint32_t n, const fspt_texture_pack *p) {
+  return update_textures(s, nullptr, nullptr, layer_ids, n, p, true, true, "fspt_scene_patch_textures_device");
 }
 
 int fspt_scene_update_environment(fspt_scene *s, const uint8_t *env, uint32_t env_w, uint32_t env_h, const uint32_t *bins, uint32_t n_bins) {

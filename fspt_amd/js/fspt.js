@@ -99,7 +99,8 @@ class AtlasLayers {
   resolution() { this.res = Math.min(this.res, this.tallest); return this.res; }
   /** RGBA8 texels of every layer, res x res each: flat colours as gl.clearColor + readPixels would store them, images
    *  through resampleImage */
-  pixels() {
+  pixels(opts) {
+    if (opts && opts.device != null) return atlasPackGpu(this.packDesc(), opts.device);   // (DESIGN 8.18) resampled on that HIP device
     const res = this.resolution(), n = res * res * 4;
     const out = new Uint8Array(n * this.entries.length);
     this.entries.forEach((e, i) => {
@@ -108,6 +109,18 @@ class AtlasLayers {
       for (let t = i * n; t < (i + 1) * n; t += 4) { out[t] = px[0]; out[t + 1] = px[1]; out[t + 2] = px[2]; out[t + 3] = 255; }
     });
     return out;
+  }
+  /** the atlas as a description for the GPU packer (fspt_texture_pack, DESIGN 8.18): {res, images, layers} - the distinct
+   *  images (an image that is layer 0 and a later layer too goes once) and per entry {kind: 'color', color} or
+   *  {kind: 'image', image, corrected, swizzle}, with the flags the images carry now, as pixels() reads them */
+  packDesc() {
+    const res = this.resolution(), images = [], at = new Map();
+    const layers = this.entries.map((e) => {
+      if (Array.isArray(e)) return { kind: 'color', color: [0, 1, 2].map((k) => Number(e[k])) };
+      if (!at.has(e)) { at.set(e, images.length); images.push(e); }
+      return { kind: 'image', image: at.get(e), corrected: !!e.corrected, swizzle: e.swizzle ? Array.from(e.swizzle, Number) : [0, 1, 2, 3] };
+    });
+    return { res, images, layers };
   }
   describe() {
     return this.entries.map((e) => (Array.isArray(e) ? { color: e.map(Number) } :
@@ -214,6 +227,9 @@ function buildScene(sceneOrProps, objTexts, env, leafSize, opts) {
   opts = opts || {};
   const bvh = opts.bvh === undefined ? 'sah' : opts.bvh;
   if (bvh !== 'sah' && bvh !== 'gpu') throw new RangeError("buildScene: opts.bvh must be 'sah' or 'gpu'");
+  const textures = opts.textures === undefined ? 'cpu' : opts.textures;   // 'gpu': the atlas is resampled on HIP device opts.device (DESIGN 8.18)
+  if (textures !== 'cpu' && textures !== 'gpu') throw new RangeError("buildScene: opts.textures must be 'cpu' or 'gpu'");
+  if (textures === 'gpu' && opts.host) throw new RangeError("buildScene: opts.textures 'gpu' packs this host's AtlasLayers, not opts.host's packer");
   const scene = Array.isArray(sceneOrProps) ? { props: sceneOrProps } : sceneOrProps;
   const props = mergeSceneProps(scene);
   // the reference's own host modules when the caller has them (INTEGRATION.md), the resolver above otherwise
@@ -257,7 +273,8 @@ function buildScene(sceneOrProps, objTexts, env, leafSize, opts) {
     s.atlas = opts.atlasPixels(packer);
     s.layers = null;
   } else {
-    s.atlas = packer.pixels(); s.atlasRes = packer.res; s.atlasLayers = packer.entries.length;
+    s.atlas = packer.pixels(textures === 'gpu' ? { device: opts.device || 0 } : undefined); s.atlasRes = packer.res; s.atlasLayers = packer.entries.length;
+    Object.defineProperty(s, 'packer', { value: packer, enumerable: false });   // (updateTextures takes it; not a part of the arrays)
     s.layers = packer.describe();
   }
   if (env) { s.env = env.rgbe; s.envW = env.width; s.envH = env.height; s.bins = addon.envBins(env.rgbe, env.width, env.height); }
@@ -341,6 +358,48 @@ function skyGenerate(o, device) {
   return { rgbe: addon.skyGenerate(device || 0, k.params, k.viewSamples, k.lightSamples, k.width, k.height), width: k.width, height: k.height };
 }
 /** env_sampler.js's bins of an RGBE map, built on HIP device `device` (fspt_env_bins_gpu; addon.envBins is the CPU's) */
+/* Texture packing on the GPU (DESIGN 8.18).  A description is {res, images: [{width, height, data}], layers: [{kind: 'color',
+ * color} | {kind: 'image', image, corrected, swizzle} | {kind: 'pixels', image}]} (AtlasLayers.packDesc()); it crosses to the
+ * addon as typed arrays.  Sizes are checked here, values by the library. */
+const TEX_KINDS = { color: 0, image: 1, pixels: 2 };
+function texDescArgs(fn, d) {
+  if (d instanceof AtlasLayers) d = d.packDesc();
+  if (d == null || typeof d !== 'object' || !Array.isArray(d.images) || !Array.isArray(d.layers)) throw new TypeError(fn + ': expected a texture description {res, images, layers}');
+  if (!Number.isInteger(d.res) || d.res < 0 || d.res > 0xFFFFFFFF) throw new RangeError(fn + ': res must be an integer');
+  const dims = new Uint32Array(d.images.length * 2);
+  const images = d.images.map((im, i) => {
+    if (im == null || !Number.isInteger(im.width) || !Number.isInteger(im.height) || im.width < 0 || im.height < 0 || im.width > 0xFFFFFFFF || im.height > 0xFFFFFFFF ||
+        im.data == null || !ArrayBuffer.isView(im.data) || im.data.BYTES_PER_ELEMENT !== 1 || im.data.length !== im.width * im.height * 4) {
+      throw new RangeError(fn + ': images[' + i + '] must be {width, height, data: width x height x 4 bytes}');
+    }
+    dims[2 * i] = im.width; dims[2 * i + 1] = im.height;
+    return im.data instanceof Uint8Array ? im.data : new Uint8Array(im.data.buffer, im.data.byteOffset, im.data.length);
+  });
+  const layers = new Float32Array(d.layers.length * 10);
+  d.layers.forEach((y, l) => {
+    if (y == null || typeof y !== 'object') throw new TypeError(fn + ': layers[' + l + '] must be an object');
+    const o = l * 10;
+    layers[o] = y.kind in TEX_KINDS ? TEX_KINDS[y.kind] : Number(y.kind);
+    if (y.kind === 'color') {
+      if (!y.color || y.color.length < 3) throw new RangeError(fn + ': layers[' + l + '].color must hold 3 numbers');
+      // the ABI carries float32: a colour goes as the float64 quantisation pixels() makes of it, byte / 255 (non-finite: as given, refused)
+      for (let k = 0; k < 3; k++) { const c = Number(y.color[k]); layers[o + 1 + k] = Number.isFinite(c) ? Math.floor(Math.min(Math.max(c, 0), 1) * 255 + 0.5) / 255 : c; }
+      return;
+    }
+    if (!Number.isInteger(y.image) || y.image < 0) throw new RangeError(fn + ': layers[' + l + '].image must be an index into images');
+    layers[o + 4] = y.image; layers[o + 5] = y.corrected ? 1 : 0;
+    const sw = y.swizzle == null ? [0, 1, 2, 3] : y.swizzle;
+    if (sw.length !== 4) throw new RangeError(fn + ': layers[' + l + '].swizzle must hold 4 channel indices');
+    for (let k = 0; k < 4; k++) layers[o + 6 + k] = Number(sw[k]);
+  });
+  return { images, dims, layers, res: d.res };
+}
+/** the raw atlas (Uint8Array, res^2 * layers RGBA8 texels, GL rows) of a description or an AtlasLayers, packed on HIP device
+ *  `device` (fspt_atlas_pack_gpu, DESIGN 8.18) */
+function atlasPackGpu(desc, device) {
+  const k = texDescArgs('atlasPackGpu', desc);
+  return addon.atlasPackGpu(device || 0, k.images, k.dims, k.layers, k.res);
+}
 function envBinsGpu(rgbe, w, h, device) { return addon.envBinsGpu(rgbe, w, h, device || 0); }
 
 function pipelineCode(name) {
@@ -665,6 +724,28 @@ class PathTracer {
     }
     addon.sceneUpdateMaterials(this._scene, this._nTris, mat, uv == null ? null : uv, atlas == null ? null : atlas, atlas == null ? 0 : atlasRes, atlas == null ? 0 : atlasLayers);
   }
+  /** updateMaterials with the atlas made on the GPU: {mat, uv (omitted: kept), textures: a texture description or an
+   *  AtlasLayers}.  Only the decoded images cross the bus; a kernel resamples them into a new raw atlas and the call goes on
+   *  as updateMaterials carrying it (fspt_scene_update_textures, DESIGN 8.18).  Throws Error('render in flight') during a renderAsync. */
+  updateTextures(o) {
+    if (o == null || typeof o !== 'object') throw new TypeError('updateTextures: expected {mat, uv, textures}');
+    const { mat, uv, textures } = o;
+    if (!(mat instanceof Float32Array) || mat.length !== this._nTris * 12) throw new RangeError('updateTextures: mat must be a Float32Array of ' + this._nTris + ' x 12 floats');
+    if (uv != null && (!(uv instanceof Float32Array) || uv.length !== this._nTris * 6)) throw new RangeError('updateTextures: uv must be a Float32Array of ' + this._nTris + ' x 6 floats');
+    const k = texDescArgs('updateTextures', textures);
+    addon.sceneUpdateTextures(this._scene, this._nTris, mat, uv == null ? null : uv, k.images, k.dims, k.layers, k.res);
+  }
+  /** replace layers of the atlas the scene retains: {layerIds, layers, images, res} - layers[k] (indexing `images`) becomes
+   *  layer layerIds[k]; res is the retained atlas's.  The scene is laid out again with its current materials
+   *  (fspt_scene_patch_textures, DESIGN 8.18).  Throws Error('render in flight') during a renderAsync. */
+  patchTextures(o) {
+    if (o == null || typeof o !== 'object') throw new TypeError('patchTextures: expected {layerIds, layers, images, res}');
+    const ids = o.layerIds instanceof Uint32Array ? o.layerIds : Array.isArray(o.layerIds) && o.layerIds.every((x) => Number.isInteger(x) && x >= 0 && x <= 0xFFFFFFFF) ? Uint32Array.from(o.layerIds) : null;
+    if (ids === null) throw new TypeError('patchTextures: layerIds must be a Uint32Array or an array of layer indices');
+    const k = texDescArgs('patchTextures', { res: o.res, images: o.images || [], layers: o.layers });
+    if (ids.length !== k.layers.length / 10) throw new RangeError('patchTextures: ' + ids.length + ' layer ids for ' + k.layers.length / 10 + ' layers');
+    addon.scenePatchTextures(this._scene, ids, k.images, k.dims, k.layers, k.res);
+  }
   /** a new environment: {env (Uint8Array RGBE, envW * envH texels; null: black), envW, envH, bins (Uint32Array, 4 per bin,
    *  required)} (fspt_scene_update_environment, DESIGN 8.13); state stays as for updateMaterials */
   updateEnvironment(o) {
@@ -802,5 +883,5 @@ class MultiPathTracer {
 // memory later scenes may spend on interleaved material textures (fspt_set_texture_interleave_budget; results do not depend on it)
 function setTextureInterleaveBudget(bytes) { addon.setTextureInterleaveBudget(bytes); }
 
-module.exports = { addon, setTextureInterleaveBudget, skyGenerate, envBinsGpu, SKY_DEFAULTS, MultiPathTracer, AtlasLayers, resolveMaterial, readMtl, mergeSceneProps, resampleImage, packReferenceScene, buildScene,
+module.exports = { addon, setTextureInterleaveBudget, skyGenerate, envBinsGpu, atlasPackGpu, SKY_DEFAULTS, MultiPathTracer, AtlasLayers, resolveMaterial, readMtl, mergeSceneProps, resampleImage, packReferenceScene, buildScene,
   PathTracer, saveBlob, loadBlob };

@@ -101,6 +101,9 @@ def main(argv=None):
     ap.add_argument("--bvh", choices=("sah", "gpu", "refit"), default="sah",
                     help="BVH builder: the reference's full-sweep SAH on the CPU, or binned SAH on the GPU (DESIGN 8.4); refit (with "
                          "--frames): build the first frame, then refit the tree for frames that only move triangles (DESIGN 8.6)")
+    ap.add_argument("--textures", choices=("cpu", "gpu"), default="cpu",
+                    help="with --scene: where the texture atlas is resampled - numpy on the host, or a kernel on the render device "
+                         "(DESIGN 8.18); with --bvh refit a changed atlas then reaches the live scene as decoded images")
     ap.add_argument("--rebuild-above", type=float, default=None, metavar="R",
                     help="--bvh refit: rebuild the tree in place on the GPU when a refitted frame's SAH cost exceeds R x the cost at "
                          "the last build (DESIGN 8.7; default: never)")
@@ -212,10 +215,10 @@ def main(argv=None):
                                     rebuild_above=args.rebuild_above,
                                     temporal=({"atrous": args.atrous, "clamp": None if args.temporal_clamp is None else True if args.temporal_clamp is True
                                                else {"sigma_scale": args.temporal_clamp}} if args.temporal else None),
-                                    variance=args.variance_guided, pose=args.pose, **kw)
+                                    variance=args.variance_guided, pose=args.pose, textures=args.textures, **kw)
             print(f"{len(out)} frames in {time.perf_counter() - t0:.2f} s:", *out)
         else:
-            arrays, settings = F.load_scene_file(args.scene, args.assets, bvh=args.bvh)
+            arrays, settings = F.load_scene_file(args.scene, args.assets, bvh=args.bvh, textures=args.textures)
             if sky_at is not None:
                 arrays = F.arrays_with_sky(arrays, **sky_at(0.0))
             settings["exposure"] = settings["exposure"] * args.exposure

@@ -142,7 +142,39 @@ class TexturePacker:
             self.res = self.max_res
         return self.res
 
-    def get_pixels(self):
+    def pack_desc(self):
+        """The atlas as a description for the GPU packer (fspt_texture_pack): {"res", "images", "layers"} with
+        images = the distinct decoded sources (uint8 [h, w, 4], row 0 = top; a pre-resampled layer's res x res array as it
+        is) and one layer dict per entry of image_set in order - {"kind": "color", "color"} | {"kind": "image", "image",
+        "corrected", "swizzle"} | {"kind": "pixels", "image"}.  The rules are get_pixels': get_resolution() decides res, an
+        image added twice as layer 0 and again (layer 0 is never de-duplicated) is ONE source used by two layers, and
+        corrected / swizzle are the image's when the atlas is written - its last real insertion, its last
+        metallic-roughness use."""
+        res = self.get_resolution()
+        images, index, layers = [], {}, []
+        for kind, item in self.image_set:
+            if kind == "color":
+                layers.append({"kind": "color", "color": [float(c) for c in item[:3]]})
+                continue
+            arr = item["rgba"] if kind == "image" else item
+            if id(arr) not in index:
+                index[id(arr)] = len(images)
+                images.append(arr)
+            if kind == "image":
+                layers.append({"kind": "image", "image": index[id(arr)], "corrected": bool(item["corrected"]),
+                               "swizzle": tuple(item["swizzle"] or (0, 1, 2, 3))})
+            else:
+                if item.shape[0] != res or item.shape[1] != res:
+                    raise ValueError("pre-resampled image must be res x res")
+                layers.append({"kind": "pixels", "image": index[id(arr)]})
+        return {"res": int(res), "images": images, "layers": layers}
+
+    def get_pixels(self, device=None):
+        """The atlas bytes (RGBA8, layer-major, GL rows).  device=None: resampled here in numpy; a HIP device ordinal: packed
+        on that device by fspt_atlas_pack_gpu - the same bytes where no layer is sRGB-corrected, and the
+        float32 statement of tests/texpack_ref.py in every case."""
+        if device is not None:
+            return atlas_pack_gpu(self.pack_desc(), device)
         res = self.get_resolution()
         out = np.zeros((len(self.image_set), res, res, 4), dtype=np.uint8)
         for i, (kind, item) in enumerate(self.image_set):
@@ -157,6 +189,97 @@ class TexturePacker:
                     raise ValueError("pre-resampled image must be res x res")
                 out[i] = item
         return out.reshape(-1)
+
+
+_TEX_KINDS = {"color": L.TEXLAYER_COLOR, "image": L.TEXLAYER_IMAGE, "pixels": L.TEXLAYER_PIXELS}
+
+
+def texture_pack_struct(desc, device=None, fn="texture_pack"):
+    """(L.TexturePack, on_device, source bytes, keep-alive) of a TexturePacker.pack_desc() description (or a packer).  Images are
+    uint8 arrays [h, w, 4] - or, with `device` an ordinal, contiguous uint8 torch tensors [h, w, 4] on that device, all of
+    them (the _device entries read them in place).  Sizes are checked here; what the library refuses is left
+    to it."""
+    if isinstance(desc, TexturePacker):
+        desc = desc.pack_desc()
+    images, layers = list(desc["images"]), list(desc["layers"])
+    on_dev = [hasattr(im, "data_ptr") and getattr(im, "is_cuda", False) for im in images]
+    if any(on_dev) and not all(on_dev):
+        raise TypeError(f"{fn}: images must be all host arrays or all device tensors")
+    on_device = bool(images) and all(on_dev)
+    ims = (L.TextureImage * max(len(images), 1))()
+    keep, nbytes = [], 0
+    for i, im in enumerate(images):
+        if on_device:
+            import torch
+            if device is None:
+                raise TypeError(f"{fn}: a device tensor needs a single scene; this host takes host arrays")
+            if im.dtype != torch.uint8 or not im.is_contiguous() or im.dim() != 3 or im.shape[2] != 4:
+                raise TypeError(f"{fn}: images[{i}] must be a contiguous uint8 tensor [h, w, 4]")
+            if im.device.index != device:
+                raise ValueError(f"{fn}: images[{i}] lives on {im.device}, the scene on device {device}")
+            ims[i].rgba = im.data_ptr()
+        else:
+            im = np.ascontiguousarray(im, dtype=np.uint8)
+            if im.ndim != 3 or im.shape[2] != 4:
+                raise ValueError(f"{fn}: images[{i}] has shape {im.shape}, not [h, w, 4]")
+            ims[i].rgba = im.ctypes.data
+        ims[i].h, ims[i].w = int(im.shape[0]), int(im.shape[1])
+        nbytes += int(im.shape[0]) * int(im.shape[1]) * 4
+        keep.append(im)
+    if on_device:
+        import torch
+        torch.cuda.current_stream(device).synchronize()  # whatever wrote the tensors has finished
+    lys = (L.TextureLayer * max(len(layers), 1))()
+    for l, y in enumerate(layers):
+        kind = y["kind"]
+        lys[l].kind = _TEX_KINDS[kind] if kind in _TEX_KINDS else int(kind)
+        if kind == "color":
+            # the ABI carries float32: a colour goes as the float64 quantisation get_pixels makes of it, byte / 255, which
+            # the library's floor(c * 255 + 0.5) maps back to that byte whatever float32 does to c (non-finite: as given, refused)
+            lys[l].color = (C.c_float * 3)(*[math.floor(min(max(float(c), 0.0), 1.0) * 255.0 + 0.5) / 255.0 if math.isfinite(float(c)) else float(c)
+                                             for c in y["color"][:3]])
+            continue
+        image = int(y["image"])
+        if not 0 <= image < 2 ** 32:
+            raise ValueError(f"{fn}: layers[{l}].image = {image}")
+        lys[l].image = image
+        lys[l].corrected = 1 if y.get("corrected") else 0
+        sw = [int(x) for x in (y.get("swizzle") or (0, 1, 2, 3))]
+        if len(sw) != 4 or any(not 0 <= x < 256 for x in sw):
+            raise ValueError(f"{fn}: layers[{l}].swizzle = {sw}")
+        lys[l].swizzle = (C.c_uint8 * 4)(*sw)
+    res = int(desc["res"])
+    if not 0 <= res < 2 ** 32:
+        raise ValueError(f"{fn}: res = {res}")
+    p = L.TexturePack()
+    p.images = ims; p.n_images = len(images); p.layers = lys; p.n_layers = len(layers); p.res = res
+    return p, on_device, nbytes, (ims, lys, keep)
+
+
+def atlas_pack_gpu(desc, device=0):
+    """The raw atlas of a description (TexturePacker.pack_desc(), or a packer), packed on HIP device `device`
+    (fspt_atlas_pack_gpu): uint8 [layers * res * res * 4]."""
+    p, on_device, _, keep = texture_pack_struct(desc, None, "atlas_pack_gpu")
+    out = np.zeros(int(p.res) * int(p.res) * int(p.n_layers) * 4, np.uint8)
+    L.check(L.lib().fspt_atlas_pack_gpu(int(device), C.byref(p), L.u8ptr(out) if out.size else None))
+    return out
+
+
+def atlas_pack_last_ms():
+    """The last atlas_pack_gpu of this process as a dict: upload_ms and readback_ms (host clock), kernel_ms (HIP events)."""
+    a, b, c = C.c_float(), C.c_float(), C.c_float()
+    L.check(L.lib().fspt_atlas_pack_last_ms(C.byref(a), C.byref(b), C.byref(c)))
+    return dict(upload_ms=float(a.value), kernel_ms=float(b.value), readback_ms=float(c.value))
+
+
+def texture_decode_tables():
+    """(lin, srgb): the packer's two 256-entry float32 decode tables (fspt_texture_decode_tables; no device)."""
+    lin, srgb = np.zeros(256, np.float32), np.zeros(256, np.float32)
+    L.check(L.lib().fspt_texture_decode_tables(L.fptr(lin), L.fptr(srgb)))
+    return lin, srgb
+
+
+TEXTURE_PACKERS = ("cpu", "gpu")
 
 
 def resample_image(rgba, res, corrected=False, swizzle=(0, 1, 2, 3)):
@@ -374,7 +497,7 @@ BVH_BUILDERS = ("sah", "gpu")
 
 def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas_res=2048, images=None,
                 world_transforms=None, normalize=None, mtl_texts=None, focus_rays=None, bvh="sah", device=0,
-                keep_order=False, geometry_only=False):
+                keep_order=False, geometry_only=False, textures="cpu"):
     """initBVH (main.js:284-445) for props = list of scene-JSON prop dicts and obj_texts = {path: OBJ text}.
     env = RGBE uint8 [h*w*4] or None; world_transforms = scene.worldTransforms; normalize = scene.normalize;
     mtl_texts = {url: MTL text} for `mtllib` lines (url = <dir of the OBJ>/<name>, obj_loader.js:186);
@@ -386,7 +509,11 @@ def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas
     the index in `props` of the prop packed triangle k came from.
     geometry_only=True: parse and transform the props but build NO tree: tri / mat / norm / uv come back in PARSE order, bvh is
     empty (meta["geometry_only"]); focus_rays are answered by the float64 closest hit over all triangles.  What a host of
-    moving geometry needs per frame (geometry_in_leaf_order, Scene.update_geometry)."""
+    moving geometry needs per frame (geometry_in_leaf_order, Scene.update_geometry).
+    textures = "cpu": the atlas is resampled here in numpy; "gpu": on HIP device `device` (fspt_atlas_pack_gpu, DESIGN 8.18);
+    meta["textures"] names the packer and meta["packer"] is the TexturePacker (Scene.update_textures takes it)."""
+    if textures not in TEXTURE_PACKERS:
+        raise ValueError(f"textures must be one of {TEXTURE_PACKERS}, not {textures!r}")
     if bvh not in BVH_BUILDERS:
         raise ValueError(f"bvh must be one of {BVH_BUILDERS}, not {bvh!r}")
     lib = L.lib()
@@ -475,13 +602,13 @@ def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas
             focus.append(1 - 1 / dist.value)
     finally:
         lib.fspt_builder_destroy(b)
-    atlas = packer.get_pixels()
+    atlas = packer.get_pixels(device=int(device) if textures == "gpu" else None)
     if env is not None:
         env = np.ascontiguousarray(env, dtype=np.uint8).reshape(-1)
         bins = env_bins(env, env_w, env_h)
     else:
         bins = np.array([0, 0, 1, 2048], dtype=np.uint32)  # main.js:292
-    meta = {"layers": packer.describe(), "focus": focus, "bvh": bvh}
+    meta = {"layers": packer.describe(), "focus": focus, "bvh": bvh, "textures": textures, "packer": packer}
     if geometry_only:
         meta["geometry_only"] = True
     elif keep_order:
@@ -579,14 +706,14 @@ def compose_order(base_order, order):
 
 
 def build_scene_json(scene, obj_texts, mtl_texts=None, images=None, env=None, env_w=0, env_h=0, leaf_size=4,
-                     focus_rays=None, bvh="sah", device=0, keep_order=False, geometry_only=False):
+                     focus_rays=None, bvh="sah", device=0, keep_order=False, geometry_only=False, textures="cpu"):
     """build_scene for a whole scene JSON (props / static_props / animated_props, worldTransforms, normalize,
     atlasRes: main.js:284-445,869-871,944)."""
     return build_scene(merge_scene_props(scene), obj_texts, env=env, env_w=env_w, env_h=env_h, leaf_size=leaf_size,
                        atlas_res=scene.get("atlasRes") or 2048, images=images,
                        world_transforms=scene.get("worldTransforms"), normalize=scene.get("normalize"),
                        mtl_texts=mtl_texts, focus_rays=focus_rays, bvh=bvh, device=device, keep_order=keep_order,
-                       geometry_only=geometry_only)
+                       geometry_only=geometry_only, textures=textures)
 
 
 def merge_scene_props(scene):
@@ -675,9 +802,10 @@ def synthetic_env(w=2048, h=1024, sun_deg=1.5, sun_gain=60.0, sun_dir=(0.35, 0.5
     return out.reshape(-1), w, h
 
 
-def textured_test_scene(res=16, keep_order=False):
+def textured_test_scene(res=16, keep_order=False, textures="cpu", device=0):
     """Two image-mapped quads + a flat-colour sphere: exercises the bilinear RGBA8 atlas path (atlas res > 1),
-    tangent-space normal mapping and emissive maps with procedurally generated images.  keep_order: as build_scene."""
+    tangent-space normal mapping and emissive maps with procedurally generated images.  keep_order, textures, device: as
+    build_scene."""
     rng = np.random.default_rng(5)
     yy, xx = np.mgrid[0:res, 0:res]
     checker = (((xx // 2) + (yy // 2)) % 2).astype(np.uint8)
@@ -698,8 +826,8 @@ def textured_test_scene(res=16, keep_order=False):
     ]
     texts = {"synthetic/cube_sphere.obj": cube_sphere_obj(6), "synthetic/quad.obj": QUAD_OBJ}
     env, w, h = synthetic_env(64, 32)
-    s = build_scene(props, texts, env=env, env_w=w, env_h=h, images=images, keep_order=keep_order)
-    s.meta = dict(kind="textured-test", **_kept_order(s.meta))
+    s = build_scene(props, texts, env=env, env_w=w, env_h=h, images=images, keep_order=keep_order, textures=textures, device=device)
+    s.meta = dict(kind="textured-test", packer=s.meta["packer"], **_kept_order(s.meta))
     return s
 
 
@@ -782,15 +910,15 @@ def bunny_props_textured():
     return p
 
 
-def bunny_scene_textured(n=76, env_size=(2048, 1024), sun_deg=1.5, sun_gain=60.0, res=2048, bvh="sah", device=0):
+def bunny_scene_textured(n=76, env_size=(2048, 1024), sun_deg=1.5, sun_gain=60.0, res=2048, bvh="sah", device=0, textures="cpu"):
     """The 'bunny' configs with the reference's real atlas size: 2048^2 image maps on both quads (7 image layers + the
     flat-colour layers, 16 MB each) - the 4 x 4-tap bilinear atlas gather of tracer.fs:453-456 on an atlas that does not
     fit any cache."""
     texts = {"synthetic/cube_sphere.obj": cube_sphere_obj(n), "synthetic/quad.obj": QUAD_OBJ}
     env, w, h = synthetic_env(env_size[0], env_size[1], sun_deg=sun_deg, sun_gain=sun_gain)
     s = build_scene(bunny_props_textured(), texts, env=env, env_w=w, env_h=h, images=procedural_maps(res), atlas_res=res,
-                    bvh=bvh, device=device)
-    s.meta = dict(kind="bunny-synthetic-textured", n=n, res=res, bvh=bvh)
+                    bvh=bvh, device=device, textures=textures)
+    s.meta = dict(kind="bunny-synthetic-textured", n=n, res=res, bvh=bvh, packer=s.meta["packer"])
     return s
 
 

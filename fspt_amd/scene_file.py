@@ -40,11 +40,12 @@ def mtllib_urls(obj_text, base_path):
     return urls
 
 
-def load_scene_file(scene_path, asset_root=None, leaf_size=4, bvh="sah", device=0, keep_order=False, geometry_only=False):
+def load_scene_file(scene_path, asset_root=None, leaf_size=4, bvh="sah", device=0, keep_order=False, geometry_only=False, textures="cpu"):
     """Returns (SceneArrays, settings).  settings = camera and display values with the reference's defaults
     (initGlobals, main.js:50-75): eye, dir, fov_scale, env_theta, exposure, samples, focus (lensFeatures[0]
     after shootAutoFocusRay), aperture (index.html default 0.02).  bvh / device: scene.build_scene's builder choice;
-    keep_order / geometry_only: as scene.build_scene (the latter: triangles in parse order, no tree)."""
+    keep_order / geometry_only: as scene.build_scene (the latter: triangles in parse order, no tree); textures: "cpu" or "gpu",
+    where the atlas is resampled (scene.build_scene)."""
     with open(scene_path, "r", encoding="utf-8") as fh:
         scene = json.load(fh)
     root = asset_root or os.path.dirname(os.path.dirname(os.path.abspath(scene_path)))
@@ -82,7 +83,7 @@ def load_scene_file(scene_path, asset_root=None, leaf_size=4, bvh="sah", device=
     eye, d = _camera_ray(scene)
     arrays = S.build_scene_json(scene, obj_texts, mtl_texts, images, env=env, env_w=env_w, env_h=env_h,
                                 leaf_size=leaf_size, focus_rays=[(eye, d)], bvh=bvh, device=device, keep_order=keep_order,
-                                geometry_only=geometry_only)
+                                geometry_only=geometry_only, textures=textures)
     return arrays, _settings(scene, arrays.meta["focus"][0])
 
 
@@ -291,7 +292,7 @@ def _sequence_sky(sky, k, n):
 
 
 def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", rebuild_above=None,
-                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, camera=None, sky=None, **kw):
+                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, camera=None, sky=None, textures="cpu", **kw):
     """frame=N sequencing (main.js:851-866, 966-969): for every N in `frames` load `scene_pattern.format(frame=N)`
     (the per-frame scene JSON the reference's server hands out for `?frame=N`), render it, write
     `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1.
@@ -335,8 +336,12 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     sky: None, a list of dicts (one per frame) or a callable of the frame number that returns one: Scene.update_sky's
     arguments (sun_dir, width, height, the model's parameters).  Every frame's environment is then that generated sky, whatever
     the scene file names.  With bvh="refit" the kept tracer's scene gets update_sky once per frame - nothing but the light is
-    made again, on the GPU - and a kept frame reports "sky"; every other bvh builds each frame's scene under arrays_with_sky."""
+    made again, on the GPU - and a kept frame reports "sky"; every other bvh builds each frame's scene under arrays_with_sky.
+    textures: "cpu" or "gpu" - where every frame's atlas is resampled.  With "gpu" and bvh="refit" a kept frame
+    whose atlas changed sends its decoded images, not the atlas: Scene.update_textures packs them on the device."""
     from PIL import Image
+    if textures not in S.TEXTURE_PACKERS:
+        raise ValueError(f"render_sequence: textures must be one of {S.TEXTURE_PACKERS}, not {textures!r}")
     camera = _camera_model_params(camera, kw.get("adaptive"), None if temporal is None or temporal is False else temporal)
     auto_exposure = _auto_exposure_params(auto_exposure, SEQUENCE_ADAPT if bvh == "refit" else None)
     bloom = _bloom_params(bloom)
@@ -376,7 +381,7 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
 
     if bvh != "refit":
         for n in frames:
-            arrays, settings = load_scene_file(scene_pattern.format(frame=n), asset_root, bvh=bvh, device=device)
+            arrays, settings = load_scene_file(scene_pattern.format(frame=n), asset_root, bvh=bvh, device=device, textures=textures)
             if sky is not None:
                 arrays = arrays_with_sky(arrays, device=device, **_sequence_sky(sky, len(written), n))
             rgba, _ = render_frame(arrays, settings, width, height, auto_exposure=auto_exposure, bloom=bloom, camera=camera, **kw)
@@ -415,7 +420,7 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                 settings = _settings(frame_json, 1 - 1 / dist)
                 how = "pose"
             elif base is not None:
-                g, settings = load_scene_file(path, asset_root, geometry_only=True)
+                g, settings = load_scene_file(path, asset_root, geometry_only=True, device=device, textures=textures)
                 changes = sequence_frame_changes(held, g, base.meta["tri_order"])
                 if changes is not None:
                     tri, norm = S.geometry_in_leaf_order(leaf_order, g.tri, g.norm)
@@ -441,8 +446,11 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                             res, layers, atlas = changes["atlas"] if "atlas" in changes else (None, None, None) if atlas_sent else held["atlas"]
                             atlas_sent = True
                             cur = np.asarray(leaf_order)  # mat / uv go in the CURRENT leaf order (a rebuild composed it)
-                            pt.update_materials(g.mat.reshape(-1, 12)[cur], g.uv.reshape(-1, 6)[cur] if "uv" in changes else None,
-                                                atlas, res, layers)
+                            if textures == "gpu" and atlas is not None:  #  the sources go, the device packs them
+                                pt.update_textures(g.mat.reshape(-1, 12)[cur], g.uv.reshape(-1, 6)[cur] if "uv" in changes else None, g.meta["packer"])
+                            else:
+                                pt.update_materials(g.mat.reshape(-1, 12)[cur], g.uv.reshape(-1, 6)[cur] if "uv" in changes else None,
+                                                    atlas, res, layers)
                         if {"env", "bins"} & set(changes):
                             pt.update_environment(g.env, g.env_w, g.env_h, g.bins)
                         held.update(changes)
@@ -450,7 +458,7 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
             if how == "build":
                 if pt is not None:
                     pt.close(); pt.scene.close()
-                base, settings = load_scene_file(path, asset_root, bvh="sah", device=device, keep_order=True)
+                base, settings = load_scene_file(path, asset_root, bvh="sah", device=device, keep_order=True, textures=textures)
                 pt = PathTracer(base, width, height, device=device, num_bounces=bounces)
                 cost0 = pt.scene.sah_cost() if rebuild_above is not None else None
                 leaf_order = base.meta["tri_order"]

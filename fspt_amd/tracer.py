@@ -688,6 +688,54 @@ class Scene:
         keep their accumulators, histories and exposure; `self.arrays` is not touched."""
         args, keep = self._materials_args("update_materials", mat, uv, atlas, atlas_res, atlas_layers)
         L.check(L.lib().fspt_scene_update_materials(self._h, *args))
+        if atlas is not None:
+            self._retained_atlas_res = args[3]  # (patch_textures' resolution)
+
+    def _textures_mat_uv(self, fn, mat, uv):
+        n = int(self.arrays.n_tris)
+        mat = np.ascontiguousarray(mat, dtype=np.float32)
+        if mat.size != n * 12:
+            raise ValueError(f"{fn}: mat has {mat.size} elements, the scene needs {n} x 12")
+        if uv is not None:
+            uv = np.ascontiguousarray(uv, dtype=np.float32)
+            if uv.size != n * 6:
+                raise ValueError(f"{fn}: uv has {uv.size} elements, the scene needs {n} x 6")
+        return mat, uv
+
+    @staticmethod
+    def _patch_args(fn, layer_ids, layers, images, device):
+        from . import scene as S
+        ids = np.ascontiguousarray(_u32_array(layer_ids, "layer_ids"), dtype=np.uint32).reshape(-1)
+        layers = list(layers)
+        if ids.size != len(layers):
+            raise ValueError(f"{fn}: {ids.size} layer ids for {len(layers)} layers")
+        return ids, layers, list(images or [])
+
+    def update_textures(self, mat, uv, packer_or_desc):
+        """update_materials with the atlas made on the GPU (fspt_scene_update_textures): packer_or_desc is a
+        scene.TexturePacker or its pack_desc() - the decoded sources (numpy arrays, or uint8 torch tensors [h, w, 4] on the
+        scene's device, read in place) and the layer list.  Only the sources cross the bus; the kernel resamples them into a
+        new raw atlas, and from there on the call is update_materials carrying that atlas: same layouts, same retained
+        atlas, same effect on tracers."""
+        from . import scene as S
+        mat, uv = self._textures_mat_uv("update_textures", mat, uv)
+        p, on_dev, _, keep = S.texture_pack_struct(packer_or_desc, getattr(self, "device", None), "update_textures")
+        fn = L.lib().fspt_scene_update_textures_device if on_dev else L.lib().fspt_scene_update_textures
+        L.check(fn(self._h, L.fptr(mat), None if uv is None else L.fptr(uv), C.byref(p)))
+        self._retained_atlas_res = int(p.res)
+
+    def patch_textures(self, layer_ids, layers, images=None, res=None):
+        """Replace layers of the retained raw atlas (the one the last update_materials / update_textures call carried) and lay
+        the scene out again with its current materials (fspt_scene_patch_textures): layers[k] - a layer dict
+        of TexturePacker.pack_desc() whose "image" indexes `images` - becomes layer layer_ids[k]; the resolution is the
+        retained atlas's (res=None: what this object's last update_materials / update_textures sent).  images: numpy arrays or
+        device tensors as for update_textures.  Without a retained atlas the library refuses (FSPT_E_STATE)."""
+        from . import scene as S
+        ids, layers, images = self._patch_args("patch_textures", layer_ids, layers, images, getattr(self, "device", None))
+        res = int(res) if res is not None else getattr(self, "_retained_atlas_res", None) or 1
+        p, on_dev, _, keep = S.texture_pack_struct({"res": res, "images": images, "layers": layers}, getattr(self, "device", None), "patch_textures")
+        fn = L.lib().fspt_scene_patch_textures_device if on_dev else L.lib().fspt_scene_patch_textures
+        L.check(fn(self._h, L.u32ptr(ids), ids.size, C.byref(p)))
 
     @staticmethod
     def _environment_args(fn, env, env_w, env_h, bins):
@@ -1140,6 +1188,14 @@ class PathTracer:
         history, the exposure and the bloom state stay - call clear() to restart the mean."""
         self.scene.update_materials(mat, uv, atlas, atlas_res, atlas_layers)
 
+    def update_textures(self, mat, uv, packer_or_desc):
+        """Scene.update_textures on this tracer's scene; state stays as for update_materials."""
+        self.scene.update_textures(mat, uv, packer_or_desc)
+
+    def patch_textures(self, layer_ids, layers, images=None, res=None):
+        """Scene.patch_textures on this tracer's scene; state stays as for update_materials."""
+        self.scene.patch_textures(layer_ids, layers, images, res)
+
     def update_environment(self, env, env_w, env_h, bins=None):
         """Scene.update_environment on this tracer's scene (bins=None: built on the GPU); state stays as for update_materials."""
         self.scene.update_environment(env, env_w, env_h, bins)
@@ -1567,6 +1623,24 @@ class MultiPathTracer:
         """Scene.update_materials (host arrays) on every device's copy of the scene (fspt_multi_update_materials)."""
         args, keep = Scene._materials_args(self, "update_materials", mat, uv, atlas, atlas_res, atlas_layers)
         L.check(L.lib().fspt_multi_update_materials(self._m, *args))
+        if atlas is not None:
+            self._retained_atlas_res = args[3]
+
+    def update_textures(self, mat, uv, packer_or_desc):
+        """Scene.update_textures (host arrays) on every device's copy of the scene (fspt_multi_update_textures)."""
+        from . import scene as S
+        mat, uv = Scene._textures_mat_uv(self, "update_textures", mat, uv)
+        p, _, _, keep = S.texture_pack_struct(packer_or_desc, None, "update_textures")
+        L.check(L.lib().fspt_multi_update_textures(self._m, L.fptr(mat), None if uv is None else L.fptr(uv), C.byref(p)))
+        self._retained_atlas_res = int(p.res)
+
+    def patch_textures(self, layer_ids, layers, images=None, res=None):
+        """Scene.patch_textures (host arrays) on every device's copy of the scene (fspt_multi_patch_textures)."""
+        from . import scene as S
+        ids, layers, images = Scene._patch_args("patch_textures", layer_ids, layers, images, None)
+        res = int(res) if res is not None else getattr(self, "_retained_atlas_res", None) or 1
+        p, _, _, keep = S.texture_pack_struct({"res": res, "images": images, "layers": layers}, None, "patch_textures")
+        L.check(L.lib().fspt_multi_patch_textures(self._m, L.u32ptr(ids), ids.size, C.byref(p)))
 
     def update_environment(self, env, env_w, env_h, bins=None):
         """Scene.update_environment on every device's copy of the scene (fspt_multi_update_environment; bins=None: each

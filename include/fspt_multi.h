@@ -47,6 +47,9 @@ int fspt_multi_set_skin(fspt_multi *m, const fspt_skin_desc *d);
 int fspt_multi_update_skin(fspt_multi *m, const float *xf, uint32_t n_joints, const float *morph_w, uint32_t n_morph);
 /* fspt_scene_update_materials / _environment on every device's copy of the scene; arguments the first device refuses change nothing */
 int fspt_multi_update_materials(fspt_multi *m, const float *mat, const float *uv, const uint8_t *atlas, uint32_t atlas_res, uint32_t atlas_layers);
+/* fspt_scene_update_textures / _patch_textures, host-pointer form, on every device's copy of the scene */
+int fspt_multi_update_textures(fspt_multi *m, const float *mat, const float *uv, const fspt_texture_pack *p);
+int fspt_multi_patch_textures(fspt_multi *m, const uint32_t *layer_ids, uint32_t n, const fspt_texture_pack *p);
 int fspt_multi_update_environment(fspt_multi *m, const uint8_t *env, uint32_t env_w, uint32_t env_h, const uint32_t *bins, uint32_t n_bins);
 /* fspt_scene_update_environment_auto / _sky on every device's copy: each device builds its own map and bins */
 int fspt_multi_update_environment_auto(fspt_multi *m, const uint8_t *env, uint32_t w, uint32_t h);

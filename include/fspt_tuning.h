@@ -101,6 +101,11 @@ int fspt_scene_read_appearance(fspt_scene *s, int what, void *out, uint64_t cap,
 /* the last appearance update: kernels first to last (HIP events; the read-back of the per-layer flags and the host's set
  * classification lie between them), launches, bytes uploaded, raw-atlas bytes retained on the device (0: never updated) */
 int fspt_scene_last_appearance_ms(fspt_scene *s, float *ms, uint32_t *launches, uint64_t *uploaded, uint64_t *retained);
+/* the last fspt_atlas_pack_gpu of this process: the uploads and the read-back by the host's clock, the kernel by HIP events */
+int fspt_atlas_pack_last_ms(float *upload_ms, float *kernel_ms, float *readback_ms);
+/* The argument checks of the texture entries on the host alone: a whole description (layer_ids NULL and n 0), or a patch of
+ * n layers against a retained atlas of raw_layers layers of raw_res^2 texels (raw_layers 0: none, FSPT_E_STATE).  No device. */
+int fspt_texture_pack_check_eval(const fspt_texture_pack *p, const uint32_t *layer_ids, uint32_t n, uint32_t raw_layers, uint32_t raw_res);
 /* The set classification fspt_scene_create and fspt_scene_update_materials share, on the host alone: per triangle its
  * texture set, *n_sets, and the first min(cap_sets, *n_sets) 12-word rows of the set table, from matTex, the per-layer
  * "every texel equal" flags and first texels, under the current interleaving budget.  No device. */

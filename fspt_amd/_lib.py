@@ -94,6 +94,11 @@ class TexturePack(C.Structure):
 TEXLAYER_COLOR, TEXLAYER_IMAGE, TEXLAYER_PIXELS = 0, 1, 2
 
 
+class JpegParams(C.Structure):
+    """fspt_jpeg_params: quality 1..100, subsampling 0 = 4:4:4 / 1 = 4:2:0, MCUs per restart interval (0 = one MCU row)"""
+    _fields_ = [("quality", C.c_uint32), ("subsampling", C.c_uint32), ("restart_mcus", C.c_uint32)]
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("target_rel_mse", C.c_double), ("max_ticks", C.c_uint32), ("min_ticks", C.c_uint32), ("round_ticks", C.c_uint32)]
 
@@ -327,6 +332,13 @@ SIGNATURES = {
     "fspt_multi_update_environment_auto": (C.c_int, [_VP, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]),
     "fspt_multi_update_sky": (C.c_int, [_VP, C.POINTER(SkyParams), C.c_uint32, C.c_uint32]),
     "fspt_env_box_sums_eval": (C.c_int, [C.c_int, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, _U32, C.c_uint32, C.POINTER(C.c_double)]),
+    "fspt_jpeg_bound": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(JpegParams), C.POINTER(C.c_size_t)]),
+    "fspt_jpeg_encode": (C.c_int, [C.c_int, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(JpegParams), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fspt_jpeg_encode_device": (C.c_int, [C.c_int, _VP, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(JpegParams), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fspt_jpeg_coefficients_eval": (C.c_int, [C.c_int, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(JpegParams), C.POINTER(C.c_int16)]),
+    "fspt_jpeg_last_ms": (C.c_int, [_F, C.POINTER(C.c_uint64)]),
+    "fspt_draw_jpeg": (C.c_int, [_VP, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.POINTER(JpegParams), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fspt_present_jpeg": (C.c_int, [_VP, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.POINTER(JpegParams), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
     "fspt_multi_last_stage_ms": (C.c_int, [_VP, _F, C.c_uint32]),
     "fspt_device_memory": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fspt_last_error": (C.c_char_p, []),

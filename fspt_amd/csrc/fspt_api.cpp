@@ -855,13 +855,64 @@ extern "C" int fspt_present(fspt_target *t, float exposure, float saturation, in
   HIP_TRY(hipMemcpyAsync(t->pr_host[slot], t->pr_dev[slot], n * 4, hipMemcpyDeviceToHost, ds));
   HIP_TRY(hipEventRecord(t->pr_copied[slot], ds));
   t->pr_ticks[slot] = t->acc_ticks;
+  t->pr_kind[slot] = 0;
   // the previous present's frame
   const int prev = t->pr_slot;
   t->pr_slot = slot;
   *ticks_out = 0;
   if (prev >= 0) {
     HIP_TRY(hipEventSynchronize(t->pr_copied[prev]));
-    if (t->pr_ticks[prev]) { std::memcpy(out_rgba8, t->pr_host[prev], n * 4); *ticks_out = t->pr_ticks[prev]; }
+    if (t->pr_ticks[prev] && t->pr_kind[prev] == 0) { std::memcpy(out_rgba8, t->pr_host[prev], n * 4); *ticks_out = t->pr_ticks[prev]; } // (a file fspt_present_jpeg enqueued is dropped)
+  }
+  return FSPT_OK;
+}
+
+// fspt_present with the encode behind the draw, on the draw's stream: the frame stays on the device, its
+// length comes to pinned memory in front of the slot's event, and the call that returns the file copies that many bytes.
+// pr_acc is recorded behind the ENCODE: the next frame's resolve, and with it its draw and encode, which may run on the
+// other lane's stream, start after this one has finished with the encoder's work buffers.
+extern "C" int fspt_present_jpeg(fspt_target *t, float exposure, float saturation, int denoise, float max_sigma, float scale,
+                                 const fspt_jpeg_params *p, uint8_t *out, size_t cap, size_t *bytes_out, uint32_t *ticks_out) {
+  const char *fn = "fspt_present_jpeg";
+  if (!t || !out || !bytes_out || !ticks_out) { fspt_set_error("%s: NULL argument", fn); return FSPT_E_INVALID; }
+  int rc = fspt::jpeg_check_params(p, fn);
+  if (rc) return rc;
+  if (!(scale > 0.0f && scale <= 1.0f)) { fspt_set_error("%s: scale must be in (0, 1]", fn); return FSPT_E_INVALID; }
+  if (fspt_device_count() <= 0) { fspt_set_error("%s: no HIP device available; libfspt has no CPU fallback", fn); return FSPT_E_NO_DEVICE; }
+  fspt::JpegPlan pl;
+  if ((rc = fspt::jpeg_plan(p, t->W, t->H, fn, pl))) return rc;
+  HIP_TRY(hipSetDevice(t->scene->device));
+  if ((rc = present_alloc(t))) return rc;
+  for (uint32_t *&c : t->jp_count) if (!c) HIP_TRY(hipHostMalloc((void **)&c, sizeof(uint32_t), hipHostMallocDefault));
+  if (!t->jp_copy) HIP_TRY(hipStreamCreateWithFlags(&t->jp_copy, hipStreamNonBlocking));
+  // other parameters than the encoder's: its work buffers are made again, once the frame in flight is through with them
+  if (t->pr_slot >= 0) {
+    const fspt::JpegPlan &q = t->jp.pl;
+    if (t->jp.valid && !(q.quality == pl.quality && q.sub == pl.sub && q.ri == pl.ri)) HIP_TRY(hipEventSynchronize(t->pr_copied[t->pr_slot]));
+  }
+  HIP_TRY(fspt::jpeg_ensure(t->jp, pl, 2, fspt::jpeg_bound_max(t->W, t->H)));
+  t->pr_active = true;
+  t->ev_used = 0; t->ev_overflow = false;
+  if ((rc = present_flush(t))) return rc;
+  hipStream_t ds = t->pr_acc_stream ? t->pr_acc_stream : t->stream;
+  const int slot = t->pr_slot < 0 ? 0 : t->pr_slot ^ 1;
+  HIP_TRY(draw_launch(t, t->accum, exposure, saturation, denoise, max_sigma, scale, t->pr_dev[slot], ds));
+  HIP_TRY(fspt::jpeg_launch(t->jp, t->pr_dev[slot], 1, slot, ds));
+  HIP_TRY(hipMemcpyAsync(t->jp_count[slot], t->jp.off + t->jp.pl.n_int, sizeof(uint32_t), hipMemcpyDeviceToHost, ds));
+  HIP_TRY(hipEventRecord(t->pr_acc, ds));
+  t->pr_acc_stream = ds;
+  HIP_TRY(hipEventRecord(t->pr_copied[slot], ds));
+  t->pr_ticks[slot] = t->acc_ticks;
+  t->pr_kind[slot] = 1;
+  const int prev = t->pr_slot;
+  t->pr_slot = slot;
+  *ticks_out = 0; *bytes_out = 0;
+  if (prev >= 0) {
+    HIP_TRY(hipEventSynchronize(t->pr_copied[prev]));
+    if (t->pr_ticks[prev] && t->pr_kind[prev] == 1) { // (an RGBA8 frame fspt_present enqueued is dropped)
+      if ((rc = fspt::jpeg_deliver(t->jp.out[prev], *t->jp_count[prev], out, cap, bytes_out, t->jp_copy, fn))) return rc; // (cap too small: the frame is dropped)
+      *ticks_out = t->pr_ticks[prev];
+    }
   }
   return FSPT_OK;
 }

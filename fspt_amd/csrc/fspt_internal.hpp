@@ -16,6 +16,7 @@
 //   fspt_bvh_build.hip     the GPU BVH builder;  fspt_refit.hip  in-place refit and rebuild;  fspt_pose.hip  part transforms and skinning
 //   fspt_appearance.hip    in-place appearance update: the texture-set, atlas and environment layouts and the material part of the hit records
 //   fspt_sky.hip           the sky generator and the environment's importance bins, built on the GPU
+//   fspt_jpeg.hip          the baseline JPEG encoder behind fspt_jpeg_encode, fspt_draw_jpeg and fspt_present_jpeg, and its stand-alone entries
 #pragma once
 #include "../../include/fspt.h"
 #include "../../include/fspt_tuning.h"
@@ -242,6 +243,37 @@ int env_box_sums_run(const uint8_t *rgbe, uint32_t w, uint32_t h, const uint32_t
 // then are the scene's buffers swapped and s->sky filled in.
 int environment_gpu(fspt_scene *s, const char *fn, const uint8_t *env, bool env_on_device, const fspt_sky_params *sky, uint32_t w, uint32_t h);
 void sky_release(fspt_scene *s);
+// fspt_jpeg.hip: the baseline JPEG encoder.  JpegPlan: what follows from a size and checked parameters, on the
+// host.  JpegEnc: the device memory of one encoder - the header and divisors of its plan, the work buffers, up to two
+// output buffers - owned by a target (fspt_draw_jpeg, fspt_present_jpeg) or by one stand-alone call.
+static const uint32_t JPEG_HEADER_BYTES = 629u; // SOI .. SOS: the same for every size and setting
+struct JpegPlan {
+  uint32_t w, h, quality, sub, ri; // ri: MCUs per restart interval as DRI carries it
+  uint32_t mw, mh, n_mcu, bpm, n_blocks, n_int;
+  size_t slot_bytes; // an interval's scratch slot
+  size_t bound;      // no file of this plan is longer
+};
+struct JpegEnc {
+  JpegPlan pl{};
+  bool valid = false;
+  uint8_t *cfg = nullptr;     // 128 uint16 divisors | the header
+  int16_t *coef = nullptr;    // stage one's output
+  uint8_t *scratch = nullptr; // n_int slots
+  uint32_t *len = nullptr, *off = nullptr; // per interval: bytes | where it lands; off[n_int] = the file's length
+  uint8_t *out[2] = {nullptr, nullptr};
+  size_t out_bytes = 0;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the three stages of the last launch
+};
+int jpeg_check_params(const fspt_jpeg_params *prm, const char *fn); // the parameters alone (a target's entries: before the handle is looked at)
+int jpeg_plan(const fspt_jpeg_params *prm, uint32_t w, uint32_t h, const char *fn, JpegPlan &pl); // validates: FSPT_E_INVALID, no device touched
+size_t jpeg_bound_max(uint32_t w, uint32_t h);                                                    // the largest bound of any parameters
+hipError_t jpeg_ensure(JpegEnc &e, const JpegPlan &pl, int n_out, size_t out_bytes);              // nothing of `e` may be in use
+hipError_t jpeg_launch_blocks(JpegEnc &e, const uint32_t *rgba, int bottom_up, hipStream_t st);
+hipError_t jpeg_launch(JpegEnc &e, const uint32_t *rgba, int bottom_up, int slot, hipStream_t st); // no host read, no synchronisation
+int jpeg_deliver(const uint8_t *dev, uint32_t n, uint8_t *out, size_t cap, size_t *bytes_out, hipStream_t st, const char *fn); // *bytes_out = n; cap < n: FSPT_E_INVALID, out untouched; else n bytes copied on st, which is waited for
+int jpeg_collect(JpegEnc &e, int slot, hipStream_t st, uint8_t *out, size_t cap, size_t *bytes_out, const char *fn); // waits for st, then jpeg_deliver
+void jpeg_note_ms(JpegEnc &e);  // the stage times of a finished launch, for fspt_jpeg_last_ms
+void jpeg_release(JpegEnc &e);
 // fspt_pose.hip.  pose_run: s->pose set, s->rf.stage allocated, the call ordered against the targets;
 // mats_host = n_parts x 30 floats (a | D | N).  Uploads them, runs k_pose_transform into s->rf.stage and waits.
 int pose_run(fspt_scene *s, const float *mats_host);
@@ -491,6 +523,13 @@ struct fspt_target {
   fspt::BloomP bl_p{};
   hipEvent_t bl_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // down chain | tail | up chain | draw of the last bloomed draw
   bool bl_timed = false;
+  // JPEG output (fspt_draw_jpeg / fspt_present_jpeg): allocated on first use.  Under present a slot holds either
+  // fspt_present's RGBA8 frame (pr_host) or fspt_present_jpeg's file (jp.out[slot], its length in jp_count[slot])
+  fspt::JpegEnc jp;
+  uint32_t *jp_frame = nullptr;               // fspt_draw_jpeg's drawn frame, W*H texels
+  uint32_t *jp_count[2] = {nullptr, nullptr}; // pinned host memory: a slot's byte count, current behind pr_copied[slot]
+  int pr_kind[2] = {0, 0};                    // 0: an RGBA8 frame, 1: a JPEG file
+  hipStream_t jp_copy = nullptr;              // a present file's bytes come to the host here: the copy waits for no stream that holds the next frame
 };
 
 static const uint32_t WORK_RING = 4096;

@@ -966,6 +966,73 @@ static napi_value Present(napi_env env, napi_callback_info info) {
   NAPI_OK(napi_create_uint32(env, ticks, &r));
   return r;
 }
+/* JPEG output (include/fspt.h fspt_jpeg_* / fspt_draw_jpeg / fspt_present_jpeg).  The file is written into a
+ * Uint8Array the JS host keeps; a call answers the bytes written, or -(bytes needed) when the array is too small (the
+ * library's FSPT_E_INVALID with *bytes_out above cap: nothing was written; a present frame refused so is dropped). */
+static int jpeg_args(napi_env env, const napi_value *a, fspt_jpeg_params *p) { /* quality, subsampling, restartMcus */
+  double q, s, r;
+  if (get_f64(env, a[0], &q) || get_f64(env, a[1], &s) || get_f64(env, a[2], &r)) return -1;
+  if (!(q >= 0.0 && q <= 4294967295.0 && s >= 0.0 && s <= 4294967295.0 && r >= 0.0 && r <= 4294967295.0)) {
+    napi_throw_range_error(env, NULL, "fspt_napi: JPEG parameters must be non-negative integers");
+    return -1;
+  }
+  p->quality = (uint32_t)q; p->subsampling = (uint32_t)s; p->restart_mcus = (uint32_t)r;
+  return 0;
+}
+static napi_value jpeg_answer(napi_env env, int rc, size_t cap, size_t bytes) {
+  napi_value r;
+  if (rc == FSPT_E_INVALID && bytes > cap) { NAPI_OK(napi_create_double(env, -(double)bytes, &r)); return r; }
+  FSPT_OK_OR_THROW(rc);
+  NAPI_OK(napi_create_double(env, (double)bytes, &r));
+  return r;
+}
+static napi_value JpegBound(napi_env env, napi_callback_info info) {
+  /* jpegBound(width, height, quality, subsampling, restartMcus) -> bytes no file exceeds */
+  napi_value a[5], r; double w, h; fspt_jpeg_params p; size_t n = 0;
+  if (get_args(env, info, 5, a) || get_f64(env, a[0], &w) || get_f64(env, a[1], &h) || jpeg_args(env, a + 2, &p)) return NULL;
+  FSPT_OK_OR_THROW(fspt_jpeg_bound(w >= 0.0 && w <= 4294967295.0 ? (uint32_t)w : 0u, h >= 0.0 && h <= 4294967295.0 ? (uint32_t)h : 0u, &p, &n));
+  NAPI_OK(napi_create_double(env, (double)n, &r));
+  return r;
+}
+static napi_value JpegEncode(napi_env env, napi_callback_info info) {
+  /* jpegEncode(device, Uint8Array(w*h*4), width, height, bottomUp, quality, subsampling, restartMcus, Uint8Array out) */
+  napi_value a[9]; void *src, *dst; size_t ns, nd, bytes = 0; double dev, w, h; bool up; fspt_jpeg_params p;
+  if (get_args(env, info, 9, a) || get_f64(env, a[0], &dev) || typed(env, a[1], napi_uint8_array, 0, &src, &ns) || get_f64(env, a[2], &w) || get_f64(env, a[3], &h)) return NULL;
+  NAPI_OK(napi_get_value_bool(env, a[4], &up));
+  if (jpeg_args(env, a + 5, &p) || typed(env, a[8], napi_uint8_array, 0, &dst, &nd)) return NULL;
+  if (!(w >= 1.0 && w <= 65535.0 && h >= 1.0 && h <= 65535.0) || (double)ns != w * h * 4.0) {
+    napi_throw_range_error(env, NULL, "jpegEncode: need width*height*4 bytes, width and height in 1..65535");
+    return NULL;
+  }
+  const int rc = fspt_jpeg_encode((int)dev, (const uint8_t *)src, (uint32_t)w, (uint32_t)h, up ? 1 : 0, &p, (uint8_t *)dst, nd, &bytes);
+  return jpeg_answer(env, rc, nd, bytes);
+}
+static napi_value DrawJpeg(napi_env env, napi_callback_info info) {
+  /* drawJpeg(target, source, exposure, saturation, denoise, maxSigma, scale, quality, subsampling, restartMcus, Uint8Array out) */
+  napi_value a[11]; void *h, *dst; size_t nd, bytes = 0; double src, ex, sat, sig, scale; bool den; fspt_jpeg_params p;
+  if (get_args(env, info, 11, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  if (get_f64(env, a[1], &src) || get_f64(env, a[2], &ex) || get_f64(env, a[3], &sat)) return NULL;
+  NAPI_OK(napi_get_value_bool(env, a[4], &den));
+  if (get_f64(env, a[5], &sig) || get_f64(env, a[6], &scale) || jpeg_args(env, a + 7, &p) || typed(env, a[10], napi_uint8_array, 0, &dst, &nd)) return NULL;
+  const int rc = fspt_draw_jpeg((fspt_target *)h, (int)src, (float)ex, (float)sat, den ? 1 : 0, (float)sig, (float)scale, &p, (uint8_t *)dst, nd, &bytes);
+  return jpeg_answer(env, rc, nd, bytes);
+}
+static napi_value PresentJpeg(napi_env env, napi_callback_info info) {
+  /* presentJpeg(target, exposure, saturation, denoise, maxSigma, scale, quality, subsampling, restartMcus, Uint8Array out)
+   * -> [bytes (or -needed), ticks]: fspt_present_jpeg; ticks 0 = nothing presented */
+  napi_value a[10], r, v; void *h, *dst; size_t nd, bytes = 0; double ex, sat, sig, scale; bool den; fspt_jpeg_params p; uint32_t ticks = 0;
+  if (get_args(env, info, 10, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  if (get_f64(env, a[1], &ex) || get_f64(env, a[2], &sat)) return NULL;
+  NAPI_OK(napi_get_value_bool(env, a[3], &den));
+  if (get_f64(env, a[4], &sig) || get_f64(env, a[5], &scale) || jpeg_args(env, a + 6, &p) || typed(env, a[9], napi_uint8_array, 0, &dst, &nd)) return NULL;
+  const int rc = fspt_present_jpeg((fspt_target *)h, (float)ex, (float)sat, den ? 1 : 0, (float)sig, (float)scale, &p, (uint8_t *)dst, nd, &bytes, &ticks);
+  if (!(v = jpeg_answer(env, rc, nd, bytes))) return NULL;
+  NAPI_OK(napi_create_array_with_length(env, 2, &r));
+  NAPI_OK(napi_set_element(env, r, 0, v));
+  NAPI_OK(napi_create_uint32(env, ticks, &v));
+  NAPI_OK(napi_set_element(env, r, 1, v));
+  return r;
+}
 /* guided denoiser (include/fspt.h fspt_features / fspt_denoise / fspt_draw_denoised) */
 static napi_value Features(napi_env env, napi_callback_info info) {
   /* features(target, params (as render), samples, seed) */
@@ -1635,7 +1702,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
       {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"sceneUpdateSky", SceneUpdateSky}, {"sceneUpdateEnvironmentAuto", SceneUpdateEnvironmentAuto}, {"skyGenerate", SkyGenerate}, {"atlasPackGpu", AtlasPackGpu}, {"sceneUpdateTextures", SceneUpdateTextures}, {"scenePatchTextures", ScenePatchTextures}, {"envBinsGpu", EnvBinsGpu}, {"sceneSetPose", SceneSetPose}, {"sceneUpdateTransforms", SceneUpdateTransforms}, {"sceneSetSkin", SceneSetSkin}, {"sceneUpdateSkin", SceneUpdateSkin}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
-      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setCameraModel", SetCameraModel}, {"cameraModel", CameraModel}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
+      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"jpegBound", JpegBound}, {"jpegEncode", JpegEncode}, {"drawJpeg", DrawJpeg}, {"presentJpeg", PresentJpeg}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setCameraModel", SetCameraModel}, {"cameraModel", CameraModel}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},
       {"renderAsync", RenderAsync}, {"multiCreate", MultiCreate}, {"multiDestroy", MultiDestroy}, {"multiTarget", MultiTarget},
       {"multiCamera", MultiCamera}, {"multiTrace", MultiTrace}, {"multiRender", MultiRender}, {"multiRenderAsync", MultiRenderAsync},

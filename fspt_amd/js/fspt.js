@@ -352,6 +352,24 @@ function skyArgs(fn, o) {
   const params = Float32Array.of(p.sunDir[0], p.sunDir[1], p.sunDir[2], p.turbidity, p.sunIntensity, p.sunRadius, p.gain, alb[0], alb[1], alb[2]);
   return { params, viewSamples: p.viewSamples, lightSamples: p.lightSamples, width: p.width, height: p.height };
 }
+const JPEG_SUBSAMPLING = { '444': 0, '420': 1 };
+const JPEG_SOURCES = { accumulator: 0, denoised: 1, temporal: 2, temporalDenoised: 3 };
+/** An RGBA8 image (Uint8Array of width*height*4, alpha ignored; bottomUp: row 0 is the bottom, as drawQuad returns it) as a
+ *  baseline JPEG file, encoded on the GPU (include/fspt.h fspt_jpeg_encode, DESIGN.md 8.19) -> Buffer.
+ *  opts: {quality (85), subsampling ('420' | '444'), restartMcus (0 = one MCU row), bottomUp (false), device (0)}. */
+function jpegEncode(rgba, width, height, opts) {
+  const o = opts || {};
+  const sub = JPEG_SUBSAMPLING[o.subsampling === undefined ? '420' : String(o.subsampling)];
+  if (sub === undefined) throw new RangeError("jpegEncode: subsampling must be '444' or '420'");
+  if (!(rgba instanceof Uint8Array) || rgba.length !== width * height * 4) throw new RangeError('jpegEncode: need a Uint8Array of width*height*4 bytes');
+  const q = o.quality === undefined ? 85 : o.quality, ri = o.restartMcus === undefined ? 0 : o.restartMcus;
+  let out = new Uint8Array(width * height * 4 + 1024);
+  let n = addon.jpegEncode(o.device || 0, rgba, width, height, !!o.bottomUp, q, sub, ri, out);
+  if (n < 0) { out = new Uint8Array(Math.max(-n, addon.jpegBound(width, height, q, sub, ri))); n = addon.jpegEncode(o.device || 0, rgba, width, height, !!o.bottomUp, q, sub, ri, out); }
+  if (n < 0) throw new Error('jpegEncode: the file outgrew the bound');
+  return Buffer.from(out.subarray(0, n));
+}
+
 /** a generated sky as {rgbe Uint8Array, width, height} on HIP device `device` (fspt_sky_generate): what buildScene takes as env */
 function skyGenerate(o, device) {
   const k = skyArgs('skyGenerate', o);
@@ -493,6 +511,41 @@ class PathTracer {
     if (!out || out.length !== this.resolution[0] * this.resolution[1] * 4) throw new RangeError('present: need W*H*4 bytes');
     return addon.present(this._target, exposure === undefined ? 1 : exposure, saturation === undefined ? 1 : saturation,
       !!denoise, maxSigma === undefined ? 3 : maxSigma, out, resScale === undefined ? 1 : resScale);
+  }
+  /** JPEG output (include/fspt.h fspt_draw_jpeg / fspt_present_jpeg, DESIGN.md 8.19): the frame is drawn AND encoded on the GPU -
+   *  a baseline JFIF file, byte for byte libjpeg's - and only the file crosses the bus.  opts: {source: 'accumulator' | 'denoised' |
+   *  'temporal' | 'temporalDenoised', exposure, saturation, denoise, maxSigma, scale, quality (85), subsampling ('420' | '444'),
+   *  restartMcus (0 = one MCU row)}.  drawJpeg -> Buffer.  presentJpeg -> {jpeg: Buffer | null, ticks}: the PREVIOUS call's file
+   *  (present()'s one frame of latency; null with ticks 0 when there is nothing to present).  One reusable buffer of W*H*4 + 1024
+   *  bytes, grown to the library's bound when a file needs more (a present frame that did is dropped by the library). */
+  _jpegArgs(o, fn) {
+    o = o || {};
+    const sub = JPEG_SUBSAMPLING[o.subsampling === undefined ? '420' : String(o.subsampling)];
+    if (sub === undefined) throw new RangeError(fn + ": subsampling must be '444' or '420'");
+    const q = o.quality === undefined ? 85 : o.quality, ri = o.restartMcus === undefined ? 0 : o.restartMcus;
+    if (!Number.isInteger(q) || q < 1 || q > 100) throw new RangeError(fn + ': quality must be an integer in 1..100');
+    if (!Number.isInteger(ri) || ri < 0 || ri > 65535) throw new RangeError(fn + ': restartMcus must be an integer in 0..65535');
+    if (!this._jpegBuf) this._jpegBuf = new Uint8Array(this.resolution[0] * this.resolution[1] * 4 + 1024);
+    return { o, enc: [q, sub, ri], draw: [o.exposure === undefined ? 1 : o.exposure, o.saturation === undefined ? 1 : o.saturation, !!o.denoise,
+      o.maxSigma === undefined ? 3 : o.maxSigma, o.scale === undefined ? 1 : o.scale] };
+  }
+  _jpegGrow(need, enc) {
+    this._jpegBuf = new Uint8Array(Math.max(need, addon.jpegBound(this.resolution[0], this.resolution[1], enc[0], enc[1], enc[2])));
+  }
+  drawJpeg(opts) {
+    const a = this._jpegArgs(opts, 'drawJpeg');
+    const src = JPEG_SOURCES[a.o.source === undefined ? 'accumulator' : a.o.source];
+    if (src === undefined) throw new RangeError("drawJpeg: source must be 'accumulator', 'denoised', 'temporal' or 'temporalDenoised'");
+    let n = addon.drawJpeg(this._target, src, ...a.draw, ...a.enc, this._jpegBuf);
+    if (n < 0) { this._jpegGrow(-n, a.enc); n = addon.drawJpeg(this._target, src, ...a.draw, ...a.enc, this._jpegBuf); }
+    if (n < 0) throw new Error('drawJpeg: the file outgrew the bound');
+    return Buffer.from(this._jpegBuf.subarray(0, n));
+  }
+  presentJpeg(opts) {
+    const a = this._jpegArgs(opts, 'presentJpeg');
+    const [n, ticks] = addon.presentJpeg(this._target, ...a.draw, ...a.enc, this._jpegBuf);
+    if (n < 0) { this._jpegGrow(-n, a.enc); return { jpeg: null, ticks: 0 }; }
+    return { jpeg: ticks ? Buffer.from(this._jpegBuf.subarray(0, n)) : null, ticks };
   }
   /** Guided denoiser (include/fspt.h, DESIGN.md 8).  features(): guide buffers of the current view - `samples` camera rays
    *  per pixel to their first hit; denoise(): the edge-avoiding a-trous filter of the accumulator, {iterations, sigmaColor,
@@ -883,5 +936,5 @@ class MultiPathTracer {
 // memory later scenes may spend on interleaved material textures (fspt_set_texture_interleave_budget; results do not depend on it)
 function setTextureInterleaveBudget(bytes) { addon.setTextureInterleaveBudget(bytes); }
 
-module.exports = { addon, setTextureInterleaveBudget, skyGenerate, envBinsGpu, atlasPackGpu, SKY_DEFAULTS, MultiPathTracer, AtlasLayers, resolveMaterial, readMtl, mergeSceneProps, resampleImage, packReferenceScene, buildScene,
+module.exports = { addon, setTextureInterleaveBudget, jpegEncode, skyGenerate, envBinsGpu, atlasPackGpu, SKY_DEFAULTS, MultiPathTracer, AtlasLayers, resolveMaterial, readMtl, mergeSceneProps, resampleImage, packReferenceScene, buildScene,
   PathTracer, saveBlob, loadBlob };

@@ -200,10 +200,15 @@ function renderFrame(scene, settings, width, height, opts) {
   }
 }
 
-/** scene file -> PNG file (the reference POSTs canvas.toBlob's PNG to /upload/<scene>/<frame>, main.js:859-866) */
+/** scene file -> PNG file, or a JPEG file when outPath ends in .jpg / .jpeg (the reference POSTs canvas.toBlob's PNG to /upload/<scene>/<frame>, main.js:859-866) */
 function renderToPng(scenePath, outPath, width, height, opts) {
   const { scene, settings } = loadSceneFile(scenePath, opts && opts.assetRoot, 4, { bvh: opts && opts.bvh, device: opts && opts.device });
   const fr = renderFrame(scene, settings, width, height, opts);
+  if (/\.jpe?g$/i.test(outPath)) { // a JPEG encoded on the GPU (fspt.js jpegEncode, DESIGN.md 8.19); opts.jpeg: {quality, subsampling, restartMcus}
+    fs.mkdirSync(path.dirname(path.resolve(outPath)), { recursive: true });
+    fs.writeFileSync(outPath, F.jpegEncode(fr.rgba, width, height, Object.assign({ device: opts && opts.device }, opts && opts.jpeg)));
+    return fr;
+  }
   const rgb = new Uint8Array(width * height * 3);
   for (let i = 0, j = 0; i < fr.rgba.length; i += 4, j += 3) { rgb[j] = fr.rgba[i]; rgb[j + 1] = fr.rgba[i + 1]; rgb[j + 2] = fr.rgba[i + 2]; }
   fs.mkdirSync(path.dirname(path.resolve(outPath)), { recursive: true });

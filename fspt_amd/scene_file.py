@@ -195,6 +195,24 @@ def _render_on(pt, settings, samples, seed, saturation, denoise, max_sigma, ligh
     return rgba, rad
 
 
+def is_jpeg_path(path):
+    return str(path).lower().endswith((".jpg", ".jpeg"))
+
+
+def write_image(path, rgba, jpeg=None, device=0):
+    """An RGBA8 frame [H, W, 4], row 0 = top, as the picture `path` names: .jpg / .jpeg = a baseline JPEG encoded on the GPU
+    (tracer.jpeg_encode; jpeg = None or a dict of its quality / subsampling / restart_mcus), anything else
+    through Pillow as before."""
+    if is_jpeg_path(path):
+        from .tracer import jpeg_encode
+        data = jpeg_encode(rgba, device=device, **(jpeg or {}))
+        with open(path, "wb") as f:
+            f.write(data)
+        return
+    from PIL import Image
+    Image.fromarray(rgba[:, :, :3]).save(path)
+
+
 def write_sample_map(path, counts, max_ticks):
     """Ticks per pixel (PathTracer.sample_counts(), rows bottom-up) as an 8-bit grey PNG, top row first: 255 = max_ticks."""
     import numpy as np
@@ -292,7 +310,7 @@ def _sequence_sky(sky, k, n):
 
 
 def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", rebuild_above=None,
-                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, camera=None, sky=None, textures="cpu", **kw):
+                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, camera=None, sky=None, textures="cpu", jpeg=None, **kw):
     """frame=N sequencing (main.js:851-866, 966-969): for every N in `frames` load `scene_pattern.format(frame=N)`
     (the per-frame scene JSON the reference's server hands out for `?frame=N`), render it, write
     `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1.
@@ -338,8 +356,9 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     the scene file names.  With bvh="refit" the kept tracer's scene gets update_sky once per frame - nothing but the light is
     made again, on the GPU - and a kept frame reports "sky"; every other bvh builds each frame's scene under arrays_with_sky.
     textures: "cpu" or "gpu" - where every frame's atlas is resampled.  With "gpu" and bvh="refit" a kept frame
-    whose atlas changed sends its decoded images, not the atlas: Scene.update_textures packs them on the device."""
-    from PIL import Image
+    whose atlas changed sends its decoded images, not the atlas: Scene.update_textures packs them on the device.
+    jpeg: an out_pattern that ends in .jpg / .jpeg is written as a JPEG encoded on the GPU (write_image); None
+    or a dict of jpeg_encode's quality / subsampling / restart_mcus."""
     if textures not in S.TEXTURE_PACKERS:
         raise ValueError(f"render_sequence: textures must be one of {S.TEXTURE_PACKERS}, not {textures!r}")
     camera = _camera_model_params(camera, kw.get("adaptive"), None if temporal is None or temporal is False else temporal)
@@ -376,7 +395,7 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     def save(n, rgba):
         out = out_pattern.format(frame=n)
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-        Image.fromarray(rgba[:, :, :3]).save(out)
+        write_image(out, rgba, jpeg, device)
         written.append(out)
 
     if bvh != "refit":

@@ -291,6 +291,95 @@ def bloom_set_tail_texels(n):
     L.check(L.lib().fspt_bloom_set_tail_texels(int(n)))
 
 
+JPEG_SUBSAMPLING = {"444": 0, "420": 1}
+JPEG_SOURCES = {"accumulator": 0, "denoised": 1, "temporal": 2, "temporal_denoised": 3}
+
+
+def jpeg_params(quality=85, subsampling="420", restart_mcus=0):
+    """L.JpegParams of the wrappers' keywords (fspt_jpeg_params); the library checks the ranges"""
+    if str(subsampling) not in JPEG_SUBSAMPLING:
+        raise ValueError(f"subsampling must be one of {sorted(JPEG_SUBSAMPLING)}")
+    return L.JpegParams(int(quality), JPEG_SUBSAMPLING[str(subsampling)], int(restart_mcus))
+
+
+def jpeg_bound(width, height, quality=85, subsampling="420", restart_mcus=0):
+    """Bytes no JPEG file of this size and these settings exceeds (fspt_jpeg_bound; host only)"""
+    p, n = jpeg_params(quality, subsampling, restart_mcus), C.c_size_t()
+    L.check(L.lib().fspt_jpeg_bound(int(width), int(height), C.byref(p), C.byref(n)))
+    return int(n.value)
+
+
+class _JpegBuffer:
+    """The wrappers' reusable output buffer: W*H*4 + 1024 bytes, grown to fspt_jpeg_bound when a call reports a need"""
+
+    def __init__(self, width, height):
+        self.size = (int(width), int(height))
+        self.buf = np.empty(self.size[0] * self.size[1] * 4 + 1024, np.uint8)
+
+    def call(self, p, fn):
+        """fn(out pointer, cap, byref(bytes)) -> rc, repeated once with a buffer of the bound when the first was too small"""
+        n = C.c_size_t()
+        rc = fn(L.u8ptr(self.buf), self.buf.size, C.byref(n))
+        if rc == -1 and n.value > self.buf.size:
+            b = C.c_size_t()
+            L.check(L.lib().fspt_jpeg_bound(self.size[0], self.size[1], C.byref(p), C.byref(b)))
+            self.buf = np.empty(max(int(b.value), int(n.value)), np.uint8)
+            rc = fn(L.u8ptr(self.buf), self.buf.size, C.byref(n))
+        L.check(rc)
+        return int(n.value)
+
+
+_jpeg_buffers = {}
+
+
+def jpeg_encode(image, quality=85, subsampling="420", restart_mcus=0, bottom_up=False, device=0):
+    """A baseline JPEG file (bytes) of an RGBA8 image [H, W, 4], encoded on the GPU (fspt_jpeg_encode): a numpy
+    array, or a torch tensor on the device, which is read where it is (fspt_jpeg_encode_device).  Alpha is ignored;
+    bottom_up: row 0 is the bottom, as draw() returns it."""
+    p = jpeg_params(quality, subsampling, restart_mcus)
+    on_dev = hasattr(image, "data_ptr") and getattr(image, "is_cuda", False)
+    if on_dev:
+        import torch
+        if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 4:
+            raise ValueError("image must be a uint8 [H, W, 4] tensor")
+        image = image.contiguous()
+        device = image.device.index or 0
+        torch.cuda.current_stream(device).synchronize()  # whatever wrote the tensor has finished
+    else:
+        image = np.ascontiguousarray(image)
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 4:
+            raise ValueError("image must be a uint8 [H, W, 4] array")
+    h, w = int(image.shape[0]), int(image.shape[1])
+    buf = _jpeg_buffers.get((w, h))
+    if buf is None:
+        _jpeg_buffers.clear()  # one reusable buffer: the last size's
+        buf = _jpeg_buffers[(w, h)] = _JpegBuffer(w, h)
+    lib = L.lib()
+    if on_dev:
+        n = buf.call(p, lambda o, cap, nb: lib.fspt_jpeg_encode_device(int(device), C.c_void_p(image.data_ptr()), w, h, 1 if bottom_up else 0, C.byref(p), o, cap, nb))
+    else:
+        n = buf.call(p, lambda o, cap, nb: lib.fspt_jpeg_encode(int(device), L.u8ptr(image), w, h, 1 if bottom_up else 0, C.byref(p), o, cap, nb))
+    return buf.buf[:n].tobytes()
+
+
+def jpeg_coefficients_eval(image, quality=85, subsampling="420", bottom_up=False, device=0):
+    """Stage one of the encoder alone (fspt_jpeg_coefficients_eval): int16 [blocks, 64], zig-zag order, MCU-major"""
+    p = jpeg_params(quality, subsampling, 0)
+    image = np.ascontiguousarray(image, np.uint8)
+    h, w = image.shape[:2]
+    m = 16 if p.subsampling else 8
+    out = np.zeros((((w + m - 1) // m) * ((h + m - 1) // m) * (6 if p.subsampling else 3), 64), np.int16)
+    L.check(L.lib().fspt_jpeg_coefficients_eval(int(device), L.u8ptr(image), w, h, 1 if bottom_up else 0, C.byref(p), out.ctypes.data_as(C.POINTER(C.c_int16))))
+    return out
+
+
+def jpeg_last_ms():
+    """((blocks ms, entropy ms, offsets + pack ms), bytes brought to the host) of the last jpeg_encode (fspt_jpeg_last_ms)"""
+    ms, n = (C.c_float * 3)(), C.c_uint64()
+    L.check(L.lib().fspt_jpeg_last_ms(ms, C.byref(n)))
+    return tuple(float(x) for x in ms), int(n.value)
+
+
 def light_alias_table(weights):
     """The Vose alias table (float32 prob, uint32 alias) the light table stores for these weights (fspt_light_alias_table,
     a pure host function: no device needed)."""
@@ -1283,6 +1372,37 @@ class PathTracer:
         L.check(L.lib().fspt_present(self._t, float(exposure), float(saturation), 1 if denoise else 0,
                                      float(max_sigma), float(scale), L.u8ptr(out), C.byref(ticks)))
         return (out if ticks.value else None), int(ticks.value)
+
+    # ---- JPEG output (include/fspt.h fspt_draw_jpeg / fspt_present_jpeg) ----------------------------
+    def _jpeg_buffer(self):
+        if getattr(self, "_jpeg_buf", None) is None:
+            self._jpeg_buf = _JpegBuffer(*self.resolution)
+        return self._jpeg_buf
+
+    def draw_jpeg(self, source="accumulator", exposure=1.0, saturation=1.0, denoise=False, max_sigma=3.0, scale=1.0,
+                  quality=85, subsampling="420", restart_mcus=0):
+        """draw() ("accumulator"), draw_denoised() ("denoised") or temporal_draw() ("temporal", "temporal_denoised") of the
+        same arguments as a JPEG file (bytes), encoded on the GPU: the frame never leaves the device (fspt_draw_jpeg)."""
+        if source not in JPEG_SOURCES:
+            raise ValueError(f"source must be one of {sorted(JPEG_SOURCES)}")
+        p, buf, lib = jpeg_params(quality, subsampling, restart_mcus), self._jpeg_buffer(), L.lib()
+        n = buf.call(p, lambda o, cap, nb: lib.fspt_draw_jpeg(self._t, JPEG_SOURCES[source], float(exposure), float(saturation), 1 if denoise else 0,
+                                                              float(max_sigma), float(scale), C.byref(p), o, cap, nb))
+        return buf.buf[:n].tobytes()
+
+    def present_jpeg(self, exposure=1.0, saturation=1.0, denoise=False, max_sigma=3.0, scale=1.0, quality=85, subsampling="420", restart_mcus=0):
+        """present() with the frame encoded on the GPU behind its draw (fspt_present_jpeg): (the PREVIOUS call's JPEG file as
+        bytes, its sample count), or (None, 0) when there is nothing to present.  A file that outgrows the buffer is dropped
+        by the library; the buffer is grown for the next one."""
+        p, buf, lib = jpeg_params(quality, subsampling, restart_mcus), self._jpeg_buffer(), L.lib()
+        n, ticks = C.c_size_t(), C.c_uint32()
+        rc = lib.fspt_present_jpeg(self._t, float(exposure), float(saturation), 1 if denoise else 0, float(max_sigma), float(scale), C.byref(p),
+                                   L.u8ptr(buf.buf), buf.buf.size, C.byref(n), C.byref(ticks))
+        if rc == -1 and n.value > buf.buf.size:
+            buf.buf = np.empty(max(jpeg_bound(*self.resolution, quality, subsampling, restart_mcus), int(n.value)), np.uint8)
+            return None, 0
+        L.check(rc)
+        return (buf.buf[:n.value].tobytes() if ticks.value else None), int(ticks.value)
 
     # ---- guided denoiser (include/fspt.h fspt_features / fspt_denoise, DESIGN 8) --------------------------------
     def features(self, samples=8, seed=1):

@@ -413,6 +413,13 @@ int fspt_scene_light_table(fspt_scene *scene, uint32_t *n_tris, uint32_t *n_ligh
 int fspt_light_sample_eval(fspt_scene *scene, const float *in, uint32_t n, int32_t *tri, float *out);
 /* pure host function: the Vose alias table (float64, stored float32) of n weights (finite, >= 0, some > 0) */
 int fspt_light_alias_table(const float *weights, uint32_t n, float *prob, uint32_t *alias);
+/* JPEG encoder, test hooks.  fspt_jpeg_coefficients_eval: stage one alone - the quantised coefficients of
+ * fspt_jpeg_encode's arguments (host pointers), 64 int16 per block in zig-zag order, blocks MCU-major: per MCU Y Cb Cr
+ * (4:4:4) or Y00 Y01 Y10 Y11 Cb Cr (4:2:0); coef_out holds 64 * blocks values.  fspt_jpeg_last_ms: the three stages
+ * (blocks, entropy, offsets + pack) of the last fspt_jpeg_encode / _encode_device call from HIP events, and (or NULL) the
+ * bytes it brought to the host. */
+int fspt_jpeg_coefficients_eval(int device, const uint8_t *rgba8, uint32_t w, uint32_t h, int bottom_up, const fspt_jpeg_params *p, int16_t *coef_out);
+int fspt_jpeg_last_ms(float ms[3], uint64_t *bus_bytes);
 
 #ifdef __cplusplus
 }

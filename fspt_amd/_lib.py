@@ -168,6 +168,7 @@ SIGNATURES = {
     "fspt_scene_last_skin_ms": (C.c_int, [_VP, _F, _F, _U32, C.POINTER(C.c_uint64)]),
     "fspt_skin_check_eval": (C.c_int, [C.POINTER(SkinDesc), C.c_uint32, C.POINTER(C.c_uint64)]),
     "fspt_skin_set_form": (C.c_int, [C.c_int]),
+    "fspt_logic_set_stash": (C.c_int, [C.c_int]),
     "fspt_scene_rebuild_geometry": (C.c_int, [_VP, _F, _F, _U32]),
     "fspt_scene_rebuild_geometry_device": (C.c_int, [_VP, _VP, _VP, _VP]),
     "fspt_scene_last_rebuild_ms": (C.c_int, [_VP, _F, _F, _F, _U32, _U32]),

@@ -999,6 +999,12 @@ int fspt_target_set_trace_budget(fspt_target *t, uint32_t steps) {
   return FSPT_OK;
 }
 
+int fspt_logic_set_stash(int entries) {
+  if (entries < -1) { fspt_set_error("fspt_logic_set_stash: entries must be -1 (the library's choice), 0 (none) or a cap"); return FSPT_E_INVALID; }
+  fspt::g_logic_stash = entries;
+  return FSPT_OK;
+}
+
 int fspt_target_set_primary_form(fspt_target *t, int form) {
   if (!t) { fspt_set_error("fspt_target_set_primary_form: NULL target"); return FSPT_E_INVALID; }
   FLUSH_OR_RETURN(t);

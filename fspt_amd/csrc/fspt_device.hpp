@@ -312,6 +312,7 @@ struct WfP {
   uint32_t smp_seed;
   uint32_t lights;   // as in TraceP
   float light_q;
+  uint32_t stash;    // k_wf_logic: entries of its LDS stash of shaded paths' rows (0: none; set by launch_wf)
 };
 
 // kernel classes; also the slots of fspt_last_stage_ms
@@ -462,6 +463,7 @@ hipError_t launch_trace(const TraceP &p, bool gen_rays, bool count, int num_cus,
 // count: 0 = production kernels; 1 = counting variants doing the reference's work (NEE shadow rays traced to the closest
 // hit, tracer.fs:501); 2 = counting variants of the production work (shadow rays stop at the first hit)
 hipError_t launch_wf(int kernel, const WfP &p, int count, int num_cus, hipStream_t stream);
+extern int g_logic_stash; // k_wf_logic's LDS stash (fspt_logic_set_stash): -1 the library's choice, 0 none, n at most n entries
 size_t wf_max_stack_entries(); // deepest tree (entries per lane) whose traversal stacks fit the LDS of every kernel
 hipError_t launch_tile_pack(const TilePackP &p, bool unpack, hipStream_t stream);
 hipError_t launch_bvh_test(const TraceP &p, hipStream_t stream);

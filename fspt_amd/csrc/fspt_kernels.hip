@@ -640,10 +640,20 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_trace(const TraceP p) {
 #define WF_LOGIC_THREADS 512
 #endif
 // paths per thread of one block iteration of the logic kernel (classification is cheap; a larger chunk gives the dense
-// shading phase more whole waves of work)
+// shading phase more whole waves of work).  Chosen together with the stash below: at 8 a round-2 iteration lists ~1 270
+// shaded paths and the ~740 entries the LDS leaves hold 58 % of them; at 4 it lists ~635 and (nearly) all are parked.
+// Without the stash 4 and 8 tie; with it: logic 0.1200 (parent) -> 0.1072 (8) / 0.1058 (4) ms per tick at 20-tick batches,
+// 0.1174 -> 0.1052 / 0.1030 at 128 (profiles/r07/ab_scan*.log)
 #ifndef WF_LOGIC_U
-#define WF_LOGIC_U 8
+#define WF_LOGIC_U 4
 #endif
+// k_wf_logic's LDS stash of the shaded paths' rows: the most entries the library takes by itself (launch_wf also caps it at
+// what the CU's LDS leaves; fspt_logic_set_stash overrides it), and an entry's bytes: six float4 rows.  The colour row E is
+// not parked: a seventh row changes nothing at U = 4 and loses at 8, where it costs entries (profiles/r07/README.md)
+#ifndef WF_LOGIC_STASH
+#define WF_LOGIC_STASH 65535
+#endif
+#define WF_STASH_ENTRY_BYTES 96u
 // Block iterations of the primary and the logic launch by TICKET instead of a static stride (see k_wf_primary): 1 / 0
 // (measurement hooks: profiles/r05/ab_primary_tickets_*.log, ab_logic_tickets_*.log)
 #ifndef WF_PRIMARY_TICKETS
@@ -728,10 +738,29 @@ FM_DEV void store_path(const WfSet &o, uint32_t k, const Path &ps, uint32_t slot
     st4(o.P + k, make_float4(ps.pend.x, ps.pend.y, ps.pend.z, LIGHTS ? ps.lt : 0.0f));
   }
 }
-// path k of `in` with the traversal results of its rays; returns the slot
+// The rows of a path as they lie in memory, before they mean anything: what k_wf_logic parks in LDS between its passes.
+// d / pe / sh are only loaded (and only read) when the flags word b.w says the path has them.
+struct PathRows {
+  float4 a, b, c, d, pe;
+  int sh; // the NEE shadow ray's result
+};
+FM_DEV bool rows_have_nee(uint32_t flags, bool lights) { return (flags & WF_FLAG_SHADOW) != 0u || (lights && (flags & WF_FLAG_LQ) != 0u); }
+// rows of path k of `in` from global memory (the colour row E stays where it is: unpack_path fetches it)
+template <bool LIGHTS>
+FM_DEV void load_rows(const WfSet &in, uint32_t k, const int *shadow_hit, PathRows &r) {
+  r.a = ld4(in.A + k); r.b = ld4(in.B + k); r.c = ld4(in.C + k);
+  const uint32_t flags = __float_as_uint(r.b.w);
+  r.d = r.pe = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  r.sh = -1;
+  if (rows_have_nee(flags, LIGHTS)) {
+    r.d = ld4(in.D + k); r.pe = ld4(in.P + k);
+    if ((flags & WF_FLAG_SHADOW) && shadow_hit) r.sh = ldi(shadow_hit + k);
+  }
+}
+// rows -> Path, whatever the rows' source; returns the slot
 template <int SMP, bool LIGHTS = false>
-FM_DEV uint32_t load_path(const WfSet &in, uint32_t k, Path &ps, const int *shadow_hit, int &hitA) {
-  const float4 ro = ld4(in.A + k), rd = ld4(in.B + k), th = ld4(in.C + k);
+FM_DEV uint32_t unpack_path(const WfSet &in, uint32_t k, const PathRows &r, Path &ps, int &hitA) {
+  const float4 ro = r.a, rd = r.b, th = r.c;
   const uint32_t flags = __float_as_uint(rd.w);
   float4 co = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   if (!(flags & WF_FLAG_COLZERO)) co = ld4(in.E + k);
@@ -755,14 +784,21 @@ FM_DEV uint32_t load_path(const WfSet &in, uint32_t k, Path &ps, const int *shad
   hitA = -1;
   const bool lq = LIGHTS && (flags & WF_FLAG_LQ) != 0u;
   if (ps.hasShadow || lq) {
-    const float4 sd = ld4(in.D + k), pe = ld4(in.P + k);
+    const float4 sd = r.d, pe = r.pe;
     ps.envDir = v3(sd.x, sd.y, sd.z);
     ps.wx = lq ? 1.0f : sd.w;
     ps.pend = v3(pe.x, pe.y, pe.z);
     if constexpr (LIGHTS) { ps.lq = lq ? sd.w : 0.0f; ps.lt = pe.w; }
-    if (ps.hasShadow && shadow_hit) hitA = ldi(shadow_hit + k);
+    if (ps.hasShadow) hitA = r.sh;
   }
   return __float_as_uint(ro.w);
+}
+// path k of `in` with the traversal results of its rays; returns the slot
+template <int SMP, bool LIGHTS = false>
+FM_DEV uint32_t load_path(const WfSet &in, uint32_t k, Path &ps, const int *shadow_hit, int &hitA) {
+  PathRows r;
+  load_rows<LIGHTS>(in, k, shadow_hit, r);
+  return unpack_path<SMP, LIGHTS>(in, k, r, ps, hitA);
 }
 
 // a path whose traversal was suspended: its state, bit for bit, from index i of `in` to index k of `o`, flagged and
@@ -1413,15 +1449,31 @@ __global__ __launch_bounds__(WF_PRIMARY_THREADS, WF_LOGIC_WAVES) void k_wf_prima
 //      no bounce left): a path is shaded - and survives - iff its extension ray hit something and its bounce budget is
 //      not used up (tracer.fs:446,509); everything else finishes here.  The shaded
 //      ones are listed in LDS, and ONE atomic reserves their consecutive output indices BEFORE any shading;
-//   2a every thread finishes its own non-shaded paths (NEE result, environment on a miss -> fin[slot]);
+//   2a every thread finishes its own non-shaded paths (NEE result, environment on a miss -> fin[slot]); a lane whose own
+//      path is SHADED fetches that path's rows in the same instructions - the same memory lines, which hold both kinds -
+//      and parks them, raw, in the LDS stash at the path's place in the list (pass 1's per-wave list offsets, s_wb, and a
+//      ballot give the place again: nothing is kept in registers);
 //   2b the listed paths are shaded by consecutive threads - whole waves of shading work, instead of the 1-in-5 lanes
-//      a round-2 wave has when every thread keeps its own path (VALU lane utilisation 0.34 in round 1's profile).
+//      a round-2 wave has when every thread keeps its own path (VALU lane utilisation 0.34 in round 1's profile).  Entry
+//      t of the list comes from the stash when t < WfP::stash and from memory, as in 2a, beyond it (a round in which nearly
+//      everything is shaded does not fit); unpack_path turns the rows into a Path whatever their source.
+// Why the stash: a line of A holds 8 paths, so nearly every line of the block's range holds a finishing AND a shaded path,
+// and between pass 2a's touch and pass 2b's the CU's blocks stream far more than the L2 holds: without the stash the launch
+// fetched its path state from the fabric twice (round-2 launch of a 20-tick C2 batch: 77.3 M 128-byte fabric read requests
+// -> 61.4 M with 58 % of the listed paths parked; profiles/r07/README.md).  The stash is dynamic LDS behind the staged tables,
+// sized by launch_wf to what two resident blocks per CU leave; the barrier that publishes s_gbase publishes it, the
+// iteration's closing barrier protects it.  WF_HIT_PENDING paths are neither finished nor parked.  The colour row E is read
+// from memory by whoever unpacks the path.
 template <bool COUNT, bool LDSTAB, int SMP, bool LIGHTS = false>
 __global__ __launch_bounds__(WF_LOGIC_THREADS, LIGHTS ? WF_LIGHTS_WAVES : WF_LOGIC_WAVES) void k_wf_logic(const WfP p) {
   constexpr int U = WF_LOGIC_U;
-  extern __shared__ int lds_dyn[]; // the staged tables
+  constexpr int NW = WF_LOGIC_THREADS / WAVE;
+  extern __shared__ int lds_dyn[]; // [the staged tables] | [the stash: 6 rows of p.stash float4 each]
   __shared__ uint16_t s_list[U * WF_LOGIC_THREADS];
+  __shared__ uint16_t s_wb[U * NW]; // where in s_list wave w's shaded paths of pass u begin
   __shared__ uint32_t s_n, s_total, s_gbase, s_next;
+  static_assert((sizeof(s_list) + sizeof(s_wb)) % 16 == 0, "k_wf_logic: the dynamic LDS holds 16-byte rows");
+  static_assert(U <= 16, "k_wf_logic: own_fin holds two bits per own path");
   // the launch's last carry_blocks blocks move the suspended traversals' paths on (k_wf_carry's work) and are done
   const uint32_t n_blocks = gridDim.x - p.carry_blocks;
   if (blockIdx.x >= n_blocks) {
@@ -1443,6 +1495,11 @@ __global__ __launch_bounds__(WF_LOGIC_THREADS, LIGHTS ? WF_LIGHTS_WAVES : WF_LOG
   const uint32_t n_in = p.counts[p.cnt_in].n_ext;
   WfCounts *cn = p.counts + p.cnt_out;
   Counters cnt = {0, 0, 0, 0, 0, 0};
+  // the stash: entry t of the iteration's shaded list as six float4 rows t, cap + t, ... (A B C D P {t, hit, shadow hit, -}):
+  // consecutive threads touch consecutive 16-byte words of a row
+  const uint32_t cap = p.stash;
+  float4 *stash = reinterpret_cast<float4 *>(lds_dyn + (LDSTAB ? wf_table_bytes(p.scene.n_tex_sets, p.scene.n_bins, p.n_batch) / 4u : 0u));
+  const int wave = wave_index();
 
   // paths per thread and iteration: as many as keep every block busy, at most U
   uint32_t u_eff = (n_in + n_blocks * WF_LOGIC_THREADS - 1) / (n_blocks * WF_LOGIC_THREADS);
@@ -1472,8 +1529,8 @@ __global__ __launch_bounds__(WF_LOGIC_THREADS, LIGHTS ? WF_LIGHTS_WAVES : WF_LOG
       uint32_t wb = 0;
       if (lane == 0 && m) wb = atomicAdd(&s_n, (uint32_t)__popcll(m));
       wb = __builtin_amdgcn_readfirstlane(wb);
-      if (shade) s_list[wb + lane_rank(m)] = (uint16_t)loc;
-
+      if (shade) { s_list[wb + lane_rank(m)] = (uint16_t)loc; own_fin |= 0x10000u << u; }
+      if (lane == 0) s_wb[u * NW + (uint32_t)wave] = (uint16_t)wb;
     }
     __syncthreads();
     uint32_t my_gbase = 0;
@@ -1484,40 +1541,64 @@ __global__ __launch_bounds__(WF_LOGIC_THREADS, LIGHTS ? WF_LIGHTS_WAVES : WF_LOG
       my_gbase = tot ? atomicAdd(&cn->n_ext, tot) : 0u; // consumed after phase 2a, which covers its round trip
       if (tickets) s_next = n_blocks + atomicAdd(ticket, 1u);
     }
-    // ---- 2a (own finishing paths) then 2b (listed paths, dense) through ONE copy of the path code ----
+    // ---- 2a (own finishing paths; own shaded paths -> stash) then 2b (listed paths, dense) through ONE copy of the path code ----
     uint32_t n_shade = 0, gbase = 0;
     for (uint32_t jt = 0;; ++jt) {
-      uint32_t i = 0, k_out = 0;
-      bool active = false;
+      uint32_t i = 0, k_out = 0, tsh = 0;
+      bool active = false, fill = false, parked = false;
       if (jt < u_eff) {
         i = base + jt * WF_LOGIC_THREADS + threadIdx.x;
         active = (own_fin >> jt) & 1u;
+        if (cap) { // (kernel-uniform) a shaded path's place in the list, as pass 1 counted it
+          const bool sh = (own_fin >> (16u + jt)) & 1u;
+          tsh = (uint32_t)s_wb[jt * NW + (uint32_t)wave] + lane_rank(__ballot(sh));
+          fill = sh && tsh < cap;
+        }
       } else {
         if (jt == u_eff) {
           if (threadIdx.x == 0) s_gbase = my_gbase;
-          __syncthreads();
+          __syncthreads(); // (publishes the stash too)
           n_shade = s_total;
           gbase = s_gbase;
           if (tickets) it_next = __builtin_amdgcn_readfirstlane(s_next);
         }
-        const uint32_t tsh = (jt - u_eff) * WF_LOGIC_THREADS + threadIdx.x;
+        tsh = (jt - u_eff) * WF_LOGIC_THREADS + threadIdx.x;
         if ((jt - u_eff) * WF_LOGIC_THREADS >= n_shade) break; // block-uniform
         active = tsh < n_shade;
+        parked = active && tsh < cap; // (beyond the stash: from memory, as the finishing paths)
         if (active) { i = base + s_list[tsh]; k_out = gbase + tsh; }
       }
-      if (active) {
-        Path ps;
-        int hitA;
-        const uint32_t slot = load_path<SMP, LIGHTS>(in, i, ps, p.shadow_hit, hitA);
-        const float2 h = ld2(p.hit + i);
-        const uint32_t j = slot % p.n_batch;
-        const bool finished = advance_path<COUNT, SMP, LIGHTS>(S, ps, hitA, h.x, __float_as_int(h.y), s_rb[j], p.smp_seed, p.first_tick + j,
-                                                               p.env_theta, p.num_bounces, cnt, p.light_q);
-        if (finished) st3(p.fin + 3 * (size_t)slot, ps.color);
-        else store_path<SMP, LIGHTS>(out, k_out, ps, slot);
+      if (active || fill) {
+        PathRows r;
+        float2 h;
+        if (parked) {
+          r.a = stash[tsh]; r.b = stash[cap + tsh]; r.c = stash[2u * cap + tsh];
+          const float4 hh = stash[5u * cap + tsh];
+          h = make_float2(hh.x, hh.y);
+          r.sh = __float_as_int(hh.z);
+          r.d = r.pe = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+          if (rows_have_nee(__float_as_uint(r.b.w), LIGHTS)) { r.d = stash[3u * cap + tsh]; r.pe = stash[4u * cap + tsh]; }
+        } else {
+          load_rows<LIGHTS>(in, i, p.shadow_hit, r);
+          h = ld2(p.hit + i);
+        }
+        if (fill) {
+          stash[tsh] = r.a; stash[cap + tsh] = r.b; stash[2u * cap + tsh] = r.c;
+          stash[5u * cap + tsh] = make_float4(h.x, h.y, __int_as_float(r.sh), 0.0f);
+          if (rows_have_nee(__float_as_uint(r.b.w), LIGHTS)) { stash[3u * cap + tsh] = r.d; stash[4u * cap + tsh] = r.pe; }
+        } else {
+          Path ps;
+          int hitA;
+          const uint32_t slot = unpack_path<SMP, LIGHTS>(in, i, r, ps, hitA);
+          const uint32_t j = slot % p.n_batch;
+          const bool finished = advance_path<COUNT, SMP, LIGHTS>(S, ps, hitA, h.x, __float_as_int(h.y), s_rb[j], p.smp_seed, p.first_tick + j,
+                                                                 p.env_theta, p.num_bounces, cnt, p.light_q);
+          if (finished) st3(p.fin + 3 * (size_t)slot, ps.color);
+          else store_path<SMP, LIGHTS>(out, k_out, ps, slot);
+        }
       }
     }
-    __syncthreads(); // s_list / s_total are rewritten by the next iteration
+    __syncthreads(); // s_list / s_wb / s_total and the stash are rewritten by the next iteration
   }
   flush_counters<COUNT>(cnt, p.counters, 4, lane);
 }
@@ -1965,6 +2046,8 @@ size_t wf_max_stack_entries() {
   return (lds_cu - tables) / ((WF_PRIMARY_THREADS / WAVE) * WAVE * sizeof(int));
 }
 
+int g_logic_stash = -1; // fspt_logic_set_stash's: -1 = WF_LOGIC_STASH, 0 = none, n = at most n entries
+
 hipError_t launch_wf(int kernel, const WfP &p, int count, int num_cus, hipStream_t stream) {
   // the most paths / samples the launch can have to process (sizes the grid; the kernels read the real counts)
   uint32_t total = p.n_batch * p.work_total;
@@ -2053,10 +2136,18 @@ hipError_t launch_wf(int kernel, const WfP &p, int count, int num_cus, hipStream
         });
       });
     } else {
-      const size_t dyn = tab ? tab_bytes : 0u;
+      size_t dyn = tab ? tab_bytes : 0u;
+      // the stash takes what TWO resident blocks per CU leave of the CU's LDS next to the tables, the list and the static
+      // words (1 KiB covers those and the allocation granularity): it never costs a resident block
+      WfP q = p;
+      const size_t per_block = 160u * 1024u / 2u, fixed = (size_t)WF_LOGIC_U * WF_LOGIC_THREADS * sizeof(uint16_t) + 1024u + dyn;
+      uint32_t fit = per_block > fixed ? (uint32_t)((per_block - fixed) / WF_STASH_ENTRY_BYTES) : 0u;
+      if (fit > (uint32_t)WF_LOGIC_U * WF_LOGIC_THREADS) fit = (uint32_t)WF_LOGIC_U * WF_LOGIC_THREADS; // (a list is no longer)
+      q.stash = g_logic_stash < 0 ? min(fit, (uint32_t)WF_LOGIC_STASH) : min(fit, (uint32_t)g_logic_stash);
+      dyn += (size_t)q.stash * WF_STASH_ENTRY_BYTES;
       e = with_flag(count != 0, [&](auto C) {
         return with_flag(tab, [&](auto T) {
-          return with_shading(p, [&](auto M, auto L) { return launch(k_wf_logic<C, T, M, L>, dim3(grid), dim3(WF_LOGIC_THREADS), dyn, stream, p); });
+          return with_shading(p, [&](auto M, auto L) { return launch(k_wf_logic<C, T, M, L>, dim3(grid), dim3(WF_LOGIC_THREADS), dyn, stream, q); });
         });
       });
     }

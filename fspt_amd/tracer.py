@@ -280,6 +280,12 @@ def skin_set_form(form):
     L.check(L.lib().fspt_skin_set_form(int(form)))
 
 
+def logic_set_stash(entries):
+    """k_wf_logic's LDS stash of the shaded paths' rows, process-wide (fspt_logic_set_stash, a measurement switch): -1 = the
+    library's choice, 0 = none (every listed path is read from memory again), n = at most n entries.  The bits are the same."""
+    L.check(L.lib().fspt_logic_set_stash(int(entries)))
+
+
 def bloom_set_form(form):
     """The pyramid's form, process-wide (fspt_bloom_set_form, a measurement switch): 0 = one launch per level, 1 = the small
     levels in one workgroup (k_bloom_tail).  The bits are the same."""

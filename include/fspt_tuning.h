@@ -149,6 +149,12 @@ int fspt_intersect_form(fspt_scene *scene, int two_level, const float *rays, uin
  * a third batch is spent only when the first form lost by no more than its cold start explains; then the faster form
  * runs - form 1 on the 70 k-triangle scene, form 2 on the 1 M-triangle one. */
 int fspt_target_set_primary_form(fspt_target *target, int form);
+/* Measurement switch, process-wide: the logic launch (k_wf_logic) lists the paths it shades per block iteration and shades them
+ * in whole waves; the lanes that own those paths fetch their state rows beside the finishing paths' and park them in LDS, so
+ * that the shading pass does not fetch the same memory lines a second time.  entries: -1 = the library's choice (what two
+ * resident blocks per CU leave of the LDS), 0 = no stash (every listed path is read from memory again), n = at most n entries
+ * of 96 bytes; listed paths beyond the stash are read from memory.  FSPT_E_INVALID below -1.  The bits are the same. */
+int fspt_logic_set_stash(int entries);
 /* The form the next batch of `batch_ticks` ticks will use and what has been measured for that batch size so far
  * (best ms per sample of form 1, form 2; < 0: not measured yet).  Blocking (waits for a measurement in flight). */
 int fspt_target_get_primary_form(fspt_target *target, uint32_t batch_ticks, int *form, double ms_per_sample[2]);

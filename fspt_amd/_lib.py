@@ -99,6 +99,11 @@ class JpegParams(C.Structure):
     _fields_ = [("quality", C.c_uint32), ("subsampling", C.c_uint32), ("restart_mcus", C.c_uint32)]
 
 
+class PngParams(C.Structure):
+    """fspt_png_params: channels 3 = RGB / 4 = RGBA, filter 0..4 or 5 = adaptive, bytes of the filtered stream per deflate chunk (0 = FSPT_PNG_CHUNK)"""
+    _fields_ = [("channels", C.c_uint32), ("filter", C.c_uint32), ("chunk_bytes", C.c_uint32)]
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("target_rel_mse", C.c_double), ("max_ticks", C.c_uint32), ("min_ticks", C.c_uint32), ("round_ticks", C.c_uint32)]
 
@@ -340,6 +345,12 @@ SIGNATURES = {
     "fspt_jpeg_last_ms": (C.c_int, [_F, C.POINTER(C.c_uint64)]),
     "fspt_draw_jpeg": (C.c_int, [_VP, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.POINTER(JpegParams), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
     "fspt_present_jpeg": (C.c_int, [_VP, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.POINTER(JpegParams), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
+    "fspt_png_bound": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(PngParams), C.POINTER(C.c_size_t)]),
+    "fspt_png_encode": (C.c_int, [C.c_int, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(PngParams), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fspt_png_encode_device": (C.c_int, [C.c_int, _VP, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(PngParams), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fspt_png_filtered_eval": (C.c_int, [C.c_int, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(PngParams), C.POINTER(C.c_uint8)]),
+    "fspt_png_last_ms": (C.c_int, [_F, C.POINTER(C.c_uint64)]),
+    "fspt_draw_png": (C.c_int, [_VP, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.POINTER(PngParams), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
     "fspt_multi_last_stage_ms": (C.c_int, [_VP, _F, C.c_uint32]),
     "fspt_device_memory": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fspt_last_error": (C.c_char_p, []),

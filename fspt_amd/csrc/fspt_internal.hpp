@@ -17,6 +17,7 @@
 //   fspt_appearance.hip    in-place appearance update: the texture-set, atlas and environment layouts and the material part of the hit records
 //   fspt_sky.hip           the sky generator and the environment's importance bins, built on the GPU
 //   fspt_jpeg.hip          the baseline JPEG encoder behind fspt_jpeg_encode, fspt_draw_jpeg and fspt_present_jpeg, and its stand-alone entries
+//   fspt_png.hip           the PNG encoder behind fspt_png_encode and fspt_draw_png, and its stand-alone entries
 #pragma once
 #include "../../include/fspt.h"
 #include "../../include/fspt_tuning.h"
@@ -274,6 +275,38 @@ int jpeg_deliver(const uint8_t *dev, uint32_t n, uint8_t *out, size_t cap, size_
 int jpeg_collect(JpegEnc &e, int slot, hipStream_t st, uint8_t *out, size_t cap, size_t *bytes_out, const char *fn); // waits for st, then jpeg_deliver
 void jpeg_note_ms(JpegEnc &e);  // the stage times of a finished launch, for fspt_jpeg_last_ms
 void jpeg_release(JpegEnc &e);
+// fspt_png.hip: the PNG encoder, laid out as the JPEG one.  PngPlan: what follows from a size and checked
+// parameters, on the host.  PngEnc: the device memory of one encoder - the signature and IHDR of its plan, the filtered
+// stream, a scratch slot and a record (bytes, CRC-32, Adler pair) per chunk, one output buffer - owned by a target
+// (fspt_draw_png) or by one stand-alone call.
+static const uint32_t PNG_HEADER_BYTES = 33u; // signature and IHDR
+struct PngPlan {
+  uint32_t w, h, channels, filter, cb; // cb: the bytes of the filtered stream per chunk
+  uint32_t row_bytes, n_chunks;
+  size_t stream_bytes;
+  size_t slot_bytes; // a chunk's scratch slot
+  size_t bound;      // no file of this plan is longer
+};
+struct PngEnc {
+  PngPlan pl{};
+  bool valid = false;
+  uint8_t *cfg = nullptr;     // the header
+  uint8_t *stream = nullptr;  // stage one's output
+  uint8_t *scratch = nullptr; // n_chunks slots
+  uint32_t *meta = nullptr, *off = nullptr; // per chunk: 4 words | where its IDAT lands; off[n_chunks + 1] = the file's length
+  uint8_t *out = nullptr;
+  size_t out_bytes = 0;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the three stages of the last launch
+};
+int png_check_params(const fspt_png_params *prm, const char *fn); // the parameters alone (a target's entry: before the handle is looked at)
+int png_plan(const fspt_png_params *prm, uint32_t w, uint32_t h, bool for_device, const char *fn, PngPlan &pl); // validates: FSPT_E_INVALID, no device touched; for_device: the file must stay below 4 GiB
+size_t png_bound_max(uint32_t w, uint32_t h, uint32_t cb);                             // the largest bound of any parameters with chunks of cb
+hipError_t png_ensure(PngEnc &e, const PngPlan &pl, bool with_out, size_t out_bytes); // nothing of `e` may be in use
+hipError_t png_launch_filter(PngEnc &e, const uint32_t *rgba, int bottom_up, hipStream_t st);
+hipError_t png_launch(PngEnc &e, const uint32_t *rgba, int bottom_up, hipStream_t st); // no host read, no synchronisation
+int png_collect(PngEnc &e, hipStream_t st, uint8_t *out, size_t cap, size_t *bytes_out, const char *fn); // waits for st, then jpeg_deliver's rules
+void png_note_ms(PngEnc &e);  // the stage times of a finished launch, for fspt_png_last_ms
+void png_release(PngEnc &e);
 // fspt_pose.hip.  pose_run: s->pose set, s->rf.stage allocated, the call ordered against the targets;
 // mats_host = n_parts x 30 floats (a | D | N).  Uploads them, runs k_pose_transform into s->rf.stage and waits.
 int pose_run(fspt_scene *s, const float *mats_host);
@@ -526,7 +559,9 @@ struct fspt_target {
   // JPEG output (fspt_draw_jpeg / fspt_present_jpeg): allocated on first use.  Under present a slot holds either
   // fspt_present's RGBA8 frame (pr_host) or fspt_present_jpeg's file (jp.out[slot], its length in jp_count[slot])
   fspt::JpegEnc jp;
-  uint32_t *jp_frame = nullptr;               // fspt_draw_jpeg's drawn frame, W*H texels
+  uint32_t *jp_frame = nullptr;               // fspt_draw_jpeg's and fspt_draw_png's drawn frame, W*H texels
+  fspt::PngEnc pg;                            // PNG output (fspt_draw_png): allocated on first use
+  uint32_t pg_cb = 0;                         // the smallest chunk size fspt_draw_png was asked for: pg.out is sized for it
   uint32_t *jp_count[2] = {nullptr, nullptr}; // pinned host memory: a slot's byte count, current behind pr_copied[slot]
   int pr_kind[2] = {0, 0};                    // 0: an RGBA8 frame, 1: a JPEG file
   hipStream_t jp_copy = nullptr;              // a present file's bytes come to the host here: the copy waits for no stream that holds the next frame

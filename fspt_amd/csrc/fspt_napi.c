@@ -1033,6 +1033,67 @@ static napi_value PresentJpeg(napi_env env, napi_callback_info info) {
   NAPI_OK(napi_set_element(env, r, 1, v));
   return r;
 }
+/* PNG output (include/fspt.h fspt_png_* / fspt_draw_png): as the JPEG entries above - the file goes into a
+ * Uint8Array the JS host keeps, the answer is the bytes written or -(bytes needed). */
+static int png_args(napi_env env, const napi_value *a, fspt_png_params *p) { /* channels, filter, chunkBytes */
+  double c, f, b;
+  if (get_f64(env, a[0], &c) || get_f64(env, a[1], &f) || get_f64(env, a[2], &b)) return -1;
+  if (!(c >= 0.0 && c <= 4294967295.0 && f >= 0.0 && f <= 4294967295.0 && b >= 0.0 && b <= 4294967295.0)) {
+    napi_throw_range_error(env, NULL, "fspt_napi: PNG parameters must be non-negative integers");
+    return -1;
+  }
+  p->channels = (uint32_t)c; p->filter = (uint32_t)f; p->chunk_bytes = (uint32_t)b;
+  return 0;
+}
+static napi_value PngBound(napi_env env, napi_callback_info info) {
+  /* pngBound(width, height, channels, filter, chunkBytes) -> bytes no file exceeds */
+  napi_value a[5], r; double w, h; fspt_png_params p; size_t n = 0;
+  if (get_args(env, info, 5, a) || get_f64(env, a[0], &w) || get_f64(env, a[1], &h) || png_args(env, a + 2, &p)) return NULL;
+  FSPT_OK_OR_THROW(fspt_png_bound(w >= 0.0 && w <= 4294967295.0 ? (uint32_t)w : 0u, h >= 0.0 && h <= 4294967295.0 ? (uint32_t)h : 0u, &p, &n));
+  NAPI_OK(napi_create_double(env, (double)n, &r));
+  return r;
+}
+static int png_image_args(napi_env env, const napi_value *a, const char *fn, double *dev, void **src, uint32_t *w, uint32_t *h, bool *up, fspt_png_params *p) {
+  /* device, Uint8Array(w*h*4), width, height, bottomUp, channels, filter, chunkBytes */
+  size_t ns; double dw, dh; char msg[96];
+  if (get_f64(env, a[0], dev) || typed(env, a[1], napi_uint8_array, 0, src, &ns) || get_f64(env, a[2], &dw) || get_f64(env, a[3], &dh)) return -1;
+  if (napi_get_value_bool(env, a[4], up) != napi_ok || png_args(env, a + 5, p)) return -1;
+  if (!(dw >= 1.0 && dw <= 65535.0 && dh >= 1.0 && dh <= 65535.0) || (double)ns != dw * dh * 4.0) {
+    snprintf(msg, sizeof msg, "%s: need width*height*4 bytes, width and height in 1..65535", fn);
+    napi_throw_range_error(env, NULL, msg);
+    return -1;
+  }
+  *w = (uint32_t)dw; *h = (uint32_t)dh;
+  return 0;
+}
+static napi_value PngEncode(napi_env env, napi_callback_info info) {
+  /* pngEncode(device, Uint8Array(w*h*4), width, height, bottomUp, channels, filter, chunkBytes, Uint8Array out) */
+  napi_value a[9]; void *src, *dst; size_t nd, bytes = 0; double dev; uint32_t w, h; bool up; fspt_png_params p;
+  if (get_args(env, info, 9, a) || png_image_args(env, a, "pngEncode", &dev, &src, &w, &h, &up, &p) || typed(env, a[8], napi_uint8_array, 0, &dst, &nd)) return NULL;
+  const int rc = fspt_png_encode((int)dev, (const uint8_t *)src, w, h, up ? 1 : 0, &p, (uint8_t *)dst, nd, &bytes);
+  return jpeg_answer(env, rc, nd, bytes);
+}
+static napi_value PngFilteredEval(napi_env env, napi_callback_info info) {
+  /* pngFilteredEval(device, Uint8Array(w*h*4), width, height, bottomUp, channels, filter, chunkBytes, Uint8Array(h * (1 + w * channels)) out) */
+  napi_value a[9]; void *src, *dst; size_t nd; double dev; uint32_t w, h; bool up; fspt_png_params p;
+  if (get_args(env, info, 9, a) || png_image_args(env, a, "pngFilteredEval", &dev, &src, &w, &h, &up, &p) || typed(env, a[8], napi_uint8_array, 0, &dst, &nd)) return NULL;
+  if ((p.channels != 3u && p.channels != 4u) || nd != (size_t)h * (1u + (size_t)w * p.channels)) {
+    napi_throw_range_error(env, NULL, "pngFilteredEval: need channels 3 or 4 and an output of height * (1 + width * channels) bytes");
+    return NULL;
+  }
+  FSPT_OK_OR_THROW(fspt_png_filtered_eval((int)dev, (const uint8_t *)src, w, h, up ? 1 : 0, &p, (uint8_t *)dst));
+  return NULL;
+}
+static napi_value DrawPng(napi_env env, napi_callback_info info) {
+  /* drawPng(target, source, exposure, saturation, denoise, maxSigma, scale, channels, filter, chunkBytes, Uint8Array out) */
+  napi_value a[11]; void *h, *dst; size_t nd, bytes = 0; double src, ex, sat, sig, scale; bool den; fspt_png_params p;
+  if (get_args(env, info, 11, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  if (get_f64(env, a[1], &src) || get_f64(env, a[2], &ex) || get_f64(env, a[3], &sat)) return NULL;
+  NAPI_OK(napi_get_value_bool(env, a[4], &den));
+  if (get_f64(env, a[5], &sig) || get_f64(env, a[6], &scale) || png_args(env, a + 7, &p) || typed(env, a[10], napi_uint8_array, 0, &dst, &nd)) return NULL;
+  const int rc = fspt_draw_png((fspt_target *)h, (int)src, (float)ex, (float)sat, den ? 1 : 0, (float)sig, (float)scale, &p, (uint8_t *)dst, nd, &bytes);
+  return jpeg_answer(env, rc, nd, bytes);
+}
 /* guided denoiser (include/fspt.h fspt_features / fspt_denoise / fspt_draw_denoised) */
 static napi_value Features(napi_env env, napi_callback_info info) {
   /* features(target, params (as render), samples, seed) */
@@ -1702,7 +1763,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
       {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"sceneUpdateSky", SceneUpdateSky}, {"sceneUpdateEnvironmentAuto", SceneUpdateEnvironmentAuto}, {"skyGenerate", SkyGenerate}, {"atlasPackGpu", AtlasPackGpu}, {"sceneUpdateTextures", SceneUpdateTextures}, {"scenePatchTextures", ScenePatchTextures}, {"envBinsGpu", EnvBinsGpu}, {"sceneSetPose", SceneSetPose}, {"sceneUpdateTransforms", SceneUpdateTransforms}, {"sceneSetSkin", SceneSetSkin}, {"sceneUpdateSkin", SceneUpdateSkin}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
-      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"jpegBound", JpegBound}, {"jpegEncode", JpegEncode}, {"drawJpeg", DrawJpeg}, {"presentJpeg", PresentJpeg}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setCameraModel", SetCameraModel}, {"cameraModel", CameraModel}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
+      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"jpegBound", JpegBound}, {"jpegEncode", JpegEncode}, {"drawJpeg", DrawJpeg}, {"presentJpeg", PresentJpeg}, {"pngBound", PngBound}, {"pngEncode", PngEncode}, {"pngFilteredEval", PngFilteredEval}, {"drawPng", DrawPng}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setCameraModel", SetCameraModel}, {"cameraModel", CameraModel}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},
       {"renderAsync", RenderAsync}, {"multiCreate", MultiCreate}, {"multiDestroy", MultiDestroy}, {"multiTarget", MultiTarget},
       {"multiCamera", MultiCamera}, {"multiTrace", MultiTrace}, {"multiRender", MultiRender}, {"multiRenderAsync", MultiRenderAsync},

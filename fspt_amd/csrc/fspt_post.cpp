@@ -840,6 +840,21 @@ int fspt_bloom_eval(int device, const float *rgba, uint32_t W, uint32_t H, uint3
 // ---------------------------------------------------------------------------
 // JPEG output (fspt_jpeg.hip)
 // ---------------------------------------------------------------------------
+// fspt_draw_jpeg's and fspt_draw_png's frame: that of the entry the source stands for, refused as that entry refuses it
+static int encoded_source(fspt_target *t, int source, const float4 *&src, int &denoise, float &max_sigma, float &scale) {
+  src = t->accum;
+  if (source == FSPT_SOURCE_DENOISED) {
+    if (!t->dn_valid) { fspt_set_error("fspt_draw_denoised: no fspt_denoise call yet"); return FSPT_E_STATE; }
+    src = t->dn_out;
+  } else if (source != FSPT_SOURCE_ACCUMULATOR) {
+    if (!t->tm_valid) { fspt_set_error("fspt_temporal_draw: no fspt_temporal_accumulate call yet"); return FSPT_E_STATE; }
+    if (source == FSPT_SOURCE_TEMPORAL_DENOISED && !t->tm_dn_valid) { fspt_set_error("fspt_temporal_draw: no fspt_temporal_denoise call since the last fspt_temporal_accumulate / fspt_denoise"); return FSPT_E_STATE; }
+    src = source == FSPT_SOURCE_TEMPORAL_DENOISED ? t->dn_out : t->tm_hist[t->tm_cur];
+  }
+  if (source != FSPT_SOURCE_ACCUMULATOR) { denoise = 0; max_sigma = 0.0f; scale = 1.0f; }
+  return FSPT_OK;
+}
+
 int fspt_draw_jpeg(fspt_target *t, int source, float exposure, float saturation, int denoise, float max_sigma, float scale,
                    const fspt_jpeg_params *p, uint8_t *out, size_t cap, size_t *bytes_out) {
   const char *fn = "fspt_draw_jpeg";
@@ -851,23 +866,40 @@ int fspt_draw_jpeg(fspt_target *t, int source, float exposure, float saturation,
   if ((rc = dn_enter(t, true, fn))) return rc; // (joins a present: nothing of t->jp is in use behind it)
   fspt::JpegPlan pl;
   if ((rc = fspt::jpeg_plan(p, t->W, t->H, fn, pl))) return rc;
-  // the frame of the entry the source stands for, refused as that entry refuses it
-  const float4 *src = t->accum;
-  if (source == FSPT_SOURCE_DENOISED) {
-    if (!t->dn_valid) { fspt_set_error("fspt_draw_denoised: no fspt_denoise call yet"); return FSPT_E_STATE; }
-    src = t->dn_out;
-  } else if (source != FSPT_SOURCE_ACCUMULATOR) {
-    if (!t->tm_valid) { fspt_set_error("fspt_temporal_draw: no fspt_temporal_accumulate call yet"); return FSPT_E_STATE; }
-    if (source == FSPT_SOURCE_TEMPORAL_DENOISED && !t->tm_dn_valid) { fspt_set_error("fspt_temporal_draw: no fspt_temporal_denoise call since the last fspt_temporal_accumulate / fspt_denoise"); return FSPT_E_STATE; }
-    src = source == FSPT_SOURCE_TEMPORAL_DENOISED ? t->dn_out : t->tm_hist[t->tm_cur];
-  }
-  if (source != FSPT_SOURCE_ACCUMULATOR) { denoise = 0; max_sigma = 0.0f; scale = 1.0f; }
+  const float4 *src = nullptr;
+  if ((rc = encoded_source(t, source, src, denoise, max_sigma, scale))) return rc;
   if (!t->jp_frame) HIP_TRY(hipMalloc((void **)&t->jp_frame, (size_t)t->W * t->H * 4));
   hipError_t e = fspt::jpeg_ensure(t->jp, pl, 1, fspt::jpeg_bound_max(t->W, t->H));
   if (e == hipSuccess) e = draw_launch(t, src, exposure, saturation, denoise, max_sigma, scale, t->jp_frame, t->stream);
   if (e == hipSuccess) e = fspt::jpeg_launch(t->jp, t->jp_frame, 1, 0, t->stream);
   if (e != hipSuccess) return hip_fail(fn, e);
   return fspt::jpeg_collect(t->jp, 0, t->stream, out, cap, bytes_out, fn);
+}
+
+// ---------------------------------------------------------------------------
+// PNG output (fspt_png.hip)
+// ---------------------------------------------------------------------------
+int fspt_draw_png(fspt_target *t, int source, float exposure, float saturation, int denoise, float max_sigma, float scale,
+                  const fspt_png_params *p, uint8_t *out, size_t cap, size_t *bytes_out) {
+  const char *fn = "fspt_draw_png";
+  if (!t || !out || !bytes_out) { fspt_set_error("%s: NULL argument", fn); return FSPT_E_INVALID; }
+  if (source < FSPT_SOURCE_ACCUMULATOR || source > FSPT_SOURCE_TEMPORAL_DENOISED) { fspt_set_error("%s: unknown source %d", fn, source); return FSPT_E_INVALID; }
+  int rc = fspt::png_check_params(p, fn);
+  if (rc) return rc;
+  if (source == FSPT_SOURCE_ACCUMULATOR && !(scale > 0.0f && scale <= 1.0f)) { fspt_set_error("%s: scale must be in (0, 1]", fn); return FSPT_E_INVALID; }
+  if ((rc = dn_enter(t, true, fn))) return rc;
+  fspt::PngPlan pl;
+  if ((rc = fspt::png_plan(p, t->W, t->H, true, fn, pl))) return rc;
+  const float4 *src = nullptr;
+  if ((rc = encoded_source(t, source, src, denoise, max_sigma, scale))) return rc;
+  if (!t->jp_frame) HIP_TRY(hipMalloc((void **)&t->jp_frame, (size_t)t->W * t->H * 4));
+  // the output buffer: the bound of RGBA at the smallest chunk size asked for so far; it grows, and outlives a change of the parameters
+  t->pg_cb = t->pg_cb ? std::min(t->pg_cb, pl.cb) : pl.cb;
+  hipError_t e = fspt::png_ensure(t->pg, pl, true, fspt::png_bound_max(t->W, t->H, t->pg_cb));
+  if (e == hipSuccess) e = draw_launch(t, src, exposure, saturation, denoise, max_sigma, scale, t->jp_frame, t->stream);
+  if (e == hipSuccess) e = fspt::png_launch(t->pg, t->jp_frame, 1, t->stream);
+  if (e != hipSuccess) return hip_fail(fn, e);
+  return fspt::png_collect(t->pg, t->stream, out, cap, bytes_out, fn);
 }
 
 } // extern "C"
@@ -877,7 +909,7 @@ void post_release(fspt_target *t) {
   hipFree(t->feat); hipFree(t->dn_tmp[0]); hipFree(t->dn_tmp[1]); hipFree(t->dn_out);
   hipFree(t->tm_hist[0]); hipFree(t->tm_hist[1]); hipFree(t->tm_g[0]); hipFree(t->tm_g[1]); hipFree(t->tm_m);
   sv_free(t); cl_free(t); ax_free(t); bl_free(t);
-  fspt::jpeg_release(t->jp); hipFree(t->jp_frame);
+  fspt::jpeg_release(t->jp); fspt::png_release(t->pg); hipFree(t->jp_frame);
   for (uint32_t *c : t->jp_count) if (c) hipHostFree(c);
   if (t->jp_copy) hipStreamDestroy(t->jp_copy);
   for (hipEvent_t ev : t->tm_ev) if (ev) hipEventDestroy(ev);

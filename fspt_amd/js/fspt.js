@@ -352,6 +352,36 @@ function skyArgs(fn, o) {
   const params = Float32Array.of(p.sunDir[0], p.sunDir[1], p.sunDir[2], p.turbidity, p.sunIntensity, p.sunRadius, p.gain, alb[0], alb[1], alb[2]);
   return { params, viewSamples: p.viewSamples, lightSamples: p.lightSamples, width: p.width, height: p.height };
 }
+const PNG_FILTERS = { none: 0, sub: 1, up: 2, average: 3, paeth: 4, adaptive: 5 };
+/** {channels (3 | 4), filter (a name of PNG_FILTERS, 'adaptive'), chunkBytes (0 = the library's default)} -> the addon's three numbers */
+function pngArgs(o, fn) {
+  const ch = o.channels === undefined ? 3 : o.channels, f = PNG_FILTERS[o.filter === undefined ? 'adaptive' : String(o.filter)];
+  const cb = o.chunkBytes === undefined ? 0 : o.chunkBytes;
+  if (ch !== 3 && ch !== 4) throw new RangeError(fn + ': channels must be 3 or 4');
+  if (f === undefined) throw new RangeError(fn + ": filter must be 'none', 'sub', 'up', 'average', 'paeth' or 'adaptive'");
+  if (!Number.isInteger(cb) || (cb !== 0 && (cb < 256 || cb > 32768))) throw new RangeError(fn + ': chunkBytes must be 0 or an integer in 256..32768');
+  return [ch, f, cb];
+}
+/** An RGBA8 image (Uint8Array of width*height*4; bottomUp: row 0 is the bottom, as drawQuad returns it) as a lossless PNG file,
+ *  filtered and deflated on the GPU (include/fspt.h fspt_png_encode, DESIGN.md 8.20) -> Buffer.
+ *  opts: {channels (3 = RGB, 4 = RGBA), filter ('adaptive'), chunkBytes (0), bottomUp (false), device (0)}. */
+function pngEncode(rgba, width, height, opts) {
+  const o = opts || {}, enc = pngArgs(o, 'pngEncode');
+  if (!(rgba instanceof Uint8Array) || rgba.length !== width * height * 4) throw new RangeError('pngEncode: need a Uint8Array of width*height*4 bytes');
+  let out = new Uint8Array(width * height * 4 + 1024);
+  let n = addon.pngEncode(o.device || 0, rgba, width, height, !!o.bottomUp, ...enc, out);
+  if (n < 0) { out = new Uint8Array(Math.max(-n, addon.pngBound(width, height, ...enc))); n = addon.pngEncode(o.device || 0, rgba, width, height, !!o.bottomUp, ...enc, out); }
+  if (n < 0) throw new Error('pngEncode: the file outgrew the bound');
+  return Buffer.from(out.subarray(0, n));
+}
+/** stage one of pngEncode alone (fspt_png_filtered_eval): the filtered stream, height rows of 1 + width * channels bytes */
+function pngFilteredEval(rgba, width, height, opts) {
+  const o = opts || {}, enc = pngArgs(o, 'pngFilteredEval');
+  if (!(rgba instanceof Uint8Array) || rgba.length !== width * height * 4) throw new RangeError('pngFilteredEval: need a Uint8Array of width*height*4 bytes');
+  const out = new Uint8Array(height * (1 + width * enc[0]));
+  addon.pngFilteredEval(o.device || 0, rgba, width, height, !!o.bottomUp, ...enc, out);
+  return out;
+}
 const JPEG_SUBSAMPLING = { '444': 0, '420': 1 };
 const JPEG_SOURCES = { accumulator: 0, denoised: 1, temporal: 2, temporalDenoised: 3 };
 /** An RGBA8 image (Uint8Array of width*height*4, alpha ignored; bottomUp: row 0 is the bottom, as drawQuad returns it) as a
@@ -540,6 +570,24 @@ class PathTracer {
     if (n < 0) { this._jpegGrow(-n, a.enc); n = addon.drawJpeg(this._target, src, ...a.draw, ...a.enc, this._jpegBuf); }
     if (n < 0) throw new Error('drawJpeg: the file outgrew the bound');
     return Buffer.from(this._jpegBuf.subarray(0, n));
+  }
+  /** drawJpeg's lossless sibling (include/fspt.h fspt_draw_png, DESIGN.md 8.20): the frame is drawn, filtered and deflated on the
+   *  GPU and only the PNG file crosses the bus -> Buffer.  opts: drawJpeg's source and draw settings, pngEncode's channels / filter /
+   *  chunkBytes.  Its own reusable buffer, grown to the library's bound when a file needs more. */
+  drawPng(opts) {
+    const o = opts || {}, enc = pngArgs(o, 'drawPng');
+    const src = JPEG_SOURCES[o.source === undefined ? 'accumulator' : o.source];
+    if (src === undefined) throw new RangeError("drawPng: source must be 'accumulator', 'denoised', 'temporal' or 'temporalDenoised'");
+    const draw = [o.exposure === undefined ? 1 : o.exposure, o.saturation === undefined ? 1 : o.saturation, !!o.denoise,
+      o.maxSigma === undefined ? 3 : o.maxSigma, o.scale === undefined ? 1 : o.scale];
+    if (!this._pngBuf) this._pngBuf = new Uint8Array(this.resolution[0] * this.resolution[1] * 4 + 1024);
+    let n = addon.drawPng(this._target, src, ...draw, ...enc, this._pngBuf);
+    if (n < 0) {
+      this._pngBuf = new Uint8Array(Math.max(-n, addon.pngBound(this.resolution[0], this.resolution[1], ...enc)));
+      n = addon.drawPng(this._target, src, ...draw, ...enc, this._pngBuf);
+    }
+    if (n < 0) throw new Error('drawPng: the file outgrew the bound');
+    return Buffer.from(this._pngBuf.subarray(0, n));
   }
   presentJpeg(opts) {
     const a = this._jpegArgs(opts, 'presentJpeg');
@@ -936,5 +984,5 @@ class MultiPathTracer {
 // memory later scenes may spend on interleaved material textures (fspt_set_texture_interleave_budget; results do not depend on it)
 function setTextureInterleaveBudget(bytes) { addon.setTextureInterleaveBudget(bytes); }
 
-module.exports = { addon, setTextureInterleaveBudget, jpegEncode, skyGenerate, envBinsGpu, atlasPackGpu, SKY_DEFAULTS, MultiPathTracer, AtlasLayers, resolveMaterial, readMtl, mergeSceneProps, resampleImage, packReferenceScene, buildScene,
+module.exports = { addon, setTextureInterleaveBudget, jpegEncode, pngEncode, pngFilteredEval, skyGenerate, envBinsGpu, atlasPackGpu, SKY_DEFAULTS, MultiPathTracer, AtlasLayers, resolveMaterial, readMtl, mergeSceneProps, resampleImage, packReferenceScene, buildScene,
   PathTracer, saveBlob, loadBlob };

@@ -209,6 +209,11 @@ function renderToPng(scenePath, outPath, width, height, opts) {
     fs.writeFileSync(outPath, F.jpegEncode(fr.rgba, width, height, Object.assign({ device: opts && opts.device }, opts && opts.jpeg)));
     return fr;
   }
+  if (opts && opts.pngGpu) { // a PNG filtered and deflated on the GPU (fspt.js pngEncode, DESIGN.md 8.20); opts.png: {channels, filter, chunkBytes}
+    fs.mkdirSync(path.dirname(path.resolve(outPath)), { recursive: true });
+    fs.writeFileSync(outPath, F.pngEncode(fr.rgba, width, height, Object.assign({ device: opts.device }, opts.png)));
+    return fr;
+  }
   const rgb = new Uint8Array(width * height * 3);
   for (let i = 0, j = 0; i < fr.rgba.length; i += 4, j += 3) { rgb[j] = fr.rgba[i]; rgb[j + 1] = fr.rgba[i + 1]; rgb[j + 2] = fr.rgba[i + 2]; }
   fs.mkdirSync(path.dirname(path.resolve(outPath)), { recursive: true });
@@ -232,13 +237,14 @@ function renderSequence(scenePattern, frames, outPattern, width, height, opts) {
 module.exports = { decodePng, encodePng, decodeJpeg, mtllibUrls, loadSceneFile, renderFrame, renderToPng, renderSequence };
 
 // node fspt_amd/js/scene_file.js scene/bunny.json out.png [--width W] [--height H] [--samples N] [--bounces B] [--seed S]
-//                                [--asset-root DIR] [--denoise] [--frames A:B] [--bvh sah|gpu] [--auto-exposure [KEY]] [--bloom [INTENSITY]]   (mirrors `python -m fspt_amd.render`;
+//                                [--asset-root DIR] [--denoise] [--frames A:B] [--bvh sah|gpu] [--auto-exposure [KEY]] [--bloom [INTENSITY]] [--png-gpu]   (mirrors `python -m fspt_amd.render`;
 //                                with --frames both paths contain {frame}: the reference's ?frame=N loop)
 if (require.main === module) {
   const argv = process.argv.slice(2), pos = [], o = { width: 960, height: 540 };
   for (let i = 0; i < argv.length; i++) {
     const a = argv[i];
     if (a === '--denoise') o.denoise = true;
+    else if (a === '--png-gpu') o.pngGpu = true;
     else if (a === '--auto-exposure') {  // (KEY is optional: the next word is taken only if it is a number)
       if (i + 1 < argv.length && argv[i + 1] !== '' && Number.isFinite(Number(argv[i + 1]))) {
         const key = Number(argv[++i]);
@@ -256,10 +262,10 @@ if (require.main === module) {
     else if (a.startsWith('--')) o[a.slice(2).replace(/-([a-z])/g, (m, c) => c.toUpperCase())] = argv[++i];
     else pos.push(a);
   }
-  if (pos.length !== 2) { console.error('usage: node scene_file.js <scene.json> <out.png> [--width W] [--height H] [--samples N] [--bounces B] [--seed S] [--asset-root DIR] [--denoise] [--frames A:B] [--bvh sah|gpu] [--auto-exposure [KEY]] [--bloom [INTENSITY]]'); process.exit(2); }
+  if (pos.length !== 2) { console.error('usage: node scene_file.js <scene.json> <out.png> [--width W] [--height H] [--samples N] [--bounces B] [--seed S] [--asset-root DIR] [--denoise] [--frames A:B] [--bvh sah|gpu] [--auto-exposure [KEY]] [--bloom [INTENSITY]] [--png-gpu]'); process.exit(2); }
   const num = (k) => (o[k] === undefined ? undefined : Number(o[k]));
   const t0 = Date.now();
-  const ro = { samples: num('samples'), bounces: num('bounces'), seed: num('seed'), assetRoot: o.assetRoot, denoise: !!o.denoise, bvh: o.bvh, autoExposure: o.autoExposure, bloom: o.bloom };
+  const ro = { samples: num('samples'), bounces: num('bounces'), seed: num('seed'), assetRoot: o.assetRoot, denoise: !!o.denoise, bvh: o.bvh, autoExposure: o.autoExposure, bloom: o.bloom, pngGpu: !!o.pngGpu };
   if (o.frames) {
     const [a, b] = String(o.frames).split(':').map(Number), frames = [];
     for (let n = a; n < b; n++) frames.push(n);

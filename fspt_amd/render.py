@@ -11,6 +11,7 @@ reference's format (scene/<name>.json with props / static_props / animated_props
     python -m fspt_amd.render --scene 'web/scene/anim_{frame}.json' --frames 0:24 --bvh refit --out 'out/{frame}.png'  # build once, refit
     python -m fspt_amd.render --scene 'web/scene/anim_{frame}.json' --frames 0:24 --bvh refit --pose --out 'out/{frame}.png'  # one matrix per prop per frame
     python -m fspt_amd.render --out bunny.jpg --jpeg-quality 90 --jpeg-444   # drawn and JPEG-encoded on the GPU
+    python -m fspt_amd.render --out bunny.png --png-gpu                      # drawn, filtered and deflated on the GPU
     python -m fspt_amd.render --out pano.png --width 1024 --height 512 --camera equirect  # 360-degree panorama (also: ortho, fisheye:180, stereo:0.064)
 
 Path tracing runs in the HIP kernels (fspt_render), tone mapping in the draw.fs kernel (fspt_draw); --atrous K runs
@@ -86,6 +87,7 @@ def main(argv=None):
     ap.add_argument("--out", default="fspt.png")
     ap.add_argument("--jpeg-quality", type=int, default=85, metavar="Q", help="--out *.jpg / *.jpeg: libjpeg quality 1..100 (encoded on the GPU, DESIGN 8.19)")
     ap.add_argument("--jpeg-444", action="store_true", help="--out *.jpg / *.jpeg: no chroma subsampling (default 4:2:0)")
+    ap.add_argument("--png-gpu", action="store_true", help="--out *.png: filter and deflate the file on the GPU (DESIGN 8.20; the default is Pillow on the host)")
     ap.add_argument("--width", type=int, default=960)
     ap.add_argument("--height", type=int, default=540)
     ap.add_argument("--spp", type=int, default=256)
@@ -154,6 +156,9 @@ def main(argv=None):
     jpeg = dict(quality=args.jpeg_quality, subsampling="444" if args.jpeg_444 else "420")
     if (args.jpeg_quality != 85 or args.jpeg_444) and not is_jpeg_path(args.out):
         ap.error("--jpeg-quality and --jpeg-444 need an --out that ends in .jpg or .jpeg")
+    if args.png_gpu and not args.out.lower().endswith(".png"):
+        ap.error("--png-gpu needs an --out that ends in .png")
+    png = "gpu" if args.png_gpu else None
     if args.sky_to is not None and not (args.sky and args.scene and args.frames):
         ap.error("--sky-to needs --sky, --scene and --frames")
     try:
@@ -224,7 +229,7 @@ def main(argv=None):
                                     rebuild_above=args.rebuild_above,
                                     temporal=({"atrous": args.atrous, "clamp": None if args.temporal_clamp is None else True if args.temporal_clamp is True
                                                else {"sigma_scale": args.temporal_clamp}} if args.temporal else None),
-                                    variance=args.variance_guided, pose=args.pose, textures=args.textures, jpeg=jpeg, **kw)
+                                    variance=args.variance_guided, pose=args.pose, textures=args.textures, jpeg=jpeg, png=png, **kw)
             print(f"{len(out)} frames in {time.perf_counter() - t0:.2f} s:", *out)
         else:
             arrays, settings = F.load_scene_file(args.scene, args.assets, bvh=args.bvh, textures=args.textures)
@@ -234,7 +239,7 @@ def main(argv=None):
             rgba, rad = F.render_frame(arrays, settings, args.width, args.height, **kw)
             if args.hdr:
                 np.save(args.hdr, rad)
-            write_image(args.out, rgba, jpeg)
+            write_image(args.out, rgba, jpeg, png=png)
             print("wrote", args.out, f"({arrays.n_tris} triangles, {spp or settings['samples']} spp)")
         return
     t0 = time.perf_counter()
@@ -280,6 +285,8 @@ def main(argv=None):
         pt.denoise(iterations=args.atrous)
     if is_jpeg_path(args.out):  # drawn and encoded on the device: only the file comes back
         data = pt.draw_jpeg("denoised" if args.atrous > 0 else "accumulator", args.exposure, args.saturation, args.denoise, **jpeg)
+    elif args.png_gpu:
+        data = pt.draw_png("denoised" if args.atrous > 0 else "accumulator", args.exposure, args.saturation, args.denoise)
     elif args.atrous > 0:
         rgba = pt.drawDenoised(args.exposure, args.saturation)
     else:
@@ -287,7 +294,7 @@ def main(argv=None):
     print(f"{args.width}x{args.height} x {args.spp} spp in {dt:.3f} s = {samples / dt / 1e6:.0f} Msamples/s")
     if args.hdr:
         np.save(args.hdr, pt.readRadiance())
-    if is_jpeg_path(args.out):
+    if is_jpeg_path(args.out) or args.png_gpu:
         with open(args.out, "wb") as f:
             f.write(data)
     else:

@@ -199,13 +199,22 @@ def is_jpeg_path(path):
     return str(path).lower().endswith((".jpg", ".jpeg"))
 
 
-def write_image(path, rgba, jpeg=None, device=0):
+def write_image(path, rgba, jpeg=None, device=0, png=None):
     """An RGBA8 frame [H, W, 4], row 0 = top, as the picture `path` names: .jpg / .jpeg = a baseline JPEG encoded on the GPU
     (tracer.jpeg_encode; jpeg = None or a dict of its quality / subsampling / restart_mcus), anything else
-    through Pillow as before."""
+    through Pillow as before - unless png is "gpu" or a dict of tracer.png_encode's channels / filter / chunk_bytes: then the
+    PNG is filtered and deflated on the GPU."""
     if is_jpeg_path(path):
         from .tracer import jpeg_encode
         data = jpeg_encode(rgba, device=device, **(jpeg or {}))
+        with open(path, "wb") as f:
+            f.write(data)
+        return
+    if png is not None:
+        if png != "gpu" and not isinstance(png, dict):
+            raise ValueError(f'write_image: png must be None, "gpu" or a dict of png_encode\'s parameters, not {png!r}')
+        from .tracer import png_encode
+        data = png_encode(rgba, device=device, **({} if png == "gpu" else png))
         with open(path, "wb") as f:
             f.write(data)
         return
@@ -310,7 +319,7 @@ def _sequence_sky(sky, k, n):
 
 
 def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", rebuild_above=None,
-                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, camera=None, sky=None, textures="cpu", jpeg=None, **kw):
+                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, camera=None, sky=None, textures="cpu", jpeg=None, png=None, **kw):
     """frame=N sequencing (main.js:851-866, 966-969): for every N in `frames` load `scene_pattern.format(frame=N)`
     (the per-frame scene JSON the reference's server hands out for `?frame=N`), render it, write
     `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1.
@@ -358,7 +367,9 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     textures: "cpu" or "gpu" - where every frame's atlas is resampled.  With "gpu" and bvh="refit" a kept frame
     whose atlas changed sends its decoded images, not the atlas: Scene.update_textures packs them on the device.
     jpeg: an out_pattern that ends in .jpg / .jpeg is written as a JPEG encoded on the GPU (write_image); None
-    or a dict of jpeg_encode's quality / subsampling / restart_mcus."""
+    or a dict of jpeg_encode's quality / subsampling / restart_mcus.
+    png: None = every other out_pattern goes through Pillow; "gpu" or a dict of png_encode's channels / filter /
+    chunk_bytes = it is written as a PNG encoded on the GPU (write_image)."""
     if textures not in S.TEXTURE_PACKERS:
         raise ValueError(f"render_sequence: textures must be one of {S.TEXTURE_PACKERS}, not {textures!r}")
     camera = _camera_model_params(camera, kw.get("adaptive"), None if temporal is None or temporal is False else temporal)
@@ -395,7 +406,7 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     def save(n, rgba):
         out = out_pattern.format(frame=n)
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-        write_image(out, rgba, jpeg, device)
+        write_image(out, rgba, jpeg, device, png)
         written.append(out)
 
     if bvh != "refit":

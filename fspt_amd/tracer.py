@@ -316,10 +316,11 @@ def jpeg_bound(width, height, quality=85, subsampling="420", restart_mcus=0):
 
 
 class _JpegBuffer:
-    """The wrappers' reusable output buffer: W*H*4 + 1024 bytes, grown to fspt_jpeg_bound when a call reports a need"""
+    """The wrappers' reusable output buffer: W*H*4 + 1024 bytes, grown to fspt_jpeg_bound (the PNG wrappers': fspt_png_bound)
+    when a call reports a need"""
 
-    def __init__(self, width, height):
-        self.size = (int(width), int(height))
+    def __init__(self, width, height, bound="fspt_jpeg_bound"):
+        self.size, self.bound = (int(width), int(height)), bound
         self.buf = np.empty(self.size[0] * self.size[1] * 4 + 1024, np.uint8)
 
     def call(self, p, fn):
@@ -328,7 +329,7 @@ class _JpegBuffer:
         rc = fn(L.u8ptr(self.buf), self.buf.size, C.byref(n))
         if rc == -1 and n.value > self.buf.size:
             b = C.c_size_t()
-            L.check(L.lib().fspt_jpeg_bound(self.size[0], self.size[1], C.byref(p), C.byref(b)))
+            L.check(getattr(L.lib(), self.bound)(self.size[0], self.size[1], C.byref(p), C.byref(b)))
             self.buf = np.empty(max(int(b.value), int(n.value)), np.uint8)
             rc = fn(L.u8ptr(self.buf), self.buf.size, C.byref(n))
         L.check(rc)
@@ -383,6 +384,81 @@ def jpeg_last_ms():
     """((blocks ms, entropy ms, offsets + pack ms), bytes brought to the host) of the last jpeg_encode (fspt_jpeg_last_ms)"""
     ms, n = (C.c_float * 3)(), C.c_uint64()
     L.check(L.lib().fspt_jpeg_last_ms(ms, C.byref(n)))
+    return tuple(float(x) for x in ms), int(n.value)
+
+
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
+
+
+def png_params(channels=3, filter="adaptive", chunk_bytes=0):
+    """L.PngParams of the wrappers' keywords (fspt_png_params); filter: a name of PNG_FILTERS or its number.
+    The library checks the ranges."""
+    if int(channels) not in (3, 4):
+        raise ValueError("channels must be 3 or 4")
+    if filter not in PNG_FILTERS and filter not in PNG_FILTERS.values():
+        raise ValueError(f"filter must be one of {sorted(PNG_FILTERS)} or 0..5")
+    return L.PngParams(int(channels), PNG_FILTERS.get(filter, filter), int(chunk_bytes))
+
+
+def png_bound(width, height, channels=3, filter="adaptive", chunk_bytes=0):
+    """Bytes no PNG file of this size and these settings exceeds (fspt_png_bound; host only)"""
+    p, n = png_params(channels, filter, chunk_bytes), C.c_size_t()
+    L.check(L.lib().fspt_png_bound(int(width), int(height), C.byref(p), C.byref(n)))
+    return int(n.value)
+
+
+def _rgba8(image):
+    image = np.ascontiguousarray(image)
+    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 4:
+        raise ValueError("image must be a uint8 [H, W, 4] array")
+    return image
+
+
+_png_buffers = {}
+
+
+def png_encode(image, channels=3, filter="adaptive", chunk_bytes=0, bottom_up=False, device=0):
+    """A PNG file (bytes) of an RGBA8 image [H, W, 4], encoded on the GPU (fspt_png_encode): a numpy array, or
+    a torch tensor on the device, which is read where it is (fspt_png_encode_device).  channels 3 drops alpha, 4 keeps it
+    (straight); bottom_up: row 0 is the bottom, as draw() returns it."""
+    p = png_params(channels, filter, chunk_bytes)
+    on_dev = hasattr(image, "data_ptr") and getattr(image, "is_cuda", False)
+    if on_dev:
+        import torch
+        if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 4:
+            raise ValueError("image must be a uint8 [H, W, 4] tensor")
+        image = image.contiguous()
+        device = image.device.index or 0
+        torch.cuda.current_stream(device).synchronize()  # whatever wrote the tensor has finished
+    else:
+        image = _rgba8(image)
+    h, w = int(image.shape[0]), int(image.shape[1])
+    buf = _png_buffers.get((w, h))
+    if buf is None:
+        _png_buffers.clear()  # one reusable buffer: the last size's
+        buf = _png_buffers[(w, h)] = _JpegBuffer(w, h, "fspt_png_bound")
+    lib = L.lib()
+    if on_dev:
+        n = buf.call(p, lambda o, cap, nb: lib.fspt_png_encode_device(int(device), C.c_void_p(image.data_ptr()), w, h, 1 if bottom_up else 0, C.byref(p), o, cap, nb))
+    else:
+        n = buf.call(p, lambda o, cap, nb: lib.fspt_png_encode(int(device), L.u8ptr(image), w, h, 1 if bottom_up else 0, C.byref(p), o, cap, nb))
+    return buf.buf[:n].tobytes()
+
+
+def png_filtered_eval(image, channels=3, filter="adaptive", bottom_up=False, device=0):
+    """Stage one of the encoder alone (fspt_png_filtered_eval): the filtered stream, uint8 [H, 1 + W * channels]"""
+    p = png_params(channels, filter, 0)
+    image = _rgba8(image)
+    h, w = image.shape[:2]
+    out = np.zeros((h, 1 + w * p.channels), np.uint8)
+    L.check(L.lib().fspt_png_filtered_eval(int(device), L.u8ptr(image), w, h, 1 if bottom_up else 0, C.byref(p), L.u8ptr(out)))
+    return out
+
+
+def png_last_ms():
+    """((filter ms, deflate ms, offsets + pack ms), bytes brought to the host) of the last png_encode (fspt_png_last_ms)"""
+    ms, n = (C.c_float * 3)(), C.c_uint64()
+    L.check(L.lib().fspt_png_last_ms(ms, C.byref(n)))
     return tuple(float(x) for x in ms), int(n.value)
 
 
@@ -1394,6 +1470,20 @@ class PathTracer:
         p, buf, lib = jpeg_params(quality, subsampling, restart_mcus), self._jpeg_buffer(), L.lib()
         n = buf.call(p, lambda o, cap, nb: lib.fspt_draw_jpeg(self._t, JPEG_SOURCES[source], float(exposure), float(saturation), 1 if denoise else 0,
                                                               float(max_sigma), float(scale), C.byref(p), o, cap, nb))
+        return buf.buf[:n].tobytes()
+
+    def draw_png(self, source="accumulator", exposure=1.0, saturation=1.0, denoise=False, max_sigma=3.0, scale=1.0,
+                 channels=3, filter="adaptive", chunk_bytes=0):
+        """draw() ("accumulator"), draw_denoised() ("denoised") or temporal_draw() ("temporal", "temporal_denoised") of the
+        same arguments as a lossless PNG file (bytes), filtered and deflated on the GPU: only the file comes back
+        (fspt_draw_png)."""
+        if source not in JPEG_SOURCES:
+            raise ValueError(f"source must be one of {sorted(JPEG_SOURCES)}")
+        if getattr(self, "_png_buf", None) is None:
+            self._png_buf = _JpegBuffer(*self.resolution, "fspt_png_bound")
+        p, buf, lib = png_params(channels, filter, chunk_bytes), self._png_buf, L.lib()
+        n = buf.call(p, lambda o, cap, nb: lib.fspt_draw_png(self._t, JPEG_SOURCES[source], float(exposure), float(saturation), 1 if denoise else 0,
+                                                             float(max_sigma), float(scale), C.byref(p), o, cap, nb))
         return buf.buf[:n].tobytes()
 
     def present_jpeg(self, exposure=1.0, saturation=1.0, denoise=False, max_sigma=3.0, scale=1.0, quality=85, subsampling="420", restart_mcus=0):

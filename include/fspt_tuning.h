@@ -426,6 +426,14 @@ int fspt_light_alias_table(const float *weights, uint32_t n, float *prob, uint32
  * bytes it brought to the host. */
 int fspt_jpeg_coefficients_eval(int device, const uint8_t *rgba8, uint32_t w, uint32_t h, int bottom_up, const fspt_jpeg_params *p, int16_t *coef_out);
 int fspt_jpeg_last_ms(float ms[3], uint64_t *bus_bytes);
+/* PNG encoder.  FSPT_PNG_CHUNK: the bytes of the filtered stream one deflate chunk (one workgroup, one IDAT)
+ * takes when fspt_png_params.chunk_bytes is 0; 8.20 has the time and size tables it was chosen from.
+ * fspt_png_filtered_eval: stage one alone - the filtered stream of fspt_png_encode's arguments (host pointers), h rows of
+ * 1 + w * channels bytes.  fspt_png_last_ms: the three stages (filter, deflate, offsets + pack) of the last fspt_png_encode /
+ * _encode_device call from HIP events, and (or NULL) the bytes it brought to the host. */
+#define FSPT_PNG_CHUNK 16384u
+int fspt_png_filtered_eval(int device, const uint8_t *rgba8, uint32_t w, uint32_t h, int bottom_up, const fspt_png_params *p, uint8_t *stream_out);
+int fspt_png_last_ms(float ms[3], uint64_t *bus_bytes);
 
 #ifdef __cplusplus
 }

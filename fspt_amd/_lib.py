@@ -104,6 +104,11 @@ class PngParams(C.Structure):
     _fields_ = [("channels", C.c_uint32), ("filter", C.c_uint32), ("chunk_bytes", C.c_uint32)]
 
 
+class ExrParams(C.Structure):
+    """fspt_exr_params: compression 0 = none / 2 = ZIPS / 3 = ZIP, pixel type 1 = HALF / 2 = FLOAT, layer bits (1 alpha, 2 albedo, 4 normal, 8 depth), bytes of a block's predicted stream per deflate chunk (0 = FSPT_EXR_CHUNK)"""
+    _fields_ = [("compression", C.c_uint32), ("pixel_type", C.c_uint32), ("layers", C.c_uint32), ("chunk_bytes", C.c_uint32)]
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("target_rel_mse", C.c_double), ("max_ticks", C.c_uint32), ("min_ticks", C.c_uint32), ("round_ticks", C.c_uint32)]
 
@@ -351,6 +356,12 @@ SIGNATURES = {
     "fspt_png_filtered_eval": (C.c_int, [C.c_int, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(PngParams), C.POINTER(C.c_uint8)]),
     "fspt_png_last_ms": (C.c_int, [_F, C.POINTER(C.c_uint64)]),
     "fspt_draw_png": (C.c_int, [_VP, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.POINTER(PngParams), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fspt_exr_bound": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(ExrParams), C.POINTER(C.c_size_t)]),
+    "fspt_exr_encode": (C.c_int, [C.c_int, _F, _F, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(ExrParams), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fspt_exr_encode_device": (C.c_int, [C.c_int, _VP, _VP, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(ExrParams), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fspt_exr_set_form": (C.c_int, [C.c_int]),
+    "fspt_exr_last_ms": (C.c_int, [_F, C.POINTER(C.c_uint64)]),
+    "fspt_draw_exr": (C.c_int, [_VP, C.c_int, C.POINTER(ExrParams), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
     "fspt_multi_last_stage_ms": (C.c_int, [_VP, _F, C.c_uint32]),
     "fspt_device_memory": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fspt_last_error": (C.c_char_p, []),

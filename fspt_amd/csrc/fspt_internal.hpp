@@ -18,6 +18,7 @@
 //   fspt_sky.hip           the sky generator and the environment's importance bins, built on the GPU
 //   fspt_jpeg.hip          the baseline JPEG encoder behind fspt_jpeg_encode, fspt_draw_jpeg and fspt_present_jpeg, and its stand-alone entries
 //   fspt_png.hip           the PNG encoder behind fspt_png_encode and fspt_draw_png, and its stand-alone entries
+//   fspt_exr.hip           the OpenEXR encoder behind fspt_exr_encode and fspt_draw_exr; its deflate is fspt_png.hip's kernel (deflate_launch)
 #pragma once
 #include "../../include/fspt.h"
 #include "../../include/fspt_tuning.h"
@@ -307,6 +308,54 @@ hipError_t png_launch(PngEnc &e, const uint32_t *rgba, int bottom_up, hipStream_
 int png_collect(PngEnc &e, hipStream_t st, uint8_t *out, size_t cap, size_t *bytes_out, const char *fn); // waits for st, then jpeg_deliver's rules
 void png_note_ms(PngEnc &e);  // the stage times of a finished launch, for fspt_png_last_ms
 void png_release(PngEnc &e);
+// The deflate both encoders share (k_png_deflate, fspt_png.hip): `stream` is n_seg segments of seg_bytes one behind the
+// other (the last holds what is left of stream_bytes), each one zlib stream of its own, cut into chunks of cb from its first
+// byte: chunk k is chunk k % cps of segment k / cps.  The first chunk of a segment carries the zlib header, the last one
+// BFINAL; a chunk's bytes land in its scratch slot and (bytes, CRC-32 of its IDAT when `crc`, Adler A, B) in its 4 words of
+// `meta`.  PNG is one segment: seg_bytes = stream_bytes, cps = n_chunks.
+static const uint32_t DEFLATE_META = 4u, DEFLATE_CHUNK_MIN = 256u, DEFLATE_CHUNK_MAX = 32768u, DEFLATE_ADLER = 65521u;
+struct DeflateP {
+  const uint8_t *stream;
+  size_t stream_bytes, seg_bytes;
+  uint32_t cb, cps, crc;
+  uint8_t *scratch;
+  size_t slot_bytes;
+  uint32_t *meta;
+};
+size_t deflate_slot_bytes(uint32_t cb);
+hipError_t deflate_launch(const DeflateP &p, uint32_t n_chunks, hipStream_t st);
+// fspt_exr.hip: the OpenEXR encoder, laid out as the PNG one.  ExrPlan: what follows from a size and checked
+// parameters, on the host.  ExrEnc: the device memory of one encoder - the header of its plan, the predicted stream and the
+// raw bytes of every block, the deflate's slots and records, a record per block, one output buffer - owned by a target
+// (fspt_draw_exr) or by one stand-alone call.
+static const uint32_t EXR_MAX_CHANNELS = 11u, EXR_HEADER_MAX = 512u;
+struct ExrChannel { uint32_t src, bytes, off; }; // src: 0..3 = the rgba float, 4..11 = the feature float src - 4; off: in units of w bytes within a scanline
+struct ExrPlan {
+  uint32_t w, h, compression, pixel_type, layers, cb, form;
+  uint32_t n_ch, px_bytes, lpb, n_blocks, cps, n_chunks, hdr_len;
+  ExrChannel ch[EXR_MAX_CHANNELS]; // in file order
+  size_t line_bytes, block_bytes, data_bytes; // a scanline | a full block | every block, uncompressed
+  size_t slot_bytes, bound;
+  uint8_t hdr[EXR_HEADER_MAX];
+};
+struct ExrEnc {
+  ExrPlan pl{};
+  bool valid = false;
+  uint8_t *cfg = nullptr;                    // the header
+  uint8_t *stream = nullptr, *raw = nullptr; // the deflate's input | the same blocks as they are (form 1)
+  uint8_t *scratch = nullptr;
+  uint32_t *meta = nullptr, *chunk_off = nullptr; // per chunk: 4 words | where its bytes start in its block's data
+  uint64_t *blk = nullptr;                        // per block: the block's offset in the file, (size << 32 | Adler-32); blk[2 n_blocks] = the file's length
+  uint8_t *out = nullptr;
+  size_t out_bytes = 0;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+};
+int exr_plan(const fspt_exr_params *prm, uint32_t w, uint32_t h, bool for_device, const char *fn, ExrPlan &pl); // validates: FSPT_E_INVALID, no device touched
+hipError_t exr_ensure(ExrEnc &e, const ExrPlan &pl, size_t out_bytes);                 // nothing of `e` may be in use
+hipError_t exr_launch(ExrEnc &e, const float4 *rgba, const float4 *feat, int bottom_up, hipStream_t st); // no host read, no synchronisation
+int exr_collect(ExrEnc &e, hipStream_t st, uint8_t *out, size_t cap, size_t *bytes_out, const char *fn);
+void exr_note_ms(ExrEnc &e);
+void exr_release(ExrEnc &e);
 // fspt_pose.hip.  pose_run: s->pose set, s->rf.stage allocated, the call ordered against the targets;
 // mats_host = n_parts x 30 floats (a | D | N).  Uploads them, runs k_pose_transform into s->rf.stage and waits.
 int pose_run(fspt_scene *s, const float *mats_host);
@@ -562,6 +611,8 @@ struct fspt_target {
   uint32_t *jp_frame = nullptr;               // fspt_draw_jpeg's and fspt_draw_png's drawn frame, W*H texels
   fspt::PngEnc pg;                            // PNG output (fspt_draw_png): allocated on first use
   uint32_t pg_cb = 0;                         // the smallest chunk size fspt_draw_png was asked for: pg.out is sized for it
+  fspt::ExrEnc ex;                            // OpenEXR output (fspt_draw_exr): allocated on first use
+  size_t ex_bound = 0;                        // the largest bound fspt_draw_exr was asked for: ex.out is sized for it
   uint32_t *jp_count[2] = {nullptr, nullptr}; // pinned host memory: a slot's byte count, current behind pr_copied[slot]
   int pr_kind[2] = {0, 0};                    // 0: an RGBA8 frame, 1: a JPEG file
   hipStream_t jp_copy = nullptr;              // a present file's bytes come to the host here: the copy waits for no stream that holds the next frame

@@ -1094,6 +1094,46 @@ static napi_value DrawPng(napi_env env, napi_callback_info info) {
   const int rc = fspt_draw_png((fspt_target *)h, (int)src, (float)ex, (float)sat, den ? 1 : 0, (float)sig, (float)scale, &p, (uint8_t *)dst, nd, &bytes);
   return jpeg_answer(env, rc, nd, bytes);
 }
+/* OpenEXR output (include/fspt.h fspt_exr_* / fspt_draw_exr): as the PNG entries above */
+static int exr_args(napi_env env, const napi_value *a, fspt_exr_params *p) { /* compression, pixelType, layers, chunkBytes */
+  double v[4];
+  for (int i = 0; i < 4; ++i) {
+    if (get_f64(env, a[i], &v[i])) return -1;
+    if (!(v[i] >= 0.0 && v[i] <= 4294967295.0)) { napi_throw_range_error(env, NULL, "fspt_napi: EXR parameters must be non-negative integers"); return -1; }
+  }
+  p->compression = (uint32_t)v[0]; p->pixel_type = (uint32_t)v[1]; p->layers = (uint32_t)v[2]; p->chunk_bytes = (uint32_t)v[3];
+  return 0;
+}
+static napi_value ExrBound(napi_env env, napi_callback_info info) {
+  /* exrBound(width, height, compression, pixelType, layers, chunkBytes) -> bytes no file exceeds */
+  napi_value a[6], r; double w, h; fspt_exr_params p; size_t n = 0;
+  if (get_args(env, info, 6, a) || get_f64(env, a[0], &w) || get_f64(env, a[1], &h) || exr_args(env, a + 2, &p)) return NULL;
+  FSPT_OK_OR_THROW(fspt_exr_bound(w >= 0.0 && w <= 4294967295.0 ? (uint32_t)w : 0u, h >= 0.0 && h <= 4294967295.0 ? (uint32_t)h : 0u, &p, &n));
+  NAPI_OK(napi_create_double(env, (double)n, &r));
+  return r;
+}
+static napi_value ExrEncode(napi_env env, napi_callback_info info) {
+  /* exrEncode(device, Float32Array(w*h*4), Float32Array(w*h*8) | null, width, height, bottomUp, compression, pixelType, layers, chunkBytes, Uint8Array out) */
+  napi_value a[11]; void *src, *feat, *dst; size_t ns, nf, nd, bytes = 0; double dev, w, h; bool up; fspt_exr_params p;
+  if (get_args(env, info, 11, a) || get_f64(env, a[0], &dev) || typed(env, a[1], napi_float32_array, 0, &src, &ns) || typed(env, a[2], napi_float32_array, 1, &feat, &nf)) return NULL;
+  if (get_f64(env, a[3], &w) || get_f64(env, a[4], &h)) return NULL;
+  NAPI_OK(napi_get_value_bool(env, a[5], &up));
+  if (exr_args(env, a + 6, &p) || typed(env, a[10], napi_uint8_array, 0, &dst, &nd)) return NULL;
+  if (!(w >= 1.0 && w <= 65535.0 && h >= 1.0 && h <= 65535.0) || (double)ns != w * h * 4.0 || (feat && (double)nf != w * h * 8.0)) {
+    napi_throw_range_error(env, NULL, "exrEncode: need width*height*4 floats, features of width*height*8 floats or null, width and height in 1..65535");
+    return NULL;
+  }
+  const int rc = fspt_exr_encode((int)dev, (const float *)src, (const float *)feat, (uint32_t)w, (uint32_t)h, up ? 1 : 0, &p, (uint8_t *)dst, nd, &bytes);
+  return jpeg_answer(env, rc, nd, bytes);
+}
+static napi_value DrawExr(napi_env env, napi_callback_info info) {
+  /* drawExr(target, source, compression, pixelType, layers, chunkBytes, Uint8Array out) */
+  napi_value a[7]; void *h, *dst; size_t nd, bytes = 0; double src; fspt_exr_params p;
+  if (get_args(env, info, 7, a) || unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  if (get_f64(env, a[1], &src) || exr_args(env, a + 2, &p) || typed(env, a[6], napi_uint8_array, 0, &dst, &nd)) return NULL;
+  const int rc = fspt_draw_exr((fspt_target *)h, (int)src, &p, (uint8_t *)dst, nd, &bytes);
+  return jpeg_answer(env, rc, nd, bytes);
+}
 /* guided denoiser (include/fspt.h fspt_features / fspt_denoise / fspt_draw_denoised) */
 static napi_value Features(napi_env env, napi_callback_info info) {
   /* features(target, params (as render), samples, seed) */
@@ -1763,7 +1803,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
       {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"sceneUpdateSky", SceneUpdateSky}, {"sceneUpdateEnvironmentAuto", SceneUpdateEnvironmentAuto}, {"skyGenerate", SkyGenerate}, {"atlasPackGpu", AtlasPackGpu}, {"sceneUpdateTextures", SceneUpdateTextures}, {"scenePatchTextures", ScenePatchTextures}, {"envBinsGpu", EnvBinsGpu}, {"sceneSetPose", SceneSetPose}, {"sceneUpdateTransforms", SceneUpdateTransforms}, {"sceneSetSkin", SceneSetSkin}, {"sceneUpdateSkin", SceneUpdateSkin}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
-      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"jpegBound", JpegBound}, {"jpegEncode", JpegEncode}, {"drawJpeg", DrawJpeg}, {"presentJpeg", PresentJpeg}, {"pngBound", PngBound}, {"pngEncode", PngEncode}, {"pngFilteredEval", PngFilteredEval}, {"drawPng", DrawPng}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setCameraModel", SetCameraModel}, {"cameraModel", CameraModel}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
+      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"jpegBound", JpegBound}, {"jpegEncode", JpegEncode}, {"drawJpeg", DrawJpeg}, {"presentJpeg", PresentJpeg}, {"pngBound", PngBound}, {"pngEncode", PngEncode}, {"pngFilteredEval", PngFilteredEval}, {"drawPng", DrawPng}, {"exrBound", ExrBound}, {"exrEncode", ExrEncode}, {"drawExr", DrawExr}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setCameraModel", SetCameraModel}, {"cameraModel", CameraModel}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},
       {"renderAsync", RenderAsync}, {"multiCreate", MultiCreate}, {"multiDestroy", MultiDestroy}, {"multiTarget", MultiTarget},
       {"multiCamera", MultiCamera}, {"multiTrace", MultiTrace}, {"multiRender", MultiRender}, {"multiRenderAsync", MultiRenderAsync},

@@ -4,7 +4,8 @@
 // independent chunks of literals and distance-1 matches under a length-limited dynamic Huffman code per chunk.
 //   k_png_filter    one workgroup per row: the five filters' costs from the raw neighbours, reduced across the workgroup,
 //                   then the chosen residuals into the flat stream, a whole dword per lane where the row owns it
-//   k_png_deflate   one workgroup per chunk: run heads and lengths by a scan, tokens in closed form per position, the
+//   k_png_deflate   (also the OpenEXR encoder's, fspt_exr.hip: the input is segments, each a zlib stream of its own whose chunks restart
+//                   at its first byte; a PNG is one segment)  one workgroup per chunk: run heads and lengths by a scan, tokens in closed form per position, the
 //                   histogram by LDS atomics, the code by a rank sort and one lane's merge, the bits OR-ed into an LDS
 //                   buffer at scanned offsets (disjoint bits: order does not matter), the stored block where it is not
 //                   longer, the chunk's Adler pair and its IDAT's CRC-32 as sums over the lanes' slices
@@ -21,10 +22,10 @@ constexpr uint32_t PNG_FT = 256u;       // lanes of a filter workgroup
 constexpr uint32_t PNG_DT = 512u;       // lanes of a deflate workgroup
 constexpr uint32_t PNG_NSYM = 286u;     // literal/length symbols
 constexpr uint32_t PNG_SYMS = 288u;     // (arrays of them)
-constexpr uint32_t PNG_ADLER = 65521u;
-constexpr uint32_t PNG_CHUNK_MIN = 256u, PNG_CHUNK_MAX = 32768u;
+constexpr uint32_t PNG_ADLER = DEFLATE_ADLER;
+constexpr uint32_t PNG_CHUNK_MIN = DEFLATE_CHUNK_MIN, PNG_CHUNK_MAX = DEFLATE_CHUNK_MAX;
 constexpr uint32_t PNG_CHUNK_EXTRA = 12u; // beyond a chunk's own bytes: the zlib header (2), a stored header (5) and the empty stored block (5) at the most
-constexpr uint32_t PNG_META = 4u;         // words per chunk: bytes, CRC-32, Adler A, Adler B
+constexpr uint32_t PNG_META = DEFLATE_META; // words per chunk: bytes, CRC-32, Adler A, Adler B
 
 struct PngFilterP {
   const uint32_t *rgba; // w x h texels
@@ -116,14 +117,7 @@ __global__ void __launch_bounds__(PNG_FT) k_png_filter(PngFilterP p) {
   }
 }
 
-struct PngDeflateP {
-  const uint8_t *stream;
-  size_t stream_bytes;
-  uint32_t cb, n_chunks;
-  uint8_t *scratch;
-  size_t slot_bytes;
-  uint32_t *meta; // per chunk: PNG_META words
-};
+using PngDeflateP = DeflateP; // (fspt_internal.hpp: the OpenEXR encoder launches the same kernel)
 
 // a lane's writer into the LDS bit buffer, deflate's order: bit position p counts from the least significant bit of word 0
 struct LsbSink {
@@ -263,9 +257,12 @@ __global__ void __launch_bounds__(PNG_DT) k_png_deflate(PngDeflateP p) {
   __shared__ uint32_t s_scan[PNG_DT], s_scan2[PNG_DT], s_crc[256], s_lencode[256];
   __shared__ uint32_t s_nsyms, s_hlit, s_hclen, s_hbits, s_red[3];
   const uint32_t t = threadIdx.x, k = blockIdx.x;
-  const size_t base = (size_t)k * p.cb;
-  const uint32_t n = (uint32_t)min((size_t)p.cb, p.stream_bytes - base);
-  const bool last = k + 1u == p.n_chunks;
+  // chunk j of segment seg: a segment is a zlib stream of its own, and its chunks restart at its first byte
+  const uint32_t seg = k / p.cps, j = k - seg * p.cps;
+  const size_t seg_base = (size_t)seg * p.seg_bytes, seg_len = min(p.seg_bytes, p.stream_bytes - seg_base);
+  const size_t base = seg_base + (size_t)j * p.cb;
+  const uint32_t n = (uint32_t)min((size_t)p.cb, seg_len - (size_t)j * p.cb);
+  const bool first = j == 0u, last = (size_t)j * p.cb + n == seg_len;
   const uint32_t in_words = (p.cb + 3u) / 4u + 1u, out_words = (p.cb + PNG_CHUNK_EXTRA + 3u) / 4u + 2u;
   uint32_t *s_out = s_dyn + in_words;
   const uint8_t *in = (const uint8_t *)s_dyn;
@@ -361,7 +358,7 @@ __global__ void __launch_bounds__(PNG_DT) k_png_deflate(PngDeflateP p) {
   }
   const uint32_t body = s_scan[PNG_DT - 1u];
   const uint32_t dyn_bits = s_hbits + body + s_len[256];
-  const uint32_t ob = k == 0u ? 2u : 0u; // the zlib header in front of the first chunk
+  const uint32_t ob = first ? 2u : 0u; // the zlib header in front of a segment's first chunk
   const bool stored = (dyn_bits + 7u) / 8u >= 5u + n;
   uint32_t L; // the chunk's bytes in the file
   if (stored) {
@@ -404,7 +401,7 @@ __global__ void __launch_bounds__(PNG_DT) k_png_deflate(PngDeflateP p) {
   }
   __syncthreads();
   if (t == 0) {
-    if (k == 0u) { outb[0] = 0x78; outb[1] = 0x01; }
+    if (first) { outb[0] = 0x78; outb[1] = 0x01; }
     if (!stored && !last) { outb[L - 2u] = 0xFF; outb[L - 1u] = 0xFF; }
   }
   __syncthreads();
@@ -413,12 +410,12 @@ __global__ void __launch_bounds__(PNG_DT) k_png_deflate(PngDeflateP p) {
   {
     const uint32_t cspan = (L + PNG_DT - 1u) / PNG_DT, clo = min(t * cspan, L), chi = min(clo + cspan, L);
     uint32_t x = 0;
-    if (chi > clo) {
+    if (p.crc && chi > clo) {
       uint32_t c = 0xFFFFFFFFu;
       for (uint32_t i = clo; i < chi; ++i) c = s_crc[(c ^ outb[i]) & 255u] ^ (c >> 8);
       x = png_crc_shift(~c, L - chi);
     }
-    if (t == 0) x ^= png_crc_shift(PNG_CRC_IDAT, L);
+    if (p.crc && t == 0) x ^= png_crc_shift(PNG_CRC_IDAT, L);
     uint32_t sa = 0, sb = 0; // (a lane: at most 64 bytes of 255 at a weight of 32768)
     for (uint32_t i = lo; i < hi; ++i) { const uint32_t v = in[i]; sa += v; sb += (n - i) * v; }
     sb %= PNG_ADLER;
@@ -520,6 +517,18 @@ size_t png_dyn_lds(uint32_t cb) { return (((size_t)cb + 3u) / 4u + 1u + ((size_t
 
 } // namespace
 
+size_t deflate_slot_bytes(uint32_t cb) { return ((size_t)cb + PNG_CHUNK_EXTRA + 3u) / 4u * 4u + 4u; }
+
+hipError_t deflate_launch(const DeflateP &p, uint32_t n_chunks, hipStream_t st) {
+  const size_t lds = png_dyn_lds(p.cb);
+  if (lds > 48u * 1024u) {
+    const hipError_t err = hipFuncSetAttribute((const void *)k_png_deflate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)png_dyn_lds(PNG_CHUNK_MAX));
+    if (err != hipSuccess) return err;
+  }
+  hipLaunchKernelGGL(k_png_deflate, dim3(n_chunks), dim3(PNG_DT), lds, st, p);
+  return hipGetLastError();
+}
+
 static const fspt_png_params PNG_DEFAULTS = {3u, (uint32_t)FSPT_PNG_FILTER_ADAPTIVE, FSPT_PNG_CHUNK};
 
 int png_check_params(const fspt_png_params *prm, const char *fn) {
@@ -543,7 +552,7 @@ int png_plan(const fspt_png_params *prm, uint32_t w, uint32_t h, bool for_device
   pl.bound = png_bound_of(w, h, pl.channels, pl.cb);
   if (for_device && pl.bound > 0xFFFFFFFFull) { fspt_set_error("%s: a file of %u x %u could pass 4 GiB", fn, w, h); return FSPT_E_INVALID; }
   pl.n_chunks = (uint32_t)((pl.stream_bytes + pl.cb - 1u) / pl.cb);
-  pl.slot_bytes = ((size_t)pl.cb + PNG_CHUNK_EXTRA + 3u) / 4u * 4u + 4u;
+  pl.slot_bytes = deflate_slot_bytes(pl.cb);
   return FSPT_OK;
 }
 
@@ -601,16 +610,12 @@ hipError_t png_launch_filter(PngEnc &e, const uint32_t *rgba, int bottom_up, hip
 // e.off[n_chunks + 1].  Events 0..3 bracket the three stages.  No host read, no synchronisation.
 hipError_t png_launch(PngEnc &e, const uint32_t *rgba, int bottom_up, hipStream_t st) {
   const PngPlan &pl = e.pl;
-  const size_t lds = png_dyn_lds(pl.cb);
-  hipError_t err = hipSuccess;
-  if (lds > 48u * 1024u) err = hipFuncSetAttribute((const void *)k_png_deflate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)png_dyn_lds(PNG_CHUNK_MAX));
-  if (err == hipSuccess) err = hipEventRecord(e.ev[0], st);
+  hipError_t err = hipEventRecord(e.ev[0], st);
   if (err == hipSuccess) err = png_launch_filter(e, rgba, bottom_up, st);
   if (err == hipSuccess) err = hipEventRecord(e.ev[1], st);
   if (err != hipSuccess) return err;
-  PngDeflateP d{e.stream, pl.stream_bytes, pl.cb, pl.n_chunks, e.scratch, pl.slot_bytes, e.meta};
-  hipLaunchKernelGGL(k_png_deflate, dim3(pl.n_chunks), dim3(PNG_DT), lds, st, d);
-  err = hipGetLastError();
+  const DeflateP d{e.stream, pl.stream_bytes, pl.stream_bytes, pl.cb, pl.n_chunks, 1u, e.scratch, pl.slot_bytes, e.meta}; // one segment
+  err = deflate_launch(d, pl.n_chunks, st);
   if (err == hipSuccess) err = hipEventRecord(e.ev[2], st);
   if (err != hipSuccess) return err;
   hipLaunchKernelGGL(k_png_offsets, dim3(1), dim3(256), 0, st, (const uint32_t *)e.meta, pl.n_chunks, PNG_HEADER_BYTES, pl.cb, pl.stream_bytes, e.off);

@@ -902,6 +902,30 @@ int fspt_draw_png(fspt_target *t, int source, float exposure, float saturation, 
   return fspt::png_collect(t->pg, t->stream, out, cap, bytes_out, fn);
 }
 
+// ---------------------------------------------------------------------------
+// OpenEXR output (fspt_exr.hip): the HDR buffer itself, no draw in front of it
+// ---------------------------------------------------------------------------
+int fspt_draw_exr(fspt_target *t, int source, const fspt_exr_params *p, uint8_t *out, size_t cap, size_t *bytes_out) {
+  const char *fn = "fspt_draw_exr";
+  if (!t || !out || !bytes_out) { fspt_set_error("%s: NULL argument", fn); return FSPT_E_INVALID; }
+  if (source < FSPT_SOURCE_ACCUMULATOR || source > FSPT_SOURCE_TEMPORAL_DENOISED) { fspt_set_error("%s: unknown source %d", fn, source); return FSPT_E_INVALID; }
+  fspt::ExrPlan pl;
+  int rc = fspt::exr_plan(p, t->W, t->H, true, fn, pl);
+  if (rc) return rc;
+  if ((rc = dn_enter(t, true, fn))) return rc; // (joins a present)
+  const float4 *src = nullptr;
+  int denoise = 0; float max_sigma = 0.0f, scale = 1.0f;
+  if ((rc = encoded_source(t, source, src, denoise, max_sigma, scale))) return rc;
+  const bool guided = (pl.layers & ((uint32_t)FSPT_EXR_ALBEDO | (uint32_t)FSPT_EXR_NORMAL | (uint32_t)FSPT_EXR_DEPTH)) != 0u;
+  if (guided && !t->feat_valid) { fspt_set_error("%s: feature layers and no fspt_features call yet", fn); return FSPT_E_STATE; }
+  // the output buffer: the largest bound asked for so far; it grows, and outlives a change of the parameters
+  t->ex_bound = std::max(t->ex_bound, pl.bound);
+  hipError_t e = fspt::exr_ensure(t->ex, pl, t->ex_bound);
+  if (e == hipSuccess) e = fspt::exr_launch(t->ex, src, guided ? t->feat : nullptr, 1, t->stream);
+  if (e != hipSuccess) return hip_fail(fn, e);
+  return fspt::exr_collect(t->ex, t->stream, out, cap, bytes_out, fn);
+}
+
 } // extern "C"
 
 // fspt_target_destroy's share of the image chain (both streams are idle): every buffer and event above
@@ -909,7 +933,7 @@ void post_release(fspt_target *t) {
   hipFree(t->feat); hipFree(t->dn_tmp[0]); hipFree(t->dn_tmp[1]); hipFree(t->dn_out);
   hipFree(t->tm_hist[0]); hipFree(t->tm_hist[1]); hipFree(t->tm_g[0]); hipFree(t->tm_g[1]); hipFree(t->tm_m);
   sv_free(t); cl_free(t); ax_free(t); bl_free(t);
-  fspt::jpeg_release(t->jp); fspt::png_release(t->pg); hipFree(t->jp_frame);
+  fspt::jpeg_release(t->jp); fspt::png_release(t->pg); fspt::exr_release(t->ex); hipFree(t->jp_frame);
   for (uint32_t *c : t->jp_count) if (c) hipHostFree(c);
   if (t->jp_copy) hipStreamDestroy(t->jp_copy);
   for (hipEvent_t ev : t->tm_ev) if (ev) hipEventDestroy(ev);

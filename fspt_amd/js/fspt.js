@@ -382,6 +382,38 @@ function pngFilteredEval(rgba, width, height, opts) {
   addon.pngFilteredEval(o.device || 0, rgba, width, height, !!o.bottomUp, ...enc, out);
   return out;
 }
+const EXR_COMPRESSIONS = { none: 0, zips: 2, zip: 3 };
+const EXR_LAYERS = { alpha: 1, albedo: 2, normal: 4, depth: 8 };
+/** {compression ('zip' | 'zips' | 'none'), float32 (false: HALF; Z is always FLOAT), layers (names of EXR_LAYERS: an array, or one string with
+ *  commas), chunkBytes (0 = the library's default)} -> the addon's four numbers */
+function exrArgs(o, fn) {
+  const c = EXR_COMPRESSIONS[o.compression === undefined ? 'zip' : String(o.compression)];
+  const names = o.layers === undefined ? [] : Array.isArray(o.layers) ? o.layers : String(o.layers).split(',').filter((x) => x);
+  const cb = o.chunkBytes === undefined ? 0 : o.chunkBytes;
+  if (c === undefined) throw new RangeError(fn + ": compression must be 'none', 'zips' or 'zip'");
+  let bits = 0;
+  for (const n of names) {
+    if (EXR_LAYERS[n] === undefined) throw new RangeError(fn + ": layers must be among 'alpha', 'albedo', 'normal' and 'depth'");
+    bits |= EXR_LAYERS[n];
+  }
+  if (!Number.isInteger(cb) || (cb !== 0 && (cb < 256 || cb > 32768))) throw new RangeError(fn + ': chunkBytes must be 0 or an integer in 256..32768');
+  return [c, o.float32 ? 2 : 1, bits, cb];
+}
+/** Scene-linear radiance (Float32Array of width*height*4; bottomUp: row 0 is the bottom, as readRadiance returns it) and, for the albedo,
+ *  normal and depth layers, the features (Float32Array of width*height*8, as readFeatures returns them) as a scanline OpenEXR file made
+ *  on the GPU (include/fspt.h fspt_exr_encode, DESIGN.md 8.21) -> Buffer.
+ *  opts: {compression ('zip'), float32 (false), layers ([]), chunkBytes (0), bottomUp (false), device (0)}. */
+function exrEncode(rgba, features, width, height, opts) {
+  const o = opts || {}, enc = exrArgs(o, 'exrEncode');
+  if (!(rgba instanceof Float32Array) || rgba.length !== width * height * 4) throw new RangeError('exrEncode: need a Float32Array of width*height*4 floats');
+  if (enc[2] & 14 ? !(features instanceof Float32Array) || features.length !== width * height * 8 : features != null && !(features instanceof Float32Array && features.length === width * height * 8)) {
+    throw new RangeError('exrEncode: the albedo, normal and depth layers need features, a Float32Array of width*height*8 floats');
+  }
+  const out = new Uint8Array(addon.exrBound(width, height, ...enc));
+  const n = addon.exrEncode(o.device || 0, rgba, features || null, width, height, !!o.bottomUp, ...enc, out);
+  if (n < 0) throw new Error('exrEncode: the file outgrew the bound');
+  return Buffer.from(out.subarray(0, n));
+}
 const JPEG_SUBSAMPLING = { '444': 0, '420': 1 };
 const JPEG_SOURCES = { accumulator: 0, denoised: 1, temporal: 2, temporalDenoised: 3 };
 /** An RGBA8 image (Uint8Array of width*height*4, alpha ignored; bottomUp: row 0 is the bottom, as drawQuad returns it) as a
@@ -588,6 +620,20 @@ class PathTracer {
     }
     if (n < 0) throw new Error('drawPng: the file outgrew the bound');
     return Buffer.from(this._pngBuf.subarray(0, n));
+  }
+  /** The HDR buffer itself as a scene-linear OpenEXR file (include/fspt.h fspt_draw_exr, DESIGN.md 8.21): readRadiance's ('accumulator'),
+   *  denoise's, temporalAccumulate's or temporalDenoise's buffer, with the guides of features() as layers; made on the GPU, only the file
+   *  crosses the bus -> Buffer.  opts: {source, compression, float32, layers, chunkBytes} as exrEncode's.  No exposure, bloom or tone map. */
+  drawExr(opts) {
+    const o = opts || {}, enc = exrArgs(o, 'drawExr');
+    const src = JPEG_SOURCES[o.source === undefined ? 'accumulator' : o.source];
+    if (src === undefined) throw new RangeError("drawExr: source must be 'accumulator', 'denoised', 'temporal' or 'temporalDenoised'");
+    const need = addon.exrBound(this.resolution[0], this.resolution[1], ...enc);
+    if (!this._exrBuf || this._exrBuf.length < need) this._exrBuf = new Uint8Array(need);
+    let n = addon.drawExr(this._target, src, ...enc, this._exrBuf);
+    if (n < 0) { this._exrBuf = new Uint8Array(-n); n = addon.drawExr(this._target, src, ...enc, this._exrBuf); }
+    if (n < 0) throw new Error('drawExr: the file outgrew the bound');
+    return Buffer.from(this._exrBuf.subarray(0, n));
   }
   presentJpeg(opts) {
     const a = this._jpegArgs(opts, 'presentJpeg');
@@ -984,5 +1030,5 @@ class MultiPathTracer {
 // memory later scenes may spend on interleaved material textures (fspt_set_texture_interleave_budget; results do not depend on it)
 function setTextureInterleaveBudget(bytes) { addon.setTextureInterleaveBudget(bytes); }
 
-module.exports = { addon, setTextureInterleaveBudget, jpegEncode, pngEncode, pngFilteredEval, skyGenerate, envBinsGpu, atlasPackGpu, SKY_DEFAULTS, MultiPathTracer, AtlasLayers, resolveMaterial, readMtl, mergeSceneProps, resampleImage, packReferenceScene, buildScene,
+module.exports = { addon, setTextureInterleaveBudget, jpegEncode, pngEncode, pngFilteredEval, exrEncode, skyGenerate, envBinsGpu, atlasPackGpu, SKY_DEFAULTS, MultiPathTracer, AtlasLayers, resolveMaterial, readMtl, mergeSceneProps, resampleImage, packReferenceScene, buildScene,
   PathTracer, saveBlob, loadBlob };

@@ -200,13 +200,18 @@ function renderFrame(scene, settings, width, height, opts) {
   }
 }
 
-/** scene file -> PNG file, or a JPEG file when outPath ends in .jpg / .jpeg (the reference POSTs canvas.toBlob's PNG to /upload/<scene>/<frame>, main.js:859-866) */
+/** scene file -> PNG file, a JPEG file when outPath ends in .jpg / .jpeg, or an OpenEXR file of the radiance when it ends in .exr (the reference POSTs canvas.toBlob's PNG to /upload/<scene>/<frame>, main.js:859-866) */
 function renderToPng(scenePath, outPath, width, height, opts) {
   const { scene, settings } = loadSceneFile(scenePath, opts && opts.assetRoot, 4, { bvh: opts && opts.bvh, device: opts && opts.device });
   const fr = renderFrame(scene, settings, width, height, opts);
   if (/\.jpe?g$/i.test(outPath)) { // a JPEG encoded on the GPU (fspt.js jpegEncode, DESIGN.md 8.19); opts.jpeg: {quality, subsampling, restartMcus}
     fs.mkdirSync(path.dirname(path.resolve(outPath)), { recursive: true });
     fs.writeFileSync(outPath, F.jpegEncode(fr.rgba, width, height, Object.assign({ device: opts && opts.device }, opts && opts.jpeg)));
+    return fr;
+  }
+  if (/\.exr$/i.test(outPath)) { // the radiance as a scene-linear OpenEXR file made on the GPU (fspt.js exrEncode, DESIGN.md 8.21); opts.exr: {compression, float32, layers: ['alpha'], chunkBytes}
+    fs.mkdirSync(path.dirname(path.resolve(outPath)), { recursive: true });
+    fs.writeFileSync(outPath, F.exrEncode(fr.radiance, null, width, height, Object.assign({ device: opts && opts.device, bottomUp: true }, opts && opts.exr)));
     return fr;
   }
   if (opts && opts.pngGpu) { // a PNG filtered and deflated on the GPU (fspt.js pngEncode, DESIGN.md 8.20); opts.png: {channels, filter, chunkBytes}

@@ -12,6 +12,7 @@ reference's format (scene/<name>.json with props / static_props / animated_props
     python -m fspt_amd.render --scene 'web/scene/anim_{frame}.json' --frames 0:24 --bvh refit --pose --out 'out/{frame}.png'  # one matrix per prop per frame
     python -m fspt_amd.render --out bunny.jpg --jpeg-quality 90 --jpeg-444   # drawn and JPEG-encoded on the GPU
     python -m fspt_amd.render --out bunny.png --png-gpu                      # drawn, filtered and deflated on the GPU
+    python -m fspt_amd.render --out bunny.exr --exr-layers albedo,normal,depth  # scene-linear OpenEXR with the guides as layers, made on the GPU
     python -m fspt_amd.render --out pano.png --width 1024 --height 512 --camera equirect  # 360-degree panorama (also: ortho, fisheye:180, stereo:0.064)
 
 Path tracing runs in the HIP kernels (fspt_render), tone mapping in the draw.fs kernel (fspt_draw); --atrous K runs
@@ -98,7 +99,10 @@ def main(argv=None):
     ap.add_argument("--denoise", action="store_true", help="draw.fs's 5x5 firefly clamp")
     ap.add_argument("--atrous", type=int, default=0, help="guided a-trous denoiser iterations (0 = off; built-in scene)")
     ap.add_argument("--feature-samples", type=int, default=8, help="camera rays per pixel of the denoiser's guide buffers")
-    ap.add_argument("--hdr", default=None, help="also save the RGBA32F radiance buffer as .npy")
+    ap.add_argument("--hdr", default=None, help="also save the RGBA32F radiance buffer: a name that ends in .exr as OpenEXR made on the GPU (DESIGN 8.21), any other as .npy")
+    ap.add_argument("--exr-layers", default="", help="--out / --hdr *.exr: layers beside R G B, of albedo,normal,depth,alpha")
+    ap.add_argument("--exr-float", action="store_true", help="--out / --hdr *.exr: 32-bit FLOAT channels (the default is HALF; Z is always FLOAT)")
+    ap.add_argument("--exr-compression", default="zip", choices=("none", "zips", "zip"), help="--out / --hdr *.exr: blocks of 16 scanlines deflated (zip, the default), of one (zips), or none")
     ap.add_argument("--scene", default=None, help="scene JSON ({frame} is replaced per frame with --frames)")
     ap.add_argument("--assets", default=None, help="web root the JSON's paths are relative to (default: parent of the scene folder)")
     ap.add_argument("--frames", default=None, help="A:B = frames A..B-1 (the reference's ?frame=N loop, main.js:851-866)")
@@ -152,7 +156,18 @@ def main(argv=None):
         ap.error(str(e))
     if not 1 <= args.jpeg_quality <= 100:
         ap.error("--jpeg-quality must lie in 1..100")
-    from .scene_file import is_jpeg_path, write_image
+    from .scene_file import is_exr_path, is_jpeg_path, write_image
+    exr_out, exr_hdr = is_exr_path(args.out), bool(args.hdr) and is_exr_path(args.hdr)
+    if (args.exr_layers or args.exr_float or args.exr_compression != "zip") and not (exr_out or exr_hdr):
+        ap.error("--exr-layers, --exr-float and --exr-compression need an --out or --hdr that ends in .exr")
+    try:
+        from .tracer import exr_params
+        exr = dict(compression=args.exr_compression, float32=args.exr_float, layers=[x for x in args.exr_layers.split(",") if x])
+        exr_guided = bool(exr_params(**exr).layers & 14)
+    except ValueError as e:
+        ap.error("--exr-layers: " + str(e))
+    if exr_guided and args.scene and not (args.frames and args.bvh == "refit"):
+        ap.error("--exr-layers albedo, normal and depth are available for the built-in scene, or with --frames and --bvh refit")
     jpeg = dict(quality=args.jpeg_quality, subsampling="444" if args.jpeg_444 else "420")
     if (args.jpeg_quality != 85 or args.jpeg_444) and not is_jpeg_path(args.out):
         ap.error("--jpeg-quality and --jpeg-444 need an --out that ends in .jpg or .jpeg")
@@ -229,7 +244,7 @@ def main(argv=None):
                                     rebuild_above=args.rebuild_above,
                                     temporal=({"atrous": args.atrous, "clamp": None if args.temporal_clamp is None else True if args.temporal_clamp is True
                                                else {"sigma_scale": args.temporal_clamp}} if args.temporal else None),
-                                    variance=args.variance_guided, pose=args.pose, textures=args.textures, jpeg=jpeg, png=png, **kw)
+                                    variance=args.variance_guided, pose=args.pose, textures=args.textures, jpeg=jpeg, png=png, exr=exr, **kw)
             print(f"{len(out)} frames in {time.perf_counter() - t0:.2f} s:", *out)
         else:
             arrays, settings = F.load_scene_file(args.scene, args.assets, bvh=args.bvh, textures=args.textures)
@@ -237,9 +252,11 @@ def main(argv=None):
                 arrays = F.arrays_with_sky(arrays, **sky_at(0.0))
             settings["exposure"] = settings["exposure"] * args.exposure
             rgba, rad = F.render_frame(arrays, settings, args.width, args.height, **kw)
-            if args.hdr:
+            if exr_hdr:
+                write_image(args.hdr, np.ascontiguousarray(rad[::-1]), exr=exr)
+            elif args.hdr:
                 np.save(args.hdr, rad)
-            write_image(args.out, rgba, jpeg, png=png)
+            write_image(args.out, np.ascontiguousarray(rad[::-1]) if exr_out else rgba, jpeg, png=png, exr=exr)
             print("wrote", args.out, f"({arrays.n_tris} triangles, {spp or settings['samples']} spp)")
         return
     t0 = time.perf_counter()
@@ -283,7 +300,11 @@ def main(argv=None):
     if args.atrous > 0:
         pt.features(args.feature_samples, args.seed)
         pt.denoise(iterations=args.atrous)
-    if is_jpeg_path(args.out):  # drawn and encoded on the device: only the file comes back
+    if exr_guided and args.atrous <= 0:
+        pt.features(args.feature_samples, args.seed)
+    if exr_out:  # the radiance itself, and the guides, as a file made on the device
+        data = pt.draw_exr("denoised" if args.atrous > 0 else "accumulator", **exr)
+    elif is_jpeg_path(args.out):  # drawn and encoded on the device: only the file comes back
         data = pt.draw_jpeg("denoised" if args.atrous > 0 else "accumulator", args.exposure, args.saturation, args.denoise, **jpeg)
     elif args.png_gpu:
         data = pt.draw_png("denoised" if args.atrous > 0 else "accumulator", args.exposure, args.saturation, args.denoise)
@@ -292,9 +313,12 @@ def main(argv=None):
     else:
         rgba = pt.draw(args.exposure, args.saturation, args.denoise)
     print(f"{args.width}x{args.height} x {args.spp} spp in {dt:.3f} s = {samples / dt / 1e6:.0f} Msamples/s")
-    if args.hdr:
+    if exr_hdr:
+        with open(args.hdr, "wb") as f:
+            f.write(pt.draw_exr("accumulator", **exr))
+    elif args.hdr:
         np.save(args.hdr, pt.readRadiance())
-    if is_jpeg_path(args.out) or args.png_gpu:
+    if exr_out or is_jpeg_path(args.out) or args.png_gpu:
         with open(args.out, "wb") as f:
             f.write(data)
     else:

@@ -199,11 +199,38 @@ def is_jpeg_path(path):
     return str(path).lower().endswith((".jpg", ".jpeg"))
 
 
-def write_image(path, rgba, jpeg=None, device=0, png=None):
+def is_exr_path(path):
+    return str(path).lower().endswith(".exr")
+
+
+EXR_KEYS = ("compression", "float32", "layers", "chunk_bytes")
+
+
+def exr_settings(exr):
+    """None or a dict of tracer.exr_encode's compression / float32 / layers / chunk_bytes, checked: (the dict, its layer bits)"""
+    from .tracer import exr_params
+    exr = {} if exr is None else dict(exr)
+    if set(exr) - set(EXR_KEYS):
+        raise TypeError(f"unknown exr parameters {sorted(set(exr) - set(EXR_KEYS))}")
+    return exr, int(exr_params(**exr).layers)
+
+
+def write_image(path, rgba, jpeg=None, device=0, png=None, exr=None, features=None):
     """An RGBA8 frame [H, W, 4], row 0 = top, as the picture `path` names: .jpg / .jpeg = a baseline JPEG encoded on the GPU
     (tracer.jpeg_encode; jpeg = None or a dict of its quality / subsampling / restart_mcus), anything else
     through Pillow as before - unless png is "gpu" or a dict of tracer.png_encode's channels / filter / chunk_bytes: then the
-    PNG is filtered and deflated on the GPU."""
+    PNG is filtered and deflated on the GPU.  .exr = a scene-linear OpenEXR file made on the GPU
+    (tracer.exr_encode): `rgba` is then the float32 radiance [H, W, 4], row 0 = top, exr = None or a dict of its
+    compression / float32 / layers / chunk_bytes, features = the float32 guides [H, W, 8] its albedo, normal and depth
+    layers need."""
+    if is_exr_path(path):
+        from .tracer import exr_encode
+        if getattr(rgba, "dtype", None) != np.float32:
+            raise ValueError("write_image: an .exr takes the float32 radiance, not a drawn frame")
+        data = exr_encode(rgba, features, device=device, **exr_settings(exr)[0])
+        with open(path, "wb") as f:
+            f.write(data)
+        return
     if is_jpeg_path(path):
         from .tracer import jpeg_encode
         data = jpeg_encode(rgba, device=device, **(jpeg or {}))
@@ -319,7 +346,7 @@ def _sequence_sky(sky, k, n):
 
 
 def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", rebuild_above=None,
-                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, camera=None, sky=None, textures="cpu", jpeg=None, png=None, **kw):
+                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, camera=None, sky=None, textures="cpu", jpeg=None, png=None, exr=None, **kw):
     """frame=N sequencing (main.js:851-866, 966-969): for every N in `frames` load `scene_pattern.format(frame=N)`
     (the per-frame scene JSON the reference's server hands out for `?frame=N`), render it, write
     `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1.
@@ -369,7 +396,15 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     jpeg: an out_pattern that ends in .jpg / .jpeg is written as a JPEG encoded on the GPU (write_image); None
     or a dict of jpeg_encode's quality / subsampling / restart_mcus.
     png: None = every other out_pattern goes through Pillow; "gpu" or a dict of png_encode's channels / filter /
-    chunk_bytes = it is written as a PNG encoded on the GPU (write_image)."""
+    chunk_bytes = it is written as a PNG encoded on the GPU (write_image).
+    exr: an out_pattern that ends in .exr is written as a scene-linear OpenEXR file of the frame's radiance -
+    under bvh="refit" by PathTracer.draw_exr (the accumulator, or the temporal result), so that only the file leaves the
+    device; None or a dict of its compression / float32 / layers / chunk_bytes.  The albedo, normal and depth layers need
+    bvh="refit" (the live tracer's features)."""
+    as_exr = is_exr_path(out_pattern)
+    exr, exr_layers = exr_settings(exr)
+    if as_exr and bvh != "refit" and exr_layers & 14:
+        raise ValueError('render_sequence: the albedo, normal and depth layers of an .exr need bvh="refit"')
     if textures not in S.TEXTURE_PACKERS:
         raise ValueError(f"render_sequence: textures must be one of {S.TEXTURE_PACKERS}, not {textures!r}")
     camera = _camera_model_params(camera, kw.get("adaptive"), None if temporal is None or temporal is False else temporal)
@@ -403,10 +438,14 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     if variance and (temporal is None or atrous < 1):
         raise ValueError('render_sequence: variance needs temporal with "atrous" >= 1 (the variance guides the a-trous filter)')
 
-    def save(n, rgba):
+    def save(n, rgba, data=None):
         out = out_pattern.format(frame=n)
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-        write_image(out, rgba, jpeg, device, png)
+        if data is not None:  # a file made on the device
+            with open(out, "wb") as f:
+                f.write(data)
+        else:
+            write_image(out, rgba, jpeg, device, png, exr)
         written.append(out)
 
     if bvh != "refit":
@@ -414,10 +453,10 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
             arrays, settings = load_scene_file(scene_pattern.format(frame=n), asset_root, bvh=bvh, device=device, textures=textures)
             if sky is not None:
                 arrays = arrays_with_sky(arrays, device=device, **_sequence_sky(sky, len(written), n))
-            rgba, _ = render_frame(arrays, settings, width, height, auto_exposure=auto_exposure, bloom=bloom, camera=camera, **kw)
+            rgba, rad = render_frame(arrays, settings, width, height, auto_exposure=auto_exposure, bloom=bloom, camera=camera, **kw)
             if on_frame:
                 on_frame(n, "build")
-            save(n, rgba)
+            save(n, np.ascontiguousarray(rad[::-1]) if as_exr else rgba)
         return written
 
     from .tracer import PathTracer
@@ -511,7 +550,7 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                 pt.update_sky(**_sequence_sky(sky, len(written), n))
                 how = "sky" if how != "build" else how
             if temporal is None:
-                rgba, _ = _render_on(pt, settings, **opt)
+                rgba, _ = _render_on(pt, settings, **opt, draw=not as_exr)
             else:
                 _render_on(pt, settings, **{**opt, "seed": opt["seed"] + len(written), "denoise": False},
                            draw=auto_exposure is None)  # (its draw is not the frame; under auto-exposure it would adapt twice a frame)
@@ -523,10 +562,16 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                 elif atrous > 0:
                     pt.features(8, opt["seed"])
                     pt.temporal_denoise(iterations=atrous)
-                rgba = pt.temporal_draw(settings["exposure"], opt["saturation"], denoised=atrous > 0)
+                if not as_exr:
+                    rgba = pt.temporal_draw(settings["exposure"], opt["saturation"], denoised=atrous > 0)
             if on_frame:
                 on_frame(n, how)
-            save(n, rgba[::-1].copy())
+            if as_exr:
+                if exr_layers & 14 and not (temporal is not None and (variance or atrous > 0)):
+                    pt.features(8, opt["seed"])
+                save(n, None, pt.draw_exr("accumulator" if temporal is None else "temporal_denoised" if atrous > 0 else "temporal", **exr))
+            else:
+                save(n, rgba[::-1].copy())
     finally:
         if pt is not None:
             pt.close(); pt.scene.close()

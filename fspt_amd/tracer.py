@@ -462,6 +462,102 @@ def png_last_ms():
     return tuple(float(x) for x in ms), int(n.value)
 
 
+EXR_COMPRESSIONS = {"none": 0, "zips": 2, "zip": 3}
+EXR_LAYERS = {"alpha": 1, "albedo": 2, "normal": 4, "depth": 8}
+EXR_GUIDED = 2 | 4 | 8  # the layers that read the features
+
+
+def exr_params(compression="zip", float32=False, layers=(), chunk_bytes=0):
+    """L.ExrParams of the wrappers' keywords (fspt_exr_params).  compression: a name of EXR_COMPRESSIONS or its
+    number; float32: FLOAT channels, not HALF (Z is always FLOAT); layers: names of EXR_LAYERS (a sequence, or one string
+    with commas) or their bit set.  The library checks the ranges."""
+    if compression not in EXR_COMPRESSIONS and compression not in EXR_COMPRESSIONS.values():
+        raise ValueError(f"compression must be one of {sorted(EXR_COMPRESSIONS)}")
+    if isinstance(layers, str):
+        layers = [x for x in layers.split(",") if x]
+    if not isinstance(layers, int):
+        bad = [x for x in layers if x not in EXR_LAYERS]
+        if bad:
+            raise ValueError(f"layers must be among {sorted(EXR_LAYERS)}, not {bad}")
+        bits = 0
+        for x in layers:
+            bits |= EXR_LAYERS[x]
+        layers = bits
+    return L.ExrParams(EXR_COMPRESSIONS.get(compression, compression), 2 if float32 else 1, int(layers), int(chunk_bytes))
+
+
+def exr_bound(width, height, compression="zip", float32=False, layers=(), chunk_bytes=0):
+    """Bytes no OpenEXR file of this size and these settings exceeds (fspt_exr_bound; host only)"""
+    p, n = exr_params(compression, float32, layers, chunk_bytes), C.c_size_t()
+    L.check(L.lib().fspt_exr_bound(int(width), int(height), C.byref(p), C.byref(n)))
+    return int(n.value)
+
+
+class _ExrBuffer:
+    """The wrappers' reusable output buffer: fspt_exr_bound of the last size and settings, kept while it is large enough"""
+
+    def __init__(self):
+        self.buf = np.empty(0, np.uint8)
+
+    def call(self, w, h, p, fn):
+        b, n = C.c_size_t(), C.c_size_t()
+        L.check(L.lib().fspt_exr_bound(w, h, C.byref(p), C.byref(b)))
+        if self.buf.size < b.value:
+            self.buf = np.empty(int(b.value), np.uint8)
+        L.check(fn(L.u8ptr(self.buf), self.buf.size, C.byref(n)))
+        return self.buf[:int(n.value)].tobytes()
+
+
+_exr_buffer = _ExrBuffer()
+
+
+def exr_encode(rgba, features=None, compression="zip", float32=False, layers=(), chunk_bytes=0, bottom_up=False, device=0):
+    """A scanline OpenEXR file (bytes) of float32 radiance [H, W, 4] and, for the albedo, normal and depth layers, the
+    features [H, W, 8] as readFeatures() returns them, encoded on the GPU (fspt_exr_encode): numpy arrays, or
+    torch tensors on the device, which are read where they are (fspt_exr_encode_device).  bottom_up: row 0 is the bottom, as
+    every buffer of the library; the file's first scanline is the top."""
+    p = exr_params(compression, float32, layers, chunk_bytes)
+    on_dev = hasattr(rgba, "data_ptr") and getattr(rgba, "is_cuda", False)
+    if on_dev:
+        import torch
+        if rgba.dtype != torch.float32 or rgba.dim() != 3 or rgba.shape[2] != 4:
+            raise ValueError("rgba must be a float32 [H, W, 4] tensor")
+        rgba = rgba.contiguous()
+        if features is not None:
+            if not getattr(features, "is_cuda", False) or features.dtype != torch.float32 or tuple(features.shape) != (rgba.shape[0], rgba.shape[1], 8) or features.device != rgba.device:
+                raise ValueError("features must be a float32 [H, W, 8] tensor on the device of rgba")
+            features = features.contiguous()
+        device = rgba.device.index or 0
+        torch.cuda.current_stream(device).synchronize()  # whatever wrote the tensors has finished
+    else:
+        rgba = np.ascontiguousarray(rgba)
+        if rgba.dtype != np.float32 or rgba.ndim != 3 or rgba.shape[2] != 4:
+            raise ValueError("rgba must be a float32 [H, W, 4] array")
+        if features is not None:
+            features = np.ascontiguousarray(features)
+            if features.dtype != np.float32 or features.shape != (rgba.shape[0], rgba.shape[1], 8):
+                raise ValueError("features must be a float32 [H, W, 8] array")
+    h, w = int(rgba.shape[0]), int(rgba.shape[1])
+    lib, bu = L.lib(), 1 if bottom_up else 0
+    if on_dev:
+        f = C.c_void_p(features.data_ptr()) if features is not None else None
+        return _exr_buffer.call(w, h, p, lambda o, cap, nb: lib.fspt_exr_encode_device(int(device), C.c_void_p(rgba.data_ptr()), f, w, h, bu, C.byref(p), o, cap, nb))
+    f = L.fptr(features) if features is not None else None
+    return _exr_buffer.call(w, h, p, lambda o, cap, nb: lib.fspt_exr_encode(int(device), L.fptr(rgba), f, w, h, bu, C.byref(p), o, cap, nb))
+
+
+def exr_set_form(form):
+    """Where a block that falls back to raw takes its bytes from (fspt_exr_set_form): 0 = converted again, 1 = a kept copy"""
+    L.check(L.lib().fspt_exr_set_form(int(form)))
+
+
+def exr_last_ms():
+    """((rows ms, deflate ms, offsets + pack ms), bytes brought to the host) of the last exr_encode (fspt_exr_last_ms)"""
+    ms, n = (C.c_float * 3)(), C.c_uint64()
+    L.check(L.lib().fspt_exr_last_ms(ms, C.byref(n)))
+    return tuple(float(x) for x in ms), int(n.value)
+
+
 def light_alias_table(weights):
     """The Vose alias table (float32 prob, uint32 alias) the light table stores for these weights (fspt_light_alias_table,
     a pure host function: no device needed)."""
@@ -1485,6 +1581,19 @@ class PathTracer:
         n = buf.call(p, lambda o, cap, nb: lib.fspt_draw_png(self._t, JPEG_SOURCES[source], float(exposure), float(saturation), 1 if denoise else 0,
                                                              float(max_sigma), float(scale), C.byref(p), o, cap, nb))
         return buf.buf[:n].tobytes()
+
+    def draw_exr(self, source="accumulator", compression="zip", float32=False, layers=(), chunk_bytes=0):
+        """The HDR buffer itself - read_radiance()'s ("accumulator"), denoise()'s ("denoised"), temporal_accumulate()'s
+        ("temporal") or temporal_denoise()'s ("temporal_denoised") - as a scene-linear OpenEXR file (bytes), with the
+        first-hit guides of features() as layers ("albedo", "normal", "depth"; "alpha" is the buffer's fourth float),
+        made on the GPU: only the file comes back (fspt_draw_exr).  No exposure, bloom or tone map."""
+        if source not in JPEG_SOURCES:
+            raise ValueError(f"source must be one of {sorted(JPEG_SOURCES)}")
+        if getattr(self, "_exr_buf", None) is None:
+            self._exr_buf = _ExrBuffer()
+        p, lib = exr_params(compression, float32, layers, chunk_bytes), L.lib()
+        W, H = self.resolution
+        return self._exr_buf.call(W, H, p, lambda o, cap, nb: lib.fspt_draw_exr(self._t, JPEG_SOURCES[source], C.byref(p), o, cap, nb))
 
     def present_jpeg(self, exposure=1.0, saturation=1.0, denoise=False, max_sigma=3.0, scale=1.0, quality=85, subsampling="420", restart_mcus=0):
         """present() with the frame encoded on the GPU behind its draw (fspt_present_jpeg): (the PREVIOUS call's JPEG file as

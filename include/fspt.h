@@ -178,7 +178,7 @@ int fspt_draw_scaled(fspt_target *target, float exposure, float saturation, int 
 /* drawQuad inside tick() (main.js:838-857), pipelined with one frame of latency (DESIGN.md 4.3): enqueues the ticks recorded since the last flush and
  * fspt_draw_scaled's k_draw of the result, then writes the frame the PREVIOUS call enqueued to out_rgba8 and its sample count (1 + its newest tick index) to
  * *ticks_out, blocking only for that frame.  *ticks_out = 0: nothing to present (first call after a join; out untouched).  Every entry but fspt_camera and fspt_trace joins. */
-int fspt_present(fspt_target *t, float exposure, float saturation, int denoise, float max_sigma, float scale, uint8_t *out_rgba8, uint32_t *ticks_out); /* JPEG output: a baseline JFIF file (Annex K tables under libjpeg's quality rule, restart_mcus MCUs per restart interval, 0 = one MCU row) made on the GPU from an RGBA8 frame (alpha ignored; bottom_up: row 0 is the bottom, as fspt_draw writes it), byte for byte libjpeg's on the MCU grid; only the file crosses the bus. FSPT_E_INVALID before a device is touched: NULL, w or h of 0 or above 65535, quality outside 1..100, an unknown subsampling or source, restart_mcus above 65535. cap smaller than the file: FSPT_E_INVALID, *bytes_out = the size needed, out untouched. */ enum { FSPT_JPEG_444 = 0, FSPT_JPEG_420 = 1 }; typedef struct fspt_jpeg_params { uint32_t quality, subsampling, restart_mcus; } fspt_jpeg_params; /* NULL = 85, 420, 0 */ enum { FSPT_SOURCE_ACCUMULATOR = 0, FSPT_SOURCE_DENOISED = 1, FSPT_SOURCE_TEMPORAL = 2, FSPT_SOURCE_TEMPORAL_DENOISED = 3 }; int fspt_jpeg_bound(uint32_t w, uint32_t h, const fspt_jpeg_params *p, size_t *bytes); /* host only: no frame is longer */ int fspt_jpeg_encode(int device, const uint8_t *rgba8, uint32_t w, uint32_t h, int bottom_up, const fspt_jpeg_params *p, uint8_t *out, size_t cap, size_t *bytes_out); /* host pointers */ int fspt_jpeg_encode_device(int device, const uint8_t *rgba8, uint32_t w, uint32_t h, int bottom_up, const fspt_jpeg_params *p, uint8_t *out, size_t cap, size_t *bytes_out); /* rgba8 in device memory, out on the host */ /* fspt_draw_scaled (source ACCUMULATOR), fspt_draw_denoised (DENOISED; denoise, max_sigma and scale are not used) or fspt_temporal_draw (TEMPORAL, TEMPORAL_DENOISED) of the same arguments, with their errors, then fspt_jpeg_encode of that frame with bottom_up = 1; the frame stays on the device. */ int fspt_draw_jpeg(fspt_target *t, int source, float exposure, float saturation, int denoise, float max_sigma, float scale, const fspt_jpeg_params *p, uint8_t *out, size_t cap, size_t *bytes_out); /* fspt_present with the encode enqueued behind the draw: the PREVIOUS call's file, exactly *bytes_out bytes of it, and its sample count; *ticks_out = 0 and *bytes_out = 0: nothing to present. fspt_present and fspt_present_jpeg may alternate on a target: a call returns the previous frame only when the same entry enqueued it, otherwise it waits for that frame, drops it and returns ticks 0. A frame refused because cap is too small is dropped. */ int fspt_present_jpeg(fspt_target *t, float exposure, float saturation, int denoise, float max_sigma, float scale, const fspt_jpeg_params *p, uint8_t *out, size_t cap, size_t *bytes_out, uint32_t *ticks_out); /* PNG output: a lossless PNG file (8 bit, RGB = colour type 2 or RGBA = colour type 6 with straight alpha, no interlace) made on the GPU from an RGBA8 frame (bottom_up as above), byte for byte tests/png_ref.py's: the five filters with the smallest sum of signed magnitudes per row (or one fixed filter), then deflate in independent chunks of chunk_bytes of the filtered stream - literals and distance-1 matches under a dynamic Huffman code per chunk, a stored block where that is not shorter - one IDAT per chunk and one for the Adler-32.  Only the file crosses the bus.  FSPT_E_INVALID before a device is touched: NULL, w or h of 0 or above 65535, channels other than 0, 3, 4, a filter above FSPT_PNG_FILTER_ADAPTIVE, chunk_bytes other than 0 or 256..32768, an unknown source, a file that could pass 4 GiB.  cap smaller than the file: FSPT_E_INVALID, bytes_out = the size needed, out untouched. */ enum { FSPT_PNG_FILTER_NONE = 0, FSPT_PNG_FILTER_SUB = 1, FSPT_PNG_FILTER_UP = 2, FSPT_PNG_FILTER_AVERAGE = 3, FSPT_PNG_FILTER_PAETH = 4, FSPT_PNG_FILTER_ADAPTIVE = 5 }; typedef struct fspt_png_params { uint32_t channels, filter, chunk_bytes; } fspt_png_params; /* NULL = 3, adaptive, FSPT_PNG_CHUNK; channels 0 and chunk_bytes 0 = those defaults too */ int fspt_png_bound(uint32_t w, uint32_t h, const fspt_png_params *p, size_t *bytes); /* host only: no file is longer */ int fspt_png_encode(int device, const uint8_t *rgba8, uint32_t w, uint32_t h, int bottom_up, const fspt_png_params *p, uint8_t *out, size_t cap, size_t *bytes_out); /* host pointers */ int fspt_png_encode_device(int device, const uint8_t *rgba8, uint32_t w, uint32_t h, int bottom_up, const fspt_png_params *p, uint8_t *out, size_t cap, size_t *bytes_out); /* rgba8: device memory of `device`; out: host */ /* fspt_draw's frame (source, exposure .. scale as fspt_draw_jpeg's: auto-exposure and bloom take part) as a PNG file; blocking */ int fspt_draw_png(fspt_target *t, int source, float exposure, float saturation, int denoise, float max_sigma, float scale, const fspt_png_params *p, uint8_t *out, size_t cap, size_t *bytes_out);
+int fspt_present(fspt_target *t, float exposure, float saturation, int denoise, float max_sigma, float scale, uint8_t *out_rgba8, uint32_t *ticks_out); /* JPEG output (DESIGN 8.19): a baseline JFIF file (Annex K tables under libjpeg's quality rule, restart_mcus MCUs per restart interval, 0 = one MCU row) made on the GPU from an RGBA8 frame (alpha ignored; bottom_up: row 0 is the bottom, as fspt_draw writes it), byte for byte libjpeg's on the MCU grid; only the file crosses the bus. FSPT_E_INVALID before a device is touched: NULL, w or h of 0 or above 65535, quality outside 1..100, an unknown subsampling or source, restart_mcus above 65535. cap smaller than the file: FSPT_E_INVALID, *bytes_out = the size needed, out untouched. */ enum { FSPT_JPEG_444 = 0, FSPT_JPEG_420 = 1 }; typedef struct fspt_jpeg_params { uint32_t quality, subsampling, restart_mcus; } fspt_jpeg_params; /* NULL = 85, 420, 0 */ enum { FSPT_SOURCE_ACCUMULATOR = 0, FSPT_SOURCE_DENOISED = 1, FSPT_SOURCE_TEMPORAL = 2, FSPT_SOURCE_TEMPORAL_DENOISED = 3 }; int fspt_jpeg_bound(uint32_t w, uint32_t h, const fspt_jpeg_params *p, size_t *bytes); /* host only: no frame is longer */ int fspt_jpeg_encode(int device, const uint8_t *rgba8, uint32_t w, uint32_t h, int bottom_up, const fspt_jpeg_params *p, uint8_t *out, size_t cap, size_t *bytes_out); /* host pointers */ int fspt_jpeg_encode_device(int device, const uint8_t *rgba8, uint32_t w, uint32_t h, int bottom_up, const fspt_jpeg_params *p, uint8_t *out, size_t cap, size_t *bytes_out); /* rgba8 in device memory, out on the host */ /* fspt_draw_scaled (source ACCUMULATOR), fspt_draw_denoised (DENOISED; denoise, max_sigma and scale are not used) or fspt_temporal_draw (TEMPORAL, TEMPORAL_DENOISED) of the same arguments, with their errors, then fspt_jpeg_encode of that frame with bottom_up = 1; the frame stays on the device. */ int fspt_draw_jpeg(fspt_target *t, int source, float exposure, float saturation, int denoise, float max_sigma, float scale, const fspt_jpeg_params *p, uint8_t *out, size_t cap, size_t *bytes_out); /* fspt_present with the encode enqueued behind the draw: the PREVIOUS call's file, exactly *bytes_out bytes of it, and its sample count; *ticks_out = 0 and *bytes_out = 0: nothing to present. fspt_present and fspt_present_jpeg may alternate on a target: a call returns the previous frame only when the same entry enqueued it, otherwise it waits for that frame, drops it and returns ticks 0. A frame refused because cap is too small is dropped. */ int fspt_present_jpeg(fspt_target *t, float exposure, float saturation, int denoise, float max_sigma, float scale, const fspt_jpeg_params *p, uint8_t *out, size_t cap, size_t *bytes_out, uint32_t *ticks_out); /* PNG output (DESIGN 8.20): a lossless PNG file (8 bit, RGB = colour type 2 or RGBA = colour type 6 with straight alpha, no interlace) made on the GPU from an RGBA8 frame (bottom_up as above), byte for byte tests/png_ref.py's: the five filters with the smallest sum of signed magnitudes per row (or one fixed filter), then deflate in independent chunks of chunk_bytes of the filtered stream - literals and distance-1 matches under a dynamic Huffman code per chunk, a stored block where that is not shorter - one IDAT per chunk and one for the Adler-32.  Only the file crosses the bus.  FSPT_E_INVALID before a device is touched: NULL, w or h of 0 or above 65535, channels other than 0, 3, 4, a filter above FSPT_PNG_FILTER_ADAPTIVE, chunk_bytes other than 0 or 256..32768, an unknown source, a file that could pass 4 GiB.  cap smaller than the file: FSPT_E_INVALID, bytes_out = the size needed, out untouched. */ enum { FSPT_PNG_FILTER_NONE = 0, FSPT_PNG_FILTER_SUB = 1, FSPT_PNG_FILTER_UP = 2, FSPT_PNG_FILTER_AVERAGE = 3, FSPT_PNG_FILTER_PAETH = 4, FSPT_PNG_FILTER_ADAPTIVE = 5 }; typedef struct fspt_png_params { uint32_t channels, filter, chunk_bytes; } fspt_png_params; /* NULL = 3, adaptive, FSPT_PNG_CHUNK; channels 0 and chunk_bytes 0 = those defaults too */ int fspt_png_bound(uint32_t w, uint32_t h, const fspt_png_params *p, size_t *bytes); /* host only: no file is longer */ int fspt_png_encode(int device, const uint8_t *rgba8, uint32_t w, uint32_t h, int bottom_up, const fspt_png_params *p, uint8_t *out, size_t cap, size_t *bytes_out); /* host pointers */ int fspt_png_encode_device(int device, const uint8_t *rgba8, uint32_t w, uint32_t h, int bottom_up, const fspt_png_params *p, uint8_t *out, size_t cap, size_t *bytes_out); /* rgba8: device memory of `device`; out: host */ /* fspt_draw's frame (source, exposure .. scale as fspt_draw_jpeg's: auto-exposure and bloom take part) as a PNG file; blocking */ int fspt_draw_png(fspt_target *t, int source, float exposure, float saturation, int denoise, float max_sigma, float scale, const fspt_png_params *p, uint8_t *out, size_t cap, size_t *bytes_out); /* OpenEXR output (DESIGN 8.21): a single-part scanline OpenEXR 2 file made on the GPU from W*H*4 floats of scene-linear radiance (no exposure, bloom or tone map) and, for the feature layers, fspt_read_features' W*H*8 floats; byte for byte tests/exr_ref.py's.  Channels in file order, those present: A B G N.X N.Y N.Z R Z albedo.B albedo.G albedo.R.  R G B always; the others by `layers`.  Z (the first hit's distance, 1e5 for a miss) is always FLOAT, the rest take pixel_type.  A is the source's fourth float as stored: 1 in the accumulator and in a denoised buffer, the history length in a temporal one. HALF is round-to-nearest-even in integer arithmetic; every NaN becomes 0x7E00 / 0x7FC00000.  bottom_up: row 0 of the buffers is the bottom (as every library buffer); the file's scanline 0 is the top.  ZIP deflates blocks of 16 scanlines, ZIPS of one, each a zlib stream of its own cut into chunks of chunk_bytes; a block that deflate does not shorten is stored raw.  Only the file crosses the bus.  FSPT_E_INVALID before a device is touched: NULL (features only where a feature layer asks for them), w or h of 0 or above 65535, an unknown compression, pixel type, layer bit or source, chunk_bytes other than 0 or 256..32768, a file that could pass 4 GiB.  cap smaller than the file: FSPT_E_INVALID, *bytes_out = the size needed, out untouched. */ enum { FSPT_EXR_NONE = 0, FSPT_EXR_ZIPS = 2, FSPT_EXR_ZIP = 3 }; enum { FSPT_EXR_HALF = 1, FSPT_EXR_FLOAT = 2 }; enum { FSPT_EXR_ALPHA = 1, FSPT_EXR_ALBEDO = 2, FSPT_EXR_NORMAL = 4, FSPT_EXR_DEPTH = 8 }; typedef struct fspt_exr_params { uint32_t compression, pixel_type, layers, chunk_bytes; } fspt_exr_params; /* NULL = ZIP, HALF, 0 (RGB), FSPT_EXR_CHUNK; chunk_bytes 0 = that default too */ int fspt_exr_bound(uint32_t w, uint32_t h, const fspt_exr_params *p, size_t *bytes); /* host only: no file is longer */ int fspt_exr_encode(int device, const float *rgba, const float *features, uint32_t w, uint32_t h, int bottom_up, const fspt_exr_params *p, uint8_t *out, size_t cap, size_t *bytes_out); /* host pointers */ int fspt_exr_encode_device(int device, const float *rgba, const float *features, uint32_t w, uint32_t h, int bottom_up, const fspt_exr_params *p, uint8_t *out, size_t cap, size_t *bytes_out); /* rgba, features: device memory of `device`, 16-byte aligned; out: host */ /* The buffer `source` stands for (the accumulator, fspt_denoise's, fspt_temporal_accumulate's or fspt_temporal_denoise's result; FSPT_E_STATE as the entry that draws it) and, for feature layers, fspt_features' buffer (FSPT_E_STATE without one) as an OpenEXR file; blocking; joins a present. */ int fspt_draw_exr(fspt_target *t, int source, const fspt_exr_params *p, uint8_t *out, size_t cap, size_t *bytes_out);
 
 /* Guided denoiser (DESIGN.md 8; the reference lists "denoising" under post processing).  fspt_features: `samples` camera
  * rays per pixel of the whole target (k_camera's ray for randBase r_s, the s-th fspt_rand_base_next value from `seed`) to

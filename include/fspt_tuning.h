@@ -434,6 +434,14 @@ int fspt_jpeg_last_ms(float ms[3], uint64_t *bus_bytes);
 #define FSPT_PNG_CHUNK 16384u
 int fspt_png_filtered_eval(int device, const uint8_t *rgba8, uint32_t w, uint32_t h, int bottom_up, const fspt_png_params *p, uint8_t *stream_out);
 int fspt_png_last_ms(float ms[3], uint64_t *bus_bytes);
+/* OpenEXR encoder.  FSPT_EXR_CHUNK: the bytes of a block's predicted stream one deflate chunk (one workgroup)
+ * takes when fspt_exr_params.chunk_bytes is 0; 8.21 has the table it was chosen from.  fspt_exr_set_form: where a block that
+ * falls back to raw takes its bytes from - 0 (default) = k_exr_pack converts them again from the floats, 1 = k_exr_rows keeps
+ * a raw copy of every block next to the predicted one.  The files are the same.  fspt_exr_last_ms: the three stages (rows,
+ * deflate, offsets + pack) of the last fspt_exr_encode / _encode_device and the bytes that call brought to the host. */
+#define FSPT_EXR_CHUNK 8192u
+int fspt_exr_set_form(int form);
+int fspt_exr_last_ms(float ms[3], uint64_t *bus_bytes);
 
 #ifdef __cplusplus
 }

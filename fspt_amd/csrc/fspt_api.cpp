@@ -888,7 +888,7 @@ extern "C" int fspt_present_jpeg(fspt_target *t, float exposure, float saturatio
   // other parameters than the encoder's: its work buffers are made again, once the frame in flight is through with them
   if (t->pr_slot >= 0) {
     const fspt::JpegPlan &q = t->jp.pl;
-    if (t->jp.valid && !(q.quality == pl.quality && q.sub == pl.sub && q.ri == pl.ri)) HIP_TRY(hipEventSynchronize(t->pr_copied[t->pr_slot]));
+    if (t->jp.c.valid && !(q.quality == pl.quality && q.sub == pl.sub && q.ri == pl.ri)) HIP_TRY(hipEventSynchronize(t->pr_copied[t->pr_slot]));
   }
   HIP_TRY(fspt::jpeg_ensure(t->jp, pl, 2, fspt::jpeg_bound_max(t->W, t->H)));
   t->pr_active = true;
@@ -910,7 +910,7 @@ extern "C" int fspt_present_jpeg(fspt_target *t, float exposure, float saturatio
   if (prev >= 0) {
     HIP_TRY(hipEventSynchronize(t->pr_copied[prev]));
     if (t->pr_ticks[prev] && t->pr_kind[prev] == 1) { // (an RGBA8 frame fspt_present enqueued is dropped)
-      if ((rc = fspt::jpeg_deliver(t->jp.out[prev], *t->jp_count[prev], out, cap, bytes_out, t->jp_copy, fn))) return rc; // (cap too small: the frame is dropped)
+      if ((rc = fspt::enc_deliver(t->jp.c.out[prev], *t->jp_count[prev], out, cap, bytes_out, t->jp_copy, fn, fspt::g_jpeg_format))) return rc; // (cap too small: the frame is dropped)
       *ticks_out = t->pr_ticks[prev];
     }
   }

@@ -7,11 +7,12 @@
 //                   first half, the odd ones behind them, each minus the byte to its left in that order, which is a byte of
 //                   the value before it (the neighbouring pixel, the end of the channel before, the end of the scanline
 //                   before; at the seam the block's last even byte).  Compression none: the planar bytes into the file.
-//   k_png_deflate   (fspt_png.hip) a block is a segment: a zlib stream of its own, in chunks that restart at its first byte
+//   k_deflate       (fspt_deflate.hip) a block is a segment: a zlib stream of its own, in chunks that restart at its first byte
 //   k_exr_offsets   per block the chunks' lengths and Adler pairs combined, compressed or raw, a scan of the sizes in 64 bits:
 //                   the header, the offset table and every block's (y, size)
 //   k_exr_pack      one workgroup per chunk: its deflated bytes, or, where its block fell back, that range of the raw block
 #include "fspt_internal.hpp"
+#include "fspt_encode_device.hpp"
 
 namespace fspt {
 namespace {
@@ -175,14 +176,7 @@ __global__ void __launch_bounds__(256) k_exr_offsets(ExrOffP p) {
       }
     }
     const uint64_t v = i < p.n_blocks ? 8ull + size : 0ull;
-    s[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256u; d <<= 1) {
-      const uint64_t o = t >= d ? s[t - d] : 0ull;
-      __syncthreads();
-      s[t] += o;
-      __syncthreads();
-    }
+    enc_scan256(s, v);
     const uint64_t off = running + s[t] - v;
     if (i < p.n_blocks) {
       p.blk[2u * i] = off; p.blk[2u * i + 1u] = ((uint64_t)size << 32) | adler;
@@ -228,8 +222,6 @@ __global__ void __launch_bounds__(256) k_exr_pack(ExrPackP p, ExrRowsP r) {
   }
 }
 
-float g_exr_ms[3] = {0.0f, 0.0f, 0.0f};
-uint64_t g_exr_bus_bytes = 0;
 int g_exr_form = 0;
 
 struct HdrWriter {
@@ -312,43 +304,30 @@ static bool same_plan(const ExrPlan &a, const ExrPlan &b) {
   return a.w == b.w && a.h == b.h && a.compression == b.compression && a.pixel_type == b.pixel_type && a.layers == b.layers && a.cb == b.cb && a.form == b.form;
 }
 
-void exr_release(ExrEnc &e) {
-  hipFree(e.cfg); hipFree(e.stream); hipFree(e.raw); hipFree(e.scratch); hipFree(e.meta); hipFree(e.blk); hipFree(e.out);
-  for (hipEvent_t &ev : e.ev) { if (ev) hipEventDestroy(ev); ev = nullptr; }
-  e.cfg = nullptr; e.stream = nullptr; e.raw = nullptr; e.scratch = nullptr; e.meta = nullptr; e.chunk_off = nullptr; e.blk = nullptr; e.out = nullptr;
-  e.valid = false; e.out_bytes = 0;
-}
-
 hipError_t exr_ensure(ExrEnc &e, const ExrPlan &pl, size_t out_bytes) {
-  hipError_t err = hipSuccess;
-  if (!(e.out && e.out_bytes >= out_bytes)) {
-    hipFree(e.out); e.out = nullptr; e.out_bytes = 0;
-    err = hipMalloc((void **)&e.out, out_bytes);
-    if (err == hipSuccess) e.out_bytes = out_bytes;
-  }
-  for (hipEvent_t &ev : e.ev) if (!ev && err == hipSuccess) err = hipEventCreate(&ev);
-  if (err != hipSuccess || (e.valid && same_plan(e.pl, pl))) return err;
-  hipFree(e.cfg); hipFree(e.stream); hipFree(e.raw); hipFree(e.scratch); hipFree(e.meta); hipFree(e.blk);
-  e.cfg = nullptr; e.stream = nullptr; e.raw = nullptr; e.scratch = nullptr; e.meta = nullptr; e.chunk_off = nullptr; e.blk = nullptr; e.valid = false;
+  hipError_t err = enc_ensure_out(e.c, 1, out_bytes);
+  if (err != hipSuccess || (e.c.valid && same_plan(e.pl, pl))) return err;
+  enc_replan(e.c);
   const bool z = pl.compression != (uint32_t)FSPT_EXR_NONE;
-  err = hipMalloc((void **)&e.cfg, EXR_HEADER_MAX + sizeof pl.ch);
-  if (err == hipSuccess) err = hipMalloc((void **)&e.blk, ((size_t)pl.n_blocks * 2u + 1u) * 8u);
-  if (err == hipSuccess && z) err = hipMalloc((void **)&e.stream, pl.data_bytes + 8u);
-  if (err == hipSuccess && z && pl.form) err = hipMalloc((void **)&e.raw, pl.data_bytes + 8u);
-  if (err == hipSuccess && z) err = hipMalloc((void **)&e.scratch, (size_t)pl.n_chunks * pl.slot_bytes);
-  if (err == hipSuccess && z) err = hipMalloc((void **)&e.meta, (size_t)pl.n_chunks * (DEFLATE_META + 1u) * 4u);
+  enc_make(e.c, err, e.cfg, EXR_HEADER_MAX + sizeof pl.ch);
+  enc_make(e.c, err, e.blk, ((size_t)pl.n_blocks * 2u + 1u) * 8u);
+  enc_make(e.c, err, e.stream, pl.data_bytes + 8u, z);
+  enc_make(e.c, err, e.raw, pl.data_bytes + 8u, z && pl.form);
+  enc_make(e.c, err, e.scratch, (size_t)pl.n_chunks * pl.slot_bytes, z);
+  enc_make(e.c, err, e.meta, (size_t)pl.n_chunks * (DEFLATE_META + 1u) * 4u, z);
+  e.chunk_off = e.meta ? e.meta + (size_t)pl.n_chunks * DEFLATE_META : nullptr;
   if (err == hipSuccess) err = hipMemcpy(e.cfg, pl.hdr, pl.hdr_len, hipMemcpyHostToDevice);
   if (err == hipSuccess) err = hipMemcpy(e.cfg + EXR_HEADER_MAX, pl.ch, sizeof pl.ch, hipMemcpyHostToDevice);
   if (err != hipSuccess) return err;
-  e.chunk_off = z ? e.meta + (size_t)pl.n_chunks * DEFLATE_META : nullptr;
-  e.pl = pl; e.valid = true;
+  e.pl = pl; e.c.valid = true;
   return hipSuccess;
 }
 
-// The whole encode into e.out on `st`; the file's length lands in e.blk[2 n_blocks].  Events 0..3 bracket the three stages.
+// The whole encode into e.c.out[0] on `st`; the file's length lands in e.blk[2 n_blocks].  Events 0..3 bracket the three stages.
 hipError_t exr_launch(ExrEnc &e, const float4 *rgba, const float4 *feat, int bottom_up, hipStream_t st) {
   const ExrPlan &pl = e.pl;
   const bool z = pl.compression != (uint32_t)FSPT_EXR_NONE;
+  uint8_t *const out = e.c.out[0];
   ExrRowsP r{};
   r.rgba = (const uint4 *)rgba; r.feat = (const uint4 *)feat;
   r.w = pl.w; r.h = pl.h; r.bottom_up = bottom_up ? 1u : 0u; r.n_ch = pl.n_ch; r.lpb = pl.lpb;
@@ -357,46 +336,31 @@ hipError_t exr_launch(ExrEnc &e, const float4 *rgba, const float4 *feat, int bot
   r.ch = (const ExrChannel *)(e.cfg + EXR_HEADER_MAX);
   r.stream = e.stream;
   if (z) { r.raw = e.raw; r.raw_stride = pl.block_bytes; r.raw_skip = 0; }
-  else { r.raw = e.out; r.raw_stride = pl.line_bytes + 8u; r.raw_skip = (size_t)pl.hdr_len + 8u * (size_t)pl.n_blocks + 8u; } // straight into the file
-  hipError_t err = hipEventRecord(e.ev[0], st);
+  else { r.raw = out; r.raw_stride = pl.line_bytes + 8u; r.raw_skip = (size_t)pl.hdr_len + 8u * (size_t)pl.n_blocks + 8u; } // straight into the file
+  hipError_t err = hipEventRecord(e.c.ev[0], st);
   if (err != hipSuccess) return err;
   hipLaunchKernelGGL(k_exr_rows, dim3((pl.w + EXR_RT - 1u) / EXR_RT, pl.h), dim3(EXR_RT), 0, st, r);
   err = hipGetLastError();
-  if (err == hipSuccess) err = hipEventRecord(e.ev[1], st);
+  if (err == hipSuccess) err = hipEventRecord(e.c.ev[1], st);
   if (err == hipSuccess && z) {
     const DeflateP d{e.stream, pl.data_bytes, pl.block_bytes, pl.cb, pl.cps, 0u, e.scratch, pl.slot_bytes, e.meta}; // a segment per block
     err = deflate_launch(d, pl.n_chunks, st);
   }
-  if (err == hipSuccess) err = hipEventRecord(e.ev[2], st);
+  if (err == hipSuccess) err = hipEventRecord(e.c.ev[2], st);
   if (err != hipSuccess) return err;
-  const ExrOffP o{e.meta, e.cfg, pl.hdr_len, pl.n_blocks, pl.cps, pl.cb, pl.lpb, pl.h, (uint32_t)pl.line_bytes, z ? 1u : 0u, e.chunk_off, e.blk, e.out};
+  const ExrOffP o{e.meta, e.cfg, pl.hdr_len, pl.n_blocks, pl.cps, pl.cb, pl.lpb, pl.h, (uint32_t)pl.line_bytes, z ? 1u : 0u, e.chunk_off, e.blk, out};
   hipLaunchKernelGGL(k_exr_offsets, dim3(1), dim3(256), 0, st, o);
   if (z) {
-    const ExrPackP k{e.meta, e.chunk_off, e.blk, e.scratch, pl.slot_bytes, pl.cps, pl.cb, pl.form, e.out};
+    const ExrPackP k{e.meta, e.chunk_off, e.blk, e.scratch, pl.slot_bytes, pl.cps, pl.cb, pl.form, out};
     hipLaunchKernelGGL(k_exr_pack, dim3(pl.n_chunks), dim3(256), 0, st, k, r);
   }
   err = hipGetLastError();
-  if (err == hipSuccess) err = hipEventRecord(e.ev[3], st);
+  if (err == hipSuccess) err = hipEventRecord(e.c.ev[3], st);
   return err;
 }
 
 int exr_collect(ExrEnc &e, hipStream_t st, uint8_t *out, size_t cap, size_t *bytes_out, const char *fn) {
-  uint64_t n = 0;
-  hipError_t err = hipMemcpyAsync(&n, e.blk + 2u * (size_t)e.pl.n_blocks, 8, hipMemcpyDeviceToHost, st);
-  if (err == hipSuccess) err = hipStreamSynchronize(st);
-  if (err != hipSuccess) { fspt_set_error("%s: %s", fn, hipGetErrorString(err)); return FSPT_E_HIP; }
-  *bytes_out = (size_t)n;
-  if (cap < n) { fspt_set_error("%s: the file takes %llu bytes, the buffer holds %zu", fn, (unsigned long long)n, cap); return FSPT_E_INVALID; }
-  err = hipMemcpyAsync(out, e.out, (size_t)n, hipMemcpyDeviceToHost, st);
-  if (err == hipSuccess) err = hipStreamSynchronize(st);
-  if (err != hipSuccess) { fspt_set_error("%s: %s", fn, hipGetErrorString(err)); return FSPT_E_HIP; }
-  g_exr_bus_bytes = n + 8u;
-  return FSPT_OK;
-}
-
-void exr_note_ms(ExrEnc &e) {
-  for (int k = 0; k < 3; ++k) if (hipEventElapsedTime(&g_exr_ms[k], e.ev[k], e.ev[k + 1]) != hipSuccess) g_exr_ms[k] = 0.0f;
-  (void)hipGetLastError();
+  return enc_collect(e.blk + 2u * (size_t)e.pl.n_blocks, e.c.out[0], out, cap, bytes_out, st, fn, g_exr_format);
 }
 
 } // namespace fspt
@@ -406,45 +370,33 @@ static int exr_encode_any(const char *fn, int device, const float *rgba, const f
                           const fspt_exr_params *p, uint8_t *out, size_t cap, size_t *bytes_out) {
   if (!rgba || !out || !bytes_out) { fspt_set_error("%s: NULL argument", fn); return FSPT_E_INVALID; }
   fspt::ExrPlan pl;
-  int rc = fspt::exr_plan(p, w, h, true, fn, pl);
+  const int rc = fspt::exr_plan(p, w, h, true, fn, pl);
   if (rc) return rc;
   const bool guided = (pl.layers & ((uint32_t)FSPT_EXR_ALBEDO | (uint32_t)FSPT_EXR_NORMAL | (uint32_t)FSPT_EXR_DEPTH)) != 0u;
   if (guided && !features) { fspt_set_error("%s: feature layers need the features", fn); return FSPT_E_INVALID; }
-  if (fspt_device_count() <= 0) { fspt_set_error("%s: no HIP device available; libfspt has no CPU fallback", fn); return FSPT_E_NO_DEVICE; }
-  if ((rc = check_device(device))) return rc;
   fspt::ExrEnc e;
-  fspt::Hold hold;
-  const size_t px = (size_t)w * h;
-  const float4 *src = (const float4 *)rgba, *feat = guided ? (const float4 *)features : nullptr;
-  hipError_t err = fspt::exr_ensure(e, pl, pl.bound);
-  if (err == hipSuccess && !on_device) {
-    void *d = nullptr;
-    err = hold.make(&d, px * (guided ? 48u : 16u));
-    if (err == hipSuccess) err = hipMemcpy(d, rgba, px * 16u, hipMemcpyHostToDevice);
-    if (err == hipSuccess && guided) err = hipMemcpy((char *)d + px * 16u, features, px * 32u, hipMemcpyHostToDevice);
-    src = (const float4 *)d; feat = guided ? src + px : nullptr;
-  }
-  if (err == hipSuccess) err = fspt::exr_launch(e, src, feat, bottom_up, nullptr);
-  if (err != hipSuccess) {
-    (void)hipDeviceSynchronize(); (void)hipGetLastError();
-    fspt_set_error("%s: %s", fn, hipGetErrorString(err));
-    rc = err == hipErrorOutOfMemory ? FSPT_E_NOMEM : FSPT_E_HIP;
-  } else {
-    rc = fspt::exr_collect(e, nullptr, out, cap, bytes_out, fn);
-    if (rc == FSPT_OK || rc == FSPT_E_INVALID) fspt::exr_note_ms(e);
-  }
-  fspt::exr_release(e);
-  return rc;
+  const auto launch = [&](fspt::Hold &hold) {
+    const size_t px = (size_t)w * h;
+    const float4 *src = (const float4 *)rgba, *feat = guided ? (const float4 *)features : nullptr;
+    hipError_t err = hipSuccess;
+    if (!on_device) { // one buffer: the radiance, the features behind it
+      void *d = nullptr;
+      err = hold.make(&d, px * (guided ? 48u : 16u));
+      if (err == hipSuccess) err = hipMemcpy(d, rgba, px * 16u, hipMemcpyHostToDevice);
+      if (err == hipSuccess && guided) err = hipMemcpy((char *)d + px * 16u, features, px * 32u, hipMemcpyHostToDevice);
+      src = (const float4 *)d; feat = guided ? src + px : nullptr;
+    }
+    if (err == hipSuccess) err = fspt::exr_launch(e, src, feat, bottom_up, nullptr);
+    return err;
+  };
+  return fspt::enc_run(fn, device, e.c, fspt::g_exr_format, [&] { return fspt::exr_ensure(e, pl, pl.bound); }, launch,
+                       [&] { return fspt::exr_collect(e, nullptr, out, cap, bytes_out, fn); });
 }
 
 extern "C" {
 
 int fspt_exr_bound(uint32_t w, uint32_t h, const fspt_exr_params *p, size_t *bytes) {
-  if (!bytes) { fspt_set_error("fspt_exr_bound: NULL argument"); return FSPT_E_INVALID; }
-  fspt::ExrPlan pl;
-  const int rc = fspt::exr_plan(p, w, h, false, "fspt_exr_bound", pl);
-  if (rc == FSPT_OK) *bytes = pl.bound;
-  return rc;
+  return fspt::enc_bound<fspt::ExrPlan>("fspt_exr_bound", bytes, [&](fspt::ExrPlan &pl) { return fspt::exr_plan(p, w, h, false, "fspt_exr_bound", pl); });
 }
 
 int fspt_exr_encode(int device, const float *rgba, const float *features, uint32_t w, uint32_t h, int bottom_up, const fspt_exr_params *p, uint8_t *out, size_t cap, size_t *bytes_out) {
@@ -461,11 +413,6 @@ int fspt_exr_set_form(int form) {
   return FSPT_OK;
 }
 
-int fspt_exr_last_ms(float ms[3], uint64_t *bus_bytes) {
-  if (!ms) { fspt_set_error("fspt_exr_last_ms: NULL argument"); return FSPT_E_INVALID; }
-  std::memcpy(ms, fspt::g_exr_ms, sizeof fspt::g_exr_ms);
-  if (bus_bytes) *bus_bytes = fspt::g_exr_bus_bytes;
-  return FSPT_OK;
-}
+int fspt_exr_last_ms(float ms[3], uint64_t *bus_bytes) { return fspt::enc_last_ms(fspt::g_exr_format, "fspt_exr_last_ms", ms, bus_bytes); }
 
 } // extern "C"

@@ -7,6 +7,7 @@
 //   fspt_sched_batch.cpp   the batch scheduler of the wavefront pipeline (render_wavefront) and its path state
 //   fspt_sched_stream.cpp  the stream scheduler (render_stream): a fixed pool of live paths
 //   fspt_multi.cpp         one frame over several devices (fspt_multi_*), tile pack / unpack, the optional RCCL exchange
+//   fspt_encode.cpp        what the three encoders' host halves share: output buffers and events, delivery, stage times, the stand-alone sequence
 //   scene_build.cpp        the native scene builder (OBJ / MTL / SAH BVH; no GPU)
 // and the device side, declared in fspt_device.hpp:
 //   fspt_kernels.hip       the renderers: the path tracer's two execution strategies, k_bvh_test, k_tile_pack, the light table
@@ -18,7 +19,8 @@
 //   fspt_sky.hip           the sky generator and the environment's importance bins, built on the GPU
 //   fspt_jpeg.hip          the baseline JPEG encoder behind fspt_jpeg_encode, fspt_draw_jpeg and fspt_present_jpeg, and its stand-alone entries
 //   fspt_png.hip           the PNG encoder behind fspt_png_encode and fspt_draw_png, and its stand-alone entries
-//   fspt_exr.hip           the OpenEXR encoder behind fspt_exr_encode and fspt_draw_exr; its deflate is fspt_png.hip's kernel (deflate_launch)
+//   fspt_exr.hip           the OpenEXR encoder behind fspt_exr_encode and fspt_draw_exr, and its stand-alone entries
+//   fspt_deflate.hip       the deflate of the last two (deflate_launch);  fspt_encode_device.hpp  the offsets kernels' scan
 #pragma once
 #include "../../include/fspt.h"
 #include "../../include/fspt_tuning.h"
@@ -36,6 +38,7 @@
 #include <cmath>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 void fspt_set_error(const char *fmt, ...);
@@ -207,7 +210,8 @@ void appearance_release(fspt_scene *s);
 // device buffers of a transaction: freed unless taken
 struct Hold {
   std::vector<void *> p;
-  ~Hold() { for (void *q : p) hipFree(q); }
+  ~Hold() { clear(); }
+  void clear() { for (void *q : p) hipFree(q); p.clear(); }
   hipError_t make(void **dst, size_t bytes) {
     *dst = nullptr;
     const hipError_t e = hipMalloc(dst, bytes ? bytes : 16);
@@ -245,6 +249,70 @@ int env_box_sums_run(const uint8_t *rgbe, uint32_t w, uint32_t h, const uint32_t
 // then are the scene's buffers swapped and s->sky filled in.
 int environment_gpu(fspt_scene *s, const char *fn, const uint8_t *env, bool env_on_device, const fspt_sky_params *sky, uint32_t w, uint32_t h);
 void sky_release(fspt_scene *s);
+// fspt_encode.cpp: what the host halves of the three encoders below share.  EncCommon: the part of an encoder's
+// device memory that does not depend on the format - the output buffers, which only grow and outlive a change of the
+// parameters, the events around the three stages of the last launch, and `work`, the owner of every buffer made for the
+// current plan (the encoders keep typed pointers into it, made by enc_make and good while `valid`).  EncFormat: what delivery and the
+// fspt_*_last_ms entries know of a format.
+struct EncCommon {
+  bool valid = false; // `work` holds the buffers of the encoder's plan
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  uint8_t *out[2] = {nullptr, nullptr};
+  size_t out_bytes = 0; // of every out[k] that is there
+  Hold work;
+};
+struct EncFormat {
+  const char *noun;   // what a buffer too small is told it cannot hold: "frame" or "file"
+  uint32_t len_bytes; // the device's length word: 4 or 8 bytes
+  float ms[3];        // the stage times of the last stand-alone encode
+  uint64_t bus_bytes; // what its delivery brought to the host: the file and its length word
+};
+extern EncFormat g_jpeg_format, g_png_format, g_exr_format;
+hipError_t enc_ensure_out(EncCommon &c, int n_out, size_t out_bytes); // n_out buffers of at least out_bytes, and the events; nothing of `c` may be in use
+void enc_replan(EncCommon &c);                                        // the work buffers go: a new plan makes its own
+void enc_release(EncCommon &c);
+// *bytes_out = n; cap < n: FSPT_E_INVALID, out untouched; else n bytes of dev copied on st, which is waited for
+int enc_deliver(const uint8_t *dev, uint64_t n, uint8_t *out, size_t cap, size_t *bytes_out, hipStream_t st, const char *fn, EncFormat &f);
+// what every blocking entry ends with: the length word at len_dev is read on st, st is waited for, then enc_deliver
+int enc_collect(const void *len_dev, const uint8_t *dev, uint8_t *out, size_t cap, size_t *bytes_out, hipStream_t st, const char *fn, EncFormat &f);
+int enc_last_ms(const EncFormat &f, const char *fn, float ms[3], uint64_t *bus_bytes);
+void enc_note_ms(const EncCommon &c, EncFormat &f); // the stage times of a finished launch, for fspt_*_last_ms
+// A stand-alone entry behind its NULL checks and its plan: the device, `ensure`, `launch` (uploads what is on the host into
+// buffers of the Hold, then launches), `collect` - whose stage times are noted when it returns FSPT_OK or FSPT_E_INVALID -
+// and the release of `c`.  The stage-one forms have nothing to collect: their launch copies back, and they pass nullptr.
+int enc_enter(const char *fn, int device);                   // a device at all, then this one
+int enc_fail(const char *fn, hipError_t err);                // the device is drained, the error set: FSPT_E_NOMEM or FSPT_E_HIP
+template <class Ensure, class Launch, class Collect>
+int enc_run(const char *fn, int device, EncCommon &c, EncFormat &f, Ensure ensure, Launch launch, Collect collect) {
+  int rc = enc_enter(fn, device);
+  if (rc) return rc;
+  Hold hold;
+  hipError_t err = ensure();
+  if (err == hipSuccess) err = launch(hold);
+  if (err != hipSuccess) rc = enc_fail(fn, err);
+  else if constexpr (!std::is_same<Collect, std::nullptr_t>::value) {
+    rc = collect();
+    if (rc == FSPT_OK || rc == FSPT_E_INVALID) enc_note_ms(c, f);
+  }
+  enc_release(c);
+  return rc;
+}
+// a work buffer of the plan being made in its typed pointer, which stays NULL when the plan does not want it or an earlier one failed
+template <class P>
+void enc_make(EncCommon &c, hipError_t &err, P *&ptr, size_t bytes, bool wanted = true) {
+  ptr = nullptr;
+  if (wanted && err == hipSuccess) err = c.work.make((void **)&ptr, bytes);
+}
+hipError_t enc_upload(Hold &hold, const void *host, size_t bytes, const void **dev); // *dev: a buffer of the Hold with the host's bytes
+// fspt_*_bound: plan(pl) validates; no device touched
+template <class Plan, class F>
+int enc_bound(const char *fn, size_t *bytes, F plan) {
+  if (!bytes) { fspt_set_error("%s: NULL argument", fn); return FSPT_E_INVALID; }
+  Plan pl;
+  const int rc = plan(pl);
+  if (rc == FSPT_OK) *bytes = pl.bound;
+  return rc;
+}
 // fspt_jpeg.hip: the baseline JPEG encoder.  JpegPlan: what follows from a size and checked parameters, on the
 // host.  JpegEnc: the device memory of one encoder - the header and divisors of its plan, the work buffers, up to two
 // output buffers - owned by a target (fspt_draw_jpeg, fspt_present_jpeg) or by one stand-alone call.
@@ -257,14 +325,11 @@ struct JpegPlan {
 };
 struct JpegEnc {
   JpegPlan pl{};
-  bool valid = false;
+  EncCommon c;
   uint8_t *cfg = nullptr;     // 128 uint16 divisors | the header
   int16_t *coef = nullptr;    // stage one's output
   uint8_t *scratch = nullptr; // n_int slots
   uint32_t *len = nullptr, *off = nullptr; // per interval: bytes | where it lands; off[n_int] = the file's length
-  uint8_t *out[2] = {nullptr, nullptr};
-  size_t out_bytes = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the three stages of the last launch
 };
 int jpeg_check_params(const fspt_jpeg_params *prm, const char *fn); // the parameters alone (a target's entries: before the handle is looked at)
 int jpeg_plan(const fspt_jpeg_params *prm, uint32_t w, uint32_t h, const char *fn, JpegPlan &pl); // validates: FSPT_E_INVALID, no device touched
@@ -272,14 +337,10 @@ size_t jpeg_bound_max(uint32_t w, uint32_t h);                                  
 hipError_t jpeg_ensure(JpegEnc &e, const JpegPlan &pl, int n_out, size_t out_bytes);              // nothing of `e` may be in use
 hipError_t jpeg_launch_blocks(JpegEnc &e, const uint32_t *rgba, int bottom_up, hipStream_t st);
 hipError_t jpeg_launch(JpegEnc &e, const uint32_t *rgba, int bottom_up, int slot, hipStream_t st); // no host read, no synchronisation
-int jpeg_deliver(const uint8_t *dev, uint32_t n, uint8_t *out, size_t cap, size_t *bytes_out, hipStream_t st, const char *fn); // *bytes_out = n; cap < n: FSPT_E_INVALID, out untouched; else n bytes copied on st, which is waited for
-int jpeg_collect(JpegEnc &e, int slot, hipStream_t st, uint8_t *out, size_t cap, size_t *bytes_out, const char *fn); // waits for st, then jpeg_deliver
-void jpeg_note_ms(JpegEnc &e);  // the stage times of a finished launch, for fspt_jpeg_last_ms
-void jpeg_release(JpegEnc &e);
-// fspt_png.hip: the PNG encoder, laid out as the JPEG one.  PngPlan: what follows from a size and checked
-// parameters, on the host.  PngEnc: the device memory of one encoder - the signature and IHDR of its plan, the filtered
-// stream, a scratch slot and a record (bytes, CRC-32, Adler pair) per chunk, one output buffer - owned by a target
-// (fspt_draw_png) or by one stand-alone call.
+int jpeg_collect(JpegEnc &e, int slot, hipStream_t st, uint8_t *out, size_t cap, size_t *bytes_out, const char *fn);
+// fspt_png.hip: the PNG encoder.  PngPlan: what follows from a size and checked parameters, on the host.
+// PngEnc: the device memory of one encoder - the signature and IHDR of its plan, the filtered stream, a scratch slot and a
+// record (bytes, CRC-32, Adler pair) per chunk, one output buffer - owned by a target (fspt_draw_png) or by one stand-alone call.
 static const uint32_t PNG_HEADER_BYTES = 33u; // signature and IHDR
 struct PngPlan {
   uint32_t w, h, channels, filter, cb; // cb: the bytes of the filtered stream per chunk
@@ -290,30 +351,26 @@ struct PngPlan {
 };
 struct PngEnc {
   PngPlan pl{};
-  bool valid = false;
+  EncCommon c;
   uint8_t *cfg = nullptr;     // the header
   uint8_t *stream = nullptr;  // stage one's output
   uint8_t *scratch = nullptr; // n_chunks slots
   uint32_t *meta = nullptr, *off = nullptr; // per chunk: 4 words | where its IDAT lands; off[n_chunks + 1] = the file's length
-  uint8_t *out = nullptr;
-  size_t out_bytes = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the three stages of the last launch
 };
 int png_check_params(const fspt_png_params *prm, const char *fn); // the parameters alone (a target's entry: before the handle is looked at)
 int png_plan(const fspt_png_params *prm, uint32_t w, uint32_t h, bool for_device, const char *fn, PngPlan &pl); // validates: FSPT_E_INVALID, no device touched; for_device: the file must stay below 4 GiB
 size_t png_bound_max(uint32_t w, uint32_t h, uint32_t cb);                             // the largest bound of any parameters with chunks of cb
-hipError_t png_ensure(PngEnc &e, const PngPlan &pl, bool with_out, size_t out_bytes); // nothing of `e` may be in use
+hipError_t png_ensure(PngEnc &e, const PngPlan &pl, int n_out, size_t out_bytes);     // nothing of `e` may be in use
 hipError_t png_launch_filter(PngEnc &e, const uint32_t *rgba, int bottom_up, hipStream_t st);
 hipError_t png_launch(PngEnc &e, const uint32_t *rgba, int bottom_up, hipStream_t st); // no host read, no synchronisation
-int png_collect(PngEnc &e, hipStream_t st, uint8_t *out, size_t cap, size_t *bytes_out, const char *fn); // waits for st, then jpeg_deliver's rules
-void png_note_ms(PngEnc &e);  // the stage times of a finished launch, for fspt_png_last_ms
-void png_release(PngEnc &e);
-// The deflate both encoders share (k_png_deflate, fspt_png.hip): `stream` is n_seg segments of seg_bytes one behind the
+int png_collect(PngEnc &e, hipStream_t st, uint8_t *out, size_t cap, size_t *bytes_out, const char *fn);
+// fspt_deflate.hip: the deflate both encoders share (k_deflate): `stream` is n_seg segments of seg_bytes one behind the
 // other (the last holds what is left of stream_bytes), each one zlib stream of its own, cut into chunks of cb from its first
 // byte: chunk k is chunk k % cps of segment k / cps.  The first chunk of a segment carries the zlib header, the last one
 // BFINAL; a chunk's bytes land in its scratch slot and (bytes, CRC-32 of its IDAT when `crc`, Adler A, B) in its 4 words of
 // `meta`.  PNG is one segment: seg_bytes = stream_bytes, cps = n_chunks.
 static const uint32_t DEFLATE_META = 4u, DEFLATE_CHUNK_MIN = 256u, DEFLATE_CHUNK_MAX = 32768u, DEFLATE_ADLER = 65521u;
+static const uint32_t DEFLATE_CHUNK_EXTRA = 12u; // beyond a chunk's own bytes: the zlib header (2), a stored header (5) and the empty stored block (5) at the most
 struct DeflateP {
   const uint8_t *stream;
   size_t stream_bytes, seg_bytes;
@@ -324,10 +381,10 @@ struct DeflateP {
 };
 size_t deflate_slot_bytes(uint32_t cb);
 hipError_t deflate_launch(const DeflateP &p, uint32_t n_chunks, hipStream_t st);
-// fspt_exr.hip: the OpenEXR encoder, laid out as the PNG one.  ExrPlan: what follows from a size and checked
-// parameters, on the host.  ExrEnc: the device memory of one encoder - the header of its plan, the predicted stream and the
-// raw bytes of every block, the deflate's slots and records, a record per block, one output buffer - owned by a target
-// (fspt_draw_exr) or by one stand-alone call.
+// fspt_exr.hip: the OpenEXR encoder.  ExrPlan: what follows from a size and checked parameters, on the host.
+// ExrEnc: the device memory of one encoder - the header of its plan, the predicted stream and the raw bytes of every block,
+// the deflate's slots and records, a record per block, one output buffer - owned by a target (fspt_draw_exr) or by one
+// stand-alone call.
 static const uint32_t EXR_MAX_CHANNELS = 11u, EXR_HEADER_MAX = 512u;
 struct ExrChannel { uint32_t src, bytes, off; }; // src: 0..3 = the rgba float, 4..11 = the feature float src - 4; off: in units of w bytes within a scanline
 struct ExrPlan {
@@ -340,22 +397,17 @@ struct ExrPlan {
 };
 struct ExrEnc {
   ExrPlan pl{};
-  bool valid = false;
+  EncCommon c;
   uint8_t *cfg = nullptr;                    // the header
   uint8_t *stream = nullptr, *raw = nullptr; // the deflate's input | the same blocks as they are (form 1)
   uint8_t *scratch = nullptr;
   uint32_t *meta = nullptr, *chunk_off = nullptr; // per chunk: 4 words | where its bytes start in its block's data
   uint64_t *blk = nullptr;                        // per block: the block's offset in the file, (size << 32 | Adler-32); blk[2 n_blocks] = the file's length
-  uint8_t *out = nullptr;
-  size_t out_bytes = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 int exr_plan(const fspt_exr_params *prm, uint32_t w, uint32_t h, bool for_device, const char *fn, ExrPlan &pl); // validates: FSPT_E_INVALID, no device touched
 hipError_t exr_ensure(ExrEnc &e, const ExrPlan &pl, size_t out_bytes);                 // nothing of `e` may be in use
 hipError_t exr_launch(ExrEnc &e, const float4 *rgba, const float4 *feat, int bottom_up, hipStream_t st); // no host read, no synchronisation
 int exr_collect(ExrEnc &e, hipStream_t st, uint8_t *out, size_t cap, size_t *bytes_out, const char *fn);
-void exr_note_ms(ExrEnc &e);
-void exr_release(ExrEnc &e);
 // fspt_pose.hip.  pose_run: s->pose set, s->rf.stage allocated, the call ordered against the targets;
 // mats_host = n_parts x 30 floats (a | D | N).  Uploads them, runs k_pose_transform into s->rf.stage and waits.
 int pose_run(fspt_scene *s, const float *mats_host);
@@ -606,13 +658,13 @@ struct fspt_target {
   hipEvent_t bl_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // down chain | tail | up chain | draw of the last bloomed draw
   bool bl_timed = false;
   // JPEG output (fspt_draw_jpeg / fspt_present_jpeg): allocated on first use.  Under present a slot holds either
-  // fspt_present's RGBA8 frame (pr_host) or fspt_present_jpeg's file (jp.out[slot], its length in jp_count[slot])
+  // fspt_present's RGBA8 frame (pr_host) or fspt_present_jpeg's file (jp.c.out[slot], its length in jp_count[slot])
   fspt::JpegEnc jp;
-  uint32_t *jp_frame = nullptr;               // fspt_draw_jpeg's and fspt_draw_png's drawn frame, W*H texels
+  uint32_t *enc_frame = nullptr;              // fspt_draw_jpeg's and fspt_draw_png's drawn frame, W*H texels
   fspt::PngEnc pg;                            // PNG output (fspt_draw_png): allocated on first use
-  uint32_t pg_cb = 0;                         // the smallest chunk size fspt_draw_png was asked for: pg.out is sized for it
+  uint32_t pg_cb = 0;                         // the smallest chunk size fspt_draw_png was asked for: pg.c.out[0] is sized for it
   fspt::ExrEnc ex;                            // OpenEXR output (fspt_draw_exr): allocated on first use
-  size_t ex_bound = 0;                        // the largest bound fspt_draw_exr was asked for: ex.out is sized for it
+  size_t ex_bound = 0;                        // the largest bound fspt_draw_exr was asked for: ex.c.out[0] is sized for it
   uint32_t *jp_count[2] = {nullptr, nullptr}; // pinned host memory: a slot's byte count, current behind pr_copied[slot]
   int pr_kind[2] = {0, 0};                    // 0: an RGBA8 frame, 1: a JPEG file
   hipStream_t jp_copy = nullptr;              // a present file's bytes come to the host here: the copy waits for no stream that holds the next frame

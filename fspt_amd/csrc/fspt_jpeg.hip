@@ -10,6 +10,7 @@
 //   k_jpeg_offsets      a scan of the interval lengths (each followed by a 2-byte marker): where every interval lands
 //   k_jpeg_pack         header and intervals into one contiguous stream, RSTn between them, EOI, the byte count
 #include "fspt_internal.hpp"
+#include "fspt_encode_device.hpp"
 #include "fspt_jpeg_tables.hpp"
 
 namespace fspt {
@@ -250,14 +251,7 @@ __global__ void __launch_bounds__(256) k_jpeg_offsets(const uint32_t *__restrict
   for (uint32_t base = 0; base < n; base += 256u) {
     const uint32_t i = base + t;
     const uint32_t v = i < n ? len[i] + 2u : 0u;
-    s[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256u; d <<= 1) {
-      const uint32_t o = t >= d ? s[t - d] : 0u;
-      __syncthreads();
-      s[t] += o;
-      __syncthreads();
-    }
+    enc_scan256(s, v);
     const uint32_t r = running;
     if (i < n) off[i] = r + s[t] - v;
     __syncthreads();
@@ -283,9 +277,6 @@ void put_segment(std::vector<uint8_t> &o, uint8_t marker, const std::vector<uint
   o.push_back(0xFF); o.push_back(marker); o.push_back((uint8_t)(n >> 8)); o.push_back((uint8_t)n);
   o.insert(o.end(), payload.begin(), payload.end());
 }
-
-float g_jpeg_ms[3] = {0.0f, 0.0f, 0.0f};
-uint64_t g_jpeg_bus_bytes = 0;
 
 } // namespace
 
@@ -354,42 +345,26 @@ static bool same_plan(const JpegPlan &a, const JpegPlan &b) {
   return a.w == b.w && a.h == b.h && a.quality == b.quality && a.sub == b.sub && a.ri == b.ri;
 }
 
-void jpeg_release(JpegEnc &e) {
-  hipFree(e.cfg); hipFree(e.coef); hipFree(e.scratch); hipFree(e.len);
-  for (uint8_t *&o : e.out) { hipFree(o); o = nullptr; }
-  for (hipEvent_t &ev : e.ev) { if (ev) hipEventDestroy(ev); ev = nullptr; }
-  e.cfg = nullptr; e.coef = nullptr; e.scratch = nullptr; e.len = nullptr; e.off = nullptr;
-  e.valid = false; e.out_bytes = 0;
-}
-
 // The encoder's device memory for `pl`: the header and divisors once per (size, parameters), the work buffers, and n_out
 // output buffers of out_bytes each (>= pl.bound; they outlive a change of the parameters).  Nothing of it may be in use.
 hipError_t jpeg_ensure(JpegEnc &e, const JpegPlan &pl, int n_out, size_t out_bytes) {
-  hipError_t err = hipSuccess;
-  for (int k = 0; k < n_out && err == hipSuccess; ++k) {
-    if (e.out[k] && e.out_bytes >= out_bytes) continue;
-    hipFree(e.out[k]); e.out[k] = nullptr;
-    err = hipMalloc((void **)&e.out[k], out_bytes);
-  }
-  if (err == hipSuccess) e.out_bytes = std::max(e.out_bytes, out_bytes);
-  for (hipEvent_t &ev : e.ev) if (!ev && err == hipSuccess) err = hipEventCreate(&ev);
-  if (err != hipSuccess || (e.valid && same_plan(e.pl, pl))) return err;
-  hipFree(e.cfg); hipFree(e.coef); hipFree(e.scratch); hipFree(e.len);
-  e.cfg = nullptr; e.coef = nullptr; e.scratch = nullptr; e.len = nullptr; e.valid = false;
+  hipError_t err = enc_ensure_out(e.c, n_out, out_bytes);
+  if (err != hipSuccess || (e.c.valid && same_plan(e.pl, pl))) return err;
+  enc_replan(e.c);
   std::vector<uint8_t> hdr;
   uint16_t q[128];
   jpeg_header(pl, hdr, q);
   if (hdr.size() != JPEG_HEADER_BYTES) return hipErrorInvalidValue; // (fspt_jpeg_bound counts on it)
   const size_t blocks8 = ((size_t)pl.n_blocks + 7u) / 8u * 8u;      // k_jpeg_blocks stores whole waves of live blocks only; padded all the same
-  err = hipMalloc((void **)&e.cfg, 256 + hdr.size());
-  if (err == hipSuccess) err = hipMalloc((void **)&e.coef, blocks8 * 128u);
-  if (err == hipSuccess) err = hipMalloc((void **)&e.scratch, (size_t)pl.n_int * pl.slot_bytes);
-  if (err == hipSuccess) err = hipMalloc((void **)&e.len, ((size_t)pl.n_int * 2u + 1u) * 4u);
+  enc_make(e.c, err, e.cfg, 256 + hdr.size());
+  enc_make(e.c, err, e.coef, blocks8 * 128u);
+  enc_make(e.c, err, e.scratch, (size_t)pl.n_int * pl.slot_bytes);
+  enc_make(e.c, err, e.len, ((size_t)pl.n_int * 2u + 1u) * 4u);
+  e.off = e.len ? e.len + pl.n_int : nullptr;
   if (err == hipSuccess) err = hipMemcpy(e.cfg, q, 256, hipMemcpyHostToDevice);
   if (err == hipSuccess) err = hipMemcpy(e.cfg + 256, hdr.data(), hdr.size(), hipMemcpyHostToDevice);
   if (err != hipSuccess) return err;
-  e.off = e.len + pl.n_int;
-  e.pl = pl; e.valid = true;
+  e.pl = pl; e.c.valid = true;
   return hipSuccess;
 }
 
@@ -402,94 +377,58 @@ hipError_t jpeg_launch_blocks(JpegEnc &e, const uint32_t *rgba, int bottom_up, h
   return hipGetLastError();
 }
 
-// The whole encode of `rgba` (device memory, w x h texels) into e.out[slot] on `st`; the file's length lands in
+// The whole encode of `rgba` (device memory, w x h texels) into e.c.out[slot] on `st`; the file's length lands in
 // e.off[n_int].  Events 0..3 bracket the three stages.  No host read, no synchronisation.
 hipError_t jpeg_launch(JpegEnc &e, const uint32_t *rgba, int bottom_up, int slot, hipStream_t st) {
   const JpegPlan &pl = e.pl;
-  hipError_t err = hipEventRecord(e.ev[0], st);
+  hipError_t err = hipEventRecord(e.c.ev[0], st);
   if (err == hipSuccess) err = jpeg_launch_blocks(e, rgba, bottom_up, st);
-  if (err == hipSuccess) err = hipEventRecord(e.ev[1], st);
+  if (err == hipSuccess) err = hipEventRecord(e.c.ev[1], st);
   if (err != hipSuccess) return err;
   JpegEntropyP en{e.coef, pl.n_mcu, pl.ri, pl.bpm, e.scratch, pl.slot_bytes, e.len};
   hipLaunchKernelGGL(k_jpeg_entropy, dim3(pl.n_int), dim3(64), 0, st, en);
   err = hipGetLastError();
-  if (err == hipSuccess) err = hipEventRecord(e.ev[2], st);
+  if (err == hipSuccess) err = hipEventRecord(e.c.ev[2], st);
   if (err != hipSuccess) return err;
   hipLaunchKernelGGL(k_jpeg_offsets, dim3(1), dim3(256), 0, st, (const uint32_t *)e.len, pl.n_int, JPEG_HEADER_BYTES, e.off);
   hipLaunchKernelGGL(k_jpeg_pack, dim3(pl.n_int), dim3(256), 0, st, (const uint8_t *)e.cfg + 256, JPEG_HEADER_BYTES, (const uint8_t *)e.scratch, pl.slot_bytes,
-                     (const uint32_t *)e.len, (const uint32_t *)e.off, pl.n_int, e.out[slot]);
+                     (const uint32_t *)e.len, (const uint32_t *)e.off, pl.n_int, e.c.out[slot]);
   err = hipGetLastError();
-  if (err == hipSuccess) err = hipEventRecord(e.ev[3], st);
+  if (err == hipSuccess) err = hipEventRecord(e.c.ev[3], st);
   return err;
 }
 
-// What every blocking entry ends with: `st` is waited for, the length is read, and exactly that many bytes are copied
 int jpeg_collect(JpegEnc &e, int slot, hipStream_t st, uint8_t *out, size_t cap, size_t *bytes_out, const char *fn) {
-  uint32_t n = 0;
-  hipError_t err = hipMemcpyAsync(&n, e.off + e.pl.n_int, 4, hipMemcpyDeviceToHost, st);
-  if (err == hipSuccess) err = hipStreamSynchronize(st);
-  if (err != hipSuccess) { fspt_set_error("%s: %s", fn, hipGetErrorString(err)); return FSPT_E_HIP; }
-  return jpeg_deliver(e.out[slot], n, out, cap, bytes_out, st, fn);
-}
-
-int jpeg_deliver(const uint8_t *dev, uint32_t n, uint8_t *out, size_t cap, size_t *bytes_out, hipStream_t st, const char *fn) {
-  *bytes_out = n;
-  if (cap < n) { fspt_set_error("%s: the frame takes %u bytes, the buffer holds %zu", fn, n, cap); return FSPT_E_INVALID; }
-  hipError_t err = hipMemcpyAsync(out, dev, n, hipMemcpyDeviceToHost, st);
-  if (err == hipSuccess) err = hipStreamSynchronize(st);
-  if (err != hipSuccess) { fspt_set_error("%s: %s", fn, hipGetErrorString(err)); return FSPT_E_HIP; }
-  g_jpeg_bus_bytes = (uint64_t)n + 4u;
-  return FSPT_OK;
-}
-
-void jpeg_note_ms(JpegEnc &e) {
-  for (int k = 0; k < 3; ++k) if (hipEventElapsedTime(&g_jpeg_ms[k], e.ev[k], e.ev[k + 1]) != hipSuccess) g_jpeg_ms[k] = 0.0f;
-  (void)hipGetLastError();
+  return enc_collect(e.off + e.pl.n_int, e.c.out[slot], out, cap, bytes_out, st, fn, g_jpeg_format);
 }
 
 } // namespace fspt
 
-// The stand-alone entries: NULL and range checks first, then the device.  coef_out: fspt_jpeg_coefficients_eval's form.
+// The stand-alone entries: NULL and range checks first, then the device.  coef_out: fspt_jpeg_coefficients_eval's form,
+// stage one alone and its coefficients copied back.
 static int jpeg_encode_any(const char *fn, int device, const uint8_t *rgba8, bool on_device, uint32_t w, uint32_t h, int bottom_up,
                            const fspt_jpeg_params *p, uint8_t *out, size_t cap, size_t *bytes_out, int16_t *coef_out) {
   if (!rgba8 || (coef_out ? false : !out || !bytes_out)) { fspt_set_error("%s: NULL argument", fn); return FSPT_E_INVALID; }
   fspt::JpegPlan pl;
-  int rc = fspt::jpeg_plan(p, w, h, fn, pl);
+  const int rc = fspt::jpeg_plan(p, w, h, fn, pl);
   if (rc) return rc;
-  if (fspt_device_count() <= 0) { fspt_set_error("%s: no HIP device available; libfspt has no CPU fallback", fn); return FSPT_E_NO_DEVICE; }
-  if ((rc = check_device(device))) return rc;
   fspt::JpegEnc e;
-  fspt::Hold hold;
-  const uint32_t *src = (const uint32_t *)rgba8;
-  hipError_t err = fspt::jpeg_ensure(e, pl, coef_out ? 0 : 1, pl.bound);
-  if (err == hipSuccess && !on_device) {
-    void *d = nullptr;
-    err = hold.make(&d, (size_t)w * h * 4);
-    if (err == hipSuccess) err = hipMemcpy(d, rgba8, (size_t)w * h * 4, hipMemcpyHostToDevice);
-    src = (const uint32_t *)d;
-  }
-  if (err == hipSuccess) err = coef_out ? fspt::jpeg_launch_blocks(e, src, bottom_up, nullptr) : fspt::jpeg_launch(e, src, bottom_up, 0, nullptr);
-  if (err == hipSuccess && coef_out) err = hipMemcpy(coef_out, e.coef, (size_t)pl.n_blocks * 128u, hipMemcpyDeviceToHost);
-  if (err != hipSuccess) {
-    (void)hipDeviceSynchronize(); (void)hipGetLastError();
-    fspt_set_error("%s: %s", fn, hipGetErrorString(err));
-    rc = err == hipErrorOutOfMemory ? FSPT_E_NOMEM : FSPT_E_HIP;
-  } else if (!coef_out) {
-    rc = fspt::jpeg_collect(e, 0, nullptr, out, cap, bytes_out, fn);
-    if (rc == FSPT_OK || rc == FSPT_E_INVALID) fspt::jpeg_note_ms(e);
-  }
-  fspt::jpeg_release(e);
-  return rc;
+  const auto launch = [&](fspt::Hold &hold) {
+    const void *src = rgba8;
+    hipError_t err = on_device ? hipSuccess : fspt::enc_upload(hold, rgba8, (size_t)w * h * 4, &src);
+    if (err == hipSuccess) err = coef_out ? fspt::jpeg_launch_blocks(e, (const uint32_t *)src, bottom_up, nullptr) : fspt::jpeg_launch(e, (const uint32_t *)src, bottom_up, 0, nullptr);
+    if (err == hipSuccess && coef_out) err = hipMemcpy(coef_out, e.coef, (size_t)pl.n_blocks * 128u, hipMemcpyDeviceToHost);
+    return err;
+  };
+  const auto ensure = [&] { return fspt::jpeg_ensure(e, pl, coef_out ? 0 : 1, pl.bound); };
+  if (coef_out) return fspt::enc_run(fn, device, e.c, fspt::g_jpeg_format, ensure, launch, nullptr);
+  return fspt::enc_run(fn, device, e.c, fspt::g_jpeg_format, ensure, launch, [&] { return fspt::jpeg_collect(e, 0, nullptr, out, cap, bytes_out, fn); });
 }
 
 extern "C" {
 
 int fspt_jpeg_bound(uint32_t w, uint32_t h, const fspt_jpeg_params *p, size_t *bytes) {
-  if (!bytes) { fspt_set_error("fspt_jpeg_bound: NULL argument"); return FSPT_E_INVALID; }
-  fspt::JpegPlan pl;
-  const int rc = fspt::jpeg_plan(p, w, h, "fspt_jpeg_bound", pl);
-  if (rc == FSPT_OK) *bytes = pl.bound;
-  return rc;
+  return fspt::enc_bound<fspt::JpegPlan>("fspt_jpeg_bound", bytes, [&](fspt::JpegPlan &pl) { return fspt::jpeg_plan(p, w, h, "fspt_jpeg_bound", pl); });
 }
 
 int fspt_jpeg_encode(int device, const uint8_t *rgba8, uint32_t w, uint32_t h, int bottom_up, const fspt_jpeg_params *p, uint8_t *out, size_t cap, size_t *bytes_out) {
@@ -505,11 +444,6 @@ int fspt_jpeg_coefficients_eval(int device, const uint8_t *rgba8, uint32_t w, ui
   return jpeg_encode_any("fspt_jpeg_coefficients_eval", device, rgba8, false, w, h, bottom_up, p, nullptr, 0, nullptr, coef_out);
 }
 
-int fspt_jpeg_last_ms(float ms[3], uint64_t *bus_bytes) {
-  if (!ms) { fspt_set_error("fspt_jpeg_last_ms: NULL argument"); return FSPT_E_INVALID; }
-  std::memcpy(ms, fspt::g_jpeg_ms, sizeof fspt::g_jpeg_ms);
-  if (bus_bytes) *bus_bytes = fspt::g_jpeg_bus_bytes;
-  return FSPT_OK;
-}
+int fspt_jpeg_last_ms(float ms[3], uint64_t *bus_bytes) { return fspt::enc_last_ms(fspt::g_jpeg_format, "fspt_jpeg_last_ms", ms, bus_bytes); }
 
 } // extern "C"

@@ -838,7 +838,7 @@ int fspt_bloom_eval(int device, const float *rgba, uint32_t W, uint32_t H, uint3
 }
 
 // ---------------------------------------------------------------------------
-// JPEG output (fspt_jpeg.hip)
+// Encoded output: JPEG (fspt_jpeg.hip), PNG (8.20; fspt_png.hip), OpenEXR (8.21; fspt_exr.hip)
 // ---------------------------------------------------------------------------
 // fspt_draw_jpeg's and fspt_draw_png's frame: that of the entry the source stands for, refused as that entry refuses it
 static int encoded_source(fspt_target *t, int source, const float4 *&src, int &denoise, float &max_sigma, float &scale) {
@@ -855,63 +855,68 @@ static int encoded_source(fspt_target *t, int source, const float4 *&src, int &d
   return FSPT_OK;
 }
 
+} // extern "C"
+
+// what every fspt_draw_<format> starts with
+static int encoded_args(const fspt_target *t, int source, const uint8_t *out, const size_t *bytes_out, const char *fn) {
+  if (!t || !out || !bytes_out) { fspt_set_error("%s: NULL argument", fn); return FSPT_E_INVALID; }
+  if (source < FSPT_SOURCE_ACCUMULATOR || source > FSPT_SOURCE_TEMPORAL_DENOISED) { fspt_set_error("%s: unknown source %d", fn, source); return FSPT_E_INVALID; }
+  return FSPT_OK;
+}
+
+// fspt_draw_jpeg and fspt_draw_png up to the collect: the refusals in their order - arguments, `check` (the parameters alone),
+// the scale, the pipeline, `plan`, the source's state - then `ensure`, the frame drawn into t->enc_frame, `launch` on t->stream
+template <class Check, class Plan, class Ensure, class Launch>
+static int draw_encoded(fspt_target *t, const char *fn, int source, float exposure, float saturation, int denoise, float max_sigma, float scale,
+                        const uint8_t *out, const size_t *bytes_out, Check check, Plan plan, Ensure ensure, Launch launch) {
+  int rc = encoded_args(t, source, out, bytes_out, fn);
+  if (rc || (rc = check())) return rc;
+  if (source == FSPT_SOURCE_ACCUMULATOR && !(scale > 0.0f && scale <= 1.0f)) { fspt_set_error("%s: scale must be in (0, 1]", fn); return FSPT_E_INVALID; }
+  if ((rc = dn_enter(t, true, fn))) return rc; // (joins a present: nothing of the encoders is in use behind it)
+  if ((rc = plan())) return rc;
+  const float4 *src = nullptr;
+  if ((rc = encoded_source(t, source, src, denoise, max_sigma, scale))) return rc;
+  if (!t->enc_frame) HIP_TRY(hipMalloc((void **)&t->enc_frame, (size_t)t->W * t->H * 4));
+  hipError_t e = ensure();
+  if (e == hipSuccess) e = draw_launch(t, src, exposure, saturation, denoise, max_sigma, scale, t->enc_frame, t->stream);
+  if (e == hipSuccess) e = launch();
+  return e == hipSuccess ? FSPT_OK : hip_fail(fn, e);
+}
+
+extern "C" {
+
 int fspt_draw_jpeg(fspt_target *t, int source, float exposure, float saturation, int denoise, float max_sigma, float scale,
                    const fspt_jpeg_params *p, uint8_t *out, size_t cap, size_t *bytes_out) {
   const char *fn = "fspt_draw_jpeg";
-  if (!t || !out || !bytes_out) { fspt_set_error("%s: NULL argument", fn); return FSPT_E_INVALID; }
-  if (source < FSPT_SOURCE_ACCUMULATOR || source > FSPT_SOURCE_TEMPORAL_DENOISED) { fspt_set_error("%s: unknown source %d", fn, source); return FSPT_E_INVALID; }
-  int rc = fspt::jpeg_check_params(p, fn);
-  if (rc) return rc;
-  if (source == FSPT_SOURCE_ACCUMULATOR && !(scale > 0.0f && scale <= 1.0f)) { fspt_set_error("%s: scale must be in (0, 1]", fn); return FSPT_E_INVALID; }
-  if ((rc = dn_enter(t, true, fn))) return rc; // (joins a present: nothing of t->jp is in use behind it)
   fspt::JpegPlan pl;
-  if ((rc = fspt::jpeg_plan(p, t->W, t->H, fn, pl))) return rc;
-  const float4 *src = nullptr;
-  if ((rc = encoded_source(t, source, src, denoise, max_sigma, scale))) return rc;
-  if (!t->jp_frame) HIP_TRY(hipMalloc((void **)&t->jp_frame, (size_t)t->W * t->H * 4));
-  hipError_t e = fspt::jpeg_ensure(t->jp, pl, 1, fspt::jpeg_bound_max(t->W, t->H));
-  if (e == hipSuccess) e = draw_launch(t, src, exposure, saturation, denoise, max_sigma, scale, t->jp_frame, t->stream);
-  if (e == hipSuccess) e = fspt::jpeg_launch(t->jp, t->jp_frame, 1, 0, t->stream);
-  if (e != hipSuccess) return hip_fail(fn, e);
-  return fspt::jpeg_collect(t->jp, 0, t->stream, out, cap, bytes_out, fn);
+  const int rc = draw_encoded(t, fn, source, exposure, saturation, denoise, max_sigma, scale, out, bytes_out,
+                              [&] { return fspt::jpeg_check_params(p, fn); }, [&] { return fspt::jpeg_plan(p, t->W, t->H, fn, pl); },
+                              [&] { return fspt::jpeg_ensure(t->jp, pl, 1, fspt::jpeg_bound_max(t->W, t->H)); },
+                              [&] { return fspt::jpeg_launch(t->jp, t->enc_frame, 1, 0, t->stream); });
+  return rc ? rc : fspt::jpeg_collect(t->jp, 0, t->stream, out, cap, bytes_out, fn);
 }
 
-// ---------------------------------------------------------------------------
-// PNG output (fspt_png.hip)
-// ---------------------------------------------------------------------------
 int fspt_draw_png(fspt_target *t, int source, float exposure, float saturation, int denoise, float max_sigma, float scale,
                   const fspt_png_params *p, uint8_t *out, size_t cap, size_t *bytes_out) {
   const char *fn = "fspt_draw_png";
-  if (!t || !out || !bytes_out) { fspt_set_error("%s: NULL argument", fn); return FSPT_E_INVALID; }
-  if (source < FSPT_SOURCE_ACCUMULATOR || source > FSPT_SOURCE_TEMPORAL_DENOISED) { fspt_set_error("%s: unknown source %d", fn, source); return FSPT_E_INVALID; }
-  int rc = fspt::png_check_params(p, fn);
-  if (rc) return rc;
-  if (source == FSPT_SOURCE_ACCUMULATOR && !(scale > 0.0f && scale <= 1.0f)) { fspt_set_error("%s: scale must be in (0, 1]", fn); return FSPT_E_INVALID; }
-  if ((rc = dn_enter(t, true, fn))) return rc;
   fspt::PngPlan pl;
-  if ((rc = fspt::png_plan(p, t->W, t->H, true, fn, pl))) return rc;
-  const float4 *src = nullptr;
-  if ((rc = encoded_source(t, source, src, denoise, max_sigma, scale))) return rc;
-  if (!t->jp_frame) HIP_TRY(hipMalloc((void **)&t->jp_frame, (size_t)t->W * t->H * 4));
-  // the output buffer: the bound of RGBA at the smallest chunk size asked for so far; it grows, and outlives a change of the parameters
-  t->pg_cb = t->pg_cb ? std::min(t->pg_cb, pl.cb) : pl.cb;
-  hipError_t e = fspt::png_ensure(t->pg, pl, true, fspt::png_bound_max(t->W, t->H, t->pg_cb));
-  if (e == hipSuccess) e = draw_launch(t, src, exposure, saturation, denoise, max_sigma, scale, t->jp_frame, t->stream);
-  if (e == hipSuccess) e = fspt::png_launch(t->pg, t->jp_frame, 1, t->stream);
-  if (e != hipSuccess) return hip_fail(fn, e);
-  return fspt::png_collect(t->pg, t->stream, out, cap, bytes_out, fn);
+  const int rc = draw_encoded(t, fn, source, exposure, saturation, denoise, max_sigma, scale, out, bytes_out,
+                              [&] { return fspt::png_check_params(p, fn); }, [&] { return fspt::png_plan(p, t->W, t->H, true, fn, pl); },
+                              [&] { // the output buffer: the bound of RGBA at the smallest chunk size asked for so far; it grows, and outlives a change of the parameters
+                                t->pg_cb = t->pg_cb ? std::min(t->pg_cb, pl.cb) : pl.cb;
+                                return fspt::png_ensure(t->pg, pl, 1, fspt::png_bound_max(t->W, t->H, t->pg_cb));
+                              },
+                              [&] { return fspt::png_launch(t->pg, t->enc_frame, 1, t->stream); });
+  return rc ? rc : fspt::png_collect(t->pg, t->stream, out, cap, bytes_out, fn);
 }
 
-// ---------------------------------------------------------------------------
-// OpenEXR output (fspt_exr.hip): the HDR buffer itself, no draw in front of it
-// ---------------------------------------------------------------------------
+// OpenEXR: the HDR buffer itself, no draw in front of it; the plan before the pipeline, the features' state last
 int fspt_draw_exr(fspt_target *t, int source, const fspt_exr_params *p, uint8_t *out, size_t cap, size_t *bytes_out) {
   const char *fn = "fspt_draw_exr";
-  if (!t || !out || !bytes_out) { fspt_set_error("%s: NULL argument", fn); return FSPT_E_INVALID; }
-  if (source < FSPT_SOURCE_ACCUMULATOR || source > FSPT_SOURCE_TEMPORAL_DENOISED) { fspt_set_error("%s: unknown source %d", fn, source); return FSPT_E_INVALID; }
-  fspt::ExrPlan pl;
-  int rc = fspt::exr_plan(p, t->W, t->H, true, fn, pl);
+  int rc = encoded_args(t, source, out, bytes_out, fn);
   if (rc) return rc;
+  fspt::ExrPlan pl;
+  if ((rc = fspt::exr_plan(p, t->W, t->H, true, fn, pl))) return rc;
   if ((rc = dn_enter(t, true, fn))) return rc; // (joins a present)
   const float4 *src = nullptr;
   int denoise = 0; float max_sigma = 0.0f, scale = 1.0f;
@@ -933,7 +938,7 @@ void post_release(fspt_target *t) {
   hipFree(t->feat); hipFree(t->dn_tmp[0]); hipFree(t->dn_tmp[1]); hipFree(t->dn_out);
   hipFree(t->tm_hist[0]); hipFree(t->tm_hist[1]); hipFree(t->tm_g[0]); hipFree(t->tm_g[1]); hipFree(t->tm_m);
   sv_free(t); cl_free(t); ax_free(t); bl_free(t);
-  fspt::jpeg_release(t->jp); fspt::png_release(t->pg); fspt::exr_release(t->ex); hipFree(t->jp_frame);
+  fspt::enc_release(t->jp.c); fspt::enc_release(t->pg.c); fspt::enc_release(t->ex.c); hipFree(t->enc_frame);
   for (uint32_t *c : t->jp_count) if (c) hipHostFree(c);
   if (t->jp_copy) hipStreamDestroy(t->jp_copy);
   for (hipEvent_t ev : t->tm_ev) if (ev) hipEventDestroy(ev);

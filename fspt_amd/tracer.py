@@ -315,58 +315,90 @@ def jpeg_bound(width, height, quality=85, subsampling="420", restart_mcus=0):
     return int(n.value)
 
 
-class _JpegBuffer:
-    """The wrappers' reusable output buffer: W*H*4 + 1024 bytes, grown to fspt_jpeg_bound (the PNG wrappers': fspt_png_bound)
-    when a call reports a need"""
+def _host_image(a, dtype, channels, name):
+    a = np.ascontiguousarray(a)
+    if a.dtype != np.dtype(dtype) or a.ndim != 3 or a.shape[2] != channels:
+        raise ValueError(f"{name} must be a {dtype} [H, W, {channels}] array")
+    return a
 
-    def __init__(self, width, height, bound="fspt_jpeg_bound"):
-        self.size, self.bound = (int(width), int(height)), bound
-        self.buf = np.empty(self.size[0] * self.size[1] * 4 + 1024, np.uint8)
 
-    def call(self, p, fn):
-        """fn(out pointer, cap, byref(bytes)) -> rc, repeated once with a buffer of the bound when the first was too small"""
+def _image_arg(a, dtype, channels, name, device, sync=True):
+    """(the image, whether it is on the device, the device) of an encoder's input: a `dtype` [H, W, channels] numpy array,
+    made contiguous, or a torch tensor on the device, made contiguous, with its device's index and its stream synchronised
+    (sync=False: the caller has more tensors to copy and synchronises behind the last one)"""
+    if not (hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)):
+        return _host_image(a, dtype, channels, name), False, device
+    import torch
+    if a.dtype != getattr(torch, dtype) or a.dim() != 3 or a.shape[2] != channels:
+        raise ValueError(f"{name} must be a {dtype} [H, W, {channels}] tensor")
+    a = a.contiguous()
+    device = a.device.index or 0
+    if sync:
+        torch.cuda.current_stream(device).synchronize()  # whatever wrote the tensor, the copy above included, has finished
+    return a, True, device
+
+
+class _FileBuffer:
+    """The wrappers' reusable output buffer of one format; bound: the name of its fspt_*_bound.  JPEG and PNG: W*H*4 + 1024
+    bytes of the last size, grown to the bound when a call reports a need.  bound_first (OpenEXR): the bound of the call's
+    size and settings before the call, kept while it is large enough."""
+
+    def __init__(self, bound, bound_first=False):
+        self.bound, self.bound_first = bound, bound_first
+        self.size, self.buf = None, np.empty(0, np.uint8)
+
+    def grow(self, w, h, p, need=0):
+        """at least the bound of (w, h, p) and `need` bytes"""
+        b = C.c_size_t()
+        L.check(getattr(L.lib(), self.bound)(w, h, C.byref(p), C.byref(b)))
+        if self.buf.size < max(int(b.value), int(need)):
+            self.buf = np.empty(max(int(b.value), int(need)), np.uint8)
+
+    def ready(self, w, h, p):
+        """the buffer a call of this size and these settings starts with"""
+        if self.bound_first:
+            self.grow(w, h, p)
+        elif self.size != (w, h):
+            self.size, self.buf = (w, h), np.empty(w * h * 4 + 1024, np.uint8)
+        return self.buf
+
+    def call(self, w, h, p, fn):
+        """The file (bytes) of fn(out pointer, cap, byref(bytes)) -> rc, repeated once with a grown buffer when the first was
+        too small"""
         n = C.c_size_t()
+        self.ready(w, h, p)
         rc = fn(L.u8ptr(self.buf), self.buf.size, C.byref(n))
         if rc == -1 and n.value > self.buf.size:
-            b = C.c_size_t()
-            L.check(getattr(L.lib(), self.bound)(self.size[0], self.size[1], C.byref(p), C.byref(b)))
-            self.buf = np.empty(max(int(b.value), int(n.value)), np.uint8)
+            self.grow(w, h, p, n.value)
             rc = fn(L.u8ptr(self.buf), self.buf.size, C.byref(n))
         L.check(rc)
-        return int(n.value)
+        return self.buf[:int(n.value)].tobytes()
 
 
-_jpeg_buffers = {}
+def _last_ms(name):
+    """((the three stages' ms), bytes brought to the host) of the last stand-alone encode of a format (fspt_<name>_last_ms)"""
+    ms, n = (C.c_float * 3)(), C.c_uint64()
+    L.check(getattr(L.lib(), f"fspt_{name}_last_ms")(ms, C.byref(n)))
+    return tuple(float(x) for x in ms), int(n.value)
+
+
+_jpeg_buffer, _png_buffer, _exr_buffer = _FileBuffer("fspt_jpeg_bound"), _FileBuffer("fspt_png_bound"), _FileBuffer("fspt_exr_bound", True)
+
+
+def _encode_rgba8(buf, host_entry, device_entry, image, p, bottom_up, device):
+    """jpeg_encode and png_encode behind their parameters"""
+    image, on_dev, device = _image_arg(image, "uint8", 4, "image", device)
+    h, w = int(image.shape[0]), int(image.shape[1])
+    src = C.c_void_p(image.data_ptr()) if on_dev else L.u8ptr(image)
+    entry = getattr(L.lib(), device_entry if on_dev else host_entry)
+    return buf.call(w, h, p, lambda o, cap, nb: entry(int(device), src, w, h, 1 if bottom_up else 0, C.byref(p), o, cap, nb))
 
 
 def jpeg_encode(image, quality=85, subsampling="420", restart_mcus=0, bottom_up=False, device=0):
     """A baseline JPEG file (bytes) of an RGBA8 image [H, W, 4], encoded on the GPU (fspt_jpeg_encode): a numpy
     array, or a torch tensor on the device, which is read where it is (fspt_jpeg_encode_device).  Alpha is ignored;
     bottom_up: row 0 is the bottom, as draw() returns it."""
-    p = jpeg_params(quality, subsampling, restart_mcus)
-    on_dev = hasattr(image, "data_ptr") and getattr(image, "is_cuda", False)
-    if on_dev:
-        import torch
-        if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 4:
-            raise ValueError("image must be a uint8 [H, W, 4] tensor")
-        image = image.contiguous()
-        device = image.device.index or 0
-        torch.cuda.current_stream(device).synchronize()  # whatever wrote the tensor has finished
-    else:
-        image = np.ascontiguousarray(image)
-        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 4:
-            raise ValueError("image must be a uint8 [H, W, 4] array")
-    h, w = int(image.shape[0]), int(image.shape[1])
-    buf = _jpeg_buffers.get((w, h))
-    if buf is None:
-        _jpeg_buffers.clear()  # one reusable buffer: the last size's
-        buf = _jpeg_buffers[(w, h)] = _JpegBuffer(w, h)
-    lib = L.lib()
-    if on_dev:
-        n = buf.call(p, lambda o, cap, nb: lib.fspt_jpeg_encode_device(int(device), C.c_void_p(image.data_ptr()), w, h, 1 if bottom_up else 0, C.byref(p), o, cap, nb))
-    else:
-        n = buf.call(p, lambda o, cap, nb: lib.fspt_jpeg_encode(int(device), L.u8ptr(image), w, h, 1 if bottom_up else 0, C.byref(p), o, cap, nb))
-    return buf.buf[:n].tobytes()
+    return _encode_rgba8(_jpeg_buffer, "fspt_jpeg_encode", "fspt_jpeg_encode_device", image, jpeg_params(quality, subsampling, restart_mcus), bottom_up, device)
 
 
 def jpeg_coefficients_eval(image, quality=85, subsampling="420", bottom_up=False, device=0):
@@ -382,9 +414,7 @@ def jpeg_coefficients_eval(image, quality=85, subsampling="420", bottom_up=False
 
 def jpeg_last_ms():
     """((blocks ms, entropy ms, offsets + pack ms), bytes brought to the host) of the last jpeg_encode (fspt_jpeg_last_ms)"""
-    ms, n = (C.c_float * 3)(), C.c_uint64()
-    L.check(L.lib().fspt_jpeg_last_ms(ms, C.byref(n)))
-    return tuple(float(x) for x in ms), int(n.value)
+    return _last_ms("jpeg")
 
 
 PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
@@ -407,48 +437,17 @@ def png_bound(width, height, channels=3, filter="adaptive", chunk_bytes=0):
     return int(n.value)
 
 
-def _rgba8(image):
-    image = np.ascontiguousarray(image)
-    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 4:
-        raise ValueError("image must be a uint8 [H, W, 4] array")
-    return image
-
-
-_png_buffers = {}
-
-
 def png_encode(image, channels=3, filter="adaptive", chunk_bytes=0, bottom_up=False, device=0):
     """A PNG file (bytes) of an RGBA8 image [H, W, 4], encoded on the GPU (fspt_png_encode): a numpy array, or
     a torch tensor on the device, which is read where it is (fspt_png_encode_device).  channels 3 drops alpha, 4 keeps it
     (straight); bottom_up: row 0 is the bottom, as draw() returns it."""
-    p = png_params(channels, filter, chunk_bytes)
-    on_dev = hasattr(image, "data_ptr") and getattr(image, "is_cuda", False)
-    if on_dev:
-        import torch
-        if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 4:
-            raise ValueError("image must be a uint8 [H, W, 4] tensor")
-        image = image.contiguous()
-        device = image.device.index or 0
-        torch.cuda.current_stream(device).synchronize()  # whatever wrote the tensor has finished
-    else:
-        image = _rgba8(image)
-    h, w = int(image.shape[0]), int(image.shape[1])
-    buf = _png_buffers.get((w, h))
-    if buf is None:
-        _png_buffers.clear()  # one reusable buffer: the last size's
-        buf = _png_buffers[(w, h)] = _JpegBuffer(w, h, "fspt_png_bound")
-    lib = L.lib()
-    if on_dev:
-        n = buf.call(p, lambda o, cap, nb: lib.fspt_png_encode_device(int(device), C.c_void_p(image.data_ptr()), w, h, 1 if bottom_up else 0, C.byref(p), o, cap, nb))
-    else:
-        n = buf.call(p, lambda o, cap, nb: lib.fspt_png_encode(int(device), L.u8ptr(image), w, h, 1 if bottom_up else 0, C.byref(p), o, cap, nb))
-    return buf.buf[:n].tobytes()
+    return _encode_rgba8(_png_buffer, "fspt_png_encode", "fspt_png_encode_device", image, png_params(channels, filter, chunk_bytes), bottom_up, device)
 
 
 def png_filtered_eval(image, channels=3, filter="adaptive", bottom_up=False, device=0):
     """Stage one of the encoder alone (fspt_png_filtered_eval): the filtered stream, uint8 [H, 1 + W * channels]"""
     p = png_params(channels, filter, 0)
-    image = _rgba8(image)
+    image = _host_image(image, "uint8", 4, "image")
     h, w = image.shape[:2]
     out = np.zeros((h, 1 + w * p.channels), np.uint8)
     L.check(L.lib().fspt_png_filtered_eval(int(device), L.u8ptr(image), w, h, 1 if bottom_up else 0, C.byref(p), L.u8ptr(out)))
@@ -457,9 +456,7 @@ def png_filtered_eval(image, channels=3, filter="adaptive", bottom_up=False, dev
 
 def png_last_ms():
     """((filter ms, deflate ms, offsets + pack ms), bytes brought to the host) of the last png_encode (fspt_png_last_ms)"""
-    ms, n = (C.c_float * 3)(), C.c_uint64()
-    L.check(L.lib().fspt_png_last_ms(ms, C.byref(n)))
-    return tuple(float(x) for x in ms), int(n.value)
+    return _last_ms("png")
 
 
 EXR_COMPRESSIONS = {"none": 0, "zips": 2, "zip": 3}
@@ -493,50 +490,24 @@ def exr_bound(width, height, compression="zip", float32=False, layers=(), chunk_
     return int(n.value)
 
 
-class _ExrBuffer:
-    """The wrappers' reusable output buffer: fspt_exr_bound of the last size and settings, kept while it is large enough"""
-
-    def __init__(self):
-        self.buf = np.empty(0, np.uint8)
-
-    def call(self, w, h, p, fn):
-        b, n = C.c_size_t(), C.c_size_t()
-        L.check(L.lib().fspt_exr_bound(w, h, C.byref(p), C.byref(b)))
-        if self.buf.size < b.value:
-            self.buf = np.empty(int(b.value), np.uint8)
-        L.check(fn(L.u8ptr(self.buf), self.buf.size, C.byref(n)))
-        return self.buf[:int(n.value)].tobytes()
-
-
-_exr_buffer = _ExrBuffer()
-
-
 def exr_encode(rgba, features=None, compression="zip", float32=False, layers=(), chunk_bytes=0, bottom_up=False, device=0):
     """A scanline OpenEXR file (bytes) of float32 radiance [H, W, 4] and, for the albedo, normal and depth layers, the
     features [H, W, 8] as readFeatures() returns them, encoded on the GPU (fspt_exr_encode): numpy arrays, or
     torch tensors on the device, which are read where they are (fspt_exr_encode_device).  bottom_up: row 0 is the bottom, as
     every buffer of the library; the file's first scanline is the top."""
     p = exr_params(compression, float32, layers, chunk_bytes)
-    on_dev = hasattr(rgba, "data_ptr") and getattr(rgba, "is_cuda", False)
+    rgba, on_dev, device = _image_arg(rgba, "float32", 4, "rgba", device, sync=False)
     if on_dev:
         import torch
-        if rgba.dtype != torch.float32 or rgba.dim() != 3 or rgba.shape[2] != 4:
-            raise ValueError("rgba must be a float32 [H, W, 4] tensor")
-        rgba = rgba.contiguous()
         if features is not None:
             if not getattr(features, "is_cuda", False) or features.dtype != torch.float32 or tuple(features.shape) != (rgba.shape[0], rgba.shape[1], 8) or features.device != rgba.device:
                 raise ValueError("features must be a float32 [H, W, 8] tensor on the device of rgba")
             features = features.contiguous()
-        device = rgba.device.index or 0
-        torch.cuda.current_stream(device).synchronize()  # whatever wrote the tensors has finished
-    else:
-        rgba = np.ascontiguousarray(rgba)
-        if rgba.dtype != np.float32 or rgba.ndim != 3 or rgba.shape[2] != 4:
-            raise ValueError("rgba must be a float32 [H, W, 4] array")
-        if features is not None:
-            features = np.ascontiguousarray(features)
-            if features.dtype != np.float32 or features.shape != (rgba.shape[0], rgba.shape[1], 8):
-                raise ValueError("features must be a float32 [H, W, 8] array")
+        torch.cuda.current_stream(device).synchronize()  # whatever wrote the tensors, the copies above included, has finished
+    elif features is not None:
+        features = np.ascontiguousarray(features)
+        if features.dtype != np.float32 or features.shape != (rgba.shape[0], rgba.shape[1], 8):
+            raise ValueError("features must be a float32 [H, W, 8] array")
     h, w = int(rgba.shape[0]), int(rgba.shape[1])
     lib, bu = L.lib(), 1 if bottom_up else 0
     if on_dev:
@@ -553,9 +524,7 @@ def exr_set_form(form):
 
 def exr_last_ms():
     """((rows ms, deflate ms, offsets + pack ms), bytes brought to the host) of the last exr_encode (fspt_exr_last_ms)"""
-    ms, n = (C.c_float * 3)(), C.c_uint64()
-    L.check(L.lib().fspt_exr_last_ms(ms, C.byref(n)))
-    return tuple(float(x) for x in ms), int(n.value)
+    return _last_ms("exr")
 
 
 def light_alias_table(weights):
@@ -1552,10 +1521,10 @@ class PathTracer:
         return (out if ticks.value else None), int(ticks.value)
 
     # ---- JPEG output (include/fspt.h fspt_draw_jpeg / fspt_present_jpeg) ----------------------------
-    def _jpeg_buffer(self):
-        if getattr(self, "_jpeg_buf", None) is None:
-            self._jpeg_buf = _JpegBuffer(*self.resolution)
-        return self._jpeg_buf
+    def _file_buffer(self, fmt, bound_first=False):
+        if getattr(self, f"_{fmt}_buf", None) is None:
+            setattr(self, f"_{fmt}_buf", _FileBuffer(f"fspt_{fmt}_bound", bound_first))
+        return getattr(self, f"_{fmt}_buf")
 
     def draw_jpeg(self, source="accumulator", exposure=1.0, saturation=1.0, denoise=False, max_sigma=3.0, scale=1.0,
                   quality=85, subsampling="420", restart_mcus=0):
@@ -1563,10 +1532,9 @@ class PathTracer:
         same arguments as a JPEG file (bytes), encoded on the GPU: the frame never leaves the device (fspt_draw_jpeg)."""
         if source not in JPEG_SOURCES:
             raise ValueError(f"source must be one of {sorted(JPEG_SOURCES)}")
-        p, buf, lib = jpeg_params(quality, subsampling, restart_mcus), self._jpeg_buffer(), L.lib()
-        n = buf.call(p, lambda o, cap, nb: lib.fspt_draw_jpeg(self._t, JPEG_SOURCES[source], float(exposure), float(saturation), 1 if denoise else 0,
-                                                              float(max_sigma), float(scale), C.byref(p), o, cap, nb))
-        return buf.buf[:n].tobytes()
+        p, lib = jpeg_params(quality, subsampling, restart_mcus), L.lib()
+        return self._file_buffer("jpeg").call(*self.resolution, p, lambda o, cap, nb: lib.fspt_draw_jpeg(
+            self._t, JPEG_SOURCES[source], float(exposure), float(saturation), 1 if denoise else 0, float(max_sigma), float(scale), C.byref(p), o, cap, nb))
 
     def draw_png(self, source="accumulator", exposure=1.0, saturation=1.0, denoise=False, max_sigma=3.0, scale=1.0,
                  channels=3, filter="adaptive", chunk_bytes=0):
@@ -1575,12 +1543,9 @@ class PathTracer:
         (fspt_draw_png)."""
         if source not in JPEG_SOURCES:
             raise ValueError(f"source must be one of {sorted(JPEG_SOURCES)}")
-        if getattr(self, "_png_buf", None) is None:
-            self._png_buf = _JpegBuffer(*self.resolution, "fspt_png_bound")
-        p, buf, lib = png_params(channels, filter, chunk_bytes), self._png_buf, L.lib()
-        n = buf.call(p, lambda o, cap, nb: lib.fspt_draw_png(self._t, JPEG_SOURCES[source], float(exposure), float(saturation), 1 if denoise else 0,
-                                                             float(max_sigma), float(scale), C.byref(p), o, cap, nb))
-        return buf.buf[:n].tobytes()
+        p, lib = png_params(channels, filter, chunk_bytes), L.lib()
+        return self._file_buffer("png").call(*self.resolution, p, lambda o, cap, nb: lib.fspt_draw_png(
+            self._t, JPEG_SOURCES[source], float(exposure), float(saturation), 1 if denoise else 0, float(max_sigma), float(scale), C.byref(p), o, cap, nb))
 
     def draw_exr(self, source="accumulator", compression="zip", float32=False, layers=(), chunk_bytes=0):
         """The HDR buffer itself - read_radiance()'s ("accumulator"), denoise()'s ("denoised"), temporal_accumulate()'s
@@ -1589,22 +1554,20 @@ class PathTracer:
         made on the GPU: only the file comes back (fspt_draw_exr).  No exposure, bloom or tone map."""
         if source not in JPEG_SOURCES:
             raise ValueError(f"source must be one of {sorted(JPEG_SOURCES)}")
-        if getattr(self, "_exr_buf", None) is None:
-            self._exr_buf = _ExrBuffer()
         p, lib = exr_params(compression, float32, layers, chunk_bytes), L.lib()
-        W, H = self.resolution
-        return self._exr_buf.call(W, H, p, lambda o, cap, nb: lib.fspt_draw_exr(self._t, JPEG_SOURCES[source], C.byref(p), o, cap, nb))
+        return self._file_buffer("exr", True).call(*self.resolution, p, lambda o, cap, nb: lib.fspt_draw_exr(self._t, JPEG_SOURCES[source], C.byref(p), o, cap, nb))
 
     def present_jpeg(self, exposure=1.0, saturation=1.0, denoise=False, max_sigma=3.0, scale=1.0, quality=85, subsampling="420", restart_mcus=0):
         """present() with the frame encoded on the GPU behind its draw (fspt_present_jpeg): (the PREVIOUS call's JPEG file as
         bytes, its sample count), or (None, 0) when there is nothing to present.  A file that outgrows the buffer is dropped
         by the library; the buffer is grown for the next one."""
-        p, buf, lib = jpeg_params(quality, subsampling, restart_mcus), self._jpeg_buffer(), L.lib()
+        p, buf, lib = jpeg_params(quality, subsampling, restart_mcus), self._file_buffer("jpeg"), L.lib()
         n, ticks = C.c_size_t(), C.c_uint32()
+        buf.ready(*self.resolution, p)
         rc = lib.fspt_present_jpeg(self._t, float(exposure), float(saturation), 1 if denoise else 0, float(max_sigma), float(scale), C.byref(p),
                                    L.u8ptr(buf.buf), buf.buf.size, C.byref(n), C.byref(ticks))
         if rc == -1 and n.value > buf.buf.size:
-            buf.buf = np.empty(max(jpeg_bound(*self.resolution, quality, subsampling, restart_mcus), int(n.value)), np.uint8)
+            buf.grow(*self.resolution, p, n.value)
             return None, 0
         L.check(rc)
         return (buf.buf[:n.value].tobytes() if ticks.value else None), int(ticks.value)

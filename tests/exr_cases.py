@@ -80,7 +80,14 @@ def cases():
     # compressed and raw blocks in one file
     out.append(("split", 24, 64, X.ZIP, X.FLOAT, 0, 0, False, False))
     out.append(("split", 24, 6, X.ZIPS, X.FLOAT, X.ALPHA, 300, True, False))
-    # the edge values as pixels
+    # block counts at, just past and two tiles past the offset scan's width of 256: its 64-bit carry from tile to tile
+    for w, h in ((3, 256), (3, 257), (2, 513)):
+        out.append(("rendered", w, h, X.ZIPS, X.HALF, 0, 256, False, False))
+    out.append(("rendered", 50, 257, X.ZIPS, X.HALF, 0, 256, True, False))  # 300 bytes a line: two chunks a block, 514 chunks
+    out.append(("rendered", 1, 4112, X.ZIP, X.HALF, 0, 256, False, False))  # 257 blocks of 16 lines
+    out.append(("rendered", 2, 300, X.NONE, X.HALF, 0, 256, True, False))
+    out.append(("rendered", 40, 300, X.ZIPS, X.HALF, 0, 256, False, False))  # 240 bytes a line: some deflate, some stay raw, on both sides of block 256
+    # the edge values as pixels (tests/test_exr_cpu.py takes the first of them as CASES[-3]: they stay last)
     for pt, comp in ((X.HALF, X.ZIP), (X.FLOAT, X.ZIPS), (X.HALF, X.NONE)):
         out.append(("edges", len(EDGE_BITS), 3, comp, pt, ALL_LAYERS, 0, False, True))
     return out

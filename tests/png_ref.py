@@ -1,5 +1,5 @@
 """tests/png_ref.py - the PNG encoder of DESIGN 8.20 restated in integers: the definition the GPU encoder
-(fspt_amd/csrc/fspt_png.hip) has to reproduce byte for byte.  numpy for the filter stage, a plain Python bit writer behind
+(fspt_amd/csrc/fspt_png.hip, fspt_deflate.hip) has to reproduce byte for byte.  numpy for the filter stage, a plain Python bit writer behind
 it.  No float takes part, and nothing of zlib: the checksums are written out here and tests/test_png_cpu.py compares them
 (and the files) with zlib and Pillow.
 

@@ -49,6 +49,18 @@ def test_the_file_is_the_restatements(case):
         assert got == want, explain(got, want)
 
 
+def test_more_blocks_than_the_offset_scan_is_wide():
+    """what the restatement says of the cases that put k_exr_offsets' scan past its first tile (each of them is one of
+    test_the_file_is_the_restatements' cases): the block counts, two chunks a block, and compressed and raw blocks in one
+    file on both sides of block 256"""
+    wide = {c[1:4]: reference(c)[1] for c in CASES if c[6] == 256 and c[2] >= 256}
+    assert {k: len(st["raw"]) for k, st in wide.items()} == {(3, 256, X.ZIPS): 256, (3, 257, X.ZIPS): 257, (2, 513, X.ZIPS): 513, (50, 257, X.ZIPS): 257,
+                                                            (1, 4112, X.ZIP): 257, (2, 300, X.NONE): 300, (40, 300, X.ZIPS): 300}
+    assert len(wide[(50, 257, X.ZIPS)]["kinds"]) == 514
+    mixed = wide[(40, 300, X.ZIPS)]["raw"]
+    assert {True, False} == set(mixed[:256]) == set(mixed[256:])
+
+
 def test_row_order_device_form_and_determinism():
     import torch
     case = next(c for c in CASES if c[1:3] == (301, 18) and c[5] == (X.ALPHA | X.DEPTH))
@@ -67,6 +79,25 @@ def test_row_order_device_form_and_determinism():
     # features that no layer asks for change nothing, and need not be there
     rgb = next(c for c in CASES if c[1:3] == (3, 33) and c[4] == X.FLOAT)
     assert gpu_file(rgb, buffers(rgb)[0], np.full((33, 3, 8), 7.0, np.float32)) == reference(rgb)[0]
+
+
+def test_strided_tensors_on_a_side_stream():
+    """rgba and features as views of wider tensors, written on a stream of their own: exr_encode copies both to contiguous
+    tensors on that stream and waits for it behind the second copy, before the library reads them on its own stream"""
+    import torch
+    case = next(c for c in CASES if c[1:3] == (301, 18) and c[5] == (X.ALPHA | X.DEPTH))
+    want, _ = reference(case)
+    rgba, feat = buffers(case)
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        wide_r = torch.zeros((18, 301, 6), dtype=torch.float32, device="cuda:0")
+        wide_f = torch.zeros((18, 301, 11), dtype=torch.float32, device="cuda:0")
+        wide_r[..., 1:5] = torch.from_numpy(rgba).to("cuda:0")
+        wide_f[..., 2:10] = torch.from_numpy(feat).to("cuda:0")
+        tr, tf = wide_r[..., 1:5], wide_f[..., 2:10]
+        assert not tr.is_contiguous() and not tf.is_contiguous()
+        got = gpu_file(case, tr, tf)
+    assert got == want, explain(got, want)
 
 
 def test_cap_and_errors():

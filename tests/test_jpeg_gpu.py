@@ -65,6 +65,17 @@ def test_many_workgroups_and_intervals(content):
     assert wraps
 
 
+@pytest.mark.parametrize("size,intervals", (((128, 128), 256), ((8, 2056), 257), ((8, 4104), 513)), ids=lambda v: str(v).replace(" ", ""))
+def test_interval_counts_around_the_offset_scans_width(size, intervals):
+    """every MCU an interval: as many intervals as k_jpeg_offsets scans in one tile of 256, one more, and two tiles and one -
+    the carry from tile to tile, and RSTn wrapping many times"""
+    w, h = size
+    _, mw, mh = J.mcu_grid(w, h, J.S444)
+    assert J.restart_interval(w, h, J.S444, 1) == 1 and mw * mh == intervals
+    want = check_case(w, h, ("444", J.S444), 75, 1, "noise", bool(intervals & 1))
+    assert want.count(b"\xFF\xD0") == (intervals - 1 + 7) // 8
+
+
 def test_every_quality_on_one_image():
     a = image("noise", 24, 16)
     for q in (1, 2, 25, 49, 50, 51, 90, 99, 100):

@@ -58,6 +58,19 @@ def test_many_chunks(content):
         assert set(st["blocks"]) == {P.DYNAMIC} and any(n >= 258 for kind, n in P.tokens(st["stream"][:32768]) if kind == "len")
 
 
+@pytest.mark.parametrize("size,chunks", (((85, 256), 256), ((85, 257), 257), ((85, 513), 513), ((86, 255), 258)), ids=lambda v: str(v).replace(" ", ""))
+def test_chunk_counts_around_the_offset_scans_width(size, chunks):
+    """chunks of 256 bytes, a row of 85 RGB pixels being one: as many chunks as k_png_offsets scans in one tile of 256, one
+    more, and two tiles and one - the carries of the offsets and of the Adler sums from tile to tile; 86 pixels: chunks off
+    the row boundaries and a partial last one"""
+    a = image("rendered", *size)
+    _, st = check_case(a, 3, P.ADAPTIVE, 256, False)
+    assert len(st["blocks"]) == chunks
+    if chunks == 257:  # four channels: 341 bytes a row, 343 chunks off the rows
+        _, st = check_case(a, 4, P.ADAPTIVE, 256, True)
+        assert len(st["blocks"]) == (size[1] * (1 + 4 * size[0]) + 255) // 256 > 256
+
+
 def test_both_code_limits_are_hit():
     """the literal/length code against 15 bits and the code-length code against 7: the restatement's statistics say that the
     limit was met, and the device's file is the restatement's"""

@@ -284,6 +284,10 @@ SIGNATURES = {
     "fspt_scene_light_table": (C.c_int, [_VP, _U32, _U32, _U32, _F, _F, _U32, _U32, _F, _U32]),
     "fspt_light_sample_eval": (C.c_int, [_VP, _F, C.c_uint32, C.POINTER(C.c_int32), _F]),
     "fspt_light_alias_table": (C.c_int, [_F, C.c_uint32, _F, _U32]),
+    "fspt_scene_set_light_builder": (C.c_int, [_VP, C.c_int]),
+    "fspt_scene_get_light_builder": (C.c_int, [_VP, C.POINTER(C.c_int)]),
+    "fspt_light_alias_table_gpu": (C.c_int, [C.c_int, _F, C.c_uint32, _F, _U32, _F]),
+    "fspt_scene_light_build_stats": (C.c_int, [_VP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _F]),
     "fspt_last_kernel_ms": (C.c_int, [_VP, _F, _U32]),
     "fspt_target_set_pipeline": (C.c_int, [_VP, C.c_int, C.c_uint32]),
     "fspt_target_set_primary_form": (C.c_int, [_VP, C.c_int]),

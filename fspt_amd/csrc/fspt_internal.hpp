@@ -17,6 +17,7 @@
 //   fspt_bvh_build.hip     the GPU BVH builder;  fspt_refit.hip  in-place refit and rebuild;  fspt_pose.hip  part transforms and skinning
 //   fspt_appearance.hip    in-place appearance update: the texture-set, atlas and environment layouts and the material part of the hit records
 //   fspt_sky.hip           the sky generator and the environment's importance bins, built on the GPU
+//   fspt_lights_build.hip  the emitter light table of a live scene, built on the GPU (opt-in)
 //   fspt_jpeg.hip          the baseline JPEG encoder behind fspt_jpeg_encode, fspt_draw_jpeg and fspt_present_jpeg, and its stand-alone entries
 //   fspt_png.hip           the PNG encoder behind fspt_png_encode and fspt_draw_png, and its stand-alone entries
 //   fspt_exr.hip           the OpenEXR encoder behind fspt_exr_encode and fspt_draw_exr, and its stand-alone entries
@@ -52,6 +53,8 @@ void fspt_set_error(const char *fmt, ...);
     }                                                                                             \
   } while (0)
 
+namespace fspt { struct LightsWork; } // (fspt_lights_build.hip) the GPU light-table builder's device memory
+
 struct fspt_scene {
   int device = 0;
   int num_cus = 256;
@@ -70,6 +73,21 @@ struct fspt_scene {
   std::vector<uint32_t> l_alias_h;  // per entry
   std::vector<float> l_pick_h;      // per leaf slot
   std::vector<uint32_t> l_slot_tri; // per leaf slot: its triangle
+  // fspt_scene_set_light_builder (fspt_lights_build.hip).  Under FSPT_LIGHT_BUILDER_GPU the d.light_* arrays
+  // live in `work` (made by the first such build; l_alias .. l_pick stay NULL) and the host copies above are filled only
+  // when fspt_scene_light_table or fspt_light_sample_eval asks.  A scene that never opts in allocates no device memory for it;
+  // its host build creates the two events of host_ev and records them around its device work (fspt_scene_light_build_stats).
+  struct LightsGpu {
+    int builder = FSPT_LIGHT_BUILDER_HOST;
+    fspt::LightsWork *work = nullptr;
+    bool topo_valid = false;        // work's triangle-to-slot arrays match the tree (geometry_publish clears it)
+    bool mirrors_valid = false;     // the host copies hold the table `work` holds
+    bool timed = false;             // work's events bracket a build
+    int built_by = -1;              // the builder of the last build (-1: none yet): whose events fspt_scene_light_build_stats reads
+    uint64_t bytes_d2h = 0, bytes_h2d = 0; // what that build moved over the bus
+    hipEvent_t host_ev[2] = {nullptr, nullptr}; // around the host builder's device work
+    bool host_timed = false;
+  } lg;
   // fspt_scene_update_geometry.  The scene knows its live targets (fspt_target_create / _destroy), so that an
   // update is ordered against their recorded ticks and their streams.  `rf` is what a refit needs of the reference tree and
   // fspt_scene_create no longer has when it returns: host memory until the first update, which makes the device copies
@@ -249,6 +267,15 @@ int env_box_sums_run(const uint8_t *rgbe, uint32_t w, uint32_t h, const uint32_t
 // then are the scene's buffers swapped and s->sky filled in.
 int environment_gpu(fspt_scene *s, const char *fn, const uint8_t *env, bool env_on_device, const fspt_sky_params *sky, uint32_t w, uint32_t h);
 void sky_release(fspt_scene *s);
+// fspt_lights_build.hip.  lights_build_gpu: light_table_ensure's work under FSPT_LIGHT_BUILDER_GPU, on the NULL
+// stream and waited for - the table from the scene's device arrays into s->lg.work and s->d.light_*, one 8-byte read.
+// lights_mirrors_gpu: the host copies of that table.  lights_build_ms: the GPU time of the last such build (0: none).
+// light_alias_table_gpu_run: fspt_light_alias_table_gpu's device side on the current device, host pointers.
+int lights_build_gpu(fspt_scene *s);
+int lights_mirrors_gpu(fspt_scene *s);
+int lights_build_ms(fspt_scene *s, float *ms);
+void lights_release(fspt_scene *s);
+int light_alias_table_gpu_run(const float *weights, uint32_t n, float *prob, uint32_t *alias, float *light_p);
 // fspt_encode.cpp: what the host halves of the three encoders below share.  EncCommon: the part of an encoder's
 // device memory that does not depend on the format - the output buffers, which only grow and outlive a change of the
 // parameters, the events around the three stages of the last launch, and `work`, the owner of every buffer made for the

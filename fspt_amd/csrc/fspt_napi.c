@@ -1375,6 +1375,22 @@ static napi_value SetLights(napi_env env, napi_callback_info info) {
   FSPT_OK_OR_THROW(fspt_target_set_lights((fspt_target *)h, mode, (float)f));
   return undefined(env);
 }
+/* sceneSetLightBuilder(scene, builder) / sceneGetLightBuilder(scene) -> builder: fspt_scene_set_light_builder / _get_ (DESIGN
+ * 8.23; builder: FSPT_LIGHT_BUILDER_HOST / FSPT_LIGHT_BUILDER_GPU).  The guard of sceneUpdateGeometry. */
+static napi_value SceneSetLightBuilder(napi_env env, napi_callback_info info) {
+  napi_value a[2]; void *h; int32_t builder;
+  if (get_args(env, info, 2, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  NAPI_OK(napi_get_value_int32(env, a[1], &builder));
+  FSPT_OK_OR_THROW(fspt_scene_set_light_builder((fspt_scene *)h, builder));
+  return undefined(env);
+}
+static napi_value SceneGetLightBuilder(napi_env env, napi_callback_info info) {
+  napi_value a[1], r; void *h; int builder = 0;
+  if (get_args(env, info, 1, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  FSPT_OK_OR_THROW(fspt_scene_get_light_builder((fspt_scene *)h, &builder));
+  NAPI_OK(napi_create_int32(env, builder, &r));
+  return r;
+}
 /* setCameraModel(target, model, angle, ipd): fspt_target_set_camera_model (model: FSPT_CAMERA_*).  fspt.js has
  * checked the arguments; they are checked again here (the target's height for STEREO: by the library). */
 static napi_value SetCameraModel(napi_env env, napi_callback_info info) {
@@ -1803,7 +1819,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
       {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"sceneUpdateSky", SceneUpdateSky}, {"sceneUpdateEnvironmentAuto", SceneUpdateEnvironmentAuto}, {"skyGenerate", SkyGenerate}, {"atlasPackGpu", AtlasPackGpu}, {"sceneUpdateTextures", SceneUpdateTextures}, {"scenePatchTextures", ScenePatchTextures}, {"envBinsGpu", EnvBinsGpu}, {"sceneSetPose", SceneSetPose}, {"sceneUpdateTransforms", SceneUpdateTransforms}, {"sceneSetSkin", SceneSetSkin}, {"sceneUpdateSkin", SceneUpdateSkin}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
-      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"jpegBound", JpegBound}, {"jpegEncode", JpegEncode}, {"drawJpeg", DrawJpeg}, {"presentJpeg", PresentJpeg}, {"pngBound", PngBound}, {"pngEncode", PngEncode}, {"pngFilteredEval", PngFilteredEval}, {"drawPng", DrawPng}, {"exrBound", ExrBound}, {"exrEncode", ExrEncode}, {"drawExr", DrawExr}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setCameraModel", SetCameraModel}, {"cameraModel", CameraModel}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
+      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"jpegBound", JpegBound}, {"jpegEncode", JpegEncode}, {"drawJpeg", DrawJpeg}, {"presentJpeg", PresentJpeg}, {"pngBound", PngBound}, {"pngEncode", PngEncode}, {"pngFilteredEval", PngFilteredEval}, {"drawPng", DrawPng}, {"exrBound", ExrBound}, {"exrEncode", ExrEncode}, {"drawExr", DrawExr}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setCameraModel", SetCameraModel}, {"cameraModel", CameraModel}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"sceneSetLightBuilder", SceneSetLightBuilder}, {"sceneGetLightBuilder", SceneGetLightBuilder}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},
       {"renderAsync", RenderAsync}, {"multiCreate", MultiCreate}, {"multiDestroy", MultiDestroy}, {"multiTarget", MultiTarget},
       {"multiCamera", MultiCamera}, {"multiTrace", MultiTrace}, {"multiRender", MultiRender}, {"multiRenderAsync", MultiRenderAsync},

@@ -60,13 +60,28 @@ static bool alias_build(const float *w, uint32_t n, std::vector<float> &prob, st
   return true;
 }
 
+// the host copies of the table, which the GPU builder fills only when somebody asks
+static int light_mirrors_ensure(fspt_scene *s) {
+  if (s->lg.builder != FSPT_LIGHT_BUILDER_GPU || s->lg.mirrors_valid) return FSPT_OK;
+  return fspt::lights_mirrors_gpu(s);
+}
+
 // The scene's emitter light table: per-triangle weights on the device (k_light_weights over one leaf slot of
 // each triangle), the alias table of the triangles with weight > 0 on the host, their light records on the device
 int light_table_ensure(fspt_scene *s) {
   if (s->lights_built) return FSPT_OK;
   int rc = check_device(s->device);
   if (rc) return rc;
+  if (s->lg.builder == FSPT_LIGHT_BUILDER_GPU) { // (the same arrays, made by fspt_lights_build.hip's kernels)
+    rc = fspt::lights_build_gpu(s);
+    if (rc) return rc;
+    s->lg.built_by = FSPT_LIGHT_BUILDER_GPU;
+    s->lights_built = true;
+    return FSPT_OK;
+  }
   const uint32_t T = s->n_tris;
+  for (hipEvent_t &ev : s->lg.host_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
+  s->lg.host_timed = false;
   // leaf slots and their triangles (the hit records are stored per slot)
   const size_t slots_n = s->n_slots;
   s->l_slot_tri.resize(slots_n);
@@ -82,6 +97,7 @@ int light_table_ensure(fspt_scene *s) {
   float *d_w = nullptr;
   hipError_t e = hipMalloc((void **)&d_slots, (size_t)T * 4);
   if (e == hipSuccess) e = hipMalloc((void **)&d_w, (size_t)T * 4);
+  if (e == hipSuccess) e = hipEventRecord(s->lg.host_ev[0], nullptr);
   if (e == hipSuccess) e = hipMemcpy(d_slots, tri_slot.data(), (size_t)T * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = fspt::launch_light_weights(s->d, d_slots, T, d_w, nullptr, nullptr);
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -120,8 +136,13 @@ int light_table_ensure(fspt_scene *s) {
     if (e == hipSuccess) e = hipMemcpy(s->l_pick, s->l_pick_h.data(), slots_n * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
   }
+  if (e == hipSuccess) e = hipEventRecord(s->lg.host_ev[1], nullptr);
   hipFree(d_slots); hipFree(d_w);
   if (e != hipSuccess) { fspt_set_error("light table: %s", hipGetErrorString(e)); return FSPT_E_HIP; }
+  s->lg.host_timed = true;
+  s->lg.built_by = FSPT_LIGHT_BUILDER_HOST;
+  s->lg.bytes_d2h = (uint64_t)slots_n * 4 + (uint64_t)T * 4;
+  s->lg.bytes_h2d = (uint64_t)T * 4 + (n ? (uint64_t)n * 16 + (uint64_t)slots_n * 4 : 0u);
   s->d.light_alias = (const uint2 *)s->l_alias;
   s->d.light_rec = (const float4 *)s->l_rec;
   s->d.light_p = (const float *)s->l_p;
@@ -372,6 +393,7 @@ int geometry_changed_lights(fspt_scene *s) {
     s->d.light_alias = nullptr; s->d.light_rec = nullptr; s->d.light_p = nullptr; s->d.light_pick = nullptr;
     s->d.n_lights = 0;
     s->lights_built = false;
+    s->lg.mirrors_valid = false; // (the GPU builder's arrays stay allocated: its next build writes them again)
   }
   for (fspt_target *t : s->targets)
     if (t->lights == FSPT_LIGHTS_EMITTERS) { rc = light_table_ensure(s); if (rc) return rc; break; }
@@ -391,6 +413,7 @@ void geometry_publish(fspt_scene *s, const TreeTopology &tp, uint32_t n_nodes, s
   // measured +-0 (profiles/r06/ab_final_constants_c3.log, f_spare0), so the spare stays.
   s->d.stack_n = tp.max_depth + 1;
   s->d.n_top = tp.n_interior < 256u ? tp.n_interior : 256u; // interior nodes numbered breadth-first
+  s->lg.topo_valid = false; // (the GPU light builder's triangle-to-slot arrays)
   s->depth = tp.max_depth; s->n_nodes = n_nodes; s->n_interior = tp.n_interior; s->n_slots = n_slots;
 }
 
@@ -695,6 +718,8 @@ int fspt_scene_destroy(fspt_scene *s) {
   fspt::pose_release(s);
   fspt::skin_release(s);
   fspt::sky_release(s);
+  fspt::lights_release(s);
+  for (hipEvent_t &ev : s->lg.host_ev) if (ev) hipEventDestroy(ev);
   delete s;
   return FSPT_OK;
 }
@@ -716,7 +741,8 @@ int fspt_scene_light_count(fspt_scene *s, uint32_t *n_lights) {
 int fspt_scene_light_table(fspt_scene *s, uint32_t *n_tris, uint32_t *n_lights, uint32_t *n_slots, float *weights, float *prob,
                            uint32_t *alias, uint32_t *tris, float *pick, uint32_t *slot_tri) {
   if (!s) { fspt_set_error("fspt_scene_light_table: NULL scene"); return FSPT_E_INVALID; }
-  const int rc = light_table_ensure(s);
+  int rc = light_table_ensure(s);
+  if (!rc) rc = light_mirrors_ensure(s);
   if (rc) return rc;
   if (n_tris) *n_tris = (uint32_t)s->l_weight.size();
   if (n_lights) *n_lights = (uint32_t)s->l_tri.size();
@@ -744,8 +770,55 @@ int fspt_light_sample_eval(fspt_scene *s, const float *in, uint32_t n, int32_t *
   st.down(out, d_out, (size_t)n * 32);
   st.down(tri, d_e, (size_t)n * 4);
   if ((rc = st.done("fspt_light_sample_eval"))) return rc;
+  if ((rc = light_mirrors_ensure(s))) return rc;
   for (uint32_t i = 0; i < n; ++i) tri[i] = (int32_t)s->l_tri[(uint32_t)tri[i]];
   return FSPT_OK;
+}
+
+int fspt_scene_set_light_builder(fspt_scene *s, int builder) {
+  if (!s) { fspt_set_error("fspt_scene_set_light_builder: NULL scene"); return FSPT_E_INVALID; }
+  if (builder != FSPT_LIGHT_BUILDER_HOST && builder != FSPT_LIGHT_BUILDER_GPU) {
+    fspt_set_error("fspt_scene_set_light_builder: builder must be FSPT_LIGHT_BUILDER_HOST (0) or FSPT_LIGHT_BUILDER_GPU (1), got %d", builder);
+    return FSPT_E_INVALID;
+  }
+  int rc = check_device(s->device);
+  if (!rc) rc = geometry_order_targets(s); // the targets' recorded ticks see the table they were recorded under
+  if (rc) return rc;
+  const int old = s->lg.builder;
+  s->lg.builder = builder;
+  rc = geometry_changed_lights(s);
+  if (rc) s->lg.builder = old; // (the table stays dropped, as after a live-scene update whose rebuild fails: the next use builds it)
+  return rc;
+}
+
+int fspt_scene_get_light_builder(fspt_scene *s, int *builder) {
+  if (!s || !builder) { fspt_set_error("fspt_scene_get_light_builder: NULL argument"); return FSPT_E_INVALID; }
+  *builder = s->lg.builder;
+  return FSPT_OK;
+}
+
+int fspt_scene_light_build_stats(fspt_scene *s, uint64_t *bytes_d2h, uint64_t *bytes_h2d, float *ms) {
+  if (!s) { fspt_set_error("fspt_scene_light_build_stats: NULL scene"); return FSPT_E_INVALID; }
+  if (bytes_d2h) *bytes_d2h = s->lg.bytes_d2h;
+  if (bytes_h2d) *bytes_h2d = s->lg.bytes_h2d;
+  if (!ms) return FSPT_OK;
+  *ms = 0.0f;
+  int rc = check_device(s->device);
+  if (rc) return rc;
+  if (s->lg.built_by == FSPT_LIGHT_BUILDER_GPU) return fspt::lights_build_ms(s, ms);
+  if (s->lg.built_by == FSPT_LIGHT_BUILDER_HOST && s->lg.host_timed) {
+    HIP_TRY(hipEventSynchronize(s->lg.host_ev[1]));
+    HIP_TRY(hipEventElapsedTime(ms, s->lg.host_ev[0], s->lg.host_ev[1]));
+  }
+  return FSPT_OK;
+}
+
+int fspt_light_alias_table_gpu(int device, const float *weights, uint32_t n, float *prob, uint32_t *alias, float *light_p) {
+  if (!weights || n == 0) { fspt_set_error("fspt_light_alias_table_gpu: NULL/empty argument"); return FSPT_E_INVALID; }
+  if (n > (1u << 23)) { fspt_set_error("fspt_light_alias_table_gpu: %u entries, the GPU builder takes at most %u", n, 1u << 23); return FSPT_E_INVALID; }
+  const int rc = check_device(device);
+  if (rc) return rc;
+  return fspt::light_alias_table_gpu_run(weights, n, prob, alias, light_p);
 }
 
 int fspt_scene_two_level_nodes(const fspt_scene *s, int *present, uint64_t *bytes) {

@@ -764,6 +764,17 @@ class PathTracer {
     if (typeof f !== 'number' || !(f > 0 && f <= 1)) throw new RangeError('setLights: emitterFraction must be a number in (0, 1]');
     addon.setLights(this._target, code, f);
   }
+  /** who builds the scene's emitter light table (include/fspt.h fspt_scene_set_light_builder, DESIGN 8.23): 'host' (default)
+   *  or 'gpu' (on the device: 8 bytes are read back per build).  Drops an existing table; it is rebuilt at once when the
+   *  lights are on.  Throws Error('render in flight') during a renderAsync. */
+  setLightBuilder(builder) {
+    const code = { host: 0, gpu: 1 }[builder];
+    if (code === undefined) throw new RangeError("setLightBuilder: builder must be 'host' or 'gpu'");
+    addon.sceneSetLightBuilder(this._scene, code);
+  }
+  getLightBuilder() {
+    return ['host', 'gpu'][addon.sceneGetLightBuilder(this._scene)];
+  }
   /** the camera model (include/fspt.h fspt_target_set_camera_model, DESIGN 8.15): { model: 'pinhole' (default) | 'ortho' |
    *  'fisheye' | 'equirect' | 'stereo', angle (fisheye: field of view over the frame height in radians, in (0, 2 pi],
    *  default pi), ipd (stereo: scene units, >= 0, default 0.064; the height must be even) }.  Runs the recorded ticks

@@ -7,6 +7,7 @@ reference's format (scene/<name>.json with props / static_props / animated_props
     python -m fspt_amd.render --out bunny.png --spp 16 --atrous 5 --feature-samples 8   # guided denoiser
     python -m fspt_amd.render --out bunny.png --spp 16 --sampler sobol --sampler-seed 3  # Owen-scrambled Sobol sampler
     python -m fspt_amd.render --scene web/scene/bunny.json --lights --emitter-fraction 0.5  # sample emissive triangles
+    python -m fspt_amd.render --scene web/scene/bunny.json --lights --light-builder gpu   # ... their table built on the GPU
     python -m fspt_amd.render --mesh-n 289 --bvh gpu --spp 16 --out c3.png  # binned-SAH tree built on the GPU
     python -m fspt_amd.render --scene 'web/scene/anim_{frame}.json' --frames 0:24 --bvh refit --out 'out/{frame}.png'  # build once, refit
     python -m fspt_amd.render --scene 'web/scene/anim_{frame}.json' --frames 0:24 --bvh refit --pose --out 'out/{frame}.png'  # one matrix per prop per frame
@@ -140,6 +141,9 @@ def main(argv=None):
     ap.add_argument("--lights", action="store_true", help="next-event estimation of emissive triangles (fspt_target_set_lights)")
     ap.add_argument("--emitter-fraction", type=float, default=0.5,
                     help="with --lights: probability a vertex samples an emitter rather than the environment, in (0, 1]")
+    ap.add_argument("--light-builder", choices=("host", "gpu"), default=None,
+                    help="with --lights: who builds the emitter light table (fspt_scene_set_light_builder, DESIGN 8.23); gpu = on the "
+                         "device, nothing but 8 bytes is read back per build")
     ap.add_argument("--adaptive", type=float, default=None, metavar="REL_MSE",
                     help="adaptive sampling: stop a 32x32 tile once its estimated relative MSE is below REL_MSE (--spp = the most)")
     ap.add_argument("--sample-map", default=None, help="with --adaptive: write the ticks per pixel as a grey PNG")
@@ -197,6 +201,8 @@ def main(argv=None):
         ap.error("--emitter-fraction must lie in (0, 1]")
     if args.emitter_fraction != 0.5 and not args.lights:
         ap.error("--emitter-fraction needs --lights")
+    if args.light_builder is not None and not args.lights:
+        ap.error("--light-builder needs --lights")
     if args.temporal and args.adaptive is not None:
         ap.error("--temporal cannot be combined with --adaptive")
     if args.temporal and not (args.bvh == "refit" and args.frames):
@@ -227,6 +233,8 @@ def main(argv=None):
         kw = dict(samples=spp, bounces=args.bounces, seed=args.seed, saturation=args.saturation, denoise=args.denoise)
         if args.lights:
             kw.update(lights="emitters", emitter_fraction=args.emitter_fraction)
+            if args.light_builder is not None:
+                kw.update(light_builder=args.light_builder)
         if args.adaptive is not None:
             kw.update(samples=args.spp, adaptive=args.adaptive, sample_map=args.sample_map)
         if args.auto_exposure is not None:
@@ -277,6 +285,8 @@ def main(argv=None):
         pt.update_sky(**sky_at(0.0))
         print("sky: {n_bins} bins; generated in {sky_ms:.2f} ms, binned in {bins_ms:.2f} ms, tiled in {tile_ms:.2f} ms".format(**pt.last_sky()))
     if args.lights:
+        if args.light_builder is not None:
+            pt.scene.set_light_builder(args.light_builder)
         pt.set_lights("emitters", args.emitter_fraction)
     if args.auto_exposure is not None:
         pt.set_auto_exposure(True, **({} if args.auto_exposure is True else {"key": args.auto_exposure}))

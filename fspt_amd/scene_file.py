@@ -100,7 +100,7 @@ def _settings(scene, focus):
 
 def render_frame(arrays, settings, width, height, samples=None, bounces=4, seed=1, saturation=1.0, denoise=False,
                  max_sigma=3.0, device=0, lights=None, emitter_fraction=0.5, adaptive=None, sample_map=None, auto_exposure=None,
-                 bloom=None, camera=None):
+                 bloom=None, camera=None, light_builder=None):
     """One frame as the reference produces it in frame mode: `samples` ticks from a cleared accumulator
     (main.js:838-857; its very first, discarded tick is not reproduced), then drawQuad.  Returns
     (rgba8 [H, W, 4] top row first - what canvas.toBlob encodes -, radiance [H, W, 4] bottom row first).
@@ -110,8 +110,10 @@ def render_frame(arrays, settings, width, height, samples=None, bounces=4, seed=
     PathTracer.set_auto_exposure's parameters (DESIGN 8.11): the frame is metered on the GPU and the scene's `exposure`
     becomes a compensation; a still adapts instantly.  bloom: True or a dict of PathTracer.set_bloom's parameters (DESIGN
     8.12): the drawing mixes the HDR pyramid's glow in before the exposure.  camera: None or a dict of
-    PathTracer.set_camera_model's arguments (not with adaptive)."""
+    PathTracer.set_camera_model's arguments (not with adaptive).  light_builder: None, "host" or "gpu" - who
+    builds the emitter light table of lights="emitters" (Scene.set_light_builder)."""
     from .tracer import PathTracer
+    _light_builder(light_builder, lights)
     auto_exposure = _auto_exposure_params(auto_exposure)
     bloom = _bloom_params(bloom)
     camera = _camera_model_params(camera, adaptive)
@@ -123,6 +125,8 @@ def render_frame(arrays, settings, width, height, samples=None, bounces=4, seed=
             pt.set_auto_exposure(True, **auto_exposure)
         if bloom is not None:
             pt.set_bloom(True, **bloom)
+        if light_builder is not None:
+            pt.scene.set_light_builder(light_builder)
         rgba, rad = _render_on(pt, settings, samples, seed, saturation, denoise, max_sigma, lights, emitter_fraction, adaptive,
                                sample_map)
     finally:
@@ -132,6 +136,17 @@ def render_frame(arrays, settings, width, height, samples=None, bounces=4, seed=
 
 
 SEQUENCE_ADAPT = 0.25  # render_sequence's auto-exposure step per frame, in log2 (1 = instant): within 10 % of a new light in 8 frames
+
+
+def _light_builder(light_builder, lights):
+    """refuses a light_builder the library would refuse, or one without the lights it builds the table of"""
+    from .tracer import LIGHT_BUILDERS
+    if light_builder is None:
+        return
+    if light_builder not in LIGHT_BUILDERS:
+        raise ValueError("light_builder must be one of %s, got %r" % (sorted(LIGHT_BUILDERS), light_builder))
+    if lights != "emitters":
+        raise ValueError('light_builder needs lights="emitters"')
 
 
 def _auto_exposure_params(auto_exposure, adapt=None):
@@ -400,7 +415,9 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     exr: an out_pattern that ends in .exr is written as a scene-linear OpenEXR file of the frame's radiance -
     under bvh="refit" by PathTracer.draw_exr (the accumulator, or the temporal result), so that only the file leaves the
     device; None or a dict of its compression / float32 / layers / chunk_bytes.  The albedo, normal and depth layers need
-    bvh="refit" (the live tracer's features)."""
+    bvh="refit" (the live tracer's features).
+    light_builder (in kw, with lights="emitters"): "gpu" = every scene's emitter light table is built on the
+    device (Scene.set_light_builder), so that a kept frame's update reads 8 bytes back for it."""
     as_exr = is_exr_path(out_pattern)
     exr, exr_layers = exr_settings(exr)
     if as_exr and bvh != "refit" and exr_layers & 14:
@@ -464,6 +481,8 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                adaptive=None, sample_map=None)
     bounces = kw.get("bounces", 4)
     opt.update({k: v for k, v in kw.items() if k in opt})
+    light_builder = kw.get("light_builder")  #  every scene built here gets it before its first frame
+    _light_builder(light_builder, opt["lights"])
     base, pt, cost0, leaf_order = None, None, None, None
 
     atlas_sent = False
@@ -535,6 +554,8 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                 rest_json = None
                 if camera is not None:
                     pt.set_camera_model(**camera)
+                if light_builder is not None:
+                    pt.scene.set_light_builder(light_builder)
                 if pose and not frame_json.get("normalize"):
                     pt.scene.set_pose(base.meta["tri_part"], n_parts=len(S.merge_scene_props(frame_json)))
                     rest_json = frame_json

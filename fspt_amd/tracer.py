@@ -539,6 +539,19 @@ def light_alias_table(weights):
     return prob, alias
 
 
+def light_alias_table_gpu(weights, device=0):
+    """(prob float32, alias uint32, light_p float32) of the GPU builder's table for these raw weights (finite, >= 0, some
+    > 0; fspt_light_alias_table_gpu, a test hook)."""
+    w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+    if w.size == 0:
+        raise ValueError("weights must not be empty")
+    prob = np.empty(w.size, np.float32)
+    alias = np.empty(w.size, np.uint32)
+    lp = np.empty(w.size, np.float32)
+    L.check(L.lib().fspt_light_alias_table_gpu(int(device), L.fptr(w), int(w.size), L.fptr(prob), L.u32ptr(alias), L.fptr(lp)))
+    return prob, alias, lp
+
+
 def _u32_array(a, name):
     a = np.asarray(a)
     if a.dtype.kind not in "iu":
@@ -559,6 +572,7 @@ def _sampler_seed(seed):
 PIPELINES = {"megakernel": 0, "wavefront": 1, "stream": 2}  # fspt_target_set_pipeline codes
 SAMPLERS = {"reference": 0, "sobol": 1}  # fspt_target_set_sampler codes
 LIGHTS = {"off": 0, "emitters": 1}  # fspt_target_set_lights codes
+LIGHT_BUILDERS = {"host": 0, "gpu": 1}  # fspt_scene_set_light_builder codes
 CAMERA_MODELS = {"pinhole": 0, "ortho": 1, "fisheye": 2, "equirect": 3, "stereo": 4}  # fspt_target_set_camera_model codes
 
 
@@ -651,6 +665,27 @@ class Scene:
                                                L.u32ptr(r["alias"]), L.u32ptr(r["tris"]), L.fptr(r["pick"]),
                                                L.u32ptr(r["slot_tri"])))
         return r
+
+    def set_light_builder(self, builder):
+        """Who builds the emitter light table (fspt_scene_set_light_builder): "host" (default) or "gpu" (nothing
+        but 8 bytes crosses the bus per build; the same entries, not the same bytes).  Drops an existing table; rebuilt at
+        once when a tracer of the scene has lights on."""
+        if builder not in LIGHT_BUILDERS:
+            raise ValueError("light builder must be one of %s, got %r" % (sorted(LIGHT_BUILDERS), builder))
+        L.check(L.lib().fspt_scene_set_light_builder(self._h, LIGHT_BUILDERS[builder]))
+
+    @property
+    def light_builder(self):
+        b = C.c_int()
+        L.check(L.lib().fspt_scene_get_light_builder(self._h, C.byref(b)))
+        return {v: n for n, v in LIGHT_BUILDERS.items()}[b.value]
+
+    def light_build_stats(self):
+        """(bytes device -> host, bytes host -> device, GPU ms) of the scene's last light-table build
+        (fspt_scene_light_build_stats); zeros before the first.  Blocking."""
+        d, h, ms = C.c_uint64(), C.c_uint64(), C.c_float()
+        L.check(L.lib().fspt_scene_light_build_stats(self._h, C.byref(d), C.byref(h), C.byref(ms)))
+        return int(d.value), int(h.value), float(ms.value)
 
     def light_sample_eval(self, queries):
         """The device's emitter sample for queries float32 [n, 10] = (ro.xyz, n.xyz, u0, u1, u2, u3; u1 is the

@@ -148,7 +148,7 @@ enum { FSPT_CAMERA_PINHOLE = 0, FSPT_CAMERA_ORTHO = 1, FSPT_CAMERA_FISHEYE = 2, 
 typedef struct fspt_camera_model_params { int model; float angle; float ipd; } fspt_camera_model_params;
 int fspt_target_set_camera_model(fspt_target *target, const fspt_camera_model_params *params);
 int fspt_target_get_camera_model(fspt_target *target, fspt_camera_model_params *params);
-enum { FSPT_LIGHTS_OFF = 0, FSPT_LIGHTS_EMITTERS = 1 }; /* NEE of emissive triangles: off (default, the reference bit for bit) | emitters (fspt_tuning.h) */ int fspt_target_set_lights(fspt_target *target, int mode, float emitter_fraction); int fspt_target_get_lights(fspt_target *target, int *mode, float *emitter_fraction); int fspt_scene_light_count(fspt_scene *scene, uint32_t *n_lights);
+enum { FSPT_LIGHTS_OFF = 0, FSPT_LIGHTS_EMITTERS = 1 }; /* NEE of emissive triangles: off (default, the reference bit for bit) | emitters (DESIGN 8.3; fspt_tuning.h) */ int fspt_target_set_lights(fspt_target *target, int mode, float emitter_fraction); int fspt_target_get_lights(fspt_target *target, int *mode, float *emitter_fraction); int fspt_scene_light_count(fspt_scene *scene, uint32_t *n_lights); /* who builds that table (DESIGN 8.23; fspt_tuning.h): the host (default) | the GPU (opt-in: 8 bytes cross the bus; the same entries, not the same bytes); setting it drops the table and rebuilds it when a target has the mode on; if that rebuild fails the builder stays what it was */ enum { FSPT_LIGHT_BUILDER_HOST = 0, FSPT_LIGHT_BUILDER_GPU = 1 }; int fspt_scene_set_light_builder(fspt_scene *scene, int builder); int fspt_scene_get_light_builder(fspt_scene *scene, int *builder);
 /* Several GPUs (one frame cut into 32x32 tiles over the devices of a node; the reference has nothing here - README.md:28
  * lists "Tiled rendering" as a TODO): include/fspt_multi.h, included at the end of this file. */
 

@@ -419,6 +419,19 @@ int fspt_scene_light_table(fspt_scene *scene, uint32_t *n_tris, uint32_t *n_ligh
 int fspt_light_sample_eval(fspt_scene *scene, const float *in, uint32_t n, int32_t *tri, float *out);
 /* pure host function: the Vose alias table (float64, stored float32) of n weights (finite, >= 0, some > 0) */
 int fspt_light_alias_table(const float *weights, uint32_t n, float *prob, uint32_t *alias);
+/* The GPU builder's table (fspt_scene_set_light_builder), in integers so that no summation order shows:
+ * q_e = max(1, rint(w_e / w_max 2^32)), T = sum q, mass m_e = n q_e against a bucket of T; the lights (m < T) and the heavies
+ * in entry order with their inclusive deficits D_j and excesses X_k (128-bit); light l_j keeps m and is aliased to the first
+ * heavy with X_k > D_{j-1}; heavy h_k keeps r = T + X_k - D_{j*(k)}, j*(k) = #{j : D_{j-1} < X_k}, and is aliased to h_{k+1}
+ * when r < T; prob = (float)(r / T); light_p[e] = (float)((prob_e + 2^-40 sum over the entries aliased to e of
+ * (2^40 - floor(prob_j 2^40))) / n).  At most 2^23 entries.  tests/lighttable_ref.py restates it.
+ * fspt_light_alias_table_gpu, test hook: that table of n raw weights (finite, >= 0, some > 0; a weight of 0 is kept as an
+ * entry with q = 0) on HIP device `device`; prob, alias, light_p hold n values (any may be NULL).
+ * fspt_scene_light_build_stats: what the scene's last table build - of either builder - moved over the bus, and its GPU time
+ * from HIP events around its device work (the host builder's span includes the host's work between its two launches).
+ * Zeros before the first build.  Blocking. */
+int fspt_light_alias_table_gpu(int device, const float *weights, uint32_t n, float *prob, uint32_t *alias, float *light_p);
+int fspt_scene_light_build_stats(fspt_scene *scene, uint64_t *bytes_d2h, uint64_t *bytes_h2d, float *ms);
 /* JPEG encoder, test hooks.  fspt_jpeg_coefficients_eval: stage one alone - the quantised coefficients of
  * fspt_jpeg_encode's arguments (host pointers), 64 int16 per block in zig-zag order, blocks MCU-major: per MCU Y Cb Cr
  * (4:4:4) or Y00 Y01 Y10 Y11 Cb Cr (4:2:0); coef_out holds 64 * blocks values.  fspt_jpeg_last_ms: the three stages

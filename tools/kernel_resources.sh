@@ -4,10 +4,11 @@
 # fspt_post.hip (the image chain) - and of fspt_pose.hip (k_pose_transform; k_skin_transform),
 # fspt_appearance.hip (the k_ap_* layouts), fspt_texpack.hip (k_tex_resample) and the encoders: fspt_jpeg.hip
 # (DESIGN 8.19), fspt_png.hip, fspt_exr.hip and fspt_deflate.hip (k_deflate, the last two's)
+# and fspt_lights_build.hip (the k_lt_* kernels of the GPU light-table builder)
 # (hipcc -Rpass-analysis=kernel-resource-usage), demangled, in one table.
 # usage: tools/kernel_resources.sh [extra -D flags]
 cd "$(dirname "$0")/.." || exit 1
-for f in fspt_kernels fspt_passes fspt_post fspt_pose fspt_appearance fspt_texpack fspt_jpeg fspt_png fspt_exr fspt_deflate; do
+for f in fspt_kernels fspt_passes fspt_post fspt_pose fspt_appearance fspt_texpack fspt_jpeg fspt_png fspt_exr fspt_deflate fspt_lights_build; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off ${AB_SLP:--fno-slp-vectorize} -std=c++17 -Wno-unused-value -c --cuda-device-only \
     -Rpass-analysis=kernel-resource-usage "$@" fspt_amd/csrc/$f.hip -o /tmp/${f}_res.o 2>&1
 done |

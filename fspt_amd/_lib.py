@@ -71,6 +71,15 @@ class SkinDesc(C.Structure):
                 ("morph_norm", C.POINTER(C.c_float)), ("n_morph", C.c_uint32)]
 
 
+class MeshDesc(C.Structure):
+    """fspt_mesh_desc: host pointers"""
+    _fields_ = [("vertex", C.POINTER(C.c_uint32)), ("n_vertices", C.c_uint32), ("uv", C.POINTER(C.c_double)),
+                ("smooth", C.POINTER(C.c_uint8)), ("rank", C.POINTER(C.c_uint32)), ("tri", C.POINTER(C.c_float)), ("norm", C.POINTER(C.c_float))]
+
+
+MESH_STATIC = 0xFFFFFFFF
+
+
 class SkyParams(C.Structure):
     """fspt_sky_params"""
     _fields_ = [("sun_dir", C.c_float * 3), ("turbidity", C.c_float), ("sun_intensity", C.c_float), ("sun_radius", C.c_float),
@@ -178,6 +187,17 @@ SIGNATURES = {
     "fspt_scene_last_skin_ms": (C.c_int, [_VP, _F, _F, _U32, C.POINTER(C.c_uint64)]),
     "fspt_skin_check_eval": (C.c_int, [C.POINTER(SkinDesc), C.c_uint32, C.POINTER(C.c_uint64)]),
     "fspt_skin_set_form": (C.c_int, [C.c_int]),
+    "fspt_scene_set_mesh": (C.c_int, [_VP, C.POINTER(MeshDesc)]),
+    "fspt_scene_update_vertices": (C.c_int, [_VP, _F, C.c_uint32]),
+    "fspt_scene_update_vertices_device": (C.c_int, [_VP, _VP, C.c_uint32]),
+    "fspt_multi_set_mesh": (C.c_int, [_VP, C.POINTER(MeshDesc)]),
+    "fspt_multi_update_vertices": (C.c_int, [_VP, _F, C.c_uint32]),
+    "fspt_scene_read_mesh": (C.c_int, [_VP, _F, _F]),
+    "fspt_scene_last_mesh_ms": (C.c_int, [_VP, _F, _F, _U32, C.POINTER(C.c_uint64)]),
+    "fspt_scene_last_mesh_pass_ms": (C.c_int, [_VP, _F]),
+    "fspt_mesh_frames_eval": (C.c_int, [C.c_int, C.POINTER(MeshDesc), C.c_uint32, _F, _F, _F]),
+    "fspt_f64_probe_eval": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double)]),
+    "fspt_builder_get_mesh": (C.c_int, [_VP, _U32, C.POINTER(C.c_double), _U32, _F]),
     "fspt_logic_set_stash": (C.c_int, [C.c_int]),
     "fspt_scene_rebuild_geometry": (C.c_int, [_VP, _F, _F, _U32]),
     "fspt_scene_rebuild_geometry_device": (C.c_int, [_VP, _VP, _VP, _VP]),

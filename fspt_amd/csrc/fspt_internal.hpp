@@ -2,7 +2,7 @@
 // opaque handles of include/fspt.h, the tuning defaults, and the helpers that cross file boundaries.
 //   fspt_api.cpp           the target object, every entry point that is neither the scene, a scheduler, the image chain nor a live-scene update (include/fspt.h order)
 //   fspt_scene.cpp         the scene object: fspt_scene_create's host layouts, the one install and release of every scene part, the emitter light table
-//   fspt_scene_update.cpp  what changes a live scene or reports on such a change: refit, rebuild, pose, skin, appearance, motion origin
+//   fspt_scene_update.cpp  what changes a live scene or reports on such a change: refit, rebuild, pose, skin, mesh, appearance, motion origin
 //   fspt_post.cpp          the image chain behind the accumulator: draw, denoiser, temporal stages, auto-exposure, bloom
 //   fspt_sched_batch.cpp   the batch scheduler of the wavefront pipeline (render_wavefront) and its path state
 //   fspt_sched_stream.cpp  the stream scheduler (render_stream): a fixed pool of live paths
@@ -14,7 +14,7 @@
 //   fspt_passes.hip        the passes no renderer calls: k_camera (every camera model), k_intersect, k_features, k_temporal_gbuffer,
 //                          k_adaptive_*, the test hooks; both on fspt_traverse.hpp, fspt_surface.hpp, fspt_camera_model.hpp
 //   fspt_post.hip          every kernel that reads only images: what fspt_post.cpp launches, but for k_features and k_temporal_gbuffer
-//   fspt_bvh_build.hip     the GPU BVH builder;  fspt_refit.hip  in-place refit and rebuild;  fspt_pose.hip  part transforms and skinning
+//   fspt_bvh_build.hip     the GPU BVH builder;  fspt_refit.hip  in-place refit and rebuild;  fspt_pose.hip  part transforms, skinning and the vertex-position update
 //   fspt_appearance.hip    in-place appearance update: the texture-set, atlas and environment layouts and the material part of the hit records
 //   fspt_sky.hip           the sky generator and the environment's importance bins, built on the GPU
 //   fspt_lights_build.hip  the emitter light table of a live scene, built on the GPU (opt-in)
@@ -163,6 +163,28 @@ struct fspt_scene {
     hipEvent_t ev[2] = {nullptr, nullptr};
     float last_ms = 0.0f;           // k_skin_transform of the last call
   } skin;
+  // fspt_scene_set_mesh / fspt_scene_update_vertices (fspt_pose.hip): an indexed mesh whose normal frames are
+  // derived from new vertex positions every frame.  Per triangle (current leaf order; a rebuild permutes them) the corner
+  // indices, three uv constants, a face id and the rest copy of the static ones; per vertex the incident faces by face id
+  // (a rebuild leaves them alone).  A scene that never sets a mesh allocates nothing for it; the derived arrays go to rf.stage.
+  struct Mesh {
+    uint32_t *vertex = nullptr;     // n_tris x 3 indices < n_vertices, or 3 x FSPT_MESH_STATIC (NULL: no mesh)
+    double *cst = nullptr;          // n_tris x 3: du1[1], du0[1], r of calcTangents, float64 (static: 0)
+    uint32_t *face = nullptr;       // n_tris: the face id (leaf position at set_mesh), bit 31 = smooth
+    float *rest = nullptr;          // n_tris x 9 | n_tris x 27 rest copy, or NULL when no triangle is static
+    uint32_t *adj_off = nullptr;    // n_vertices + 1: a vertex's span in adj_face (NULL: no triangle is smooth)
+    uint32_t *adj_face = nullptr;   // per incident corner a face id, ascending rank of the face
+    double *fnorm = nullptr;        // scratch, n_tris x 3 by face id: the face normals (NULL: no triangle is smooth)
+    double *vnorm = nullptr;        // scratch, n_vertices x 3: total * (1 / count)
+    float *pos = nullptr;           // the host form's upload: n_vertices x 3
+    uint32_t n_vertices = 0, n_adj = 0; // n_adj = adj_off[n_vertices], the entries of adj_face
+    uint64_t bytes = 0;            // what the arrays above hold
+    bool meshed = false;            // rf.stage holds the output of the last update_vertices, and the refit accepted it (fspt_scene_read_mesh)
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // first, last, and between the three passes
+    float last_ms = 0.0f;           // the derive kernels of the last call, first to last
+    float pass_ms[3] = {0.0f, 0.0f, 0.0f}; // k_mesh_faces | k_mesh_vertex_normals | k_mesh_smooth_frames (a flat-only mesh: the first alone)
+    uint32_t last_launches = 0;
+  } mesh;
   // fspt_scene_update_sky / _environment_auto / _environment_device (fspt_sky.hip): the last such call
   struct Sky {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -444,6 +466,13 @@ void pose_release(fspt_scene *s);
 // skin.frame) or the scene's device memory.  Runs k_skin_transform into s->rf.stage and waits.
 int skin_run(fspt_scene *s, const float *xf, const float *morph_w, bool on_device);
 void skin_release(fspt_scene *s);
+// fspt_pose.hip.  mesh_run: the derive kernels of M for T triangles from pos (n_vertices x 3 floats, device
+// memory) into stage (tri 9 T | norm 27 T) on the NULL stream; no wait; `between`: two events recorded between the passes.  mesh_update: s->mesh set, s->rf.stage allocated,
+// the call ordered; pos = host memory (uploaded to mesh.pos) or the scene's device memory.  Runs them, waits and times.
+uint32_t mesh_run(const fspt_scene::Mesh &M, uint32_t T, const float *pos, float *stage, hipEvent_t *between = nullptr);
+int mesh_update(fspt_scene *s, const float *pos, bool on_device);
+void mesh_release(fspt_scene::Mesh &M);
+int f64_probe_run(int op, const double *a, const double *b, uint32_t n, double *out);
 // the joint table's form: 0 = read from global memory, 1 = staged once per block in LDS when it fits SKIN_LDS_MAX_BYTES
 extern int g_skin_form;
 #ifndef SKIN_FORM

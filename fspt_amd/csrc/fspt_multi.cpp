@@ -233,6 +233,12 @@ int fspt_multi_set_skin(fspt_multi *m, const fspt_skin_desc *d) {
 int fspt_multi_update_skin(fspt_multi *m, const float *xf, uint32_t n_joints, const float *morph_w, uint32_t n_morph) {
   MULTI_EACH_SCENE(fspt_multi_update_skin, fspt_scene_update_skin(s, xf, n_joints, morph_w, n_morph));
 }
+int fspt_multi_set_mesh(fspt_multi *m, const fspt_mesh_desc *d) {
+  MULTI_EACH_SCENE(fspt_multi_set_mesh, fspt_scene_set_mesh(s, d));
+}
+int fspt_multi_update_vertices(fspt_multi *m, const float *pos, uint32_t n_vertices) {
+  MULTI_EACH_SCENE(fspt_multi_update_vertices, fspt_scene_update_vertices(s, pos, n_vertices));
+}
 int fspt_multi_update_materials(fspt_multi *m, const float *mat, const float *uv, const uint8_t *atlas, uint32_t atlas_res, uint32_t atlas_layers) {
   MULTI_EACH_SCENE(fspt_multi_update_materials, fspt_scene_update_materials(s, mat, uv, atlas, atlas_res, atlas_layers));
 }

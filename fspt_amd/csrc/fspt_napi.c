@@ -381,6 +381,54 @@ static napi_value SceneUpdateSkin(napi_env env, napi_callback_info info) {
   FSPT_OK_OR_THROW(fspt_scene_update_skin((fspt_scene *)h, (const float *)xf, (uint32_t)(nx / 12), nm ? (const float *)mw : NULL, (uint32_t)nm));
   return undefined(env);
 }
+/* sceneSetMesh(scene, nTris, vertex Uint32Array | null, nVertices, uv Float64Array, smooth Uint8Array | null, rank Uint32Array | null,
+ * tri Float32Array | null, norm Float32Array | null): fspt_scene_set_mesh.  vertex null drops the mesh; else per
+ * triangle 3 indices (0xFFFFFFFF three times: static), 6 raw vt values, a smooth flag, a rank, and the rest 9 / 27 floats the
+ * static triangles keep.  The guard of sceneUpdateGeometry. */
+static napi_value SceneSetMesh(napi_env env, napi_callback_info info) {
+  napi_value a[9]; void *h, *vertex = NULL, *uv = NULL, *smooth = NULL, *rank = NULL, *tri = NULL, *norm = NULL;
+  size_t nv = 0, nu = 0, ns = 0, nr = 0, nt = 0, nn = 0; uint32_t n = 0, n_vertices = 0;
+  fspt_mesh_desc d;
+  if (get_args(env, info, 9, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[1], &n));
+  if (typed(env, a[2], napi_uint32_array, 1, &vertex, &nv)) return NULL;
+  if (!vertex) { FSPT_OK_OR_THROW(fspt_scene_set_mesh((fspt_scene *)h, NULL)); return undefined(env); }
+  NAPI_OK(napi_get_value_uint32(env, a[3], &n_vertices));
+  if (typed(env, a[4], napi_float64_array, 0, &uv, &nu) || typed(env, a[5], napi_uint8_array, 1, &smooth, &ns) || typed(env, a[6], napi_uint32_array, 1, &rank, &nr) ||
+      typed(env, a[7], napi_float32_array, 1, &tri, &nt) || typed(env, a[8], napi_float32_array, 1, &norm, &nn)) return NULL;
+  if (nv != (size_t)n * 3 || nu != (size_t)n * 6 || (smooth && ns != (size_t)n) || (rank && nr != (size_t)n) || (tri && nt != (size_t)n * 9) || (norm && nn != (size_t)n * 27)) {
+    napi_throw_range_error(env, NULL, "fspt_napi: setMesh needs 3 indices (vertex), 6 doubles (uv), 1 flag (smooth), 1 rank, 9 floats (tri) and 27 floats (norm) per triangle of the scene");
+    return NULL;
+  }
+  d.vertex = (const uint32_t *)vertex; d.n_vertices = n_vertices; d.uv = (const double *)uv; d.smooth = (const uint8_t *)smooth;
+  d.rank = (const uint32_t *)rank; d.tri = (const float *)tri; d.norm = (const float *)norm;
+  FSPT_OK_OR_THROW(fspt_scene_set_mesh((fspt_scene *)h, &d));
+  return undefined(env);
+}
+/* sceneUpdateVertices(scene, pos Float32Array): fspt_scene_update_vertices with pos.length / 3 vertices. */
+static napi_value SceneUpdateVertices(napi_env env, napi_callback_info info) {
+  napi_value a[2]; void *h, *pos = NULL; size_t np = 0;
+  if (get_args(env, info, 2, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  if (typed(env, a[1], napi_float32_array, 0, &pos, &np)) return NULL;
+  if (np == 0 || np % 3) { napi_throw_range_error(env, NULL, "fspt_napi: updateVertices needs 3 floats per vertex"); return NULL; }
+  FSPT_OK_OR_THROW(fspt_scene_update_vertices((fspt_scene *)h, (const float *)pos, (uint32_t)(np / 3)));
+  return undefined(env);
+}
+/* sceneReadMesh(scene, nTris) -> { tri: Float32Array, norm: Float32Array }: fspt_scene_read_mesh. */
+static napi_value SceneReadMesh(napi_env env, napi_callback_info info) {
+  napi_value a[2], ab, tt, tn, out; void *h, *tri = NULL, *norm = NULL; uint32_t n = 0;
+  if (get_args(env, info, 2, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[1], &n));
+  NAPI_OK(napi_create_arraybuffer(env, (size_t)n * 36, &tri, &ab));
+  NAPI_OK(napi_create_typedarray(env, napi_float32_array, (size_t)n * 9, ab, 0, &tt));
+  NAPI_OK(napi_create_arraybuffer(env, (size_t)n * 108, &norm, &ab));
+  NAPI_OK(napi_create_typedarray(env, napi_float32_array, (size_t)n * 27, ab, 0, &tn));
+  FSPT_OK_OR_THROW(fspt_scene_read_mesh((fspt_scene *)h, (float *)tri, (float *)norm));
+  NAPI_OK(napi_create_object(env, &out));
+  NAPI_OK(napi_set_named_property(env, out, "tri", tt));
+  NAPI_OK(napi_set_named_property(env, out, "norm", tn));
+  return out;
+}
 /* sceneUpdateMaterials(scene, nTris, mat Float32Array, uv Float32Array | null, atlas Uint8Array | null, atlasRes, atlasLayers):
  * fspt_scene_update_materials.  12 / 6 floats per triangle of the scene; an atlas holds atlasRes^2 * atlasLayers
  * RGBA8 texels (null: the atlas of the scene's last call that carried one).  The guard of sceneUpdateGeometry. */
@@ -1817,7 +1865,7 @@ static napi_value AbiVersion(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
-      {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"sceneUpdateSky", SceneUpdateSky}, {"sceneUpdateEnvironmentAuto", SceneUpdateEnvironmentAuto}, {"skyGenerate", SkyGenerate}, {"atlasPackGpu", AtlasPackGpu}, {"sceneUpdateTextures", SceneUpdateTextures}, {"scenePatchTextures", ScenePatchTextures}, {"envBinsGpu", EnvBinsGpu}, {"sceneSetPose", SceneSetPose}, {"sceneUpdateTransforms", SceneUpdateTransforms}, {"sceneSetSkin", SceneSetSkin}, {"sceneUpdateSkin", SceneUpdateSkin}, {"targetCreate", TargetCreate},
+      {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"sceneUpdateSky", SceneUpdateSky}, {"sceneUpdateEnvironmentAuto", SceneUpdateEnvironmentAuto}, {"skyGenerate", SkyGenerate}, {"atlasPackGpu", AtlasPackGpu}, {"sceneUpdateTextures", SceneUpdateTextures}, {"scenePatchTextures", ScenePatchTextures}, {"envBinsGpu", EnvBinsGpu}, {"sceneSetPose", SceneSetPose}, {"sceneUpdateTransforms", SceneUpdateTransforms}, {"sceneSetSkin", SceneSetSkin}, {"sceneUpdateSkin", SceneUpdateSkin}, {"sceneSetMesh", SceneSetMesh}, {"sceneUpdateVertices", SceneUpdateVertices}, {"sceneReadMesh", SceneReadMesh}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
       {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"jpegBound", JpegBound}, {"jpegEncode", JpegEncode}, {"drawJpeg", DrawJpeg}, {"presentJpeg", PresentJpeg}, {"pngBound", PngBound}, {"pngEncode", PngEncode}, {"pngFilteredEval", PngFilteredEval}, {"drawPng", DrawPng}, {"exrBound", ExrBound}, {"exrEncode", ExrEncode}, {"drawExr", DrawExr}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setCameraModel", SetCameraModel}, {"cameraModel", CameraModel}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"sceneSetLightBuilder", SceneSetLightBuilder}, {"sceneGetLightBuilder", SceneGetLightBuilder}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},

@@ -5,6 +5,9 @@
 // GPU skinning (fspt_scene_set_skin / fspt_scene_update_skin): four joints and weights per triangle corner
 // and optional morph targets; a frame is one 3 x 4 matrix per joint and one weight per target.
 //   k_skin_transform   morph, blend, vertex and normal frame per corner -> the staging array (further down)
+// Vertex-position update (fspt_scene_set_mesh / fspt_scene_update_vertices): an indexed mesh; a frame is one
+// float32 position per vertex, and the normal frames are derived again by the reference's rules in float64.
+//   k_mesh_faces, k_mesh_vertex_normals, k_mesh_smooth_frames   positions -> the staging array (last in this file)
 // What the refit (fspt_refit.hip refit_run) is then fed is that staging array: the kernel below is the "deformation kernel"
 // fspt_scene_update_geometry_device was designed for.
 // Arithmetic (the contract of DESIGN 2: float32, an fma exactly where one is written; tests/pose_ref.py restates it):
@@ -158,7 +161,239 @@ void skin_launch(bool lds, uint32_t blocks, hipStream_t st, const fspt_scene::Sk
                        K.rest, rn, K.morph, K.morph_norm, mw, K.n_morph, (const float4 *)xf, K.n_joints, T, stage, stage + (size_t)T * 9);
 }
 
+// ---------------------------------------------------------------------------
+// Vertex-position update (fspt_scene_set_mesh / fspt_scene_update_vertices; tests/mesh_ref.py restates the
+// arithmetic).  A frame is pos[n_vertices][3] float32; the staging array is derived from it by obj_loader.js's rules in the
+// reference's float64: every position promoted exactly, every operation the one vector.js / scene_build.cpp writes, in that
+// order, no fma (-ffp-contract=off), sqrt and / correctly rounded (tests/test_mesh_gpu.py probes both), one float64 ->
+// float32 conversion per output.
+//   k_mesh_faces        tri = the three positions; n_f = normalize(cross(p1 - p0, p2 - p0)) to fnorm[face id] when a later
+//                       pass needs it; flat triangles get their three frames here (n_0 = n_1 = n_2 = n_f: one frame, and
+//                       the isNaN quirk can only replace all three); static triangles copy their rest 9 + 27 floats
+//   k_mesh_vertex_normals  per vertex: total = (0,0,0) + the face normals of its incident corners in ascending rank (the
+//                       CSR rows set_mesh sorted), then total * (1.0 / count); not renormalised; no atomics
+//   k_mesh_smooth_frames   smooth triangles: the corner's frame from its vertex normal, then the quirk (below)
+// A flat-only mesh runs the first kernel alone.
+// Shape: one lane per corner, 63 corners per wave (lane 63 idles, 1.6 % of the lanes), so a wave holds 21 whole triangles and
+// a corner reaches its triangle's other corners by __shfl instead of gathering their positions again or going through
+// LDS.  A lane writes 12 B of tri and 36 B of norm at c * 12 / c * 36: each store instruction of a wave covers one dense
+// span (756 B / 2 268 B; the spans of consecutive waves abut, so the partial lines at their ends are completed by the
+// neighbour).  The per-triangle constants (24 B) and face words are read by the three lanes of a triangle from the same
+// address.  What is NOT dense are the gathers by vertex index - 12 B of pos per corner in the first kernel, 24 B of vnorm per
+// corner in the third, 24 B of fnorm per incident corner in the second.  Done about them: each is issued once per corner (the
+// other two positions come by shuffle; the third kernel re-reads the positions from the tri it wrote, densely), and the
+// per-vertex pass sums a vertex of valence 6 once, not 18 times.  Left: no reordering of vertices - a mesh whose index
+// order scatters a triangle's vertices over pos pays a 64-byte sector per 12 bytes used; pos is 12 B per vertex and stays
+// L2-resident between the corners that share it.
+struct V3 { double x, y, z; };
+__device__ inline V3 v3(double x, double y, double z) { V3 r; r.x = x; r.y = y; r.z = z; return r; }
+__device__ inline V3 v_sub(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
+__device__ inline V3 v_add(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
+__device__ inline V3 v_scale(V3 a, double s) { return v3(a.x * s, a.y * s, a.z * s); }
+__device__ inline double v_dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ inline V3 v_cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, -(a.x * b.z - a.z * b.x), a.x * b.y - a.y * b.x); } // vector.js:112-117
+__device__ inline V3 v_normalize(V3 v) { // vector.js:6-13
+  const double m = __builtin_sqrt(v.x * v.x + v.y * v.y + v.z * v.z);
+  return v_scale(v, 1.0 / m);
+}
+__device__ inline V3 v_shfl(V3 a, int src) { return v3(__shfl(a.x, src), __shfl(a.y, src), __shfl(a.z, src)); }
+
+// calcTangents' loop body for one corner (obj_loader.js:88-97): the pushed tangent / bitangent, whether the reference's
+// isNaN test fires, and what it then assigns
+struct MeshFrame { V3 t, b, ft, fb; bool nan; };
+__device__ inline MeshFrame mesh_frame(V3 n, V3 pre_tangent) {
+  MeshFrame f;
+  const V3 pre_bt = v_normalize(v_cross(n, pre_tangent));
+  f.t = v_normalize(v_cross(pre_bt, n));
+  f.b = v_normalize(v_cross(n, f.t));
+  const double d = v_dot(f.t, f.b);
+  f.nan = d != d;
+  f.ft = v_cross(n, v3(0.0, 1.0, 0.0));
+  f.fb = v_cross(f.ft, n);
+  return f;
+}
+// deltaPos0 / deltaPos1 and the triangle's constants k = (du1[1], du0[1], r) -> preTangent (obj_loader.js:85)
+__device__ inline V3 mesh_pre_tangent(V3 dp0, V3 dp1, const double *k) {
+  return v_normalize(v_scale(v_sub(v_scale(dp0, k[0]), v_scale(dp1, k[1])), k[2]));
+}
+__device__ inline void mesh_store_frame(float *o, V3 n, V3 t, V3 b) {
+  o[0] = (float)n.x; o[1] = (float)n.y; o[2] = (float)n.z;
+  o[3] = (float)t.x; o[4] = (float)t.y; o[5] = (float)t.z;
+  o[6] = (float)b.x; o[7] = (float)b.y; o[8] = (float)b.z;
+}
+
+// corner c of the launch, 63 per wave: false for the idle lane and past the end
+__device__ inline bool mesh_corner(uint32_t T, size_t *c, uint32_t *lane) {
+  *lane = threadIdx.x & 63u;
+  *c = ((size_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * 63u + *lane;
+  return *lane < 63u && *c < (size_t)T * 3;
+}
+
+__global__ __launch_bounds__(256) void k_mesh_faces(const uint32_t *__restrict__ vertex, const double *__restrict__ cst, const uint32_t *__restrict__ face,
+                                                    const float *__restrict__ rest, const float *__restrict__ pos, uint32_t n_vertices, uint32_t T,
+                                                    double *__restrict__ fnorm, float *__restrict__ out_tri, float *__restrict__ out_norm) {
+  size_t c; uint32_t lane;
+  const bool live = mesh_corner(T, &c, &lane);
+  const uint32_t vi = live ? vertex[c] : FSPT_MESH_STATIC;
+  const bool moves = vi < n_vertices; // (set_mesh checked the indices: a live corner is this or static)
+  float p[3] = {0.0f, 0.0f, 0.0f};
+  if (moves) { p[0] = pos[(size_t)vi * 3]; p[1] = pos[(size_t)vi * 3 + 1]; p[2] = pos[(size_t)vi * 3 + 2]; }
+  const uint32_t i = lane % 3u; // (63 = 21 x 3: the corner's place in its triangle)
+  const int b = (int)(lane - i);
+  V3 q[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) q[k] = v3((double)__shfl(p[0], b + k), (double)__shfl(p[1], b + k), (double)__shfl(p[2], b + k));
+  if (!live) return;
+  const size_t t = c / 3;
+  if (!moves) { // a static triangle: its rest copy
+    if (vi != FSPT_MESH_STATIC || !rest) return;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out_tri[c * 3 + k] = rest[c * 3 + k];
+    const float *rn = rest + (size_t)T * 9 + c * 9;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) out_norm[c * 9 + k] = rn[k];
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out_tri[c * 3 + k] = p[k];
+  const V3 e1 = v_sub(q[1], q[0]), e2 = v_sub(q[2], q[0]);
+  const V3 n = v_normalize(v_cross(e1, e2)); // obj_loader.js:40-44
+  const uint32_t fw = face[t], f = fw & 0x7FFFFFFFu;
+  if (fnorm && f < T) fnorm[(size_t)f * 3 + i] = i == 0 ? n.x : (i == 1 ? n.y : n.z); // (the triangle's three lanes hold the same n)
+  if (fw >> 31) return; // smooth: k_mesh_smooth_frames writes its frames
+  const MeshFrame fr = mesh_frame(n, mesh_pre_tangent(e1, e2, cst + t * 3));
+  // the three corners share n, so they share the test: the quirk assigns all of 0..2 or none
+  mesh_store_frame(out_norm + c * 9, n, fr.nan ? fr.ft : fr.t, fr.nan ? fr.fb : fr.b);
+}
+
+__global__ __launch_bounds__(256) void k_mesh_vertex_normals(const uint32_t *__restrict__ adj_off, const uint32_t *__restrict__ adj_face, uint32_t n_adj,
+                                                             const double *__restrict__ fnorm, uint32_t T, uint32_t n_vertices, double *__restrict__ vnorm) {
+  const size_t v = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if (v >= n_vertices) return;
+  const uint32_t lo = adj_off[v], hi = adj_off[v + 1];
+  if (lo >= hi || hi > n_adj) return; // no incident corner: nothing reads it
+  V3 total = v3(0.0, 0.0, 0.0);
+  for (uint32_t k = lo; k < hi; ++k) { // obj_loader.js:46-52, in the order the faces were pushed
+    const uint32_t f = adj_face[k];
+    if (f >= T) return; // (set_mesh made the rows: never taken)
+    total = v_add(total, v3(fnorm[(size_t)f * 3], fnorm[(size_t)f * 3 + 1], fnorm[(size_t)f * 3 + 2]));
+  }
+  const V3 m = v_scale(total, 1.0 / (double)(hi - lo));
+  vnorm[v * 3] = m.x; vnorm[v * 3 + 1] = m.y; vnorm[v * 3 + 2] = m.z;
+}
+
+// The quirk of obj_loader.js:93-99, literally.  `triangle.tangents` starts empty; corner i pushes its tangent, and when
+// its isNaN test fires it first ASSIGNS the fallback at index i (growing the array to i + 1 when it is shorter).  With f
+// the first corner whose test fires, the array's entries 0..2 - what the record takes - are therefore
+//   i < f: T_i      i == f: fallback_i      i > f: fallback_i if corner i's test fires, else T_(i-1) (pushed one place late)
+// and the bitangents alike.  Patterns {2}, {1,2}, {0,1,2} end finite; {0}, {0,2} leave T_0's NaN at corner 1 and {1},
+// {0,1} leave T_1's at corner 2, which the refit's check then refuses.
+__global__ __launch_bounds__(256) void k_mesh_smooth_frames(const uint32_t *__restrict__ vertex, const double *__restrict__ cst, const uint32_t *__restrict__ face,
+                                                            const double *__restrict__ vnorm, uint32_t n_vertices, uint32_t T,
+                                                            const float *__restrict__ out_tri, float *__restrict__ out_norm) {
+  size_t c; uint32_t lane;
+  const bool live = mesh_corner(T, &c, &lane);
+  const size_t t = c / 3;
+  const uint32_t vi = live ? vertex[c] : FSPT_MESH_STATIC;
+  const bool smooth = live && vi < n_vertices && (face[t] >> 31);
+  if (!__any(smooth)) return; // (wave-uniform)
+  float p[3] = {0.0f, 0.0f, 0.0f};
+  if (smooth) { p[0] = out_tri[c * 3]; p[1] = out_tri[c * 3 + 1]; p[2] = out_tri[c * 3 + 2]; } // the positions k_mesh_faces copied: dense
+  const uint32_t i = lane % 3u;
+  const int b = (int)(lane - i);
+  V3 q[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) q[k] = v3((double)__shfl(p[0], b + k), (double)__shfl(p[1], b + k), (double)__shfl(p[2], b + k));
+  V3 n = v3(0.0, 0.0, 0.0);
+  MeshFrame fr;
+  fr.t = fr.b = fr.ft = fr.fb = n;
+  fr.nan = false;
+  if (smooth) {
+    n = v3(vnorm[(size_t)vi * 3], vnorm[(size_t)vi * 3 + 1], vnorm[(size_t)vi * 3 + 2]);
+    fr = mesh_frame(n, mesh_pre_tangent(v_sub(q[1], q[0]), v_sub(q[2], q[0]), cst + t * 3));
+  }
+  V3 et = fr.t, eb = fr.b; // entry i of the arrays when no test fired before corner i
+  if (__any(fr.nan)) { // (wave-uniform; rare)
+    const int fired = fr.nan ? 1 : 0;
+    const int n0 = __shfl(fired, b), n1 = __shfl(fired, b + 1), n2 = __shfl(fired, b + 2);
+    const int prev = lane ? (int)lane - 1 : 0;
+    const V3 pt = v_shfl(fr.t, prev), pb = v_shfl(fr.b, prev);
+    const uint32_t first = n0 ? 0u : (n1 ? 1u : (n2 ? 2u : 3u));
+    if (fr.nan) { et = fr.ft; eb = fr.fb; }   // i == first, or a later corner whose own test fires
+    else if (i > first) { et = pt; eb = pb; } // the push of corner i - 1, one place late
+  }
+  if (smooth) mesh_store_frame(out_norm + c * 9, n, et, eb);
+}
+
+// f64 sqrt (op 0) and / (op 1) as this file's kernels compile them (fspt_f64_probe_eval)
+__global__ __launch_bounds__(256) void k_f64_probe(int op, const double *__restrict__ a, const double *__restrict__ b, uint32_t n, double *__restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  out[i] = op == 0 ? __builtin_sqrt(a[i]) : a[i] / b[i];
+}
+
 } // namespace
+
+uint32_t mesh_run(const fspt_scene::Mesh &M, uint32_t T, const float *pos, float *stage, hipEvent_t *between) {
+  if (!T) return 0;
+  hipStream_t st = nullptr;
+  const size_t waves = ((size_t)T * 3 + 62) / 63;
+  const uint32_t blocks = (uint32_t)((waves + 3) / 4);
+  float *out_tri = stage, *out_norm = stage + (size_t)T * 9;
+  const bool smooth = M.adj_off != nullptr;
+  hipLaunchKernelGGL(k_mesh_faces, dim3(blocks), dim3(256), 0, st, M.vertex, M.cst, M.face, M.rest, pos, M.n_vertices, T, smooth ? M.fnorm : nullptr, out_tri, out_norm);
+  if (!smooth) return 1;
+  if (between) (void)hipEventRecord(between[0], st);
+  hipLaunchKernelGGL(k_mesh_vertex_normals, dim3((M.n_vertices + 255u) / 256u), dim3(256), 0, st, M.adj_off, M.adj_face, M.n_adj, M.fnorm, T, M.n_vertices, M.vnorm);
+  if (between) (void)hipEventRecord(between[1], st);
+  hipLaunchKernelGGL(k_mesh_smooth_frames, dim3(blocks), dim3(256), 0, st, M.vertex, M.cst, M.face, M.vnorm, M.n_vertices, T, out_tri, out_norm);
+  return 3;
+}
+
+void mesh_release(fspt_scene::Mesh &M) {
+  hipFree(M.vertex); hipFree(M.cst); hipFree(M.face); hipFree(M.rest); hipFree(M.adj_off); hipFree(M.adj_face);
+  hipFree(M.fnorm); hipFree(M.vnorm); hipFree(M.pos);
+  for (hipEvent_t &e : M.ev) if (e) { hipEventDestroy(e); e = nullptr; }
+  M = fspt_scene::Mesh();
+}
+
+int mesh_update(fspt_scene *s, const float *pos, bool on_device) {
+  fspt_scene::Mesh &M = s->mesh;
+  for (hipEvent_t &e : M.ev) if (!e) HIP_TRY(hipEventCreate(&e));
+  if (!on_device) {
+    HIP_TRY(hipMemcpy(M.pos, pos, (size_t)M.n_vertices * 12, hipMemcpyHostToDevice));
+    pos = M.pos;
+  }
+  hipStream_t st = nullptr;
+  HIP_TRY(hipEventRecord(M.ev[0], st));
+  M.last_launches = mesh_run(M, s->n_tris, pos, s->rf.stage, M.ev + 2);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(M.ev[1], st));
+  HIP_TRY(hipEventSynchronize(M.ev[1]));
+  HIP_TRY(hipEventElapsedTime(&M.last_ms, M.ev[0], M.ev[1]));
+  M.pass_ms[0] = M.last_ms; M.pass_ms[1] = M.pass_ms[2] = 0.0f;
+  if (M.last_launches == 3) { // faces | vertex normals | smooth frames
+    HIP_TRY(hipEventElapsedTime(&M.pass_ms[0], M.ev[0], M.ev[2]));
+    HIP_TRY(hipEventElapsedTime(&M.pass_ms[1], M.ev[2], M.ev[3]));
+    HIP_TRY(hipEventElapsedTime(&M.pass_ms[2], M.ev[3], M.ev[1]));
+  }
+  M.meshed = false; // (fspt_scene_update_vertices sets it once the refit has accepted the arrays)
+  s->pose.posed = false; // (the staging array no longer holds a pose's or a skin's output)
+  s->skin.skinned = false;
+  return FSPT_OK;
+}
+
+int f64_probe_run(int op, const double *a, const double *b, uint32_t n, double *out) {
+  double *d = nullptr;
+  HIP_TRY(hipMalloc((void **)&d, (size_t)n * 24));
+  struct Free { double *p; ~Free() { hipFree(p); } } guard{d};
+  HIP_TRY(hipMemcpy(d, a, (size_t)n * 8, hipMemcpyHostToDevice));
+  if (op == 1) HIP_TRY(hipMemcpy(d + n, b, (size_t)n * 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_f64_probe, dim3((n + 255u) / 256u), dim3(256), 0, nullptr, op, d, d + n, n, d + 2 * (size_t)n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, d + 2 * (size_t)n, (size_t)n * 8, hipMemcpyDeviceToHost));
+  return FSPT_OK;
+}
 
 int g_skin_form = SKIN_FORM; // the shipped joint-table form, or fspt_skin_set_form's
 
@@ -192,6 +427,7 @@ int skin_run(fspt_scene *s, const float *xf, const float *morph_w, bool on_devic
   HIP_TRY(hipEventElapsedTime(&K.last_ms, K.ev[0], K.ev[1]));
   K.skinned = true;
   s->pose.posed = false; // (the staging array no longer holds a pose's output)
+  s->mesh.meshed = false;
   return FSPT_OK;
 }
 
@@ -224,6 +460,7 @@ int pose_run(fspt_scene *s, const float *mats_host) {
   HIP_TRY(hipEventElapsedTime(&P.last_ms, P.ev[0], P.ev[1]));
   P.posed = true;
   s->skin.skinned = false; // (the staging array no longer holds a skin's output)
+  s->mesh.meshed = false;
   return FSPT_OK;
 }
 

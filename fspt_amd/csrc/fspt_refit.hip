@@ -7,7 +7,7 @@
 //   k_refit_quads       the two-level nodes from the refitted 64-byte nodes + fspt_scene_create's usability test
 // and what installs a NEW tree over the same triangles (fspt_scene_rebuild_geometry; rebuild_run below):
 //   k_rebuild_slot_map  triangle -> the old leaf slot of the leaf that owns it (one writer per triangle)
-//   k_rebuild_permute   the caller's tri / norm in the new leaf order (what refit_run is then fed); the pose of DESIGN 8.14, the skin of 8.16
+//   k_rebuild_permute   the caller's tri / norm in the new leaf order (what refit_run is then fed); the pose of DESIGN 8.14, the skin of 8.16, the mesh of 8.24
 //   k_rebuild_gather    per NEW leaf slot: the 192-byte hit record of its triangle's old slot (12 lanes x 16 bytes), slot_tri,
 //                       and the "-1" padding of the leaf records
 //   k_rebuild_nodes     the interior nodes' child references
@@ -314,6 +314,7 @@ struct RebuildGuard {
   uint32_t *p_part = nullptr; // the pose in the new leaf order
   float *p_rest = nullptr;
   void *k_new[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // the skin in the new leaf order: joints, weights, rest, morph, morph_norm
+  void *m_new[4] = {nullptr, nullptr, nullptr, nullptr}; // the mesh in the new leaf order: vertex, cst, face, rest
   hipEvent_t ev[2] = {nullptr, nullptr};
   bool keep = false;
   ~RebuildGuard() {
@@ -324,6 +325,7 @@ struct RebuildGuard {
     geometry_free(ns);
     hipFree(p_part); hipFree(p_rest);
     for (void *p : k_new) hipFree(p);
+    for (void *p : m_new) hipFree(p);
     refit_release(&ns);
   }
 };
@@ -406,6 +408,12 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
       {K.joints, 6u, 1}, {K.weights, 12u, 1}, {K.rest, K.has_norm ? 36u : 9u, 1}, {K.morph, 9u, K.n_morph}, {K.morph_norm, 27u, K.n_morph}};
   for (int a = 0; K.joints && a < 5; ++a)
     if (k_old[a].src) REBUILD_ALLOC(&G.k_new[a], (size_t)T * k_old[a].words * 4 * k_old[a].slices);
+  // the mesh's per-triangle arrays alike (float64 constants as two words each); its vertex -> face rows and the face
+  // normals they index are in face ids, which a rebuild does not change, and stay as they are
+  const fspt_scene::Mesh &M = s->mesh;
+  const struct { const void *src; uint32_t words; } m_old[4] = {{M.vertex, 3u}, {M.cst, 6u}, {M.face, 1u}, {M.rest, 36u}};
+  for (int a = 0; M.vertex && a < 4; ++a)
+    if (m_old[a].src) REBUILD_ALLOC(&G.m_new[a], (size_t)T * m_old[a].words * 4);
   rc = refit_prepare(&ns);
   if (rc) return rc;
   HIP_TRY(hipEventCreate(&G.ev[0]));
@@ -446,6 +454,19 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
     for (size_t m = 0; m < k_old[a].slices; ++m, ++launches)
       hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * W, BS)), dim3(BS), 0, st, src + m * T * W, G.bt.order, T, W, dst + m * T * W);
   }
+  for (int a = 0; M.vertex && a < 4; ++a) { // the mesh follows its triangles; rest = 9 T vertices | 27 T records
+    if (!m_old[a].src) continue;
+    const float *src = (const float *)m_old[a].src;
+    float *dst = (float *)G.m_new[a];
+    if (a == 3) {
+      hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 9, BS)), dim3(BS), 0, st, src, G.bt.order, T, 9u, dst);
+      hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 27, BS)), dim3(BS), 0, st, src + (size_t)T * 9, G.bt.order, T, 27u, dst + (size_t)T * 9);
+      launches += 2;
+      continue;
+    }
+    hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * m_old[a].words, BS)), dim3(BS), 0, st, src, G.bt.order, T, m_old[a].words, dst);
+    ++launches;
+  }
   hipLaunchKernelGGL(k_rebuild_gather, dim3(blocks_for(n_slots * 12, BS)), dim3(BS), 0, st, (const float4 *)s->shade, old_slots, G.d_map, G.bt.order,
                      ns.rf.d_leaf, nl, LS, T, (float4 *)ns.shade, (uint32_t *)ns.slot_tri, (float *)ns.tris);
   ++launches;
@@ -480,6 +501,12 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
     Ks.joints = (uint16_t *)G.k_new[0]; Ks.weights = (float *)G.k_new[1]; Ks.rest = (float *)G.k_new[2];
     Ks.morph = (float *)G.k_new[3]; Ks.morph_norm = (float *)G.k_new[4];
     Ks.skinned = false;
+  }
+  if (s->mesh.vertex) {
+    fspt_scene::Mesh &Ms = s->mesh;
+    hipFree(Ms.vertex); hipFree(Ms.cst); hipFree(Ms.face); hipFree(Ms.rest);
+    Ms.vertex = (uint32_t *)G.m_new[0]; Ms.cst = (double *)G.m_new[1]; Ms.face = (uint32_t *)G.m_new[2]; Ms.rest = (float *)G.m_new[3];
+    Ms.meshed = false;
   }
   s->rf = std::move(ns.rf);
   s->motion = ns.motion; s->nodes = ns.nodes; s->quads = ns.quads; s->tris = ns.tris; s->slot_tri = ns.slot_tri; s->shade = ns.shade;

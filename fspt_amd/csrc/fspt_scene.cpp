@@ -717,6 +717,7 @@ int fspt_scene_destroy(fspt_scene *s) {
   fspt::appearance_release(s);
   fspt::pose_release(s);
   fspt::skin_release(s);
+  fspt::mesh_release(s->mesh);
   fspt::sky_release(s);
   fspt::lights_release(s);
   for (hipEvent_t &ev : s->lg.host_ev) if (ev) hipEventDestroy(ev);

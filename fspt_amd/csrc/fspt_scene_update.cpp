@@ -1,5 +1,5 @@
 // fspt_scene_update.cpp - every entry that changes a live scene, or reports on such a change: in-place geometry update
-// (DESIGN 8.6), rebuild (8.7), appearance update (8.13), part transforms (8.14), skinning (8.16), the GPU sky (8.17), the motion origin (8.8)
+// (DESIGN 8.6), rebuild (8.7), appearance update (8.13), part transforms (8.14), skinning (8.16), the vertex-position update (8.24), the GPU sky (8.17), the motion origin (8.8)
 // and the read-outs that go with them.  What the families share stands once, first; every refusal names the calling entry.
 #include "fspt_internal.hpp"
 #include "fspt_texpack_check.hpp"
@@ -47,7 +47,7 @@ static int begin_refit(fspt_scene *s) {
   return rc ? rc : fspt::refit_prepare(s);
 }
 
-// The staging array, tri (T x 9) | norm (T x 27): made by the first call that fills it - a host-form upload, a pose or a skin.
+// The staging array, tri (T x 9) | norm (T x 27): made by the first call that fills it - a host-form upload, a pose, a skin or a mesh.
 // (Not a part of begin_refit: the device forms of update_geometry / rebuild_geometry never fill it and allocate nothing for it.)
 static int stage_ensure(fspt_scene *s) {
   const size_t T = s->n_tris;
@@ -62,6 +62,7 @@ static int stage_upload(fspt_scene *s, const float *&tri, const float *&norm) {
   const size_t T = s->n_tris;
   s->pose.posed = false; // (the staging array no longer holds a pose's or a skin's output)
   s->skin.skinned = false;
+  s->mesh.meshed = false;
   HIP_TRY(hipMemcpy(s->rf.stage, tri, T * 9 * 4, hipMemcpyHostToDevice));
   if (norm) HIP_TRY(hipMemcpy(s->rf.stage + T * 9, norm, T * 27 * 4, hipMemcpyHostToDevice));
   tri = s->rf.stage;
@@ -69,7 +70,7 @@ static int stage_upload(fspt_scene *s, const float *&tri, const float *&norm) {
   return FSPT_OK;
 }
 
-// The staging array's tri / norm (either may be NULL) to the host: what the last pose or skin wrote.
+// The staging array's tri / norm (either may be NULL) to the host: what the last pose, skin or mesh update wrote.
 static int stage_download(fspt_scene *s, float *tri, float *norm) {
   const int rc = check_device(s->device);
   if (rc) return rc;
@@ -384,6 +385,206 @@ int fspt_scene_last_skin_ms(fspt_scene *s, float *skin_ms, float *refit_ms, uint
   if (launches) *launches = s->rf.last_launches + 1u;
   if (bytes) *bytes = skin_bytes(s);
   return FSPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// vertex-position update (kernels in fspt_pose.hip)
+// ---------------------------------------------------------------------------
+// What fspt_scene_set_mesh derives on the host, once: the uv constants of calcTangents in float64 (scene_build.cpp's
+// statement of obj_loader.js:72-84), the face words, and the vertex -> face rows sorted by rank.
+struct MeshHost {
+  std::vector<double> cst;
+  std::vector<uint32_t> face, adj_off, adj_face;
+  bool any_static = false, any_smooth = false;
+};
+
+// fspt_scene_set_mesh's validation and host work: no device.  FSPT_OK, or FSPT_E_INVALID with the error set and *bad = the index.
+static int mesh_check(const fspt_mesh_desc *d, size_t T, const char *fn, uint64_t *bad, MeshHost &H) {
+  if (!d || !d->vertex || !d->uv) { fspt_set_error("%s: the description, vertex or uv is NULL", fn); return FSPT_E_INVALID; }
+  if (d->n_vertices == 0 || d->n_vertices == FSPT_MESH_STATIC) { fspt_set_error("%s: n_vertices = %u, must lie in [1, 2^32 - 2]", fn, d->n_vertices); return FSPT_E_INVALID; }
+  if (T >= (1u << 31)) { fspt_set_error("%s: %zu triangles, at most 2^31 - 1", fn, T); return FSPT_E_INVALID; }
+  H.cst.assign(T * 3, 0.0);
+  H.face.resize(T);
+  const double EPS = 2.220446049250313e-16; // Number.EPSILON
+  for (size_t t = 0; t < T; ++t) {
+    const uint32_t *v = d->vertex + t * 3;
+    const int n_static = (v[0] == FSPT_MESH_STATIC) + (v[1] == FSPT_MESH_STATIC) + (v[2] == FSPT_MESH_STATIC);
+    const bool smooth = d->smooth && d->smooth[t];
+    H.face[t] = (uint32_t)t | (smooth && !n_static ? 0x80000000u : 0u);
+    if (n_static == 3) {
+      if (!d->tri || !d->norm) { *bad = t; fspt_set_error("%s: triangle %zu is static but the rest tri / norm is NULL", fn, t); return FSPT_E_INVALID; }
+      for (size_t i = 0; i < 36; ++i) {
+        const float x = i < 9 ? d->tri[t * 9 + i] : d->norm[t * 27 + (i - 9)];
+        if (!std::isfinite(x)) { *bad = t; fspt_set_error("%s: static triangle %zu: a rest value is not finite", fn, t); return FSPT_E_INVALID; }
+      }
+      H.any_static = true;
+      continue;
+    }
+    if (n_static) { *bad = t; fspt_set_error("%s: triangle %zu is only partly static", fn, t); return FSPT_E_INVALID; }
+    for (int i = 0; i < 3; ++i)
+      if (v[i] >= d->n_vertices) { *bad = t * 3 + i; fspt_set_error("%s: vertex[%zu] = %u, n_vertices = %u", fn, t * 3 + i, v[i], d->n_vertices); return FSPT_E_INVALID; }
+    double uv[3][2];
+    for (int i = 0; i < 3; ++i)
+      for (int k = 0; k < 2; ++k) {
+        const double raw = d->uv[t * 6 + i * 2 + k];
+        if (!std::isfinite(raw)) { *bad = t * 6 + i * 2 + k; fspt_set_error("%s: uv[%zu] is not finite (a triangle without vt can only be static)", fn, t * 6 + i * 2 + k); return FSPT_E_INVALID; }
+        uv[i][k] = raw + EPS * (i + 1);
+      }
+    const double du0[2] = {uv[1][0] - uv[0][0], uv[1][1] - uv[0][1]};
+    const double du1[2] = {uv[2][0] - uv[0][0], uv[2][1] - uv[0][1]};
+    const double r = 1.0 / ((du0[0] * du1[1]) - (du0[1] * du1[0]));
+    H.cst[t * 3] = du1[1]; H.cst[t * 3 + 1] = du0[1]; H.cst[t * 3 + 2] = r; // (r may be inf / NaN: degenerate uvs, the quirk's case)
+    H.any_smooth = H.any_smooth || smooth;
+  }
+  // the order the face normals are summed in
+  std::vector<uint32_t> by_rank(T);
+  for (size_t t = 0; t < T; ++t) by_rank[t] = (uint32_t)t;
+  if (d->rank) {
+    std::sort(by_rank.begin(), by_rank.end(), [&](uint32_t a, uint32_t b) { return d->rank[a] < d->rank[b]; });
+    for (size_t k = 1; k < T; ++k)
+      if (d->rank[by_rank[k]] == d->rank[by_rank[k - 1]]) { *bad = by_rank[k]; fspt_set_error("%s: rank %u is given to triangles %u and %u", fn, d->rank[by_rank[k]], by_rank[k - 1], by_rank[k]); return FSPT_E_INVALID; }
+  }
+  if (!H.any_smooth) return FSPT_OK;
+  H.adj_off.assign((size_t)d->n_vertices + 1, 0u);
+  for (size_t t = 0; t < T; ++t)
+    for (int i = 0; i < 3; ++i)
+      if (d->vertex[t * 3 + i] != FSPT_MESH_STATIC) ++H.adj_off[(size_t)d->vertex[t * 3 + i] + 1];
+  for (size_t v = 0; v < d->n_vertices; ++v) H.adj_off[v + 1] += H.adj_off[v];
+  H.adj_face.resize(H.adj_off[d->n_vertices]);
+  std::vector<uint32_t> at(H.adj_off.begin(), H.adj_off.end() - 1);
+  for (size_t k = 0; k < T; ++k) { // a face that names a vertex twice is pushed twice (obj_loader.js:154-158)
+    const uint32_t t = by_rank[k];
+    for (int i = 0; i < 3; ++i)
+      if (d->vertex[(size_t)t * 3 + i] != FSPT_MESH_STATIC) H.adj_face[at[d->vertex[(size_t)t * 3 + i]]++] = t;
+  }
+  return FSPT_OK;
+}
+
+// the device side of a checked description; the new arrays first (a failure leaves *out untouched and frees its own)
+static hipError_t mesh_upload(const fspt_mesh_desc *d, size_t T, const MeshHost &H, fspt_scene::Mesh *out) {
+  fspt_scene::Mesh N;
+  const size_t T1 = T ? T : 1, nv = d->n_vertices, na = H.adj_face.size();
+  const bool sm = H.any_smooth, st = H.any_static;
+  const DevicePart parts[] = {
+      {(void **)&N.vertex, d->vertex, T * 12, T1 * 12, 0}, {(void **)&N.cst, H.cst.data(), T * 24, T1 * 24, 0}, {(void **)&N.face, H.face.data(), T * 4, T1 * 4, 0},
+      {(void **)&N.pos, nullptr, 0, nv * 12, 0},
+      {(void **)&N.rest, st ? d->tri : nullptr, T * 36, st ? T1 * 144 : 0, 0}, {(void **)&N.rest, st ? d->norm : nullptr, T * 108, 0, T * 36},
+      {(void **)&N.adj_off, sm ? H.adj_off.data() : nullptr, (nv + 1) * 4, sm ? (nv + 1) * 4 : 0, 0},
+      {(void **)&N.adj_face, sm ? H.adj_face.data() : nullptr, na * 4, sm ? (na ? na : 1) * 4 : 0, 0},
+      {(void **)&N.fnorm, nullptr, 0, sm ? T1 * 24 : 0, 0}, {(void **)&N.vnorm, nullptr, 0, sm ? nv * 24 : 0, 0}};
+  const hipError_t e = alloc_and_upload(parts, sizeof(parts) / sizeof(parts[0]));
+  if (e != hipSuccess) return e;
+  N.n_vertices = d->n_vertices;
+  N.n_adj = (uint32_t)na;
+  N.bytes = 0;
+  for (const DevicePart &p : parts) N.bytes += p.alloc;
+  *out = N;
+  return hipSuccess;
+}
+
+static int mesh_refuse_hip(const char *fn, hipError_t e, size_t T, uint32_t nv) {
+  fspt_set_error("%s: %s (%zu triangles, %u vertices)", fn, hipGetErrorString(e), T, nv);
+  return e == hipErrorOutOfMemory ? FSPT_E_NOMEM : FSPT_E_HIP;
+}
+
+int fspt_scene_set_mesh(fspt_scene *s, const fspt_mesh_desc *d) {
+  const char *fn = "fspt_scene_set_mesh";
+  if (!s) { fspt_set_error("%s: NULL scene", fn); return FSPT_E_INVALID; }
+  if (!d) { // drop the mesh
+    if (!s->mesh.vertex) return FSPT_OK;
+    int rc = check_device(s->device);
+    if (rc) return rc;
+    fspt::mesh_release(s->mesh);
+    return FSPT_OK;
+  }
+  const size_t T = s->n_tris;
+  uint64_t bad = 0;
+  MeshHost H;
+  int rc = mesh_check(d, T, fn, &bad, H);
+  if (rc) return rc;
+  if (!s->rf.ok) return refuse_not_refittable(fn);
+  if ((rc = check_device(s->device))) return rc;
+  fspt_scene::Mesh N; // the new arrays first: an allocation that fails leaves the old mesh
+  const hipError_t e = mesh_upload(d, T, H, &N);
+  if (e != hipSuccess) return mesh_refuse_hip(fn, e, T, d->n_vertices);
+  fspt::mesh_release(s->mesh);
+  s->mesh = N;
+  return FSPT_OK;
+}
+
+static int update_vertices(fspt_scene *s, const float *pos, uint32_t n_vertices, bool on_device, const char *fn) {
+  if (!s || !pos) { fspt_set_error("%s: NULL scene or pos", fn); return FSPT_E_INVALID; }
+  const fspt_scene::Mesh &M = s->mesh;
+  if (!M.vertex) { fspt_set_error("%s: the scene has no mesh (fspt_scene_set_mesh)", fn); return FSPT_E_STATE; }
+  if (n_vertices != M.n_vertices) { fspt_set_error("%s: %u positions, the mesh has %u vertices", fn, n_vertices, M.n_vertices); return FSPT_E_INVALID; }
+  if (on_device) {
+    if ((uintptr_t)pos % 4) { fspt_set_error("%s: pos must be 4-byte aligned", fn); return FSPT_E_INVALID; }
+  } else if (const int rc = check_finite(fn, "pos", pos, (size_t)n_vertices * 3)) { // no device needed: refuse before anything is touched
+    return rc;
+  }
+  int rc = begin_refit(s);
+  if (rc || (rc = stage_ensure(s)) || (rc = fspt::mesh_update(s, pos, on_device))) return rc;
+  const size_t T = s->n_tris;
+  if ((rc = refit_device_arrays(s, s->rf.stage, s->rf.stage + T * 9, fn))) return rc;
+  s->mesh.meshed = true; // (a refused frame is not handed out by fspt_scene_read_mesh)
+  return FSPT_OK;
+}
+
+int fspt_scene_update_vertices(fspt_scene *s, const float *pos, uint32_t n_vertices) {
+  return update_vertices(s, pos, n_vertices, false, "fspt_scene_update_vertices");
+}
+
+int fspt_scene_update_vertices_device(fspt_scene *s, const float *pos, uint32_t n_vertices) {
+  return update_vertices(s, pos, n_vertices, true, "fspt_scene_update_vertices_device");
+}
+
+int fspt_scene_read_mesh(fspt_scene *s, float *tri, float *norm) {
+  if (!s || (!tri && !norm)) { fspt_set_error("fspt_scene_read_mesh: NULL argument"); return FSPT_E_INVALID; }
+  if (!s->mesh.vertex || !s->mesh.meshed) { fspt_set_error("fspt_scene_read_mesh: no fspt_scene_update_vertices since the mesh was set, the scene rebuilt, posed, skinned or its geometry uploaded"); return FSPT_E_STATE; }
+  return stage_download(s, tri, norm);
+}
+
+int fspt_scene_last_mesh_ms(fspt_scene *s, float *derive_ms, float *refit_ms, uint32_t *launches, uint64_t *bytes) {
+  if (!s) { fspt_set_error("fspt_scene_last_mesh_ms: NULL scene"); return FSPT_E_INVALID; }
+  if (derive_ms) *derive_ms = s->mesh.last_ms;
+  if (refit_ms) *refit_ms = s->rf.last_ms;
+  if (launches) *launches = s->rf.last_launches + s->mesh.last_launches;
+  if (bytes) *bytes = s->mesh.vertex ? s->mesh.bytes : 0;
+  return FSPT_OK;
+}
+
+int fspt_scene_last_mesh_pass_ms(fspt_scene *s, float ms[3]) {
+  if (!s || !ms) { fspt_set_error("fspt_scene_last_mesh_pass_ms: NULL argument"); return FSPT_E_INVALID; }
+  for (int i = 0; i < 3; ++i) ms[i] = s->mesh.pass_ms[i];
+  return FSPT_OK;
+}
+
+// The derive kernels alone: no scene, no refit and so no non-finite check.  The description is validated first, without a device.
+int fspt_mesh_frames_eval(int device, const fspt_mesh_desc *d, uint32_t n_tris, const float *pos, float *tri_out, float *norm_out) {
+  const char *fn = "fspt_mesh_frames_eval";
+  uint64_t bad = 0;
+  MeshHost H;
+  int rc = mesh_check(d, n_tris, fn, &bad, H);
+  if (rc) return rc;
+  if (!pos || n_tris == 0 || (!tri_out && !norm_out)) { fspt_set_error("%s: NULL/empty argument", fn); return FSPT_E_INVALID; }
+  if ((rc = check_device(device))) return rc;
+  struct Temp { fspt_scene::Mesh M; float *stage = nullptr; ~Temp() { fspt::mesh_release(M); hipFree(stage); } } tmp;
+  hipError_t e = mesh_upload(d, n_tris, H, &tmp.M);
+  if (e == hipSuccess) e = hipMalloc((void **)&tmp.stage, (size_t)n_tris * 144);
+  if (e != hipSuccess) { (void)hipGetLastError(); return mesh_refuse_hip(fn, e, n_tris, d->n_vertices); }
+  HIP_TRY(hipMemcpy(tmp.M.pos, pos, (size_t)d->n_vertices * 12, hipMemcpyHostToDevice));
+  fspt::mesh_run(tmp.M, n_tris, tmp.M.pos, tmp.stage);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  if (tri_out) HIP_TRY(hipMemcpy(tri_out, tmp.stage, (size_t)n_tris * 36, hipMemcpyDeviceToHost));
+  if (norm_out) HIP_TRY(hipMemcpy(norm_out, tmp.stage + (size_t)n_tris * 9, (size_t)n_tris * 108, hipMemcpyDeviceToHost));
+  return FSPT_OK;
+}
+
+int fspt_f64_probe_eval(int device, int op, const double *a, const double *b, uint32_t n, double *out) {
+  if (!a || !out || !n || (op != 0 && op != 1) || (op == 1 && !b)) { fspt_set_error("fspt_f64_probe_eval: NULL/empty argument or op not 0 (sqrt) / 1 (div)"); return FSPT_E_INVALID; }
+  const int rc = check_device(device);
+  return rc ? rc : fspt::f64_probe_run(op, a, b, n, out);
 }
 
 // ---------------------------------------------------------------------------

@@ -84,6 +84,8 @@ struct Tri {
   D3 v[3];
   int vi[3];
   double uv[3][2];
+  double uv_raw[3][2];  // the vt values as parsed, before calcTangents (NaN without vt): fspt_builder_get_mesh
+  uint32_t gvi[3];       // vi made global over the OBJs
   bool has_uv0 = false;
   D3 n[3];
   std::vector<D3> tangents, bitangents;
@@ -154,6 +156,8 @@ struct fspt_builder {
   struct HostNode { Box box; int left, right; uint32_t lo, hi; bool leaf; };
   std::vector<HostNode> host_nodes;
   std::vector<uint32_t> tri_order;
+  // every OBJ's `v` lines, one after the other, as world positions (a vertex no face names included); fspt_builder_get_mesh
+  std::vector<D3> mesh_pos;
   // the last fspt_builder_build_gpu (fspt_builder_gpu_stats); gpu_built is false after fspt_builder_build
   bool gpu_built = false;
   float gpu_kernel_ms = 0.0f;
@@ -191,6 +195,8 @@ int parse_obj(fspt_builder *B, const char *text, size_t len, const fspt_prop_des
     return false;
   };
   Box prop_bounds;  // parsed.bounds (obj_loader.js:17,137-142)
+  const size_t vertex_base = B->mesh_pos.size();  // this OBJ's vertex 0 among all OBJs' vertices
+  const D3 no_pos = d3(std::numeric_limits<double>::quiet_NaN(), std::numeric_limits<double>::quiet_NaN(), std::numeric_limits<double>::quiet_NaN());
 
   auto apply_rotations = [&](D3 v) {
     for (uint32_t r = 0; r < prop->n_rotate; ++r) {
@@ -240,7 +246,12 @@ int parse_obj(fspt_builder *B, const char *text, size_t len, const fspt_prop_des
       if (i == 0) tri.has_uv0 = ok;
       tri.uv[i][0] = ok ? uvs[(size_t)ti].second.first : std::numeric_limits<double>::quiet_NaN();
       tri.uv[i][1] = ok ? uvs[(size_t)ti].second.second : std::numeric_limits<double>::quiet_NaN();
+      tri.gvi[i] = (uint32_t)(vertex_base + (size_t)vi);
+      if (B->mesh_pos.size() <= tri.gvi[i]) B->mesh_pos.resize((size_t)tri.gvi[i] + 1, no_pos);
+      B->mesh_pos[tri.gvi[i]] = tri.v[i];
     }
+    for (int i = 0; i < 3; ++i)
+      for (int k = 0; k < 2; ++k) tri.uv_raw[i][k] = tri.has_uv0 ? tri.uv[i][k] : std::numeric_limits<double>::quiet_NaN();
     for (int i = 0; i < 3; ++i) tri.box.add_vertex(tri.v[i]);
     for (int i = 0; i < 3; ++i) {  // Vec3.max(bounds.max, vert) / Vec3.min(bounds.min, vert)
       prop_bounds.mx = d3(jsmax(prop_bounds.mx.x, tri.v[i].x), jsmax(prop_bounds.mx.y, tri.v[i].y), jsmax(prop_bounds.mx.z, tri.v[i].z));
@@ -417,6 +428,9 @@ int parse_obj(fspt_builder *B, const char *text, size_t len, const fspt_prop_des
   // main.js:317-318: bounds.addVertex(parsed.bounds.max); bounds.addVertex(parsed.bounds.min)
   B->bounds.add_vertex(prop_bounds.mx);
   B->bounds.add_vertex(prop_bounds.mn);
+  B->mesh_pos.resize(vertex_base + vertices.size(), no_pos);
+  for (size_t i = 0; i < vertices.size(); ++i)  // a `v` line no face names: where the loader would have put it
+    if (std::isnan(B->mesh_pos[vertex_base + i].x)) B->mesh_pos[vertex_base + i] = apply_transforms(vertices[i], false);
   return 0;
 }
 
@@ -671,6 +685,7 @@ int fspt_builder_normalize(fspt_builder *b, double size) {
   double sc = 2 * size / longest;
   for (auto &t : b->geometry)
     for (int j = 0; j < 3; ++j) t.v[j] = scale(sub(t.v[j], centroid), sc);
+  for (D3 &v : b->mesh_pos) v = scale(sub(v, centroid), sc);
   b->built = false;
   return FSPT_OK;
 }
@@ -876,6 +891,22 @@ int fspt_builder_geometry(const fspt_builder *b, uint32_t *n_tris, float *tri, f
   if (mat) std::memcpy(mat, vm.data(), vm.size() * 4);
   if (norm) std::memcpy(norm, vn.data(), vn.size() * 4);
   if (uv) std::memcpy(uv, vu.data(), vu.size() * 4);
+  return FSPT_OK;
+}
+
+int fspt_builder_get_mesh(const fspt_builder *b, uint32_t *vertex, double *uv, uint32_t *n_vertices, float *positions) {
+  if (!b || !b->built) { fspt_set_error("fspt_builder_get_mesh: builder not built"); return FSPT_E_STATE; }
+  if (n_vertices) *n_vertices = (uint32_t)b->mesh_pos.size();
+  for (size_t k = 0; k < b->tri_order.size(); ++k) {
+    const Tri &t = b->geometry[b->tri_order[k]];
+    for (int i = 0; i < 3; ++i) {
+      if (vertex) vertex[k * 3 + i] = t.gvi[i];
+      if (uv) { uv[k * 6 + i * 2] = t.uv_raw[i][0]; uv[k * 6 + i * 2 + 1] = t.uv_raw[i][1]; }
+    }
+  }
+  for (size_t v = 0; positions && v < b->mesh_pos.size(); ++v) {
+    positions[v * 3] = (float)b->mesh_pos[v].x; positions[v * 3 + 1] = (float)b->mesh_pos[v].y; positions[v * 3 + 2] = (float)b->mesh_pos[v].z;
+  }
   return FSPT_OK;
 }
 

@@ -857,6 +857,40 @@ class PathTracer {
     if (morphWeights != null && !(morphWeights instanceof Float32Array)) throw new RangeError('updateSkin: morphWeights must be a Float32Array of n_morph floats');
     addon.sceneUpdateSkin(this._scene, xf, morphWeights == null || morphWeights.length === 0 ? null : morphWeights);
   }
+  /** Hand the scene an indexed mesh (fspt_scene_set_mesh, DESIGN 8.24): { vertex: Uint32Array, 3 indices per triangle in the
+   *  current leaf order (0xFFFFFFFF three times: a static triangle), uv: Float64Array, the 6 raw vt values per triangle,
+   *  nVertices (default max(vertex) + 1), smooth: Uint8Array | null, one flag per triangle (null: all flat), rank: Uint32Array |
+   *  null, the order a face normal is summed in (null: the leaf position), tri / norm: the rest mesh the static triangles keep
+   *  (null only when none is static) }.  setMesh(null) drops the mesh.  Nothing renders differently until updateVertices. */
+  setMesh(mesh) {
+    if (mesh == null) { addon.sceneSetMesh(this._scene, this._nTris, null, 0, null, null, null, null, null); return; }
+    const { vertex, uv, nVertices, smooth, rank, tri, norm } = mesh;
+    const n = this._nTris;
+    if (!(vertex instanceof Uint32Array) || vertex.length !== n * 3) throw new RangeError('setMesh: vertex must be a Uint32Array of ' + n + ' x 3 indices');
+    if (!(uv instanceof Float64Array) || uv.length !== n * 6) throw new RangeError('setMesh: uv must be a Float64Array of ' + n + ' x 6 values');
+    if (smooth != null && (!(smooth instanceof Uint8Array) || smooth.length !== n)) throw new RangeError('setMesh: smooth must be a Uint8Array of ' + n + ' flags');
+    if (rank != null && (!(rank instanceof Uint32Array) || rank.length !== n)) throw new RangeError('setMesh: rank must be a Uint32Array of ' + n + ' ranks');
+    if (tri != null && (!(tri instanceof Float32Array) || tri.length !== n * 9)) throw new RangeError('setMesh: tri must be a Float32Array of ' + n + ' x 9 floats');
+    if (norm != null && (!(norm instanceof Float32Array) || norm.length !== n * 27)) throw new RangeError('setMesh: norm must be a Float32Array of ' + n + ' x 27 floats');
+    let nv = 0, anyStatic = false;
+    for (let i = 0; i < vertex.length; i++) { if (vertex[i] === 0xFFFFFFFF) anyStatic = true; else if (vertex[i] >= nv) nv = vertex[i] + 1; }
+    nv = Math.max(nv, 1);
+    if (anyStatic && (tri == null || norm == null)) throw new RangeError('setMesh: static triangles need the rest tri and norm');
+    if (nVertices != null) {
+      if (!Number.isInteger(nVertices) || nVertices < nv || nVertices > 0xFFFFFFFE) throw new RangeError('setMesh: nVertices must be an integer in [max(vertex) + 1, 2^32 - 2]');
+      nv = nVertices;
+    }
+    addon.sceneSetMesh(this._scene, n, vertex, nv, uv, smooth == null ? null : smooth, rank == null ? null : rank, tri == null ? null : tri, norm == null ? null : norm);
+  }
+  /** One frame of the mesh: pos = one position per vertex (Float32Array, 3 floats each).  Kernels derive the vertices and
+   *  normal frames of every meshed triangle by the reference's rules in float64 and the tree is refitted exactly as
+   *  updateGeometry on the result would (fspt_scene_update_vertices, DESIGN 8.24). */
+  updateVertices(pos) {
+    if (!(pos instanceof Float32Array) || pos.length === 0 || pos.length % 3 !== 0) throw new RangeError('updateVertices: pos must be a Float32Array of n_vertices x 3 floats');
+    addon.sceneUpdateVertices(this._scene, pos);
+  }
+  /** { tri, norm }: the Float32Arrays (9 / 27 floats per triangle) the most recent updateVertices derived (fspt_scene_read_mesh). */
+  readMesh() { return addon.sceneReadMesh(this._scene, this._nTris); }
   /** The arguments of updateGeometry, but the scene gets a NEW tree - the binned SAH of the GPU builder over `tri` in the
    *  order given - built on the GPU and installed in place (fspt_scene_rebuild_geometry, DESIGN 8.7).  Returns a Uint32Array:
    *  order[k] = index in `tri` of the triangle now at leaf position k; later updateGeometry / rebuildGeometry calls take

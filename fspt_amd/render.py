@@ -117,6 +117,10 @@ def main(argv=None):
     ap.add_argument("--rebuild-above", type=float, default=None, metavar="R",
                     help="--bvh refit: rebuild the tree in place on the GPU when a refitted frame's SAH cost exceeds R x the cost at "
                          "the last build (DESIGN 8.7; default: never)")
+    ap.add_argument("--mesh", action="store_true",
+                    help="--bvh refit --frames: a frame whose OBJs differ from the first frame's only in their `v` lines parses "
+                         "only those; one position per vertex goes to the GPU, which derives the normals and refits (DESIGN 8.24; "
+                         "normals from float32 positions: not bit-equal to the parse path)")
     ap.add_argument("--pose", action="store_true",
                     help="--bvh refit --frames: a frame that only moves its props rigidly parses no OBJ; one matrix per prop goes to "
                          "the GPU, which poses the first frame's triangles and refits (DESIGN 8.14; float32 matrices: not bit-equal "
@@ -209,6 +213,8 @@ def main(argv=None):
         ap.error("--temporal needs --bvh refit and --frames")
     if args.pose and not (args.bvh == "refit" and args.frames):
         ap.error("--pose needs --bvh refit and --frames")
+    if args.mesh and not (args.bvh == "refit" and args.frames):
+        ap.error("--mesh needs --bvh refit and --frames")
     if args.temporal_clamp is not None and not args.temporal:
         ap.error("--temporal-clamp needs --temporal")
     if args.temporal_clamp is not None and args.temporal_clamp is not True and not args.temporal_clamp >= 0.0:
@@ -252,7 +258,7 @@ def main(argv=None):
                                     rebuild_above=args.rebuild_above,
                                     temporal=({"atrous": args.atrous, "clamp": None if args.temporal_clamp is None else True if args.temporal_clamp is True
                                                else {"sigma_scale": args.temporal_clamp}} if args.temporal else None),
-                                    variance=args.variance_guided, pose=args.pose, textures=args.textures, jpeg=jpeg, png=png, exr=exr, **kw)
+                                    variance=args.variance_guided, pose=args.pose, mesh=args.mesh, textures=args.textures, jpeg=jpeg, png=png, exr=exr, **kw)
             print(f"{len(out)} frames in {time.perf_counter() - t0:.2f} s:", *out)
         else:
             arrays, settings = F.load_scene_file(args.scene, args.assets, bvh=args.bvh, textures=args.textures)

@@ -497,7 +497,7 @@ BVH_BUILDERS = ("sah", "gpu")
 
 def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas_res=2048, images=None,
                 world_transforms=None, normalize=None, mtl_texts=None, focus_rays=None, bvh="sah", device=0,
-                keep_order=False, geometry_only=False, textures="cpu"):
+                keep_order=False, geometry_only=False, textures="cpu", keep_mesh=False):
     """initBVH (main.js:284-445) for props = list of scene-JSON prop dicts and obj_texts = {path: OBJ text}.
     env = RGBE uint8 [h*w*4] or None; world_transforms = scene.worldTransforms; normalize = scene.normalize;
     mtl_texts = {url: MTL text} for `mtllib` lines (url = <dir of the OBJ>/<name>, obj_loader.js:186);
@@ -511,7 +511,15 @@ def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas
     empty (meta["geometry_only"]); focus_rays are answered by the float64 closest hit over all triangles.  What a host of
     moving geometry needs per frame (geometry_in_leaf_order, Scene.update_geometry).
     textures = "cpu": the atlas is resampled here in numpy; "gpu": on HIP device `device` (fspt_atlas_pack_gpu, DESIGN 8.18);
-    meta["textures"] names the packer and meta["packer"] is the TexturePacker (Scene.update_textures takes it)."""
+    meta["textures"] names the packer and meta["packer"] is the TexturePacker (Scene.update_textures takes it).
+    keep_mesh=True (with keep_order): the triangles as an indexed mesh for Scene.set_mesh, in leaf order -
+    meta["tri_vertex"] [n, 3] uint32 vertex indices, global over the props' OBJs; meta["tri_uv64"] [n, 6] float64 raw vt values
+    (NaN for a triangle without vt); meta["tri_smooth"] [n] uint8, 1 where the prop's normals are "smooth";
+    meta["tri_static"] [n] bool, True where the triangle cannot be meshed (a `normals: "mesh"` prop, or no vt);
+    meta["n_vertices"]; meta["vertices"] [n_vertices, 3] float32 world positions as the builder emitted them (a `v` line no
+    face names is transformed like the others: the array can go to Scene.update_vertices as it is)."""
+    if keep_mesh and (not keep_order or geometry_only):
+        raise ValueError("keep_mesh needs keep_order=True and a built tree")
     if textures not in TEXTURE_PACKERS:
         raise ValueError(f"textures must be one of {TEXTURE_PACKERS}, not {textures!r}")
     if bvh not in BVH_BUILDERS:
@@ -595,6 +603,12 @@ def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas
         if keep_order and not geometry_only:
             order = np.zeros(nt.value, np.uint32)
             L.check(lib.fspt_builder_tri_order(b, L.u32ptr(order)))
+        if keep_mesh:
+            nv = C.c_uint32()
+            L.check(lib.fspt_builder_get_mesh(b, None, None, C.byref(nv), None))
+            tri_vertex = np.zeros((nt.value, 3), np.uint32); tri_uv64 = np.zeros((nt.value, 6), np.float64)
+            vertices = np.zeros((nv.value, 3), np.float32)
+            L.check(lib.fspt_builder_get_mesh(b, L.u32ptr(tri_vertex), tri_uv64.ctypes.data_as(C.POINTER(C.c_double)), None, L.fptr(vertices)))
         for eye, d in (focus_rays or []):
             dist = C.c_double()
             L.check(lib.fspt_builder_autofocus(b, (C.c_double * 3)(*[float(x) for x in eye]),
@@ -615,6 +629,10 @@ def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas
         meta["tri_order"] = order
         # the prop (index into `props`) of every packed triangle: the part ids of Scene.set_pose
         meta["tri_part"] = np.searchsorted(np.asarray(prop_end, np.int64), order.astype(np.int64), side="right").astype(np.uint32)
+        if keep_mesh:
+            mode = np.array([_NORMALS_MODE[p.get("normals")] for p in props], np.int64)[meta["tri_part"]]
+            meta.update(tri_vertex=tri_vertex, tri_uv64=tri_uv64, n_vertices=int(nv.value), vertices=vertices,
+                        tri_smooth=(mode == 1).astype(np.uint8), tri_static=(mode == 2) | ~np.isfinite(tri_uv64).all(axis=1))
     return SceneArrays(bvh=bvh_arr, tri=tri, mat=mat, norm=norm, uv=uv, atlas=atlas, atlas_res=packer.res,
                        atlas_layers=len(packer.image_set), env=env, env_w=env_w, env_h=env_h, bins=bins,
                        leaf_size=leaf_size, depth=dp.value, meta=meta)
@@ -706,14 +724,14 @@ def compose_order(base_order, order):
 
 
 def build_scene_json(scene, obj_texts, mtl_texts=None, images=None, env=None, env_w=0, env_h=0, leaf_size=4,
-                     focus_rays=None, bvh="sah", device=0, keep_order=False, geometry_only=False, textures="cpu"):
+                     focus_rays=None, bvh="sah", device=0, keep_order=False, geometry_only=False, textures="cpu", keep_mesh=False):
     """build_scene for a whole scene JSON (props / static_props / animated_props, worldTransforms, normalize,
     atlasRes: main.js:284-445,869-871,944)."""
     return build_scene(merge_scene_props(scene), obj_texts, env=env, env_w=env_w, env_h=env_h, leaf_size=leaf_size,
                        atlas_res=scene.get("atlasRes") or 2048, images=images,
                        world_transforms=scene.get("worldTransforms"), normalize=scene.get("normalize"),
                        mtl_texts=mtl_texts, focus_rays=focus_rays, bvh=bvh, device=device, keep_order=keep_order,
-                       geometry_only=geometry_only, textures=textures)
+                       geometry_only=geometry_only, textures=textures, keep_mesh=keep_mesh)
 
 
 def merge_scene_props(scene):

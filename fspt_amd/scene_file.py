@@ -40,12 +40,13 @@ def mtllib_urls(obj_text, base_path):
     return urls
 
 
-def load_scene_file(scene_path, asset_root=None, leaf_size=4, bvh="sah", device=0, keep_order=False, geometry_only=False, textures="cpu"):
+def load_scene_file(scene_path, asset_root=None, leaf_size=4, bvh="sah", device=0, keep_order=False, geometry_only=False, textures="cpu", keep_mesh=False):
     """Returns (SceneArrays, settings).  settings = camera and display values with the reference's defaults
     (initGlobals, main.js:50-75): eye, dir, fov_scale, env_theta, exposure, samples, focus (lensFeatures[0]
     after shootAutoFocusRay), aperture (index.html default 0.02).  bvh / device: scene.build_scene's builder choice;
     keep_order / geometry_only: as scene.build_scene (the latter: triangles in parse order, no tree); textures: "cpu" or "gpu",
-    where the atlas is resampled (scene.build_scene)."""
+    where the atlas is resampled (scene.build_scene); keep_mesh: as scene.build_scene, and
+    meta["obj_texts"] = the props' OBJ texts in merge_scene_props order."""
     with open(scene_path, "r", encoding="utf-8") as fh:
         scene = json.load(fh)
     root = asset_root or os.path.dirname(os.path.dirname(os.path.abspath(scene_path)))
@@ -83,7 +84,9 @@ def load_scene_file(scene_path, asset_root=None, leaf_size=4, bvh="sah", device=
     eye, d = _camera_ray(scene)
     arrays = S.build_scene_json(scene, obj_texts, mtl_texts, images, env=env, env_w=env_w, env_h=env_h,
                                 leaf_size=leaf_size, focus_rays=[(eye, d)], bvh=bvh, device=device, keep_order=keep_order,
-                                geometry_only=geometry_only, textures=textures)
+                                geometry_only=geometry_only, textures=textures, keep_mesh=keep_mesh)
+    if keep_mesh:
+        arrays.meta["obj_texts"] = [obj_texts[p["path"]] for p in props]
     return arrays, _settings(scene, arrays.meta["focus"][0])
 
 
@@ -336,6 +339,53 @@ def sequence_pose_matrices(base_scene, frame_scene):
     return np.asarray(out, np.float64).reshape(-1, 12).astype(np.float32)
 
 
+def _obj_split(text):
+    """(the OBJ's lines that are not `v` lines, its `v` lines' three numbers as float64 [n, 3]) - obj_loader.js:162-168's split"""
+    rest, v = [], []
+    for line in text.split("\n"):
+        tok = S._js_split_spaces(line)
+        if tok[0] == "v":
+            v.append([float(x) for x in tok[1:4]])
+        else:
+            rest.append(line)
+    return rest, np.asarray(v, np.float64).reshape(-1, 3)
+
+
+def sequence_mesh_frame(base_scene, base_objs, frame_scene, frame_objs):
+    """render_sequence(bvh="refit", mesh=True)'s classification of a frame, as a pure function of two scene JSONs (dicts) and
+    their props' OBJ texts (merge_scene_props order): True when the frame is the base frame with other vertex positions - the
+    scenes are equal once every prop's `path` is removed, neither has a `normalize`, and prop by prop the OBJs have the same
+    number of `v` lines and are equal in every other line.  Such a frame is fully described by sequence_mesh_positions."""
+    def stripped(scene):
+        out = {k: v for k, v in scene.items() if k not in ("props", "static_props", "animated_props")}
+        out["props"] = [{k: v for k, v in p.items() if k != "path"} for p in S.merge_scene_props(scene)]
+        return out
+
+    if base_scene.get("normalize") or frame_scene.get("normalize") or len(base_objs) != len(frame_objs):
+        return False
+    if stripped(base_scene) != stripped(frame_scene):
+        return False
+    for a, b in zip(base_objs, frame_objs):
+        if a is b or a == b:
+            continue
+        (ra, va), (rb, vb) = _obj_split(a), _obj_split(b)
+        if ra != rb or va.shape != vb.shape:
+            return False
+    return True
+
+
+def sequence_mesh_positions(scene, obj_texts):
+    """float32 [n_vertices, 3]: every prop's `v` lines (merge_scene_props order, one OBJ after the other: the indices of
+    meta["tri_vertex"]) as world positions, float32(prop_matrix(prop) applied in float64) - what Scene.update_vertices is handed.
+    (The parse path applies the prop's steps one by one; the composed matrix can differ from it in the last bit.)"""
+    out = []
+    for prop, text in zip(S.merge_scene_props(scene), obj_texts):
+        m = S.prop_matrix(prop, scene.get("worldTransforms"))
+        v = _obj_split(text)[1]
+        out.append(v @ m[:, :3].T + m[:, 3])
+    return np.concatenate(out).astype(np.float32) if out else np.zeros((0, 3), np.float32)
+
+
 def _parse_order_parts(base):
     """part id per PARSE-order triangle from a base built with keep_order (the inverse of meta["tri_part"]'s gather)"""
     out = np.zeros(base.n_tris, np.uint32)
@@ -361,7 +411,7 @@ def _sequence_sky(sky, k, n):
 
 
 def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", rebuild_above=None,
-                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, camera=None, sky=None, textures="cpu", jpeg=None, png=None, exr=None, **kw):
+                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, camera=None, sky=None, textures="cpu", jpeg=None, png=None, exr=None, mesh=False, **kw):
     """frame=N sequencing (main.js:851-866, 966-969): for every N in `frames` load `scene_pattern.format(frame=N)`
     (the per-frame scene JSON the reference's server hands out for `?frame=N`), render it, write
     `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1.
@@ -382,7 +432,15 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     above, and the pose is re-set from what that frame uploaded.  The pictures are NOT bit-equal to the parse path's: there
     the transform is applied in float64 to the OBJ's vertices and rounded once, here a float32 matrix is applied in float32
     to the rest frame's float32 triangles - which is why it is opt-in.
-    on_frame(N, "build" | "refit" | "rebuild" | "appearance" | "pose" | "sky") reports what a frame did.
+    mesh=True (bvh="refit" only): the scene also keeps its triangles as an indexed mesh (Scene.set_mesh from the
+    build's meta).  A frame that sequence_mesh_frame finds to be the build frame with other `v` lines - and whose static
+    triangles (no vt, or `normals: "mesh"`) did not move - builds nothing: its OBJs are still read and split line by line in
+    Python (to compare the other lines and collect the `v` ones), and its sequence_mesh_positions go to
+    Scene.update_vertices, kernels derive the normal frames and the tree is refitted; it reports "mesh".  Any other frame takes
+    the path above, and the mesh path then rests until the next frame that builds.  Like pose, NOT bit-equal to the parse
+    path: there normals come from the float64 positions, here from their float32 roundings, and the auto-focus ray is shot
+    through Scene.intersect in float32 where the parse path asks the builder in float64.
+    on_frame(N, "build" | "refit" | "rebuild" | "appearance" | "pose" | "mesh" | "sky") reports what a frame did.
     temporal (bvh="refit" only): True or a dict of PathTracer.temporal_accumulate's parameters, plus "atrous": K
     for K a-trous iterations on the result.  Every frame then follows the protocol motion_begin, update_geometry, clear and
     render, temporal_accumulate, and the picture written is temporal_draw of the result (`denoise`, the firefly filter of
@@ -452,6 +510,8 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
         temporal = None
     if pose and bvh != "refit":
         raise ValueError('render_sequence: pose needs bvh="refit" (one scene across the frames)')
+    if mesh and bvh != "refit":
+        raise ValueError('render_sequence: mesh needs bvh="refit" (one scene across the frames)')
     if variance and (temporal is None or atrous < 1):
         raise ValueError('render_sequence: variance needs temporal with "atrous" >= 1 (the variance guides the a-trous filter)')
 
@@ -488,6 +548,7 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     atlas_sent = False
     held = None  # the appearance the live scene holds now (not the base's: a change that persists is uploaded once)
     rest_json = None  # pose=True: the scene JSON of the frame whose triangles are the live scene's rest mesh
+    mesh_json, mesh_rest = None, None  # mesh=True: the scene JSON and positions of the frame that built the live scene, while the mesh path is open
 
     def read_json(p):
         with open(p, "r", encoding="utf-8") as fh:
@@ -497,8 +558,30 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
         for n in frames:
             path = scene_pattern.format(frame=n)
             how = "build"
-            frame_json = read_json(path) if pose else None
-            if base is not None and rest_json is not None and sequence_pose_frame(rest_json, frame_json):
+            frame_json = read_json(path) if pose or mesh else None
+            mesh_pos = None
+            if base is not None and mesh_json is not None:
+                root = asset_root or os.path.dirname(os.path.dirname(os.path.abspath(path)))
+                texts, frame_objs = {}, []
+                for p in S.merge_scene_props(frame_json):
+                    if p["path"] not in texts:
+                        texts[p["path"]] = _read_text(root, p["path"])
+                    frame_objs.append(texts[p["path"]])
+                if sequence_mesh_frame(mesh_json, base.meta["obj_texts"], frame_json, frame_objs):
+                    mesh_pos = sequence_mesh_positions(frame_json, frame_objs)
+                    still = np.unique(base.meta["tri_vertex"][base.meta["tri_static"]])
+                    if mesh_pos.shape != mesh_rest.shape or not np.array_equal(mesh_pos[still], mesh_rest[still]):
+                        mesh_pos = None  # (a static triangle moved: the parse path)
+            if mesh_pos is not None:
+                if temporal is not None:
+                    pt.scene.motion_begin()
+                pt.update_vertices(mesh_pos)
+                eye, d = _camera_ray(frame_json)
+                t, hit, _, _ = pt.scene.intersect(np.float32([eye + d]))
+                dist = float(t[0]) if hit[0] >= 0 else 1e6  # shootAutoFocusRay's maxT (main.js:447-546)
+                settings = _settings(frame_json, 1 - 1 / dist)
+                how = "mesh"
+            elif base is not None and rest_json is not None and sequence_pose_frame(rest_json, frame_json):
                 if temporal is not None:
                     pt.scene.motion_begin()
                 pt.update_transforms(sequence_pose_matrices(rest_json, frame_json))
@@ -510,6 +593,7 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
             elif base is not None:
                 g, settings = load_scene_file(path, asset_root, geometry_only=True, device=device, textures=textures)
                 changes = sequence_frame_changes(held, g, base.meta["tri_order"])
+                mesh_json = None  # (what the scene holds is no longer the build frame's mesh with other positions)
                 if changes is not None:
                     tri, norm = S.geometry_in_leaf_order(leaf_order, g.tri, g.norm)
                     if temporal is not None:
@@ -546,12 +630,16 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
             if how == "build":
                 if pt is not None:
                     pt.close(); pt.scene.close()
-                base, settings = load_scene_file(path, asset_root, bvh="sah", device=device, keep_order=True, textures=textures)
+                base, settings = load_scene_file(path, asset_root, bvh="sah", device=device, keep_order=True, textures=textures, keep_mesh=mesh)
                 pt = PathTracer(base, width, height, device=device, num_bounces=bounces)
                 cost0 = pt.scene.sah_cost() if rebuild_above is not None else None
                 leaf_order = base.meta["tri_order"]
                 held, atlas_sent = held_appearance(base), False
                 rest_json = None
+                mesh_json = None
+                if mesh and not frame_json.get("normalize"):
+                    pt.scene.set_mesh()
+                    mesh_json, mesh_rest = frame_json, sequence_mesh_positions(frame_json, base.meta["obj_texts"])
                 if camera is not None:
                     pt.set_camera_model(**camera)
                 if light_builder is not None:

@@ -931,6 +931,122 @@ class Scene:
         L.check(L.lib().fspt_scene_last_skin_ms(self._h, C.byref(a), C.byref(b), C.byref(n), C.byref(by)))
         return dict(skin_ms=float(a.value), refit_ms=float(b.value), launches=int(n.value), bytes=int(by.value))
 
+    @staticmethod
+    def _mesh_desc(fn, arrays, moved, vertex, uv, n_vertices, smooth, rank, static, tri, norm):
+        """(fspt_mesh_desc, the arrays it points into) for the triangles of `arrays`; defaults from its meta
+        (build_scene(..., keep_order=True, keep_mesh=True)); sizes and types checked here, values by the library"""
+        n, meta = int(arrays.n_tris), arrays.meta
+        if vertex is None:
+            if "tri_vertex" not in meta:
+                raise ValueError(f"{fn}: the arrays carry no meta['tri_vertex'] (build_scene(..., keep_order=True, keep_mesh=True)); pass vertex, uv and n_vertices")
+            if moved:
+                raise ValueError(f"{fn}: the scene's triangles are no longer in the order of its arrays; pass vertex, uv, ... in the current leaf order")
+            vertex, uv = meta["tri_vertex"], (meta["tri_uv64"] if uv is None else uv)
+            n_vertices = meta["n_vertices"] if n_vertices is None else n_vertices
+            smooth = meta["tri_smooth"] if smooth is None else smooth
+            rank = meta["tri_order"] if rank is None else rank
+            static = meta["tri_static"] if static is None else static
+        if uv is None:
+            raise ValueError(f"{fn}: vertex given without uv")
+        vertex = np.array(_u32_array(vertex, "vertex"), dtype=np.uint32).reshape(-1)
+        uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(-1)
+        if vertex.size != n * 3 or uv.size != n * 6:
+            raise ValueError(f"{fn}: vertex has {vertex.size} and uv {uv.size} elements, the scene needs {n} x 3 and {n} x 6")
+        if static is not None:
+            static = np.asarray(static, dtype=bool).reshape(-1)
+            if static.size != n:
+                raise ValueError(f"{fn}: static has {static.size} elements, the scene has {n} triangles")
+            vertex.reshape(-1, 3)[static] = L.MESH_STATIC
+        if n_vertices is None:
+            live = vertex[vertex != L.MESH_STATIC]
+            n_vertices = int(live.max()) + 1 if live.size else 1
+        u8 = lambda a, what: None if a is None else np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+        smooth = u8(smooth, "smooth")
+        rank = None if rank is None else np.ascontiguousarray(_u32_array(rank, "rank"), dtype=np.uint32).reshape(-1)
+        for name, a in (("smooth", smooth), ("rank", rank)):
+            if a is not None and a.size != n:
+                raise ValueError(f"{fn}: {name} has {a.size} elements, the scene has {n} triangles")
+        if (vertex == L.MESH_STATIC).any():
+            if tri is None:
+                if norm is not None:
+                    raise ValueError(f"{fn}: norm given without tri")
+                if moved:
+                    raise ValueError(f"{fn}: the scene's geometry is no longer that of its arrays; pass the static triangles' rest tri and norm in the current leaf order")
+                tri, norm = arrays.tri, arrays.norm
+            tri, norm = _host_geometry(fn, n, tri, norm)
+            if norm is None:
+                raise ValueError(f"{fn}: static triangles need a rest norm")
+        else:
+            tri = norm = None
+        f = lambda a: None if a is None else L.fptr(a)
+        d = L.MeshDesc(L.u32ptr(vertex), int(n_vertices), uv.ctypes.data_as(C.POINTER(C.c_double)),
+                       None if smooth is None else smooth.ctypes.data_as(C.POINTER(C.c_uint8)), None if rank is None else L.u32ptr(rank), f(tri), f(norm))
+        return d, (vertex, uv, smooth, rank, tri, norm)
+
+    @staticmethod
+    def _mesh_frame(fn, pos, device):
+        """(on device, pos, n_vertices, what to keep alive) for update_vertices: a contiguous float32 numpy array, or the
+        data pointer of a float32 torch tensor on `device` (None: device tensors are refused)"""
+        if hasattr(pos, "data_ptr") and getattr(pos, "is_cuda", False):
+            import torch
+            if device is None:
+                raise TypeError(f"{fn}: pos must be a host array here")
+            if pos.dtype != torch.float32 or not pos.is_contiguous():
+                raise TypeError(f"{fn}: pos must be a contiguous float32 tensor")
+            if pos.device.index != device:
+                raise ValueError(f"{fn}: pos lives on {pos.device}, the scene on device {device}")
+            if pos.numel() == 0 or pos.numel() % 3:
+                raise ValueError(f"{fn}: pos has {pos.numel()} elements, not n_vertices x 3")
+            torch.cuda.current_stream(device).synchronize()  # whatever wrote the tensor has finished
+            return True, C.c_void_p(pos.data_ptr()), pos.numel() // 3, pos
+        pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1)
+        if pos.size == 0 or pos.size % 3:
+            raise ValueError(f"{fn}: pos has {pos.size} elements, not n_vertices x 3")
+        return False, L.fptr(pos), pos.size // 3, pos
+
+    def set_mesh(self, vertex=None, uv=None, n_vertices=None, smooth=None, rank=None, static=None, tri=None, norm=None, drop=False):
+        """Hand the scene an indexed mesh (fspt_scene_set_mesh).  Per triangle in the current LEAF order: vertex
+        [n, 3] indices < n_vertices, uv [n, 6] float64 raw vt values, smooth [n] 0 / 1 (None: all flat), rank [n] the order a
+        face normal is summed in (None: the leaf position), static [n] bool: triangles that keep their rest tri / norm (the
+        default rest copy is `self.arrays`).  With vertex=None everything comes from the arrays' meta
+        (build_scene(..., keep_order=True, keep_mesh=True)) - refused once the scene has been given another order.
+        drop=True drops the mesh and frees it.  Nothing renders differently until update_vertices."""
+        if drop:
+            L.check(L.lib().fspt_scene_set_mesh(self._h, None))
+            return
+        d, keep = self._mesh_desc("set_mesh", self.arrays, getattr(self, "_moved", False), vertex, uv, n_vertices, smooth, rank, static, tri, norm)
+        L.check(L.lib().fspt_scene_set_mesh(self._h, C.byref(d)))
+
+    def update_vertices(self, pos):
+        """One frame of the mesh: pos = one float32 position per vertex [n_vertices, 3].  Kernels derive every meshed
+        triangle's vertices and normal frames from them by the reference's rules in float64 (face normals, for smooth
+        triangles the mean of the incident face normals, calcTangents) and the tree is refitted exactly as
+        update_geometry on those arrays would (fspt_scene_update_vertices).  A numpy array takes the host form
+        (checked: a non-finite position is refused); a float32 torch tensor on the scene's device is read where it is
+        (the `_device` form; no host check - a collapsed face is refused by the refit's check).  Any error leaves the
+        scene as it was."""
+        on_dev, p, nv, keep = self._mesh_frame("update_vertices", pos, self.device)
+        fn = L.lib().fspt_scene_update_vertices_device if on_dev else L.lib().fspt_scene_update_vertices
+        L.check(fn(self._h, p, nv))
+
+    def read_mesh(self):
+        """(tri [n, 9], norm [n, 27]) as the most recent update_vertices wrote them (fspt_scene_read_mesh)."""
+        n = int(self.arrays.n_tris)
+        tri = np.zeros((n, 9), np.float32)
+        norm = np.zeros((n, 27), np.float32)
+        L.check(L.lib().fspt_scene_read_mesh(self._h, L.fptr(tri), L.fptr(norm)))
+        return tri, norm
+
+    @property
+    def last_mesh(self):
+        """The most recent update_vertices as a dict: derive_ms (the derive kernels), refit_ms, launches, and bytes - what
+        the mesh holds on the device by the library's accounting (fspt_scene_last_mesh_ms; 0 without a mesh)."""
+        a, b, n, by = C.c_float(), C.c_float(), C.c_uint32(), C.c_uint64()
+        L.check(L.lib().fspt_scene_last_mesh_ms(self._h, C.byref(a), C.byref(b), C.byref(n), C.byref(by)))
+        ps = np.zeros(3, np.float32)
+        L.check(L.lib().fspt_scene_last_mesh_pass_ms(self._h, L.fptr(ps)))
+        return dict(derive_ms=float(a.value), refit_ms=float(b.value), launches=int(n.value), bytes=int(by.value), pass_ms=[float(x) for x in ps])
+
     def _materials_args(self, fn, mat, uv, atlas, atlas_res, atlas_layers):
         n = int(self.arrays.n_tris)
         mat = np.ascontiguousarray(mat, dtype=np.float32)
@@ -1454,6 +1570,23 @@ class PathTracer:
         """Scene.last_skin of this tracer's scene."""
         return self.scene.last_skin
 
+    def set_mesh(self, *args, **kwargs):
+        """Scene.set_mesh on this tracer's scene."""
+        self.scene.set_mesh(*args, **kwargs)
+
+    def update_vertices(self, pos):
+        """Scene.update_vertices on this tracer's scene (every tracer of the scene sees it); call clear() to restart the mean."""
+        self.scene.update_vertices(pos)
+
+    def read_mesh(self):
+        """Scene.read_mesh of this tracer's scene."""
+        return self.scene.read_mesh()
+
+    @property
+    def last_mesh(self):
+        """Scene.last_mesh of this tracer's scene."""
+        return self.scene.last_mesh
+
     def update_materials(self, mat, uv=None, atlas=None, atlas_res=None, atlas_layers=None):
         """Scene.update_materials on this tracer's scene (every tracer of the scene sees it); the accumulator, the temporal
         history, the exposure and the bloom state stay - call clear() to restart the mean."""
@@ -1941,6 +2074,19 @@ class MultiPathTracer:
         """Scene.update_skin (host arrays) on every device's copy of the scene (fspt_multi_update_skin)."""
         _, pxf, nj, pmw, nm, keep = Scene._skin_frame("update_skin", xf, morph_weights, None)
         L.check(L.lib().fspt_multi_update_skin(self._m, pxf, nj, pmw, nm))
+
+    def set_mesh(self, vertex=None, uv=None, n_vertices=None, smooth=None, rank=None, static=None, tri=None, norm=None, drop=False):
+        """Scene.set_mesh on every device's copy of the scene (fspt_multi_set_mesh)."""
+        if drop:
+            L.check(L.lib().fspt_multi_set_mesh(self._m, None))
+            return
+        d, keep = Scene._mesh_desc("set_mesh", self.arrays, getattr(self, "_moved", False), vertex, uv, n_vertices, smooth, rank, static, tri, norm)
+        L.check(L.lib().fspt_multi_set_mesh(self._m, C.byref(d)))
+
+    def update_vertices(self, pos):
+        """Scene.update_vertices (a host array) on every device's copy of the scene (fspt_multi_update_vertices)."""
+        _, p, nv, keep = Scene._mesh_frame("update_vertices", pos, None)
+        L.check(L.lib().fspt_multi_update_vertices(self._m, p, nv))
 
     def update_materials(self, mat, uv=None, atlas=None, atlas_res=None, atlas_layers=None):
         """Scene.update_materials (host arrays) on every device's copy of the scene (fspt_multi_update_materials)."""

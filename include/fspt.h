@@ -72,14 +72,14 @@ typedef struct fspt_scene_desc {
 /* device = HIP device ordinal.  Builds the MI355X-native layouts (64-byte two-child nodes, 144-byte leaf records, 192-byte hit records, material texture sets in 128-byte tiles; DESIGN.md 3). */
 int fspt_scene_create(const fspt_scene_desc *desc, int device, fspt_scene **out); int fspt_scene_destroy(fspt_scene *scene);
 int fspt_scene_depth(const fspt_scene *scene, uint32_t *depth); /* Maximum depth of the uploaded tree (root = 0); sizes the LDS stacks. */
-/* Moving geometry: new vertices (9 floats) and, unless norm is NULL, normTex records (27 floats) for the n_tris
- * triangles in leaf order; the tree is REFITTED on the GPU (leaf and hit records, every box bottom-up, two-level nodes, light
- * table) exactly as fspt_scene_create would build it from the same topology.  Non-finite input: FSPT_E_INVALID, scene unchanged;
- * leaves that do not tile [0, n_tris): FSPT_E_STATE.  Blocking; ordered against every target; accumulators are not cleared.  _rebuild_
- * (DESIGN 8.7): same input, a NEW tree - fspt_builder_build_gpu's binned SAH over tri in the order given - built on the GPU, installed in the same
- * scene (targets stay valid; errors leave it as it was); order_out (or NULL)[k] = input index of the triangle now at leaf position k: the leaf order of later calls */
+/* Moving geometry (DESIGN 8.6): new vertices (9 floats) and, unless norm is NULL, normTex records (27 floats) for the n_tris triangles in leaf order; the tree is REFITTED on the GPU (leaf and hit records, every box bottom-up, two-level nodes, light
+ * table) exactly as fspt_scene_create would build it from the same topology.  Non-finite input: FSPT_E_INVALID, scene unchanged; leaves that do not tile [0, n_tris): FSPT_E_STATE.  Blocking; ordered against every target; accumulators are not cleared.  _rebuild_
+ * (DESIGN 8.7): same input, a NEW tree - fspt_builder_build_gpu's binned SAH over tri in the order given - built on the GPU, installed in the same scene (targets stay valid; errors leave it as it was); order_out (or NULL)[k] = input index of the triangle now at leaf position k: the leaf order of later calls */
 int fspt_scene_update_geometry(fspt_scene *s, const float *tri, const float *norm); int fspt_scene_rebuild_geometry(fspt_scene *s, const float *tri, const float *norm, uint32_t *order_out); /* host pointers */
 int fspt_scene_update_geometry_device(fspt_scene *s, const float *tri, const float *norm); int fspt_scene_rebuild_geometry_device(fspt_scene *s, const float *tri, const float *norm, uint32_t *order_out); /* memory of the scene's device */ /* Part transforms (DESIGN 8.14): set_pose hands the scene a part id < n_parts per triangle and the rest tri (9 floats) / norm (27, or NULL: the records' normal part is left alone) in the current leaf order (host pointers; part NULL drops the pose; renders nothing differently; a rebuild permutes it).  update_transforms: xf = n_parts x 12 floats, row-major 3 x 4 (a00 a01 a02 tx | ...); a kernel poses the rest mesh (normals by the cofactor matrix, tangents by the matrix, both scaled to the matrix's rms) and the tree is refitted exactly as fspt_scene_update_geometry_device on the posed arrays.  FSPT_E_STATE without a pose; FSPT_E_INVALID (scene unchanged): wrong n_parts, a non-finite or singular matrix, an overflowing product. */ int fspt_scene_set_pose(fspt_scene *s, const uint32_t *part, uint32_t n_parts, const float *tri, const float *norm); int fspt_scene_update_transforms(fspt_scene *s, const float *xf, uint32_t n_parts); /* Skinning (DESIGN 8.16): set_skin hands the scene, per triangle corner (3 per triangle, current leaf order), joints (4 ids < n_joints) and weights (4 finite floats, used as given), the rest tri (9 floats per triangle) / norm (27, or NULL), and n_morph <= 64 morph targets as deltas, target-major: morph [n_morph][T][9], morph_norm [n_morph][T][27] (or NULL; needs norm); host pointers, validated before anything is touched, d NULL drops the skin; a rebuild permutes it.  update_skin: xf = n_joints x 12 floats, row-major 3 x 4 per joint, morph_w = n_morph floats (NULL when 0); a kernel applies the morphs, blends the four matrices, poses vertex and frame per corner and the tree is refitted exactly as fspt_scene_update_geometry_device on those arrays.  _device: xf (16-byte aligned) / morph_w in the scene's device memory, no host check.  FSPT_E_STATE without a skin; FSPT_E_INVALID (scene unchanged): other counts, a non-finite matrix or weight, a blend that collapses or overflows. */ typedef struct fspt_skin_desc { const uint16_t *joints; const float *weights; uint32_t n_joints; const float *tri, *norm, *morph, *morph_norm; uint32_t n_morph; } fspt_skin_desc; int fspt_scene_set_skin(fspt_scene *s, const fspt_skin_desc *d); int fspt_scene_update_skin(fspt_scene *s, const float *xf, uint32_t n_joints, const float *morph_w, uint32_t n_morph); int fspt_scene_update_skin_device(fspt_scene *s, const float *xf, uint32_t n_joints, const float *morph_w, uint32_t n_morph);
+#define FSPT_MESH_STATIC 0xFFFFFFFFu /* fspt_mesh_desc.vertex: all three of a triangle = it is static */
+/* Vertex-position update (DESIGN 8.24): set_mesh hands the scene an indexed mesh - per triangle (current leaf order) three vertex indices < n_vertices (all three FSPT_MESH_STATIC: a static triangle, which keeps the rest tri / norm given here), the six raw vt values in float64 (before obj_loader.js's EPSILON offsets), a smooth flag (NULL: all flat) and the rank its face normal is summed in (distinct; NULL: the leaf position); host pointers, validated before anything is touched, d NULL drops the mesh; a rebuild permutes it.  update_vertices: pos = n_vertices x 3 float32; kernels derive tri and the normal frames by obj_loader.js's rules in float64 (face normal; for smooth triangles the unnormalised mean of the incident face normals in rank order; calcTangents with its isNaN fallback) and the tree is refitted exactly as fspt_scene_update_geometry_device on those arrays.  _device: pos in the scene's device memory, no host check.  FSPT_E_STATE without a mesh; FSPT_E_INVALID (scene unchanged): another count, an index out of range, a partly static triangle, a non-finite uv or position, a repeated rank, a static triangle without a rest copy, a face that collapses. */
+typedef struct fspt_mesh_desc { const uint32_t *vertex; uint32_t n_vertices; const double *uv; const uint8_t *smooth; const uint32_t *rank; const float *tri, *norm; } fspt_mesh_desc; int fspt_scene_set_mesh(fspt_scene *s, const fspt_mesh_desc *d); int fspt_scene_update_vertices(fspt_scene *s, const float *pos, uint32_t n_vertices); int fspt_scene_update_vertices_device(fspt_scene *s, const float *pos, uint32_t n_vertices);
 int fspt_scene_sah_cost(fspt_scene *s, double *cost); /* SAH cost of the current boxes relative to the root's area, float64 */ /* Appearance (DESIGN 8.13): new matTex (12 floats per triangle, current leaf order), uvs (or NULL: kept) and atlas (or NULL: the one the scene's last update_materials call carried, FSPT_E_STATE when none did; res / layers may differ from the scene's) | new environment (NULL = black) and bins.  Laid out on the GPU; afterwards the scene renders bit for bit like fspt_scene_create of the same arrays.  Blocking; ordered against every target like fspt_scene_update_geometry; validated like fspt_scene_create; an error leaves the scene as it was; accumulators and per-target state are not touched. */ int fspt_scene_update_materials(fspt_scene *s, const float *mat, const float *uv, const uint8_t *atlas, uint32_t atlas_res, uint32_t atlas_layers); int fspt_scene_update_environment(fspt_scene *s, const uint8_t *env, uint32_t env_w, uint32_t env_h, const uint32_t *bins, uint32_t n_bins); /* Texture packing (DESIGN 8.18): the raw atlas made on the GPU from decoded sources - per layer a flat colour, a res x res RGBA8 image copied as given (GL rows), or an RGBA8 image (row 0 = top) resampled bilinearly (REPEAT in s, CLAMP_TO_EDGE in t), sRGB-decoded when corrected, swizzled, premultiplied; float32, bit for bit the hosts' resample_image. atlas_pack_gpu stands alone (atlas_out: res^2 * n_layers * 4 bytes). update_textures = fspt_scene_update_materials with the atlas packed on the scene's device (only the sources cross the bus); patch_textures: p->layers[k] replaces layer layer_ids[k] of the retained atlas (p->res = its res; FSPT_E_STATE without one), the scene is laid out again with its current materials. _device: images[i].rgba in the scene's device memory (4-byte aligned, not checked on the host). FSPT_E_INVALID before anything is touched: NULL, res / w / h of 0 or above 16384, n_layers == 0, an image index out of range, a swizzle entry above 3, an unknown kind, a non-finite colour, a _PIXELS image that is not res x res, a layer id at or above the retained layers or twice. */ enum { FSPT_TEXLAYER_COLOR = 0, FSPT_TEXLAYER_IMAGE = 1, FSPT_TEXLAYER_PIXELS = 2 }; typedef struct fspt_texture_image { const uint8_t *rgba; uint32_t w, h; } fspt_texture_image; typedef struct fspt_texture_layer { int32_t kind; float color[3]; uint32_t image; uint32_t corrected; uint8_t swizzle[4]; } fspt_texture_layer; typedef struct fspt_texture_pack { const fspt_texture_image *images; uint32_t n_images; const fspt_texture_layer *layers; uint32_t n_layers; uint32_t res; } fspt_texture_pack; int fspt_texture_decode_tables(float lin[256], float srgb[256]); int fspt_atlas_pack_gpu(int device, const fspt_texture_pack *p, uint8_t *atlas_out); int fspt_scene_update_textures(fspt_scene *s, const float *mat, const float *uv, const fspt_texture_pack *p); int fspt_scene_update_textures_device(fspt_scene *s, const float *mat, const float *uv, const fspt_texture_pack *p); int fspt_scene_patch_textures(fspt_scene *s, const uint32_t *layer_ids, uint32_t n, const fspt_texture_pack *p); int fspt_scene_patch_textures_device(fspt_scene *s, const uint32_t *layer_ids, uint32_t n, const fspt_texture_pack *p);
 
 /* ------------------------------------------------------------------------

@@ -45,6 +45,9 @@ int fspt_multi_update_transforms(fspt_multi *m, const float *xf, uint32_t n_part
 /* fspt_scene_set_skin / fspt_scene_update_skin (the host form) on every device's copy of the scene */
 int fspt_multi_set_skin(fspt_multi *m, const fspt_skin_desc *d);
 int fspt_multi_update_skin(fspt_multi *m, const float *xf, uint32_t n_joints, const float *morph_w, uint32_t n_morph);
+/* fspt_scene_set_mesh / fspt_scene_update_vertices (the host form) on every device's copy of the scene */
+int fspt_multi_set_mesh(fspt_multi *m, const fspt_mesh_desc *d);
+int fspt_multi_update_vertices(fspt_multi *m, const float *pos, uint32_t n_vertices);
 /* fspt_scene_update_materials / _environment on every device's copy of the scene; arguments the first device refuses change nothing */
 int fspt_multi_update_materials(fspt_multi *m, const float *mat, const float *uv, const uint8_t *atlas, uint32_t atlas_res, uint32_t atlas_layers);
 /* fspt_scene_update_textures / _patch_textures, host-pointer form, on every device's copy of the scene */

@@ -89,6 +89,25 @@ int fspt_scene_read_skin(fspt_scene *s, float *tri, float *norm);
 int fspt_scene_last_skin_ms(fspt_scene *s, float *skin_ms, float *refit_ms, uint32_t *launches, uint64_t *bytes);
 int fspt_skin_check_eval(const fspt_skin_desc *d, uint32_t n_tris, uint64_t *bad_index);
 int fspt_skin_set_form(int form);
+/* Vertex-position update, test and measurement hooks.
+ * read_mesh: the tri (n_tris x 9) / norm (n_tris x 27; either may be NULL) the most recent fspt_scene_update_vertices[_device]
+ * wrote to the staging array the refit read (FSPT_E_STATE when another call has reused the array since, a refused
+ * fspt_scene_update_vertices among them: what the refit's check refused is not handed out).
+ * last_mesh_ms: GPU ms of the derive kernels (first to last), GPU ms of the refit behind them, kernels launched, and the
+ * bytes the mesh holds on the device by the library's accounting: n_tris x (12 + 24 + 4 [+ 144 with a static triangle])
+ * + n_vertices x 12 (the host form's frame) and, with a smooth triangle, (n_vertices + 1) x 4 + incident corners x 4 +
+ * n_tris x 24 + n_vertices x 24; 0 without a mesh.  Any pointer may be NULL.
+ * last_mesh_pass_ms: derive_ms pass by pass: k_mesh_faces, k_mesh_vertex_normals, k_mesh_smooth_frames (a flat-only mesh
+ * runs the first alone: the other two are 0).
+ * mesh_frames_eval: fspt_scene_set_mesh's validation (first, without a device: FSPT_E_INVALID with the reason), then the
+ * derive kernels alone on `device` - no scene, no refit and so no non-finite check: what the isNaN quirk leaves is seen.
+ * f64_probe_eval: out[i] = sqrt(a[i]) (op 0; b unused) or a[i] / b[i] (op 1) in float64 as those kernels compile them:
+ * the contract needs both correctly rounded. */
+int fspt_scene_read_mesh(fspt_scene *s, float *tri, float *norm);
+int fspt_scene_last_mesh_ms(fspt_scene *s, float *derive_ms, float *refit_ms, uint32_t *launches, uint64_t *bytes);
+int fspt_scene_last_mesh_pass_ms(fspt_scene *s, float ms[3]);
+int fspt_mesh_frames_eval(int device, const fspt_mesh_desc *d, uint32_t n_tris, const float *pos, float *tri_out, float *norm_out);
+int fspt_f64_probe_eval(int device, int op, const double *a, const double *b, uint32_t n, double *out);
 /* Camera models, measurement hook: k_camera of the target's model (FSPT_E_STATE under pinhole) `reps` times
  * into the ray buffers on the target's stream between two HIP events; *ms_per_launch = their distance / reps.  Blocking; a flush
  * point; the ray buffers are overwritten (a recorded fspt_camera call's rays are made again on demand; injected rays are gone:
@@ -214,6 +233,13 @@ int fspt_builder_tri_order(const fspt_builder *b, uint32_t *order);
 /* The builder's triangles in PARSE order, packed like fspt_builder_get's arrays (9 / 12 / 27 / 6 floats each; NULL = skip);
  * works before a build: what a host moves and hands to fspt_scene_update_geometry through fspt_builder_tri_order's order. */
 int fspt_builder_geometry(const fspt_builder *b, uint32_t *n_tris, float *tri, float *mat, float *norm, float *uv);
+/* The built tree's triangles as an indexed mesh (fspt_scene_set_mesh), in leaf order: vertex = 3 indices per
+ * triangle, made global over the OBJs by an offset per OBJ; uv = the 6 raw vt values in float64, before calcTangents'
+ * offsets (NaN for a triangle without vt: its uvs depend on the positions, so it can only be static); *n_vertices = the
+ * `v` lines of all OBJs; positions = their world positions (n_vertices x 3, float32 of the float64 the builder holds; a
+ * vertex no face names is transformed like the others, so the array can go back to fspt_scene_update_vertices as it is).
+ * Any pointer may be NULL. */
+int fspt_builder_get_mesh(const fspt_builder *b, uint32_t *vertex, double *uv, uint32_t *n_vertices, float *positions);
 
 /* ---- test hook ------------------------------------------------------------------------------------------------------ */
 /* Device-side evaluation of the deterministic math primitives (DESIGN.md

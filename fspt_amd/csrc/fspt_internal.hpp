@@ -93,6 +93,7 @@ struct fspt_scene {
   // fspt_scene_create no longer has when it returns: host memory until the first update, which makes the device copies
   // (fspt_refit.hip) - a scene that is never updated allocates nothing for it on the GPU.
   std::vector<fspt_target *> targets;
+  enum StageOwner { STAGE_NONE, STAGE_POSE, STAGE_SKIN, STAGE_MESH };
   struct Refit {
     static const uint32_t NO_DST = 0xFFFFFFFFu;
     bool ok = false;                  // the leaves' triStarts are distinct and tile [0, n_tris); every node has one parent
@@ -107,7 +108,8 @@ struct fspt_scene {
     uint32_t *d_leaf = nullptr;       // leaf_first | leaf_cnt | leaf_dst
     uint32_t *d_lvl = nullptr;        // lvl_nodes
     uint32_t *d_flag = nullptr;       // [0] non-finite input seen, [1] the two-level nodes are not usable
-    float *stage = nullptr;           // the host form's upload: 9 + 27 floats per triangle
+    float *stage = nullptr;           // the staging array, tri 9 T | norm 27 T: a host form's upload or a deformer's output
+    StageOwner stage_owner = STAGE_NONE; // whose accepted frame `stage` holds (stage_disown; granted by the update path alone)
     hipEvent_t ev[2] = {nullptr, nullptr};
     float last_ms = 0.0f;             // kernels of the last update, first to last
     uint32_t last_launches = 0;
@@ -135,7 +137,7 @@ struct fspt_scene {
   } ap;
   // fspt_scene_set_pose / fspt_scene_update_transforms (fspt_pose.hip): per triangle (current leaf order) a part
   // id and the rest mesh, on the device; a rebuild permutes them with the triangles.  A scene that never sets a pose
-  // allocates nothing for it; the posed arrays go to rf.stage.
+  // allocates nothing for it; the posed arrays go to rf.stage, which an accepted frame owns as STAGE_POSE.
   struct Pose {
     uint32_t *part = nullptr;       // n_tris ids < n_parts (NULL: no pose)
     float *rest = nullptr;          // n_tris x 9 rest vertices | n_tris x 27 rest normTex records when has_norm
@@ -143,13 +145,11 @@ struct fspt_scene {
     uint32_t n_parts = 0;
     float *mats = nullptr;          // the last call's n_parts x 30 floats (a | D | N); grows as needed
     uint32_t mats_cap = 0;          // parts it holds
-    bool posed = false;             // rf.stage holds the last update_transforms' output (fspt_scene_read_pose)
-    hipEvent_t ev[2] = {nullptr, nullptr};
     float last_ms = 0.0f;           // k_pose_transform of the last call
   } pose;
   // fspt_scene_set_skin / fspt_scene_update_skin (fspt_pose.hip): per triangle corner (current leaf order) four
   // joint ids and weights, the rest mesh and the morph targets, on the device; a rebuild permutes them with the triangles.
-  // A scene that never sets a skin allocates nothing for it; the skinned arrays go to rf.stage.
+  // A scene that never sets a skin allocates nothing for it; the skinned arrays go to rf.stage (STAGE_SKIN).
   struct Skin {
     uint16_t *joints = nullptr;     // n_tris x 3 x 4 ids < n_joints (NULL: no skin)
     float *weights = nullptr;       // n_tris x 3 x 4
@@ -159,14 +159,12 @@ struct fspt_scene {
     float *frame = nullptr;         // the host form's upload: n_joints x 12 floats | n_morph weights
     bool has_norm = false;
     uint32_t n_joints = 0, n_morph = 0;
-    bool skinned = false;           // rf.stage holds the last update_skin's output (fspt_scene_read_skin)
-    hipEvent_t ev[2] = {nullptr, nullptr};
     float last_ms = 0.0f;           // k_skin_transform of the last call
   } skin;
   // fspt_scene_set_mesh / fspt_scene_update_vertices (fspt_pose.hip): an indexed mesh whose normal frames are
   // derived from new vertex positions every frame.  Per triangle (current leaf order; a rebuild permutes them) the corner
   // indices, three uv constants, a face id and the rest copy of the static ones; per vertex the incident faces by face id
-  // (a rebuild leaves them alone).  A scene that never sets a mesh allocates nothing for it; the derived arrays go to rf.stage.
+  // (a rebuild leaves them alone).  A scene that never sets a mesh allocates nothing for it; the derived arrays go to rf.stage (STAGE_MESH).
   struct Mesh {
     uint32_t *vertex = nullptr;     // n_tris x 3 indices < n_vertices, or 3 x FSPT_MESH_STATIC (NULL: no mesh)
     double *cst = nullptr;          // n_tris x 3: du1[1], du0[1], r of calcTangents, float64 (static: 0)
@@ -178,13 +176,13 @@ struct fspt_scene {
     double *vnorm = nullptr;        // scratch, n_vertices x 3: total * (1 / count)
     float *pos = nullptr;           // the host form's upload: n_vertices x 3
     uint32_t n_vertices = 0, n_adj = 0; // n_adj = adj_off[n_vertices], the entries of adj_face
-    uint64_t bytes = 0;            // what the arrays above hold
-    bool meshed = false;            // rf.stage holds the output of the last update_vertices, and the refit accepted it (fspt_scene_read_mesh)
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // first, last, and between the three passes
     float last_ms = 0.0f;           // the derive kernels of the last call, first to last
     float pass_ms[3] = {0.0f, 0.0f, 0.0f}; // k_mesh_faces | k_mesh_vertex_normals | k_mesh_smooth_frames (a flat-only mesh: the first alone)
     uint32_t last_launches = 0;
   } mesh;
+  // the events that time a deformer's kernels, whichever it is: first, last, and between the mesh's three passes.  Made by the
+  // first update_transforms / _skin / _vertices, destroyed with the scene.
+  hipEvent_t deform_ev[4] = {nullptr, nullptr, nullptr, nullptr};
   // fspt_scene_update_sky / _environment_auto / _environment_device (fspt_sky.hip): the last such call
   struct Sky {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -457,21 +455,36 @@ int exr_plan(const fspt_exr_params *prm, uint32_t w, uint32_t h, bool for_device
 hipError_t exr_ensure(ExrEnc &e, const ExrPlan &pl, size_t out_bytes);                 // nothing of `e` may be in use
 hipError_t exr_launch(ExrEnc &e, const float4 *rgba, const float4 *feat, int bottom_up, hipStream_t st); // no host read, no synchronisation
 int exr_collect(ExrEnc &e, hipStream_t st, uint8_t *out, size_t cap, size_t *bytes_out, const char *fn);
-// fspt_pose.hip.  pose_run: s->pose set, s->rf.stage allocated, the call ordered against the targets;
-// mats_host = n_parts x 30 floats (a | D | N).  Uploads them, runs k_pose_transform into s->rf.stage and waits.
-int pose_run(fspt_scene *s, const float *mats_host);
-void pose_release(fspt_scene *s);
-// fspt_pose.hip.  skin_run: s->skin set, s->rf.stage allocated, the call ordered against the targets; xf =
-// n_joints x 12 floats (16-byte aligned when on the device), morph_w = n_morph floats, host memory (uploaded to
-// skin.frame) or the scene's device memory.  Runs k_skin_transform into s->rf.stage and waits.
-int skin_run(fspt_scene *s, const float *xf, const float *morph_w, bool on_device);
-void skin_release(fspt_scene *s);
-// fspt_pose.hip.  mesh_run: the derive kernels of M for T triangles from pos (n_vertices x 3 floats, device
-// memory) into stage (tri 9 T | norm 27 T) on the NULL stream; no wait; `between`: two events recorded between the passes.  mesh_update: s->mesh set, s->rf.stage allocated,
-// the call ordered; pos = host memory (uploaded to mesh.pos) or the scene's device memory.  Runs them, waits and times.
+// fspt_pose.hip: the three deformers that fill s->rf.stage (tri 9 T | norm 27 T) - part transforms, skinning
+// (8.16), the vertex-position update (8.24).  Set, update, read, release and rebuild are stated once for all of them
+// (fspt_scene_update.cpp, rebuild_run); what is a deformer's own is its frame upload and its launch, below.
+// A deformer's device arrays, once, as data: `rows` rows of span[0] + span[1] words in each of `slices` slices.  An array
+// that follows the triangles (rows = n_tris) is permuted span by span and slice by slice when a rebuild changes the leaf
+// order: rest = 9 T | 27 T in one allocation is two spans, a morph array one slice per target.  *p NULL: not there.
+struct DeformArray { void **p; size_t rows; uint32_t span[2]; size_t slices; bool follows; };
+std::vector<DeformArray> deform_arrays(fspt_scene::Pose &P, size_t T);
+std::vector<DeformArray> deform_arrays(fspt_scene::Skin &K, size_t T);
+std::vector<DeformArray> deform_arrays(fspt_scene::Mesh &M, size_t T);
+inline std::vector<DeformArray> deform_arrays(fspt_scene *s, fspt_scene::StageOwner who) {
+  return who == fspt_scene::STAGE_POSE ? deform_arrays(s->pose, s->n_tris) : who == fspt_scene::STAGE_SKIN ? deform_arrays(s->skin, s->n_tris) : deform_arrays(s->mesh, s->n_tris);
+}
+uint64_t deform_bytes(const std::vector<DeformArray> &arrays); // what the arrays that are there hold
+void mesh_release(fspt_scene::Mesh &M);                        // (a mesh without a scene: fspt_mesh_frames_eval)
+void deformer_release(fspt_scene *s, fspt_scene::StageOwner who); // frees its arrays, resets it, takes the staging array from it
+// The staging array is about to be written, or `only`'s arrays to change: no frame (of `only`) is handed out any more.
+inline void stage_disown(fspt_scene *s, fspt_scene::StageOwner only = fspt_scene::STAGE_NONE) {
+  if (only == fspt_scene::STAGE_NONE || s->rf.stage_owner == only) s->rf.stage_owner = fspt_scene::STAGE_NONE;
+}
+// The frame uploads (host forms; the device of the scene is current): pose_upload grows pose.mats as needed and takes
+// n_parts x 30 floats (a | D | N); skin_upload takes n_joints x 12 floats | n_morph weights into skin.frame.
+// The launches: a deformer's kernels into s->rf.stage (allocated) on the NULL stream, no wait; they return the kernels
+// launched.  skin_run: xf (16-byte aligned) and morph_w are device memory.  mesh_run needs no scene: the derive kernels of
+// M for T triangles from pos (n_vertices x 3 floats, device memory) into stage; `between`: two events recorded between the passes.
+int pose_upload(fspt_scene::Pose &P, const float *mats_host);
+uint32_t pose_run(fspt_scene *s);
+int skin_upload(fspt_scene::Skin &K, const float *xf, const float *morph_w);
+uint32_t skin_run(fspt_scene *s, const float *xf, const float *morph_w);
 uint32_t mesh_run(const fspt_scene::Mesh &M, uint32_t T, const float *pos, float *stage, hipEvent_t *between = nullptr);
-int mesh_update(fspt_scene *s, const float *pos, bool on_device);
-void mesh_release(fspt_scene::Mesh &M);
 int f64_probe_run(int op, const double *a, const double *b, uint32_t n, double *out);
 // the joint table's form: 0 = read from global memory, 1 = staged once per block in LDS when it fits SKIN_LDS_MAX_BYTES
 extern int g_skin_form;

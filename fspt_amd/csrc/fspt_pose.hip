@@ -350,39 +350,6 @@ uint32_t mesh_run(const fspt_scene::Mesh &M, uint32_t T, const float *pos, float
   return 3;
 }
 
-void mesh_release(fspt_scene::Mesh &M) {
-  hipFree(M.vertex); hipFree(M.cst); hipFree(M.face); hipFree(M.rest); hipFree(M.adj_off); hipFree(M.adj_face);
-  hipFree(M.fnorm); hipFree(M.vnorm); hipFree(M.pos);
-  for (hipEvent_t &e : M.ev) if (e) { hipEventDestroy(e); e = nullptr; }
-  M = fspt_scene::Mesh();
-}
-
-int mesh_update(fspt_scene *s, const float *pos, bool on_device) {
-  fspt_scene::Mesh &M = s->mesh;
-  for (hipEvent_t &e : M.ev) if (!e) HIP_TRY(hipEventCreate(&e));
-  if (!on_device) {
-    HIP_TRY(hipMemcpy(M.pos, pos, (size_t)M.n_vertices * 12, hipMemcpyHostToDevice));
-    pos = M.pos;
-  }
-  hipStream_t st = nullptr;
-  HIP_TRY(hipEventRecord(M.ev[0], st));
-  M.last_launches = mesh_run(M, s->n_tris, pos, s->rf.stage, M.ev + 2);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(M.ev[1], st));
-  HIP_TRY(hipEventSynchronize(M.ev[1]));
-  HIP_TRY(hipEventElapsedTime(&M.last_ms, M.ev[0], M.ev[1]));
-  M.pass_ms[0] = M.last_ms; M.pass_ms[1] = M.pass_ms[2] = 0.0f;
-  if (M.last_launches == 3) { // faces | vertex normals | smooth frames
-    HIP_TRY(hipEventElapsedTime(&M.pass_ms[0], M.ev[0], M.ev[2]));
-    HIP_TRY(hipEventElapsedTime(&M.pass_ms[1], M.ev[2], M.ev[3]));
-    HIP_TRY(hipEventElapsedTime(&M.pass_ms[2], M.ev[3], M.ev[1]));
-  }
-  M.meshed = false; // (fspt_scene_update_vertices sets it once the refit has accepted the arrays)
-  s->pose.posed = false; // (the staging array no longer holds a pose's or a skin's output)
-  s->skin.skinned = false;
-  return FSPT_OK;
-}
-
 int f64_probe_run(int op, const double *a, const double *b, uint32_t n, double *out) {
   double *d = nullptr;
   HIP_TRY(hipMalloc((void **)&d, (size_t)n * 24));
@@ -397,71 +364,80 @@ int f64_probe_run(int op, const double *a, const double *b, uint32_t n, double *
 
 int g_skin_form = SKIN_FORM; // the shipped joint-table form, or fspt_skin_set_form's
 
-void skin_release(fspt_scene *s) {
-  fspt_scene::Skin &K = s->skin;
-  hipFree(K.joints); hipFree(K.weights); hipFree(K.rest); hipFree(K.morph); hipFree(K.morph_norm); hipFree(K.frame);
-  for (hipEvent_t &e : K.ev) if (e) { hipEventDestroy(e); e = nullptr; }
-  K = fspt_scene::Skin();
-}
-
-int skin_run(fspt_scene *s, const float *xf, const float *morph_w, bool on_device) {
-  fspt_scene::Skin &K = s->skin;
+uint32_t skin_run(fspt_scene *s, const float *xf, const float *morph_w) {
+  const fspt_scene::Skin &K = s->skin;
   const uint32_t T = s->n_tris;
-  for (hipEvent_t &e : K.ev) if (!e) HIP_TRY(hipEventCreate(&e));
-  if (!on_device) { // the frame goes to the skin's own buffer: n_joints x 12 floats | n_morph weights
-    HIP_TRY(hipMemcpy(K.frame, xf, (size_t)K.n_joints * 48, hipMemcpyHostToDevice));
-    if (K.n_morph) HIP_TRY(hipMemcpy(K.frame + (size_t)K.n_joints * 12, morph_w, (size_t)K.n_morph * 4, hipMemcpyHostToDevice));
-    xf = K.frame; morph_w = K.frame + (size_t)K.n_joints * 12;
-  }
   const bool lds = g_skin_form == 1 && (size_t)K.n_joints * 48 <= SKIN_LDS_MAX_BYTES;
   const uint32_t blocks = (uint32_t)(((size_t)T * 3 + 255) / 256);
   hipStream_t st = nullptr;
-  HIP_TRY(hipEventRecord(K.ev[0], st));
   if (blocks) {
     if (K.has_norm) { if (K.n_morph) skin_launch<true, true>(lds, blocks, st, K, xf, morph_w, T, s->rf.stage); else skin_launch<true, false>(lds, blocks, st, K, xf, morph_w, T, s->rf.stage); }
     else { if (K.n_morph) skin_launch<false, true>(lds, blocks, st, K, xf, morph_w, T, s->rf.stage); else skin_launch<false, false>(lds, blocks, st, K, xf, morph_w, T, s->rf.stage); }
   }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(K.ev[1], st));
-  HIP_TRY(hipEventSynchronize(K.ev[1]));
-  HIP_TRY(hipEventElapsedTime(&K.last_ms, K.ev[0], K.ev[1]));
-  K.skinned = true;
-  s->pose.posed = false; // (the staging array no longer holds a pose's output)
-  s->mesh.meshed = false;
+  return blocks ? 1u : 0u;
+}
+
+int skin_upload(fspt_scene::Skin &K, const float *xf, const float *morph_w) {
+  HIP_TRY(hipMemcpy(K.frame, xf, (size_t)K.n_joints * 48, hipMemcpyHostToDevice));
+  if (K.n_morph) HIP_TRY(hipMemcpy(K.frame + (size_t)K.n_joints * 12, morph_w, (size_t)K.n_morph * 4, hipMemcpyHostToDevice));
   return FSPT_OK;
 }
 
-void pose_release(fspt_scene *s) {
-  fspt_scene::Pose &P = s->pose;
-  hipFree(P.part); hipFree(P.rest); hipFree(P.mats);
-  for (hipEvent_t &e : P.ev) if (e) { hipEventDestroy(e); e = nullptr; }
-  P = fspt_scene::Pose();
+uint32_t pose_run(fspt_scene *s) {
+  const fspt_scene::Pose &P = s->pose;
+  const uint32_t T = s->n_tris, BS = 256;
+  const size_t n = (size_t)T * (P.has_norm ? 12 : 3);
+  hipStream_t st = nullptr;
+  if (n)
+    hipLaunchKernelGGL(k_pose_transform, dim3((uint32_t)((n + BS - 1) / BS)), dim3(BS), 0, st, P.rest, P.has_norm ? P.rest + (size_t)T * 9 : nullptr,
+                       P.part, P.mats, T, P.n_parts, s->rf.stage, s->rf.stage + (size_t)T * 9);
+  return n ? 1u : 0u;
 }
 
-int pose_run(fspt_scene *s, const float *mats_host) {
-  fspt_scene::Pose &P = s->pose;
-  const uint32_t T = s->n_tris, BS = 256;
+int pose_upload(fspt_scene::Pose &P, const float *mats_host) {
   if (P.mats_cap < P.n_parts) {
     hipFree(P.mats); P.mats = nullptr; P.mats_cap = 0;
     HIP_TRY(hipMalloc((void **)&P.mats, (size_t)P.n_parts * 30 * 4));
     P.mats_cap = P.n_parts;
   }
-  for (hipEvent_t &e : P.ev) if (!e) HIP_TRY(hipEventCreate(&e));
   HIP_TRY(hipMemcpy(P.mats, mats_host, (size_t)P.n_parts * 30 * 4, hipMemcpyHostToDevice));
-  const size_t n = (size_t)T * (P.has_norm ? 12 : 3);
-  hipStream_t st = nullptr;
-  HIP_TRY(hipEventRecord(P.ev[0], st));
-  if (n)
-    hipLaunchKernelGGL(k_pose_transform, dim3((uint32_t)((n + BS - 1) / BS)), dim3(BS), 0, st, P.rest, P.has_norm ? P.rest + (size_t)T * 9 : nullptr,
-                       P.part, P.mats, T, P.n_parts, s->rf.stage, s->rf.stage + (size_t)T * 9);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(P.ev[1], st));
-  HIP_TRY(hipEventSynchronize(P.ev[1]));
-  HIP_TRY(hipEventElapsedTime(&P.last_ms, P.ev[0], P.ev[1]));
-  P.posed = true;
-  s->skin.skinned = false; // (the staging array no longer holds a skin's output)
-  s->mesh.meshed = false;
   return FSPT_OK;
+}
+
+// The arrays of each deformer, in the order a rebuild permutes them (ids and float64 constants go as words).  The mesh's
+// vertex -> face rows and the face normals they index are in face ids, which a rebuild does not change: they do not follow.
+std::vector<DeformArray> deform_arrays(fspt_scene::Pose &P, size_t T) {
+  return {{(void **)&P.part, T, {1u, 0u}, 1, true}, {(void **)&P.rest, T, {9u, P.has_norm ? 27u : 0u}, 1, true}, {(void **)&P.mats, P.mats_cap, {30u, 0u}, 1, false}};
+}
+
+std::vector<DeformArray> deform_arrays(fspt_scene::Skin &K, size_t T) {
+  return {{(void **)&K.joints, T, {6u, 0u}, 1, true}, {(void **)&K.weights, T, {12u, 0u}, 1, true}, {(void **)&K.rest, T, {9u, K.has_norm ? 27u : 0u}, 1, true},
+          {(void **)&K.morph, T, {9u, 0u}, K.n_morph, true}, {(void **)&K.morph_norm, T, {27u, 0u}, K.n_morph, true},
+          {(void **)&K.frame, 1, {K.n_joints * 12u + K.n_morph, 0u}, 1, false}};
+}
+
+std::vector<DeformArray> deform_arrays(fspt_scene::Mesh &M, size_t T) {
+  const size_t nv = M.n_vertices;
+  return {{(void **)&M.vertex, T, {3u, 0u}, 1, true}, {(void **)&M.cst, T, {6u, 0u}, 1, true}, {(void **)&M.face, T, {1u, 0u}, 1, true}, {(void **)&M.rest, T, {9u, 27u}, 1, true},
+          {(void **)&M.pos, nv, {3u, 0u}, 1, false}, {(void **)&M.adj_off, nv + 1, {1u, 0u}, 1, false}, {(void **)&M.adj_face, M.n_adj ? M.n_adj : 1u, {1u, 0u}, 1, false},
+          {(void **)&M.fnorm, T, {6u, 0u}, 1, false}, {(void **)&M.vnorm, nv, {6u, 0u}, 1, false}};
+}
+
+uint64_t deform_bytes(const std::vector<DeformArray> &arrays) {
+  uint64_t bytes = 0;
+  for (const DeformArray &a : arrays) if (*a.p) bytes += (uint64_t)a.rows * (a.span[0] + a.span[1]) * 4u * a.slices;
+  return bytes;
+}
+
+static void arrays_free(const std::vector<DeformArray> &arrays) { for (const DeformArray &a : arrays) hipFree(*a.p); }
+
+void mesh_release(fspt_scene::Mesh &M) { arrays_free(deform_arrays(M, 0)); M = fspt_scene::Mesh(); }
+
+void deformer_release(fspt_scene *s, fspt_scene::StageOwner who) {
+  if (who == fspt_scene::STAGE_POSE) { arrays_free(deform_arrays(s->pose, 0)); s->pose = fspt_scene::Pose(); }
+  if (who == fspt_scene::STAGE_SKIN) { arrays_free(deform_arrays(s->skin, 0)); s->skin = fspt_scene::Skin(); }
+  if (who == fspt_scene::STAGE_MESH) mesh_release(s->mesh);
+  stage_disown(s, who);
 }
 
 } // namespace fspt

@@ -311,21 +311,15 @@ struct RebuildGuard {
   BvhGpuDevice bt;
   uint32_t *d_map = nullptr;
   int32_t *d_cref = nullptr;
-  uint32_t *p_part = nullptr; // the pose in the new leaf order
-  float *p_rest = nullptr;
-  void *k_new[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // the skin in the new leaf order: joints, weights, rest, morph, morph_norm
-  void *m_new[4] = {nullptr, nullptr, nullptr, nullptr}; // the mesh in the new leaf order: vertex, cst, face, rest
+  Hold moved; // the deformers' arrays that follow the triangles, in the new leaf order
   hipEvent_t ev[2] = {nullptr, nullptr};
   bool keep = false;
   ~RebuildGuard() {
     bvh_device_release(bt);
     hipFree(d_map); hipFree(d_cref);
     for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
-    if (keep) return;
+    if (keep) { moved.p.clear(); return; }
     geometry_free(ns);
-    hipFree(p_part); hipFree(p_rest);
-    for (void *p : k_new) hipFree(p);
-    for (void *p : m_new) hipFree(p);
     refit_release(&ns);
   }
 };
@@ -397,23 +391,15 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
   REBUILD_ALLOC(&ns.rf.stage, (size_t)T * 36 * 4); // tri | norm in the new leaf order; the scene's staging array from now on
   REBUILD_ALLOC(&G.d_map, (size_t)T * 4);
   REBUILD_ALLOC(&G.d_cref, cref.size() * 4);
-  const fspt_scene::Pose &P = s->pose;
-  if (P.part) {
-    REBUILD_ALLOC(&G.p_part, (size_t)T * 4);
-    REBUILD_ALLOC(&G.p_rest, (size_t)T * (P.has_norm ? 36 : 9) * 4);
+  // every deformer's arrays that follow their triangles (ids and float64 constants as words)
+  std::vector<DeformArray> follow;
+  for (fspt_scene::StageOwner who : {fspt_scene::STAGE_POSE, fspt_scene::STAGE_SKIN, fspt_scene::STAGE_MESH})
+    for (const DeformArray &a : deform_arrays(s, who)) if (a.follows && *a.p) follow.push_back(a);
+  for (const DeformArray &a : follow) {
+    void *p = nullptr;
+    REBUILD_ALLOC(&p, (size_t)T * (a.span[0] + a.span[1]) * 4 * a.slices);
+    G.moved.p.push_back(p);
   }
-  // the skin's arrays as (array, words per triangle, slices of T triangles): a morph array is one slice per target
-  const fspt_scene::Skin &K = s->skin;
-  const struct { const void *src; uint32_t words; size_t slices; } k_old[5] = {
-      {K.joints, 6u, 1}, {K.weights, 12u, 1}, {K.rest, K.has_norm ? 36u : 9u, 1}, {K.morph, 9u, K.n_morph}, {K.morph_norm, 27u, K.n_morph}};
-  for (int a = 0; K.joints && a < 5; ++a)
-    if (k_old[a].src) REBUILD_ALLOC(&G.k_new[a], (size_t)T * k_old[a].words * 4 * k_old[a].slices);
-  // the mesh's per-triangle arrays alike (float64 constants as two words each); its vertex -> face rows and the face
-  // normals they index are in face ids, which a rebuild does not change, and stay as they are
-  const fspt_scene::Mesh &M = s->mesh;
-  const struct { const void *src; uint32_t words; } m_old[4] = {{M.vertex, 3u}, {M.cst, 6u}, {M.face, 1u}, {M.rest, 36u}};
-  for (int a = 0; M.vertex && a < 4; ++a)
-    if (m_old[a].src) REBUILD_ALLOC(&G.m_new[a], (size_t)T * m_old[a].words * 4);
   rc = refit_prepare(&ns);
   if (rc) return rc;
   HIP_TRY(hipEventCreate(&G.ev[0]));
@@ -431,41 +417,17 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
   hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 9, BS)), dim3(BS), 0, st, tri, G.bt.order, T, 9u, ptri);
   launches += 2;
   if (norm) { hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 27, BS)), dim3(BS), 0, st, norm, G.bt.order, T, 27u, pnorm); ++launches; }
-  if (P.part) { // the pose follows its triangles: part ids (as words), rest vertices, rest normTex records
-    hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T, BS)), dim3(BS), 0, st, (const float *)P.part, G.bt.order, T, 1u, (float *)G.p_part);
-    hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 9, BS)), dim3(BS), 0, st, P.rest, G.bt.order, T, 9u, G.p_rest);
-    launches += 2;
-    if (P.has_norm) {
-      hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 27, BS)), dim3(BS), 0, st, P.rest + (size_t)T * 9, G.bt.order, T, 27u, G.p_rest + (size_t)T * 9);
-      ++launches;
-    }
-  }
-  for (int a = 0; K.joints && a < 5; ++a) { // the skin follows its triangles (ids as words); rest = 9 T vertices | 27 T records
-    if (!k_old[a].src) continue;
-    const float *src = (const float *)k_old[a].src;
-    float *dst = (float *)G.k_new[a];
-    if (a == 2) {
-      hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 9, BS)), dim3(BS), 0, st, src, G.bt.order, T, 9u, dst);
-      ++launches;
-      if (K.has_norm) { hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 27, BS)), dim3(BS), 0, st, src + (size_t)T * 9, G.bt.order, T, 27u, dst + (size_t)T * 9); ++launches; }
-      continue;
-    }
-    const uint32_t W = k_old[a].words;
-    for (size_t m = 0; m < k_old[a].slices; ++m, ++launches)
-      hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * W, BS)), dim3(BS), 0, st, src + m * T * W, G.bt.order, T, W, dst + m * T * W);
-  }
-  for (int a = 0; M.vertex && a < 4; ++a) { // the mesh follows its triangles; rest = 9 T vertices | 27 T records
-    if (!m_old[a].src) continue;
-    const float *src = (const float *)m_old[a].src;
-    float *dst = (float *)G.m_new[a];
-    if (a == 3) {
-      hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 9, BS)), dim3(BS), 0, st, src, G.bt.order, T, 9u, dst);
-      hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * 27, BS)), dim3(BS), 0, st, src + (size_t)T * 9, G.bt.order, T, 27u, dst + (size_t)T * 9);
-      launches += 2;
-      continue;
-    }
-    hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * m_old[a].words, BS)), dim3(BS), 0, st, src, G.bt.order, T, m_old[a].words, dst);
-    ++launches;
+  for (size_t i = 0; i < follow.size(); ++i) { // span by span, slice by slice
+    const float *src = (const float *)*follow[i].p;
+    float *dst = (float *)G.moved.p[i];
+    size_t at = 0;
+    for (size_t m = 0; m < follow[i].slices; ++m)
+      for (const uint32_t W : follow[i].span) {
+        if (!W) continue;
+        hipLaunchKernelGGL(k_rebuild_permute, dim3(blocks_for((size_t)T * W, BS)), dim3(BS), 0, st, src + at, G.bt.order, T, W, dst + at);
+        at += (size_t)T * W;
+        ++launches;
+      }
   }
   hipLaunchKernelGGL(k_rebuild_gather, dim3(blocks_for(n_slots * 12, BS)), dim3(BS), 0, st, (const float4 *)s->shade, old_slots, G.d_map, G.bt.order,
                      ns.rf.d_leaf, nl, LS, T, (float4 *)ns.shade, (uint32_t *)ns.slot_tri, (float *)ns.tris);
@@ -490,25 +452,9 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
   G.keep = true;
   geometry_free(*s);
   refit_release(s);
-  if (s->pose.part) { // (rf.stage is a new array: what read_pose would return is gone)
-    hipFree(s->pose.part); hipFree(s->pose.rest);
-    s->pose.part = G.p_part; s->pose.rest = G.p_rest;
-    s->pose.posed = false;
-  }
-  if (s->skin.joints) {
-    fspt_scene::Skin &Ks = s->skin;
-    hipFree(Ks.joints); hipFree(Ks.weights); hipFree(Ks.rest); hipFree(Ks.morph); hipFree(Ks.morph_norm);
-    Ks.joints = (uint16_t *)G.k_new[0]; Ks.weights = (float *)G.k_new[1]; Ks.rest = (float *)G.k_new[2];
-    Ks.morph = (float *)G.k_new[3]; Ks.morph_norm = (float *)G.k_new[4];
-    Ks.skinned = false;
-  }
-  if (s->mesh.vertex) {
-    fspt_scene::Mesh &Ms = s->mesh;
-    hipFree(Ms.vertex); hipFree(Ms.cst); hipFree(Ms.face); hipFree(Ms.rest);
-    Ms.vertex = (uint32_t *)G.m_new[0]; Ms.cst = (double *)G.m_new[1]; Ms.face = (uint32_t *)G.m_new[2]; Ms.rest = (float *)G.m_new[3];
-    Ms.meshed = false;
-  }
+  for (size_t i = 0; i < follow.size(); ++i) { hipFree(*follow[i].p); *follow[i].p = G.moved.p[i]; }
   s->rf = std::move(ns.rf);
+  stage_disown(s); // (rf.stage is a new array: what read_pose / _skin / _mesh would return is gone)
   s->motion = ns.motion; s->nodes = ns.nodes; s->quads = ns.quads; s->tris = ns.tris; s->slot_tri = ns.slot_tri; s->shade = ns.shade;
   geometry_publish(s, tp, nn, n_slots, quads_ok != 0);
   s->rb.build_ms = G.bt.kernel_ms;

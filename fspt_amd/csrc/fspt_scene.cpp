@@ -715,9 +715,8 @@ int fspt_scene_destroy(fspt_scene *s) {
   hipFree(s->atlas); hipFree(s->atlas4); hipFree(s->tex_sets); hipFree(s->env); hipFree(s->bins); hipFree(s->l_alias); hipFree(s->l_rec); hipFree(s->l_p); hipFree(s->l_pick);
   fspt::refit_release(s);
   fspt::appearance_release(s);
-  fspt::pose_release(s);
-  fspt::skin_release(s);
-  fspt::mesh_release(s->mesh);
+  for (fspt_scene::StageOwner who : {fspt_scene::STAGE_POSE, fspt_scene::STAGE_SKIN, fspt_scene::STAGE_MESH}) fspt::deformer_release(s, who);
+  for (hipEvent_t ev : s->deform_ev) if (ev) hipEventDestroy(ev);
   fspt::sky_release(s);
   fspt::lights_release(s);
   for (hipEvent_t &ev : s->lg.host_ev) if (ev) hipEventDestroy(ev);

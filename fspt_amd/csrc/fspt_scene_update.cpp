@@ -1,6 +1,7 @@
 // fspt_scene_update.cpp - every entry that changes a live scene, or reports on such a change: in-place geometry update
 // (DESIGN 8.6), rebuild (8.7), appearance update (8.13), part transforms (8.14), skinning (8.16), the vertex-position update (8.24), the GPU sky (8.17), the motion origin (8.8)
-// and the read-outs that go with them.  What the families share stands once, first; every refusal names the calling entry.
+// and the read-outs that go with them.  What the families share stands once, first - for the three deformers that fill the
+// staging array that is their whole set, drop, update and read path; every refusal names the calling entry.
 #include "fspt_internal.hpp"
 #include "fspt_texpack_check.hpp"
 
@@ -60,9 +61,7 @@ static int stage_upload(fspt_scene *s, const float *&tri, const float *&norm) {
   const int rc = stage_ensure(s);
   if (rc) return rc;
   const size_t T = s->n_tris;
-  s->pose.posed = false; // (the staging array no longer holds a pose's or a skin's output)
-  s->skin.skinned = false;
-  s->mesh.meshed = false;
+  fspt::stage_disown(s);
   HIP_TRY(hipMemcpy(s->rf.stage, tri, T * 9 * 4, hipMemcpyHostToDevice));
   if (norm) HIP_TRY(hipMemcpy(s->rf.stage + T * 9, norm, T * 27 * 4, hipMemcpyHostToDevice));
   tri = s->rf.stage;
@@ -70,8 +69,12 @@ static int stage_upload(fspt_scene *s, const float *&tri, const float *&norm) {
   return FSPT_OK;
 }
 
-// The staging array's tri / norm (either may be NULL) to the host: what the last pose, skin or mesh update wrote.
-static int stage_download(fspt_scene *s, float *tri, float *norm) {
+// fspt_scene_read_pose / _skin / _mesh: the staging array's tri / norm (either may be NULL) to the host, while it holds a
+// frame of `who` that the refit accepted.  `none` / `no_norm`: the entry's texts for "no such frame" / "it fills no norm".
+static int read_stage(fspt_scene *s, const char *fn, fspt_scene::StageOwner who, bool has_norm, float *tri, float *norm, const char *none, const char *no_norm) {
+  if (!s || (!tri && !norm)) { fspt_set_error("%s: NULL argument", fn); return FSPT_E_INVALID; }
+  if (s->rf.stage_owner != who) { fspt_set_error("%s: %s", fn, none); return FSPT_E_STATE; }
+  if (norm && !has_norm) { fspt_set_error("%s: %s", fn, no_norm); return FSPT_E_STATE; }
   const int rc = check_device(s->device);
   if (rc) return rc;
   const size_t T = s->n_tris;
@@ -106,12 +109,28 @@ static hipError_t alloc_and_upload(const DevicePart *parts, size_t n) {
   return e;
 }
 
-extern "C" {
+// ... and when that failed: the code, and the text with the entry's own counts in its parenthesis
+static int refuse_hip(const char *fn, hipError_t e, const char *counts_fmt, ...) {
+  char counts[128];
+  va_list ap;
+  va_start(ap, counts_fmt);
+  vsnprintf(counts, sizeof(counts), counts_fmt, ap);
+  va_end(ap);
+  fspt_set_error("%s: %s (%s)", fn, hipGetErrorString(e), counts);
+  return e == hipErrorOutOfMemory ? FSPT_E_NOMEM : FSPT_E_HIP;
+}
 
-// ---------------------------------------------------------------------------
-// in-place geometry update (DESIGN 8.6; kernels in fspt_refit.hip)
-// ---------------------------------------------------------------------------
-// the refit of update_geometry / update_transforms proper: tri / norm are device memory, the call is ordered and s->rf prepared
+// fspt_scene_set_pose / _skin / _mesh with a NULL description: a deformer that is not set is dropped without touching a device
+static int drop_deformer(fspt_scene *s, fspt_scene::StageOwner who, bool is_set) {
+  if (!is_set) return FSPT_OK;
+  const int rc = check_device(s->device);
+  if (rc) return rc;
+  fspt::deformer_release(s, who);
+  return FSPT_OK;
+}
+
+// the refit of update_geometry and of the deformers proper (kernels in fspt_refit.hip): tri / norm are device
+// memory, the call is ordered and s->rf prepared
 static int refit_device_arrays(fspt_scene *s, const float *tri, const float *norm, const char *fn) {
   int rc = FSPT_OK;
   if (!s->quads && s->n_interior) { // a scene created from refitted boxes may have two-level nodes where this one had none
@@ -125,6 +144,45 @@ static int refit_device_arrays(fspt_scene *s, const float *tri, const float *nor
   return geometry_changed_lights(s);
 }
 
+// Fill the staging array, then refit from it: what update_transforms, update_skin and update_vertices share once their
+// arguments are checked.  `upload` (a host form's frame; FSPT_OK or the error) runs with the scene's device current and
+// outside the timing; `enqueue` puts the deformer's kernels on the NULL stream - three passes record deform_ev[2] and [3]
+// between them - and returns its launches.  *ms: first kernel to last; pass_ms / launches: may be NULL.  `who` owns the
+// staging array once the refit has accepted the frame, and nobody does from the first write on until then.
+template <class Upload, class Enqueue>
+static int deform_and_refit(fspt_scene *s, const char *fn, fspt_scene::StageOwner who, bool has_norm, float *ms, float *pass_ms, uint32_t *launches, Upload upload, Enqueue enqueue) {
+  int rc = begin_refit(s);
+  if (rc || (rc = stage_ensure(s))) return rc;
+  hipEvent_t *ev = s->deform_ev;
+  for (int i = 0; i < 4; ++i) if (!ev[i]) HIP_TRY(hipEventCreate(&ev[i]));
+  if ((rc = upload())) return rc;
+  fspt::stage_disown(s);
+  HIP_TRY(hipEventRecord(ev[0], nullptr));
+  const uint32_t n = enqueue();
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ev[1], nullptr));
+  HIP_TRY(hipEventSynchronize(ev[1]));
+  HIP_TRY(hipEventElapsedTime(ms, ev[0], ev[1]));
+  if (launches) *launches = n;
+  if (pass_ms) {
+    pass_ms[0] = *ms; pass_ms[1] = pass_ms[2] = 0.0f;
+    if (n == 3) { // faces | vertex normals | smooth frames
+      HIP_TRY(hipEventElapsedTime(&pass_ms[0], ev[0], ev[2]));
+      HIP_TRY(hipEventElapsedTime(&pass_ms[1], ev[2], ev[3]));
+      HIP_TRY(hipEventElapsedTime(&pass_ms[2], ev[3], ev[1]));
+    }
+  }
+  const size_t T = s->n_tris;
+  if ((rc = refit_device_arrays(s, s->rf.stage, has_norm ? s->rf.stage + T * 9 : nullptr, fn))) return rc;
+  s->rf.stage_owner = who; // (a refused frame is not handed out by fspt_scene_read_pose / _skin / _mesh)
+  return FSPT_OK;
+}
+
+extern "C" {
+
+// ---------------------------------------------------------------------------
+// in-place geometry update (DESIGN 8.6; kernels in fspt_refit.hip)
+// ---------------------------------------------------------------------------
 static int update_geometry(fspt_scene *s, const float *tri, const float *norm, bool on_device, const char *fn) {
   if (!s || !tri) { fspt_set_error("%s: NULL scene or tri", fn); return FSPT_E_INVALID; }
   int rc = FSPT_OK;
@@ -198,13 +256,7 @@ int fspt_pose_matrices_eval(const float *xf, uint32_t n_parts, float *out, uint3
 
 int fspt_scene_set_pose(fspt_scene *s, const uint32_t *part, uint32_t n_parts, const float *tri, const float *norm) {
   if (!s) { fspt_set_error("fspt_scene_set_pose: NULL scene"); return FSPT_E_INVALID; }
-  if (!part) { // drop the pose
-    if (!s->pose.part && !s->pose.mats) return FSPT_OK;
-    int rc = check_device(s->device);
-    if (rc) return rc;
-    fspt::pose_release(s);
-    return FSPT_OK;
-  }
+  if (!part) return drop_deformer(s, fspt_scene::STAGE_POSE, s->pose.part || s->pose.mats);
   if (!tri || n_parts == 0) { fspt_set_error("fspt_scene_set_pose: tri is NULL or n_parts is 0"); return FSPT_E_INVALID; }
   const size_t T = s->n_tris;
   for (size_t i = 0; i < T; ++i) if (part[i] >= n_parts) { fspt_set_error("fspt_scene_set_pose: part[%zu] = %u, n_parts = %u", i, part[i], n_parts); return FSPT_E_INVALID; }
@@ -219,15 +271,12 @@ int fspt_scene_set_pose(fspt_scene *s, const uint32_t *part, uint32_t n_parts, c
   const DevicePart parts[] = {{(void **)&d_part, part, T * 4, T1 * 4, 0}, {(void **)&d_rest, tri, T * 36, T1 * (norm ? 144 : 36), 0},
                               {(void **)&d_rest, norm, T * 108, 0, T * 36}};
   const hipError_t e = alloc_and_upload(parts, 3);
-  if (e != hipSuccess) {
-    fspt_set_error("fspt_scene_set_pose: %s (%zu triangles)", hipGetErrorString(e), T);
-    return e == hipErrorOutOfMemory ? FSPT_E_NOMEM : FSPT_E_HIP;
-  }
-  hipFree(s->pose.part); hipFree(s->pose.rest);
+  if (e != hipSuccess) return refuse_hip("fspt_scene_set_pose", e, "%zu triangles", T);
+  hipFree(s->pose.part); hipFree(s->pose.rest); // (pose.mats stays: it holds matrices, whatever the triangles)
   s->pose.part = d_part; s->pose.rest = d_rest;
   s->pose.has_norm = norm != nullptr;
   s->pose.n_parts = n_parts;
-  s->pose.posed = false;
+  fspt::stage_disown(s, fspt_scene::STAGE_POSE);
   return FSPT_OK;
 }
 
@@ -241,17 +290,13 @@ int fspt_scene_update_transforms(fspt_scene *s, const float *xf, uint32_t n_part
     fspt_set_error("fspt_scene_update_transforms: part %u: %s (scene unchanged)", bad, why);
     return FSPT_E_INVALID;
   }
-  int rc = begin_refit(s);
-  if (rc || (rc = stage_ensure(s)) || (rc = fspt::pose_run(s, mats.data()))) return rc;
-  const size_t T = s->n_tris;
-  return refit_device_arrays(s, s->rf.stage, s->pose.has_norm ? s->rf.stage + T * 9 : nullptr, "fspt_scene_update_transforms");
+  return deform_and_refit(s, "fspt_scene_update_transforms", fspt_scene::STAGE_POSE, s->pose.has_norm, &s->pose.last_ms, nullptr, nullptr,
+                          [&] { return fspt::pose_upload(s->pose, mats.data()); }, [&] { return fspt::pose_run(s); });
 }
 
 int fspt_scene_read_pose(fspt_scene *s, float *tri, float *norm) {
-  if (!s || (!tri && !norm)) { fspt_set_error("fspt_scene_read_pose: NULL argument"); return FSPT_E_INVALID; }
-  if (!s->pose.part || !s->pose.posed) { fspt_set_error("fspt_scene_read_pose: no fspt_scene_update_transforms since the pose was set, the scene rebuilt or its geometry uploaded"); return FSPT_E_STATE; }
-  if (norm && !s->pose.has_norm) { fspt_set_error("fspt_scene_read_pose: the pose has no rest norm"); return FSPT_E_STATE; }
-  return stage_download(s, tri, norm);
+  return read_stage(s, "fspt_scene_read_pose", fspt_scene::STAGE_POSE, s && s->pose.has_norm, tri, norm,
+                    "no fspt_scene_update_transforms since the pose was set, the scene rebuilt or its geometry uploaded", "the pose has no rest norm");
 }
 
 int fspt_scene_last_pose_ms(fspt_scene *s, float *transform_ms, float *refit_ms, uint32_t *launches) {
@@ -297,22 +342,9 @@ int fspt_skin_set_form(int form) {
   return FSPT_OK;
 }
 
-static uint64_t skin_bytes(const fspt_scene *s) {
-  const fspt_scene::Skin &K = s->skin;
-  if (!K.joints) return 0;
-  const uint64_t T = s->n_tris;
-  return T * (24 + 48 + 36 + (K.has_norm ? 108 : 0)) + (uint64_t)K.n_morph * T * (36 + (K.morph_norm ? 108 : 0)) + (uint64_t)K.n_joints * 48 + (uint64_t)K.n_morph * 4;
-}
-
 int fspt_scene_set_skin(fspt_scene *s, const fspt_skin_desc *d) {
   if (!s) { fspt_set_error("fspt_scene_set_skin: NULL scene"); return FSPT_E_INVALID; }
-  if (!d) { // drop the skin
-    if (!s->skin.joints) return FSPT_OK;
-    int rc = check_device(s->device);
-    if (rc) return rc;
-    fspt::skin_release(s);
-    return FSPT_OK;
-  }
+  if (!d) return drop_deformer(s, fspt_scene::STAGE_SKIN, s->skin.joints != nullptr);
   const size_t T = s->n_tris;
   uint64_t bad = 0;
   int rc = skin_check(d, T, "fspt_scene_set_skin", &bad);
@@ -329,14 +361,11 @@ int fspt_scene_set_skin(fspt_scene *s, const fspt_skin_desc *d) {
       {(void **)&N.morph, d->morph, M * T * 36, M * T1 * 36, 0}, {(void **)&N.morph_norm, d->morph_norm, M * T * 108, d->morph_norm ? M * T1 * 108 : 0, 0},
       {(void **)&N.frame, nullptr, 0, (size_t)d->n_joints * 48 + M * 4, 0}, {(void **)&N.rest, d->norm, T * 108, 0, T * 36}};
   const hipError_t e = alloc_and_upload(parts, sizeof(parts) / sizeof(parts[0]));
-  if (e != hipSuccess) {
-    fspt_set_error("fspt_scene_set_skin: %s (%zu triangles, %u joints, %u morph targets)", hipGetErrorString(e), T, d->n_joints, d->n_morph);
-    return e == hipErrorOutOfMemory ? FSPT_E_NOMEM : FSPT_E_HIP;
-  }
+  if (e != hipSuccess) return refuse_hip("fspt_scene_set_skin", e, "%zu triangles, %u joints, %u morph targets", T, d->n_joints, d->n_morph);
   N.has_norm = d->norm != nullptr;
   N.n_joints = d->n_joints;
   N.n_morph = d->n_morph;
-  fspt::skin_release(s);
+  fspt::deformer_release(s, fspt_scene::STAGE_SKIN);
   s->skin = N;
   return FSPT_OK;
 }
@@ -357,10 +386,10 @@ static int update_skin(fspt_scene *s, const float *xf, uint32_t n_joints, const 
     for (uint32_t m = 0; m < n_morph; ++m)
       if (!std::isfinite(morph_w[m])) { fspt_set_error("%s: morph target %u: its weight is not finite (scene unchanged)", fn, m); return FSPT_E_INVALID; }
   }
-  int rc = begin_refit(s);
-  if (rc || (rc = stage_ensure(s)) || (rc = fspt::skin_run(s, xf, morph_w, on_device))) return rc;
-  const size_t T = s->n_tris;
-  return refit_device_arrays(s, s->rf.stage, K.has_norm ? s->rf.stage + T * 9 : nullptr, fn);
+  // the host form's frame goes to the skin's own buffer: n_joints x 12 floats | n_morph weights
+  const float *d_xf = on_device ? xf : K.frame, *d_w = on_device ? morph_w : K.frame + (size_t)K.n_joints * 12;
+  return deform_and_refit(s, fn, fspt_scene::STAGE_SKIN, K.has_norm, &s->skin.last_ms, nullptr, nullptr,
+                          [&] { return on_device ? FSPT_OK : fspt::skin_upload(s->skin, xf, morph_w); }, [&] { return fspt::skin_run(s, d_xf, d_w); });
 }
 
 int fspt_scene_update_skin(fspt_scene *s, const float *xf, uint32_t n_joints, const float *morph_w, uint32_t n_morph) {
@@ -372,10 +401,8 @@ int fspt_scene_update_skin_device(fspt_scene *s, const float *xf, uint32_t n_joi
 }
 
 int fspt_scene_read_skin(fspt_scene *s, float *tri, float *norm) {
-  if (!s || (!tri && !norm)) { fspt_set_error("fspt_scene_read_skin: NULL argument"); return FSPT_E_INVALID; }
-  if (!s->skin.joints || !s->skin.skinned) { fspt_set_error("fspt_scene_read_skin: no fspt_scene_update_skin since the skin was set, the scene rebuilt, posed or its geometry uploaded"); return FSPT_E_STATE; }
-  if (norm && !s->skin.has_norm) { fspt_set_error("fspt_scene_read_skin: the skin has no rest norm"); return FSPT_E_STATE; }
-  return stage_download(s, tri, norm);
+  return read_stage(s, "fspt_scene_read_skin", fspt_scene::STAGE_SKIN, s && s->skin.has_norm, tri, norm,
+                    "no fspt_scene_update_skin since the skin was set, the scene rebuilt, posed or its geometry uploaded", "the skin has no rest norm");
 }
 
 int fspt_scene_last_skin_ms(fspt_scene *s, float *skin_ms, float *refit_ms, uint32_t *launches, uint64_t *bytes) {
@@ -383,7 +410,7 @@ int fspt_scene_last_skin_ms(fspt_scene *s, float *skin_ms, float *refit_ms, uint
   if (skin_ms) *skin_ms = s->skin.last_ms;
   if (refit_ms) *refit_ms = s->rf.last_ms;
   if (launches) *launches = s->rf.last_launches + 1u;
-  if (bytes) *bytes = skin_bytes(s);
+  if (bytes) *bytes = fspt::deform_bytes(fspt::deform_arrays(s->skin, s->n_tris));
   return FSPT_OK;
 }
 
@@ -476,27 +503,14 @@ static hipError_t mesh_upload(const fspt_mesh_desc *d, size_t T, const MeshHost 
   if (e != hipSuccess) return e;
   N.n_vertices = d->n_vertices;
   N.n_adj = (uint32_t)na;
-  N.bytes = 0;
-  for (const DevicePart &p : parts) N.bytes += p.alloc;
   *out = N;
   return hipSuccess;
-}
-
-static int mesh_refuse_hip(const char *fn, hipError_t e, size_t T, uint32_t nv) {
-  fspt_set_error("%s: %s (%zu triangles, %u vertices)", fn, hipGetErrorString(e), T, nv);
-  return e == hipErrorOutOfMemory ? FSPT_E_NOMEM : FSPT_E_HIP;
 }
 
 int fspt_scene_set_mesh(fspt_scene *s, const fspt_mesh_desc *d) {
   const char *fn = "fspt_scene_set_mesh";
   if (!s) { fspt_set_error("%s: NULL scene", fn); return FSPT_E_INVALID; }
-  if (!d) { // drop the mesh
-    if (!s->mesh.vertex) return FSPT_OK;
-    int rc = check_device(s->device);
-    if (rc) return rc;
-    fspt::mesh_release(s->mesh);
-    return FSPT_OK;
-  }
+  if (!d) return drop_deformer(s, fspt_scene::STAGE_MESH, s->mesh.vertex != nullptr);
   const size_t T = s->n_tris;
   uint64_t bad = 0;
   MeshHost H;
@@ -506,28 +520,26 @@ int fspt_scene_set_mesh(fspt_scene *s, const fspt_mesh_desc *d) {
   if ((rc = check_device(s->device))) return rc;
   fspt_scene::Mesh N; // the new arrays first: an allocation that fails leaves the old mesh
   const hipError_t e = mesh_upload(d, T, H, &N);
-  if (e != hipSuccess) return mesh_refuse_hip(fn, e, T, d->n_vertices);
-  fspt::mesh_release(s->mesh);
+  if (e != hipSuccess) return refuse_hip(fn, e, "%zu triangles, %u vertices", T, d->n_vertices);
+  fspt::deformer_release(s, fspt_scene::STAGE_MESH);
   s->mesh = N;
   return FSPT_OK;
 }
 
 static int update_vertices(fspt_scene *s, const float *pos, uint32_t n_vertices, bool on_device, const char *fn) {
   if (!s || !pos) { fspt_set_error("%s: NULL scene or pos", fn); return FSPT_E_INVALID; }
-  const fspt_scene::Mesh &M = s->mesh;
-  if (!M.vertex) { fspt_set_error("%s: the scene has no mesh (fspt_scene_set_mesh)", fn); return FSPT_E_STATE; }
-  if (n_vertices != M.n_vertices) { fspt_set_error("%s: %u positions, the mesh has %u vertices", fn, n_vertices, M.n_vertices); return FSPT_E_INVALID; }
+  if (!s->mesh.vertex) { fspt_set_error("%s: the scene has no mesh (fspt_scene_set_mesh)", fn); return FSPT_E_STATE; }
+  if (n_vertices != s->mesh.n_vertices) { fspt_set_error("%s: %u positions, the mesh has %u vertices", fn, n_vertices, s->mesh.n_vertices); return FSPT_E_INVALID; }
   if (on_device) {
     if ((uintptr_t)pos % 4) { fspt_set_error("%s: pos must be 4-byte aligned", fn); return FSPT_E_INVALID; }
   } else if (const int rc = check_finite(fn, "pos", pos, (size_t)n_vertices * 3)) { // no device needed: refuse before anything is touched
     return rc;
   }
-  int rc = begin_refit(s);
-  if (rc || (rc = stage_ensure(s)) || (rc = fspt::mesh_update(s, pos, on_device))) return rc;
-  const size_t T = s->n_tris;
-  if ((rc = refit_device_arrays(s, s->rf.stage, s->rf.stage + T * 9, fn))) return rc;
-  s->mesh.meshed = true; // (a refused frame is not handed out by fspt_scene_read_mesh)
-  return FSPT_OK;
+  fspt_scene::Mesh &M = s->mesh;
+  const float *d_pos = on_device ? pos : M.pos; // the host form's frame goes to the mesh's own buffer
+  return deform_and_refit(s, fn, fspt_scene::STAGE_MESH, true, &M.last_ms, M.pass_ms, &M.last_launches,
+                          [&] { if (!on_device) HIP_TRY(hipMemcpy(M.pos, pos, (size_t)M.n_vertices * 12, hipMemcpyHostToDevice)); return FSPT_OK; },
+                          [&] { return fspt::mesh_run(M, s->n_tris, d_pos, s->rf.stage, s->deform_ev + 2); });
 }
 
 int fspt_scene_update_vertices(fspt_scene *s, const float *pos, uint32_t n_vertices) {
@@ -539,9 +551,8 @@ int fspt_scene_update_vertices_device(fspt_scene *s, const float *pos, uint32_t 
 }
 
 int fspt_scene_read_mesh(fspt_scene *s, float *tri, float *norm) {
-  if (!s || (!tri && !norm)) { fspt_set_error("fspt_scene_read_mesh: NULL argument"); return FSPT_E_INVALID; }
-  if (!s->mesh.vertex || !s->mesh.meshed) { fspt_set_error("fspt_scene_read_mesh: no fspt_scene_update_vertices since the mesh was set, the scene rebuilt, posed, skinned or its geometry uploaded"); return FSPT_E_STATE; }
-  return stage_download(s, tri, norm);
+  return read_stage(s, "fspt_scene_read_mesh", fspt_scene::STAGE_MESH, true, tri, norm,
+                    "no fspt_scene_update_vertices since the mesh was set, the scene rebuilt, posed, skinned or its geometry uploaded", "");
 }
 
 int fspt_scene_last_mesh_ms(fspt_scene *s, float *derive_ms, float *refit_ms, uint32_t *launches, uint64_t *bytes) {
@@ -549,7 +560,7 @@ int fspt_scene_last_mesh_ms(fspt_scene *s, float *derive_ms, float *refit_ms, ui
   if (derive_ms) *derive_ms = s->mesh.last_ms;
   if (refit_ms) *refit_ms = s->rf.last_ms;
   if (launches) *launches = s->rf.last_launches + s->mesh.last_launches;
-  if (bytes) *bytes = s->mesh.vertex ? s->mesh.bytes : 0;
+  if (bytes) *bytes = fspt::deform_bytes(fspt::deform_arrays(s->mesh, s->n_tris));
   return FSPT_OK;
 }
 
@@ -571,7 +582,7 @@ int fspt_mesh_frames_eval(int device, const fspt_mesh_desc *d, uint32_t n_tris, 
   struct Temp { fspt_scene::Mesh M; float *stage = nullptr; ~Temp() { fspt::mesh_release(M); hipFree(stage); } } tmp;
   hipError_t e = mesh_upload(d, n_tris, H, &tmp.M);
   if (e == hipSuccess) e = hipMalloc((void **)&tmp.stage, (size_t)n_tris * 144);
-  if (e != hipSuccess) { (void)hipGetLastError(); return mesh_refuse_hip(fn, e, n_tris, d->n_vertices); }
+  if (e != hipSuccess) { (void)hipGetLastError(); return refuse_hip(fn, e, "%zu triangles, %u vertices", (size_t)n_tris, d->n_vertices); }
   HIP_TRY(hipMemcpy(tmp.M.pos, pos, (size_t)d->n_vertices * 12, hipMemcpyHostToDevice));
   fspt::mesh_run(tmp.M, n_tris, tmp.M.pos, tmp.stage);
   HIP_TRY(hipGetLastError());
@@ -605,8 +616,8 @@ static int rebuild_geometry(fspt_scene *s, const float *tri, const float *norm, 
   if (hipGetDevice(&restore.prev) != hipSuccess) restore.prev = -1;
   if ((rc = begin_refit(s))) return rc;
   if (!on_device) {
-    // (the upload drops the pose's / the skin's claim on the staging array at once: a rebuild that fails behind it must
-    // not leave fspt_scene_read_pose / fspt_scene_read_skin handing out the uploaded arrays)
+    // (the upload takes the staging array from its owner at once: a rebuild that fails behind it must not leave
+    // fspt_scene_read_pose / _skin / _mesh handing out the uploaded arrays)
     if ((rc = stage_upload(s, tri, norm))) return rc;
   } else {
     int finite = 1;

@@ -182,11 +182,15 @@ def test_static_triangles_keep_their_rest_bytes():
 
 
 # ---- a scene ----------------------------------------------------------------------------------------------------------
-def cloth_scene():
-    """a smooth 9 x 9 cloth, a flat fan, and - static, they have no vt - a floor and a small emitter"""
-    pos, faces, vts, fvt = R.grid_mesh(9, 9, seed=7)
+def cloth_scene(grid=9, fan=9, shuffle=False):
+    """a smooth grid x grid cloth, a flat fan, and - static, they have no vt - a floor and a small emitter; shuffle: the
+    cloth's faces in a hashed order"""
+    pos, faces, vts, fvt = R.grid_mesh(grid, grid, seed=7)
+    if shuffle:
+        perm = np.argsort(hashed_u64(len(faces), 11), kind="stable")
+        faces, fvt = np.asarray(faces)[perm], np.asarray(fvt)[perm]
     cloth = R.obj_text((pos - np.float32([0.5, 0.5, 0.0])) * np.float32(1.4), faces, vts, fvt)
-    fpos, ffaces, fvts, ffvt = R.fan_mesh(9)
+    fpos, ffaces, fvts, ffvt = R.fan_mesh(fan)
     fan = R.obj_text(fpos * np.float32(0.4) + np.float32([0.9, 0.2, 0.3]), ffaces, fvts, ffvt)
     quad = "v 0.5 0.0 0.5\nv 0.5 0.0 -0.5\nv -0.5 0.0 -0.5\nv -0.5 0.0 0.5\nf 1 3 2\nf 3 1 4\n"
     lamp = "mtllib lamp.mtl\nusemtl lamp\n" + quad
@@ -361,6 +365,55 @@ def test_mesh_pose_and_skin_alternate(cloth):
     with pytest.raises(FsptError):
         A.read_mesh()
     A.close(); B.close()
+
+
+def test_rebuild_permutes_all_three_deformers():
+    """T = 257: odd, one past a 256-thread block of k_rebuild_permute at one word per triangle, no multiple of the derive
+    kernels' 21 triangles per wave.  Pose, skin (two morph targets with morph_norm) and mesh are set at once; one rebuild
+    permutes every array that follows the triangles, and each deformer then works with nothing from the caller."""
+    import pose_ref as PR
+    import skin_ref as SR
+    arrays = cloth_scene(grid=11, fan=53, shuffle=True)
+    T, m = arrays.n_tris, arrays.meta
+    assert T == 257 and m["tri_static"].sum() == 4 and m["tri_smooth"].sum() == 200
+    rest_t, rest_n = arrays.tri.reshape(-1, 9), arrays.norm.reshape(-1, 27)
+    part = (hashed_u64(T, 3) % np.uint64(3)).astype(np.uint32)
+    xp = np.float32([[1, 0, 0, 0.05, 0, 1, 0, 0, 0, 0, 1, 0], [0.9, 0, 0, 0, 0, 1.1, 0, 0, 0, 0, 1, 0.02], [0, -1, 0, 0, 1.2, 0.3, 0, 0.1, 0, 0, 1, 0]])
+    joints = (hashed_u64(T * 12, 4) % np.uint64(5)).astype(np.uint16).reshape(T, 3, 4)
+    raw = (hashed_u64(T * 12, 5) % np.uint64(1000)).astype(np.float64).reshape(-1, 4) + 1.0
+    weights = (raw / raw.sum(1, keepdims=True)).astype(np.float32).reshape(T, 3, 4)
+    morph = (np.float32(0.03) * R.hashed(2 * T * 9, 21)).reshape(2, T, 9)
+    mnorm = (np.float32(0.1) * R.hashed(2 * T * 27, 22)).reshape(2, T, 27)
+    xs = np.float32([[1, 0, 0, 0.01 * k, 0.1 * k, 1, 0, 0.03, 0, 0, 1 - 0.05 * k, 0] for k in range(5)])
+    mw = np.float32([0.6, -0.25])
+    pos = deformed(arrays, 0)
+    A = Scene(arrays)
+    A.set_mesh(); A.set_pose(part, n_parts=3); A.set_skin(joints, weights, morph=morph, morph_norm=mnorm)
+    held = A.last_skin["bytes"], A.last_mesh["bytes"]
+    assert held[0] == T * 216 + 2 * T * 144 + 5 * 48 + 2 * 4 and held[1] > 0
+    order = A.rebuild_geometry(rest_t, rest_n).astype(np.int64)
+    assert np.array_equal(np.sort(order), np.arange(T)) and not np.array_equal(order, np.arange(T))
+    reads = (("pose", A.read_pose), ("skin", A.read_skin), ("mesh", A.read_mesh))
+    for _, read in reads:
+        with pytest.raises(FsptError) as ei:
+            read()  # the staging array is the rebuild's
+        assert ei.value.code == -6
+    steps = [("pose", lambda: A.update_transforms(xp), lambda: PR.pose(part[order], rest_t[order], rest_n[order], xp)),
+             ("skin", lambda: A.update_skin(xs, mw), lambda: SR.skin(joints[order], weights[order], rest_t[order], rest_n[order], xs, morph[:, order], mnorm[:, order], mw)),
+             ("mesh", lambda: A.update_vertices(pos), lambda: reference(arrays, pos, order))]
+    for name, run, ref in steps:
+        want = ref()
+        assert np.isfinite(want[0]).all() and np.isfinite(want[1]).all(), name  # (else the refit would refuse the frame)
+        run()
+        for other, read in reads:
+            if other != name:
+                with pytest.raises(FsptError) as ei:
+                    read()
+                assert ei.value.code == -6 and f"fspt_scene_read_{other}" in str(ei.value)
+        got = dict(reads)[name]()
+        assert np.array_equal(bits(got[0]), bits(want[0])) and np.array_equal(bits(got[1]), bits(want[1])), name
+    assert (A.last_skin["bytes"], A.last_mesh["bytes"]) == held
+    A.close()
 
 
 def test_recorded_ticks_run_before_the_update(cloth):

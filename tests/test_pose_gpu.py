@@ -345,7 +345,30 @@ def test_errors_leave_the_scene_unchanged(scenes):
         sc.update_transforms(good.reshape(-1)[:-1])
     with pytest.raises(ValueError):
         sc.set_pose(part[:-1])
+    # read_pose hands out only a frame the scene took: a refusal on the host leaves the accepted frame readable, one by
+    # the refit's check (the kernel has overwritten the staging array by then) leaves none
+    rest_t, rest_n = arrays.tri.reshape(-1, 9), arrays.norm.reshape(-1, 27)
+    first = transform_set("shear", n_parts)
+    sc.update_transforms(first)
+    want = PR.pose(part, rest_t, rest_n, first)
+    f1, h1 = again(pt), sc.intersect(rays)
+    for what, xf in (("n_parts", good[:-1]), ("nan", nan), ("singular", singular)):
+        with pytest.raises(FsptError) as ei:
+            sc.update_transforms(xf)
+        assert ei.value.code == -1, what
+        got = sc.read_pose()
+        assert np.array_equal(bits(got[0]), bits(want[0])) and np.array_equal(bits(got[1]), bits(want[1])), what
+    with pytest.raises(FsptError) as ei:
+        sc.update_transforms(overflow)
+    assert ei.value.code == -1
+    with pytest.raises(FsptError) as ei:
+        sc.read_pose()
+    assert ei.value.code == -6 and "fspt_scene_read_pose" in str(ei.value)
+    assert same_hits(sc.intersect(rays), h1) and np.array_equal(again(pt), f1)  # the scene keeps the frame it took
     sc.update_transforms(good)  # and the pose still works
+    want = PR.pose(part, rest_t, rest_n, good)
+    got = sc.read_pose()
+    assert np.array_equal(bits(got[0]), bits(want[0])) and np.array_equal(bits(got[1]), bits(want[1]))
     assert not np.array_equal(again(pt), f0)
     pt.close(); sc.close()
 

@@ -290,6 +290,12 @@ def test_device_form_equals_the_host_form(scenes):
         B.update_skin(d_xf * float("nan"), d_mw)  # no host check: the refit's finiteness check refuses the result
     assert ei.value.code == -1
     assert np.array_equal(frame(B), f0)
+    with pytest.raises(FsptError) as ei:
+        B.read_skin()  # the refused frame is in the staging array: nothing is handed out
+    assert ei.value.code == -6 and "fspt_scene_read_skin" in str(ei.value)
+    B.update_skin(d_xf, d_mw)
+    for a, b in zip(reference(arrays, skin, xf, mw), B.read_skin()):
+        assert np.array_equal(bits(a), bits(b))
     # no morph weights for a skin without targets
     B.set_skin(skin[0], skin[1])
     B.update_skin(d_xf)
@@ -488,7 +494,30 @@ def test_errors_leave_the_scene_unchanged(scenes):
         sc.update_skin(good.reshape(-1)[:-1], mw)
     with pytest.raises(ValueError):
         sc.set_skin(j[:-1], w)
+    # read_skin hands out only a frame the scene took: a refusal on the host leaves the accepted frame readable, one by
+    # the refit's check (the kernel has overwritten the staging array by then) leaves none
+    skin = (j, one_hot, morph, None)
+    first = frame_set("shear_mirror", 5)
+    sc.update_skin(first, mw)
+    want = reference(arrays, skin, first, mw)
+    f1, h1 = again(pt), sc.intersect(rays)
+    for what, xf, m in (("n_joints", good[:-1], mw), ("nan", nan, mw), ("nan_weight", good, np.float32([np.nan]))):
+        with pytest.raises(FsptError) as ei:
+            sc.update_skin(xf, m)
+        assert ei.value.code == -1, what
+        got = sc.read_skin()
+        assert np.array_equal(bits(got[0]), bits(want[0])) and np.array_equal(bits(got[1]), bits(want[1])), what
+    with pytest.raises(FsptError) as ei:
+        sc.update_skin(collapse, mw)
+    assert ei.value.code == -1
+    with pytest.raises(FsptError) as ei:
+        sc.read_skin()
+    assert ei.value.code == -6 and "fspt_scene_read_skin" in str(ei.value)
+    assert same_hits(sc.intersect(rays), h1) and np.array_equal(again(pt), f1)  # the scene keeps the frame it took
     sc.update_skin(good, mw)  # and the skin still works
+    want = reference(arrays, skin, good, mw)
+    got = sc.read_skin()
+    assert np.array_equal(bits(got[0]), bits(want[0])) and np.array_equal(bits(got[1]), bits(want[1]))
     assert not np.array_equal(again(pt), f0)
     sc.set_skin(None)
     assert sc.last_skin["bytes"] == 0

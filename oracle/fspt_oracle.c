@@ -620,7 +620,7 @@ static float emission_weight(const oracle_scene *s, const oracle_lights *L, floa
 typedef struct {
   int hasShadow, strategy; /* strategy 0: q = 0, 1: environment, 2: emitter */
   vec3 dir, pend; float wx, lt, lq, q;
-  float u[4], v; light_sample_t ls; float cn, pdfB, wL;
+  float u[4], v; light_sample_t ls; float cn, pdfB, wL, sc;
 } nee_t;
 static void vertex_nee(const oracle_scene *s, const oracle_lights *L, const bounce_t *b, vec3 thr, int i, int iters,
                        uint32_t numBounces, rng_t *g, nee_t *n) {
@@ -662,6 +662,7 @@ static void vertex_nee(const oracle_scene *s, const oracle_lights *L, const boun
     float den = om_fma(n->pdfB, n->pdfB, a2);
     n->wL = a2 / den;
     float sc = ((n->cn * a2) / den) / qp; /* cos w_L / (q pdf_L) */
+    n->sc = sc;
     n->hasShadow = n->cn > 0.0f && n->ls.pdf > 0.0f && sc < INFINITY;
     n->dir = w;
     n->pend = v3(((thr.x * f.x) * n->ls.le.x) * sc, ((thr.y * f.y) * n->ls.le.y) * sc, ((thr.z * f.z) * n->ls.le.z) * sc);
@@ -670,6 +671,7 @@ static void vertex_nee(const oracle_scene *s, const oracle_lights *L, const boun
   } else {
     n->strategy = 1;
     float sc = n->wx / (1.0f - q);
+    n->sc = sc;
     n->pend = v_scale(n->pend, sc);
     n->wx = 1.0f;
   }
@@ -879,12 +881,19 @@ static void trace_tick(const oracle_scene *s, uint32_t W, uint32_t H, const floa
     counters->env_lookups += total.env_lookups;
   }
 }
+/* L: emitter NEE, NULL: off */
+void oracle_trace_lights(const oracle_scene *s, uint32_t W, uint32_t H, const float *pos, const float *dir,
+                         uint32_t tick, float randBase, float envTheta, uint32_t numBounces, float *accum,
+                         oracle_counters *counters, oracle_first_hit *first_hits, uint32_t shard,
+                         uint32_t n_shards, uint32_t tile, const oracle_lights *L) {
+  trace_tick(s, W, H, pos, dir, tick, randBase, envTheta, numBounces, accum, counters, first_hits, shard, n_shards, tile, L);
+}
 void oracle_trace(const oracle_scene *s, uint32_t W, uint32_t H, const float *pos, const float *dir,
                   uint32_t tick, float randBase, float envTheta, uint32_t numBounces, float *accum,
                   oracle_counters *counters, oracle_first_hit *first_hits, uint32_t shard,
                   uint32_t n_shards, uint32_t tile) {
-  trace_tick(s, W, H, pos, dir, tick, randBase, envTheta, numBounces, accum, counters, first_hits, shard, n_shards, tile,
-             NULL);
+  oracle_trace_lights(s, W, H, pos, dir, tick, randBase, envTheta, numBounces, accum, counters, first_hits, shard, n_shards,
+                      tile, NULL);
 }
 
 /* bvh_test.fs main (224-232), the reference's `mode=test` replacement of tracer.fs (main.js:879-883): the
@@ -1244,8 +1253,9 @@ void oracle_light_sample(const oracle_scene *s, const oracle_lights *L, const fl
  *   0 strategy (0 q = 0, 1 environment, 2 emitter)  1 entry (-1)  2 pdf_L  3 pdf_B  4 w_L  5-7 pend  8 lt  9 lq  10 q
  *   11 hasShadow  12-14 shadow direction  15 wx  16 specular  17 metallic  18 rough (squared)  19 rnd() calls
  *   20-22 ro  23-25 macroNormal  26-28 incident  29-31 texDiffuse  32-34 light point  35-37 Le  38 dist  39 n . w
- *   40 bsdfPdf  41 light triangle (-1)  42-45 u0..u3  46 inside  47 dielectric */
-#define ORACLE_VERTEX_FLOATS 48
+ *   40 bsdfPdf  41 light triangle (-1)  42-45 u0..u3  46 inside  47 dielectric
+ *   48 sc: cos w_L / (q pdf_L) of an emitter sample, weights.x / (1 - q) of the environment strategy (0 at q = 0) */
+#define ORACLE_VERTEX_FLOATS 49
 void oracle_light_vertex_probe(const oracle_scene *s, const oracle_lights *L, const float *rays, const float *t_in,
                                const int32_t *index_in, const float *rec, uint32_t rec_stride, float randBase,
                                float envTheta, uint32_t bounce, uint32_t numBounces, uint32_t n, float *out) {
@@ -1275,7 +1285,7 @@ void oracle_light_vertex_probe(const oracle_scene *s, const oracle_lights *L, co
     o[35] = nn.ls.le.x; o[36] = nn.ls.le.y; o[37] = nn.ls.le.z; o[38] = nn.ls.dist; o[39] = nn.cn;
     o[40] = b.bsdfPdf; o[41] = (float)nn.ls.tri;
     for (int k = 0; k < 4; ++k) o[42 + k] = nn.u[k];
-    o[46] = (float)b.inside; o[47] = b.dielectric;
+    o[46] = (float)b.inside; o[47] = b.dielectric; o[48] = nn.sc;
   }
 }
 

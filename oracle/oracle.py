@@ -101,16 +101,19 @@ def camera_probe(W, H, P, I, fov_scale, lens, rec):
 
 
 def trace(arrays, W, H, pos, d, tick, rand_base, env_theta, num_bounces, accum, counters=None, first_hits=False,
-          shard=0, n_shards=1, tile=32):
+          shard=0, n_shards=1, tile=32, lights=None):
+    """lights = (table, q): next-event estimation of emissive triangles (olights); None: off."""
     s = oscene(arrays)
+    L, keep = olights(arrays, lights)
     pos = np.ascontiguousarray(pos, np.float32); d = np.ascontiguousarray(d, np.float32)
     assert accum.dtype == np.float32 and accum.flags.c_contiguous
     fh = np.zeros(W * H, FIRST_HIT_DTYPE) if first_hits else None
-    lib().oracle_trace(C.byref(s), C.c_uint32(W), C.c_uint32(H), _fp(pos), _fp(d), C.c_uint32(tick),
-                       C.c_float(rand_base), C.c_float(env_theta), C.c_uint32(num_bounces), _fp(accum),
-                       C.byref(counters) if counters is not None else None,
-                       fh.ctypes.data_as(C.c_void_p) if fh is not None else None,
-                       C.c_uint32(shard), C.c_uint32(n_shards), C.c_uint32(tile))
+    lib().oracle_trace_lights(C.byref(s), C.c_uint32(W), C.c_uint32(H), _fp(pos), _fp(d), C.c_uint32(tick),
+                              C.c_float(rand_base), C.c_float(env_theta), C.c_uint32(num_bounces), _fp(accum),
+                              C.byref(counters) if counters is not None else None,
+                              fh.ctypes.data_as(C.c_void_p) if fh is not None else None,
+                              C.c_uint32(shard), C.c_uint32(n_shards), C.c_uint32(tile), _lp(L))
+    del keep
     return fh
 
 
@@ -207,7 +210,7 @@ VERTEX_FIELDS = {"strategy": 0, "entry": 1, "pdf_L": 2, "pdf_B": 3, "w_L": 4, "p
                  "has_shadow": 11, "dir": slice(12, 15), "wx": 15, "specular": 16, "metallic": 17, "rough": 18, "used": 19,
                  "ro": slice(20, 23), "normal": slice(23, 26), "incident": slice(26, 29), "diffuse": slice(29, 32),
                  "x": slice(32, 35), "le": slice(35, 38), "dist": 38, "cn": 39, "bsdf_pdf": 40, "tri": 41,
-                 "u": slice(42, 46), "inside": 46, "dielectric": 47}
+                 "u": slice(42, 46), "inside": 46, "dielectric": 47, "sc": 48}
 
 
 def light_vertex_probe(arrays, lights, rays, t, index, rec=None, rand_base=1.0, env_theta=0.0, bounce=0, num_bounces=4):
@@ -221,7 +224,7 @@ def light_vertex_probe(arrays, lights, rays, t, index, rec=None, rand_base=1.0, 
     t = np.ascontiguousarray(t, np.float32).reshape(n); index = np.ascontiguousarray(index, np.int32).reshape(n)
     if rec is not None:
         rec = np.ascontiguousarray(rec, np.float32).reshape(n, -1)
-    out = np.zeros((n, 48), np.float32)
+    out = np.zeros((n, 49), np.float32)
     lib().oracle_light_vertex_probe(C.byref(s), _lp(L), _fp(rays), _fp(t), index.ctypes.data_as(C.POINTER(C.c_int32)),
                                     _fp(rec) if rec is not None else None, C.c_uint32(rec.shape[1] if rec is not None else 0),
                                     C.c_float(rand_base), C.c_float(env_theta), C.c_uint32(bounce), C.c_uint32(num_bounces),

@@ -118,6 +118,11 @@ class ExrParams(C.Structure):
     _fields_ = [("compression", C.c_uint32), ("pixel_type", C.c_uint32), ("layers", C.c_uint32), ("chunk_bytes", C.c_uint32)]
 
 
+class ExrMattes(C.Structure):
+    """fspt_exr_mattes, by kind (0 object, 1 material): the ranks (W*H*12 floats), the manifest's bytes and their length"""
+    _fields_ = [("ranks", C.c_void_p * 2), ("manifest", C.c_char_p * 2), ("manifest_len", C.c_size_t * 2)]
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("target_rel_mse", C.c_double), ("max_ticks", C.c_uint32), ("min_ticks", C.c_uint32), ("round_ticks", C.c_uint32)]
 
@@ -386,6 +391,15 @@ SIGNATURES = {
     "fspt_exr_set_form": (C.c_int, [C.c_int]),
     "fspt_exr_last_ms": (C.c_int, [_F, C.POINTER(C.c_uint64)]),
     "fspt_draw_exr": (C.c_int, [_VP, C.c_int, C.POINTER(ExrParams), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fspt_matte_hash": (C.c_uint32, [C.c_char_p, C.c_size_t]),
+    "fspt_scene_set_matte_ids": (C.c_int, [_VP, C.c_int, _U32]),
+    "fspt_scene_set_matte_manifest": (C.c_int, [_VP, C.c_int, C.c_char_p, C.c_size_t]),
+    "fspt_mattes": (C.c_int, [_VP, C.POINTER(CameraParams), C.c_uint32, C.c_uint64]),
+    "fspt_read_mattes": (C.c_int, [_VP, C.c_int, _F]),
+    "fspt_mattes_lost": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_uint64)]),
+    "fspt_exr_bound_mattes": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(ExrParams), C.POINTER(ExrMattes), C.POINTER(C.c_size_t)]),
+    "fspt_exr_encode_mattes": (C.c_int, [C.c_int, _F, _F, C.POINTER(ExrMattes), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(ExrParams), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fspt_exr_encode_mattes_device": (C.c_int, [C.c_int, _VP, _VP, C.POINTER(ExrMattes), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(ExrParams), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
     "fspt_multi_last_stage_ms": (C.c_int, [_VP, _F, C.c_uint32]),
     "fspt_device_memory": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fspt_last_error": (C.c_char_p, []),

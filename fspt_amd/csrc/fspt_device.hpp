@@ -338,6 +338,16 @@ struct FeatureP {
   float4 *feat;   // 2 x float4 per pixel: (albedo.rgb, depth), (normal.xyz, coverage)
 };
 struct FeatureModelP { FeatureP f; CameraModelP cm; }; // k_features under a camera model (the pinhole camera's block is FeatureP)
+// ID mattes (fspt_mattes): k_mattes traces k_features' rays; f.feat is not used.  Table a (and b, when the launch
+// carries two kinds): one id per triangle, 3 x float4 per pixel of ranks, a 64-bit counter of lost samples.  Named members,
+// not arrays: an array in the arguments indexed by a variable would be copied to scratch.
+struct MatteP {
+  FeatureP f;
+  const uint32_t *ids_a, *ids_b;
+  float4 *out_a, *out_b;
+  unsigned long long *lost_a, *lost_b;
+};
+struct MatteModelP { MatteP m; CameraModelP cm; };
 struct AtrousP {
   const float4 *src; // u^k, or (demod) the accumulator
   float4 *dst;
@@ -490,6 +500,7 @@ hipError_t launch_adaptive_error(const AdaptiveP &p, hipStream_t stream);
 hipError_t launch_adaptive_select(const AdaptiveP &p, hipStream_t stream);
 // the two passes of the image chain that trace rays (fspt_post.cpp launches them)
 hipError_t launch_features(const FeatureP &p, const CameraModelP &cm, hipStream_t stream); // (the guides follow the camera model)
+hipError_t launch_mattes(const MatteP &p, const CameraModelP &cm, hipStream_t stream);    // kinds: table a alone (ids_b NULL) or both; zeroes the lost counters first
 hipError_t launch_temporal_gbuffer(const TemporalGP &p, hipStream_t stream);
 
 // ---------------------------------------------------------------------------

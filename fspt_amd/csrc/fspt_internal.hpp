@@ -189,6 +189,10 @@ struct fspt_scene {
     float sky_ms = 0.0f, bins_ms = 0.0f, tile_ms = 0.0f; // the generator | radiance, table, tree and the n_bins read-back | the tiling
     uint32_t launches = 0, readbacks = 0, n_bins = 0;
   } sky;
+  // fspt_scene_set_matte_ids / _manifest: per kind (FSPT_MATTE_*) one id per triangle (current leaf order; a
+  // rebuild permutes it), on the device, NULL: the kind has no ids; the manifest's bytes stay on the host, for a file header.
+  uint32_t *matte_ids[2] = {nullptr, nullptr};
+  std::string matte_manifest[2];
 };
 // Material texture sets: what fspt_scene_create and fspt_scene_update_materials derive from matTex's layer ids and
 // the per-layer "every texel equal" flags - the sets in first-appearance order, each triangle's set, a set's form under the
@@ -432,28 +436,32 @@ hipError_t deflate_launch(const DeflateP &p, uint32_t n_chunks, hipStream_t st);
 // ExrEnc: the device memory of one encoder - the header of its plan, the predicted stream and the raw bytes of every block,
 // the deflate's slots and records, a record per block, one output buffer - owned by a target (fspt_draw_exr) or by one
 // stand-alone call.
-static const uint32_t EXR_MAX_CHANNELS = 11u, EXR_HEADER_MAX = 512u;
-struct ExrChannel { uint32_t src, bytes, off; }; // src: 0..3 = the rgba float, 4..11 = the feature float src - 4; off: in units of w bytes within a scanline
+// The Cryptomatte layers add twelve FLOAT channels per kind and header attributes that carry the manifests, so
+// the header is sized per plan; a plan with a matte layer runs the second instantiation of k_exr_rows, every other plan today's.
+static const uint32_t EXR_MAX_CHANNELS = 35u, EXR_MANIFEST_MAX = 1u << 20;
+struct ExrChannel { uint32_t src, bytes, off; }; // src: 0..3 = the rgba float, 4..11 = the feature float src - 4, 12..23 / 24..35 = float src - 12 / - 24 of the object / material ranks; off: in units of w bytes within a scanline
+struct ExrMattes { const float4 *ranks[2]; const char *manifest[2]; size_t manifest_len[2]; }; // by FSPT_MATTE_*; ranks in device memory (the plan reads the manifests alone)
 struct ExrPlan {
   uint32_t w, h, compression, pixel_type, layers, cb, form;
   uint32_t n_ch, px_bytes, lpb, n_blocks, cps, n_chunks, hdr_len;
   ExrChannel ch[EXR_MAX_CHANNELS]; // in file order
   size_t line_bytes, block_bytes, data_bytes; // a scanline | a full block | every block, uncompressed
   size_t slot_bytes, bound;
-  uint8_t hdr[EXR_HEADER_MAX];
+  std::vector<uint8_t> hdr; // hdr_len bytes
 };
 struct ExrEnc {
   ExrPlan pl{};
   EncCommon c;
-  uint8_t *cfg = nullptr;                    // the header
+  uint8_t *cfg = nullptr;                    // the header, then (16-byte aligned) the channels
   uint8_t *stream = nullptr, *raw = nullptr; // the deflate's input | the same blocks as they are (form 1)
   uint8_t *scratch = nullptr;
   uint32_t *meta = nullptr, *chunk_off = nullptr; // per chunk: 4 words | where its bytes start in its block's data
   uint64_t *blk = nullptr;                        // per block: the block's offset in the file, (size << 32 | Adler-32); blk[2 n_blocks] = the file's length
 };
-int exr_plan(const fspt_exr_params *prm, uint32_t w, uint32_t h, bool for_device, const char *fn, ExrPlan &pl); // validates: FSPT_E_INVALID, no device touched
+// validates: FSPT_E_INVALID, no device touched.  crypto: the entry accepts the Cryptomatte layer bits; m (or NULL: none): their manifests
+int exr_plan(const fspt_exr_params *prm, uint32_t w, uint32_t h, bool for_device, const char *fn, ExrPlan &pl, bool crypto = false, const ExrMattes *m = nullptr);
 hipError_t exr_ensure(ExrEnc &e, const ExrPlan &pl, size_t out_bytes);                 // nothing of `e` may be in use
-hipError_t exr_launch(ExrEnc &e, const float4 *rgba, const float4 *feat, int bottom_up, hipStream_t st); // no host read, no synchronisation
+hipError_t exr_launch(ExrEnc &e, const float4 *rgba, const float4 *feat, int bottom_up, hipStream_t st, const ExrMattes *m = nullptr); // no host read, no synchronisation; m: the ranks of the plan's matte layers
 int exr_collect(ExrEnc &e, hipStream_t st, uint8_t *out, size_t cap, size_t *bytes_out, const char *fn);
 // fspt_pose.hip: the three deformers that fill s->rf.stage (tri 9 T | norm 27 T) - part transforms, skinning
 // (8.16), the vertex-position update (8.24).  Set, update, read, release and rebuild are stated once for all of them
@@ -737,6 +745,11 @@ struct fspt_target {
   uint32_t *jp_count[2] = {nullptr, nullptr}; // pinned host memory: a slot's byte count, current behind pr_copied[slot]
   int pr_kind[2] = {0, 0};                    // 0: an RGBA8 frame, 1: a JPEG file
   hipStream_t jp_copy = nullptr;              // a present file's bytes come to the host here: the copy waits for no stream that holds the next frame
+  // ID mattes (fspt_mattes): allocated on first use.  mt[k]: 3 x float4 per pixel of kind k; mt_lost: the
+  // two kinds' lost-sample counters; mt_valid[k]: the last pass computed kind k.  (Last: the fields above keep their places.)
+  float4 *mt[2] = {nullptr, nullptr};
+  unsigned long long *mt_lost = nullptr;
+  bool mt_valid[2] = {false, false};
 };
 
 static const uint32_t WORK_RING = 4096;

@@ -1182,6 +1182,113 @@ static napi_value DrawExr(napi_env env, napi_callback_info info) {
   const int rc = fspt_draw_exr((fspt_target *)h, (int)src, &p, (uint8_t *)dst, nd, &bytes);
   return jpeg_answer(env, rc, nd, bytes);
 }
+/* ID mattes (include/fspt.h fspt_matte_hash .. fspt_exr_encode_mattes).  A manifest is a JS string or null; the
+ * copies made here are freed before the call returns (the library keeps its own). */
+static int matte_text(napi_env env, napi_value v, char **text, size_t *len) { /* string | null | undefined -> malloc'd UTF-8 or NULL */
+  napi_valuetype vt;
+  *text = NULL; *len = 0;
+  if (napi_typeof(env, v, &vt) != napi_ok) return -1;
+  if (vt == napi_null || vt == napi_undefined) return 0;
+  if (napi_get_value_string_utf8(env, v, NULL, 0, len) != napi_ok) { napi_throw_type_error(env, NULL, "fspt_napi: expected a string or null"); return -1; }
+  *text = (char *)malloc(*len + 1);
+  if (!*text) { napi_throw_error(env, NULL, "fspt_napi: out of memory"); return -1; }
+  napi_get_value_string_utf8(env, v, *text, *len + 1, len);
+  return 0;
+}
+static int matte_kind(napi_env env, napi_value v, int *kind) {
+  double k;
+  if (get_f64(env, v, &k)) return -1;
+  if (k != 0.0 && k != 1.0) { napi_throw_range_error(env, NULL, "fspt_napi: kind must be 0 (object) or 1 (material)"); return -1; }
+  *kind = (int)k;
+  return 0;
+}
+static napi_value MatteHash(napi_env env, napi_callback_info info) {
+  /* matteHash(name) -> the 32-bit id */
+  napi_value a[1], r; char *text; size_t len;
+  if (get_args(env, info, 1, a) || matte_text(env, a[0], &text, &len)) return NULL;
+  const uint32_t h = fspt_matte_hash(text, len);
+  free(text);
+  NAPI_OK(napi_create_uint32(env, h, &r));
+  return r;
+}
+static napi_value SceneSetMatte(napi_env env, napi_callback_info info) {
+  /* sceneSetMatte(scene, nTris, kind, ids Uint32Array | null (drops the kind), manifest string | null): both setters; the guard of sceneUpdateGeometry */
+  napi_value a[5]; void *h, *ids = NULL; size_t ni = 0, len = 0; uint32_t n = 0; int kind = 0; char *text = NULL;
+  if (get_args(env, info, 5, a) || unwrap_k(env, a[0], H_SCENE, &h)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[1], &n));
+  if (matte_kind(env, a[2], &kind) || typed(env, a[3], napi_uint32_array, 1, &ids, &ni)) return NULL;
+  if (ids && ni != (size_t)n) { napi_throw_range_error(env, NULL, "fspt_napi: setMatte needs 1 id per triangle of the scene"); return NULL; }
+  if (matte_text(env, a[4], &text, &len)) return NULL;
+  int rc = fspt_scene_set_matte_ids((fspt_scene *)h, kind, (const uint32_t *)ids);
+  if (rc == FSPT_OK) rc = fspt_scene_set_matte_manifest((fspt_scene *)h, kind, ids ? text : NULL, ids ? len : 0);
+  free(text);
+  FSPT_OK_OR_THROW(rc);
+  return undefined(env);
+}
+static napi_value Mattes(napi_env env, napi_callback_info info) {
+  /* mattes(target, params (as render), samples, seed) */
+  napi_value a[4]; void *h; uint32_t n; uint64_t seed64 = 0;
+  if (get_args(env, info, 4, a)) return NULL;
+  fspt_camera_params cp;
+  if (parse_camera_params(env, a[1], &cp)) return NULL;
+  if (unwrap_k(env, a[0], H_TARGET, &h)) return NULL;
+  NAPI_OK(napi_get_value_uint32(env, a[2], &n));
+  if (parse_seed(env, a[3], &seed64)) return NULL;
+  FSPT_OK_OR_THROW(fspt_mattes((fspt_target *)h, &cp, n, seed64));
+  return undefined(env);
+}
+static napi_value ReadMattes(napi_env env, napi_callback_info info) {
+  /* readMattes(target, kind, Float32Array(W*H*12)) -> the array */
+  napi_value a[3]; void *h, *p; size_t n; int kind; uint32_t W = 0, H = 0;
+  if (get_args(env, info, 3, a) || unwrap_k(env, a[0], H_TARGET, &h) || matte_kind(env, a[1], &kind) || typed(env, a[2], napi_float32_array, 0, &p, &n)) return NULL;
+  FSPT_OK_OR_THROW(fspt_target_size((fspt_target *)h, &W, &H));
+  if (n != (size_t)W * H * 12) { napi_throw_range_error(env, NULL, "fspt_napi: readMattes needs W*H*12 floats"); return NULL; }
+  FSPT_OK_OR_THROW(fspt_read_mattes((fspt_target *)h, kind, (float *)p));
+  return a[2];
+}
+static napi_value MattesLost(napi_env env, napi_callback_info info) {
+  /* mattesLost(target, kind) -> samples the last pass dropped */
+  napi_value a[2], r; void *h; int kind; uint64_t lost = 0;
+  if (get_args(env, info, 2, a) || unwrap_k(env, a[0], H_TARGET, &h) || matte_kind(env, a[1], &kind)) return NULL;
+  FSPT_OK_OR_THROW(fspt_mattes_lost((fspt_target *)h, kind, &lost));
+  NAPI_OK(napi_create_double(env, (double)lost, &r));
+  return r;
+}
+static napi_value ExrBoundMattes(napi_env env, napi_callback_info info) {
+  /* exrBoundMattes(width, height, compression, pixelType, layers, chunkBytes, objectManifest string | null, materialManifest string | null) */
+  napi_value a[8], r; double w, h; fspt_exr_params p; size_t n = 0; fspt_exr_mattes m; char *t0 = NULL, *t1 = NULL;
+  memset(&m, 0, sizeof m);
+  if (get_args(env, info, 8, a) || get_f64(env, a[0], &w) || get_f64(env, a[1], &h) || exr_args(env, a + 2, &p)) return NULL;
+  if (matte_text(env, a[6], &t0, &m.manifest_len[0])) return NULL;
+  if (matte_text(env, a[7], &t1, &m.manifest_len[1])) { free(t0); return NULL; }
+  m.manifest[0] = t0; m.manifest[1] = t1;
+  const int rc = fspt_exr_bound_mattes(w >= 0.0 && w <= 4294967295.0 ? (uint32_t)w : 0u, h >= 0.0 && h <= 4294967295.0 ? (uint32_t)h : 0u, &p, &m, &n);
+  free(t0); free(t1);
+  FSPT_OK_OR_THROW(rc);
+  NAPI_OK(napi_create_double(env, (double)n, &r));
+  return r;
+}
+static napi_value ExrEncodeMattes(napi_env env, napi_callback_info info) {
+  /* exrEncodeMattes(device, Float32Array(w*h*4), Float32Array(w*h*8) | null, object ranks Float32Array(w*h*12) | null, material ranks | null,
+   *                 objectManifest string | null, materialManifest string | null, width, height, bottomUp, compression, pixelType, layers, chunkBytes, Uint8Array out) */
+  napi_value a[15]; void *src, *feat, *r0, *r1, *dst; size_t ns, nf, n0, n1, nd, bytes = 0; double dev, w, h; bool up; fspt_exr_params p; fspt_exr_mattes m; char *t0 = NULL, *t1 = NULL;
+  memset(&m, 0, sizeof m);
+  if (get_args(env, info, 15, a) || get_f64(env, a[0], &dev) || typed(env, a[1], napi_float32_array, 0, &src, &ns) || typed(env, a[2], napi_float32_array, 1, &feat, &nf)) return NULL;
+  if (typed(env, a[3], napi_float32_array, 1, &r0, &n0) || typed(env, a[4], napi_float32_array, 1, &r1, &n1)) return NULL;
+  if (get_f64(env, a[7], &w) || get_f64(env, a[8], &h)) return NULL;
+  NAPI_OK(napi_get_value_bool(env, a[9], &up));
+  if (exr_args(env, a + 10, &p) || typed(env, a[14], napi_uint8_array, 0, &dst, &nd)) return NULL;
+  if (!(w >= 1.0 && w <= 65535.0 && h >= 1.0 && h <= 65535.0) || (double)ns != w * h * 4.0 || (feat && (double)nf != w * h * 8.0) || (r0 && (double)n0 != w * h * 12.0) || (r1 && (double)n1 != w * h * 12.0)) {
+    napi_throw_range_error(env, NULL, "exrEncode: need width*height*4 floats, features of width*height*8 floats or null, ranks of width*height*12 floats or null, width and height in 1..65535");
+    return NULL;
+  }
+  if (matte_text(env, a[5], &t0, &m.manifest_len[0])) return NULL;
+  if (matte_text(env, a[6], &t1, &m.manifest_len[1])) { free(t0); return NULL; }
+  m.ranks[0] = (const float *)r0; m.ranks[1] = (const float *)r1; m.manifest[0] = t0; m.manifest[1] = t1;
+  const int rc = fspt_exr_encode_mattes((int)dev, (const float *)src, (const float *)feat, &m, (uint32_t)w, (uint32_t)h, up ? 1 : 0, &p, (uint8_t *)dst, nd, &bytes);
+  free(t0); free(t1);
+  return jpeg_answer(env, rc, nd, bytes);
+}
 /* guided denoiser (include/fspt.h fspt_features / fspt_denoise / fspt_draw_denoised) */
 static napi_value Features(napi_env env, napi_callback_info info) {
   /* features(target, params (as render), samples, seed) */
@@ -1867,7 +1974,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   struct { const char *name; napi_callback fn; } fns[] = {
       {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy}, {"sceneUpdateGeometry", SceneUpdateGeometry}, {"sceneRebuildGeometry", SceneRebuildGeometry}, {"sceneSahCost", SceneSahCost}, {"sceneUpdateMaterials", SceneUpdateMaterials}, {"sceneUpdateEnvironment", SceneUpdateEnvironment}, {"sceneUpdateSky", SceneUpdateSky}, {"sceneUpdateEnvironmentAuto", SceneUpdateEnvironmentAuto}, {"skyGenerate", SkyGenerate}, {"atlasPackGpu", AtlasPackGpu}, {"sceneUpdateTextures", SceneUpdateTextures}, {"scenePatchTextures", ScenePatchTextures}, {"envBinsGpu", EnvBinsGpu}, {"sceneSetPose", SceneSetPose}, {"sceneUpdateTransforms", SceneUpdateTransforms}, {"sceneSetSkin", SceneSetSkin}, {"sceneUpdateSkin", SceneUpdateSkin}, {"sceneSetMesh", SceneSetMesh}, {"sceneUpdateVertices", SceneUpdateVertices}, {"sceneReadMesh", SceneReadMesh}, {"targetCreate", TargetCreate},
       {"targetDestroy", TargetDestroy}, {"camera", Camera}, {"trace", Trace}, {"traceTest", TraceTest}, {"render", Render}, {"clear", Clear},
-      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"jpegBound", JpegBound}, {"jpegEncode", JpegEncode}, {"drawJpeg", DrawJpeg}, {"presentJpeg", PresentJpeg}, {"pngBound", PngBound}, {"pngEncode", PngEncode}, {"pngFilteredEval", PngFilteredEval}, {"drawPng", DrawPng}, {"exrBound", ExrBound}, {"exrEncode", ExrEncode}, {"drawExr", DrawExr}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setCameraModel", SetCameraModel}, {"cameraModel", CameraModel}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"sceneSetLightBuilder", SceneSetLightBuilder}, {"sceneGetLightBuilder", SceneGetLightBuilder}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
+      {"sync", Sync}, {"readRadiance", ReadRadiance}, {"draw", Draw}, {"present", Present}, {"jpegBound", JpegBound}, {"jpegEncode", JpegEncode}, {"drawJpeg", DrawJpeg}, {"presentJpeg", PresentJpeg}, {"pngBound", PngBound}, {"pngEncode", PngEncode}, {"pngFilteredEval", PngFilteredEval}, {"drawPng", DrawPng}, {"exrBound", ExrBound}, {"exrEncode", ExrEncode}, {"drawExr", DrawExr}, {"matteHash", MatteHash}, {"sceneSetMatte", SceneSetMatte}, {"mattes", Mattes}, {"readMattes", ReadMattes}, {"mattesLost", MattesLost}, {"exrBoundMattes", ExrBoundMattes}, {"exrEncodeMattes", ExrEncodeMattes}, {"features", Features}, {"denoise", Denoise}, {"drawDenoised", DrawDenoised}, {"temporalAccumulate", TemporalAccumulate}, {"temporalReset", TemporalReset}, {"temporalDenoise", TemporalDenoise}, {"temporalDraw", TemporalDraw}, {"temporalSetMoments", TemporalSetMoments}, {"temporalSetClamp", TemporalSetClamp}, {"setAutoExposure", SetAutoExposure}, {"exposure", Exposure}, {"exposureReset", ExposureReset}, {"setBloom", SetBloom}, {"bloom", Bloom}, {"temporalDenoiseVariance", TemporalDenoiseVariance}, {"sceneMotionBegin", SceneMotionBegin}, {"sceneMotionEnd", SceneMotionEnd}, {"setShard", SetShard}, {"setViewport", SetViewport}, {"setCameraModel", SetCameraModel}, {"cameraModel", CameraModel}, {"setSampler", SetSampler}, {"setLights", SetLights}, {"sceneSetLightBuilder", SceneSetLightBuilder}, {"sceneGetLightBuilder", SceneGetLightBuilder}, {"renderAdaptive", RenderAdaptive}, {"readSampleCounts", ReadSampleCounts}, {"setPipeline", SetPipeline}, {"setPool", SetPool}, {"setTraceBudget", SetTraceBudget},
       {"setMemoryLimit", SetMemoryLimit}, {"setTextureInterleaveBudget", SetTextureInterleaveBudget}, {"pathStateBytes", PathStateBytes}, {"prepare", Prepare}, {"setTail", SetTail}, {"setDeferred", SetDeferred}, {"setStageTiming", SetStageTiming},
       {"renderAsync", RenderAsync}, {"multiCreate", MultiCreate}, {"multiDestroy", MultiDestroy}, {"multiTarget", MultiTarget},
       {"multiCamera", MultiCamera}, {"multiTrace", MultiTrace}, {"multiRender", MultiRender}, {"multiRenderAsync", MultiRenderAsync},

@@ -6,6 +6,7 @@
 //                          front of the single-tick trace from the ray buffers
 //   k_intersect            intersectScene for a list of rays (fspt_intersect)
 //   k_features<MODEL>      the denoiser's guide buffers of the first hit, under the target's camera
+//   k_mattes<MODEL, NK>    the ID mattes of the first hit: k_features' rays, a ranking table per kind in registers
 //   k_temporal_gbuffer     the G-buffer and motion pass of temporal accumulation
 //   k_adaptive_error / k_adaptive_select   adaptive sampling's per-tile error and tile list
 //   k_sampler_eval, k_math                 test hooks: the Sobol sampler and fspt-math, value by value
@@ -146,6 +147,94 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_features(const P pp) {
   const size_t i = (size_t)y * p.W + x;
   p.feat[2 * i] = make_float4(ar / fs, ag / fs, ab / fs, z / fs);
   p.feat[2 * i + 1] = make_float4(nx / fs, ny / fs, nz / fs, hits / fs);
+}
+
+// ---- ID mattes (fspt_mattes) ---------------------------------------------------------------------------
+// A pixel's ranking table of one kind: six (id, count) slots, empty = id 0, filled from slot 0 up.  Twelve named scalars
+// and no array: every step below is an unrolled compare-and-select, so the table stays in registers (an array indexed by
+// a variable, or a conditional among neighbouring members, would go through scratch - see fspt_exr.hip's exr_sel).
+struct MatteTab { uint32_t i0, i1, i2, i3, i4, i5, c0, c1, c2, c3, c4, c5; };
+
+// One sample's id (0: a miss or a triangle without a matte, skipped): the slot that holds it counts it, else the lowest
+// empty slot takes (id, 1), else the sample is lost.  Returns the samples lost: 0 or 1.
+FM_DEV uint32_t matte_count(MatteTab &t, uint32_t id) {
+  const bool live = id != 0u;
+  const bool h0 = live && t.i0 == id, h1 = live && t.i1 == id, h2 = live && t.i2 == id, h3 = live && t.i3 == id, h4 = live && t.i4 == id, h5 = live && t.i5 == id;
+  const bool take = live && !(h0 || h1 || h2 || h3 || h4 || h5);
+  const bool e0 = take && t.i0 == 0u, e1 = take && t.i0 != 0u && t.i1 == 0u, e2 = take && t.i1 != 0u && t.i2 == 0u, e3 = take && t.i2 != 0u && t.i3 == 0u,
+             e4 = take && t.i3 != 0u && t.i4 == 0u, e5 = take && t.i4 != 0u && t.i5 == 0u;
+  const uint32_t lost = (uint32_t)(take && t.i5 != 0u);
+  t.i0 = e0 ? id : t.i0; t.i1 = e1 ? id : t.i1; t.i2 = e2 ? id : t.i2; t.i3 = e3 ? id : t.i3; t.i4 = e4 ? id : t.i4; t.i5 = e5 ? id : t.i5;
+  t.c0 += (uint32_t)(h0 || e0); t.c1 += (uint32_t)(h1 || e1); t.c2 += (uint32_t)(h2 || e2); t.c3 += (uint32_t)(h3 || e3); t.c4 += (uint32_t)(h4 || e4); t.c5 += (uint32_t)(h5 || e5);
+  return lost;
+}
+
+// compare-exchange of two (key, id) pairs: the larger key first
+#define MATTE_CX(ka, ia, kb, ib) do { const bool sw_ = ka < kb; const uint32_t k0_ = sw_ ? kb : ka, k1_ = sw_ ? ka : kb, i0_ = sw_ ? ib : ia, i1_ = sw_ ? ia : ib; ka = k0_; kb = k1_; ia = i0_; ib = i1_; } while (0)
+
+// The ranks of a table - its slots by count descending, ties by slot ascending - as the pixel's three float4: a fixed
+// 12-comparator sorting network on the unique keys (count << 3) | (7 - slot), the ids carried along.
+FM_DEV void matte_store(const MatteTab &t, float fs, float4 *out) {
+  uint32_t k0 = (t.c0 << 3) | 7u, k1 = (t.c1 << 3) | 6u, k2 = (t.c2 << 3) | 5u, k3 = (t.c3 << 3) | 4u, k4 = (t.c4 << 3) | 3u, k5 = (t.c5 << 3) | 2u;
+  uint32_t i0 = t.i0, i1 = t.i1, i2 = t.i2, i3 = t.i3, i4 = t.i4, i5 = t.i5;
+  MATTE_CX(k0, i0, k5, i5); MATTE_CX(k1, i1, k3, i3); MATTE_CX(k2, i2, k4, i4);
+  MATTE_CX(k1, i1, k2, i2); MATTE_CX(k3, i3, k4, i4);
+  MATTE_CX(k0, i0, k3, i3); MATTE_CX(k2, i2, k5, i5);
+  MATTE_CX(k0, i0, k1, i1); MATTE_CX(k2, i2, k3, i3); MATTE_CX(k4, i4, k5, i5);
+  MATTE_CX(k1, i1, k2, i2); MATTE_CX(k3, i3, k4, i4);
+  out[0] = make_float4(__uint_as_float(i0), (float)(k0 >> 3) / fs, __uint_as_float(i1), (float)(k1 >> 3) / fs);
+  out[1] = make_float4(__uint_as_float(i2), (float)(k2 >> 3) / fs, __uint_as_float(i3), (float)(k3 >> 3) / fs);
+  out[2] = make_float4(__uint_as_float(i4), (float)(k4 >> 3) / fs, __uint_as_float(i5), (float)(k5 >> 3) / fs);
+}
+
+// a wave's lost samples into the kind's counter: one atomic per wave that lost any
+FM_DEV void matte_lost(uint32_t lost, unsigned long long *counter) {
+  for (int off = WAVE / 2; off > 0; off >>= 1) lost += __shfl_down(lost, off, WAVE);
+  if (((threadIdx.y * blockDim.x + threadIdx.x) & (WAVE - 1)) == 0 && lost) atomicAdd(counter, (unsigned long long)lost);
+}
+
+FM_DEV const MatteP &matte_p(const MatteP &p) { return p; }
+FM_DEV const MatteP &matte_p(const MatteModelP &p) { return p.m; }
+FM_DEV CameraModelP model_p(const MatteP &) { return CameraModelP{}; }
+FM_DEV const CameraModelP &model_p(const MatteModelP &p) { return p.cm; }
+
+// One thread per pixel of the whole target, 16 x 16-pixel blocks and the wave's LDS stack like k_features, whose rays these
+// are: sample s is ray_of's ray for the s-th randBase of the stream, traced once to its closest hit; the hit triangle's id
+// of each kind (NK = 1: table a alone, 2: a and b from the same hit) goes through matte_count in sample order.  A lane
+// outside the target traces nothing and stays for the wave's sum of lost samples.
+template <int MODEL, int NK, class P>
+__global__ __launch_bounds__(BLOCK_THREADS) void k_mattes(const P pp) {
+  extern __shared__ int lds_stack[];
+  const MatteP &m = matte_p(pp);
+  const FeatureP &p = m.f;
+  const DScene &S = p.scene;
+  int *stack = lane_stack(lds_stack, threadIdx.y * blockDim.x + threadIdx.x, S.stack_n);
+  const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+  const bool inside = x < p.W && y < p.H;
+  Counters cnt = {0, 0, 0, 0, 0, 0};
+  uint64_t st = p.seed;
+  MatteTab ta = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, tb = ta;
+  uint32_t lost_a = 0u, lost_b = 0u;
+  const uint32_t n = inside ? p.samples : 0u;
+  for (uint32_t s = 0; s < n; ++s) {
+    const float rb = rand_base_step(st);
+    V3 o, d;
+    ray_of<SMP_REF, MODEL>(x, y, p.W, p.H, p.cam, model_p(pp), rb, 0u, 0u, o, d);
+    int hitA, hitB;
+    float tB;
+    trace_rays<false, false>(S, stack, o, false, d, d, hitA, tB, hitB, cnt);
+    const int tri = slot_to_tri(S, hitB);
+    lost_a += matte_count(ta, tri >= 0 ? m.ids_a[tri] : 0u);
+    if constexpr (NK == 2) lost_b += matte_count(tb, tri >= 0 ? m.ids_b[tri] : 0u);
+  }
+  const float fs = (float)p.samples;
+  const size_t i = (size_t)y * p.W + x;
+  if (inside) matte_store(ta, fs, m.out_a + 3 * i);
+  matte_lost(lost_a, m.lost_a);
+  if constexpr (NK == 2) {
+    if (inside) matte_store(tb, fs, m.out_b + 3 * i);
+    matte_lost(lost_b, m.lost_b);
+  }
 }
 
 // ---- temporal accumulation (fspt_temporal_accumulate): the G-buffer pass (blend, clamp, variance: fspt_post.hip) ----
@@ -330,6 +419,20 @@ hipError_t launch_features(const FeatureP &p, const CameraModelP &cm, hipStream_
   const hipError_t e = with_model(cm.model, [&](auto M) {
     if constexpr (M == CAM_PINHOLE) return launch(k_features<M, FeatureP>, g, b, lds, stream, p);
     else return launch(k_features<M, FeatureModelP>, g, b, lds, stream, FeatureModelP{p, cm});
+  });
+  return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t launch_mattes(const MatteP &p, const CameraModelP &cm, hipStream_t stream) {
+  const FeatureP &f = p.f;
+  const dim3 g((f.W + 15) / 16, (f.H + 15) / 16), b(16, 16);
+  const size_t lds = stack_bytes(f.scene);
+  hipError_t e = hipMemsetAsync(p.lost_a, 0, 8, stream);
+  if (e == hipSuccess && p.ids_b) e = hipMemsetAsync(p.lost_b, 0, 8, stream);
+  if (e != hipSuccess) return e;
+  e = with_model(cm.model, [&](auto M) {
+    if constexpr (M == CAM_PINHOLE) return p.ids_b ? launch(k_mattes<M, 2, MatteP>, g, b, lds, stream, p) : launch(k_mattes<M, 1, MatteP>, g, b, lds, stream, p);
+    else return p.ids_b ? launch(k_mattes<M, 2, MatteModelP>, g, b, lds, stream, MatteModelP{p, cm}) : launch(k_mattes<M, 1, MatteModelP>, g, b, lds, stream, MatteModelP{p, cm});
   });
   return e != hipSuccess ? e : hipGetLastError();
 }

@@ -204,6 +204,53 @@ int fspt_read_features(fspt_target *t, float *out) {
   return read_back(t, out, t->feat, (size_t)t->W * t->H * 32, "fspt_read_features");
 }
 
+// ID mattes: k_features' rays once more, the ids of the scene's kinds ranked per pixel.  The kinds with ids
+// fill the launch's tables in kind order; nothing but the matte buffers is written.
+int fspt_mattes(fspt_target *t, const fspt_camera_params *cam, uint32_t samples, uint64_t seed) {
+  const char *fn = "fspt_mattes";
+  if (t && cam && (samples == 0 || samples > 65535u)) { fspt_set_error("%s: samples must be in 1..65535", fn); return FSPT_E_INVALID; }
+  int rc = dn_enter(t, cam != nullptr, fn);
+  if (rc) return rc;
+  const fspt_scene *sc = t->scene;
+  if (!sc->matte_ids[0] && !sc->matte_ids[1]) { fspt_set_error("%s: the scene has no matte ids (fspt_scene_set_matte_ids)", fn); return FSPT_E_STATE; }
+  const size_t px = (size_t)t->W * t->H;
+  if (!t->mt_lost) HIP_TRY(hipMalloc((void **)&t->mt_lost, 16));
+  for (int k = 0; k < 2; ++k) if (sc->matte_ids[k] && (rc = dn_alloc(&t->mt[k], px * 48))) return rc;
+  fspt::MatteP p{};
+  p.f.scene = sc->d;
+  p.f.W = t->W; p.f.H = t->H;
+  std::memcpy(p.f.cam.P, cam->P, 12); std::memcpy(p.f.cam.I, cam->I, 12);
+  p.f.cam.fov_scale = cam->fov_scale; p.f.cam.lens[0] = cam->lens[0]; p.f.cam.lens[1] = cam->lens[1];
+  p.f.samples = samples;
+  p.f.seed = seed;
+  const int a = sc->matte_ids[0] ? 0 : 1; // table a: the first kind with ids; table b: the material ids when both have
+  p.ids_a = sc->matte_ids[a]; p.out_a = t->mt[a]; p.lost_a = t->mt_lost + a;
+  if (a == 0 && sc->matte_ids[1]) { p.ids_b = sc->matte_ids[1]; p.out_b = t->mt[1]; p.lost_b = t->mt_lost + 1; }
+  t->mt_valid[0] = t->mt_valid[1] = false;
+  HIP_TRY(fspt::launch_mattes(p, t->cam_model, t->stream));
+  for (int k = 0; k < 2; ++k) t->mt_valid[k] = sc->matte_ids[k] != nullptr;
+  return FSPT_OK;
+}
+
+// what fspt_read_mattes and fspt_mattes_lost start with
+static int mattes_enter(fspt_target *t, int kind, bool args_ok, const char *fn) {
+  if (t && args_ok && kind != FSPT_MATTE_OBJECT && kind != FSPT_MATTE_MATERIAL) { fspt_set_error("%s: unknown kind %d", fn, kind); return FSPT_E_INVALID; }
+  const int rc = dn_enter(t, args_ok, fn);
+  if (rc) return rc;
+  if (!t->mt_valid[kind]) { fspt_set_error("%s: no fspt_mattes call yet that computed kind %d", fn, kind); return FSPT_E_STATE; }
+  return FSPT_OK;
+}
+
+int fspt_read_mattes(fspt_target *t, int kind, float *out) {
+  const int rc = mattes_enter(t, kind, out != nullptr, "fspt_read_mattes");
+  return rc ? rc : read_back(t, out, t->mt[kind], (size_t)t->W * t->H * 48, "fspt_read_mattes");
+}
+
+int fspt_mattes_lost(fspt_target *t, int kind, uint64_t *lost) {
+  const int rc = mattes_enter(t, kind, lost != nullptr, "fspt_mattes_lost");
+  return rc ? rc : read_back(t, lost, t->mt_lost + kind, 8, "fspt_mattes_lost");
+}
+
 int fspt_denoise(fspt_target *t, const fspt_denoise_params *prm, float *out) {
   int rc = dn_enter(t, true, "fspt_denoise");
   if (rc) return rc;
@@ -916,17 +963,21 @@ int fspt_draw_exr(fspt_target *t, int source, const fspt_exr_params *p, uint8_t 
   int rc = encoded_args(t, source, out, bytes_out, fn);
   if (rc) return rc;
   fspt::ExrPlan pl;
-  if ((rc = fspt::exr_plan(p, t->W, t->H, true, fn, pl))) return rc;
+  fspt::ExrMattes mt{}; // the target's matte buffers and the scene's manifests
+  for (int k = 0; k < 2; ++k) { mt.ranks[k] = t->mt[k]; mt.manifest[k] = t->scene->matte_manifest[k].data(); mt.manifest_len[k] = t->scene->matte_manifest[k].size(); }
+  if ((rc = fspt::exr_plan(p, t->W, t->H, true, fn, pl, true, &mt))) return rc;
   if ((rc = dn_enter(t, true, fn))) return rc; // (joins a present)
   const float4 *src = nullptr;
   int denoise = 0; float max_sigma = 0.0f, scale = 1.0f;
   if ((rc = encoded_source(t, source, src, denoise, max_sigma, scale))) return rc;
   const bool guided = (pl.layers & ((uint32_t)FSPT_EXR_ALBEDO | (uint32_t)FSPT_EXR_NORMAL | (uint32_t)FSPT_EXR_DEPTH)) != 0u;
   if (guided && !t->feat_valid) { fspt_set_error("%s: feature layers and no fspt_features call yet", fn); return FSPT_E_STATE; }
+  for (int k = 0; k < 2; ++k)
+    if ((pl.layers & ((uint32_t)FSPT_EXR_CRYPTO_OBJECT << k)) && !t->mt_valid[k]) { fspt_set_error("%s: a matte layer and no fspt_mattes call yet that computed kind %d", fn, k); return FSPT_E_STATE; }
   // the output buffer: the largest bound asked for so far; it grows, and outlives a change of the parameters
   t->ex_bound = std::max(t->ex_bound, pl.bound);
   hipError_t e = fspt::exr_ensure(t->ex, pl, t->ex_bound);
-  if (e == hipSuccess) e = fspt::exr_launch(t->ex, src, guided ? t->feat : nullptr, 1, t->stream);
+  if (e == hipSuccess) e = fspt::exr_launch(t->ex, src, guided ? t->feat : nullptr, 1, t->stream, &mt);
   if (e != hipSuccess) return hip_fail(fn, e);
   return fspt::exr_collect(t->ex, t->stream, out, cap, bytes_out, fn);
 }
@@ -935,6 +986,7 @@ int fspt_draw_exr(fspt_target *t, int source, const fspt_exr_params *p, uint8_t 
 
 // fspt_target_destroy's share of the image chain (both streams are idle): every buffer and event above
 void post_release(fspt_target *t) {
+  hipFree(t->mt[0]); hipFree(t->mt[1]); hipFree(t->mt_lost);
   hipFree(t->feat); hipFree(t->dn_tmp[0]); hipFree(t->dn_tmp[1]); hipFree(t->dn_out);
   hipFree(t->tm_hist[0]); hipFree(t->tm_hist[1]); hipFree(t->tm_g[0]); hipFree(t->tm_g[1]); hipFree(t->tm_m);
   sv_free(t); cl_free(t); ax_free(t); bl_free(t);

@@ -395,6 +395,7 @@ int rebuild_run(fspt_scene *s, const float *tri, const float *norm, uint32_t *or
   std::vector<DeformArray> follow;
   for (fspt_scene::StageOwner who : {fspt_scene::STAGE_POSE, fspt_scene::STAGE_SKIN, fspt_scene::STAGE_MESH})
     for (const DeformArray &a : deform_arrays(s, who)) if (a.follows && *a.p) follow.push_back(a);
+  for (uint32_t *&ids : s->matte_ids) if (ids) follow.push_back(DeformArray{(void **)&ids, T, {1u, 0u}, 1, true}); // the matte ids, a word per triangle
   for (const DeformArray &a : follow) {
     void *p = nullptr;
     REBUILD_ALLOC(&p, (size_t)T * (a.span[0] + a.span[1]) * 4 * a.slices);

@@ -713,6 +713,7 @@ int fspt_scene_destroy(fspt_scene *s) {
   hipSetDevice(s->device);
   geometry_free(*s);
   hipFree(s->atlas); hipFree(s->atlas4); hipFree(s->tex_sets); hipFree(s->env); hipFree(s->bins); hipFree(s->l_alias); hipFree(s->l_rec); hipFree(s->l_p); hipFree(s->l_pick);
+  hipFree(s->matte_ids[0]); hipFree(s->matte_ids[1]);
   fspt::refit_release(s);
   fspt::appearance_release(s);
   for (fspt_scene::StageOwner who : {fspt_scene::STAGE_POSE, fspt_scene::STAGE_SKIN, fspt_scene::STAGE_MESH}) fspt::deformer_release(s, who);

@@ -938,4 +938,69 @@ int fspt_scene_motion_end(fspt_scene *s) {
   return FSPT_OK;
 }
 
+// ---------------------------------------------------------------------------
+// ID mattes: the ids and manifests a scene carries (the pass: fspt_post.cpp fspt_mattes)
+// ---------------------------------------------------------------------------
+// MurmurHash3_x86_32, seed 0, then Cryptomatte's float rule: the id is read as a float, so its exponent is neither 0 nor 255
+uint32_t fspt_matte_hash(const char *name, size_t len) {
+  const uint8_t *d = (const uint8_t *)name;
+  const auto rotl = [](uint32_t x, int r) { return (x << r) | (x >> (32 - r)); };
+  uint32_t h = 0u;
+  const size_t nb = name ? len / 4 : 0;
+  if (!name) len = 0;
+  for (size_t i = 0; i < nb; ++i) {
+    uint32_t k = (uint32_t)d[4 * i] | (uint32_t)d[4 * i + 1] << 8 | (uint32_t)d[4 * i + 2] << 16 | (uint32_t)d[4 * i + 3] << 24;
+    k *= 0xcc9e2d51u; k = rotl(k, 15); k *= 0x1b873593u;
+    h ^= k; h = rotl(h, 13); h = h * 5u + 0xe6546b64u;
+  }
+  uint32_t k = 0u;
+  const uint8_t *tail = d + nb * 4;
+  switch (len & 3u) {
+    case 3: k ^= (uint32_t)tail[2] << 16; // fall through
+    case 2: k ^= (uint32_t)tail[1] << 8;  // fall through
+    case 1: k ^= tail[0]; k *= 0xcc9e2d51u; k = rotl(k, 15); k *= 0x1b873593u; h ^= k;
+  }
+  h ^= (uint32_t)len;
+  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+  const uint32_t e = (h >> 23) & 255u;
+  return e == 0u || e == 255u ? h ^ (1u << 23) : h;
+}
+
+static int matte_kind_check(const fspt_scene *s, int kind, const char *fn) {
+  if (!s) { fspt_set_error("%s: NULL scene", fn); return FSPT_E_INVALID; }
+  if (kind != FSPT_MATTE_OBJECT && kind != FSPT_MATTE_MATERIAL) { fspt_set_error("%s: unknown kind %d", fn, kind); return FSPT_E_INVALID; }
+  return FSPT_OK;
+}
+
+int fspt_scene_set_matte_ids(fspt_scene *s, int kind, const uint32_t *ids) {
+  const char *fn = "fspt_scene_set_matte_ids";
+  int rc = matte_kind_check(s, kind, fn);
+  if (rc) return rc;
+  const size_t T = s->n_tris;
+  for (size_t i = 0; ids && i < T; ++i) { // (a normal finite float: the encoder's NaN canonicalisation never touches an id)
+    const uint32_t e = (ids[i] >> 23) & 255u;
+    if (ids[i] != 0u && (e == 0u || e == 255u)) { fspt_set_error("%s: ids[%zu] = 0x%08x has exponent field %u (ids unchanged)", fn, i, ids[i], e); return FSPT_E_INVALID; }
+  }
+  if (!ids && !s->matte_ids[kind]) return FSPT_OK; // nothing to drop: no device touched
+  if ((rc = begin_scene_change(s))) return rc;    // (a pass a target has enqueued reads the old table)
+  uint32_t *d = nullptr;
+  if (ids) {
+    const DevicePart part = {(void **)&d, ids, T * 4, (T ? T : 1) * 4, 0};
+    const hipError_t e = alloc_and_upload(&part, 1);
+    if (e != hipSuccess) return refuse_hip(fn, e, "%zu triangles", T);
+  }
+  hipFree(s->matte_ids[kind]);
+  s->matte_ids[kind] = d;
+  return FSPT_OK;
+}
+
+int fspt_scene_set_matte_manifest(fspt_scene *s, int kind, const char *json, size_t len) {
+  const char *fn = "fspt_scene_set_matte_manifest";
+  const int rc = matte_kind_check(s, kind, fn);
+  if (rc) return rc;
+  if (len > fspt::EXR_MANIFEST_MAX) { fspt_set_error("%s: a manifest holds at most %u bytes", fn, fspt::EXR_MANIFEST_MAX); return FSPT_E_INVALID; }
+  s->matte_manifest[kind].assign(json && len ? json : "", json ? len : 0);
+  return FSPT_OK;
+}
+
 } // extern "C"

@@ -383,7 +383,21 @@ function pngFilteredEval(rgba, width, height, opts) {
   return out;
 }
 const EXR_COMPRESSIONS = { none: 0, zips: 2, zip: 3 };
-const EXR_LAYERS = { alpha: 1, albedo: 2, normal: 4, depth: 8 };
+const EXR_LAYERS = { alpha: 1, albedo: 2, normal: 4, depth: 8, crypto_object: 16, crypto_material: 32 }; // (the last two: the Cryptomatte ID mattes of DESIGN.md 8.25)
+const EXR_CRYPTO = 16 | 32;
+const MATTE_KINDS = { object: 0, material: 1 };
+function matteKind(kind, fn) {
+  const k = MATTE_KINDS[kind];
+  if (k === undefined) throw new RangeError(fn + ": kind must be 'object' or 'material'");
+  return k;
+}
+/** The 32-bit id of a name (include/fspt.h fspt_matte_hash, DESIGN.md 8.25): MurmurHash3_x86_32 of its UTF-8 bytes, seed 0, then Cryptomatte's float rule */
+function matteHash(name) { return addon.matteHash(String(name)); }
+/** Cryptomatte's manifest of `names`: JSON {"name":"%08x", ...} in the order given (non-ASCII characters escaped, as the Python host writes them) */
+function matteManifest(names) {
+  const esc = (s) => JSON.stringify(String(s)).replace(/[\u007f-\uffff]/g, (c) => '\\u' + c.charCodeAt(0).toString(16).padStart(4, '0'));
+  return '{' + names.map((n) => esc(n) + ':"' + matteHash(n).toString(16).padStart(8, '0') + '"').join(',') + '}';
+}
 /** {compression ('zip' | 'zips' | 'none'), float32 (false: HALF; Z is always FLOAT), layers (names of EXR_LAYERS: an array, or one string with
  *  commas), chunkBytes (0 = the library's default)} -> the addon's four numbers */
 function exrArgs(o, fn) {
@@ -405,12 +419,29 @@ function exrArgs(o, fn) {
  *  opts: {compression ('zip'), float32 (false), layers ([]), chunkBytes (0), bottomUp (false), device (0)}. */
 function exrEncode(rgba, features, width, height, opts) {
   const o = opts || {}, enc = exrArgs(o, 'exrEncode');
+  if (o.mattes != null) return exrEncodeMattes(rgba, features, width, height, o, enc);
   if (!(rgba instanceof Float32Array) || rgba.length !== width * height * 4) throw new RangeError('exrEncode: need a Float32Array of width*height*4 floats');
   if (enc[2] & 14 ? !(features instanceof Float32Array) || features.length !== width * height * 8 : features != null && !(features instanceof Float32Array && features.length === width * height * 8)) {
     throw new RangeError('exrEncode: the albedo, normal and depth layers need features, a Float32Array of width*height*8 floats');
   }
   const out = new Uint8Array(addon.exrBound(width, height, ...enc));
   const n = addon.exrEncode(o.device || 0, rgba, features || null, width, height, !!o.bottomUp, ...enc, out);
+  if (n < 0) throw new Error('exrEncode: the file outgrew the bound');
+  return Buffer.from(out.subarray(0, n));
+}
+/** exrEncode with opts.mattes = { object, material }: each a Float32Array of width*height*12 floats as readMattes(kind, true) returns
+ *  it, or { ranks, manifest (a string) }, for the 'crypto_object' / 'crypto_material' layers (fspt_exr_encode_mattes, DESIGN.md 8.25) */
+function exrEncodeMattes(rgba, features, width, height, o, enc) {
+  if (!(rgba instanceof Float32Array) || rgba.length !== width * height * 4) throw new RangeError('exrEncode: need a Float32Array of width*height*4 floats');
+  const ranks = [null, null], manifest = [null, null];
+  for (const kind of Object.keys(o.mattes)) {
+    const k = matteKind(kind, 'exrEncode'), v = o.mattes[kind];
+    ranks[k] = v instanceof Float32Array ? v : v.ranks;
+    manifest[k] = v instanceof Float32Array || v.manifest == null || v.manifest === '' ? null : String(v.manifest);
+    if (!(ranks[k] instanceof Float32Array) || ranks[k].length !== width * height * 12) throw new RangeError('exrEncode: matte ranks must be a Float32Array of width*height*12 floats');
+  }
+  const out = new Uint8Array(addon.exrBoundMattes(width, height, ...enc, manifest[0], manifest[1]));
+  const n = addon.exrEncodeMattes(o.device || 0, rgba, features || null, ranks[0], ranks[1], manifest[0], manifest[1], width, height, !!o.bottomUp, ...enc, out);
   if (n < 0) throw new Error('exrEncode: the file outgrew the bound');
   return Buffer.from(out.subarray(0, n));
 }
@@ -494,6 +525,7 @@ class PathTracer {
     this.resolution = [width, height];
     this._scene = addon.sceneCreate(scene, device || 0);
     this._nTris = scene.tri.length / 9;       // updateGeometry checks its arrays against it
+    this._manifests = [null, null];            // setMatte's manifests by kind (drawExr's bound counts them)
     this._target = addon.targetCreate(this._scene, width, height);
     // main.js:67-74
     this.fovScale = 0.5; this.envTheta = 0; this.dir = [0, 0, -1]; this.eye = [0, 0, 2];
@@ -628,7 +660,8 @@ class PathTracer {
     const o = opts || {}, enc = exrArgs(o, 'drawExr');
     const src = JPEG_SOURCES[o.source === undefined ? 'accumulator' : o.source];
     if (src === undefined) throw new RangeError("drawExr: source must be 'accumulator', 'denoised', 'temporal' or 'temporalDenoised'");
-    const need = addon.exrBound(this.resolution[0], this.resolution[1], ...enc);
+    const need = enc[2] & EXR_CRYPTO ? addon.exrBoundMattes(this.resolution[0], this.resolution[1], ...enc, this._manifests[0], this._manifests[1])
+      : addon.exrBound(this.resolution[0], this.resolution[1], ...enc);
     if (!this._exrBuf || this._exrBuf.length < need) this._exrBuf = new Uint8Array(need);
     let n = addon.drawExr(this._target, src, ...enc, this._exrBuf);
     if (n < 0) { this._exrBuf = new Uint8Array(-n); n = addon.drawExr(this._target, src, ...enc, this._exrBuf); }
@@ -649,6 +682,45 @@ class PathTracer {
     addon.features(this._target, { P: this.eye, I: this.dir, fovScale: this.fovScale, lens: this.lensFeatures,
       envTheta: this.envTheta, numBounces: this.numBounces }, samples === undefined ? 8 : samples, seed === undefined ? 1 : seed);
   }
+  /** ID mattes (include/fspt.h fspt_scene_set_matte_ids / _manifest, fspt_mattes; DESIGN.md 8.25).  setMatte(kind, triLabel, names):
+   *  kind 'object' | 'material'; triLabel = per triangle (current leaf order) an index into names, negative = no matte; a triangle's id
+   *  is matteHash of its name, the manifest matteManifest(names); two names with one hash throw.  setMatte(kind, null) drops the kind.
+   *  mattes(samples, seed): features()' rays, the ids ranked per pixel.  readMattes(kind) -> { ids: Uint32Array(W*H*6), coverage:
+   *  Float32Array(W*H*6) }, rows bottom-up, rank 0 first (raw = true: the Float32Array(W*H*12) itself, what exrEncode's mattes take).
+   *  mattesLost(kind): the samples the last pass dropped.  drawExr takes the layers 'crypto_object' and 'crypto_material'.
+   *  Every one of them throws Error('render in flight') during a renderAsync. */
+  setMatte(kind, triLabel, names) {
+    const k = matteKind(kind, 'setMatte');
+    if (triLabel == null) { addon.sceneSetMatte(this._scene, this._nTris, k, null, null); this._manifests[k] = null; return; }
+    if (triLabel.length !== this._nTris) throw new RangeError('setMatte: triLabel must hold ' + this._nTris + ' labels');
+    const hashes = names.map((n) => matteHash(n)), seen = new Map();
+    names.forEach((n, i) => {
+      if (seen.has(hashes[i]) && seen.get(hashes[i]) !== String(n)) throw new RangeError('setMatte: the names ' + JSON.stringify(seen.get(hashes[i])) + ' and ' + JSON.stringify(String(n)) + ' have one hash');
+      seen.set(hashes[i], String(n));
+    });
+    const ids = new Uint32Array(this._nTris);
+    for (let i = 0; i < ids.length; i++) {
+      const l = triLabel[i];
+      if (l >= names.length) throw new RangeError('setMatte: label ' + l + ', ' + names.length + ' names');
+      ids[i] = l >= 0 ? hashes[l] : 0;
+    }
+    const manifest = matteManifest(names);
+    addon.sceneSetMatte(this._scene, this._nTris, k, ids, manifest);
+    this._manifests[k] = manifest;
+  }
+  mattes(samples, seed) {
+    addon.mattes(this._target, { P: this.eye, I: this.dir, fovScale: this.fovScale, lens: this.lensFeatures,
+      envTheta: this.envTheta, numBounces: this.numBounces }, samples === undefined ? 8 : samples, seed === undefined ? 1 : seed);
+  }
+  readMattes(kind, raw) {
+    const px = this.resolution[0] * this.resolution[1];
+    const out = addon.readMattes(this._target, matteKind(kind, 'readMattes'), new Float32Array(px * 12));
+    if (raw) return out;
+    const bits = new Uint32Array(out.buffer), ids = new Uint32Array(px * 6), coverage = new Float32Array(px * 6);
+    for (let i = 0; i < px * 6; i++) { ids[i] = bits[2 * i]; coverage[i] = out[2 * i + 1]; }
+    return { ids, coverage };
+  }
+  mattesLost(kind) { return addon.mattesLost(this._target, matteKind(kind, 'mattesLost')); }
   denoise(opts, out) {
     out = out || new Float32Array(this.resolution[0] * this.resolution[1] * 4);
     if (out.length !== this.resolution[0] * this.resolution[1] * 4) throw new RangeError('denoise: need W*H*4 floats');
@@ -1075,5 +1147,5 @@ class MultiPathTracer {
 // memory later scenes may spend on interleaved material textures (fspt_set_texture_interleave_budget; results do not depend on it)
 function setTextureInterleaveBudget(bytes) { addon.setTextureInterleaveBudget(bytes); }
 
-module.exports = { addon, setTextureInterleaveBudget, jpegEncode, pngEncode, pngFilteredEval, exrEncode, skyGenerate, envBinsGpu, atlasPackGpu, SKY_DEFAULTS, MultiPathTracer, AtlasLayers, resolveMaterial, readMtl, mergeSceneProps, resampleImage, packReferenceScene, buildScene,
+module.exports = { addon, setTextureInterleaveBudget, jpegEncode, pngEncode, pngFilteredEval, exrEncode, matteHash, matteManifest, skyGenerate, envBinsGpu, atlasPackGpu, SKY_DEFAULTS, MultiPathTracer, AtlasLayers, resolveMaterial, readMtl, mergeSceneProps, resampleImage, packReferenceScene, buildScene,
   PathTracer, saveBlob, loadBlob };

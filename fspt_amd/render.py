@@ -101,7 +101,8 @@ def main(argv=None):
     ap.add_argument("--atrous", type=int, default=0, help="guided a-trous denoiser iterations (0 = off; built-in scene)")
     ap.add_argument("--feature-samples", type=int, default=8, help="camera rays per pixel of the denoiser's guide buffers")
     ap.add_argument("--hdr", default=None, help="also save the RGBA32F radiance buffer: a name that ends in .exr as OpenEXR made on the GPU (DESIGN 8.21), any other as .npy")
-    ap.add_argument("--exr-layers", default="", help="--out / --hdr *.exr: layers beside R G B, of albedo,normal,depth,alpha")
+    ap.add_argument("--exr-layers", default="", help="--out / --hdr *.exr: layers beside R G B, of albedo,normal,depth,alpha,crypto_object,crypto_material (the last two: Cryptomatte ID mattes, DESIGN 8.25)")
+    ap.add_argument("--matte-samples", type=int, default=8, help="camera rays per pixel of the ID mattes (--exr-layers crypto_object,crypto_material), in 1..65535")
     ap.add_argument("--exr-float", action="store_true", help="--out / --hdr *.exr: 32-bit FLOAT channels (the default is HALF; Z is always FLOAT)")
     ap.add_argument("--exr-compression", default="zip", choices=("none", "zips", "zip"), help="--out / --hdr *.exr: blocks of 16 scanlines deflated (zip, the default), of one (zips), or none")
     ap.add_argument("--scene", default=None, help="scene JSON ({frame} is replaced per frame with --frames)")
@@ -171,11 +172,15 @@ def main(argv=None):
     try:
         from .tracer import exr_params
         exr = dict(compression=args.exr_compression, float32=args.exr_float, layers=[x for x in args.exr_layers.split(",") if x])
-        exr_guided = bool(exr_params(**exr).layers & 14)
+        exr_guided, exr_mattes = bool(exr_params(**exr).layers & 14), bool(exr_params(**exr).layers & 48)
     except ValueError as e:
         ap.error("--exr-layers: " + str(e))
     if exr_guided and args.scene and not (args.frames and args.bvh == "refit"):
         ap.error("--exr-layers albedo, normal and depth are available for the built-in scene, or with --frames and --bvh refit")
+    if exr_mattes and args.scene and not (args.frames and args.bvh == "refit"):
+        ap.error("--exr-layers crypto_object and crypto_material are available for the built-in scene, or with --frames and --bvh refit")
+    if not 1 <= args.matte_samples <= 65535:
+        ap.error("--matte-samples must lie in 1..65535")
     jpeg = dict(quality=args.jpeg_quality, subsampling="444" if args.jpeg_444 else "420")
     if (args.jpeg_quality != 85 or args.jpeg_444) and not is_jpeg_path(args.out):
         ap.error("--jpeg-quality and --jpeg-444 need an --out that ends in .jpg or .jpeg")
@@ -258,7 +263,8 @@ def main(argv=None):
                                     rebuild_above=args.rebuild_above,
                                     temporal=({"atrous": args.atrous, "clamp": None if args.temporal_clamp is None else True if args.temporal_clamp is True
                                                else {"sigma_scale": args.temporal_clamp}} if args.temporal else None),
-                                    variance=args.variance_guided, pose=args.pose, mesh=args.mesh, textures=args.textures, jpeg=jpeg, png=png, exr=exr, **kw)
+                                    variance=args.variance_guided, pose=args.pose, mesh=args.mesh, textures=args.textures, jpeg=jpeg, png=png, exr=exr,
+                                    matte_samples=args.matte_samples, **kw)
             print(f"{len(out)} frames in {time.perf_counter() - t0:.2f} s:", *out)
         else:
             arrays, settings = F.load_scene_file(args.scene, args.assets, bvh=args.bvh, textures=args.textures)
@@ -274,7 +280,7 @@ def main(argv=None):
             print("wrote", args.out, f"({arrays.n_tris} triangles, {spp or settings['samples']} spp)")
         return
     t0 = time.perf_counter()
-    arrays = S.bunny_scene(n=args.mesh_n, bvh=args.bvh)
+    arrays = S.bunny_scene(n=args.mesh_n, bvh=args.bvh, keep_order=exr_mattes)  # (the mattes' names come from the props)
     print(f"scene: {arrays.n_tris} triangles, {arrays.n_nodes} nodes, depth {arrays.depth} ({args.bvh} tree) in "
           f"{time.perf_counter() - t0:.2f} s")
     pt = PathTracer(arrays, args.width, args.height, num_bounces=args.bounces)
@@ -318,6 +324,9 @@ def main(argv=None):
         pt.denoise(iterations=args.atrous)
     if exr_guided and args.atrous <= 0:
         pt.features(args.feature_samples, args.seed)
+    if exr_mattes:
+        pt.scene.set_default_mattes()
+        pt.mattes(args.matte_samples, args.seed)
     if exr_out:  # the radiance itself, and the guides, as a file made on the device
         data = pt.draw_exr("denoised" if args.atrous > 0 else "accumulator", **exr)
     elif is_jpeg_path(args.out):  # drawn and encoded on the device: only the file comes back

@@ -505,6 +505,7 @@ def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas
     meta["focus"] = shootAutoFocusRay's lensFeatures[0] = 1 - 1/dist for each (main.js:447-546).
     bvh = "sah": the reference's full-sweep SAH tree (bvh.js, on the CPU); "gpu": the binned-SAH tree built on HIP device
     `device` (fspt_builder_build_gpu; leaf_size 1..64).  meta["bvh"] names the builder; keep_order=True adds
+    meta["prop_names"] ("<index>:<prop path>" per prop, the object names of Scene.set_default_mattes),
     meta["tri_order"]: packed triangle k is the k'th triangle of the OBJs in the order they were added, and meta["tri_part"]:
     the index in `props` of the prop packed triangle k came from.
     geometry_only=True: parse and transform the props but build NO tree: tri / mat / norm / uv come back in PARSE order, bvh is
@@ -629,6 +630,8 @@ def build_scene(props, obj_texts, env=None, env_w=0, env_h=0, leaf_size=4, atlas
         meta["tri_order"] = order
         # the prop (index into `props`) of every packed triangle: the part ids of Scene.set_pose
         meta["tri_part"] = np.searchsorted(np.asarray(prop_end, np.int64), order.astype(np.int64), side="right").astype(np.uint32)
+        # a name per prop, distinct whatever the paths: what Scene.set_default_mattes hashes for the object matte
+        meta["prop_names"] = ["%d:%s" % (i, p.get("path", "")) for i, p in enumerate(props)]
         if keep_mesh:
             mode = np.array([_NORMALS_MODE[p.get("normals")] for p in props], np.int64)[meta["tri_part"]]
             meta.update(tri_vertex=tri_vertex, tri_uv64=tri_uv64, n_vertices=int(nv.value), vertices=vertices,
@@ -850,7 +853,7 @@ def textured_test_scene(res=16, keep_order=False, textures="cpu", device=0):
 
 
 def _kept_order(meta):
-    return {k: meta[k] for k in ("tri_order", "tri_part") if k in meta}
+    return {k: meta[k] for k in ("tri_order", "tri_part", "prop_names") if k in meta}
 
 
 def bunny_props():

@@ -411,7 +411,7 @@ def _sequence_sky(sky, k, n):
 
 
 def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_root=None, bvh="sah", rebuild_above=None,
-                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, camera=None, sky=None, textures="cpu", jpeg=None, png=None, exr=None, mesh=False, **kw):
+                    on_frame=None, temporal=None, variance=False, auto_exposure=None, bloom=None, pose=False, camera=None, sky=None, textures="cpu", jpeg=None, png=None, exr=None, mesh=False, matte_samples=8, **kw):
     """frame=N sequencing (main.js:851-866, 966-969): for every N in `frames` load `scene_pattern.format(frame=N)`
     (the per-frame scene JSON the reference's server hands out for `?frame=N`), render it, write
     `out_pattern.format(frame=N)` (the reference POSTs the canvas PNG to /upload/<scene>/<N>), go on to N + 1.
@@ -473,13 +473,15 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
     exr: an out_pattern that ends in .exr is written as a scene-linear OpenEXR file of the frame's radiance -
     under bvh="refit" by PathTracer.draw_exr (the accumulator, or the temporal result), so that only the file leaves the
     device; None or a dict of its compression / float32 / layers / chunk_bytes.  The albedo, normal and depth layers need
-    bvh="refit" (the live tracer's features).
+    bvh="refit" (the live tracer's features), and so do "crypto_object" and "crypto_material" (DESIGN 8.25): the ids are set
+    once, when the scene is built (Scene.set_default_mattes: the props, and the first frame's materials), follow the
+    triangles through every update and rebuild, and each frame's file carries a mattes() pass of matte_samples rays per pixel.
     light_builder (in kw, with lights="emitters"): "gpu" = every scene's emitter light table is built on the
     device (Scene.set_light_builder), so that a kept frame's update reads 8 bytes back for it."""
     as_exr = is_exr_path(out_pattern)
     exr, exr_layers = exr_settings(exr)
-    if as_exr and bvh != "refit" and exr_layers & 14:
-        raise ValueError('render_sequence: the albedo, normal and depth layers of an .exr need bvh="refit"')
+    if as_exr and bvh != "refit" and exr_layers & (14 | 48):
+        raise ValueError('render_sequence: the albedo, normal, depth and matte layers of an .exr need bvh="refit"')
     if textures not in S.TEXTURE_PACKERS:
         raise ValueError(f"render_sequence: textures must be one of {S.TEXTURE_PACKERS}, not {textures!r}")
     camera = _camera_model_params(camera, kw.get("adaptive"), None if temporal is None or temporal is False else temporal)
@@ -642,6 +644,8 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
                     mesh_json, mesh_rest = frame_json, sequence_mesh_positions(frame_json, base.meta["obj_texts"])
                 if camera is not None:
                     pt.set_camera_model(**camera)
+                if as_exr and exr_layers & 48:
+                    pt.scene.set_default_mattes()
                 if light_builder is not None:
                     pt.scene.set_light_builder(light_builder)
                 if pose and not frame_json.get("normalize"):
@@ -678,6 +682,8 @@ def render_sequence(scene_pattern, frames, out_pattern, width, height, asset_roo
             if as_exr:
                 if exr_layers & 14 and not (temporal is not None and (variance or atrous > 0)):
                     pt.features(8, opt["seed"])
+                if exr_layers & 48:
+                    pt.mattes(matte_samples, opt["seed"])
                 save(n, None, pt.draw_exr("accumulator" if temporal is None else "temporal_denoised" if atrous > 0 else "temporal", **exr))
             else:
                 save(n, rgba[::-1].copy())

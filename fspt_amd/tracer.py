@@ -346,11 +346,15 @@ class _FileBuffer:
     def __init__(self, bound, bound_first=False):
         self.bound, self.bound_first = bound, bound_first
         self.size, self.buf = None, np.empty(0, np.uint8)
+        self.mattes = None  # OpenEXR with Cryptomatte layers: the call's L.ExrMattes, whose manifests count in the bound
 
     def grow(self, w, h, p, need=0):
         """at least the bound of (w, h, p) and `need` bytes"""
         b = C.c_size_t()
-        L.check(getattr(L.lib(), self.bound)(w, h, C.byref(p), C.byref(b)))
+        if self.mattes is not None:
+            L.check(L.lib().fspt_exr_bound_mattes(w, h, C.byref(p), C.byref(self.mattes), C.byref(b)))
+        else:
+            L.check(getattr(L.lib(), self.bound)(w, h, C.byref(p), C.byref(b)))
         if self.buf.size < max(int(b.value), int(need)):
             self.buf = np.empty(max(int(b.value), int(need)), np.uint8)
 
@@ -460,8 +464,52 @@ def png_last_ms():
 
 
 EXR_COMPRESSIONS = {"none": 0, "zips": 2, "zip": 3}
-EXR_LAYERS = {"alpha": 1, "albedo": 2, "normal": 4, "depth": 8}
+EXR_LAYERS = {"alpha": 1, "albedo": 2, "normal": 4, "depth": 8, "crypto_object": 16, "crypto_material": 32}
 EXR_GUIDED = 2 | 4 | 8  # the layers that read the features
+EXR_CRYPTO = 16 | 32    # the Cryptomatte layers: draw_exr and exr_encode(mattes=...) take them, exr_bound does not
+MATTE_KINDS = {"object": 0, "material": 1}
+
+
+def _matte_kind(kind):
+    if kind not in MATTE_KINDS and kind not in MATTE_KINDS.values():
+        raise ValueError(f"kind must be one of {sorted(MATTE_KINDS)}")
+    return MATTE_KINDS.get(kind, kind)
+
+
+def matte_hash(name):
+    """The 32-bit id of a name (fspt_matte_hash): MurmurHash3_x86_32 of its UTF-8 bytes with seed 0, then
+    Cryptomatte's float rule (an exponent field of 0 or 255 has bit 23 flipped)."""
+    b = name if isinstance(name, bytes) else str(name).encode("utf-8")
+    return int(L.lib().fspt_matte_hash(b, len(b)))
+
+
+def matte_manifest(names):
+    """Cryptomatte's manifest of `names`: JSON {"name":"%08x", ...} in the order given, as bytes"""
+    import json
+    return ("{" + ",".join("%s:\"%08x\"" % (json.dumps(str(n)), matte_hash(n)) for n in names) + "}").encode("utf-8")
+
+
+def _exr_mattes(mattes, shape, on_dev):
+    """(L.ExrMattes, what it points to) of exr_encode's mattes={kind: ranks or (ranks, manifest bytes)}; ranks float32 [H, W, 12]"""
+    m, keep = L.ExrMattes(), []
+    for kind, v in (mattes or {}).items():
+        k = _matte_kind(kind)
+        ranks, manifest = v if isinstance(v, tuple) else (v, b"")
+        if on_dev:
+            import torch
+            if not getattr(ranks, "is_cuda", False) or ranks.dtype != torch.float32 or tuple(ranks.shape) != shape + (12,):
+                raise ValueError("matte ranks must be float32 [H, W, 12] tensors on the device of rgba")
+            ranks = ranks.contiguous()
+            m.ranks[k] = ranks.data_ptr()
+        else:
+            ranks = np.ascontiguousarray(ranks)
+            if ranks.dtype != np.float32 or ranks.shape != shape + (12,):
+                raise ValueError("matte ranks must be float32 [H, W, 12] arrays")
+            m.ranks[k] = ranks.ctypes.data
+        manifest = bytes(manifest or b"")
+        m.manifest[k], m.manifest_len[k] = (manifest if manifest else None), len(manifest)
+        keep += [ranks, manifest]
+    return m, keep
 
 
 def exr_params(compression="zip", float32=False, layers=(), chunk_bytes=0):
@@ -490,13 +538,16 @@ def exr_bound(width, height, compression="zip", float32=False, layers=(), chunk_
     return int(n.value)
 
 
-def exr_encode(rgba, features=None, compression="zip", float32=False, layers=(), chunk_bytes=0, bottom_up=False, device=0):
+def exr_encode(rgba, features=None, compression="zip", float32=False, layers=(), chunk_bytes=0, bottom_up=False, device=0, mattes=None):
     """A scanline OpenEXR file (bytes) of float32 radiance [H, W, 4] and, for the albedo, normal and depth layers, the
     features [H, W, 8] as readFeatures() returns them, encoded on the GPU (fspt_exr_encode): numpy arrays, or
     torch tensors on the device, which are read where they are (fspt_exr_encode_device).  bottom_up: row 0 is the bottom, as
-    every buffer of the library; the file's first scanline is the top."""
+    every buffer of the library; the file's first scanline is the top.  mattes: {"object" / "material":
+    ranks [H, W, 12] as fspt_read_mattes returns them, or (ranks, manifest bytes)} for the "crypto_object" /
+    "crypto_material" layers (fspt_exr_encode_mattes); arrays or tensors like rgba."""
     p = exr_params(compression, float32, layers, chunk_bytes)
     rgba, on_dev, device = _image_arg(rgba, "float32", 4, "rgba", device, sync=False)
+    m, keep = _exr_mattes(mattes, (int(rgba.shape[0]), int(rgba.shape[1])), on_dev) if mattes is not None else (None, None)
     if on_dev:
         import torch
         if features is not None:
@@ -510,6 +561,14 @@ def exr_encode(rgba, features=None, compression="zip", float32=False, layers=(),
             raise ValueError("features must be a float32 [H, W, 8] array")
     h, w = int(rgba.shape[0]), int(rgba.shape[1])
     lib, bu = L.lib(), 1 if bottom_up else 0
+    if m is not None:
+        buf = _FileBuffer("fspt_exr_bound", True)
+        buf.mattes = m
+        if on_dev:
+            f = C.c_void_p(features.data_ptr()) if features is not None else None
+            return buf.call(w, h, p, lambda o, cap, nb: lib.fspt_exr_encode_mattes_device(int(device), C.c_void_p(rgba.data_ptr()), f, C.byref(m), w, h, bu, C.byref(p), o, cap, nb))
+        f = L.fptr(features) if features is not None else None
+        return buf.call(w, h, p, lambda o, cap, nb: lib.fspt_exr_encode_mattes(int(device), L.fptr(rgba), f, C.byref(m), w, h, bu, C.byref(p), o, cap, nb))
     if on_dev:
         f = C.c_void_p(features.data_ptr()) if features is not None else None
         return _exr_buffer.call(w, h, p, lambda o, cap, nb: lib.fspt_exr_encode_device(int(device), C.c_void_p(rgba.data_ptr()), f, w, h, bu, C.byref(p), o, cap, nb))
@@ -627,6 +686,7 @@ class Scene:
         self.arrays = arrays
         self.device = device
         self._h = C.c_void_p()
+        self.matte_manifests = {}  # kind number -> the manifest bytes set_matte handed the library
         desc = arrays.desc()
         L.check(L.lib().fspt_scene_create(C.byref(desc), device, C.byref(self._h)))
 
@@ -697,6 +757,60 @@ class Scene:
         L.check(L.lib().fspt_light_sample_eval(self._h, L.fptr(q), int(q.shape[0]), tri.ctypes.data_as(C.POINTER(C.c_int32)),
                                                L.fptr(out)))
         return tri, out
+
+    # ---- ID mattes (include/fspt.h fspt_scene_set_matte_ids / _manifest) -------------------------------
+    def set_matte(self, kind, tri_label, names):
+        """The ids of kind "object" or "material": tri_label [n_tris] = per triangle (the scene's current leaf order) an
+        index into `names`, negative = no matte (id 0); a triangle's id is matte_hash of its name, the manifest
+        matte_manifest(names).  Two different names with one hash: ValueError.  tri_label None drops the kind."""
+        k = _matte_kind(kind)
+        lib = L.lib()
+        if tri_label is None:
+            L.check(lib.fspt_scene_set_matte_ids(self._h, k, None))
+            L.check(lib.fspt_scene_set_matte_manifest(self._h, k, None, 0))
+            self.matte_manifests.pop(k, None)
+            return
+        names = [str(n) for n in names]
+        hashes, seen = np.array([matte_hash(n) for n in names], np.uint32).reshape(-1), {}
+        for n, h in zip(names, hashes):
+            if seen.setdefault(int(h), n) != n:
+                raise ValueError(f"set_matte: the names {seen[int(h)]!r} and {n!r} have one hash, {int(h):08x}")
+        label = np.asarray(tri_label).astype(np.int64).reshape(-1)
+        if label.size != int(self.arrays.n_tris):
+            raise ValueError(f"set_matte: {label.size} labels, the scene has {int(self.arrays.n_tris)} triangles")
+        if label.size and label.max() >= len(names):
+            raise ValueError(f"set_matte: label {int(label.max())}, {len(names)} names")
+        ids = np.zeros(label.size, np.uint32)
+        if len(names):
+            ids = np.where(label >= 0, hashes[np.clip(label, 0, len(names) - 1)], np.uint32(0)).astype(np.uint32)
+        ids = np.ascontiguousarray(ids)
+        manifest = matte_manifest(names)
+        L.check(lib.fspt_scene_set_matte_ids(self._h, k, L.u32ptr(ids)))
+        L.check(lib.fspt_scene_set_matte_manifest(self._h, k, manifest, len(manifest)))
+        self.matte_manifests[k] = manifest
+
+    def set_matte_ids(self, kind, ids):
+        """The raw form (fspt_scene_set_matte_ids): one uint32 id per triangle, 0 = no matte; None drops the kind"""
+        k = _matte_kind(kind)
+        if ids is None:
+            L.check(L.lib().fspt_scene_set_matte_ids(self._h, k, None))
+            return
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        if ids.size != int(self.arrays.n_tris):
+            raise ValueError(f"set_matte_ids: {ids.size} ids, the scene has {int(self.arrays.n_tris)} triangles")
+        L.check(L.lib().fspt_scene_set_matte_ids(self._h, k, L.u32ptr(ids)))
+
+    def set_default_mattes(self):
+        """Objects from meta["tri_part"] and meta["prop_names"] (build_scene(..., keep_order=True)), materials from the
+        distinct rows of arrays.mat, named m0000, m0001, ... in order of first appearance."""
+        meta = getattr(self.arrays, "meta", None) or {}
+        if "tri_part" not in meta or "prop_names" not in meta:
+            raise ValueError("set_default_mattes: the arrays carry no meta['tri_part'] / meta['prop_names'] (build_scene(..., keep_order=True))")
+        self.set_matte("object", meta["tri_part"], meta["prop_names"])
+        rows = np.ascontiguousarray(self.arrays.mat, dtype=np.float32).reshape(-1, 12).view(np.uint32)
+        _, first, inverse = np.unique(rows, axis=0, return_index=True, return_inverse=True)
+        rank = np.argsort(np.argsort(first))  # a distinct row's number in order of first appearance
+        self.set_matte("material", rank[np.asarray(inverse).reshape(-1)], ["m%04d" % i for i in range(len(first))])
 
     def two_level_nodes(self):
         """(the scene has two-level nodes, their bytes): fspt_scene_create builds them when every box of the tree is the
@@ -1723,7 +1837,13 @@ class PathTracer:
         if source not in JPEG_SOURCES:
             raise ValueError(f"source must be one of {sorted(JPEG_SOURCES)}")
         p, lib = exr_params(compression, float32, layers, chunk_bytes), L.lib()
-        return self._file_buffer("exr", True).call(*self.resolution, p, lambda o, cap, nb: lib.fspt_draw_exr(self._t, JPEG_SOURCES[source], C.byref(p), o, cap, nb))
+        buf = self._file_buffer("exr", True)
+        buf.mattes = None
+        if p.layers & EXR_CRYPTO:  # the scene's manifests count in the bound ("crypto_object", "crypto_material": DESIGN 8.25)
+            buf.mattes = L.ExrMattes()
+            for k, manifest in self.scene.matte_manifests.items():
+                buf.mattes.manifest[k], buf.mattes.manifest_len[k] = manifest, len(manifest)
+        return buf.call(*self.resolution, p, lambda o, cap, nb: lib.fspt_draw_exr(self._t, JPEG_SOURCES[source], C.byref(p), o, cap, nb))
 
     def present_jpeg(self, exposure=1.0, saturation=1.0, denoise=False, max_sigma=3.0, scale=1.0, quality=85, subsampling="420", restart_mcus=0):
         """present() with the frame encoded on the GPU behind its draw (fspt_present_jpeg): (the PREVIOUS call's JPEG file as
@@ -1748,6 +1868,32 @@ class PathTracer:
         cp.fov_scale = self.fovScale; cp.lens = (C.c_float * 2)(*self.lensFeatures)
         cp.env_theta = self.envTheta; cp.num_bounces = self.num_bounces
         L.check(L.lib().fspt_features(self._t, C.byref(cp), int(samples), int(seed)))
+
+    # ---- ID mattes (include/fspt.h fspt_mattes) -------------------------------------------------------
+    def mattes(self, samples=8, seed=1):
+        """Object and material coverage of the set_camera() view: features()' rays, the ids of the scene's kinds ranked per
+        pixel (fspt_mattes).  The scene needs ids (Scene.set_matte / set_default_mattes)."""
+        cp = L.CameraParams()
+        cp.P = (C.c_float * 3)(*self.eye); cp.I = (C.c_float * 3)(*self.dir)
+        cp.fov_scale = self.fovScale; cp.lens = (C.c_float * 2)(*self.lensFeatures)
+        cp.env_theta = self.envTheta; cp.num_bounces = self.num_bounces
+        L.check(L.lib().fspt_mattes(self._t, C.byref(cp), int(samples), int(seed)))
+
+    def read_mattes(self, kind, raw=False):
+        """(ids uint32 [H, W, 6], coverage float32 [H, W, 6]) of the last mattes(), row 0 = bottom, rank 0 first; raw: the
+        float32 [H, W, 12] buffer itself (id0 c0 .. id5 c5), what exr_encode(mattes=...) takes"""
+        W, H = self.resolution
+        out = np.zeros((H, W, 12), np.float32)
+        L.check(L.lib().fspt_read_mattes(self._t, _matte_kind(kind), L.fptr(out)))
+        if raw:
+            return out
+        return np.ascontiguousarray(out.view(np.uint32)[..., 0::2]), np.ascontiguousarray(out[..., 1::2])
+
+    def mattes_lost(self, kind):
+        """Samples the last mattes() dropped because a pixel's six slots were taken (fspt_mattes_lost)"""
+        n = C.c_uint64()
+        L.check(L.lib().fspt_mattes_lost(self._t, _matte_kind(kind), C.byref(n)))
+        return int(n.value)
 
     def readFeatures(self):
         """float32 [H, W, 8], row 0 = bottom: albedo.rgb, depth, normal.xyz, coverage (sample means)."""

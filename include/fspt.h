@@ -41,8 +41,7 @@ enum {
   FSPT_E_STATE = -6      /* call order (e.g. trace before camera)        */
 };
 
-typedef struct fspt_scene fspt_scene;
-typedef struct fspt_target fspt_target;
+typedef struct fspt_scene fspt_scene; typedef struct fspt_target fspt_target;
 typedef struct fspt_builder fspt_builder;
 
 /* ------------------------------------------------------------------------
@@ -213,7 +212,9 @@ int fspt_temporal_set_clamp(fspt_target *t, int on, float fast_history, float si
 int fspt_target_set_auto_exposure(fspt_target *t, int on, const fspt_exposure_params *p); /* p NULL = defaults; default off */ int fspt_exposure_reset(fspt_target *t); /* the next metering is a first one */
 int fspt_exposure_get(fspt_target *t, float *exposure, float *log2_mean, uint32_t *metered); /* blocking; joins a present */ /* Bloom (DESIGN 8.12; rule and defaults: fspt_tuning.h): every drawing entry first builds an HDR pyramid of the buffer it draws and mixes its glow in before the exposure. */ typedef struct fspt_bloom_params { float intensity, scatter; uint32_t levels; } fspt_bloom_params; int fspt_target_set_bloom(fspt_target *t, int on, const fspt_bloom_params *p); /* p NULL = defaults; default off */ int fspt_target_get_bloom(fspt_target *t, int *on, fspt_bloom_params *p);
 /* intersectScene (tracer.fs:366-404) as a stand-alone entry: n rays (origin xyz, dir xyz) -> closest hit t and triangle index (-1 = miss, t = 1e5), optionally loop-iteration and leaf-visit counts per ray.  Host pointers. */
-int fspt_intersect(fspt_scene *scene, const float *rays, uint32_t n, float *t_out, int32_t *index_out, uint32_t *steps_out, uint32_t *leaves_out);
+int fspt_intersect(fspt_scene *scene, const float *rays, uint32_t n, float *t_out, int32_t *index_out, uint32_t *steps_out, uint32_t *leaves_out); /* ID mattes (DESIGN 8.25): per pixel, which objects and which materials cover it and by how much, as Cryptomatte stores it.  An id is a 32-bit name hash kept as the bits of a normal finite float: fspt_matte_hash = MurmurHash3_x86_32 (seed 0) of the bytes, then h ^= 1 << 23 when the exponent field (h >> 23) & 255 is 0 or 255. set_matte_ids: one id per triangle of the scene's current tri array (the index fspt_intersect reports, the order update_geometry takes), copied to the device; 0 = no matte (counts like a miss); any other id with exponent field 0 or 255: FSPT_E_INVALID naming the first such index, nothing changed; NULL drops the kind.  The table survives the update entries; a rebuild permutes it with the order it returns.  set_matte_manifest: opaque bytes (at most 2^20) kept on the host for the file header; NULL / 0 = none. fspt_mattes: `samples` (1..65535) camera rays per pixel of the whole target - the very rays fspt_features(cam, samples, seed) traces - each traced once; per kind with ids a table of FSPT_MATTE_RANKS slots: a hit's id raises its slot's count, else takes the lowest empty slot, else the sample is lost.  Ranks = slots by count descending, ties first seen first; rank r = (the id's bits as a float, (float)count / (float)samples), empty ranks (0, 0).  FSPT_E_STATE: no ids of any kind.  A flush point, joins a present, clears nothing.  read_mattes: W*H*12 floats (id0 c0 .. id5 c5), rows bottom-up; mattes_lost: the samples the last pass dropped; both blocking, FSPT_E_STATE before a pass or for a kind it did not compute. */ enum { FSPT_MATTE_OBJECT = 0, FSPT_MATTE_MATERIAL = 1 };
+#define FSPT_MATTE_RANKS 6
+uint32_t fspt_matte_hash(const char *name, size_t len); /* host only */ int fspt_scene_set_matte_ids(fspt_scene *s, int kind, const uint32_t *ids); int fspt_scene_set_matte_manifest(fspt_scene *s, int kind, const char *json, size_t len); int fspt_mattes(fspt_target *t, const fspt_camera_params *cam, uint32_t samples, uint64_t seed); int fspt_read_mattes(fspt_target *t, int kind, float *out); int fspt_mattes_lost(fspt_target *t, int kind, uint64_t *lost); /* Cryptomatte layers in an OpenEXR file (DESIGN 8.25): fspt_exr_* with two more layer bits, accepted by these entries and by fspt_draw_exr (which takes the target's matte buffers and the scene's manifests; a bit without a pass for that kind: FSPT_E_STATE) and refused by fspt_exr_bound / _encode / _encode_device as before.  Per kind present twelve FLOAT channels Crypto<Object|Material>0<0|1|2>.<R|G|B|A> = id(2j), cov(2j), id(2j+1), cov(2j+1) of level j, in the file's byte-sorted channel order (between B and G, material first), and directly behind `compression` the string attributes cryptomatte/<key>/conversion = uint32_to_float32, /hash = MurmurHash3_32, /manifest (when given), /name, <key> = the first seven hex digits of the layer name's hash.  ranks[k]: W*H*12 floats as fspt_read_mattes returns them (needed where the bit is set), manifest[k] / manifest_len[k]: at most 2^20 bytes, NULL / 0 = none; m NULL in the bound: no manifests. */ enum { FSPT_EXR_CRYPTO_OBJECT = 16, FSPT_EXR_CRYPTO_MATERIAL = 32 }; typedef struct fspt_exr_mattes { const float *ranks[2]; const char *manifest[2]; size_t manifest_len[2]; } fspt_exr_mattes; /* by FSPT_MATTE_* */ int fspt_exr_bound_mattes(uint32_t w, uint32_t h, const fspt_exr_params *p, const fspt_exr_mattes *m, size_t *bytes); /* host only */ int fspt_exr_encode_mattes(int device, const float *rgba, const float *features, const fspt_exr_mattes *m, uint32_t w, uint32_t h, int bottom_up, const fspt_exr_params *p, uint8_t *out, size_t cap, size_t *bytes_out); /* host pointers */ int fspt_exr_encode_mattes_device(int device, const float *rgba, const float *features, const fspt_exr_mattes *m, uint32_t w, uint32_t h, int bottom_up, const fspt_exr_params *p, uint8_t *out, size_t cap, size_t *bytes_out); /* rgba, features, ranks: device memory of `device`, 16-byte aligned; manifests and out: host */
 
 /* Work counters for the byte accounting of SURVEY 8d, summed since the last fspt_clear / fspt_counters_reset while
  * counting is enabled (slower kernel variants).  enable = 1 counts the REFERENCE's work (NEE shadow rays traced to
@@ -289,8 +290,7 @@ int fspt_builder_get(const fspt_builder *b, float *bvh, float *tri, float *mat, 
  * cap bins (4 uint32 each) and the real count to *n_bins. */
 int fspt_env_bins(const uint8_t *rgbe, uint32_t w, uint32_t h, uint32_t *bins, uint32_t cap, uint32_t *n_bins); /* The same bins, built on HIP device `device` from a summed-area table of the map (DESIGN 8.17): same contract, host pointers. */ int fspt_env_bins_gpu(const uint8_t *rgbe, uint32_t w, uint32_t h, int device, uint32_t *bins, uint32_t cap, uint32_t *n_bins); /* GPU sky (DESIGN 8.17; the model, defaults and ranges: fspt_tuning.h): single-scattering Rayleigh + Mie seen from the ground, as a w x h equirect map in envSample's mapping (row 0 = straight up), 1..65535 texels per side.  sun_dir: finite, non-zero, normalised by the library; below the horizon is night.  A value out of range: FSPT_E_INVALID, before a device is touched. */ typedef struct fspt_sky_params { float sun_dir[3]; float turbidity, sun_intensity, sun_radius, gain; float ground_albedo[3]; uint32_t view_samples, light_samples; } fspt_sky_params; /* rgbe_out: w*h*4 bytes (RGBE as the environment takes it); linear_out: w*h*3 floats, the radiance before the encode.  Either may be NULL.  Host pointers. */ int fspt_sky_generate(int device, const fspt_sky_params *p, uint32_t w, uint32_t h, uint8_t *rgbe_out, float *linear_out); /* fspt_scene_update_environment without the host's bins: _auto takes host RGBE, _device RGBE in the scene's device memory, and the bins are built on the GPU from the uploaded map; _sky generates the map there too, so that no texel crosses the bus. Afterwards the scene renders bit for bit like fspt_scene_create of the same bytes and fspt_env_bins of them.  Blocking; ordered against every target; an error leaves the scene as it was; accumulators and per-target state are not touched. */ int fspt_scene_update_environment_auto(fspt_scene *s, const uint8_t *env, uint32_t w, uint32_t h); int fspt_scene_update_environment_device(fspt_scene *s, const uint8_t *env, uint32_t w, uint32_t h); int fspt_scene_update_sky(fspt_scene *s, const fspt_sky_params *p, uint32_t w, uint32_t h);
 
-const char *fspt_last_error(void); int fspt_abi_version(void);
-int fspt_device_count(void); /* visible HIP devices (0 when none / no driver) */
+const char *fspt_last_error(void); int fspt_abi_version(void); int fspt_device_count(void); /* visible HIP devices (0 when none / no driver) */
 
 #ifdef __cplusplus
 }
